@@ -7,8 +7,8 @@ region, R/kernel.cu:676-691) and, for N > 1, the single RCCL gather of the row s
 Default workload = config C2 (BASELINE.json configs[1]): Book-1 final random-spheres scene, list world
 ("no BVH"), 1200x800, 500 spp, depth 50, fp64 like the reference.
 
-Multi-GPU (rows dealt to ranks in 8-row stripes, no data-path collective, one gather at frame end).  Both legs are
-measured in one run and reported in one line:
+Multi-GPU (rows dealt to ranks in 8-row stripes, no data-path collective, one gather at frame end).  The headline leg
+is always measured; with --full the other leg is measured in the same run and reported in the same line:
   weak    (the headline, "scaling": "weak") the frame keeps its view and width and gets N x the rows, so every rank
           renders one base frame's worth of pixels of the same distribution;
   strong  (the "strong" sub-record) the BASELINE frame itself is striped over the N ranks (what north_star configs 4-5 do),
@@ -22,9 +22,12 @@ measured in one run and reported in one line:
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
-Besides the contract's keys the JSON line carries `parity` (rows of the frame just timed against the CPU oracle at the
-full spp), `roofline` (fp64-VALU issue-slot bound, scalars only) and `cpu_baseline` (the oracle timed on the host cores,
-rank 0 at N = 1 only).
+A plain run sets up, warms up, times the K frames and prints the JSON line: only what the headline needs.  --full adds
+what takes runs of its own: `pipelined` (the same K frames with two in flight), the other scaling leg at N > 1, and at
+N = 1 `parity` (rows of the frame just timed against the CPU oracle at the full spp, and the other build on the same
+rows), `roofline` (fp64-VALU issue-slot bound, scalars only) and `cpu_baseline` (the oracle timed on the host cores).
+--dump-outputs DIR writes the frame of the last timed step to DIR/frame.npy (float64, H x W x 3), so that two builds
+can be compared output for output: the inputs (scene, seed, frame size, spp) depend on the arguments alone.
 """
 import argparse
 import glob
@@ -117,6 +120,24 @@ def parity_of(got, want):
         "ppm8_equal": float(np.mean(np.all(q(got) == q(want), axis=-1))),
         "max_abs_diff": float(diff.max()),
     }
+
+
+DUMP_LIMIT_BYTES = 64 * 10**6
+
+
+def dump_outputs(out_dir, frame):
+    """The frame the timed path delivered in its last step, as DIR/frame.npy (float64).  A frame larger than the limit (weak
+    scaling on many ranks) is written as a fixed, seeded sample of its rows and the indices of those rows."""
+    os.makedirs(out_dir, exist_ok=True)
+    frame = np.ascontiguousarray(frame, dtype=np.float64)
+    if frame.nbytes <= DUMP_LIMIT_BYTES:
+        np.save(os.path.join(out_dir, "frame.npy"), frame)
+        return
+    row_bytes = frame.nbytes // frame.shape[0]
+    n = max(1, (DUMP_LIMIT_BYTES - 8 * frame.shape[0]) // row_bytes)
+    rows = np.sort(np.random.default_rng(1984).choice(frame.shape[0], size=n, replace=False))
+    np.save(os.path.join(out_dir, "frame_rows.npy"), frame[rows])
+    np.save(os.path.join(out_dir, "frame_row_index.npy"), rows.astype(np.float64))
 
 
 def committed_pmc(workload, spp, variant):
@@ -308,13 +329,13 @@ def main():
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
                     help="N GPUs: which leg is the headline (the other one is reported as a sub-record): weak = N x the rows of the "
                          "base frame (default), strong = the base frame striped over the ranks")
-    ap.add_argument("--one-leg", action="store_true", help="N GPUs: measure the headline leg only")
+    ap.add_argument("--one-leg", action="store_true", help="with --full, N GPUs: measure the headline leg only")
     ap.add_argument("--emulate-ranks", type=int, default=0,
                     help="one GPU: after the headline, render rank 0..N-1 of an N-way stripe split of the frame one after "
                          "another and report max_r T_r vs T_1/N as \"emulated_scaling\"")
     ap.add_argument("--emulate-ppw", default="", help="with --emulate-ranks: comma-separated pixels_per_wave values to repeat the "
                                                      "emulation with (tuning; the record of record uses the library's own choice)")
-    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the oracle leg (no cpu_baseline, no parity)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the oracle leg (no cpu_baseline, no parity)")
     ap.add_argument("--oracle-budget", type=float, default=14.0, help="seconds of oracle work for the parity / cpu_baseline band")
     ap.add_argument("--max-depth", type=int, default=50, help="diagnostics only (the headline uses the reference's 50)")
     ap.add_argument("--coop-threshold", type=int, default=0, help="tuning knob (0 = library default)")
@@ -324,7 +345,14 @@ def main():
     ap.add_argument("--pixels-per-wave", type=int, default=0, help="rt_render_params.pixels_per_wave (0 = the library's choice)")
     ap.add_argument("--pipeline", type=int, default=None,
                     help="after the headline (one frame after another) also time the same K frames with this many in "
-                         "flight on per-film streams and report it as \"pipelined\" (1 GPU only; 1 = skip)")
+                         "flight on per-film streams and report it as \"pipelined\" (1 GPU only; 1 = skip; default 1, "
+                         "with --full 2, C5: 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: pipelined frames, the other scaling leg "
+                         "(N GPUs), parity against the CPU oracle, the CPU baseline and the roofline (1 GPU)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the frame of the last timed step to DIR/frame.npy (float64; above 64 MB a fixed sample of "
+                         "its rows, DIR/frame_rows.npy + DIR/frame_row_index.npy)")
     ap.add_argument("--overdue", type=int, default=0, help="tuning knob: rays/sample budget before a pixel goes cooperative")
     ap.add_argument("--rendezvous-only", action="store_true",
                     help="start the ranks, form the process group over gloo on the CPU, reduce one number, print it and exit: checks "
@@ -359,7 +387,9 @@ def main():
     if args.warmup is None:
         args.warmup = 0 if long_frames else 1
     if args.pipeline is None:
-        args.pipeline = 1 if long_frames else 2
+        args.pipeline = 1 if (long_frames or not args.full) else 2
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be at least 1 and --warmup at least 0")
 
     import torch
     import raytracinginoneweekendincuda_amd as rt
@@ -417,8 +447,10 @@ def main():
         return out
 
     head = leg(args.scaling)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, head["frame"])
     other = None
-    if world > 1 and not args.one_leg:
+    if world > 1 and args.full and not args.one_leg:
         other = leg("strong" if args.scaling == "weak" else "weak")
     H = head["height"]
     film = films[H]
@@ -527,7 +559,7 @@ def main():
                 pr, _ = emulate(args.emulate_ranks, pixels_per_wave=v)
                 out.setdefault("emulated_scaling_by_pixels_per_wave", {})[str(v)] = {
                     "per_rank_ms": pr, "max_rank_ms": max(pr), "speedup": t1_ms / max(pr), "efficiency": t1_ms / max(pr) / args.emulate_ranks}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             base, stats, want, rows = oracle_band(wl, spp, args.max_depth, earth, args.oracle_budget)
             out["cpu_baseline"] = base
             # ---- parity: the rows of the frame just timed against the oracle at the full spp ----

@@ -1,6 +1,6 @@
 """VGPRs / scratch / spills of every render_kernel instantiation in the built library (llvm-readelf on the code objects)."""
-import re, subprocess, sys
-so = sys.argv[1] if len(sys.argv) > 1 else '/root/repo/raytracinginoneweekendincuda_amd/librtow_hip.so'
+import os, re, subprocess, sys
+so = sys.argv[1] if len(sys.argv) > 1 else os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', 'raytracinginoneweekendincuda_amd', 'librtow_hip.so')
 data = open(so, 'rb').read()
 idx = [m.start() for m in re.finditer(b'\x7fELF', data)]
 rows = []

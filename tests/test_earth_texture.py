@@ -14,6 +14,7 @@ import raytracinginoneweekendincuda_amd as rt
 from conftest import ROOT
 
 GOLD = os.path.join(ROOT, "tests", "golden", "earthmap_stb.npz")
+JPG = os.path.join(ROOT, "tests", "golden", "earthmap.jpg")   # the reference's texture file, as it ships
 
 
 def test_rtwimage_bytes_reproduces_stb_ldr_to_hdr_and_float_to_byte():
@@ -37,16 +38,15 @@ def test_golden_image_shape_and_documented_decoder_gap():
     assert int(g["pillow_vs_stb_max_abs"]) <= 3 and float(g["pillow_vs_stb_frac_bytes_differing"]) < 0.01
 
 
-@pytest.mark.skipif(not (os.path.exists("/root/reference/earthmap.jpg") and
-                         os.path.exists(os.path.join(ROOT, "oracle", "_ref", "libstb_ref.so"))),
-                    reason="needs the reference checkout and oracle/_ref (build container only)")
+@pytest.mark.skipif(not os.path.exists(os.path.join(ROOT, "oracle", "_ref", "libstb_ref.so")),
+                    reason="needs the reference's stb_image build in oracle/_ref (made by build() where the reference checkout is present)")
 def test_fixture_is_what_the_reference_stb_build_decodes_today():
     L = C.CDLL(os.path.join(ROOT, "oracle", "_ref", "libstb_ref.so"))
     L.stbi_load.restype = C.POINTER(C.c_ubyte)
     L.stbi_load.argtypes = [C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int]
     L.stbi_image_free.argtypes = [C.c_void_p]
     w, h, ch = C.c_int(), C.c_int(), C.c_int()
-    p = L.stbi_load(b"/root/reference/earthmap.jpg", C.byref(w), C.byref(h), C.byref(ch), 3)
+    p = L.stbi_load(JPG.encode(), C.byref(w), C.byref(h), C.byref(ch), 3)
     assert p
     srgb = np.ctypeslib.as_array(p, shape=(h.value, w.value, 3)).copy()
     L.stbi_image_free(p)

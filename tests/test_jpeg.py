@@ -1,7 +1,7 @@
 """Image ingest: csrc/jpeg_decode.cpp restates what the reference's stb_image does to a sequential Huffman JPEG;
 rt_rtwimage_load is RtwImage::Load (R/RtwImage.h:51-87).  Pinned by the reference's own decoder: tests/golden/jpeg_cases.npz
 holds JPEG files made with Pillow (tests/golden/make_jpeg_golden.py) and the pixels R/StbImageImpl.cpp decodes from them;
-where the reference checkout is present, its earthmap.jpg itself must come out as tests/golden/earthmap_stb.npz, which the
+the reference's earthmap.jpg itself (tests/golden/earthmap.jpg) must come out as tests/golden/earthmap_stb.npz, which the
 reference's stb build produced.  No GPU needed."""
 import os
 
@@ -27,9 +27,8 @@ def test_cases_cover_the_sampling_layouts():
     assert {"444", "422", "420", "grey", "420_restart", "low_quality"} <= set(NAMES)
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/earthmap.jpg"), reason="the reference's texture file is only in the build container")
 def test_rtwimage_load_reproduces_the_references_earth_texture():
-    got = rt.load_image("/root/reference/earthmap.jpg")
+    got = rt.load_image(os.path.join(ROOT, "tests", "golden", "earthmap.jpg"))
     with np.load(os.path.join(ROOT, "tests", "golden", "earthmap_stb.npz")) as g:
         want = g["bytes"]
     assert got is not None and got.shape == want.shape == (512, 1024, 3)

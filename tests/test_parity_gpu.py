@@ -512,7 +512,7 @@ BANDS = [("c2", 500, 0.999, 0.99, 0.99), ("c3", 500, 0.999, 0.99, 0.99), ("c4", 
 def test_band_of_the_benchmark_frame_at_benchmark_spp(oracle, earth, cfg, spp, min_strict, min_fast, min_exact):
     """Eight full-width rows through the middle of the benchmark frame at the benchmark's own spp (C5: 64 of its 5000),
     both builds, against the oracle.  This is where a contracted discriminant flipping a grazing hit would show: a flip
-    moves a pixel by ~1/spp of a colour.  (bench.py reports the same comparison for the frame it times: `parity`.)"""
+    moves a pixel by ~1/spp of a colour.  (bench.py --full reports the same comparison for the frame it times: `parity`.)"""
     scene_id, world, w, h = FULL[cfg]
     e = earth if scene_id == 9 else None
     stripe = (h // 2) // 8
