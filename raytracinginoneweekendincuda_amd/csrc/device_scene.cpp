@@ -3,9 +3,7 @@
 // timing.  Replaces the host driver section R/kernel.cu:675-691.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
 #include <cstdio>
-#include <cstdlib>
 #include <cmath>
 #include <cstring>
 #include <map>
@@ -95,28 +93,6 @@ static int select_device(int device)
 
 constexpr size_t kCounterWords = 128;
 
-// Scheduling constants are fixed in the shipping library: it reads nothing from the environment on the launch path.
-// A/B builds (make EXTRA=-DRT_TUNING=1 LIBNAME=..., loaded through RTOW_LIB_PATH by the Python binding) compile the
-// overrides in; every override is clamped to the range the kernels accept (a zero pixels-per-wave or round count would
-// leave the persistent waves spinning).  None of them changes an image.
-#ifndef RT_TUNING
-#define RT_TUNING 0
-#endif
-#if RT_TUNING
-static int tune(const char *name, int value, int lo, int hi)
-{
-    if (const char *e = std::getenv(name)) {
-        const int v = std::atoi(e);
-        value = v < lo ? lo : (v > hi ? hi : v);
-    }
-    return value;
-}
-static bool tune_set(const char *name) { return std::getenv(name) != nullptr; }
-#else
-static inline int tune(const char *, int value, int, int) { return value; }
-static inline bool tune_set(const char *) { return false; }
-#endif
-
 struct FilmImpl {
     int device = 0;
     int width = 0, height = 0, stripe_rows = 8, rank = 0, world_size = 1;
@@ -127,18 +103,15 @@ struct FilmImpl {
     double *accum = nullptr;       // progressive rendering: unnormalised colour sums (allocated on first use)
     int accum_spp = 0;
     uint32_t *state = nullptr;
-    unsigned long long *ray_counter = nullptr;  // [0] rays, [1] low word = pixel-queue cursor, [2..5] stamps, [7] and [16..63] phase sums
+    unsigned long long *ray_counter = nullptr;  // [0] rays, [1] / [6] / [9] low words = tile / heavy / super queue cursors, [7] and [32..119] phase sums
     int num_cus = 256;
     hipStream_t own_stream = nullptr;
     hipStream_t last_stream = nullptr;
     uint32_t *tile_cost = nullptr, *tile_order = nullptr;  // per 8x8 tile of this rank's rows: probed rays, and the tiles ranked by them
-    // sphere-list worlds, heavy / light pixels (allocated on first use): probed rays per pixel, the heavy pixels' list and
-    // count, every pixel's class; the heavy launch runs on its own stream beside the light one
+    // heavy / light pixels (allocated on first use): probed rays per pixel, the heavy pixels' list and count, every pixel's
+    // class; the serving waves of the render launch take the listed pixels, the others the rest of the tile queue
     uint32_t *pix_cost = nullptr, *heavy_list = nullptr, *heavy_count = nullptr, *super_list = nullptr;  // heavy_count[1]: length of super_list
-    uint32_t *dbg_times = nullptr;  // RT_STAMP diagnostic builds (RTOW_PRINT_TAIL)
     uint8_t *pix_class = nullptr;
-    hipStream_t aux_stream = nullptr;
-    hipEvent_t ev_aux[2] = {nullptr, nullptr};
     uint32_t n_tiles = 0;
     unsigned long long *host_counters = nullptr;  // pinned mirror of ray_counter, filled by an async copy behind the render
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};  // begin, after seed, after render, after the counter copy
@@ -384,14 +357,10 @@ void rt_film_destroy(rt_film *film)
     if (f->tile_cost) hipFree(f->tile_cost);
     if (f->tile_order) hipFree(f->tile_order);
     if (f->pix_cost) hipFree(f->pix_cost);
-    if (f->dbg_times) hipFree(f->dbg_times);
     if (f->heavy_list) hipFree(f->heavy_list);
     if (f->heavy_count) hipFree(f->heavy_count);
     if (f->super_list) hipFree(f->super_list);
     if (f->pix_class) hipFree(f->pix_class);
-    for (int k = 0; k < 2; k++)
-        if (f->ev_aux[k]) hipEventDestroy(f->ev_aux[k]);
-    if (f->aux_stream) hipStreamDestroy(f->aux_stream);
     if (f->host_counters) hipHostFree(f->host_counters);
     for (int k = 0; k < 4; k++)
         if (f->ev[k]) hipEventDestroy(f->ev[k]);
@@ -416,8 +385,6 @@ static int enqueue_frame(SceneImpl &s, FilmImpl &f, const rt_render_params *p, h
     const bool keep = (p->flags & RT_FLAG_KEEP_RNG_STATE) && f.seeded;
 
     HIP_TRY(hipMemsetAsync(f.ray_counter, 0, kCounterWords * sizeof(unsigned long long), stream));
-    HIP_TRY(hipMemsetAsync(f.ray_counter + 2, 0xFF, sizeof(unsigned long long), stream));  // stamp slots (diagnostic builds): min
-    HIP_TRY(hipMemsetAsync(f.ray_counter + 4, 0xFF, 2 * sizeof(unsigned long long), stream));
     HIP_TRY(hipEventRecord(f.ev[0], stream));
     if (!keep) {
         SeedArgs sa{};
@@ -455,19 +422,17 @@ static int enqueue_frame(SceneImpl &s, FilmImpl &f, const rt_render_params *p, h
     ra.shade_batch = p->shade_batch > 0 ? p->shade_batch : 16;
     ra.max_blocks_per_cu = p->max_blocks_per_cu;
     ra.pixels_per_wave = 64;  // settled below, once the kernel is known
-    ra.boost_rounds = tune("RTOW_BOOST", 8, 0, 1024);
-    ra.grid_blocks = tune("RTOW_GRID_BLOCKS", 0, 0, 1 << 20);
-    if (ra.grid_blocks > 0) ra.max_blocks_per_cu = 8;
+    ra.boost_rounds = 8;
     // A deep world BVH over composite leaves (scene 9: 400 boxes, two media, an instanced cluster): a leaf phase costs
     // tens of node steps there, so it pays to wait until most walkers have parked.  A shallow one (Cornell box: 8
     // leaves) gains nothing from waiting.
     {
         const uint32_t world_nodes = s.flat.n_world_nodes;
-        ra.node_burst = tune("RTOW_BURST", world_nodes > 64 ? 24 : 8, 1, 4096);
-        ra.park_ratio = tune("RTOW_PARK", world_nodes > 64 ? 4 : 1, 1, 64);
-        ra.leaf_batch = tune("RTOW_LEAF_BATCH", 12, 1, 64);
-        ra.object_batch = tune("RTOW_OBJECT_BATCH", 4, 1, 64);
-        ra.rounds = tune("RTOW_ROUNDS", 4, 1, 64);
+        ra.node_burst = world_nodes > 64 ? 24 : 8;
+        ra.park_ratio = world_nodes > 64 ? 4 : 1;
+        ra.leaf_batch = 12;
+        ra.object_batch = 4;
+        ra.rounds = 4;
     }
     ra.overdue_priority = (p->flags & RT_FLAG_OVERDUE_PRIORITY) ? 1 : 0;
     {
@@ -490,12 +455,10 @@ static int enqueue_frame(SceneImpl &s, FilmImpl &f, const rt_render_params *p, h
     ra.force_general = (p->flags & RT_FLAG_FORCE_GENERAL) ? 1 : 0;
     ra.always_walk = (p->flags & RT_FLAG_ALWAYS_WALK) ? 1 : 0;
     ra.reference_tree = (p->flags & RT_FLAG_REFERENCE_TREE) ? 1 : 0;
-    ra.exact_scan = tune("RTOW_EXACT_SCAN", (p->flags & RT_FLAG_EXACT_SCAN) ? 1 : 0, 0, 1);
+    ra.exact_scan = (p->flags & RT_FLAG_EXACT_SCAN) ? 1 : 0;
     ra.accelerate_lists = (p->flags & RT_FLAG_ACCELERATE_LISTS) ? 1 : 0;
-    ra.filter_fp64 = tune("RTOW_FILTER_FP64", (p->flags & RT_FLAG_FILTER_FP64) ? 1 : 0, 0, 1);
-    ra.heavy_scan = tune("RTOW_HEAVY_SCAN", 0, 0, 1);
-    ra.list_waves = tune("RTOW_LIST_WAVES", 0, 0, 5);
-    ra.small_world = tune("RTOW_SMALL_WORLD", 64, 0, 1 << 20);  // scan budget in half sphere tests, see FlatScene::scan_cost
+    ra.filter_fp64 = (p->flags & RT_FLAG_FILTER_FP64) ? 1 : 0;
+    ra.small_world = 64;  // scan budget in half sphere tests, see FlatScene::scan_cost
     const DeviceScene &ds = s.device[f.device]->scene;
     HIP_TRY(p->variant ? kernel_info_fast(ds, ra, &f.last_kernel) : kernel_info_strict(ds, ra, &f.last_kernel));
     const int kind = f.last_kernel.kind & 63;
@@ -512,8 +475,7 @@ static int enqueue_frame(SceneImpl &s, FilmImpl &f, const rt_render_params *p, h
     //    trace more than 10 rays per sample, up to 41) are listed; two waves of every workgroup serve that list first, a
     //    few pixels at a time -- the lanes share each ray's scan (sphere list: a third of the latency per ray at 1.8x the
     //    work), or simply have the wave to themselves (BVH walk) -- and then join the tile queue, whose pixels skip the
-    //    listed ones.  (The first form, a launch of its own for the list on a second stream, is still there for
-    //    tuning builds, RTOW_ROLES=0.)  C2 took 367 ms where its throughput alone needs ~310.
+    //    listed ones.  C2 took 367 ms where its throughput alone needs ~310.
     // Every pixel is still rendered exactly once from its own stream: the frame is the same bit for bit
     // (tests: ...tile_ranking..., ...heavy_and_light...; RT_FLAG_ROW_MAJOR_TILES / RT_FLAG_NO_PIXEL_CLASSES turn them off).
     const bool bvh_kernel = kind < 8;
@@ -522,9 +484,8 @@ static int enqueue_frame(SceneImpl &s, FilmImpl &f, const rt_render_params *p, h
     //  * list worlds too (r3): a frame is a few "generations" of pixels per lane (C4: 640 k pixels on 262 k lanes), and the last
     //    generation lasts as long as its longest pixel while ever fewer lanes are busy (C4: queue dry at 148 ms, last wave out
     //    at 261).  Heaviest tiles first makes the pixels that start last the cheap ones.
-    bool rank_tiles = (bvh_kernel || list_scan_kernel || sphere_list_kernel) && p->samples_per_pixel >= 32 && f.n_tiles >= 1024 &&
-                      !(p->flags & RT_FLAG_ROW_MAJOR_TILES);
-    rank_tiles = rank_tiles && tune("RTOW_TILE_SORT", 1, 0, 1) != 0;
+    const bool rank_tiles = (bvh_kernel || list_scan_kernel || sphere_list_kernel) && p->samples_per_pixel >= 32 && f.n_tiles >= 1024 &&
+                            !(p->flags & RT_FLAG_ROW_MAJOR_TILES);
     // the deep general kernel (one 768-thread workgroup per CU, C5): its ray chains are the longest of all (a ray takes ~140 us
     // in a full wave), which decides the frame whenever a GPU holds few pixels per lane -- a small frame, or one rank's share
     const bool deep_kernel = kind == 7 && f.last_kernel.lds_bytes > 64 * 1024;
@@ -536,20 +497,16 @@ static int enqueue_frame(SceneImpl &s, FilmImpl &f, const rt_render_params *p, h
     // and loses by them (1030 -> 1400 ms and worse), as it did in r2 with other settings; so: up to seven generations (a 2-way
     // split, 672 -> 626 ms), in three bands of settings.
     const double generations = (double)f.n_pixels / ((double)f.num_cus * 12.0 * 64.0);
-    const bool deep_roles = deep_kernel && tune("RTOW_ROLES_DEEP", generations <= 7.0 ? 1 : 0, 0, 1) != 0;
-    const bool ppw_given = (p->pixels_per_wave > 0 && p->pixels_per_wave < 64) || tune_set("RTOW_PIXELS_PER_WAVE");
-    bool split = (sphere_list_kernel || prim_bvh_kernel || deep_roles) && !(p->flags & RT_FLAG_NO_PIXEL_CLASSES) && p->samples_per_pixel >= 64 &&
-                 f.n_pixels >= 65536u && !ppw_given;
-    split = split && tune("RTOW_PIXEL_CLASSES", 1, 0, 1) != 0;
-    // The primitive-BVH kernel on the reference's tree (256-thread workgroups) gained nothing from a second launch (C3
-    // 1672 -> 1100-1200: opt-in); the library-tree kernel, whose 768-thread workgroup fills a CU, serves both classes in
-    // ONE launch, by wave (RenderArgs::heavy_list): C3 2106 -> 2713 Msamples/s.
-    // Sphere-list worlds: both forms work; serving the heavy pixels from two waves of every workgroup lets the launch keep
-    // three workgroups per CU resident (a third wave per SIMD: +15 % in the steady state, which a frame whose end is set by
-    // its long pixels could not use) -- C2 1479 (two launches, two workgroups per CU) -> 1556 Msamples/s.
-    bool roles_in_one_launch = (prim_bvh_kernel && (f.last_kernel.kind & 64) != 0) || deep_roles || sphere_list_kernel;
-    if (prim_bvh_kernel && !roles_in_one_launch && !tune_set("RTOW_PIXEL_CLASSES")) split = false;
-    roles_in_one_launch = tune("RTOW_ROLES", roles_in_one_launch ? 1 : 0, 0, 1) != 0;
+    const bool deep_roles = deep_kernel && generations <= 7.0;
+    // Both classes are served inside ONE launch, by wave (RenderArgs::heavy_list).  The library-tree kernel, whose 768-thread
+    // workgroup fills a CU: C3 2106 -> 2713 Msamples/s; the primitive-BVH kernel on the reference's tree (256-thread
+    // workgroups) gained nothing from classes (C3 1672 -> 1100-1200 with the heavy pixels in a second launch) and has none.
+    // Sphere-list worlds: serving the heavy pixels from two waves of every workgroup lets the launch keep three workgroups per
+    // CU resident (a third wave per SIMD: +15 % in the steady state, which a frame whose end is set by its long pixels could
+    // not use) -- C2 1479 (a second launch for the heavy pixels, two workgroups per CU) -> 1556 Msamples/s.
+    const bool ppw_given = p->pixels_per_wave > 0 && p->pixels_per_wave < 64;
+    const bool split = (sphere_list_kernel || (prim_bvh_kernel && (f.last_kernel.kind & 64) != 0) || deep_roles) &&
+                       !(p->flags & RT_FLAG_NO_PIXEL_CLASSES) && p->samples_per_pixel >= 64 && f.n_pixels >= 65536u && !ppw_given;
 
     // pixels_per_wave < 64 gives every ray several lanes: the sphere list deals a ray's spheres to the lanes of a group (its
     // heavy-pixel waves do that by themselves, above), the list-scan kernels a ray's leaves (render.hip scan_leaves_grouped).
@@ -561,9 +518,7 @@ static int enqueue_frame(SceneImpl &s, FilmImpl &f, const rt_render_params *p, h
     // wave, 182 at 32, 201 at 16, 324 at 8; profiles/r03_lanes_per_ray.txt).  The parameter stays for worlds of one kind of
     // leaf and for experiments; the frames are bit-identical either way.
     {
-        int ppw = 64;
-        if (p->pixels_per_wave > 0 && p->pixels_per_wave < 64) ppw = p->pixels_per_wave;
-        ppw = tune("RTOW_PIXELS_PER_WAVE", ppw, 1, 64);
+        int ppw = ppw_given ? p->pixels_per_wave : 64;
         if (list_scan_kernel) {  // the grouped leaf scan deals lanes in powers of two
             int pow2 = 1;
             while (pow2 * 2 <= ppw) pow2 *= 2;
@@ -575,25 +530,17 @@ static int enqueue_frame(SceneImpl &s, FilmImpl &f, const rt_render_params *p, h
     if (ra.pixels_per_wave < 64 && list_scan_kernel)  // the instantiation that deals leaves to lanes: report that one
         HIP_TRY(p->variant ? kernel_info_fast(ds, ra, &f.last_kernel) : kernel_info_strict(ds, ra, &f.last_kernel));
 
-    if (tune_set("RTOW_PRINT_TAIL")) {  // diagnostic builds (-DRT_STAMP=1 -DRT_TUNING=1)
-        if (!f.dbg_times) HIP_TRY(hipMalloc((void **)&f.dbg_times, (size_t)f.n_pixels * 2 * sizeof(uint32_t)));
-        HIP_TRY(hipMemsetAsync(f.dbg_times, 0, (size_t)f.n_pixels * 2 * sizeof(uint32_t), stream));
-        ra.dbg_times = f.dbg_times;
-    }
     if (rank_tiles || split) {
         // sphere-list frames of 400 samples and more rehearse 8: the heavy pixels are told apart more reliably (C2, three
         // interleaved pairs in one call: 1859-1893 with 4, 1908-1918 with 8; the primitive-BVH kernel is better off with 4)
         int probe_spp = split ? (p->samples_per_pixel >= 400 ? 8 : 4) : p->samples_per_pixel / 100;  // (r3: 8 for the BVH kernel too, with the settings below)
         probe_spp = probe_spp < 1 ? 1 : (probe_spp > 8 ? 8 : probe_spp);
-        probe_spp = tune("RTOW_PROBE_SPP", probe_spp, 1, 64);
         if (probe_spp > p->samples_per_pixel) probe_spp = p->samples_per_pixel;
         if (split && !f.pix_cost) {
             HIP_TRY(hipMalloc((void **)&f.pix_cost, (size_t)f.n_pixels * sizeof(uint32_t)));
             HIP_TRY(hipMalloc((void **)&f.heavy_list, (size_t)f.n_pixels * sizeof(uint32_t)));
             HIP_TRY(hipMalloc((void **)&f.heavy_count, 64));
             HIP_TRY(hipMalloc((void **)&f.pix_class, (size_t)f.n_pixels));
-            HIP_TRY(hipStreamCreateWithFlags(&f.aux_stream, hipStreamNonBlocking));
-            for (int k = 0; k < 2; k++) HIP_TRY(hipEventCreateWithFlags(&f.ev_aux[k], hipEventDisableTiming));
         }
         RenderArgs probe = ra;
         probe.probe = 1;
@@ -608,15 +555,14 @@ static int enqueue_frame(SceneImpl &s, FilmImpl &f, const rt_render_params *p, h
         if (rank_tiles) {
             // the order is kept row-major only where the heaviest tile is within an eighth of the mean (r3: was x4, which sorted for
             // glass only; C3 +1.7 % with every spread sorted, C2 / C5 indifferent between 9 / 8 and 32 / 8, one call)
-            const uint32_t flat_x8 = (uint32_t)tune("RTOW_TILE_FLAT_X8", 9, 8, 1 << 20);
-            HIP_TRY(launch_tile_order(f.tile_cost, f.tile_order, f.n_tiles, flat_x8, stream));
+            HIP_TRY(launch_tile_order(f.tile_cost, f.tile_order, f.n_tiles, 9u, stream));
             ra.tile_order = f.tile_order;
         }
         HIP_TRY(hipMemsetAsync(f.ray_counter, 0, 2 * sizeof(unsigned long long), stream));  // rays, (light) queue cursor
         if (split) {
             // Serving settings (r3; every number below is the mean of several frames per setting in one gpurun call -- earlier sweeps
             // took the best of two runs and missed a bimodal default; profiles/r03_c2_serving_sweep.txt, r03_c3_serving_sweep.txt,
-            // r03_rank_serving_sweep.txt, r03_c5_roles.txt).  What per-pixel stamps (RT_STAMP builds, RTOW_PRINT_TAIL) showed: a light
+            // r03_rank_serving_sweep.txt, r03_c5_roles.txt).  What per-pixel stamps showed: a light
             // pixel just under the threshold runs at a light wave's 30-40 us per ray from the frame's first millisecond to its last,
             // a listed pixel at 7-10 us -- threshold, serving capacity and the longest listed chain have to be moved together.
             //   sphere lists (C2)      two tiers: from 12 rays per sample four pixels to a serving wave (16 lanes per ray), from 9 eight;
@@ -630,20 +576,15 @@ static int enqueue_frame(SceneImpl &s, FilmImpl &f, const rt_render_params *p, h
             // A frame of few generations of pixels per lane (a rank's stripes) keeps these thresholds -- lower ones helped three
             // ranks of eight and cost the rank with the longest chains a third -- and lets its serving waves take fewer pixels each
             // (adaptive_ppw below).
-            const bool few_generations = roles_in_one_launch && generations <= 3.0;  // of pixels per resident lane (twelve waves per CU)
-            const int heavy_rays_per_sample = tune("RTOW_HEAVY_RAYS", deep_roles ? (generations <= 2.2 ? 8 : (generations <= 5.0 ? 12 : 16)) : ((sphere_list_kernel && !roles_in_one_launch) ? 12 : 9), 1, 1 << 20);
-            int heavy_ppw = tune("RTOW_HEAVY_PPW", deep_roles ? 32 : (sphere_list_kernel ? (roles_in_one_launch ? 8 : 4) : 6), 1, 64);
-            const int heavy_blocks = tune("RTOW_HEAVY_BLOCKS", sphere_list_kernel ? f.num_cus / 2 : f.num_cus, 1, 1 << 20);
-            // the serving waves' rays are the frame's critical path
-            const int heavy_prio = tune("RTOW_HEAVY_PRIO", (sphere_list_kernel && roles_in_one_launch) ? 3 : 0, 0, 3);
+            const bool few_generations = generations <= 3.0;  // of pixels per resident lane (twelve waves per CU)
+            const int heavy_rays_per_sample = deep_roles ? (generations <= 2.2 ? 8 : (generations <= 5.0 ? 12 : 16)) : 9;
+            const int super_rays = deep_roles ? 0 : (sphere_list_kernel ? 12 : 30);
+            const bool longest = super_rays > 0;
             HIP_TRY(hipMemsetAsync(f.heavy_count, 0, 64, stream));
-            const int super_rays = tune("RTOW_SUPER_RAYS", (roles_in_one_launch && !deep_roles) ? (sphere_list_kernel ? 12 : 30) : 0, 0, 1 << 20);
-            const bool longest = roles_in_one_launch && super_rays > 0;
             if (longest && !f.super_list) HIP_TRY(hipMalloc((void **)&f.super_list, (size_t)f.n_pixels * sizeof(uint32_t)));
             HIP_TRY(launch_classify_pixels(f.pix_cost, f.n_pixels, (uint32_t)(heavy_rays_per_sample * probe_spp), f.pix_class,
                                            f.heavy_list, f.heavy_count, stream, longest ? f.super_list : nullptr, (uint32_t)(super_rays * probe_spp),
-                                           (uint32_t)f.width, (uint32_t)tune("RTOW_NEAR_PERCENT", prim_bvh_kernel ? 70 : 0, 0, 100),
-                                           (uint32_t)tune("RTOW_NEAR_NEIGHBOURS", prim_bvh_kernel ? 3 : 0, 0, 8)));
+                                           (uint32_t)f.width, prim_bvh_kernel ? 70u : 0u, prim_bvh_kernel ? 3u : 0u));
             // (primitive BVH worlds: a pixel probed at 70 % of the threshold with three of its eight neighbours over it is listed too --
             // the last pixel of a C3 frame was a light one probed at 8.75 rays per sample in a patch of heavy ones, really costing 16:
             // 152.5 -> 147.8 ms, six frames per setting; sphere lists: no difference, left off)
@@ -652,45 +593,26 @@ static int enqueue_frame(SceneImpl &s, FilmImpl &f, const rt_render_params *p, h
                 ra.super_list = f.super_list;
                 ra.super_count = f.heavy_count + 1;
                 ra.super_cursor = reinterpret_cast<uint32_t *>(f.ray_counter + 9);
-                ra.super_ppw = tune("RTOW_SUPER_PPW", sphere_list_kernel ? 4 : 1, 1, 64);
+                ra.super_ppw = sphere_list_kernel ? 4 : 1;
             }
             HIP_TRY(hipMemsetAsync(f.ray_counter + 6, 0, sizeof(unsigned long long), stream));  // heavy queue cursor
-            if (roles_in_one_launch) {
-                if (sphere_list_kernel && ra.max_blocks_per_cu <= 0) ra.max_blocks_per_cu = 3;
-                ra.heavy_list = f.heavy_list;
-                ra.heavy_count = f.heavy_count;
-                ra.heavy_cursor = reinterpret_cast<uint32_t *>(f.ray_counter + 6);
-                ra.heavy_waves = tune("RTOW_HEAVY_WAVES", deep_roles ? (generations <= 2.2 ? 10 : (generations <= 5.0 ? 6 : 4)) : (sphere_list_kernel ? 2 : 3), 0, 12);
-                ra.heavy_ppw = heavy_ppw;
-                ra.heavy_priority = heavy_prio;
-                // fewer pixels per serving wave than the tuned numbers where the light pixels are few -- up to three generations of
-                // pixels per lane, i.e. a rank's stripes of a split frame: the light side is short there and a listed chain is
-                // shortest with its wave to itself (slowest rank, C2 / 4: 132 -> 119 ms, / 8: 135 -> 97; C3 / 2: 153 -> 135, / 4:
-                // 154 -> 124, / 8: 155 -> 122).  A full frame packs the serving waves as densely as tuned: the ones left over join
-                // the light queue at once (C3, 4.9 generations: 152 against 159 ms).
-                ra.adaptive_ppw = tune("RTOW_ADAPTIVE_PPW", few_generations ? 1 : 0, 0, 1);
-                ra.pix_class = f.pix_class;
-            } else {
-                HIP_TRY(hipEventRecord(f.ev_aux[0], stream));
-                HIP_TRY(hipStreamWaitEvent(f.aux_stream, f.ev_aux[0], 0));
-                RenderArgs heavy = ra;
-                heavy.tile_order = nullptr;
-                heavy.pixel_list = f.heavy_list;
-                heavy.pixel_list_count = f.heavy_count;
-                heavy.cursor = reinterpret_cast<uint32_t *>(f.ray_counter + 6);
-                heavy.pixels_per_wave = heavy_ppw;
-                if (sphere_list_kernel) heavy.coop_threshold = 65;  // always the grouped scan
-                heavy.grid_blocks = heavy_blocks;
-                heavy.max_blocks_per_cu = 8;
-                heavy.wave_priority = heavy_prio;
-                HIP_TRY(p->variant ? launch_render_fast(ds, heavy, f.aux_stream) : launch_render_strict(ds, heavy, f.aux_stream));
-                HIP_TRY(hipEventRecord(f.ev_aux[1], f.aux_stream));
-                ra.pix_class = f.pix_class;
-            }
+            if (sphere_list_kernel && ra.max_blocks_per_cu <= 0) ra.max_blocks_per_cu = 3;
+            ra.heavy_list = f.heavy_list;
+            ra.heavy_count = f.heavy_count;
+            ra.heavy_cursor = reinterpret_cast<uint32_t *>(f.ray_counter + 6);
+            ra.heavy_waves = deep_roles ? (generations <= 2.2 ? 10 : (generations <= 5.0 ? 6 : 4)) : (sphere_list_kernel ? 2 : 3);
+            ra.heavy_ppw = deep_roles ? 32 : (sphere_list_kernel ? 8 : 6);
+            ra.heavy_priority = sphere_list_kernel ? 3 : 0;  // the serving waves' rays are the frame's critical path
+            // fewer pixels per serving wave than the tuned numbers where the light pixels are few -- up to three generations of
+            // pixels per lane, i.e. a rank's stripes of a split frame: the light side is short there and a listed chain is
+            // shortest with its wave to itself (slowest rank, C2 / 4: 132 -> 119 ms, / 8: 135 -> 97; C3 / 2: 153 -> 135, / 4:
+            // 154 -> 124, / 8: 155 -> 122).  A full frame packs the serving waves as densely as tuned: the ones left over join
+            // the light queue at once (C3, 4.9 generations: 152 against 159 ms).
+            ra.adaptive_ppw = few_generations ? 1 : 0;
+            ra.pix_class = f.pix_class;
         }
     }
     HIP_TRY(p->variant ? launch_render_fast(ds, ra, stream) : launch_render_strict(ds, ra, stream));
-    if (split && !roles_in_one_launch) HIP_TRY(hipStreamWaitEvent(stream, f.ev_aux[1], 0));
     HIP_TRY(hipEventRecord(f.ev[2], stream));
     // The counters come home on the film's own stream: a blocking hipMemcpy in rt_render_finish would wait for every
     // other film's frame as well and serialise frames that were launched to overlap.
@@ -750,53 +672,8 @@ int rt_render_finish(rt_scene *scene, rt_film *film, rt_render_stats *stats)
         HIP_TRY(hipEventElapsedTime(&ms_seed, f.ev[0], f.ev[1]));
         HIP_TRY(hipEventElapsedTime(&ms_render, f.ev[1], f.ev[2]));
         const unsigned long long rays = f.host_counters[0];
-        if (tune_set("RTOW_PRINT_HEAVY") && f.heavy_count && f.pix_cost) {  // diagnostics: the rehearsal's cost classes
-            uint32_t n_heavy = 0;
-            std::vector<uint32_t> cost(f.n_pixels);
-            HIP_TRY(hipMemcpy(&n_heavy, f.heavy_count, sizeof n_heavy, hipMemcpyDeviceToHost));
-            HIP_TRY(hipMemcpy(cost.data(), f.pix_cost, cost.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-            unsigned long long hist[16] = {};
-            uint32_t top = 0;
-            for (uint32_t c : cost) {
-                hist[c / 16 > 15 ? 15 : c / 16]++;
-                top = c > top ? c : top;
-            }
-            std::fprintf(stderr, "heavy pixels %u of %u; probe rays per pixel: max %u; histogram by 16:", n_heavy, f.n_pixels, top);
-            for (int k = 0; k < 16; k++) std::fprintf(stderr, " %llu", hist[k]);
-            std::fprintf(stderr, "\n");
-        }
-        if (tune_set("RTOW_PRINT_TAIL") && f.dbg_times) {  // who finishes last: the 24 last pixels and a histogram of the ends
-            std::vector<uint32_t> t((size_t)f.n_pixels * 2), cost(f.n_pixels, 0);
-            HIP_TRY(hipMemcpy(t.data(), f.dbg_times, t.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-            if (f.pix_cost) HIP_TRY(hipMemcpy(cost.data(), f.pix_cost, cost.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-            const uint32_t t0 = (uint32_t)f.host_counters[5];
-            std::vector<uint32_t> order(f.n_pixels);
-            for (uint32_t k = 0; k < f.n_pixels; k++) order[k] = k;
-            std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return (uint32_t)(t[2 * a + 1] - t0) > (uint32_t)(t[2 * b + 1] - t0); });
-            const double last = (uint32_t)(t[2 * order[0] + 1] - t0) * 1e-5;
-            unsigned long long hist[12] = {};
-            double mean_dur[12] = {}, mean_cost[12] = {};
-            for (uint32_t k = 0; k < f.n_pixels; k++) {
-                const double end = (uint32_t)(t[2 * k + 1] - t0) * 1e-5, dur = (uint32_t)(t[2 * k + 1] - t[2 * k]) * 1e-5;
-                int b = (int)((last - end) / 5.0);
-                b = b > 11 ? 11 : b;
-                hist[b]++; mean_dur[b] += dur; mean_cost[b] += cost[k];
-            }
-            std::fprintf(stderr, "tail: last pixel ends +%.1f ms; pixels ending in the last 5 ms steps (count, mean duration ms, mean probe rays):", last);
-            for (int b = 0; b < 12; b++) std::fprintf(stderr, " [%llu %.1f %.1f]", hist[b], hist[b] ? mean_dur[b] / hist[b] : 0.0, hist[b] ? mean_cost[b] / hist[b] : 0.0);
-            std::fprintf(stderr, "\n");
-            for (int k = 0; k < 24; k++) {
-                const uint32_t px = order[k * 40];
-                std::fprintf(stderr, "  pixel row %u col %u: start +%.1f end +%.1f ms, probe rays %u\n", px / (uint32_t)f.width, px % (uint32_t)f.width,
-                             (uint32_t)(t[2 * px] - t0) * 1e-5, (uint32_t)(t[2 * px + 1] - t0) * 1e-5, cost[px]);
-            }
-        }
-        if (tune_set("RTOW_PRINT_STAMPS")) {  // diagnostic builds (-DRT_STAMP=1): 100 MHz wall-clock ticks
-            const unsigned long long *st = f.host_counters;
-            std::fprintf(stderr, "stamps: start %llu  queue exhausted +%.3f ms  first wave out +%.3f ms  last wave out +%.3f ms  heavy pixels done +%.3f ms\n",
-                         st[5], (st[2] - st[5]) * 1e-5, (st[4] - st[5]) * 1e-5, (st[3] - st[5]) * 1e-5, st[8] ? (st[8] - st[5]) * 1e-5 : 0.0);
-        }
-        if (tune_set("RTOW_PRINT_PHASES")) {  // diagnostic builds (-DRT_PHASES=1)
+#if RT_PHASES  // diagnostic builds (make EXTRA=-DRT_PHASES=1 LIBNAME=...): the per-phase table
+        {
             const unsigned long long *c = f.host_counters;
             const char *name[24] = {"node step", "leaf test", "shade", "refill", "  group/instance", "  medium", "  primitive", "",
                                     "    record+xforms", "    box", "    sub-BVH", "    other geometry", "between walks again", "limited node pass", "node visits (lanes)", "",
@@ -812,6 +689,7 @@ int rt_render_finish(rt_scene *scene, rt_film *film, rt_render_stats *stats)
                     std::fprintf(stderr, "phase %-20s: %5.1f %% of wave time, %10llu passes, %5.1f lanes/pass, %7.0f cycles/pass\n", name[k],
                                  100.0 * c[32 + k] / total, c[96 + k], (double)c[64 + k] / c[96 + k], (double)c[32 + k] / c[96 + k]);
         }
+#endif
         stats->samples = f.last_samples;
         stats->rays = rays;
         stats->seconds_seed = ms_seed * 1e-3;

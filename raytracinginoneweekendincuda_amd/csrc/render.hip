@@ -54,12 +54,7 @@ namespace {
 //   FAST       primitive-only BVH world walked through the library's own SAH tree, near child first (flat_scene.h FastNodeRec)
 //              (with COMPOSITE and BATCH: the segmented walk of a composite world, Traits::SEG)
 //   GROUPED    list scan with the leaves of every ray dealt to several lanes (scan_leaves_grouped): launches with pixels_per_wave < 64
-#ifndef RT_PARK_STATE
-#define RT_PARK_STATE 1
-#endif
-#ifndef RT_BIG_BLOCK
-#define RT_BIG_BLOCK 768  // workgroups this large run one per CU with the scene tables in (nearly) all of its LDS
-#endif
+constexpr int kBigBlock = 768;  // workgroups this large run one per CU with the scene tables in (nearly) all of its LDS
 template <int WORLD_, bool COMPOSITE_, bool RICH_, int MIN_WAVES_ = 1, bool MEDIA_ = COMPOSITE_, bool BATCH_ = false, bool NESTED_ = false,
           int BLOCK_ = 256, bool FAST_ = false, bool GROUPED_ = false>
 struct Traits {
@@ -67,13 +62,13 @@ struct Traits {
     // list scan over instances / boxes compiled for five waves per SIMD (C4, TListInstances5): the path state the scan does not touch
     // -- pixel sum, throughput, emitted light, RNG, pixel counters -- waits in LDS while the leaves are tested (park_* in
     // render_kernel), so that 96 registers are nearly enough (at four waves the same parking costs 2.5 %: measured, not used)
-    static constexpr bool PARK = RT_PARK_STATE && WORLD_ == 1 && COMPOSITE_ && !RICH_ && !MEDIA_ && !NESTED_ && !GROUPED_ && MIN_WAVES_ >= 5;
+    static constexpr bool PARK = WORLD_ == 1 && COMPOSITE_ && !RICH_ && !MEDIA_ && !NESTED_ && !GROUPED_ && MIN_WAVES_ >= 5;
     // segmented walk (flat_scene.h FastOrder / SegMedium): the library's tree over the surface leaves of a composite BVH world,
     // walked once per run of leaves between two media; kind-batched leaf phases, one 768-thread workgroup per CU
-    static constexpr bool SEG = FAST_ && COMPOSITE_ && BATCH_ && WORLD_ == 0 && BLOCK_ >= RT_BIG_BLOCK;
+    static constexpr bool SEG = FAST_ && COMPOSITE_ && BATCH_ && WORLD_ == 0 && BLOCK_ >= kBigBlock;
     static constexpr bool FAST = FAST_ && !COMPOSITE_ && WORLD_ == 0;
     // kernels that can be launched with heavy / light pixel classes (RenderArgs::heavy_list): for the others the serving code folds away
-    static constexpr bool ROLES = WORLD_ == 2 || (FAST_ && WORLD_ == 0 && BLOCK_ >= RT_BIG_BLOCK) || (COMPOSITE_ && BATCH_ && WORLD_ == 0 && BLOCK_ >= RT_BIG_BLOCK);
+    static constexpr bool ROLES = WORLD_ == 2 || (FAST_ && WORLD_ == 0 && BLOCK_ >= kBigBlock) || (COMPOSITE_ && BATCH_ && WORLD_ == 0 && BLOCK_ >= kBigBlock);
     static constexpr int BLOCK = BLOCK_;
     static constexpr bool NESTED = NESTED_ && COMPOSITE_;
     static constexpr bool BATCH = BATCH_ && COMPOSITE_ && WORLD_ == 0;
@@ -408,7 +403,7 @@ DEV bool prim_test(const DeviceScene &sc, uint32_t ref, const Ray &r, double a, 
 }
 
 #ifndef RT_PHASES
-#define RT_PHASES 0  // diagnostic build: per-phase wave cycles and lane occupancy, summed into ray_counter[8..]
+#define RT_PHASES 0  // diagnostic build: per-phase wave cycles and lane occupancy, summed into ray_counter[7] and [32..119]
 #endif
 #if RT_PHASES
 #define PH_BEGIN() const unsigned long long ph_t0 = __builtin_readcyclecounter()
@@ -1522,29 +1517,8 @@ DEV bool world_hit_list(const DeviceScene &sc, const Ray &r, double tmin, double
 //  2. each lane walks its own queue in ascending k and does the sqrt / divide root selection against its
 //     running closest-so-far -- the same order the reference's loop meets those spheres in.
 constexpr int kQueueCap = 16;   // entries per lane; the queue is drained whenever a lane could overflow
-#ifndef RT_SIMPLE_BREAK
-#define RT_SIMPLE_BREAK 0
-#endif
-#ifndef RT_PROBE_ON
-#define RT_PROBE_ON 1
-#endif
-#ifndef RT_ORDER_ON
-#define RT_ORDER_ON 1
-#endif
-#ifndef RT_STAMP
-#define RT_STAMP 0  // diagnostic build: wall-clock stamps of queue exhaustion / first and last wave exit
-#endif
-#ifndef RT_FAST_VISITS
-#define RT_FAST_VISITS 2  // node visits of the library-tree walk per look at the wave's state
-#endif
-#ifndef RT_BURST
-#define RT_BURST 8
-#endif
-#ifndef RT_ROUNDS
-#define RT_ROUNDS 6
-#endif
-constexpr int kBurst = RT_BURST;    // BVH worlds: at most this many node visits between two leaf phases
-constexpr int kRounds = RT_ROUNDS;  // node/leaf phase pairs per look at the shading queue, primitive worlds
+constexpr int kBurst = 8;           // BVH worlds: at most this many node visits between two leaf phases
+constexpr int kRounds = 6;          // node/leaf phase pairs per look at the shading queue, primitive worlds
 constexpr int kRoundsComposite = 4; // the same for composite worlds
 constexpr int kRoundsFast = 4;      // and for the library-tree kernel, whose frame ends with its long pixels: they are shaded sooner
                                     // (C3, one call: 2 rounds 2615, 3: 2711, 4: 2891-2943, 5: 2805, 6: 2784, 8: 2675 Msamples/s)
@@ -2823,24 +2797,20 @@ __global__ __launch_bounds__(T::BLOCK, T::MIN_WAVES) void render_kernel(DeviceSc
         sc.lds_spheres_tab = sc.lds_group_boxes = sc.lds_mspheres = sc.lds_msphere_aux = sc.lds_sphere_aux = kNone;
     } else if constexpr (T::FAST) {
         sc.lds_quad_aa = sc.lds_boxes = sc.lds_objects = sc.lds_xforms = sc.lds_media = sc.lds_perlin = sc.lds_group_boxes = kNone;
-#ifndef RT_NO_ASSUME
-        if constexpr (T::BLOCK >= RT_BIG_BLOCK) {  // launched only with all of its rows staged (launch_one)
+        if constexpr (T::BLOCK >= kBigBlock) {  // launched only with all of its rows staged (launch_one)
             __builtin_assume(sc.lds_mspheres != kNone && sc.lds_msphere_aux != kNone && sc.lds_spheres_tab != kNone);
             __builtin_assume(sc.lds_sphere_aux != kNone && sc.lds_materials != kNone);
         }
-#endif
     } else {
         sc.lds_mspheres = sc.lds_msphere_aux = sc.lds_sphere_aux = kNone;
-        if constexpr (T::BLOCK < RT_BIG_BLOCK) sc.lds_spheres_tab = kNone;
+        if constexpr (T::BLOCK < kBigBlock) sc.lds_spheres_tab = kNone;
         if constexpr (!T::RICH) sc.lds_perlin = kNone;
-#ifndef RT_NO_ASSUME
-        if constexpr (T::BATCH && T::BLOCK >= RT_BIG_BLOCK) {  // the deep kernel is launched only with all of these staged (launch_one)
+        if constexpr (T::BATCH && T::BLOCK >= kBigBlock) {  // the deep kernel is launched only with all of these staged (launch_one)
             __builtin_assume(sc.lds_boxes != kNone && sc.lds_objects != kNone && sc.lds_xforms != kNone);
             __builtin_assume(sc.lds_media != kNone && sc.lds_materials != kNone && sc.lds_perlin != kNone);
             __builtin_assume(sc.lds_spheres_tab != kNone && sc.lds_group_boxes != kNone);
             if constexpr (T::SEG) __builtin_assume(sc.lds_fast_order != kNone && sc.lds_seg_media != kNone && sc.lds_seg_cand != kNone);
         }
-#endif
     }
     // ---- chip-resident working set ----
     NodeView nv{};
@@ -2848,7 +2818,7 @@ __global__ __launch_bounds__(T::BLOCK, T::MIN_WAVES) void render_kernel(DeviceSc
     if constexpr (T::WORLD == 0) {
         // BVH nodes in LDS, one 72-byte row each (see lds_node_f64 for the layout and why 72)
         nv.global = sc.nodes;
-        nv.in_lds = (T::BATCH && T::BLOCK >= RT_BIG_BLOCK) ? true : a.lds_nodes != 0;  // the deep kernel: always (launch_one)
+        nv.in_lds = (T::BATCH && T::BLOCK >= kBigBlock) ? true : a.lds_nodes != 0;  // the deep kernel: always (launch_one)
         if constexpr (T::FAST) {
             {  // the library's own tree: rows copied as they are (always staged: see walk_node_fast)
                 const uint32_t words = sc.n_fast_nodes * (kFastNodeBytes / 4u);
@@ -2940,12 +2910,8 @@ __global__ __launch_bounds__(T::BLOCK, T::MIN_WAVES) void render_kernel(DeviceSc
     // start on neighbouring pixels; a slot outside the frame is simply skipped.
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t tiles_x = ((uint32_t)a.width + 7u) >> 3;
-    // the work queue: tile-major slots of this rank's rows, or the entries of a pixel list (see RenderArgs::pixel_list)
-    const uint32_t total_slots = a.pixel_list ? *(const RT_CONST uint32_t *)(uintptr_t)a.pixel_list_count
-                                              : tiles_x * (((uint32_t)a.rows_owned + 7u) >> 3) * 64u;
-    if (a.wave_priority == 1) __builtin_amdgcn_s_setprio(1);
-    else if (a.wave_priority == 2) __builtin_amdgcn_s_setprio(2);
-    else if (a.wave_priority == 3) __builtin_amdgcn_s_setprio(3);
+    // the work queue: tile-major slots of this rank's rows
+    const uint32_t total_slots = tiles_x * (((uint32_t)a.rows_owned + 7u) >> 3) * 64u;
     const CameraRec *__restrict__ cam = sc.camera;
 
     // this wave's role (wave-uniform): serve the list of heavy pixels first, a few at a time (RenderArgs::heavy_list)
@@ -3003,9 +2969,6 @@ __global__ __launch_bounds__(T::BLOCK, T::MIN_WAVES) void render_kernel(DeviceSc
     walk_best.obj = kNone;
     [[maybe_unused]] SegState seg{0u, kSegEnd, 0u};  // segmented walk: hi == kSegEnd also means "nothing more to walk" for an idle lane
 
-#if RT_STAMP
-    if (threadIdx.x == 0 && blockIdx.x == 0 && !a.probe) atomicMin(a.ray_counter + 5, (unsigned long long)wall_clock64());
-#endif
 #if RT_PHASES
     PhaseSums ph{};
     const unsigned long long ph_start = __builtin_readcyclecounter();
@@ -3052,25 +3015,22 @@ __global__ __launch_bounds__(T::BLOCK, T::MIN_WAVES) void render_kernel(DeviceSc
                     else if (from_list) heavy_dry = true;
                     else exhausted = true;
                 }
-#if RT_STAMP
-                if (exhausted && lane == 0 && !a.probe) atomicMin(a.ray_counter + 2, (unsigned long long)wall_clock64());
-#endif
                 const uint32_t slot = base + (uint32_t)__popcll(need & ((1ull << lane) - 1ull));
                 if (((need >> lane) & 1ull) && slot < queue_len) {
                     // heaviest tiles first when the launcher has ranked them (see rt_render_launch); else row-major
                     const uint32_t w = slot & 63u;
-                    uint32_t tile = (RT_ORDER_ON && a.tile_order && !a.pixel_list && !from_list) ? a.tile_order[slot >> 6] : slot >> 6;
+                    uint32_t tile = (a.tile_order && !from_list) ? a.tile_order[slot >> 6] : slot >> 6;
                     int pi = (int)((tile % tiles_x) * 8u + (w & 7u));
                     int lr = (int)((tile / tiles_x) * 8u + (w >> 3));
                     bool take = pi < a.width && lr < a.rows_owned;
-                    if (a.pixel_list || from_list) {  // listed pixels: compact index -> row, column
-                        const uint32_t loc = from_super ? a.super_list[slot] : (from_list ? a.heavy_list[slot] : a.pixel_list[slot]);
+                    if (from_list) {  // listed pixels: compact index -> row, column
+                        const uint32_t loc = from_super ? a.super_list[slot] : a.heavy_list[slot];
                         lr = (int)(loc / (uint32_t)a.width);
                         pi = (int)(loc % (uint32_t)a.width);
                         tile = ((uint32_t)lr >> 3) * tiles_x + ((uint32_t)pi >> 3);
                         take = true;
                     } else if (a.pix_class && take) {
-                        take = a.pix_class[(size_t)lr * (size_t)a.width + (size_t)pi] == 0;  // the other launch's pixel
+                        take = a.pix_class[(size_t)lr * (size_t)a.width + (size_t)pi] == 0;  // a listed pixel: the serving waves take it
                     }
                     if (take) {
                         i = pi;
@@ -3090,12 +3050,9 @@ __global__ __launch_bounds__(T::BLOCK, T::MIN_WAVES) void render_kernel(DeviceSc
                         sample = 0;
                         depth = 0;
                         pix_rays = 0;
-                        if (RT_PROBE_ON) my_tile = tile;
+                        my_tile = tile;
                         ray = camera_ray(cam, i, j, a.width, a.height, rng);
                         active = true;
-#if RT_STAMP
-                        if (a.dbg_times && !a.probe) a.dbg_times[2 * local] = (uint32_t)wall_clock64();
-#endif
                         if constexpr (T::PARK) {
                             park_put_int<T::BLOCK>(sc.lds_park, 0, (uint32_t)i);
                             park_put_int<T::BLOCK>(sc.lds_park, 1, (uint32_t)j);
@@ -3128,9 +3085,6 @@ __global__ __launch_bounds__(T::BLOCK, T::MIN_WAVES) void render_kernel(DeviceSc
 #if RT_PHASES == 2
                 ph_flush(a, ph, ph_start, lane);
                 ph_serving = false;
-#endif
-#if RT_STAMP
-                if (lane == 0 && !a.probe) atomicMax(a.ray_counter + 8, (unsigned long long)wall_clock64());  // last serving wave done with the heavy list
 #endif
                 continue;
             }
@@ -3165,7 +3119,7 @@ __global__ __launch_bounds__(T::BLOCK, T::MIN_WAVES) void render_kernel(DeviceSc
         bool thin = false;
         if constexpr (T::WORLD == 0 && !T::COMPOSITE) {
             // Frame tail of a sphere world: the queue is dry and few lanes are left -- scan instead of walking (scan_grouped_ms).
-            thin = sc.ms_planes != nullptr && ((exhausted && __popcll(live) < a.coop_threshold) || (heavy_mode && a.heavy_scan));
+            thin = sc.ms_planes != nullptr && exhausted && __popcll(live) < a.coop_threshold;
             if (thin) {
                 PH_BEGIN();
                 scan_grouped_ms(sc, lane, live, ray, 0.001, DBL_MAX, h, hit);
@@ -3203,15 +3157,11 @@ __global__ __launch_bounds__(T::BLOCK, T::MIN_WAVES) void render_kernel(DeviceSc
                     const bool mover = walk_moving(walk.state);
                     [[maybe_unused]] bool limited_walks = false;
                     if constexpr (T::SEG) limited_walks = __any(mover && seg.hi != kSegEnd);
-#if RT_SIMPLE_BREAK
-                    if (!__any(mover)) break;
-#else
                     const int movers = __popcll(__ballot(mover));
                     const int parked = __popcll(__ballot(walk_parked(walk.state)));
                     // most walkers are waiting at leaves: go test them.  A composite leaf (box, instance, medium) costs
                     // tens of node steps, so there the leaf phase waits for a larger share of the walkers.
                     if (movers == 0 || movers * (T::COMPOSITE ? a.park_ratio : 1) < parked) break;
-#endif
                     {
                         PH_BEGIN();
 #if RT_PHASES
@@ -3329,7 +3279,7 @@ __global__ __launch_bounds__(T::BLOCK, T::MIN_WAVES) void render_kernel(DeviceSc
             const bool no_bounces = a.max_depth <= 0;  // R/kernel.cu:71: the bounce loop never runs, RayColor returns black
             if (!no_bounces) {
                 if constexpr (T::PARK) {
-                    if (RT_PROBE_ON && a.probe) park_put_int<T::BLOCK>(sc.lds_park, 4, park_get_int<T::BLOCK>(sc.lds_park, 4) + 1u);  // only the rehearsal asks
+                    if (a.probe) park_put_int<T::BLOCK>(sc.lds_park, 4, park_get_int<T::BLOCK>(sc.lds_park, 4) + 1u);  // only the rehearsal asks
                 } else {
                     pix_rays++;
                 }
@@ -3391,7 +3341,7 @@ __global__ __launch_bounds__(T::BLOCK, T::MIN_WAVES) void render_kernel(DeviceSc
                     throughput = mk(1.0, 1.0, 1.0);
                     accumulated = mk(0.0, 0.0, 0.0);
                     depth = 0;
-                } else if (RT_PROBE_ON && a.probe) {
+                } else if (a.probe) {
                     // cost probe: the samples were a rehearsal (the saved RNG state is untouched); book the rays
                     if constexpr (T::PARK) {
                         local = (size_t)park_get_int<T::BLOCK>(sc.lds_park, 2);
@@ -3404,9 +3354,6 @@ __global__ __launch_bounds__(T::BLOCK, T::MIN_WAVES) void render_kernel(DeviceSc
                     active = false;
                 } else {
                     // R/kernel.cu:146-153: save the RNG state, average, gamma 2
-#if RT_STAMP
-                    if (a.dbg_times) a.dbg_times[2 * local + 1] = (uint32_t)wall_clock64();
-#endif
                     if constexpr (T::PARK) local = (size_t)park_get_int<T::BLOCK>(sc.lds_park, 2);
                     a.state[0 * (size_t)a.n_pixels + local] = rng.d;
                     a.state[1 * (size_t)a.n_pixels + local] = rng.v0;
@@ -3461,12 +3408,6 @@ __global__ __launch_bounds__(T::BLOCK, T::MIN_WAVES) void render_kernel(DeviceSc
     if (RT_PHASES == 1 || ph_serving) ph_flush(a, ph, ph_start, lane);
 #endif
 
-#if RT_STAMP
-    if (lane == 0 && !a.probe) {
-        atomicMax(a.ray_counter + 3, (unsigned long long)wall_clock64());
-        atomicMin(a.ray_counter + 4, (unsigned long long)wall_clock64());  // first wave to finish
-    }
-#endif
     // one atomic per wave for the ray counter
     const unsigned long long total = wave_rays;
     if (lane == 0 && total) atomicAdd(a.ray_counter, total);
@@ -3581,45 +3522,23 @@ hipError_t RT_CAT(launch_seed_, RT_SUFFIX)(const SeedArgs &a, hipStream_t stream
 #endif
 
 namespace {
-#ifndef RT_WAVES_SPHERES
-#define RT_WAVES_SPHERES 3  // three workgroups per CU serve the heavy and the light pixels (rt_render_launch): 168 VGPRs at most
-#endif
-#ifndef RT_WAVES_BVH
-#define RT_WAVES_BVH 3
-#endif
-using TSphereList = Traits<2, false, false, RT_WAVES_SPHERES>;
-using TBvhPrims = Traits<0, false, false, RT_WAVES_BVH>;
-#ifndef RT_BLOCK_FAST
-#define RT_BLOCK_FAST 768
-#endif
-using TBvhPrimsFast = Traits<0, false, false, RT_WAVES_BVH, false, false, false, RT_BLOCK_FAST, true>;  // through the library's own tree
-#ifndef RT_WAVES_GENERAL
-#define RT_WAVES_GENERAL 2
-#endif
-#ifndef RT_WAVES_INSTANCES
-#define RT_WAVES_INSTANCES 3  // 168 VGPRs: the instances kernel sits right at the step from three waves per SIMD to two
-#endif
-using TBvhGeneral = Traits<0, true, true, RT_WAVES_GENERAL>;
-using TListGeneral = Traits<1, true, true, RT_WAVES_GENERAL>;
-using TBvhInstances = Traits<0, true, false, RT_WAVES_INSTANCES, false>;  // instances / boxes, no media, plain textures (C4)
+using TSphereList = Traits<2, false, false, 3>;  // three workgroups per CU serve the heavy and the light pixels (rt_render_launch): 168 VGPRs at most
+using TBvhPrims = Traits<0, false, false, 3>;
+using TBvhPrimsFast = Traits<0, false, false, 3, false, false, false, 768, true>;  // through the library's own tree
+using TBvhGeneral = Traits<0, true, true, 2>;
+using TListGeneral = Traits<1, true, true, 2>;
+// instances / boxes, no media, plain textures (C4).  168 VGPRs: the instances kernel sits right at the step from three waves per
+// SIMD to two
+using TBvhInstances = Traits<0, true, false, 3, false>;
 // The media and general kernels need ~220 and ~300 VGPRs.  Walking a deep tree they are latency-bound -- one wave per
 // SIMD runs at half the speed of two -- so three waves with a hundred-odd registers spilled to scratch still win
 // (Cornell smoke +5 %, C5 +4.5 %).  A shallow world with expensive shading (Perlin, image texture) loses a third that
 // way, so the general kernel exists in both shapes and the launcher picks by the depth of the world's tree.
-#ifndef RT_WAVES_MEDIA
-#define RT_WAVES_MEDIA 3
-#endif
-using TBvhMedia = Traits<0, true, false, RT_WAVES_MEDIA, true>;                      // + ConstantMedium (Cornell smoke)
-#ifndef RT_WAVES_DEEP
-#define RT_WAVES_DEEP 3
-#endif
-#ifndef RT_BLOCK_DEEP
-#define RT_BLOCK_DEEP 768
-#endif
-using TBvhGeneralDeep = Traits<0, true, true, RT_WAVES_DEEP, true, true, false, RT_BLOCK_DEEP>;
+using TBvhMedia = Traits<0, true, false, 3, true>;  // + ConstantMedium (Cornell smoke)
+using TBvhGeneralDeep = Traits<0, true, true, 3, true, true, false, 768>;
 // ... and walked through the library's tree, one walk per run of surface leaves between two media (Traits::SEG): worlds that
 // flat_scene.h SCENE_SEGMENTED describes (C5)
-using TBvhSegmented = Traits<0, true, true, RT_WAVES_DEEP, true, true, false, RT_BLOCK_DEEP, true>;
+using TBvhSegmented = Traits<0, true, true, 3, true, true, false, 768, true>;
 // List scans over primitives / instances without media or table-walking textures.  Also the BVH worlds of small
 // scenes: for up to 16 leaves within a cost budget (FlatScene::scan_cost) a scan of all of them in the tree's leaf order -- every lane on the same leaf, rows
 // through uniform loads, no node visits, no phases -- beats walking the tree (Cornell box: 8 leaves, 7 nodes).  Without
@@ -3631,10 +3550,8 @@ using TBvhSegmented = Traits<0, true, true, RT_WAVES_DEEP, true, true, false, RT
 using TBvhNested = Traits<0, true, true, 2, true, false, true>;
 using TListNested = Traits<1, true, true, 2, true, false, true>;
 using TListPrims = Traits<1, false, false, 4>;  // 127-129 VGPRs without the bound: the strict build would drop to three waves for one register
-#ifndef RT_WAVES_LIST_INSTANCES
-#define RT_WAVES_LIST_INSTANCES 4  // 128 VGPRs and 52 B of scratch for a fourth wave per SIMD: C4 +2.4 % (139 VGPRs, none, three waves before)
-#endif
-using TListInstances = Traits<1, true, false, RT_WAVES_LIST_INSTANCES, false>;
+// 128 VGPRs and 52 B of scratch for a fourth wave per SIMD: C4 +2.4 % (139 VGPRs, none, three waves before)
+using TListInstances = Traits<1, true, false, 4, false>;
 // The same kernel compiled for FIVE waves per SIMD (96 VGPRs and 64 B of scratch with the path state parked in LDS, Traits::PARK).  Its passes take 1.38 times as long
 // -- the SIMDs' issue slots are nearly full with four waves -- so in the steady state it is the slower of the two; but a pixel's
 // samples are one chain, pixels of these worlds all cost about the same, and a frame is therefore a whole number of pixel
@@ -3643,11 +3560,8 @@ using TListInstances = Traits<1, true, false, RT_WAVES_LIST_INSTANCES, false>;
 using TListInstances5 = Traits<1, true, false, 5, false>;
 // The same two with the leaves of every ray dealt to lanes (pixels_per_wave < 64: fewer pixels than lanes, the frame is bound
 // by the latency of a ray, not by throughput -- registers matter more than a fourth wave)
-#ifndef RT_WAVES_GROUPED
-#define RT_WAVES_GROUPED 3
-#endif
-using TListPrimsGrouped = Traits<1, false, false, RT_WAVES_GROUPED, false, false, false, 256, false, true>;
-using TListInstancesGrouped = Traits<1, true, false, RT_WAVES_GROUPED, false, false, false, 256, false, true>;
+using TListPrimsGrouped = Traits<1, false, false, 3, false, false, false, 256, false, true>;
+using TListInstancesGrouped = Traits<1, true, false, 3, false, false, false, 256, false, true>;
 
 // Do the node rows and the sphere / material rows of a primitive world fit the library-tree kernel's LDS?  (The same sums as
 // launch_one<TBvhPrimsFast>'s placement, for callers that have no reference tree to fall back to.)
@@ -3678,7 +3592,7 @@ hipError_t launch_one(const DeviceScene &sc_in, RenderArgs a, hipStream_t stream
             lds = need;
             a.lds_nodes = 1;
         }
-        if (T::FAST && T::BLOCK >= RT_BIG_BLOCK && a.lds_nodes) {
+        if (T::FAST && T::BLOCK >= kBigBlock && a.lds_nodes) {
             // One workgroup per CU: the sphere rows the leaf tests and the hit record read and the material rows follow the
             // node rows into the CU's LDS -- a frame ends with its longest pixel, and that pixel's chain is made of exactly
             // these dependent reads (C3: leaf pass 2100 -> ... cycles, shading pass 11000 -> ... cycles).
@@ -3696,7 +3610,7 @@ hipError_t launch_one(const DeviceScene &sc_in, RenderArgs a, hipStream_t stream
             place(sc.lds_materials, (size_t)sc.n_materials * sizeof(MaterialRec));
             lds = off;
         }
-        if constexpr (T::FAST && T::BLOCK >= RT_BIG_BLOCK) {
+        if constexpr (T::FAST && T::BLOCK >= kBigBlock) {
             // The library-tree kernel reads these rows from LDS only (no global side in its accessors: head of
             // render_kernel); a world whose rows do not fit is walked by the reference-tree kernel.
             const bool fits = a.lds_nodes && (sc.n_mspheres == 0 || (sc.lds_mspheres != kNone && sc.lds_msphere_aux != kNone)) &&
@@ -3721,7 +3635,7 @@ hipError_t launch_one(const DeviceScene &sc_in, RenderArgs a, hipStream_t stream
             // chases through (object -> transforms -> medium; material rows; Perlin tables: a few KB even in the Book-2
             // final scene) and, where they fit as well, the quad / box rows (Cornell box: 2 KB).
             // three 256-thread workgroups per CU share its 160 KB, or one of 768 threads has (nearly) all of it
-            const size_t budget = T::BLOCK >= RT_BIG_BLOCK ? 158 * 1024 : 52 * 1024;
+            const size_t budget = T::BLOCK >= kBigBlock ? 158 * 1024 : 52 * 1024;
             size_t off = (lds + 15) & ~(size_t)15;
             auto place = [&](uint32_t &slot, size_t bytes, size_t cap) {
                 if (bytes == 0 || bytes > cap || off + bytes + 64 > budget) return;
@@ -3735,7 +3649,7 @@ hipError_t launch_one(const DeviceScene &sc_in, RenderArgs a, hipStream_t stream
             place(sc.lds_materials, (size_t)sc.n_materials * sizeof(MaterialRec), 4096);
             if (T::RICH) place(sc.lds_perlin, (size_t)sc.n_perlin * sizeof(PerlinRec), 2 * sizeof(PerlinRec));
             const size_t b_quads = (size_t)sc.n_quads * sizeof(AAQuad), b_boxes = (size_t)sc.n_boxes * sizeof(BoxRec);
-            if (T::BLOCK >= RT_BIG_BLOCK) {  // the big tables, most useful first
+            if (T::BLOCK >= kBigBlock) {  // the big tables, most useful first
                 place(sc.lds_boxes, b_boxes, 80 * 1024);
                 place(sc.lds_spheres_tab, (size_t)sc.n_spheres * sizeof(SphereGeom), 40 * 1024);
                 place(sc.lds_quad_aa, b_quads, 16 * 1024);
@@ -3744,7 +3658,7 @@ hipError_t launch_one(const DeviceScene &sc_in, RenderArgs a, hipStream_t stream
                 place(sc.lds_boxes, b_boxes, 16 * 1024);
             }
             lds = off;
-            if constexpr (T::BATCH && T::BLOCK >= RT_BIG_BLOCK) {
+            if constexpr (T::BATCH && T::BLOCK >= kBigBlock) {
                 // The deep kernel reads its node rows and every table from LDS only (its accessors have no global side: see
                 // the head of render_kernel).  A scene that does not fit goes to the general kernel, which reads what is
                 // not staged from L2.
@@ -3805,9 +3719,7 @@ hipError_t launch_one(const DeviceScene &sc_in, RenderArgs a, hipStream_t stream
     uint32_t resident = (uint32_t)per_cu * (uint32_t)(a.num_cus > 0 ? a.num_cus : 256);
     constexpr uint32_t kWavesPerBlock = (uint32_t)T::BLOCK / 64u;
     uint32_t blocks = (tiles + kWavesPerBlock - 1u) / kWavesPerBlock;
-    if (a.pixel_list) blocks = resident;  // a pixel list's length lives on the device: the launcher caps the grid (grid_blocks)
     if (blocks > resident) blocks = resident;
-    if (a.grid_blocks > 0 && blocks > (uint32_t)a.grid_blocks) blocks = (uint32_t)a.grid_blocks;  // tuning experiments
     dim3 grid(blocks), block(T::BLOCK);
     hipLaunchKernelGGL(kernel, grid, block, lds, stream, sc, a);
     return hipGetLastError();
@@ -3847,7 +3759,6 @@ namespace {
 // with the fewest waves.
 int list_instances_waves(const RenderArgs &a)
 {
-    if (a.list_waves == 4 || a.list_waves == 5) return a.list_waves;  // RT_TUNING builds / tests
     const double pixels = (double)a.width * (double)a.rows_owned;
     const double cus = a.num_cus > 0 ? (double)a.num_cus : 256.0;
     const double gen4 = std::ceil(pixels / (cus * 16.0 * 64.0) - 0.02), gen5 = std::ceil(pixels / (cus * 20.0 * 64.0) - 0.02);

@@ -30,18 +30,12 @@ struct RenderArgs {
     uint32_t *tile_cost;        // probe launches: rays traced per 8x8 tile (one counter per tile of this rank's rows)
     const uint32_t *tile_order; // render launches: queue position -> tile (nullptr = tiles in row-major order)
     int32_t probe;              // 1 = cost probe: trace `spp` samples per pixel, write nothing but tile_cost / pix_cost
-    // Sphere-list worlds, two classes of pixels (device_scene.cpp rt_render_launch): the probe books every pixel's rays in
-    // pix_cost; classify_pixels marks the heavy ones in pix_class and lists them; the frame is then two launches -- the
-    // listed pixels (pixel_list, a few lanes-per-ray waves, started first) and all the others (pix_class != 0 is skipped).
+    // Two classes of pixels (device_scene.cpp enqueue_frame): the probe books every pixel's rays in pix_cost;
+    // classify_pixels marks the heavy ones in pix_class and lists them.  The render launch then serves both: the first
+    // `heavy_waves` waves of every workgroup serve heavy_list (heavy_ppw pixels at a time, through heavy_cursor) and join
+    // the tile queue when the list is done; the tile queue skips the pixels whose class is non-zero.
     uint32_t *pix_cost;               // probe launches: rays traced by each owned pixel
-    uint32_t *dbg_times;              // RT_STAMP builds: per pixel, low words of the wall clock at its start and at its end
-    const uint32_t *pixel_list;       // render launch over a list of owned pixels (compact indices) instead of the tile queue
-    const uint32_t *pixel_list_count; // device word holding the length of pixel_list
-    const uint8_t *pix_class;         // tile-queue launches: pixels whose class is non-zero belong to another launch
-    int32_t wave_priority;            // s_setprio for this launch's waves (0..3)
-    // The same two classes inside ONE launch (kernels whose workgroup fills a CU: a second launch could not be resident
-    // beside it): the first `heavy_waves` waves of every workgroup serve heavy_list (heavy_ppw pixels at a time, through
-    // heavy_cursor) and join the tile queue when the list is done; the tile queue skips pix_class != 0 as above.
+    const uint8_t *pix_class;         // tile queue: pixels whose class is non-zero are served from heavy_list / super_list
     const uint32_t *heavy_list;
     const uint32_t *heavy_count;
     // ... the very longest chains among them (classify_pixels: probed cost >= super_threshold) on a list of their own, which the
@@ -65,8 +59,6 @@ struct RenderArgs {
     int32_t object_batch;   // the same for instances / groups (their cooperative scan serves one ray at a time: a small batch is fine)
     int32_t lds_nodes;      // set by the launcher: BVH nodes are staged in LDS
     int32_t small_world;    // BVH worlds without media are scanned, not walked, up to this scan cost (and 16 leaves)
-    int32_t list_waves;     // instanced-list kernel: 4 or 5 waves per SIMD, 0 = by the frame's pixel generations (render.hip list_instances_waves)
-    int32_t heavy_scan;     // sphere BVH worlds: the waves that serve the heavy pixels scan all leaves instead of walking
     int32_t accelerate_lists;  // list worlds of primitives: walk the library's tree instead of scanning the list
     int32_t exact_scan;     // sphere-list worlds: no conservative filter in front of the reference's sphere test
     int32_t filter_fp64;    // sphere-list worlds: the fp64 form of that filter, one sphere at a time (default: packed fp32, two at a time)
@@ -79,8 +71,7 @@ struct RenderArgs {
     int32_t lds_spheres;    // set by the launcher: sphere planes staged in LDS for the cooperative scan
     int32_t overdue_priority;
     int32_t boost_rounds;   // overdue-only cooperative passes inserted after each pixel-parallel pass
-    int32_t grid_blocks;        // tuning: hard cap on the persistent grid (0 = none)
-    int32_t max_blocks_per_cu;  // tuning: cap on resident workgroups per CU (0 = whatever fits)
+    int32_t max_blocks_per_cu;  // cap on resident workgroups per CU (0 = whatever fits)
     int32_t pixels_per_wave;    // sphere-list kernel: at most this many lanes of a wave hold a pixel (64 = all of them)
     int32_t shade_batch;    // BVH kernels: shade once this many lanes have finished their walk
     uint32_t ray_budget;    // sphere-list kernel: a pixel past this many rays is finished cooperatively

@@ -699,11 +699,12 @@ def test_thin_wave_scan_of_a_sphere_bvh_world_equals_the_walk(oracle, scene_id, 
     assert np.array_equal(scan.view(np.uint64), want.view(np.uint64))
 
 
-def test_heavy_and_light_pixels_in_two_launches_give_the_same_frame(oracle):
+def test_heavy_and_light_pixels_in_one_launch_give_the_same_frame(oracle):
     """Sphere-list worlds (config C2): a rehearsal of the first samples finds the pixels with long ray chains (glass);
-    they are rendered by a launch of their own, a few pixels per wave with the lanes sharing each ray's scan, beside the
-    launch of all the others.  Every pixel is rendered exactly once from its own RNG stream, so the frame, the ray count
-    and the saved RNG state are those of the single launch (RT_FLAG_NO_PIXEL_CLASSES = 64); rows against the oracle too."""
+    two serving waves of every workgroup render them first, a few pixels per wave with the lanes sharing each ray's scan,
+    while the other waves render all the others from the tile queue.  Every pixel is rendered exactly once from its own
+    RNG stream, so the frame, the ray count and the saved RNG state are those of the launch without pixel classes
+    (RT_FLAG_NO_PIXEL_CLASSES = 64); rows against the oracle too."""
     w, h, spp = 512, 256, 64          # 131072 pixels: the smallest frame that is split
     s = rt.builtin_scene(11, 1, w, h)
     film_a, film_b = rt.Film(w, h), rt.Film(w, h)
