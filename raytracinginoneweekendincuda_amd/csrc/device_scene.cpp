@@ -682,6 +682,16 @@ int rt_render_finish(rt_scene *scene, rt_film *film, rt_render_stats *stats)
             if ((f.last_kernel.kind & 63) >= 16) {  // sphere-list kernel: slots 0 / 1 are its two scans
                 name[0] = "scan, pixel-parallel";
                 name[1] = "scan, cooperative";
+                name[12] = name[13] = "";  // slots 12, 13, 15: the survivor counts of the pixel-parallel scan (render.hip ScanSums)
+                const double passes = (double)c[96 + 0], groups = (double)c[96 + 12], taken = (double)c[64 + 12];
+                if (groups > 0) {
+                    std::fprintf(stderr, "survivors: %.0f passes, %.2f groups of 4 per pass, groups taken f = %.4f\n", passes, groups / passes, taken / groups);
+                    std::fprintf(stderr, "survivors: spheres with a passing lane per taken group %.3f, lane appends per pass %.1f, lanes behind per pass %.2f\n",
+                                 (double)c[32 + 12] / taken, (double)c[96 + 13] / passes, (double)c[64 + 13] / passes);
+                    std::fprintf(stderr, "survivors: drains per pass %.2f, drain iterations (wave max of count) per pass %.2f, drain cycles %.1f %% of the "
+                                 "pixel-parallel scan's (%.0f of %.0f per pass)\n", (double)c[96 + 15] / passes, (double)c[64 + 15] / passes,
+                                 100.0 * c[32 + 13] / c[32 + 0], (double)c[32 + 13] / passes, (double)c[32 + 0] / passes);
+                }
             }
             const double total = (double)c[7];
             for (int k = 0; k < 24; k++)

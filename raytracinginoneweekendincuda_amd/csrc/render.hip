@@ -438,6 +438,19 @@ struct PhaseSums {
 #define PH_ARG
 #define PH_PASS
 #define PH_SUB_BEGIN() do { } while (0)
+#endif
+#if RT_PHASES
+// Survivor counts of the sphere-list scan through the filter, one pixel-parallel pass (wave-uniform: every active lane holds the same
+// values).  The render loop adds them to the wave-level phase slots 12, 13 and 15 (device_scene.cpp prints them as the survivor table).
+struct ScanSums {
+    uint32_t groups, taken, spheres, appends, behind;  // groups of 4 examined / taken; spheres with a passing lane; lane appends; lanes behind
+    uint32_t drains, drain_iters, drain_cycles;        // drain calls; wave max of count per call, summed; cycles spent draining
+};
+#define SS_ARG , ScanSums &ss
+#define SS_PASS , ss
+#else
+#define SS_ARG
+#define SS_PASS
 #define PH_COUNT(k) do { } while (0)
 #define PH_SUB_END(k) do { } while (0)
 #endif
@@ -1661,7 +1674,21 @@ DEV void scan_rows_arrived(const SphereScanRow &g0, const SphereScanRow &g1, con
     asm volatile("" ::"s"(g2.cx), "s"(g2.cy), "s"(g2.cz), "s"(g2.k), "s"(g3.cx), "s"(g3.cy), "s"(g3.cz), "s"(g3.k));
 }
 
-// Four spheres through the filter: four independent chains, one branch for the four of them.
+// Append sphere k to this lane's queue if `keep`.  Called for a sphere that some lane of the wave passed (a wave-uniform
+// branch on the ballot of the pass bits, so a sphere no lane passed costs no vector instruction): every lane writes its
+// next slot and only the lanes that keep the sphere move `count` on, so the append needs no exec mask of its own.  A slot
+// written in vain is overwritten by the lane's next append or lies beyond `count`, where the drain does not read; it is
+// always inside the queue: the scans drain before any lane could hold kQueueCap entries, so count < kQueueCap here.
+constexpr int kFilterTrip = 8;  // spheres per trip of the filtered scans; they drain when a lane holds more than kQueueCap - kFilterTrip
+static_assert(kFilterTrip < kQueueCap, "a trip of appends must fit between the drain threshold and the end of the queue");
+DEV void append_survivor(uint16_t *queue, uint32_t lane, uint32_t &count, uint32_t k, bool keep)
+{
+    queue[count * 64u + lane] = (uint16_t)k;
+    count += keep ? 1u : 0u;
+}
+
+// Four spheres through the filter: four independent chains, one wave-level branch for the four of them, then one per sphere
+// that some lane passed.
 DEV void filter_four(const SphereScanRow &g0, const SphereScanRow &g1, const SphereScanRow &g2, const SphereScanRow &g3, uint32_t k0,
                      const ScanRay &f, uint16_t *queue, uint32_t lane, uint32_t &count)
 {
@@ -1673,15 +1700,14 @@ DEV void filter_four(const SphereScanRow &g0, const SphereScanRow &g1, const Sph
         q[u] = filter_q(f, s[u], g[u]->cx, g[u]->cy, g[u]->cz);
     }
     asm volatile("" : "+v"(q[0]), "+v"(q[1]), "+v"(q[2]), "+v"(q[3]));
-    const bool p0 = q[0] > g0.k, p1 = q[1] > g1.k, p2 = q[2] > g2.k, p3 = q[3] > g3.k;
-    if (p0 | p1 | p2 | p3) {
-        const bool p[4] = {p0, p1, p2, p3};
+    const bool p[4] = {q[0] > g0.k, q[1] > g1.k, q[2] > g2.k, q[3] > g3.k};
+    const unsigned long long m[4] = {__ballot(p[0]), __ballot(p[1]), __ballot(p[2]), __ballot(p[3])};  // the compares' own lane masks
+    if (m[0] | m[1] | m[2] | m[3]) {
 #pragma unroll
         for (int u = 0; u < 4; u++) {
-            if (p[u] && !filter_behind(f, s[u], q[u], g[u]->k)) {
-                queue[count * 64u + lane] = (uint16_t)(k0 + u);
-                count++;
-            }
+            if (!m[u]) continue;  // wave-uniform: no lane passed this sphere
+            const bool keep = p[u] && !filter_behind(f, s[u], q[u], g[u]->k);
+            append_survivor(queue, lane, count, k0 + u, keep);
         }
     }
 }
@@ -1690,8 +1716,15 @@ DEV void filter_four(const SphereScanRow &g0, const SphereScanRow &g1, const Sph
 // from the LDS planes of the cooperative scan (a queue entry costs one LDS round trip instead of one to L2).
 template <bool ROWS_IN_LDS>
 DEV void drain_filtered(const SphereGeom *__restrict__ spheres, uint32_t planes_off, uint32_t n_padded, const uint16_t *queue, uint32_t lane,
-                        uint32_t &count, const Ray &r, double a, double tmin, double &closest, uint32_t &best_k)
+                        uint32_t &count, const Ray &r, double a, double tmin, double &closest, uint32_t &best_k SS_ARG)
 {
+#if RT_PHASES
+    const unsigned long long ss_t0 = __builtin_readcyclecounter();
+    uint32_t ss_max = count;
+    for (int off = 32; off > 0; off >>= 1) ss_max = max(ss_max, (uint32_t)__shfl_xor((int)ss_max, off, 64));
+    ss.drains++;
+    ss.drain_iters += ss_max;
+#endif
     for (uint32_t s = 0; s < count; s++) {
         uint32_t k = queue[s * 64u + lane];
         SphereGeom g;
@@ -1708,6 +1741,10 @@ DEV void drain_filtered(const SphereGeom *__restrict__ spheres, uint32_t planes_
         }
     }
     count = 0;
+#if RT_PHASES
+    asm volatile("" ::"v"(closest), "v"(best_k));
+    ss.drain_cycles += (uint32_t)(__builtin_readcyclecounter() - ss_t0);
+#endif
 }
 
 // ---- the same filter in packed fp32, two spheres per instruction (r3) -------------------------------------------------------
@@ -1762,9 +1799,10 @@ DEV void scan_pairs_arrived(const SphereScanPair &g0, const SphereScanPair &g1)
     asm volatile("" ::"s"(g0.cx[0]), "s"(g0.cx[1]), "s"(g0.cy[0]), "s"(g0.cy[1]), "s"(g0.cz[0]), "s"(g0.cz[1]), "s"(g0.k[0]), "s"(g0.k[1]));
     asm volatile("" ::"s"(g1.cx[0]), "s"(g1.cx[1]), "s"(g1.cy[0]), "s"(g1.cy[1]), "s"(g1.cz[0]), "s"(g1.cz[1]), "s"(g1.k[0]), "s"(g1.k[1]));
 }
-// Two pairs = four spheres (list positions k0 .. k0 + 3): two packed chains, four compares, one branch for the four of them.
+// Two pairs = four spheres (list positions k0 .. k0 + 3): two packed chains, four compares, one wave-level branch for the four of
+// them, then the survivor path only for the spheres some lane passed (as in filter_four).
 DEV void filter_pairs(const SphereScanPair &g0, const SphereScanPair &g1, uint32_t k0, const ScanRay32 &f, uint16_t *queue, uint32_t lane,
-                      uint32_t &count)
+                      uint32_t &count SS_ARG)
 {
     const v2f ux = {f.ux, f.ux}, uy = {f.uy, f.uy}, uz = {f.uz, f.uz}, px = {f.px, f.px}, py = {f.py, f.py}, pz = {f.pz, f.pz}, nt = {f.nthr, f.nthr};
     const SphereScanPair *g[2] = {&g0, &g1};
@@ -1775,19 +1813,26 @@ DEV void filter_pairs(const SphereScanPair &g0, const SphereScanPair &g1, uint32
         s[h] = __builtin_elementwise_fma(cz, uz, __builtin_elementwise_fma(cy, uy, cx * ux));
         q[h] = __builtin_elementwise_fma(s[h], s[h], __builtin_elementwise_fma(pz, cz, __builtin_elementwise_fma(py, cy, __builtin_elementwise_fma(px, cx, nt))));
     }
-    const bool p0 = q[0].x > g0.k[0], p1 = q[0].y > g0.k[1], p2 = q[1].x > g1.k[0], p3 = q[1].y > g1.k[1];
-    if (p0 | p1 | p2 | p3) {
-        const bool p[4] = {p0, p1, p2, p3};
+    const bool p[4] = {q[0].x > g0.k[0], q[0].y > g0.k[1], q[1].x > g1.k[0], q[1].y > g1.k[1]};
+    const unsigned long long m[4] = {__ballot(p[0]), __ballot(p[1]), __ballot(p[2]), __ballot(p[3])};  // the compares' own lane masks
+#if RT_PHASES
+    ss.groups++;
+    ss.taken += (m[0] | m[1] | m[2] | m[3]) ? 1u : 0u;
+    ss.spheres += (m[0] ? 1u : 0u) + (m[1] ? 1u : 0u) + (m[2] ? 1u : 0u) + (m[3] ? 1u : 0u);
+#endif
+    if (m[0] | m[1] | m[2] | m[3]) {
         const float sv[4] = {s[0].x, s[0].y, s[1].x, s[1].y}, qv[4] = {q[0].x, q[0].y, q[1].x, q[1].y};
         const float kv[4] = {g0.k[0], g0.k[1], g1.k[0], g1.k[1]};
 #pragma unroll
         for (int u = 0; u < 4; u++) {
+            if (!m[u]) continue;  // wave-uniform: no lane passed this sphere
             const float bu = f.od - sv[u];
             const bool behind = bu > f.root_m && __builtin_fmaf(bu, bu, kv[u] - qv[u]) > 0.0f;  // k = -inf (always passes): never behind
-            if (p[u] && !behind) {
-                queue[count * 64u + lane] = (uint16_t)(k0 + u);
-                count++;
-            }
+#if RT_PHASES
+            ss.appends += (uint32_t)__popcll(__ballot(p[u] && !behind));
+            ss.behind += (uint32_t)__popcll(__ballot(p[u] && behind));
+#endif
+            append_survivor(queue, lane, count, k0 + u, p[u] && !behind);
         }
     }
 }
@@ -1796,7 +1841,7 @@ DEV void filter_pairs(const SphereScanPair &g0, const SphereScanPair &g1, uint32
 // spheres) per trip in two register sets like scan_filtered; the survivors go through drain_filtered, i.e. the reference's test.
 template <bool ROWS_IN_LDS>
 DEV bool scan_filtered32(const DeviceScene &sc, uint32_t planes_off, uint32_t n_padded, uint16_t *queue, uint32_t lane, const Ray &r, double tmin,
-                         double tmax, HitInfo &best)
+                         double tmax, HitInfo &best SS_ARG)
 {
     const SphereScanPair *__restrict__ rows = sc.sphere_scan32;
     const SphereGeom *__restrict__ spheres = sc.spheres;
@@ -1814,22 +1859,22 @@ DEV bool scan_filtered32(const DeviceScene &sc, uint32_t planes_off, uint32_t n_
     for (uint32_t k0 = 0; k0 < n4; k0 += 4) {
         scan_pairs_arrived(a0, a1);
         const SphereScanPair b0 = load_scan_pair(rows, k0 + 2), b1 = load_scan_pair(rows, k0 + 3);
-        filter_pairs(a0, a1, 2u * k0, f, queue, lane, count);
+        filter_pairs(a0, a1, 2u * k0, f, queue, lane, count SS_PASS);
         const uint32_t kn = (k0 + 4 < n4) ? k0 + 4 : k0;  // last trip re-reads its own rows (stays in bounds)
         scan_pairs_arrived(b0, b1);
         a0 = load_scan_pair(rows, kn);
         a1 = load_scan_pair(rows, kn + 1);
-        filter_pairs(b0, b1, 2u * k0 + 4u, f, queue, lane, count);
-        if (__any(count > (uint32_t)(kQueueCap - 8))) drain_filtered<ROWS_IN_LDS>(spheres, planes_off, n_padded, queue, lane, count, r, a, tmin, closest, best_k);
+        filter_pairs(b0, b1, 2u * k0 + 4u, f, queue, lane, count SS_PASS);
+        if (__any(count > (uint32_t)(kQueueCap - kFilterTrip))) drain_filtered<ROWS_IN_LDS>(spheres, planes_off, n_padded, queue, lane, count, r, a, tmin, closest, best_k SS_PASS);
     }
     for (uint32_t k = n4; k < n_pairs; k++) {  // up to three pairs left: one at a time, the second half of the call idle
         const SphereScanPair g = load_scan_pair(rows, k);
         const float inf = __builtin_inff();
         const SphereScanPair none{{0.0f, 0.0f}, {0.0f, 0.0f}, {0.0f, 0.0f}, {inf, inf}};
-        filter_pairs(g, none, 2u * k, f, queue, lane, count);
-        if (__any(count > (uint32_t)(kQueueCap - 4))) drain_filtered<ROWS_IN_LDS>(spheres, planes_off, n_padded, queue, lane, count, r, a, tmin, closest, best_k);
+        filter_pairs(g, none, 2u * k, f, queue, lane, count SS_PASS);
+        if (__any(count > (uint32_t)(kQueueCap - 4))) drain_filtered<ROWS_IN_LDS>(spheres, planes_off, n_padded, queue, lane, count, r, a, tmin, closest, best_k SS_PASS);
     }
-    drain_filtered<ROWS_IN_LDS>(spheres, planes_off, n_padded, queue, lane, count, r, a, tmin, closest, best_k);
+    drain_filtered<ROWS_IN_LDS>(spheres, planes_off, n_padded, queue, lane, count, r, a, tmin, closest, best_k SS_PASS);
     if (best_k == kNone) return false;
     best.t = closest;
     best.ref = make_ref(REF_SPHERE, best_k);
@@ -1841,7 +1886,7 @@ DEV bool scan_filtered32(const DeviceScene &sc, uint32_t planes_off, uint32_t n_
 // as in scan_uniform below.
 template <bool ROWS_IN_LDS>
 DEV bool scan_filtered(const DeviceScene &sc, uint32_t planes_off, uint32_t n_padded, uint16_t *queue, uint32_t lane, const Ray &r, double tmin,
-                       double tmax, HitInfo &best)
+                       double tmax, HitInfo &best SS_ARG)
 {
     const SphereScanRow *__restrict__ rows = sc.sphere_scan;
     const SphereGeom *__restrict__ spheres = sc.spheres;
@@ -1866,7 +1911,7 @@ DEV bool scan_filtered(const DeviceScene &sc, uint32_t planes_off, uint32_t n_pa
         a0 = load_scan_row(rows, kn); a1 = load_scan_row(rows, kn + 1);
         a2 = load_scan_row(rows, kn + 2); a3 = load_scan_row(rows, kn + 3);
         filter_four(b0, b1, b2, b3, k0 + 4, f, queue, lane, count);
-        if (__any(count > (uint32_t)(kQueueCap - 8))) drain_filtered<ROWS_IN_LDS>(spheres, planes_off, n_padded, queue, lane, count, r, a, tmin, closest, best_k);
+        if (__any(count > (uint32_t)(kQueueCap - kFilterTrip))) drain_filtered<ROWS_IN_LDS>(spheres, planes_off, n_padded, queue, lane, count, r, a, tmin, closest, best_k SS_PASS);
     }
     for (uint32_t k = n8; k < n; k++) {
         const SphereScanRow g = load_scan_row(rows, k);
@@ -1876,9 +1921,9 @@ DEV bool scan_filtered(const DeviceScene &sc, uint32_t planes_off, uint32_t n_pa
             queue[count * 64u + lane] = (uint16_t)k;
             count++;
         }
-        if (__any(count >= (uint32_t)kQueueCap)) drain_filtered<ROWS_IN_LDS>(spheres, planes_off, n_padded, queue, lane, count, r, a, tmin, closest, best_k);
+        if (__any(count >= (uint32_t)kQueueCap)) drain_filtered<ROWS_IN_LDS>(spheres, planes_off, n_padded, queue, lane, count, r, a, tmin, closest, best_k SS_PASS);
     }
-    drain_filtered<ROWS_IN_LDS>(spheres, planes_off, n_padded, queue, lane, count, r, a, tmin, closest, best_k);
+    drain_filtered<ROWS_IN_LDS>(spheres, planes_off, n_padded, queue, lane, count, r, a, tmin, closest, best_k SS_PASS);
     if (best_k == kNone) return false;
     best.t = closest;
     best.ref = make_ref(REF_SPHERE, best_k);
@@ -3103,12 +3148,26 @@ __global__ __launch_bounds__(T::BLOCK, T::MIN_WAVES) void render_kernel(DeviceSc
             if (boost) todo = overdue;
             if (!boost && a.pixels_per_wave >= 64 && __popcll(live) >= a.coop_threshold) {
                 PH_BEGIN();
+#if RT_PHASES
+                ScanSums ss{};
+#endif
                 if (active) hit = a.exact_scan    ? scan_uniform(sc, queue, lane, ray, 0.001, DBL_MAX, h)
-                                 : a.filter_fp64 ? (sv.in_lds ? scan_filtered<true>(sc, sv.planes_off, sv.n_padded, queue, lane, ray, 0.001, DBL_MAX, h)
-                                                              : scan_filtered<false>(sc, 0u, 0u, queue, lane, ray, 0.001, DBL_MAX, h))
-                                 : sv.in_lds     ? scan_filtered32<true>(sc, sv.planes_off, sv.n_padded, queue, lane, ray, 0.001, DBL_MAX, h)
-                                                 : scan_filtered32<false>(sc, 0u, 0u, queue, lane, ray, 0.001, DBL_MAX, h);
+                                 : a.filter_fp64 ? (sv.in_lds ? scan_filtered<true>(sc, sv.planes_off, sv.n_padded, queue, lane, ray, 0.001, DBL_MAX, h SS_PASS)
+                                                              : scan_filtered<false>(sc, 0u, 0u, queue, lane, ray, 0.001, DBL_MAX, h SS_PASS))
+                                 : sv.in_lds     ? scan_filtered32<true>(sc, sv.planes_off, sv.n_padded, queue, lane, ray, 0.001, DBL_MAX, h SS_PASS)
+                                                 : scan_filtered32<false>(sc, 0u, 0u, queue, lane, ray, 0.001, DBL_MAX, h SS_PASS);
                 PH_END(0, active);
+#if RT_PHASES
+                {  // the scan ran in the active lanes only: take the (wave-uniform) sums from the first of them
+                    const int src = __ffsll((long long)__ballot(active)) - 1;
+                    if (src >= 0) {
+                    const auto rl = [src](uint32_t v) { return (unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)v, src); };
+                    ph.n[12] += rl(ss.groups);  ph.l[12] += rl(ss.taken);        ph.t[12] += rl(ss.spheres);
+                    ph.n[13] += rl(ss.appends); ph.l[13] += rl(ss.behind);       ph.t[13] += rl(ss.drain_cycles);
+                    ph.n[15] += rl(ss.drains);  ph.l[15] += rl(ss.drain_iters);
+                    }
+                }
+#endif
             } else {
                 PH_BEGIN();
                 if (sv.in_lds && !a.coop_single) scan_grouped(sv, lane, todo, ray, 0.001, DBL_MAX, h, hit);
