@@ -378,6 +378,37 @@ int rt_film_bind_pixels(rt_film *film, void *device_pixels)
     return RT_OK;
 }
 
+// Does every hit of this launch lie inside its leaf's box?  The library's own search structures -- its SAH tree, the scan of
+// all leaves of a small BVH world, the segmented walk, RT_FLAG_ACCELERATE_LISTS, the thin-wave scan -- meet the leaves in
+// another order than the reference's tree, and find the reference's closest hit only because (1) no leaf they search draws
+// random numbers and (2) no hit lies outside its leaf's box, where the reference's tree would cull it.  A moving sphere
+// leaves its box (c0 .. c1) at ray times outside its own [time0, time1] (R/MovingSphere.h:51 does not clamp frac), so
+// the camera's shutter decides, per launch.  The ray times are those of render.hip camera_ray, time0 + u * (time1 - time0),
+// with u = xorwow_uniform in [2^-33, 1] (monotone in u; the fast build fuses the multiply-add); frac is (tm - t0) / dt as in
+// msphere_center, which a unit-time row evaluates as tm itself -- the same value.
+static bool hits_stay_in_boxes(const FlatScene &f, const CameraRec &cam, int variant)
+{
+    if (f.ms_nonfinite) return false;
+    if (f.ms_intervals.empty()) return true;
+    const double span = cam.time1 - cam.time0;
+    double tm[2];
+    const double u[2] = {(double)0x1p-33f, 1.0};
+    for (int k = 0; k < 2; k++) {
+        if (variant) {
+            tm[k] = std::fma(u[k], span, cam.time0);
+        } else {
+            volatile double prod = u[k] * span;  // no contraction: the strict build's two roundings
+            tm[k] = cam.time0 + prod;
+        }
+    }
+    for (const MsInterval &iv : f.ms_intervals)
+        for (double t : tm) {
+            const double frac = (t - iv.t0) / iv.dt;
+            if (!(frac >= 0.0 && frac <= 1.0)) return false;  // (NaN too)
+        }
+    return true;
+}
+
 // Everything rt_render_launch puts on the stream: seeding, the rehearsal and its bookkeeping, the render kernel, the
 // counter copy.  Called with the film already marked in flight (a failure half-way leaves kernels running).
 static int enqueue_frame(SceneImpl &s, FilmImpl &f, const rt_render_params *p, hipStream_t stream)
@@ -459,13 +490,20 @@ static int enqueue_frame(SceneImpl &s, FilmImpl &f, const rt_render_params *p, h
     ra.accelerate_lists = (p->flags & RT_FLAG_ACCELERATE_LISTS) ? 1 : 0;
     ra.filter_fp64 = (p->flags & RT_FLAG_FILTER_FP64) ? 1 : 0;
     ra.small_world = 64;  // scan budget in half sphere tests, see FlatScene::scan_cost
+    // a launch whose hits may leave their boxes takes the reference's tree in the reference's order (hits_stay_in_boxes)
+    const bool in_boxes = hits_stay_in_boxes(s.flat, s.camera, p->variant);
+    if (!in_boxes) {
+        ra.reference_tree = 1;    // no library tree, no segmented walk
+        ra.always_walk = 1;       // no scan of a small BVH world's leaves
+        ra.accelerate_lists = 0;
+    }
     const DeviceScene &ds = s.device[f.device]->scene;
     HIP_TRY(p->variant ? kernel_info_fast(ds, ra, &f.last_kernel) : kernel_info_strict(ds, ra, &f.last_kernel));
     const int kind = f.last_kernel.kind & 63;
     // BVH sphere worlds: thin waves may scan all leaves together instead of walking (scan_grouped_ms), but the planes
     // come from L2 and a chip full of thin waves scanning is bound by L2 bandwidth: measured slower than walking at every
     // threshold (C3: 1748 Msamples/s never, 1681 at 17, 1048 at 33).  Off unless asked for.
-    if (kind < 8 && p->coop_threshold <= 0) ra.coop_threshold = 0;
+    if (kind < 8 && (p->coop_threshold <= 0 || !in_boxes)) ra.coop_threshold = 0;
     // A pixel's samples are one sequential chain (one RNG stream), so a frame cannot end before its longest pixel does
     // (glass: up to max_depth rays per sample).  One rehearsal of the first samples of every pixel -- the same RNG streams,
     // nothing written but ray counts, cost probe_spp / spp of the frame -- serves two schedulers:

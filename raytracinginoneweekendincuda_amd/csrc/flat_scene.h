@@ -108,7 +108,10 @@ constexpr uint32_t kTreeObjBit = 0x80000000u;  // HitInfo::obj of a hit inside a
 struct BvhNodeRec { double xlo, xhi, ylo, yhi, zlo, zhi; uint32_t a, b, escape, pad; };
 
 // The library's own tree for BVH worlds of primitives only.  Such a world's closest hit does not depend on how it is
-// searched (no leaf draws random numbers: the reference's BVH == list invariant, Docs 2-3 BVH :733,:772), so instead of
+// searched -- the reference's BVH == list invariant, Docs 2-3 BVH :733,:772 -- as long as two things hold: no leaf draws
+// random numbers, and every hit lies inside its leaf's box.  The second fails for a moving sphere at a ray time outside its
+// own [time0, time1] (R/MovingSphere.h:51 does not clamp), so a launch whose shutter allows that walks the reference's tree
+// instead (device_scene.cpp hits_stay_in_boxes).  Where both hold, instead of
 // the reference's median-split tree in its fixed visiting order (36 node visits and 5 leaf tests per ray on the random-
 // spheres scene) the kernel may walk a surface-area-heuristic tree near child first.  Still a stackless walk over a flat
 // array: every node carries, for each of the eight sign octants of the ray direction, the node to go to when its box is hit
@@ -131,7 +134,8 @@ constexpr uint32_t kFastBottom = 0x8000u;    // hit link of a bottom node: this 
 constexpr uint32_t kFastMaxNodes = 0x8000u;  // node indices stay below kFastBottom
 
 // The same tree over the SURFACE leaves of a BVH world that also holds ConstantMedium leaves (the Book-2 final scene: 400
-// boxes, spheres, an instanced cluster, and two media).  Only a medium's test draws random numbers, so only for the media
+// boxes, spheres, an instanced cluster, and two media).  Only a medium's test draws random numbers (and hits stay inside
+// their boxes, as above: otherwise the launch takes the reference's tree), so only for the media
 // does it matter what the reference has found before it reaches them: the closest hit among the leaves that PRECEDE the
 // medium in the reference's fixed visiting order (world_items order; the BVH only prunes).  The surfaces between two
 // media are one segment whose closest hit may be searched in any order.  A ray therefore walks the library's tree once

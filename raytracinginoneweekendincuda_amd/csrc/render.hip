@@ -3178,6 +3178,8 @@ __global__ __launch_bounds__(T::BLOCK, T::MIN_WAVES) void render_kernel(DeviceSc
         bool thin = false;
         if constexpr (T::WORLD == 0 && !T::COMPOSITE) {
             // Frame tail of a sphere world: the queue is dry and few lanes are left -- scan instead of walking (scan_grouped_ms).
+            // The same closest hit as the walk: no leaf draws random numbers, and the launcher sets coop_threshold = 0 where a
+            // hit could lie outside its leaf's box (a moving sphere at a ray time outside its interval: hits_stay_in_boxes).
             thin = sc.ms_planes != nullptr && exhausted && __popcll(live) < a.coop_threshold;
             if (thin) {
                 PH_BEGIN();
@@ -3601,8 +3603,9 @@ using TBvhSegmented = Traits<0, true, true, 3, true, true, false, 768, true>;
 // List scans over primitives / instances without media or table-walking textures.  Also the BVH worlds of small
 // scenes: for up to 16 leaves within a cost budget (FlatScene::scan_cost) a scan of all of them in the tree's leaf order -- every lane on the same leaf, rows
 // through uniform loads, no node visits, no phases -- beats walking the tree (Cornell box: 8 leaves, 7 nodes).  Without
-// media no leaf draws random numbers, so the closest hit is the one the walk finds (the reference's own BVH = list
-// invariant; `tests/test_parity_gpu.py::test_small_world_scan_equals_the_bvh_walk`).
+// media no leaf draws random numbers, and as long as every hit lies inside its leaf's box (a moving sphere leaves its box at
+// ray times outside its own interval: the launcher then walks, device_scene.cpp hits_stay_in_boxes), the closest hit is the
+// one the walk finds (the reference's own BVH = list invariant; `tests/test_parity_gpu.py::test_small_world_scan_equals_the_bvh_walk`).
 // General nesting (REF_TREE leaves, tree_hit): the general kernels plus the interpreter.  Its stack of 16 frames lives in
 // scratch -- the reference's own recursion needs a 32 KiB stack per thread (R/kernel.cu:599) -- so these instantiations
 // are only ever launched for scenes that nest objects beyond what ObjectRec expresses (none of the ten built-in scenes).

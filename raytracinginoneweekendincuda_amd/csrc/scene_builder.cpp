@@ -290,6 +290,20 @@ static bool has_coincident_primitives(const SceneImpl &s, const std::vector<uint
     return false;
 }
 
+// A moving sphere whose centre moves lies outside its bounding box (c0 .. c1, R/MovingSphere.h) at ray times outside its own
+// [time0, time1]: R/MovingSphere.h:51 does not clamp frac.  Which of such hits a tree culls then depends on the tree, so no
+// tree of the library's own may stand in for a list that holds one -- commit does not know the shutter.
+static bool has_moving_centre(const SceneImpl &s, const std::vector<uint32_t> &handles)
+{
+    for (uint32_t hnd : handles) {
+        const HostHittable &h = s.hittables[hnd - 1];
+        if (h.kind != HKind::MovingSphere) continue;
+        const D3 dc = sub(h.c1, h.c0);
+        if (dc.x != 0.0 || dc.y != 0.0 || dc.z != 0.0) return true;  // (NaN too)
+    }
+    return false;
+}
+
 struct Flattener {
     SceneImpl &s;
     FlatScene &f;
@@ -605,9 +619,11 @@ struct Flattener {
                 all_q &= k == HKind::Quad;
             }
             obj.count = (uint32_t)prims.size();
-            if (prims.size() >= kSubBvhMinPrims && !has_coincident_primitives(s, prims)) {
+            if (prims.size() >= kSubBvhMinPrims && !has_coincident_primitives(s, prims) && !has_moving_centre(s, prims)) {
                 // A closest-hit scan and a BVH over the same primitives return the same hit (the reference's own
-                // invariant, Docs 2-3 BVH :733,:772); primitives draw no random numbers, so nothing else changes.
+                // invariant, Docs 2-3 BVH :733,:772) when two things hold: primitives draw no random numbers, and every hit
+                // lies inside its primitive's box.  A moving sphere breaks the second at ray times outside its interval
+                // (has_moving_centre): such a group stays a list scanned in order, as the reference's HittableList does.
                 HostHittable sub{};
                 sub.kind = HKind::Bvh;
                 std::vector<uint32_t> objs = prims;
@@ -1169,6 +1185,20 @@ int flatten_scene(SceneImpl &s)
         bool unit_time = !f.mspheres.empty();
         for (const MSphereGeom &m : f.mspheres) unit_time &= (m.t0 == 0.0 && m.dt == 1.0);
         if (unit_time) f.flags |= SCENE_MS_UNIT_TIME;
+        // The rows whose hits may leave their boxes, for the launcher's test of the shutter (FlatScene::ms_intervals).  A row
+        // with dc == 0 is where its box is at every time; one with dt == 0 has a centre of inf / NaN and is never hit.
+        for (const MSphereGeom &m : f.mspheres) {
+            if ((m.dcx == 0.0 && m.dcy == 0.0 && m.dcz == 0.0) || m.dt == 0.0) continue;
+            const double v[8] = {m.c0x, m.c0y, m.c0z, m.dcx, m.dcy, m.dcz, m.t0, m.dt};
+            bool finite = true;
+            for (double x : v) finite &= std::isfinite(x);
+            if (finite) f.ms_intervals.push_back({m.t0, m.dt});
+            else f.ms_nonfinite = true;
+        }
+        auto before = [](const MsInterval &a, const MsInterval &b) { return a.t0 < b.t0 || (a.t0 == b.t0 && a.dt < b.dt); };
+        auto same = [](const MsInterval &a, const MsInterval &b) { return a.t0 == b.t0 && a.dt == b.dt; };
+        std::sort(f.ms_intervals.begin(), f.ms_intervals.end(), before);
+        f.ms_intervals.erase(std::unique(f.ms_intervals.begin(), f.ms_intervals.end(), same), f.ms_intervals.end());
         // A BVH world of nothing but spheres and unit-time moving spheres: thin waves scan all of them together instead of
         // walking (order-independent: no leaf draws random numbers).  The planes hold the leaves in leaf order, a static
         // sphere as a moving one that does not move (c0 + t * 0 = c0 exactly; not done when a centre component is -0.0).

@@ -56,6 +56,10 @@ struct HostTexture {
     uint32_t a = 0, b = 0;  // checker: even/odd handles; image: image index; noise: perlin index
 };
 
+struct MsInterval {
+    double t0, dt;
+};
+
 struct FlatScene {
     std::vector<SphereGeom> spheres;
     std::vector<SphereScanRow> sphere_scan;  // parallel to spheres
@@ -96,6 +100,11 @@ struct FlatScene {
     uint32_t flags = 0;
     uint32_t n_world_nodes = 0;
     uint32_t scan_cost = 0;  // cost of testing every world leaf once (scene_builder.cpp), for the scan-or-walk choice
+    // Moving-sphere rows whose centre moves (dc != 0) over an interval of non-zero length (dt != 0): their distinct (t0, dt).
+    // The launcher checks them against the camera's shutter (device_scene.cpp hits_stay_in_boxes); ms_nonfinite: such a
+    // row has a non-finite centre, motion or interval, and no shutter keeps it inside its box.
+    std::vector<MsInterval> ms_intervals;
+    bool ms_nonfinite = false;
 };
 
 struct DeviceTables;  // device_scene.cpp

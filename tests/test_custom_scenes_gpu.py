@@ -223,14 +223,15 @@ def test_coincident_primitives_resolve_like_the_reference(world_kind):
 
 
 # ---- the segmented walk of deep composite worlds with media (flat_scene.h FastOrder / SegMedium, render.hip seg_advance) ----
-def _deep_media_world(media):
+def _deep_media_world(media, motion=(0.0, 1.0), shutter=(0.0, 1.0)):
     """~110 leaves under one BvhNode: a field of plain boxes, spheres of every material, instanced boxes, an instanced cluster of
     40 spheres (sub-BVH + cooperative scan), and ConstantMedium leaves as `media` names them:
       mist    a sphere of radius 60 around everything, camera included (sorted first by the reference's build)
       ball    a small glass ball with fog inside, in the middle of the field
       crate   a rotated, translated box of smoke (boundary = six quads behind two transforms)
       far     a ball of fog behind the camera's far wall that hardly any ray's line meets
-      lone    (extra leaves arranged so that one medium ends up alone in a span-1 node: hit twice)"""
+      lone    (extra leaves arranged so that one medium ends up alone in a span-1 node: hit twice)
+    `motion`: (time0, time1) of its moving sphere; `shutter`: the camera's (time0, time1) (tests/test_motion_time_gpu.py)."""
     def build(s, Rng):
         rng = Rng(7)
         u = rng.uniform
@@ -243,7 +244,7 @@ def _deep_media_world(media):
         mats = [s.Lambertian((0.7, 0.2, 0.2)), s.Metal((0.8, 0.8, 0.9), 0.1), s.Dielectric(1.5), s.DiffuseLight((3.0, 3.0, 2.5))]
         for k in range(16):
             items.append(s.Sphere((-7.0 + 0.95 * k, 0.8 + 0.6 * u(), -6.0 + 12.0 * u()), 0.3 + 0.25 * u(), mats[k % 4]))
-        items.append(s.MovingSphere((3.0, 1.5, 1.0), (3.0, 2.0, 1.0), 0.0, 1.0, 0.5, mats[0]))
+        items.append(s.MovingSphere((3.0, 1.5, 1.0), (3.0, 2.0, 1.0), motion[0], motion[1], 0.5, mats[0]))
         items.append(s.Quad((-4.0, 6.0, -4.0), (8.0, 0, 0), (0, 0, 8.0), s.DiffuseLight((4.0, 4.0, 4.0))))
         for k in range(4):
             box = s.MakeBox((0, 0, 0), (0.9, 1.6 + 0.3 * k, 0.9), white)
@@ -270,7 +271,7 @@ def _deep_media_world(media):
         for extra in range(media.count("more")):   # more media than the segmented walk handles: the reference-order kernel takes over
             items.append(s.ConstantMedium(s.Sphere((-6.0 + 3.0 * extra, 3.0, -3.0), 0.5, s.Dielectric(1.5)), 0.8, (0.3, 0.9, 0.3)))
         s.SetWorld(s.BvhNode(items))
-        s.Camera((12.0, 6.0, 14.0), (0.0, 0.5, 0.0), (0, 1, 0), 38.0, W / H, 0.05, 18.0, 0.0, 1.0, (0.35, 0.45, 0.7))
+        s.Camera((12.0, 6.0, 14.0), (0.0, 0.5, 0.0), (0, 1, 0), 38.0, W / H, 0.05, 18.0, shutter[0], shutter[1], (0.35, 0.45, 0.7))
         s.Commit()
     return build
 
