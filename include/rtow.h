@@ -227,7 +227,8 @@ typedef struct rt_render_stats {
     uint32_t rows;                /* rows owned by this rank */
     uint32_t kernel_vgprs;
     uint32_t lds_bytes;
-    uint32_t kernel_kind;         /* which instantiation ran: world*4 + composite*2 + rich (world 0 bvh, 1 list, 2 sphere list) */
+    uint32_t kernel_kind;         /* which instantiation ran: world*8 + media*4 + composite*2 + rich (world 0 bvh, 1 list, 2 sphere
+                                     list) + nested*32 + library-tree*64 + grouped*128 + segmented*256 (launch_one, csrc/render.hip) */
     uint32_t pixels_per_wave;     /* what rt_render_params.pixels_per_wave came to for this launch (64 = one lane per ray) */
 } rt_render_stats;
 
