@@ -219,7 +219,7 @@ typedef struct rt_render_params {
                                       the 8x8 tiles by rays traced and the heaviest start first; the image is the same either way) */
 
 typedef struct rt_render_stats {
-    uint64_t samples;             /* pixels rendered by this rank x spp */
+    uint64_t samples;             /* samples this launch took: pixels rendered by this rank x spp, fewer with adaptive sampling */
     uint64_t rays;                /* RayColor loop iterations (one world Hit each) */
     double seconds_seed;          /* RNG seeding kernel, HIP events */
     double seconds_render;        /* render kernel, HIP events */
@@ -228,7 +228,8 @@ typedef struct rt_render_stats {
     uint32_t kernel_vgprs;
     uint32_t lds_bytes;
     uint32_t kernel_kind;         /* which instantiation ran: world*8 + media*4 + composite*2 + rich (world 0 bvh, 1 list, 2 sphere
-                                     list) + nested*32 + library-tree*64 + grouped*128 + segmented*256 (launch_one, csrc/render.hip) */
+                                     list) + nested*32 + library-tree*64 + grouped*128 + segmented*256 + adaptive*512 (launch_one,
+                                     csrc/render.hip) */
     uint32_t pixels_per_wave;     /* what rt_render_params.pixels_per_wave came to for this launch (64 = one lane per ray) */
 } rt_render_stats;
 
@@ -244,6 +245,45 @@ RTOW_API void *rt_film_device_pixels(rt_film *film);
  * rt_film_pixel_bytes() bytes on the film's device.  NULL restores the film's own buffer. */
 RTOW_API int rt_film_bind_pixels(rt_film *film, void *device_pixels);
 RTOW_API size_t rt_film_pixel_bytes(rt_film *film);
+
+/* ---- adaptive sampling: "render until the noise is below a threshold, at most samples_per_pixel samples" ----
+ * Per pixel the film keeps, next to the colour sum (r, g, b): n = samples taken so far in this frame, and q = the sum over those
+ * samples of y^2, y = (r_s + g_s) + b_s the plain sum of the three channels of sample s's radiance.  The rule is looked at
+ * exactly when n >= min_samples and (n - min_samples) % check_interval == 0, and a pixel stops at the first such n where, with
+ * N = (double)n and s = (r + g) + b:
+ *     lhs = q*N - s*s;   m = max(s, luminance_floor*N);   rhs = ((tau*tau)*(N - 1))*(m*m);   stops <=> lhs <= rhs
+ * (a NaN anywhere: it goes on) -- "standard error of the mean of y <= tau * max(mean of y, luminance_floor)" without divisions
+ * or roots, every operation an IEEE-754 double operation in this order, never fused (the strict and the fast build alike).  A pixel that never stops ends at the
+ * launch's samples_per_pixel, which is the cap.  Its value is sqrt(sum / n) with its OWN n: pixel for pixel the frame a plain
+ * render of n samples gives.  The rule stops too early where light is found rarely (a pixel whose first min_samples samples
+ * all miss a small lamp has q = s = 0): min_samples is the guard.  noise_threshold = 0 is accepted but decides pixels of equal
+ * samples by rounding noise; use >= 1e-3, and NULL for "never stop early".
+ * Accumulated frames (RT_FLAG_KEEP_RNG_STATE | RT_FLAG_ACCUMULATE): n, q and the stopped mark persist like the sums;
+ * samples_per_pixel is then the most ADDITIONAL samples a pixel takes, check points count on the pixel's total n (k launches of S
+ * are one launch of k*S), a stopped pixel is never touched again.  Changing the setting between two launches of one accumulated
+ * frame makes the second rt_render_launch return RT_ERR_STATE; a re-seeding launch begins a new frame.  A launch without
+ * RT_FLAG_ACCUMULATE, adaptive or not, ends an accumulated adaptive frame the film held (it overwrites the stopped pixels, which
+ * nothing would write again).  A stopped pixel lives only in the buffer that was bound when it stopped: after
+ * rt_film_bind_pixels to another buffer in the middle of such a frame the new buffer lacks the pixels that had stopped before. */
+typedef struct rt_adaptive_params {
+    int32_t min_samples, check_interval;      /* >= 2, >= 1 */
+    double noise_threshold, luminance_floor;  /* tau >= 0, floor > 0 (0.01 is a good one) */
+} rt_adaptive_params;
+/* NULL = off (default).  Takes effect at the next launch.  RT_ERR_INVALID for parameters out of range,
+ * RT_ERR_STATE while a launch on the film is in flight. */
+RTOW_API int rt_film_set_adaptive(rt_film *film, const rt_adaptive_params *params);
+/* Samples each pixel has had so far in this frame, full W x H, pixel (i,j) at j*W+i like rt_film_download;
+ * pixels this rank does not own are 0.  Without adaptive: the frame's spp everywhere (0 before the first launch). */
+RTOW_API int rt_film_download_sample_counts(rt_film *film, uint32_t *counts_full, int width, int height);
+/* The rule above on the host, the same source the kernel compiles: 1 = a pixel with these sums stops at n,
+ * 0 = it goes on (n below min_samples or not a check point included); -RT_ERR_INVALID for parameters out of range. */
+RTOW_API int rt_adaptive_converged(const rt_adaptive_params *p, uint32_t n, double sum_r, double sum_g,
+                                   double sum_b, double sum_y2);
+/* Introspection for tests: the rule as the adaptive render kernels of one build compile it (variant 0 strict, 1 fast), run on
+ * the device over `count` entries: q_out[k] = sums_rgbq[4k+3] + y^2 with y = the plain sum of sample_rgb[3k..3k+2], and
+ * stops_out[k] = the rule on (n[k], sums_rgbq[4k], [4k+1], [4k+2], q_out[k]).  Host arrays in and out. */
+RTOW_API int rt_adaptive_rule_on_device(int device, int variant, const rt_adaptive_params *p, uint32_t count, const uint32_t *n,
+                                        const double *sums_rgbq, const double *sample_rgb, double *q_out, uint8_t *stops_out);
 
 /* Upload the committed scene to a device (idempotent per device). */
 RTOW_API int rt_scene_upload(rt_scene *s, int device);

@@ -22,6 +22,9 @@ from .api import (  # noqa: F401
     jpeg_decode,
     library_path,
     lib,
+    AdaptiveParams,
+    adaptive_converged,
+    adaptive_rule_on_device,
     FLAG_KEEP_RNG_STATE,
     FLAG_FORCE_GENERAL,
     FLAG_OVERDUE_PRIORITY,
@@ -35,4 +38,5 @@ __all__ = [
     "RtowError", "Rng", "Scene", "Film", "RenderParams", "RenderStats", "builtin_scene",
     "stripe_rows", "deinterleave", "write_ppm", "write_ppm_binary", "write_pfm", "rtwimage_bytes", "load_image", "library_path", "lib",
     "FLAG_KEEP_RNG_STATE", "FLAG_FORCE_GENERAL", "FLAG_OVERDUE_PRIORITY", "FLAG_ACCUMULATE", "FLAG_ROW_MAJOR_TILES", "FLAG_ALWAYS_WALK",
+    "AdaptiveParams", "adaptive_converged", "adaptive_rule_on_device",
 ]

@@ -24,6 +24,11 @@ class RenderStats(C.Structure):
     ]
 
 
+class AdaptiveParams(C.Structure):
+    _fields_ = [("min_samples", C.c_int32), ("check_interval", C.c_int32), ("noise_threshold", C.c_double),
+                ("luminance_floor", C.c_double)]
+
+
 class SceneInfo(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in (
         "world_kind", "n_leaves", "n_nodes", "n_spheres", "n_moving_spheres", "n_quads", "n_objects", "n_xforms",
@@ -96,6 +101,10 @@ SIGNATURES = {
     "rt_render_launch": (I, [P, P, C.POINTER(RenderParams)]),
     "rt_render_finish": (I, [P, P, C.POINTER(RenderStats)]),
     "rt_film_download": (I, [P, D3, I, I]),
+    "rt_film_set_adaptive": (I, [P, C.POINTER(AdaptiveParams)]),
+    "rt_film_download_sample_counts": (I, [P, C.POINTER(C.c_uint32), I, I]),
+    "rt_adaptive_converged": (I, [C.POINTER(AdaptiveParams), C.c_uint32, D, D, D, D]),
+    "rt_adaptive_rule_on_device": (I, [I, I, C.POINTER(AdaptiveParams), C.c_uint32, C.POINTER(C.c_uint32), D3, D3, D3, C.POINTER(C.c_uint8)]),
     "rt_deinterleave": (I, [D3, I, I, I, I, C.c_size_t, D3]),
     "rt_render": (I, [P, C.POINTER(RenderParams), D3, C.POINTER(RenderStats)]),
     "rt_write_ppm": (I, [C.c_char_p, D3, I, I]),

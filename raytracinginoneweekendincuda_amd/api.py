@@ -11,7 +11,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import RenderParams, RenderStats, SceneInfo  # noqa: F401
+from ._lib import AdaptiveParams, RenderParams, RenderStats, SceneInfo  # noqa: F401
 
 
 class RtowError(RuntimeError):
@@ -247,7 +247,20 @@ class Scene:
 
     # ---- one-call render on one GPU ----
     def render(self, width, height, spp, max_depth=50, seed=1984, variant=0, device=0, flags=0, coop_threshold=0,
-               overdue=0, shade_batch=0, max_blocks_per_cu=0, pixels_per_wave=0):
+               overdue=0, shade_batch=0, max_blocks_per_cu=0, pixels_per_wave=0, adaptive=None):
+        """``adaptive``: None, or the arguments of ``Film.set_adaptive`` as a tuple / dict -- ``spp`` is then the most
+        samples a pixel takes, and the stats carry the per-pixel counts as ``sample_counts`` ((H, W) uint32)."""
+        if adaptive is not None:
+            film = Film(width, height, device=device)
+            if isinstance(adaptive, dict):
+                film.set_adaptive(**adaptive)
+            else:
+                film.set_adaptive(*adaptive)
+            st = film.render(self, spp, max_depth=max_depth, seed=seed, variant=variant, flags=flags, coop_threshold=coop_threshold,
+                             overdue=overdue, shade_batch=shade_batch, max_blocks_per_cu=max_blocks_per_cu,
+                             pixels_per_wave=pixels_per_wave)
+            st.sample_counts = film.sample_counts()
+            return film.download(), st
         p = RenderParams(width, height, spp, max_depth, seed, 8, 0, 1, variant, device, flags, None, coop_threshold, overdue,
                          shade_batch, max_blocks_per_cu, pixels_per_wave, 0)
         frame = np.zeros((height, width, 3), dtype=np.float64)
@@ -315,6 +328,48 @@ class Film:
         frame = np.zeros((self.height, self.width, 3), dtype=np.float64)
         _check(lib().rt_film_download(self._p, frame.ctypes.data_as(_lib.D3), self.width, self.height))
         return frame
+
+    def set_adaptive(self, min_samples=None, check_interval=None, noise_threshold=None, luminance_floor=0.01):
+        """Adaptive sampling for the launches that follow (include/rtow.h rt_film_set_adaptive): a pixel stops at the first
+        check point -- min_samples, then every check_interval samples -- where the standard error of its mean is at most
+        noise_threshold x max(mean, luminance_floor); the launch's spp is the cap.  ``set_adaptive(None)`` turns it off."""
+        if min_samples is None:
+            _check(lib().rt_film_set_adaptive(self._p, None))
+            return
+        p = AdaptiveParams(int(min_samples), int(check_interval), float(noise_threshold), float(luminance_floor))
+        _check(lib().rt_film_set_adaptive(self._p, C.byref(p)))
+
+    def sample_counts(self):
+        """Samples every pixel has had so far in this frame, (H, W) uint32, row 0 = bottom like ``download``; 0 in rows of
+        other ranks.  Without adaptive sampling: the frame's spp everywhere."""
+        counts = np.zeros((self.height, self.width), dtype=np.uint32)
+        _check(lib().rt_film_download_sample_counts(self._p, counts.ctypes.data_as(C.POINTER(C.c_uint32)), self.width, self.height))
+        return counts
+
+
+def adaptive_rule_on_device(n, sums_rgbq, sample_rgb, min_samples, check_interval, noise_threshold, luminance_floor=0.01, variant=0, device=0):
+    """Tests: the rule as the adaptive render kernels of a build (variant 0 strict, 1 fast) compile it, run on the GPU over arrays
+    (rt_adaptive_rule_on_device).  Returns (q + y^2 of the sample, stops) for n (k,), sums_rgbq (k, 4), sample_rgb (k, 3)."""
+    n = np.ascontiguousarray(n, dtype=np.uint32)
+    sums = np.ascontiguousarray(sums_rgbq, dtype=np.float64)
+    sample = np.ascontiguousarray(sample_rgb, dtype=np.float64)
+    assert sums.shape == (n.size, 4) and sample.shape == (n.size, 3)
+    q_out, stops = np.zeros(n.size, dtype=np.float64), np.zeros(n.size, dtype=np.uint8)
+    p = AdaptiveParams(int(min_samples), int(check_interval), float(noise_threshold), float(luminance_floor))
+    _check(lib().rt_adaptive_rule_on_device(device, variant, C.byref(p), n.size, n.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                            sums.ctypes.data_as(_lib.D3), sample.ctypes.data_as(_lib.D3), q_out.ctypes.data_as(_lib.D3),
+                                            stops.ctypes.data_as(C.POINTER(C.c_uint8))))
+    return q_out, stops.astype(bool)
+
+
+def adaptive_converged(n, sum_r, sum_g, sum_b, sum_y2, min_samples, check_interval, noise_threshold, luminance_floor=0.01):
+    """The stopping rule on the host, from the source the kernel compiles (rt_adaptive_converged): does a pixel with colour
+    sums (sum_r, sum_g, sum_b) and sum of squared sample sums sum_y2 stop at n samples?"""
+    p = AdaptiveParams(int(min_samples), int(check_interval), float(noise_threshold), float(luminance_floor))
+    rc = lib().rt_adaptive_converged(C.byref(p), int(n), float(sum_r), float(sum_g), float(sum_b), float(sum_y2))
+    if rc < 0:
+        raise RtowError(f"status {-rc}: {_err()}")
+    return bool(rc)
 
 
 def rtwimage_bytes(decoded_rgb):

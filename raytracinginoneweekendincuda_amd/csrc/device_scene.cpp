@@ -103,7 +103,7 @@ struct FilmImpl {
     double *accum = nullptr;       // progressive rendering: unnormalised colour sums (allocated on first use)
     int accum_spp = 0;
     uint32_t *state = nullptr;
-    unsigned long long *ray_counter = nullptr;  // [0] rays, [1] / [6] / [9] low words = tile / heavy / super queue cursors, [7] and [32..119] phase sums
+    unsigned long long *ray_counter = nullptr;  // [0] rays, [2] samples taken (adaptive sampling), [1] / [6] / [9] low words = tile / heavy / super queue cursors, [7] and [32..119] phase sums
     int num_cus = 256;
     hipStream_t own_stream = nullptr;
     hipStream_t last_stream = nullptr;
@@ -122,7 +122,35 @@ struct FilmImpl {
     int last_variant = 0;
     KernelInfo last_kernel{};
     int last_pixels_per_wave = 64;
+    // adaptive sampling (rt_film_set_adaptive; adaptive_rule.h): the setting for the next launch, the setting the accumulated
+    // frame in progress was begun with, and the per-pixel planes (allocated on first use): samples so far, sum of y^2, stopped
+    bool adaptive = false, frame_adaptive = false, last_adaptive = false;
+    AdaptiveRule rule{}, frame_rule{};
+    uint32_t *ad_n = nullptr;
+    double *ad_q = nullptr;
+    uint8_t *ad_mark = nullptr;
+    bool rendered = false;
+    int frame_spp = 0;  // without adaptive: samples every owned pixel has had in the frame the film holds
 };
+
+static bool same_rule(const AdaptiveRule &a, const AdaptiveRule &b)
+{
+    return a.min_samples == b.min_samples && a.check_interval == b.check_interval && a.noise_threshold == b.noise_threshold &&
+           a.luminance_floor == b.luminance_floor;
+}
+
+static bool rule_in_range(const rt_adaptive_params &p)
+{
+    return p.min_samples >= 2 && p.check_interval >= 1 && p.noise_threshold >= 0.0 && std::isfinite(p.noise_threshold) &&
+           p.luminance_floor > 0.0 && std::isfinite(p.luminance_floor);  // (comparisons with a NaN are false)
+}
+static AdaptiveRule to_rule(const rt_adaptive_params &p) { return AdaptiveRule{p.min_samples, p.check_interval, p.noise_threshold, p.luminance_floor}; }
+
+// Does this launch add to the accumulated frame the film holds (as opposed to beginning a frame)?
+static bool continues_frame(const FilmImpl &f, const rt_render_params *p)
+{
+    return (p->flags & RT_FLAG_ACCUMULATE) && (p->flags & RT_FLAG_KEEP_RNG_STATE) && f.seeded && f.accum && f.accum_spp > 0;
+}
 
 // a launch of `s` into `f` is (about to be) in flight / is over
 static void mark_in_flight(SceneImpl &s, FilmImpl &f)
@@ -361,6 +389,9 @@ void rt_film_destroy(rt_film *film)
     if (f->heavy_count) hipFree(f->heavy_count);
     if (f->super_list) hipFree(f->super_list);
     if (f->pix_class) hipFree(f->pix_class);
+    if (f->ad_n) hipFree(f->ad_n);
+    if (f->ad_q) hipFree(f->ad_q);
+    if (f->ad_mark) hipFree(f->ad_mark);
     if (f->host_counters) hipHostFree(f->host_counters);
     for (int k = 0; k < 4; k++)
         if (f->ev[k]) hipEventDestroy(f->ev[k]);
@@ -414,6 +445,7 @@ static bool hits_stay_in_boxes(const FlatScene &f, const CameraRec &cam, int var
 static int enqueue_frame(SceneImpl &s, FilmImpl &f, const rt_render_params *p, hipStream_t stream)
 {
     const bool keep = (p->flags & RT_FLAG_KEEP_RNG_STATE) && f.seeded;
+    const bool continues = continues_frame(f, p);
 
     HIP_TRY(hipMemsetAsync(f.ray_counter, 0, kCounterWords * sizeof(unsigned long long), stream));
     HIP_TRY(hipEventRecord(f.ev[0], stream));
@@ -443,6 +475,36 @@ static int enqueue_frame(SceneImpl &s, FilmImpl &f, const rt_render_params *p, h
         ra.accum = f.accum;
         ra.spp_before = f.accum_spp;
         if (p->samples_per_pixel > 0) f.accum_spp += p->samples_per_pixel;
+        if (!continues) {  // what this frame is begun with, it has to be continued with (rt_render_launch)
+            f.frame_adaptive = f.adaptive;
+            f.frame_rule = f.rule;
+        }
+        f.frame_spp = f.accum_spp;
+    } else {
+        f.frame_spp = p->samples_per_pixel;
+        // a launch without ACCUMULATE overwrites every pixel -- also the stopped ones of an accumulated adaptive frame, which no later
+        // launch would write again: that frame has ended
+        if (f.adaptive || f.frame_adaptive) f.accum_spp = 0;
+    }
+    if (f.adaptive) {
+        // samples_per_pixel is the most a pixel may take in this launch; n, q and the mark live per pixel and persist with the
+        // sums of an accumulated frame
+        const size_t np = f.n_pixels ? f.n_pixels : 1;
+        if (!f.ad_n) {
+            HIP_TRY(hipMalloc((void **)&f.ad_n, np * sizeof(uint32_t)));
+            HIP_TRY(hipMalloc((void **)&f.ad_q, np * sizeof(double)));
+            HIP_TRY(hipMalloc((void **)&f.ad_mark, np));
+        }
+        if (!continues) {
+            HIP_TRY(hipMemsetAsync(f.ad_n, 0, np * sizeof(uint32_t), stream));
+            HIP_TRY(hipMemsetAsync(f.ad_q, 0, np * sizeof(double), stream));
+            HIP_TRY(hipMemsetAsync(f.ad_mark, 0, np, stream));
+        }
+        ra.adaptive = 1;
+        ra.rule = f.rule;
+        ra.ad_n = f.ad_n;
+        ra.ad_q = f.ad_q;
+        ra.ad_mark = f.ad_mark;
     }
     ra.state = f.state;
     ra.ray_counter = f.ray_counter;
@@ -582,6 +644,10 @@ static int enqueue_frame(SceneImpl &s, FilmImpl &f, const rt_render_params *p, h
         }
         RenderArgs probe = ra;
         probe.probe = 1;
+        probe.adaptive = 0;  // the rehearsal is the plain kernel's: it only counts rays
+        probe.ad_n = nullptr;
+        probe.ad_q = nullptr;
+        probe.ad_mark = nullptr;
         probe.spp = probe_spp;
         probe.accum = nullptr;
         probe.spp_before = 0;
@@ -673,6 +739,9 @@ int rt_render_launch(rt_scene *scene, rt_film *film, const rt_render_params *p)
     if (f.in_flight)
         return fail(RT_ERR_STATE, "rt_render_launch: this film already has a render in flight (rt_render_finish it first; "
                                   "use one film per frame in flight)");
+    if (continues_frame(f, p) && (f.adaptive != f.frame_adaptive || (f.adaptive && !same_rule(f.rule, f.frame_rule))))
+        return fail(RT_ERR_STATE, "rt_render_launch: adaptive sampling was switched or given other parameters in the middle of an "
+                                  "accumulated frame (begin a frame by re-seeding, or set it back)");
     if (int rc = rt_scene_upload(scene, f.device)) return rc;
     if (int rc = select_device(f.device)) return rc;
     hipStream_t stream = p->stream ? (hipStream_t)p->stream : f.own_stream;
@@ -690,6 +759,8 @@ int rt_render_launch(rt_scene *scene, rt_film *film, const rt_render_params *p)
     }
     f.last_samples = (uint64_t)f.n_pixels * (uint64_t)p->samples_per_pixel;
     f.last_variant = p->variant;
+    f.last_adaptive = f.adaptive;
+    f.rendered = true;
     return RT_OK;
 }
 
@@ -738,7 +809,7 @@ int rt_render_finish(rt_scene *scene, rt_film *film, rt_render_stats *stats)
                                  100.0 * c[32 + k] / total, c[96 + k], (double)c[64 + k] / c[96 + k], (double)c[32 + k] / c[96 + k]);
         }
 #endif
-        stats->samples = f.last_samples;
+        stats->samples = f.last_adaptive ? (uint64_t)f.host_counters[2] : f.last_samples;  // adaptive: what the waves counted
         stats->rays = rays;
         stats->seconds_seed = ms_seed * 1e-3;
         stats->seconds_render = ms_render * 1e-3;
@@ -767,6 +838,73 @@ int rt_film_download(rt_film *film, double *frame_full, int width, int height)
             lr++;
         }
     return RT_OK;
+}
+
+int rt_film_set_adaptive(rt_film *film, const rt_adaptive_params *params)
+{
+    if (!film) return fail(RT_ERR_INVALID, "rt_film_set_adaptive: null film");
+    FilmImpl &f = *F(film);
+    if (f.in_flight) return fail(RT_ERR_STATE, "rt_film_set_adaptive: a render is in flight");
+    if (params && !rule_in_range(*params))
+        return fail(RT_ERR_INVALID, "rt_film_set_adaptive: needs min_samples >= 2, check_interval >= 1, noise_threshold >= 0, luminance_floor > 0");
+    f.adaptive = params != nullptr;
+    if (params) f.rule = to_rule(*params);
+    return RT_OK;
+}
+
+int rt_film_download_sample_counts(rt_film *film, uint32_t *counts_full, int width, int height)
+{
+    if (!film || !counts_full) return fail(RT_ERR_INVALID, "rt_film_download_sample_counts: null argument");
+    FilmImpl &f = *F(film);
+    if (width != f.width || height != f.height) return fail(RT_ERR_INVALID, "rt_film_download_sample_counts: frame size mismatch");
+    if (f.in_flight) return fail(RT_ERR_STATE, "rt_film_download_sample_counts: a render is in flight");
+    if (int rc = select_device(f.device)) return rc;
+    std::vector<uint32_t> compact((size_t)f.n_pixels, f.rendered ? (uint32_t)f.frame_spp : 0u);
+    if (f.rendered && f.last_adaptive && f.n_pixels)
+        HIP_TRY(hipMemcpy(compact.data(), f.ad_n, compact.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    std::memset(counts_full, 0, (size_t)width * (size_t)height * sizeof(uint32_t));
+    size_t lr = 0;
+    for (int j = 0; j < height; j++)
+        if ((j / f.stripe_rows) % f.world_size == f.rank) {
+            std::memcpy(counts_full + (size_t)j * width, compact.data() + lr * (size_t)width, sizeof(uint32_t) * (size_t)width);
+            lr++;
+        }
+    return RT_OK;
+}
+
+int rt_adaptive_converged(const rt_adaptive_params *p, uint32_t n, double sum_r, double sum_g, double sum_b, double sum_y2)
+{
+    if (!p || !rule_in_range(*p)) {
+        set_error("rt_adaptive_converged: needs min_samples >= 2, check_interval >= 1, noise_threshold >= 0, luminance_floor > 0");
+        return -(int)RT_ERR_INVALID;
+    }
+    return adaptive_converged(to_rule(*p), n, sum_r, sum_g, sum_b, sum_y2) ? 1 : 0;
+}
+
+int rt_adaptive_rule_on_device(int device, int variant, const rt_adaptive_params *p, uint32_t count, const uint32_t *n,
+                               const double *sums_rgbq, const double *sample_rgb, double *q_out, uint8_t *stops_out)
+{
+    if (!p || !rule_in_range(*p) || (variant != 0 && variant != 1) || (count && (!n || !sums_rgbq || !sample_rgb || !q_out || !stops_out)))
+        return fail(RT_ERR_INVALID, "rt_adaptive_rule_on_device: bad argument");
+    if (count == 0) return RT_OK;
+    if (int rc = select_device(device)) return rc;
+    const size_t bytes[5] = {count * sizeof(uint32_t), (size_t)count * 4 * sizeof(double), (size_t)count * 3 * sizeof(double),
+                             count * sizeof(double), (size_t)count};
+    const void *host_in[3] = {n, sums_rgbq, sample_rgb};
+    void *dev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    hipError_t e = hipSuccess;
+    for (int k = 0; k < 5 && e == hipSuccess; k++) e = hipMalloc(&dev[k], bytes[k]);
+    for (int k = 0; k < 3 && e == hipSuccess; k++) e = hipMemcpy(dev[k], host_in[k], bytes[k], hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        auto launch = variant ? launch_adaptive_rule_fast : launch_adaptive_rule_strict;
+        e = launch(to_rule(*p), count, (const uint32_t *)dev[0], (const double *)dev[1], (const double *)dev[2], (double *)dev[3], (uint8_t *)dev[4], nullptr);
+    }
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(q_out, dev[3], bytes[3], hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(stops_out, dev[4], bytes[4], hipMemcpyDeviceToHost);
+    for (void *d : dev)
+        if (d) hipFree(d);
+    return e == hipSuccess ? RT_OK : hip_fail(e, "rt_adaptive_rule_on_device");
 }
 
 int rt_render(rt_scene *scene, const rt_render_params *params, double *frame, rt_render_stats *stats)

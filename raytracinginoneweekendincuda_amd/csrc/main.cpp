@@ -2,6 +2,7 @@
 // (R/kernel.cu:570-742): same defaults (1440x720, sceneId 9, spp rule, seed 1984, depth 50), same
 // stderr lines, same output.ppm, exit code 99 on a device error.
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -156,6 +157,11 @@ int main(int argc, char **argv)
     std::string out = "output.ppm";
     std::string earth_path;      // decoded 8-bit sRGB pixels of the earth texture (P6): converted like RtwImage::Load does
     bool earth_is_bytes = false; // --earth-bytes: the file already holds what RtwImage::Load hands to ImageTexture
+    // adaptive sampling (--noise): a pixel stops once its noise is below the threshold, --spp is then the most it takes
+    double noise = -1.0;
+    int min_spp = 16, check_every = 16;
+    std::string samples_map;     // --samples-map: the samples every pixel took, as a 16-bit PGM
+    bool noise_given = false, adaptive_option = false;  // --noise seen; an option that only means something with it seen
     for (int k = 1; k < argc; k++) {
         std::string a = argv[k];
         auto val = [&](const char *name) -> const char * {
@@ -175,6 +181,24 @@ int main(int argc, char **argv)
         else if (const char *v = val("--flags")) flags = (unsigned)std::strtoul(v, nullptr, 0);
         else if (a == "--accelerate-lists") flags |= RT_FLAG_ACCELERATE_LISTS;
         else if (const char *v = val("--output")) out = v;
+        else if (const char *v = val("--noise")) {
+            char *end = nullptr;
+            noise = std::strtod(v, &end);
+            noise_given = true;
+            if (end == v || *end != 0 || !std::isfinite(noise) || noise < 0.0) {
+                std::fprintf(stderr, "--noise needs a finite number >= 0, not '%s'\n", v);
+                return 2;
+            }
+        } else if (const char *v = val("--min-spp")) {
+            min_spp = std::atoi(v);
+            adaptive_option = true;
+        } else if (const char *v = val("--check-every")) {
+            check_every = std::atoi(v);
+            adaptive_option = true;
+        } else if (const char *v = val("--samples-map")) {
+            samples_map = v;
+            adaptive_option = true;
+        }
         else if (const char *v = val("--earth")) earth_path = v;
         else if (const char *v = val("--earth-bytes")) {
             earth_path = v;
@@ -184,6 +208,12 @@ int main(int argc, char **argv)
                          "usage: rtow [--scene 0..11] [--width W] [--height H] [--spp N] [--depth D] [--seed S]\n"
                          "            [--world bvh|list] [--variant strict|fast] [--device N] [--gpus N] [--output file.ppm]\n"
                          "            [--earth earthmap.jpg|decoded.ppm | --earth-bytes texture.ppm] [--accelerate-lists] [--flags N]\n"
+                         "            [--noise T [--min-spp N] [--check-every K] [--samples-map file.pgm]]\n"
+                         "  --noise        adaptive sampling: a pixel stops at the first check (after --min-spp samples, default 16, then every\n"
+                         "                 --check-every, default 16) where the standard error of its mean is at most T x max(mean, 0.01);\n"
+                         "                 --spp is then the most samples a pixel takes.  Use T >= 0.001.  One GPU (no --gpus)\n"
+                         "  --samples-map  with --noise: the samples every pixel took as a binary PGM (P5, 16 bit, clamped to 65535; rows top\n"
+                         "                 first like the PPM)\n"
                          "  --earth        the texture of scenes 2 and 9: a JPEG file (default: ./earthmap.jpg, like the reference) is read as\n"
                          "                 RtwImage::Load reads it -- decoded as the reference's stb_image decodes it, bit for bit; a binary PPM\n"
                          "                 (P6) is taken as pixels some other decoder produced (libjpeg's differ from stb's in ~0.6 %% of the\n"
@@ -196,6 +226,15 @@ int main(int argc, char **argv)
                          "  --flags        RT_FLAG_* bits of include/rtow.h (none of them changes the picture)\n");
             return 2;
         }
+    }
+    const bool adaptive = noise_given;
+    if (!adaptive && adaptive_option) {
+        std::fprintf(stderr, "--min-spp, --check-every and --samples-map need --noise\n");
+        return 2;
+    }
+    if (adaptive && gpus >= 1) {
+        std::fprintf(stderr, "--noise renders on one GPU (no --gpus)\n");
+        return 2;
     }
     if (spp < 0) spp = (scene_id == 9) ? 100 : ((scene_id >= 5 && scene_id <= 8) ? 200 : 10);  // R/kernel.cu:593
 
@@ -262,6 +301,36 @@ int main(int argc, char **argv)
     double gather_s = 0.0;
     if (gpus >= 1) {
         if (render_multi_gpu(scene, p, gpus, frame.data(), &st, &gather_s) != 0) return die("render (multi-GPU)");
+    } else if (adaptive) {
+        rt_film *film = rt_film_create(device, width, height, p.stripe_rows, 0, 1);
+        if (!film) return die("film");
+        const rt_adaptive_params ap{min_spp, check_every, noise, 0.01};
+        if (rt_film_set_adaptive(film, &ap) != RT_OK) return die("adaptive");
+        if (rt_render_launch(scene, film, &p) != RT_OK || rt_render_finish(scene, film, &st) != RT_OK) return die("render");
+        if (rt_film_download(film, frame.data(), width, height) != RT_OK) return die("download");
+        std::vector<uint32_t> counts((size_t)width * height);
+        if (rt_film_download_sample_counts(film, counts.data(), width, height) != RT_OK) return die("sample counts");
+        rt_film_destroy(film);
+        std::fprintf(stderr, "adaptive: %.2f samples per pixel on average (noise %g, at least %d, at most %d).\n",
+                     (double)st.samples / ((double)width * height), noise, min_spp, spp);
+        if (!samples_map.empty()) {
+            FILE *fp = std::fopen(samples_map.c_str(), "wb");
+            if (!fp) {
+                std::fprintf(stderr, "cannot write %s\n", samples_map.c_str());
+                return 99;
+            }
+            std::fprintf(fp, "P5\n%d %d\n65535\n", width, height);
+            std::vector<unsigned char> row((size_t)width * 2);
+            for (int j = height - 1; j >= 0; j--) {  // top row first; big-endian samples as PGM prescribes
+                for (int i = 0; i < width; i++) {
+                    const uint32_t c = counts[(size_t)j * width + i] > 65535u ? 65535u : counts[(size_t)j * width + i];
+                    row[2 * i] = (unsigned char)(c >> 8);
+                    row[2 * i + 1] = (unsigned char)(c & 255u);
+                }
+                std::fwrite(row.data(), 1, row.size(), fp);
+            }
+            std::fclose(fp);
+        }
     } else if (rt_render(scene, &p, frame.data(), &st) != RT_OK) {
         return die("render");
     }

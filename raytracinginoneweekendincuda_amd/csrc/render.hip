@@ -20,11 +20,14 @@
 // other constants of rarely executed code (log, sin, acos, atan2) out of the main loop into ~100 VGPRs and the register
 // allocator then spills them: 520 B/lane of scratch in the deep general kernel, 80 B without (C5 +10 %); the tight
 // primitive walk loses 5-7 % the same way, hence the split.
+// Both groups are compiled once more with RT_ADAPT=1: those objects hold the Adaptive<> forms of the group's instantiations
+// (adaptive sampling, adaptive_rule.h) and nothing else, so that the objects without it hold exactly the kernels they always held.
 #include <hip/hip_runtime.h>
 
 #include <cfloat>
 #include <cstddef>
 #include <cstdint>
+#include <type_traits>
 
 #include "flat_scene.h"
 #include "render_iface.h"
@@ -35,6 +38,9 @@
 #endif
 #ifndef RT_GROUP
 #define RT_GROUP 0
+#endif
+#ifndef RT_ADAPT  // 1: this translation unit holds the Adaptive<> instantiations of its group and nothing else
+#define RT_ADAPT 0
 #endif
 
 namespace rtow {
@@ -77,7 +83,22 @@ struct Traits {
     static constexpr int WORLD = WORLD_;
     static constexpr bool COMPOSITE = COMPOSITE_;
     static constexpr bool RICH = RICH_;
+    static constexpr bool ADAPTIVE = false;
 };
+// The same instantiation with adaptive sampling (adaptive_rule.h): a type of its own, so that a film without it launches
+// exactly the kernels it always did.  Three more registers of path state (q, and the samples the pixel had before the
+// launch), the rule at the end of a sample, the per-pixel planes where a pixel is taken up and laid down.
+template <class T>
+struct Adaptive : T {
+    static constexpr bool ADAPTIVE = true;
+};
+// the instantiation U as the launch that chose T wants it: adaptive or not
+template <class T, class U>
+struct LikeImpl { using type = U; };
+template <class T, class U>
+struct LikeImpl<Adaptive<T>, U> { using type = Adaptive<U>; };
+template <class T, class U>
+using Like = typename LikeImpl<T, U>::type;
 
 struct Vec {
     double x, y, z;
@@ -3001,6 +3022,10 @@ __global__ __launch_bounds__(T::BLOCK, T::MIN_WAVES) void render_kernel(DeviceSc
     Ray ray{};
     int sample = 0, depth = 0;
     uint32_t wave_rays = 0;  // rays of the whole wave (uniform)
+    // adaptive sampling: samples the pixel had before this launch, its sum of y^2, and the samples this wave has taken (uniform)
+    [[maybe_unused]] uint32_t ad_before = 0;
+    [[maybe_unused]] double ad_q = 0.0;
+    [[maybe_unused]] unsigned long long wave_samples = 0;
 
     uint32_t pix_rays = 0;  // rays this lane's current pixel has traced so far
     uint32_t my_tile = 0;   // tile of the current pixel (cost probe)
@@ -3077,10 +3102,17 @@ __global__ __launch_bounds__(T::BLOCK, T::MIN_WAVES) void render_kernel(DeviceSc
                     } else if (a.pix_class && take) {
                         take = a.pix_class[(size_t)lr * (size_t)a.width + (size_t)pi] == 0;  // a listed pixel: the serving waves take it
                     }
+                    if constexpr (T::ADAPTIVE) {  // stopped by the rule in an earlier launch of this frame: it stays as it is
+                        if (take && a.ad_mark[(size_t)lr * (size_t)a.width + (size_t)pi] != 0) take = false;
+                    }
                     if (take) {
                         i = pi;
                         j = owned_row(lr, a.stripe_rows, a.rank, a.world_size);
                         local = (size_t)lr * (size_t)a.width + (size_t)pi;
+                        if constexpr (T::ADAPTIVE) {
+                            ad_before = a.ad_n[local];
+                            ad_q = a.ad_q[local];
+                        }
                         rng.d = a.state[0 * (size_t)a.n_pixels + local];
                         rng.v0 = a.state[1 * (size_t)a.n_pixels + local];
                         rng.v1 = a.state[2 * (size_t)a.n_pixels + local];
@@ -3336,6 +3368,7 @@ __global__ __launch_bounds__(T::BLOCK, T::MIN_WAVES) void render_kernel(DeviceSc
             PH_END(1, (todo >> lane) & 1ull);
         }
         if (a.max_depth > 0) wave_rays += (uint32_t)__popcll(todo);
+        [[maybe_unused]] bool sample_ends = false;
         if ((todo >> lane) & 1ull) {
             const bool no_bounces = a.max_depth <= 0;  // R/kernel.cu:71: the bounce loop never runs, RayColor returns black
             if (!no_bounces) {
@@ -3391,7 +3424,16 @@ __global__ __launch_bounds__(T::BLOCK, T::MIN_WAVES) void render_kernel(DeviceSc
                     sample = (int)park_get_int<T::BLOCK>(sc.lds_park, 3);
                 }
                 col = col + accumulated;
-                if (++sample < a.spp) {
+                bool more = ++sample < a.spp;
+                [[maybe_unused]] bool converged = false;
+                if constexpr (T::ADAPTIVE) {
+                    sample_ends = true;
+                    ad_q = adaptive_add_sample(ad_q, accumulated.x, accumulated.y, accumulated.z);
+                    // (also at the launch's cap: the mark must be right for a later launch of the frame)
+                    converged = adaptive_converged(a.rule, ad_before + (uint32_t)sample, col.x, col.y, col.z, ad_q);
+                    if (converged) more = false;
+                }
+                if (more) {
                     if constexpr (T::PARK) {
                         park_put_vec<T::BLOCK>(sc.lds_park, 0, col);
                         park_put_int<T::BLOCK>(sc.lds_park, 3, (uint32_t)sample);
@@ -3427,7 +3469,15 @@ __global__ __launch_bounds__(T::BLOCK, T::MIN_WAVES) void render_kernel(DeviceSc
                         a.accum[local * 3 + 1] = col.y;
                         a.accum[local * 3 + 2] = col.z;
                     }
-                    col = over(col, (double)(a.spp_before + a.spp));
+                    if constexpr (T::ADAPTIVE) {  // the pixel's own n
+                        const uint32_t n = ad_before + (uint32_t)sample;
+                        a.ad_n[local] = n;
+                        a.ad_q[local] = ad_q;
+                        a.ad_mark[local] = converged ? 1 : 0;
+                        col = over(col, (double)n);
+                    } else {
+                        col = over(col, (double)(a.spp_before + a.spp));
+                    }
                     a.pixels[local * 3 + 0] = sqrt(col.x);
                     a.pixels[local * 3 + 1] = sqrt(col.y);
                     a.pixels[local * 3 + 2] = sqrt(col.z);
@@ -3457,6 +3507,7 @@ __global__ __launch_bounds__(T::BLOCK, T::MIN_WAVES) void render_kernel(DeviceSc
                 }
             }
         }
+        if constexpr (T::ADAPTIVE) wave_samples += (unsigned long long)__popcll(__ballot(sample_ends));
 #if RT_PHASES
         if (todo) {
             ph.t[2] += __builtin_readcyclecounter() - ph_ts;
@@ -3472,9 +3523,12 @@ __global__ __launch_bounds__(T::BLOCK, T::MIN_WAVES) void render_kernel(DeviceSc
     // one atomic per wave for the ray counter
     const unsigned long long total = wave_rays;
     if (lane == 0 && total) atomicAdd(a.ray_counter, total);
+    if constexpr (T::ADAPTIVE) {  // ... and one for the samples taken
+        if (lane == 0 && wave_samples) atomicAdd(a.ray_counter + 2, wave_samples);
+    }
 }
 
-#if RT_STRICT && RT_GROUP == 0
+#if RT_STRICT && RT_GROUP == 0 && !RT_ADAPT
 // Rank the tiles by probed cost, heaviest first.  A pixel's samples are sequential (one RNG stream), so the frame can
 // never end before its longest pixel does: those pixels have to start first, not wherever row-major order puts them.
 __global__ __launch_bounds__(1024) void tile_order_kernel(const uint32_t *cost, uint32_t *order, uint32_t n, uint32_t flat_x8)
@@ -3572,7 +3626,7 @@ hipError_t launch_tile_order(const uint32_t *tile_cost, uint32_t *tile_order, ui
 #define RT_CAT2(a, b) a##b
 #define RT_CAT(a, b) RT_CAT2(a, b)
 
-#if RT_GROUP == 0
+#if RT_GROUP == 0 && !RT_ADAPT
 hipError_t RT_CAT(launch_seed_, RT_SUFFIX)(const SeedArgs &a, hipStream_t stream)
 {
     if (a.n_pixels == 0) return hipSuccess;
@@ -3644,6 +3698,7 @@ hipError_t launch_one(const DeviceScene &sc_in, RenderArgs a, hipStream_t stream
     DeviceScene sc = sc_in;
     [[maybe_unused]] const RenderArgs a_in = a;
     if (!T::ROLES && a.heavy_list) return hipErrorInvalidValue;  // this instantiation has no serving waves (Traits::ROLES): its listed pixels would never be rendered
+    if (T::ADAPTIVE != (a.adaptive != 0) || (T::ADAPTIVE && (a.probe || !a.ad_n || !a.ad_q || !a.ad_mark))) return hipErrorInvalidValue;  // rehearsals run the plain kernels
     auto kernel = render_kernel<RT_STRICT, T>;
     uint32_t tiles = (((uint32_t)a.width + 7u) >> 3) * (((uint32_t)a.rows_owned + 7u) >> 3);
     size_t lds = 0;
@@ -3678,7 +3733,7 @@ hipError_t launch_one(const DeviceScene &sc_in, RenderArgs a, hipStream_t stream
             const bool fits = a.lds_nodes && (sc.n_mspheres == 0 || (sc.lds_mspheres != kNone && sc.lds_msphere_aux != kNone)) &&
                               (sc.n_spheres == 0 || (sc.lds_spheres_tab != kNone && sc.lds_sphere_aux != kNone)) &&
                               (sc.n_materials == 0 || sc.lds_materials != kNone);
-            if (!fits) return launch_one<TBvhPrims>(sc_in, a_in, stream, info);
+            if (!fits) return launch_one<Like<T, TBvhPrims>>(sc_in, a_in, stream, info);
             auto empty = [](uint32_t &slot) { if (slot == kNone) slot = 0; };  // an empty table is never read
             empty(sc.lds_mspheres); empty(sc.lds_msphere_aux); empty(sc.lds_spheres_tab); empty(sc.lds_sphere_aux); empty(sc.lds_materials);
         }
@@ -3731,9 +3786,9 @@ hipError_t launch_one(const DeviceScene &sc_in, RenderArgs a, hipStream_t stream
                 // (the quad rows stay optional: a box's six faces are read only for a hit point on one of its edges)
                 if constexpr (T::SEG) {  // the reference's tree in the reference's order instead
                     if (!fits || !(sc.flags & SCENE_SEGMENTED) || sc.fast_nodes == nullptr || sc.n_seg_media > kSegMaxMedia)
-                        return launch_one<TBvhGeneralDeep>(sc_in, a_in, stream, info);
+                        return launch_one<Like<T, TBvhGeneralDeep>>(sc_in, a_in, stream, info);
                 } else {
-                    if (!fits) return launch_one<TBvhGeneral>(sc_in, a_in, stream, info);
+                    if (!fits) return launch_one<Like<T, TBvhGeneral>>(sc_in, a_in, stream, info);
                 }
                 auto empty = [](uint32_t &slot) { if (slot == kNone) slot = 0; };  // an empty table is never read
                 empty(sc.lds_objects); empty(sc.lds_xforms); empty(sc.lds_media); empty(sc.lds_group_boxes); empty(sc.lds_materials);
@@ -3761,7 +3816,7 @@ hipError_t launch_one(const DeviceScene &sc_in, RenderArgs a, hipStream_t stream
         info->vgprs = attr.numRegs;
         info->lds_bytes = (int)(attr.sharedSizeBytes + lds);
         info->kind = T::WORLD * 8 + (T::MEDIA ? 4 : 0) + (T::COMPOSITE ? 2 : 0) + (T::RICH ? 1 : 0) + (T::NESTED ? 32 : 0) + (T::FAST ? 64 : 0) +
-                     (T::GROUPED ? 128 : 0) + (T::SEG ? 256 : 0);
+                     (T::GROUPED ? 128 : 0) + (T::SEG ? 256 : 0) + (T::ADAPTIVE ? 512 : 0);
         return hipSuccess;
     }
     if (a.n_pixels == 0 || a.spp <= 0) return hipSuccess;
@@ -3793,24 +3848,78 @@ hipError_t launch_one(const DeviceScene &sc_in, RenderArgs a, hipStream_t stream
 enum CompositeKernel { CK_LIST_PRIMS, CK_LIST_INSTANCES, CK_LIST_GENERAL, CK_LIST_NESTED, CK_BVH_INSTANCES, CK_BVH_MEDIA,
                        CK_BVH_GENERAL, CK_BVH_GENERAL_DEEP, CK_BVH_NESTED, CK_LIST_PRIMS_GROUPED, CK_LIST_INSTANCES_GROUPED, CK_BVH_SEGMENTED, CK_LIST_INSTANCES_5 };
 hipError_t RT_CAT(launch_composite_, RT_SUFFIX)(int which, const DeviceScene &sc, const RenderArgs &a, hipStream_t stream, KernelInfo *info);
+// ... of group 0, and the Adaptive<> forms of both (each group's in a translation unit of their own, RT_ADAPT == 1)
+enum PrimsKernel { PK_SPHERE_LIST, PK_BVH_PRIMS, PK_BVH_PRIMS_FAST };
+hipError_t RT_CAT(launch_adaptive_prims_, RT_SUFFIX)(int which, const DeviceScene &sc, const RenderArgs &a, hipStream_t stream, KernelInfo *info);
+hipError_t RT_CAT(launch_adaptive_composite_, RT_SUFFIX)(int which, const DeviceScene &sc, const RenderArgs &a, hipStream_t stream, KernelInfo *info);
 
 #if RT_GROUP == 1
+namespace {
+template <bool AD>
+hipError_t launch_composite_as(int which, const DeviceScene &sc, const RenderArgs &a, hipStream_t stream, KernelInfo *info)
+{
+    using Any = std::conditional_t<AD, Adaptive<TListPrims>, TListPrims>;  // Like<Any, U>: U, adaptive or not
+    switch (which) {
+    case CK_LIST_PRIMS: return launch_one<Like<Any, TListPrims>>(sc, a, stream, info);
+    case CK_LIST_INSTANCES: return launch_one<Like<Any, TListInstances>>(sc, a, stream, info);
+    case CK_LIST_INSTANCES_5:
+        // Adaptive frames take the four-wave build: the five-wave one (Traits::PARK) is chosen where a frame is a whole number of
+        // generations of pixels that all cost the same (list_instances_waves), which pixels that stop at different sample counts
+        // no longer are -- and its parked state has no room for q without giving back the registers the parking won.
+        if constexpr (AD) return launch_one<Adaptive<TListInstances>>(sc, a, stream, info);
+        else return launch_one<TListInstances5>(sc, a, stream, info);
+    case CK_LIST_PRIMS_GROUPED: return launch_one<Like<Any, TListPrimsGrouped>>(sc, a, stream, info);
+    case CK_LIST_INSTANCES_GROUPED: return launch_one<Like<Any, TListInstancesGrouped>>(sc, a, stream, info);
+    case CK_LIST_GENERAL: return launch_one<Like<Any, TListGeneral>>(sc, a, stream, info);
+    case CK_LIST_NESTED: return launch_one<Like<Any, TListNested>>(sc, a, stream, info);
+    case CK_BVH_INSTANCES: return launch_one<Like<Any, TBvhInstances>>(sc, a, stream, info);
+    case CK_BVH_MEDIA: return launch_one<Like<Any, TBvhMedia>>(sc, a, stream, info);
+    case CK_BVH_GENERAL: return launch_one<Like<Any, TBvhGeneral>>(sc, a, stream, info);
+    case CK_BVH_GENERAL_DEEP: return launch_one<Like<Any, TBvhGeneralDeep>>(sc, a, stream, info);
+    case CK_BVH_SEGMENTED: return launch_one<Like<Any, TBvhSegmented>>(sc, a, stream, info);
+    default: return launch_one<Like<Any, TBvhNested>>(sc, a, stream, info);
+    }
+}
+} // namespace
+#if RT_ADAPT
+hipError_t RT_CAT(launch_adaptive_composite_, RT_SUFFIX)(int which, const DeviceScene &sc, const RenderArgs &a, hipStream_t stream, KernelInfo *info)
+{
+    return launch_composite_as<true>(which, sc, a, stream, info);
+}
+#else
 hipError_t RT_CAT(launch_composite_, RT_SUFFIX)(int which, const DeviceScene &sc, const RenderArgs &a, hipStream_t stream, KernelInfo *info)
 {
+    return launch_composite_as<false>(which, sc, a, stream, info);
+}
+#endif
+#elif RT_ADAPT
+// The rule exactly as this translation unit compiles it for its render kernels, on arrays: one more sample (ar, ag, ab) into q,
+// then the rule on (n, r, g, b, q).  For the test that no build fuses the rule's operations (rt_adaptive_rule_on_device).
+template <int STRICT>
+__global__ __launch_bounds__(256) void adaptive_rule_kernel(AdaptiveRule rule, uint32_t count, const uint32_t *n, const double *sums_rgbq,
+                                                            const double *sample_rgb, double *q_out, uint8_t *stops_out)
+{
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= count) return;
+    const double q = adaptive_add_sample(sums_rgbq[4 * (size_t)k + 3], sample_rgb[3 * (size_t)k], sample_rgb[3 * (size_t)k + 1], sample_rgb[3 * (size_t)k + 2]);
+    q_out[k] = q;
+    stops_out[k] = adaptive_converged(rule, n[k], sums_rgbq[4 * (size_t)k], sums_rgbq[4 * (size_t)k + 1], sums_rgbq[4 * (size_t)k + 2], q) ? 1 : 0;
+}
+hipError_t RT_CAT(launch_adaptive_rule_, RT_SUFFIX)(const AdaptiveRule &rule, uint32_t count, const uint32_t *n, const double *sums_rgbq,
+                                                    const double *sample_rgb, double *q_out, uint8_t *stops_out, hipStream_t stream)
+{
+    if (count == 0) return hipSuccess;
+    hipLaunchKernelGGL(adaptive_rule_kernel<RT_STRICT>, dim3((count + 255u) / 256u), dim3(256), 0, stream, rule, count, n, sums_rgbq, sample_rgb, q_out,
+                       stops_out);
+    return hipGetLastError();
+}
+
+hipError_t RT_CAT(launch_adaptive_prims_, RT_SUFFIX)(int which, const DeviceScene &sc, const RenderArgs &a, hipStream_t stream, KernelInfo *info)
+{
     switch (which) {
-    case CK_LIST_PRIMS: return launch_one<TListPrims>(sc, a, stream, info);
-    case CK_LIST_INSTANCES: return launch_one<TListInstances>(sc, a, stream, info);
-    case CK_LIST_INSTANCES_5: return launch_one<TListInstances5>(sc, a, stream, info);
-    case CK_LIST_PRIMS_GROUPED: return launch_one<TListPrimsGrouped>(sc, a, stream, info);
-    case CK_LIST_INSTANCES_GROUPED: return launch_one<TListInstancesGrouped>(sc, a, stream, info);
-    case CK_LIST_GENERAL: return launch_one<TListGeneral>(sc, a, stream, info);
-    case CK_LIST_NESTED: return launch_one<TListNested>(sc, a, stream, info);
-    case CK_BVH_INSTANCES: return launch_one<TBvhInstances>(sc, a, stream, info);
-    case CK_BVH_MEDIA: return launch_one<TBvhMedia>(sc, a, stream, info);
-    case CK_BVH_GENERAL: return launch_one<TBvhGeneral>(sc, a, stream, info);
-    case CK_BVH_GENERAL_DEEP: return launch_one<TBvhGeneralDeep>(sc, a, stream, info);
-    case CK_BVH_SEGMENTED: return launch_one<TBvhSegmented>(sc, a, stream, info);
-    default: return launch_one<TBvhNested>(sc, a, stream, info);
+    case PK_SPHERE_LIST: return launch_one<Adaptive<TSphereList>>(sc, a, stream, info);
+    case PK_BVH_PRIMS_FAST: return launch_one<Adaptive<TBvhPrimsFast>>(sc, a, stream, info);
+    default: return launch_one<Adaptive<TBvhPrims>>(sc, a, stream, info);
     }
 }
 #else
@@ -3830,15 +3939,27 @@ int list_instances_waves(const RenderArgs &a)
 
 hipError_t dispatch(const DeviceScene &sc, const RenderArgs &a, hipStream_t stream, KernelInfo *info)
 {
-    auto composite_kernel = [&](int which) { return RT_CAT(launch_composite_, RT_SUFFIX)(which, sc, a, stream, info); };
+    // a film with adaptive sampling on: the same choice among the Adaptive<> instantiations
+    auto composite_kernel = [&](int which) {
+        return a.adaptive ? RT_CAT(launch_adaptive_composite_, RT_SUFFIX)(which, sc, a, stream, info)
+                          : RT_CAT(launch_composite_, RT_SUFFIX)(which, sc, a, stream, info);
+    };
+    auto prims_kernel = [&](int which) {
+        if (a.adaptive) return RT_CAT(launch_adaptive_prims_, RT_SUFFIX)(which, sc, a, stream, info);
+        switch (which) {
+        case PK_SPHERE_LIST: return launch_one<TSphereList>(sc, a, stream, info);
+        case PK_BVH_PRIMS_FAST: return launch_one<TBvhPrimsFast>(sc, a, stream, info);
+        default: return launch_one<TBvhPrims>(sc, a, stream, info);
+        }
+    };
     const bool composite = sc.n_objects != 0 || sc.n_boxes != 0;
     const bool rich = (sc.flags & SCENE_RICH_TEXTURES) != 0;
     // RT_FLAG_ACCELERATE_LISTS: a list world of primitives through the library's tree, when its rows fit the kernel's LDS
     if (a.accelerate_lists && sc.world_kind == WORLD_LIST && sc.fast_nodes && !composite && !rich && !(sc.flags & SCENE_HAS_MEDIA) &&
         !(sc.flags & SCENE_HAS_TREES) && !a.force_general && fast_rows_fit(sc))
-        return launch_one<TBvhPrimsFast>(sc, a, stream, info);
+        return prims_kernel(PK_BVH_PRIMS_FAST);
     if ((sc.flags & SCENE_LIST_ALL_SPHERES) && !rich && sc.n_spheres <= 65535u && !a.force_general)
-        return launch_one<TSphereList>(sc, a, stream, info);
+        return prims_kernel(PK_SPHERE_LIST);
     if (sc.flags & SCENE_HAS_TREES) return composite_kernel(sc.world_kind == WORLD_BVH ? CK_BVH_NESTED : CK_LIST_NESTED);
     const bool media = (sc.flags & SCENE_HAS_MEDIA) != 0;
     const bool scan_world = sc.world_kind == WORLD_LIST || (sc.n_world_items <= 16u && sc.scan_cost <= (uint32_t)a.small_world && !a.always_walk);
@@ -3851,9 +3972,8 @@ hipError_t dispatch(const DeviceScene &sc, const RenderArgs &a, hipStream_t stre
     }
     if (sc.world_kind == WORLD_BVH) {
         if (!composite && !rich && !a.force_general)
-            return (sc.fast_nodes && !a.reference_tree && sc.n_fast_nodes * kFastNodeBytes <= kFastLdsBudget)
-                       ? launch_one<TBvhPrimsFast>(sc, a, stream, info)
-                       : launch_one<TBvhPrims>(sc, a, stream, info);
+            return prims_kernel((sc.fast_nodes && !a.reference_tree && sc.n_fast_nodes * kFastNodeBytes <= kFastLdsBudget) ? PK_BVH_PRIMS_FAST
+                                                                                                                            : PK_BVH_PRIMS);
         if (!rich && !a.force_general) return composite_kernel(media ? CK_BVH_MEDIA : CK_BVH_INSTANCES);
         // deep worlds: the library's tree, one walk per run of surfaces between media, where the scene has one (RT_FLAG_REFERENCE_TREE:
         // the reference's tree in the reference's order); both fall back when their tables do not fit the LDS of a CU

@@ -4,6 +4,7 @@
 
 #include <cstdint>
 
+#include "adaptive_rule.h"
 #include "flat_scene.h"
 #include "rng.h"
 
@@ -75,6 +76,15 @@ struct RenderArgs {
     int32_t pixels_per_wave;    // sphere-list kernel: at most this many lanes of a wave hold a pixel (64 = all of them)
     int32_t shade_batch;    // BVH kernels: shade once this many lanes have finished their walk
     uint32_t ray_budget;    // sphere-list kernel: a pixel past this many rays is finished cooperatively
+    // Adaptive sampling (adaptive_rule.h; the Adaptive<> instantiations of render.hip, chosen by `adaptive`): spp is then the most
+    // samples a pixel may take in this launch.  Per owned pixel: samples taken so far in this frame, the sum of y^2 over them, and
+    // whether the rule has stopped the pixel (a later launch of the frame drops it from the queue untouched).  The launcher zeroes
+    // the three planes where a frame begins.  Samples taken by the launch are summed into ray_counter[2].
+    int32_t adaptive;
+    AdaptiveRule rule;
+    uint32_t *ad_n;
+    double *ad_q;
+    uint8_t *ad_mark;
 };
 
 struct KernelInfo {
@@ -87,6 +97,12 @@ hipError_t launch_render_strict(const DeviceScene &sc, const RenderArgs &a, hipS
 hipError_t launch_render_fast(const DeviceScene &sc, const RenderArgs &a, hipStream_t stream);
 hipError_t kernel_info_strict(const DeviceScene &sc, const RenderArgs &a, KernelInfo *info);
 hipError_t kernel_info_fast(const DeviceScene &sc, const RenderArgs &a, KernelInfo *info);
+
+// the stopping rule as the adaptive render kernels of that build compile it, on device arrays of `count` entries (tests)
+hipError_t launch_adaptive_rule_strict(const AdaptiveRule &rule, uint32_t count, const uint32_t *n, const double *sums_rgbq,
+                                       const double *sample_rgb, double *q_out, uint8_t *stops_out, hipStream_t stream);
+hipError_t launch_adaptive_rule_fast(const AdaptiveRule &rule, uint32_t count, const uint32_t *n, const double *sums_rgbq,
+                                     const double *sample_rgb, double *q_out, uint8_t *stops_out, hipStream_t stream);
 
 // class 1 + an entry in `list` (its length in *count, which the caller has zeroed) for every pixel whose probed cost is at
 // least `threshold` rays, class 0 for the others; with super_list: the pixels of at least super_threshold rays go there instead
