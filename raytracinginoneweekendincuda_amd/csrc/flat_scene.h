@@ -5,6 +5,7 @@
 // R/Texture.h:24-30) becomes a tagged row in one of these tables; virtual dispatch becomes a switch on
 // the tag; the pointer BVH (R/BvhNode.h:165-167) becomes a preorder array with escape links.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 namespace rtow {
@@ -35,8 +36,15 @@ struct SphereScanRow { double cx, cy, cz, k; };
 // v_pk_fma_f32 -- two fp32 fmas per lane -- in the slot of one fp64 fma, so a conservative fp32 filter over pairs of spheres
 // costs 9 instructions per TWO spheres where the fp64 one costs 8 per sphere.  k = fl32(|c|^2 - r^2); -inf = "always passes"
 // (a sphere beyond the reach the fp32 margin is sized for, e.g. the ground sphere of radius 1000, or a non-finite row);
-// +inf = padding of an odd count.
+// +inf = padding: never passes, whatever the ray (a degenerate ray's q is +inf, and +inf > +inf is false).  The table is padded to
+// whole trips of the scan (kScanTripPairs pairs) plus the kScanAheadPairs pairs that the last trip reads ahead for a next one, so
+// the scan's loop needs neither a tail nor a clamp of its prefetch.
 struct SphereScanPair { float cx[2], cy[2], cz[2], k[2]; };
+constexpr uint32_t kScanTripPairs = 4, kScanAheadPairs = 2;
+static inline constexpr size_t scan32_padded_pairs(size_t n_spheres)
+{
+    return (n_spheres + 2 * kScanTripPairs - 1) / (2 * kScanTripPairs) * kScanTripPairs + kScanAheadPairs;
+}
 struct SphereAux { double inv_r; uint32_t mat; uint32_t pad; };
 
 // MovingSphere (R/MovingSphere.h:19-36): centre(t) = c0 + ((t - t0) / dt) * dc

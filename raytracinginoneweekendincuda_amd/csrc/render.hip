@@ -1810,22 +1810,49 @@ DEV ScanRay32 scan_ray32(const Ray &r, double a, double reach)
     }
     return f;
 }
-DEV SphereScanPair load_scan_pair(const SphereScanPair *table, uint32_t k)
+// One pair of rows at `byte_off + ahead` past `table` (the sum is formed in 64 bits: `ahead`, a constant, then becomes the load's
+// immediate offset and `byte_off` its register offset, with no addition in the loop), which the host pads (scene_builder.cpp kScanTripPairs) so that a whole trip and the
+// prefetch behind it stay inside it.  The load is volatile: an ordinary scalar load is sunk to its first use, which puts the loads
+// of a trip's second half directly in front of the wait that retires them; a volatile one keeps its place among the branches, half
+// a trip of filter arithmetic ahead of its wait.  It is still one s_load_dwordx8 from the (immutable) table.
+typedef float v8f __attribute__((ext_vector_type(8)));
+DEV SphereScanPair load_scan_pair(const SphereScanPair *table, uint32_t byte_off, uint32_t ahead)
 {
-    const RT_CONST float *p = (const RT_CONST float *)(uintptr_t)(table + k);
-    return SphereScanPair{{p[0], p[1]}, {p[2], p[3]}, {p[4], p[5]}, {p[6], p[7]}};
+    const RT_CONST char *p = ((const RT_CONST char *)(uintptr_t)table + byte_off) + ahead;
+    const v8f v = *(const volatile RT_CONST v8f *)p;
+    return SphereScanPair{{v[0], v[1]}, {v[2], v[3]}, {v[4], v[5]}, {v[6], v[7]}};
 }
 DEV void scan_pairs_arrived(const SphereScanPair &g0, const SphereScanPair &g1)
 {
     asm volatile("" ::"s"(g0.cx[0]), "s"(g0.cx[1]), "s"(g0.cy[0]), "s"(g0.cy[1]), "s"(g0.cz[0]), "s"(g0.cz[1]), "s"(g0.k[0]), "s"(g0.k[1]));
     asm volatile("" ::"s"(g1.cx[0]), "s"(g1.cx[1]), "s"(g1.cy[0]), "s"(g1.cy[1]), "s"(g1.cz[0]), "s"(g1.cz[1]), "s"(g1.k[0]), "s"(g1.k[1]));
 }
-// Two pairs = four spheres (list positions k0 .. k0 + 3): two packed chains, four compares, one wave-level branch for the four of
-// them, then the survivor path only for the spheres some lane passed (as in filter_four).
-DEV void filter_pairs(const SphereScanPair &g0, const SphereScanPair &g1, uint32_t k0, const ScanRay32 &f, uint16_t *queue, uint32_t lane,
-                      uint32_t &count SS_ARG)
+// The ray's side of the packed filter: every term twice, once per sphere of a pair.
+struct ScanRayPairs {
+    v2f ux, uy, uz, px, py, pz, nt;
+    float od, root_m;
+};
+DEV ScanRayPairs scan_ray_pairs(const ScanRay32 &f)
 {
-    const v2f ux = {f.ux, f.ux}, uy = {f.uy, f.uy}, uz = {f.uz, f.uz}, px = {f.px, f.px}, py = {f.py, f.py}, pz = {f.pz, f.pz}, nt = {f.nthr, f.nthr};
+    return ScanRayPairs{{f.ux, f.ux}, {f.uy, f.uy}, {f.uz, f.uz}, {f.px, f.px}, {f.py, f.py}, {f.pz, f.pz}, {f.nthr, f.nthr}, f.od, f.root_m};
+}
+// A no-op that the two operands which open the filter's chains pass THROUGH.  Placed behind the loads of the other register set
+// it keeps the filter's arithmetic behind those loads (they are volatile and it is an asm volatile: their order holds), so the
+// loads are issued at the head of their half of the trip and not wherever the scheduler drops them among the arithmetic.
+DEV void filter_starts_here(ScanRayPairs &f)
+{
+    asm volatile("" : "+v"(f.ux), "+v"(f.nt));
+}
+// Two pairs = four spheres (list positions k0 .. k0 + 3): two packed chains, four compares, one wave-level branch for the four of
+// them, then the survivor path only for the spheres some lane passed (as in filter_four).  `earlier` is the ballot of what the
+// same trip passed before these four; the return value adds these four's to it.  The one branch is taken when either is non-zero,
+// and `after_appends` (the caller's drain test: see scan_filtered32) runs behind that same branch, so a trip in which no lane
+// passed anything executes two compares and two branches not taken for its eight spheres.
+template <class AFTER>
+DEV unsigned long long filter_pairs(const SphereScanPair &g0, const SphereScanPair &g1, uint32_t k0, const ScanRayPairs &f, uint16_t *queue, uint32_t lane,
+                                    uint32_t &count, unsigned long long earlier, AFTER &&after_appends SS_ARG)
+{
+    const v2f ux = f.ux, uy = f.uy, uz = f.uz, px = f.px, py = f.py, pz = f.pz, nt = f.nt;
     const SphereScanPair *g[2] = {&g0, &g1};
     v2f s[2], q[2];
 #pragma unroll
@@ -1836,12 +1863,14 @@ DEV void filter_pairs(const SphereScanPair &g0, const SphereScanPair &g1, uint32
     }
     const bool p[4] = {q[0].x > g0.k[0], q[0].y > g0.k[1], q[1].x > g1.k[0], q[1].y > g1.k[1]};
     const unsigned long long m[4] = {__ballot(p[0]), __ballot(p[1]), __ballot(p[2]), __ballot(p[3])};  // the compares' own lane masks
+    const unsigned long long mine = m[0] | m[1] | m[2] | m[3];
 #if RT_PHASES
     ss.groups++;
-    ss.taken += (m[0] | m[1] | m[2] | m[3]) ? 1u : 0u;
+    ss.taken += mine ? 1u : 0u;
     ss.spheres += (m[0] ? 1u : 0u) + (m[1] ? 1u : 0u) + (m[2] ? 1u : 0u) + (m[3] ? 1u : 0u);
 #endif
-    if (m[0] | m[1] | m[2] | m[3]) {
+    const unsigned long long all = mine | earlier;
+    if (__builtin_expect(all != 0, 0)) {
         const float sv[4] = {s[0].x, s[0].y, s[1].x, s[1].y}, qv[4] = {q[0].x, q[0].y, q[1].x, q[1].y};
         const float kv[4] = {g0.k[0], g0.k[1], g1.k[0], g1.k[1]};
 #pragma unroll
@@ -1855,45 +1884,52 @@ DEV void filter_pairs(const SphereScanPair &g0, const SphereScanPair &g1, uint32
 #endif
             append_survivor(queue, lane, count, k0 + u, p[u] && !behind);
         }
+        after_appends();
     }
+    return all;
 }
 
 // Pixel-parallel scan through the packed fp32 filter: pairs of sphere rows are wave-uniform (scalar path), four pairs (eight
 // spheres) per trip in two register sets like scan_filtered; the survivors go through drain_filtered, i.e. the reference's test.
+// The table is padded to whole trips with rows that never pass, plus the two pairs the last trip prefetches (kScanTripPairs,
+// kScanAheadPairs), so the loop has no tail and no clamp: its only state is the byte offset of the trip, from which the survivor
+// path derives the sphere index.
+// Queue bound: `count` changes only in append_survivor.  At the head of a trip every lane holds at most kQueueCap - kFilterTrip
+// entries: true at the start, kept by a trip that appends nothing, and restored by the drain test that follows every trip in
+// which some lane passed a sphere.  A trip appends at most kFilterTrip entries per lane, so a lane writes its slot `count` only
+// while count < kQueueCap.
 template <bool ROWS_IN_LDS>
 DEV bool scan_filtered32(const DeviceScene &sc, uint32_t planes_off, uint32_t n_padded, uint16_t *queue, uint32_t lane, const Ray &r, double tmin,
                          double tmax, HitInfo &best SS_ARG)
 {
+    static_assert(kFilterTrip == 2 * kScanTripPairs && kScanAheadPairs == 2, "one trip = four pairs in two halves; set A of the next trip is read ahead");
+    constexpr uint32_t kPairBytes = (uint32_t)sizeof(SphereScanPair), kTripBytes = kScanTripPairs * kPairBytes;
     const SphereScanPair *__restrict__ rows = sc.sphere_scan32;
     const SphereGeom *__restrict__ spheres = sc.spheres;
-    const uint32_t n = sc.n_spheres;
-    const uint32_t n_pairs = (n + 1u) >> 1, n4 = n_pairs & ~3u;  // the last pair of an odd list is padded with a row that never passes
+    uint32_t end = ((sc.n_spheres + (uint32_t)kFilterTrip - 1u) / (uint32_t)kFilterTrip) * kTripBytes;  // bytes of whole trips
     const double a = dot(r.d, r.d);
-    const ScanRay32 f = scan_ray32(r, a, sc.scan_reach32);
+    ScanRayPairs f = scan_ray_pairs(scan_ray32(r, a, sc.scan_reach32));
     double closest = tmax;
     uint32_t best_k = kNone, count = 0;
-    SphereScanPair a0{}, a1{};
-    if (n4) {
-        a0 = load_scan_pair(rows, 0);
-        a1 = load_scan_pair(rows, 1);
-    }
-    for (uint32_t k0 = 0; k0 < n4; k0 += 4) {
-        scan_pairs_arrived(a0, a1);
-        const SphereScanPair b0 = load_scan_pair(rows, k0 + 2), b1 = load_scan_pair(rows, k0 + 3);
-        filter_pairs(a0, a1, 2u * k0, f, queue, lane, count SS_PASS);
-        const uint32_t kn = (k0 + 4 < n4) ? k0 + 4 : k0;  // last trip re-reads its own rows (stays in bounds)
-        scan_pairs_arrived(b0, b1);
-        a0 = load_scan_pair(rows, kn);
-        a1 = load_scan_pair(rows, kn + 1);
-        filter_pairs(b0, b1, 2u * k0 + 4u, f, queue, lane, count SS_PASS);
-        if (__any(count > (uint32_t)(kQueueCap - kFilterTrip))) drain_filtered<ROWS_IN_LDS>(spheres, planes_off, n_padded, queue, lane, count, r, a, tmin, closest, best_k SS_PASS);
-    }
-    for (uint32_t k = n4; k < n_pairs; k++) {  // up to three pairs left: one at a time, the second half of the call idle
-        const SphereScanPair g = load_scan_pair(rows, k);
-        const float inf = __builtin_inff();
-        const SphereScanPair none{{0.0f, 0.0f}, {0.0f, 0.0f}, {0.0f, 0.0f}, {inf, inf}};
-        filter_pairs(g, none, 2u * k, f, queue, lane, count SS_PASS);
-        if (__any(count > (uint32_t)(kQueueCap - 4))) drain_filtered<ROWS_IN_LDS>(spheres, planes_off, n_padded, queue, lane, count, r, a, tmin, closest, best_k SS_PASS);
+    if (end) {
+        SphereScanPair a0 = load_scan_pair(rows, 0u, 0u), a1 = load_scan_pair(rows, 0u, kPairBytes);
+        uint32_t off = 0;
+        do {
+            const uint32_t k0 = off / (kPairBytes / 2u);  // sphere index of the trip: used on the survivor path only
+            scan_pairs_arrived(a0, a1);
+            const SphereScanPair b0 = load_scan_pair(rows, off, 2u * kPairBytes), b1 = load_scan_pair(rows, off, 3u * kPairBytes);
+            filter_starts_here(f);
+            const unsigned long long passed = filter_pairs(a0, a1, k0, f, queue, lane, count, 0ull, [] {} SS_PASS);
+            scan_pairs_arrived(b0, b1);
+            a0 = load_scan_pair(rows, off, 4u * kPairBytes);  // the next trip's, or the padding behind the last one
+            a1 = load_scan_pair(rows, off, 5u * kPairBytes);
+            filter_starts_here(f);
+            filter_pairs(b0, b1, k0 + 4u, f, queue, lane, count, passed, [&] {
+                if (__any(count > (uint32_t)(kQueueCap - kFilterTrip))) drain_filtered<ROWS_IN_LDS>(spheres, planes_off, n_padded, queue, lane, count, r, a, tmin, closest, best_k SS_PASS);
+            } SS_PASS);
+            off += kTripBytes;
+            asm volatile("" : "+s"(off), "+s"(end));  // the loop's own two registers: every mention weighs against spilling them
+        } while (off != end);
     }
     drain_filtered<ROWS_IN_LDS>(spheres, planes_off, n_padded, queue, lane, count, r, a, tmin, closest, best_k SS_PASS);
     if (best_k == kNone) return false;

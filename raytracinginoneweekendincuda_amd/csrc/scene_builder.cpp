@@ -1160,7 +1160,7 @@ int flatten_scene(SceneImpl &s)
             std::sort(sorted.begin(), sorted.end());
             const double bulk = sorted.empty() ? 0.0 : 4.0 * sorted[sorted.size() / 2];
             f.scan_reach32 = 0.0;
-            f.sphere_scan32.assign((f.sphere_scan.size() + 1) / 2, SphereScanPair{});
+            f.sphere_scan32.assign(scan32_padded_pairs(f.sphere_scan.size()), SphereScanPair{});
             const float inf = std::numeric_limits<float>::infinity();
             for (size_t k = 0; k < 2 * f.sphere_scan32.size(); k++) {
                 SphereScanPair &pr = f.sphere_scan32[k / 2];
