@@ -228,8 +228,8 @@ typedef struct rt_render_stats {
     uint32_t kernel_vgprs;
     uint32_t lds_bytes;
     uint32_t kernel_kind;         /* which instantiation ran: world*8 + media*4 + composite*2 + rich (world 0 bvh, 1 list, 2 sphere
-                                     list) + nested*32 + library-tree*64 + grouped*128 + segmented*256 + adaptive*512 (launch_one,
-                                     csrc/render.hip) */
+                                     list) + nested*32 + library-tree*64 + grouped*128 + segmented*256 + adaptive*512 (KIND_*,
+                                     csrc/launch_plan.h) */
     uint32_t pixels_per_wave;     /* what rt_render_params.pixels_per_wave came to for this launch (64 = one lane per ray) */
 } rt_render_stats;
 
@@ -284,6 +284,29 @@ RTOW_API int rt_adaptive_converged(const rt_adaptive_params *p, uint32_t n, doub
  * stops_out[k] = the rule on (n[k], sums_rgbq[4k], [4k+1], [4k+2], q_out[k]).  Host arrays in and out. */
 RTOW_API int rt_adaptive_rule_on_device(int device, int variant, const rt_adaptive_params *p, uint32_t count, const uint32_t *n,
                                         const double *sums_rgbq, const double *sample_rgb, double *q_out, uint8_t *stops_out);
+
+/* Introspection for tests: what rt_render_launch would decide for a committed scene and these params on a GPU of num_cus
+ * compute units (film geometry from params: width, height, stripe_rows, rank, world_size; adaptive: as after
+ * rt_film_set_adaptive).  Needs no device: the launch reaches its decisions through the same function (csrc/launch_plan.h)
+ * and takes none anywhere else.  The frames do not depend on any of these fields, only the time they take. */
+typedef struct rt_launch_plan {
+    int32_t kernel_kind, lds_bytes, pixels_per_wave; /* as rt_render_stats reports them after the launch */
+    int32_t kernel, probe_kernel;  /* the instantiation of the launch and of its rehearsal (csrc/launch_plan.h KernelId; not ABI) */
+    int32_t waves_per_simd;        /* the occupancy that instantiation is compiled for */
+    int32_t lds_nodes, lds_spheres; /* node rows / sphere planes are staged in LDS */
+    int32_t reference_tree, always_walk, accelerate_lists; /* the flags of that name as the kernel choice saw them: a shutter
+                                      that lets a moving sphere leave its box forces the reference's tree, walked, no accelerated list */
+    int32_t coop_threshold, max_blocks_per_cu, probe_max_blocks_per_cu;
+    int32_t node_burst, park_ratio, leaf_batch, object_batch, rounds, shade_batch;
+    uint32_t ray_budget;
+    int32_t rank_tiles, pixel_classes; /* rehearsal: 8x8 tiles ranked by cost / heavy pixels listed and served by waves of their own */
+    int32_t probe_spp;             /* samples per pixel of the rehearsal (0: none) */
+    int32_t tile_flatness_x8;      /* tiles stay row-major where the heaviest is below this / 8 of the mean */
+    int32_t heavy_threshold, super_threshold; /* probed rays from which a pixel is listed / listed among the longest (0: no such list) */
+    int32_t near_percent, near_neighbours; /* ... or at this share of the threshold with that many of its 8 neighbours over it */
+    int32_t heavy_waves, heavy_ppw, super_ppw, heavy_priority, adaptive_ppw; /* serving waves per workgroup, pixels each takes, ... */
+} rt_launch_plan;
+RTOW_API int rt_plan_launch(rt_scene *s, const rt_render_params *params, int num_cus, int adaptive, rt_launch_plan *out);
 
 /* Upload the committed scene to a device (idempotent per device). */
 RTOW_API int rt_scene_upload(rt_scene *s, int device);

@@ -11,6 +11,7 @@ from .api import (  # noqa: F401
     Film,
     RenderParams,
     RenderStats,
+    LaunchPlan,
     builtin_scene,
     stripe_rows,
     deinterleave,

@@ -29,6 +29,16 @@ class AdaptiveParams(C.Structure):
                 ("luminance_floor", C.c_double)]
 
 
+class LaunchPlan(C.Structure):
+    """rt_launch_plan: what a launch decides (csrc/launch_plan.h); every field but ray_budget is an int32."""
+    _fields_ = [(n, C.c_uint32 if n == "ray_budget" else C.c_int32) for n in (
+        "kernel_kind", "lds_bytes", "pixels_per_wave", "kernel", "probe_kernel", "waves_per_simd", "lds_nodes", "lds_spheres",
+        "reference_tree", "always_walk", "accelerate_lists", "coop_threshold", "max_blocks_per_cu", "probe_max_blocks_per_cu",
+        "node_burst", "park_ratio", "leaf_batch", "object_batch", "rounds", "shade_batch", "ray_budget",
+        "rank_tiles", "pixel_classes", "probe_spp", "tile_flatness_x8", "heavy_threshold", "super_threshold",
+        "near_percent", "near_neighbours", "heavy_waves", "heavy_ppw", "super_ppw", "heavy_priority", "adaptive_ppw")]
+
+
 class SceneInfo(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in (
         "world_kind", "n_leaves", "n_nodes", "n_spheres", "n_moving_spheres", "n_quads", "n_objects", "n_xforms",
@@ -97,6 +107,7 @@ SIGNATURES = {
     "rt_film_device_pixels": (P, [P]),
     "rt_film_pixel_bytes": (C.c_size_t, [P]),
     "rt_film_bind_pixels": (I, [P, P]),
+    "rt_plan_launch": (I, [P, C.POINTER(RenderParams), I, I, C.POINTER(LaunchPlan)]),
     "rt_scene_upload": (I, [P, I]),
     "rt_render_launch": (I, [P, P, C.POINTER(RenderParams)]),
     "rt_render_finish": (I, [P, P, C.POINTER(RenderStats)]),

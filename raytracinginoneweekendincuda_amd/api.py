@@ -11,7 +11,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import AdaptiveParams, RenderParams, RenderStats, SceneInfo  # noqa: F401
+from ._lib import AdaptiveParams, LaunchPlan, RenderParams, RenderStats, SceneInfo  # noqa: F401
 
 
 class RtowError(RuntimeError):
@@ -241,6 +241,13 @@ class Scene:
         out = np.zeros(27, dtype=np.float64)
         _check(lib().rt_scene_dump_camera(self._p, out.ctypes.data_as(_lib.D3)))
         return out
+
+    def plan_launch(self, params, num_cus=256, adaptive=False):
+        """Tests: what a launch of this committed scene with these RenderParams decides on a GPU of ``num_cus`` compute units
+        -- kernel, LDS, schedule (rt_plan_launch; no device needed).  Returns a dict of the rt_launch_plan fields."""
+        out = LaunchPlan()
+        _check(lib().rt_plan_launch(self._p, C.byref(params), num_cus, 1 if adaptive else 0, C.byref(out)))
+        return {n: getattr(out, n) for n, _ in LaunchPlan._fields_}
 
     def upload(self, device=0):
         _check(lib().rt_scene_upload(self._p, device))

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/rtow.h"
+#include "launch_plan.h"
 #include "render_iface.h"
 #include "scene_host.h"
 
@@ -120,8 +121,8 @@ struct FilmImpl {
     SceneImpl *scene_in_flight = nullptr;  // the scene whose tables the launch in flight reads
     uint64_t last_samples = 0;
     int last_variant = 0;
-    KernelInfo last_kernel{};
-    int last_pixels_per_wave = 64;
+    rt_launch_plan last_plan{};  // of the last launch
+    KernelInfo last_kernel{};    // what launch_one reports of the kernel it was given (rt_render_stats)
     // adaptive sampling (rt_film_set_adaptive; adaptive_rule.h): the setting for the next launch, the setting the accumulated
     // frame in progress was begun with, and the per-pixel planes (allocated on first use): samples so far, sum of y^2, stopped
     bool adaptive = false, frame_adaptive = false, last_adaptive = false;
@@ -293,33 +294,11 @@ int rt_scene_upload(rt_scene *scene, int device)
         release_device_tables(dt);
         return rc;
     }
-    d.world_kind = f.world_kind;
-    d.n_world_items = (uint32_t)f.world_items.size();
-    d.n_nodes = (uint32_t)f.nodes.size();
-    d.n_world_nodes = f.n_world_nodes;
-    d.scan_cost = f.scan_cost;
-    d.n_spheres = (uint32_t)f.spheres.size();
+    scene_counts(f, d);
     d.scan_reach = f.scan_reach;
     d.scan_reach32 = f.scan_reach32;
-    d.n_mspheres = (uint32_t)f.mspheres.size();
-    d.n_quads = (uint32_t)f.quads.size();
-    d.n_objects = (uint32_t)f.objects.size();
-    d.n_boxes = (uint32_t)f.boxes.size();
-    d.n_xforms = (uint32_t)f.xforms.size();
     if (!(f.flags & SCENE_WORLD_MSPHERES)) d.ms_planes = nullptr;
-    d.ms_padded = f.ms_padded;
-    d.n_fast_nodes = (uint32_t)f.fast_nodes.size();
     if (f.fast_nodes.empty()) d.fast_nodes = nullptr;
-    d.n_seg_media = (uint32_t)f.seg_media.size();
-    d.n_seg_cand = (uint32_t)f.seg_cand.size();
-    d.lds_fast_order = d.lds_seg_media = d.lds_seg_cand = kNone;
-    d.n_media = (uint32_t)f.media.size();
-    d.n_materials = (uint32_t)f.materials.size();
-    d.n_perlin = (uint32_t)f.perlin.size();
-    d.n_group_boxes = (uint32_t)f.group_boxes.size();
-    d.lds_quad_aa = d.lds_boxes = d.lds_objects = d.lds_xforms = d.lds_media = d.lds_materials = d.lds_perlin = d.lds_spheres_tab = d.lds_group_boxes = kNone;
-    d.lds_mspheres = d.lds_msphere_aux = d.lds_sphere_aux = kNone;
-    d.flags = f.flags;
     s.device[device] = dt;
     return RT_OK;
 }
@@ -342,8 +321,10 @@ rt_film *rt_film_create(int device, int width, int height, int stripe_rows, int 
     f->stripe_rows = stripe_rows;
     f->rank = rank;
     f->world_size = world_size;
-    f->rows_owned = rt_stripe_rows(height, stripe_rows, rank, world_size, nullptr, 0);
-    f->n_pixels = (uint32_t)f->rows_owned * (uint32_t)width;
+    const FilmGeometry geometry = film_geometry(width, height, stripe_rows, rank, world_size);
+    f->rows_owned = geometry.rows_owned;
+    f->n_pixels = geometry.n_pixels;
+    f->n_tiles = geometry.n_tiles;
     size_t np = f->n_pixels ? f->n_pixels : 1;
     hipError_t e = hipMalloc((void **)&f->own_pixels, np * 3 * sizeof(double));
     if (e == hipSuccess) e = hipMemset(f->own_pixels, 0, np * 3 * sizeof(double));
@@ -356,7 +337,6 @@ rt_film *rt_film_create(int device, int width, int height, int stripe_rows, int 
         if (e == hipSuccess) f->num_cus = prop.multiProcessorCount;
     }
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&f->own_stream, hipStreamNonBlocking);
-    f->n_tiles = (((uint32_t)width + 7u) >> 3) * (((uint32_t)f->rows_owned + 7u) >> 3);
     if (e == hipSuccess) e = hipMalloc((void **)&f->tile_cost, (f->n_tiles ? f->n_tiles : 1) * sizeof(uint32_t));
     if (e == hipSuccess) e = hipMalloc((void **)&f->tile_order, (f->n_tiles ? f->n_tiles : 1) * sizeof(uint32_t));
     if (e == hipSuccess) e = hipHostMalloc((void **)&f->host_counters, kCounterWords * sizeof(unsigned long long), hipHostMallocDefault);
@@ -409,62 +389,36 @@ int rt_film_bind_pixels(rt_film *film, void *device_pixels)
     return RT_OK;
 }
 
-// Does every hit of this launch lie inside its leaf's box?  The library's own search structures -- its SAH tree, the scan of
-// all leaves of a small BVH world, the segmented walk, RT_FLAG_ACCELERATE_LISTS, the thin-wave scan -- meet the leaves in
-// another order than the reference's tree, and find the reference's closest hit only because (1) no leaf they search draws
-// random numbers and (2) no hit lies outside its leaf's box, where the reference's tree would cull it.  A moving sphere
-// leaves its box (c0 .. c1) at ray times outside its own [time0, time1] (R/MovingSphere.h:51 does not clamp frac), so
-// the camera's shutter decides, per launch.  The ray times are those of render.hip camera_ray, time0 + u * (time1 - time0),
-// with u = xorwow_uniform in [2^-33, 1] (monotone in u; the fast build fuses the multiply-add); frac is (tm - t0) / dt as in
-// msphere_center, which a unit-time row evaluates as tm itself -- the same value.
-static bool hits_stay_in_boxes(const FlatScene &f, const CameraRec &cam, int variant)
+// The strict and the fast build of render.hip, by rt_render_params::variant.
+struct Build {
+    hipError_t (*seed)(const SeedArgs &, hipStream_t);
+    hipError_t (*render)(int, const DeviceScene &, const RenderArgs &, hipStream_t);
+    hipError_t (*info)(int, const DeviceScene &, const RenderArgs &, KernelInfo *);
+    hipError_t (*adaptive_rule)(const AdaptiveRule &, uint32_t, const uint32_t *, const double *, const double *, double *, uint8_t *, hipStream_t);
+};
+static const Build kBuilds[2] = {{launch_seed_strict, launch_render_strict, kernel_info_strict, launch_adaptive_rule_strict},
+                                 {launch_seed_fast, launch_render_fast, kernel_info_fast, launch_adaptive_rule_fast}};
+
+static int seed_film(FilmImpl &f, const rt_render_params *p, hipStream_t stream)
 {
-    if (f.ms_nonfinite) return false;
-    if (f.ms_intervals.empty()) return true;
-    const double span = cam.time1 - cam.time0;
-    double tm[2];
-    const double u[2] = {(double)0x1p-33f, 1.0};
-    for (int k = 0; k < 2; k++) {
-        if (variant) {
-            tm[k] = std::fma(u[k], span, cam.time0);
-        } else {
-            volatile double prod = u[k] * span;  // no contraction: the strict build's two roundings
-            tm[k] = cam.time0 + prod;
-        }
-    }
-    for (const MsInterval &iv : f.ms_intervals)
-        for (double t : tm) {
-            const double frac = (t - iv.t0) / iv.dt;
-            if (!(frac >= 0.0 && frac <= 1.0)) return false;  // (NaN too)
-        }
-    return true;
+    SeedArgs sa{};
+    sa.state = f.state;
+    if (int rc = device_jump_table(f.device, &sa.jump_table)) return rc;
+    sa.base = xorwow_seed(p->seed, kSaltCurandDevice);
+    sa.n_pixels = f.n_pixels;
+    sa.width = f.width;
+    sa.stripe_rows = f.stripe_rows;
+    sa.rank = f.rank;
+    sa.world_size = f.world_size;
+    HIP_TRY(kBuilds[p->variant].seed(sa, stream));
+    f.seeded = true;
+    return RT_OK;
 }
 
-// Everything rt_render_launch puts on the stream: seeding, the rehearsal and its bookkeeping, the render kernel, the
-// counter copy.  Called with the film already marked in flight (a failure half-way leaves kernels running).
-static int enqueue_frame(SceneImpl &s, FilmImpl &f, const rt_render_params *p, hipStream_t stream)
+// Film bookkeeping: the frame this launch begins or adds to -- the running sums of an accumulated frame, the per-pixel
+// planes of adaptive sampling -- and where the kernel finds them.
+static int book_frame(FilmImpl &f, const rt_render_params *p, bool keep, bool continues, RenderArgs &ra, hipStream_t stream)
 {
-    const bool keep = (p->flags & RT_FLAG_KEEP_RNG_STATE) && f.seeded;
-    const bool continues = continues_frame(f, p);
-
-    HIP_TRY(hipMemsetAsync(f.ray_counter, 0, kCounterWords * sizeof(unsigned long long), stream));
-    HIP_TRY(hipEventRecord(f.ev[0], stream));
-    if (!keep) {
-        SeedArgs sa{};
-        sa.state = f.state;
-        if (int rc = device_jump_table(f.device, &sa.jump_table)) return rc;
-        sa.base = xorwow_seed(p->seed, kSaltCurandDevice);
-        sa.n_pixels = f.n_pixels;
-        sa.width = f.width;
-        sa.stripe_rows = f.stripe_rows;
-        sa.rank = f.rank;
-        sa.world_size = f.world_size;
-        HIP_TRY(p->variant ? launch_seed_fast(sa, stream) : launch_seed_strict(sa, stream));
-        f.seeded = true;
-    }
-    HIP_TRY(hipEventRecord(f.ev[1], stream));
-    RenderArgs ra{};
-    ra.pixels = f.pixels;
     if (p->flags & RT_FLAG_ACCUMULATE) {
         // progressive frame: this launch's samples are added to the film's running sums (needs the saved RNG streams)
         if (!f.accum) {
@@ -506,36 +460,30 @@ static int enqueue_frame(SceneImpl &s, FilmImpl &f, const rt_render_params *p, h
         ra.ad_q = f.ad_q;
         ra.ad_mark = f.ad_mark;
     }
+    return RT_OK;
+}
+
+// The kernel's arguments from the film, the caller's params and the plan (launch_plan.h): no decision is taken here.
+static void fill_render_args(const FilmImpl &f, const rt_render_params *p, const rt_launch_plan &plan, RenderArgs &ra)
+{
+    ra.pixels = f.pixels;
     ra.state = f.state;
     ra.ray_counter = f.ray_counter;
     ra.cursor = reinterpret_cast<uint32_t *>(f.ray_counter + 1);
-    ra.coop_threshold = p->coop_threshold > 0 ? p->coop_threshold : 24;
+    ra.coop_threshold = plan.coop_threshold;
     ra.coop_single = (p->flags & RT_FLAG_COOP_SINGLE) ? 1 : 0;
     ra.num_cus = f.num_cus;
-    ra.shade_batch = p->shade_batch > 0 ? p->shade_batch : 16;
-    ra.max_blocks_per_cu = p->max_blocks_per_cu;
-    ra.pixels_per_wave = 64;  // settled below, once the kernel is known
+    ra.shade_batch = plan.shade_batch;
+    ra.max_blocks_per_cu = plan.max_blocks_per_cu;
+    ra.pixels_per_wave = plan.pixels_per_wave;
     ra.boost_rounds = 8;
-    // A deep world BVH over composite leaves (scene 9: 400 boxes, two media, an instanced cluster): a leaf phase costs
-    // tens of node steps there, so it pays to wait until most walkers have parked.  A shallow one (Cornell box: 8
-    // leaves) gains nothing from waiting.
-    {
-        const uint32_t world_nodes = s.flat.n_world_nodes;
-        ra.node_burst = world_nodes > 64 ? 24 : 8;
-        ra.park_ratio = world_nodes > 64 ? 4 : 1;
-        ra.leaf_batch = 12;
-        ra.object_batch = 4;
-        ra.rounds = 4;
-    }
+    ra.node_burst = plan.node_burst;
+    ra.park_ratio = plan.park_ratio;
+    ra.leaf_batch = plan.leaf_batch;
+    ra.object_batch = plan.object_batch;
+    ra.rounds = plan.rounds;
     ra.overdue_priority = (p->flags & RT_FLAG_OVERDUE_PRIORITY) ? 1 : 0;
-    {
-        // Off by default: on the Book-1 scenes a cooperative ray costs ~10x a pixel-parallel one, and every budget
-        // tried (3..16 rays/sample, 2..32 boost rounds) lost more in throughput than it won back in frame tail.
-        double per_sample = p->overdue_rays_per_sample > 0 ? (double)p->overdue_rays_per_sample : 1.0e9;
-        double budget = per_sample * (double)p->samples_per_pixel;
-        ra.ray_budget = budget >= 4.0e9 ? 0xFFFFFFFFu : (uint32_t)budget;
-        if (p->overdue_rays_per_sample < 0) ra.ray_budget = 0xFFFFFFFFu;  // negative: never
-    }
+    ra.ray_budget = plan.ray_budget;
     ra.n_pixels = f.n_pixels;
     ra.width = f.width;
     ra.height = f.height;
@@ -546,177 +494,107 @@ static int enqueue_frame(SceneImpl &s, FilmImpl &f, const rt_render_params *p, h
     ra.rank = f.rank;
     ra.world_size = f.world_size;
     ra.force_general = (p->flags & RT_FLAG_FORCE_GENERAL) ? 1 : 0;
-    ra.always_walk = (p->flags & RT_FLAG_ALWAYS_WALK) ? 1 : 0;
-    ra.reference_tree = (p->flags & RT_FLAG_REFERENCE_TREE) ? 1 : 0;
+    ra.always_walk = plan.always_walk;
+    ra.reference_tree = plan.reference_tree;
     ra.exact_scan = (p->flags & RT_FLAG_EXACT_SCAN) ? 1 : 0;
-    ra.accelerate_lists = (p->flags & RT_FLAG_ACCELERATE_LISTS) ? 1 : 0;
+    ra.accelerate_lists = plan.accelerate_lists;
     ra.filter_fp64 = (p->flags & RT_FLAG_FILTER_FP64) ? 1 : 0;
-    ra.small_world = 64;  // scan budget in half sphere tests, see FlatScene::scan_cost
-    // a launch whose hits may leave their boxes takes the reference's tree in the reference's order (hits_stay_in_boxes)
-    const bool in_boxes = hits_stay_in_boxes(s.flat, s.camera, p->variant);
-    if (!in_boxes) {
-        ra.reference_tree = 1;    // no library tree, no segmented walk
-        ra.always_walk = 1;       // no scan of a small BVH world's leaves
-        ra.accelerate_lists = 0;
+    ra.small_world = (int32_t)kSmallWorldScanCost;
+}
+
+// the planes the plan's pixel classes need (allocated on first use, kept with the film)
+static int allocate_class_planes(FilmImpl &f, const rt_launch_plan &plan)
+{
+    if (!plan.pixel_classes) return RT_OK;
+    if (!f.pix_cost) {
+        HIP_TRY(hipMalloc((void **)&f.pix_cost, (size_t)f.n_pixels * sizeof(uint32_t)));
+        HIP_TRY(hipMalloc((void **)&f.heavy_list, (size_t)f.n_pixels * sizeof(uint32_t)));
+        HIP_TRY(hipMalloc((void **)&f.heavy_count, 64));
+        HIP_TRY(hipMalloc((void **)&f.pix_class, (size_t)f.n_pixels));
     }
+    if (plan.super_threshold > 0 && !f.super_list) HIP_TRY(hipMalloc((void **)&f.super_list, (size_t)f.n_pixels * sizeof(uint32_t)));
+    return RT_OK;
+}
+
+// The rehearsal and what follows from it (plan_frame has the reasons): the probe launch, the tiles ranked by its ray counts,
+// the pixels classified by them; `ra` receives the order and the lists for the render launch.
+static int enqueue_rehearsal(FilmImpl &f, const DeviceScene &ds, const rt_launch_plan &plan, const Build &build, RenderArgs &ra, hipStream_t stream)
+{
+    RenderArgs probe = ra;
+    probe.probe = 1;
+    probe.adaptive = 0;  // the rehearsal is the plain kernel's: it only counts rays
+    probe.ad_n = nullptr;
+    probe.ad_q = nullptr;
+    probe.ad_mark = nullptr;
+    probe.spp = plan.probe_spp;
+    probe.accum = nullptr;
+    probe.spp_before = 0;
+    probe.max_blocks_per_cu = plan.probe_max_blocks_per_cu;
+    probe.tile_cost = plan.rank_tiles ? f.tile_cost : nullptr;
+    probe.tile_order = nullptr;
+    probe.pix_cost = plan.pixel_classes ? f.pix_cost : nullptr;
+    if (plan.rank_tiles) HIP_TRY(hipMemsetAsync(f.tile_cost, 0, f.n_tiles * sizeof(uint32_t), stream));
+    HIP_TRY(build.render(plan.probe_kernel, ds, probe, stream));
+    if (plan.rank_tiles) {
+        HIP_TRY(launch_tile_order(f.tile_cost, f.tile_order, f.n_tiles, (uint32_t)plan.tile_flatness_x8, stream));
+        ra.tile_order = f.tile_order;
+    }
+    HIP_TRY(hipMemsetAsync(f.ray_counter, 0, 2 * sizeof(unsigned long long), stream));  // rays, (light) queue cursor
+    if (!plan.pixel_classes) return RT_OK;
+    const bool longest = plan.super_threshold > 0;
+    HIP_TRY(hipMemsetAsync(f.heavy_count, 0, 64, stream));
+    HIP_TRY(launch_classify_pixels(f.pix_cost, f.n_pixels, (uint32_t)plan.heavy_threshold, f.pix_class, f.heavy_list, f.heavy_count, stream,
+                                   longest ? f.super_list : nullptr, (uint32_t)plan.super_threshold, (uint32_t)f.width,
+                                   (uint32_t)plan.near_percent, (uint32_t)plan.near_neighbours));
+    if (longest) {
+        HIP_TRY(hipMemsetAsync(f.ray_counter + 9, 0, sizeof(unsigned long long), stream));
+        ra.super_list = f.super_list;
+        ra.super_count = f.heavy_count + 1;
+        ra.super_cursor = reinterpret_cast<uint32_t *>(f.ray_counter + 9);
+        ra.super_ppw = plan.super_ppw;
+    }
+    HIP_TRY(hipMemsetAsync(f.ray_counter + 6, 0, sizeof(unsigned long long), stream));  // heavy queue cursor
+    ra.heavy_list = f.heavy_list;
+    ra.heavy_count = f.heavy_count;
+    ra.heavy_cursor = reinterpret_cast<uint32_t *>(f.ray_counter + 6);
+    ra.heavy_waves = plan.heavy_waves;
+    ra.heavy_ppw = plan.heavy_ppw;
+    ra.heavy_priority = plan.heavy_priority;
+    ra.adaptive_ppw = plan.adaptive_ppw;
+    ra.pix_class = f.pix_class;
+    return RT_OK;
+}
+
+// Everything rt_render_launch puts on the stream: seeding, the rehearsal and its bookkeeping, the render kernel, the
+// counter copy.  Called with the film already marked in flight (a failure half-way leaves kernels running).  What runs and
+// how is plan_launch's decision (launch_plan.h); this function carries it out.
+static int enqueue_frame(SceneImpl &s, FilmImpl &f, const rt_render_params *p, hipStream_t stream)
+{
+    const bool keep = (p->flags & RT_FLAG_KEEP_RNG_STATE) && f.seeded;
+    const bool continues = continues_frame(f, p);
+    const Build &build = kBuilds[p->variant];
     const DeviceScene &ds = s.device[f.device]->scene;
-    HIP_TRY(p->variant ? kernel_info_fast(ds, ra, &f.last_kernel) : kernel_info_strict(ds, ra, &f.last_kernel));
-    const int kind = f.last_kernel.kind & 63;
-    // BVH sphere worlds: thin waves may scan all leaves together instead of walking (scan_grouped_ms), but the planes
-    // come from L2 and a chip full of thin waves scanning is bound by L2 bandwidth: measured slower than walking at every
-    // threshold (C3: 1748 Msamples/s never, 1681 at 17, 1048 at 33).  Off unless asked for.
-    if (kind < 8 && (p->coop_threshold <= 0 || !in_boxes)) ra.coop_threshold = 0;
-    // A pixel's samples are one sequential chain (one RNG stream), so a frame cannot end before its longest pixel does
-    // (glass: up to max_depth rays per sample).  One rehearsal of the first samples of every pixel -- the same RNG streams,
-    // nothing written but ray counts, cost probe_spp / spp of the frame -- serves two schedulers:
-    //  * BVH worlds, heaviest tiles first: the 8x8 tiles are ranked by rays traced and the pixel queue hands them out in
-    //    that order (in row-major order C3's queue drained at 38 ms and the last wave left at 99 ms);
-    //  * sphere-list and primitive-BVH worlds, heavy and light pixels: the few pixels with long chains (0.4 % of C2's
-    //    trace more than 10 rays per sample, up to 41) are listed; two waves of every workgroup serve that list first, a
-    //    few pixels at a time -- the lanes share each ray's scan (sphere list: a third of the latency per ray at 1.8x the
-    //    work), or simply have the wave to themselves (BVH walk) -- and then join the tile queue, whose pixels skip the
-    //    listed ones.  C2 took 367 ms where its throughput alone needs ~310.
-    // Every pixel is still rendered exactly once from its own stream: the frame is the same bit for bit
-    // (tests: ...tile_ranking..., ...heavy_and_light...; RT_FLAG_ROW_MAJOR_TILES / RT_FLAG_NO_PIXEL_CLASSES turn them off).
-    const bool bvh_kernel = kind < 8;
-    const bool sphere_list_kernel = kind >= 16 && kind < 32, prim_bvh_kernel = kind == 0;
-    const bool list_scan_kernel = kind == 8 || kind == 10;  // list scans without media: leaves can be dealt to lanes (render.hip scan_leaves_grouped)
-    //  * list worlds too (r3): a frame is a few "generations" of pixels per lane (C4: 640 k pixels on 262 k lanes), and the last
-    //    generation lasts as long as its longest pixel while ever fewer lanes are busy (C4: queue dry at 148 ms, last wave out
-    //    at 261).  Heaviest tiles first makes the pixels that start last the cheap ones.
-    const bool rank_tiles = (bvh_kernel || list_scan_kernel || sphere_list_kernel) && p->samples_per_pixel >= 32 && f.n_tiles >= 1024 &&
-                            !(p->flags & RT_FLAG_ROW_MAJOR_TILES);
-    // the deep general kernel (one 768-thread workgroup per CU, C5): its ray chains are the longest of all (a ray takes ~140 us
-    // in a full wave), which decides the frame whenever a GPU holds few pixels per lane -- a small frame, or one rank's share
-    const bool deep_kernel = kind == 7 && f.last_kernel.lds_bytes > 64 * 1024;
-    // (r3) Heavy and light pixels for this kernel too -- where the frame is a few generations of pixels on the GPU's lanes, i.e. a
-    // rank's stripes of a split frame.  C5 at 200 spp, one rank of N rendered alone: 699 / 712 / 646 / 597 / 709 / 479 ms for
-    // N = 2 / 3 / 4 / 6 / 8 / 16 without classes -- no scaling at all, every rank waits for its longest chains -- and
-    // 737 / 566 / 447 / 395 / 368 / 302 ms with them (profiles/r03_c5_roles.txt; the 8-way figure 293 with the settings of the
-    // second sweep there: ten of twelve waves serving 32 pixels each from 8 rays per sample -- most of the frame, in half-filled waves).  A whole frame (13 generations) is throughput
-    // and loses by them (1030 -> 1400 ms and worse), as it did in r2 with other settings; so: up to seven generations (a 2-way
-    // split, 672 -> 626 ms), in three bands of settings.
-    const double generations = (double)f.n_pixels / ((double)f.num_cus * 12.0 * 64.0);
-    const bool deep_roles = deep_kernel && generations <= 7.0;
-    // Both classes are served inside ONE launch, by wave (RenderArgs::heavy_list).  The library-tree kernel, whose 768-thread
-    // workgroup fills a CU: C3 2106 -> 2713 Msamples/s; the primitive-BVH kernel on the reference's tree (256-thread
-    // workgroups) gained nothing from classes (C3 1672 -> 1100-1200 with the heavy pixels in a second launch) and has none.
-    // Sphere-list worlds: serving the heavy pixels from two waves of every workgroup lets the launch keep three workgroups per
-    // CU resident (a third wave per SIMD: +15 % in the steady state, which a frame whose end is set by its long pixels could
-    // not use) -- C2 1479 (a second launch for the heavy pixels, two workgroups per CU) -> 1556 Msamples/s.
-    const bool ppw_given = p->pixels_per_wave > 0 && p->pixels_per_wave < 64;
-    const bool split = (sphere_list_kernel || (prim_bvh_kernel && (f.last_kernel.kind & 64) != 0) || deep_roles) &&
-                       !(p->flags & RT_FLAG_NO_PIXEL_CLASSES) && p->samples_per_pixel >= 64 && f.n_pixels >= 65536u && !ppw_given;
 
-    // pixels_per_wave < 64 gives every ray several lanes: the sphere list deals a ray's spheres to the lanes of a group (its
-    // heavy-pixel waves do that by themselves, above), the list-scan kernels a ray's leaves (render.hip scan_leaves_grouped).
-    // 0 = the library's choice, and that is 64 for every frame size measured: a pixel's samples are one sequential chain, a
-    // launch ends with its longest pixel, and the pass of a wave that holds a few rays takes as long as one that holds 64 --
-    // 17.6 us on the Cornell box whether the film owns 640 k pixels or 5 k (1 / 128 of C4: 118 ms for every split from 1 / 8
-    // on) -- while the grouped pass is LONGER, not shorter: the eight leaves of that world are three kinds of code, which a
-    // group of lanes executes one after the other just as one lane does, plus the exchange (C4 / 8: 117 ms at 64 pixels per
-    // wave, 182 at 32, 201 at 16, 324 at 8; profiles/r03_lanes_per_ray.txt).  The parameter stays for worlds of one kind of
-    // leaf and for experiments; the frames are bit-identical either way.
-    {
-        int ppw = ppw_given ? p->pixels_per_wave : 64;
-        if (list_scan_kernel) {  // the grouped leaf scan deals lanes in powers of two
-            int pow2 = 1;
-            while (pow2 * 2 <= ppw) pow2 *= 2;
-            ppw = pow2;
-        }
-        ra.pixels_per_wave = ppw;
-    }
-    f.last_pixels_per_wave = ra.pixels_per_wave;
-    if (ra.pixels_per_wave < 64 && list_scan_kernel)  // the instantiation that deals leaves to lanes: report that one
-        HIP_TRY(p->variant ? kernel_info_fast(ds, ra, &f.last_kernel) : kernel_info_strict(ds, ra, &f.last_kernel));
-
-    if (rank_tiles || split) {
-        // sphere-list frames of 400 samples and more rehearse 8: the heavy pixels are told apart more reliably (C2, three
-        // interleaved pairs in one call: 1859-1893 with 4, 1908-1918 with 8; the primitive-BVH kernel is better off with 4)
-        int probe_spp = split ? (p->samples_per_pixel >= 400 ? 8 : 4) : p->samples_per_pixel / 100;  // (r3: 8 for the BVH kernel too, with the settings below)
-        probe_spp = probe_spp < 1 ? 1 : (probe_spp > 8 ? 8 : probe_spp);
-        if (probe_spp > p->samples_per_pixel) probe_spp = p->samples_per_pixel;
-        if (split && !f.pix_cost) {
-            HIP_TRY(hipMalloc((void **)&f.pix_cost, (size_t)f.n_pixels * sizeof(uint32_t)));
-            HIP_TRY(hipMalloc((void **)&f.heavy_list, (size_t)f.n_pixels * sizeof(uint32_t)));
-            HIP_TRY(hipMalloc((void **)&f.heavy_count, 64));
-            HIP_TRY(hipMalloc((void **)&f.pix_class, (size_t)f.n_pixels));
-        }
-        RenderArgs probe = ra;
-        probe.probe = 1;
-        probe.adaptive = 0;  // the rehearsal is the plain kernel's: it only counts rays
-        probe.ad_n = nullptr;
-        probe.ad_q = nullptr;
-        probe.ad_mark = nullptr;
-        probe.spp = probe_spp;
-        probe.accum = nullptr;
-        probe.spp_before = 0;
-        probe.tile_cost = rank_tiles ? f.tile_cost : nullptr;
-        probe.tile_order = nullptr;
-        probe.pix_cost = split ? f.pix_cost : nullptr;
-        if (rank_tiles) HIP_TRY(hipMemsetAsync(f.tile_cost, 0, f.n_tiles * sizeof(uint32_t), stream));
-        HIP_TRY(p->variant ? launch_render_fast(ds, probe, stream) : launch_render_strict(ds, probe, stream));
-        if (rank_tiles) {
-            // the order is kept row-major only where the heaviest tile is within an eighth of the mean (r3: was x4, which sorted for
-            // glass only; C3 +1.7 % with every spread sorted, C2 / C5 indifferent between 9 / 8 and 32 / 8, one call)
-            HIP_TRY(launch_tile_order(f.tile_cost, f.tile_order, f.n_tiles, 9u, stream));
-            ra.tile_order = f.tile_order;
-        }
-        HIP_TRY(hipMemsetAsync(f.ray_counter, 0, 2 * sizeof(unsigned long long), stream));  // rays, (light) queue cursor
-        if (split) {
-            // Serving settings (r3; every number below is the mean of several frames per setting in one gpurun call -- earlier sweeps
-            // took the best of two runs and missed a bimodal default; profiles/r03_c2_serving_sweep.txt, r03_c3_serving_sweep.txt,
-            // r03_rank_serving_sweep.txt, r03_c5_roles.txt).  What per-pixel stamps showed: a light
-            // pixel just under the threshold runs at a light wave's 30-40 us per ray from the frame's first millisecond to its last,
-            // a listed pixel at 7-10 us -- threshold, serving capacity and the longest listed chain have to be moved together.
-            //   sphere lists (C2)      two tiers: from 12 rays per sample four pixels to a serving wave (16 lanes per ray), from 9 eight;
-            //                          two serving waves of four per workgroup.  Eight to a wave for all: 188...246 ms by which wave
-            //                          held the longest chains; one tier of four: 198.6 ms; two tiers: 190.5
-            //   primitive BVH (C3)     from 9 rays per sample six to a serving wave, three serving waves of twelve, eight rehearsed
-            //                          samples; from 30 rays per sample ONE to a wave (super_list): 162 -> 153 ms
-            //   deep segmented (C5)    only for frames of at most seven generations of pixels per lane (deep_roles above), 32 to a
-            //                          serving wave: 8 / 12 / 16 rays per sample and 10 / 6 / 4 serving waves of twelve for up to
-            //                          2.2 / 5 / 7 generations
-            // A frame of few generations of pixels per lane (a rank's stripes) keeps these thresholds -- lower ones helped three
-            // ranks of eight and cost the rank with the longest chains a third -- and lets its serving waves take fewer pixels each
-            // (adaptive_ppw below).
-            const bool few_generations = generations <= 3.0;  // of pixels per resident lane (twelve waves per CU)
-            const int heavy_rays_per_sample = deep_roles ? (generations <= 2.2 ? 8 : (generations <= 5.0 ? 12 : 16)) : 9;
-            const int super_rays = deep_roles ? 0 : (sphere_list_kernel ? 12 : 30);
-            const bool longest = super_rays > 0;
-            HIP_TRY(hipMemsetAsync(f.heavy_count, 0, 64, stream));
-            if (longest && !f.super_list) HIP_TRY(hipMalloc((void **)&f.super_list, (size_t)f.n_pixels * sizeof(uint32_t)));
-            HIP_TRY(launch_classify_pixels(f.pix_cost, f.n_pixels, (uint32_t)(heavy_rays_per_sample * probe_spp), f.pix_class,
-                                           f.heavy_list, f.heavy_count, stream, longest ? f.super_list : nullptr, (uint32_t)(super_rays * probe_spp),
-                                           (uint32_t)f.width, prim_bvh_kernel ? 70u : 0u, prim_bvh_kernel ? 3u : 0u));
-            // (primitive BVH worlds: a pixel probed at 70 % of the threshold with three of its eight neighbours over it is listed too --
-            // the last pixel of a C3 frame was a light one probed at 8.75 rays per sample in a patch of heavy ones, really costing 16:
-            // 152.5 -> 147.8 ms, six frames per setting; sphere lists: no difference, left off)
-            if (longest) {
-                HIP_TRY(hipMemsetAsync(f.ray_counter + 9, 0, sizeof(unsigned long long), stream));
-                ra.super_list = f.super_list;
-                ra.super_count = f.heavy_count + 1;
-                ra.super_cursor = reinterpret_cast<uint32_t *>(f.ray_counter + 9);
-                ra.super_ppw = sphere_list_kernel ? 4 : 1;
-            }
-            HIP_TRY(hipMemsetAsync(f.ray_counter + 6, 0, sizeof(unsigned long long), stream));  // heavy queue cursor
-            if (sphere_list_kernel && ra.max_blocks_per_cu <= 0) ra.max_blocks_per_cu = 3;
-            ra.heavy_list = f.heavy_list;
-            ra.heavy_count = f.heavy_count;
-            ra.heavy_cursor = reinterpret_cast<uint32_t *>(f.ray_counter + 6);
-            ra.heavy_waves = deep_roles ? (generations <= 2.2 ? 10 : (generations <= 5.0 ? 6 : 4)) : (sphere_list_kernel ? 2 : 3);
-            ra.heavy_ppw = deep_roles ? 32 : (sphere_list_kernel ? 8 : 6);
-            ra.heavy_priority = sphere_list_kernel ? 3 : 0;  // the serving waves' rays are the frame's critical path
-            // fewer pixels per serving wave than the tuned numbers where the light pixels are few -- up to three generations of
-            // pixels per lane, i.e. a rank's stripes of a split frame: the light side is short there and a listed chain is
-            // shortest with its wave to itself (slowest rank, C2 / 4: 132 -> 119 ms, / 8: 135 -> 97; C3 / 2: 153 -> 135, / 4:
-            // 154 -> 124, / 8: 155 -> 122).  A full frame packs the serving waves as densely as tuned: the ones left over join
-            // the light queue at once (C3, 4.9 generations: 152 against 159 ms).
-            ra.adaptive_ppw = few_generations ? 1 : 0;
-            ra.pix_class = f.pix_class;
-        }
-    }
-    HIP_TRY(p->variant ? launch_render_fast(ds, ra, stream) : launch_render_strict(ds, ra, stream));
+    HIP_TRY(hipMemsetAsync(f.ray_counter, 0, kCounterWords * sizeof(unsigned long long), stream));
+    HIP_TRY(hipEventRecord(f.ev[0], stream));
+    if (!keep)
+        if (int rc = seed_film(f, p, stream)) return rc;
+    HIP_TRY(hipEventRecord(f.ev[1], stream));
+    RenderArgs ra{};
+    if (int rc = book_frame(f, p, keep, continues, ra, stream)) return rc;
+    const FilmGeometry geometry{f.width, f.height, f.rows_owned, f.n_pixels, f.n_tiles};
+    const rt_launch_plan plan = plan_launch(ds, geometry, f.num_cus, *p, f.adaptive, hits_stay_in_boxes(s.flat, s.camera, p->variant));
+    fill_render_args(f, p, plan, ra);
+    KernelInfo info{};
+    HIP_TRY(build.info(plan.kernel, ds, ra, &info));  // the registers the compiler gave it; the rest is the plan's
+    if (info.kind != plan.kernel_kind || info.lds_bytes != plan.lds_bytes)
+        return fail(RT_ERR_STATE, "rt_render_launch: the kernel is not the one the launch plan describes");
+    f.last_plan = plan;
+    f.last_kernel = info;
+    if (int rc = allocate_class_planes(f, plan)) return rc;
+    if (plan.probe_spp > 0)
+        if (int rc = enqueue_rehearsal(f, ds, plan, build, ra, stream)) return rc;
+    HIP_TRY(build.render(plan.kernel, ds, ra, stream));
     HIP_TRY(hipEventRecord(f.ev[2], stream));
     // The counters come home on the film's own stream: a blocking hipMemcpy in rt_render_finish would wait for every
     // other film's frame as well and serialise frames that were launched to overlap.
@@ -764,6 +642,36 @@ int rt_render_launch(rt_scene *scene, rt_film *film, const rt_render_params *p)
     return RT_OK;
 }
 
+#if RT_PHASES  // diagnostic builds (make EXTRA=-DRT_PHASES=1 LIBNAME=...): the per-phase table
+static void print_phases(const FilmImpl &f)
+{
+    const unsigned long long *c = f.host_counters;
+    const char *name[24] = {"node step", "leaf test", "shade", "refill", "  group/instance", "  medium", "  primitive", "",
+                            "    record+xforms", "    box", "    sub-BVH", "    other geometry", "between walks again", "limited node pass", "node visits (lanes)", "",
+                            "box pass", "medium pass / between walks", "object pass", "primitive pass", "  hit record", "  scatter",
+                            "  next camera ray", "  pixel done"};
+    if (is_sphere_list_kernel(f.last_kernel.kind)) {  // slots 0 / 1 are its two scans
+        name[0] = "scan, pixel-parallel";
+        name[1] = "scan, cooperative";
+        name[12] = name[13] = "";  // slots 12, 13, 15: the survivor counts of the pixel-parallel scan (render.hip ScanSums)
+        const double passes = (double)c[96 + 0], groups = (double)c[96 + 12], taken = (double)c[64 + 12];
+        if (groups > 0) {
+            std::fprintf(stderr, "survivors: %.0f passes, %.2f groups of 4 per pass, groups taken f = %.4f\n", passes, groups / passes, taken / groups);
+            std::fprintf(stderr, "survivors: spheres with a passing lane per taken group %.3f, lane appends per pass %.1f, lanes behind per pass %.2f\n",
+                         (double)c[32 + 12] / taken, (double)c[96 + 13] / passes, (double)c[64 + 13] / passes);
+            std::fprintf(stderr, "survivors: drains per pass %.2f, drain iterations (wave max of count) per pass %.2f, drain cycles %.1f %% of the "
+                         "pixel-parallel scan's (%.0f of %.0f per pass)\n", (double)c[96 + 15] / passes, (double)c[64 + 15] / passes,
+                         100.0 * c[32 + 13] / c[32 + 0], (double)c[32 + 13] / passes, (double)c[32 + 0] / passes);
+        }
+    }
+    const double total = (double)c[7];
+    for (int k = 0; k < 24; k++)
+        if (name[k][0] && c[96 + k])
+            std::fprintf(stderr, "phase %-20s: %5.1f %% of wave time, %10llu passes, %5.1f lanes/pass, %7.0f cycles/pass\n", name[k],
+                         100.0 * c[32 + k] / total, c[96 + k], (double)c[64 + k] / c[96 + k], (double)c[32 + k] / c[96 + k]);
+}
+#endif
+
 int rt_render_finish(rt_scene *scene, rt_film *film, rt_render_stats *stats)
 {
     (void)scene;
@@ -781,33 +689,8 @@ int rt_render_finish(rt_scene *scene, rt_film *film, rt_render_stats *stats)
         HIP_TRY(hipEventElapsedTime(&ms_seed, f.ev[0], f.ev[1]));
         HIP_TRY(hipEventElapsedTime(&ms_render, f.ev[1], f.ev[2]));
         const unsigned long long rays = f.host_counters[0];
-#if RT_PHASES  // diagnostic builds (make EXTRA=-DRT_PHASES=1 LIBNAME=...): the per-phase table
-        {
-            const unsigned long long *c = f.host_counters;
-            const char *name[24] = {"node step", "leaf test", "shade", "refill", "  group/instance", "  medium", "  primitive", "",
-                                    "    record+xforms", "    box", "    sub-BVH", "    other geometry", "between walks again", "limited node pass", "node visits (lanes)", "",
-                                    "box pass", "medium pass / between walks", "object pass", "primitive pass", "  hit record", "  scatter",
-                                    "  next camera ray", "  pixel done"};
-            if ((f.last_kernel.kind & 63) >= 16) {  // sphere-list kernel: slots 0 / 1 are its two scans
-                name[0] = "scan, pixel-parallel";
-                name[1] = "scan, cooperative";
-                name[12] = name[13] = "";  // slots 12, 13, 15: the survivor counts of the pixel-parallel scan (render.hip ScanSums)
-                const double passes = (double)c[96 + 0], groups = (double)c[96 + 12], taken = (double)c[64 + 12];
-                if (groups > 0) {
-                    std::fprintf(stderr, "survivors: %.0f passes, %.2f groups of 4 per pass, groups taken f = %.4f\n", passes, groups / passes, taken / groups);
-                    std::fprintf(stderr, "survivors: spheres with a passing lane per taken group %.3f, lane appends per pass %.1f, lanes behind per pass %.2f\n",
-                                 (double)c[32 + 12] / taken, (double)c[96 + 13] / passes, (double)c[64 + 13] / passes);
-                    std::fprintf(stderr, "survivors: drains per pass %.2f, drain iterations (wave max of count) per pass %.2f, drain cycles %.1f %% of the "
-                                 "pixel-parallel scan's (%.0f of %.0f per pass)\n", (double)c[96 + 15] / passes, (double)c[64 + 15] / passes,
-                                 100.0 * c[32 + 13] / c[32 + 0], (double)c[32 + 13] / passes, (double)c[32 + 0] / passes);
-                }
-            }
-            const double total = (double)c[7];
-            for (int k = 0; k < 24; k++)
-                if (name[k][0] && c[96 + k])
-                    std::fprintf(stderr, "phase %-20s: %5.1f %% of wave time, %10llu passes, %5.1f lanes/pass, %7.0f cycles/pass\n", name[k],
-                                 100.0 * c[32 + k] / total, c[96 + k], (double)c[64 + k] / c[96 + k], (double)c[32 + k] / c[96 + k]);
-        }
+#if RT_PHASES
+        print_phases(f);
 #endif
         stats->samples = f.last_adaptive ? (uint64_t)f.host_counters[2] : f.last_samples;  // adaptive: what the waves counted
         stats->rays = rays;
@@ -818,7 +701,7 @@ int rt_render_finish(rt_scene *scene, rt_film *film, rt_render_stats *stats)
         stats->kernel_vgprs = (uint32_t)f.last_kernel.vgprs;
         stats->lds_bytes = (uint32_t)f.last_kernel.lds_bytes;
         stats->kernel_kind = (uint32_t)f.last_kernel.kind;
-        stats->pixels_per_wave = (uint32_t)f.last_pixels_per_wave;
+        stats->pixels_per_wave = (uint32_t)f.last_plan.pixels_per_wave;
     }
     return RT_OK;
 }
@@ -896,8 +779,7 @@ int rt_adaptive_rule_on_device(int device, int variant, const rt_adaptive_params
     for (int k = 0; k < 5 && e == hipSuccess; k++) e = hipMalloc(&dev[k], bytes[k]);
     for (int k = 0; k < 3 && e == hipSuccess; k++) e = hipMemcpy(dev[k], host_in[k], bytes[k], hipMemcpyHostToDevice);
     if (e == hipSuccess) {
-        auto launch = variant ? launch_adaptive_rule_fast : launch_adaptive_rule_strict;
-        e = launch(to_rule(*p), count, (const uint32_t *)dev[0], (const double *)dev[1], (const double *)dev[2], (double *)dev[3], (uint8_t *)dev[4], nullptr);
+        e = kBuilds[variant].adaptive_rule(to_rule(*p), count, (const uint32_t *)dev[0], (const double *)dev[1], (const double *)dev[2], (double *)dev[3], (uint8_t *)dev[4], nullptr);
     }
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e == hipSuccess) e = hipMemcpy(q_out, dev[3], bytes[3], hipMemcpyDeviceToHost);

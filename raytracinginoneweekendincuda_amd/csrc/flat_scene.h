@@ -119,7 +119,7 @@ struct BvhNodeRec { double xlo, xhi, ylo, yhi, zlo, zhi; uint32_t a, b, escape, 
 // searched -- the reference's BVH == list invariant, Docs 2-3 BVH :733,:772 -- as long as two things hold: no leaf draws
 // random numbers, and every hit lies inside its leaf's box.  The second fails for a moving sphere at a ray time outside its
 // own [time0, time1] (R/MovingSphere.h:51 does not clamp), so a launch whose shutter allows that walks the reference's tree
-// instead (device_scene.cpp hits_stay_in_boxes).  Where both hold, instead of
+// instead (launch_plan.cpp hits_stay_in_boxes).  Where both hold, instead of
 // the reference's median-split tree in its fixed visiting order (36 node visits and 5 leaf tests per ray on the random-
 // spheres scene) the kernel may walk a surface-area-heuristic tree near child first.  Still a stackless walk over a flat
 // array: every node carries, for each of the eight sign octants of the ray direction, the node to go to when its box is hit
@@ -245,7 +245,7 @@ struct DeviceScene {
     // dynamic LDS block, set by the launcher per table; kNone = read the global table.
     uint32_t lds_quad_aa, lds_boxes, lds_objects, lds_xforms, lds_media, lds_materials, lds_perlin, lds_spheres_tab, lds_group_boxes,
         lds_mspheres, lds_msphere_aux, lds_sphere_aux;  // the primitive tables of a sphere world (library-tree kernel, one workgroup per CU)
-    uint32_t lds_fast_order, lds_seg_media, lds_seg_cand;  // segmented walk: always staged (render.hip launch_one)
+    uint32_t lds_fast_order, lds_seg_media, lds_seg_cand;  // segmented walk: always staged (launch_plan.cpp lds_layout)
     uint32_t lds_park;  // parked path state of the instanced-list kernel (render.hip Traits::PARK)
     uint32_t flags;
 };

@@ -30,6 +30,7 @@
 #include <type_traits>
 
 #include "flat_scene.h"
+#include "launch_plan.h"
 #include "render_iface.h"
 #include "rng.h"
 
@@ -1106,7 +1107,6 @@ DEV bool fast_row_hit(uint32_t base, const Walk &w, double closest)
 }
 // The rows are only ever read from LDS (the launcher falls back to the reference-tree kernel when they do not fit): a
 // branch between an LDS and a global copy made the compiler merge the two into generic pointers and flat loads.
-[[maybe_unused]] constexpr uint32_t kFastLdsBudget = 60 * 1024;
 DEV void walk_node_fast(const Ray &r, double tmin, Walk &w)
 {
     const uint32_t n = w.state;
@@ -3694,7 +3694,7 @@ using TBvhSegmented = Traits<0, true, true, 3, true, true, false, 768, true>;
 // scenes: for up to 16 leaves within a cost budget (FlatScene::scan_cost) a scan of all of them in the tree's leaf order -- every lane on the same leaf, rows
 // through uniform loads, no node visits, no phases -- beats walking the tree (Cornell box: 8 leaves, 7 nodes).  Without
 // media no leaf draws random numbers, and as long as every hit lies inside its leaf's box (a moving sphere leaves its box at
-// ray times outside its own interval: the launcher then walks, device_scene.cpp hits_stay_in_boxes), the closest hit is the
+// ray times outside its own interval: the launcher then walks, launch_plan.cpp hits_stay_in_boxes), the closest hit is the
 // one the walk finds (the reference's own BVH = list invariant; `tests/test_parity_gpu.py::test_small_world_scan_equals_the_bvh_walk`).
 // General nesting (REF_TREE leaves, tree_hit): the general kernels plus the interpreter.  Its stack of 16 frames lives in
 // scratch -- the reference's own recursion needs a 32 KiB stack per thread (R/kernel.cu:599) -- so these instantiations
@@ -3708,167 +3708,66 @@ using TListInstances = Traits<1, true, false, 4, false>;
 // -- the SIMDs' issue slots are nearly full with four waves -- so in the steady state it is the slower of the two; but a pixel's
 // samples are one chain, pixels of these worlds all cost about the same, and a frame is therefore a whole number of pixel
 // "generations" on the resident lanes: 800 x 800 pixels are 2.44 generations on the 262 144 lanes of four waves per SIMD -- three,
-// the last 44 % full -- and 1.95 on the 327 680 of five: two.  dispatch() picks by that count (list_instances_waves).
+// the last 44 % full -- and 1.95 on the 327 680 of five: two.  launch_plan.cpp choose_kernel picks by that count (list_instances_waves).
 using TListInstances5 = Traits<1, true, false, 5, false>;
 // The same two with the leaves of every ray dealt to lanes (pixels_per_wave < 64: fewer pixels than lanes, the frame is bound
 // by the latency of a ray, not by throughput -- registers matter more than a fourth wave)
 using TListPrimsGrouped = Traits<1, false, false, 3, false, false, false, 256, false, true>;
 using TListInstancesGrouped = Traits<1, true, false, 3, false, false, false, 256, false, true>;
 
-// Do the node rows and the sphere / material rows of a primitive world fit the library-tree kernel's LDS?  (The same sums as
-// launch_one<TBvhPrimsFast>'s placement, for callers that have no reference tree to fall back to.)
-[[maybe_unused]] static bool fast_rows_fit(const DeviceScene &sc)
+// The host-only planner (launch_plan.h) describes these instantiations by a table of its own: the two must agree.
+template <class T>
+constexpr KernelProps props_of()
 {
-    auto up = [](size_t b) { return (b + 15) & ~(size_t)15; };
-    const size_t nodes = (size_t)sc.n_fast_nodes * kFastNodeBytes;
-    if (nodes > 60 * 1024) return false;
-    const size_t rows = up(nodes) + up((size_t)sc.n_mspheres * sizeof(MSphereGeom)) + up((size_t)sc.n_mspheres * sizeof(SphereAux)) +
-                        up((size_t)sc.n_spheres * sizeof(SphereGeom)) + up((size_t)sc.n_spheres * sizeof(SphereAux)) +
-                        up((size_t)sc.n_materials * sizeof(MaterialRec));
-    return rows + 5 * 64 <= 158 * 1024;
+    return KernelProps{T::WORLD, T::COMPOSITE, T::RICH, T::MEDIA, T::BATCH, T::NESTED, T::BLOCK, T::FAST, T::SEG, T::GROUPED, T::PARK, T::MIN_WAVES};
 }
+#define RT_SAME_KERNEL(ID, T) static_assert(same_props(kKernelProps[ID], props_of<T>()), "launch_plan.h kKernelProps[" #ID "] is not " #T)
+RT_SAME_KERNEL(K_SPHERE_LIST, TSphereList); RT_SAME_KERNEL(K_BVH_PRIMS, TBvhPrims); RT_SAME_KERNEL(K_BVH_PRIMS_FAST, TBvhPrimsFast);
+RT_SAME_KERNEL(K_LIST_PRIMS, TListPrims); RT_SAME_KERNEL(K_LIST_INSTANCES, TListInstances); RT_SAME_KERNEL(K_LIST_INSTANCES_5, TListInstances5);
+RT_SAME_KERNEL(K_LIST_PRIMS_GROUPED, TListPrimsGrouped); RT_SAME_KERNEL(K_LIST_INSTANCES_GROUPED, TListInstancesGrouped);
+RT_SAME_KERNEL(K_LIST_GENERAL, TListGeneral); RT_SAME_KERNEL(K_LIST_NESTED, TListNested); RT_SAME_KERNEL(K_BVH_INSTANCES, TBvhInstances);
+RT_SAME_KERNEL(K_BVH_MEDIA, TBvhMedia); RT_SAME_KERNEL(K_BVH_GENERAL, TBvhGeneral); RT_SAME_KERNEL(K_BVH_GENERAL_DEEP, TBvhGeneralDeep);
+RT_SAME_KERNEL(K_BVH_SEGMENTED, TBvhSegmented); RT_SAME_KERNEL(K_BVH_NESTED, TBvhNested);
+static_assert(kBigBlock == kBigBlockThreads && kLdsNodeBytes == kStagedNodeBytes && kFastNodeBytes == sizeof(FastNodeF) &&
+                  kQueueCap * 64 * sizeof(uint16_t) == kSurvivorQueueBytesPerWave && kParkBytesPerThread == kParkedBytesPerThread,
+              "launch_plan.h lays the LDS out with other sizes than the kernels read it with");
 
+// One instantiation, as planned: the LDS layout is lds_layout's (the planner chose T because it fits), the grid is persistent.
 template <class T>
 hipError_t launch_one(const DeviceScene &sc_in, RenderArgs a, hipStream_t stream, KernelInfo *info)
 {
-    DeviceScene sc = sc_in;
-    [[maybe_unused]] const RenderArgs a_in = a;
     if (!T::ROLES && a.heavy_list) return hipErrorInvalidValue;  // this instantiation has no serving waves (Traits::ROLES): its listed pixels would never be rendered
     if (T::ADAPTIVE != (a.adaptive != 0) || (T::ADAPTIVE && (a.probe || !a.ad_n || !a.ad_q || !a.ad_mark))) return hipErrorInvalidValue;  // rehearsals run the plain kernels
     auto kernel = render_kernel<RT_STRICT, T>;
     uint32_t tiles = (((uint32_t)a.width + 7u) >> 3) * (((uint32_t)a.rows_owned + 7u) >> 3);
-    size_t lds = 0;
-    a.lds_nodes = 0;
-    if (T::WORLD == 0) {
-        size_t need = (T::FAST || T::SEG) ? (size_t)sc.n_fast_nodes * kFastNodeBytes : (size_t)sc.n_world_nodes * kLdsNodeBytes;
-        if (need <= 60 * 1024) {  // keep >= 2 workgroups (of 256 threads) per CU resident
-            lds = need;
-            a.lds_nodes = 1;
-        }
-        if (T::FAST && T::BLOCK >= kBigBlock && a.lds_nodes) {
-            // One workgroup per CU: the sphere rows the leaf tests and the hit record read and the material rows follow the
-            // node rows into the CU's LDS -- a frame ends with its longest pixel, and that pixel's chain is made of exactly
-            // these dependent reads (C3: leaf pass 2100 -> ... cycles, shading pass 11000 -> ... cycles).
-            const size_t budget = 158 * 1024;
-            size_t off = (lds + 15) & ~(size_t)15;
-            auto place = [&](uint32_t &slot, size_t bytes) {
-                if (bytes == 0 || off + bytes + 64 > budget) return;
-                slot = (uint32_t)off;
-                off += (bytes + 15) & ~(size_t)15;
-            };
-            place(sc.lds_mspheres, (size_t)sc.n_mspheres * sizeof(MSphereGeom));
-            place(sc.lds_msphere_aux, (size_t)sc.n_mspheres * sizeof(SphereAux));
-            place(sc.lds_spheres_tab, (size_t)sc.n_spheres * sizeof(SphereGeom));
-            place(sc.lds_sphere_aux, (size_t)sc.n_spheres * sizeof(SphereAux));
-            place(sc.lds_materials, (size_t)sc.n_materials * sizeof(MaterialRec));
-            lds = off;
-        }
-        if constexpr (T::FAST && T::BLOCK >= kBigBlock) {
-            // The library-tree kernel reads these rows from LDS only (no global side in its accessors: head of
-            // render_kernel); a world whose rows do not fit is walked by the reference-tree kernel.
-            const bool fits = a.lds_nodes && (sc.n_mspheres == 0 || (sc.lds_mspheres != kNone && sc.lds_msphere_aux != kNone)) &&
-                              (sc.n_spheres == 0 || (sc.lds_spheres_tab != kNone && sc.lds_sphere_aux != kNone)) &&
-                              (sc.n_materials == 0 || sc.lds_materials != kNone);
-            if (!fits) return launch_one<Like<T, TBvhPrims>>(sc_in, a_in, stream, info);
-            auto empty = [](uint32_t &slot) { if (slot == kNone) slot = 0; };  // an empty table is never read
-            empty(sc.lds_mspheres); empty(sc.lds_msphere_aux); empty(sc.lds_spheres_tab); empty(sc.lds_sphere_aux); empty(sc.lds_materials);
-        }
-        if constexpr (T::SEG) {  // the leaf positions per node and the media, right behind the node rows
-            size_t off = (lds + 15) & ~(size_t)15;
-            sc.lds_fast_order = (uint32_t)off;
-            off += ((size_t)sc.n_fast_nodes * sizeof(FastOrder) + 15) & ~(size_t)15;
-            sc.lds_seg_media = (uint32_t)off;
-            off += ((size_t)(sc.n_seg_media ? sc.n_seg_media : 1u) * sizeof(SegMedium) + 15) & ~(size_t)15;
-            sc.lds_seg_cand = (uint32_t)off;
-            off += ((size_t)(sc.n_seg_cand ? sc.n_seg_cand : 1u) * sizeof(SegCandidate) + 15) & ~(size_t)15;
-            lds = off;
-        }
-        if (T::COMPOSITE) {
-            // Small tables ride along behind the node rows, each on its own merits: the records a leaf test or the shading
-            // chases through (object -> transforms -> medium; material rows; Perlin tables: a few KB even in the Book-2
-            // final scene) and, where they fit as well, the quad / box rows (Cornell box: 2 KB).
-            // three 256-thread workgroups per CU share its 160 KB, or one of 768 threads has (nearly) all of it
-            const size_t budget = T::BLOCK >= kBigBlock ? 158 * 1024 : 52 * 1024;
-            size_t off = (lds + 15) & ~(size_t)15;
-            auto place = [&](uint32_t &slot, size_t bytes, size_t cap) {
-                if (bytes == 0 || bytes > cap || off + bytes + 64 > budget) return;
-                slot = (uint32_t)off;
-                off += (bytes + 15) & ~(size_t)15;
-            };
-            place(sc.lds_objects, (size_t)sc.n_objects * sizeof(ObjectRec), 4096);
-            place(sc.lds_xforms, (size_t)sc.n_xforms * sizeof(Xform), 4096);
-            place(sc.lds_media, (size_t)sc.n_media * sizeof(MediumRec), 2048);
-            place(sc.lds_group_boxes, (size_t)sc.n_group_boxes * sizeof(GroupBox), 4096);
-            place(sc.lds_materials, (size_t)sc.n_materials * sizeof(MaterialRec), 4096);
-            if (T::RICH) place(sc.lds_perlin, (size_t)sc.n_perlin * sizeof(PerlinRec), 2 * sizeof(PerlinRec));
-            const size_t b_quads = (size_t)sc.n_quads * sizeof(AAQuad), b_boxes = (size_t)sc.n_boxes * sizeof(BoxRec);
-            if (T::BLOCK >= kBigBlock) {  // the big tables, most useful first
-                place(sc.lds_boxes, b_boxes, 80 * 1024);
-                place(sc.lds_spheres_tab, (size_t)sc.n_spheres * sizeof(SphereGeom), 40 * 1024);
-                place(sc.lds_quad_aa, b_quads, 16 * 1024);
-            } else if (b_quads + b_boxes <= 16 * 1024 && off + b_quads + b_boxes + 96 <= budget) {
-                place(sc.lds_quad_aa, b_quads, 16 * 1024);
-                place(sc.lds_boxes, b_boxes, 16 * 1024);
-            }
-            lds = off;
-            if constexpr (T::BATCH && T::BLOCK >= kBigBlock) {
-                // The deep kernel reads its node rows and every table from LDS only (its accessors have no global side: see
-                // the head of render_kernel).  A scene that does not fit goes to the general kernel, which reads what is
-                // not staged from L2.
-                const bool fits = a.lds_nodes && (sc.n_objects == 0 || sc.lds_objects != kNone) && (sc.n_xforms == 0 || sc.lds_xforms != kNone) &&
-                                  (sc.n_media == 0 || sc.lds_media != kNone) && (sc.n_group_boxes == 0 || sc.lds_group_boxes != kNone) &&
-                                  (sc.n_materials == 0 || sc.lds_materials != kNone) && (sc.n_perlin == 0 || sc.lds_perlin != kNone) &&
-                                  (sc.n_boxes == 0 || sc.lds_boxes != kNone) && (sc.n_spheres == 0 || sc.lds_spheres_tab != kNone);
-                // (the quad rows stay optional: a box's six faces are read only for a hit point on one of its edges)
-                if constexpr (T::SEG) {  // the reference's tree in the reference's order instead
-                    if (!fits || !(sc.flags & SCENE_SEGMENTED) || sc.fast_nodes == nullptr || sc.n_seg_media > kSegMaxMedia)
-                        return launch_one<Like<T, TBvhGeneralDeep>>(sc_in, a_in, stream, info);
-                } else {
-                    if (!fits) return launch_one<Like<T, TBvhGeneral>>(sc_in, a_in, stream, info);
-                }
-                auto empty = [](uint32_t &slot) { if (slot == kNone) slot = 0; };  // an empty table is never read
-                empty(sc.lds_objects); empty(sc.lds_xforms); empty(sc.lds_media); empty(sc.lds_group_boxes); empty(sc.lds_materials);
-                empty(sc.lds_perlin); empty(sc.lds_boxes); empty(sc.lds_spheres_tab);
-            }
-        }
-    } else if (T::WORLD == 2) {
-        lds = (T::BLOCK / 64) * kQueueCap * 64 * sizeof(uint16_t);
-        size_t planes = (size_t)((sc.n_spheres + 63u) & ~63u) * 5 * sizeof(double);
-        a.lds_spheres = 0;
-        if (planes <= 48 * 1024) {
-            lds += planes;
-            a.lds_spheres = 1;
-        }
-    }
-    if constexpr (T::PARK) {  // the parked path state, one entry per thread (list worlds stage no tables: their rows come through scalar loads)
-        const size_t off = (lds + 15) & ~(size_t)15;
-        sc.lds_park = (uint32_t)off;
-        lds = off + (size_t)T::BLOCK * kParkBytesPerThread;
-    }
+    constexpr KernelProps props = props_of<T>();
+    const LdsLayout layout = lds_layout(props, sc_in);
+    if (!layout.fits) return hipErrorInvalidValue;  // choose_kernel picks an instantiation that reads its tables from LDS only where they fit
+    DeviceScene sc = sc_in;
+    apply_layout(layout, sc);
+    a.lds_nodes = layout.lds_nodes;
+    a.lds_spheres = layout.lds_spheres;
+    const size_t lds = layout.bytes;
     if (info) {
         hipFuncAttributes attr;
         hipError_t e = hipFuncGetAttributes(&attr, reinterpret_cast<const void *>(kernel));
         if (e != hipSuccess) return e;
         info->vgprs = attr.numRegs;
         info->lds_bytes = (int)(attr.sharedSizeBytes + lds);
-        info->kind = T::WORLD * 8 + (T::MEDIA ? 4 : 0) + (T::COMPOSITE ? 2 : 0) + (T::RICH ? 1 : 0) + (T::NESTED ? 32 : 0) + (T::FAST ? 64 : 0) +
-                     (T::GROUPED ? 128 : 0) + (T::SEG ? 256 : 0) + (T::ADAPTIVE ? 512 : 0);
+        info->kind = kernel_kind(props, T::ADAPTIVE);
         return hipSuccess;
     }
     if (a.n_pixels == 0 || a.spp <= 0) return hipSuccess;
     // persistent grid: as many workgroups as the chip holds at once (never more than there are tiles)
     int per_cu = 0;
-    if (lds > 48 * 1024) {  // more dynamic LDS than the default limit: ask for it (up to the CU's 160 KB)
+    if (lds > kDefaultDynamicLds) {  // more dynamic LDS than the default limit: ask for it (up to the CU's 160 KB)
         hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (ea != hipSuccess) return ea;
     }
     hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, T::BLOCK, lds);
     if (e != hipSuccess) return e;
     if (per_cu < 1) per_cu = 1;
-    // Sphere-list worlds: two resident workgroups per CU beat three although three fit -- a third wave per SIMD
-    // speeds the steady state up, but with fewer pixels per lane the frame tail grows by more (measured on C2).
-    int cap = a.max_blocks_per_cu > 0 ? a.max_blocks_per_cu : (T::WORLD == 2 ? 2 : 0);
-    if (cap > 0 && per_cu > cap) per_cu = cap;
+    if (a.max_blocks_per_cu > 0 && per_cu > a.max_blocks_per_cu) per_cu = a.max_blocks_per_cu;  // (plan_frame: sphere lists)
     uint32_t resident = (uint32_t)per_cu * (uint32_t)(a.num_cus > 0 ? a.num_cus : 256);
     constexpr uint32_t kWavesPerBlock = (uint32_t)T::BLOCK / 64u;
     uint32_t blocks = (tiles + kWavesPerBlock - 1u) / kWavesPerBlock;
@@ -3880,12 +3779,9 @@ hipError_t launch_one(const DeviceScene &sc_in, RenderArgs a, hipStream_t stream
 
 } // namespace
 
-// instantiations of group 1, by id (defined in the RT_GROUP == 1 translation unit)
-enum CompositeKernel { CK_LIST_PRIMS, CK_LIST_INSTANCES, CK_LIST_GENERAL, CK_LIST_NESTED, CK_BVH_INSTANCES, CK_BVH_MEDIA,
-                       CK_BVH_GENERAL, CK_BVH_GENERAL_DEEP, CK_BVH_NESTED, CK_LIST_PRIMS_GROUPED, CK_LIST_INSTANCES_GROUPED, CK_BVH_SEGMENTED, CK_LIST_INSTANCES_5 };
+// From the planner's kernel id (launch_plan.h KernelId) to its instantiation.  The ids of group 1 are served by the
+// RT_GROUP == 1 translation unit, the Adaptive<> forms of both groups by translation units of their own (RT_ADAPT == 1).
 hipError_t RT_CAT(launch_composite_, RT_SUFFIX)(int which, const DeviceScene &sc, const RenderArgs &a, hipStream_t stream, KernelInfo *info);
-// ... of group 0, and the Adaptive<> forms of both (each group's in a translation unit of their own, RT_ADAPT == 1)
-enum PrimsKernel { PK_SPHERE_LIST, PK_BVH_PRIMS, PK_BVH_PRIMS_FAST };
 hipError_t RT_CAT(launch_adaptive_prims_, RT_SUFFIX)(int which, const DeviceScene &sc, const RenderArgs &a, hipStream_t stream, KernelInfo *info);
 hipError_t RT_CAT(launch_adaptive_composite_, RT_SUFFIX)(int which, const DeviceScene &sc, const RenderArgs &a, hipStream_t stream, KernelInfo *info);
 
@@ -3896,24 +3792,22 @@ hipError_t launch_composite_as(int which, const DeviceScene &sc, const RenderArg
 {
     using Any = std::conditional_t<AD, Adaptive<TListPrims>, TListPrims>;  // Like<Any, U>: U, adaptive or not
     switch (which) {
-    case CK_LIST_PRIMS: return launch_one<Like<Any, TListPrims>>(sc, a, stream, info);
-    case CK_LIST_INSTANCES: return launch_one<Like<Any, TListInstances>>(sc, a, stream, info);
-    case CK_LIST_INSTANCES_5:
-        // Adaptive frames take the four-wave build: the five-wave one (Traits::PARK) is chosen where a frame is a whole number of
-        // generations of pixels that all cost the same (list_instances_waves), which pixels that stop at different sample counts
-        // no longer are -- and its parked state has no room for q without giving back the registers the parking won.
-        if constexpr (AD) return launch_one<Adaptive<TListInstances>>(sc, a, stream, info);
+    case K_LIST_PRIMS: return launch_one<Like<Any, TListPrims>>(sc, a, stream, info);
+    case K_LIST_INSTANCES: return launch_one<Like<Any, TListInstances>>(sc, a, stream, info);
+    case K_LIST_INSTANCES_5:  // no adaptive form: choose_kernel gives adaptive frames the four-wave build
+        if constexpr (AD) return hipErrorInvalidValue;
         else return launch_one<TListInstances5>(sc, a, stream, info);
-    case CK_LIST_PRIMS_GROUPED: return launch_one<Like<Any, TListPrimsGrouped>>(sc, a, stream, info);
-    case CK_LIST_INSTANCES_GROUPED: return launch_one<Like<Any, TListInstancesGrouped>>(sc, a, stream, info);
-    case CK_LIST_GENERAL: return launch_one<Like<Any, TListGeneral>>(sc, a, stream, info);
-    case CK_LIST_NESTED: return launch_one<Like<Any, TListNested>>(sc, a, stream, info);
-    case CK_BVH_INSTANCES: return launch_one<Like<Any, TBvhInstances>>(sc, a, stream, info);
-    case CK_BVH_MEDIA: return launch_one<Like<Any, TBvhMedia>>(sc, a, stream, info);
-    case CK_BVH_GENERAL: return launch_one<Like<Any, TBvhGeneral>>(sc, a, stream, info);
-    case CK_BVH_GENERAL_DEEP: return launch_one<Like<Any, TBvhGeneralDeep>>(sc, a, stream, info);
-    case CK_BVH_SEGMENTED: return launch_one<Like<Any, TBvhSegmented>>(sc, a, stream, info);
-    default: return launch_one<Like<Any, TBvhNested>>(sc, a, stream, info);
+    case K_LIST_PRIMS_GROUPED: return launch_one<Like<Any, TListPrimsGrouped>>(sc, a, stream, info);
+    case K_LIST_INSTANCES_GROUPED: return launch_one<Like<Any, TListInstancesGrouped>>(sc, a, stream, info);
+    case K_LIST_GENERAL: return launch_one<Like<Any, TListGeneral>>(sc, a, stream, info);
+    case K_LIST_NESTED: return launch_one<Like<Any, TListNested>>(sc, a, stream, info);
+    case K_BVH_INSTANCES: return launch_one<Like<Any, TBvhInstances>>(sc, a, stream, info);
+    case K_BVH_MEDIA: return launch_one<Like<Any, TBvhMedia>>(sc, a, stream, info);
+    case K_BVH_GENERAL: return launch_one<Like<Any, TBvhGeneral>>(sc, a, stream, info);
+    case K_BVH_GENERAL_DEEP: return launch_one<Like<Any, TBvhGeneralDeep>>(sc, a, stream, info);
+    case K_BVH_SEGMENTED: return launch_one<Like<Any, TBvhSegmented>>(sc, a, stream, info);
+    case K_BVH_NESTED: return launch_one<Like<Any, TBvhNested>>(sc, a, stream, info);
+    default: return hipErrorInvalidValue;
     }
 }
 } // namespace
@@ -3953,81 +3847,38 @@ hipError_t RT_CAT(launch_adaptive_rule_, RT_SUFFIX)(const AdaptiveRule &rule, ui
 hipError_t RT_CAT(launch_adaptive_prims_, RT_SUFFIX)(int which, const DeviceScene &sc, const RenderArgs &a, hipStream_t stream, KernelInfo *info)
 {
     switch (which) {
-    case PK_SPHERE_LIST: return launch_one<Adaptive<TSphereList>>(sc, a, stream, info);
-    case PK_BVH_PRIMS_FAST: return launch_one<Adaptive<TBvhPrimsFast>>(sc, a, stream, info);
-    default: return launch_one<Adaptive<TBvhPrims>>(sc, a, stream, info);
+    case K_SPHERE_LIST: return launch_one<Adaptive<TSphereList>>(sc, a, stream, info);
+    case K_BVH_PRIMS_FAST: return launch_one<Adaptive<TBvhPrimsFast>>(sc, a, stream, info);
+    case K_BVH_PRIMS: return launch_one<Adaptive<TBvhPrims>>(sc, a, stream, info);
+    default: return hipErrorInvalidValue;
     }
 }
 #else
 namespace {
-// Four or five waves per SIMD for the instanced-list kernel (TListInstances5): whole generations of pixels on the resident
-// lanes times the duration of a pass at that occupancy (1 : 1.38, measured on C4: three generations of 85.7 ms against two of
-// 118.6).  A frame that does not fill the lanes of four waves stays there: its time is its pixels' chains, and a pass is shortest
-// with the fewest waves.
-int list_instances_waves(const RenderArgs &a)
+hipError_t launch_kernel(int which, const DeviceScene &sc, const RenderArgs &a, hipStream_t stream, KernelInfo *info)
 {
-    const double pixels = (double)a.width * (double)a.rows_owned;
-    const double cus = a.num_cus > 0 ? (double)a.num_cus : 256.0;
-    const double gen4 = std::ceil(pixels / (cus * 16.0 * 64.0) - 0.02), gen5 = std::ceil(pixels / (cus * 20.0 * 64.0) - 0.02);
-    if (gen4 <= 1.0) return 4;
-    return gen5 * 1.38 < gen4 ? 5 : 4;
-}
-
-hipError_t dispatch(const DeviceScene &sc, const RenderArgs &a, hipStream_t stream, KernelInfo *info)
-{
-    // a film with adaptive sampling on: the same choice among the Adaptive<> instantiations
-    auto composite_kernel = [&](int which) {
+    // a film with adaptive sampling on: the same kernel among the Adaptive<> instantiations
+    if (which >= K_FIRST_COMPOSITE)
         return a.adaptive ? RT_CAT(launch_adaptive_composite_, RT_SUFFIX)(which, sc, a, stream, info)
                           : RT_CAT(launch_composite_, RT_SUFFIX)(which, sc, a, stream, info);
-    };
-    auto prims_kernel = [&](int which) {
-        if (a.adaptive) return RT_CAT(launch_adaptive_prims_, RT_SUFFIX)(which, sc, a, stream, info);
-        switch (which) {
-        case PK_SPHERE_LIST: return launch_one<TSphereList>(sc, a, stream, info);
-        case PK_BVH_PRIMS_FAST: return launch_one<TBvhPrimsFast>(sc, a, stream, info);
-        default: return launch_one<TBvhPrims>(sc, a, stream, info);
-        }
-    };
-    const bool composite = sc.n_objects != 0 || sc.n_boxes != 0;
-    const bool rich = (sc.flags & SCENE_RICH_TEXTURES) != 0;
-    // RT_FLAG_ACCELERATE_LISTS: a list world of primitives through the library's tree, when its rows fit the kernel's LDS
-    if (a.accelerate_lists && sc.world_kind == WORLD_LIST && sc.fast_nodes && !composite && !rich && !(sc.flags & SCENE_HAS_MEDIA) &&
-        !(sc.flags & SCENE_HAS_TREES) && !a.force_general && fast_rows_fit(sc))
-        return prims_kernel(PK_BVH_PRIMS_FAST);
-    if ((sc.flags & SCENE_LIST_ALL_SPHERES) && !rich && sc.n_spheres <= 65535u && !a.force_general)
-        return prims_kernel(PK_SPHERE_LIST);
-    if (sc.flags & SCENE_HAS_TREES) return composite_kernel(sc.world_kind == WORLD_BVH ? CK_BVH_NESTED : CK_LIST_NESTED);
-    const bool media = (sc.flags & SCENE_HAS_MEDIA) != 0;
-    const bool scan_world = sc.world_kind == WORLD_LIST || (sc.n_world_items <= 16u && sc.scan_cost <= (uint32_t)a.small_world && !a.always_walk);
-    if (scan_world && !rich && !media && !a.force_general) {
-        // pixels_per_wave < 64 (a power of two: rt_render_launch): the instantiation that deals a ray's leaves to lanes
-        const bool grouped = a.pixels_per_wave < 64 && (a.pixels_per_wave & (a.pixels_per_wave - 1)) == 0 && a.pixels_per_wave > 0;
-        if (grouped) return composite_kernel(composite ? CK_LIST_INSTANCES_GROUPED : CK_LIST_PRIMS_GROUPED);
-        if (composite && list_instances_waves(a) == 5) return composite_kernel(CK_LIST_INSTANCES_5);
-        return composite_kernel(composite ? CK_LIST_INSTANCES : CK_LIST_PRIMS);
+    if (a.adaptive) return RT_CAT(launch_adaptive_prims_, RT_SUFFIX)(which, sc, a, stream, info);
+    switch (which) {
+    case K_SPHERE_LIST: return launch_one<TSphereList>(sc, a, stream, info);
+    case K_BVH_PRIMS_FAST: return launch_one<TBvhPrimsFast>(sc, a, stream, info);
+    case K_BVH_PRIMS: return launch_one<TBvhPrims>(sc, a, stream, info);
+    default: return hipErrorInvalidValue;
     }
-    if (sc.world_kind == WORLD_BVH) {
-        if (!composite && !rich && !a.force_general)
-            return prims_kernel((sc.fast_nodes && !a.reference_tree && sc.n_fast_nodes * kFastNodeBytes <= kFastLdsBudget) ? PK_BVH_PRIMS_FAST
-                                                                                                                            : PK_BVH_PRIMS);
-        if (!rich && !a.force_general) return composite_kernel(media ? CK_BVH_MEDIA : CK_BVH_INSTANCES);
-        // deep worlds: the library's tree, one walk per run of surfaces between media, where the scene has one (RT_FLAG_REFERENCE_TREE:
-        // the reference's tree in the reference's order); both fall back when their tables do not fit the LDS of a CU
-        if (sc.n_world_nodes > 64 && (sc.flags & SCENE_SEGMENTED) && !a.reference_tree) return composite_kernel(CK_BVH_SEGMENTED);
-        return composite_kernel(sc.n_world_nodes > 64 ? CK_BVH_GENERAL_DEEP : CK_BVH_GENERAL);
-    }
-    return composite_kernel(CK_LIST_GENERAL);
 }
 } // namespace
 
-hipError_t RT_CAT(launch_render_, RT_SUFFIX)(const DeviceScene &sc, const RenderArgs &a, hipStream_t stream)
+hipError_t RT_CAT(launch_render_, RT_SUFFIX)(int kernel, const DeviceScene &sc, const RenderArgs &a, hipStream_t stream)
 {
-    return dispatch(sc, a, stream, nullptr);
+    return launch_kernel(kernel, sc, a, stream, nullptr);
 }
 
-hipError_t RT_CAT(kernel_info_, RT_SUFFIX)(const DeviceScene &sc, const RenderArgs &a, KernelInfo *info)
+hipError_t RT_CAT(kernel_info_, RT_SUFFIX)(int kernel, const DeviceScene &sc, const RenderArgs &a, KernelInfo *info)
 {
-    return dispatch(sc, a, nullptr, info);
+    return launch_kernel(kernel, sc, a, nullptr, info);
 }
 #endif
 

@@ -31,7 +31,7 @@ struct RenderArgs {
     uint32_t *tile_cost;        // probe launches: rays traced per 8x8 tile (one counter per tile of this rank's rows)
     const uint32_t *tile_order; // render launches: queue position -> tile (nullptr = tiles in row-major order)
     int32_t probe;              // 1 = cost probe: trace `spp` samples per pixel, write nothing but tile_cost / pix_cost
-    // Two classes of pixels (device_scene.cpp enqueue_frame): the probe books every pixel's rays in pix_cost;
+    // Two classes of pixels (launch_plan.cpp plan_frame, device_scene.cpp enqueue_rehearsal): the probe books every pixel's rays in pix_cost;
     // classify_pixels marks the heavy ones in pix_class and lists them.  The render launch then serves both: the first
     // `heavy_waves` waves of every workgroup serve heavy_list (heavy_ppw pixels at a time, through heavy_cursor) and join
     // the tile queue when the list is done; the tile queue skips the pixels whose class is non-zero.
@@ -58,7 +58,7 @@ struct RenderArgs {
     int32_t leaf_batch;     // composite BVH worlds: a kind of leaf is tested once this many lanes of the wave wait for it
     int32_t rounds;         // kind-batched kernels: node / leaf rounds per look at the shading queue
     int32_t object_batch;   // the same for instances / groups (their cooperative scan serves one ray at a time: a small batch is fine)
-    int32_t lds_nodes;      // set by the launcher: BVH nodes are staged in LDS
+    int32_t lds_nodes;      // set by the launcher (launch_plan.h lds_layout): BVH nodes are staged in LDS
     int32_t small_world;    // BVH worlds without media are scanned, not walked, up to this scan cost (and 16 leaves)
     int32_t accelerate_lists;  // list worlds of primitives: walk the library's tree instead of scanning the list
     int32_t exact_scan;     // sphere-list worlds: no conservative filter in front of the reference's sphere test
@@ -69,7 +69,7 @@ struct RenderArgs {
     int32_t coop_threshold; // sphere-list kernel: below this many live lanes a wave scans cooperatively
     int32_t coop_single;    // experiments: cooperative scan one ray at a time (the older scheme) instead of in groups
     int32_t num_cus;
-    int32_t lds_spheres;    // set by the launcher: sphere planes staged in LDS for the cooperative scan
+    int32_t lds_spheres;    // set by the launcher (lds_layout): sphere planes staged in LDS for the cooperative scan
     int32_t overdue_priority;
     int32_t boost_rounds;   // overdue-only cooperative passes inserted after each pixel-parallel pass
     int32_t max_blocks_per_cu;  // cap on resident workgroups per CU (0 = whatever fits)
@@ -88,15 +88,17 @@ struct RenderArgs {
 };
 
 struct KernelInfo {
-    int vgprs, lds_bytes, kind;  // kind = WORLD * 4 + COMPOSITE * 2 + RICH
+    int vgprs, lds_bytes, kind;  // kind: launch_plan.h kernel_kind() = WORLD * 8 + MEDIA * 4 + COMPOSITE * 2 + RICH + the KIND_* bits
 };
 
+// `kernel`: the instantiation to run, a KernelId.  Which one, what it stages in LDS and how the frame is scheduled is decided
+// in launch_plan.h and nowhere else: these entry points run what they are given (and refuse what does not fit).
 hipError_t launch_seed_strict(const SeedArgs &a, hipStream_t stream);
 hipError_t launch_seed_fast(const SeedArgs &a, hipStream_t stream);
-hipError_t launch_render_strict(const DeviceScene &sc, const RenderArgs &a, hipStream_t stream);
-hipError_t launch_render_fast(const DeviceScene &sc, const RenderArgs &a, hipStream_t stream);
-hipError_t kernel_info_strict(const DeviceScene &sc, const RenderArgs &a, KernelInfo *info);
-hipError_t kernel_info_fast(const DeviceScene &sc, const RenderArgs &a, KernelInfo *info);
+hipError_t launch_render_strict(int kernel, const DeviceScene &sc, const RenderArgs &a, hipStream_t stream);
+hipError_t launch_render_fast(int kernel, const DeviceScene &sc, const RenderArgs &a, hipStream_t stream);
+hipError_t kernel_info_strict(int kernel, const DeviceScene &sc, const RenderArgs &a, KernelInfo *info);
+hipError_t kernel_info_fast(int kernel, const DeviceScene &sc, const RenderArgs &a, KernelInfo *info);
 
 // the stopping rule as the adaptive render kernels of that build compile it, on device arrays of `count` entries (tests)
 hipError_t launch_adaptive_rule_strict(const AdaptiveRule &rule, uint32_t count, const uint32_t *n, const double *sums_rgbq,

@@ -101,7 +101,7 @@ struct FlatScene {
     uint32_t n_world_nodes = 0;
     uint32_t scan_cost = 0;  // cost of testing every world leaf once (scene_builder.cpp), for the scan-or-walk choice
     // Moving-sphere rows whose centre moves (dc != 0) over an interval of non-zero length (dt != 0): their distinct (t0, dt).
-    // The launcher checks them against the camera's shutter (device_scene.cpp hits_stay_in_boxes); ms_nonfinite: such a
+    // The launcher checks them against the camera's shutter (launch_plan.cpp hits_stay_in_boxes); ms_nonfinite: such a
     // row has a non-finite centre, motion or interval, and no shutter keeps it inside its box.
     std::vector<MsInterval> ms_intervals;
     bool ms_nonfinite = false;
