@@ -305,7 +305,17 @@ typedef struct rt_launch_plan {
     int32_t heavy_threshold, super_threshold; /* probed rays from which a pixel is listed / listed among the longest (0: no such list) */
     int32_t near_percent, near_neighbours; /* ... or at this share of the threshold with that many of its 8 neighbours over it */
     int32_t heavy_waves, heavy_ppw, super_ppw, heavy_priority, adaptive_ppw; /* serving waves per workgroup, pixels each takes, ... */
+    /* The LDS layout of the launch, table by table (csrc/launch_plan.h LdsLayout, the very result the launch applies).  At the front
+     * of the dynamic LDS block lie lds_front_bytes of node rows (BVH worlds) or survivor queues and sphere planes (sphere lists);
+     * behind them the tables, in the order of RT_LDS_TABLE_NAMES.  lds_table_offset[k] = byte offset of table k in the block,
+     * 0xFFFFFFFF = the kernel reads it from global memory; lds_table_bytes[k] = the table's unpadded size, 0 for an empty table and
+     * for one this instantiation never considers. */
+    int32_t lds_front_bytes;
+    uint32_t lds_table_offset[16], lds_table_bytes[16];
 } rt_launch_plan;
+#define RT_LDS_TABLES 16
+#define RT_LDS_TABLE_NAMES "quad_aa boxes objects xforms media materials perlin spheres_tab group_boxes mspheres msphere_aux " \
+                           "sphere_aux fast_order seg_media seg_cand park"
 RTOW_API int rt_plan_launch(rt_scene *s, const rt_render_params *params, int num_cus, int adaptive, rt_launch_plan *out);
 
 /* Upload the committed scene to a device (idempotent per device). */

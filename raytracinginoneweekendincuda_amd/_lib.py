@@ -30,13 +30,20 @@ class AdaptiveParams(C.Structure):
 
 
 class LaunchPlan(C.Structure):
-    """rt_launch_plan: what a launch decides (csrc/launch_plan.h); every field but ray_budget is an int32."""
+    """rt_launch_plan: what a launch decides (csrc/launch_plan.h); every scalar field but ray_budget is an int32."""
     _fields_ = [(n, C.c_uint32 if n == "ray_budget" else C.c_int32) for n in (
         "kernel_kind", "lds_bytes", "pixels_per_wave", "kernel", "probe_kernel", "waves_per_simd", "lds_nodes", "lds_spheres",
         "reference_tree", "always_walk", "accelerate_lists", "coop_threshold", "max_blocks_per_cu", "probe_max_blocks_per_cu",
         "node_burst", "park_ratio", "leaf_batch", "object_batch", "rounds", "shade_batch", "ray_budget",
         "rank_tiles", "pixel_classes", "probe_spp", "tile_flatness_x8", "heavy_threshold", "super_threshold",
-        "near_percent", "near_neighbours", "heavy_waves", "heavy_ppw", "super_ppw", "heavy_priority", "adaptive_ppw")]
+        "near_percent", "near_neighbours", "heavy_waves", "heavy_ppw", "super_ppw", "heavy_priority", "adaptive_ppw",
+        "lds_front_bytes")] + [("lds_table_offset", C.c_uint32 * 16), ("lds_table_bytes", C.c_uint32 * 16)]
+
+
+# the order of rt_launch_plan.lds_table_offset / lds_table_bytes (include/rtow.h RT_LDS_TABLE_NAMES, csrc/launch_plan.h LdsTable)
+LDS_TABLES = ("quad_aa", "boxes", "objects", "xforms", "media", "materials", "perlin", "spheres_tab", "group_boxes", "mspheres",
+              "msphere_aux", "sphere_aux", "fast_order", "seg_media", "seg_cand", "park")
+LDS_GLOBAL = 0xFFFFFFFF   # lds_table_offset of a table the kernel reads from global memory
 
 
 class SceneInfo(C.Structure):

@@ -244,10 +244,15 @@ class Scene:
 
     def plan_launch(self, params, num_cus=256, adaptive=False):
         """Tests: what a launch of this committed scene with these RenderParams decides on a GPU of ``num_cus`` compute units
-        -- kernel, LDS, schedule (rt_plan_launch; no device needed).  Returns a dict of the rt_launch_plan fields."""
+        -- kernel, LDS, schedule (rt_plan_launch; no device needed).  Returns a dict of the rt_launch_plan fields; the LDS
+        layout as ``lds_tables``: {table name: (byte offset in the dynamic LDS block, or None where the kernel reads the
+        table from global memory; the table's unpadded bytes)}, behind ``lds_front_bytes`` of node rows or sphere planes."""
         out = LaunchPlan()
         _check(lib().rt_plan_launch(self._p, C.byref(params), num_cus, 1 if adaptive else 0, C.byref(out)))
-        return {n: getattr(out, n) for n, _ in LaunchPlan._fields_}
+        plan = {n: getattr(out, n) for n, _ in LaunchPlan._fields_ if not n.startswith("lds_table_")}
+        plan["lds_tables"] = {name: (None if off == _lib.LDS_GLOBAL else off, size)
+                              for name, off, size in zip(_lib.LDS_TABLES, out.lds_table_offset, out.lds_table_bytes)}
+        return plan
 
     def upload(self, device=0):
         _check(lib().rt_scene_upload(self._p, device))

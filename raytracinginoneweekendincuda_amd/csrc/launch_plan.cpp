@@ -22,7 +22,8 @@ LdsLayout lds_layout(const KernelProps &k, const DeviceScene &sc)
     size_t lds = 0, off = 0, budget = 0;
     auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
     // a table goes behind what is placed already if it is not empty, within its own cap, and leaves the slack of the budget
-    auto place = [&](uint32_t &slot, size_t bytes, size_t cap) {
+    auto place = [&](LdsTable t, uint32_t &slot, size_t bytes, size_t cap) {
+        l.table_bytes[t] = (uint32_t)bytes;
         if (bytes == 0 || bytes > cap || off + bytes + kPlaceSlack > budget) return;
         slot = (uint32_t)off;
         off += up16(bytes);
@@ -37,6 +38,7 @@ LdsLayout lds_layout(const KernelProps &k, const DeviceScene &sc)
             lds = need;
             l.lds_nodes = 1;
         }
+        l.front = lds;
         if (k.fast && big) {
             // One workgroup per CU: the sphere rows the leaf tests and the hit record read and the material rows follow the
             // node rows into the CU's LDS -- a frame ends with its longest pixel, and that pixel's chain is made of exactly
@@ -44,11 +46,11 @@ LdsLayout lds_layout(const KernelProps &k, const DeviceScene &sc)
             if (l.lds_nodes) {
                 budget = kWholeCuBudget;
                 off = up16(lds);
-                place(l.mspheres, (size_t)sc.n_mspheres * sizeof(MSphereGeom), no_cap);
-                place(l.msphere_aux, (size_t)sc.n_mspheres * sizeof(SphereAux), no_cap);
-                place(l.spheres_tab, (size_t)sc.n_spheres * sizeof(SphereGeom), no_cap);
-                place(l.sphere_aux, (size_t)sc.n_spheres * sizeof(SphereAux), no_cap);
-                place(l.materials, (size_t)sc.n_materials * sizeof(MaterialRec), no_cap);
+                place(T_MSPHERES, l.mspheres, (size_t)sc.n_mspheres * sizeof(MSphereGeom), no_cap);
+                place(T_MSPHERE_AUX, l.msphere_aux, (size_t)sc.n_mspheres * sizeof(SphereAux), no_cap);
+                place(T_SPHERES_TAB, l.spheres_tab, (size_t)sc.n_spheres * sizeof(SphereGeom), no_cap);
+                place(T_SPHERE_AUX, l.sphere_aux, (size_t)sc.n_spheres * sizeof(SphereAux), no_cap);
+                place(T_MATERIALS, l.materials, (size_t)sc.n_materials * sizeof(MaterialRec), no_cap);
                 lds = off;
             }
             // The library-tree kernel reads these rows from LDS only (no global side in its accessors: head of
@@ -60,11 +62,11 @@ LdsLayout lds_layout(const KernelProps &k, const DeviceScene &sc)
         if (k.seg) {  // the leaf positions per node and the media, right behind the node rows
             off = up16(lds);
             l.fast_order = (uint32_t)off;
-            off += up16((size_t)sc.n_fast_nodes * sizeof(FastOrder));
+            off += up16(l.table_bytes[T_FAST_ORDER] = (uint32_t)((size_t)sc.n_fast_nodes * sizeof(FastOrder)));
             l.seg_media = (uint32_t)off;
-            off += up16((size_t)(sc.n_seg_media ? sc.n_seg_media : 1u) * sizeof(SegMedium));
+            off += up16(l.table_bytes[T_SEG_MEDIA] = (uint32_t)((size_t)(sc.n_seg_media ? sc.n_seg_media : 1u) * sizeof(SegMedium)));
             l.seg_cand = (uint32_t)off;
-            off += up16((size_t)(sc.n_seg_cand ? sc.n_seg_cand : 1u) * sizeof(SegCandidate));
+            off += up16(l.table_bytes[T_SEG_CAND] = (uint32_t)((size_t)(sc.n_seg_cand ? sc.n_seg_cand : 1u) * sizeof(SegCandidate)));
             lds = off;
         }
         if (k.composite) {
@@ -73,20 +75,22 @@ LdsLayout lds_layout(const KernelProps &k, const DeviceScene &sc)
             // final scene) and, where they fit as well, the quad / box rows (Cornell box: 2 KB).
             budget = big ? kWholeCuBudget : kSharedCuBudget;
             off = up16(lds);
-            place(l.objects, (size_t)sc.n_objects * sizeof(ObjectRec), 4096);
-            place(l.xforms, (size_t)sc.n_xforms * sizeof(Xform), 4096);
-            place(l.media, (size_t)sc.n_media * sizeof(MediumRec), 2048);
-            place(l.group_boxes, (size_t)sc.n_group_boxes * sizeof(GroupBox), 4096);
-            place(l.materials, (size_t)sc.n_materials * sizeof(MaterialRec), 4096);
-            if (k.rich) place(l.perlin, (size_t)sc.n_perlin * sizeof(PerlinRec), 2 * sizeof(PerlinRec));
+            place(T_OBJECTS, l.objects, (size_t)sc.n_objects * sizeof(ObjectRec), 4096);
+            place(T_XFORMS, l.xforms, (size_t)sc.n_xforms * sizeof(Xform), 4096);
+            place(T_MEDIA, l.media, (size_t)sc.n_media * sizeof(MediumRec), 2048);
+            place(T_GROUP_BOXES, l.group_boxes, (size_t)sc.n_group_boxes * sizeof(GroupBox), 4096);
+            place(T_MATERIALS, l.materials, (size_t)sc.n_materials * sizeof(MaterialRec), 4096);
+            if (k.rich) place(T_PERLIN, l.perlin, (size_t)sc.n_perlin * sizeof(PerlinRec), 2 * sizeof(PerlinRec));
             const size_t b_quads = (size_t)sc.n_quads * sizeof(AAQuad), b_boxes = (size_t)sc.n_boxes * sizeof(BoxRec);
+            l.table_bytes[T_QUAD_AA] = (uint32_t)b_quads;  // (placed together or not at all where workgroups share the CU)
+            l.table_bytes[T_BOXES] = (uint32_t)b_boxes;
             if (big) {  // the big tables, most useful first
-                place(l.boxes, b_boxes, 80 * 1024);
-                place(l.spheres_tab, (size_t)sc.n_spheres * sizeof(SphereGeom), 40 * 1024);
-                place(l.quad_aa, b_quads, 16 * 1024);
+                place(T_BOXES, l.boxes, b_boxes, 80 * 1024);
+                place(T_SPHERES_TAB, l.spheres_tab, (size_t)sc.n_spheres * sizeof(SphereGeom), 40 * 1024);
+                place(T_QUAD_AA, l.quad_aa, b_quads, 16 * 1024);
             } else if (b_quads + b_boxes <= 16 * 1024 && off + b_quads + b_boxes + 96 <= budget) {
-                place(l.quad_aa, b_quads, 16 * 1024);
-                place(l.boxes, b_boxes, 16 * 1024);
+                place(T_QUAD_AA, l.quad_aa, b_quads, 16 * 1024);
+                place(T_BOXES, l.boxes, b_boxes, 16 * 1024);
             }
             lds = off;
             if (k.batch && big) {
@@ -108,11 +112,12 @@ LdsLayout lds_layout(const KernelProps &k, const DeviceScene &sc)
             lds += planes;
             l.lds_spheres = 1;
         }
+        l.front = lds;
     }
     if (k.park) {  // the parked path state, one entry per thread (list worlds stage no tables: their rows come through scalar loads)
         off = up16(lds);
         l.park = (uint32_t)off;
-        lds = off + (size_t)k.block * kParkedBytesPerThread;
+        lds = off + (l.table_bytes[T_PARK] = (uint32_t)((size_t)k.block * kParkedBytesPerThread));
     }
     l.bytes = lds;
     return l;
@@ -407,6 +412,18 @@ rt_launch_plan plan_frame(int kind, int lds_bytes, const FilmGeometry &film, int
     return plan;
 }
 
+// The layout as rt_launch_plan lists it: the slots of LdsLayout in the order of LdsTable, nothing decided or computed here.
+static void show_layout(const LdsLayout &l, rt_launch_plan &plan)
+{
+    const uint32_t offsets[kLdsTables] = {l.quad_aa, l.boxes, l.objects, l.xforms, l.media, l.materials, l.perlin, l.spheres_tab,
+                                          l.group_boxes, l.mspheres, l.msphere_aux, l.sphere_aux, l.fast_order, l.seg_media, l.seg_cand, l.park};
+    plan.lds_front_bytes = (int)l.front;
+    for (int t = 0; t < kLdsTables; t++) {
+        plan.lds_table_offset[t] = offsets[t];
+        plan.lds_table_bytes[t] = l.table_bytes[t];
+    }
+}
+
 rt_launch_plan plan_launch(const DeviceScene &sc, const FilmGeometry &film, int num_cus, const rt_render_params &p, bool adaptive,
                            bool in_boxes)
 {
@@ -435,6 +452,7 @@ rt_launch_plan plan_launch(const DeviceScene &sc, const FilmGeometry &film, int 
     plan.lds_bytes = (int)layout.bytes;
     plan.lds_nodes = layout.lds_nodes;
     plan.lds_spheres = layout.lds_spheres;
+    show_layout(layout, plan);
     o.adaptive = false;  // the rehearsal is the plain kernel's: it only counts rays
     plan.probe_kernel = choose_kernel(sc, o);
     return plan;

@@ -116,7 +116,18 @@ struct LdsLayout {
     int lds_nodes = 0, lds_spheres = 0;  // RenderArgs::lds_nodes, ::lds_spheres
     size_t bytes = 0;                    // dynamic LDS of the launch (the render kernels have no static LDS)
     bool fits = true;                    // everything this instantiation reads from LDS only is staged
+    // For rt_plan_launch (tests): what lies at the front of the block -- node rows, or survivor queues and sphere planes -- and
+    // the unpadded size of every table this instantiation considered, staged or not, in the order of LdsTable.
+    size_t front = 0;
+    uint32_t table_bytes[RT_LDS_TABLES] = {};
 };
+// The slots of LdsLayout in the order rt_launch_plan lists them (include/rtow.h RT_LDS_TABLE_NAMES).
+enum LdsTable : int {
+    T_QUAD_AA, T_BOXES, T_OBJECTS, T_XFORMS, T_MEDIA, T_MATERIALS, T_PERLIN, T_SPHERES_TAB, T_GROUP_BOXES, T_MSPHERES, T_MSPHERE_AUX,
+    T_SPHERE_AUX, T_FAST_ORDER, T_SEG_MEDIA, T_SEG_CAND, T_PARK,
+    kLdsTables,
+};
+static_assert(kLdsTables == RT_LDS_TABLES, "rt_launch_plan lists another number of tables than LdsLayout has slots");
 // `sc`: only its count and flag fields are read (scene_counts)
 LdsLayout lds_layout(const KernelProps &k, const DeviceScene &sc);
 inline void apply_layout(const LdsLayout &l, DeviceScene &sc)

@@ -2553,12 +2553,35 @@ DEV Surface make_surface(const DeviceScene &sc, const Ray &r, const HitInfo &h)
 // ------------------------------------------------------------------------------------------------
 // textures and materials
 // ------------------------------------------------------------------------------------------------
+// perlin_noise (table in global memory) and perlin_noise_lds (table staged in LDS) are two codings of one sum, and which
+// of them a launch runs is lds_layout's choice -- which must not show in the frame.  One is a rolled loop over the corners
+// with run-time a, b, c, the other is unrolled with constants, and the fast build fused the multiply-adds of the two
+// differently (two Perlin tables staged against three in global memory: 0.3 % of a marble frame's pixels differed).  So no
+// product of either is fused into the add that follows it: it goes through unfused(), an empty asm that the backend cannot
+// look through (the fast objects fuse in the backend whatever a contraction pragma says: adaptive_rule.h).  The strict build
+// fuses nothing anyway and compiles exactly what it compiled without.
+DEV double unfused(double x)
+{
+#if !RT_STRICT
+    asm("" : "+v"(x));
+#endif
+    return x;
+}
+DEV double perlin_fade(double u) { return u * u * (3.0 - unfused(2.0 * u)); }
+// the term of corner (a, b, c): its trilinear weight times gradient . offset, R/Perlin.h:120-139
+DEV double perlin_corner(int a, int b, int c, double u, double v, double w, double uu, double vv, double ww, Vec g)
+{
+    const Vec wv = mk(u - a, v - b, w - c);
+    const double wa = unfused(a * uu) + unfused((1 - a) * (1 - uu)), wb = unfused(b * vv) + unfused((1 - b) * (1 - vv));
+    const double wc = unfused(c * ww) + unfused((1 - c) * (1 - ww));
+    return unfused(wa * wb * wc * (unfused(g.x * wv.x) + unfused(g.y * wv.y) + unfused(g.z * wv.z)));
+}
 DEV double perlin_noise(const PerlinRec *pn, Vec p)  // R/Perlin.h:38-60,120-139
 {
     double fx = floor(p.x), fy = floor(p.y), fz = floor(p.z);
     double u = p.x - fx, v = p.y - fy, w = p.z - fz;
     int i = (int)fx, j = (int)fy, k = (int)fz;
-    double uu = u * u * (3.0 - 2.0 * u), vv = v * v * (3.0 - 2.0 * v), ww = w * w * (3.0 - 2.0 * w);
+    double uu = perlin_fade(u), vv = perlin_fade(v), ww = perlin_fade(w);
     double accum = 0.0;
     // corners one after another (same summation order as the reference; keeps the register footprint small)
 #pragma unroll 1
@@ -2569,8 +2592,7 @@ DEV double perlin_noise(const PerlinRec *pn, Vec p)  // R/Perlin.h:38-60,120-139
             for (int c = 0; c < 2; c++) {
                 int idx = pn->perm_x[(i + a) & 255] ^ pn->perm_y[(j + b) & 255] ^ pn->perm_z[(k + c) & 255];
                 Vec g = mk(pn->vec[idx][0], pn->vec[idx][1], pn->vec[idx][2]);
-                Vec wv = mk(u - a, v - b, w - c);
-                accum += (a * uu + (1 - a) * (1 - uu)) * (b * vv + (1 - b) * (1 - vv)) * (c * ww + (1 - c) * (1 - ww)) * dot(g, wv);
+                accum += perlin_corner(a, b, c, u, v, w, uu, vv, ww, g);
             }
     return accum;
 }
@@ -2586,7 +2608,7 @@ DEV double perlin_noise_lds(uint32_t off, Vec p)  // R/Perlin.h:38-60,120-139
     double fx = floor(p.x), fy = floor(p.y), fz = floor(p.z);
     double u = p.x - fx, v = p.y - fy, w = p.z - fz;
     int i = (int)fx, j = (int)fy, k = (int)fz;
-    double uu = u * u * (3.0 - 2.0 * u), vv = v * v * (3.0 - 2.0 * v), ww = w * w * (3.0 - 2.0 * w);
+    double uu = perlin_fade(u), vv = perlin_fade(v), ww = perlin_fade(w);
     const int px[2] = {perm[i & 255], perm[(i + 1) & 255]};
     const int py[2] = {perm[256 + (j & 255)], perm[256 + ((j + 1) & 255)]};
     const int pz[2] = {perm[512 + (k & 255)], perm[512 + ((k + 1) & 255)]};
@@ -2599,8 +2621,7 @@ DEV double perlin_noise_lds(uint32_t off, Vec p)  // R/Perlin.h:38-60,120-139
             for (int c = 0; c < 2; c++) {
                 const int idx = px[a] ^ py[b] ^ pz[c];
                 Vec g = mk(vec[idx * 3 + 0], vec[idx * 3 + 1], vec[idx * 3 + 2]);
-                Vec wv = mk(u - a, v - b, w - c);
-                accum += (a * uu + (1 - a) * (1 - uu)) * (b * vv + (1 - b) * (1 - vv)) * (c * ww + (1 - c) * (1 - ww)) * dot(g, wv);
+                accum += perlin_corner(a, b, c, u, v, w, uu, vv, ww, g);
             }
     return accum;
 }
