@@ -331,6 +331,67 @@ RTOW_API int rt_film_download(rt_film *film, double *frame_full, int width, int 
 RTOW_API int rt_deinterleave(const double *gathered, int width, int height, int stripe_rows, int world_size,
                              size_t rank_stride_doubles, double *frame_full);
 
+/* ---- first-hit feature buffers (AOVs) and the edge-avoiding a-trous filter that uses them as edge stops ----
+ * rt_film_render_features fills three film-owned device planes for the rows the film owns, compact like the pixels: albedo
+ * (3 doubles per pixel), shading normal (3) and depth (1) of the closest hit over [0.001, inf) of the pixel's primary rays, found
+ * by the traversal, leaf tests and hit record of the render kernels (the reference's tree or list in the reference's order).
+ *   samples >= 1: the pixel's stream is seeded as a render seeds it, curand_init(seed, pixelIndex, 0); every feature sample's
+ *     primary ray takes the camera's draws of a render sample, in the same order, and nothing else is drawn except by the
+ *     world's hit test itself (media).  The pixel's value is (1 / N) * (sum over its samples in order), as a render averages.
+ *   samples == 0: one ray through the pixel centre, u = (i + 0.5) / W, v = (j + 0.5) / H, no lens offset, time = time0; the
+ *     camera draws nothing (media still draw from the pixel's stream); the one sample is stored as it is.
+ * What a sample records:          surface hit                                          medium hit                  miss
+ *   albedo   Lambertian / isotropic: the material's texture at (u, v, p); metal:       the phase material's        the camera's
+ *            its albedo; dielectric: (1, 1, 1); diffuse light: its emitted colour      texture value               background
+ *   normal   the unit shading normal, faced against the ray, in world space            (0, 0, 0)                   (0, 0, 0)
+ *   depth    t * |ray direction|                                                       the same                    0
+ * The film's saved RNG state, its pixels, sums and statistics are neither read nor written: a feature pass between two
+ * progressive launches changes nothing of the frame.  The call returns when the planes are filled (it waits on params->stream,
+ * NULL = the film's own).  RT_ERR_STATE while a render of the film is in flight. */
+typedef struct rt_feature_params {
+    int32_t width, height;
+    int32_t samples;     /* 0: one ray through the pixel centre; N >= 1: N jittered primary rays, averaged */
+    uint64_t seed;       /* the per-pixel stream, as in rt_render_params */
+    int32_t variant;     /* 0 strict, 1 fast, as for renders */
+    void *stream;
+    int32_t reserved[4];
+} rt_feature_params;
+RTOW_API int rt_film_render_features(rt_scene *s, rt_film *film, const rt_feature_params *params);
+/* The full frame, pixel (i, j) at j*W+i like rt_film_download (albedo and normal W*H*3 doubles, depth W*H); pixels this rank
+ * does not own are 0.  Any pointer may be NULL.  RT_ERR_STATE before the film's first feature pass. */
+RTOW_API int rt_film_download_features(rt_film *film, double *albedo_full, double *normal_full, double *depth_full, int width,
+                                       int height);
+/* Device pointer of one compact plane (which: 0 albedo, 1 normal, 2 depth), for callers that gather over RCCL as they do with
+ * the pixels; NULL before the first feature pass. */
+RTOW_API void *rt_film_device_features(rt_film *film, int which);
+
+/* The edge-avoiding a-trous wavelet filter of Dammertz et al. 2010.  Level k = 0 .. iterations-1 reads level k-1's output (the
+ * guides never change) and, for pixel p and the 25 taps q = p + 2^k * (dx, dy), dx, dy in {-2..2}, dy outer, dx inner, both
+ * ascending, taps outside the frame skipped:
+ *     h = {1/16, 1/4, 3/8, 1/4, 1/16}
+ *     e = |c_p - c_q|^2 / (sigma_color * 2^-k)^2 + |a_p - a_q|^2 / sigma_albedo^2 + |n_p - n_q|^2 / sigma_normal^2
+ *         + ((z_p - z_q) / max(z_p, z_q, 1e-30))^2 / sigma_depth^2
+ *     w = h[dx+2] * h[dy+2] * exp(-e);     out_p = (sum w * c_q) / (sum w)
+ * c = the colour as the film stores it (the reference's sqrt-gamma values, unclamped), a, n, z = albedo, normal, depth.  fp64,
+ * no contraction, one exp per tap; |.|^2 is the plain three-term sum; a sigma of +inf switches its term off (it contributes an
+ * exact 0).  A tap whose colour is not finite (NaN, +-inf) has weight 0; a centre whose colour is not finite passes through. */
+typedef struct rt_denoise_params {
+    int32_t iterations;                 /* 1..8 levels; level k uses step 2^k, k = 0.. */
+    double sigma_color, sigma_albedo, sigma_normal, sigma_depth;   /* > 0; +inf switches a term off */
+} rt_denoise_params;
+/* Filters the film's pixels with the film's feature planes into a second film-owned buffer (read it with
+ * rt_film_download_denoised): never in place, the raw pixels, sums and RNG state stay as they are and accumulated or adaptive
+ * frames continue afterwards.  RT_ERR_INVALID for parameters out of range; RT_ERR_UNSUPPORTED for a film that owns only part of
+ * the frame (world_size > 1: its neighbours live on other ranks -- gather and use rt_denoise_frame); RT_ERR_STATE before a
+ * feature pass on this film and while a render is in flight.  Returns when the result is there. */
+RTOW_API int rt_film_denoise(rt_film *film, const rt_denoise_params *params);
+RTOW_API int rt_film_download_denoised(rt_film *film, double *frame_full, int width, int height);
+/* The same kernel on uploaded copies of host arrays (frames gathered from several ranks; synthetic inputs): color and out W*H*3,
+ * albedo and normal W*H*3, depth W*H; albedo, normal and depth may each be NULL, that term is then off.  Parameters are checked
+ * before the device is touched. */
+RTOW_API int rt_denoise_frame(int device, const double *color, const double *albedo, const double *normal, const double *depth,
+                              int width, int height, const rt_denoise_params *params, double *out);
+
 /* Convenience: create film, upload, render 1 GPU, download.  frame = W*H*3 doubles. */
 RTOW_API int rt_render(rt_scene *s, const rt_render_params *params, double *frame, rt_render_stats *stats);
 

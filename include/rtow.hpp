@@ -139,4 +139,81 @@ private:
     bool own_ = true;
 };
 
+// A film on one GPU with the feature pass and the a-trous filter (rtow.h "first-hit feature buffers"): render, then
+//   film.RenderFeatures(scene); film.Denoise(); auto clean = film.Denoised();
+class Film {
+public:
+    struct Features {
+        std::vector<double> albedo, normal, depth;  // W*H*3, W*H*3, W*H; pixel (i, j) at j*W+i, j = 0 bottom
+    };
+    Film(int device, int width, int height, int stripe_rows = 8, int rank = 0, int world_size = 1)
+        : f_(rt_film_create(device, width, height, stripe_rows, rank, world_size)), w_(width), h_(height)
+    {
+        if (!f_) throw Error(rt_last_error());
+    }
+    ~Film() { rt_film_destroy(f_); }
+    Film(const Film &) = delete;
+    Film &operator=(const Film &) = delete;
+    rt_film *raw() { return f_; }
+
+    rt_render_stats Render(Scene &scene, const rt_render_params &params)
+    {
+        rt_render_stats st{};
+        check(rt_render_launch(scene.raw(), f_, &params));
+        check(rt_render_finish(scene.raw(), f_, &st));
+        return st;
+    }
+    std::vector<double> Download()
+    {
+        std::vector<double> frame((size_t)w_ * h_ * 3);
+        check(rt_film_download(f_, frame.data(), w_, h_));
+        return frame;
+    }
+    void RenderFeatures(Scene &scene, int samples = 0, unsigned long long seed = 1984, int variant = 0, void *stream = nullptr)
+    {
+        rt_feature_params p{};
+        p.width = w_;
+        p.height = h_;
+        p.samples = samples;
+        p.seed = seed;
+        p.variant = variant;
+        p.stream = stream;
+        check(rt_film_render_features(scene.raw(), f_, &p));
+    }
+    Features DownloadFeatures()
+    {
+        Features out;
+        out.albedo.resize((size_t)w_ * h_ * 3);
+        out.normal.resize((size_t)w_ * h_ * 3);
+        out.depth.resize((size_t)w_ * h_);
+        check(rt_film_download_features(f_, out.albedo.data(), out.normal.data(), out.depth.data(), w_, h_));
+        return out;
+    }
+    void *DeviceFeatures(int which) { return rt_film_device_features(f_, which); }
+    void Denoise(const rt_denoise_params &params = rt_denoise_params{5, 0.6, 0.1, 0.3, 0.1}) { check(rt_film_denoise(f_, &params)); }
+    std::vector<double> Denoised()
+    {
+        std::vector<double> frame((size_t)w_ * h_ * 3);
+        check(rt_film_download_denoised(f_, frame.data(), w_, h_));
+        return frame;
+    }
+
+private:
+    void check(int status)
+    {
+        if (status != RT_OK) throw Error(rt_last_error());
+    }
+    rt_film *f_;
+    int w_, h_;
+};
+
+// rt_denoise_frame on host frames (gathered from several ranks): albedo, normal, depth may each be null
+inline std::vector<double> DenoiseFrame(int device, const double *color, const double *albedo, const double *normal, const double *depth, int width,
+                                        int height, const rt_denoise_params &params = rt_denoise_params{5, 0.6, 0.1, 0.3, 0.1})
+{
+    std::vector<double> out((size_t)width * height * 3);
+    if (rt_denoise_frame(device, color, albedo, normal, depth, width, height, &params, out.data()) != RT_OK) throw Error(rt_last_error());
+    return out;
+}
+
 } // namespace rtow_api

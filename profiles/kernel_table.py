@@ -1,9 +1,11 @@
-"""VGPRs / scratch / spills of every render_kernel instantiation in the built library (llvm-readelf on the code objects)."""
+"""VGPRs / scratch / spills of every render_kernel instantiation in the built library (llvm-readelf on the code objects), then
+the feature and filter kernels (feature_kernel, atrous_kernel) by name with their static LDS as well."""
 import os, re, subprocess, sys
 so = sys.argv[1] if len(sys.argv) > 1 else os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', 'raytracinginoneweekendincuda_amd', 'librtow_hip.so')
 data = open(so, 'rb').read()
 idx = [m.start() for m in re.finditer(b'\x7fELF', data)]
 rows = []
+others = []
 for i, st in enumerate(idx[1:]):
     end = idx[i + 2] if i + 2 < len(idx) else len(data)
     open('/tmp/kt.elf', 'wb').write(data[st:end])
@@ -21,6 +23,14 @@ for i, st in enumerate(idx[1:]):
                 strict, world, comp, rich, waves, media, batch, nested, block, fast, grouped = (int(x) for k, x in enumerate(m.groups()) if k != 1)
                 rows.append((int(adaptive), world, comp, rich, media, batch, nested, fast, grouped, block, waves, 'strict' if strict else 'fast',
                              int(cur['vgpr_count']), int(cur['private_segment_fixed_size']), int(cur['vgpr_spill_count'])))
+            m = re.search(r'(feature_kernel)ILi(\d)ENS_12_GLOBAL__N_16TraitsILi(\d)|(atrous_kernel)', n)
+            if m:
+                name = m.group(4) or '%s world %s %s' % (m.group(1), m.group(3), 'strict' if int(m.group(2)) else 'fast')
+                others.append((name, int(cur['vgpr_count']), int(cur['private_segment_fixed_size']), int(cur['vgpr_spill_count']),
+                               int(cur['group_segment_fixed_size'])))
             cur = {}
 print("world comp rich media batch nested fast grouped block waves build vgpr scratchB spills")
 for r in sorted(rows): print(*r[1:], *(['adaptive'] if r[0] else []))
+if others:
+    print("kernel vgpr scratchB spills ldsB")
+    for r in sorted(others): print(*r)

@@ -29,6 +29,16 @@ class AdaptiveParams(C.Structure):
                 ("luminance_floor", C.c_double)]
 
 
+class FeatureParams(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("samples", C.c_int32), ("seed", C.c_uint64), ("variant", C.c_int32),
+                ("stream", C.c_void_p), ("reserved", C.c_int32 * 4)]
+
+
+class DenoiseParams(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("sigma_color", C.c_double), ("sigma_albedo", C.c_double), ("sigma_normal", C.c_double),
+                ("sigma_depth", C.c_double)]
+
+
 class LaunchPlan(C.Structure):
     """rt_launch_plan: what a launch decides (csrc/launch_plan.h); every scalar field but ray_budget is an int32."""
     _fields_ = [(n, C.c_uint32 if n == "ray_budget" else C.c_int32) for n in (
@@ -123,6 +133,12 @@ SIGNATURES = {
     "rt_film_download_sample_counts": (I, [P, C.POINTER(C.c_uint32), I, I]),
     "rt_adaptive_converged": (I, [C.POINTER(AdaptiveParams), C.c_uint32, D, D, D, D]),
     "rt_adaptive_rule_on_device": (I, [I, I, C.POINTER(AdaptiveParams), C.c_uint32, C.POINTER(C.c_uint32), D3, D3, D3, C.POINTER(C.c_uint8)]),
+    "rt_film_render_features": (I, [P, P, C.POINTER(FeatureParams)]),
+    "rt_film_download_features": (I, [P, D3, D3, D3, I, I]),
+    "rt_film_device_features": (P, [P, I]),
+    "rt_film_denoise": (I, [P, C.POINTER(DenoiseParams)]),
+    "rt_film_download_denoised": (I, [P, D3, I, I]),
+    "rt_denoise_frame": (I, [I, D3, D3, D3, D3, I, I, C.POINTER(DenoiseParams), D3]),
     "rt_deinterleave": (I, [D3, I, I, I, I, C.c_size_t, D3]),
     "rt_render": (I, [P, C.POINTER(RenderParams), D3, C.POINTER(RenderStats)]),
     "rt_write_ppm": (I, [C.c_char_p, D3, I, I]),

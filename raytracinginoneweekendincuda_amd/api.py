@@ -11,7 +11,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import AdaptiveParams, LaunchPlan, RenderParams, RenderStats, SceneInfo  # noqa: F401
+from ._lib import AdaptiveParams, DenoiseParams, FeatureParams, LaunchPlan, RenderParams, RenderStats, SceneInfo  # noqa: F401
 
 
 class RtowError(RuntimeError):
@@ -36,6 +36,10 @@ FLAG_NO_PIXEL_CLASSES = 64  # sphere-list worlds: one launch for all pixels (no 
 # rt_scene_set_options (read by the next commit)
 SCENE_PLAIN_QUADS = 1           # every quad takes the general test; boxes stay lists of six quads
 SCENE_REFERENCE_TREE_ONLY = 2   # no library tree for primitive worlds
+
+
+# Film.denoise / denoise_frame defaults (DESIGN.md section 5 has the frames they were chosen on)
+DENOISE_DEFAULTS = {"iterations": 5, "sigma_color": 0.6, "sigma_albedo": 0.1, "sigma_normal": 0.3, "sigma_depth": 0.1}
 
 
 def lib():
@@ -357,6 +361,66 @@ class Film:
         counts = np.zeros((self.height, self.width), dtype=np.uint32)
         _check(lib().rt_film_download_sample_counts(self._p, counts.ctypes.data_as(C.POINTER(C.c_uint32)), self.width, self.height))
         return counts
+
+    # ---- first-hit feature buffers and the a-trous filter (include/rtow.h) ----
+    def render_features(self, scene, samples=0, seed=1984, variant=0, stream=None):
+        """Albedo, shading normal and depth of the first hit of every owned pixel into planes the film keeps
+        (rt_film_render_features).  ``samples`` 0: one ray through the pixel centre; N >= 1: N primary rays drawn exactly as a
+        render of that seed draws them, averaged.  Touches nothing of the frame the film holds."""
+        p = FeatureParams(self.width, self.height, int(samples), int(seed), int(variant), stream)
+        _check(lib().rt_film_render_features(scene._p, self._p, C.byref(p)))
+
+    def features(self):
+        """(albedo (H, W, 3), normal (H, W, 3), depth (H, W)) of the last feature pass, row 0 = bottom like ``download``; 0 in
+        rows of other ranks."""
+        albedo = np.zeros((self.height, self.width, 3), dtype=np.float64)
+        normal = np.zeros((self.height, self.width, 3), dtype=np.float64)
+        depth = np.zeros((self.height, self.width), dtype=np.float64)
+        _check(lib().rt_film_download_features(self._p, albedo.ctypes.data_as(_lib.D3), normal.ctypes.data_as(_lib.D3),
+                                               depth.ctypes.data_as(_lib.D3), self.width, self.height))
+        return albedo, normal, depth
+
+    def device_features(self, which):
+        """Device pointer of one compact feature plane (0 albedo, 1 normal, 2 depth), or None before the first feature pass."""
+        return lib().rt_film_device_features(self._p, which)
+
+    def denoise(self, iterations=DENOISE_DEFAULTS["iterations"], sigma_color=DENOISE_DEFAULTS["sigma_color"],
+                sigma_albedo=DENOISE_DEFAULTS["sigma_albedo"], sigma_normal=DENOISE_DEFAULTS["sigma_normal"],
+                sigma_depth=DENOISE_DEFAULTS["sigma_depth"]):
+        """The edge-avoiding a-trous filter over the film's pixels, guided by its feature planes, into a buffer of its own
+        (rt_film_denoise; read it with ``denoised``).  The raw pixels stay as they are.  A sigma of ``inf`` switches its term off."""
+        p = DenoiseParams(int(iterations), float(sigma_color), float(sigma_albedo), float(sigma_normal), float(sigma_depth))
+        _check(lib().rt_film_denoise(self._p, C.byref(p)))
+
+    def denoised(self):
+        frame = np.zeros((self.height, self.width, 3), dtype=np.float64)
+        _check(lib().rt_film_download_denoised(self._p, frame.ctypes.data_as(_lib.D3), self.width, self.height))
+        return frame
+
+
+def denoise_frame(color, albedo=None, normal=None, depth=None, iterations=DENOISE_DEFAULTS["iterations"],
+                  sigma_color=DENOISE_DEFAULTS["sigma_color"], sigma_albedo=DENOISE_DEFAULTS["sigma_albedo"],
+                  sigma_normal=DENOISE_DEFAULTS["sigma_normal"], sigma_depth=DENOISE_DEFAULTS["sigma_depth"], device=0):
+    """The film's filter on host arrays (rt_denoise_frame): color (H, W, 3); albedo, normal (H, W, 3) and depth (H, W) may each
+    be None, that term is then off.  For frames gathered from several ranks and for synthetic inputs."""
+    color = np.ascontiguousarray(color, dtype=np.float64)
+    assert color.ndim == 3 and color.shape[2] == 3
+    h, w = color.shape[:2]
+
+    def guide(a, shape):
+        if a is None:
+            return None, None
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        assert a.shape == shape
+        return a, a.ctypes.data_as(_lib.D3)
+
+    albedo, pa = guide(albedo, (h, w, 3))
+    normal, pn = guide(normal, (h, w, 3))
+    depth, pz = guide(depth, (h, w))
+    out = np.zeros_like(color)
+    p = DenoiseParams(int(iterations), float(sigma_color), float(sigma_albedo), float(sigma_normal), float(sigma_depth))
+    _check(lib().rt_denoise_frame(device, color.ctypes.data_as(_lib.D3), pa, pn, pz, w, h, C.byref(p), out.ctypes.data_as(_lib.D3)))
+    return out
 
 
 def adaptive_rule_on_device(n, sums_rgbq, sample_rgb, min_samples, check_interval, noise_threshold, luminance_floor=0.01, variant=0, device=0):

@@ -6,6 +6,7 @@
 #include <cstdio>
 #include <cmath>
 #include <cstring>
+#include <initializer_list>
 #include <map>
 #include <mutex>
 #include <string>
@@ -132,6 +133,10 @@ struct FilmImpl {
     uint8_t *ad_mark = nullptr;
     bool rendered = false;
     int frame_spp = 0;  // without adaptive: samples every owned pixel has had in the frame the film holds
+    // first-hit feature planes (rt_film_render_features) and the filtered frame (rt_film_denoise), allocated on first use: compact
+    // like the pixels; denoise_tmp is the other half of the filter's ping-pong
+    double *feat_albedo = nullptr, *feat_normal = nullptr, *feat_depth = nullptr, *denoised = nullptr, *denoise_tmp = nullptr;
+    bool has_features = false, has_denoised = false;
 };
 
 static bool same_rule(const AdaptiveRule &a, const AdaptiveRule &b)
@@ -372,6 +377,8 @@ void rt_film_destroy(rt_film *film)
     if (f->ad_n) hipFree(f->ad_n);
     if (f->ad_q) hipFree(f->ad_q);
     if (f->ad_mark) hipFree(f->ad_mark);
+    for (double *plane : {f->feat_albedo, f->feat_normal, f->feat_depth, f->denoised, f->denoise_tmp})
+        if (plane) hipFree(plane);
     if (f->host_counters) hipHostFree(f->host_counters);
     for (int k = 0; k < 4; k++)
         if (f->ev[k]) hipEventDestroy(f->ev[k]);
@@ -787,6 +794,182 @@ int rt_adaptive_rule_on_device(int device, int variant, const rt_adaptive_params
     for (void *d : dev)
         if (d) hipFree(d);
     return e == hipSuccess ? RT_OK : hip_fail(e, "rt_adaptive_rule_on_device");
+}
+
+// ---- first-hit feature buffers and the a-trous filter ----
+static const char *denoise_params_error(const rt_denoise_params *p)
+{
+    if (!p) return "null params";
+    if (p->iterations < 1 || p->iterations > 8) return "iterations must be 1..8";
+    for (double sigma : {p->sigma_color, p->sigma_albedo, p->sigma_normal, p->sigma_depth})
+        if (!(sigma > 0.0)) return "every sigma must be > 0 (+inf switches its term off)";  // (a NaN fails the comparison)
+    return nullptr;
+}
+
+// The levels of the filter over full-frame device planes: level 0 reads `color`, the last level writes `out`, the ones between
+// alternate between `out` and `tmp` (tmp may be null for a single level).  color, out and tmp are distinct.
+static int enqueue_atrous(const double *color, const double *albedo, const double *normal, const double *depth, int width, int height,
+                          const rt_denoise_params &p, double *out, double *tmp, hipStream_t stream)
+{
+    auto inv_sq = [](double sigma) { return 1.0 / (sigma * sigma); };  // +inf: 0
+    AtrousArgs a{};
+    a.albedo = albedo;
+    a.normal = normal;
+    a.depth = depth;
+    a.width = width;
+    a.height = height;
+    a.inv_albedo = inv_sq(p.sigma_albedo);
+    a.inv_normal = inv_sq(p.sigma_normal);
+    a.inv_depth = inv_sq(p.sigma_depth);
+    const double *in = color;
+    for (int k = 0; k < p.iterations; k++) {
+        double *dst = ((p.iterations - 1 - k) % 2 == 0) ? out : tmp;  // the last level lands in `out`
+        a.in = in;
+        a.out = dst;
+        a.step = 1 << k;
+        a.inv_color = inv_sq(p.sigma_color * std::ldexp(1.0, -k));
+        HIP_TRY(launch_atrous(a, stream));
+        in = dst;
+    }
+    return RT_OK;
+}
+
+int rt_film_render_features(rt_scene *scene, rt_film *film, const rt_feature_params *p)
+{
+    if (!scene || !film || !p) return fail(RT_ERR_INVALID, "rt_film_render_features: null argument");
+    SceneImpl &s = *S(scene);
+    FilmImpl &f = *F(film);
+    if (p->width != f.width || p->height != f.height) return fail(RT_ERR_INVALID, "rt_film_render_features: params do not match the film's size");
+    if (p->samples < 0) return fail(RT_ERR_INVALID, "rt_film_render_features: negative samples");
+    if (p->variant != 0 && p->variant != 1) return fail(RT_ERR_INVALID, "rt_film_render_features: variant must be 0 (strict) or 1 (fast)");
+    if (f.in_flight) return fail(RT_ERR_STATE, "rt_film_render_features: a render of this film is in flight (rt_render_finish it first)");
+    if (int rc = rt_scene_upload(scene, f.device)) return rc;
+    if (int rc = select_device(f.device)) return rc;
+    const size_t np = f.n_pixels ? f.n_pixels : 1;
+    if (!f.feat_albedo) HIP_TRY(hipMalloc((void **)&f.feat_albedo, np * 3 * sizeof(double)));
+    if (!f.feat_normal) HIP_TRY(hipMalloc((void **)&f.feat_normal, np * 3 * sizeof(double)));
+    if (!f.feat_depth) HIP_TRY(hipMalloc((void **)&f.feat_depth, np * sizeof(double)));
+    FeatureArgs fa{};
+    fa.albedo = f.feat_albedo;
+    fa.normal = f.feat_normal;
+    fa.depth = f.feat_depth;
+    if (int rc = device_jump_table(f.device, &fa.jump_table)) return rc;
+    fa.base = xorwow_seed(p->seed, kSaltCurandDevice);
+    fa.n_pixels = f.n_pixels;
+    fa.width = f.width;
+    fa.height = f.height;
+    fa.samples = p->samples;
+    fa.stripe_rows = f.stripe_rows;
+    fa.rank = f.rank;
+    fa.world_size = f.world_size;
+    hipStream_t stream = p->stream ? (hipStream_t)p->stream : f.own_stream;
+    const DeviceScene &ds = s.device[f.device]->scene;
+    HIP_TRY(p->variant == 0 ? launch_features_strict(ds, fa, stream) : launch_features_fast(ds, fa, stream));
+    HIP_TRY(hipStreamSynchronize(stream));  // the kernel reads the scene's tables: done before the caller may change them
+    f.has_features = true;
+    f.has_denoised = false;
+    return RT_OK;
+}
+
+// compact rows of `channels` doubles per pixel -> the full frame, rows of other ranks 0
+static int download_plane(const FilmImpl &f, const double *device_plane, int channels, double *full)
+{
+    std::vector<double> compact((size_t)f.n_pixels * channels);
+    if (f.n_pixels) HIP_TRY(hipMemcpy(compact.data(), device_plane, compact.size() * sizeof(double), hipMemcpyDeviceToHost));
+    const size_t row = (size_t)f.width * channels;
+    std::memset(full, 0, row * (size_t)f.height * sizeof(double));
+    size_t lr = 0;
+    for (int j = 0; j < f.height; j++)
+        if ((j / f.stripe_rows) % f.world_size == f.rank) {
+            std::memcpy(full + (size_t)j * row, compact.data() + lr * row, sizeof(double) * row);
+            lr++;
+        }
+    return RT_OK;
+}
+
+int rt_film_download_features(rt_film *film, double *albedo_full, double *normal_full, double *depth_full, int width, int height)
+{
+    if (!film) return fail(RT_ERR_INVALID, "rt_film_download_features: null film");
+    FilmImpl &f = *F(film);
+    if (width != f.width || height != f.height) return fail(RT_ERR_INVALID, "rt_film_download_features: frame size mismatch");
+    if (!f.has_features) return fail(RT_ERR_STATE, "rt_film_download_features: no feature pass has run on this film (rt_film_render_features)");
+    if (int rc = select_device(f.device)) return rc;
+    if (albedo_full)
+        if (int rc = download_plane(f, f.feat_albedo, 3, albedo_full)) return rc;
+    if (normal_full)
+        if (int rc = download_plane(f, f.feat_normal, 3, normal_full)) return rc;
+    if (depth_full)
+        if (int rc = download_plane(f, f.feat_depth, 1, depth_full)) return rc;
+    return RT_OK;
+}
+
+void *rt_film_device_features(rt_film *film, int which)
+{
+    if (!film || !F(film)->has_features) return nullptr;
+    return which == 0 ? F(film)->feat_albedo : which == 1 ? F(film)->feat_normal : which == 2 ? F(film)->feat_depth : nullptr;
+}
+
+int rt_film_denoise(rt_film *film, const rt_denoise_params *p)
+{
+    if (!film) return fail(RT_ERR_INVALID, "rt_film_denoise: null film");
+    if (const char *why = denoise_params_error(p)) return fail(RT_ERR_INVALID, std::string("rt_film_denoise: ") + why);
+    FilmImpl &f = *F(film);
+    if (f.world_size > 1)
+        return fail(RT_ERR_UNSUPPORTED, "rt_film_denoise: this film owns only part of the frame, its pixels' neighbours live on other "
+                                        "ranks (gather the planes and use rt_denoise_frame)");
+    if (f.in_flight) return fail(RT_ERR_STATE, "rt_film_denoise: a render of this film is in flight (rt_render_finish it first)");
+    if (!f.has_features) return fail(RT_ERR_STATE, "rt_film_denoise: no feature pass has run on this film (rt_film_render_features)");
+    if (int rc = select_device(f.device)) return rc;
+    const size_t bytes = (size_t)(f.n_pixels ? f.n_pixels : 1) * 3 * sizeof(double);
+    if (!f.denoised) HIP_TRY(hipMalloc((void **)&f.denoised, bytes));
+    if (!f.denoise_tmp && p->iterations > 1) HIP_TRY(hipMalloc((void **)&f.denoise_tmp, bytes));
+    // (one rank owns every row: the compact planes are the full frame)
+    if (int rc = enqueue_atrous(f.pixels, f.feat_albedo, f.feat_normal, f.feat_depth, f.width, f.height, *p, f.denoised, f.denoise_tmp, f.own_stream))
+        return rc;
+    HIP_TRY(hipStreamSynchronize(f.own_stream));
+    f.has_denoised = true;
+    return RT_OK;
+}
+
+int rt_film_download_denoised(rt_film *film, double *frame_full, int width, int height)
+{
+    if (!film || !frame_full) return fail(RT_ERR_INVALID, "rt_film_download_denoised: null argument");
+    FilmImpl &f = *F(film);
+    if (width != f.width || height != f.height) return fail(RT_ERR_INVALID, "rt_film_download_denoised: frame size mismatch");
+    if (!f.has_denoised) return fail(RT_ERR_STATE, "rt_film_download_denoised: nothing filtered yet (rt_film_denoise)");
+    if (int rc = select_device(f.device)) return rc;
+    return download_plane(f, f.denoised, 3, frame_full);
+}
+
+int rt_denoise_frame(int device, const double *color, const double *albedo, const double *normal, const double *depth, int width,
+                     int height, const rt_denoise_params *p, double *out)
+{
+    if (!color || !out) return fail(RT_ERR_INVALID, "rt_denoise_frame: null colour or output");
+    if (width <= 0 || height <= 0 || (int64_t)width * height >= (int64_t)1 << 31) return fail(RT_ERR_INVALID, "rt_denoise_frame: bad frame size");
+    if (const char *why = denoise_params_error(p)) return fail(RT_ERR_INVALID, std::string("rt_denoise_frame: ") + why);
+    if (int rc = select_device(device)) return rc;
+    const size_t n = (size_t)width * (size_t)height;
+    const void *host_in[4] = {color, albedo, normal, depth};
+    const size_t bytes[6] = {n * 3 * sizeof(double), n * 3 * sizeof(double), n * 3 * sizeof(double), n * sizeof(double),
+                             n * 3 * sizeof(double), n * 3 * sizeof(double)};  // colour, albedo, normal, depth, out, tmp
+    void *dev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    hipError_t e = hipSuccess;
+    for (int k = 0; k < 6 && e == hipSuccess; k++) {
+        if (k < 4 && !host_in[k]) continue;
+        if (k == 5 && p->iterations == 1) continue;
+        e = hipMalloc(&dev[k], bytes[k]);
+        if (e == hipSuccess && k < 4) e = hipMemcpy(dev[k], host_in[k], bytes[k], hipMemcpyHostToDevice);
+    }
+    int rc = RT_OK;
+    if (e == hipSuccess)
+        rc = enqueue_atrous((const double *)dev[0], (const double *)dev[1], (const double *)dev[2], (const double *)dev[3], width, height, *p,
+                            (double *)dev[4], (double *)dev[5], nullptr);
+    if (e == hipSuccess && rc == RT_OK) e = hipDeviceSynchronize();
+    if (e == hipSuccess && rc == RT_OK) e = hipMemcpy(out, dev[4], bytes[4], hipMemcpyDeviceToHost);
+    for (void *d : dev)
+        if (d) hipFree(d);
+    if (rc != RT_OK) return rc;
+    return e == hipSuccess ? RT_OK : hip_fail(e, "rt_denoise_frame");
 }
 
 int rt_render(rt_scene *scene, const rt_render_params *params, double *frame, rt_render_stats *stats)

@@ -17,8 +17,15 @@
 // Multi-GPU frame: rows dealt to the N GPUs of the node in 8-row stripes (rank = stripe % N), every GPU renders its
 // stripes into a compact buffer, ONE ncclGather over xGMI brings them to GPU 0, the host de-interleaves.
 // Single process, one HIP stream and one RCCL communicator per device.
+// --denoise / --aov-prefix with --gpus: every rank runs the feature pass on its stripes and the three planes are gathered like
+// the pixels (same staging buffers, same communicators), then scattered into full frames on the host.
+struct FeatureRequest {
+    int samples;
+    std::vector<double> albedo, normal, depth;  // full frames: W*H*3, W*H*3, W*H
+};
+
 static int render_multi_gpu(rt_scene *scene, rt_render_params base, int n_gpus, double *frame, rt_render_stats *total,
-                            double *gather_seconds)
+                            double *gather_seconds, FeatureRequest *features = nullptr)
 {
     const int W = base.width, H = base.height, stripe = 8;
     int rows_max = 0;
@@ -91,6 +98,47 @@ static int render_multi_gpu(rt_scene *scene, rt_render_params base, int n_gpus, 
     hip_ok(hipSetDevice(0), "hipSetDevice(0)");
     hip_ok(hipMemcpy(gathered.data(), recv, gathered.size() * sizeof(double), hipMemcpyDeviceToHost), "hipMemcpy(D2H)");
     int rc = rt_deinterleave(gathered.data(), W, H, stripe, n_gpus, count, frame);
+    if (rc == RT_OK && features) {
+        rt_feature_params fp{};
+        fp.width = W;
+        fp.height = H;
+        fp.samples = features->samples;
+        fp.seed = base.seed;
+        fp.variant = base.variant;
+        for (int r = 0; r < n_gpus; r++) {
+            fp.stream = streams[r];
+            if (rt_film_render_features(scene, films[r], &fp) != RT_OK) return 1;
+        }
+        std::vector<double> *planes[3] = {&features->albedo, &features->normal, &features->depth};
+        for (int which = 0; which < 3; which++) {
+            const int channels = which == 2 ? 1 : 3;
+            const size_t plane_count = (size_t)rows_max * W * channels;  // doubles per rank (the pixels' staging buffers hold 3 per pixel)
+            for (int r = 0; r < n_gpus; r++) {
+                const size_t owned = (size_t)rt_stripe_rows(H, stripe, r, n_gpus, nullptr, 0) * W * channels;
+                hip_ok(hipSetDevice(r), "hipSetDevice");
+                hip_ok(hipMemcpyAsync(send[r], rt_film_device_features(films[r], which), owned * sizeof(double), hipMemcpyDeviceToDevice, streams[r]),
+                       "hipMemcpyAsync(feature plane)");
+            }
+            nccl_ok(ncclGroupStart(), "ncclGroupStart");
+            for (int r = 0; r < n_gpus; r++)
+                nccl_ok(ncclGather(send[r], r == 0 ? recv : nullptr, plane_count, ncclDouble, 0, comms[r], streams[r]), "ncclGather(features)");
+            nccl_ok(ncclGroupEnd(), "ncclGroupEnd");
+            for (int r = 0; r < n_gpus; r++) {
+                hip_ok(hipSetDevice(r), "hipSetDevice");
+                hip_ok(hipStreamSynchronize(streams[r]), "hipStreamSynchronize");
+            }
+            hip_ok(hipSetDevice(0), "hipSetDevice(0)");
+            hip_ok(hipMemcpy(gathered.data(), recv, plane_count * n_gpus * sizeof(double), hipMemcpyDeviceToHost), "hipMemcpy(D2H)");
+            planes[which]->assign((size_t)W * H * channels, 0.0);
+            std::vector<int> rows((size_t)rows_max);
+            for (int r = 0; r < n_gpus; r++) {
+                const int n = rt_stripe_rows(H, stripe, r, n_gpus, rows.data(), rows_max);
+                for (int lr = 0; lr < n; lr++)
+                    std::memcpy(planes[which]->data() + (size_t)rows[lr] * W * channels, gathered.data() + (size_t)r * plane_count + (size_t)lr * W * channels,
+                                sizeof(double) * (size_t)W * channels);
+            }
+        }
+    }
     for (int r = 0; r < n_gpus; r++) {
         hipSetDevice(r);
         ncclCommDestroy(comms[r]);
@@ -162,6 +210,12 @@ int main(int argc, char **argv)
     int min_spp = 16, check_every = 16;
     std::string samples_map;     // --samples-map: the samples every pixel took, as a 16-bit PGM
     bool noise_given = false, adaptive_option = false;  // --noise seen; an option that only means something with it seen
+    // first-hit feature buffers and the a-trous filter (--denoise, --aov-prefix)
+    bool denoise = false, denoise_option = false;  // --denoise seen; an option that only means something with it seen
+    rt_denoise_params dp{5, 0.6, 0.1, 0.3, 0.1};   // the library's defaults
+    int feature_samples = 0;
+    bool feature_samples_given = false;
+    std::string raw_output, aov_prefix;
     for (int k = 1; k < argc; k++) {
         std::string a = argv[k];
         auto val = [&](const char *name) -> const char * {
@@ -199,6 +253,23 @@ int main(int argc, char **argv)
             samples_map = v;
             adaptive_option = true;
         }
+        else if (a == "--denoise") denoise = true;
+        else if (const char *v = val("--denoise-iterations")) {
+            dp.iterations = std::atoi(v);
+            denoise_option = true;
+        } else if (const char *v = val("--denoise-sigmas")) {
+            if (std::sscanf(v, "%lf,%lf,%lf,%lf", &dp.sigma_color, &dp.sigma_albedo, &dp.sigma_normal, &dp.sigma_depth) != 4) {
+                std::fprintf(stderr, "--denoise-sigmas needs four numbers c,a,n,z (inf switches a term off), not '%s'\n", v);
+                return 2;
+            }
+            denoise_option = true;
+        } else if (const char *v = val("--raw-output")) {
+            raw_output = v;
+            denoise_option = true;
+        } else if (const char *v = val("--feature-samples")) {
+            feature_samples = std::atoi(v);
+            feature_samples_given = true;
+        } else if (const char *v = val("--aov-prefix")) aov_prefix = v;
         else if (const char *v = val("--earth")) earth_path = v;
         else if (const char *v = val("--earth-bytes")) {
             earth_path = v;
@@ -209,6 +280,14 @@ int main(int argc, char **argv)
                          "            [--world bvh|list] [--variant strict|fast] [--device N] [--gpus N] [--output file.ppm]\n"
                          "            [--earth earthmap.jpg|decoded.ppm | --earth-bytes texture.ppm] [--accelerate-lists] [--flags N]\n"
                          "            [--noise T [--min-spp N] [--check-every K] [--samples-map file.pgm]]\n"
+                         "            [--denoise [--denoise-iterations N] [--denoise-sigmas c,a,n,z] [--raw-output file.ppm]]\n"
+                         "            [--aov-prefix P] [--feature-samples N]\n"
+                         "  --denoise      --output gets the frame after the edge-avoiding a-trous filter (1..8 levels, default 5; sigmas of the colour,\n"
+                         "                 albedo, normal and depth edge stops, inf = off), guided by the first hits' albedo, normal and depth;\n"
+                         "                 --raw-output: the unfiltered frame beside it\n"
+                         "  --aov-prefix   write those three buffers as P_albedo.pfm, P_normal.pfm and P_depth.pfm (depth in all three channels)\n"
+                         "  --feature-samples  primary rays per pixel for the buffers, drawn as the render draws them (default 0: one ray through\n"
+                         "                 the pixel centre)\n"
                          "  --noise        adaptive sampling: a pixel stops at the first check (after --min-spp samples, default 16, then every\n"
                          "                 --check-every, default 16) where the standard error of its mean is at most T x max(mean, 0.01);\n"
                          "                 --spp is then the most samples a pixel takes.  Use T >= 0.001.  One GPU (no --gpus)\n"
@@ -234,6 +313,20 @@ int main(int argc, char **argv)
     }
     if (adaptive && gpus >= 1) {
         std::fprintf(stderr, "--noise renders on one GPU (no --gpus)\n");
+        return 2;
+    }
+    const bool wants_features = denoise || !aov_prefix.empty();
+    if (!denoise && denoise_option) {
+        std::fprintf(stderr, "--denoise-iterations, --denoise-sigmas and --raw-output need --denoise\n");
+        return 2;
+    }
+    if (!wants_features && feature_samples_given) {
+        std::fprintf(stderr, "--feature-samples needs --denoise or --aov-prefix\n");
+        return 2;
+    }
+    if (feature_samples < 0 || dp.iterations < 1 || dp.iterations > 8 || !(dp.sigma_color > 0) || !(dp.sigma_albedo > 0) || !(dp.sigma_normal > 0) ||
+        !(dp.sigma_depth > 0)) {
+        std::fprintf(stderr, "--feature-samples needs N >= 0, --denoise-iterations 1..8, --denoise-sigmas four numbers > 0\n");
         return 2;
     }
     if (spp < 0) spp = (scene_id == 9) ? 100 : ((scene_id >= 5 && scene_id <= 8) ? 200 : 10);  // R/kernel.cu:593
@@ -299,8 +392,41 @@ int main(int argc, char **argv)
     rt_render_stats st{};
     auto t0 = std::chrono::steady_clock::now();
     double gather_s = 0.0;
+    FeatureRequest features{feature_samples, {}, {}, {}};
+    std::vector<double> clean;  // --denoise: the filtered frame
+    // one GPU: the feature pass on the film that holds the frame, the planes to the host, the filter on the film
+    auto film_features = [&](rt_film *film) {
+        rt_feature_params fp{};
+        fp.width = width;
+        fp.height = height;
+        fp.samples = feature_samples;
+        fp.seed = seed;
+        fp.variant = variant;
+        features.albedo.resize(frame.size());
+        features.normal.resize(frame.size());
+        features.depth.resize((size_t)width * height);
+        if (rt_film_render_features(scene, film, &fp) != RT_OK ||
+            rt_film_download_features(film, features.albedo.data(), features.normal.data(), features.depth.data(), width, height) != RT_OK)
+            return false;
+        if (!denoise) return true;
+        clean.resize(frame.size());
+        return rt_film_denoise(film, &dp) == RT_OK && rt_film_download_denoised(film, clean.data(), width, height) == RT_OK;
+    };
     if (gpus >= 1) {
-        if (render_multi_gpu(scene, p, gpus, frame.data(), &st, &gather_s) != 0) return die("render (multi-GPU)");
+        if (render_multi_gpu(scene, p, gpus, frame.data(), &st, &gather_s, wants_features ? &features : nullptr) != 0) return die("render (multi-GPU)");
+        if (denoise) {  // the planes are gathered: the same kernel on the whole frame, on GPU 0
+            clean.resize(frame.size());
+            if (rt_denoise_frame(0, frame.data(), features.albedo.data(), features.normal.data(), features.depth.data(), width, height, &dp,
+                                 clean.data()) != RT_OK)
+                return die("denoise");
+        }
+    } else if (wants_features && !adaptive) {
+        rt_film *film = rt_film_create(device, width, height, p.stripe_rows, 0, 1);
+        if (!film) return die("film");
+        if (rt_render_launch(scene, film, &p) != RT_OK || rt_render_finish(scene, film, &st) != RT_OK) return die("render");
+        if (rt_film_download(film, frame.data(), width, height) != RT_OK) return die("download");
+        if (!film_features(film)) return die("features / denoise");
+        rt_film_destroy(film);
     } else if (adaptive) {
         rt_film *film = rt_film_create(device, width, height, p.stripe_rows, 0, 1);
         if (!film) return die("film");
@@ -310,6 +436,8 @@ int main(int argc, char **argv)
         if (rt_film_download(film, frame.data(), width, height) != RT_OK) return die("download");
         std::vector<uint32_t> counts((size_t)width * height);
         if (rt_film_download_sample_counts(film, counts.data(), width, height) != RT_OK) return die("sample counts");
+        // an adaptive frame is filtered like any other: the film's pixels, whatever sample count each has
+        if (wants_features && !film_features(film)) return die("features / denoise");
         rt_film_destroy(film);
         std::fprintf(stderr, "adaptive: %.2f samples per pixel on average (noise %g, at least %d, at most %d).\n",
                      (double)st.samples / ((double)width * height), noise, min_spp, spp);
@@ -340,7 +468,16 @@ int main(int argc, char **argv)
     std::fprintf(stderr, "took %g seconds.\n", kern);
     std::fprintf(stderr, "%.1f Msamples/s, %.1f Mray/s (kernels); %.3f s wall incl. upload/download\n",
                  st.samples / kern * 1e-6, st.rays / kern * 1e-6, wall);
-    if (rt_write_ppm(out.c_str(), frame.data(), width, height) != RT_OK) return die("ppm");
+    if (rt_write_ppm(out.c_str(), denoise ? clean.data() : frame.data(), width, height) != RT_OK) return die("ppm");
+    if (!raw_output.empty() && rt_write_ppm(raw_output.c_str(), frame.data(), width, height) != RT_OK) return die("ppm (raw)");
+    if (!aov_prefix.empty()) {
+        std::vector<double> depth3(frame.size());  // depth in all three channels: one PFM writer for all
+        for (size_t k = 0; k < features.depth.size(); k++) depth3[3 * k] = depth3[3 * k + 1] = depth3[3 * k + 2] = features.depth[k];
+        if (rt_write_pfm((aov_prefix + "_albedo.pfm").c_str(), features.albedo.data(), width, height) != RT_OK ||
+            rt_write_pfm((aov_prefix + "_normal.pfm").c_str(), features.normal.data(), width, height) != RT_OK ||
+            rt_write_pfm((aov_prefix + "_depth.pfm").c_str(), depth3.data(), width, height) != RT_OK)
+            return die("pfm");
+    }
     std::fprintf(stderr, "\nDone. Saved to %s\n", out.c_str());
     rt_scene_destroy(scene);
     return 0;

@@ -43,6 +43,9 @@
 #ifndef RT_ADAPT  // 1: this translation unit holds the Adaptive<> instantiations of its group and nothing else
 #define RT_ADAPT 0
 #endif
+#ifndef RT_FEATURES  // 1: this translation unit holds the first-hit feature kernels (feature_kernel) and nothing else
+#define RT_FEATURES 0
+#endif
 
 namespace rtow {
 namespace {
@@ -3585,7 +3588,7 @@ __global__ __launch_bounds__(T::BLOCK, T::MIN_WAVES) void render_kernel(DeviceSc
     }
 }
 
-#if RT_STRICT && RT_GROUP == 0 && !RT_ADAPT
+#if RT_STRICT && RT_GROUP == 0 && !RT_ADAPT && !RT_FEATURES
 // Rank the tiles by probed cost, heaviest first.  A pixel's samples are sequential (one RNG stream), so the frame can
 // never end before its longest pixel does: those pixels have to start first, not wherever row-major order puts them.
 __global__ __launch_bounds__(1024) void tile_order_kernel(const uint32_t *cost, uint32_t *order, uint32_t n, uint32_t flat_x8)
@@ -3683,7 +3686,7 @@ hipError_t launch_tile_order(const uint32_t *tile_cost, uint32_t *tile_order, ui
 #define RT_CAT2(a, b) a##b
 #define RT_CAT(a, b) RT_CAT2(a, b)
 
-#if RT_GROUP == 0 && !RT_ADAPT
+#if RT_GROUP == 0 && !RT_ADAPT && !RT_FEATURES
 hipError_t RT_CAT(launch_seed_, RT_SUFFIX)(const SeedArgs &a, hipStream_t stream)
 {
     if (a.n_pixels == 0) return hipSuccess;
@@ -3806,7 +3809,107 @@ hipError_t RT_CAT(launch_composite_, RT_SUFFIX)(int which, const DeviceScene &sc
 hipError_t RT_CAT(launch_adaptive_prims_, RT_SUFFIX)(int which, const DeviceScene &sc, const RenderArgs &a, hipStream_t stream, KernelInfo *info);
 hipError_t RT_CAT(launch_adaptive_composite_, RT_SUFFIX)(int which, const DeviceScene &sc, const RenderArgs &a, hipStream_t stream, KernelInfo *info);
 
-#if RT_GROUP == 1
+#if RT_FEATURES
+// ------------------------------------------------------------------------------------------------
+// First-hit feature pass (rt_film_render_features): albedo, shading normal and depth of the closest hit over [0.001, inf) of
+// every primary ray.  One lane per owned pixel, no persistent waves, no LDS staging, every table from global memory; the world is
+// searched as the general kernels search it under RT_FLAG_REFERENCE_TREE | RT_FLAG_FORCE_GENERAL -- the reference's tree
+// (walk_node / walk_leaves) or list (world_hit_list) in the reference's order, so that media draw what they draw in a render and
+// coincident primitives are decided as the reference decides them -- and the hit record is make_surface's.
+// ------------------------------------------------------------------------------------------------
+namespace {
+// samples == 0: the ray through the pixel centre, no lens offset, at the shutter's opening; the camera takes no draws
+DEV Ray centre_ray(const CameraRec *cam_generic, int i, int j, int width, int height)
+{
+    const RT_CONST CameraRec *cam = (const RT_CONST CameraRec *)(uintptr_t)cam_generic;
+    const double u = ((double)i + 0.5) / (double)width, v = ((double)j + 0.5) / (double)height;
+    const Vec origin = load3c(cam->origin);
+    Ray r;
+    r.o = origin;
+    r.d = load3c(cam->llc) + u * load3c(cam->horizontal) + v * load3c(cam->vertical) - origin;
+    r.tm = cam->time0;
+    return r;
+}
+}  // namespace
+
+template <int STRICT, class T>
+__global__ __launch_bounds__(256) void feature_kernel(DeviceScene sc, FeatureArgs a)
+{
+    sc.lds_quad_aa = sc.lds_boxes = sc.lds_objects = sc.lds_xforms = sc.lds_media = sc.lds_materials = sc.lds_perlin = kNone;
+    sc.lds_spheres_tab = sc.lds_group_boxes = sc.lds_mspheres = sc.lds_msphere_aux = sc.lds_sphere_aux = kNone;
+    const uint32_t local = blockIdx.x * blockDim.x + threadIdx.x;
+    if (local >= a.n_pixels) return;
+    const int lr = (int)(local / (uint32_t)a.width), i = (int)(local % (uint32_t)a.width);
+    const int j = owned_row(lr, a.stripe_rows, a.rank, a.world_size);
+    Xorwow rng = a.base;  // as seed_kernel seeds the pixel: pixelIndex, R/kernel.cu:117-118
+    xorwow_skip_sequences(a.jump_table, (uint64_t)((int64_t)j * a.width + i), rng);
+    const CameraRec *__restrict__ cam = sc.camera;
+    const NodeView nv{sc.nodes, 0u, false};
+    Vec albedo = mk(0.0, 0.0, 0.0), normal = mk(0.0, 0.0, 0.0);
+    double depth = 0.0;
+    const int n = a.samples > 0 ? a.samples : 1;
+    for (int sample = 0; sample < n; sample++) {
+        const Ray ray = a.samples > 0 ? camera_ray(cam, i, j, a.width, a.height, rng) : centre_ray(cam, i, j, a.width, a.height);
+        HitInfo h;
+        h.t = 0.0;
+        h.ref = kNone;
+        h.obj = kNone;
+        bool hit = false;
+        if constexpr (T::WORLD == 0) {
+            if (sc.n_world_nodes != 0) {
+                Walk w{};
+                walk_begin<false>(w, ray, DBL_MAX);
+                while (w.state != kNone) {
+                    if (walk_moving(w.state)) walk_node<false>(nv, ray, 0.001, w);
+                    else walk_leaves<T>(sc, nv, ray, 0.001, w, h, rng);
+                }
+                hit = w.any;
+            }
+        } else {
+            hit = world_hit_list<T>(sc, ray, 0.001, DBL_MAX, h, rng);
+        }
+        Vec value, sn = mk(0.0, 0.0, 0.0);
+        double sd = 0.0;
+        if (!hit) {
+            value = load3c(((const RT_CONST CameraRec *)(uintptr_t)cam)->bg);
+        } else {
+            const Surface s = make_surface<T>(sc, ray, h);
+            const MatView mp = material_view<false>(sc, s.mat);
+            const uint32_t kind = mp.u32(MAT_OFF(kind));
+            if (kind == MAT_METAL) value = mp.vec(MAT_OFF(r));
+            else if (kind == MAT_DIELECTRIC) value = mk(1.0, 1.0, 1.0);
+            else value = material_texture<T>(sc, mp, mp.u32(MAT_OFF(tex_inline)), s.u, s.v, s.p);  // Lambertian, isotropic, diffuse light
+            if ((h.ref >> kRefShift) != REF_MEDIUM) sn = s.n;
+            sd = h.t * length(ray.d);
+        }
+        // the sum as a render forms it: accumulated = 0 + throughput (1, 1, 1) * value, col += accumulated (render_kernel)
+        albedo = albedo + (mk(0.0, 0.0, 0.0) + mk(1.0, 1.0, 1.0) * value);
+        normal = normal + sn;
+        depth = depth + sd;
+    }
+    if (a.samples > 0) {
+        albedo = over(albedo, (double)n);
+        normal = over(normal, (double)n);
+        depth = (1 / (double)n) * depth;
+    }
+    a.albedo[(size_t)local * 3 + 0] = albedo.x;
+    a.albedo[(size_t)local * 3 + 1] = albedo.y;
+    a.albedo[(size_t)local * 3 + 2] = albedo.z;
+    a.normal[(size_t)local * 3 + 0] = normal.x;
+    a.normal[(size_t)local * 3 + 1] = normal.y;
+    a.normal[(size_t)local * 3 + 2] = normal.z;
+    a.depth[local] = depth;
+}
+
+hipError_t RT_CAT(launch_features_, RT_SUFFIX)(const DeviceScene &sc, const FeatureArgs &a, hipStream_t stream)
+{
+    if (a.n_pixels == 0) return hipSuccess;
+    const dim3 grid((a.n_pixels + 255u) / 256u), block(256);
+    if (sc.world_kind == WORLD_BVH) hipLaunchKernelGGL((feature_kernel<RT_STRICT, TBvhNested>), grid, block, 0, stream, sc, a);
+    else hipLaunchKernelGGL((feature_kernel<RT_STRICT, TListNested>), grid, block, 0, stream, sc, a);
+    return hipGetLastError();
+}
+#elif RT_GROUP == 1
 namespace {
 template <bool AD>
 hipError_t launch_composite_as(int which, const DeviceScene &sc, const RenderArgs &a, hipStream_t stream, KernelInfo *info)

@@ -106,6 +106,35 @@ hipError_t launch_adaptive_rule_strict(const AdaptiveRule &rule, uint32_t count,
 hipError_t launch_adaptive_rule_fast(const AdaptiveRule &rule, uint32_t count, const uint32_t *n, const double *sums_rgbq,
                                      const double *sample_rgb, double *q_out, uint8_t *stops_out, hipStream_t stream);
 
+// First-hit feature pass (rt_film_render_features; the RT_FEATURES objects of render.hip): one lane per owned pixel, the
+// reference's tree or list in the reference's order through the same leaf tests and make_surface as the render kernels.  The
+// pixel's stream is seeded in the kernel (curand_init(seed, pixelIndex, 0)): the film's saved state is neither read nor written.
+struct FeatureArgs {
+    double *albedo, *normal;     // rows_owned x width x 3 each, compact like RenderArgs::pixels
+    double *depth;               // rows_owned x width
+    const uint32_t *jump_table;  // kJumpTableWords
+    Xorwow base;                 // salted seed state (sequence 0)
+    uint32_t n_pixels;
+    int32_t width, height;
+    int32_t samples;             // 0: one ray through the pixel centre; N >= 1: N camera_ray samples, averaged
+    int32_t stripe_rows, rank, world_size;
+};
+hipError_t launch_features_strict(const DeviceScene &sc, const FeatureArgs &a, hipStream_t stream);
+hipError_t launch_features_fast(const DeviceScene &sc, const FeatureArgs &a, hipStream_t stream);
+
+// One level of the edge-avoiding a-trous filter (denoise.hip; include/rtow.h rt_denoise_params has the stencil): full-frame
+// planes, `in` and `out` distinct.  A guide that is nullptr switches its term off; inv_* = 1 / sigma^2 (0 for sigma = +inf), the
+// colour's already scaled for the level.
+struct AtrousArgs {
+    const double *in;       // height x width x 3
+    double *out;
+    const double *albedo, *normal;  // height x width x 3, or nullptr
+    const double *depth;            // height x width, or nullptr
+    int32_t width, height, step;
+    double inv_color, inv_albedo, inv_normal, inv_depth;
+};
+hipError_t launch_atrous(const AtrousArgs &a, hipStream_t stream);
+
 // class 1 + an entry in `list` (its length in *count, which the caller has zeroed) for every pixel whose probed cost is at
 // least `threshold` rays, class 0 for the others; with super_list: the pixels of at least super_threshold rays go there instead
 // (length count[1])
