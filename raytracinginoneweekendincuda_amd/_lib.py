@@ -47,7 +47,8 @@ class LaunchPlan(C.Structure):
         "node_burst", "park_ratio", "leaf_batch", "object_batch", "rounds", "shade_batch", "ray_budget",
         "rank_tiles", "pixel_classes", "probe_spp", "tile_flatness_x8", "heavy_threshold", "super_threshold",
         "near_percent", "near_neighbours", "heavy_waves", "heavy_ppw", "super_ppw", "heavy_priority", "adaptive_ppw",
-        "lds_front_bytes")] + [("lds_table_offset", C.c_uint32 * 16), ("lds_table_bytes", C.c_uint32 * 16)]
+        "lds_front_bytes")] + [("lds_table_offset", C.c_uint32 * 16), ("lds_table_bytes", C.c_uint32 * 16),
+                               ("probe_keeps", C.c_int32), ("probe_ray_cap", C.c_int32)]
 
 
 # the order of rt_launch_plan.lds_table_offset / lds_table_bytes (include/rtow.h RT_LDS_TABLE_NAMES, csrc/launch_plan.h LdsTable)
@@ -125,6 +126,7 @@ SIGNATURES = {
     "rt_film_pixel_bytes": (C.c_size_t, [P]),
     "rt_film_bind_pixels": (I, [P, P]),
     "rt_plan_launch": (I, [P, C.POINTER(RenderParams), I, I, C.POINTER(LaunchPlan)]),
+    "rt_film_download_probe_costs": (I, [P, C.POINTER(C.c_uint32), I, I]),
     "rt_scene_upload": (I, [P, I]),
     "rt_render_launch": (I, [P, P, C.POINTER(RenderParams)]),
     "rt_render_finish": (I, [P, P, C.POINTER(RenderStats)]),

@@ -362,6 +362,13 @@ class Film:
         _check(lib().rt_film_download_sample_counts(self._p, counts.ctypes.data_as(C.POINTER(C.c_uint32)), self.width, self.height))
         return counts
 
+    def probe_costs(self):
+        """Tests: the rays the rehearsal of the last launch booked per pixel, (H, W) uint32 like ``sample_counts`` -- a pixel it
+        stopped at the plan's ``probe_ray_cap`` has at least that many.  Raises where that launch classified no pixels."""
+        costs = np.zeros((self.height, self.width), dtype=np.uint32)
+        _check(lib().rt_film_download_probe_costs(self._p, costs.ctypes.data_as(C.POINTER(C.c_uint32)), self.width, self.height))
+        return costs
+
     # ---- first-hit feature buffers and the a-trous filter (include/rtow.h) ----
     def render_features(self, scene, samples=0, seed=1984, variant=0, stream=None):
         """Albedo, shading normal and depth of the first hit of every owned pixel into planes the film keeps

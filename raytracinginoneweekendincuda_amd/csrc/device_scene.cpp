@@ -104,6 +104,7 @@ struct FilmImpl {
     double *own_pixels = nullptr;
     double *accum = nullptr;       // progressive rendering: unnormalised colour sums (allocated on first use)
     int accum_spp = 0;
+    double *carry = nullptr;       // frames without RT_FLAG_ACCUMULATE: the sums a rehearsal hands to its frame launch (allocated on first use)
     uint32_t *state = nullptr;
     unsigned long long *ray_counter = nullptr;  // [0] rays, [2] samples taken (adaptive sampling), [1] / [6] / [9] low words = tile / heavy / super queue cursors, [7] and [32..119] phase sums
     int num_cus = 256;
@@ -365,6 +366,7 @@ void rt_film_destroy(rt_film *film)
     }
     if (f->own_pixels) hipFree(f->own_pixels);
     if (f->accum) hipFree(f->accum);
+    if (f->carry) hipFree(f->carry);
     if (f->state) hipFree(f->state);
     if (f->ray_counter) hipFree(f->ray_counter);
     if (f->tile_cost) hipFree(f->tile_cost);
@@ -524,18 +526,29 @@ static int allocate_class_planes(FilmImpl &f, const rt_launch_plan &plan)
 }
 
 // The rehearsal and what follows from it (plan_frame has the reasons): the probe launch, the tiles ranked by its ray counts,
-// the pixels classified by them; `ra` receives the order and the lists for the render launch.
+// the pixels classified by them; `ra` receives the order and the lists for the render launch.  Where the rehearsal keeps its
+// samples (plan.probe_keeps) it is the frame's first probe_spp samples: it continues from and writes to the frame's running sums
+// -- the film's, or a plane of the film's own for a frame that is not accumulated -- and `ra` becomes the launch of the rest.
 static int enqueue_rehearsal(FilmImpl &f, const DeviceScene &ds, const rt_launch_plan &plan, const Build &build, RenderArgs &ra, hipStream_t stream)
 {
+    const bool keeps = plan.probe_keeps != 0;
+    if (keeps && !ra.accum) {
+        if (!f.carry) HIP_TRY(hipMalloc((void **)&f.carry, (size_t)(f.n_pixels ? f.n_pixels : 1) * 3 * sizeof(double)));
+        ra.accum = f.carry;
+        ra.spp_before = 0;
+    }
     RenderArgs probe = ra;
-    probe.probe = 1;
-    probe.adaptive = 0;  // the rehearsal is the plain kernel's: it only counts rays
+    probe.probe = keeps ? 2 : 1;
+    probe.adaptive = 0;  // the rehearsal is the plain kernel's
     probe.ad_n = nullptr;
     probe.ad_q = nullptr;
     probe.ad_mark = nullptr;
     probe.spp = plan.probe_spp;
-    probe.accum = nullptr;
-    probe.spp_before = 0;
+    if (!keeps) {  // it only counts rays
+        probe.accum = nullptr;
+        probe.spp_before = 0;
+    }
+    probe.probe_ray_cap = plan.probe_ray_cap;
     probe.max_blocks_per_cu = plan.probe_max_blocks_per_cu;
     probe.tile_cost = plan.rank_tiles ? f.tile_cost : nullptr;
     probe.tile_order = nullptr;
@@ -546,7 +559,19 @@ static int enqueue_rehearsal(FilmImpl &f, const DeviceScene &ds, const rt_launch
         HIP_TRY(launch_tile_order(f.tile_cost, f.tile_order, f.n_tiles, (uint32_t)plan.tile_flatness_x8, stream));
         ra.tile_order = f.tile_order;
     }
-    HIP_TRY(hipMemsetAsync(f.ray_counter, 0, 2 * sizeof(unsigned long long), stream));  // rays, (light) queue cursor
+    if (keeps) {
+        // the rehearsed samples are the frame's, and so are their rays: only the (light) queue cursor starts again
+        HIP_TRY(hipMemsetAsync(f.ray_counter + 1, 0, sizeof(unsigned long long), stream));
+        ra.spp -= plan.probe_spp;
+        ra.spp_before += plan.probe_spp;
+        ra.resumed_spp = plan.probe_spp;
+        if (plan.probe_ray_cap > 0) {  // the pixels the cap stopped saved nothing: the refill tells them by their cost
+            ra.probe_ray_cap = plan.probe_ray_cap;
+            ra.pix_cost = f.pix_cost;
+        }
+    } else {
+        HIP_TRY(hipMemsetAsync(f.ray_counter, 0, 2 * sizeof(unsigned long long), stream));  // rays, (light) queue cursor
+    }
     if (!plan.pixel_classes) return RT_OK;
     const bool longest = plan.super_threshold > 0;
     HIP_TRY(hipMemsetAsync(f.heavy_count, 0, 64, stream));
@@ -639,6 +664,7 @@ int rt_render_launch(rt_scene *scene, rt_film *film, const rt_render_params *p)
         const std::string why = rt_last_error();
         hipStreamSynchronize(stream);  // whatever did get enqueued
         mark_done(f);
+        f.seeded = false;  // a rehearsal that ran has advanced the streams by part of a frame: the next launch seeds again
         set_error(why);
         return rc;
     }
@@ -757,6 +783,27 @@ int rt_film_download_sample_counts(rt_film *film, uint32_t *counts_full, int wid
     for (int j = 0; j < height; j++)
         if ((j / f.stripe_rows) % f.world_size == f.rank) {
             std::memcpy(counts_full + (size_t)j * width, compact.data() + lr * (size_t)width, sizeof(uint32_t) * (size_t)width);
+            lr++;
+        }
+    return RT_OK;
+}
+
+int rt_film_download_probe_costs(rt_film *film, uint32_t *costs_full, int width, int height)
+{
+    if (!film || !costs_full) return fail(RT_ERR_INVALID, "rt_film_download_probe_costs: null argument");
+    FilmImpl &f = *F(film);
+    if (width != f.width || height != f.height) return fail(RT_ERR_INVALID, "rt_film_download_probe_costs: frame size mismatch");
+    if (f.in_flight) return fail(RT_ERR_STATE, "rt_film_download_probe_costs: a render is in flight");
+    if (!f.rendered || !f.last_plan.pixel_classes || !f.pix_cost)
+        return fail(RT_ERR_STATE, "rt_film_download_probe_costs: the film's last launch classified no pixels");
+    if (int rc = select_device(f.device)) return rc;
+    std::vector<uint32_t> compact((size_t)f.n_pixels);
+    if (f.n_pixels) HIP_TRY(hipMemcpy(compact.data(), f.pix_cost, compact.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    std::memset(costs_full, 0, (size_t)width * (size_t)height * sizeof(uint32_t));
+    size_t lr = 0;
+    for (int j = 0; j < height; j++)
+        if ((j / f.stripe_rows) % f.world_size == f.rank) {
+            std::memcpy(costs_full + (size_t)j * width, compact.data() + lr * (size_t)width, sizeof(uint32_t) * (size_t)width);
             lr++;
         }
     return RT_OK;

@@ -1,6 +1,7 @@
 // launch_plan.cpp -- see launch_plan.h: the kernel choice, the LDS layout and the frame plan of a launch, host-only.
 #include "launch_plan.h"
 
+#include <cassert>
 #include <cmath>
 #include <cstring>
 
@@ -293,8 +294,8 @@ rt_launch_plan plan_frame(int kind, int lds_bytes, const FilmGeometry &film, int
     const bool bvh_kernel = is_bvh_kernel(kind);
     if (bvh_kernel && (p.coop_threshold <= 0 || !in_boxes)) plan.coop_threshold = 0;
     // A pixel's samples are one sequential chain (one RNG stream), so a frame cannot end before its longest pixel does
-    // (glass: up to max_depth rays per sample).  One rehearsal of the first samples of every pixel -- the same RNG streams,
-    // nothing written but ray counts, cost probe_spp / spp of the frame -- serves two schedulers:
+    // (glass: up to max_depth rays per sample).  One rehearsal of the first samples of every pixel, their rays counted, serves
+    // two schedulers (what becomes of the samples themselves: probe_keeps below):
     //  * BVH worlds, heaviest tiles first: the 8x8 tiles are ranked by rays traced and the pixel queue hands them out in
     //    that order (in row-major order C3's queue drained at 38 ms and the last wave left at 99 ms);
     //  * sphere-list and primitive-BVH worlds, heavy and light pixels: the few pixels with long chains (0.4 % of C2's
@@ -366,6 +367,12 @@ rt_launch_plan plan_frame(int kind, int lds_bytes, const FilmGeometry &film, int
         probe_spp = probe_spp < 1 ? 1 : (probe_spp > 8 ? 8 : probe_spp);
         if (probe_spp > spp) probe_spp = spp;
         plan.probe_spp = probe_spp;
+        // The rehearsal is the frame's first probe_spp samples: every pixel saves its stream and its colour sum where it finishes
+        // them, and the frame launch renders the spp - probe_spp that are left (C2: 8 of 500 sample passes were rendered twice).
+        // Not for adaptive films: the rule's sum of y^2 and its check points would have to run in the plain kernel that rehearses;
+        // their rehearsal writes nothing but ray counts and the frame launch starts every pixel at its first sample.
+        plan.probe_keeps = (kind & KIND_ADAPTIVE) ? 0 : 1;
+        assert(probe_spp < spp);  // ranking needs 32 samples, classes 64, at most 8 are rehearsed: the frame launch is never empty
     }
     // the order is kept row-major only where the heaviest tile is within an eighth of the mean (r3: was x4, which sorted for
     // glass only; C3 +1.7 % with every spread sorted, C2 / C5 indifferent between 9 / 8 and 32 / 8, one call)
@@ -408,6 +415,11 @@ rt_launch_plan plan_frame(int kind, int lds_bytes, const FilmGeometry &film, int
         // 154 -> 124, / 8: 155 -> 122).  A full frame packs the serving waves as densely as tuned: the ones left over join
         // the light queue at once (C3, 4.9 generations: 152 against 159 ms).
         plan.adaptive_ppw = few_generations ? 1 : 0;
+        // The rehearsal knows no classes yet: its launch ends on its longest pixels (glass: up to max_depth rays per sample, every
+        // one of them a pass of its wave), a handful the whole chip waits for -- and what it rehearses them for is decided at
+        // super_threshold rays.  There a pixel stops, in mid-sample; it keeps nothing, the frame launch renders all its samples
+        // (0.1-0.4 % of the pixels).  Tiles that hold such pixels book less than they cost: the ranking may move, the frame cannot.
+        plan.probe_ray_cap = plan.super_threshold;
     }
     return plan;
 }
@@ -453,7 +465,7 @@ rt_launch_plan plan_launch(const DeviceScene &sc, const FilmGeometry &film, int 
     plan.lds_nodes = layout.lds_nodes;
     plan.lds_spheres = layout.lds_spheres;
     show_layout(layout, plan);
-    o.adaptive = false;  // the rehearsal is the plain kernel's: it only counts rays
+    o.adaptive = false;  // the rehearsal is the plain kernel's (of an adaptive film it only counts rays: probe_keeps)
     plan.probe_kernel = choose_kernel(sc, o);
     return plan;
 }

@@ -3099,6 +3099,18 @@ __global__ __launch_bounds__(T::BLOCK, T::MIN_WAVES) void render_kernel(DeviceSc
     walk_best.obj = kNone;
     [[maybe_unused]] SegState seg{0u, kSegEnd, 0u};  // segmented walk: hi == kSegEnd also means "nothing more to walk" for an idle lane
 
+    // the rehearsal (RenderArgs::probe): a pixel's rays are booked where it ends, or where it reaches the ray cap
+    const uint32_t probe_cap = (!T::ADAPTIVE && a.probe && a.probe_ray_cap > 0) ? (uint32_t)a.probe_ray_cap : 0xFFFFFFFFu;  // (rehearsals run the plain kernels)
+    auto book_cost = [&](uint32_t rays) {
+        if constexpr (T::PARK) {  // the pixel's index and its tile come back from LDS
+            local = (size_t)park_get_int<T::BLOCK>(sc.lds_park, 2);
+            const uint32_t row = (uint32_t)local / (uint32_t)a.width, column = (uint32_t)local % (uint32_t)a.width;
+            my_tile = (row >> 3) * tiles_x + (column >> 3);
+        }
+        if (a.tile_cost) atomicAdd(a.tile_cost + my_tile, rays);
+        if (a.pix_cost) a.pix_cost[local] = rays;
+    };
+
 #if RT_PHASES
     PhaseSums ph{};
     const unsigned long long ph_start = __builtin_readcyclecounter();
@@ -3180,11 +3192,20 @@ __global__ __launch_bounds__(T::BLOCK, T::MIN_WAVES) void render_kernel(DeviceSc
                         rng.v3 = a.state[4 * (size_t)a.n_pixels + local];
                         rng.v4 = a.state[5 * (size_t)a.n_pixels + local];
                         col = mk(0.0, 0.0, 0.0);
-                        if (a.accum && a.spp_before > 0)  // progressive: continue the running sum in the same order
+                        sample = 0;
+                        int sum_spp = a.spp_before;  // samples in the pixel's running sum
+                        // behind a rehearsal that kept its samples: a pixel it stopped at the ray cap saved nothing, it starts from
+                        // its first sample (RenderArgs::resumed_spp)
+                        if constexpr (!T::ADAPTIVE) {  // (adaptive frames resume from nothing: launch_one)
+                            if (a.resumed_spp > 0 && a.probe_ray_cap > 0 && a.pix_cost[local] >= (uint32_t)a.probe_ray_cap) {
+                                sample = -a.resumed_spp;
+                                sum_spp -= a.resumed_spp;
+                            }
+                        }
+                        if (a.accum && sum_spp > 0)  // progressive: continue the running sum in the same order
                             col = mk(a.accum[local * 3 + 0], a.accum[local * 3 + 1], a.accum[local * 3 + 2]);
                         throughput = mk(1.0, 1.0, 1.0);
                         accumulated = mk(0.0, 0.0, 0.0);
-                        sample = 0;
                         depth = 0;
                         pix_rays = 0;
                         my_tile = tile;
@@ -3194,7 +3215,7 @@ __global__ __launch_bounds__(T::BLOCK, T::MIN_WAVES) void render_kernel(DeviceSc
                             park_put_int<T::BLOCK>(sc.lds_park, 0, (uint32_t)i);
                             park_put_int<T::BLOCK>(sc.lds_park, 1, (uint32_t)j);
                             park_put_int<T::BLOCK>(sc.lds_park, 2, (uint32_t)local);
-                            park_put_int<T::BLOCK>(sc.lds_park, 3, 0u);
+                            park_put_int<T::BLOCK>(sc.lds_park, 3, (uint32_t)sample);
                             park_put_int<T::BLOCK>(sc.lds_park, 4, 0u);
                             park_put_vec<T::BLOCK>(sc.lds_park, 0, col);
                             park_put_vec<T::BLOCK>(sc.lds_park, 3, throughput);
@@ -3429,7 +3450,24 @@ __global__ __launch_bounds__(T::BLOCK, T::MIN_WAVES) void render_kernel(DeviceSc
         }
         if (a.max_depth > 0) wave_rays += (uint32_t)__popcll(todo);
         [[maybe_unused]] bool sample_ends = false;
-        if ((todo >> lane) & 1ull) {
+        bool mine = (todo >> lane) & 1ull;
+        if (probe_cap != 0xFFFFFFFFu && a.max_depth > 0) {
+            // The rehearsal stops at the decision: with this ray the pixel's count reaches the cap (RenderArgs::probe_ray_cap) -- it is
+            // listed among the longest chains whatever it traces from here on, and those are what the launch would end on.  The lane
+            // books the count and goes idle in mid-sample; nothing of the pixel is saved, and the rays it has counted leave the
+            // wave's sum again (the frame launch traces them once more).
+            uint32_t rays = pix_rays + 1u;
+            if constexpr (T::PARK) rays = park_get_int<T::BLOCK>(sc.lds_park, 4) + 1u;
+            const bool capped = mine && rays >= probe_cap;
+            if (capped) {
+                book_cost(rays);
+                active = false;
+                mine = false;
+                if constexpr (T::SEG) seg.hi = kSegEnd;  // no pixel: nothing between walks either
+            }
+            wave_rays -= probe_cap * (uint32_t)__popcll(__ballot(capped));
+        }
+        if (mine) {
             const bool no_bounces = a.max_depth <= 0;  // R/kernel.cu:71: the bounce loop never runs, RayColor returns black
             if (!no_bounces) {
                 if constexpr (T::PARK) {
@@ -3505,15 +3543,21 @@ __global__ __launch_bounds__(T::BLOCK, T::MIN_WAVES) void render_kernel(DeviceSc
                     accumulated = mk(0.0, 0.0, 0.0);
                     depth = 0;
                 } else if (a.probe) {
-                    // cost probe: the samples were a rehearsal (the saved RNG state is untouched); book the rays
-                    if constexpr (T::PARK) {
-                        local = (size_t)park_get_int<T::BLOCK>(sc.lds_park, 2);
-                        pix_rays = park_get_int<T::BLOCK>(sc.lds_park, 4);
-                        const uint32_t row = (uint32_t)local / (uint32_t)a.width, column = (uint32_t)local % (uint32_t)a.width;
-                        my_tile = (row >> 3) * tiles_x + (column >> 3);
+                    // the rehearsal: book the rays; where the frame launch resumes from it (RenderArgs::probe == 2), the pixel's stream
+                    // and its sum so far are saved as a frame saves them, and no pixel is written
+                    if constexpr (T::PARK) pix_rays = park_get_int<T::BLOCK>(sc.lds_park, 4);
+                    book_cost(pix_rays);
+                    if (a.probe == 2) {
+                        a.state[0 * (size_t)a.n_pixels + local] = rng.d;
+                        a.state[1 * (size_t)a.n_pixels + local] = rng.v0;
+                        a.state[2 * (size_t)a.n_pixels + local] = rng.v1;
+                        a.state[3 * (size_t)a.n_pixels + local] = rng.v2;
+                        a.state[4 * (size_t)a.n_pixels + local] = rng.v3;
+                        a.state[5 * (size_t)a.n_pixels + local] = rng.v4;
+                        a.accum[local * 3 + 0] = col.x;
+                        a.accum[local * 3 + 1] = col.y;
+                        a.accum[local * 3 + 2] = col.z;
                     }
-                    if (a.tile_cost) atomicAdd(a.tile_cost + my_tile, pix_rays);
-                    if (a.pix_cost) a.pix_cost[local] = pix_rays;
                     active = false;
                 } else {
                     // R/kernel.cu:146-153: save the RNG state, average, gamma 2
@@ -3762,6 +3806,8 @@ hipError_t launch_one(const DeviceScene &sc_in, RenderArgs a, hipStream_t stream
 {
     if (!T::ROLES && a.heavy_list) return hipErrorInvalidValue;  // this instantiation has no serving waves (Traits::ROLES): its listed pixels would never be rendered
     if (T::ADAPTIVE != (a.adaptive != 0) || (T::ADAPTIVE && (a.probe || !a.ad_n || !a.ad_q || !a.ad_mark))) return hipErrorInvalidValue;  // rehearsals run the plain kernels
+    // a rehearsal that keeps its samples needs the sum plane; a frame launch behind a capped one, the costs the cap left
+    if ((a.probe == 2 && !a.accum) || (a.resumed_spp > 0 && (T::ADAPTIVE || a.probe || !a.accum || (a.probe_ray_cap > 0 && !a.pix_cost)))) return hipErrorInvalidValue;
     auto kernel = render_kernel<RT_STRICT, T>;
     uint32_t tiles = (((uint32_t)a.width + 7u) >> 3) * (((uint32_t)a.rows_owned + 7u) >> 3);
     constexpr KernelProps props = props_of<T>();

@@ -30,12 +30,21 @@ struct RenderArgs {
     uint32_t *cursor;            // pixel-queue cursor, zeroed before every launch
     uint32_t *tile_cost;        // probe launches: rays traced per 8x8 tile (one counter per tile of this rank's rows)
     const uint32_t *tile_order; // render launches: queue position -> tile (nullptr = tiles in row-major order)
-    int32_t probe;              // 1 = cost probe: trace `spp` samples per pixel, write nothing but tile_cost / pix_cost
+    // The rehearsal (launch_plan.cpp plan_frame): the first `spp` samples of every pixel, their rays booked in tile_cost / pix_cost.
+    // 1 = it writes nothing else (adaptive films: the frame launch renders every sample again); 2 = it keeps them: a pixel that
+    // finishes saves its RNG words to `state` and its colour sum to `accum` (never `pixels`), and the frame launch resumes there.
+    int32_t probe;
+    // probe launches: a pixel whose rays reach this many books them and stops at once, in mid-sample, saving nothing (0 = no cap;
+    // the pixel is on the longest-chain list whatever else it would have traced).  Its rays leave ray_counter again.
+    int32_t probe_ray_cap;
+    // frame launches behind a rehearsal that kept its samples: `spp` and `spp_before` are already moved by this many samples, and
+    // a pixel whose pix_cost reached probe_ray_cap (it saved nothing) starts this many samples earlier, from its state as seeded
+    int32_t resumed_spp;
     // Two classes of pixels (launch_plan.cpp plan_frame, device_scene.cpp enqueue_rehearsal): the probe books every pixel's rays in pix_cost;
     // classify_pixels marks the heavy ones in pix_class and lists them.  The render launch then serves both: the first
     // `heavy_waves` waves of every workgroup serve heavy_list (heavy_ppw pixels at a time, through heavy_cursor) and join
     // the tile queue when the list is done; the tile queue skips the pixels whose class is non-zero.
-    uint32_t *pix_cost;               // probe launches: rays traced by each owned pixel
+    uint32_t *pix_cost;               // probe launches: rays traced by each owned pixel (frame launches read it where resumed_spp and probe_ray_cap are set)
     const uint8_t *pix_class;         // tile queue: pixels whose class is non-zero are served from heavy_list / super_list
     const uint32_t *heavy_list;
     const uint32_t *heavy_count;
