@@ -401,6 +401,75 @@ RTOW_API int rt_film_download_denoised(rt_film *film, double *frame_full, int wi
 RTOW_API int rt_denoise_frame(int device, const double *color, const double *albedo, const double *normal, const double *depth,
                               int width, int height, const rt_denoise_params *params, double *out);
 
+/* ---- ray queries: closest hit and occlusion for caller-supplied rays ----
+ * Ray k is origin[3k..3k+2] + t * direction[3k..3k+2] (the direction need not be a unit vector: t is the ray parameter) at time
+ * time[k], searched over the reference's interval of Hittable::Hit: tmin < t < tmax for spheres, tmin <= t <= tmax for quads
+ * (R/Sphere.h:38,50, R/Quad.h:59-64).  A per-ray array that is NULL takes the scalar of rt_query_params for every ray.
+ *   mode 0, closest hit: the reference's world->Hit(ray, tmin, tmax, rec, &stream).  The reference's own tree or list is visited in
+ *     the reference's order, through the leaf tests and the hit record of the render kernels -- what the general kernels do under
+ *     RT_FLAG_REFERENCE_TREE | RT_FLAG_FORCE_GENERAL -- so the reference's tie rules hold (RT_FLAG_REFERENCE_TREE) and a
+ *     ConstantMedium draws from the ray's stream, curand_init(seed, k + first_sequence, 0); nothing else draws.  The library's own
+ *     tree is never used: it is valid only while every hit stays inside its leaf's box, which depends on the shutter (flat_scene.h
+ *     FastNodeRec), and a caller's times are arbitrary.
+ *   mode 1, occlusion: occluded[k] = 1 exactly where the closest-hit query of ray k with the same parameters reports a hit.  In a
+ *     world without ConstantMedium leaves the search stops at the first accepted hit; with media it is the full search (what a
+ *     medium answers depends on what was found before it).  Only `occluded` is written.
+ * What a closest-hit query writes, each output only where its pointer is not NULL (an output left NULL costs no texture or
+ * material work):
+ *   t           the ray parameter of the hit, +inf for a miss
+ *   normal      the unit shading normal, faced against the ray, in world space; (0, 0, 0) for a medium hit and for a miss
+ *   uv          HitRecord U, V of the primitive that was hit; (0, 0) for a medium hit and for a miss
+ *   albedo      the table of rt_film_render_features above, the camera's background for a miss included
+ *   leaf        the position, in rt_scene_dump_leaves order, of the world leaf whose test produced the winning record; -1: miss
+ *   front_face  HitRecord FrontFace (1 for a medium hit, 0 for a miss)
+ *   material    0 Lambertian, 1 metal, 2 dielectric, 3 diffuse light, 4 isotropic; 255 for a miss
+ *   occluded    1 for a hit, 0 for a miss
+ * Both calls return when the results are there (they wait on the stream), so no query outlives a destroy or a re-commit of the
+ * scene; a query reads and writes no film.  Parameters are checked before the device is touched: RT_ERR_STATE before commit;
+ * RT_ERR_INVALID for a count below 0 or above 2^30, a NULL origin or direction with count > 0, a mode or variant other than 0 / 1,
+ * a tmin that is NaN, tmax < tmin (or NaN).  count == 0 returns RT_OK without a launch.  A ray with a zero or non-finite direction
+ * terminates (every walk is a bounded loop); its result is unspecified. */
+typedef struct rt_query_params {
+    int64_t  count;            /* rays; 0 is allowed (no launch), > 2^30 is RT_ERR_INVALID */
+    double   tmin, tmax;       /* used where the per-ray arrays are NULL; tmax = +inf means DBL_MAX, what a render passes */
+    double   time;             /* used where times is NULL */
+    uint64_t seed;             /* ray k draws from curand_init(seed, k + first_sequence, 0): only media draw */
+    uint64_t first_sequence;
+    int32_t  mode;             /* 0 closest hit, 1 occlusion */
+    int32_t  variant;          /* 0 strict, 1 fast, as for renders */
+    int32_t  device;
+    void    *stream;           /* NULL = the default stream */
+    int32_t  reserved[4];
+} rt_query_params;
+typedef struct rt_query_rays {
+    const double *origin, *direction;   /* count x 3 each */
+    const double *time, *tmin, *tmax;   /* count each, any may be NULL */
+} rt_query_rays;
+typedef struct rt_query_hits {
+    double *t;             /* count */
+    double *normal;        /* count x 3 */
+    double *uv;            /* count x 2 */
+    double *albedo;        /* count x 3 */
+    int32_t *leaf;         /* count */
+    uint8_t *front_face;   /* count */
+    uint8_t *material;     /* count */
+    uint8_t *occluded;     /* count; any pointer may be NULL */
+} rt_query_hits;
+typedef struct rt_query_stats {
+    uint64_t rays, hits;
+    double seconds;               /* the query kernel, HIP events */
+    uint32_t kernel_vgprs, scratch_bytes;   /* of the instantiation that ran: registers, private memory per lane */
+} rt_query_stats;
+/* rays and hits hold device pointers (on params->device).  stats may be NULL: the call is then the launch and the wait alone (no
+ * events, no count of the rays that hit).  A scene is thread-compatible, as everywhere in this header: one call at a time. */
+RTOW_API int rt_scene_intersect_device(rt_scene *s, const rt_query_params *params, const rt_query_rays *rays, const rt_query_hits *hits,
+                                       rt_query_stats *stats);
+/* the same on host arrays (uploaded, queried, copied back) */
+RTOW_API int rt_scene_intersect(rt_scene *s, const rt_query_params *params, const rt_query_rays *rays, const rt_query_hits *hits,
+                                rt_query_stats *stats);
+/* sizeof of rt_query_params, rt_query_rays, rt_query_hits, rt_query_stats as this library was compiled (bindings check theirs) */
+RTOW_API void rt_query_abi_sizes(uint32_t out4[4]);
+
 /* Convenience: create film, upload, render 1 GPU, download.  frame = W*H*3 doubles. */
 RTOW_API int rt_render(rt_scene *s, const rt_render_params *params, double *frame, rt_render_stats *stats);
 

@@ -7,6 +7,7 @@
 // to delete, sharing a child between two parents is fine (the reference double-frees there,
 // Docs 2-10 :202-213).
 #pragma once
+#include <limits>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -124,6 +125,57 @@ public:
         check(rt_scene_set_camera(s_, f, a, u, vfov, aspect, aperture, focusDist, time0, time1, bg));
     }
     void Commit() { check(rt_scene_commit(s_)); }
+
+    // Ray queries on host arrays (rtow.h "ray queries"): origins and directions hold 3 doubles per ray; an output vector is
+    // filled only where `want` names it ("t normal uv albedo leaf front_face material", any subset, space separated).
+    struct Hits {
+        std::vector<double> t, normal, uv, albedo;
+        std::vector<int32_t> leaf;
+        std::vector<uint8_t> front_face, material;
+    };
+    Hits Intersect(const std::vector<double> &origins, const std::vector<double> &directions, rt_query_params params = DefaultQuery(),
+                   const std::string &want = "t normal uv albedo leaf front_face material", const double *times = nullptr)
+    {
+        if (origins.size() != directions.size() || origins.size() % 3 != 0) throw Error("Intersect: origins and directions must hold 3 doubles per ray");
+        const size_t n = origins.size() / 3;
+        Hits out;
+        auto wanted = [&](const char *name) { return (" " + want + " ").find(std::string(" ") + name + " ") != std::string::npos; };
+        if (wanted("t")) out.t.resize(n);
+        if (wanted("normal")) out.normal.resize(3 * n);
+        if (wanted("uv")) out.uv.resize(2 * n);
+        if (wanted("albedo")) out.albedo.resize(3 * n);
+        if (wanted("leaf")) out.leaf.resize(n);
+        if (wanted("front_face")) out.front_face.resize(n);
+        if (wanted("material")) out.material.resize(n);
+        params.count = (int64_t)n;
+        params.mode = 0;
+        auto ptr = [](auto &v) { return v.empty() ? nullptr : v.data(); };
+        const rt_query_rays rays{origins.data(), directions.data(), times, nullptr, nullptr};
+        const rt_query_hits hits{ptr(out.t), ptr(out.normal), ptr(out.uv), ptr(out.albedo), ptr(out.leaf), ptr(out.front_face), ptr(out.material), nullptr};
+        check(rt_scene_intersect(s_, &params, &rays, &hits, nullptr));
+        return out;
+    }
+    std::vector<uint8_t> Occluded(const std::vector<double> &origins, const std::vector<double> &directions, rt_query_params params = DefaultQuery(),
+                                  const double *times = nullptr)
+    {
+        if (origins.size() != directions.size() || origins.size() % 3 != 0) throw Error("Occluded: origins and directions must hold 3 doubles per ray");
+        std::vector<uint8_t> out(origins.size() / 3);
+        params.count = (int64_t)out.size();
+        params.mode = 1;
+        const rt_query_rays rays{origins.data(), directions.data(), times, nullptr, nullptr};
+        const rt_query_hits hits{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, out.data()};
+        check(rt_scene_intersect(s_, &params, &rays, &hits, nullptr));
+        return out;
+    }
+    // what a render passes: [0.001, inf), time 0, seed 1984, the strict build, device 0
+    static rt_query_params DefaultQuery()
+    {
+        rt_query_params p{};
+        p.tmin = 0.001;
+        p.tmax = std::numeric_limits<double>::infinity();
+        p.seed = 1984;
+        return p;
+    }
 
 private:
     rt_handle ok(rt_handle h)

@@ -39,6 +39,30 @@ class DenoiseParams(C.Structure):
                 ("sigma_depth", C.c_double)]
 
 
+class QueryParams(C.Structure):
+    _fields_ = [("count", C.c_int64), ("tmin", C.c_double), ("tmax", C.c_double), ("time", C.c_double), ("seed", C.c_uint64),
+                ("first_sequence", C.c_uint64), ("mode", C.c_int32), ("variant", C.c_int32), ("device", C.c_int32),
+                ("stream", C.c_void_p), ("reserved", C.c_int32 * 4)]
+
+
+class QueryRays(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("origin", "direction", "time", "tmin", "tmax")]
+
+
+# the outputs of a closest-hit query in the order of rt_query_hits: name -> (numpy dtype, trailing shape)
+QUERY_OUTPUTS = {"t": ("float64", ()), "normal": ("float64", (3,)), "uv": ("float64", (2,)), "albedo": ("float64", (3,)),
+                 "leaf": ("int32", ()), "front_face": ("uint8", ()), "material": ("uint8", ()), "occluded": ("uint8", ())}
+
+
+class QueryHits(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in QUERY_OUTPUTS]
+
+
+class QueryStats(C.Structure):
+    _fields_ = [("rays", C.c_uint64), ("hits", C.c_uint64), ("seconds", C.c_double), ("kernel_vgprs", C.c_uint32),
+                ("scratch_bytes", C.c_uint32)]
+
+
 class LaunchPlan(C.Structure):
     """rt_launch_plan: what a launch decides (csrc/launch_plan.h); every scalar field but ray_budget is an int32."""
     _fields_ = [(n, C.c_uint32 if n == "ray_budget" else C.c_int32) for n in (
@@ -141,6 +165,9 @@ SIGNATURES = {
     "rt_film_denoise": (I, [P, C.POINTER(DenoiseParams)]),
     "rt_film_download_denoised": (I, [P, D3, I, I]),
     "rt_denoise_frame": (I, [I, D3, D3, D3, D3, I, I, C.POINTER(DenoiseParams), D3]),
+    "rt_scene_intersect_device": (I, [P, C.POINTER(QueryParams), C.POINTER(QueryRays), C.POINTER(QueryHits), C.POINTER(QueryStats)]),
+    "rt_scene_intersect": (I, [P, C.POINTER(QueryParams), C.POINTER(QueryRays), C.POINTER(QueryHits), C.POINTER(QueryStats)]),
+    "rt_query_abi_sizes": (None, [C.POINTER(C.c_uint32)]),
     "rt_deinterleave": (I, [D3, I, I, I, I, C.c_size_t, D3]),
     "rt_render": (I, [P, C.POINTER(RenderParams), D3, C.POINTER(RenderStats)]),
     "rt_write_ppm": (I, [C.c_char_p, D3, I, I]),

@@ -7,11 +7,13 @@ so on; ``Film.render`` is the RenderInit + Render launch pair (R/kernel.cu:675-6
 writer at R/kernel.cu:696-721.  Errors surface as RtowError carrying the library's message.
 """
 import ctypes as C
+import numbers
 
 import numpy as np
 
 from . import _lib
-from ._lib import AdaptiveParams, DenoiseParams, FeatureParams, LaunchPlan, RenderParams, RenderStats, SceneInfo  # noqa: F401
+from ._lib import (AdaptiveParams, DenoiseParams, FeatureParams, LaunchPlan, QueryHits, QueryParams, QueryRays, QueryStats,  # noqa: F401
+                   RenderParams, RenderStats, SceneInfo)
 
 
 class RtowError(RuntimeError):
@@ -260,6 +262,88 @@ class Scene:
 
     def upload(self, device=0):
         _check(lib().rt_scene_upload(self._p, device))
+
+    # ---- ray queries (include/rtow.h rt_scene_intersect) ----
+    def _query(self, mode, want, origins, directions, times, tmin, tmax, time, seed, first_sequence, variant, device, stats):
+        on_gpu = type(origins).__module__.split(".")[0] == "torch"
+        if on_gpu:
+            import torch
+
+        def ray_array(name, a, tail):
+            """A caller's array as the library reads it: float64, C-contiguous, (count,) + tail.  Nothing is converted or copied."""
+            if on_gpu:
+                if not isinstance(a, torch.Tensor) or not a.is_cuda or a.device != origins.device:
+                    raise RtowError(f"{name}: a CUDA tensor on the device of the origins is required")
+                if a.dtype != torch.float64 or not a.is_contiguous():
+                    raise RtowError(f"{name}: a contiguous float64 tensor is required (got {a.dtype}, contiguous={a.is_contiguous()})")
+            else:
+                if not isinstance(a, np.ndarray) or a.dtype != np.float64 or not a.flags.c_contiguous:
+                    raise RtowError(f"{name}: a C-contiguous float64 numpy array is required")
+            if a.ndim != 1 + len(tail) or tuple(a.shape[1:]) != tail:
+                raise RtowError(f"{name}: shape (count,{' 3' if tail else ''}) is required, got {tuple(a.shape)}")
+            return a
+
+        if on_gpu and not (isinstance(origins, torch.Tensor) and origins.is_cuda):
+            raise RtowError("origins: torch tensors must live on the GPU (numpy arrays take the host call)")
+        origins = ray_array("origins", origins, (3,))
+        count = int(origins.shape[0])
+        per_ray = {"directions": (directions, (3,)), "times": (times, ()), "tmin": (tmin, ()), "tmax": (tmax, ())}
+        arrays = {}
+        for name, (a, tail) in per_ray.items():
+            if name != "directions" and (a is None or isinstance(a, numbers.Real) or (isinstance(a, np.ndarray) and a.ndim == 0)):
+                continue   # one value for all rays (a Python or numpy scalar): float() below
+            arrays[name] = ray_array(name, a, tail)
+            if int(arrays[name].shape[0]) != count:
+                raise RtowError(f"{name}: {int(arrays[name].shape[0])} entries for {count} rays")
+        unknown = [w for w in want if w not in _lib.QUERY_OUTPUTS]
+        if unknown:
+            raise RtowError(f"unknown query output {unknown[0]!r} (one of {', '.join(_lib.QUERY_OUTPUTS)})")
+
+        def address(a):
+            return a.data_ptr() if on_gpu else a.ctypes.data
+
+        out = {}
+        for name in want:
+            dtype, tail = _lib.QUERY_OUTPUTS[name]
+            shape = (max(count, 1),) + tail   # (never an empty allocation: its address may be null)
+            if on_gpu:
+                out[name] = torch.empty(shape, dtype=getattr(torch, dtype), device=origins.device)
+            else:
+                out[name] = np.empty(shape, dtype=dtype)
+        stream = None
+        if on_gpu:
+            device = origins.device.index if origins.device.index is not None else torch.cuda.current_device()
+            stream = torch.cuda.current_stream(origins.device).cuda_stream or None
+        p = QueryParams(count, float(tmin) if "tmin" not in arrays else 0.0, float(tmax) if "tmax" not in arrays else 0.0,
+                        float(time), int(seed), int(first_sequence), mode, int(variant), int(device), stream)
+        rays = QueryRays(address(origins), address(arrays["directions"]), *(address(arrays[n]) if n in arrays else None
+                                                                           for n in ("times", "tmin", "tmax")))
+        hits = QueryHits(**{name: address(a) for name, a in out.items()})
+        st = QueryStats() if stats else None
+        call = lib().rt_scene_intersect_device if on_gpu else lib().rt_scene_intersect
+        _check(call(self._p, C.byref(p), C.byref(rays), C.byref(hits), C.byref(st) if stats else None))
+        return {name: a[:count] for name, a in out.items()}, st
+
+    def intersect(self, origins, directions, times=None, tmin=0.001, tmax=float("inf"), time=0.0, seed=1984, first_sequence=0,
+                  variant=0, want=("t", "normal", "uv", "albedo", "leaf", "front_face", "material"), device=0, stats=False):
+        """The closest hit of every ray ``origins[k] + t * directions[k]`` (both (count, 3) float64) over (tmin, tmax): the
+        reference's ``world->Hit``, its own tree or list in its own order (include/rtow.h rt_scene_intersect has the rules and what
+        each output holds).  ``times``, ``tmin`` and ``tmax`` may each be a (count,) array or one value for all rays.  Returns a
+        dict of the outputs named in ``want``; an output that is not asked for costs no work.  numpy arrays take the host call
+        and come back as numpy arrays; torch CUDA tensors are read in place, on ``torch.cuda.current_stream()``, and come back as
+        tensors on the same device.  Other dtypes and non-contiguous inputs raise RtowError: nothing is converted silently.
+        Only a ConstantMedium draws random numbers: ray k from ``curand_init(seed, k + first_sequence, 0)``.  ``stats=True``:
+        (outputs, QueryStats)."""
+        out, st = self._query(0, tuple(want), origins, directions, times, tmin, tmax, time, seed, first_sequence, variant, device, stats)
+        return (out, st) if stats else out
+
+    def occluded(self, origins, directions, times=None, tmin=0.001, tmax=float("inf"), time=0.0, seed=1984, first_sequence=0,
+                 variant=0, device=0, stats=False):
+        """(count,) bool: does ray k hit anything over (tmin, tmax)?  Exactly ``isfinite(intersect(...)["t"])``; a world without
+        media stops at the first accepted hit.  Arguments as for ``intersect``."""
+        out, st = self._query(1, ("occluded",), origins, directions, times, tmin, tmax, time, seed, first_sequence, variant, device, stats)
+        hit = out["occluded"] != 0
+        return (hit, st) if stats else hit
 
     # ---- one-call render on one GPU ----
     def render(self, width, height, spp, max_depth=50, seed=1984, variant=0, device=0, flags=0, coop_threshold=0,

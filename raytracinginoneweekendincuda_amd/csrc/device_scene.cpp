@@ -35,6 +35,7 @@ struct DeviceTables {
     uint64_t generation = 0;  // SceneImpl::generation these tables were made from
     std::vector<void *> allocations;
     DeviceScene scene{};
+    const uint32_t *node_leaf_pos = nullptr;  // ray queries (rt_scene_intersect_device): FlatScene::node_leaf_pos
 };
 
 void release_device_tables(DeviceTables *t)
@@ -289,6 +290,7 @@ int rt_scene_upload(rt_scene *scene, int device)
     }
     up(f.seg_cand, d.seg_cand);
     up(f.world_items, d.world_items);
+    up(f.node_leaf_pos, dt->node_leaf_pos);
     up(f.materials, d.materials);
     up(f.textures, d.textures);
     up(f.images, d.images);
@@ -1017,6 +1019,140 @@ int rt_denoise_frame(int device, const double *color, const double *albedo, cons
         if (d) hipFree(d);
     if (rc != RT_OK) return rc;
     return e == hipSuccess ? RT_OK : hip_fail(e, "rt_denoise_frame");
+}
+
+// ---- ray queries ----
+// everything that can be refused without a device, in the order include/rtow.h lists it
+static int query_check(rt_scene *scene, const rt_query_params *p, const rt_query_rays *rays, const rt_query_hits *hits, const char *who)
+{
+    const std::string name(who);
+    if (!scene || !p || !rays || !hits) return fail(RT_ERR_INVALID, name + ": null argument");
+    if (!S(scene)->committed) return fail(RT_ERR_STATE, name + ": scene not committed (rt_scene_commit)");
+    if (p->count < 0 || p->count > ((int64_t)1 << 30)) return fail(RT_ERR_INVALID, name + ": count must be 0 .. 2^30");
+    if (p->mode != 0 && p->mode != 1) return fail(RT_ERR_INVALID, name + ": mode must be 0 (closest hit) or 1 (occlusion)");
+    if (p->variant != 0 && p->variant != 1) return fail(RT_ERR_INVALID, name + ": variant must be 0 (strict) or 1 (fast)");
+    if (p->count > 0 && (!rays->origin || !rays->direction)) return fail(RT_ERR_INVALID, name + ": null origin or direction");
+    if (!rays->tmin && std::isnan(p->tmin)) return fail(RT_ERR_INVALID, name + ": tmin is NaN");
+    if (!rays->tmax && !(p->tmax >= (rays->tmin ? p->tmax : p->tmin))) return fail(RT_ERR_INVALID, name + ": tmax < tmin (or NaN)");
+    return RT_OK;
+}
+
+int rt_scene_intersect_device(rt_scene *scene, const rt_query_params *p, const rt_query_rays *rays, const rt_query_hits *hits,
+                              rt_query_stats *stats)
+{
+    if (int rc = query_check(scene, p, rays, hits, "rt_scene_intersect_device")) return rc;
+    if (stats) *stats = rt_query_stats{};
+    if (p->count == 0) return RT_OK;
+    SceneImpl &s = *S(scene);
+    if (int rc = rt_scene_upload(scene, p->device)) return rc;  // (selects the device)
+    DeviceTables &dt = *s.device[p->device];
+    QueryArgs qa{};
+    qa.origin = rays->origin;
+    qa.direction = rays->direction;
+    qa.time = rays->time;
+    qa.tmin = rays->tmin;
+    qa.tmax = rays->tmax;
+    qa.time_all = p->time;
+    qa.tmin_all = p->tmin;
+    qa.tmax_all = p->tmax;
+    qa.occluded = hits->occluded;
+    if (p->mode == 0) {  // an occlusion query writes nothing else
+        qa.t = hits->t;
+        qa.normal = hits->normal;
+        qa.uv = hits->uv;
+        qa.albedo = hits->albedo;
+        qa.leaf = hits->leaf;
+        qa.front_face = hits->front_face;
+        qa.material = hits->material;
+    }
+    qa.node_leaf_pos = dt.node_leaf_pos;
+    if (int rc = device_jump_table(p->device, &qa.jump_table)) return rc;
+    qa.base = xorwow_seed(p->seed, kSaltCurandDevice);
+    qa.first_sequence = p->first_sequence;
+    qa.count = (uint32_t)p->count;
+    qa.mode = p->mode;
+    hipStream_t stream = (hipStream_t)p->stream;
+    auto launch = p->variant == 0 ? launch_query_strict : launch_query_fast;
+    if (!stats) {  // nothing to report: the launch and the wait
+        hipError_t e = launch(dt.scene, qa, stream, nullptr);
+        // the kernel reads the scene's tables and the caller's arrays: done before either may change
+        const hipError_t waited = hipStreamSynchronize(stream);
+        if (e == hipSuccess) e = waited;
+        return e == hipSuccess ? RT_OK : hip_fail(e, "rt_scene_intersect_device");
+    }
+    // with statistics: the kernel's registers, two events around it, and a word of this call's own for the rays that hit (queries
+    // of one scene may run on several streams at once)
+    QueryKernelInfo info{};
+    HIP_TRY(launch(dt.scene, qa, stream, &info));
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    unsigned long long found = 0;
+    hipError_t e = hipMalloc((void **)&qa.hit_counter, sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipEventCreate(&ev[0]);
+    if (e == hipSuccess) e = hipEventCreate(&ev[1]);
+    if (e == hipSuccess) e = hipMemsetAsync(qa.hit_counter, 0, sizeof(unsigned long long), stream);
+    if (e == hipSuccess) e = hipEventRecord(ev[0], stream);
+    if (e == hipSuccess) e = launch(dt.scene, qa, stream, nullptr);
+    if (e == hipSuccess) e = hipEventRecord(ev[1], stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(&found, qa.hit_counter, sizeof found, hipMemcpyDeviceToHost, stream);
+    const hipError_t waited = hipStreamSynchronize(stream);
+    if (e == hipSuccess) e = waited;
+    float ms = 0.0f;
+    if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev[0], ev[1]);
+    for (hipEvent_t v : ev)
+        if (v) hipEventDestroy(v);
+    if (qa.hit_counter) hipFree(qa.hit_counter);
+    if (e != hipSuccess) return hip_fail(e, "rt_scene_intersect_device");
+    stats->rays = (uint64_t)p->count;
+    stats->hits = found;
+    stats->seconds = (double)ms * 1e-3;
+    stats->kernel_vgprs = (uint32_t)info.vgprs;
+    stats->scratch_bytes = (uint32_t)info.scratch_bytes;
+    return RT_OK;
+}
+
+int rt_scene_intersect(rt_scene *scene, const rt_query_params *p, const rt_query_rays *rays, const rt_query_hits *hits, rt_query_stats *stats)
+{
+    if (int rc = query_check(scene, p, rays, hits, "rt_scene_intersect")) return rc;
+    if (stats) *stats = rt_query_stats{};
+    if (p->count == 0) return RT_OK;
+    if (int rc = select_device(p->device)) return rc;
+    const size_t n = (size_t)p->count;
+    // inputs 0..4 (origin, direction, time, tmin, tmax), outputs 5..12 in the order of rt_query_hits
+    const void *host_in[5] = {rays->origin, rays->direction, rays->time, rays->tmin, rays->tmax};
+    void *host_out[8] = {hits->t, hits->normal, hits->uv, hits->albedo, hits->leaf, hits->front_face, hits->material, hits->occluded};
+    const size_t bytes[13] = {n * 3 * sizeof(double), n * 3 * sizeof(double), n * sizeof(double), n * sizeof(double), n * sizeof(double),
+                              n * sizeof(double), n * 3 * sizeof(double), n * 2 * sizeof(double), n * 3 * sizeof(double), n * sizeof(int32_t),
+                              n, n, n};
+    void *dev[13] = {};
+    hipError_t e = hipSuccess;
+    for (int k = 0; k < 13 && e == hipSuccess; k++) {
+        if (k < 5 ? !host_in[k] : (!host_out[k - 5] || (p->mode == 1 && k != 12))) continue;
+        e = hipMalloc(&dev[k], bytes[k]);
+        if (e == hipSuccess && k < 5) e = hipMemcpy(dev[k], host_in[k], bytes[k], hipMemcpyHostToDevice);
+    }
+    int rc = RT_OK;
+    if (e == hipSuccess) {
+        const rt_query_rays dr{(const double *)dev[0], (const double *)dev[1], (const double *)dev[2], (const double *)dev[3], (const double *)dev[4]};
+        const rt_query_hits dh{(double *)dev[5], (double *)dev[6], (double *)dev[7], (double *)dev[8], (int32_t *)dev[9],
+                               (uint8_t *)dev[10], (uint8_t *)dev[11], (uint8_t *)dev[12]};
+        rt_query_params dp = *p;
+        dp.stream = nullptr;  // the copies around the query are synchronous: nothing to order on the caller's stream
+        rc = rt_scene_intersect_device(scene, &dp, &dr, &dh, stats);
+    }
+    for (int k = 5; k < 13 && e == hipSuccess && rc == RT_OK; k++)
+        if (dev[k]) e = hipMemcpy(host_out[k - 5], dev[k], bytes[k], hipMemcpyDeviceToHost);
+    for (void *d : dev)
+        if (d) hipFree(d);
+    if (rc != RT_OK) return rc;
+    return e == hipSuccess ? RT_OK : hip_fail(e, "rt_scene_intersect");
+}
+
+void rt_query_abi_sizes(uint32_t out4[4])
+{
+    out4[0] = (uint32_t)sizeof(rt_query_params);
+    out4[1] = (uint32_t)sizeof(rt_query_rays);
+    out4[2] = (uint32_t)sizeof(rt_query_hits);
+    out4[3] = (uint32_t)sizeof(rt_query_stats);
 }
 
 int rt_render(rt_scene *scene, const rt_render_params *params, double *frame, rt_render_stats *stats)

@@ -216,6 +216,8 @@ int main(int argc, char **argv)
     int feature_samples = 0;
     bool feature_samples_given = false;
     std::string raw_output, aov_prefix;
+    bool pick = false;           // --pick i,j: what the centre ray of that pixel hits, one line, no render
+    int pick_i = 0, pick_j = 0;
     for (int k = 1; k < argc; k++) {
         std::string a = argv[k];
         auto val = [&](const char *name) -> const char * {
@@ -270,6 +272,13 @@ int main(int argc, char **argv)
             feature_samples = std::atoi(v);
             feature_samples_given = true;
         } else if (const char *v = val("--aov-prefix")) aov_prefix = v;
+        else if (const char *v = val("--pick")) {
+            if (std::sscanf(v, "%d,%d", &pick_i, &pick_j) != 2) {
+                std::fprintf(stderr, "--pick needs a pixel i,j, not '%s'\n", v);
+                return 2;
+            }
+            pick = true;
+        }
         else if (const char *v = val("--earth")) earth_path = v;
         else if (const char *v = val("--earth-bytes")) {
             earth_path = v;
@@ -281,7 +290,9 @@ int main(int argc, char **argv)
                          "            [--earth earthmap.jpg|decoded.ppm | --earth-bytes texture.ppm] [--accelerate-lists] [--flags N]\n"
                          "            [--noise T [--min-spp N] [--check-every K] [--samples-map file.pgm]]\n"
                          "            [--denoise [--denoise-iterations N] [--denoise-sigmas c,a,n,z] [--raw-output file.ppm]]\n"
-                         "            [--aov-prefix P] [--feature-samples N]\n"
+                         "            [--aov-prefix P] [--feature-samples N] [--pick i,j]\n"
+                         "  --pick         render nothing: print what the ray through the centre of pixel (i, j) hits (j = 0 is the bottom row) --\n"
+                         "                 leaf, material kind, t, point, normal, albedo -- at the shutter's opening, over [0.001, inf)\n"
                          "  --denoise      --output gets the frame after the edge-avoiding a-trous filter (1..8 levels, default 5; sigmas of the colour,\n"
                          "                 albedo, normal and depth edge stops, inf = off), guided by the first hits' albedo, normal and depth;\n"
                          "                 --raw-output: the unfiltered frame beside it\n"
@@ -331,7 +342,11 @@ int main(int argc, char **argv)
     }
     if (spp < 0) spp = (scene_id == 9) ? 100 : ((scene_id >= 5 && scene_id <= 8) ? 200 : 10);  // R/kernel.cu:593
 
-    std::fprintf(stderr, "Rendering a %dx%d image with %d samples per pixel in 8x8 blocks.\n", width, height, spp);
+    if (pick && (pick_i < 0 || pick_i >= width || pick_j < 0 || pick_j >= height)) {
+        std::fprintf(stderr, "--pick: pixel (%d, %d) is outside the %dx%d frame\n", pick_i, pick_j, width, height);
+        return 2;
+    }
+    if (!pick) std::fprintf(stderr, "Rendering a %dx%d image with %d samples per pixel in 8x8 blocks.\n", width, height, spp);
     rt_scene *scene = rt_scene_create();
     // R/kernel.cu:656-665: scenes 2 and 9 load earthmap.jpg through stb_image.  This executable carries no JPEG decoder:
     // the decoded pixels come in as a PPM (--earth / --earth-bytes; ./earthmap.ppm is picked up like the reference picks
@@ -375,6 +390,38 @@ int main(int argc, char **argv)
     if (rt_scene_build_builtin(scene, scene_id, world_kind, width, height, seed, earth.empty() ? nullptr : earth.data(), earth_w,
                                earth_h) != RT_OK)
         return die("scene");
+
+    if (pick) {  // one closest-hit query (rt_scene_intersect) for the pixel's centre ray as the feature pass builds it
+        double cam[27];  // bg, origin, lower-left corner, horizontal, vertical, u, v, w, lens radius, time0, time1
+        if (rt_scene_dump_camera(scene, cam) != RT_OK) return die("camera");
+        const double u = ((double)pick_i + 0.5) / (double)width, v = ((double)pick_j + 0.5) / (double)height;
+        double o[3], d[3];
+        for (int a = 0; a < 3; a++) {
+            o[a] = cam[3 + a];
+            d[a] = ((cam[6 + a] + u * cam[9 + a]) + v * cam[12 + a]) - o[a];
+        }
+        rt_query_params qp{};
+        qp.count = 1;
+        qp.tmin = 0.001;
+        qp.tmax = INFINITY;
+        qp.time = cam[25];
+        qp.seed = seed;
+        qp.first_sequence = (unsigned long long)pick_j * (unsigned long long)width + (unsigned long long)pick_i;  // the pixel's stream
+        qp.variant = variant;
+        qp.device = device;
+        const rt_query_rays rays{o, d, nullptr, nullptr, nullptr};
+        double t = 0.0, n[3], albedo[3];
+        int32_t leaf = -1;
+        uint8_t kind = 255;
+        const rt_query_hits hits{&t, n, nullptr, albedo, &leaf, nullptr, &kind, nullptr};
+        if (rt_scene_intersect(scene, &qp, &rays, &hits, nullptr) != RT_OK) return die("pick");
+        static const char *const kinds[] = {"lambertian", "metal", "dielectric", "diffuse_light", "isotropic"};
+        std::printf("pick %d,%d: leaf %d material %s t %.17g point %.17g %.17g %.17g normal %.17g %.17g %.17g albedo %.17g %.17g %.17g\n", pick_i,
+                    pick_j, (int)leaf, kind < 5 ? kinds[kind] : "none", t, o[0] + t * d[0], o[1] + t * d[1], o[2] + t * d[2], n[0], n[1], n[2],
+                    albedo[0], albedo[1], albedo[2]);
+        rt_scene_destroy(scene);
+        return 0;
+    }
 
     rt_render_params p{};
     p.width = width;

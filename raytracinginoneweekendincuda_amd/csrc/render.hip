@@ -46,6 +46,9 @@
 #ifndef RT_FEATURES  // 1: this translation unit holds the first-hit feature kernels (feature_kernel) and nothing else
 #define RT_FEATURES 0
 #endif
+#ifndef RT_QUERY  // 1: this translation unit holds the ray-query kernels (query_kernel) and nothing else
+#define RT_QUERY 0
+#endif
 
 namespace rtow {
 namespace {
@@ -3953,6 +3956,216 @@ hipError_t RT_CAT(launch_features_, RT_SUFFIX)(const DeviceScene &sc, const Feat
     const dim3 grid((a.n_pixels + 255u) / 256u), block(256);
     if (sc.world_kind == WORLD_BVH) hipLaunchKernelGGL((feature_kernel<RT_STRICT, TBvhNested>), grid, block, 0, stream, sc, a);
     else hipLaunchKernelGGL((feature_kernel<RT_STRICT, TListNested>), grid, block, 0, stream, sc, a);
+    return hipGetLastError();
+}
+#elif RT_QUERY
+// ------------------------------------------------------------------------------------------------
+// Ray queries (rt_scene_intersect): closest hit or occlusion for caller-supplied rays.  The feature pass's search once more -- one
+// lane per ray, no LDS, every table from global memory, the reference's tree or list in the reference's order through leaf_test /
+// walk_node -- with the ray, its time and its interval read from the caller's arrays.  The two short outer loops are this
+// section's own copies (world_hit_list, walk_leaves): they note which world leaf produced the winning record and, for an
+// occlusion query of a world without media, stop at the first accepted hit.  The library's own tree is never walked here: it is
+// valid only while hits stay inside their leaves' boxes, which depends on the shutter, and a caller's times are arbitrary.
+// Termination for any ray, degenerate ones included: the list loop runs n_world_items times; every walk_node step either moves
+// to a node with a higher index (n + 1, or an escape link, which always points forward in the preorder array) or parks, a
+// parked lane leaves through the escape link, and the last escape is kNone -- at most two steps per node whatever the box tests
+// answer (NaNs only make them false); leaf tests are straight-line code or loops over table counts (tree_hit: a bounded stack).
+// ------------------------------------------------------------------------------------------------
+namespace {
+// R/HittableList.h:39-57 as world_hit_list runs it, plus the position of the winning leaf; FIRST: leave at the first accepted hit
+template <class T>
+DEV bool query_hit_list(const DeviceScene &sc, const Ray &r, double tmin, double tmax, bool first, HitInfo &best, uint32_t &leaf, Xorwow &rng)
+{
+    const double a = dot(r.d, r.d);
+    double closest = tmax;
+    bool any = false;
+    const uint32_t n = sc.n_world_items;
+    for (uint32_t k = 0; k < n; k++) {
+        const uint32_t ref = (uint32_t)__builtin_amdgcn_readfirstlane((int)((const RT_CONST uint32_t *)(uintptr_t)sc.world_items)[k]);
+        if (leaf_test<T>(sc, ref, r, a, tmin, closest, best, rng)) {
+            any = true;
+            closest = best.t;
+            leaf = k;
+            if (first) break;
+        }
+    }
+    return any;
+}
+
+// walk_leaves for a parked lane (the bottom node's one or two leaves in the reference's order; a span-1 node holds its leaf twice and
+// only a medium is tested again), plus the position of the winning leaf from the table parallel to nodes[]
+template <class T>
+DEV void query_walk_leaves(const DeviceScene &sc, const uint32_t *__restrict__ node_leaf_pos, const Ray &r, double tmin, Walk &w, HitInfo &best,
+                           uint32_t &leaf, Xorwow &rng)
+{
+    const uint32_t n = w.state & ~kWalkParked;
+    const BvhNodeRec *node = sc.nodes + n;
+    const uint32_t na = node->a, nb = node->b, next = node->escape;
+    const bool again = nb != na || is_medium_leaf(nb);
+    for (int c = 0; c < 2; c++) {  // one inlined copy of the leaf test
+        if (c == 1 && !again) break;
+        if (leaf_test<T>(sc, c ? nb : na, r, w.a, tmin, w.closest, best, rng)) {
+            w.any = true;
+            w.closest = best.t;
+            leaf = node_leaf_pos[2u * n + (uint32_t)c];
+        }
+    }
+    w.state = next;
+}
+
+// HitRecord U, V of the primitive that won (R/Sphere.h:44, R/MovingSphere.h:70, R/Quad.h:96-97), in the space the hit was found in
+// as make_surface finds it -- which computes them only for materials that read them
+template <class T>
+DEV void query_uv(const DeviceScene &sc, const Ray &r, const HitInfo &h, double &u, double &v)
+{
+    u = 0.0;
+    v = 0.0;
+    const uint32_t tag = h.ref >> kRefShift, idx = h.ref & kRefIndexMask;
+    if (tag == REF_MEDIUM) return;
+    Ray lr = r;
+    if (h.obj != kNone) {
+        uint32_t xf_first, xf_count;
+        if (h.obj & kTreeObjBit) {
+            const TreeNodeRec n = sc.tree_nodes[h.obj & ~kTreeObjBit];
+            xf_first = n.chain_first;
+            xf_count = n.chain_count;
+        } else {
+            const ObjectRec o = get_object(sc, h.obj);
+            xf_first = o.xf_first;
+            xf_count = o.xf_count;
+        }
+        lr = chain_ray(sc, xf_first, xf_count, r);
+    }
+    const Vec p = at(lr, h.t);
+    if (tag == REF_QUAD) {
+        const QuadGeom q = sc.quads[idx];
+        const Vec ph = p - mk(q.qx, q.qy, q.qz), w = mk(q.wx, q.wy, q.wz);
+        u = dot(w, cross(ph, mk(q.vx, q.vy, q.vz)));
+        v = dot(w, cross(mk(q.ux, q.uy, q.uz), ph));
+    } else if (tag == REF_SPHERE) {
+        const SphereGeom g = sc.spheres[idx];
+        sphere_uv(sc.sphere_aux[idx].inv_r * (p - mk(g.cx, g.cy, g.cz)), u, v);
+    } else {
+        const Vec c = msphere_center(sc.mspheres[idx], lr.tm, (sc.flags & SCENE_MS_UNIT_TIME) != 0);
+        sphere_uv(sc.msphere_aux[idx].inv_r * (p - c), u, v);
+    }
+}
+}  // namespace
+
+// MODE 0 closest hit, 1 occlusion
+template <int STRICT, class T, int MODE>
+__global__ __launch_bounds__(256) void query_kernel(DeviceScene sc, QueryArgs a)
+{
+    sc.lds_quad_aa = sc.lds_boxes = sc.lds_objects = sc.lds_xforms = sc.lds_media = sc.lds_materials = sc.lds_perlin = kNone;
+    sc.lds_spheres_tab = sc.lds_group_boxes = sc.lds_mspheres = sc.lds_msphere_aux = sc.lds_sphere_aux = kNone;
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= a.count) return;
+    Ray ray;
+    ray.o = mk(a.origin[(size_t)k * 3 + 0], a.origin[(size_t)k * 3 + 1], a.origin[(size_t)k * 3 + 2]);
+    ray.d = mk(a.direction[(size_t)k * 3 + 0], a.direction[(size_t)k * 3 + 1], a.direction[(size_t)k * 3 + 2]);
+    ray.tm = a.time ? a.time[k] : a.time_all;
+    const double tmin = a.tmin ? a.tmin[k] : a.tmin_all;
+    const double tmax = fmin(a.tmax ? a.tmax[k] : a.tmax_all, DBL_MAX);  // +inf: DBL_MAX, what a render passes (R/kernel.cu:77)
+    const bool media = (sc.flags & SCENE_HAS_MEDIA) != 0;
+    Xorwow rng = a.base;  // curand_init(seed, k + first_sequence, 0); only a medium's test draws
+    if (media) xorwow_skip_sequences(a.jump_table, a.first_sequence + (uint64_t)k, rng);
+    const bool first = MODE == 1 && !media;  // a medium's answer depends on what was found before it: the full search
+    HitInfo h;
+    h.t = 0.0;
+    h.ref = kNone;
+    h.obj = kNone;
+    uint32_t leaf = kNone;
+    bool hit = false;
+    if constexpr (T::WORLD == 0) {
+        if (sc.n_world_nodes != 0) {
+            const NodeView nv{sc.nodes, 0u, false};
+            Walk w{};
+            walk_begin<false>(w, ray, tmax);
+            while (w.state != kNone) {
+                if (walk_moving(w.state)) {
+                    walk_node<false>(nv, ray, tmin, w);
+                } else {
+                    query_walk_leaves<T>(sc, a.node_leaf_pos, ray, tmin, w, h, leaf, rng);
+                    if (first && w.any) break;
+                }
+            }
+            hit = w.any;
+        }
+    } else {
+        hit = query_hit_list<T>(sc, ray, tmin, tmax, first, h, leaf, rng);
+    }
+    if (a.hit_counter) {
+        const unsigned long long found = __ballot(hit);  // one atomic per wave (per group of lanes that arrive together)
+        if (hit && (uint32_t)__ffsll((long long)found) - 1u == (threadIdx.x & 63u)) atomicAdd(a.hit_counter, (unsigned long long)__popcll(found));
+    }
+    if (a.occluded) a.occluded[k] = hit ? 1 : 0;
+    if constexpr (MODE == 0) {
+        if (a.t) a.t[k] = hit ? h.t : (double)INFINITY;
+        if (a.leaf) a.leaf[k] = hit ? (int32_t)leaf : -1;
+        const bool want_material = a.material || a.albedo;
+        if (!(a.normal || a.uv || a.front_face || want_material)) return;
+        Vec normal = mk(0.0, 0.0, 0.0), value = mk(0.0, 0.0, 0.0);
+        double u = 0.0, v = 0.0;
+        uint32_t kind = 255u;
+        bool front = false;
+        if (!hit) {
+            if (a.albedo) value = load3c(((const RT_CONST CameraRec *)(uintptr_t)sc.camera)->bg);
+        } else {
+            if (a.uv) query_uv<T>(sc, ray, h, u, v);
+            if (a.normal || a.front_face || want_material) {  // (U/V alone need no hit record)
+                const Surface s = make_surface<T>(sc, ray, h);
+                if ((h.ref >> kRefShift) != REF_MEDIUM) normal = s.n;
+                front = s.front;
+                if (want_material) {
+                    const MatView mp = material_view<false>(sc, s.mat);
+                    kind = mp.u32(MAT_OFF(kind));
+                    if (a.albedo) {  // the table of rt_film_render_features
+                        if (kind == MAT_METAL) value = mp.vec(MAT_OFF(r));
+                        else if (kind == MAT_DIELECTRIC) value = mk(1.0, 1.0, 1.0);
+                        else value = material_texture<T>(sc, mp, mp.u32(MAT_OFF(tex_inline)), s.u, s.v, s.p);
+                    }
+                }
+            }
+        }
+        // as the feature pass stores its one sample, 0 + x: no negative zeros
+        value = mk(0.0, 0.0, 0.0) + (mk(0.0, 0.0, 0.0) + mk(1.0, 1.0, 1.0) * value);
+        normal = mk(0.0, 0.0, 0.0) + normal;
+        if (a.normal) {
+            a.normal[(size_t)k * 3 + 0] = normal.x;
+            a.normal[(size_t)k * 3 + 1] = normal.y;
+            a.normal[(size_t)k * 3 + 2] = normal.z;
+        }
+        if (a.uv) {
+            a.uv[(size_t)k * 2 + 0] = u;
+            a.uv[(size_t)k * 2 + 1] = v;
+        }
+        if (a.albedo) {
+            a.albedo[(size_t)k * 3 + 0] = value.x;
+            a.albedo[(size_t)k * 3 + 1] = value.y;
+            a.albedo[(size_t)k * 3 + 2] = value.z;
+        }
+        if (a.front_face) a.front_face[k] = front ? 1 : 0;
+        if (a.material) a.material[k] = (uint8_t)kind;
+    }
+}
+
+hipError_t RT_CAT(launch_query_, RT_SUFFIX)(const DeviceScene &sc, const QueryArgs &a, hipStream_t stream, QueryKernelInfo *info)
+{
+    if (a.mode != 0 && a.mode != 1) return hipErrorInvalidValue;
+    if (sc.world_kind == WORLD_BVH && !a.node_leaf_pos) return hipErrorInvalidValue;
+    void (*kernel)(DeviceScene, QueryArgs);
+    if (sc.world_kind == WORLD_BVH) kernel = a.mode == 0 ? query_kernel<RT_STRICT, TBvhNested, 0> : query_kernel<RT_STRICT, TBvhNested, 1>;
+    else kernel = a.mode == 0 ? query_kernel<RT_STRICT, TListNested, 0> : query_kernel<RT_STRICT, TListNested, 1>;
+    if (info) {
+        hipFuncAttributes attr;
+        hipError_t e = hipFuncGetAttributes(&attr, reinterpret_cast<const void *>(kernel));
+        if (e != hipSuccess) return e;
+        info->vgprs = attr.numRegs;
+        info->scratch_bytes = (int)attr.localSizeBytes;
+        return hipSuccess;
+    }
+    if (a.count == 0) return hipSuccess;
+    hipLaunchKernelGGL(kernel, dim3((a.count + 255u) / 256u), dim3(256), 0, stream, sc, a);
     return hipGetLastError();
 }
 #elif RT_GROUP == 1

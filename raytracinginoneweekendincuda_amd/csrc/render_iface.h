@@ -131,6 +131,33 @@ struct FeatureArgs {
 hipError_t launch_features_strict(const DeviceScene &sc, const FeatureArgs &a, hipStream_t stream);
 hipError_t launch_features_fast(const DeviceScene &sc, const FeatureArgs &a, hipStream_t stream);
 
+// Ray queries (rt_scene_intersect; the RT_QUERY objects of render.hip): one lane per caller-supplied ray, the reference's tree or
+// list in the reference's order as in the feature pass, every table from global memory.  Ray k's stream is seeded in the kernel,
+// curand_init(seed, k + first_sequence, 0), and only where the scene has media: nothing else draws.
+struct QueryArgs {
+    const double *origin, *direction;   // count x 3 each
+    const double *time, *tmin, *tmax;   // count each, or nullptr: the scalars below
+    double time_all, tmin_all, tmax_all;
+    double *t, *normal, *uv, *albedo;   // outputs, each may be nullptr (rt_query_hits)
+    int32_t *leaf;
+    uint8_t *front_face, *material, *occluded;
+    // BVH worlds: per node of the world's tree, the positions among the world's leaves (rt_scene_dump_leaves order) of a bottom
+    // node's leaves a and b (FlatScene::node_leaf_pos)
+    const uint32_t *node_leaf_pos;
+    unsigned long long *hit_counter;    // one word, zeroed by the caller: rays that report a hit; nullptr: not counted
+    const uint32_t *jump_table;         // kJumpTableWords
+    Xorwow base;                        // salted seed state (sequence 0)
+    uint64_t first_sequence;
+    uint32_t count;
+    int32_t mode;                       // 0 closest hit, 1 occlusion (only `occluded` is written)
+};
+struct QueryKernelInfo {
+    int vgprs, scratch_bytes;
+};
+// info != nullptr: report the instantiation that would run instead of launching it
+hipError_t launch_query_strict(const DeviceScene &sc, const QueryArgs &a, hipStream_t stream, QueryKernelInfo *info = nullptr);
+hipError_t launch_query_fast(const DeviceScene &sc, const QueryArgs &a, hipStream_t stream, QueryKernelInfo *info = nullptr);
+
 // One level of the edge-avoiding a-trous filter (denoise.hip; include/rtow.h rt_denoise_params has the stencil): full-frame
 // planes, `in` and `out` distinct.  A guide that is nullptr switches its term off; inv_* = 1 / sigma^2 (0 for sigma = +inf), the
 // colour's already scaled for the level.

@@ -1092,6 +1092,24 @@ int flatten_scene(SceneImpl &s)
         if (world.tree.empty()) return fail(RT_ERR_INVALID, "BvhNode world has no nodes");
         fl.thread_tree(world, 0, kNone, ref_of_handle);
         f.n_world_nodes = (uint32_t)f.nodes.size();
+        // Ray queries report which world leaf was hit: per node of the world's tree, the positions among the leaves of a bottom
+        // node's two.  build_tree halves [start, end) of the sorted leaves and thread_tree numbers the nodes in the same
+        // preorder, so the ranges are recomputed rather than looked up by handle (a handle may be listed twice).
+        f.node_leaf_pos.assign(2 * (size_t)f.n_world_nodes, kNone);
+        uint32_t next_node = 0;
+        auto number = [&](auto &&self, int ti, uint32_t start, uint32_t end) -> void {
+            const auto &tn = world.tree[(size_t)ti];
+            const uint32_t me = next_node++;
+            if (tn.left < 0) {
+                f.node_leaf_pos[2 * (size_t)me] = start;
+                f.node_leaf_pos[2 * (size_t)me + 1] = end - 1;  // span 1: the same leaf twice
+                return;
+            }
+            const uint32_t mid = start + (end - start) / 2;
+            self(self, tn.left, start, mid);
+            self(self, tn.right, mid, end);
+        };
+        number(number, 0, 0u, (uint32_t)leaves.size());
     } else {
         bool all_spheres = !f.world_items.empty();
         for (size_t k = 0; k < f.world_items.size(); k++) all_spheres &= f.world_items[k] == make_ref(REF_SPHERE, (uint32_t)k);

@@ -89,6 +89,7 @@ struct FlatScene {
     std::vector<SegMedium> seg_media;    // SCENE_SEGMENTED
     std::vector<SegCandidate> seg_cand;  // SCENE_SEGMENTED
     std::vector<uint32_t> world_items;   // leaf refs in final order (both world kinds)
+    std::vector<uint32_t> node_leaf_pos; // WORLD_BVH: per world node, the positions in world_items of a bottom node's leaves a and b (ray queries)
     std::vector<Box> leaf_boxes;         // introspection
     std::vector<int> leaf_kinds;         // introspection: the leaf's kind as constructed (0 sphere, 1 moving sphere, 2 quad, 3 composite)
     std::vector<MaterialRec> materials;
