@@ -13,6 +13,8 @@
 #include <vector>
 
 #include "../../include/rtow.h"
+#include "device_arena.h"
+#include "film_rows.h"
 #include "launch_plan.h"
 #include "render_iface.h"
 #include "scene_host.h"
@@ -31,40 +33,13 @@ static int hip_fail(hipError_t e, const char *what)
     } while (0)
 
 struct DeviceTables {
-    int device = -1;
     uint64_t generation = 0;  // SceneImpl::generation these tables were made from
-    std::vector<void *> allocations;
+    DeviceArena memory;       // every table below
     DeviceScene scene{};
     const uint32_t *node_leaf_pos = nullptr;  // ray queries (rt_scene_intersect_device): FlatScene::node_leaf_pos
 };
 
-void release_device_tables(DeviceTables *t)
-{
-    if (!t) return;
-    int prev = 0;
-    hipGetDevice(&prev);
-    hipSetDevice(t->device);
-    for (void *p : t->allocations) hipFree(p);
-    hipSetDevice(prev);
-    delete t;
-}
-
-template <class T>
-static int upload(DeviceTables &dt, const std::vector<T> &host, const T *&dev)
-{
-    dev = nullptr;
-    // keep every table pointer valid (never null) so that speculative loads stay in bounds
-    size_t bytes = (host.empty() ? 1 : host.size()) * sizeof(T);
-    void *p = nullptr;
-    HIP_TRY(hipMalloc(&p, bytes));
-    dt.allocations.push_back(p);
-    if (!host.empty())
-        HIP_TRY(hipMemcpy(p, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice));
-    else
-        HIP_TRY(hipMemset(p, 0, bytes));
-    dev = static_cast<const T *>(p);
-    return RT_OK;
-}
+void release_device_tables(DeviceTables *t) { delete t; }
 
 // jump table: one copy per device for the life of the process
 static std::mutex g_jump_mutex;
@@ -95,12 +70,14 @@ static int select_device(int device)
 }
 
 constexpr size_t kCounterWords = 128;
+constexpr size_t kHeavyCountWords = 16;  // FilmImpl::heavy_count: [0] length of heavy_list, [1] of super_list
 
 struct FilmImpl {
     int device = 0;
-    int width = 0, height = 0, stripe_rows = 8, rank = 0, world_size = 1;
-    int rows_owned = 0;
-    uint32_t n_pixels = 0;
+    int stripe_rows = 8, rank = 0, world_size = 1;
+    FilmGeometry geometry{};       // the frame's size and this rank's share of it (film_geometry)
+    DeviceArena planes;            // every device pointer below that is the film's own, allocated at creation or on first use
+    size_t plane_pixels() const { return geometry.n_pixels ? geometry.n_pixels : 1; }  // never an empty plane
     double *pixels = nullptr;      // where the kernel writes (own_pixels or a bound external buffer)
     double *own_pixels = nullptr;
     double *accum = nullptr;       // progressive rendering: unnormalised colour sums (allocated on first use)
@@ -116,7 +93,6 @@ struct FilmImpl {
     // class; the serving waves of the render launch take the listed pixels, the others the rest of the tile queue
     uint32_t *pix_cost = nullptr, *heavy_list = nullptr, *heavy_count = nullptr, *super_list = nullptr;  // heavy_count[1]: length of super_list
     uint8_t *pix_class = nullptr;
-    uint32_t n_tiles = 0;
     unsigned long long *host_counters = nullptr;  // pinned mirror of ray_counter, filled by an async copy behind the render
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};  // begin, after seed, after render, after the counter copy
     bool seeded = false;
@@ -158,6 +134,17 @@ static AdaptiveRule to_rule(const rt_adaptive_params &p) { return AdaptiveRule{p
 static bool continues_frame(const FilmImpl &f, const rt_render_params *p)
 {
     return (p->flags & RT_FLAG_ACCUMULATE) && (p->flags & RT_FLAG_KEEP_RNG_STATE) && f.seeded && f.accum && f.accum_spp > 0;
+}
+
+// A compact device plane of the film, `channels` values per pixel -> the full frame on the host.  The rows of other ranks
+// are zeroed, as include/rtow.h documents for every download but rt_film_download, which leaves them as the caller had them.
+template <class T>
+static int download_rows(const FilmImpl &f, const T *device_plane, int channels, bool clear_other_rows, T *full)
+{
+    std::vector<T> compact((size_t)f.geometry.n_pixels * channels);
+    if (f.geometry.n_pixels) HIP_TRY(hipMemcpy(compact.data(), device_plane, compact.size() * sizeof(T), hipMemcpyDeviceToHost));
+    scatter_owned_rows(compact.data(), channels, f.geometry.width, f.geometry.height, f.stripe_rows, f.rank, f.world_size, clear_other_rows, full);
+    return RT_OK;
 }
 
 // a launch of `s` into `f` is (about to be) in flight / is over
@@ -223,13 +210,13 @@ int rt_scene_upload(rt_scene *scene, int device)
         s.device[device] = nullptr;
     }
     DeviceTables *dt = new DeviceTables;
-    dt->device = device;
+    dt->memory = DeviceArena(device);
     dt->generation = s.generation;
     const FlatScene &f = s.flat;
     DeviceScene &d = dt->scene;
-    int rc = RT_OK;
+    hipError_t e = hipSuccess;
     auto up = [&](auto &host, auto &dev) {
-        if (rc == RT_OK) rc = upload(*dt, host, dev);
+        if (e == hipSuccess) e = dt->memory.upload(host, dev);
     };
     up(f.spheres, d.spheres);
     up(f.sphere_scan, d.sphere_scan);
@@ -298,9 +285,9 @@ int rt_scene_upload(rt_scene *scene, int device)
     up(f.perlin, d.perlin);
     std::vector<CameraRec> cam_host(1, s.camera);
     up(cam_host, d.camera);
-    if (rc != RT_OK) {
+    if (e != hipSuccess) {
         release_device_tables(dt);
-        return rc;
+        return hip_fail(e, "rt_scene_upload: table upload");
     }
     scene_counts(f, d);
     d.scan_reach = f.scan_reach;
@@ -324,29 +311,25 @@ rt_film *rt_film_create(int device, int width, int height, int stripe_rows, int 
     if (select_device(device) != RT_OK) return nullptr;
     FilmImpl *f = new FilmImpl;
     f->device = device;
-    f->width = width;
-    f->height = height;
+    f->planes = DeviceArena(device);
     f->stripe_rows = stripe_rows;
     f->rank = rank;
     f->world_size = world_size;
-    const FilmGeometry geometry = film_geometry(width, height, stripe_rows, rank, world_size);
-    f->rows_owned = geometry.rows_owned;
-    f->n_pixels = geometry.n_pixels;
-    f->n_tiles = geometry.n_tiles;
-    size_t np = f->n_pixels ? f->n_pixels : 1;
-    hipError_t e = hipMalloc((void **)&f->own_pixels, np * 3 * sizeof(double));
+    f->geometry = film_geometry(width, height, stripe_rows, rank, world_size);
+    const size_t np = f->plane_pixels();
+    hipError_t e = f->planes.alloc(np * 3, f->own_pixels);
     if (e == hipSuccess) e = hipMemset(f->own_pixels, 0, np * 3 * sizeof(double));
     f->pixels = f->own_pixels;
-    if (e == hipSuccess) e = hipMalloc((void **)&f->state, np * 6 * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc((void **)&f->ray_counter, kCounterWords * sizeof(unsigned long long));
+    if (e == hipSuccess) e = f->planes.alloc(np * 6, f->state);
+    if (e == hipSuccess) e = f->planes.alloc(kCounterWords, f->ray_counter);
     if (e == hipSuccess) {
         hipDeviceProp_t prop;
         e = hipGetDeviceProperties(&prop, device);
         if (e == hipSuccess) f->num_cus = prop.multiProcessorCount;
     }
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&f->own_stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipMalloc((void **)&f->tile_cost, (f->n_tiles ? f->n_tiles : 1) * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc((void **)&f->tile_order, (f->n_tiles ? f->n_tiles : 1) * sizeof(uint32_t));
+    if (e == hipSuccess) e = f->planes.alloc(f->geometry.n_tiles, f->tile_cost);
+    if (e == hipSuccess) e = f->planes.alloc(f->geometry.n_tiles, f->tile_order);
     if (e == hipSuccess) e = hipHostMalloc((void **)&f->host_counters, kCounterWords * sizeof(unsigned long long), hipHostMallocDefault);
     for (int k = 0; k < 4 && e == hipSuccess; k++) e = hipEventCreate(&f->ev[k]);
     if (e != hipSuccess) {
@@ -366,32 +349,15 @@ void rt_film_destroy(rt_film *film)
         if (f->last_stream) hipStreamSynchronize(f->last_stream);
         mark_done(*f);
     }
-    if (f->own_pixels) hipFree(f->own_pixels);
-    if (f->accum) hipFree(f->accum);
-    if (f->carry) hipFree(f->carry);
-    if (f->state) hipFree(f->state);
-    if (f->ray_counter) hipFree(f->ray_counter);
-    if (f->tile_cost) hipFree(f->tile_cost);
-    if (f->tile_order) hipFree(f->tile_order);
-    if (f->pix_cost) hipFree(f->pix_cost);
-    if (f->heavy_list) hipFree(f->heavy_list);
-    if (f->heavy_count) hipFree(f->heavy_count);
-    if (f->super_list) hipFree(f->super_list);
-    if (f->pix_class) hipFree(f->pix_class);
-    if (f->ad_n) hipFree(f->ad_n);
-    if (f->ad_q) hipFree(f->ad_q);
-    if (f->ad_mark) hipFree(f->ad_mark);
-    for (double *plane : {f->feat_albedo, f->feat_normal, f->feat_depth, f->denoised, f->denoise_tmp})
-        if (plane) hipFree(plane);
     if (f->host_counters) hipHostFree(f->host_counters);
     for (int k = 0; k < 4; k++)
         if (f->ev[k]) hipEventDestroy(f->ev[k]);
     if (f->own_stream) hipStreamDestroy(f->own_stream);
-    delete f;
+    delete f;  // and with it the planes
 }
 
 void *rt_film_device_pixels(rt_film *film) { return film ? F(film)->pixels : nullptr; }
-size_t rt_film_pixel_bytes(rt_film *film) { return film ? (size_t)F(film)->n_pixels * 3 * sizeof(double) : 0; }
+size_t rt_film_pixel_bytes(rt_film *film) { return film ? (size_t)F(film)->geometry.n_pixels * 3 * sizeof(double) : 0; }
 int rt_film_bind_pixels(rt_film *film, void *device_pixels)
 {
     if (!film) return fail(RT_ERR_INVALID, "rt_film_bind_pixels: null film");
@@ -406,9 +372,12 @@ struct Build {
     hipError_t (*render)(int, const DeviceScene &, const RenderArgs &, hipStream_t);
     hipError_t (*info)(int, const DeviceScene &, const RenderArgs &, KernelInfo *);
     hipError_t (*adaptive_rule)(const AdaptiveRule &, uint32_t, const uint32_t *, const double *, const double *, double *, uint8_t *, hipStream_t);
+    hipError_t (*features)(const DeviceScene &, const FeatureArgs &, hipStream_t);
+    hipError_t (*query)(const DeviceScene &, const QueryArgs &, hipStream_t, QueryKernelInfo *);
 };
-static const Build kBuilds[2] = {{launch_seed_strict, launch_render_strict, kernel_info_strict, launch_adaptive_rule_strict},
-                                 {launch_seed_fast, launch_render_fast, kernel_info_fast, launch_adaptive_rule_fast}};
+static const Build kBuilds[2] = {
+    {launch_seed_strict, launch_render_strict, kernel_info_strict, launch_adaptive_rule_strict, launch_features_strict, launch_query_strict},
+    {launch_seed_fast, launch_render_fast, kernel_info_fast, launch_adaptive_rule_fast, launch_features_fast, launch_query_fast}};
 
 static int seed_film(FilmImpl &f, const rt_render_params *p, hipStream_t stream)
 {
@@ -416,8 +385,8 @@ static int seed_film(FilmImpl &f, const rt_render_params *p, hipStream_t stream)
     sa.state = f.state;
     if (int rc = device_jump_table(f.device, &sa.jump_table)) return rc;
     sa.base = xorwow_seed(p->seed, kSaltCurandDevice);
-    sa.n_pixels = f.n_pixels;
-    sa.width = f.width;
+    sa.n_pixels = f.geometry.n_pixels;
+    sa.width = f.geometry.width;
     sa.stripe_rows = f.stripe_rows;
     sa.rank = f.rank;
     sa.world_size = f.world_size;
@@ -433,7 +402,7 @@ static int book_frame(FilmImpl &f, const rt_render_params *p, bool keep, bool co
     if (p->flags & RT_FLAG_ACCUMULATE) {
         // progressive frame: this launch's samples are added to the film's running sums (needs the saved RNG streams)
         if (!f.accum) {
-            HIP_TRY(hipMalloc((void **)&f.accum, (size_t)(f.n_pixels ? f.n_pixels : 1) * 3 * sizeof(double)));
+            HIP_TRY(f.planes.alloc(f.plane_pixels() * 3, f.accum));
             f.accum_spp = 0;
         }
         if (!keep) f.accum_spp = 0;  // re-seeded: start a new frame
@@ -454,11 +423,11 @@ static int book_frame(FilmImpl &f, const rt_render_params *p, bool keep, bool co
     if (f.adaptive) {
         // samples_per_pixel is the most a pixel may take in this launch; n, q and the mark live per pixel and persist with the
         // sums of an accumulated frame
-        const size_t np = f.n_pixels ? f.n_pixels : 1;
+        const size_t np = f.plane_pixels();
         if (!f.ad_n) {
-            HIP_TRY(hipMalloc((void **)&f.ad_n, np * sizeof(uint32_t)));
-            HIP_TRY(hipMalloc((void **)&f.ad_q, np * sizeof(double)));
-            HIP_TRY(hipMalloc((void **)&f.ad_mark, np));
+            HIP_TRY(f.planes.alloc(np, f.ad_n));
+            HIP_TRY(f.planes.alloc(np, f.ad_q));
+            HIP_TRY(f.planes.alloc(np, f.ad_mark));
         }
         if (!continues) {
             HIP_TRY(hipMemsetAsync(f.ad_n, 0, np * sizeof(uint32_t), stream));
@@ -495,10 +464,10 @@ static void fill_render_args(const FilmImpl &f, const rt_render_params *p, const
     ra.rounds = plan.rounds;
     ra.overdue_priority = (p->flags & RT_FLAG_OVERDUE_PRIORITY) ? 1 : 0;
     ra.ray_budget = plan.ray_budget;
-    ra.n_pixels = f.n_pixels;
-    ra.width = f.width;
-    ra.height = f.height;
-    ra.rows_owned = f.rows_owned;
+    ra.n_pixels = f.geometry.n_pixels;
+    ra.width = f.geometry.width;
+    ra.height = f.geometry.height;
+    ra.rows_owned = f.geometry.rows_owned;
     ra.spp = p->samples_per_pixel;
     ra.max_depth = p->max_depth;
     ra.stripe_rows = f.stripe_rows;
@@ -518,12 +487,12 @@ static int allocate_class_planes(FilmImpl &f, const rt_launch_plan &plan)
 {
     if (!plan.pixel_classes) return RT_OK;
     if (!f.pix_cost) {
-        HIP_TRY(hipMalloc((void **)&f.pix_cost, (size_t)f.n_pixels * sizeof(uint32_t)));
-        HIP_TRY(hipMalloc((void **)&f.heavy_list, (size_t)f.n_pixels * sizeof(uint32_t)));
-        HIP_TRY(hipMalloc((void **)&f.heavy_count, 64));
-        HIP_TRY(hipMalloc((void **)&f.pix_class, (size_t)f.n_pixels));
+        HIP_TRY(f.planes.alloc(f.geometry.n_pixels, f.pix_cost));
+        HIP_TRY(f.planes.alloc(f.geometry.n_pixels, f.heavy_list));
+        HIP_TRY(f.planes.alloc(kHeavyCountWords, f.heavy_count));
+        HIP_TRY(f.planes.alloc(f.geometry.n_pixels, f.pix_class));
     }
-    if (plan.super_threshold > 0 && !f.super_list) HIP_TRY(hipMalloc((void **)&f.super_list, (size_t)f.n_pixels * sizeof(uint32_t)));
+    if (plan.super_threshold > 0 && !f.super_list) HIP_TRY(f.planes.alloc(f.geometry.n_pixels, f.super_list));
     return RT_OK;
 }
 
@@ -535,7 +504,7 @@ static int enqueue_rehearsal(FilmImpl &f, const DeviceScene &ds, const rt_launch
 {
     const bool keeps = plan.probe_keeps != 0;
     if (keeps && !ra.accum) {
-        if (!f.carry) HIP_TRY(hipMalloc((void **)&f.carry, (size_t)(f.n_pixels ? f.n_pixels : 1) * 3 * sizeof(double)));
+        if (!f.carry) HIP_TRY(f.planes.alloc(f.plane_pixels() * 3, f.carry));
         ra.accum = f.carry;
         ra.spp_before = 0;
     }
@@ -555,10 +524,10 @@ static int enqueue_rehearsal(FilmImpl &f, const DeviceScene &ds, const rt_launch
     probe.tile_cost = plan.rank_tiles ? f.tile_cost : nullptr;
     probe.tile_order = nullptr;
     probe.pix_cost = plan.pixel_classes ? f.pix_cost : nullptr;
-    if (plan.rank_tiles) HIP_TRY(hipMemsetAsync(f.tile_cost, 0, f.n_tiles * sizeof(uint32_t), stream));
+    if (plan.rank_tiles) HIP_TRY(hipMemsetAsync(f.tile_cost, 0, f.geometry.n_tiles * sizeof(uint32_t), stream));
     HIP_TRY(build.render(plan.probe_kernel, ds, probe, stream));
     if (plan.rank_tiles) {
-        HIP_TRY(launch_tile_order(f.tile_cost, f.tile_order, f.n_tiles, (uint32_t)plan.tile_flatness_x8, stream));
+        HIP_TRY(launch_tile_order(f.tile_cost, f.tile_order, f.geometry.n_tiles, (uint32_t)plan.tile_flatness_x8, stream));
         ra.tile_order = f.tile_order;
     }
     if (keeps) {
@@ -576,9 +545,9 @@ static int enqueue_rehearsal(FilmImpl &f, const DeviceScene &ds, const rt_launch
     }
     if (!plan.pixel_classes) return RT_OK;
     const bool longest = plan.super_threshold > 0;
-    HIP_TRY(hipMemsetAsync(f.heavy_count, 0, 64, stream));
-    HIP_TRY(launch_classify_pixels(f.pix_cost, f.n_pixels, (uint32_t)plan.heavy_threshold, f.pix_class, f.heavy_list, f.heavy_count, stream,
-                                   longest ? f.super_list : nullptr, (uint32_t)plan.super_threshold, (uint32_t)f.width,
+    HIP_TRY(hipMemsetAsync(f.heavy_count, 0, kHeavyCountWords * sizeof(uint32_t), stream));
+    HIP_TRY(launch_classify_pixels(f.pix_cost, f.geometry.n_pixels, (uint32_t)plan.heavy_threshold, f.pix_class, f.heavy_list, f.heavy_count, stream,
+                                   longest ? f.super_list : nullptr, (uint32_t)plan.super_threshold, (uint32_t)f.geometry.width,
                                    (uint32_t)plan.near_percent, (uint32_t)plan.near_neighbours));
     if (longest) {
         HIP_TRY(hipMemsetAsync(f.ray_counter + 9, 0, sizeof(unsigned long long), stream));
@@ -616,8 +585,7 @@ static int enqueue_frame(SceneImpl &s, FilmImpl &f, const rt_render_params *p, h
     HIP_TRY(hipEventRecord(f.ev[1], stream));
     RenderArgs ra{};
     if (int rc = book_frame(f, p, keep, continues, ra, stream)) return rc;
-    const FilmGeometry geometry{f.width, f.height, f.rows_owned, f.n_pixels, f.n_tiles};
-    const rt_launch_plan plan = plan_launch(ds, geometry, f.num_cus, *p, f.adaptive, hits_stay_in_boxes(s.flat, s.camera, p->variant));
+    const rt_launch_plan plan = plan_launch(ds, f.geometry, f.num_cus, *p, f.adaptive, hits_stay_in_boxes(s.flat, s.camera, p->variant));
     fill_render_args(f, p, plan, ra);
     KernelInfo info{};
     HIP_TRY(build.info(plan.kernel, ds, ra, &info));  // the registers the compiler gave it; the rest is the plan's
@@ -642,7 +610,7 @@ int rt_render_launch(rt_scene *scene, rt_film *film, const rt_render_params *p)
     if (!scene || !film || !p) return fail(RT_ERR_INVALID, "rt_render_launch: null argument");
     SceneImpl &s = *S(scene);
     FilmImpl &f = *F(film);
-    if (p->width != f.width || p->height != f.height || p->stripe_rows != f.stripe_rows || p->rank != f.rank ||
+    if (p->width != f.geometry.width || p->height != f.geometry.height || p->stripe_rows != f.stripe_rows || p->rank != f.rank ||
         p->world_size != f.world_size || p->device != f.device)
         return fail(RT_ERR_INVALID, "rt_render_launch: params do not match the film's geometry/device");
     if (p->samples_per_pixel < 0 || p->max_depth < 0) return fail(RT_ERR_INVALID, "rt_render_launch: negative spp/depth");
@@ -670,7 +638,7 @@ int rt_render_launch(rt_scene *scene, rt_film *film, const rt_render_params *p)
         set_error(why);
         return rc;
     }
-    f.last_samples = (uint64_t)f.n_pixels * (uint64_t)p->samples_per_pixel;
+    f.last_samples = (uint64_t)f.geometry.n_pixels * (uint64_t)p->samples_per_pixel;
     f.last_variant = p->variant;
     f.last_adaptive = f.adaptive;
     f.rendered = true;
@@ -731,8 +699,8 @@ int rt_render_finish(rt_scene *scene, rt_film *film, rt_render_stats *stats)
         stats->rays = rays;
         stats->seconds_seed = ms_seed * 1e-3;
         stats->seconds_render = ms_render * 1e-3;
-        stats->pixels = f.n_pixels;
-        stats->rows = (uint32_t)f.rows_owned;
+        stats->pixels = f.geometry.n_pixels;
+        stats->rows = (uint32_t)f.geometry.rows_owned;
         stats->kernel_vgprs = (uint32_t)f.last_kernel.vgprs;
         stats->lds_bytes = (uint32_t)f.last_kernel.lds_bytes;
         stats->kernel_kind = (uint32_t)f.last_kernel.kind;
@@ -745,17 +713,9 @@ int rt_film_download(rt_film *film, double *frame_full, int width, int height)
 {
     if (!film || !frame_full) return fail(RT_ERR_INVALID, "rt_film_download: null argument");
     FilmImpl &f = *F(film);
-    if (width != f.width || height != f.height) return fail(RT_ERR_INVALID, "rt_film_download: frame size mismatch");
+    if (width != f.geometry.width || height != f.geometry.height) return fail(RT_ERR_INVALID, "rt_film_download: frame size mismatch");
     if (int rc = select_device(f.device)) return rc;
-    std::vector<double> compact((size_t)f.n_pixels * 3);
-    if (f.n_pixels) HIP_TRY(hipMemcpy(compact.data(), f.pixels, compact.size() * sizeof(double), hipMemcpyDeviceToHost));
-    size_t lr = 0;
-    for (int j = 0; j < height; j++)
-        if ((j / f.stripe_rows) % f.world_size == f.rank) {
-            std::memcpy(frame_full + (size_t)j * width * 3, compact.data() + lr * (size_t)width * 3, sizeof(double) * (size_t)width * 3);
-            lr++;
-        }
-    return RT_OK;
+    return download_rows(f, f.pixels, 3, false, frame_full);
 }
 
 int rt_film_set_adaptive(rt_film *film, const rt_adaptive_params *params)
@@ -774,19 +734,13 @@ int rt_film_download_sample_counts(rt_film *film, uint32_t *counts_full, int wid
 {
     if (!film || !counts_full) return fail(RT_ERR_INVALID, "rt_film_download_sample_counts: null argument");
     FilmImpl &f = *F(film);
-    if (width != f.width || height != f.height) return fail(RT_ERR_INVALID, "rt_film_download_sample_counts: frame size mismatch");
+    if (width != f.geometry.width || height != f.geometry.height) return fail(RT_ERR_INVALID, "rt_film_download_sample_counts: frame size mismatch");
     if (f.in_flight) return fail(RT_ERR_STATE, "rt_film_download_sample_counts: a render is in flight");
     if (int rc = select_device(f.device)) return rc;
-    std::vector<uint32_t> compact((size_t)f.n_pixels, f.rendered ? (uint32_t)f.frame_spp : 0u);
-    if (f.rendered && f.last_adaptive && f.n_pixels)
-        HIP_TRY(hipMemcpy(compact.data(), f.ad_n, compact.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    std::memset(counts_full, 0, (size_t)width * (size_t)height * sizeof(uint32_t));
-    size_t lr = 0;
-    for (int j = 0; j < height; j++)
-        if ((j / f.stripe_rows) % f.world_size == f.rank) {
-            std::memcpy(counts_full + (size_t)j * width, compact.data() + lr * (size_t)width, sizeof(uint32_t) * (size_t)width);
-            lr++;
-        }
+    if (f.rendered && f.last_adaptive) return download_rows(f, f.ad_n, 1, true, counts_full);
+    // without adaptive sampling every owned pixel has had the frame's samples: nothing to fetch
+    const std::vector<uint32_t> compact((size_t)f.geometry.n_pixels, f.rendered ? (uint32_t)f.frame_spp : 0u);
+    scatter_owned_rows(compact.data(), 1, width, height, f.stripe_rows, f.rank, f.world_size, true, counts_full);
     return RT_OK;
 }
 
@@ -794,21 +748,12 @@ int rt_film_download_probe_costs(rt_film *film, uint32_t *costs_full, int width,
 {
     if (!film || !costs_full) return fail(RT_ERR_INVALID, "rt_film_download_probe_costs: null argument");
     FilmImpl &f = *F(film);
-    if (width != f.width || height != f.height) return fail(RT_ERR_INVALID, "rt_film_download_probe_costs: frame size mismatch");
+    if (width != f.geometry.width || height != f.geometry.height) return fail(RT_ERR_INVALID, "rt_film_download_probe_costs: frame size mismatch");
     if (f.in_flight) return fail(RT_ERR_STATE, "rt_film_download_probe_costs: a render is in flight");
     if (!f.rendered || !f.last_plan.pixel_classes || !f.pix_cost)
         return fail(RT_ERR_STATE, "rt_film_download_probe_costs: the film's last launch classified no pixels");
     if (int rc = select_device(f.device)) return rc;
-    std::vector<uint32_t> compact((size_t)f.n_pixels);
-    if (f.n_pixels) HIP_TRY(hipMemcpy(compact.data(), f.pix_cost, compact.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    std::memset(costs_full, 0, (size_t)width * (size_t)height * sizeof(uint32_t));
-    size_t lr = 0;
-    for (int j = 0; j < height; j++)
-        if ((j / f.stripe_rows) % f.world_size == f.rank) {
-            std::memcpy(costs_full + (size_t)j * width, compact.data() + lr * (size_t)width, sizeof(uint32_t) * (size_t)width);
-            lr++;
-        }
-    return RT_OK;
+    return download_rows(f, f.pix_cost, 1, true, costs_full);
 }
 
 int rt_adaptive_converged(const rt_adaptive_params *p, uint32_t n, double sum_r, double sum_g, double sum_b, double sum_y2)
@@ -827,22 +772,21 @@ int rt_adaptive_rule_on_device(int device, int variant, const rt_adaptive_params
         return fail(RT_ERR_INVALID, "rt_adaptive_rule_on_device: bad argument");
     if (count == 0) return RT_OK;
     if (int rc = select_device(device)) return rc;
-    const size_t bytes[5] = {count * sizeof(uint32_t), (size_t)count * 4 * sizeof(double), (size_t)count * 3 * sizeof(double),
-                             count * sizeof(double), (size_t)count};
-    const void *host_in[3] = {n, sums_rgbq, sample_rgb};
-    void *dev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    hipError_t e = hipSuccess;
-    for (int k = 0; k < 5 && e == hipSuccess; k++) e = hipMalloc(&dev[k], bytes[k]);
-    for (int k = 0; k < 3 && e == hipSuccess; k++) e = hipMemcpy(dev[k], host_in[k], bytes[k], hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        e = kBuilds[variant].adaptive_rule(to_rule(*p), count, (const uint32_t *)dev[0], (const double *)dev[1], (const double *)dev[2], (double *)dev[3], (uint8_t *)dev[4], nullptr);
-    }
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = hipMemcpy(q_out, dev[3], bytes[3], hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(stops_out, dev[4], bytes[4], hipMemcpyDeviceToHost);
-    for (void *d : dev)
-        if (d) hipFree(d);
-    return e == hipSuccess ? RT_OK : hip_fail(e, "rt_adaptive_rule_on_device");
+    DeviceArena scratch(device);
+    const uint32_t *d_n = nullptr;
+    const double *d_sums = nullptr, *d_sample = nullptr;
+    double *d_q = nullptr;
+    uint8_t *d_stops = nullptr;
+    HIP_TRY(scratch.upload(n, count, d_n));
+    HIP_TRY(scratch.upload(sums_rgbq, (size_t)count * 4, d_sums));
+    HIP_TRY(scratch.upload(sample_rgb, (size_t)count * 3, d_sample));
+    HIP_TRY(scratch.alloc(count, d_q));
+    HIP_TRY(scratch.alloc(count, d_stops));
+    HIP_TRY(kBuilds[variant].adaptive_rule(to_rule(*p), count, d_n, d_sums, d_sample, d_q, d_stops, nullptr));
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(q_out, d_q, count * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(stops_out, d_stops, count, hipMemcpyDeviceToHost));
+    return RT_OK;
 }
 
 // ---- first-hit feature buffers and the a-trous filter ----
@@ -888,51 +832,35 @@ int rt_film_render_features(rt_scene *scene, rt_film *film, const rt_feature_par
     if (!scene || !film || !p) return fail(RT_ERR_INVALID, "rt_film_render_features: null argument");
     SceneImpl &s = *S(scene);
     FilmImpl &f = *F(film);
-    if (p->width != f.width || p->height != f.height) return fail(RT_ERR_INVALID, "rt_film_render_features: params do not match the film's size");
+    if (p->width != f.geometry.width || p->height != f.geometry.height) return fail(RT_ERR_INVALID, "rt_film_render_features: params do not match the film's size");
     if (p->samples < 0) return fail(RT_ERR_INVALID, "rt_film_render_features: negative samples");
     if (p->variant != 0 && p->variant != 1) return fail(RT_ERR_INVALID, "rt_film_render_features: variant must be 0 (strict) or 1 (fast)");
     if (f.in_flight) return fail(RT_ERR_STATE, "rt_film_render_features: a render of this film is in flight (rt_render_finish it first)");
     if (int rc = rt_scene_upload(scene, f.device)) return rc;
     if (int rc = select_device(f.device)) return rc;
-    const size_t np = f.n_pixels ? f.n_pixels : 1;
-    if (!f.feat_albedo) HIP_TRY(hipMalloc((void **)&f.feat_albedo, np * 3 * sizeof(double)));
-    if (!f.feat_normal) HIP_TRY(hipMalloc((void **)&f.feat_normal, np * 3 * sizeof(double)));
-    if (!f.feat_depth) HIP_TRY(hipMalloc((void **)&f.feat_depth, np * sizeof(double)));
+    const size_t np = f.plane_pixels();
+    if (!f.feat_albedo) HIP_TRY(f.planes.alloc(np * 3, f.feat_albedo));
+    if (!f.feat_normal) HIP_TRY(f.planes.alloc(np * 3, f.feat_normal));
+    if (!f.feat_depth) HIP_TRY(f.planes.alloc(np, f.feat_depth));
     FeatureArgs fa{};
     fa.albedo = f.feat_albedo;
     fa.normal = f.feat_normal;
     fa.depth = f.feat_depth;
     if (int rc = device_jump_table(f.device, &fa.jump_table)) return rc;
     fa.base = xorwow_seed(p->seed, kSaltCurandDevice);
-    fa.n_pixels = f.n_pixels;
-    fa.width = f.width;
-    fa.height = f.height;
+    fa.n_pixels = f.geometry.n_pixels;
+    fa.width = f.geometry.width;
+    fa.height = f.geometry.height;
     fa.samples = p->samples;
     fa.stripe_rows = f.stripe_rows;
     fa.rank = f.rank;
     fa.world_size = f.world_size;
     hipStream_t stream = p->stream ? (hipStream_t)p->stream : f.own_stream;
     const DeviceScene &ds = s.device[f.device]->scene;
-    HIP_TRY(p->variant == 0 ? launch_features_strict(ds, fa, stream) : launch_features_fast(ds, fa, stream));
+    HIP_TRY(kBuilds[p->variant].features(ds, fa, stream));
     HIP_TRY(hipStreamSynchronize(stream));  // the kernel reads the scene's tables: done before the caller may change them
     f.has_features = true;
     f.has_denoised = false;
-    return RT_OK;
-}
-
-// compact rows of `channels` doubles per pixel -> the full frame, rows of other ranks 0
-static int download_plane(const FilmImpl &f, const double *device_plane, int channels, double *full)
-{
-    std::vector<double> compact((size_t)f.n_pixels * channels);
-    if (f.n_pixels) HIP_TRY(hipMemcpy(compact.data(), device_plane, compact.size() * sizeof(double), hipMemcpyDeviceToHost));
-    const size_t row = (size_t)f.width * channels;
-    std::memset(full, 0, row * (size_t)f.height * sizeof(double));
-    size_t lr = 0;
-    for (int j = 0; j < f.height; j++)
-        if ((j / f.stripe_rows) % f.world_size == f.rank) {
-            std::memcpy(full + (size_t)j * row, compact.data() + lr * row, sizeof(double) * row);
-            lr++;
-        }
     return RT_OK;
 }
 
@@ -940,15 +868,15 @@ int rt_film_download_features(rt_film *film, double *albedo_full, double *normal
 {
     if (!film) return fail(RT_ERR_INVALID, "rt_film_download_features: null film");
     FilmImpl &f = *F(film);
-    if (width != f.width || height != f.height) return fail(RT_ERR_INVALID, "rt_film_download_features: frame size mismatch");
+    if (width != f.geometry.width || height != f.geometry.height) return fail(RT_ERR_INVALID, "rt_film_download_features: frame size mismatch");
     if (!f.has_features) return fail(RT_ERR_STATE, "rt_film_download_features: no feature pass has run on this film (rt_film_render_features)");
     if (int rc = select_device(f.device)) return rc;
     if (albedo_full)
-        if (int rc = download_plane(f, f.feat_albedo, 3, albedo_full)) return rc;
+        if (int rc = download_rows(f, f.feat_albedo, 3, true, albedo_full)) return rc;
     if (normal_full)
-        if (int rc = download_plane(f, f.feat_normal, 3, normal_full)) return rc;
+        if (int rc = download_rows(f, f.feat_normal, 3, true, normal_full)) return rc;
     if (depth_full)
-        if (int rc = download_plane(f, f.feat_depth, 1, depth_full)) return rc;
+        if (int rc = download_rows(f, f.feat_depth, 1, true, depth_full)) return rc;
     return RT_OK;
 }
 
@@ -969,11 +897,10 @@ int rt_film_denoise(rt_film *film, const rt_denoise_params *p)
     if (f.in_flight) return fail(RT_ERR_STATE, "rt_film_denoise: a render of this film is in flight (rt_render_finish it first)");
     if (!f.has_features) return fail(RT_ERR_STATE, "rt_film_denoise: no feature pass has run on this film (rt_film_render_features)");
     if (int rc = select_device(f.device)) return rc;
-    const size_t bytes = (size_t)(f.n_pixels ? f.n_pixels : 1) * 3 * sizeof(double);
-    if (!f.denoised) HIP_TRY(hipMalloc((void **)&f.denoised, bytes));
-    if (!f.denoise_tmp && p->iterations > 1) HIP_TRY(hipMalloc((void **)&f.denoise_tmp, bytes));
+    if (!f.denoised) HIP_TRY(f.planes.alloc(f.plane_pixels() * 3, f.denoised));
+    if (!f.denoise_tmp && p->iterations > 1) HIP_TRY(f.planes.alloc(f.plane_pixels() * 3, f.denoise_tmp));
     // (one rank owns every row: the compact planes are the full frame)
-    if (int rc = enqueue_atrous(f.pixels, f.feat_albedo, f.feat_normal, f.feat_depth, f.width, f.height, *p, f.denoised, f.denoise_tmp, f.own_stream))
+    if (int rc = enqueue_atrous(f.pixels, f.feat_albedo, f.feat_normal, f.feat_depth, f.geometry.width, f.geometry.height, *p, f.denoised, f.denoise_tmp, f.own_stream))
         return rc;
     HIP_TRY(hipStreamSynchronize(f.own_stream));
     f.has_denoised = true;
@@ -984,10 +911,10 @@ int rt_film_download_denoised(rt_film *film, double *frame_full, int width, int 
 {
     if (!film || !frame_full) return fail(RT_ERR_INVALID, "rt_film_download_denoised: null argument");
     FilmImpl &f = *F(film);
-    if (width != f.width || height != f.height) return fail(RT_ERR_INVALID, "rt_film_download_denoised: frame size mismatch");
+    if (width != f.geometry.width || height != f.geometry.height) return fail(RT_ERR_INVALID, "rt_film_download_denoised: frame size mismatch");
     if (!f.has_denoised) return fail(RT_ERR_STATE, "rt_film_download_denoised: nothing filtered yet (rt_film_denoise)");
     if (int rc = select_device(f.device)) return rc;
-    return download_plane(f, f.denoised, 3, frame_full);
+    return download_rows(f, f.denoised, 3, true, frame_full);
 }
 
 int rt_denoise_frame(int device, const double *color, const double *albedo, const double *normal, const double *depth, int width,
@@ -998,27 +925,19 @@ int rt_denoise_frame(int device, const double *color, const double *albedo, cons
     if (const char *why = denoise_params_error(p)) return fail(RT_ERR_INVALID, std::string("rt_denoise_frame: ") + why);
     if (int rc = select_device(device)) return rc;
     const size_t n = (size_t)width * (size_t)height;
-    const void *host_in[4] = {color, albedo, normal, depth};
-    const size_t bytes[6] = {n * 3 * sizeof(double), n * 3 * sizeof(double), n * 3 * sizeof(double), n * sizeof(double),
-                             n * 3 * sizeof(double), n * 3 * sizeof(double)};  // colour, albedo, normal, depth, out, tmp
-    void *dev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    hipError_t e = hipSuccess;
-    for (int k = 0; k < 6 && e == hipSuccess; k++) {
-        if (k < 4 && !host_in[k]) continue;
-        if (k == 5 && p->iterations == 1) continue;
-        e = hipMalloc(&dev[k], bytes[k]);
-        if (e == hipSuccess && k < 4) e = hipMemcpy(dev[k], host_in[k], bytes[k], hipMemcpyHostToDevice);
-    }
-    int rc = RT_OK;
-    if (e == hipSuccess)
-        rc = enqueue_atrous((const double *)dev[0], (const double *)dev[1], (const double *)dev[2], (const double *)dev[3], width, height, *p,
-                            (double *)dev[4], (double *)dev[5], nullptr);
-    if (e == hipSuccess && rc == RT_OK) e = hipDeviceSynchronize();
-    if (e == hipSuccess && rc == RT_OK) e = hipMemcpy(out, dev[4], bytes[4], hipMemcpyDeviceToHost);
-    for (void *d : dev)
-        if (d) hipFree(d);
-    if (rc != RT_OK) return rc;
-    return e == hipSuccess ? RT_OK : hip_fail(e, "rt_denoise_frame");
+    DeviceArena scratch(device);
+    const double *d_color = nullptr, *d_albedo = nullptr, *d_normal = nullptr, *d_depth = nullptr;  // a guide not given stays null
+    double *d_out = nullptr, *d_tmp = nullptr;
+    HIP_TRY(scratch.upload(color, n * 3, d_color));
+    if (albedo) HIP_TRY(scratch.upload(albedo, n * 3, d_albedo));
+    if (normal) HIP_TRY(scratch.upload(normal, n * 3, d_normal));
+    if (depth) HIP_TRY(scratch.upload(depth, n, d_depth));
+    HIP_TRY(scratch.alloc(n * 3, d_out));
+    if (p->iterations > 1) HIP_TRY(scratch.alloc(n * 3, d_tmp));
+    if (int rc = enqueue_atrous(d_color, d_albedo, d_normal, d_depth, width, height, *p, d_out, d_tmp, nullptr)) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(out, d_out, n * 3 * sizeof(double), hipMemcpyDeviceToHost));
+    return RT_OK;
 }
 
 // ---- ray queries ----
@@ -1072,7 +991,7 @@ int rt_scene_intersect_device(rt_scene *scene, const rt_query_params *p, const r
     qa.count = (uint32_t)p->count;
     qa.mode = p->mode;
     hipStream_t stream = (hipStream_t)p->stream;
-    auto launch = p->variant == 0 ? launch_query_strict : launch_query_fast;
+    const auto launch = kBuilds[p->variant].query;
     if (!stats) {  // nothing to report: the launch and the wait
         hipError_t e = launch(dt.scene, qa, stream, nullptr);
         // the kernel reads the scene's tables and the caller's arrays: done before either may change
@@ -1084,10 +1003,12 @@ int rt_scene_intersect_device(rt_scene *scene, const rt_query_params *p, const r
     // of one scene may run on several streams at once)
     QueryKernelInfo info{};
     HIP_TRY(launch(dt.scene, qa, stream, &info));
+    DeviceArena scratch(p->device);
+    HIP_TRY(scratch.alloc(1, qa.hit_counter));
+    // from here on the chain: the events are destroyed, and the stream waited for, whatever fails
     hipEvent_t ev[2] = {nullptr, nullptr};
     unsigned long long found = 0;
-    hipError_t e = hipMalloc((void **)&qa.hit_counter, sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipEventCreate(&ev[0]);
+    hipError_t e = hipEventCreate(&ev[0]);
     if (e == hipSuccess) e = hipEventCreate(&ev[1]);
     if (e == hipSuccess) e = hipMemsetAsync(qa.hit_counter, 0, sizeof(unsigned long long), stream);
     if (e == hipSuccess) e = hipEventRecord(ev[0], stream);
@@ -1100,7 +1021,6 @@ int rt_scene_intersect_device(rt_scene *scene, const rt_query_params *p, const r
     if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev[0], ev[1]);
     for (hipEvent_t v : ev)
         if (v) hipEventDestroy(v);
-    if (qa.hit_counter) hipFree(qa.hit_counter);
     if (e != hipSuccess) return hip_fail(e, "rt_scene_intersect_device");
     stats->rays = (uint64_t)p->count;
     stats->hits = found;
@@ -1117,34 +1037,42 @@ int rt_scene_intersect(rt_scene *scene, const rt_query_params *p, const rt_query
     if (p->count == 0) return RT_OK;
     if (int rc = select_device(p->device)) return rc;
     const size_t n = (size_t)p->count;
-    // inputs 0..4 (origin, direction, time, tmin, tmax), outputs 5..12 in the order of rt_query_hits
-    const void *host_in[5] = {rays->origin, rays->direction, rays->time, rays->tmin, rays->tmax};
-    void *host_out[8] = {hits->t, hits->normal, hits->uv, hits->albedo, hits->leaf, hits->front_face, hits->material, hits->occluded};
-    const size_t bytes[13] = {n * 3 * sizeof(double), n * 3 * sizeof(double), n * sizeof(double), n * sizeof(double), n * sizeof(double),
-                              n * sizeof(double), n * 3 * sizeof(double), n * 2 * sizeof(double), n * 3 * sizeof(double), n * sizeof(int32_t),
-                              n, n, n};
-    void *dev[13] = {};
-    hipError_t e = hipSuccess;
-    for (int k = 0; k < 13 && e == hipSuccess; k++) {
-        if (k < 5 ? !host_in[k] : (!host_out[k - 5] || (p->mode == 1 && k != 12))) continue;
-        e = hipMalloc(&dev[k], bytes[k]);
-        if (e == hipSuccess && k < 5) e = hipMemcpy(dev[k], host_in[k], bytes[k], hipMemcpyHostToDevice);
+    DeviceArena scratch(p->device);
+    rt_query_rays dr{};  // the caller's arrays on the device; what the caller left null stays null
+    HIP_TRY(scratch.upload(rays->origin, n * 3, dr.origin));
+    HIP_TRY(scratch.upload(rays->direction, n * 3, dr.direction));
+    if (rays->time) HIP_TRY(scratch.upload(rays->time, n, dr.time));
+    if (rays->tmin) HIP_TRY(scratch.upload(rays->tmin, n, dr.tmin));
+    if (rays->tmax) HIP_TRY(scratch.upload(rays->tmax, n, dr.tmax));
+    rt_query_hits dh{};
+    // `per_ray` values for every output the caller wants; an occlusion query writes `occluded` alone: its other outputs are
+    // neither allocated nor copied
+    auto want = [&](auto *host, auto *&dev, size_t per_ray) { return host ? scratch.alloc(n * per_ray, dev) : hipSuccess; };
+    auto fetch = [&](auto *host, auto *dev, size_t per_ray) {
+        return dev ? hipMemcpy(host, dev, n * per_ray * sizeof *dev, hipMemcpyDeviceToHost) : hipSuccess;
+    };
+    if (p->mode == 0) {
+        HIP_TRY(want(hits->t, dh.t, 1));
+        HIP_TRY(want(hits->normal, dh.normal, 3));
+        HIP_TRY(want(hits->uv, dh.uv, 2));
+        HIP_TRY(want(hits->albedo, dh.albedo, 3));
+        HIP_TRY(want(hits->leaf, dh.leaf, 1));
+        HIP_TRY(want(hits->front_face, dh.front_face, 1));
+        HIP_TRY(want(hits->material, dh.material, 1));
     }
-    int rc = RT_OK;
-    if (e == hipSuccess) {
-        const rt_query_rays dr{(const double *)dev[0], (const double *)dev[1], (const double *)dev[2], (const double *)dev[3], (const double *)dev[4]};
-        const rt_query_hits dh{(double *)dev[5], (double *)dev[6], (double *)dev[7], (double *)dev[8], (int32_t *)dev[9],
-                               (uint8_t *)dev[10], (uint8_t *)dev[11], (uint8_t *)dev[12]};
-        rt_query_params dp = *p;
-        dp.stream = nullptr;  // the copies around the query are synchronous: nothing to order on the caller's stream
-        rc = rt_scene_intersect_device(scene, &dp, &dr, &dh, stats);
-    }
-    for (int k = 5; k < 13 && e == hipSuccess && rc == RT_OK; k++)
-        if (dev[k]) e = hipMemcpy(host_out[k - 5], dev[k], bytes[k], hipMemcpyDeviceToHost);
-    for (void *d : dev)
-        if (d) hipFree(d);
-    if (rc != RT_OK) return rc;
-    return e == hipSuccess ? RT_OK : hip_fail(e, "rt_scene_intersect");
+    HIP_TRY(want(hits->occluded, dh.occluded, 1));
+    rt_query_params dp = *p;
+    dp.stream = nullptr;  // the copies around the query are synchronous: nothing to order on the caller's stream
+    if (int rc = rt_scene_intersect_device(scene, &dp, &dr, &dh, stats)) return rc;
+    HIP_TRY(fetch(hits->t, dh.t, 1));
+    HIP_TRY(fetch(hits->normal, dh.normal, 3));
+    HIP_TRY(fetch(hits->uv, dh.uv, 2));
+    HIP_TRY(fetch(hits->albedo, dh.albedo, 3));
+    HIP_TRY(fetch(hits->leaf, dh.leaf, 1));
+    HIP_TRY(fetch(hits->front_face, dh.front_face, 1));
+    HIP_TRY(fetch(hits->material, dh.material, 1));
+    HIP_TRY(fetch(hits->occluded, dh.occluded, 1));
+    return RT_OK;
 }
 
 void rt_query_abi_sizes(uint32_t out4[4])
