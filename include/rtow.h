@@ -470,6 +470,63 @@ RTOW_API int rt_scene_intersect(rt_scene *s, const rt_query_params *params, cons
 /* sizeof of rt_query_params, rt_query_rays, rt_query_hits, rt_query_stats as this library was compiled (bindings check theirs) */
 RTOW_API void rt_query_abi_sizes(uint32_t out4[4]);
 
+/* ---- radiance queries: path-trace caller-supplied rays ----
+ * Ray k is origin[3k..3k+2] + t * direction[3k..3k+2] at time time[k] (params->time where `time` is NULL), as in the ray queries.
+ * `samples` paths are traced from it, one after the other, all drawing from the ray's one stream.  Sample s is what the
+ * reference's RayColor(ray, world, max_depth, &stream) returns (R/kernel.cu:66-98), as the render kernels compute it: throughput
+ * (1, 1, 1), accumulated (0, 0, 0), depth 0; the world is searched over (0.001, DBL_MAX); a miss adds throughput * background and
+ * ends the path; a hit adds what the material emits and scatters, and the path ends where the material does not scatter or
+ * where ++depth >= max_depth.  The world is searched as the ray queries search it -- the reference's own tree or list in the
+ * reference's order, every table from global memory, never the library's own tree -- so media draw what they draw in a render.
+ * Here every ray draws (scatter directions, Fresnel choices, media): the stream of ray k is rng_state[6k..6k+5] = {d, v0..v4} as
+ * rt_rng_state writes them, or, where rays->rng_state is NULL, curand_init(seed, k + first_sequence, 0) -- always seeded.
+ * Outputs, each only where its pointer is not NULL (not all three may be NULL):
+ *   radiance   (1 / samples) * (((0 + L_1) + L_2) + ...), linear: no gamma, no clamp -- the square root of it is the pixel a
+ *              render of `samples` samples writes for the same rays and streams
+ *   path_rays  world searches (iterations of RayColor's loop) over all samples of the ray, modulo 2^32
+ *   rng_state  the ray's stream after its last draw, to continue it in a later call; may be the array rays->rng_state points to
+ * max_depth == 0: every radiance is 0, nothing is searched, nothing is drawn (the state that goes out is the state that came in).
+ * Both calls return when the results are there (they wait on the stream) and read and write no film.  Parameters are checked
+ * before the device is touched: RT_ERR_STATE before commit; RT_ERR_INVALID for a count below 0 or above 2^30, samples outside
+ * 1 .. 2^20, max_depth < 0, a variant other than 0 / 1, a NULL origin or direction with count > 0, all three outputs NULL.
+ * count == 0 returns RT_OK without a launch.  A ray with a zero or non-finite direction terminates (at most samples * max_depth
+ * bounded searches); its result is unspecified. */
+typedef struct rt_radiance_params {
+    int64_t  count;            /* rays; 0 is allowed (no launch), > 2^30 is RT_ERR_INVALID */
+    int32_t  samples;          /* 1 .. 2^20: paths traced per ray, all from the ray's one stream, one after the other */
+    int32_t  max_depth;        /* >= 0, as rt_render_params.max_depth; 0: black, nothing searched, nothing drawn */
+    double   time;             /* used where rays->time is NULL */
+    uint64_t seed;             /* ray k: curand_init(seed, k + first_sequence, 0), unless rays->rng_state is given */
+    uint64_t first_sequence;
+    int32_t  variant;          /* 0 strict, 1 fast, as for renders */
+    int32_t  device;
+    void    *stream;           /* NULL = the default stream */
+    int32_t  reserved[4];
+} rt_radiance_params;
+typedef struct rt_radiance_rays {
+    const double   *origin, *direction;   /* count x 3 each */
+    const double   *time;                 /* count, or NULL */
+    const uint32_t *rng_state;            /* count x 6 {d, v0..v4} as rt_rng_state writes them, or NULL: seeded as above */
+} rt_radiance_rays;
+typedef struct rt_radiance_out {
+    double   *radiance;        /* count x 3 */
+    uint32_t *path_rays;       /* count */
+    uint32_t *rng_state;       /* count x 6; any pointer may be NULL, not all three */
+} rt_radiance_out;
+typedef struct rt_radiance_stats {
+    uint64_t rays;                          /* the sum of path_rays (counted whether or not path_rays is asked for) */
+    double seconds;                         /* the radiance kernel, HIP events */
+    uint32_t kernel_vgprs, scratch_bytes;   /* of the instantiation that ran: registers, private memory per lane */
+} rt_radiance_stats;
+/* rays and out hold device pointers (on params->device).  stats may be NULL: the call is then the launch and the wait alone. */
+RTOW_API int rt_scene_radiance_device(rt_scene *s, const rt_radiance_params *params, const rt_radiance_rays *rays,
+                                      const rt_radiance_out *out, rt_radiance_stats *stats);
+/* the same on host arrays (uploaded, traced, copied back) */
+RTOW_API int rt_scene_radiance(rt_scene *s, const rt_radiance_params *params, const rt_radiance_rays *rays, const rt_radiance_out *out,
+                               rt_radiance_stats *stats);
+/* sizeof of rt_radiance_params, rt_radiance_rays, rt_radiance_out, rt_radiance_stats as this library was compiled */
+RTOW_API void rt_radiance_abi_sizes(uint32_t out4[4]);
+
 /* Convenience: create film, upload, render 1 GPU, download.  frame = W*H*3 doubles. */
 RTOW_API int rt_render(rt_scene *s, const rt_render_params *params, double *frame, rt_render_stats *stats);
 

@@ -63,6 +63,28 @@ class QueryStats(C.Structure):
                 ("scratch_bytes", C.c_uint32)]
 
 
+class RadianceParams(C.Structure):
+    _fields_ = [("count", C.c_int64), ("samples", C.c_int32), ("max_depth", C.c_int32), ("time", C.c_double), ("seed", C.c_uint64),
+                ("first_sequence", C.c_uint64), ("variant", C.c_int32), ("device", C.c_int32), ("stream", C.c_void_p),
+                ("reserved", C.c_int32 * 4)]
+
+
+class RadianceRays(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("origin", "direction", "time", "rng_state")]
+
+
+# the outputs of a radiance query in the order of rt_radiance_out: name -> (numpy dtype, trailing shape)
+RADIANCE_OUTPUTS = {"radiance": ("float64", (3,)), "path_rays": ("uint32", ()), "rng_state": ("uint32", (6,))}
+
+
+class RadianceOut(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in RADIANCE_OUTPUTS]
+
+
+class RadianceStats(C.Structure):
+    _fields_ = [("rays", C.c_uint64), ("seconds", C.c_double), ("kernel_vgprs", C.c_uint32), ("scratch_bytes", C.c_uint32)]
+
+
 class LaunchPlan(C.Structure):
     """rt_launch_plan: what a launch decides (csrc/launch_plan.h); every scalar field but ray_budget is an int32."""
     _fields_ = [(n, C.c_uint32 if n == "ray_budget" else C.c_int32) for n in (
@@ -168,6 +190,9 @@ SIGNATURES = {
     "rt_scene_intersect_device": (I, [P, C.POINTER(QueryParams), C.POINTER(QueryRays), C.POINTER(QueryHits), C.POINTER(QueryStats)]),
     "rt_scene_intersect": (I, [P, C.POINTER(QueryParams), C.POINTER(QueryRays), C.POINTER(QueryHits), C.POINTER(QueryStats)]),
     "rt_query_abi_sizes": (None, [C.POINTER(C.c_uint32)]),
+    "rt_scene_radiance_device": (I, [P, C.POINTER(RadianceParams), C.POINTER(RadianceRays), C.POINTER(RadianceOut), C.POINTER(RadianceStats)]),
+    "rt_scene_radiance": (I, [P, C.POINTER(RadianceParams), C.POINTER(RadianceRays), C.POINTER(RadianceOut), C.POINTER(RadianceStats)]),
+    "rt_radiance_abi_sizes": (None, [C.POINTER(C.c_uint32)]),
     "rt_deinterleave": (I, [D3, I, I, I, I, C.c_size_t, D3]),
     "rt_render": (I, [P, C.POINTER(RenderParams), D3, C.POINTER(RenderStats)]),
     "rt_write_ppm": (I, [C.c_char_p, D3, I, I]),
@@ -192,5 +217,11 @@ def load():
         fn = getattr(lib, name)  # AttributeError if the library does not export what rtow.h declares
         fn.restype = res
         fn.argtypes = args
+    # the radiance structures as this library was compiled against ours: a mismatch would scribble over the caller's arrays
+    sizes = (C.c_uint32 * 4)()
+    lib.rt_radiance_abi_sizes(sizes)
+    ours = [C.sizeof(x) for x in (RadianceParams, RadianceRays, RadianceOut, RadianceStats)]
+    if list(sizes) != ours:
+        raise ImportError(f"{LIB_PATH}: rt_radiance_* structures are {list(sizes)} bytes in the library, {ours} in the binding")
     _lib = lib
     return lib

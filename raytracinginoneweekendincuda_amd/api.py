@@ -13,7 +13,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import (AdaptiveParams, DenoiseParams, FeatureParams, LaunchPlan, QueryHits, QueryParams, QueryRays, QueryStats,  # noqa: F401
-                   RenderParams, RenderStats, SceneInfo)
+                   RadianceOut, RadianceParams, RadianceRays, RadianceStats, RenderParams, RenderStats, SceneInfo)
 
 
 class RtowError(RuntimeError):
@@ -344,6 +344,87 @@ class Scene:
         out, st = self._query(1, ("occluded",), origins, directions, times, tmin, tmax, time, seed, first_sequence, variant, device, stats)
         hit = out["occluded"] != 0
         return (hit, st) if stats else hit
+
+    # ---- radiance queries (include/rtow.h rt_scene_radiance) ----
+    def radiance(self, origins, directions, times=None, samples=1, max_depth=50, time=0.0, seed=1984, first_sequence=0, rng_state=None,
+                 variant=0, want=("radiance",), device=0, stats=False):
+        """The light that comes back along every ray ``origins[k] + t * directions[k]`` (both (count, 3) float64): ``samples`` paths
+        per ray, each the reference's ``RayColor`` with ``max_depth`` bounces, all from the ray's one stream (include/rtow.h
+        rt_scene_radiance has the rules).  ``times`` may be a (count,) array or None (``time`` for all rays).  ``rng_state`` is a
+        (count, 6) array of 32-bit words, ``Rng.state()`` per ray, or None: ray k then draws from
+        ``curand_init(seed, k + first_sequence, 0)``.  Returns a dict of the outputs named in ``want``: "radiance" (count, 3) float64,
+        linear (no gamma, no clamp); "path_rays" (count,) uint32, the world searches of the ray; "rng_state" (count, 6) uint32, the
+        stream after its last draw.  numpy arrays take the host call and come back as numpy arrays; torch CUDA tensors are read in
+        place, on ``torch.cuda.current_stream()``, and come back as tensors on the same device (``rng_state`` then of dtype uint32 or
+        int32; the output has the input's dtype, uint32 without one).  Other dtypes, shapes and non-contiguous inputs raise RtowError:
+        nothing is converted silently.  ``stats=True``: (outputs, RadianceStats)."""
+        on_gpu = type(origins).__module__.split(".")[0] == "torch"
+        if on_gpu:
+            import torch
+            words = (torch.uint32, torch.int32)
+        else:
+            words = (np.uint32, np.int32)
+
+        def ray_array(name, a, tail, dtypes, what):
+            if on_gpu:
+                if not isinstance(a, torch.Tensor) or not a.is_cuda or a.device != origins.device:
+                    raise RtowError(f"{name}: a CUDA tensor on the device of the origins is required")
+                if a.dtype not in dtypes or not a.is_contiguous():
+                    raise RtowError(f"{name}: a contiguous {what} tensor is required (got {a.dtype}, contiguous={a.is_contiguous()})")
+            else:
+                if not isinstance(a, np.ndarray) or a.dtype not in dtypes or not a.flags.c_contiguous:
+                    raise RtowError(f"{name}: a C-contiguous {what} numpy array is required")
+            if a.ndim != 1 + len(tail) or tuple(a.shape[1:]) != tail:
+                raise RtowError(f"{name}: shape {('count',) + tail} is required, got {tuple(a.shape)}")
+            return a
+
+        if on_gpu and not (isinstance(origins, torch.Tensor) and origins.is_cuda):
+            raise RtowError("origins: torch tensors must live on the GPU (numpy arrays take the host call)")
+        f64 = (torch.float64,) if on_gpu else (np.float64,)
+        origins = ray_array("origins", origins, (3,), f64, "float64")
+        count = int(origins.shape[0])
+        arrays = {"directions": ray_array("directions", directions, (3,), f64, "float64")}
+        if times is not None:
+            arrays["times"] = ray_array("times", times, (), f64, "float64")
+        if rng_state is not None:
+            arrays["rng_state"] = ray_array("rng_state", rng_state, (6,), words, "uint32 (or int32)")
+        for name, a in arrays.items():
+            if int(a.shape[0]) != count:
+                raise RtowError(f"{name}: {int(a.shape[0])} entries for {count} rays")
+        want = tuple(want)
+        unknown = [w for w in want if w not in _lib.RADIANCE_OUTPUTS]
+        if unknown:
+            raise RtowError(f"unknown radiance output {unknown[0]!r} (one of {', '.join(_lib.RADIANCE_OUTPUTS)})")
+        if not want:
+            raise RtowError("want: at least one of " + ", ".join(_lib.RADIANCE_OUTPUTS))
+        if not isinstance(samples, numbers.Integral) or not isinstance(max_depth, numbers.Integral):
+            raise RtowError("samples and max_depth are integers")
+
+        def address(a):
+            return a.data_ptr() if on_gpu else a.ctypes.data
+
+        out = {}
+        for name in want:
+            dtype, tail = _lib.RADIANCE_OUTPUTS[name]
+            shape = (max(count, 1),) + tail   # (never an empty allocation: its address may be null)
+            if on_gpu:
+                kind = rng_state.dtype if name == "rng_state" and rng_state is not None else getattr(torch, dtype)
+                out[name] = torch.empty(shape, dtype=kind, device=origins.device)
+            else:
+                out[name] = np.empty(shape, dtype=dtype)
+        stream = None
+        if on_gpu:
+            device = origins.device.index if origins.device.index is not None else torch.cuda.current_device()
+            stream = torch.cuda.current_stream(origins.device).cuda_stream or None
+        p = RadianceParams(count, int(samples), int(max_depth), float(time), int(seed), int(first_sequence), int(variant), int(device), stream)
+        rays = RadianceRays(address(origins), address(arrays["directions"]),
+                            *(address(arrays[n]) if n in arrays else None for n in ("times", "rng_state")))
+        outs = RadianceOut(**{name: address(a) for name, a in out.items()})
+        st = RadianceStats() if stats else None
+        call = lib().rt_scene_radiance_device if on_gpu else lib().rt_scene_radiance
+        _check(call(self._p, C.byref(p), C.byref(rays), C.byref(outs), C.byref(st) if stats else None))
+        out = {name: a[:count] for name, a in out.items()}
+        return (out, st) if stats else out
 
     # ---- one-call render on one GPU ----
     def render(self, width, height, spp, max_depth=50, seed=1984, variant=0, device=0, flags=0, coop_threshold=0,

@@ -374,10 +374,13 @@ struct Build {
     hipError_t (*adaptive_rule)(const AdaptiveRule &, uint32_t, const uint32_t *, const double *, const double *, double *, uint8_t *, hipStream_t);
     hipError_t (*features)(const DeviceScene &, const FeatureArgs &, hipStream_t);
     hipError_t (*query)(const DeviceScene &, const QueryArgs &, hipStream_t, QueryKernelInfo *);
+    hipError_t (*radiance)(const DeviceScene &, const RadianceArgs &, hipStream_t, QueryKernelInfo *);
 };
 static const Build kBuilds[2] = {
-    {launch_seed_strict, launch_render_strict, kernel_info_strict, launch_adaptive_rule_strict, launch_features_strict, launch_query_strict},
-    {launch_seed_fast, launch_render_fast, kernel_info_fast, launch_adaptive_rule_fast, launch_features_fast, launch_query_fast}};
+    {launch_seed_strict, launch_render_strict, kernel_info_strict, launch_adaptive_rule_strict, launch_features_strict, launch_query_strict,
+     launch_radiance_strict},
+    {launch_seed_fast, launch_render_fast, kernel_info_fast, launch_adaptive_rule_fast, launch_features_fast, launch_query_fast,
+     launch_radiance_fast}};
 
 static int seed_film(FilmImpl &f, const rt_render_params *p, hipStream_t stream)
 {
@@ -1081,6 +1084,119 @@ void rt_query_abi_sizes(uint32_t out4[4])
     out4[1] = (uint32_t)sizeof(rt_query_rays);
     out4[2] = (uint32_t)sizeof(rt_query_hits);
     out4[3] = (uint32_t)sizeof(rt_query_stats);
+}
+
+// ---- radiance queries ----
+// everything that can be refused without a device, in the order include/rtow.h lists it
+static int radiance_check(rt_scene *scene, const rt_radiance_params *p, const rt_radiance_rays *rays, const rt_radiance_out *out, const char *who)
+{
+    const std::string name(who);
+    if (!scene || !p || !rays || !out) return fail(RT_ERR_INVALID, name + ": null argument");
+    if (!S(scene)->committed) return fail(RT_ERR_STATE, name + ": scene not committed (rt_scene_commit)");
+    if (p->count < 0 || p->count > ((int64_t)1 << 30)) return fail(RT_ERR_INVALID, name + ": count must be 0 .. 2^30");
+    if (p->samples < 1 || p->samples > (1 << 20)) return fail(RT_ERR_INVALID, name + ": samples must be 1 .. 2^20");
+    if (p->max_depth < 0) return fail(RT_ERR_INVALID, name + ": max_depth must be >= 0");
+    if (p->variant != 0 && p->variant != 1) return fail(RT_ERR_INVALID, name + ": variant must be 0 (strict) or 1 (fast)");
+    if (p->count > 0 && (!rays->origin || !rays->direction)) return fail(RT_ERR_INVALID, name + ": null origin or direction");
+    if (!out->radiance && !out->path_rays && !out->rng_state) return fail(RT_ERR_INVALID, name + ": every output is null");
+    return RT_OK;
+}
+
+int rt_scene_radiance_device(rt_scene *scene, const rt_radiance_params *p, const rt_radiance_rays *rays, const rt_radiance_out *out,
+                             rt_radiance_stats *stats)
+{
+    if (int rc = radiance_check(scene, p, rays, out, "rt_scene_radiance_device")) return rc;
+    if (stats) *stats = rt_radiance_stats{};
+    if (p->count == 0) return RT_OK;
+    SceneImpl &s = *S(scene);
+    if (int rc = rt_scene_upload(scene, p->device)) return rc;  // (selects the device)
+    DeviceTables &dt = *s.device[p->device];
+    RadianceArgs ra{};
+    ra.origin = rays->origin;
+    ra.direction = rays->direction;
+    ra.time = rays->time;
+    ra.time_all = p->time;
+    ra.rng_in = rays->rng_state;
+    ra.radiance = out->radiance;
+    ra.path_rays = out->path_rays;
+    ra.rng_out = out->rng_state;
+    if (int rc = device_jump_table(p->device, &ra.jump_table)) return rc;
+    ra.base = xorwow_seed(p->seed, kSaltCurandDevice);
+    ra.first_sequence = p->first_sequence;
+    ra.count = (uint32_t)p->count;
+    ra.samples = p->samples;
+    ra.max_depth = p->max_depth;
+    hipStream_t stream = (hipStream_t)p->stream;
+    const auto launch = kBuilds[p->variant].radiance;
+    if (!stats) {  // nothing to report: the launch and the wait
+        hipError_t e = launch(dt.scene, ra, stream, nullptr);
+        // the kernel reads the scene's tables and the caller's arrays: done before either may change
+        const hipError_t waited = hipStreamSynchronize(stream);
+        if (e == hipSuccess) e = waited;
+        return e == hipSuccess ? RT_OK : hip_fail(e, "rt_scene_radiance_device");
+    }
+    // with statistics: the kernel's registers, two events around it, and a word of this call's own for the searches
+    QueryKernelInfo info{};
+    HIP_TRY(launch(dt.scene, ra, stream, &info));
+    DeviceArena scratch(p->device);
+    HIP_TRY(scratch.alloc(1, ra.ray_counter));
+    // from here on the chain: the events are destroyed, and the stream waited for, whatever fails
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    unsigned long long traced = 0;
+    hipError_t e = hipEventCreate(&ev[0]);
+    if (e == hipSuccess) e = hipEventCreate(&ev[1]);
+    if (e == hipSuccess) e = hipMemsetAsync(ra.ray_counter, 0, sizeof(unsigned long long), stream);
+    if (e == hipSuccess) e = hipEventRecord(ev[0], stream);
+    if (e == hipSuccess) e = launch(dt.scene, ra, stream, nullptr);
+    if (e == hipSuccess) e = hipEventRecord(ev[1], stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(&traced, ra.ray_counter, sizeof traced, hipMemcpyDeviceToHost, stream);
+    const hipError_t waited = hipStreamSynchronize(stream);
+    if (e == hipSuccess) e = waited;
+    float ms = 0.0f;
+    if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev[0], ev[1]);
+    for (hipEvent_t v : ev)
+        if (v) hipEventDestroy(v);
+    if (e != hipSuccess) return hip_fail(e, "rt_scene_radiance_device");
+    stats->rays = traced;
+    stats->seconds = (double)ms * 1e-3;
+    stats->kernel_vgprs = (uint32_t)info.vgprs;
+    stats->scratch_bytes = (uint32_t)info.scratch_bytes;
+    return RT_OK;
+}
+
+int rt_scene_radiance(rt_scene *scene, const rt_radiance_params *p, const rt_radiance_rays *rays, const rt_radiance_out *out,
+                      rt_radiance_stats *stats)
+{
+    if (int rc = radiance_check(scene, p, rays, out, "rt_scene_radiance")) return rc;
+    if (stats) *stats = rt_radiance_stats{};
+    if (p->count == 0) return RT_OK;
+    if (int rc = select_device(p->device)) return rc;
+    const size_t n = (size_t)p->count;
+    DeviceArena scratch(p->device);
+    rt_radiance_rays dr{};  // the caller's arrays on the device; what the caller left null stays null
+    HIP_TRY(scratch.upload(rays->origin, n * 3, dr.origin));
+    HIP_TRY(scratch.upload(rays->direction, n * 3, dr.direction));
+    if (rays->time) HIP_TRY(scratch.upload(rays->time, n, dr.time));
+    if (rays->rng_state) HIP_TRY(scratch.upload(rays->rng_state, n * 6, dr.rng_state));
+    rt_radiance_out dout{};
+    if (out->radiance) HIP_TRY(scratch.alloc(n * 3, dout.radiance));
+    if (out->path_rays) HIP_TRY(scratch.alloc(n, dout.path_rays));
+    if (out->rng_state) HIP_TRY(scratch.alloc(n * 6, dout.rng_state));
+    rt_radiance_params dp = *p;
+    dp.stream = nullptr;  // the copies around the query are synchronous: nothing to order on the caller's stream
+    if (int rc = rt_scene_radiance_device(scene, &dp, &dr, &dout, stats)) return rc;
+    if (out->radiance) HIP_TRY(hipMemcpy(out->radiance, dout.radiance, n * 3 * sizeof(double), hipMemcpyDeviceToHost));
+    if (out->path_rays) HIP_TRY(hipMemcpy(out->path_rays, dout.path_rays, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (out->rng_state) HIP_TRY(hipMemcpy(out->rng_state, dout.rng_state, n * 6 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+void rt_radiance_abi_sizes(uint32_t out4[4])
+{
+    out4[0] = (uint32_t)sizeof(rt_radiance_params);
+    out4[1] = (uint32_t)sizeof(rt_radiance_rays);
+    out4[2] = (uint32_t)sizeof(rt_radiance_out);
+    out4[3] = (uint32_t)sizeof(rt_radiance_stats);
 }
 
 int rt_render(rt_scene *scene, const rt_render_params *params, double *frame, rt_render_stats *stats)

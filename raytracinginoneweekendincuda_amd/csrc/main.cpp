@@ -218,6 +218,7 @@ int main(int argc, char **argv)
     std::string raw_output, aov_prefix;
     bool pick = false;           // --pick i,j: what the centre ray of that pixel hits, one line, no render
     int pick_i = 0, pick_j = 0;
+    bool radiance_at = false;    // --radiance-at i,j: the light that comes back along the centre ray of that pixel, one line, no render
     for (int k = 1; k < argc; k++) {
         std::string a = argv[k];
         auto val = [&](const char *name) -> const char * {
@@ -278,6 +279,12 @@ int main(int argc, char **argv)
                 return 2;
             }
             pick = true;
+        } else if (const char *v = val("--radiance-at")) {
+            if (std::sscanf(v, "%d,%d", &pick_i, &pick_j) != 2) {
+                std::fprintf(stderr, "--radiance-at needs a pixel i,j, not '%s'\n", v);
+                return 2;
+            }
+            pick = radiance_at = true;
         }
         else if (const char *v = val("--earth")) earth_path = v;
         else if (const char *v = val("--earth-bytes")) {
@@ -290,9 +297,11 @@ int main(int argc, char **argv)
                          "            [--earth earthmap.jpg|decoded.ppm | --earth-bytes texture.ppm] [--accelerate-lists] [--flags N]\n"
                          "            [--noise T [--min-spp N] [--check-every K] [--samples-map file.pgm]]\n"
                          "            [--denoise [--denoise-iterations N] [--denoise-sigmas c,a,n,z] [--raw-output file.ppm]]\n"
-                         "            [--aov-prefix P] [--feature-samples N] [--pick i,j]\n"
+                         "            [--aov-prefix P] [--feature-samples N] [--pick i,j] [--radiance-at i,j]\n"
                          "  --pick         render nothing: print what the ray through the centre of pixel (i, j) hits (j = 0 is the bottom row) --\n"
                          "                 leaf, material kind, t, point, normal, albedo -- at the shutter's opening, over [0.001, inf)\n"
+                         "  --radiance-at  render nothing: path-trace the same ray, --spp samples (default 1) of --depth bounces from the pixel's stream,\n"
+                         "                 and print the linear radiance, the rays traced and the kernel's time\n"
                          "  --denoise      --output gets the frame after the edge-avoiding a-trous filter (1..8 levels, default 5; sigmas of the colour,\n"
                          "                 albedo, normal and depth edge stops, inf = off), guided by the first hits' albedo, normal and depth;\n"
                          "                 --raw-output: the unfiltered frame beside it\n"
@@ -340,10 +349,11 @@ int main(int argc, char **argv)
         std::fprintf(stderr, "--feature-samples needs N >= 0, --denoise-iterations 1..8, --denoise-sigmas four numbers > 0\n");
         return 2;
     }
+    if (radiance_at && spp < 0) spp = 1;
     if (spp < 0) spp = (scene_id == 9) ? 100 : ((scene_id >= 5 && scene_id <= 8) ? 200 : 10);  // R/kernel.cu:593
 
     if (pick && (pick_i < 0 || pick_i >= width || pick_j < 0 || pick_j >= height)) {
-        std::fprintf(stderr, "--pick: pixel (%d, %d) is outside the %dx%d frame\n", pick_i, pick_j, width, height);
+        std::fprintf(stderr, "%s: pixel (%d, %d) is outside the %dx%d frame\n", radiance_at ? "--radiance-at" : "--pick", pick_i, pick_j, width, height);
         return 2;
     }
     if (!pick) std::fprintf(stderr, "Rendering a %dx%d image with %d samples per pixel in 8x8 blocks.\n", width, height, spp);
@@ -399,6 +409,27 @@ int main(int argc, char **argv)
         for (int a = 0; a < 3; a++) {
             o[a] = cam[3 + a];
             d[a] = ((cam[6 + a] + u * cam[9 + a]) + v * cam[12 + a]) - o[a];
+        }
+        if (radiance_at) {  // one radiance query (rt_scene_radiance) for the same ray, from the pixel's stream
+            rt_radiance_params rp{};
+            rp.count = 1;
+            rp.samples = spp;
+            rp.max_depth = depth;
+            rp.time = cam[25];
+            rp.seed = seed;
+            rp.first_sequence = (unsigned long long)pick_j * (unsigned long long)width + (unsigned long long)pick_i;
+            rp.variant = variant;
+            rp.device = device;
+            const rt_radiance_rays rr{o, d, nullptr, nullptr};
+            double radiance[3];
+            uint32_t path_rays = 0;
+            const rt_radiance_out ro{radiance, &path_rays, nullptr};
+            rt_radiance_stats rs{};
+            if (rt_scene_radiance(scene, &rp, &rr, &ro, &rs) != RT_OK) return die("radiance-at");
+            std::printf("radiance %d,%d: samples %d radiance %.17g %.17g %.17g rays %u seconds %.9g\n", pick_i, pick_j, spp, radiance[0], radiance[1],
+                        radiance[2], (unsigned)path_rays, rs.seconds);
+            rt_scene_destroy(scene);
+            return 0;
         }
         rt_query_params qp{};
         qp.count = 1;

@@ -49,6 +49,9 @@
 #ifndef RT_QUERY  // 1: this translation unit holds the ray-query kernels (query_kernel) and nothing else
 #define RT_QUERY 0
 #endif
+#ifndef RT_RADIANCE  // 1: this translation unit holds the radiance-query kernels (radiance_kernel) and nothing else
+#define RT_RADIANCE 0
+#endif
 
 namespace rtow {
 namespace {
@@ -4156,6 +4159,119 @@ hipError_t RT_CAT(launch_query_, RT_SUFFIX)(const DeviceScene &sc, const QueryAr
     void (*kernel)(DeviceScene, QueryArgs);
     if (sc.world_kind == WORLD_BVH) kernel = a.mode == 0 ? query_kernel<RT_STRICT, TBvhNested, 0> : query_kernel<RT_STRICT, TBvhNested, 1>;
     else kernel = a.mode == 0 ? query_kernel<RT_STRICT, TListNested, 0> : query_kernel<RT_STRICT, TListNested, 1>;
+    if (info) {
+        hipFuncAttributes attr;
+        hipError_t e = hipFuncGetAttributes(&attr, reinterpret_cast<const void *>(kernel));
+        if (e != hipSuccess) return e;
+        info->vgprs = attr.numRegs;
+        info->scratch_bytes = (int)attr.localSizeBytes;
+        return hipSuccess;
+    }
+    if (a.count == 0) return hipSuccess;
+    hipLaunchKernelGGL(kernel, dim3((a.count + 255u) / 256u), dim3(256), 0, stream, sc, a);
+    return hipGetLastError();
+}
+#elif RT_RADIANCE
+// ------------------------------------------------------------------------------------------------
+// Radiance queries (rt_scene_radiance): RayColor (R/kernel.cu:66-98) for caller-supplied rays.  The ray queries' search -- one
+// lane per ray, no LDS, every table from global memory, the reference's tree or list in the reference's order (walk_node /
+// walk_leaves, world_hit_list) -- followed by make_surface and shade, exactly the block of render_kernel at "R/kernel.cu:74-79".
+// One flattened loop: an iteration is one world search and one shade step for every lane still live; a lane whose path ends adds
+// it to its sum and starts its next sample, from the same ray, in the same iteration (render_kernel's path regeneration), and
+// leaves when its last sample is done.  Lanes at different samples and depths so share the search code; a loop over samples
+// around a loop over bounces would idle every lane until the longest path of each round ends.
+// Termination for any ray: at most samples * max_depth iterations, each a bounded search (the ray queries' argument above
+// query_hit_list) and straight-line shading; the rejection loops of shade depend on the stream alone.
+// ------------------------------------------------------------------------------------------------
+template <int STRICT, class T>
+__global__ __launch_bounds__(256) void radiance_kernel(DeviceScene sc, RadianceArgs a)
+{
+    sc.lds_quad_aa = sc.lds_boxes = sc.lds_objects = sc.lds_xforms = sc.lds_media = sc.lds_materials = sc.lds_perlin = kNone;
+    sc.lds_spheres_tab = sc.lds_group_boxes = sc.lds_mspheres = sc.lds_msphere_aux = sc.lds_sphere_aux = kNone;
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t rays = 0;  // world searches of this lane's ray, all samples
+    if (k < a.count) {
+        Ray first;
+        first.o = mk(a.origin[(size_t)k * 3 + 0], a.origin[(size_t)k * 3 + 1], a.origin[(size_t)k * 3 + 2]);
+        first.d = mk(a.direction[(size_t)k * 3 + 0], a.direction[(size_t)k * 3 + 1], a.direction[(size_t)k * 3 + 2]);
+        first.tm = a.time ? a.time[k] : a.time_all;
+        Xorwow rng;
+        if (a.rng_in) {  // {d, v0..v4} as rt_rng_state writes them
+            const uint32_t *w = a.rng_in + (size_t)k * 6;
+            rng.d = w[0]; rng.v0 = w[1]; rng.v1 = w[2]; rng.v2 = w[3]; rng.v3 = w[4]; rng.v4 = w[5];
+        } else {  // curand_init(seed, k + first_sequence, 0)
+            rng = a.base;
+            xorwow_skip_sequences(a.jump_table, a.first_sequence + (uint64_t)k, rng);
+        }
+        const NodeView nv{sc.nodes, 0u, false};
+        Vec sum = mk(0.0, 0.0, 0.0);
+        if (a.max_depth > 0) {  // R/kernel.cu:71: otherwise the bounce loop never runs, RayColor returns black and draws nothing
+            Ray ray = first;
+            Vec throughput = mk(1.0, 1.0, 1.0), accumulated = mk(0.0, 0.0, 0.0);
+            int depth = 0, sample = 0;
+            for (;;) {
+                HitInfo h;
+                h.t = 0.0;
+                h.ref = kNone;
+                h.obj = kNone;
+                bool hit = false;
+                if constexpr (T::WORLD == 0) {
+                    if (sc.n_world_nodes != 0) {
+                        Walk w{};
+                        walk_begin<false>(w, ray, DBL_MAX);
+                        while (w.state != kNone) {
+                            if (walk_moving(w.state)) walk_node<false>(nv, ray, 0.001, w);
+                            else walk_leaves<T>(sc, nv, ray, 0.001, w, h, rng);
+                        }
+                        hit = w.any;
+                    }
+                } else {
+                    hit = world_hit_list<T>(sc, ray, 0.001, DBL_MAX, h, rng);
+                }
+                rays++;
+                bool path_ends;
+                if (!hit) {  // R/kernel.cu:74-79
+                    accumulated = accumulated + throughput * load3c(((const RT_CONST CameraRec *)(uintptr_t)sc.camera)->bg);
+                    path_ends = true;
+                } else {
+                    const Surface s = make_surface<T>(sc, ray, h);
+                    path_ends = !shade<T>(sc, s, ray, throughput, accumulated, rng);
+                    if (!path_ends && ++depth >= a.max_depth) path_ends = true;  // R/kernel.cu:71,97
+                }
+                if (path_ends) {  // R/kernel.cu:143: col += RayColor(...)
+                    sum = sum + accumulated;
+                    if (++sample >= a.samples) break;
+                    ray = first;
+                    throughput = mk(1.0, 1.0, 1.0);
+                    accumulated = mk(0.0, 0.0, 0.0);
+                    depth = 0;
+                }
+            }
+        }
+        if (a.radiance) {  // linear: the mean as a render forms it (R/kernel.cu:150), no gamma
+            const Vec mean = over(sum, (double)a.samples);
+            a.radiance[(size_t)k * 3 + 0] = mean.x;
+            a.radiance[(size_t)k * 3 + 1] = mean.y;
+            a.radiance[(size_t)k * 3 + 2] = mean.z;
+        }
+        if (a.path_rays) a.path_rays[k] = rays;
+        if (a.rng_out) {  // may be the array the state came from: this lane has read its six words
+            uint32_t *w = a.rng_out + (size_t)k * 6;
+            w[0] = rng.d; w[1] = rng.v0; w[2] = rng.v1; w[3] = rng.v2; w[4] = rng.v3; w[5] = rng.v4;
+        }
+    }
+    if (a.ray_counter) {  // one atomic per wave: every lane of the wave is here again
+        unsigned long long total = rays;
+        for (int step = 32; step > 0; step >>= 1) total += __shfl_xor(total, step, 64);
+        if ((threadIdx.x & 63u) == 0 && total) atomicAdd(a.ray_counter, total);
+    }
+}
+
+hipError_t RT_CAT(launch_radiance_, RT_SUFFIX)(const DeviceScene &sc, const RadianceArgs &a, hipStream_t stream, QueryKernelInfo *info)
+{
+    if (a.samples < 1 || a.max_depth < 0 || !a.origin || !a.direction || !(a.radiance || a.path_rays || a.rng_out)) return hipErrorInvalidValue;
+    void (*kernel)(DeviceScene, RadianceArgs) =
+        sc.world_kind == WORLD_BVH ? radiance_kernel<RT_STRICT, TBvhNested> : radiance_kernel<RT_STRICT, TListNested>;
     if (info) {
         hipFuncAttributes attr;
         hipError_t e = hipFuncGetAttributes(&attr, reinterpret_cast<const void *>(kernel));

@@ -158,6 +158,28 @@ struct QueryKernelInfo {
 hipError_t launch_query_strict(const DeviceScene &sc, const QueryArgs &a, hipStream_t stream, QueryKernelInfo *info = nullptr);
 hipError_t launch_query_fast(const DeviceScene &sc, const QueryArgs &a, hipStream_t stream, QueryKernelInfo *info = nullptr);
 
+// Radiance queries (rt_scene_radiance; the RT_RADIANCE objects of render.hip): one lane per caller-supplied ray, `samples` paths
+// from it one after the other -- the search of the ray queries, then make_surface and shade as in render_kernel -- all from the
+// ray's one stream: rng_in[6k..6k+5] = {d, v0..v4} where given, else curand_init(seed, k + first_sequence, 0) in the kernel.
+struct RadianceArgs {
+    const double *origin, *direction;   // count x 3 each
+    const double *time;                 // count, or nullptr: time_all
+    double time_all;
+    const uint32_t *rng_in;             // count x 6, or nullptr: seeded from base
+    double *radiance;                   // count x 3: (1 / samples) * (sum of the samples), linear; may be nullptr
+    uint32_t *path_rays;                // count: world searches over all samples of the ray; may be nullptr
+    uint32_t *rng_out;                  // count x 6: the stream after the last draw; may be nullptr, may be rng_in
+    unsigned long long *ray_counter;    // one word, zeroed by the caller: the sum of path_rays; nullptr: not counted
+    const uint32_t *jump_table;         // kJumpTableWords
+    Xorwow base;                        // salted seed state (sequence 0)
+    uint64_t first_sequence;
+    uint32_t count;
+    int32_t samples, max_depth;
+};
+// info != nullptr: report the instantiation that would run instead of launching it
+hipError_t launch_radiance_strict(const DeviceScene &sc, const RadianceArgs &a, hipStream_t stream, QueryKernelInfo *info = nullptr);
+hipError_t launch_radiance_fast(const DeviceScene &sc, const RadianceArgs &a, hipStream_t stream, QueryKernelInfo *info = nullptr);
+
 // One level of the edge-avoiding a-trous filter (denoise.hip; include/rtow.h rt_denoise_params has the stencil): full-frame
 // planes, `in` and `out` distinct.  A guide that is nullptr switches its term off; inv_* = 1 / sigma^2 (0 for sigma = +inf), the
 // colour's already scaled for the level.
