@@ -154,6 +154,11 @@ RTOW_API int rt_scene_dump_nodes(rt_scene *s, int max_nodes, double *box_out, ui
  * octant the {hit, escape} links (16 x uint16 per node, 0xFFFF = end). */
 RTOW_API int rt_scene_dump_fast_nodes(rt_scene *s, int max_nodes, double *box_out, uint32_t *ab_out, uint16_t *link_out);
 RTOW_API int rt_scene_dump_camera(rt_scene *s, double out27[27]);
+/* The segments of the sphere-list scan over the scene's static spheres (0 segments without any), in list order: first row, row
+ * count (whole trips of eight rows; the last may end in padding) and axis per segment -- 0 x, 1 y, 2 z: every row of the segment
+ * that the fp32 filter decides has shared_out[k] as that centre coordinate, bit for bit, and the scan forms its terms once per ray;
+ * 3: a general segment (shared_out[k] = 0).  The segments tile the rows exactly.  Host only.  Returns the segment count. */
+RTOW_API int rt_scene_dump_scan_segments(rt_scene *s, int max_segments, uint32_t *rows_axis_out, float *shared_out);
 
 /* ---- render (RenderInit + Render, R/kernel.cu:110-154,675-691) ---- */
 typedef struct rt_render_params {

@@ -3,7 +3,9 @@
 Compiles render.hip to gfx950 assembly with the flags csrc/Makefile uses for render_strict.o and render_fast.o, finds every loop
 that runs the packed fp32 filter (v_pk_mul_f32 / v_pk_fma_f32 on scalar rows) and walks one trip of it along the QUIET path -- the
 path of a trip in which no lane passes any sphere -- counting what the wave issues there and how far ahead of its wait every
-scalar load is issued.
+scalar load is issued.  There are two such loops per scan: the GENERAL form (a v_pk_mul_f32 opens every s chain: 7 packed
+instructions per pair of spheres) and the RUN form of a segment whose rows share a centre coordinate (no multiply on a scalar
+row: 5 per pair).  The loop over the segments that holds both is not a trip of either and is left out.
 
 The quiet path is followed by these rules: a ballot compared with zero is zero; the drain test (v_cmp_lt_u32 on the queue count)
 is false; exec is not empty; a conditional branch to the loop's header is taken; any other conditional branch out of the loop is
@@ -58,8 +60,12 @@ def op_of(ln):
     return s.split()[0]
 
 
-def quiet_trip(lines, lo, hi, header):
-    """Walk one trip from the header's label along the quiet path: list of (line index, text, taken?) and notes."""
+SQUARE = re.compile(r"v_pk_fma_f32 v\[\d+:\d+\], (v\[\d+:\d+\]), \1,")  # q = fma(s, s, ...): one per pair of spheres
+
+
+def quiet_trip(lines, lo, hi, header, headers=()):
+    """Walk one trip from the header's label along the quiet path: list of (line index, text, taken?) and notes.  A path that
+    enters another loop of `headers` is the trip of an outer loop: returns (None, notes)."""
     labels = {}
     in_loop = set()
     for i in range(lo, hi):
@@ -78,6 +84,8 @@ def quiet_trip(lines, lo, hi, header):
         m = LABEL.match(ln)
         if m and m.group(1) == header:
             break
+        if m and m.group(1) in headers:
+            return None, [f"enters loop {m.group(1)}"]
         op = op_of(ln)
         if op is None:
             i += 1
@@ -181,16 +189,21 @@ def main():
                 if m and i + 1 < hi and "Loop Header" in " ".join(lines[i:i + 3]):
                     headers.append(m.group(1))
             for header in headers:
-                path, notes = quiet_trip(lines, lo, hi, header)
-                pk_mul = sum(1 for _, s, _ in path if s.startswith("v_pk_mul_f32") and re.search(r"\bs\[\d+:\d+\]", s))
-                if not pk_mul or not any(s.startswith("s_load_dwordx8") for _, s, _ in path):
+                path, notes = quiet_trip(lines, lo, hi, header, headers)
+                if path is None:
                     continue
+                on_rows = sum(1 for _, s, _ in path if s.startswith(("v_pk_mul_f32", "v_pk_fma_f32")) and re.search(r"\bs\[\d+:\d+\]", s))
+                pk_mul = sum(1 for _, s, _ in path if s.startswith("v_pk_mul_f32") and re.search(r"\bs\[\d+:\d+\]", s))
+                pairs = sum(1 for _, s, _ in path if SQUARE.match(s))
+                if not on_rows or not pairs or not any(s.startswith("s_load_dwordx8") for _, s, _ in path):
+                    continue
+                form = "general" if pk_mul else "run"
                 c, other, dist = census(path)
                 regs = next((ln.split()[-1] for ln in lines[lo:hi + 400] if ".amdhsa_next_free_vgpr" in ln), "?")
                 scratch = next((ln.split()[-1] for ln in lines[lo:hi + 400] if ".amdhsa_private_segment_fixed_size" in ln), "?")
                 m = re.search(r"TraitsILi(\d)", name)
-                print(f"\n{build} build, kernel ...Traits<{m.group(1) if m else '?'},...> ({regs} VGPRs, {scratch} B scratch), loop {header}: "
-                      f"{2 * pk_mul} spheres per trip")
+                print(f"\n{build} build, kernel ...Traits<{m.group(1) if m else '?'},...> ({regs} VGPRs, {scratch} B scratch), {form} loop {header}: "
+                      f"{2 * pairs} spheres per trip")
                 print(f"  quiet trip: {c['total']} instructions = {c['filter_valu']} filter VALU + {c['other_valu']} other VALU + {c['salu']} SALU + "
                       f"{c['smem']} SMEM + {c['waits']} waits + {c['nops']} s_nop + {c['branches']} branches ({c['taken']} taken)")
                 for s in other:

@@ -248,6 +248,18 @@ class Scene:
         _check(lib().rt_scene_dump_camera(self._p, out.ctypes.data_as(_lib.D3)))
         return out
 
+    def scan_segments(self):
+        """Tests: the segments of the sphere-list scan in list order (rt_scene_dump_scan_segments; no device needed), as a list of
+        (first_row, n_rows, axis, shared): axis 0 / 1 / 2 and the fp32 centre coordinate every decided row of a run segment
+        shares, or (first_row, n_rows, None, 0.0) for a general segment."""
+        n = lib().rt_scene_dump_scan_segments(self._p, 0, None, None)
+        if n < 0:
+            raise RtowError(_err())
+        rows = np.zeros((max(n, 1), 3), dtype=np.uint32)
+        shared = np.zeros(max(n, 1), dtype=np.float32)
+        lib().rt_scene_dump_scan_segments(self._p, n, rows.ctypes.data_as(C.POINTER(C.c_uint32)), shared.ctypes.data_as(C.POINTER(C.c_float)))
+        return [(int(r[0]), int(r[1]), None if r[2] == 3 else int(r[2]), shared[k]) for k, r in enumerate(rows[:n])]
+
     def plan_launch(self, params, num_cus=256, adaptive=False):
         """Tests: what a launch of this committed scene with these RenderParams decides on a GPU of ``num_cus`` compute units
         -- kernel, LDS, schedule (rt_plan_launch; no device needed).  Returns a dict of the rt_launch_plan fields; the LDS

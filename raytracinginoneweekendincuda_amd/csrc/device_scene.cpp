@@ -209,10 +209,22 @@ int rt_scene_upload(rt_scene *scene, int device)
         release_device_tables(s.device[device]);
         s.device[device] = nullptr;
     }
+    const FlatScene &f = s.flat;
+    {
+        // The packed scan's loop (render.hip scan_filtered32) takes its bounds from the segment records alone: they must tile the
+        // table's trips exactly, in order, and none may be empty -- a loop that ran past its end would read beyond the table.
+        const size_t trips = (f.sphere_scan.size() + 2 * kScanTripPairs - 1) / (2 * kScanTripPairs);
+        size_t at = 0;
+        bool tiled = f.sphere_scan32.size() == scan32_padded_pairs(f.sphere_scan.size());
+        for (const ScanSegment &sg : f.scan_segments) {
+            tiled = tiled && sg.first_trip == at && sg.n_trips > 0 && sg.axis <= kScanAxisNone;
+            at += sg.n_trips;
+        }
+        if (!tiled || at != trips) return fail(RT_ERR_STATE, "rt_scene_upload: the scan segments do not tile the sphere table");
+    }
     DeviceTables *dt = new DeviceTables;
     dt->memory = DeviceArena(device);
     dt->generation = s.generation;
-    const FlatScene &f = s.flat;
     DeviceScene &d = dt->scene;
     hipError_t e = hipSuccess;
     auto up = [&](auto &host, auto &dev) {
@@ -221,6 +233,7 @@ int rt_scene_upload(rt_scene *scene, int device)
     up(f.spheres, d.spheres);
     up(f.sphere_scan, d.sphere_scan);
     up(f.sphere_scan32, d.sphere_scan32);
+    up(f.scan_segments, d.scan_segments);
     up(f.sphere_aux, d.sphere_aux);
     up(f.mspheres, d.mspheres);
     up(f.ms_planes, d.ms_planes);

@@ -45,6 +45,18 @@ static inline constexpr size_t scan32_padded_pairs(size_t n_spheres)
 {
     return (n_spheres + 2 * kScanTripPairs - 1) / (2 * kScanTripPairs) * kScanTripPairs + kScanAheadPairs;
 }
+// The trips of that table in list order, cut into segments (scene_builder.cpp cut_scan_segments).  In a RUN segment every row the
+// filter decides has the bit-same fp32 centre coordinate `c` on `axis`, so the two multiply-adds of the filter that only involve that
+// coordinate are formed once per ray and segment instead of once per row (render.hip filter_pairs<true>).  Rows with k = -inf or
+// +inf fit any run: the run form never reads the shared coordinate from a row.  The rows of a run are stored with their two VARYING
+// coordinates in the cx and cz slots (axis x: cy, cz; axis y: cx, cz; axis z: cx, cy) and the shared one in the cy slot, so one
+// loop body serves the three axes and the kernel only picks the ray's operands per segment.  Table and stride are the general
+// form's: the scan's byte offset runs straight through the segment boundaries.  The segments tile [0, trips) exactly, in order.
+struct ScanSegment { uint32_t first_trip, n_trips, axis; float c; };  // axis 0 x, 1 y, 2 z; kScanAxisNone: a general segment (c = 0)
+constexpr uint32_t kScanAxisNone = 3u;
+// A switch of segments costs the wave about ten instructions and a trip of a run saves eight, so a run pays from two trips on;
+// four leaves a margin and keeps lists that only happen to repeat a coordinate here and there on the one loop they run today.
+constexpr uint32_t kScanRunMinTrips = 4u;
 struct SphereAux { double inv_r; uint32_t mat; uint32_t pad; };
 
 // MovingSphere (R/MovingSphere.h:19-36): centre(t) = c0 + ((t - t0) / dt) * dc
@@ -197,6 +209,7 @@ struct DeviceScene {
     double scan_reach;                 // max over spheres of |centre| + radius (bounds the filter's rounding error)
     const SphereScanPair *sphere_scan32;  // pairs (2 i, 2 i + 1) of the same list
     double scan_reach32;               // max of |centre| + radius over the spheres the fp32 filter decides (the others always pass)
+    const ScanSegment *scan_segments;  // the trips of sphere_scan32 as general and shared-coordinate segments
     const SphereAux *sphere_aux;
     const MSphereGeom *mspheres;
     const SphereAux *msphere_aux;
@@ -240,6 +253,7 @@ struct DeviceScene {
     uint32_t scan_cost;      // what testing every world leaf once costs, in half sphere tests
     uint32_t n_spheres, n_mspheres, n_quads, n_objects, n_boxes, n_xforms;
     uint32_t n_media, n_materials, n_perlin, n_group_boxes;
+    uint32_t n_scan_segments;
     // Tables a leaf test or the shading chases through -- object record -> transforms -> box / quad rows, medium rows,
     // material rows, Perlin tables -- are staged in LDS behind the node rows where they fit.  Byte offsets into the
     // dynamic LDS block, set by the launcher per table; kNone = read the global table.

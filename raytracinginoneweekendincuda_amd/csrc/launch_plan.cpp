@@ -146,6 +146,7 @@ void scene_counts(const FlatScene &f, DeviceScene &d)
     d.n_materials = (uint32_t)f.materials.size();
     d.n_perlin = (uint32_t)f.perlin.size();
     d.n_group_boxes = (uint32_t)f.group_boxes.size();
+    d.n_scan_segments = (uint32_t)f.scan_segments.size();
     d.flags = f.flags;
     apply_layout(LdsLayout{}, d);  // nothing is staged until a launch lays its LDS out
 }

@@ -1789,6 +1789,19 @@ DEV void drain_filtered(const SphereGeom *__restrict__ spheres, uint32_t planes_
 // M / 2r (C2: W = 30, M = 3.4e-3, 4 % of a small sphere's radius).  The behind-the-origin shortcut keeps its form with
 // the fp32 margins (bu > 2^-9 W >> its own error 2^-21 W; bu^2 - disc/a > M).  tests/test_filter_margin.py restates both
 // forms operation by operation.
+// The RUN form (r13; flat_scene.h ScanSegment): over a range of rows whose centres share the fp32 coordinate c on one axis, say y,
+//     s0 = fl(c uy),  l0 = fl(py c + nt)                  once per ray and segment
+//     s = fma(cz, uz, fma(cx, ux, s0)),  Q = fma(s, s, fma(pz, cz, fma(px, cx, l0)))
+// is the general form with its sums taken in another order: the same seven products of the same rounded operands, and the same
+// seven roundings -- three on the way to s (s0 takes the place of the opening product cx ux), four on the way to Q (l0 takes the
+// place of the opening fma on nt) -- each of a partial sum of the same terms.  The bound above never used the order: it charges
+// every rounding 2^-24 of the largest partial sum it can meet, W |u| <= W for s and W^2 + M for the chain of Q (|2 p.C| <= 2 W^2
+// only with all three products in; any subset is no larger than 2 |p| |C|), and s enters Q through s^2 <= W^2 with twice its
+// relative error.  So the run form's error is at most the same 2^-24 (17 W^2 + 5 M), the margin M = 2^-18 W^2, root_m, nthr and
+// `scan_reach32` stay as they are, and c -- the bit-same fp32 value the rows would have held -- is rounded once, on the host, as
+// every centre coordinate is.  Rows with k = -inf / +inf keep zeros for a centre: their s = s0 and Q = s0^2 + l0 are finite (or
+// +inf for a degenerate ray), never NaN, so they pass always / never as in the general form.  tests/test_filter_shared_axis.py
+// restates the run form the same way.
 typedef float v2f __attribute__((ext_vector_type(2)));
 struct ScanRay32 {
     float ux, uy, uz, px, py, pz;  // d / |d|,  2 (o - (o.u) u)
@@ -1848,18 +1861,27 @@ DEV ScanRayPairs scan_ray_pairs(const ScanRay32 &f)
 // A no-op that the two operands which open the filter's chains pass THROUGH.  Placed behind the loads of the other register set
 // it keeps the filter's arithmetic behind those loads (they are volatile and it is an asm volatile: their order holds), so the
 // loads are issued at the head of their half of the trip and not wherever the scheduler drops them among the arithmetic.
-DEV void filter_starts_here(ScanRayPairs &f)
+DEV void filter_starts_here(v2f &opens_s, v2f &opens_q)
 {
-    asm volatile("" : "+v"(f.ux), "+v"(f.nt));
+    asm volatile("" : "+v"(opens_s), "+v"(opens_q));
+}
+// One segment of the table's trips (flat_scene.h ScanSegment), read on the scalar path: one s_load_dwordx4 per segment.
+DEV ScanSegment load_scan_segment(const ScanSegment *table, uint32_t k)
+{
+    const RT_CONST uint32_t *p = (const RT_CONST uint32_t *)(uintptr_t)(table + k);
+    return ScanSegment{p[0], p[1], p[2], __builtin_bit_cast(float, p[3])};
 }
 // Two pairs = four spheres (list positions k0 .. k0 + 3): two packed chains, four compares, one wave-level branch for the four of
 // them, then the survivor path only for the spheres some lane passed (as in filter_four).  `earlier` is the ballot of what the
 // same trip passed before these four; the return value adds these four's to it.  The one branch is taken when either is non-zero,
 // and `after_appends` (the caller's drain test: see scan_filtered32) runs behind that same branch, so a trip in which no lane
 // passed anything executes two compares and two branches not taken for its eight spheres.
-template <class AFTER>
-DEV unsigned long long filter_pairs(const SphereScanPair &g0, const SphereScanPair &g1, uint32_t k0, const ScanRayPairs &f, uint16_t *queue, uint32_t lane,
-                                    uint32_t &count, unsigned long long earlier, AFTER &&after_appends SS_ARG)
+// RUN: the rows of a run segment -- cx and cz slots hold the two varying coordinates, f.ux / f.uz / f.px / f.pz the ray's terms
+// for them, s0 = c u and l0 = fma(p, c, nt) the shared coordinate's share of both chains (scan_filtered32): five packed
+// instructions per pair instead of seven.  Otherwise s0 and l0 are not read.
+template <bool RUN, class AFTER>
+DEV unsigned long long filter_pairs(const SphereScanPair &g0, const SphereScanPair &g1, uint32_t k0, const ScanRayPairs &f, v2f s0, v2f l0, uint16_t *queue,
+                                    uint32_t lane, uint32_t &count, unsigned long long earlier, AFTER &&after_appends SS_ARG)
 {
     const v2f ux = f.ux, uy = f.uy, uz = f.uz, px = f.px, py = f.py, pz = f.pz, nt = f.nt;
     const SphereScanPair *g[2] = {&g0, &g1};
@@ -1867,8 +1889,13 @@ DEV unsigned long long filter_pairs(const SphereScanPair &g0, const SphereScanPa
 #pragma unroll
     for (int h = 0; h < 2; h++) {
         const v2f cx = {g[h]->cx[0], g[h]->cx[1]}, cy = {g[h]->cy[0], g[h]->cy[1]}, cz = {g[h]->cz[0], g[h]->cz[1]};
-        s[h] = __builtin_elementwise_fma(cz, uz, __builtin_elementwise_fma(cy, uy, cx * ux));
-        q[h] = __builtin_elementwise_fma(s[h], s[h], __builtin_elementwise_fma(pz, cz, __builtin_elementwise_fma(py, cy, __builtin_elementwise_fma(px, cx, nt))));
+        if constexpr (RUN) {
+            s[h] = __builtin_elementwise_fma(cz, uz, __builtin_elementwise_fma(cx, ux, s0));
+            q[h] = __builtin_elementwise_fma(s[h], s[h], __builtin_elementwise_fma(pz, cz, __builtin_elementwise_fma(px, cx, l0)));
+        } else {
+            s[h] = __builtin_elementwise_fma(cz, uz, __builtin_elementwise_fma(cy, uy, cx * ux));
+            q[h] = __builtin_elementwise_fma(s[h], s[h], __builtin_elementwise_fma(pz, cz, __builtin_elementwise_fma(py, cy, __builtin_elementwise_fma(px, cx, nt))));
+        }
     }
     const bool p[4] = {q[0].x > g0.k[0], q[0].y > g0.k[1], q[1].x > g1.k[0], q[1].y > g1.k[1]};
     const unsigned long long m[4] = {__ballot(p[0]), __ballot(p[1]), __ballot(p[2]), __ballot(p[3])};  // the compares' own lane masks
@@ -1898,6 +1925,32 @@ DEV unsigned long long filter_pairs(const SphereScanPair &g0, const SphereScanPa
     return all;
 }
 
+// One trip of the packed scan at byte offset `off`, in the general or the run form; the loads, their waits and the branches are the
+// same in both.  `opens_s` / `opens_q` are the operands that open the filter's two chains: s0 and l0 of the run segment, or the
+// ray's own ux and nt in the general form (which filter_pairs<false> reads from `f`).  There they alias members of `f` on purpose:
+// it is what ties filter_starts_here to the very registers the general chains open with.
+template <bool RUN, bool ROWS_IN_LDS>
+DEV void scan_trip(const SphereScanPair *__restrict__ rows, const SphereGeom *__restrict__ spheres, uint32_t &off, uint32_t &end, SphereScanPair &a0,
+                   SphereScanPair &a1, const ScanRayPairs &f, v2f &opens_s, v2f &opens_q, uint32_t planes_off, uint32_t n_padded, uint16_t *queue, uint32_t lane,
+                   uint32_t &count, const Ray &r, double a, double tmin, double &closest, uint32_t &best_k SS_ARG)
+{
+    constexpr uint32_t kPairBytes = (uint32_t)sizeof(SphereScanPair), kTripBytes = kScanTripPairs * kPairBytes;
+    const uint32_t k0 = off / (kPairBytes / 2u);  // sphere index of the trip: used on the survivor path only
+    scan_pairs_arrived(a0, a1);
+    const SphereScanPair b0 = load_scan_pair(rows, off, 2u * kPairBytes), b1 = load_scan_pair(rows, off, 3u * kPairBytes);
+    filter_starts_here(opens_s, opens_q);
+    const unsigned long long passed = filter_pairs<RUN>(a0, a1, k0, f, opens_s, opens_q, queue, lane, count, 0ull, [] {} SS_PASS);
+    scan_pairs_arrived(b0, b1);
+    a0 = load_scan_pair(rows, off, 4u * kPairBytes);  // the next trip's (of whichever segment), or the padding behind the last one
+    a1 = load_scan_pair(rows, off, 5u * kPairBytes);
+    filter_starts_here(opens_s, opens_q);
+    filter_pairs<RUN>(b0, b1, k0 + 4u, f, opens_s, opens_q, queue, lane, count, passed, [&] {
+        if (__any(count > (uint32_t)(kQueueCap - kFilterTrip))) drain_filtered<ROWS_IN_LDS>(spheres, planes_off, n_padded, queue, lane, count, r, a, tmin, closest, best_k SS_PASS);
+    } SS_PASS);
+    off += kTripBytes;
+    asm volatile("" : "+s"(off), "+s"(end));  // the loop's own two registers: every mention weighs against spilling them
+}
+DEV void scan_swap(v2f &a, v2f &b) { const v2f t = a; a = b; b = t; }
 // Pixel-parallel scan through the packed fp32 filter: pairs of sphere rows are wave-uniform (scalar path), four pairs (eight
 // spheres) per trip in two register sets like scan_filtered; the survivors go through drain_filtered, i.e. the reference's test.
 // The table is padded to whole trips with rows that never pass, plus the two pairs the last trip prefetches (kScanTripPairs,
@@ -1914,31 +1967,35 @@ DEV bool scan_filtered32(const DeviceScene &sc, uint32_t planes_off, uint32_t n_
     static_assert(kFilterTrip == 2 * kScanTripPairs && kScanAheadPairs == 2, "one trip = four pairs in two halves; set A of the next trip is read ahead");
     constexpr uint32_t kPairBytes = (uint32_t)sizeof(SphereScanPair), kTripBytes = kScanTripPairs * kPairBytes;
     const SphereScanPair *__restrict__ rows = sc.sphere_scan32;
+    const ScanSegment *__restrict__ segments = sc.scan_segments;
     const SphereGeom *__restrict__ spheres = sc.spheres;
-    uint32_t end = ((sc.n_spheres + (uint32_t)kFilterTrip - 1u) / (uint32_t)kFilterTrip) * kTripBytes;  // bytes of whole trips
+    const uint32_t n_segments = sc.n_scan_segments;  // they tile the table's trips in order (scene_builder.cpp cut_scan_segments)
     const double a = dot(r.d, r.d);
     ScanRayPairs f = scan_ray_pairs(scan_ray32(r, a, sc.scan_reach32));
     double closest = tmax;
     uint32_t best_k = kNone, count = 0;
-    if (end) {
+    if (n_segments) {
         SphereScanPair a0 = load_scan_pair(rows, 0u, 0u), a1 = load_scan_pair(rows, 0u, kPairBytes);
-        uint32_t off = 0;
-        do {
-            const uint32_t k0 = off / (kPairBytes / 2u);  // sphere index of the trip: used on the survivor path only
-            scan_pairs_arrived(a0, a1);
-            const SphereScanPair b0 = load_scan_pair(rows, off, 2u * kPairBytes), b1 = load_scan_pair(rows, off, 3u * kPairBytes);
-            filter_starts_here(f);
-            const unsigned long long passed = filter_pairs(a0, a1, k0, f, queue, lane, count, 0ull, [] {} SS_PASS);
-            scan_pairs_arrived(b0, b1);
-            a0 = load_scan_pair(rows, off, 4u * kPairBytes);  // the next trip's, or the padding behind the last one
-            a1 = load_scan_pair(rows, off, 5u * kPairBytes);
-            filter_starts_here(f);
-            filter_pairs(b0, b1, k0 + 4u, f, queue, lane, count, passed, [&] {
-                if (__any(count > (uint32_t)(kQueueCap - kFilterTrip))) drain_filtered<ROWS_IN_LDS>(spheres, planes_off, n_padded, queue, lane, count, r, a, tmin, closest, best_k SS_PASS);
-            } SS_PASS);
-            off += kTripBytes;
-            asm volatile("" : "+s"(off), "+s"(end));  // the loop's own two registers: every mention weighs against spilling them
-        } while (off != end);
+        uint32_t off = 0, end = 0;
+        for (uint32_t seg = 0; seg != n_segments; seg++) {
+            const ScanSegment sg = load_scan_segment(segments, seg);
+            end = (sg.first_trip + sg.n_trips) * kTripBytes;  // off stands at sg.first_trip * kTripBytes: the segments tile the trips
+            if (sg.axis == kScanAxisNone) {
+                do scan_trip<false, ROWS_IN_LDS>(rows, spheres, off, end, a0, a1, f, f.ux, f.nt, planes_off, n_padded, queue, lane, count, r, a, tmin, closest, best_k SS_PASS);
+                while (off != end);
+            } else {
+                // The ray's terms for the run's two varying coordinates go where the rows keep those (flat_scene.h ScanSegment),
+                // the shared coordinate's to the middle slot, and back behind the run.
+                if (sg.axis == 0u) { scan_swap(f.ux, f.uy); scan_swap(f.px, f.py); }
+                if (sg.axis == 2u) { scan_swap(f.uz, f.uy); scan_swap(f.pz, f.py); }
+                const v2f c = {sg.c, sg.c};
+                v2f s0 = c * f.uy, l0 = __builtin_elementwise_fma(f.py, c, f.nt);  // one rounding each, as in the general form's chains
+                do scan_trip<true, ROWS_IN_LDS>(rows, spheres, off, end, a0, a1, f, s0, l0, planes_off, n_padded, queue, lane, count, r, a, tmin, closest, best_k SS_PASS);
+                while (off != end);
+                if (sg.axis == 0u) { scan_swap(f.ux, f.uy); scan_swap(f.px, f.py); }
+                if (sg.axis == 2u) { scan_swap(f.uz, f.uy); scan_swap(f.pz, f.py); }
+            }
+        }
     }
     drain_filtered<ROWS_IN_LDS>(spheres, planes_off, n_padded, queue, lane, count, r, a, tmin, closest, best_k SS_PASS);
     if (best_k == kNone) return false;

@@ -924,6 +924,74 @@ static void build_fast_tree(FlatScene &f, bool reference_tree_only)
     }
 }
 
+// Cut the trips of sphere_scan32 into segments in list order (flat_scene.h ScanSegment) and store the rows of every run with
+// their varying coordinates in the cx and cz slots.  A run is a maximal range of whole trips whose decided rows (finite k) share
+// one fp32 centre coordinate bit for bit; undecided rows and padding fit any run.  From each trip on, the axis that reaches
+// farthest wins (x before y before z on a tie); a reach below kScanRunMinTrips leaves the trip to a general segment, and no
+// later run could have begun at that trip either, since it would have reached at least as far from there.
+static void cut_scan_segments(FlatScene &f)
+{
+    f.scan_segments.clear();
+    const size_t trips = (f.sphere_scan.size() + 2 * kScanTripPairs - 1) / (2 * kScanTripPairs);
+    struct Shared { bool any, conflict; uint32_t bits; };  // one trip, one axis: the coordinate of its decided rows
+    std::vector<Shared> shared(3 * trips, Shared{false, false, 0u});
+    for (size_t t = 0; t < trips; t++)
+        for (size_t k = 2 * kScanTripPairs * t; k < 2 * kScanTripPairs * (t + 1); k++) {
+            const SphereScanPair &pr = f.sphere_scan32[k / 2];
+            const int h = (int)(k & 1);
+            if (!std::isfinite(pr.k[h])) continue;
+            const float c[3] = {pr.cx[h], pr.cy[h], pr.cz[h]};
+            for (int a = 0; a < 3; a++) {
+                Shared &sh = shared[3 * t + a];
+                uint32_t bits;
+                std::memcpy(&bits, &c[a], sizeof bits);
+                if (sh.any && sh.bits != bits) sh.conflict = true;
+                sh.any = true;
+                sh.bits = bits;
+            }
+        }
+    size_t t = 0;
+    while (t < trips) {
+        size_t best_len = 0;
+        uint32_t best_axis = kScanAxisNone, best_bits = 0u;
+        for (uint32_t a = 0; a < 3; a++) {
+            size_t len = 0;
+            bool have = false;
+            uint32_t bits = 0u;  // a run without a decided row shares +0
+            for (size_t u = t; u < trips; u++, len++) {
+                const Shared &sh = shared[3 * u + a];
+                if (sh.conflict || (sh.any && have && sh.bits != bits)) break;
+                if (sh.any) {
+                    have = true;
+                    bits = sh.bits;
+                }
+            }
+            if (len > best_len) {
+                best_len = len;
+                best_axis = a;
+                best_bits = bits;
+            }
+        }
+        if (best_len >= kScanRunMinTrips) {
+            ScanSegment sg{(uint32_t)t, (uint32_t)best_len, best_axis, 0.0f};
+            std::memcpy(&sg.c, &best_bits, sizeof sg.c);
+            f.scan_segments.push_back(sg);
+            for (size_t p = kScanTripPairs * t; p < kScanTripPairs * (t + best_len); p++) {
+                SphereScanPair &pr = f.sphere_scan32[p];
+                for (int h = 0; h < 2; h++) {
+                    if (best_axis == 0) std::swap(pr.cx[h], pr.cy[h]);
+                    if (best_axis == 2) std::swap(pr.cz[h], pr.cy[h]);
+                }
+            }
+            t += best_len;
+        } else {
+            if (!f.scan_segments.empty() && f.scan_segments.back().axis == kScanAxisNone) f.scan_segments.back().n_trips++;
+            else f.scan_segments.push_back(ScanSegment{(uint32_t)t, 1u, kScanAxisNone, 0.0f});
+            t++;
+        }
+    }
+}
+
 // The segmented walk of a BVH world with composite leaves (flat_scene.h FastOrder / SegMedium): the library's tree over the
 // world's surface leaves, every node with the range of leaf positions below it, and the medium leaves in visiting order.
 static void build_segment_tree(FlatScene &f, bool reference_tree_only)
@@ -1197,6 +1265,7 @@ int flatten_scene(SceneImpl &s)
                 if (decided) f.scan_reach32 = std::max(f.scan_reach32, reach[k]);
             }
             f.scan_reach32 *= 1.0 + 0x1p-20;
+            cut_scan_segments(f);
         }
     }
     {
@@ -1786,6 +1855,23 @@ int rt_scene_dump_camera(rt_scene *s, double out27[27])
     out27[25] = c.time0;
     out27[26] = c.time1;
     return RT_OK;
+}
+
+int rt_scene_dump_scan_segments(rt_scene *s, int max_segments, uint32_t *rows_axis_out, float *shared_out)
+{
+    if (!s || !S(s)->committed) return -fail(RT_ERR_STATE, "rt_scene_dump_scan_segments: scene not committed");
+    const FlatScene &f = S(s)->flat;
+    const int n = (int)f.scan_segments.size();
+    for (int k = 0; k < n && k < max_segments; k++) {
+        const ScanSegment &sg = f.scan_segments[k];
+        if (rows_axis_out) {
+            rows_axis_out[3 * k] = sg.first_trip * 2u * kScanTripPairs;
+            rows_axis_out[3 * k + 1] = sg.n_trips * 2u * kScanTripPairs;
+            rows_axis_out[3 * k + 2] = sg.axis;
+        }
+        if (shared_out) shared_out[k] = sg.c;
+    }
+    return n;
 }
 
 int rt_stripe_rows(int height, int stripe_rows, int rank, int world_size, int *rows_out, int max_rows)

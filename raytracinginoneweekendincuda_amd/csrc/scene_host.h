@@ -66,6 +66,7 @@ struct FlatScene {
     double scan_reach = 0.0;
     std::vector<SphereScanPair> sphere_scan32;  // pairs of sphere_scan rows in fp32
     double scan_reach32 = 0.0;
+    std::vector<ScanSegment> scan_segments;  // tile the trips of sphere_scan32 in order (flat_scene.h ScanSegment)
     std::vector<SphereAux> sphere_aux;
     std::vector<MSphereGeom> mspheres;
     std::vector<double> ms_planes;       // SCENE_WORLD_MSPHERES: seven planes of ms_padded doubles (see DeviceScene)
