@@ -275,66 +275,76 @@ class Scene:
     def upload(self, device=0):
         _check(lib().rt_scene_upload(self._p, device))
 
-    # ---- ray queries (include/rtow.h rt_scene_intersect) ----
-    def _query(self, mode, want, origins, directions, times, tmin, tmax, time, seed, first_sequence, variant, device, stats):
+    # ---- caller-supplied rays: the engine under the ray queries and the radiance queries ----
+    def _ray_batch(self, kind, origins, directions, inputs, outputs, want, calls, structs, stats, device):
+        """One batch of rays through a pair of library entry points, ``calls`` = (on host arrays, on device arrays): numpy arrays
+        take the first, torch CUDA tensors the second, in place and on the current stream.  ``inputs``: the optional per-ray arrays as
+        (name, value, tail shape, dtype names, scalar_ok); None, or a scalar where ``scalar_ok``, leaves the name to the call's
+        parameters.  ``outputs``: the library's table {name: (dtype name, tail shape)} (_lib.*_OUTPUTS), of which ``want`` names
+        those to return.  ``structs(count, rays, outs, device, stream)`` builds the call's three ctypes structs from the addresses
+        of the arrays given and wanted; ``stats``: the statistics struct's type, or None.  Returns ({name: output[:count]}, stats)."""
         on_gpu = type(origins).__module__.split(".")[0] == "torch"
         if on_gpu:
             import torch
 
-        def ray_array(name, a, tail):
-            """A caller's array as the library reads it: float64, C-contiguous, (count,) + tail.  Nothing is converted or copied."""
+        def ray_array(name, a, tail, dtypes=("float64",)):
+            """A caller's array as the library reads it: C-contiguous, (count,) + tail, one of ``dtypes``.  Nothing is converted or copied."""
+            what = dtypes[0] + "".join(f" (or {d})" for d in dtypes[1:])
             if on_gpu:
                 if not isinstance(a, torch.Tensor) or not a.is_cuda or a.device != origins.device:
                     raise RtowError(f"{name}: a CUDA tensor on the device of the origins is required")
-                if a.dtype != torch.float64 or not a.is_contiguous():
-                    raise RtowError(f"{name}: a contiguous float64 tensor is required (got {a.dtype}, contiguous={a.is_contiguous()})")
-            else:
-                if not isinstance(a, np.ndarray) or a.dtype != np.float64 or not a.flags.c_contiguous:
-                    raise RtowError(f"{name}: a C-contiguous float64 numpy array is required")
+                if a.dtype not in [getattr(torch, d) for d in dtypes] or not a.is_contiguous():
+                    raise RtowError(f"{name}: a contiguous {what} tensor is required (got {a.dtype}, contiguous={a.is_contiguous()})")
+            elif not isinstance(a, np.ndarray) or a.dtype not in [np.dtype(d) for d in dtypes] or not a.flags.c_contiguous:
+                raise RtowError(f"{name}: a C-contiguous {what} numpy array is required")
             if a.ndim != 1 + len(tail) or tuple(a.shape[1:]) != tail:
-                raise RtowError(f"{name}: shape (count,{' 3' if tail else ''}) is required, got {tuple(a.shape)}")
+                raise RtowError(f"{name}: shape {('count',) + tail} is required, got {tuple(a.shape)}")
             return a
 
         if on_gpu and not (isinstance(origins, torch.Tensor) and origins.is_cuda):
             raise RtowError("origins: torch tensors must live on the GPU (numpy arrays take the host call)")
-        origins = ray_array("origins", origins, (3,))
+        arrays = {"origins": ray_array("origins", origins, (3,))}
         count = int(origins.shape[0])
-        per_ray = {"directions": (directions, (3,)), "times": (times, ()), "tmin": (tmin, ()), "tmax": (tmax, ())}
-        arrays = {}
-        for name, (a, tail) in per_ray.items():
-            if name != "directions" and (a is None or isinstance(a, numbers.Real) or (isinstance(a, np.ndarray) and a.ndim == 0)):
-                continue   # one value for all rays (a Python or numpy scalar): float() below
-            arrays[name] = ray_array(name, a, tail)
-            if int(arrays[name].shape[0]) != count:
-                raise RtowError(f"{name}: {int(arrays[name].shape[0])} entries for {count} rays")
-        unknown = [w for w in want if w not in _lib.QUERY_OUTPUTS]
+        for name, a, tail, dtypes, scalar_ok in [("directions", directions, (3,), ("float64",), False)] + list(inputs):
+            if name != "directions" and (a is None or (scalar_ok and (isinstance(a, numbers.Real) or (isinstance(a, np.ndarray) and a.ndim == 0)))):
+                continue   # one value for all rays (a Python or numpy scalar), or none: the call's parameters
+            arrays[name] = ray_array(name, a, tail, dtypes)
+            if int(a.shape[0]) != count:
+                raise RtowError(f"{name}: {int(a.shape[0])} entries for {count} rays")
+        unknown = [w for w in want if w not in outputs]
         if unknown:
-            raise RtowError(f"unknown query output {unknown[0]!r} (one of {', '.join(_lib.QUERY_OUTPUTS)})")
+            raise RtowError(f"unknown {kind} output {unknown[0]!r} (one of {', '.join(outputs)})")
 
         def address(a):
             return a.data_ptr() if on_gpu else a.ctypes.data
 
         out = {}
         for name in want:
-            dtype, tail = _lib.QUERY_OUTPUTS[name]
+            dtype, tail = outputs[name]
             shape = (max(count, 1),) + tail   # (never an empty allocation: its address may be null)
-            if on_gpu:
-                out[name] = torch.empty(shape, dtype=getattr(torch, dtype), device=origins.device)
+            if on_gpu:   # (an output that continues an input, rng_state, has the input's dtype)
+                out[name] = torch.empty(shape, dtype=arrays[name].dtype if name in arrays else getattr(torch, dtype), device=origins.device)
             else:
                 out[name] = np.empty(shape, dtype=dtype)
         stream = None
         if on_gpu:
             device = origins.device.index if origins.device.index is not None else torch.cuda.current_device()
             stream = torch.cuda.current_stream(origins.device).cuda_stream or None
-        p = QueryParams(count, float(tmin) if "tmin" not in arrays else 0.0, float(tmax) if "tmax" not in arrays else 0.0,
-                        float(time), int(seed), int(first_sequence), mode, int(variant), int(device), stream)
-        rays = QueryRays(address(origins), address(arrays["directions"]), *(address(arrays[n]) if n in arrays else None
-                                                                           for n in ("times", "tmin", "tmax")))
-        hits = QueryHits(**{name: address(a) for name, a in out.items()})
-        st = QueryStats() if stats else None
-        call = lib().rt_scene_intersect_device if on_gpu else lib().rt_scene_intersect
-        _check(call(self._p, C.byref(p), C.byref(rays), C.byref(hits), C.byref(st) if stats else None))
+        p, rays, outs = structs(count, {n: address(a) for n, a in arrays.items()}, {n: address(a) for n, a in out.items()}, int(device), stream)
+        st = stats() if stats else None
+        _check(calls[on_gpu](self._p, C.byref(p), C.byref(rays), C.byref(outs), C.byref(st) if stats else None))
         return {name: a[:count] for name, a in out.items()}, st
+
+    # ---- ray queries (include/rtow.h rt_scene_intersect) ----
+    def _query(self, mode, want, origins, directions, times, tmin, tmax, time, seed, first_sequence, variant, device, stats):
+        def structs(count, rays, outs, device, stream):
+            p = QueryParams(count, 0.0 if "tmin" in rays else float(tmin), 0.0 if "tmax" in rays else float(tmax), float(time), int(seed),
+                            int(first_sequence), mode, int(variant), device, stream)
+            return p, QueryRays(*(rays.get(n) for n in ("origins", "directions", "times", "tmin", "tmax"))), QueryHits(**outs)
+
+        inputs = [(name, a, (), ("float64",), True) for name, a in (("times", times), ("tmin", tmin), ("tmax", tmax))]
+        return self._ray_batch("query", origins, directions, inputs, _lib.QUERY_OUTPUTS, want, (lib().rt_scene_intersect, lib().rt_scene_intersect_device),
+                               structs, QueryStats if stats else None, device)
 
     def intersect(self, origins, directions, times=None, tmin=0.001, tmax=float("inf"), time=0.0, seed=1984, first_sequence=0,
                   variant=0, want=("t", "normal", "uv", "albedo", "leaf", "front_face", "material"), device=0, stats=False):
@@ -370,72 +380,17 @@ class Scene:
         place, on ``torch.cuda.current_stream()``, and come back as tensors on the same device (``rng_state`` then of dtype uint32 or
         int32; the output has the input's dtype, uint32 without one).  Other dtypes, shapes and non-contiguous inputs raise RtowError:
         nothing is converted silently.  ``stats=True``: (outputs, RadianceStats)."""
-        on_gpu = type(origins).__module__.split(".")[0] == "torch"
-        if on_gpu:
-            import torch
-            words = (torch.uint32, torch.int32)
-        else:
-            words = (np.uint32, np.int32)
+        def structs(count, rays, outs, device, stream):   # (its own refusals after the engine's, as they always came)
+            if not outs:
+                raise RtowError("want: at least one of " + ", ".join(_lib.RADIANCE_OUTPUTS))
+            if not isinstance(samples, numbers.Integral) or not isinstance(max_depth, numbers.Integral):
+                raise RtowError("samples and max_depth are integers")
+            p = RadianceParams(count, int(samples), int(max_depth), float(time), int(seed), int(first_sequence), int(variant), device, stream)
+            return p, RadianceRays(*(rays.get(n) for n in ("origins", "directions", "times", "rng_state"))), RadianceOut(**outs)
 
-        def ray_array(name, a, tail, dtypes, what):
-            if on_gpu:
-                if not isinstance(a, torch.Tensor) or not a.is_cuda or a.device != origins.device:
-                    raise RtowError(f"{name}: a CUDA tensor on the device of the origins is required")
-                if a.dtype not in dtypes or not a.is_contiguous():
-                    raise RtowError(f"{name}: a contiguous {what} tensor is required (got {a.dtype}, contiguous={a.is_contiguous()})")
-            else:
-                if not isinstance(a, np.ndarray) or a.dtype not in dtypes or not a.flags.c_contiguous:
-                    raise RtowError(f"{name}: a C-contiguous {what} numpy array is required")
-            if a.ndim != 1 + len(tail) or tuple(a.shape[1:]) != tail:
-                raise RtowError(f"{name}: shape {('count',) + tail} is required, got {tuple(a.shape)}")
-            return a
-
-        if on_gpu and not (isinstance(origins, torch.Tensor) and origins.is_cuda):
-            raise RtowError("origins: torch tensors must live on the GPU (numpy arrays take the host call)")
-        f64 = (torch.float64,) if on_gpu else (np.float64,)
-        origins = ray_array("origins", origins, (3,), f64, "float64")
-        count = int(origins.shape[0])
-        arrays = {"directions": ray_array("directions", directions, (3,), f64, "float64")}
-        if times is not None:
-            arrays["times"] = ray_array("times", times, (), f64, "float64")
-        if rng_state is not None:
-            arrays["rng_state"] = ray_array("rng_state", rng_state, (6,), words, "uint32 (or int32)")
-        for name, a in arrays.items():
-            if int(a.shape[0]) != count:
-                raise RtowError(f"{name}: {int(a.shape[0])} entries for {count} rays")
-        want = tuple(want)
-        unknown = [w for w in want if w not in _lib.RADIANCE_OUTPUTS]
-        if unknown:
-            raise RtowError(f"unknown radiance output {unknown[0]!r} (one of {', '.join(_lib.RADIANCE_OUTPUTS)})")
-        if not want:
-            raise RtowError("want: at least one of " + ", ".join(_lib.RADIANCE_OUTPUTS))
-        if not isinstance(samples, numbers.Integral) or not isinstance(max_depth, numbers.Integral):
-            raise RtowError("samples and max_depth are integers")
-
-        def address(a):
-            return a.data_ptr() if on_gpu else a.ctypes.data
-
-        out = {}
-        for name in want:
-            dtype, tail = _lib.RADIANCE_OUTPUTS[name]
-            shape = (max(count, 1),) + tail   # (never an empty allocation: its address may be null)
-            if on_gpu:
-                kind = rng_state.dtype if name == "rng_state" and rng_state is not None else getattr(torch, dtype)
-                out[name] = torch.empty(shape, dtype=kind, device=origins.device)
-            else:
-                out[name] = np.empty(shape, dtype=dtype)
-        stream = None
-        if on_gpu:
-            device = origins.device.index if origins.device.index is not None else torch.cuda.current_device()
-            stream = torch.cuda.current_stream(origins.device).cuda_stream or None
-        p = RadianceParams(count, int(samples), int(max_depth), float(time), int(seed), int(first_sequence), int(variant), int(device), stream)
-        rays = RadianceRays(address(origins), address(arrays["directions"]),
-                            *(address(arrays[n]) if n in arrays else None for n in ("times", "rng_state")))
-        outs = RadianceOut(**{name: address(a) for name, a in out.items()})
-        st = RadianceStats() if stats else None
-        call = lib().rt_scene_radiance_device if on_gpu else lib().rt_scene_radiance
-        _check(call(self._p, C.byref(p), C.byref(rays), C.byref(outs), C.byref(st) if stats else None))
-        out = {name: a[:count] for name, a in out.items()}
+        inputs = [("times", times, (), ("float64",), False), ("rng_state", rng_state, (6,), ("uint32", "int32"), False)]
+        out, st = self._ray_batch("radiance", origins, directions, inputs, _lib.RADIANCE_OUTPUTS, tuple(want),
+                                  (lib().rt_scene_radiance, lib().rt_scene_radiance_device), structs, RadianceStats if stats else None, device)
         return (out, st) if stats else out
 
     # ---- one-call render on one GPU ----

@@ -193,6 +193,88 @@ using namespace rtow;
 static inline SceneImpl *S(rt_scene *s) { return reinterpret_cast<SceneImpl *>(s); }
 static inline FilmImpl *F(rt_film *f) { return reinterpret_cast<FilmImpl *>(f); }
 
+// ---- lane-per-ray batches: what the ray queries and the radiance queries below share ----
+// everything both refuse alike without a device, in the order include/rtow.h lists it; `own` answers, between the count and the
+// variant, with the family's refusal of its own parameters (": what is wrong") or nullptr
+template <class Params, class Rays, class Own>
+static int batch_check(rt_scene *scene, const Params *p, const Rays *rays, const void *outputs, const std::string &name, Own own)
+{
+    if (!scene || !p || !rays || !outputs) return fail(RT_ERR_INVALID, name + ": null argument");
+    if (!S(scene)->committed) return fail(RT_ERR_STATE, name + ": scene not committed (rt_scene_commit)");
+    if (p->count < 0 || p->count > ((int64_t)1 << 30)) return fail(RT_ERR_INVALID, name + ": count must be 0 .. 2^30");
+    if (const char *why = own()) return fail(RT_ERR_INVALID, name + why);
+    if (p->variant != 0 && p->variant != 1) return fail(RT_ERR_INVALID, name + ": variant must be 0 (strict) or 1 (fast)");
+    if (p->count > 0 && (!rays->origin || !rays->direction)) return fail(RT_ERR_INVALID, name + ": null origin or direction");
+    return RT_OK;
+}
+
+// Runs a lane-per-ray kernel on `stream` and waits for it: the kernel reads the scene's tables and the caller's arrays, and is
+// done before either may change.  `launch(stream, info)` is the family's launcher on its filled arguments, `*counter` those
+// arguments' counter pointer.  stats == nullptr: the launch and the wait alone; otherwise the time and the kernel's registers go
+// to the members both families' statistics have, the counter's value to `*counted`.
+template <class Launch, class Stats>
+static int run_lane_kernel(Launch launch, unsigned long long **counter, int device, hipStream_t stream, const char *who, Stats *stats,
+                           unsigned long long *counted)
+{
+    if (!stats) {
+        hipError_t e = launch(stream, nullptr);
+        const hipError_t waited = hipStreamSynchronize(stream);
+        if (e == hipSuccess) e = waited;
+        return e == hipSuccess ? RT_OK : hip_fail(e, who);
+    }
+    // with statistics: the kernel's registers, two events around it, and a word of this call's own for the count (batches of one
+    // scene may run on several streams at once)
+    QueryKernelInfo info{};
+    HIP_TRY(launch(stream, &info));
+    DeviceArena scratch(device);
+    HIP_TRY(scratch.alloc(1, *counter));
+    // from here on the chain: the events are destroyed, and the stream waited for, whatever fails
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    hipError_t e = hipEventCreate(&ev[0]);
+    if (e == hipSuccess) e = hipEventCreate(&ev[1]);
+    if (e == hipSuccess) e = hipMemsetAsync(*counter, 0, sizeof(unsigned long long), stream);
+    if (e == hipSuccess) e = hipEventRecord(ev[0], stream);
+    if (e == hipSuccess) e = launch(stream, nullptr);
+    if (e == hipSuccess) e = hipEventRecord(ev[1], stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(counted, *counter, sizeof *counted, hipMemcpyDeviceToHost, stream);
+    const hipError_t waited = hipStreamSynchronize(stream);
+    if (e == hipSuccess) e = waited;
+    float ms = 0.0f;
+    if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev[0], ev[1]);
+    for (hipEvent_t v : ev)
+        if (v) hipEventDestroy(v);
+    if (e != hipSuccess) return hip_fail(e, who);
+    stats->seconds = (double)ms * 1e-3;
+    stats->kernel_vgprs = (uint32_t)info.vgprs;
+    stats->scratch_bytes = (uint32_t)info.scratch_bytes;
+    return RT_OK;
+}
+
+// The host arrays of one batch of `n` rays on the device (rt_scene_intersect, rt_scene_radiance); the copies are synchronous.
+// `dev` comes in null: an input the caller left null, an output the caller does not want, stays so.
+struct Staging {
+    struct Out { void *host; const void *dev; size_t bytes; };
+    DeviceArena arena;
+    size_t n;
+    std::vector<Out> outs;
+    template <class T>
+    hipError_t in(const T *host, size_t per_ray, const T *&dev) { return host ? arena.upload(host, n * per_ray, dev) : hipSuccess; }  // `per_ray` values a ray
+    template <class T>
+    hipError_t out(T *host, size_t per_ray, T *&dev)  // room for them, remembered for fetch()
+    {
+        if (!host) return hipSuccess;
+        const hipError_t e = arena.alloc(n * per_ray, dev);
+        if (e == hipSuccess) outs.push_back(Out{host, dev, n * per_ray * sizeof(T)});
+        return e;
+    }
+    hipError_t fetch() const  // every remembered output back to its host array
+    {
+        hipError_t e = hipSuccess;
+        for (size_t k = 0; k < outs.size() && e == hipSuccess; k++) e = hipMemcpy(outs[k].host, outs[k].dev, outs[k].bytes, hipMemcpyDeviceToHost);
+        return e;
+    }
+};
+
 extern "C" {
 
 int rt_scene_upload(rt_scene *scene, int device)
@@ -961,12 +1043,8 @@ int rt_denoise_frame(int device, const double *color, const double *albedo, cons
 static int query_check(rt_scene *scene, const rt_query_params *p, const rt_query_rays *rays, const rt_query_hits *hits, const char *who)
 {
     const std::string name(who);
-    if (!scene || !p || !rays || !hits) return fail(RT_ERR_INVALID, name + ": null argument");
-    if (!S(scene)->committed) return fail(RT_ERR_STATE, name + ": scene not committed (rt_scene_commit)");
-    if (p->count < 0 || p->count > ((int64_t)1 << 30)) return fail(RT_ERR_INVALID, name + ": count must be 0 .. 2^30");
-    if (p->mode != 0 && p->mode != 1) return fail(RT_ERR_INVALID, name + ": mode must be 0 (closest hit) or 1 (occlusion)");
-    if (p->variant != 0 && p->variant != 1) return fail(RT_ERR_INVALID, name + ": variant must be 0 (strict) or 1 (fast)");
-    if (p->count > 0 && (!rays->origin || !rays->direction)) return fail(RT_ERR_INVALID, name + ": null origin or direction");
+    const auto mode = [&] { return p->mode != 0 && p->mode != 1 ? ": mode must be 0 (closest hit) or 1 (occlusion)" : nullptr; };
+    if (int rc = batch_check(scene, p, rays, hits, name, mode)) return rc;
     if (!rays->tmin && std::isnan(p->tmin)) return fail(RT_ERR_INVALID, name + ": tmin is NaN");
     if (!rays->tmax && !(p->tmax >= (rays->tmin ? p->tmax : p->tmin))) return fail(RT_ERR_INVALID, name + ": tmax < tmin (or NaN)");
     return RT_OK;
@@ -1006,43 +1084,14 @@ int rt_scene_intersect_device(rt_scene *scene, const rt_query_params *p, const r
     qa.first_sequence = p->first_sequence;
     qa.count = (uint32_t)p->count;
     qa.mode = p->mode;
-    hipStream_t stream = (hipStream_t)p->stream;
-    const auto launch = kBuilds[p->variant].query;
-    if (!stats) {  // nothing to report: the launch and the wait
-        hipError_t e = launch(dt.scene, qa, stream, nullptr);
-        // the kernel reads the scene's tables and the caller's arrays: done before either may change
-        const hipError_t waited = hipStreamSynchronize(stream);
-        if (e == hipSuccess) e = waited;
-        return e == hipSuccess ? RT_OK : hip_fail(e, "rt_scene_intersect_device");
-    }
-    // with statistics: the kernel's registers, two events around it, and a word of this call's own for the rays that hit (queries
-    // of one scene may run on several streams at once)
-    QueryKernelInfo info{};
-    HIP_TRY(launch(dt.scene, qa, stream, &info));
-    DeviceArena scratch(p->device);
-    HIP_TRY(scratch.alloc(1, qa.hit_counter));
-    // from here on the chain: the events are destroyed, and the stream waited for, whatever fails
-    hipEvent_t ev[2] = {nullptr, nullptr};
+    // (qa by reference: run_lane_kernel sets qa.hit_counter between the launch that reports and the one that runs)
+    const auto launch = [&](hipStream_t stream, QueryKernelInfo *info) { return kBuilds[p->variant].query(dt.scene, qa, stream, info); };
     unsigned long long found = 0;
-    hipError_t e = hipEventCreate(&ev[0]);
-    if (e == hipSuccess) e = hipEventCreate(&ev[1]);
-    if (e == hipSuccess) e = hipMemsetAsync(qa.hit_counter, 0, sizeof(unsigned long long), stream);
-    if (e == hipSuccess) e = hipEventRecord(ev[0], stream);
-    if (e == hipSuccess) e = launch(dt.scene, qa, stream, nullptr);
-    if (e == hipSuccess) e = hipEventRecord(ev[1], stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(&found, qa.hit_counter, sizeof found, hipMemcpyDeviceToHost, stream);
-    const hipError_t waited = hipStreamSynchronize(stream);
-    if (e == hipSuccess) e = waited;
-    float ms = 0.0f;
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev[0], ev[1]);
-    for (hipEvent_t v : ev)
-        if (v) hipEventDestroy(v);
-    if (e != hipSuccess) return hip_fail(e, "rt_scene_intersect_device");
-    stats->rays = (uint64_t)p->count;
-    stats->hits = found;
-    stats->seconds = (double)ms * 1e-3;
-    stats->kernel_vgprs = (uint32_t)info.vgprs;
-    stats->scratch_bytes = (uint32_t)info.scratch_bytes;
+    if (int rc = run_lane_kernel(launch, &qa.hit_counter, p->device, (hipStream_t)p->stream, "rt_scene_intersect_device", stats, &found)) return rc;
+    if (stats) {
+        stats->rays = (uint64_t)p->count;
+        stats->hits = found;
+    }
     return RT_OK;
 }
 
@@ -1052,42 +1101,28 @@ int rt_scene_intersect(rt_scene *scene, const rt_query_params *p, const rt_query
     if (stats) *stats = rt_query_stats{};
     if (p->count == 0) return RT_OK;
     if (int rc = select_device(p->device)) return rc;
-    const size_t n = (size_t)p->count;
-    DeviceArena scratch(p->device);
-    rt_query_rays dr{};  // the caller's arrays on the device; what the caller left null stays null
-    HIP_TRY(scratch.upload(rays->origin, n * 3, dr.origin));
-    HIP_TRY(scratch.upload(rays->direction, n * 3, dr.direction));
-    if (rays->time) HIP_TRY(scratch.upload(rays->time, n, dr.time));
-    if (rays->tmin) HIP_TRY(scratch.upload(rays->tmin, n, dr.tmin));
-    if (rays->tmax) HIP_TRY(scratch.upload(rays->tmax, n, dr.tmax));
+    Staging stage{DeviceArena(p->device), (size_t)p->count, {}};
+    rt_query_rays dr{};
+    HIP_TRY(stage.in(rays->origin, 3, dr.origin));
+    HIP_TRY(stage.in(rays->direction, 3, dr.direction));
+    HIP_TRY(stage.in(rays->time, 1, dr.time));
+    HIP_TRY(stage.in(rays->tmin, 1, dr.tmin));
+    HIP_TRY(stage.in(rays->tmax, 1, dr.tmax));
     rt_query_hits dh{};
-    // `per_ray` values for every output the caller wants; an occlusion query writes `occluded` alone: its other outputs are
-    // neither allocated nor copied
-    auto want = [&](auto *host, auto *&dev, size_t per_ray) { return host ? scratch.alloc(n * per_ray, dev) : hipSuccess; };
-    auto fetch = [&](auto *host, auto *dev, size_t per_ray) {
-        return dev ? hipMemcpy(host, dev, n * per_ray * sizeof *dev, hipMemcpyDeviceToHost) : hipSuccess;
-    };
-    if (p->mode == 0) {
-        HIP_TRY(want(hits->t, dh.t, 1));
-        HIP_TRY(want(hits->normal, dh.normal, 3));
-        HIP_TRY(want(hits->uv, dh.uv, 2));
-        HIP_TRY(want(hits->albedo, dh.albedo, 3));
-        HIP_TRY(want(hits->leaf, dh.leaf, 1));
-        HIP_TRY(want(hits->front_face, dh.front_face, 1));
-        HIP_TRY(want(hits->material, dh.material, 1));
+    if (p->mode == 0) {  // an occlusion query writes `occluded` alone: its other outputs are neither allocated nor copied
+        HIP_TRY(stage.out(hits->t, 1, dh.t));
+        HIP_TRY(stage.out(hits->normal, 3, dh.normal));
+        HIP_TRY(stage.out(hits->uv, 2, dh.uv));
+        HIP_TRY(stage.out(hits->albedo, 3, dh.albedo));
+        HIP_TRY(stage.out(hits->leaf, 1, dh.leaf));
+        HIP_TRY(stage.out(hits->front_face, 1, dh.front_face));
+        HIP_TRY(stage.out(hits->material, 1, dh.material));
     }
-    HIP_TRY(want(hits->occluded, dh.occluded, 1));
+    HIP_TRY(stage.out(hits->occluded, 1, dh.occluded));
     rt_query_params dp = *p;
     dp.stream = nullptr;  // the copies around the query are synchronous: nothing to order on the caller's stream
     if (int rc = rt_scene_intersect_device(scene, &dp, &dr, &dh, stats)) return rc;
-    HIP_TRY(fetch(hits->t, dh.t, 1));
-    HIP_TRY(fetch(hits->normal, dh.normal, 3));
-    HIP_TRY(fetch(hits->uv, dh.uv, 2));
-    HIP_TRY(fetch(hits->albedo, dh.albedo, 3));
-    HIP_TRY(fetch(hits->leaf, dh.leaf, 1));
-    HIP_TRY(fetch(hits->front_face, dh.front_face, 1));
-    HIP_TRY(fetch(hits->material, dh.material, 1));
-    HIP_TRY(fetch(hits->occluded, dh.occluded, 1));
+    HIP_TRY(stage.fetch());
     return RT_OK;
 }
 
@@ -1104,13 +1139,8 @@ void rt_query_abi_sizes(uint32_t out4[4])
 static int radiance_check(rt_scene *scene, const rt_radiance_params *p, const rt_radiance_rays *rays, const rt_radiance_out *out, const char *who)
 {
     const std::string name(who);
-    if (!scene || !p || !rays || !out) return fail(RT_ERR_INVALID, name + ": null argument");
-    if (!S(scene)->committed) return fail(RT_ERR_STATE, name + ": scene not committed (rt_scene_commit)");
-    if (p->count < 0 || p->count > ((int64_t)1 << 30)) return fail(RT_ERR_INVALID, name + ": count must be 0 .. 2^30");
-    if (p->samples < 1 || p->samples > (1 << 20)) return fail(RT_ERR_INVALID, name + ": samples must be 1 .. 2^20");
-    if (p->max_depth < 0) return fail(RT_ERR_INVALID, name + ": max_depth must be >= 0");
-    if (p->variant != 0 && p->variant != 1) return fail(RT_ERR_INVALID, name + ": variant must be 0 (strict) or 1 (fast)");
-    if (p->count > 0 && (!rays->origin || !rays->direction)) return fail(RT_ERR_INVALID, name + ": null origin or direction");
+    const auto paths = [&] { return p->samples < 1 || p->samples > (1 << 20) ? ": samples must be 1 .. 2^20" : p->max_depth < 0 ? ": max_depth must be >= 0" : nullptr; };
+    if (int rc = batch_check(scene, p, rays, out, name, paths)) return rc;
     if (!out->radiance && !out->path_rays && !out->rng_state) return fail(RT_ERR_INVALID, name + ": every output is null");
     return RT_OK;
 }
@@ -1139,41 +1169,11 @@ int rt_scene_radiance_device(rt_scene *scene, const rt_radiance_params *p, const
     ra.count = (uint32_t)p->count;
     ra.samples = p->samples;
     ra.max_depth = p->max_depth;
-    hipStream_t stream = (hipStream_t)p->stream;
-    const auto launch = kBuilds[p->variant].radiance;
-    if (!stats) {  // nothing to report: the launch and the wait
-        hipError_t e = launch(dt.scene, ra, stream, nullptr);
-        // the kernel reads the scene's tables and the caller's arrays: done before either may change
-        const hipError_t waited = hipStreamSynchronize(stream);
-        if (e == hipSuccess) e = waited;
-        return e == hipSuccess ? RT_OK : hip_fail(e, "rt_scene_radiance_device");
-    }
-    // with statistics: the kernel's registers, two events around it, and a word of this call's own for the searches
-    QueryKernelInfo info{};
-    HIP_TRY(launch(dt.scene, ra, stream, &info));
-    DeviceArena scratch(p->device);
-    HIP_TRY(scratch.alloc(1, ra.ray_counter));
-    // from here on the chain: the events are destroyed, and the stream waited for, whatever fails
-    hipEvent_t ev[2] = {nullptr, nullptr};
+    // (ra by reference: run_lane_kernel sets ra.ray_counter between the launch that reports and the one that runs)
+    const auto launch = [&](hipStream_t stream, QueryKernelInfo *info) { return kBuilds[p->variant].radiance(dt.scene, ra, stream, info); };
     unsigned long long traced = 0;
-    hipError_t e = hipEventCreate(&ev[0]);
-    if (e == hipSuccess) e = hipEventCreate(&ev[1]);
-    if (e == hipSuccess) e = hipMemsetAsync(ra.ray_counter, 0, sizeof(unsigned long long), stream);
-    if (e == hipSuccess) e = hipEventRecord(ev[0], stream);
-    if (e == hipSuccess) e = launch(dt.scene, ra, stream, nullptr);
-    if (e == hipSuccess) e = hipEventRecord(ev[1], stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(&traced, ra.ray_counter, sizeof traced, hipMemcpyDeviceToHost, stream);
-    const hipError_t waited = hipStreamSynchronize(stream);
-    if (e == hipSuccess) e = waited;
-    float ms = 0.0f;
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev[0], ev[1]);
-    for (hipEvent_t v : ev)
-        if (v) hipEventDestroy(v);
-    if (e != hipSuccess) return hip_fail(e, "rt_scene_radiance_device");
-    stats->rays = traced;
-    stats->seconds = (double)ms * 1e-3;
-    stats->kernel_vgprs = (uint32_t)info.vgprs;
-    stats->scratch_bytes = (uint32_t)info.scratch_bytes;
+    if (int rc = run_lane_kernel(launch, &ra.ray_counter, p->device, (hipStream_t)p->stream, "rt_scene_radiance_device", stats, &traced)) return rc;
+    if (stats) stats->rays = traced;
     return RT_OK;
 }
 
@@ -1184,23 +1184,20 @@ int rt_scene_radiance(rt_scene *scene, const rt_radiance_params *p, const rt_rad
     if (stats) *stats = rt_radiance_stats{};
     if (p->count == 0) return RT_OK;
     if (int rc = select_device(p->device)) return rc;
-    const size_t n = (size_t)p->count;
-    DeviceArena scratch(p->device);
-    rt_radiance_rays dr{};  // the caller's arrays on the device; what the caller left null stays null
-    HIP_TRY(scratch.upload(rays->origin, n * 3, dr.origin));
-    HIP_TRY(scratch.upload(rays->direction, n * 3, dr.direction));
-    if (rays->time) HIP_TRY(scratch.upload(rays->time, n, dr.time));
-    if (rays->rng_state) HIP_TRY(scratch.upload(rays->rng_state, n * 6, dr.rng_state));
+    Staging stage{DeviceArena(p->device), (size_t)p->count, {}};
+    rt_radiance_rays dr{};
+    HIP_TRY(stage.in(rays->origin, 3, dr.origin));
+    HIP_TRY(stage.in(rays->direction, 3, dr.direction));
+    HIP_TRY(stage.in(rays->time, 1, dr.time));
+    HIP_TRY(stage.in(rays->rng_state, 6, dr.rng_state));
     rt_radiance_out dout{};
-    if (out->radiance) HIP_TRY(scratch.alloc(n * 3, dout.radiance));
-    if (out->path_rays) HIP_TRY(scratch.alloc(n, dout.path_rays));
-    if (out->rng_state) HIP_TRY(scratch.alloc(n * 6, dout.rng_state));
+    HIP_TRY(stage.out(out->radiance, 3, dout.radiance));
+    HIP_TRY(stage.out(out->path_rays, 1, dout.path_rays));
+    HIP_TRY(stage.out(out->rng_state, 6, dout.rng_state));
     rt_radiance_params dp = *p;
     dp.stream = nullptr;  // the copies around the query are synchronous: nothing to order on the caller's stream
     if (int rc = rt_scene_radiance_device(scene, &dp, &dr, &dout, stats)) return rc;
-    if (out->radiance) HIP_TRY(hipMemcpy(out->radiance, dout.radiance, n * 3 * sizeof(double), hipMemcpyDeviceToHost));
-    if (out->path_rays) HIP_TRY(hipMemcpy(out->path_rays, dout.path_rays, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (out->rng_state) HIP_TRY(hipMemcpy(out->rng_state, dout.rng_state, n * 6 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(stage.fetch());
     return RT_OK;
 }
 

@@ -3918,6 +3918,64 @@ hipError_t RT_CAT(launch_composite_, RT_SUFFIX)(int which, const DeviceScene &sc
 hipError_t RT_CAT(launch_adaptive_prims_, RT_SUFFIX)(int which, const DeviceScene &sc, const RenderArgs &a, hipStream_t stream, KernelInfo *info);
 hipError_t RT_CAT(launch_adaptive_composite_, RT_SUFFIX)(int which, const DeviceScene &sc, const RenderArgs &a, hipStream_t stream, KernelInfo *info);
 
+#if RT_FEATURES || RT_QUERY || RT_RADIANCE
+// ------------------------------------------------------------------------------------------------
+// Shared by the three lane-per-ray sections below (first-hit features, ray queries, radiance queries): one lane per pixel or per
+// caller-supplied ray, no persistent waves, no LDS staging.  The next kernel of this family starts from these.
+// ------------------------------------------------------------------------------------------------
+namespace {
+// every table from global memory: a kernel of this family calls this first
+DEV void global_tables_only(DeviceScene &sc)
+{
+    sc.lds_quad_aa = sc.lds_boxes = sc.lds_objects = sc.lds_xforms = sc.lds_media = sc.lds_materials = sc.lds_perlin = kNone;
+    sc.lds_spheres_tab = sc.lds_group_boxes = sc.lds_mspheres = sc.lds_msphere_aux = sc.lds_sphere_aux = kNone;
+}
+
+// ray k of a caller's arrays, at time[k] or, without that array, at time_all (the feature pass makes its rays itself)
+[[maybe_unused]] DEV Ray caller_ray(const double *origin, const double *direction, const double *time, double time_all, uint32_t k)
+{
+    Ray r;
+    r.o = mk(origin[(size_t)k * 3 + 0], origin[(size_t)k * 3 + 1], origin[(size_t)k * 3 + 2]);
+    r.d = mk(direction[(size_t)k * 3 + 0], direction[(size_t)k * 3 + 1], direction[(size_t)k * 3 + 2]);
+    r.tm = time ? time[k] : time_all;
+    return r;
+}
+
+// the albedo of a first hit (rt_film_render_features, and rt_scene_intersect after it)
+template <class T>
+DEV Vec first_hit_albedo(const DeviceScene &sc, const MatView &mp, uint32_t kind, const Surface &s)
+{
+    if (kind == MAT_METAL) return mp.vec(MAT_OFF(r));
+    if (kind == MAT_DIELECTRIC) return mk(1.0, 1.0, 1.0);
+    return material_texture<T>(sc, mp, mp.u32(MAT_OFF(tex_inline)), s.u, s.v, s.p);  // Lambertian, isotropic, diffuse light
+}
+
+// (not in radiance_kernel: there the helper moves the address arithmetic, and the unit is kept the parent build's to the instruction)
+[[maybe_unused]] DEV void store3(double *out, size_t k, Vec v)
+{
+    out[k * 3 + 0] = v.x;
+    out[k * 3 + 1] = v.y;
+    out[k * 3 + 2] = v.z;
+}
+
+// info != nullptr: report the registers and scratch of the chosen instantiation instead of launching it; else a lane per ray
+template <class Args>
+hipError_t info_or_launch(void (*kernel)(DeviceScene, Args), const DeviceScene &sc, const Args &a, uint32_t count, hipStream_t stream, QueryKernelInfo *info)
+{
+    if (info) {
+        hipFuncAttributes attr;
+        if (hipError_t e = hipFuncGetAttributes(&attr, reinterpret_cast<const void *>(kernel)); e != hipSuccess) return e;
+        info->vgprs = attr.numRegs;
+        info->scratch_bytes = (int)attr.localSizeBytes;
+        return hipSuccess;
+    }
+    if (count == 0) return hipSuccess;
+    hipLaunchKernelGGL(kernel, dim3((count + 255u) / 256u), dim3(256), 0, stream, sc, a);
+    return hipGetLastError();
+}
+}  // namespace
+#endif
+
 #if RT_FEATURES
 // ------------------------------------------------------------------------------------------------
 // First-hit feature pass (rt_film_render_features): albedo, shading normal and depth of the closest hit over [0.001, inf) of
@@ -3944,8 +4002,7 @@ DEV Ray centre_ray(const CameraRec *cam_generic, int i, int j, int width, int he
 template <int STRICT, class T>
 __global__ __launch_bounds__(256) void feature_kernel(DeviceScene sc, FeatureArgs a)
 {
-    sc.lds_quad_aa = sc.lds_boxes = sc.lds_objects = sc.lds_xforms = sc.lds_media = sc.lds_materials = sc.lds_perlin = kNone;
-    sc.lds_spheres_tab = sc.lds_group_boxes = sc.lds_mspheres = sc.lds_msphere_aux = sc.lds_sphere_aux = kNone;
+    global_tables_only(sc);
     const uint32_t local = blockIdx.x * blockDim.x + threadIdx.x;
     if (local >= a.n_pixels) return;
     const int lr = (int)(local / (uint32_t)a.width), i = (int)(local % (uint32_t)a.width);
@@ -3984,10 +4041,7 @@ __global__ __launch_bounds__(256) void feature_kernel(DeviceScene sc, FeatureArg
         } else {
             const Surface s = make_surface<T>(sc, ray, h);
             const MatView mp = material_view<false>(sc, s.mat);
-            const uint32_t kind = mp.u32(MAT_OFF(kind));
-            if (kind == MAT_METAL) value = mp.vec(MAT_OFF(r));
-            else if (kind == MAT_DIELECTRIC) value = mk(1.0, 1.0, 1.0);
-            else value = material_texture<T>(sc, mp, mp.u32(MAT_OFF(tex_inline)), s.u, s.v, s.p);  // Lambertian, isotropic, diffuse light
+            value = first_hit_albedo<T>(sc, mp, mp.u32(MAT_OFF(kind)), s);
             if ((h.ref >> kRefShift) != REF_MEDIUM) sn = s.n;
             sd = h.t * length(ray.d);
         }
@@ -4001,12 +4055,8 @@ __global__ __launch_bounds__(256) void feature_kernel(DeviceScene sc, FeatureArg
         normal = over(normal, (double)n);
         depth = (1 / (double)n) * depth;
     }
-    a.albedo[(size_t)local * 3 + 0] = albedo.x;
-    a.albedo[(size_t)local * 3 + 1] = albedo.y;
-    a.albedo[(size_t)local * 3 + 2] = albedo.z;
-    a.normal[(size_t)local * 3 + 0] = normal.x;
-    a.normal[(size_t)local * 3 + 1] = normal.y;
-    a.normal[(size_t)local * 3 + 2] = normal.z;
+    store3(a.albedo, local, albedo);
+    store3(a.normal, local, normal);
     a.depth[local] = depth;
 }
 
@@ -4022,10 +4072,10 @@ hipError_t RT_CAT(launch_features_, RT_SUFFIX)(const DeviceScene &sc, const Feat
 // ------------------------------------------------------------------------------------------------
 // Ray queries (rt_scene_intersect): closest hit or occlusion for caller-supplied rays.  The feature pass's search once more -- one
 // lane per ray, no LDS, every table from global memory, the reference's tree or list in the reference's order through leaf_test /
-// walk_node -- with the ray, its time and its interval read from the caller's arrays.  The two short outer loops are this
-// section's own copies (world_hit_list, walk_leaves): they note which world leaf produced the winning record and, for an
-// occlusion query of a world without media, stop at the first accepted hit.  The library's own tree is never walked here: it is
-// valid only while hits stay inside their leaves' boxes, which depends on the shutter, and a caller's times are arbitrary.
+// walk_node -- with the ray, its time and its interval read from the caller's arrays.  query_search is that search over this
+// section's copies of the two short outer loops (world_hit_list, walk_leaves), which note the world leaf that produced the winning
+// record and, for an occlusion query of a world without media, stop at the first accepted hit.  The library's own tree is never
+// walked here: valid only while hits stay inside their leaves' boxes, which depends on the shutter; a caller's times are arbitrary.
 // Termination for any ray, degenerate ones included: the list loop runs n_world_items times; every walk_node step either moves
 // to a node with a higher index (n + 1, or an escape link, which always points forward in the preorder array) or parks, a
 // parked lane leaves through the escape link, and the last escape is kNone -- at most two steps per node whatever the box tests
@@ -4073,6 +4123,33 @@ DEV void query_walk_leaves(const DeviceScene &sc, const uint32_t *__restrict__ n
     w.state = next;
 }
 
+// the search over the two loops above: the position of the winning leaf into `leaf`; first: no more than one accepted hit
+template <class T>
+DEV bool query_search(const DeviceScene &sc, const uint32_t *node_leaf_pos, const Ray &ray, double tmin, double tmax, bool first, HitInfo &h,
+                      uint32_t &leaf, Xorwow &rng)
+{
+    h.t = 0.0;
+    h.ref = kNone;
+    h.obj = kNone;
+    if constexpr (T::WORLD == 0) {
+        if (sc.n_world_nodes == 0) return false;
+        const NodeView nv{sc.nodes, 0u, false};
+        Walk w{};
+        walk_begin<false>(w, ray, tmax);
+        while (w.state != kNone) {
+            if (walk_moving(w.state)) {
+                walk_node<false>(nv, ray, tmin, w);
+            } else {
+                query_walk_leaves<T>(sc, node_leaf_pos, ray, tmin, w, h, leaf, rng);
+                if (first && w.any) break;
+            }
+        }
+        return w.any;
+    } else {
+        return query_hit_list<T>(sc, ray, tmin, tmax, first, h, leaf, rng);
+    }
+}
+
 // HitRecord U, V of the primitive that won (R/Sphere.h:44, R/MovingSphere.h:70, R/Quad.h:96-97), in the space the hit was found in
 // as make_surface finds it -- which computes them only for materials that read them
 template <class T>
@@ -4116,14 +4193,10 @@ DEV void query_uv(const DeviceScene &sc, const Ray &r, const HitInfo &h, double 
 template <int STRICT, class T, int MODE>
 __global__ __launch_bounds__(256) void query_kernel(DeviceScene sc, QueryArgs a)
 {
-    sc.lds_quad_aa = sc.lds_boxes = sc.lds_objects = sc.lds_xforms = sc.lds_media = sc.lds_materials = sc.lds_perlin = kNone;
-    sc.lds_spheres_tab = sc.lds_group_boxes = sc.lds_mspheres = sc.lds_msphere_aux = sc.lds_sphere_aux = kNone;
+    global_tables_only(sc);
     const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= a.count) return;
-    Ray ray;
-    ray.o = mk(a.origin[(size_t)k * 3 + 0], a.origin[(size_t)k * 3 + 1], a.origin[(size_t)k * 3 + 2]);
-    ray.d = mk(a.direction[(size_t)k * 3 + 0], a.direction[(size_t)k * 3 + 1], a.direction[(size_t)k * 3 + 2]);
-    ray.tm = a.time ? a.time[k] : a.time_all;
+    const Ray ray = caller_ray(a.origin, a.direction, a.time, a.time_all, k);
     const double tmin = a.tmin ? a.tmin[k] : a.tmin_all;
     const double tmax = fmin(a.tmax ? a.tmax[k] : a.tmax_all, DBL_MAX);  // +inf: DBL_MAX, what a render passes (R/kernel.cu:77)
     const bool media = (sc.flags & SCENE_HAS_MEDIA) != 0;
@@ -4131,29 +4204,8 @@ __global__ __launch_bounds__(256) void query_kernel(DeviceScene sc, QueryArgs a)
     if (media) xorwow_skip_sequences(a.jump_table, a.first_sequence + (uint64_t)k, rng);
     const bool first = MODE == 1 && !media;  // a medium's answer depends on what was found before it: the full search
     HitInfo h;
-    h.t = 0.0;
-    h.ref = kNone;
-    h.obj = kNone;
     uint32_t leaf = kNone;
-    bool hit = false;
-    if constexpr (T::WORLD == 0) {
-        if (sc.n_world_nodes != 0) {
-            const NodeView nv{sc.nodes, 0u, false};
-            Walk w{};
-            walk_begin<false>(w, ray, tmax);
-            while (w.state != kNone) {
-                if (walk_moving(w.state)) {
-                    walk_node<false>(nv, ray, tmin, w);
-                } else {
-                    query_walk_leaves<T>(sc, a.node_leaf_pos, ray, tmin, w, h, leaf, rng);
-                    if (first && w.any) break;
-                }
-            }
-            hit = w.any;
-        }
-    } else {
-        hit = query_hit_list<T>(sc, ray, tmin, tmax, first, h, leaf, rng);
-    }
+    const bool hit = query_search<T>(sc, a.node_leaf_pos, ray, tmin, tmax, first, h, leaf, rng);
     if (a.hit_counter) {
         const unsigned long long found = __ballot(hit);  // one atomic per wave (per group of lanes that arrive together)
         if (hit && (uint32_t)__ffsll((long long)found) - 1u == (threadIdx.x & 63u)) atomicAdd(a.hit_counter, (unsigned long long)__popcll(found));
@@ -4179,31 +4231,19 @@ __global__ __launch_bounds__(256) void query_kernel(DeviceScene sc, QueryArgs a)
                 if (want_material) {
                     const MatView mp = material_view<false>(sc, s.mat);
                     kind = mp.u32(MAT_OFF(kind));
-                    if (a.albedo) {  // the table of rt_film_render_features
-                        if (kind == MAT_METAL) value = mp.vec(MAT_OFF(r));
-                        else if (kind == MAT_DIELECTRIC) value = mk(1.0, 1.0, 1.0);
-                        else value = material_texture<T>(sc, mp, mp.u32(MAT_OFF(tex_inline)), s.u, s.v, s.p);
-                    }
+                    if (a.albedo) value = first_hit_albedo<T>(sc, mp, kind, s);
                 }
             }
         }
         // as the feature pass stores its one sample, 0 + x: no negative zeros
         value = mk(0.0, 0.0, 0.0) + (mk(0.0, 0.0, 0.0) + mk(1.0, 1.0, 1.0) * value);
         normal = mk(0.0, 0.0, 0.0) + normal;
-        if (a.normal) {
-            a.normal[(size_t)k * 3 + 0] = normal.x;
-            a.normal[(size_t)k * 3 + 1] = normal.y;
-            a.normal[(size_t)k * 3 + 2] = normal.z;
-        }
+        if (a.normal) store3(a.normal, k, normal);
         if (a.uv) {
             a.uv[(size_t)k * 2 + 0] = u;
             a.uv[(size_t)k * 2 + 1] = v;
         }
-        if (a.albedo) {
-            a.albedo[(size_t)k * 3 + 0] = value.x;
-            a.albedo[(size_t)k * 3 + 1] = value.y;
-            a.albedo[(size_t)k * 3 + 2] = value.z;
-        }
+        if (a.albedo) store3(a.albedo, k, value);
         if (a.front_face) a.front_face[k] = front ? 1 : 0;
         if (a.material) a.material[k] = (uint8_t)kind;
     }
@@ -4216,17 +4256,7 @@ hipError_t RT_CAT(launch_query_, RT_SUFFIX)(const DeviceScene &sc, const QueryAr
     void (*kernel)(DeviceScene, QueryArgs);
     if (sc.world_kind == WORLD_BVH) kernel = a.mode == 0 ? query_kernel<RT_STRICT, TBvhNested, 0> : query_kernel<RT_STRICT, TBvhNested, 1>;
     else kernel = a.mode == 0 ? query_kernel<RT_STRICT, TListNested, 0> : query_kernel<RT_STRICT, TListNested, 1>;
-    if (info) {
-        hipFuncAttributes attr;
-        hipError_t e = hipFuncGetAttributes(&attr, reinterpret_cast<const void *>(kernel));
-        if (e != hipSuccess) return e;
-        info->vgprs = attr.numRegs;
-        info->scratch_bytes = (int)attr.localSizeBytes;
-        return hipSuccess;
-    }
-    if (a.count == 0) return hipSuccess;
-    hipLaunchKernelGGL(kernel, dim3((a.count + 255u) / 256u), dim3(256), 0, stream, sc, a);
-    return hipGetLastError();
+    return info_or_launch(kernel, sc, a, a.count, stream, info);
 }
 #elif RT_RADIANCE
 // ------------------------------------------------------------------------------------------------
@@ -4243,15 +4273,11 @@ hipError_t RT_CAT(launch_query_, RT_SUFFIX)(const DeviceScene &sc, const QueryAr
 template <int STRICT, class T>
 __global__ __launch_bounds__(256) void radiance_kernel(DeviceScene sc, RadianceArgs a)
 {
-    sc.lds_quad_aa = sc.lds_boxes = sc.lds_objects = sc.lds_xforms = sc.lds_media = sc.lds_materials = sc.lds_perlin = kNone;
-    sc.lds_spheres_tab = sc.lds_group_boxes = sc.lds_mspheres = sc.lds_msphere_aux = sc.lds_sphere_aux = kNone;
+    global_tables_only(sc);
     const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
     uint32_t rays = 0;  // world searches of this lane's ray, all samples
     if (k < a.count) {
-        Ray first;
-        first.o = mk(a.origin[(size_t)k * 3 + 0], a.origin[(size_t)k * 3 + 1], a.origin[(size_t)k * 3 + 2]);
-        first.d = mk(a.direction[(size_t)k * 3 + 0], a.direction[(size_t)k * 3 + 1], a.direction[(size_t)k * 3 + 2]);
-        first.tm = a.time ? a.time[k] : a.time_all;
+        const Ray first = caller_ray(a.origin, a.direction, a.time, a.time_all, k);
         Xorwow rng;
         if (a.rng_in) {  // {d, v0..v4} as rt_rng_state writes them
             const uint32_t *w = a.rng_in + (size_t)k * 6;
@@ -4329,17 +4355,7 @@ hipError_t RT_CAT(launch_radiance_, RT_SUFFIX)(const DeviceScene &sc, const Radi
     if (a.samples < 1 || a.max_depth < 0 || !a.origin || !a.direction || !(a.radiance || a.path_rays || a.rng_out)) return hipErrorInvalidValue;
     void (*kernel)(DeviceScene, RadianceArgs) =
         sc.world_kind == WORLD_BVH ? radiance_kernel<RT_STRICT, TBvhNested> : radiance_kernel<RT_STRICT, TListNested>;
-    if (info) {
-        hipFuncAttributes attr;
-        hipError_t e = hipFuncGetAttributes(&attr, reinterpret_cast<const void *>(kernel));
-        if (e != hipSuccess) return e;
-        info->vgprs = attr.numRegs;
-        info->scratch_bytes = (int)attr.localSizeBytes;
-        return hipSuccess;
-    }
-    if (a.count == 0) return hipSuccess;
-    hipLaunchKernelGGL(kernel, dim3((a.count + 255u) / 256u), dim3(256), 0, stream, sc, a);
-    return hipGetLastError();
+    return info_or_launch(kernel, sc, a, a.count, stream, info);
 }
 #elif RT_GROUP == 1
 namespace {

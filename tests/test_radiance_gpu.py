@@ -406,6 +406,21 @@ def test_each_output_alone_is_that_output_among_all(name):
     assert same(scene.radiance(o, d, times=tm, rng_state=states, want=ALL), whole), "... and without statistics"
 
 
+@pytest.mark.parametrize("name", ["mixed bvh", "mixed list"])
+def test_statistics_count_the_searches_and_leave_the_outputs_alone(name):
+    """A call with statistics (two events and a counter word around the kernel) against the plain launch: the same outputs bit for
+    bit.  100 rays are one full wave and a ragged one for the count's reduction over each wave."""
+    scene = scene_of(name)
+    o, d, time0, _ = centre_rays(scene)
+    o, d = o[:100].copy(), d[:100].copy()
+    plain = scene.radiance(o, d, time=time0, samples=2, variant=0, want=ALL)
+    counted, st = scene.radiance(o, d, time=time0, samples=2, variant=0, want=ALL, stats=True)
+    print(f"{name}: {st.rays} searches for 100 rays x 2 samples, {st.kernel_vgprs} VGPRs, {st.seconds * 1e3:.3f} ms")
+    assert same(counted, plain)
+    assert st.rays == plain["path_rays"].sum(dtype=np.uint64) and st.rays >= 200
+    assert st.kernel_vgprs > 0 and st.seconds > 0
+
+
 def test_torch_tensors_are_read_in_place_and_leave_films_alone():
     name = "scene 7 bvh"
     scene = scene_of(name)

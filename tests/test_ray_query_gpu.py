@@ -460,6 +460,24 @@ def test_batch_edges_write_exactly_their_rays(count):
 
 
 @pytest.mark.parametrize("name", ["mixed bvh", "mixed list"])
+def test_statistics_count_the_hits_and_leave_the_outputs_alone(name):
+    """The closest-hit query with statistics (two events and a counter word around the kernel) against the plain launch: the same
+    outputs bit for bit.  100 rays are one full wave and a ragged one for the count of one atomic per wave."""
+    scene = scene_of(name)
+    o, d, time0, _ = centre_rays(scene)
+    o, d = o[:100].copy(), d[:100].copy()
+    plain = scene.intersect(o, d, time=time0, variant=0, want=ALL + ("occluded",))
+    counted, st = scene.intersect(o, d, time=time0, variant=0, want=ALL + ("occluded",), stats=True)
+    print(f"{name}: {st.hits} of {st.rays} rays hit, {st.kernel_vgprs} VGPRs, {st.seconds * 1e3:.3f} ms")
+    for key in ALL + ("occluded",):
+        assert np.array_equal(bits(counted[key]), bits(plain[key])), key
+        assert np.array_equal(bits(plain[key]), bits(closest_of(name)[key][:100])), key
+    assert st.rays == 100 and st.hits == np.isfinite(plain["t"]).sum()
+    assert 0 < st.hits, "a counter that stayed at its memset would pass the line above if every ray missed"
+    assert st.kernel_vgprs > 0 and st.seconds > 0
+
+
+@pytest.mark.parametrize("name", ["mixed bvh", "mixed list"])
 def test_permuted_rays_give_permuted_results(name):
     scene = scene_of(name)
     o, d, time0, _ = centre_rays(scene)
