@@ -206,8 +206,11 @@ typedef struct rt_render_params {
 #define RT_FLAG_REFERENCE_TREE 128u  /* BVH worlds of primitives only are walked through the library's own tree (surface-area heuristic, near
                                       child first) -- no leaf draws random numbers there, so the closest hit is the one the reference's tree
                                       gives; this flag walks the reference's own tree in its own order instead (tests, timing).  A world in
-                                      which two primitives coincide (identical spheres, overlapping quads in one plane) has no library
-                                      tree at all: there the order of the tests decides which of the two a ray sees */
+                                      which two leaves coincide -- identical spheres (a moving sphere that rests counts as the static
+                                      sphere it is), or two quads in one plane whose rectangles overlap, be they Quad leaves, faces of
+                                      MakeBox boxes, or either behind Translate / RotateY -- has no library tree at all, nor the segmented
+                                      walk of a composite world: there the order of the tests decides which of the two a ray sees.  (Not
+                                      counted: faces of untransformed opaque boxes that abut, which no ray reaches.) */
 #define RT_FLAG_EXACT_SCAN 256u      /* sphere-list worlds: every ray runs the reference's discriminant against every sphere (default: a cheaper
                                       conservative filter rejects the spheres a ray's line misses and only the survivors go through the
                                       reference's arithmetic; the image is the same bit for bit either way) */
@@ -217,7 +220,7 @@ typedef struct rt_render_params {
 #define RT_FLAG_ACCELERATE_LISTS 512u /* HittableList worlds of primitives only (no leaf draws random numbers): render through the library's
                                       own tree as a BvhNode world would be -- the reference's "BVH image == list image" invariant the other
                                       way round; off by default so that a list world is scanned as the reference scans it.  Ignored for
-                                      a list with coincident primitives (see RT_FLAG_REFERENCE_TREE) */
+                                      a list with coincident leaves (see RT_FLAG_REFERENCE_TREE) */
 #define RT_FLAG_COOP_SINGLE 1024u    /* tests: sphere-list worlds, thin waves scan one ray at a time with all 64 lanes (the older scheme)
                                       instead of several rays in groups of lanes */
 #define RT_FLAG_ROW_MAJOR_TILES 16u /* BVH worlds: keep the pixel queue in row-major tile order (default: a short rehearsal ranks

@@ -244,47 +244,229 @@ static int build_tree(SceneImpl *s, HostHittable &bvh, std::vector<uint32_t> &ob
 // flattening
 // ------------------------------------------------------------------------------------------------
 namespace {
-// Coincident primitives: two identical spheres, or two quads in one plane whose rectangles overlap.  A ray that hits both
+// Coincident surfaces: two identical spheres, or two quads in one plane whose rectangles overlap.  A ray that hits both
 // gets the same t twice, and then the ORDER of the tests decides which material it sees: the reference's list keeps the
 // first sphere it meets (strict `<`, R/Sphere.h:38,50) and the last quad (inclusive interval, R/Quad.h:59-64).  The
-// library's own accelerators (the near-child-first tree of a primitive world, the sub-BVH / cooperative scan of a large
-// group) meet the primitives in another order, so they are not built over such a set: it keeps the reference's tree or
-// its linear list.  Exact comparisons on purpose: surfaces that differ in the last bit do not tie.
+// library's own accelerators (the near-child-first tree of a primitive world, the segmented walk of a composite world and
+// its media's candidate lists, the sub-BVH / cooperative scan of a large group) meet the leaves in another order, so they are
+// not built over such a set: it keeps the reference's tree or its linear list.
+//
+// What is compared, per leaf handed in (ties inside one leaf are that leaf's own scan's business, which runs in list order):
+//   spheres   Sphere and MovingSphere leaves.  A moving sphere that rests (center0 == center1, time0 != time1) is at c0 + frac * 0
+//             = c0 exactly at every time and is keyed as the static sphere it is; one with time0 == time1 has a centre of inf /
+//             NaN and is never hit.  Exact comparison.
+//   faces     every quad: a Quad leaf, the quads of a list leaf (MakeBox: six), and both behind a Translate / RotateY chain, in
+//             world space.  Two faces that were not transformed are compared bit for bit (surfaces that differ in the last bit
+//             do not tie); a transformed face is compared with a tolerance far above its rounding, since finding a tie too
+//             many costs only speed.  Rectangles overlap when their (padded) bounding boxes meet.
+// One kind of overlap is left alone, or a field of boxes that stand side by side (the ground of the Book-2 final scene) would
+// lose its tree: two faces of closed, untransformed MakeBox boxes
+//   - that share no area (the boxes touch along an edge or a corner at most: the rays that meet both are a set of measure
+//     zero in any pixel), or
+//   - whose boxes lie on opposite sides of the shared plane (one's +x face is the other's -x face), both of a material that
+//     sends no ray inwards (Lambertian, Metal -- R/Metal.h:29 absorbs what its fuzz turns inwards --, DiffuseLight): every
+//     point of the shared area has a solid on either side, and no ray reaches it.  This assumes what the reference's scenes
+//     assume: no camera inside a solid box.
+struct TieFace {
+    double n[3], d;        // plane, the normal's sign fixed by its largest component
+    double lo[3], hi[3];   // padded bounding box of the rectangle
+    bool exact;            // not transformed: n, d, lo, hi are the quad's own
+    uint32_t leaf;         // position in `handles`
+    int box;               // index into the closed untransformed boxes, or -1
+    int axis, end;         // of such a box: the face lies in coordinate `axis` = (end ? mx : mn)[axis]
+};
+struct TieBox {
+    double mn[3], mx[3];
+    bool opaque;
+};
+
+static bool only_primitives(const SceneImpl &s, uint32_t handle)  // a primitive, or a (nested) list / BVH whose members are all primitives
+{
+    const HostHittable &h = s.hittables[handle - 1];
+    if (h.kind == HKind::Sphere || h.kind == HKind::MovingSphere || h.kind == HKind::Quad) return true;
+    if (h.kind != HKind::List && h.kind != HKind::Bvh) return false;
+    for (uint32_t c : h.items)
+        if (!only_primitives(s, c)) return false;
+    return true;
+}
+
+// A list of six quads that bound a box mn < mx as MakeBox builds it (R/Instance.h:166-184), in any order: one quad in each of the
+// six face planes, its edges along the two other axes, each starting at a corner coordinate and spanning the rounded extent
+// fl(mx - mn) towards the other one (Flattener::box_of_six has the same notion for the lowered quads).
+static bool closed_box(const SceneImpl &s, const HostHittable &list, TieBox &b, int axis_of[6], int end_of[6])
+{
+    if (list.kind != HKind::List || list.items.size() != 6) return false;
+    int edge_axis[6][2], seen[3] = {0, 0, 0};
+    double edge[6][2];
+    for (int f = 0; f < 6; f++) {
+        const HostHittable &q = s.hittables[list.items[f] - 1];
+        if (q.kind != HKind::Quad || q.material != s.hittables[list.items[0] - 1].material) return false;
+        const double o[3] = {q.q.x, q.q.y, q.q.z}, u[3] = {q.u.x, q.u.y, q.u.z}, v[3] = {q.v.x, q.v.y, q.v.z};
+        int p = -1, qa = -1;
+        for (int k = 0; k < 3; k++) {
+            if (!std::isfinite(o[k]) || !std::isfinite(u[k]) || !std::isfinite(v[k])) return false;
+            if (u[k] != 0.0) p = p == -1 ? k : -2;
+            if (v[k] != 0.0) qa = qa == -1 ? k : -2;
+        }
+        if (p < 0 || qa < 0 || p == qa) return false;
+        const int a = 3 - p - qa;
+        axis_of[f] = a;
+        edge_axis[f][0] = p;
+        edge_axis[f][1] = qa;
+        edge[f][0] = u[p];
+        edge[f][1] = v[qa];
+        if (seen[a] == 0) b.mn[a] = b.mx[a] = o[a];
+        else if (seen[a] == 1) {
+            b.mn[a] = std::min(b.mn[a], o[a]);
+            b.mx[a] = std::max(b.mx[a], o[a]);
+        } else return false;
+        seen[a]++;
+    }
+    for (int k = 0; k < 3; k++)
+        if (seen[k] != 2 || !(b.mn[k] < b.mx[k])) return false;
+    for (int f = 0; f < 6; f++) {
+        const HostHittable &q = s.hittables[list.items[f] - 1];
+        const double o[3] = {q.q.x, q.q.y, q.q.z};
+        end_of[f] = o[axis_of[f]] == b.mx[axis_of[f]] ? 1 : 0;
+        for (int e = 0; e < 2; e++) {
+            const int k = edge_axis[f][e];
+            const double ext = b.mx[k] - b.mn[k];
+            if (!(o[k] == b.mn[k] && edge[f][e] == ext) && !(o[k] == b.mx[k] && edge[f][e] == -ext)) return false;
+        }
+    }
+    const uint32_t kind = s.materials[s.hittables[list.items[0] - 1].material - 1].kind;
+    b.opaque = kind == MAT_LAMBERTIAN || kind == MAT_METAL || kind == MAT_DIFFUSE_LIGHT;
+    return true;
+}
+
 static bool has_coincident_primitives(const SceneImpl &s, const std::vector<uint32_t> &handles)
 {
     struct Key {
         double v[10];
-        uint32_t handle;
+        uint32_t leaf;
     };
     auto less = [](const Key &a, const Key &b) { return std::lexicographical_compare(a.v, a.v + 10, b.v, b.v + 10); };
     auto same = [](const Key &a, const Key &b) { return std::equal(a.v, a.v + 10, b.v); };
-    std::vector<Key> spheres, planes;
-    for (uint32_t hnd : handles) {
-        const HostHittable &h = s.hittables[hnd - 1];
-        if (h.kind == HKind::Sphere || h.kind == HKind::MovingSphere) {
-            const bool moving = h.kind == HKind::MovingSphere;
-            spheres.push_back({{h.c0.x, h.c0.y, h.c0.z, moving ? h.c1.x : h.c0.x, moving ? h.c1.y : h.c0.y, moving ? h.c1.z : h.c0.z,
-                                moving ? h.t0 : 0.0, moving ? h.t1 : 0.0, h.radius, moving ? 1.0 : 0.0}, hnd});
-        } else if (h.kind == HKind::Quad) {
-            // the plane, with the sign of the normal fixed by its first non-zero component
-            double n[3] = {h.normal.x, h.normal.y, h.normal.z}, d = h.plane_d;
-            const double lead = n[0] != 0.0 ? n[0] : (n[1] != 0.0 ? n[1] : n[2]);
-            if (lead < 0.0) {
-                for (double &c : n) c = -c;
-                d = -d;
+    std::vector<Key> spheres;
+    std::vector<TieFace> faces;
+    std::vector<TieBox> boxes;
+    double reach = 0.0;  // the largest coordinate of a face: scales the tolerance of transformed planes
+
+    auto add_face = [&](const HostHittable &q, const std::vector<const HostHittable *> &chain, uint32_t leaf, int box, int axis, int end) {
+        TieFace f{};
+        f.exact = chain.empty();
+        f.leaf = leaf;
+        f.box = box;
+        f.axis = axis;
+        f.end = end;
+        double n[3], d;
+        if (f.exact) {
+            n[0] = q.normal.x; n[1] = q.normal.y; n[2] = q.normal.z;
+            d = q.plane_d;
+            for (int k = 0; k < 3; k++) {
+                f.lo[k] = q.box.lo[k];
+                f.hi[k] = q.box.hi[k];
             }
-            planes.push_back({{n[0] + 0.0, n[1] + 0.0, n[2] + 0.0, d + 0.0, 0, 0, 0, 0, 0, 0}, hnd});  // + 0.0: -0.0 -> +0.0
+        } else {
+            D3 c[4] = {q.q, add(q.q, q.u), add(add(q.q, q.u), q.v), add(q.q, q.v)};
+            for (D3 &p : c)
+                for (size_t k = chain.size(); k-- > 0;) {  // innermost transform first (R/Instance.h:49-50, :142-147)
+                    const HostHittable &x = *chain[k];
+                    if (x.kind == HKind::Translate) p = add(p, x.offset);
+                    else p = mk(x.cos_t * p.x + x.sin_t * p.z, p.y, -x.sin_t * p.x + x.cos_t * p.z);
+                }
+            const D3 nn = normalize(cross(sub(c[1], c[0]), sub(c[3], c[0])));
+            n[0] = nn.x; n[1] = nn.y; n[2] = nn.z;
+            d = dot(nn, c[0]);
+            for (int k = 0; k < 3; k++) {
+                f.lo[k] = DBL_MAX;
+                f.hi[k] = -DBL_MAX;
+                for (const D3 &p : c) {
+                    f.lo[k] = std::min(f.lo[k], comp(p, k));
+                    f.hi[k] = std::max(f.hi[k], comp(p, k));
+                }
+            }
         }
+        if (!std::isfinite(n[0]) || !std::isfinite(n[1]) || !std::isfinite(n[2]) || !std::isfinite(d)) return;  // never hit
+        for (int k = 0; k < 3; k++) {
+            if (!std::isfinite(f.lo[k]) || !std::isfinite(f.hi[k])) return;
+            reach = std::max(reach, std::max(std::fabs(f.lo[k]), std::fabs(f.hi[k])));
+        }
+        int lead = 0;
+        for (int k = 1; k < 3; k++)
+            if (std::fabs(n[k]) > std::fabs(n[lead])) lead = k;
+        const double sign = n[lead] < 0.0 ? -1.0 : 1.0;
+        for (int k = 0; k < 3; k++) f.n[k] = sign * n[k] + 0.0;  // + 0.0: -0.0 -> +0.0
+        f.d = sign * d + 0.0;
+        faces.push_back(f);
+    };
+    auto add_prims = [&](auto &&self, uint32_t hnd, const std::vector<const HostHittable *> &chain, uint32_t leaf, int box, const int *axis_of,
+                         const int *end_of) -> void {
+        const HostHittable &h = s.hittables[hnd - 1];
+        if (h.kind == HKind::Quad) {
+            add_face(h, chain, leaf, -1, 0, 0);
+        } else if (h.kind == HKind::Sphere || h.kind == HKind::MovingSphere) {
+            if (!chain.empty()) return;  // (an instanced sphere is not compared)
+            const bool moving = h.kind == HKind::MovingSphere && !(h.c0.x == h.c1.x && h.c0.y == h.c1.y && h.c0.z == h.c1.z && h.t0 != h.t1);
+            spheres.push_back({{h.c0.x, h.c0.y, h.c0.z, moving ? h.c1.x : h.c0.x, moving ? h.c1.y : h.c0.y, moving ? h.c1.z : h.c0.z,
+                                moving ? h.t0 : 0.0, moving ? h.t1 : 0.0, h.radius, moving ? 1.0 : 0.0}, leaf});
+        } else {
+            for (size_t k = 0; k < h.items.size(); k++) {
+                const HostHittable &c = s.hittables[h.items[k] - 1];
+                if (box >= 0 && c.kind == HKind::Quad) add_face(c, chain, leaf, box, axis_of[k], end_of[k]);
+                else self(self, h.items[k], chain, leaf, -1, nullptr, nullptr);
+            }
+        }
+    };
+    for (uint32_t leaf = 0; leaf < handles.size(); leaf++) {
+        const HostHittable *h = &s.hittables[handles[leaf] - 1];
+        std::vector<const HostHittable *> chain;  // outermost first
+        while (h->kind == HKind::Translate || h->kind == HKind::RotateY) {
+            chain.push_back(h);
+            h = &s.hittables[h->child - 1];
+        }
+        // a medium's hit is drawn, not found: it ties with nothing.  General nesting gets no library tree in the first place.
+        const uint32_t inner = (uint32_t)(h - s.hittables.data()) + 1;
+        if (h->kind == HKind::Medium || !only_primitives(s, inner)) continue;
+        TieBox b;
+        int axis_of[6], end_of[6], box = -1;
+        if (chain.empty() && closed_box(s, *h, b, axis_of, end_of)) {
+            box = (int)boxes.size();
+            boxes.push_back(b);
+        }
+        add_prims(add_prims, inner, chain, leaf, box, axis_of, end_of);
     }
+
     std::sort(spheres.begin(), spheres.end(), less);
-    for (size_t k = 1; k < spheres.size(); k++)
-        if (same(spheres[k - 1], spheres[k])) return true;
-    std::sort(planes.begin(), planes.end(), less);
-    for (size_t a = 0; a < planes.size(); a++)
-        for (size_t b = a + 1; b < planes.size() && same(planes[a], planes[b]); b++) {
-            const Box &x = s.hittables[planes[a].handle - 1].box, &y = s.hittables[planes[b].handle - 1].box;
+    for (size_t a = 0; a < spheres.size(); a++)
+        for (size_t b = a + 1; b < spheres.size() && same(spheres[a], spheres[b]); b++)
+            if (spheres[a].leaf != spheres[b].leaf) return true;
+
+    std::sort(faces.begin(), faces.end(), [](const TieFace &a, const TieFace &b) { return a.d < b.d; });
+    const double tol_n = 1e-9, tol_d = 1e-9 * (1.0 + reach);
+    for (size_t a = 0; a < faces.size(); a++)
+        for (size_t b = a + 1; b < faces.size() && faces[b].d - faces[a].d <= tol_d; b++) {
+            const TieFace &x = faces[a], &y = faces[b];
+            if (x.leaf == y.leaf) continue;
+            bool same_plane = true;
+            if (x.exact && y.exact) {
+                same_plane = x.d == y.d && x.n[0] == y.n[0] && x.n[1] == y.n[1] && x.n[2] == y.n[2];
+            } else {
+                for (int k = 0; k < 3; k++) same_plane &= std::fabs(x.n[k] - y.n[k]) <= tol_n;
+            }
+            if (!same_plane) continue;
+            if (x.box >= 0 && y.box >= 0) {
+                const TieBox &p = boxes[(size_t)x.box], &q = boxes[(size_t)y.box];
+                bool area = true;
+                for (int k = 0; k < 3; k++)
+                    if (k != x.axis) area &= p.mn[k] < q.mx[k] && q.mn[k] < p.mx[k];
+                if (!area) continue;                                        // an edge or a corner at most
+                if (x.end != y.end && p.opaque && q.opaque) continue;      // a solid on either side
+                return true;
+            }
             bool overlap = true;
-            for (int k = 0; k < 3; k++) overlap &= x.lo[k] <= y.hi[k] && y.lo[k] <= x.hi[k];
+            for (int k = 0; k < 3; k++) overlap &= x.lo[k] - (x.exact ? 0.0 : 1e-4) <= y.hi[k] + (y.exact ? 0.0 : 1e-4) &&
+                                                   y.lo[k] - (y.exact ? 0.0 : 1e-4) <= x.hi[k] + (x.exact ? 0.0 : 1e-4);
             if (overlap) return true;
         }
     return false;
@@ -438,15 +620,6 @@ struct Flattener {
     }
 
     // ---- general nesting: what ObjectRec cannot express stays a tree (flat_scene.h TreeNodeRec) ----
-    bool only_primitives(uint32_t handle) const  // a (nested) list / BVH whose members are all primitives
-    {
-        const HostHittable &h = s.hittables[handle - 1];
-        if (is_primitive(h.kind)) return true;
-        if (h.kind != HKind::List && h.kind != HKind::Bvh) return false;
-        for (uint32_t c : h.items)
-            if (!only_primitives(c)) return false;
-        return true;
-    }
     // [ConstantMedium] -> Translate / RotateY chain -> a primitive or a list / BVH of primitives: the ObjectRec form
     bool fits_flat(uint32_t handle) const
     {
@@ -454,7 +627,7 @@ struct Flattener {
         if (h->kind == HKind::Medium) h = &s.hittables[h->child - 1];
         while (h->kind == HKind::Translate || h->kind == HKind::RotateY) h = &s.hittables[h->child - 1];
         if (h->kind == HKind::Medium) return false;
-        return only_primitives((uint32_t)(h - s.hittables.data()) + 1);
+        return only_primitives(s, (uint32_t)(h - s.hittables.data()) + 1);
     }
     uint32_t tree_depth_seen = 0;
     // One node of the tree for `handle`, whose Hit is called with the ray transformed by `chain` (outermost first).

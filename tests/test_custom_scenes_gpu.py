@@ -205,7 +205,9 @@ def test_coincident_primitives_resolve_like_the_reference(world_kind):
     """Two identical spheres, two overlapping quads in one plane, a quad in the plane of a box face: a ray gets the same t
     from both and the ORDER of the tests decides (first sphere: R/Sphere.h:38,50 strict; last quad: R/Quad.h:59-64
     inclusive).  Such a world gets no library tree (its near-child-first order is not the reference's) -- it is walked /
-    scanned in the reference's order and must equal the oracle; the lanes-per-ray scan resolves ties the same way."""
+    scanned in the reference's order and must equal the oracle; the lanes-per-ray scan resolves ties the same way.
+    (The twin spheres and the coplanar quads trip the guard on their own, so the box face of this world never meets an
+    out-of-order walk: that tie is exercised in tests/test_tie_worlds_gpu.py.)"""
     prod, orc = build_both(_coincident(world_kind))
     assert prod.dump_fast_nodes()[0].shape[0] == 0, "a world with coincident primitives must not get a library tree"
     want, stats = orc.render(W, H, 8, want_stats=True)
