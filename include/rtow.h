@@ -102,6 +102,36 @@ RTOW_API rt_handle rt_moving_sphere(rt_scene *s, double c0x, double c0y, double 
                                     rt_handle material);                                       /* MovingSphere.h:19 */
 RTOW_API rt_handle rt_quad(rt_scene *s, const double q[3], const double u[3], const double v[3],
                            rt_handle material);                                                /* Quad.h:25 */
+/* R/Quad.h's planar primitive with the interior rule its own comment (:86-88) names: corners Q, Q+u, Q+v.
+ *   constants   the quad's (Quad.h:33-36): n = u x v, normal = unit(n), D = normal . Q, w = n / (n . n)
+ *   Hit         Quad.h:56-71 unchanged: denom = normal . dir, |denom| < 1e-8 rejects; t = (D - normal . origin) / denom,
+ *               tmin <= t <= tmax (inclusive); alpha = w . (p x v), beta = w . (u x p) with p = ray(t) - Q
+ *   interior    accept <=> 0 <= alpha && 0 <= beta && fl(alpha + beta) <= 1: inclusive like the quad's rule, one IEEE add of the
+ *               two values the quad forms, a NaN rejects.  So a triangle is hit exactly where the quad (Q, u, v) is hit with such
+ *               alpha, beta, with the same t bit for bit.  Neighbouring triangles of a mesh are decided each by its own rounded
+ *               alpha, beta: the arithmetic promises no watertightness along shared edges (DESIGN.md section 5 has the count).
+ *   HitRecord   U = alpha, V = beta (the barycentric coordinates of Q+u and Q+v); the normal is the flat geometric one, set
+ *               against the ray (SetFaceNormal); no vertex normals, no per-vertex texture coordinates
+ *   degenerate  u x v = 0: normal and w are not finite and no ray is accepted, like a degenerate quad
+ *   box         per axis the min and max of Q, fl(Q+u), fl(Q+v), through the corner constructor the quad uses (AABB.h:34-40) with
+ *               its padding of axes thinner than 0.0001 (AABB.h:114-120)
+ * Everywhere a quad may stand a triangle may: in lists and BvhNodes, under Translate / RotateY, as a ConstantMedium boundary.  It
+ * is no box face: a list with a triangle in it is a list.  Returns 0 on an invalid material or a NULL vector. */
+RTOW_API rt_handle rt_triangle(rt_scene *s, const double q[3], const double u[3], const double v[3],
+                               rt_handle material);
+/* Triangle k has corners A = vertices[indices[3k]], B = vertices[indices[3k+1]], C = vertices[indices[3k+2]] (vertices: 3 doubles
+ * each) and is rt_triangle(A, fl(B - A), fl(C - A), material).  Returns rt_bvh_node over the n_triangles handles (the reference's
+ * rule and permutation); triangles_out, if not NULL, receives the n_triangles handles in input order (for a list, or a BvhNode
+ * shared with other objects).  Returns 0 where n_triangles < 1, n_vertices < 3, an array is NULL, the material is invalid or an
+ * index lies outside [0, n_vertices); nothing is added to the scene then. */
+RTOW_API rt_handle rt_triangle_mesh(rt_scene *s, const double *vertices, int n_vertices, const int32_t *indices,
+                                    int n_triangles, rt_handle material, rt_handle *triangles_out);
+/* Wavefront OBJ, positions and faces only: `v x y z`, `f` with i, i/j, i/j/k and i//k forms, negative (relative) indices,
+ * polygons fanned from their first corner (0 1 2, 0 2 3, ...), comments and every other statement skipped.  Indices come back
+ * 0-based.  The arrays are the library's: release them with rt_mesh_free.  RT_ERR_INVALID for an unreadable file, a file without
+ * a face, an index out of range (0 included), a vertex with fewer than three numbers or a face with fewer than three corners. */
+RTOW_API int rt_obj_load(const char *path, double **vertices, int *n_vertices, int32_t **indices, int *n_triangles);
+RTOW_API void rt_mesh_free(double *vertices, int32_t *indices);
 RTOW_API rt_handle rt_translate(rt_scene *s, rt_handle object, double ox, double oy, double oz); /* Instance.h:31 */
 RTOW_API rt_handle rt_rotate_y(rt_scene *s, rt_handle object, double angle_degrees);          /* Instance.h:74 */
 RTOW_API rt_handle rt_make_box(rt_scene *s, const double a[3], const double b[3], rt_handle material); /* Instance.h:166 */
@@ -123,7 +153,9 @@ RTOW_API int rt_scene_set_camera(rt_scene *s, const double lookfrom[3], const do
                                  const double background[3]);                                  /* Camera.h:36-72 */
 
 /* Built-in scenes: ids 0..9 = the reference's sceneId (R/kernel.cu:199-517); 10 = three-spheres (config C1);
- * 11 = scene 0 with every MovingSphere made static (config C2).  world_kind 0 = BvhNode world (the
+ * 11 = scene 0 with every MovingSphere made static (config C2); 12 = scene 7's Cornell walls, light and camera with two triangle
+ * meshes in place of the boxes (a 320-triangle Lambertian icosphere under Translate, a 20-triangle metal icosahedron under
+ * RotateY + Translate; both rt_triangle_mesh).  world_kind 0 = BvhNode world (the
  * reference's), 1 = HittableList world ("no BVH").  earth_rgb may be NULL (scenes 2 and 9 then show cyan). */
 RTOW_API int rt_scene_build_builtin(rt_scene *s, int scene_id, int world_kind, int image_width,
                                     int image_height, uint64_t seed, const unsigned char *earth_rgb,
@@ -141,12 +173,12 @@ typedef struct rt_scene_info {
     uint32_t n_xforms, n_media, n_materials, n_textures, n_perlin, n_images;
     uint32_t table_bytes;         /* bytes of the geometry tables staged on chip */
     uint32_t image_bytes;
-    uint32_t reserved[3];
+    uint32_t reserved[3];         /* [0] = n_triangles: the rows of n_quads that are triangles; [1], [2] = 0 */
 } rt_scene_info;
 RTOW_API int rt_scene_get_info(rt_scene *s, rt_scene_info *out);
 
 /* Introspection for tests (valid after commit): world leaves in final order. kind: 0 sphere, 1 moving
- * sphere, 2 quad, 3 composite object; box = {xmin,xmax,ymin,ymax,zmin,zmax}. Returns the leaf count. */
+ * sphere, 2 quad, 3 composite object, 4 triangle; box = {xmin,xmax,ymin,ymax,zmin,zmax}. Returns the leaf count. */
 RTOW_API int rt_scene_dump_leaves(rt_scene *s, int max_leaves, int *kind_out, double *box_out);
 /* Threaded-BVH nodes in preorder: box[6], a, b, escape per node (a,b = leaf refs or 0xE0000000 for inner). */
 RTOW_API int rt_scene_dump_nodes(rt_scene *s, int max_nodes, double *box_out, uint32_t *abe_out);

@@ -84,6 +84,24 @@ public:
         const double qq[3] = {q.x, q.y, q.z}, uu[3] = {u.x, u.y, u.z}, vv[3] = {v.x, v.y, v.z};
         return {ok(rt_quad(s_, qq, uu, vv, m.h))};
     }
+    Hittable Triangle(const Point3 &q, const Vector3 &u, const Vector3 &v, Material m)
+    {
+        const double qq[3] = {q.x, q.y, q.z}, uu[3] = {u.x, u.y, u.z}, vv[3] = {v.x, v.y, v.z};
+        return {ok(rt_triangle(s_, qq, uu, vv, m.h))};
+    }
+    // rt_triangle_mesh: a BvhNode over the triangles; `triangles`, if given, receives them in input order
+    Hittable TriangleMesh(const std::vector<Point3> &vertices, const std::vector<int32_t> &indices, Material m, std::vector<Hittable> *triangles = nullptr)
+    {
+        std::vector<double> xyz;
+        for (const Point3 &p : vertices) xyz.insert(xyz.end(), {p.x, p.y, p.z});
+        std::vector<rt_handle> hs(indices.size() / 3);
+        const rt_handle root = ok(rt_triangle_mesh(s_, xyz.data(), (int)vertices.size(), indices.data(), (int)(indices.size() / 3), m.h, hs.data()));
+        if (triangles) {
+            triangles->clear();
+            for (rt_handle h : hs) triangles->push_back({h});
+        }
+        return {root};
+    }
     Hittable Translate(Hittable o, const Vector3 &off) { return {ok(rt_translate(s_, o.h, off.x, off.y, off.z))}; }
     Hittable RotateY(Hittable o, double degrees) { return {ok(rt_rotate_y(s_, o.h, degrees))}; }
     Hittable MakeBox(const Point3 &a, const Point3 &b, Material m)

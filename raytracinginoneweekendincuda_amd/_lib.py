@@ -148,6 +148,10 @@ SIGNATURES = {
     "rt_sphere": (H, [P, D, D, D, D, H]),
     "rt_moving_sphere": (H, [P, D, D, D, D, D, D, D, D, D, H]),
     "rt_quad": (H, [P, D3, D3, D3, H]),
+    "rt_triangle": (H, [P, D3, D3, D3, H]),
+    "rt_triangle_mesh": (H, [P, D3, I, C.POINTER(C.c_int32), I, H, C.POINTER(H)]),
+    "rt_obj_load": (I, [C.c_char_p, C.POINTER(D3), C.POINTER(I), C.POINTER(C.POINTER(C.c_int32)), C.POINTER(I)]),
+    "rt_mesh_free": (None, [D3, C.POINTER(C.c_int32)]),
     "rt_translate": (H, [P, H, D, D, D]),
     "rt_rotate_y": (H, [P, H, D]),
     "rt_make_box": (H, [P, D3, D3, H]),

@@ -155,6 +155,22 @@ class Scene:
     def Quad(self, q, u, v, material):
         return _h(lib().rt_quad(self._p, _v3(q), _v3(u), _v3(v), material))
 
+    def Triangle(self, q, u, v, material):
+        """Corners q, q + u, q + v; the quad's plane and the interior rule 0 <= alpha, 0 <= beta, alpha + beta <= 1 (rtow.h)."""
+        return _h(lib().rt_triangle(self._p, _v3(q), _v3(u), _v3(v), material))
+
+    def TriangleMesh(self, vertices, faces, material, return_triangles=False):
+        """A BvhNode over the triangles of an indexed mesh: vertices (N, 3), faces (M, 3) of indices into them (rt_triangle_mesh).
+        With ``return_triangles`` also the M triangle handles in input order, for a list or a BvhNode shared with other objects."""
+        v = np.ascontiguousarray(vertices, dtype=np.float64)
+        f = np.ascontiguousarray(faces, dtype=np.int32)
+        if v.ndim != 2 or v.shape[1] != 3 or f.ndim != 2 or f.shape[1] != 3:
+            raise RtowError("TriangleMesh: vertices must be (N, 3) and faces (M, 3)")
+        tris = (C.c_uint32 * max(1, f.shape[0]))()
+        root = _h(lib().rt_triangle_mesh(self._p, v.ctypes.data_as(_lib.D3), v.shape[0], f.ctypes.data_as(C.POINTER(C.c_int32)),
+                                         f.shape[0], material, tris))
+        return (root, list(tris)[: f.shape[0]]) if return_triangles else root
+
     def Translate(self, obj, offset):
         return _h(lib().rt_translate(self._p, obj, *map(float, offset)))
 
@@ -211,7 +227,9 @@ class Scene:
     def info(self):
         out = SceneInfo()
         _check(lib().rt_scene_get_info(self._p, C.byref(out)))
-        return {n: getattr(out, n) for n, _ in SceneInfo._fields_ if n != "reserved"}
+        info = {n: getattr(out, n) for n, _ in SceneInfo._fields_ if n != "reserved"}
+        info["n_triangles"] = out.reserved[0]  # the rows of n_quads that are triangles
+        return info
 
     def dump_leaves(self):
         n = lib().rt_scene_dump_leaves(self._p, 0, None, None)
@@ -610,6 +628,19 @@ def jpeg_decode(data):
     ptr, w, h = C.c_void_p(), C.c_int(), C.c_int()
     _check(lib().rt_jpeg_decode(buf.ctypes.data, buf.size, C.byref(ptr), C.byref(w), C.byref(h)))
     return _take_image(ptr, w, h)
+
+
+def load_obj(path):
+    """Wavefront OBJ, positions and faces only (rt_obj_load): vertices (N, 3) float64, faces (M, 3) int32, polygons fanned."""
+    v, f = _lib.D3(), C.POINTER(C.c_int32)()
+    nv, nf = C.c_int(), C.c_int()
+    _check(lib().rt_obj_load(str(path).encode(), C.byref(v), C.byref(nv), C.byref(f), C.byref(nf)))
+    try:
+        vertices = np.ctypeslib.as_array(v, shape=(nv.value, 3)).copy()
+        faces = np.ctypeslib.as_array(f, shape=(nf.value, 3)).copy()
+    finally:
+        lib().rt_mesh_free(v, f)
+    return vertices, faces
 
 
 def load_image(path):

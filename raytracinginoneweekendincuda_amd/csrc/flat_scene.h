@@ -71,6 +71,10 @@ struct QuadGeom { double qx, qy, qz, ux, uy, uz, vx, vy, vz, wx, wy, wz, nx, ny,
 //   t = (d - na*o[a]) / (na*dir[a]);  ph = (o + t*dir) - Q;  alpha = wa*(ph[p]*kv);  beta = wa*(ku*ph[q])
 // with kv = +-v[q], ku = +-u[p] (the sign of that term in the cross product).
 struct AAQuad { double na, d, wa, qp, qq, ku, kv; uint32_t code, pad; };  // code 0: not axis-aligned; else 1 + 3a + p
+// A triangle (rt_triangle) is a row of quads[] / quad_aa[] / quad_mat[] like any quad: the same plane constants, the same t, alpha
+// and beta, hits that are REF_QUAD.  Only the interior rule differs (render.hip quad_test), and the row says so with a code
+// outside the axis-aligned range 1 .. 8; every other field of its AAQuad is zero (a triangle always takes the general test).
+constexpr uint32_t kQuadTriangle = 16u;
 // MakeBox (R/Instance.h:166-184): the six faces' planes and the two corners.  A face's interior test only decides
 // accept / reject, and alpha = (P[p] - Q[p]) / u[p] up to a few ulps; so a hit point P that is inside [mn, mx] by more
 // than 2^-30 of the coordinates' magnitude is accepted, one that is outside by as much is rejected, and only the

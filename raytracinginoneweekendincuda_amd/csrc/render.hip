@@ -289,8 +289,18 @@ DEV bool sphere_test(Vec oc, Vec d, double a, double r2, double tmin, double tma
     return false;
 }
 
-// R/Quad.h:52-99: inclusive interval, inclusive unit square.
-DEV bool quad_test(const QuadGeom &q, const Ray &r, double tmin, double tmax, double &t_out)
+// R/Quad.h:52-99: inclusive interval, inclusive unit square.  tri: the interior rule the comment above Quad::IsInterior
+// (R/Quad.h:86-88) names for a triangle, inclusive like the quad's: 0 <= alpha, 0 <= beta, fl(alpha + beta) <= 1.  Plane, t,
+// alpha and beta are the quad's own, so a triangle (Q, u, v) is hit exactly where the quad (Q, u, v) is hit with such alpha, beta.
+// Two forms of that decision give the same answers (the quad's rule is a necessary part of the triangle's: alpha, beta >= 0 and
+// fl(alpha + beta) <= 1 imply alpha, beta <= 1): the quad's rule as it was with one more branch behind it for a triangle row, or a
+// select between the two upper bounds.  Which one the register allocator takes better differs by kernel, and both were timed
+// against the parent commit (profiles/r16_kernel_table.txt, profiles/r16_triangle_ab.txt): the render kernels keep their frame
+// times with the branch (the select costs the media kernel of scene 8 3 %), the lane-per-ray kernels of the feature pass and the
+// queries keep their registers with the select (the branch takes the radiance kernel of list worlds from 168 to 170 VGPRs, from
+// three waves per SIMD to two, 35 % on scene 7).  A third form, a switch case of its own in quad_test_at, cost most kernels spills.
+#define RT_PLANAR_SELECT (RT_FEATURES || RT_QUERY || RT_RADIANCE)
+DEV bool quad_test(const QuadGeom &q, bool tri, const Ray &r, double tmin, double tmax, double &t_out)
 {
     Vec n = mk(q.nx, q.ny, q.nz);
     double denom = dot(n, r.d);
@@ -301,7 +311,15 @@ DEV bool quad_test(const QuadGeom &q, const Ray &r, double tmin, double tmax, do
     Vec w = mk(q.wx, q.wy, q.wz);
     double alpha = dot(w, cross(ph, mk(q.vx, q.vy, q.vz)));
     double beta = dot(w, cross(mk(q.ux, q.uy, q.uz), ph));
+#if RT_PLANAR_SELECT
+    const bool below = tri ? alpha + beta <= 1.0 : (alpha <= 1.0 && beta <= 1.0);
+    if (!(0.0 <= alpha && 0.0 <= beta && below)) return false;  // (a NaN rejects)
+#else
     if (!(0.0 <= alpha && alpha <= 1.0) || !(0.0 <= beta && beta <= 1.0)) return false;
+    if (tri) {
+        if (!(alpha + beta <= 1.0)) return false;  // (a NaN was rejected above)
+    }
+#endif
     t_out = t;
     return true;
 }
@@ -347,7 +365,7 @@ DEV bool quad_test_at(const DeviceScene &sc, uint32_t idx, const Ray &r, double 
     case 1 + 3 * 1 + 2: return aa_quad_test<1, 2>(q, r, tmin, tmax, t);
     case 1 + 3 * 2 + 0: return aa_quad_test<2, 0>(q, r, tmin, tmax, t);
     case 1 + 3 * 2 + 1: return aa_quad_test<2, 1>(q, r, tmin, tmax, t);
-    default: return quad_test(const_row(sc.quads, idx), r, tmin, tmax, t);
+    default: return quad_test(const_row(sc.quads, idx), q.code == kQuadTriangle, r, tmin, tmax, t);  // (flat_scene.h kQuadTriangle)
     }
 }
 

@@ -8,8 +8,10 @@
 // to what the reference's constructors compute.
 #include <algorithm>
 #include <cfloat>
+#include <charconv>
 #include <cmath>
 #include <limits>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
@@ -267,6 +269,10 @@ namespace {
 //     sends no ray inwards (Lambertian, Metal -- R/Metal.h:29 absorbs what its fuzz turns inwards --, DiffuseLight): every
 //     point of the shared area has a solid on either side, and no ray reaches it.  This assumes what the reference's scenes
 //     assume: no camera inside a solid box.
+// A pair with a triangle in it is decided on the polygons themselves (share_area): a triangle's bounding box is no padded
+// rectangle of it, and a tessellated floor, a flat region of a mesh or a height field on a lattice is nothing but coplanar
+// faces whose boxes meet.  Two convex polygons of one plane tie only where they share area; meeting in an edge or a vertex is
+// the boxes' case above, a set of rays of measure zero.  Quad-quad pairs keep the rule of the boxes that meet.
 struct TieFace {
     double n[3], d;        // plane, the normal's sign fixed by its largest component
     double lo[3], hi[3];   // padded bounding box of the rectangle
@@ -274,7 +280,45 @@ struct TieFace {
     uint32_t leaf;         // position in `handles`
     int box;               // index into the closed untransformed boxes, or -1
     int axis, end;         // of such a box: the face lies in coordinate `axis` = (end ? mx : mn)[axis]
+    int nv;                // 4: a quad Q, Q+u, Q+u+v, Q+v; 3: a triangle Q, Q+u, Q+v
+    double p[4][3];        // the corners as computed (fl(Q + u), ...), in world space
 };
+
+// Do two convex polygons of one plane (unit normal n) share area?  Separating axes over the in-plane edge normals of both.  An
+// exact pair (neither face transformed) that penetrates by at most 2^-40 of the pair's coordinate reach only touches: the
+// projections' own rounding is a few 2^-53 of that reach.  A pair with a transformed face errs towards a tie instead: only a gap
+// of more than the 1e-4 per transformed face that the rectangles' rule allows separates it.
+static bool share_area(const TieFace &x, const TieFace &y)
+{
+    double pair_reach = 0.0;
+    for (const TieFace *f : {&x, &y})
+        for (int i = 0; i < f->nv; i++)
+            for (int k = 0; k < 3; k++) pair_reach = std::max(pair_reach, std::fabs(f->p[i][k]));
+    const bool exact = x.exact && y.exact;
+    const double limit = exact ? 0x1p-40 * pair_reach : -((x.exact ? 0.0 : 1e-4) + (y.exact ? 0.0 : 1e-4));
+    const D3 n = mk(x.n[0], x.n[1], x.n[2]);
+    for (const TieFace *f : {&x, &y})
+        for (int i = 0; i < f->nv; i++) {
+            const double *a = f->p[i], *b = f->p[(i + 1) % f->nv];
+            D3 axis = cross(mk(b[0] - a[0], b[1] - a[1], b[2] - a[2]), n);
+            const double len = length(axis);
+            if (!(len > 0.0) || !std::isfinite(len)) continue;  // an edge of no length separates nothing
+            axis = over(axis, len);
+            double lo[2] = {DBL_MAX, DBL_MAX}, hi[2] = {-DBL_MAX, -DBL_MAX};
+            int side = 0;
+            for (const TieFace *g : {&x, &y}) {
+                for (int j = 0; j < g->nv; j++) {
+                    const double t = dot(axis, mk(g->p[j][0], g->p[j][1], g->p[j][2]));
+                    lo[side] = std::min(lo[side], t);
+                    hi[side] = std::max(hi[side], t);
+                }
+                side++;
+            }
+            const double depth = std::min(hi[0], hi[1]) - std::max(lo[0], lo[1]);
+            if (exact ? depth <= limit : depth < limit) return false;
+        }
+    return true;
+}
 struct TieBox {
     double mn[3], mx[3];
     bool opaque;
@@ -283,7 +327,7 @@ struct TieBox {
 static bool only_primitives(const SceneImpl &s, uint32_t handle)  // a primitive, or a (nested) list / BVH whose members are all primitives
 {
     const HostHittable &h = s.hittables[handle - 1];
-    if (h.kind == HKind::Sphere || h.kind == HKind::MovingSphere || h.kind == HKind::Quad) return true;
+    if (h.kind == HKind::Sphere || h.kind == HKind::MovingSphere || h.kind == HKind::Quad || h.kind == HKind::Triangle) return true;
     if (h.kind != HKind::List && h.kind != HKind::Bvh) return false;
     for (uint32_t c : h.items)
         if (!only_primitives(s, c)) return false;
@@ -360,6 +404,9 @@ static bool has_coincident_primitives(const SceneImpl &s, const std::vector<uint
         f.axis = axis;
         f.end = end;
         double n[3], d;
+        const bool tri = q.kind == HKind::Triangle;
+        f.nv = tri ? 3 : 4;
+        D3 c[4] = {q.q, add(q.q, q.u), tri ? add(q.q, q.v) : add(add(q.q, q.u), q.v), add(q.q, q.v)};
         if (f.exact) {
             n[0] = q.normal.x; n[1] = q.normal.y; n[2] = q.normal.z;
             d = q.plane_d;
@@ -368,7 +415,6 @@ static bool has_coincident_primitives(const SceneImpl &s, const std::vector<uint
                 f.hi[k] = q.box.hi[k];
             }
         } else {
-            D3 c[4] = {q.q, add(q.q, q.u), add(add(q.q, q.u), q.v), add(q.q, q.v)};
             for (D3 &p : c)
                 for (size_t k = chain.size(); k-- > 0;) {  // innermost transform first (R/Instance.h:49-50, :142-147)
                     const HostHittable &x = *chain[k];
@@ -381,7 +427,7 @@ static bool has_coincident_primitives(const SceneImpl &s, const std::vector<uint
             for (int k = 0; k < 3; k++) {
                 f.lo[k] = DBL_MAX;
                 f.hi[k] = -DBL_MAX;
-                for (const D3 &p : c) {
+                for (const D3 &p : c) {  // (a triangle's fourth entry repeats its third corner)
                     f.lo[k] = std::min(f.lo[k], comp(p, k));
                     f.hi[k] = std::max(f.hi[k], comp(p, k));
                 }
@@ -398,12 +444,14 @@ static bool has_coincident_primitives(const SceneImpl &s, const std::vector<uint
         const double sign = n[lead] < 0.0 ? -1.0 : 1.0;
         for (int k = 0; k < 3; k++) f.n[k] = sign * n[k] + 0.0;  // + 0.0: -0.0 -> +0.0
         f.d = sign * d + 0.0;
+        for (int i = 0; i < f.nv; i++)
+            for (int k = 0; k < 3; k++) f.p[i][k] = comp(c[i], k);
         faces.push_back(f);
     };
     auto add_prims = [&](auto &&self, uint32_t hnd, const std::vector<const HostHittable *> &chain, uint32_t leaf, int box, const int *axis_of,
                          const int *end_of) -> void {
         const HostHittable &h = s.hittables[hnd - 1];
-        if (h.kind == HKind::Quad) {
+        if (h.kind == HKind::Quad || h.kind == HKind::Triangle) {
             add_face(h, chain, leaf, -1, 0, 0);
         } else if (h.kind == HKind::Sphere || h.kind == HKind::MovingSphere) {
             if (!chain.empty()) return;  // (an instanced sphere is not compared)
@@ -442,33 +490,55 @@ static bool has_coincident_primitives(const SceneImpl &s, const std::vector<uint
         for (size_t b = a + 1; b < spheres.size() && same(spheres[a], spheres[b]); b++)
             if (spheres[a].leaf != spheres[b].leaf) return true;
 
+    // Candidate pairs are faces whose plane offsets d differ by at most tol_d; what such a pair needs besides -- one plane, and
+    // rectangles, boxes or polygons that overlap -- fails for certain where the faces' extents along any one axis do not meet.  So
+    // the faces sorted by d are cut where two neighbours differ by more than tol_d (no pair crosses such a cut), and each piece is
+    // swept along the axis it extends farthest in: a flat mesh of n faces costs its neighbours' pairs, not n^2 / 2.
     std::sort(faces.begin(), faces.end(), [](const TieFace &a, const TieFace &b) { return a.d < b.d; });
-    const double tol_n = 1e-9, tol_d = 1e-9 * (1.0 + reach);
-    for (size_t a = 0; a < faces.size(); a++)
-        for (size_t b = a + 1; b < faces.size() && faces[b].d - faces[a].d <= tol_d; b++) {
-            const TieFace &x = faces[a], &y = faces[b];
-            if (x.leaf == y.leaf) continue;
-            bool same_plane = true;
-            if (x.exact && y.exact) {
-                same_plane = x.d == y.d && x.n[0] == y.n[0] && x.n[1] == y.n[1] && x.n[2] == y.n[2];
-            } else {
-                for (int k = 0; k < 3; k++) same_plane &= std::fabs(x.n[k] - y.n[k]) <= tol_n;
-            }
-            if (!same_plane) continue;
-            if (x.box >= 0 && y.box >= 0) {
-                const TieBox &p = boxes[(size_t)x.box], &q = boxes[(size_t)y.box];
-                bool area = true;
-                for (int k = 0; k < 3; k++)
-                    if (k != x.axis) area &= p.mn[k] < q.mx[k] && q.mn[k] < p.mx[k];
-                if (!area) continue;                                        // an edge or a corner at most
-                if (x.end != y.end && p.opaque && q.opaque) continue;      // a solid on either side
-                return true;
-            }
-            bool overlap = true;
-            for (int k = 0; k < 3; k++) overlap &= x.lo[k] - (x.exact ? 0.0 : 1e-4) <= y.hi[k] + (y.exact ? 0.0 : 1e-4) &&
-                                                   y.lo[k] - (y.exact ? 0.0 : 1e-4) <= x.hi[k] + (x.exact ? 0.0 : 1e-4);
-            if (overlap) return true;
+    const double tol_n = 1e-9, tol_d = 1e-9 * (1.0 + reach), sweep_pad = 2e-4;  // sweep_pad: the most two transformed faces allow
+    auto tie = [&](const TieFace &x, const TieFace &y) {
+        if (x.leaf == y.leaf || std::fabs(x.d - y.d) > tol_d) return false;
+        bool same_plane = true;
+        if (x.exact && y.exact) {
+            same_plane = x.d == y.d && x.n[0] == y.n[0] && x.n[1] == y.n[1] && x.n[2] == y.n[2];
+        } else {
+            for (int k = 0; k < 3; k++) same_plane &= std::fabs(x.n[k] - y.n[k]) <= tol_n;
         }
+        if (!same_plane) return false;
+        if (x.box >= 0 && y.box >= 0) {
+            const TieBox &p = boxes[(size_t)x.box], &q = boxes[(size_t)y.box];
+            bool area = true;
+            for (int k = 0; k < 3; k++)
+                if (k != x.axis) area &= p.mn[k] < q.mx[k] && q.mn[k] < p.mx[k];
+            if (!area) return false;                                        // an edge or a corner at most
+            if (x.end != y.end && p.opaque && q.opaque) return false;      // a solid on either side
+            return true;
+        }
+        bool overlap = true;
+        for (int k = 0; k < 3; k++) overlap &= x.lo[k] - (x.exact ? 0.0 : 1e-4) <= y.hi[k] + (y.exact ? 0.0 : 1e-4) &&
+                                               y.lo[k] - (y.exact ? 0.0 : 1e-4) <= x.hi[k] + (x.exact ? 0.0 : 1e-4);
+        if (!overlap) return false;
+        return (x.nv == 4 && y.nv == 4) || share_area(x, y);  // two quads: the rectangles' boxes; a triangle: the polygons
+    };
+    for (size_t first = 0; first < faces.size();) {
+        size_t last = first + 1;
+        while (last < faces.size() && faces[last].d - faces[last - 1].d <= tol_d) last++;
+        double lo[3] = {DBL_MAX, DBL_MAX, DBL_MAX}, hi[3] = {-DBL_MAX, -DBL_MAX, -DBL_MAX};
+        for (size_t k = first; k < last; k++)
+            for (int a = 0; a < 3; a++) {
+                lo[a] = std::min(lo[a], faces[k].lo[a]);
+                hi[a] = std::max(hi[a], faces[k].hi[a]);
+            }
+        int ax = 0;
+        for (int a = 1; a < 3; a++)
+            if (hi[a] - lo[a] > hi[ax] - lo[ax]) ax = a;
+        std::sort(faces.begin() + (ptrdiff_t)first, faces.begin() + (ptrdiff_t)last,
+                  [ax](const TieFace &a, const TieFace &b) { return a.lo[ax] < b.lo[ax]; });
+        for (size_t a = first; a < last; a++)
+            for (size_t b = a + 1; b < last && faces[b].lo[ax] <= faces[a].hi[ax] + sweep_pad; b++)
+                if (tie(faces[a], faces[b])) return true;
+        first = last;
+    }
     return false;
 }
 
@@ -525,7 +595,11 @@ struct Flattener {
         f.quads.push_back({h.q.x, h.q.y, h.q.z, h.u.x, h.u.y, h.u.z, h.v.x, h.v.y, h.v.z, h.w.x, h.w.y, h.w.z,
                            h.normal.x, h.normal.y, h.normal.z, h.plane_d});
         // RT_SCENE_PLAIN_QUADS (tests): every quad takes the general test, boxes stay lists of six quads
-        f.quad_aa.push_back(plain_quads ? AAQuad{} : axis_aligned(f.quads.back()));
+        // A triangle is the quad's row with the mark that selects its interior rule (flat_scene.h kQuadTriangle).
+        AAQuad aa{};
+        if (h.kind == HKind::Triangle) aa.code = kQuadTriangle;
+        else if (!plain_quads) aa = axis_aligned(f.quads.back());
+        f.quad_aa.push_back(aa);
         f.quad_mat.push_back(h.material - 1);
         return make_ref(REF_QUAD, (uint32_t)f.quads.size() - 1);
     }
@@ -597,7 +671,7 @@ struct Flattener {
         return out;
     }
 
-    static bool is_primitive(HKind k) { return k == HKind::Sphere || k == HKind::MovingSphere || k == HKind::Quad; }
+    static bool is_primitive(HKind k) { return k == HKind::Sphere || k == HKind::MovingSphere || k == HKind::Quad || k == HKind::Triangle; }
 
     // Collect the primitives of a (possibly nested) list in visiting order.  A closest-hit scan over a
     // nested list equals the scan over its flattened sequence (R/HittableList.h:39-57 keeps one running
@@ -789,7 +863,7 @@ struct Flattener {
                 HKind k = s.hittables[p - 1].kind;
                 all_s &= k == HKind::Sphere;
                 all_m &= k == HKind::MovingSphere;
-                all_q &= k == HKind::Quad;
+                all_q &= k == HKind::Quad || k == HKind::Triangle;  // one table, one loop (GEOM_QUADS); never a box: box_of_six reads the codes
             }
             obj.count = (uint32_t)prims.size();
             if (prims.size() >= kSubBvhMinPrims && !has_coincident_primitives(s, prims) && !has_moving_centre(s, prims)) {
@@ -1327,7 +1401,7 @@ int flatten_scene(SceneImpl &s)
         f.world_items.push_back(ref);
         f.leaf_boxes.push_back(s.hittables[h - 1].box);
         const HKind hk = s.hittables[h - 1].kind;
-        f.leaf_kinds.push_back(hk == HKind::Sphere ? 0 : (hk == HKind::MovingSphere ? 1 : (hk == HKind::Quad ? 2 : 3)));
+        f.leaf_kinds.push_back(hk == HKind::Sphere ? 0 : (hk == HKind::MovingSphere ? 1 : (hk == HKind::Quad ? 2 : (hk == HKind::Triangle ? 4 : 3))));
     }
     if (f.world_kind == WORLD_BVH) {
         if (world.tree.empty()) return fail(RT_ERR_INVALID, "BvhNode world has no nodes");
@@ -1733,6 +1807,144 @@ rt_handle rt_quad(rt_scene *s, const double q[3], const double u[3], const doubl
     h.box = box_merge(d1, d2);
     return push_h(S(s), std::move(h));
 }
+// R/Quad.h's primitive with the interior rule its own comment (:86-88) names.  Everything but the box is the quad's.
+rt_handle rt_triangle(rt_scene *s, const double q[3], const double u[3], const double v[3], rt_handle material)
+{
+    if (!valid_mat(S(s), material) || !q || !u || !v) {
+        set_error("rt_triangle: invalid material handle or null vector");
+        return 0;
+    }
+    HostHittable h{};
+    h.kind = HKind::Triangle;
+    h.q = mk(q[0], q[1], q[2]);
+    h.u = mk(u[0], u[1], u[2]);
+    h.v = mk(v[0], v[1], v[2]);
+    h.material = material;
+    D3 n = cross(h.u, h.v);  // Quad.h:33-37
+    h.normal = normalize(n);
+    h.plane_d = dot(h.normal, h.q);
+    h.w = over(n, dot(n, n));
+    // per axis the min and max of the three corners as computed, through the quad's corner-box helper (thin axes padded)
+    const D3 b = add(h.q, h.u), c = add(h.q, h.v);
+    h.box = box_from_corners(mk(std::fmin(h.q.x, std::fmin(b.x, c.x)), std::fmin(h.q.y, std::fmin(b.y, c.y)), std::fmin(h.q.z, std::fmin(b.z, c.z))),
+                             mk(std::fmax(h.q.x, std::fmax(b.x, c.x)), std::fmax(h.q.y, std::fmax(b.y, c.y)), std::fmax(h.q.z, std::fmax(b.z, c.z))));
+    return push_h(S(s), std::move(h));
+}
+rt_handle rt_triangle_mesh(rt_scene *s, const double *vertices, int n_vertices, const int32_t *indices, int n_triangles, rt_handle material,
+                           rt_handle *triangles_out)
+{
+    if (!valid_mat(S(s), material) || !vertices || !indices || n_vertices < 3 || n_triangles < 1) {
+        set_error("rt_triangle_mesh: invalid material handle, null array, fewer than 3 vertices or no triangle");
+        return 0;
+    }
+    for (size_t k = 0; k < 3 * (size_t)n_triangles; k++)
+        if (indices[k] < 0 || indices[k] >= n_vertices) {
+            set_error("rt_triangle_mesh: index " + std::to_string(indices[k]) + " outside [0, " + std::to_string(n_vertices) + ")");
+            return 0;
+        }
+    std::vector<rt_handle> tris((size_t)n_triangles);
+    for (size_t k = 0; k < tris.size(); k++) {
+        const double *a = vertices + 3 * (size_t)indices[3 * k], *b = vertices + 3 * (size_t)indices[3 * k + 1],
+                     *c = vertices + 3 * (size_t)indices[3 * k + 2];
+        const double u[3] = {b[0] - a[0], b[1] - a[1], b[2] - a[2]}, v[3] = {c[0] - a[0], c[1] - a[1], c[2] - a[2]};
+        tris[k] = rt_triangle(s, a, u, v, material);
+        if (!tris[k]) return 0;
+    }
+    if (triangles_out) std::memcpy(triangles_out, tris.data(), sizeof(rt_handle) * tris.size());  // input order: rt_bvh_node permutes its own copy
+    return rt_bvh_node(s, tris.data(), n_triangles);
+}
+
+// Wavefront OBJ, positions and faces only.
+int rt_obj_load(const char *path, double **vertices, int *n_vertices, int32_t **indices, int *n_triangles)
+{
+    if (!path || !vertices || !n_vertices || !indices || !n_triangles) return fail(RT_ERR_INVALID, "rt_obj_load: null argument");
+    *vertices = nullptr;
+    *indices = nullptr;
+    *n_vertices = *n_triangles = 0;
+    FILE *fp = std::fopen(path, "rb");
+    if (!fp) return fail(RT_ERR_INVALID, std::string("rt_obj_load: cannot open ") + path);
+    std::string text;
+    char buf[1 << 16];
+    for (size_t got; (got = std::fread(buf, 1, sizeof buf, fp)) > 0;) text.append(buf, got);
+    const bool read_error = std::ferror(fp) != 0;
+    std::fclose(fp);
+    if (read_error) return fail(RT_ERR_INVALID, std::string("rt_obj_load: cannot read ") + path);
+
+    std::vector<double> vs;
+    std::vector<long long> fs;  // corner indices, 0-based; a positive one may name a vertex that follows (checked at the end)
+    size_t line_no = 0;
+    auto bad = [&](const char *what) { return fail(RT_ERR_INVALID, std::string("rt_obj_load: ") + path + ":" + std::to_string(line_no) + ": " + what); };
+    for (size_t pos = 0; pos < text.size();) {
+        size_t eol = text.find('\n', pos);
+        if (eol == std::string::npos) eol = text.size();
+        std::string line = text.substr(pos, eol - pos);
+        pos = eol + 1;
+        line_no++;
+        const size_t hash = line.find('#');
+        if (hash != std::string::npos) line.resize(hash);
+        const char *c = line.c_str();
+        while (*c == ' ' || *c == '\t') c++;
+        const bool is_v = c[0] == 'v' && (c[1] == ' ' || c[1] == '\t'), is_f = c[0] == 'f' && (c[1] == ' ' || c[1] == '\t');
+        if (!is_v && !is_f) continue;  // vn, vt, g, o, s, usemtl, mtllib, ...: skipped
+        c += 2;
+        if (is_v) {
+            const char *line_end = line.c_str() + line.size();
+            for (int k = 0; k < 3; k++) {  // std::from_chars: the "C" number format whatever locale the host program has set
+                while (*c == ' ' || *c == '\t') c++;
+                if (*c == '+') c++;
+                double x = 0.0;
+                const auto parsed = std::from_chars(c, line_end, x);
+                if (parsed.ec != std::errc() || parsed.ptr == c) return bad("a vertex needs three numbers");
+                vs.push_back(x);
+                c = parsed.ptr;
+            }
+            continue;
+        }
+        std::vector<long long> corner;
+        for (;;) {
+            while (*c == ' ' || *c == '\t' || *c == '\r') c++;
+            if (!*c) break;
+            char *end = nullptr;
+            const long long i = std::strtoll(c, &end, 10);
+            if (end == c || i == 0) return bad("a face corner needs a non-zero vertex index");
+            const long long n_so_far = (long long)(vs.size() / 3);
+            if (i < -n_so_far) return bad("relative vertex index out of range");
+            corner.push_back(i > 0 ? i - 1 : n_so_far + i);
+            c = end;
+            while (*c && *c != ' ' && *c != '\t' && *c != '\r') c++;  // "/j", "/j/k", "//k": texture and normal indices are not read
+        }
+        if (corner.size() < 3) return bad("a face needs three corners");
+        for (size_t k = 1; k + 1 < corner.size(); k++) {  // a polygon is fanned from its first corner
+            fs.push_back(corner[0]);
+            fs.push_back(corner[k]);
+            fs.push_back(corner[k + 1]);
+        }
+    }
+    if (fs.empty()) return fail(RT_ERR_INVALID, std::string("rt_obj_load: ") + path + " has no face");
+    const long long nv = (long long)(vs.size() / 3);
+    for (long long i : fs)
+        if (i < 0 || i >= nv) return fail(RT_ERR_INVALID, std::string("rt_obj_load: ") + path + ": vertex index out of range");
+    if (fs.size() / 3 > (size_t)INT32_MAX || nv > (long long)INT32_MAX) return fail(RT_ERR_INVALID, "rt_obj_load: mesh too large");
+    double *vout = (double *)std::malloc(vs.size() * sizeof(double));
+    int32_t *iout = (int32_t *)std::malloc(fs.size() * sizeof(int32_t));
+    if (!vout || !iout) {
+        std::free(vout);
+        std::free(iout);
+        return fail(RT_ERR_INVALID, "rt_obj_load: out of memory");
+    }
+    std::memcpy(vout, vs.data(), vs.size() * sizeof(double));
+    for (size_t k = 0; k < fs.size(); k++) iout[k] = (int32_t)fs[k];
+    *vertices = vout;
+    *indices = iout;
+    *n_vertices = (int)nv;
+    *n_triangles = (int)(fs.size() / 3);
+    return RT_OK;
+}
+void rt_mesh_free(double *vertices, int32_t *indices)
+{
+    std::free(vertices);
+    std::free(indices);
+}
 rt_handle rt_translate(rt_scene *s, rt_handle object, double ox, double oy, double oz)
 {
     HostHittable *c = get_h(S(s), object);
@@ -1962,6 +2174,7 @@ int rt_scene_get_info(rt_scene *s, rt_scene_info *out)
                                   f.objects.size() * sizeof(ObjectRec) + f.xforms.size() * sizeof(Xform) +
                                   f.materials.size() * sizeof(MaterialRec));
     out->image_bytes = (uint32_t)f.image_bytes.size();
+    for (const AAQuad &a : f.quad_aa) out->reserved[0] += a.code == kQuadTriangle;  // n_triangles (counted in n_quads too)
     return RT_OK;
 }
 

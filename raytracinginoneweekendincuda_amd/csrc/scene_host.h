@@ -18,7 +18,8 @@ struct Box {  // R/AABB.h:16-22: three closed intervals
     double lo[3], hi[3];
 };
 
-enum class HKind : uint8_t { Sphere, MovingSphere, Quad, Translate, RotateY, List, Bvh, Medium };
+enum class HKind : uint8_t { Sphere, MovingSphere, Quad, Translate, RotateY, List, Bvh, Medium,
+                             Triangle };  // the quad's fields and plane constants; corners Q, Q + u, Q + v
 
 struct HostHittable {
     HKind kind;
@@ -26,7 +27,7 @@ struct HostHittable {
     uint32_t material = 0;             // handle (1-based) for primitives; phase function for media
     D3 c0{}, c1{};                     // sphere centre(s)
     double t0 = 0, t1 = 0, radius = 0;
-    D3 q{}, u{}, v{}, w{}, normal{};   // quad
+    D3 q{}, u{}, v{}, w{}, normal{};   // quad, triangle
     double plane_d = 0;
     uint32_t child = 0;                // instance / medium: wrapped hittable handle
     D3 offset{};
@@ -92,7 +93,7 @@ struct FlatScene {
     std::vector<uint32_t> world_items;   // leaf refs in final order (both world kinds)
     std::vector<uint32_t> node_leaf_pos; // WORLD_BVH: per world node, the positions in world_items of a bottom node's leaves a and b (ray queries)
     std::vector<Box> leaf_boxes;         // introspection
-    std::vector<int> leaf_kinds;         // introspection: the leaf's kind as constructed (0 sphere, 1 moving sphere, 2 quad, 3 composite)
+    std::vector<int> leaf_kinds;         // introspection: the leaf's kind as constructed (0 sphere, 1 moving sphere, 2 quad, 3 composite, 4 triangle)
     std::vector<MaterialRec> materials;
     std::vector<TextureRec> textures;
     std::vector<ImageRec> images;

@@ -1,8 +1,10 @@
 // scenes.cpp -- the reference's ten scenes (sceneId 0..9, R/kernel.cu:199-517) plus the two benchmark
-// variants, written against the construction API exactly as a user of the reference would port
+// variants and the mesh scene (12), written against the construction API exactly as a user of the reference would port
 // CreateWorld.  Random draws the reference writes inside constructor argument lists are taken here
 // one statement at a time, left to right.
 #include <cmath>
+#include <map>
+#include <utility>
 
 #include "../../include/rtow.hpp"
 #include "scene_host.h"
@@ -87,6 +89,43 @@ void cornell_boxes(Scene &w, Material white, Hittable &box1, Hittable &box2)
     box2 = w.MakeBox(Point3(0, 0, 0), Point3(165, 165, 165), white);
     box2 = w.RotateY(box2, -18.0);
     box2 = w.Translate(box2, Vector3(130, 0, 65));
+}
+
+// An icosahedron with its twelve vertices on the sphere of `radius` about the origin, each face split in four `levels` times with the
+// new vertices pushed out onto the sphere: 20 * 4^levels triangles, outward winding.
+void icosphere(int levels, double radius, std::vector<Point3> &vertices, std::vector<int32_t> &indices)
+{
+    const double g = (1.0 + std::sqrt(5.0)) / 2.0;
+    const double base[12][3] = {{-1, g, 0}, {1, g, 0}, {-1, -g, 0}, {1, -g, 0}, {0, -1, g}, {0, 1, g},
+                                {0, -1, -g}, {0, 1, -g}, {g, 0, -1}, {g, 0, 1}, {-g, 0, -1}, {-g, 0, 1}};
+    static const int32_t faces[20][3] = {{0, 11, 5}, {0, 5, 1}, {0, 1, 7}, {0, 7, 10}, {0, 10, 11}, {1, 5, 9}, {5, 11, 4},
+                                         {11, 10, 2}, {10, 7, 6}, {7, 1, 8}, {3, 9, 4}, {3, 4, 2}, {3, 2, 6}, {3, 6, 8},
+                                         {3, 8, 9}, {4, 9, 5}, {2, 4, 11}, {6, 2, 10}, {8, 6, 7}, {9, 8, 1}};
+    auto on_sphere = [radius](double x, double y, double z) {
+        const double k = radius / std::sqrt(x * x + y * y + z * z);
+        return Point3(k * x, k * y, k * z);
+    };
+    vertices.clear();
+    for (const auto &b : base) vertices.push_back(on_sphere(b[0], b[1], b[2]));
+    indices.assign(&faces[0][0], &faces[0][0] + 60);
+    for (int level = 0; level < levels; level++) {
+        std::map<std::pair<int32_t, int32_t>, int32_t> mid_of;
+        auto mid = [&](int32_t a, int32_t b) {
+            const auto key = std::make_pair(a < b ? a : b, a < b ? b : a);
+            auto it = mid_of.find(key);
+            if (it != mid_of.end()) return it->second;
+            const Point3 &p = vertices[(size_t)a], &q = vertices[(size_t)b];
+            vertices.push_back(on_sphere(p.x + q.x, p.y + q.y, p.z + q.z));
+            return mid_of[key] = (int32_t)vertices.size() - 1;
+        };
+        std::vector<int32_t> next;
+        for (size_t k = 0; k < indices.size(); k += 3) {
+            const int32_t a = indices[k], b = indices[k + 1], c = indices[k + 2];
+            const int32_t ab = mid(a, b), bc = mid(b, c), ca = mid(c, a);
+            next.insert(next.end(), {a, ab, ca, b, bc, ab, c, ca, bc, ab, bc, ca});
+        }
+        indices.swap(next);
+    }
 }
 
 } // namespace
@@ -235,8 +274,26 @@ extern "C" int rt_scene_build_builtin(rt_scene *s, int scene_id, int world_kind,
             view.vfov = 90.0;
             break;
         }
+        case 12: {  // scene 7's walls, light and camera; two triangle meshes stand where its boxes stand
+            CornellMaterials m = cornell_materials(w, 15.0);
+            list.push_back(w.Quad(Vector3(555, 0, 0), Vector3(0, 555, 0), Vector3(0, 0, 555), m.green));
+            list.push_back(w.Quad(Vector3(0, 0, 0), Vector3(0, 555, 0), Vector3(0, 0, 555), m.red));
+            list.push_back(w.Quad(Vector3(343, 554, 332), Vector3(-130, 0, 0), Vector3(0, 0, -105), m.light));
+            list.push_back(w.Quad(Vector3(0, 0, 0), Vector3(555, 0, 0), Vector3(0, 0, 555), m.white));
+            list.push_back(w.Quad(Vector3(555, 555, 555), Vector3(-555, 0, 0), Vector3(0, 0, -555), m.white));
+            list.push_back(w.Quad(Vector3(0, 0, 555), Vector3(555, 0, 0), Vector3(0, 555, 0), m.white));
+            std::vector<Point3> vertices;
+            std::vector<int32_t> indices;
+            icosphere(2, 100.0, vertices, indices);  // 320 triangles
+            list.push_back(w.Translate(w.TriangleMesh(vertices, indices, m.white), Vector3(347.5, 100.0, 377.5)));
+            icosphere(0, 90.0, vertices, indices);   // the icosahedron itself
+            Hittable solid = w.TriangleMesh(vertices, indices, w.Metal(Color(0.8, 0.85, 0.88), 0.0));
+            list.push_back(w.Translate(w.RotateY(solid, -18.0), Vector3(212.5, 90.0, 147.5)));
+            cornell_view(view);
+            break;
+        }
         default:
-            return rtow::fail(RT_ERR_INVALID, "rt_scene_build_builtin: scene_id must be 0..11");
+            return rtow::fail(RT_ERR_INVALID, "rt_scene_build_builtin: scene_id must be 0..12");
         }
 
         // R/kernel.cu:523-528: BvhNode(list, 0, i, ...) as world; "no BVH" = HittableList(list, i)
