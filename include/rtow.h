@@ -351,16 +351,16 @@ typedef struct rt_launch_plan {
      * 0xFFFFFFFF = the kernel reads it from global memory; lds_table_bytes[k] = the table's unpadded size, 0 for an empty table and
      * for one this instantiation never considers. */
     int32_t lds_front_bytes;
-    uint32_t lds_table_offset[16], lds_table_bytes[16];
+    uint32_t lds_table_offset[17], lds_table_bytes[17];
     /* The rehearsal's samples: probe_keeps = 1 where the frame launch resumes from them (it renders samples_per_pixel - probe_spp
      * more of every pixel), 0 where it renders every sample again (adaptive films) and where there is no rehearsal.  probe_ray_cap:
      * rays at which a rehearsed pixel stops at once, its place on the longest-chain list being decided (super_threshold; 0: no
      * cap) -- such a pixel keeps nothing and the frame launch renders all of its samples. */
     int32_t probe_keeps, probe_ray_cap;
 } rt_launch_plan;
-#define RT_LDS_TABLES 16
+#define RT_LDS_TABLES 17
 #define RT_LDS_TABLE_NAMES "quad_aa boxes objects xforms media materials perlin spheres_tab group_boxes mspheres msphere_aux " \
-                           "sphere_aux fast_order seg_media seg_cand park"
+                           "sphere_aux fast_order seg_media seg_cand park scan_pairs"
 RTOW_API int rt_plan_launch(rt_scene *s, const rt_render_params *params, int num_cus, int adaptive, rt_launch_plan *out);
 /* Introspection for tests: the rays the rehearsal of the film's last launch booked for every pixel, full W x H like
  * rt_film_download_sample_counts -- at least rt_launch_plan.probe_ray_cap for a pixel the cap stopped.  RT_ERR_STATE where that

@@ -93,13 +93,13 @@ class LaunchPlan(C.Structure):
         "node_burst", "park_ratio", "leaf_batch", "object_batch", "rounds", "shade_batch", "ray_budget",
         "rank_tiles", "pixel_classes", "probe_spp", "tile_flatness_x8", "heavy_threshold", "super_threshold",
         "near_percent", "near_neighbours", "heavy_waves", "heavy_ppw", "super_ppw", "heavy_priority", "adaptive_ppw",
-        "lds_front_bytes")] + [("lds_table_offset", C.c_uint32 * 16), ("lds_table_bytes", C.c_uint32 * 16),
+        "lds_front_bytes")] + [("lds_table_offset", C.c_uint32 * 17), ("lds_table_bytes", C.c_uint32 * 17),
                                ("probe_keeps", C.c_int32), ("probe_ray_cap", C.c_int32)]
 
 
 # the order of rt_launch_plan.lds_table_offset / lds_table_bytes (include/rtow.h RT_LDS_TABLE_NAMES, csrc/launch_plan.h LdsTable)
 LDS_TABLES = ("quad_aa", "boxes", "objects", "xforms", "media", "materials", "perlin", "spheres_tab", "group_boxes", "mspheres",
-              "msphere_aux", "sphere_aux", "fast_order", "seg_media", "seg_cand", "park")
+              "msphere_aux", "sphere_aux", "fast_order", "seg_media", "seg_cand", "park", "scan_pairs")
 LDS_GLOBAL = 0xFFFFFFFF   # lds_table_offset of a table the kernel reads from global memory
 
 

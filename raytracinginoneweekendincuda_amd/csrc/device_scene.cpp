@@ -764,6 +764,17 @@ static void print_phases(const FilmImpl &f)
                          "pixel-parallel scan's (%.0f of %.0f per pass)\n", (double)c[96 + 15] / passes, (double)c[64 + 15] / passes,
                          100.0 * c[32 + 13] / c[32 + 0], (double)c[32 + 13] / passes, (double)c[32 + 0] / passes);
         }
+        name[16] = name[17] = name[18] = "";  // slots 16, 17, 18: the counts of the grouped scan (render.hip GroupedSums)
+        const double gp = (double)c[96 + 16];
+        if (gp > 0) {
+            std::fprintf(stderr, "grouped: %.0f passes through the filter, %.2f rays per pass, exact-test blocks executed per pass %.2f\n", gp,
+                         (double)c[64 + 16] / gp, (double)c[32 + 16] / gp);
+            std::fprintf(stderr, "grouped: survivors (lanes tested) per pass %.2f, largest per-lane count per pass %.2f, drains per pass %.2f\n",
+                         (double)c[32 + 17] / gp, (double)c[64 + 17] / gp, (double)c[96 + 17] / gp);
+            std::fprintf(stderr, "grouped: cycles per pass: filter %.0f, exact tests %.0f (%.1f %% and %.1f %% of the cooperative scans' %.0f)\n",
+                         (double)c[64 + 18] / gp, (double)c[32 + 18] / gp, 100.0 * c[64 + 18] / c[32 + 1], 100.0 * c[32 + 18] / c[32 + 1],
+                         (double)c[32 + 1] / (double)c[96 + 1]);
+        }
     }
     const double total = (double)c[7];
     for (int k = 0; k < 24; k++)

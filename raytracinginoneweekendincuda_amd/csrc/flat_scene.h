@@ -265,6 +265,7 @@ struct DeviceScene {
         lds_mspheres, lds_msphere_aux, lds_sphere_aux;  // the primitive tables of a sphere world (library-tree kernel, one workgroup per CU)
     uint32_t lds_fast_order, lds_seg_media, lds_seg_cand;  // segmented walk: always staged (launch_plan.cpp lds_layout)
     uint32_t lds_park;  // parked path state of the instanced-list kernel (render.hip Traits::PARK)
+    uint32_t lds_scan_pairs;  // sphere-list kernel: the packed fp32 rows of the grouped scan, behind the planes (kNone: its filter stays fp64)
     uint32_t flags;
 };
 

@@ -114,6 +114,15 @@ LdsLayout lds_layout(const KernelProps &k, const DeviceScene &sc)
             l.lds_spheres = 1;
         }
         l.front = lds;
+        // the grouped scan's packed fp32 rows (render.hip scan_grouped), 16 B a padded row in two planes of 16 B a pair, behind the fp64
+        // planes: only with them, and only where the block stays within kSharedCuBudget -- the third workgroup per CU is worth more
+        // than the filter (a block the planes alone carry past that budget would pass 64 KB with the rows)
+        const size_t pair_rows = (size_t)((sc.n_spheres + 63u) & ~63u) * 2 * sizeof(float) * 2;
+        if (l.lds_spheres && lds + pair_rows <= kSharedCuBudget) {
+            l.scan_pairs = (uint32_t)lds;
+            lds += pair_rows;
+            l.table_bytes[T_SCAN_PAIRS] = (uint32_t)pair_rows;
+        }
     }
     if (k.park) {  // the parked path state, one entry per thread (list worlds stage no tables: their rows come through scalar loads)
         off = up16(lds);
@@ -429,7 +438,8 @@ rt_launch_plan plan_frame(int kind, int lds_bytes, const FilmGeometry &film, int
 static void show_layout(const LdsLayout &l, rt_launch_plan &plan)
 {
     const uint32_t offsets[kLdsTables] = {l.quad_aa, l.boxes, l.objects, l.xforms, l.media, l.materials, l.perlin, l.spheres_tab,
-                                          l.group_boxes, l.mspheres, l.msphere_aux, l.sphere_aux, l.fast_order, l.seg_media, l.seg_cand, l.park};
+                                          l.group_boxes, l.mspheres, l.msphere_aux, l.sphere_aux, l.fast_order, l.seg_media, l.seg_cand, l.park,
+                                          l.scan_pairs};
     plan.lds_front_bytes = (int)l.front;
     for (int t = 0; t < kLdsTables; t++) {
         plan.lds_table_offset[t] = offsets[t];

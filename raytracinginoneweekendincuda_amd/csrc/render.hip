@@ -454,6 +454,10 @@ DEV bool prim_test(const DeviceScene &sc, uint32_t ref, const Ray &r, double a, 
 #ifndef RT_PHASES
 #define RT_PHASES 0  // diagnostic build: per-phase wave cycles and lane occupancy, summed into ray_counter[7] and [32..119]
 #endif
+#if RT_PHASES && (RT_FEATURES || RT_QUERY || RT_RADIANCE)
+#undef RT_PHASES
+#define RT_PHASES 0  // the phases are render_kernel's: the feature and query units of a diagnostic build are the ordinary ones
+#endif
 #if RT_PHASES
 #define PH_BEGIN() const unsigned long long ph_t0 = __builtin_readcyclecounter()
 #define PH_END(k, cond)                                                   \
@@ -497,9 +501,19 @@ struct ScanSums {
 };
 #define SS_ARG , ScanSums &ss
 #define SS_PASS , ss
+// The same for one pass of the grouped scan (scan_grouped; wave-uniform as well).  The render loop adds them to the wave-level phase
+// slots 16, 17 and 18, which no sphere-list kernel uses otherwise (device_scene.cpp prints them as the grouped table).
+struct GroupedSums {
+    uint32_t rays, tests, survivors, lane_max;  // L; exact-test blocks the wave executed; lanes that went on to the exact test; largest count of one lane
+    uint32_t drains, filter_cycles, test_cycles;  // drain calls; cycles in the filter's part and in the exact tests' part of the pass
+};
+#define GS_ARG , GroupedSums &gs
+#define GS_PASS , gs
 #else
 #define SS_ARG
 #define SS_PASS
+#define GS_ARG
+#define GS_PASS
 #define PH_COUNT(k) do { } while (0)
 #define PH_SUB_END(k) do { } while (0)
 #endif
@@ -1856,6 +1870,7 @@ DEV ScanRay32 scan_ray32(const Ray &r, double a, double reach)
 // of a trip's second half directly in front of the wait that retires them; a volatile one keeps its place among the branches, half
 // a trip of filter arithmetic ahead of its wait.  It is still one s_load_dwordx8 from the (immutable) table.
 typedef float v8f __attribute__((ext_vector_type(8)));
+typedef float v4f __attribute__((ext_vector_type(4)));
 DEV SphereScanPair load_scan_pair(const SphereScanPair *table, uint32_t byte_off, uint32_t ahead)
 {
     const RT_CONST char *p = ((const RT_CONST char *)(uintptr_t)table + byte_off) + ahead;
@@ -2131,6 +2146,15 @@ struct SphereView {
     const SphereGeom *global;
     uint32_t n, n_padded;
     bool in_lds;
+    // The grouped scan's packed fp32 filter rows, two planes of 16 B a pair behind the fp64 planes: {cx0, cx1, cy0, cy1} of pair j at
+    // pairs_off + 16 j, {cz0, cz1, k0, k1} at pairs_off + 16 (n_padded / 2 + j), in the general form (a run's rows swapped back).
+    // Lane s of a group reads pair base + s with one ds_read_b128 per plane: the lanes of a group read consecutive 16-byte slots and
+    // all groups the same ones.  Bank of a slot = 4 (slot mod 16) ... + 3; the instruction serves lanes {0-3, 12-15, 20-27},
+    // {4-11, 16-19, 28-31} and the same two sets + 32 in one cycle each, and for every g = 2 ... 64 the slots such a set reads are
+    // distinct mod 16 or equal (a broadcast): g >= 16 reads slots {0-3, 12-15, 4-11} (+16, +32, +48) of the batch, g = 8 slots
+    // 0-7 twice, g = 4, 2, 1 fewer.  No bank conflicts.
+    uint32_t pairs_off;   // 0: not staged, or RT_FLAG_FILTER_FP64 -- the grouped scan filters in fp64
+    double reach32;       // DeviceScene::scan_reach32
     DEV double plane(uint32_t p, uint32_t k) const
     {
         return reinterpret_cast<const double *>(lds_raw + planes_off)[p * n_padded + k];
@@ -2277,7 +2301,7 @@ DEV void min_with_lane(double &t, uint32_t &k, int partner)
 // (t, index) per group serves all the rays at once.  Same winner as scan_cooperative (and as the sequential scan),
 // at 1/L of its per-ray bookkeeping; against the pixel-parallel scan every lane does 1/g of the sphere tests.
 DEV void scan_grouped(const SphereView &sv, uint32_t lane, unsigned long long todo, const Ray &ray, double tmin, double tmax,
-                      HitInfo &best, bool &hit)
+                      HitInfo &best, bool &hit GS_ARG)
 {
     const int L = __popcll(todo);
     int log2m = 0;
@@ -2301,10 +2325,79 @@ DEV void scan_grouped(const SphereView &sv, uint32_t lane, unsigned long long to
     const double a = dot(r.d, r.d);
     double bt = tmax;
     uint32_t bk = kNone;
-    if (!sv.exact) {
+    if (!sv.exact && sv.pairs_off) {
+        // The packed fp32 filter (filter_pairs' general form, operation for operation) over PAIRS: lane s of a group takes pairs s,
+        // s + g, ... = spheres 2 s, 2 s + 1, 2 (s + g), ...: still ascending, each survivor tested against the hit of the one before.
+        const ScanRayPairs f = scan_ray_pairs(scan_ray32(r, a, sv.reach32));
+        const uint32_t n_pairs = sv.n_padded / 2u;
+        const v4f *rows = reinterpret_cast<const v4f *>(lds_raw + sv.pairs_off);
+#if RT_PHASES
+        uint32_t gs_mine = 0;
+        gs.rays = (uint32_t)L;
+#endif
+        for (uint32_t base = 0; base < n_pairs; base += 2u * g) {
+            v2f fs[2], fq[2], fk[2];
+#if RT_PHASES
+            const unsigned long long gs_t0 = __builtin_readcyclecounter();
+#endif
+#pragma unroll
+            for (int h = 0; h < 2; h++) {
+                uint32_t j = base + g * h + s;
+                j = j < n_pairs ? j : n_pairs - 1u;  // keeps the address inside the rows
+                const v4f lo = rows[j], hi = rows[n_pairs + j];
+                const v2f cx = {lo.x, lo.y}, cy = {lo.z, lo.w}, cz = {hi.x, hi.y};
+                fk[h] = v2f{hi.z, hi.w};
+                fs[h] = __builtin_elementwise_fma(cz, f.uz, __builtin_elementwise_fma(cy, f.uy, cx * f.ux));
+                fq[h] = __builtin_elementwise_fma(fs[h], fs[h], __builtin_elementwise_fma(f.pz, cz, __builtin_elementwise_fma(f.py, cy, __builtin_elementwise_fma(f.px, cx, f.nt))));
+            }
+            const float sv4[4] = {fs[0].x, fs[0].y, fs[1].x, fs[1].y}, qv4[4] = {fq[0].x, fq[0].y, fq[1].x, fq[1].y};
+            const float kv4[4] = {fk[0].x, fk[0].y, fk[1].x, fk[1].y};
+#if RT_PHASES
+            const unsigned long long gs_t1 = __builtin_readcyclecounter();
+#pragma unroll
+            for (int u = 0; u < 4; u++) {  // a block executes for a slot some lane passed; a lane behind leaves it before the test proper
+                const bool tested = 2u * (base + g * (uint32_t)(u >> 1) + s) + (uint32_t)(u & 1) < sv.n && qv4[u] > kv4[u];
+                const unsigned long long m = __ballot(tested);
+                gs.tests += m ? 1u : 0u;
+                gs.survivors += (uint32_t)__popcll(m);
+                gs_mine += tested ? 1u : 0u;
+            }
+            const unsigned long long gs_t2 = __builtin_readcyclecounter();
+            gs.filter_cycles += (uint32_t)(gs_t1 - gs_t0);
+#endif
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+                const uint32_t k = 2u * (base + g * (uint32_t)(u >> 1) + s) + (uint32_t)(u & 1);
+                if (k < sv.n && qv4[u] > kv4[u]) {
+                    const float bu = f.od - sv4[u];
+                    const bool behind = bu > f.root_m && __builtin_fmaf(bu, bu, kv4[u] - qv4[u]) > 0.0f;  // k = -inf (always passes): never behind
+                    double t;
+                    if (!behind && sphere_test(r.o - mk(sv.plane(0, k), sv.plane(1, k), sv.plane(2, k)), r.d, a, sv.plane(3, k), tmin, bt, t)) {
+                        bt = t;
+                        bk = k;
+                    }
+                }
+            }
+#if RT_PHASES
+            asm volatile("" ::"v"(bt), "v"(bk));
+            gs.test_cycles += (uint32_t)(__builtin_readcyclecounter() - gs_t2);
+#endif
+        }
+#if RT_PHASES
+        for (int off = 32; off > 0; off >>= 1) gs_mine = max(gs_mine, (uint32_t)__shfl_xor((int)gs_mine, off, 64));
+        gs.lane_max = gs_mine;
+#endif
+    } else if (!sv.exact) {
         const ScanRay f = scan_ray(r, a, sv.reach);
+#if RT_PHASES
+        uint32_t gs_mine = 0;
+        gs.rays = (uint32_t)L;
+#endif
         for (uint32_t base = 0; base < sv.n_padded; base += 4u * g) {
             bool pass[4];
+#if RT_PHASES
+            const unsigned long long gs_t0 = __builtin_readcyclecounter();
+#endif
 #pragma unroll
             for (int u = 0; u < 4; u++) {
                 uint32_t k = base + g * u + s;
@@ -2313,6 +2406,19 @@ DEV void scan_grouped(const SphereView &sv, uint32_t lane, unsigned long long to
                 const double fs = filter_s(f, cx, cy, cz);
                 pass[u] = filter_q(f, fs, cx, cy, cz) > sv.plane(4, k);
             }
+#if RT_PHASES
+            const unsigned long long gs_t1 = __builtin_readcyclecounter();  // behind the compares: the ballots below read their masks
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+                const bool tested = base + g * u + s < sv.n && pass[u];
+                const unsigned long long m = __ballot(tested);
+                gs.tests += m ? 1u : 0u;
+                gs.survivors += (uint32_t)__popcll(m);
+                gs_mine += tested ? 1u : 0u;
+            }
+            const unsigned long long gs_t2 = __builtin_readcyclecounter();
+            gs.filter_cycles += (uint32_t)(gs_t1 - gs_t0);
+#endif
 #pragma unroll
             for (int u = 0; u < 4; u++) {
                 const uint32_t k = base + g * u + s;
@@ -2324,7 +2430,15 @@ DEV void scan_grouped(const SphereView &sv, uint32_t lane, unsigned long long to
                     }
                 }
             }
+#if RT_PHASES
+            asm volatile("" ::"v"(bt), "v"(bk));
+            gs.test_cycles += (uint32_t)(__builtin_readcyclecounter() - gs_t2);
+#endif
         }
+#if RT_PHASES
+        for (int off = 32; off > 0; off >>= 1) gs_mine = max(gs_mine, (uint32_t)__shfl_xor((int)gs_mine, off, 64));
+        gs.lane_max = gs_mine;
+#endif
     } else
     for (uint32_t base = 0; base < sv.n_padded; base += 4u * g) {
         double b[4], c[4], disc[4];
@@ -3108,6 +3222,30 @@ __global__ __launch_bounds__(T::BLOCK, T::MIN_WAVES) void render_kernel(DeviceSc
                 planes[k] = g.cx; planes[np + k] = g.cy; planes[2 * np + k] = g.cz; planes[3 * np + k] = g.r2;
                 planes[4 * np + k] = sc.sphere_scan[k < sv.n ? k : 0].k;
             }
+            if (sc.lds_scan_pairs != kNone && sc.lds_scan_pairs != 0u && !a.filter_fp64 && !sv.exact) {
+                sv.pairs_off = sc.lds_scan_pairs;
+                sv.reach32 = sc.scan_reach32;
+                v4f *rows = reinterpret_cast<v4f *>(lds_raw + sv.pairs_off);
+                const uint32_t n_pairs = np / 2u, have = (uint32_t)scan32_padded_pairs(sv.n);
+                for (uint32_t p = threadIdx.x; p < n_pairs; p += blockDim.x) {
+                    SphereScanPair pr{{0.0f, 0.0f}, {0.0f, 0.0f}, {0.0f, 0.0f}, {__builtin_inff(), __builtin_inff()}};  // never passes
+                    if (p < have) {
+                        pr = sc.sphere_scan32[p];
+                        // a run's rows keep their varying coordinates in the cx and cz slots (scene_builder.cpp cut_scan_segments): back
+                        uint32_t axis = kScanAxisNone;
+                        for (uint32_t seg = 0; seg < sc.n_scan_segments; seg++) {
+                            const ScanSegment sg = sc.scan_segments[seg];
+                            if (p / kScanTripPairs - sg.first_trip < sg.n_trips) axis = sg.axis;
+                        }
+                        for (int h = 0; h < 2; h++) {
+                            if (axis == 0u) { const float t = pr.cx[h]; pr.cx[h] = pr.cy[h]; pr.cy[h] = t; }
+                            if (axis == 2u) { const float t = pr.cz[h]; pr.cz[h] = pr.cy[h]; pr.cy[h] = t; }
+                        }
+                    }
+                    rows[p] = v4f{pr.cx[0], pr.cx[1], pr.cy[0], pr.cy[1]};
+                    rows[n_pairs + p] = v4f{pr.cz[0], pr.cz[1], pr.k[0], pr.k[1]};
+                }
+            }
             __syncthreads();
         }
     }
@@ -3364,9 +3502,19 @@ __global__ __launch_bounds__(T::BLOCK, T::MIN_WAVES) void render_kernel(DeviceSc
 #endif
             } else {
                 PH_BEGIN();
-                if (sv.in_lds && !a.coop_single) scan_grouped(sv, lane, todo, ray, 0.001, DBL_MAX, h, hit);
+#if RT_PHASES
+                GroupedSums gs{};
+#endif
+                if (sv.in_lds && !a.coop_single) scan_grouped(sv, lane, todo, ray, 0.001, DBL_MAX, h, hit GS_PASS);
                 else scan_cooperative(sv, lane, todo, ray, 0.001, DBL_MAX, h, hit);
                 PH_END(1, (todo >> lane) & 1ull);
+#if RT_PHASES
+                if (gs.rays) {  // a grouped pass through the filter: every lane ran it and holds the same sums
+                    ph.n[16] += 1ull;       ph.l[16] += gs.rays;     ph.t[16] += gs.tests;
+                    ph.n[17] += gs.drains;  ph.l[17] += gs.lane_max; ph.t[17] += gs.survivors;
+                    ph.l[18] += gs.filter_cycles; ph.t[18] += gs.test_cycles;
+                }
+#endif
             }
         }
         bool thin = false;
