@@ -191,6 +191,13 @@ RTOW_API int rt_scene_dump_camera(rt_scene *s, double out27[27]);
  * that the fp32 filter decides has shared_out[k] as that centre coordinate, bit for bit, and the scan forms its terms once per ray;
  * 3: a general segment (shared_out[k] = 0).  The segments tile the rows exactly.  Host only.  Returns the segment count. */
 RTOW_API int rt_scene_dump_scan_segments(rt_scene *s, int max_segments, uint32_t *rows_axis_out, float *shared_out);
+/* The camera rays' candidate lists of a sphere-list world, as a launch on a film of this geometry builds them on the device (same
+ * rule, csrc/primary_cull_rule.h): per 8x8 tile of the rank's rows, row-major over its compact rows, 16 uint16 -- [0] the number
+ * of listed spheres, 0..14, or 15: too many, the tile has no list; [1..count] their positions in the sphere list, ascending.  A
+ * list holds every sphere the reference's Sphere::Hit could accept over (0.001, inf) for any camera ray of any pixel of the tile.
+ * Host only.  Returns the tile count (negative: error); writes min(tiles, max_tiles) lists where lists_out is given. */
+RTOW_API int rt_scene_dump_primary_lists(rt_scene *s, int width, int height, int stripe_rows, int rank, int world_size, int max_tiles,
+                                         uint16_t *lists_out);
 
 /* ---- render (RenderInit + Render, R/kernel.cu:110-154,675-691) ---- */
 typedef struct rt_render_params {
@@ -249,6 +256,10 @@ typedef struct rt_render_params {
 #define RT_FLAG_FILTER_FP64 2048u     /* sphere-list worlds: the conservative filter in fp64, one sphere per 8 instructions (default: its packed
                                       fp32 form, two spheres per 9 instructions, a little coarser; the survivors always go through the
                                       reference's fp64 test, so the image is the same bit for bit) -- tests, timing */
+#define RT_FLAG_NO_PRIMARY_LISTS 4096u /* sphere-list worlds: every camera ray goes through the scan of the whole list (default: where a wave
+                                      scans one ray per lane, camera rays are tested against the short list of spheres that a ray through
+                                      their 8x8 tile can reach, in list order, with the reference's test; the image is the same bit for
+                                      bit either way) -- tests, timing */
 #define RT_FLAG_ACCELERATE_LISTS 512u /* HittableList worlds of primitives only (no leaf draws random numbers): render through the library's
                                       own tree as a BvhNode world would be -- the reference's "BVH image == list image" invariant the other
                                       way round; off by default so that a list world is scanned as the reference scans it.  Ignored for

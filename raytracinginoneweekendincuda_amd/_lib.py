@@ -170,6 +170,7 @@ SIGNATURES = {
     "rt_scene_dump_fast_nodes": (I, [P, I, D3, C.POINTER(C.c_uint32), C.POINTER(C.c_uint16)]),
     "rt_scene_dump_camera": (I, [P, D3]),
     "rt_scene_dump_scan_segments": (I, [P, I, C.POINTER(C.c_uint32), C.POINTER(C.c_float)]),
+    "rt_scene_dump_primary_lists": (I, [P, I, I, I, I, I, I, C.POINTER(C.c_uint16)]),
     "rt_stripe_rows": (I, [I, I, I, I, C.POINTER(C.c_int), I]),
     "rt_film_create": (P, [I, I, I, I, I, I]),
     "rt_film_destroy": (None, [P]),

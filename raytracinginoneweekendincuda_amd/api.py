@@ -32,6 +32,7 @@ FLAG_EXACT_SCAN = 256       # sphere-list worlds: the reference's discriminant f
 FLAG_REFERENCE_TREE = 128   # primitive BVH worlds: walk the reference's own tree (default: the library's SAH tree)
 FLAG_FILTER_FP64 = 2048     # sphere-list worlds: the fp64 filter instead of its packed fp32 form (tests, timing)
 FLAG_COOP_SINGLE = 1024     # tests: sphere-list worlds, thin waves scan one ray at a time (the older scheme)
+FLAG_NO_PRIMARY_LISTS = 4096  # sphere-list worlds: camera rays scan the whole list too (default: their tile's candidate list; tests, timing)
 FLAG_NO_PIXEL_CLASSES = 64  # sphere-list worlds: one launch for all pixels (no separate launch for the long-chain pixels)
 
 
@@ -277,6 +278,17 @@ class Scene:
         shared = np.zeros(max(n, 1), dtype=np.float32)
         lib().rt_scene_dump_scan_segments(self._p, n, rows.ctypes.data_as(C.POINTER(C.c_uint32)), shared.ctypes.data_as(C.POINTER(C.c_float)))
         return [(int(r[0]), int(r[1]), None if r[2] == 3 else int(r[2]), shared[k]) for k, r in enumerate(rows[:n])]
+
+    def primary_lists(self, width, height, stripe_rows=8, rank=0, world_size=1):
+        """Tests: the camera rays' candidate lists of a sphere-list world for a film of this geometry (rt_scene_dump_primary_lists;
+        no device needed), one per 8x8 tile of the rank's rows, row-major over its compact rows: a list of sphere-list positions
+        (ascending), or None for a tile with too many candidates to list."""
+        n = lib().rt_scene_dump_primary_lists(self._p, width, height, stripe_rows, rank, world_size, 0, None)
+        if n < 0:
+            raise RtowError(_err())
+        words = np.zeros((max(n, 1), 16), dtype=np.uint16)
+        lib().rt_scene_dump_primary_lists(self._p, width, height, stripe_rows, rank, world_size, n, words.ctypes.data_as(C.POINTER(C.c_uint16)))
+        return [None if w[0] == 15 else [int(k) for k in w[1:1 + int(w[0])]] for w in words[:n]]
 
     def plan_launch(self, params, num_cus=256, adaptive=False):
         """Tests: what a launch of this committed scene with these RenderParams decides on a GPU of ``num_cus`` compute units

@@ -16,6 +16,7 @@
 #include "device_arena.h"
 #include "film_rows.h"
 #include "launch_plan.h"
+#include "primary_cull_rule.h"
 #include "render_iface.h"
 #include "scene_host.h"
 
@@ -93,6 +94,7 @@ struct FilmImpl {
     // class; the serving waves of the render launch take the listed pixels, the others the rest of the tile queue
     uint32_t *pix_cost = nullptr, *heavy_list = nullptr, *heavy_count = nullptr, *super_list = nullptr;  // heavy_count[1]: length of super_list
     uint8_t *pix_class = nullptr;
+    uint16_t *primary_lists = nullptr;  // sphere-list worlds: the camera rays' candidates per tile (primary_cull_rule.h), rebuilt by every launch that reads them
     unsigned long long *host_counters = nullptr;  // pinned mirror of ray_counter, filled by an async copy behind the render
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};  // begin, after seed, after render, after the counter copy
     bool seeded = false;
@@ -425,6 +427,8 @@ rt_film *rt_film_create(int device, int width, int height, int stripe_rows, int 
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&f->own_stream, hipStreamNonBlocking);
     if (e == hipSuccess) e = f->planes.alloc(f->geometry.n_tiles, f->tile_cost);
     if (e == hipSuccess) e = f->planes.alloc(f->geometry.n_tiles, f->tile_order);
+    // (with the film, not on first use: an allocation between two launches' kernels would sit inside the frame's timed span)
+    if (e == hipSuccess) e = f->planes.alloc((size_t)f->geometry.n_tiles * kPrimaryListWords, f->primary_lists);
     if (e == hipSuccess) e = hipHostMalloc((void **)&f->host_counters, kCounterWords * sizeof(unsigned long long), hipHostMallocDefault);
     for (int k = 0; k < 4 && e == hipSuccess; k++) e = hipEventCreate(&f->ev[k]);
     if (e != hipSuccess) {
@@ -692,6 +696,15 @@ static int enqueue_frame(SceneImpl &s, FilmImpl &f, const rt_render_params *p, h
     f.last_plan = plan;
     f.last_kernel = info;
     if (int rc = allocate_class_planes(f, plan)) return rc;
+    // Sphere lists: the candidates of every tile's camera rays, for the rehearsal and the frame launch alike.  Built by every
+    // launch that can read them -- one lane per ray, and a full wave reaches the pixel-parallel scan (render_kernel's own condition
+    // for a primary round): the camera and the scene may have changed since the last one, and the film has no key that would tell.
+    if (is_sphere_list_kernel(plan.kernel_kind) && p->max_depth > 0 && !(p->flags & (RT_FLAG_EXACT_SCAN | RT_FLAG_NO_PRIMARY_LISTS)) &&
+        plan.pixels_per_wave >= 64 && plan.coop_threshold <= 64 && ds.n_spheres <= 0xFFFFu && f.geometry.n_tiles > 0) {
+        HIP_TRY(launch_primary_lists(ds, f.primary_lists, f.geometry.n_tiles, f.geometry.width, f.geometry.height, f.geometry.rows_owned,
+                                     f.stripe_rows, f.rank, f.world_size, stream));
+        ra.primary_lists = f.primary_lists;
+    }
     if (plan.probe_spp > 0)
         if (int rc = enqueue_rehearsal(f, ds, plan, build, ra, stream)) return rc;
     HIP_TRY(build.render(plan.kernel, ds, ra, stream));
@@ -764,6 +777,15 @@ static void print_phases(const FilmImpl &f)
                          "pixel-parallel scan's (%.0f of %.0f per pass)\n", (double)c[96 + 15] / passes, (double)c[64 + 15] / passes,
                          100.0 * c[32 + 13] / c[32 + 0], (double)c[32 + 13] / passes, (double)c[32 + 0] / passes);
         }
+        name[19] = "";  // slot 19: camera rays among the live lanes of a pixel-parallel pass
+        if (c[96 + 19])
+            std::fprintf(stderr, "camera rays: %llu pixel-parallel passes, %.2f live lanes per pass, %.2f of them with a camera ray (depth 0): share %.4f\n",
+                         c[96 + 19], (double)c[64 + 19] / c[96 + 19], (double)c[32 + 19] / c[96 + 19], (double)c[32 + 19] / (double)c[64 + 19]);
+        name[23] = "";  // slot 23 and the cycle word of slot 15: the primary rounds (render.hip render_kernel)
+        if (c[96 + 23])
+            std::fprintf(stderr, "primary: %llu rounds, %.2f fresh lanes per round, %.2f list entries tested per round (%.2f per lane), %.0f cycles per round "
+                         "(%.1f %% of wave time)\n", c[96 + 23], (double)c[64 + 23] / c[96 + 23], (double)c[32 + 15] / c[96 + 23],
+                         (double)c[32 + 15] / (double)c[64 + 23], (double)c[32 + 23] / c[96 + 23], 100.0 * c[32 + 23] / (double)c[7]);
         name[16] = name[17] = name[18] = "";  // slots 16, 17, 18: the counts of the grouped scan (render.hip GroupedSums)
         const double gp = (double)c[96 + 16];
         if (gp > 0) {

@@ -31,6 +31,7 @@
 
 #include "flat_scene.h"
 #include "launch_plan.h"
+#include "primary_cull_rule.h"
 #include "render_iface.h"
 #include "rng.h"
 
@@ -1741,6 +1742,17 @@ DEV void scan_rows_arrived(const SphereScanRow &g0, const SphereScanRow &g1, con
 // next slot and only the lanes that keep the sphere move `count` on, so the append needs no exec mask of its own.  A slot
 // written in vain is overwritten by the lane's next append or lies beyond `count`, where the drain does not read; it is
 // always inside the queue: the scans drain before any lane could hold kQueueCap entries, so count < kQueueCap here.
+// Primary rounds (render_kernel; primary_cull_rule.h): when a round of list tests pays.  A round costs the wave its own
+// instructions, and a lane it takes out of the next pixel-parallel pass saves 1/64 of that pass.  Census of the built kernel
+// (DESIGN.md section 4 "(r18)"), vector instructions: a round is about 735 (30 to decide, 55 per trip of the entry loop and 5
+// trips for the fullest lane, 400 of shading and the next camera ray, 30 at the loop's head); a pass is about 1200 whatever
+// the list (survivors, drain, set-up, shading) plus 3.54 per sphere of the list (1716 for C2's 485).  The break-even number of
+// fresh lanes is 64 x 735 / (1200 + 3.54 n): 16 for C2, 34 for a list of 50, 39 at most.
+// A round also delays every secondary ray of its wave.  For a pixel whose chain of rays is what the frame waits for, that is
+// pure loss: a wave holding a pixel that has traced more than kPrimaryLongChain rays per sample (over at least 16 samples'
+// worth) runs no round that leaves a lane waiting.  C2's mean is 2.3 rays per sample; the serving threshold is 9.
+constexpr uint32_t kPrimaryRoundCost = 735, kPrimaryPassFixed = 1200, kPrimaryPassPerSphere100 = 354;
+constexpr uint32_t kPrimaryLongChain = 6;
 constexpr int kFilterTrip = 8;  // spheres per trip of the filtered scans; they drain when a lane holds more than kQueueCap - kFilterTrip
 static_assert(kFilterTrip < kQueueCap, "a trip of appends must fit between the drain threshold and the end of the queue");
 DEV void append_survivor(uint16_t *queue, uint32_t lane, uint32_t &count, uint32_t k, bool keep)
@@ -3307,8 +3319,15 @@ __global__ __launch_bounds__(T::BLOCK, T::MIN_WAVES) void render_kernel(DeviceSc
     [[maybe_unused]] unsigned long long wave_samples = 0;
 
     uint32_t pix_rays = 0;  // rays this lane's current pixel has traced so far
-    uint32_t my_tile = 0;   // tile of the current pixel (cost probe)
+    // 8x8 tile of the current pixel, in the numbering of tile_cost and of primary_lists: the rehearsal books costs under it and a
+    // primary round reads the tile's list by it, so every path of the refill that hands a lane a pixel sets it -- the tile
+    // queue, the heavy list and the super list (the listed pixels' from their row and column)
+    uint32_t my_tile = 0;
     int boost_left = 0;     // extra overdue-only passes still allowed before the next pixel-parallel pass
+    [[maybe_unused]] bool primary_since_scan = false;  // ... and one has run since the wave's last pixel-parallel pass
+    // fewest fresh lanes for which a round pays beside a pass over this list (kPrimaryRoundCost): 16 for C2's 485 spheres
+    [[maybe_unused]] const int primary_break_even = (int)((64u * kPrimaryRoundCost) / (kPrimaryPassFixed + (sc.n_spheres * kPrimaryPassPerSphere100) / 100u));
+    [[maybe_unused]] bool primary_last = false;  // the last trip of the main loop was a primary round (wave-uniform): the boost count stands
     // BVH worlds: per-lane resumable traversal (see Walk) and the hit it has found so far
     Walk walk{};
     walk.state = kNone;  // no walk in progress
@@ -3349,9 +3368,14 @@ __global__ __launch_bounds__(T::BLOCK, T::MIN_WAVES) void render_kernel(DeviceSc
                 else __builtin_amdgcn_s_setprio(0);
                 overdue = 0;
             }
-            boost = overdue != 0 && boost_left > 0;
-            if (boost) boost_left--;
-            else boost_left = a.boost_rounds;
+            if (primary_last) {  // a primary round is no pixel-parallel pass: the overdue lanes' extra passes follow the scan, as ever
+                overdue = 0;
+            } else {
+                boost = overdue != 0 && boost_left > 0;
+                if (boost) boost_left--;
+                else boost_left = a.boost_rounds;
+            }
+            primary_last = false;
         }
 
         const bool from_list = heavy_mode && !heavy_dry;  // this refill takes heavy pixels off the list
@@ -3478,7 +3502,90 @@ __global__ __launch_bounds__(T::BLOCK, T::MIN_WAVES) void render_kernel(DeviceSc
         bool hit = false;
         if constexpr (T::WORLD == 2) {
             if (boost) todo = overdue;
-            if (!boost && a.pixels_per_wave >= 64 && __popcll(live) >= a.coop_threshold) {
+            // ---- primary round (r18): camera rays against their tile's candidate list instead of the whole list ----
+            // Where the wave would run the pixel-parallel scan, the lanes whose ray is a camera ray (depth == 0) and whose tile has a
+            // list (primary_cull_rule.h: every sphere the reference could accept for ANY camera ray of the tile) run the reference's
+            // test on the listed spheres alone, in list order, and go on to the shading below; the other lanes wait.  Rounds repeat
+            // -- a lane whose path ended holds a new camera ray -- while nobody needs the scan; otherwise one round per pass, if it pays.
+            const bool scan_wave = !boost && a.pixels_per_wave >= 64 && __popcll(live) >= a.coop_threshold;
+            if (scan_wave && a.primary_lists != nullptr && a.max_depth > 0) {
+                const bool camera = active && depth == 0;
+                const unsigned long long cameras = __ballot(camera);
+                // A round that leaves lanes waiting must pay (primary_break_even), is the only one since the last scan pass (sky lanes
+                // are fresh again after every round: without this a mixed wave holds its secondary rays back round after round),
+                // and delays no pixel whose chain of rays is long enough to decide when the frame ends (kPrimaryLongChain).
+                const bool may_round = !primary_since_scan && __popcll(cameras) >= primary_break_even &&
+                                       !__any(active && pix_rays > kPrimaryLongChain * (uint32_t)(sample + 16));
+                if (cameras == live || may_round) {
+                    PH_BEGIN();
+                    // the list's first half; the second is fetched where a lane gets that far (eight registers of list words at once
+                    // cost the adaptive instantiation two spills)
+                    uint4 wa = uint4{kPrimaryNoList, 0u, 0u, 0u};
+                    const uint4 *row = reinterpret_cast<const uint4 *>(a.primary_lists + (size_t)my_tile * kPrimaryListWords);
+                    if (camera) wa = row[0];
+                    uint32_t n_listed = wa.x & 0xFFFFu;
+                    const bool fresh = camera && n_listed != kPrimaryNoList;
+                    const unsigned long long freshes = __ballot(fresh);
+                    primary_last = freshes != 0 && (freshes == live || (may_round && __popcll(freshes) >= primary_break_even));
+                    if (primary_last) primary_since_scan = true;
+                    if (primary_last) {
+                        todo = freshes;
+                        if (!fresh) n_listed = 0u;
+                        n_listed = n_listed < kPrimaryListMax ? n_listed : kPrimaryListMax;
+                        const double ra = dot(ray.d, ray.d);
+                        double closest = DBL_MAX;
+                        uint32_t best_k = kNone;
+#if RT_PHASES
+                        ph.n[23] += 1ull;
+                        ph.l[23] += (unsigned long long)__popcll(freshes);
+                        for (uint32_t e = n_listed, off = 32; off > 0; off >>= 1) {
+                            e += (uint32_t)__shfl_xor((int)e, (int)off, 64);
+                            if (off == 1) ph.t[15] += e;
+                        }
+#endif
+                        for (uint32_t s = 0; __any(s < n_listed); s++) {
+                            // the next entry: the half list moves down by one uint16; entry 7 is the first of the second half
+                            if (s == 7u) {
+                                if (s < n_listed) wa = row[1];
+                            } else {
+                                wa.x = __builtin_amdgcn_alignbit(wa.y, wa.x, 16); wa.y = __builtin_amdgcn_alignbit(wa.z, wa.y, 16);
+                                wa.z = __builtin_amdgcn_alignbit(wa.w, wa.z, 16); wa.w >>= 16;
+                            }
+                            if (s < n_listed) {
+                                const uint32_t k = wa.x & 0xFFFFu;
+                                SphereGeom g;
+                                if (sv.in_lds) {
+                                    const RT_LDS double *pl = (const RT_LDS double *)(lds_raw + sv.planes_off);
+                                    g = SphereGeom{pl[k], pl[sv.n_padded + k], pl[2u * sv.n_padded + k], pl[3u * sv.n_padded + k]};
+                                } else {
+                                    g = sc.spheres[k];
+                                }
+                                double t;
+                                if (sphere_test(ray.o - mk(g.cx, g.cy, g.cz), ray.d, ra, g.r2, 0.001, closest, t)) {
+                                    closest = t;
+                                    best_k = k;
+                                }
+                            }
+                        }
+                        hit = best_k != kNone;
+                        if (hit) {
+                            h.t = closest;
+                            h.ref = make_ref(REF_SPHERE, best_k);
+                            h.obj = kNone;
+                        }
+                    }
+#if RT_PHASES
+                    if (primary_last) {
+                        asm volatile("" ::"v"(h.t), "v"(h.ref));
+                        ph.t[23] += __builtin_readcyclecounter() - ph_t0;
+                    }
+#endif
+                }
+            }
+            if (primary_last) {
+                // (nothing more to search: `todo`, `hit` and `h` are set)
+            } else if (scan_wave) {
+                primary_since_scan = false;
                 PH_BEGIN();
 #if RT_PHASES
                 ScanSums ss{};
@@ -3490,6 +3597,9 @@ __global__ __launch_bounds__(T::BLOCK, T::MIN_WAVES) void render_kernel(DeviceSc
                                                  : scan_filtered32<false>(sc, 0u, 0u, queue, lane, ray, 0.001, DBL_MAX, h SS_PASS);
                 PH_END(0, active);
 #if RT_PHASES
+                ph.n[19] += 1ull;  // slot 19 (no primitive pass in this kernel): live lanes of the pass, and those with a camera ray
+                ph.l[19] += (unsigned long long)__popcll(live);
+                ph.t[19] += (unsigned long long)__popcll(__ballot(active && depth == 0));
                 {  // the scan ran in the active lanes only: take the (wave-uniform) sums from the first of them
                     const int src = __ffsll((long long)__ballot(active)) - 1;
                     if (src >= 0) {
@@ -3940,6 +4050,51 @@ hipError_t launch_classify_pixels(const uint32_t *pix_cost, uint32_t n_pixels, u
     if (n_pixels == 0) return hipSuccess;
     hipLaunchKernelGGL(classify_pixels_kernel, dim3((n_pixels + 255u) / 256u), dim3(256), 0, stream, pix_cost, n_pixels, threshold,
                        pix_class, list, count, super_list, super_threshold, width, near_percent, near_neighbours);
+    return hipGetLastError();
+}
+
+// The camera rays' candidate lists (primary_cull_rule.h has the rule and its proof): one thread per 8x8 tile of the rank's rows,
+// every thread on the same sphere row at the same time, so the rows come through the scalar path.  The list is written whole, as
+// two 16-byte stores; a tile with more than kPrimaryListMax candidates gets "no list".
+__global__ __launch_bounds__(256) void primary_lists_kernel(DeviceScene sc, uint16_t *lists, uint32_t n_tiles, int32_t width, int32_t height,
+                                                             int32_t rows_owned, int32_t stripe_rows, int32_t rank, int32_t world_size)
+{
+    const uint32_t tile = blockIdx.x * blockDim.x + threadIdx.x;
+    if (tile >= n_tiles) return;
+    const CameraRec cam = *sc.camera;
+    const TileCone cone = primary_tile_cone(cam, width, height, primary_tile_pixels(tile, width, rows_owned, stripe_rows, rank, world_size));
+    uint32_t w[kPrimaryListWords / 2] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};  // two uint16 per word, the count in the low half of w[0]
+    uint32_t count = 0;
+    const uint32_t n = sc.n_spheres;
+    for (uint32_t s = 0; s < n; s++) {
+        const SphereGeom g = load_sphere_row(sc.spheres, s);
+        if (!primary_may_hit(cone, g.cx, g.cy, g.cz, g.r2)) continue;
+        if (count < kPrimaryListMax) {
+            const uint32_t slot = count + 1u;
+#pragma unroll
+            for (uint32_t q = 0; q < kPrimaryListWords / 2; q++)  // (constant indices: the words stay in registers)
+                if (q == slot / 2u) w[q] |= s << ((slot & 1u) * 16u);
+        }
+        count++;
+    }
+    if (count > kPrimaryListMax) {
+#pragma unroll
+        for (uint32_t q = 0; q < kPrimaryListWords / 2; q++) w[q] = 0u;
+        count = kPrimaryNoList;
+    }
+    w[0] |= count;
+    uint4 *out = reinterpret_cast<uint4 *>(lists + (size_t)tile * kPrimaryListWords);
+    out[0] = uint4{w[0], w[1], w[2], w[3]};
+    out[1] = uint4{w[4], w[5], w[6], w[7]};
+}
+
+hipError_t launch_primary_lists(const DeviceScene &sc, uint16_t *lists, uint32_t n_tiles, int32_t width, int32_t height, int32_t rows_owned,
+                                int32_t stripe_rows, int32_t rank, int32_t world_size, hipStream_t stream)
+{
+    if (n_tiles == 0) return hipSuccess;
+    if (sc.n_spheres > 0xFFFFu) return hipErrorInvalidValue;  // a list entry is a uint16 (the caller builds no lists for such a world)
+    hipLaunchKernelGGL(primary_lists_kernel, dim3((n_tiles + 255u) / 256u), dim3(256), 0, stream, sc, lists, n_tiles, width, height, rows_owned,
+                       stripe_rows, rank, world_size);
     return hipGetLastError();
 }
 

@@ -85,6 +85,9 @@ struct RenderArgs {
     int32_t pixels_per_wave;    // sphere-list kernel: at most this many lanes of a wave hold a pixel (64 = all of them)
     int32_t shade_batch;    // BVH kernels: shade once this many lanes have finished their walk
     uint32_t ray_budget;    // sphere-list kernel: a pixel past this many rays is finished cooperatively
+    // sphere-list kernel: per 8x8 tile of this rank's rows the spheres a camera ray of the tile can reach (primary_cull_rule.h:
+    // kPrimaryListWords uint16 per tile, built by launch_primary_lists ahead of the launch), or nullptr: every ray is scanned
+    const uint16_t *primary_lists;
     // Adaptive sampling (adaptive_rule.h; the Adaptive<> instantiations of render.hip, chosen by `adaptive`): spp is then the most
     // samples a pixel may take in this launch.  Per owned pixel: samples taken so far in this frame, the sum of y^2 over them, and
     // whether the rule has stopped the pixel (a later launch of the frame drops it from the queue untouched).  The launcher zeroes
@@ -199,6 +202,11 @@ hipError_t launch_atrous(const AtrousArgs &a, hipStream_t stream);
 hipError_t launch_classify_pixels(const uint32_t *pix_cost, uint32_t n_pixels, uint32_t threshold, uint8_t *pix_class, uint32_t *list,
                                   uint32_t *count, hipStream_t stream, uint32_t *super_list = nullptr, uint32_t super_threshold = 0,
                                   uint32_t width = 0, uint32_t near_percent = 0, uint32_t near_neighbours = 0);  // a pixel of near_percent % of the threshold with that many of its 8 neighbours over it is listed too
+
+// lists[tile * kPrimaryListWords ..]: the list of primary_cull_rule.h for every 8x8 tile of the rank's rows (one thread per tile,
+// the scene's static spheres on the scalar path); `sc.camera` and `sc.spheres` are the uploaded tables
+hipError_t launch_primary_lists(const DeviceScene &sc, uint16_t *lists, uint32_t n_tiles, int32_t width, int32_t height, int32_t rows_owned,
+                                int32_t stripe_rows, int32_t rank, int32_t world_size, hipStream_t stream);
 
 // tile_order[k] = the tile with the k-th highest cost (counting sort over 256 cost classes; one workgroup)
 // (flat_x8 / 8 = ratio of the heaviest tile to the mean below which the row-major order is kept)

@@ -18,6 +18,8 @@
 #include <unordered_map>
 
 #include "../../include/rtow.h"
+#include "launch_plan.h"
+#include "primary_cull_rule.h"
 #include "scene_host.h"
 
 namespace rtow {
@@ -2258,6 +2260,22 @@ int rt_scene_dump_scan_segments(rt_scene *s, int max_segments, uint32_t *rows_ax
         if (shared_out) shared_out[k] = sg.c;
     }
     return n;
+}
+
+int rt_scene_dump_primary_lists(rt_scene *s, int width, int height, int stripe_rows, int rank, int world_size, int max_tiles, uint16_t *lists_out)
+{
+    if (!s || !S(s)->committed || !S(s)->has_camera) return -fail(RT_ERR_STATE, "rt_scene_dump_primary_lists: scene not committed, or no camera");
+    if (width <= 0 || height <= 0 || stripe_rows <= 0 || world_size <= 0 || rank < 0 || rank >= world_size)
+        return -fail(RT_ERR_INVALID, "rt_scene_dump_primary_lists: bad geometry");
+    const FlatScene &f = S(s)->flat;
+    if (f.spheres.size() > 0xFFFFu) return -fail(RT_ERR_INVALID, "rt_scene_dump_primary_lists: more spheres than a list entry can name");
+    const FilmGeometry g = film_geometry(width, height, stripe_rows, rank, world_size);
+    for (uint32_t tile = 0; tile < g.n_tiles && (int)tile < max_tiles; tile++) {
+        if (!lists_out) break;
+        const TileCone cone = primary_tile_cone(S(s)->camera, width, height, primary_tile_pixels(tile, width, g.rows_owned, stripe_rows, rank, world_size));
+        primary_list_for_tile(cone, f.spheres.data(), (uint32_t)f.spheres.size(), lists_out + (size_t)tile * kPrimaryListWords);
+    }
+    return (int)g.n_tiles;
 }
 
 int rt_stripe_rows(int height, int stripe_rows, int rank, int world_size, int *rows_out, int max_rows)
