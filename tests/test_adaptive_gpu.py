@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import raytracinginoneweekendincuda_amd as rt
+from query_helpers import bits
 from test_adaptive_host import CAP, FLOOR, MIN, STEP, oracle_frames, predict_counts, rule_numpy
 from test_custom_scenes_gpu import NESTINGS
 
@@ -39,10 +40,6 @@ def frames_of(oracle, scene_id, world_kind, w, h):
     if key not in _FRAMES:
         _FRAMES[key] = oracle_frames(oracle, scene_id, world_kind, w, h)
     return _FRAMES[key]
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint64)
 
 
 def adaptive_film(w, h, tau, min_samples=MIN, check_interval=STEP, **film_kw):

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from conftest import build_both
+from frame_helpers import compare
 
 pytestmark = pytest.mark.gpu
 
@@ -18,19 +19,12 @@ TOL = 1e-5
 W, H, SPP = 64, 32, 4
 
 
-def compare(got, want):
-    diff = np.abs(got - want)
-    exact = np.mean(np.all(got.view(np.uint64) == want.view(np.uint64), axis=-1))
-    within = np.mean(np.all(diff <= TOL, axis=-1))
-    return exact, within, diff.max()
-
-
 def check(build, w=W, h=H, spp=SPP, min_exact=0.99, variants=(0, 1), min_within_fast=0.995):
     prod, orc = build_both(build)
     want, stats = orc.render(w, h, spp, want_stats=True)
     for variant in variants:
         got, st = prod.render(w, h, spp, variant=variant)
-        exact, within, worst = compare(got, want)
+        exact, within, worst = compare(got, want, TOL)
         print(f"variant {variant}: kernel kind {st.kernel_kind}, bit-exact {exact:.4f}, within {within:.4f}, max |d| {worst:.3g}")
         assert np.isfinite(got).all()
         if variant == 0:
@@ -163,7 +157,7 @@ def test_lanes_per_ray_list_scan_gives_the_one_lane_per_ray_frame(name, world_ki
         ref, st0 = prod.render(w, h, spp, variant=variant, pixels_per_wave=64)
         assert st0.kernel_kind in (8, 10) and st0.pixels_per_wave == 64
         if variant == 0:
-            exact, within, _ = compare(ref, want)
+            exact, within, _ = compare(ref, want, TOL)
             assert within >= 0.999 and exact >= 0.99
         for ppw in (32, 16, 8, 4, 2, 1):
             got, st = prod.render(w, h, spp, variant=variant, pixels_per_wave=ppw)
@@ -212,7 +206,7 @@ def test_coincident_primitives_resolve_like_the_reference(world_kind):
     assert prod.dump_fast_nodes()[0].shape[0] == 0, "a world with coincident primitives must not get a library tree"
     want, stats = orc.render(W, H, 8, want_stats=True)
     got, st = prod.render(W, H, 8, variant=0)
-    exact, within, worst = compare(got, want)
+    exact, within, worst = compare(got, want, TOL)
     print(f"coincident world {world_kind}: kernel kind {st.kernel_kind}, bit-exact {exact:.4f}, within {within:.4f}")
     assert st.rays == stats["rays"] and within >= 0.999 and exact >= 0.99
     accel, _ = prod.render(W, H, 8, variant=0, flags=512)   # RT_FLAG_ACCELERATE_LISTS has no tree to use
@@ -294,7 +288,7 @@ def test_segmented_walk_matches_the_oracle_and_the_reference_order_walk(media):
         assert st.rays == st_ref.rays
         assert np.array_equal(seg.view(np.uint64), ref.view(np.uint64)), (media, variant)
         if variant == 0:
-            exact, within, worst = compare(seg, want)
+            exact, within, worst = compare(seg, want, TOL)
             print(f"media {media}: kernel kind {st.kernel_kind}, bit-exact {exact:.4f}, within {within:.4f}, max |d| {worst:.3g}")
             assert st.rays == stats["rays"] and within >= 0.999 and exact >= 0.98
 
@@ -304,7 +298,7 @@ def test_more_media_than_the_segmented_walk_handles_fall_back():
     got, st = prod.render(W, H, 4, variant=0, flags=2)
     assert not (st.kernel_kind & 256)
     want = orc.render(W, H, 4)
-    exact, within, _ = compare(got, want)
+    exact, within, _ = compare(got, want, TOL)
     assert within >= 0.999 and exact >= 0.98
 
 
@@ -521,5 +515,5 @@ def test_deep_kernel_falls_back_when_its_tables_do_not_fit():
     print(f"kernel kind {st.kernel_kind}, vgprs {st.kernel_vgprs}")
     assert st.kernel_vgprs > 168, "the 768-thread deep kernel (168 VGPRs) cannot hold 700 box rows"
     assert st.rays == stats["rays"]
-    exact, within, worst = compare(got, want)
+    exact, within, worst = compare(got, want, TOL)
     assert within >= 0.999 and exact >= 0.95   # Perlin: device sin differs from glibc's by an ulp in a few pixels

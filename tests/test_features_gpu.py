@@ -7,36 +7,17 @@ import numpy as np
 import pytest
 
 import raytracinginoneweekendincuda_amd as rt
-from conftest import ROOT, build_both, synthetic_earth
+from conftest import ROOT, build_both
+from query_helpers import bits, centre_rays, mixed_world, sphere_roots
 from test_custom_scenes_gpu import NESTINGS, _coincident
 
 pytestmark = pytest.mark.gpu
 
 
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint64)
-
-
-def centre_rays(scene, width, height):
-    """Origin and direction (H, W, 3) of the samples == 0 rays: u = (i + 0.5) / W, v = (j + 0.5) / H, no lens offset, from
-    dump_camera's {bg, origin, llc, horizontal, vertical, ...}, in the kernel's order of operations."""
-    cam = scene.dump_camera()
-    bg, origin, llc, hor, ver = (cam[3 * k:3 * k + 3] for k in range(5))
-    u = ((np.arange(width) + 0.5) / width)[None, :, None]
-    v = ((np.arange(height) + 0.5) / height)[:, None, None]
-    return bg, origin, ((llc + u * hor) + v * ver) - origin
-
-
-def sphere_first_hit(origin, d, centre, radius):
-    """R/Sphere.h:28-60 over [0.001, inf) for rays from outside: (hit mask, t, discriminant relative to b^2)."""
-    oc = origin - np.asarray(centre, dtype=np.float64)
-    a = d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1] + d[..., 2] * d[..., 2]
-    b = oc[0] * d[..., 0] + oc[1] * d[..., 1] + oc[2] * d[..., 2]
-    c = (oc[0] * oc[0] + oc[1] * oc[1] + oc[2] * oc[2]) - radius * radius
-    disc = b * b - a * c
-    with np.errstate(invalid="ignore"):
-        t = (-b - np.sqrt(disc)) / a
-    return (disc > 0) & (t > 0.001), t, disc / (b * b)
+def centre_ray_grid(scene, width, height):
+    """query_helpers.centre_rays in the shape of the feature planes: (background, origin (3,), directions (H, W, 3))."""
+    o, d, _, bg = centre_rays(scene, width, height)
+    return bg, o[0], d.reshape(height, width, 3)
 
 
 W, H = 32, 24
@@ -55,8 +36,9 @@ def test_sphere_depth_and_normal_equal_the_closed_form():
     s.SetWorld(s.HittableList([s.Sphere(centre, radius, s.Lambertian(colour))]))
     s.Camera((0, 0, 0), (0, 0, -1), (0, 1, 0), 40.0, W / H, 0.0, 1.0, 0.0, 0.0, bg_colour)
     s.Commit()
-    bg, origin, d = centre_rays(s, W, H)
-    hit, t, rel_disc = sphere_first_hit(origin, d, centre, radius)
+    bg, origin, d = centre_ray_grid(s, W, H)
+    t, _, rel_disc = sphere_roots(origin, d, centre, radius)
+    hit = (rel_disc > 0) & (t > 0.001)   # R/Sphere.h:28-60 over [0.001, inf) for rays from outside
     grazing = np.abs(rel_disc) <= 1e-9
     assert grazing.mean() <= 0.02, "the sphere was chosen so that (nearly) no centre ray grazes it"
     assert 0.1 < hit.mean() < 0.9
@@ -84,7 +66,7 @@ def test_quads_and_an_instanced_box_have_unit_normals_against_the_ray(world):
     s.SetWorld(s.BvhNode(items) if world == "bvh" else s.HittableList(items))
     s.Camera((0, 0.6, 3), (0, 0, -2), (0, 1, 0), 50.0, W / H, 0.0, 1.0)
     s.Commit()
-    _, origin, d = centre_rays(s, W, H)
+    _, origin, d = centre_ray_grid(s, W, H)
     albedo, normal, depth = features_of(s, samples=0)
     hit = depth > 0
     assert hit.all(), "floor and wall fill the frame"
@@ -113,8 +95,9 @@ def test_dense_medium_reports_its_boundary_and_no_normal():
     s.SetWorld(s.BvhNode([fog, s.Sphere((0, -101, -3), 100.0, s.Lambertian((0.5, 0.5, 0.5)))]))
     s.Camera((0, 0, 0), (0, 0, -1), (0, 1, 0), 50.0, W / H, 0.0, 1.0)
     s.Commit()
-    _, origin, d = centre_rays(s, W, H)
-    hit, t, _ = sphere_first_hit(origin, d, centre, radius)
+    _, origin, d = centre_ray_grid(s, W, H)
+    t, _, rel_disc = sphere_roots(origin, d, centre, radius)
+    hit = (rel_disc > 0) & (t > 0.001)
     albedo, normal, depth = features_of(s, samples=0)
     in_fog = (albedo == phase).all(axis=-1)
     assert in_fog.sum() >= 1 and not (in_fog & ~hit).any()
@@ -160,34 +143,10 @@ class View:
 TW, TH = 24, 16
 
 
-def _mixed(world_kind):
-    def build(s, Rng):
-        earth = s.ImageTexture(synthetic_earth())
-        checker = s.CheckerTexture(0.6, s.SolidColor((0.2, 0.3, 0.1)), s.SolidColor((0.9, 0.9, 0.9)))
-        marble = s.NoiseTexture(4.0, Rng(1984, 0))
-        items = [s.Sphere((0, -100.5, -1), 100.0, s.Lambertian(checker)),
-                 s.Sphere((-1.1, 0.0, -1.2), 0.5, s.Lambertian(earth)),
-                 s.Sphere((0.0, 0.0, -1.0), 0.5, s.Dielectric(1.5)),
-                 s.Sphere((1.1, 0.0, -1.2), 0.5, s.Metal((0.8, 0.6, 0.2), 0.3)),
-                 s.Sphere((0.4, 0.9, -1.6), 0.35, s.Lambertian(marble)),
-                 s.MovingSphere((-0.6, 0.8, -1.4), (-0.6, 1.1, -1.4), 0.0, 1.0, 0.25, s.Lambertian((0.7, 0.2, 0.2))),
-                 s.MovingSphere((1.5, 0.7, -0.8), (1.2, 0.7, -0.8), 0.0, 1.0, 0.2, s.Metal((0.9, 0.9, 0.9), 0.0)),
-                 s.Quad((-2.5, -0.5, -2.5), (5, 0, 0), (0, 2.5, 0), s.Lambertian(earth)),
-                 s.Quad((-2.4, -0.5, -2.4), (0, 0, 2.5), (0, 1.5, 0.3), s.DiffuseLight((3.0, 2.5, 2.0))),
-                 s.Quad((2.0, -0.5, 0.2), (0.3, 0, -2.4), (0, 1.2, 0), s.Lambertian(marble))]
-        for k in range(9):   # enough leaves for the BvhNode world to be a tree worth the name
-            items.append(s.Sphere((-2.0 + 0.5 * k, -0.35, 0.1), 0.15, (s.Lambertian((0.1, 0.2, 0.8)), s.Metal((0.7, 0.7, 0.7), 0.1),
-                                                                       s.Isotropic((0.3, 0.9, 0.3)))[k % 3]))
-        s.SetWorld(s.BvhNode(items) if world_kind == 0 else s.HittableList(items))
-        s.Camera((0.3, 0.7, 2.6), (0, 0.1, -1), (0, 1, 0), 55.0, TW / TH, 0.1, 3.4, 0.0, 1.0, (0.55, 0.65, 0.9))
-        s.Commit()
-    return build
-
-
 # name -> (scene function, media replaced by their boundaries, a Perlin texture is in sight)
 TWINS = {
-    "mixed list": (_mixed(1), False, True),
-    "mixed bvh": (_mixed(0), False, True),
+    "mixed list": (lambda s, Rng: mixed_world(s, Rng, 1, TW / TH), False, True),
+    "mixed bvh": (lambda s, Rng: mixed_world(s, Rng, 0, TW / TH), False, True),
     "many_chained_transforms": (NESTINGS["many_chained_transforms"], False, True),
     "instance_of_composites": (NESTINGS["instance_of_composites"], True, False),
     "bvh_inside_a_list_world": (NESTINGS["bvh_inside_a_list_world"], True, False),

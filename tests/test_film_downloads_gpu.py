@@ -8,6 +8,7 @@ import pytest
 
 import raytracinginoneweekendincuda_amd as rt
 from raytracinginoneweekendincuda_amd import _lib
+from query_helpers import bits
 
 pytestmark = pytest.mark.gpu
 
@@ -16,10 +17,6 @@ W, H, SPP, STRIPE, WORLD = 24, 22, 4, 4, 3
 # this sample count) stops at 2, one with a single path to the light has a relative error of 1 and goes on
 ADAPTIVE = dict(min_samples=2, check_interval=1, noise_threshold=0.5)
 SENTINEL = -123.25
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint64)
 
 
 class Rendered:

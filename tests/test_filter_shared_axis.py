@@ -1,5 +1,5 @@
 """The packed fp32 filter's shared-coordinate form (render.hip filter_pairs<true>, set up per run segment in scan_filtered32),
-restated operation by operation as tests/test_filter_margin.py restates the general form: every product-sum exact, one rounding
+restated operation by operation as tests/filter_restated.py restates the general form: every product-sum exact, one rounding
 to fp32 per operation.
 
 In a run of rows that share the centre coordinate c on one axis, the two multiply-adds that involve only c are formed once per
@@ -15,30 +15,7 @@ import math
 import numpy as np
 import pytest
 
-F = np.float32
-
-
-def dot(a, b):
-    return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]
-
-
-def fma32(a, b, c):
-    """One rounding to fp32 (the exact product of two fp32 numbers fits a double; see test_filter_margin.fma32)."""
-    with np.errstate(all="ignore"):
-        return F(np.float64(a) * np.float64(b) + np.float64(c))
-
-
-def scan_ray32(o, d, reach):
-    a = dot(d, d)
-    oo = dot(o, o)
-    w = math.sqrt(oo) + reach
-    inv = 1.0 / math.sqrt(a)
-    u = [inv * x for x in d]
-    od = dot(o, u)
-    p2 = [2.0 * (o[i] - od * u[i]) for i in range(3)]
-    root_m = 2.0 ** -9 * w
-    nthr = root_m * root_m - (oo - od * od)
-    return dict(u=[F(x) for x in u], p2=[F(x) for x in p2], od=F(od), root_m=F(root_m), nthr=F(nthr))
+from filter_restated import F, dot, fma32, host_row, reference, scan_ray32
 
 
 def run_setup(f, axis, shared):
@@ -59,23 +36,6 @@ def filter_pass_run(f, axis, s0, l0, c, k):
         bu = F(f["od"] - s)
         behind = passed and bool(bu > f["root_m"]) and bool(fma32(bu, bu, F(kf - q)) > 0)
     return passed, behind
-
-
-def reference(o, d, c, r2):
-    oc = [o[i] - c[i] for i in range(3)]
-    a = dot(d, d)
-    b = dot(oc, d)
-    cc = dot(oc, oc) - r2
-    disc = b * b - a * cc
-    return disc > 0.0, (b > 0.0 and cc > 0.0)
-
-
-def host_row(c, r):
-    from fractions import Fraction
-    r2 = r * r
-    k = float(Fraction(c[0]) ** 2 + Fraction(c[1]) ** 2 + Fraction(c[2]) ** 2 - Fraction(r2))
-    reach = (math.sqrt(dot(c, c)) + math.sqrt(r2)) * (1.0 + 2.0 ** -40)
-    return r2, k, reach
 
 
 OFFSETS = [((0.0, 0.0, 0.0), 1.0, 11.0), ((13.0, 2.0, 3.0), 1.0, 11.0), ((300.0, -200.0, 500.0), 1.0, 11.0),

@@ -12,6 +12,7 @@ import raytracinginoneweekendincuda_amd as rt
 import test_adaptive_gpu as A
 import test_motion_time_gpu as M
 import test_shading_gpu as G
+from frame_helpers import render_params
 from test_custom_scenes_gpu import _deep_media_world
 from test_motion_time import field
 
@@ -26,8 +27,8 @@ def earth():
 
 def plan(scene, w, h, spp, variant=0, flags=0, num_cus=256, adaptive=False, rank=0, world_size=1, coop_threshold=0,
          max_blocks_per_cu=0, pixels_per_wave=0):
-    p = rt.RenderParams(w, h, spp, 50, 1984, 8, rank, world_size, variant, 0, flags, None, coop_threshold, 0, 0, max_blocks_per_cu,
-                        pixels_per_wave, 0)
+    p = render_params(w, h, spp, rank=rank, world_size=world_size, variant=variant, flags=flags, coop_threshold=coop_threshold,
+                      max_blocks_per_cu=max_blocks_per_cu, pixels_per_wave=pixels_per_wave)
     return scene.plan_launch(p, num_cus=num_cus, adaptive=adaptive)
 
 

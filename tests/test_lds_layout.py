@@ -19,6 +19,7 @@ import pytest
 
 import raytracinginoneweekendincuda_amd as rt
 from conftest import build_both
+from frame_helpers import render_params
 
 W, H, SPP = 96, 64, 4
 
@@ -186,7 +187,7 @@ def product(build):
 
 
 def plan(scene, w=W, h=H, spp=SPP, variant=0, flags=0, num_cus=256, adaptive=False, pixels_per_wave=64):
-    p = rt.RenderParams(w, h, spp, 50, 1984, 8, 0, 1, variant, 0, flags, None, 0, 0, 0, 0, pixels_per_wave, 0)
+    p = render_params(w, h, spp, variant=variant, flags=flags, pixels_per_wave=pixels_per_wave)
     return scene.plan_launch(p, num_cus=num_cus, adaptive=adaptive)
 
 

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import raytracinginoneweekendincuda_amd as rt
+from frame_helpers import render_params
 
 QUEUES = 4 * 16 * 64 * 2          # four waves' survivor queues
 SHARED, MOST, PLANES_MOST = 52 * 1024, 64 * 1024, 48 * 1024
@@ -26,8 +27,7 @@ def _list_world(n):
 
 
 def _plan(scene, adaptive=False):
-    p = rt.RenderParams(96, 64, 4, 50, 1984, 8, 0, 1, 0, 0, 0, None, 0, 0, 0, 0, 64, 0)
-    return scene.plan_launch(p, num_cus=256, adaptive=adaptive)
+    return scene.plan_launch(render_params(96, 64, 4, pixels_per_wave=64), num_cus=256, adaptive=adaptive)
 
 
 def _expected(n):

@@ -15,15 +15,12 @@ import torch
 import raytracinginoneweekendincuda_amd as rt
 import test_lds_layout as L
 from conftest import build_both
-from test_custom_scenes_gpu import compare
+from frame_helpers import compare
+from query_helpers import bits
 
 pytestmark = pytest.mark.gpu
 
 W, H, SPP = L.W, L.H, L.SPP
-
-
-def bits(frame):
-    return frame.view(np.uint64)
 
 
 @pytest.mark.parametrize("case", L.staging_cases(), ids=L.CASE_IDS)

@@ -25,36 +25,16 @@ import pytest
 
 import raytracinginoneweekendincuda_amd as rt
 from conftest import build_both
+from scan_checks import SPP, assert_same_scan, assert_strict_equals_oracle, ground, material, render_twice, small_spheres
 
 pytestmark = pytest.mark.gpu
 
-W, H, SPP, MORE = 96, 64, 4, 2
+W, H = 96, 64
 FORCINGS = [dict(coop_threshold=65)] + [dict(pixels_per_wave=p) for p in (1, 2, 4, 8, 16, 32)]
 LENGTHS = [1, 2, 63, 64, 65, 127, 129, 485, 1300]
 THIN_FRAMES = [(3, 1), (5, 1), (23, 1), (8, 3)]
 A_AT, B_AT = (5, 6, 13, 21, 37), (15, 16, 31, 32)  # list positions of the coincident copies (_coincident_world)
 FROM, AT = np.array((0.0, 0.8, 1.0)), np.array((0.0, 0.3, -5.0))
-
-
-def _material(s, rnd, k):
-    if k % 7 == 0:
-        return s.Dielectric(1.5)
-    if k % 3 == 0:
-        return s.Metal(tuple(rnd.uniform(0.4, 0.9, 3)), float(rnd.uniform(0.0, 0.3)))
-    return s.Lambertian(tuple(rnd.uniform(0.1, 0.9, 3)))
-
-
-def _small_spheres(s, rnd, n):
-    """A loose field of small spheres in front of the camera (what the filter decides)."""
-    items = []
-    for k in range(n):
-        c = (float(rnd.uniform(-3, 3)), float(rnd.uniform(-0.4, 1.2)), float(rnd.uniform(-9, -3)))
-        items.append(s.Sphere(c, float(rnd.uniform(0.15, 0.45)), _material(s, rnd, k)))
-    return items
-
-
-def _ground(s):
-    return s.Sphere((0.0, -1000.5, -5.0), 1000.0, s.Lambertian((0.5, 0.5, 0.5)))
 
 
 def _finish(s, items, w, h):
@@ -66,12 +46,12 @@ def _finish(s, items, w, h):
 def _string_world(w=W, h=H):
     def build(s, Rng):
         rnd = np.random.default_rng(43)
-        items = _small_spheres(s, rnd, 37)
+        items = small_spheres(s, rnd, 37)
         axis = (AT - FROM) / np.linalg.norm(AT - FROM)
         for k in range(40):  # one field sphere after every eight of the string
             c = FROM + (3.0 + 0.3 * k) * axis + np.array((0.02 * (k % 3), 0.0, 0.0))
-            items.insert(2 + k + k // 8, s.Sphere(tuple(float(x) for x in c), 0.3, _material(s, rnd, k + 1)))
-        items.append(_ground(s))
+            items.insert(2 + k + k // 8, s.Sphere(tuple(float(x) for x in c), 0.3, material(s, rnd, k + 1)))
+        items.append(ground(s))
         _finish(s, items, w, h)
     return build
 
@@ -79,7 +59,7 @@ def _string_world(w=W, h=H):
 def _coincident_world():
     def build(s, Rng):
         rnd = np.random.default_rng(47)
-        field = _small_spheres(s, rnd, 44)
+        field = small_spheres(s, rnd, 44)
         mats = [s.Lambertian((0.8, 0.2, 0.2)), s.Metal((0.2, 0.8, 0.2), 0.0), s.Lambertian((0.2, 0.2, 0.8))]
         # List positions of the copies.  From the first copy of sphere A at 5: 6 is another lane for every g, 13 the same lane
         # for g = 2 and 8 and another for 16, 21 and 37 the same lane for all three.  Sphere B's first copy sits in the LAST lane
@@ -98,7 +78,7 @@ def _coincident_world():
                 items.append(field.pop())
         assert len(items) == 44 + len(copies)
         items.append(s.Sphere(c[0], c[1], mats[0]))
-        items.append(_ground(s))
+        items.append(ground(s))
         _finish(s, items, W, H)
     return build
 
@@ -106,8 +86,8 @@ def _coincident_world():
 def _undecided_world():
     def build(s, Rng):
         rnd = np.random.default_rng(41)
-        items = _small_spheres(s, rnd, 37)
-        items.insert(0, _ground(s))                                                            # first
+        items = small_spheres(s, rnd, 37)
+        items.insert(0, ground(s))                                                            # first
         items.insert(17, s.Sphere((0.0, 0.0, 1006.0), 1000.0, s.Metal((0.8, 0.8, 0.9), 0.1)))  # 17 and 18: one batch of four
         items.insert(18, s.Sphere((-1006.0, 0.0, -5.0), 1000.0, s.Lambertian((0.7, 0.2, 0.2))))
         items.insert(len(items) // 2, s.Sphere((0.0, 1012.0, -5.0), 1000.0, s.Lambertian((0.6, 0.7, 0.9))))  # middle
@@ -119,22 +99,13 @@ def _undecided_world():
 def _length_world(n):
     def build(s, Rng):
         rnd = np.random.default_rng(2000 + n)
-        items = _small_spheres(s, rnd, max(0, n - 2))
+        items = small_spheres(s, rnd, max(0, n - 2))
         if n >= 2:
             items.append(s.Sphere((0.0, 0.6, -6.0), 1.2, s.Metal((0.8, 0.7, 0.6), 0.05)))
-        items.append(_ground(s))
+        items.append(ground(s))
         assert len(items) == n
         _finish(s, items, W, H)
     return build
-
-
-def _render_twice(prod, w, h, variant, flags, forcing):
-    """SPP samples, then MORE from the saved RNG streams: the frame, the rays of both launches and the continued frame."""
-    film = rt.Film(w, h)
-    st = film.render(prod, SPP, variant=variant, flags=flags, **forcing)
-    first = film.download().copy()
-    st2 = film.render(prod, MORE, variant=variant, flags=flags | rt.FLAG_KEEP_RNG_STATE, **forcing)
-    return first, film.download().copy(), st.rays, st2.rays, st.kernel_kind
 
 
 def _check(build, forcings, w=W, h=H):
@@ -142,17 +113,14 @@ def _check(build, forcings, w=W, h=H):
     want, stats = orc.render(w, h, SPP, want_stats=True)
     for forcing in forcings:
         for variant in (0, 1):
-            ref = _render_twice(prod, w, h, variant, rt.FLAG_EXACT_SCAN, forcing)
-            assert ref[4] == 16, "a list of spheres is rendered by the sphere-list kernel"
+            ref = render_twice(prod, w, h, variant, rt.FLAG_EXACT_SCAN, render=forcing)
+            assert ref.kernel_kind == 16, "a list of spheres is rendered by the sphere-list kernel"
             for flags in (0, rt.FLAG_FILTER_FP64):
-                got = _render_twice(prod, w, h, variant, flags, forcing)
-                assert got[4] == 16
-                assert got[2] == ref[2] and got[3] == ref[3], (forcing, variant, flags, "ray counts differ from the exact scan")
-                assert np.array_equal(got[0].view(np.uint64), ref[0].view(np.uint64)), (forcing, variant, flags)
-                assert np.array_equal(got[1].view(np.uint64), ref[1].view(np.uint64)), (forcing, variant, flags, "continued streams")
+                got = render_twice(prod, w, h, variant, flags, render=forcing)
+                assert got.kernel_kind == 16
+                assert_same_scan(got, ref, (forcing, variant, flags, "against the exact scan"))
             if variant == 0:
-                assert ref[2] == stats["rays"], forcing
-                assert np.array_equal(ref[0].view(np.uint64), want.view(np.uint64)), forcing
+                assert_strict_equals_oracle(ref, want, stats, label=forcing)
 
 
 def test_positions_of_the_coincident_spheres_cover_same_and_other_lanes():

@@ -20,46 +20,27 @@ import pytest
 
 import raytracinginoneweekendincuda_amd as rt
 from conftest import build_both
+from scan_checks import SPP, assert_same_scan, assert_strict_equals_oracle, ground, render_twice, small_spheres
 
 pytestmark = pytest.mark.gpu
 
-W, H, SPP, MORE = 96, 64, 4, 2
+W, H = 96, 64
 TRIP = 8  # spheres per trip of the loop (render.hip kFilterTrip)
 LENGTHS = list(range(1, 2 * TRIP + 2)) + [485, 1300]
-
-
-def _material(s, rnd, k):
-    if k % 7 == 0:
-        return s.Dielectric(1.5)
-    if k % 3 == 0:
-        return s.Metal(tuple(rnd.uniform(0.4, 0.9, 3)), float(rnd.uniform(0.0, 0.3)))
-    return s.Lambertian(tuple(rnd.uniform(0.1, 0.9, 3)))
 
 
 def _world(n):
     def build(s, Rng):
         rnd = np.random.default_rng(1000 + n)
-        items = []
-        for k in range(max(0, n - 2)):  # a loose field of small spheres in front of the camera
-            c = (float(rnd.uniform(-3, 3)), float(rnd.uniform(-0.4, 1.2)), float(rnd.uniform(-9, -3)))
-            items.append(s.Sphere(c, float(rnd.uniform(0.15, 0.45)), _material(s, rnd, k)))
+        items = small_spheres(s, rnd, max(0, n - 2))
         if n >= 2:
             items.append(s.Sphere((0.0, 0.6, -6.0), 1.2, s.Metal((0.8, 0.7, 0.6), 0.05)))
-        items.append(s.Sphere((0.0, -1000.5, -5.0), 1000.0, s.Lambertian((0.5, 0.5, 0.5))))
+        items.append(ground(s))
         assert len(items) == n
         s.SetWorld(s.HittableList(items))
         s.Camera((0.0, 0.3, 0.5), (0.0, 0.0, -5.0), (0, 1, 0), 50, W / H, 0.0, 10.0)
         s.Commit()
     return build
-
-
-def _render_twice(prod, variant, flags):
-    """SPP samples, then MORE from the saved RNG streams: the frame, the rays of both launches and the continued frame."""
-    film = rt.Film(W, H)
-    st = film.render(prod, SPP, variant=variant, flags=flags)
-    first = film.download().copy()
-    st2 = film.render(prod, MORE, variant=variant, flags=flags | rt.FLAG_KEEP_RNG_STATE)
-    return first, film.download().copy(), st.rays, st2.rays, st.kernel_kind
 
 
 def test_lengths_cover_the_trip():
@@ -72,14 +53,11 @@ def test_every_list_length_equals_exact_scan_and_oracle(n):
     prod, orc = build_both(_world(n))
     want, stats = orc.render(W, H, SPP, want_stats=True)
     for variant in (0, 1):
-        ref = _render_twice(prod, variant, rt.FLAG_EXACT_SCAN)
-        assert ref[4] == 16, "a list of spheres is rendered by the sphere-list kernel"
+        ref = render_twice(prod, W, H, variant, rt.FLAG_EXACT_SCAN)
+        assert ref.kernel_kind == 16, "a list of spheres is rendered by the sphere-list kernel"
         for flags in (0, rt.FLAG_FILTER_FP64):
-            got = _render_twice(prod, variant, flags)
-            assert got[4] == 16
-            assert got[2] == ref[2] and got[3] == ref[3], (n, variant, flags, "ray counts differ from the exact scan")
-            assert np.array_equal(got[0].view(np.uint64), ref[0].view(np.uint64)), (n, variant, flags)
-            assert np.array_equal(got[1].view(np.uint64), ref[1].view(np.uint64)), (n, variant, flags, "continued streams")
+            got = render_twice(prod, W, H, variant, flags)
+            assert got.kernel_kind == 16
+            assert_same_scan(got, ref, (n, variant, flags, "against the exact scan"))
         if variant == 0:
-            assert ref[2] == stats["rays"]
-            assert np.array_equal(ref[0].view(np.uint64), want.view(np.uint64))
+            assert_strict_equals_oracle(ref, want, stats)

@@ -14,10 +14,11 @@ import pytest
 import raytracinginoneweekendincuda_amd as rt
 import scan_segment_lists as S
 from conftest import build_both
+from scan_checks import SPP, assert_same_scan, assert_strict_equals_oracle, render_twice
 
 pytestmark = pytest.mark.gpu
 
-W, H, SPP, MORE, DEPTH = S.W, S.H, 4, 2, 8
+W, H, DEPTH = S.W, S.H, 8
 LDS_SPHERE_CAP = 1216  # rows that fit the LDS planes of the sphere-list kernel (tests/test_list_scan_lengths_gpu.py)
 
 
@@ -38,15 +39,6 @@ def _cases():
 CASES = _cases()
 
 
-def _render_twice(prod, variant, flags):
-    """SPP samples, then MORE from the saved RNG streams: the frame, the continued frame, the rays of both launches, the kernel, pixels per wave."""
-    film = rt.Film(W, H)
-    st = film.render(prod, SPP, max_depth=DEPTH, variant=variant, flags=flags)
-    first = film.download().copy()
-    st2 = film.render(prod, MORE, max_depth=DEPTH, variant=variant, flags=flags | rt.FLAG_KEEP_RNG_STATE)
-    return first, film.download().copy(), st.rays, st2.rays, st.kernel_kind, st.pixels_per_wave
-
-
 def test_lists_are_small_and_one_is_over_the_cap():
     sizes = {name: len(spheres) for name, (spheres, _) in CASES.items()}
     assert all(40 <= n <= 80 for name, n in sizes.items() if name != "over_the_lds_cap"), sizes
@@ -62,17 +54,15 @@ def test_run_segments_equal_exact_scan_fp64_filter_and_oracle(name):
     assert [(f, r, a) for f, r, a, _ in segs] == want_segments, "the list does not exercise the segments it is meant to"
     want, stats = orc.render(W, H, SPP, depth=DEPTH, want_stats=True)
     for variant in (0, 1):
-        exact = _render_twice(prod, variant, rt.FLAG_EXACT_SCAN)
-        fp64 = _render_twice(prod, variant, rt.FLAG_FILTER_FP64)
-        got = _render_twice(prod, variant, 0)
-        assert exact[4] == 16 and fp64[4] == 16 and got[4] == 16, "a list of spheres is rendered by the sphere-list kernel"
-        # one lane per ray: every wave begins with 64 live lanes, above the cooperative scan's threshold, so at least the camera
-        # rays of every pixel go through the pixel-parallel scan -- the packed loop under test when no scan flag is set
-        assert got[5] == 64 and exact[5] == 64 and fp64[5] == 64
+        exact = render_twice(prod, W, H, variant, rt.FLAG_EXACT_SCAN, depth=DEPTH)
+        fp64 = render_twice(prod, W, H, variant, rt.FLAG_FILTER_FP64, depth=DEPTH)
+        got = render_twice(prod, W, H, variant, 0, depth=DEPTH)
+        for r in (exact, fp64, got):
+            assert r.kernel_kind == 16, "a list of spheres is rendered by the sphere-list kernel"
+            # one lane per ray: every wave begins with 64 live lanes, above the cooperative scan's threshold, so at least the
+            # camera rays of every pixel go through the pixel-parallel scan -- the packed loop under test when no scan flag is set
+            assert r.pixels_per_wave == 64
         for ref, what in ((exact, "exact scan"), (fp64, "fp64 filter")):
-            assert got[2] == ref[2] and got[3] == ref[3], (name, variant, what, "ray counts differ")
-            assert np.array_equal(got[0].view(np.uint64), ref[0].view(np.uint64)), (name, variant, what)
-            assert np.array_equal(got[1].view(np.uint64), ref[1].view(np.uint64)), (name, variant, what, "continued streams")
+            assert_same_scan(got, ref, (name, variant, what))
         if variant == 0:
-            assert got[2] == stats["rays"]
-            assert np.array_equal(got[0].view(np.uint64), want.view(np.uint64))
+            assert_strict_equals_oracle(got, want, stats)

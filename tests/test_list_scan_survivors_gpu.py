@@ -13,44 +13,24 @@ import pytest
 
 import raytracinginoneweekendincuda_amd as rt
 from conftest import build_both
+from scan_checks import SPP, assert_same_scan, assert_strict_equals_oracle, ground, material, render_twice, small_spheres
 
 pytestmark = pytest.mark.gpu
 
-W, H, SPP, MORE = 96, 64, 4, 2
-
-
-def _material(s, rnd, k):
-    if k % 7 == 0:
-        return s.Dielectric(1.5)
-    if k % 3 == 0:
-        return s.Metal(tuple(rnd.uniform(0.4, 0.9, 3)), float(rnd.uniform(0.0, 0.3)))
-    return s.Lambertian(tuple(rnd.uniform(0.1, 0.9, 3)))
-
-
-def _small_spheres(s, rnd, n):
-    """A loose field of small spheres in front of the camera (what the filter decides)."""
-    items = []
-    for k in range(n):
-        c = (float(rnd.uniform(-3, 3)), float(rnd.uniform(-0.4, 1.2)), float(rnd.uniform(-9, -3)))
-        items.append(s.Sphere(c, float(rnd.uniform(0.15, 0.45)), _material(s, rnd, k)))
-    return items
-
-
-def _ground(s):
-    return s.Sphere((0.0, -1000.5, -5.0), 1000.0, s.Lambertian((0.5, 0.5, 0.5)))
+W, H = 96, 64
 
 
 def _world(where):
     def build(s, Rng):
         rnd = np.random.default_rng(41)
-        items = _small_spheres(s, rnd, 37)
+        items = small_spheres(s, rnd, 37)
         if where == "middle":
-            items.insert(len(items) // 2, _ground(s))
+            items.insert(len(items) // 2, ground(s))
         elif where == "end":
-            items.append(_ground(s))
+            items.append(ground(s))
         elif where == "several":
             # four spheres far outside the bulk, spread over the list: two of them in one group of four
-            items.insert(3, _ground(s))
+            items.insert(3, ground(s))
             items.insert(17, s.Sphere((0.0, 0.0, 1006.0), 1000.0, s.Metal((0.8, 0.8, 0.9), 0.1)))
             items.insert(18, s.Sphere((-1006.0, 0.0, -5.0), 1000.0, s.Lambertian((0.7, 0.2, 0.2))))
             items.append(s.Sphere((1010.0, 0.0, -5.0), 1000.0, s.Lambertian((0.2, 0.2, 0.7))))
@@ -58,28 +38,19 @@ def _world(where):
             # 24 spheres strung along the view axis and interleaved with the field: a central ray passes them all, and
             # more than 8 before the end of the list, so its queue is drained mid-scan
             for k in range(24):
-                items.insert(k + 2 * (k % 6), s.Sphere((0.02 * (k % 3), 0.3, -3.0 - 0.35 * k), 0.3, _material(s, rnd, k + 1)))
-            items.append(_ground(s))
+                items.insert(k + 2 * (k % 6), s.Sphere((0.02 * (k % 3), 0.3, -3.0 - 0.35 * k), 0.3, material(s, rnd, k + 1)))
+            items.append(ground(s))
         elif where == "coincident":
             # the same sphere three times in a row, then twice more further down, with different materials:
             # the lowest index wins every tie (R/HittableList.h keeps the first closest hit)
             mats = [s.Lambertian((0.8, 0.2, 0.2)), s.Metal((0.2, 0.8, 0.2), 0.0), s.Lambertian((0.2, 0.2, 0.8))]
             for j, at in enumerate((5, 6, 7, 22, 30)):
                 items.insert(at, s.Sphere((0.0, 0.4, -4.0), 0.8, mats[j % 3]))
-            items.insert(0, _ground(s))
+            items.insert(0, ground(s))
         s.SetWorld(s.HittableList(items))
         s.Camera((0.0, 0.8, 1.0), (0.0, 0.3, -5.0), (0, 1, 0), 45, W / H, 0.0, 10.0)
         s.Commit()
     return build
-
-
-def _render_twice(prod, variant, flags):
-    """SPP samples, then MORE from the saved RNG streams: the frame, the rays of both launches and the continued frame."""
-    film = rt.Film(W, H)
-    st = film.render(prod, SPP, variant=variant, flags=flags)
-    first = film.download().copy()
-    st2 = film.render(prod, MORE, variant=variant, flags=flags | rt.FLAG_KEEP_RNG_STATE)
-    return first, film.download().copy(), st.rays, st2.rays, st.kernel_kind
 
 
 @pytest.mark.parametrize("where", ["middle", "end", "several", "cluster", "coincident"])
@@ -87,14 +58,11 @@ def test_filtered_scan_equals_exact_scan_and_oracle(where):
     prod, orc = build_both(_world(where))
     want, stats = orc.render(W, H, SPP, want_stats=True)
     for variant in (0, 1):
-        ref = _render_twice(prod, variant, rt.FLAG_EXACT_SCAN)
-        assert ref[4] == 16, "a list of spheres is rendered by the sphere-list kernel"
+        ref = render_twice(prod, W, H, variant, rt.FLAG_EXACT_SCAN)
+        assert ref.kernel_kind == 16, "a list of spheres is rendered by the sphere-list kernel"
         for flags in (0, rt.FLAG_FILTER_FP64):
-            got = _render_twice(prod, variant, flags)
-            assert got[4] == 16
-            assert got[2] == ref[2] and got[3] == ref[3], (variant, flags, "ray counts differ from the exact scan")
-            assert np.array_equal(got[0].view(np.uint64), ref[0].view(np.uint64)), (variant, flags)
-            assert np.array_equal(got[1].view(np.uint64), ref[1].view(np.uint64)), (variant, flags, "continued streams")
+            got = render_twice(prod, W, H, variant, flags)
+            assert got.kernel_kind == 16
+            assert_same_scan(got, ref, (variant, flags, "against the exact scan"))
         if variant == 0:
-            assert ref[2] == stats["rays"]
-            assert np.array_equal(ref[0].view(np.uint64), want.view(np.uint64))
+            assert_strict_equals_oracle(ref, want, stats)

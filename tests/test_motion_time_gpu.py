@@ -12,7 +12,8 @@ import numpy as np
 import pytest
 
 from conftest import build_both
-from test_custom_scenes_gpu import _deep_media_world, compare
+from frame_helpers import compare
+from test_custom_scenes_gpu import _deep_media_world
 from test_motion_time import H, SPP, W, field, instanced_group
 
 pytestmark = pytest.mark.gpu

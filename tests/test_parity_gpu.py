@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import raytracinginoneweekendincuda_amd as rt
+from frame_helpers import compare
 
 pytestmark = pytest.mark.gpu
 
@@ -27,19 +28,12 @@ CASES = [
 ]
 
 
-def compare(got, want):
-    diff = np.abs(got - want)
-    exact = np.mean(np.all(got.view(np.uint64) == want.view(np.uint64), axis=-1))
-    within = np.mean(np.all(diff <= TOL, axis=-1))
-    return exact, within, diff.max()
-
-
 @pytest.mark.parametrize("scene_id,world_kind,min_exact", CASES)
 def test_strict_matches_oracle(oracle, earth, scene_id, world_kind, min_exact):
     want = oracle.render(scene_id, world_kind, W, H, SPP, earth=earth)
     s = rt.builtin_scene(scene_id, world_kind, W, H, earth=earth)
     got, st = s.render(W, H, SPP, variant=0)
-    exact, within, worst = compare(got, want)
+    exact, within, worst = compare(got, want, TOL)
     print(f"scene {scene_id} world {world_kind}: bit-exact {exact:.4f}, within {TOL:g}: {within:.4f}, max |d| {worst:.3g}")
     assert st.samples == W * H * SPP
     assert within >= 0.999, f"only {within:.4f} of pixels within {TOL}"
@@ -50,7 +44,7 @@ def test_strict_matches_oracle(oracle, earth, scene_id, world_kind, min_exact):
 def test_fast_variant_within_tolerance(oracle, earth, scene_id, world_kind):
     want = oracle.render(scene_id, world_kind, W, H, SPP, earth=earth)
     got, _ = rt.builtin_scene(scene_id, world_kind, W, H, earth=earth).render(W, H, SPP, variant=1)
-    exact, within, worst = compare(got, want)
+    exact, within, worst = compare(got, want, TOL)
     print(f"fast scene {scene_id}: bit-exact {exact:.4f}, within {within:.4f}, max |d| {worst:.3g}")
     assert within >= 0.995
 
@@ -297,7 +291,7 @@ def test_full_size_rows_match_oracle(oracle):
     got, st = s.render(Wf, Hf, 1, variant=0)
     for row in (0, 399, 799):
         want = oracle.render(11, 1, Wf, Hf, 1, rows=(row, row + 1))
-        exact, within, worst = compare(got[row:row + 1], want[row:row + 1])
+        exact, within, worst = compare(got[row:row + 1], want[row:row + 1], TOL)
         assert within >= 0.999 and exact >= 0.99, (row, exact, within, worst)
 
 
@@ -497,7 +491,7 @@ def test_full_size_rows_match_oracle_bvh_configs(oracle, earth, cfg):
     got, st = rt.builtin_scene(scene_id, world, w, h, earth=e).render(w, h, 1, variant=0)
     for row in (0, h // 2 - 1, h - 1):
         want = oracle.render(scene_id, world, w, h, 1, earth=e, rows=(row, row + 1))
-        exact, within, worst = compare(got[row:row + 1], want[row:row + 1])
+        exact, within, worst = compare(got[row:row + 1], want[row:row + 1], TOL)
         print(f"{cfg} row {row}: bit-exact {exact:.4f}, within {within:.4f}, max |d| {worst:.3g}")
         assert within >= 0.999 and exact >= (0.95 if cfg == "c5" else 0.99), (cfg, row, exact, within, worst)
 
@@ -520,7 +514,7 @@ def test_band_of_the_benchmark_frame_at_benchmark_spp(oracle, earth, cfg, spp, m
     scene = rt.builtin_scene(scene_id, world, w, h, earth=e)
     for variant, floor in ((0, min_strict), (1, min_fast)):
         got, _ = _stripe_of_full_frame(scene, w, h, stripe, spp, variant)
-        exact, within, worst = compare(got, want)
+        exact, within, worst = compare(got, want, TOL)
         q = lambda f: (256.0 * np.clip(f, 0.0, 0.999)).astype(np.int32)
         ppm = np.mean(np.all(q(got) == q(want), axis=-1))
         print(f"{cfg} x{spp}spp {'strict' if variant == 0 else 'fast'}: bit-exact {exact:.4f}, within {TOL:g}: {within:.4f}, "
@@ -569,7 +563,7 @@ def test_c5_rows_at_its_real_5000_spp(oracle, earth):
     want = oracle.render(scene_id, world, w, h, spp, earth=earth, rows=(stripe * 8, stripe * 8 + n_rows))[stripe * 8:stripe * 8 + n_rows]
     scene = rt.builtin_scene(scene_id, world, w, h, earth=earth)
     got, st = _stripe_of_full_frame(scene, w, h, stripe, spp, 0)
-    exact, within, worst = compare(got[:n_rows], want)
+    exact, within, worst = compare(got[:n_rows], want, TOL)
     print(f"c5 x{spp}spp strict, rows {stripe * 8}..{stripe * 8 + n_rows - 1}: bit-exact {exact:.4f}, within {TOL:g}: {within:.4f}, "
           f"max |d| {worst:.3g}, {st.rays / st.samples:.2f} rays/sample")
     assert within >= 0.9995 and exact >= 0.98, (exact, within, worst)

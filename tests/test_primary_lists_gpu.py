@@ -13,10 +13,12 @@ import pytest
 import raytracinginoneweekendincuda_amd as rt
 import primary_list_worlds as P
 from conftest import build_both
+from frame_helpers import render_params
+from scan_checks import MORE, SPP, assert_same_scan, assert_strict_equals_oracle, render_twice
 
 pytestmark = pytest.mark.gpu
 
-SPP, MORE, DEPTH = 4, 2, 8
+DEPTH = 8
 WORLDS = P.cases()
 
 # name -> (world, keywords): width / height, depth, film (Film keywords), render (render keywords), flags (on every launch),
@@ -41,20 +43,6 @@ CASES = {
 }
 
 
-def _render_twice(prod, variant, flags, kw):
-    """SPP samples, then MORE from the saved RNG streams: frame, continued frame, the rays of both launches, kernel kind, pixels per wave."""
-    w, h = kw.get("width", P.W), kw.get("height", P.H)
-    film = rt.Film(w, h, **kw.get("film", {}))
-    if "adaptive" in kw:
-        film.set_adaptive(**kw["adaptive"])
-    common = dict(max_depth=kw.get("depth", DEPTH), variant=variant, **kw.get("render", {}))
-    flags |= kw.get("flags", 0)
-    st = film.render(prod, SPP, flags=flags, **common)
-    first = film.download().copy()
-    st2 = film.render(prod, MORE, flags=flags | rt.FLAG_KEEP_RNG_STATE, **common)
-    return first, film.download().copy(), st.rays, st2.rays, st.kernel_kind, st.pixels_per_wave
-
-
 @pytest.mark.parametrize("name", sorted(CASES))
 def test_primary_lists_change_nothing(name):
     world_name, kw = CASES[name]
@@ -63,30 +51,31 @@ def test_primary_lists_change_nothing(name):
     if (w, h) != (P.W, P.H):
         build = P.world(spheres, aspect=w / h)
     prod, orc = build_both(build)
-    film_kw = kw.get("film", {})
+    film_kw, depth = kw.get("film", {}), kw.get("depth", DEPTH)
     rows = rt.stripe_rows(h, film_kw.get("stripe_rows", 8), film_kw.get("rank", 0), film_kw.get("world_size", 1))
     want = stats = None
     if "adaptive" not in kw:
-        want, stats = orc.render(w, h, SPP, depth=kw.get("depth", DEPTH), want_stats=True)
+        want, stats = orc.render(w, h, SPP, depth=depth, want_stats=True)
+
+    def twice(variant, flags):
+        return render_twice(prod, w, h, variant, flags | kw.get("flags", 0), depth=depth, film=film_kw, render=kw.get("render"),
+                            adaptive=kw.get("adaptive"))
+
     for variant in (0, 1):
-        got = _render_twice(prod, variant, 0, kw)
-        off = _render_twice(prod, variant, rt.FLAG_NO_PRIMARY_LISTS, kw)
-        exact = _render_twice(prod, variant, rt.FLAG_EXACT_SCAN, kw)
-        fp64 = _render_twice(prod, variant, rt.FLAG_FILTER_FP64, kw)
+        got = twice(variant, 0)
+        off = twice(variant, rt.FLAG_NO_PRIMARY_LISTS)
+        exact = twice(variant, rt.FLAG_EXACT_SCAN)
+        fp64 = twice(variant, rt.FLAG_FILTER_FP64)
         for r in (got, off, exact, fp64):
-            assert r[4] & ~512 == 16, "a list of spheres is rendered by the sphere-list kernel (512: its adaptive form)"
-            assert r[5] == kw.get("ppw", 64)
+            assert r.kernel_kind & ~512 == 16, "a list of spheres is rendered by the sphere-list kernel (512: its adaptive form)"
+            assert r.pixels_per_wave == kw.get("ppw", 64)
         for ref, what in ((off, "no primary lists"), (exact, "exact scan"), (fp64, "fp64 filter")):
-            assert got[2] == ref[2] and got[3] == ref[3], (name, variant, what, "ray counts differ", got[2:4], ref[2:4])
-            assert np.array_equal(got[0].view(np.uint64), ref[0].view(np.uint64)), (name, variant, what)
-            assert np.array_equal(got[1].view(np.uint64), ref[1].view(np.uint64)), (name, variant, what, "continued streams")
+            assert_same_scan(got, ref, (name, variant, what))
         if kw.get("sky"):
             # every path is one camera ray into the sky: this is also the check that a wave of fresh lanes alone comes to an end
-            assert got[2] == w * h * SPP and got[3] == w * h * MORE
+            assert got.rays == w * h * SPP and got.more_rays == w * h * MORE
         if variant == 0 and want is not None:
-            if len(rows) == h:
-                assert got[2] == stats["rays"]
-            assert np.array_equal(got[0][rows].view(np.uint64), want[rows].view(np.uint64))
+            assert_strict_equals_oracle(got, want, stats, rows)
 
 
 @pytest.mark.parametrize("w, h, spp, rehearses", [(128, 96, 16, False), (256, 256, 64, True)])
@@ -97,7 +86,7 @@ def test_rehearsal_with_capped_pixels(w, h, spp, rehearses):
     planner rehearses with a cap, and the camera sits in a glass sphere so that some pixels reach it."""
     spheres, _ = WORLDS["camera_inside_glass"]
     prod = P.product(P.world(spheres, aspect=w / h, glass=(len(spheres) - 1,)))
-    plan = prod.plan_launch(rt.RenderParams(w, h, spp, 50, 1984, 8, 0, 1, 0, 0, 0, None, 0, 0, 0, 0, 0, 0))
+    plan = prod.plan_launch(render_params(w, h, spp))
     assert (plan["probe_spp"] > 0 and plan["pixel_classes"] == 1 and plan["probe_ray_cap"] > 0) == rehearses
     for variant in (0, 1):
         out = []

@@ -14,7 +14,8 @@ import torch
 
 import raytracinginoneweekendincuda_amd as rt
 from raytracinginoneweekendincuda_amd import _lib, api
-from conftest import ROOT, synthetic_earth
+from conftest import ROOT
+from query_helpers import bits, centre_rays, mixed_world, sphere_roots
 
 pytestmark = pytest.mark.gpu
 
@@ -22,11 +23,6 @@ W, H = 32, 24
 N = W * H
 SEED = 1984
 ALL = ("radiance", "path_rays", "rng_state")
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint64) if a.dtype == np.float64 else a
 
 
 def same(got, want, keys=ALL):
@@ -70,50 +66,13 @@ def camera_rays(scene, seed=SEED, width=W, height=H):
     return o, d, tm, states
 
 
-def centre_rays(scene, width=W, height=H):
-    """The rays through the pixel centres, ((llc + u * hor) + v * ver) - origin with u = (i + 0.5) / W, v = (j + 0.5) / H (what
-    rtow --pick and --radiance-at trace).  Returns (origins, directions, time0, background)."""
-    cam = scene.dump_camera()
-    bg, origin, llc, hor, ver = (cam[3 * k:3 * k + 3] for k in range(5))
-    u = ((np.arange(width) + 0.5) / width)[None, :, None]
-    v = ((np.arange(height) + 0.5) / height)[:, None, None]
-    d = (((llc + u * hor) + v * ver) - origin).reshape(-1, 3)
-    return np.ascontiguousarray(np.broadcast_to(origin, d.shape)), np.ascontiguousarray(d), float(cam[25]), bg.copy()
-
-
 def host_states(seed, first_sequence, count):
     return np.array([rt.Rng(seed, k + first_sequence).state() for k in range(count)], dtype=np.uint32)
 
 
 # ---- scenes ----
-def _mixed(world_kind):
-    """The mixed scene of tests/test_ray_query_gpu.py (every primitive, texture and material kind, no media): aperture 0.1 and
-    shutter 0..1, so the lens and the time draws count."""
-    s = rt.Scene()
-    earth = s.ImageTexture(synthetic_earth())
-    checker = s.CheckerTexture(0.6, s.SolidColor((0.2, 0.3, 0.1)), s.SolidColor((0.9, 0.9, 0.9)))
-    marble = s.NoiseTexture(4.0, rt.Rng(1984, 0))
-    items = [s.Sphere((0, -100.5, -1), 100.0, s.Lambertian(checker)),
-             s.Sphere((-1.1, 0.0, -1.2), 0.5, s.Lambertian(earth)),
-             s.Sphere((0.0, 0.0, -1.0), 0.5, s.Dielectric(1.5)),
-             s.Sphere((1.1, 0.0, -1.2), 0.5, s.Metal((0.8, 0.6, 0.2), 0.3)),
-             s.Sphere((0.4, 0.9, -1.6), 0.35, s.Lambertian(marble)),
-             s.MovingSphere((-0.6, 0.8, -1.4), (-0.6, 1.1, -1.4), 0.0, 1.0, 0.25, s.Lambertian((0.7, 0.2, 0.2))),
-             s.MovingSphere((1.5, 0.7, -0.8), (1.2, 0.7, -0.8), 0.0, 1.0, 0.2, s.Metal((0.9, 0.9, 0.9), 0.0)),
-             s.Quad((-2.5, -0.5, -2.5), (5, 0, 0), (0, 2.5, 0), s.Lambertian(earth)),
-             s.Quad((-2.4, -0.5, -2.4), (0, 0, 2.5), (0, 1.5, 0.3), s.DiffuseLight((3.0, 2.5, 2.0))),
-             s.Quad((2.0, -0.5, 0.2), (0.3, 0, -2.4), (0, 1.2, 0), s.Lambertian(marble))]
-    for k in range(9):
-        items.append(s.Sphere((-2.0 + 0.5 * k, -0.35, 0.1), 0.15, (s.Lambertian((0.1, 0.2, 0.8)), s.Metal((0.7, 0.7, 0.7), 0.1),
-                                                                   s.Isotropic((0.3, 0.9, 0.3)))[k % 3]))
-    s.SetWorld(s.BvhNode(items) if world_kind == 0 else s.HittableList(items))
-    s.Camera((0.3, 0.7, 2.6), (0, 0.1, -1), (0, 1, 0), 55.0, W / H, 0.1, 3.4, 0.0, 1.0, (0.55, 0.65, 0.9))
-    s.Commit()
-    return s
-
-
 SCENES = {
-    "mixed bvh": lambda: _mixed(0), "mixed list": lambda: _mixed(1),
+    "mixed bvh": lambda: mixed_world(rt.Scene(), rt.Rng, 0, W / H), "mixed list": lambda: mixed_world(rt.Scene(), rt.Rng, 1, W / H),
     "scene 9 bvh": lambda: rt.builtin_scene(9, 0, W, H), "scene 9 list": lambda: rt.builtin_scene(9, 1, W, H),   # media, boxes, earth, Perlin
     "scene 7 bvh": lambda: rt.builtin_scene(7, 0, W, H),
 }
@@ -223,10 +182,6 @@ def test_a_perfect_mirror_returns_its_colour_times_the_emitted_colour(world, var
     assert not np.array_equal(out["rng_state"], host_states(SEED, 0, N)), "Metal::Scatter draws its fuzz sample even at fuzz 0"
 
 
-def _dot3(a, b):
-    return a[..., 0] * b[..., 0] + a[..., 1] * b[..., 1] + a[..., 2] * b[..., 2]
-
-
 @functools.lru_cache(maxsize=None)
 def closed_form_sphere():
     """The closed_form_sphere scene of tests/test_ray_query_gpu.py: a Lambertian (0.6, 0.4, 0.1) sphere in background (0.2, 0.3,
@@ -236,12 +191,10 @@ def closed_form_sphere():
     s.SetWorld(s.HittableList([s.Sphere(centre, radius, s.Lambertian(colour))]))
     s.Camera((0, 0, 0), (0, 0, -1), (0, 1, 0), 40.0, W / H, 0.0, 1.0, 0.0, 0.0, bg_colour)
     s.Commit()
-    o, d, _, bg = centre_rays(s)
-    oc = o - np.asarray(centre)
-    a, b, c = _dot3(d, d), _dot3(oc, d), _dot3(oc, oc) - radius * radius   # R/Sphere.h:28-36
-    disc = b * b - a * c
-    assert not (np.abs(disc / (b * b)) <= 1e-9).any(), "no centre ray of this set grazes the sphere"
-    hits = disc > 0
+    o, d, _, bg = centre_rays(s, W, H)
+    _, _, rel_disc = sphere_roots(o, d, centre, radius)
+    assert not (np.abs(rel_disc) <= 1e-9).any(), "no centre ray of this set grazes the sphere"
+    hits = rel_disc > 0
     assert 0.33 < hits.mean() < 0.35
     return s, o, d, bg, np.asarray(colour), hits
 
@@ -411,7 +364,7 @@ def test_statistics_count_the_searches_and_leave_the_outputs_alone(name):
     """A call with statistics (two events and a counter word around the kernel) against the plain launch: the same outputs bit for
     bit.  100 rays are one full wave and a ragged one for the count's reduction over each wave."""
     scene = scene_of(name)
-    o, d, time0, _ = centre_rays(scene)
+    o, d, time0, _ = centre_rays(scene, W, H)
     o, d = o[:100].copy(), d[:100].copy()
     plain = scene.radiance(o, d, time=time0, samples=2, variant=0, want=ALL)
     counted, st = scene.radiance(o, d, time=time0, samples=2, variant=0, want=ALL, stats=True)
@@ -471,7 +424,7 @@ def test_rtow_radiance_at_prints_what_the_api_returns(scene_id, pixel, spp):
     words = lines[0].split()
     assert words[1] == f"{i},{j}:" and [words[k] for k in (2, 4, 8, 10)] == ["samples", "radiance", "rays", "seconds"], lines[0]
     scene = rt.builtin_scene(scene_id, 0, W, H)
-    o, d, time0, _ = centre_rays(scene)
+    o, d, time0, _ = centre_rays(scene, W, H)
     k = j * W + i
     out = scene.radiance(o[k:k + 1].copy(), d[k:k + 1].copy(), time=time0, samples=spp, first_sequence=k, want=("radiance", "path_rays"))
     assert int(words[3]) == spp

@@ -13,7 +13,8 @@ import torch
 
 import raytracinginoneweekendincuda_amd as rt
 from raytracinginoneweekendincuda_amd import _lib, api
-from conftest import ROOT, synthetic_earth
+from conftest import ROOT
+from query_helpers import bits, centre_rays, dot3, mixed_world, sphere_roots
 
 pytestmark = pytest.mark.gpu
 
@@ -22,38 +23,7 @@ INF = float("inf")
 ALL = ("t", "normal", "uv", "albedo", "leaf", "front_face", "material")
 
 
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint64) if a.dtype == np.float64 else a
-
-
 # ---- rays ----
-def centre_rays(scene, width=W, height=H):
-    """The samples == 0 rays of the feature pass restated from dump_camera {bg, origin, llc, horizontal, vertical, ...} in
-    centre_ray's order of operations, ((llc + u * hor) + v * ver) - origin with u = (i + 0.5) / W, v = (j + 0.5) / H: IEEE double
-    without contraction on both sides.  Ray k = j * W + i.  Returns (origins (N, 3), directions (N, 3), time0, background)."""
-    cam = scene.dump_camera()
-    bg, origin, llc, hor, ver = (cam[3 * k:3 * k + 3] for k in range(5))
-    u = ((np.arange(width) + 0.5) / width)[None, :, None]
-    v = ((np.arange(height) + 0.5) / height)[:, None, None]
-    d = (((llc + u * hor) + v * ver) - origin).reshape(-1, 3)
-    return np.ascontiguousarray(np.broadcast_to(origin, d.shape)), np.ascontiguousarray(d), float(cam[25]), bg.copy()
-
-
-def dot3(a, b):
-    return a[..., 0] * b[..., 0] + a[..., 1] * b[..., 1] + a[..., 2] * b[..., 2]
-
-
-def sphere_roots(o, d, centre, radius):
-    """R/Sphere.h:28-36: (near root, far root, discriminant relative to b^2); the roots are NaN where the line misses."""
-    oc = o - np.asarray(centre, dtype=np.float64)
-    a, b, c = dot3(d, d), dot3(oc, d), dot3(oc, oc) - radius * radius
-    disc = b * b - a * c
-    with np.errstate(invalid="ignore"):
-        root = np.sqrt(disc)
-    return (-b - root) / a, (-b + root) / a, disc / (b * b)
-
-
 def sphere_uv(n):
     """R/Sphere.h:74-81 on unit outward normals (N, 3): (u, v) as (N, 2)."""
     theta, phi = np.arccos(-n[:, 1]), np.arctan2(-n[:, 2], n[:, 0]) + np.pi
@@ -68,33 +38,8 @@ def uv_bound(n):
 
 
 # ---- scenes ----
-def _mixed(world_kind):
-    """The mixed scene of tests/test_features_gpu.py (every primitive, texture and material kind, no media), at this file's frame."""
-    s = rt.Scene()
-    earth = s.ImageTexture(synthetic_earth())
-    checker = s.CheckerTexture(0.6, s.SolidColor((0.2, 0.3, 0.1)), s.SolidColor((0.9, 0.9, 0.9)))
-    marble = s.NoiseTexture(4.0, rt.Rng(1984, 0))
-    items = [s.Sphere((0, -100.5, -1), 100.0, s.Lambertian(checker)),
-             s.Sphere((-1.1, 0.0, -1.2), 0.5, s.Lambertian(earth)),
-             s.Sphere((0.0, 0.0, -1.0), 0.5, s.Dielectric(1.5)),
-             s.Sphere((1.1, 0.0, -1.2), 0.5, s.Metal((0.8, 0.6, 0.2), 0.3)),
-             s.Sphere((0.4, 0.9, -1.6), 0.35, s.Lambertian(marble)),
-             s.MovingSphere((-0.6, 0.8, -1.4), (-0.6, 1.1, -1.4), 0.0, 1.0, 0.25, s.Lambertian((0.7, 0.2, 0.2))),
-             s.MovingSphere((1.5, 0.7, -0.8), (1.2, 0.7, -0.8), 0.0, 1.0, 0.2, s.Metal((0.9, 0.9, 0.9), 0.0)),
-             s.Quad((-2.5, -0.5, -2.5), (5, 0, 0), (0, 2.5, 0), s.Lambertian(earth)),
-             s.Quad((-2.4, -0.5, -2.4), (0, 0, 2.5), (0, 1.5, 0.3), s.DiffuseLight((3.0, 2.5, 2.0))),
-             s.Quad((2.0, -0.5, 0.2), (0.3, 0, -2.4), (0, 1.2, 0), s.Lambertian(marble))]
-    for k in range(9):
-        items.append(s.Sphere((-2.0 + 0.5 * k, -0.35, 0.1), 0.15, (s.Lambertian((0.1, 0.2, 0.8)), s.Metal((0.7, 0.7, 0.7), 0.1),
-                                                                   s.Isotropic((0.3, 0.9, 0.3)))[k % 3]))
-    s.SetWorld(s.BvhNode(items) if world_kind == 0 else s.HittableList(items))
-    s.Camera((0.3, 0.7, 2.6), (0, 0.1, -1), (0, 1, 0), 55.0, W / H, 0.1, 3.4, 0.0, 1.0, (0.55, 0.65, 0.9))
-    s.Commit()
-    return s
-
-
 SCENES = {
-    "mixed bvh": lambda: _mixed(0), "mixed list": lambda: _mixed(1),
+    "mixed bvh": lambda: mixed_world(rt.Scene(), rt.Rng, 0, W / H), "mixed list": lambda: mixed_world(rt.Scene(), rt.Rng, 1, W / H),
     "scene 9 bvh": lambda: rt.builtin_scene(9, 0, W, H), "scene 9 list": lambda: rt.builtin_scene(9, 1, W, H),   # media that draw
     "scene 8 bvh": lambda: rt.builtin_scene(8, 0, W, H), "scene 8 list": lambda: rt.builtin_scene(8, 1, W, H),
 }
@@ -112,7 +57,7 @@ def scene_of(name):
 def closest_of(name, variant=0):
     """Every output of the closest-hit query of the scene's centre rays, computed once and shared (nobody writes to it)."""
     scene = scene_of(name)
-    o, d, time0, _ = centre_rays(scene)
+    o, d, time0, _ = centre_rays(scene, W, H)
     out = scene.intersect(o, d, time=time0, variant=variant, want=ALL + ("occluded",))
     for a in out.values():
         a.setflags(write=False)
@@ -127,7 +72,7 @@ def closed_form_sphere():
     s.SetWorld(s.HittableList([s.Sphere(centre, radius, s.Lambertian(colour))]))
     s.Camera((0, 0, 0), (0, 0, -1), (0, 1, 0), 40.0, W / H, 0.0, 1.0, 0.0, 0.0, bg_colour)
     s.Commit()
-    o, d, _, bg = centre_rays(s)
+    o, d, _, bg = centre_rays(s, W, H)
     near, far, rel_disc = sphere_roots(o, d, centre, radius)
     grazing = np.abs(rel_disc) <= 1e-9
     assert grazing.mean() <= 0.02 and not grazing.any(), "no centre ray of this set grazes the sphere"
@@ -145,7 +90,7 @@ WINDOWS = {"whole": (0.001, INF, "near"), "tmax 2.0": (0.001, 2.0, None), "tmin 
 @pytest.mark.parametrize("name", sorted(SCENES))
 def test_centre_rays_equal_the_feature_pass_bit_for_bit(name):
     scene = scene_of(name)
-    o, d, _, _ = centre_rays(scene)
+    o, d, _, _ = centre_rays(scene, W, H)
     film = rt.Film(W, H)
     film.render_features(scene, samples=0, seed=1984, variant=0)
     albedo, normal, depth = (p.reshape(W * H, -1) for p in film.features())
@@ -269,7 +214,7 @@ def test_quads_and_an_instanced_box(world):
     s.SetWorld(s.BvhNode(items) if world == "bvh" else s.HittableList(items))
     s.Camera((0, 0.6, 3), (0, 0, -2), (0, 1, 0), 50.0, W / H, 0.0, 1.0)
     s.Commit()
-    o, d, time0, _ = centre_rays(s)
+    o, d, time0, _ = centre_rays(s, W, H)
     out = s.intersect(o, d, time=time0)
     t, normal = out["t"], out["normal"]
     assert np.isfinite(t).all(), "floor and wall fill the frame"
@@ -349,7 +294,7 @@ def test_leaf_is_the_position_of_the_nearest_object_in_both_world_kinds():
         s.SetWorld(s.BvhNode(items) if world == "bvh" else s.HittableList(items))
         s.Camera((0, 1.0, 2.0), (0, 0.3, -4.0), (0, 1, 0), 45.0, W / H, 0.0, 1.0)
         s.Commit()
-        o, d, time0, _ = centre_rays(s)
+        o, d, time0, _ = centre_rays(s, W, H)
         # the analytically nearest object: 0..8 the spheres, 9 the ground, -1 nothing
         ts = np.full((10, len(o)), INF)
         sure = np.ones(len(o), dtype=bool)
@@ -394,7 +339,7 @@ def test_leaf_is_the_position_of_the_nearest_object_in_both_world_kinds():
 @pytest.mark.parametrize("name", sorted(SCENES))
 def test_occluded_is_exactly_a_hit_of_the_closest_query(name, variant):
     scene = scene_of(name)
-    o, d, time0, _ = centre_rays(scene)
+    o, d, time0, _ = centre_rays(scene, W, H)
     got = closest_of(name, variant)
     assert np.array_equal(got["occluded"] != 0, np.isfinite(got["t"])), "the closest-hit query's own flag"
     for tmin, tmax in ((0.001, INF), (0.001, 3.0), (2.5, INF)):
@@ -448,7 +393,7 @@ def _device_query(scene, o, d, count, time, mode=0, first_sequence=0, variant=0)
 def test_batch_edges_write_exactly_their_rays(count):
     for name in ("mixed bvh", "mixed list"):
         scene = scene_of(name)
-        o, d, time0, _ = centre_rays(scene)
+        o, d, time0, _ = centre_rays(scene, W, H)
         whole = closest_of(name)
         got = _device_query(scene, o, d, count, time0)
         for key in ALL + ("occluded",):
@@ -464,7 +409,7 @@ def test_statistics_count_the_hits_and_leave_the_outputs_alone(name):
     """The closest-hit query with statistics (two events and a counter word around the kernel) against the plain launch: the same
     outputs bit for bit.  100 rays are one full wave and a ragged one for the count of one atomic per wave."""
     scene = scene_of(name)
-    o, d, time0, _ = centre_rays(scene)
+    o, d, time0, _ = centre_rays(scene, W, H)
     o, d = o[:100].copy(), d[:100].copy()
     plain = scene.intersect(o, d, time=time0, variant=0, want=ALL + ("occluded",))
     counted, st = scene.intersect(o, d, time=time0, variant=0, want=ALL + ("occluded",), stats=True)
@@ -480,7 +425,7 @@ def test_statistics_count_the_hits_and_leave_the_outputs_alone(name):
 @pytest.mark.parametrize("name", ["mixed bvh", "mixed list"])
 def test_permuted_rays_give_permuted_results(name):
     scene = scene_of(name)
-    o, d, time0, _ = centre_rays(scene)
+    o, d, time0, _ = centre_rays(scene, W, H)
     order = np.random.default_rng(3).permutation(len(o))
     whole = closest_of(name)
     got = scene.intersect(np.ascontiguousarray(o[order]), np.ascontiguousarray(d[order]), time=time0)
@@ -491,7 +436,7 @@ def test_permuted_rays_give_permuted_results(name):
 @pytest.mark.parametrize("name", ["scene 9 bvh", "scene 9 list"])
 def test_a_split_batch_continues_the_streams(name):
     scene = scene_of(name)
-    o, d, time0, _ = centre_rays(scene)
+    o, d, time0, _ = centre_rays(scene, W, H)
     whole = closest_of(name)
     split = 301
     first = scene.intersect(o[:split].copy(), d[:split].copy(), time=time0)
@@ -507,7 +452,7 @@ def test_a_split_batch_continues_the_streams(name):
 @pytest.mark.parametrize("name", ["mixed bvh", "scene 9 list"])
 def test_each_output_alone_is_that_output_among_all(name):
     scene = scene_of(name)
-    o, d, time0, _ = centre_rays(scene)
+    o, d, time0, _ = centre_rays(scene, W, H)
     whole = closest_of(name)
     for key in ALL + ("occluded",):
         alone = scene.intersect(o, d, time=time0, want=(key,))
@@ -519,7 +464,7 @@ def test_each_output_alone_is_that_output_among_all(name):
 def test_torch_tensors_are_read_in_place_and_leave_films_alone():
     name = "scene 8 bvh"
     scene = scene_of(name)
-    o, d, time0, _ = centre_rays(scene)
+    o, d, time0, _ = centre_rays(scene, W, H)
     film = rt.Film(W, H)
     before_stats = film.render(scene, 2, variant=0)
     before = film.download()
@@ -559,7 +504,7 @@ def test_rtow_pick_prints_what_the_api_returns(scene_id, pixel):
     words = lines[0].split()
     assert words[1] == f"{i},{j}:" and [words[k] for k in (2, 4, 6, 8, 12, 16)] == ["leaf", "material", "t", "point", "normal", "albedo"]
     scene = rt.builtin_scene(scene_id, 0, W, H)
-    o, d, time0, _ = centre_rays(scene)
+    o, d, time0, _ = centre_rays(scene, W, H)
     k = j * W + i
     out = scene.intersect(o[k:k + 1].copy(), d[k:k + 1].copy(), time=time0, first_sequence=k)
     assert np.isfinite(out["t"][0]), "the picked pixel shows an object"

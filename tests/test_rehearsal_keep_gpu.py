@@ -9,6 +9,7 @@ import pytest
 import torch
 
 import raytracinginoneweekendincuda_amd as rt
+from query_helpers import bits
 
 pytestmark = pytest.mark.gpu
 
@@ -19,10 +20,6 @@ VARIANTS = [0, 1]   # the strict and the fast build
 
 def num_cus():
     return torch.cuda.get_device_properties(0).multi_processor_count
-
-
-def bits(frame):
-    return np.ascontiguousarray(frame).view(np.uint64)
 
 
 def plans(scene, film, spp, variant, flags=0, adaptive=False, **kw):

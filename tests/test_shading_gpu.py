@@ -17,7 +17,8 @@ import numpy as np
 import pytest
 
 from conftest import build_both
-from test_custom_scenes_gpu import compare
+from frame_helpers import compare
+from query_helpers import bits
 
 pytestmark = pytest.mark.gpu
 
@@ -25,10 +26,6 @@ W, H = 96, 64
 
 FLAG_KEEP_RNG_STATE, FLAG_FORCE_GENERAL, FLAG_ACCUMULATE, FLAG_ALWAYS_WALK = 1, 2, 8, 32
 FLAG_NO_PIXEL_CLASSES, FLAG_REFERENCE_TREE, FLAG_EXACT_SCAN, FLAG_FILTER_FP64 = 64, 128, 256, 2048
-
-
-def bits(frame):
-    return frame.view(np.uint64)
 
 
 # ------------------------------------------------------------------------------------------------------------------

@@ -13,6 +13,7 @@ import pytest
 
 import tie_worlds as T
 from conftest import build_both
+from frame_helpers import compare
 
 pytestmark = pytest.mark.gpu
 
@@ -21,7 +22,7 @@ SPHERE_PAIRS = [p for p in T.PAIRS if T.PAIRS[p][1] == "sphere"]
 
 
 def against_the_oracle(what, got, st, want, stats):
-    exact, within = T.compare(got, want)
+    exact, within, _ = compare(got, want)
     print(f"{what}: kernel kind {st.kernel_kind}, bit-exact {exact:.4f}, within {within:.4f}")
     assert st.rays == stats["rays"], (what, st.rays, stats["rays"])
     assert within >= 0.999 and exact >= 0.98, (what, exact, within)

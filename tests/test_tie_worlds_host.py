@@ -16,6 +16,7 @@ import pytest
 import raytracinginoneweekendincuda_amd as rt
 import tie_worlds as T
 from conftest import OracleRng, OracleScene
+from frame_helpers import render_params
 from test_custom_scenes_gpu import _deep_media_world
 
 MIN_SHARE = 0.005
@@ -35,8 +36,7 @@ def product(build):
 
 
 def kind(scene, flags=0, w=T.W, h=T.H, spp=T.SPP, pixels_per_wave=64):
-    p = rt.RenderParams(w, h, spp, 50, 1984, 8, 0, 1, 0, 0, flags, None, 0, 0, 0, 0, pixels_per_wave, 0)
-    return scene.plan_launch(p)["kernel_kind"]
+    return scene.plan_launch(render_params(w, h, spp, flags=flags, pixels_per_wave=pixels_per_wave))["kernel_kind"]
 
 
 # ---- (1), (2): the premise, with the oracle alone ----

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import raytracinginoneweekendincuda_amd as rt
+from query_helpers import bits, centre_rays, dot3, sphere_roots
 from triangle_meshes import icosphere
 
 pytestmark = pytest.mark.gpu
@@ -19,15 +20,6 @@ W, H = 32, 24
 INF = float("inf")
 REFERENCE = rt.FLAG_REFERENCE_TREE | rt.FLAG_FORCE_GENERAL
 EDGE_BAND = 1e-9
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint64) if a.dtype == np.float64 else a
-
-
-def dot3(a, b):
-    return a[..., 0] * b[..., 0] + a[..., 1] * b[..., 1] + a[..., 2] * b[..., 2]
 
 
 # ---- rays ----
@@ -47,20 +39,10 @@ def pinhole_rays(origin, target, width=W, height=H, vfov=38.0, roll=0.0123):
     return np.ascontiguousarray(np.broadcast_to(origin, d.shape)), np.ascontiguousarray(d)
 
 
-def centre_rays(scene, width=W, height=H):
-    """The rays through the pixel centres of the scene's own camera, as the feature pass builds them (tests/test_ray_query_gpu.py)."""
-    cam = scene.dump_camera()
-    bg, origin, llc, hor, ver = (cam[3 * k:3 * k + 3] for k in range(5))
-    u = ((np.arange(width) + 0.5) / width)[None, :, None]
-    v = ((np.arange(height) + 0.5) / height)[:, None, None]
-    d = (((llc + u * hor) + v * ver) - origin).reshape(-1, 3)
-    return np.ascontiguousarray(np.broadcast_to(origin, d.shape)), np.ascontiguousarray(d), float(cam[25])
-
-
 def assert_no_centre_ray_on_an_edge(scene, width=W, height=H, what=""):
     """The reference side of a comparison of two search orders: no centre ray that hits a triangle has U, V or 1 - fl(U + V) within
     1e-9 of 0.  A triangle is a kind-4 world leaf, or lies inside a composite leaf (kind 3) and is not a medium's isotropic hit."""
-    o, d, time0 = centre_rays(scene, width, height)
+    o, d, time0, _ = centre_rays(scene, width, height)
     out = scene.intersect(o, d, time=time0, want=("t", "uv", "leaf", "material"))
     kinds = scene.dump_leaves()[0]
     hit = np.isfinite(out["t"])
@@ -393,7 +375,7 @@ def test_coplanar_triangles_of_two_leaves_keep_the_reference_trees_order(side):
     s.Camera((0.319, y, 3.117), (0.0, 0.0, 0.0), (0.0123, 1.0, 0.0), 40.0, W / H, 0.0, 1.0)
     s.Commit()
     assert s.dump_fast_nodes()[0].shape[0] == 0, "the guard finds the shared area"
-    o, d, time0 = centre_rays(s)
+    o, d, time0, _ = centre_rays(s, W, H)
     first = s.intersect(o, d, time=time0, want=("t", "leaf", "albedo"))
     both = int(np.sum(np.isfinite(first["t"]) & (first["albedo"][:, 1] == 0.1)))
     print(f"{side}: {both} centre rays end on one of the two triangles")
@@ -407,7 +389,7 @@ def test_coplanar_triangles_of_two_leaves_keep_the_reference_trees_order(side):
 @pytest.mark.parametrize("world", [0, 1], ids=["bvh", "list"])
 def test_scene_12_feature_pass_equals_the_closest_hit_query(world):
     scene = rt.builtin_scene(12, world, W, H)
-    o, d, time0 = centre_rays(scene)
+    o, d, time0, _ = centre_rays(scene, W, H)
     film = rt.Film(W, H)
     film.render_features(scene, samples=0, seed=1984, variant=0)
     albedo, normal, depth = (p.reshape(W * H, -1) for p in film.features())
@@ -506,14 +488,6 @@ def test_a_film_of_scene_12_is_the_square_root_of_the_radiance_of_its_camera_ray
 
 
 # ---- 6. an oracle that owes nothing to this code ----
-def sphere_near_root(o, d, centre, radius):
-    """R/Sphere.h:28-36 in numpy (tests/test_ray_query_gpu.py sphere_roots): the near root, NaN where the line misses."""
-    oc = o - np.asarray(centre, dtype=np.float64)
-    a, b, c = dot3(d, d), dot3(oc, d), dot3(oc, oc) - radius * radius
-    with np.errstate(invalid="ignore"):
-        return (-b - np.sqrt(b * b - a * c)) / a
-
-
 @pytest.mark.parametrize("variant", [0, 1], ids=["strict", "fast"])
 def test_an_icosphere_lies_between_its_inscribed_and_its_circumscribed_sphere(variant):
     radius, centre = 1.0, np.array([0.0713, -0.0319, -3.0117])
@@ -530,7 +504,7 @@ def test_an_icosphere_lies_between_its_inscribed_and_its_circumscribed_sphere(va
     s.Commit()
     o, d = pinhole_rays((0.0113, 0.0071, 0.0), (0.0, 0.0, -3.0), vfov=40.0)
     t_mesh = s.intersect(o, d, variant=variant, want=("t",))["t"]
-    t_out, t_in = sphere_near_root(o, d, centre, radius), sphere_near_root(o, d, centre, inner)
+    t_out, t_in = sphere_roots(o, d, centre, radius)[0], sphere_roots(o, d, centre, inner)[0]   # near roots, NaN for a miss
     mesh, outer, inside = np.isfinite(t_mesh), np.isfinite(t_out), np.isfinite(t_in)
     print(f"{inside.sum()} rays hit the inscribed sphere, {mesh.sum()} the mesh, {outer.sum()} the circumscribed sphere")
     assert inside.sum() > 150

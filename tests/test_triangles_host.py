@@ -8,6 +8,7 @@ import pytest
 
 import raytracinginoneweekendincuda_amd as rt
 from raytracinginoneweekendincuda_amd import _lib
+from frame_helpers import render_params
 from triangle_meshes import corners, icosphere, lattice
 
 RT_ERR_INVALID = 1
@@ -125,8 +126,7 @@ def test_a_world_of_triangles_plans_to_the_kernel_of_the_same_world_of_quads(wor
     plans = []
     for shape in ("triangle", "quad"):
         s = scene_with(_twenty_four(shape), world)
-        p = rt.RenderParams(400, 300, 16, 50, 1984, 8, 0, 1, 0, 0, flags, None, 0, 0, 0, 0, 0, 0)
-        plans.append(s.plan_launch(p, num_cus=256))
+        plans.append(s.plan_launch(render_params(400, 300, 16, flags=flags), num_cus=256))
     tri, quad = plans
     for key in ("kernel_kind", "kernel", "waves_per_simd", "reference_tree"):   # (the trees differ: a triangle's box is smaller)
         assert tri[key] == quad[key], key

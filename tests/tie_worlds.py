@@ -201,9 +201,3 @@ def separated_by_the_library_tree(scene, build):
 def differing(a, b):
     """Share of the pixels in which two frames differ in any bit."""
     return float(np.mean(np.any(a.view(np.uint64) != b.view(np.uint64), axis=-1)))
-
-
-def compare(got, want, tol=1e-5):
-    exact = float(np.mean(np.all(got.view(np.uint64) == want.view(np.uint64), axis=-1)))
-    within = float(np.mean(np.all(np.abs(got - want) <= tol, axis=-1)))
-    return exact, within
