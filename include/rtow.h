@@ -578,6 +578,79 @@ RTOW_API int rt_scene_radiance(rt_scene *s, const rt_radiance_params *params, co
 /* sizeof of rt_radiance_params, rt_radiance_rays, rt_radiance_out, rt_radiance_stats as this library was compiled */
 RTOW_API void rt_radiance_abi_sizes(uint32_t out4[4]);
 
+/* ---- path steps: one bounce of RayColor for caller-supplied rays ----
+ * What happens at the hit: Material::Scatter and Emitted for a caller that continues the path itself (its own termination rule,
+ * light sampling beside rt_scene_intersect's occlusion mode, per-bounce outputs).  Ray k is origin[3k..3k+2] + t *
+ * direction[3k..3k+2] at time time[k] (params->time where `time` is NULL), as in the radiance queries, and the step is one
+ * iteration of RayColor's loop (R/kernel.cu:74-94) exactly as a radiance query runs it: the world is searched over
+ * (0.001, DBL_MAX) -- the reference's own tree or list in the reference's order, every table from global memory, never the
+ * library's own tree -- then the hit record is made and the material emits and scatters.  The stream of ray k is
+ * rng_state[6k..6k+5] = {d, v0..v4} as rt_rng_state writes them, or, where rays->rng_state is NULL, curand_init(seed,
+ * k + first_sequence, 0) -- always seeded.  Media draw inside the search, materials after it, in the order of a render.
+ * Outputs, each only where its pointer is not NULL (not all may be NULL):
+ *   status       0 = miss; 1 = the path ends at this hit (a diffuse light; a metal whose scattered direction falls below the
+ *                surface); 2 = scattered
+ *   emitted      count x 3.  A miss: the camera's background.  A diffuse light: its texture's value.  Otherwise (0, 0, 0).
+ *   attenuation  count x 3.  Scatter's attenuation where status is 2; otherwise (0, 0, 0).
+ *   origin, direction, time   the scattered ray where status is 2; elsewhere the input ray, unchanged bit for bit
+ *   t            the ray parameter of the hit, +inf for a miss
+ *   normal, front_face, material   as in rt_query_hits
+ *   rng_state    count x 6: the ray's stream after the step's last draw
+ * The values are those of the radiance query's arithmetic: the step runs it from throughput (1, 1, 1) and accumulated (0, 0, 0),
+ * so emitted is 0 + 1 * x and attenuation is 1 * a -- x and a bit for bit, except that a negative zero comes out as a positive
+ * one, which no later sum can tell apart.  A caller that folds, one operation at a time and nothing fused,
+ *   acc = acc + thr * emitted   where status is 0 or 1        thr = thr * attenuation   where status is 2
+ * from acc (0, 0, 0), thr (1, 1, 1), over at most max_depth steps of the rays of status 2, has what rt_scene_radiance sums for one
+ * sample, bit for bit in the strict build (the fast build may fuse acc + thr * x, which the fold cannot restate).
+ * Every output may be the input array of the same meaning (origin, direction, time, rng_state): each ray is read, its six words
+ * included, before anything of it is written.
+ * Both calls return when the results are there (they wait on the stream) and read and write no film.  Parameters are checked
+ * before the device is touched: RT_ERR_STATE before commit; RT_ERR_INVALID for a count below 0 or above 2^30, a variant other
+ * than 0 / 1, a NULL origin or direction with count > 0, every output NULL.  count == 0 returns RT_OK without a launch.  A ray
+ * with a zero or non-finite direction terminates (one bounded search, straight-line shading; the rejection loops depend on the
+ * stream alone); its result is unspecified. */
+typedef struct rt_path_step_params {
+    int64_t  count;            /* rays; 0 is allowed (no launch), > 2^30 is RT_ERR_INVALID */
+    double   time;             /* used where rays->time is NULL */
+    uint64_t seed;             /* ray k: curand_init(seed, k + first_sequence, 0), unless rays->rng_state is given */
+    uint64_t first_sequence;
+    int32_t  variant;          /* 0 strict, 1 fast, as for renders */
+    int32_t  device;
+    void    *stream;           /* NULL = the default stream */
+    int32_t  reserved[4];
+} rt_path_step_params;
+typedef struct rt_path_step_rays {
+    const double   *origin, *direction;   /* count x 3 each */
+    const double   *time;                 /* count, or NULL */
+    const uint32_t *rng_state;            /* count x 6 {d, v0..v4} as rt_rng_state writes them, or NULL: seeded as above */
+} rt_path_step_rays;
+typedef struct rt_path_step_out {
+    uint8_t  *status;          /* count */
+    double   *emitted;         /* count x 3 */
+    double   *attenuation;     /* count x 3 */
+    double   *origin;          /* count x 3 */
+    double   *direction;       /* count x 3 */
+    double   *time;            /* count */
+    double   *t;               /* count */
+    double   *normal;          /* count x 3 */
+    uint8_t  *front_face;      /* count */
+    uint8_t  *material;        /* count */
+    uint32_t *rng_state;       /* count x 6; any pointer may be NULL, not all */
+} rt_path_step_out;
+typedef struct rt_path_step_stats {
+    uint64_t rays, scattered;               /* rays stepped; those of status 2 (counted whether or not status is asked for) */
+    double seconds;                         /* the step kernel, HIP events */
+    uint32_t kernel_vgprs, scratch_bytes;   /* of the instantiation that ran: registers, private memory per lane */
+} rt_path_step_stats;
+/* rays and out hold device pointers (on params->device).  stats may be NULL: the call is then the launch and the wait alone. */
+RTOW_API int rt_scene_path_step_device(rt_scene *s, const rt_path_step_params *params, const rt_path_step_rays *rays,
+                                       const rt_path_step_out *out, rt_path_step_stats *stats);
+/* the same on host arrays (uploaded, stepped, copied back) */
+RTOW_API int rt_scene_path_step(rt_scene *s, const rt_path_step_params *params, const rt_path_step_rays *rays, const rt_path_step_out *out,
+                                rt_path_step_stats *stats);
+/* sizeof of rt_path_step_params, rt_path_step_rays, rt_path_step_out, rt_path_step_stats as this library was compiled */
+RTOW_API void rt_path_step_abi_sizes(uint32_t out4[4]);
+
 /* Convenience: create film, upload, render 1 GPU, download.  frame = W*H*3 doubles. */
 RTOW_API int rt_render(rt_scene *s, const rt_render_params *params, double *frame, rt_render_stats *stats);
 

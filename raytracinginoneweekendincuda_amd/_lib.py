@@ -85,6 +85,30 @@ class RadianceStats(C.Structure):
     _fields_ = [("rays", C.c_uint64), ("seconds", C.c_double), ("kernel_vgprs", C.c_uint32), ("scratch_bytes", C.c_uint32)]
 
 
+class PathStepParams(C.Structure):
+    _fields_ = [("count", C.c_int64), ("time", C.c_double), ("seed", C.c_uint64), ("first_sequence", C.c_uint64), ("variant", C.c_int32),
+                ("device", C.c_int32), ("stream", C.c_void_p), ("reserved", C.c_int32 * 4)]
+
+
+class PathStepRays(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("origin", "direction", "time", "rng_state")]
+
+
+# the outputs of a path step in the order of rt_path_step_out: name -> (numpy dtype, trailing shape)
+STEP_OUTPUTS = {"status": ("uint8", ()), "emitted": ("float64", (3,)), "attenuation": ("float64", (3,)), "origin": ("float64", (3,)),
+                "direction": ("float64", (3,)), "time": ("float64", ()), "t": ("float64", ()), "normal": ("float64", (3,)),
+                "front_face": ("uint8", ()), "material": ("uint8", ()), "rng_state": ("uint32", (6,))}
+
+
+class PathStepOut(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in STEP_OUTPUTS]
+
+
+class PathStepStats(C.Structure):
+    _fields_ = [("rays", C.c_uint64), ("scattered", C.c_uint64), ("seconds", C.c_double), ("kernel_vgprs", C.c_uint32),
+                ("scratch_bytes", C.c_uint32)]
+
+
 class LaunchPlan(C.Structure):
     """rt_launch_plan: what a launch decides (csrc/launch_plan.h); every scalar field but ray_budget is an int32."""
     _fields_ = [(n, C.c_uint32 if n == "ray_budget" else C.c_int32) for n in (
@@ -199,6 +223,9 @@ SIGNATURES = {
     "rt_scene_radiance_device": (I, [P, C.POINTER(RadianceParams), C.POINTER(RadianceRays), C.POINTER(RadianceOut), C.POINTER(RadianceStats)]),
     "rt_scene_radiance": (I, [P, C.POINTER(RadianceParams), C.POINTER(RadianceRays), C.POINTER(RadianceOut), C.POINTER(RadianceStats)]),
     "rt_radiance_abi_sizes": (None, [C.POINTER(C.c_uint32)]),
+    "rt_scene_path_step_device": (I, [P, C.POINTER(PathStepParams), C.POINTER(PathStepRays), C.POINTER(PathStepOut), C.POINTER(PathStepStats)]),
+    "rt_scene_path_step": (I, [P, C.POINTER(PathStepParams), C.POINTER(PathStepRays), C.POINTER(PathStepOut), C.POINTER(PathStepStats)]),
+    "rt_path_step_abi_sizes": (None, [C.POINTER(C.c_uint32)]),
     "rt_deinterleave": (I, [D3, I, I, I, I, C.c_size_t, D3]),
     "rt_render": (I, [P, C.POINTER(RenderParams), D3, C.POINTER(RenderStats)]),
     "rt_write_ppm": (I, [C.c_char_p, D3, I, I]),
@@ -223,11 +250,14 @@ def load():
         fn = getattr(lib, name)  # AttributeError if the library does not export what rtow.h declares
         fn.restype = res
         fn.argtypes = args
-    # the radiance structures as this library was compiled against ours: a mismatch would scribble over the caller's arrays
-    sizes = (C.c_uint32 * 4)()
-    lib.rt_radiance_abi_sizes(sizes)
-    ours = [C.sizeof(x) for x in (RadianceParams, RadianceRays, RadianceOut, RadianceStats)]
-    if list(sizes) != ours:
-        raise ImportError(f"{LIB_PATH}: rt_radiance_* structures are {list(sizes)} bytes in the library, {ours} in the binding")
+    # the radiance and path-step structures as this library was compiled against ours: a mismatch would scribble over the
+    # caller's arrays
+    for what, sizes_of, structs in (("rt_radiance_*", lib.rt_radiance_abi_sizes, (RadianceParams, RadianceRays, RadianceOut, RadianceStats)),
+                                    ("rt_path_step_*", lib.rt_path_step_abi_sizes, (PathStepParams, PathStepRays, PathStepOut, PathStepStats))):
+        sizes = (C.c_uint32 * 4)()
+        sizes_of(sizes)
+        ours = [C.sizeof(x) for x in structs]
+        if list(sizes) != ours:
+            raise ImportError(f"{LIB_PATH}: {what} structures are {list(sizes)} bytes in the library, {ours} in the binding")
     _lib = lib
     return lib

@@ -13,7 +13,8 @@ import numpy as np
 
 from . import _lib
 from ._lib import (AdaptiveParams, DenoiseParams, FeatureParams, LaunchPlan, QueryHits, QueryParams, QueryRays, QueryStats,  # noqa: F401
-                   RadianceOut, RadianceParams, RadianceRays, RadianceStats, RenderParams, RenderStats, SceneInfo)
+                   PathStepOut, PathStepParams, PathStepRays, PathStepStats, RadianceOut, RadianceParams, RadianceRays, RadianceStats,
+                   RenderParams, RenderStats, SceneInfo)
 
 
 class RtowError(RuntimeError):
@@ -305,7 +306,7 @@ class Scene:
     def upload(self, device=0):
         _check(lib().rt_scene_upload(self._p, device))
 
-    # ---- caller-supplied rays: the engine under the ray queries and the radiance queries ----
+    # ---- caller-supplied rays: the engine under the ray queries, the radiance queries and the path steps ----
     def _ray_batch(self, kind, origins, directions, inputs, outputs, want, calls, structs, stats, device):
         """One batch of rays through a pair of library entry points, ``calls`` = (on host arrays, on device arrays): numpy arrays
         take the first, torch CUDA tensors the second, in place and on the current stream.  ``inputs``: the optional per-ray arrays as
@@ -421,6 +422,30 @@ class Scene:
         inputs = [("times", times, (), ("float64",), False), ("rng_state", rng_state, (6,), ("uint32", "int32"), False)]
         out, st = self._ray_batch("radiance", origins, directions, inputs, _lib.RADIANCE_OUTPUTS, tuple(want),
                                   (lib().rt_scene_radiance, lib().rt_scene_radiance_device), structs, RadianceStats if stats else None, device)
+        return (out, st) if stats else out
+
+    # ---- path steps (include/rtow.h rt_scene_path_step) ----
+    def path_step(self, origins, directions, times=None, rng_state=None, time=0.0, seed=1984, first_sequence=0, variant=0,
+                  want=("status", "emitted", "attenuation", "origin", "direction", "time", "rng_state"), device=0, stats=False):
+        """One bounce of the reference's ``RayColor`` for every ray ``origins[k] + t * directions[k]`` (both (count, 3) float64): the
+        world search, then what the material at the hit emits and how it scatters -- one iteration of the loop ``radiance`` runs,
+        for an integrator that continues the path itself (include/rtow.h rt_scene_path_step has the rules).  ``times`` and
+        ``rng_state`` as for ``radiance``.  Returns a dict of the outputs named in ``want``: "status" (count,) uint8, 0 miss, 1 the
+        path ends at this hit, 2 scattered; "emitted" and "attenuation" (count, 3) float64; "origin", "direction" (count, 3) and
+        "time" (count,), the scattered ray where status is 2 and the input ray elsewhere; "t", "normal", "front_face", "material" as
+        ``intersect`` gives them; "rng_state" (count, 6), the stream after the step's last draw.  Folding ``acc += thr * emitted``
+        where status is 0 or 1 and ``thr *= attenuation`` where it is 2, over the rays of status 2, is one sample of ``radiance``.
+        numpy arrays take the host call; torch CUDA tensors are read in place, on ``torch.cuda.current_stream()``.  Other dtypes,
+        shapes and non-contiguous inputs raise RtowError.  ``stats=True``: (outputs, PathStepStats)."""
+        def structs(count, rays, outs, device, stream):
+            if not outs:
+                raise RtowError("want: at least one of " + ", ".join(_lib.STEP_OUTPUTS))
+            p = PathStepParams(count, float(time), int(seed), int(first_sequence), int(variant), device, stream)
+            return p, PathStepRays(*(rays.get(n) for n in ("origins", "directions", "times", "rng_state"))), PathStepOut(**outs)
+
+        inputs = [("times", times, (), ("float64",), False), ("rng_state", rng_state, (6,), ("uint32", "int32"), False)]
+        out, st = self._ray_batch("path step", origins, directions, inputs, _lib.STEP_OUTPUTS, tuple(want),
+                                  (lib().rt_scene_path_step, lib().rt_scene_path_step_device), structs, PathStepStats if stats else None, device)
         return (out, st) if stats else out
 
     # ---- one-call render on one GPU ----

@@ -195,7 +195,7 @@ using namespace rtow;
 static inline SceneImpl *S(rt_scene *s) { return reinterpret_cast<SceneImpl *>(s); }
 static inline FilmImpl *F(rt_film *f) { return reinterpret_cast<FilmImpl *>(f); }
 
-// ---- lane-per-ray batches: what the ray queries and the radiance queries below share ----
+// ---- lane-per-ray batches: what the ray queries, the radiance queries and the path steps below share ----
 // everything both refuse alike without a device, in the order include/rtow.h lists it; `own` answers, between the count and the
 // variant, with the family's refusal of its own parameters (": what is wrong") or nullptr
 template <class Params, class Rays, class Own>
@@ -252,7 +252,7 @@ static int run_lane_kernel(Launch launch, unsigned long long **counter, int devi
     return RT_OK;
 }
 
-// The host arrays of one batch of `n` rays on the device (rt_scene_intersect, rt_scene_radiance); the copies are synchronous.
+// The host arrays of one batch of `n` rays on the device (rt_scene_intersect, rt_scene_radiance, rt_scene_path_step); the copies are synchronous.
 // `dev` comes in null: an input the caller left null, an output the caller does not want, stays so.
 struct Staging {
     struct Out { void *host; const void *dev; size_t bytes; };
@@ -474,12 +474,13 @@ struct Build {
     hipError_t (*features)(const DeviceScene &, const FeatureArgs &, hipStream_t);
     hipError_t (*query)(const DeviceScene &, const QueryArgs &, hipStream_t, QueryKernelInfo *);
     hipError_t (*radiance)(const DeviceScene &, const RadianceArgs &, hipStream_t, QueryKernelInfo *);
+    hipError_t (*step)(const DeviceScene &, const StepArgs &, hipStream_t, QueryKernelInfo *);
 };
 static const Build kBuilds[2] = {
     {launch_seed_strict, launch_render_strict, kernel_info_strict, launch_adaptive_rule_strict, launch_features_strict, launch_query_strict,
-     launch_radiance_strict},
+     launch_radiance_strict, launch_step_strict},
     {launch_seed_fast, launch_render_fast, kernel_info_fast, launch_adaptive_rule_fast, launch_features_fast, launch_query_fast,
-     launch_radiance_fast}};
+     launch_radiance_fast, launch_step_fast}};
 
 static int seed_film(FilmImpl &f, const rt_render_params *p, hipStream_t stream)
 {
@@ -1240,6 +1241,101 @@ void rt_radiance_abi_sizes(uint32_t out4[4])
     out4[1] = (uint32_t)sizeof(rt_radiance_rays);
     out4[2] = (uint32_t)sizeof(rt_radiance_out);
     out4[3] = (uint32_t)sizeof(rt_radiance_stats);
+}
+
+// ---- path steps ----
+// everything that can be refused without a device, in the order include/rtow.h lists it
+static int path_step_check(rt_scene *scene, const rt_path_step_params *p, const rt_path_step_rays *rays, const rt_path_step_out *out, const char *who)
+{
+    const std::string name(who);
+    const auto nothing = [] { return (const char *)nullptr; };  // no parameters of its own
+    if (int rc = batch_check(scene, p, rays, out, name, nothing)) return rc;
+    if (!out->status && !out->emitted && !out->attenuation && !out->origin && !out->direction && !out->time && !out->t && !out->normal &&
+        !out->front_face && !out->material && !out->rng_state)
+        return fail(RT_ERR_INVALID, name + ": every output is null");
+    return RT_OK;
+}
+
+int rt_scene_path_step_device(rt_scene *scene, const rt_path_step_params *p, const rt_path_step_rays *rays, const rt_path_step_out *out,
+                              rt_path_step_stats *stats)
+{
+    if (int rc = path_step_check(scene, p, rays, out, "rt_scene_path_step_device")) return rc;
+    if (stats) *stats = rt_path_step_stats{};
+    if (p->count == 0) return RT_OK;
+    SceneImpl &s = *S(scene);
+    if (int rc = rt_scene_upload(scene, p->device)) return rc;  // (selects the device)
+    DeviceTables &dt = *s.device[p->device];
+    StepArgs sa{};
+    sa.origin = rays->origin;
+    sa.direction = rays->direction;
+    sa.time = rays->time;
+    sa.time_all = p->time;
+    sa.rng_in = rays->rng_state;
+    sa.status = out->status;
+    sa.emitted = out->emitted;
+    sa.attenuation = out->attenuation;
+    sa.origin_out = out->origin;
+    sa.direction_out = out->direction;
+    sa.time_out = out->time;
+    sa.t = out->t;
+    sa.normal = out->normal;
+    sa.front_face = out->front_face;
+    sa.material = out->material;
+    sa.rng_out = out->rng_state;
+    if (int rc = device_jump_table(p->device, &sa.jump_table)) return rc;
+    sa.base = xorwow_seed(p->seed, kSaltCurandDevice);
+    sa.first_sequence = p->first_sequence;
+    sa.count = (uint32_t)p->count;
+    // (sa by reference: run_lane_kernel sets sa.scattered_counter between the launch that reports and the one that runs)
+    const auto launch = [&](hipStream_t stream, QueryKernelInfo *info) { return kBuilds[p->variant].step(dt.scene, sa, stream, info); };
+    unsigned long long scattered = 0;
+    if (int rc = run_lane_kernel(launch, &sa.scattered_counter, p->device, (hipStream_t)p->stream, "rt_scene_path_step_device", stats, &scattered))
+        return rc;
+    if (stats) {
+        stats->rays = (uint64_t)p->count;
+        stats->scattered = scattered;
+    }
+    return RT_OK;
+}
+
+int rt_scene_path_step(rt_scene *scene, const rt_path_step_params *p, const rt_path_step_rays *rays, const rt_path_step_out *out,
+                       rt_path_step_stats *stats)
+{
+    if (int rc = path_step_check(scene, p, rays, out, "rt_scene_path_step")) return rc;
+    if (stats) *stats = rt_path_step_stats{};
+    if (p->count == 0) return RT_OK;
+    if (int rc = select_device(p->device)) return rc;
+    Staging stage{DeviceArena(p->device), (size_t)p->count, {}};
+    rt_path_step_rays dr{};
+    HIP_TRY(stage.in(rays->origin, 3, dr.origin));
+    HIP_TRY(stage.in(rays->direction, 3, dr.direction));
+    HIP_TRY(stage.in(rays->time, 1, dr.time));
+    HIP_TRY(stage.in(rays->rng_state, 6, dr.rng_state));
+    rt_path_step_out dout{};
+    HIP_TRY(stage.out(out->status, 1, dout.status));
+    HIP_TRY(stage.out(out->emitted, 3, dout.emitted));
+    HIP_TRY(stage.out(out->attenuation, 3, dout.attenuation));
+    HIP_TRY(stage.out(out->origin, 3, dout.origin));
+    HIP_TRY(stage.out(out->direction, 3, dout.direction));
+    HIP_TRY(stage.out(out->time, 1, dout.time));
+    HIP_TRY(stage.out(out->t, 1, dout.t));
+    HIP_TRY(stage.out(out->normal, 3, dout.normal));
+    HIP_TRY(stage.out(out->front_face, 1, dout.front_face));
+    HIP_TRY(stage.out(out->material, 1, dout.material));
+    HIP_TRY(stage.out(out->rng_state, 6, dout.rng_state));
+    rt_path_step_params dp = *p;
+    dp.stream = nullptr;  // the copies around the step are synchronous: nothing to order on the caller's stream
+    if (int rc = rt_scene_path_step_device(scene, &dp, &dr, &dout, stats)) return rc;
+    HIP_TRY(stage.fetch());
+    return RT_OK;
+}
+
+void rt_path_step_abi_sizes(uint32_t out4[4])
+{
+    out4[0] = (uint32_t)sizeof(rt_path_step_params);
+    out4[1] = (uint32_t)sizeof(rt_path_step_rays);
+    out4[2] = (uint32_t)sizeof(rt_path_step_out);
+    out4[3] = (uint32_t)sizeof(rt_path_step_stats);
 }
 
 int rt_render(rt_scene *scene, const rt_render_params *params, double *frame, rt_render_stats *stats)

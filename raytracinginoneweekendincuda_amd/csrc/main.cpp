@@ -219,6 +219,7 @@ int main(int argc, char **argv)
     bool pick = false;           // --pick i,j: what the centre ray of that pixel hits, one line, no render
     int pick_i = 0, pick_j = 0;
     bool radiance_at = false;    // --radiance-at i,j: the light that comes back along the centre ray of that pixel, one line, no render
+    bool trace_at = false;       // --trace-at i,j: that path vertex by vertex (rt_scene_path_step), then --radiance-at's line
     for (int k = 1; k < argc; k++) {
         std::string a = argv[k];
         auto val = [&](const char *name) -> const char * {
@@ -285,6 +286,12 @@ int main(int argc, char **argv)
                 return 2;
             }
             pick = radiance_at = true;
+        } else if (const char *v = val("--trace-at")) {
+            if (std::sscanf(v, "%d,%d", &pick_i, &pick_j) != 2) {
+                std::fprintf(stderr, "--trace-at needs a pixel i,j, not '%s'\n", v);
+                return 2;
+            }
+            pick = radiance_at = trace_at = true;
         }
         else if (const char *v = val("--earth")) earth_path = v;
         else if (const char *v = val("--earth-bytes")) {
@@ -297,11 +304,14 @@ int main(int argc, char **argv)
                          "            [--earth earthmap.jpg|decoded.ppm | --earth-bytes texture.ppm] [--accelerate-lists] [--flags N]\n"
                          "            [--noise T [--min-spp N] [--check-every K] [--samples-map file.pgm]]\n"
                          "            [--denoise [--denoise-iterations N] [--denoise-sigmas c,a,n,z] [--raw-output file.ppm]]\n"
-                         "            [--aov-prefix P] [--feature-samples N] [--pick i,j] [--radiance-at i,j]\n"
+                         "            [--aov-prefix P] [--feature-samples N] [--pick i,j] [--radiance-at i,j] [--trace-at i,j]\n"
                          "  --pick         render nothing: print what the ray through the centre of pixel (i, j) hits (j = 0 is the bottom row) --\n"
                          "                 leaf, material kind, t, point, normal, albedo -- at the shutter's opening, over [0.001, inf)\n"
                          "  --radiance-at  render nothing: path-trace the same ray, --spp samples (default 1) of --depth bounces from the pixel's stream,\n"
                          "                 and print the linear radiance, the rays traced and the kernel's time\n"
+                         "  --trace-at     render nothing: the same paths one bounce at a time (rt_scene_path_step), a line per vertex -- sample, depth,\n"
+                         "                 status (0 miss, 1 the path ends, 2 scattered), t, material, emitted, attenuation -- folded here, on the host;\n"
+                         "                 the last line is --radiance-at's (to the last bit with --variant strict; its time is the steps' kernels')\n"
                          "  --denoise      --output gets the frame after the edge-avoiding a-trous filter (1..8 levels, default 5; sigmas of the colour,\n"
                          "                 albedo, normal and depth edge stops, inf = off), guided by the first hits' albedo, normal and depth;\n"
                          "                 --raw-output: the unfiltered frame beside it\n"
@@ -350,10 +360,14 @@ int main(int argc, char **argv)
         return 2;
     }
     if (radiance_at && spp < 0) spp = 1;
+    if (trace_at && (spp < 1 || depth < 0)) {  // (what rt_scene_radiance refuses for --radiance-at)
+        std::fprintf(stderr, "--trace-at needs --spp >= 1 and --depth >= 0\n");
+        return 2;
+    }
     if (spp < 0) spp = (scene_id == 9) ? 100 : (((scene_id >= 5 && scene_id <= 8) || scene_id == 12) ? 200 : 10);  // R/kernel.cu:593 (12: lit like 7)
 
     if (pick && (pick_i < 0 || pick_i >= width || pick_j < 0 || pick_j >= height)) {
-        std::fprintf(stderr, "%s: pixel (%d, %d) is outside the %dx%d frame\n", radiance_at ? "--radiance-at" : "--pick", pick_i, pick_j, width, height);
+        std::fprintf(stderr, "%s: pixel (%d, %d) is outside the %dx%d frame\n", trace_at ? "--trace-at" : radiance_at ? "--radiance-at" : "--pick", pick_i, pick_j, width, height);
         return 2;
     }
     if (!pick) std::fprintf(stderr, "Rendering a %dx%d image with %d samples per pixel in 8x8 blocks.\n", width, height, spp);
@@ -409,6 +423,53 @@ int main(int argc, char **argv)
         for (int a = 0; a < 3; a++) {
             o[a] = cam[3 + a];
             d[a] = ((cam[6 + a] + u * cam[9 + a]) + v * cam[12 + a]) - o[a];
+        }
+        if (trace_at) {  // the radiance query below as a caller's own integrator: one path step a vertex, the fold of include/rtow.h
+#pragma clang fp contract(off)
+            static const char *const kinds[] = {"lambertian", "metal", "dielectric", "diffuse_light", "isotropic"};
+            rt_path_step_params sp{};
+            sp.count = 1;
+            sp.time = cam[25];
+            sp.seed = seed;
+            sp.first_sequence = (unsigned long long)pick_j * (unsigned long long)width + (unsigned long long)pick_i;
+            sp.variant = variant;
+            sp.device = device;
+            uint32_t state[6];
+            bool seeded = false;  // the first step seeds the pixel's stream in the library; every later one continues it
+            double sum[3] = {0.0, 0.0, 0.0}, seconds = 0.0;
+            unsigned rays_traced = 0;
+            for (int sample = 0; sample < spp && depth > 0; sample++) {
+                double ro[3] = {o[0], o[1], o[2]}, rd[3] = {d[0], d[1], d[2]}, tm = cam[25];
+                double thr[3] = {1.0, 1.0, 1.0}, acc[3] = {0.0, 0.0, 0.0};
+                for (int bounce = 0; bounce < depth; bounce++) {
+                    const rt_path_step_rays sr{ro, rd, &tm, seeded ? state : nullptr};
+                    uint8_t status = 0, kind = 255;
+                    double emitted[3], atten[3], t = 0.0;
+                    const rt_path_step_out so{&status, emitted, atten, ro, rd, &tm, &t, nullptr, nullptr, &kind, state};
+                    rt_path_step_stats ss{};
+                    if (rt_scene_path_step(scene, &sp, &sr, &so, &ss) != RT_OK) return die("trace-at");
+                    seeded = true;
+                    seconds += ss.seconds;
+                    rays_traced++;
+                    std::printf("vertex: sample %d depth %d status %u t %.17g material %s emitted %.17g %.17g %.17g attenuation %.17g %.17g %.17g\n", sample,
+                                bounce, (unsigned)status, t, kind < 5 ? kinds[kind] : "none", emitted[0], emitted[1], emitted[2], atten[0], atten[1],
+                                atten[2]);
+                    if (status != 2) {
+                        for (int a = 0; a < 3; a++) {
+                            const double product = thr[a] * emitted[a];
+                            acc[a] = acc[a] + product;
+                        }
+                        break;
+                    }
+                    for (int a = 0; a < 3; a++) thr[a] = thr[a] * atten[a];
+                }
+                for (int a = 0; a < 3; a++) sum[a] = sum[a] + acc[a];
+            }
+            const double inv = 1 / (double)spp;
+            std::printf("radiance %d,%d: samples %d radiance %.17g %.17g %.17g rays %u seconds %.9g\n", pick_i, pick_j, spp, inv * sum[0], inv * sum[1],
+                        inv * sum[2], rays_traced, seconds);
+            rt_scene_destroy(scene);
+            return 0;
         }
         if (radiance_at) {  // one radiance query (rt_scene_radiance) for the same ray, from the pixel's stream
             rt_radiance_params rp{};

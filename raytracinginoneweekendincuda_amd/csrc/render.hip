@@ -53,6 +53,9 @@
 #ifndef RT_RADIANCE  // 1: this translation unit holds the radiance-query kernels (radiance_kernel) and nothing else
 #define RT_RADIANCE 0
 #endif
+#ifndef RT_STEP  // 1: this translation unit holds the path-step kernels (step_kernel) and nothing else
+#define RT_STEP 0
+#endif
 
 namespace rtow {
 namespace {
@@ -300,7 +303,7 @@ DEV bool sphere_test(Vec oc, Vec d, double a, double r2, double tmin, double tma
 // times with the branch (the select costs the media kernel of scene 8 3 %), the lane-per-ray kernels of the feature pass and the
 // queries keep their registers with the select (the branch takes the radiance kernel of list worlds from 168 to 170 VGPRs, from
 // three waves per SIMD to two, 35 % on scene 7).  A third form, a switch case of its own in quad_test_at, cost most kernels spills.
-#define RT_PLANAR_SELECT (RT_FEATURES || RT_QUERY || RT_RADIANCE)
+#define RT_PLANAR_SELECT (RT_FEATURES || RT_QUERY || RT_RADIANCE || RT_STEP)
 DEV bool quad_test(const QuadGeom &q, bool tri, const Ray &r, double tmin, double tmax, double &t_out)
 {
     Vec n = mk(q.nx, q.ny, q.nz);
@@ -455,7 +458,7 @@ DEV bool prim_test(const DeviceScene &sc, uint32_t ref, const Ray &r, double a, 
 #ifndef RT_PHASES
 #define RT_PHASES 0  // diagnostic build: per-phase wave cycles and lane occupancy, summed into ray_counter[7] and [32..119]
 #endif
-#if RT_PHASES && (RT_FEATURES || RT_QUERY || RT_RADIANCE)
+#if RT_PHASES && (RT_FEATURES || RT_QUERY || RT_RADIANCE || RT_STEP)
 #undef RT_PHASES
 #define RT_PHASES 0  // the phases are render_kernel's: the feature and query units of a diagnostic build are the ordinary ones
 #endif
@@ -4239,9 +4242,9 @@ hipError_t RT_CAT(launch_composite_, RT_SUFFIX)(int which, const DeviceScene &sc
 hipError_t RT_CAT(launch_adaptive_prims_, RT_SUFFIX)(int which, const DeviceScene &sc, const RenderArgs &a, hipStream_t stream, KernelInfo *info);
 hipError_t RT_CAT(launch_adaptive_composite_, RT_SUFFIX)(int which, const DeviceScene &sc, const RenderArgs &a, hipStream_t stream, KernelInfo *info);
 
-#if RT_FEATURES || RT_QUERY || RT_RADIANCE
+#if RT_FEATURES || RT_QUERY || RT_RADIANCE || RT_STEP
 // ------------------------------------------------------------------------------------------------
-// Shared by the three lane-per-ray sections below (first-hit features, ray queries, radiance queries): one lane per pixel or per
+// Shared by the four lane-per-ray sections below (first-hit features, ray queries, radiance queries, path steps): one lane per pixel or per
 // caller-supplied ray, no persistent waves, no LDS staging.  The next kernel of this family starts from these.
 // ------------------------------------------------------------------------------------------------
 namespace {
@@ -4676,6 +4679,95 @@ hipError_t RT_CAT(launch_radiance_, RT_SUFFIX)(const DeviceScene &sc, const Radi
     if (a.samples < 1 || a.max_depth < 0 || !a.origin || !a.direction || !(a.radiance || a.path_rays || a.rng_out)) return hipErrorInvalidValue;
     void (*kernel)(DeviceScene, RadianceArgs) =
         sc.world_kind == WORLD_BVH ? radiance_kernel<RT_STRICT, TBvhNested> : radiance_kernel<RT_STRICT, TListNested>;
+    return info_or_launch(kernel, sc, a, a.count, stream, info);
+}
+#elif RT_STEP
+// ------------------------------------------------------------------------------------------------
+// Path steps (rt_scene_path_step): one iteration of RayColor's loop (R/kernel.cu:74-94) for caller-supplied rays, so that an
+// integrator outside the library can continue the path itself.  radiance_kernel's iteration -- its search loop, its miss branch and
+// its make_surface / shade call, line for line -- run once, from throughput (1, 1, 1) and accumulated (0, 0, 0): what shade leaves
+// in `accumulated` is then 0 + 1 * x, the emitted or background value x itself, and what it leaves in `throughput` is 1 * a, the
+// attenuation a itself (a negative zero comes out positive), in the strict build and in the fast one (fma(1, x, 0) is x).  A host
+// that folds acc = acc + thr * emitted, thr = thr * attenuation over the steps repeats radiance_kernel's arithmetic in the strict
+// build.  The hit record's outputs are query_kernel's.  Termination for any ray: one bounded search (the argument above
+// query_hit_list) and straight-line shading; the rejection loops of shade depend on the stream alone.
+// ------------------------------------------------------------------------------------------------
+template <int STRICT, class T>
+__global__ __launch_bounds__(256) void step_kernel(DeviceScene sc, StepArgs a)
+{
+    global_tables_only(sc);
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= a.count) return;
+    // the ray and the six words are read here, before anything is written: every output may be the input array of the same meaning
+    Ray ray = caller_ray(a.origin, a.direction, a.time, a.time_all, k);
+    Xorwow rng;
+    if (a.rng_in) {  // {d, v0..v4} as rt_rng_state writes them
+        const uint32_t *w = a.rng_in + (size_t)k * 6;
+        rng.d = w[0]; rng.v0 = w[1]; rng.v1 = w[2]; rng.v2 = w[3]; rng.v3 = w[4]; rng.v4 = w[5];
+    } else {  // curand_init(seed, k + first_sequence, 0)
+        rng = a.base;
+        xorwow_skip_sequences(a.jump_table, a.first_sequence + (uint64_t)k, rng);
+    }
+    const NodeView nv{sc.nodes, 0u, false};
+    Vec throughput = mk(1.0, 1.0, 1.0), accumulated = mk(0.0, 0.0, 0.0);
+    HitInfo h;
+    h.t = 0.0;
+    h.ref = kNone;
+    h.obj = kNone;
+    bool hit = false;
+    if constexpr (T::WORLD == 0) {
+        if (sc.n_world_nodes != 0) {
+            Walk w{};
+            walk_begin<false>(w, ray, DBL_MAX);
+            while (w.state != kNone) {
+                if (walk_moving(w.state)) walk_node<false>(nv, ray, 0.001, w);
+                else walk_leaves<T>(sc, nv, ray, 0.001, w, h, rng);
+            }
+            hit = w.any;
+        }
+    } else {
+        hit = world_hit_list<T>(sc, ray, 0.001, DBL_MAX, h, rng);
+    }
+    Vec normal = mk(0.0, 0.0, 0.0);
+    uint32_t kind = 255u;
+    bool front = false, scattered = false;
+    if (!hit) {  // R/kernel.cu:74-79
+        accumulated = accumulated + throughput * load3c(((const RT_CONST CameraRec *)(uintptr_t)sc.camera)->bg);
+    } else {
+        const Surface s = make_surface<T>(sc, ray, h);
+        if (a.normal && (h.ref >> kRefShift) != REF_MEDIUM) normal = s.n;
+        front = s.front;
+        if (a.material) kind = material_view<false>(sc, s.mat).u32(MAT_OFF(kind));
+        scattered = shade<T>(sc, s, ray, throughput, accumulated, rng);  // scattered: `ray` is the next ray; else it is untouched
+    }
+    if (a.scattered_counter) {
+        const unsigned long long found = __ballot(scattered);  // one atomic per wave (per group of lanes that arrive together)
+        if (scattered && (uint32_t)__ffsll((long long)found) - 1u == (threadIdx.x & 63u))
+            atomicAdd(a.scattered_counter, (unsigned long long)__popcll(found));
+    }
+    if (a.status) a.status[k] = !hit ? 0 : scattered ? 2 : 1;
+    if (a.emitted) store3(a.emitted, k, accumulated);
+    // (a metal whose direction falls below the surface ends the path before shade multiplies: throughput is still (1, 1, 1))
+    if (a.attenuation) store3(a.attenuation, k, scattered ? throughput : mk(0.0, 0.0, 0.0));
+    if (a.origin_out) store3(a.origin_out, k, ray.o);
+    if (a.direction_out) store3(a.direction_out, k, ray.d);
+    if (a.time_out) a.time_out[k] = ray.tm;
+    if (a.t) a.t[k] = hit ? h.t : (double)INFINITY;
+    if (a.normal) store3(a.normal, k, mk(0.0, 0.0, 0.0) + normal);  // as query_kernel: no negative zeros
+    if (a.front_face) a.front_face[k] = front ? 1 : 0;
+    if (a.material) a.material[k] = (uint8_t)kind;
+    if (a.rng_out) {  // may be the array the state came from: this lane has read its six words
+        uint32_t *w = a.rng_out + (size_t)k * 6;
+        w[0] = rng.d; w[1] = rng.v0; w[2] = rng.v1; w[3] = rng.v2; w[4] = rng.v3; w[5] = rng.v4;
+    }
+}
+
+hipError_t RT_CAT(launch_step_, RT_SUFFIX)(const DeviceScene &sc, const StepArgs &a, hipStream_t stream, QueryKernelInfo *info)
+{
+    const bool any = a.status || a.emitted || a.attenuation || a.origin_out || a.direction_out || a.time_out || a.t || a.normal || a.front_face ||
+                     a.material || a.rng_out;
+    if (!a.origin || !a.direction || !any) return hipErrorInvalidValue;
+    void (*kernel)(DeviceScene, StepArgs) = sc.world_kind == WORLD_BVH ? step_kernel<RT_STRICT, TBvhNested> : step_kernel<RT_STRICT, TListNested>;
     return info_or_launch(kernel, sc, a, a.count, stream, info);
 }
 #elif RT_GROUP == 1

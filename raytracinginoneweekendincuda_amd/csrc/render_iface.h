@@ -183,6 +183,31 @@ struct RadianceArgs {
 hipError_t launch_radiance_strict(const DeviceScene &sc, const RadianceArgs &a, hipStream_t stream, QueryKernelInfo *info = nullptr);
 hipError_t launch_radiance_fast(const DeviceScene &sc, const RadianceArgs &a, hipStream_t stream, QueryKernelInfo *info = nullptr);
 
+// Path steps (rt_scene_path_step; the RT_STEP objects of render.hip): one lane per caller-supplied ray, one iteration of the radiance
+// kernel's loop -- one search, make_surface, shade -- and what a caller needs to continue the path: rt_path_step_out's arrays.
+// Every output may be nullptr (not all), and may be the input array of the same meaning: a lane reads before it writes.
+struct StepArgs {
+    const double *origin, *direction;   // count x 3 each
+    const double *time;                 // count, or nullptr: time_all
+    double time_all;
+    const uint32_t *rng_in;             // count x 6, or nullptr: seeded from base
+    uint8_t *status;                    // count: 0 miss, 1 the path ends at this hit, 2 scattered
+    double *emitted, *attenuation;      // count x 3 each
+    double *origin_out, *direction_out; // count x 3 each: the scattered ray, or the input ray where status != 2
+    double *time_out;                   // count
+    double *t, *normal;                 // count, count x 3: as QueryArgs
+    uint8_t *front_face, *material;     // count each: as QueryArgs
+    uint32_t *rng_out;                  // count x 6: the stream after the step's last draw
+    unsigned long long *scattered_counter;  // one word, zeroed by the caller: rays of status 2; nullptr: not counted
+    const uint32_t *jump_table;         // kJumpTableWords
+    Xorwow base;                        // salted seed state (sequence 0)
+    uint64_t first_sequence;
+    uint32_t count;
+};
+// info != nullptr: report the instantiation that would run instead of launching it
+hipError_t launch_step_strict(const DeviceScene &sc, const StepArgs &a, hipStream_t stream, QueryKernelInfo *info = nullptr);
+hipError_t launch_step_fast(const DeviceScene &sc, const StepArgs &a, hipStream_t stream, QueryKernelInfo *info = nullptr);
+
 // One level of the edge-avoiding a-trous filter (denoise.hip; include/rtow.h rt_denoise_params has the stencil): full-frame
 // planes, `in` and `out` distinct.  A guide that is nullptr switches its term off; inv_* = 1 / sigma^2 (0 for sigma = +inf), the
 // colour's already scaled for the level.
