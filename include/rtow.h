@@ -651,6 +651,97 @@ RTOW_API int rt_scene_path_step(rt_scene *s, const rt_path_step_params *params, 
 /* sizeof of rt_path_step_params, rt_path_step_rays, rt_path_step_out, rt_path_step_stats as this library was compiled */
 RTOW_API void rt_path_step_abi_sizes(uint32_t out4[4]);
 
+/* ---- path advances: step a batch of paths by one bounce, fold what ended, keep the live rays packed, on the device ----
+ * What a caller's loop around rt_scene_path_step does between two steps, done by the library: one call steps the live rays, adds
+ * the light of the paths that ended to a radiance array, writes the scattered rays packed, in their input order, into a second
+ * set of arrays and leaves their number in device memory, so that the next call can be enqueued without the host learning it.
+ * Let n = min(*rays->count, params->count), or params->count where rays->count is NULL.  Rows at and beyond n are never read.  A
+ * word larger than the capacity params->count is clamped: it is no error, and nothing beyond params->count rows is read or
+ * written.  Operation by operation, for each k < n with alive[k] != 0 (every k < n where `alive` is NULL):
+ *   ray k is stepped exactly as rt_scene_path_step steps it: the same search, hit record, shading and stream rules, the stream
+ *   rng_state[6k..6k+5] or, where that is NULL, curand_init(seed, k + first_sequence, 0).
+ *   id = ray_id[k] (k where ray_id is NULL), thr = throughput[3k..3k+2] ((1, 1, 1) where throughput is NULL).
+ *   status 0 or 1 (the path ends): where out->radiance is given and 0 <= id < sources,
+ *       radiance[id] = radiance[id] + thr * emitted
+ *     the product rounded, then the sum -- one operation at a time in the strict build, the fold stated above for the path steps;
+ *     the fast build may fuse the two (0 + thr * e is exact either way).  An id outside the range adds nothing.  THE IDS OF LIVE
+ *     RAYS MUST BE DISTINCT: each ended ray is one plain load, add and store, no atomics.
+ *   status 2 (scattered): the ray is survivor j, where j counts the survivors before it in input order -- the compaction is
+ *     stable.  Row j of each output given holds the scattered ray (origin, direction), its time, the stream after the step
+ *     (rng_state), thr * attenuation (throughput; one multiply in either build), the id (ray_id), and t, normal, front_face,
+ *     material of the hit it scattered from, as rt_query_hits.
+ * A ray with alive[k] == 0 is dropped untraced: nothing is added for it and it is no survivor.  *out->count = the number of
+ * survivors.  Output rows from the survivors' count up to params->count are unspecified.  Inputs are only read.
+ * Folding sources = count fresh rays over max_depth calls -- a zeroed radiance array, the two array sets swapped each time, whoever
+ * is still alive after the last call dropped -- is rt_scene_radiance with samples = 1, bit for bit in the strict build.
+ * Aliasing: an output array may NOT be the input array of the same meaning (origin, direction, time, rng_state, throughput,
+ * ray_id; RT_ERR_INVALID, decided by pointer equality): a compaction across workgroups cannot be done in place.  out->count may
+ * be the word rays->count points to: it is read by the first kernel of the call and written by the last.
+ * Waiting: with stats == NULL, rt_scene_path_advance_device ENQUEUES ON params->stream AND RETURNS WITHOUT WAITING -- the point of
+ * the call, and the one difference from its siblings above.  With stats it waits and fills them.  rt_scene_destroy, a re-commit
+ * followed by an upload, and whatever else frees the scene's device tables first wait for the last advance enqueued on that
+ * scene.  As everywhere, one call at a time per scene; advances that share a workspace must be on one stream or ordered by the
+ * caller, and the caller's arrays must stay allocated until the stream has run the call.
+ * The host-array form rt_scene_path_advance uploads, runs, waits and copies back the count word and the first *out->count rows of
+ * each output; `workspace` is ignored, rays->count and out->count are host words, radiance (sources x 3) is copied both ways.
+ * Refusals, all before the device is touched, in this order: RT_ERR_STATE before commit; RT_ERR_INVALID for count or sources
+ * outside 0 .. 2^30, a variant other than 0 / 1, a NULL origin or direction input with count > 0, a NULL out->origin,
+ * out->direction or out->count, out->radiance given with sources == 0, an aliased pair, and in the device call a workspace that
+ * is NULL or smaller than rt_path_advance_workspace_bytes(count) (a count of 0 needs none).  count == 0 is RT_OK with nothing
+ * launched and nothing written; the other parameters are still checked.  A zero or non-finite direction terminates with an
+ * unspecified result, as in the path steps. */
+typedef struct rt_path_advance_params {
+    int64_t  count;            /* capacity: rows readable in every input and writable in every output; 0 .. 2^30 */
+    int64_t  sources;          /* rows of out->radiance; 0 .. 2^30 */
+    double   time;             /* used where rays->time is NULL */
+    uint64_t seed;             /* ray k: curand_init(seed, k + first_sequence, 0), unless rays->rng_state is given */
+    uint64_t first_sequence;
+    int32_t  variant;          /* 0 strict, 1 fast */
+    int32_t  device;
+    void    *stream;           /* NULL = the default stream */
+    void    *workspace;        /* device call only: device memory, >= rt_path_advance_workspace_bytes(count); its layout is private */
+    uint64_t workspace_bytes;
+    int32_t  reserved[4];
+} rt_path_advance_params;
+typedef struct rt_path_advance_rays {
+    const double   *origin, *direction;   /* count x 3 each */
+    const double   *time;                 /* count, or NULL */
+    const uint32_t *rng_state;            /* count x 6, or NULL: seeded */
+    const double   *throughput;           /* count x 3, or NULL: (1, 1, 1) */
+    const int32_t  *ray_id;               /* count, or NULL: k */
+    const uint8_t  *alive;                /* count, or NULL: all; a ray with alive[k] == 0 is dropped untraced */
+    const uint32_t *count;                /* one word, or NULL: params->count.  Rays stepped = min(*count, params->count) */
+} rt_path_advance_rays;
+typedef struct rt_path_advance_out {
+    double   *radiance;        /* sources x 3, read-modify-write; or NULL: nothing is folded */
+    double   *origin;          /* count x 3; required */
+    double   *direction;       /* count x 3; required */
+    double   *time;            /* count; this and the following are optional */
+    uint32_t *rng_state;       /* count x 6 */
+    double   *throughput;      /* count x 3 */
+    int32_t  *ray_id;          /* count */
+    double   *t;               /* count: the hit the survivor scattered from, as rt_query_hits */
+    double   *normal;          /* count x 3 */
+    uint8_t  *front_face;      /* count */
+    uint8_t  *material;        /* count */
+    uint32_t *count;           /* one word: the survivors; required */
+} rt_path_advance_out;
+typedef struct rt_path_advance_stats {
+    uint64_t rays, scattered;               /* rays stepped (below n and alive); the survivors */
+    double seconds;                         /* the call's three kernels, HIP events */
+    uint32_t kernel_vgprs, scratch_bytes;   /* of the step kernel that ran: registers, private memory per lane */
+} rt_path_advance_stats;
+/* rays and out hold device pointers (on params->device), the two count words included.  stats == NULL: enqueue and return. */
+RTOW_API int rt_scene_path_advance_device(rt_scene *s, const rt_path_advance_params *params, const rt_path_advance_rays *rays,
+                                          const rt_path_advance_out *out, rt_path_advance_stats *stats);
+/* the same on host arrays (uploaded, advanced, waited for, copied back) */
+RTOW_API int rt_scene_path_advance(rt_scene *s, const rt_path_advance_params *params, const rt_path_advance_rays *rays,
+                                   const rt_path_advance_out *out, rt_path_advance_stats *stats);
+/* bytes of workspace a device call of capacity `count` needs: 0 for 0, non-decreasing in count */
+RTOW_API uint64_t rt_path_advance_workspace_bytes(int64_t count);
+/* sizeof of rt_path_advance_params, rt_path_advance_rays, rt_path_advance_out, rt_path_advance_stats as this library was compiled */
+RTOW_API void rt_path_advance_abi_sizes(uint32_t out4[4]);
+
 /* Convenience: create film, upload, render 1 GPU, download.  frame = W*H*3 doubles. */
 RTOW_API int rt_render(rt_scene *s, const rt_render_params *params, double *frame, rt_render_stats *stats);
 

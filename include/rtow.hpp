@@ -195,6 +195,14 @@ public:
         return p;
     }
 
+    // One bounce for a batch of paths, the ended ones folded and the live rays kept packed (rtow.h "path advances"): the structs
+    // pass through as they are.  Device pointers and no statistics: the call is enqueued on params.stream and returns.
+    void PathAdvance(const rt_path_advance_params &params, const rt_path_advance_rays &rays, const rt_path_advance_out &out,
+                     rt_path_advance_stats *stats = nullptr, bool device_pointers = true)
+    {
+        check(device_pointers ? rt_scene_path_advance_device(s_, &params, &rays, &out, stats) : rt_scene_path_advance(s_, &params, &rays, &out, stats));
+    }
+
 private:
     rt_handle ok(rt_handle h)
     {

@@ -9,6 +9,7 @@ from .api import (  # noqa: F401
     Rng,
     Scene,
     Film,
+    PathBatch,
     RenderParams,
     RenderStats,
     LaunchPlan,
@@ -38,7 +39,7 @@ from .api import (  # noqa: F401
 )
 
 __all__ = [
-    "RtowError", "Rng", "Scene", "Film", "RenderParams", "RenderStats", "builtin_scene",
+    "RtowError", "Rng", "Scene", "Film", "PathBatch", "RenderParams", "RenderStats", "builtin_scene",
     "stripe_rows", "deinterleave", "write_ppm", "write_ppm_binary", "write_pfm", "rtwimage_bytes", "load_image", "load_obj", "library_path", "lib",
     "FLAG_KEEP_RNG_STATE", "FLAG_FORCE_GENERAL", "FLAG_OVERDUE_PRIORITY", "FLAG_ACCUMULATE", "FLAG_ROW_MAJOR_TILES", "FLAG_ALWAYS_WALK",
     "AdaptiveParams", "adaptive_converged", "adaptive_rule_on_device",

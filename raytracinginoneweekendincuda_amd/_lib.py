@@ -109,6 +109,32 @@ class PathStepStats(C.Structure):
                 ("scratch_bytes", C.c_uint32)]
 
 
+class PathAdvanceParams(C.Structure):
+    _fields_ = [("count", C.c_int64), ("sources", C.c_int64), ("time", C.c_double), ("seed", C.c_uint64), ("first_sequence", C.c_uint64),
+                ("variant", C.c_int32), ("device", C.c_int32), ("stream", C.c_void_p), ("workspace", C.c_void_p),
+                ("workspace_bytes", C.c_uint64), ("reserved", C.c_int32 * 4)]
+
+
+class PathAdvanceRays(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("origin", "direction", "time", "rng_state", "throughput", "ray_id", "alive", "count")]
+
+
+# the per-survivor outputs of a path advance in the order of rt_path_advance_out (without `radiance` in front of them and `count`
+# behind): name -> (numpy dtype, trailing shape)
+ADVANCE_OUTPUTS = {"origin": ("float64", (3,)), "direction": ("float64", (3,)), "time": ("float64", ()), "rng_state": ("uint32", (6,)),
+                   "throughput": ("float64", (3,)), "ray_id": ("int32", ()), "t": ("float64", ()), "normal": ("float64", (3,)),
+                   "front_face": ("uint8", ()), "material": ("uint8", ())}
+
+
+class PathAdvanceOut(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("radiance",) + tuple(ADVANCE_OUTPUTS) + ("count",)]
+
+
+class PathAdvanceStats(C.Structure):
+    _fields_ = [("rays", C.c_uint64), ("scattered", C.c_uint64), ("seconds", C.c_double), ("kernel_vgprs", C.c_uint32),
+                ("scratch_bytes", C.c_uint32)]
+
+
 class LaunchPlan(C.Structure):
     """rt_launch_plan: what a launch decides (csrc/launch_plan.h); every scalar field but ray_budget is an int32."""
     _fields_ = [(n, C.c_uint32 if n == "ray_budget" else C.c_int32) for n in (
@@ -226,6 +252,10 @@ SIGNATURES = {
     "rt_scene_path_step_device": (I, [P, C.POINTER(PathStepParams), C.POINTER(PathStepRays), C.POINTER(PathStepOut), C.POINTER(PathStepStats)]),
     "rt_scene_path_step": (I, [P, C.POINTER(PathStepParams), C.POINTER(PathStepRays), C.POINTER(PathStepOut), C.POINTER(PathStepStats)]),
     "rt_path_step_abi_sizes": (None, [C.POINTER(C.c_uint32)]),
+    "rt_scene_path_advance_device": (I, [P, C.POINTER(PathAdvanceParams), C.POINTER(PathAdvanceRays), C.POINTER(PathAdvanceOut), C.POINTER(PathAdvanceStats)]),
+    "rt_scene_path_advance": (I, [P, C.POINTER(PathAdvanceParams), C.POINTER(PathAdvanceRays), C.POINTER(PathAdvanceOut), C.POINTER(PathAdvanceStats)]),
+    "rt_path_advance_workspace_bytes": (C.c_uint64, [C.c_int64]),
+    "rt_path_advance_abi_sizes": (None, [C.POINTER(C.c_uint32)]),
     "rt_deinterleave": (I, [D3, I, I, I, I, C.c_size_t, D3]),
     "rt_render": (I, [P, C.POINTER(RenderParams), D3, C.POINTER(RenderStats)]),
     "rt_write_ppm": (I, [C.c_char_p, D3, I, I]),
@@ -250,10 +280,11 @@ def load():
         fn = getattr(lib, name)  # AttributeError if the library does not export what rtow.h declares
         fn.restype = res
         fn.argtypes = args
-    # the radiance and path-step structures as this library was compiled against ours: a mismatch would scribble over the
+    # the radiance, path-step and path-advance structures as this library was compiled against ours: a mismatch would scribble over the
     # caller's arrays
     for what, sizes_of, structs in (("rt_radiance_*", lib.rt_radiance_abi_sizes, (RadianceParams, RadianceRays, RadianceOut, RadianceStats)),
-                                    ("rt_path_step_*", lib.rt_path_step_abi_sizes, (PathStepParams, PathStepRays, PathStepOut, PathStepStats))):
+                                    ("rt_path_step_*", lib.rt_path_step_abi_sizes, (PathStepParams, PathStepRays, PathStepOut, PathStepStats)),
+                                    ("rt_path_advance_*", lib.rt_path_advance_abi_sizes, (PathAdvanceParams, PathAdvanceRays, PathAdvanceOut, PathAdvanceStats))):
         sizes = (C.c_uint32 * 4)()
         sizes_of(sizes)
         ours = [C.sizeof(x) for x in structs]

@@ -13,6 +13,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import (AdaptiveParams, DenoiseParams, FeatureParams, LaunchPlan, QueryHits, QueryParams, QueryRays, QueryStats,  # noqa: F401
+                   PathAdvanceOut, PathAdvanceParams, PathAdvanceRays, PathAdvanceStats,
                    PathStepOut, PathStepParams, PathStepRays, PathStepStats, RadianceOut, RadianceParams, RadianceRays, RadianceStats,
                    RenderParams, RenderStats, SceneInfo)
 
@@ -448,6 +449,62 @@ class Scene:
                                   (lib().rt_scene_path_step, lib().rt_scene_path_step_device), structs, PathStepStats if stats else None, device)
         return (out, st) if stats else out
 
+    # ---- path advances (include/rtow.h rt_scene_path_advance) ----
+    def path_advance(self, origins, directions, times=None, rng_state=None, throughput=None, ray_id=None, alive=None, radiance=None,
+                     time=0.0, seed=1984, first_sequence=0, variant=0,
+                     want=("origin", "direction", "time", "rng_state", "throughput", "ray_id"), device=0, stats=False):
+        """One bounce for a batch of paths, with what a loop around ``path_step`` does between two steps done on the device: every
+        ray with ``alive[k] != 0`` (all, without ``alive``) is stepped as ``path_step`` steps it; a path that ends adds
+        ``throughput[k] * emitted`` to ``radiance[ray_id[k]]``, in place (``radiance``: (sources, 3) float64 or None; an id outside
+        0 .. sources - 1 adds nothing; the ids of live rays must be distinct); the scattered rays come back packed, in input order.
+        ``throughput`` (count, 3) float64 defaults to ones, ``ray_id`` (count,) int32 to k, ``alive`` is (count,) uint8; ``times`` and
+        ``rng_state`` as for ``path_step``.  Returns a dict of the outputs named in ``want``, each cut to the number of survivors:
+        "origin", "direction", "time", "rng_state" (the scattered ray and its stream), "throughput" (``throughput[k] * attenuation``),
+        "ray_id", and "t", "normal", "front_face", "material" of the hit the survivor scattered from.  The call reads the
+        survivors' count, so it waits for the device (``PathBatch`` is the form that does not).  numpy arrays take the host call;
+        torch CUDA tensors are read in place, on ``torch.cuda.current_stream()``, with a workspace tensor of this call's own.
+        Other dtypes, shapes and non-contiguous inputs raise RtowError.  ``stats=True``: (outputs, PathAdvanceStats)."""
+        on_gpu = type(origins).__module__.split(".")[0] == "torch"
+        wanted = tuple(want)
+        kept = {}   # what the call uses beside the per-ray arrays: alive until the count has been read
+
+        def structs(count, rays, outs, device, stream):
+            sources = 0
+            if radiance is not None:
+                if on_gpu:
+                    import torch
+                    ok = isinstance(radiance, torch.Tensor) and radiance.is_cuda and radiance.device == origins.device and \
+                        radiance.dtype == torch.float64 and radiance.is_contiguous()
+                else:
+                    ok = isinstance(radiance, np.ndarray) and radiance.dtype == np.float64 and radiance.flags.c_contiguous and radiance.flags.writeable
+                if not ok or radiance.ndim != 2 or radiance.shape[1] != 3:
+                    raise RtowError("radiance: a contiguous (sources, 3) float64 array of the kind of the origins is required")
+                sources = int(radiance.shape[0])
+            nbytes = int(lib().rt_path_advance_workspace_bytes(count))
+            if on_gpu:
+                import torch
+                kept["count"] = torch.zeros(1, dtype=torch.int32, device=origins.device)
+                kept["workspace"] = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=origins.device)
+                address = lambda a: a.data_ptr()   # noqa: E731
+            else:
+                kept["count"] = np.zeros(1, dtype=np.uint32)
+                address = lambda a: a.ctypes.data   # noqa: E731
+            p = PathAdvanceParams(count, sources, float(time), int(seed), int(first_sequence), int(variant), device, stream,
+                                  address(kept["workspace"]) if on_gpu else None, nbytes if on_gpu else 0)
+            r = PathAdvanceRays(*(rays.get(n) for n in ("origins", "directions", "times", "rng_state", "throughput", "ray_id", "alive")), None)
+            o = PathAdvanceOut(address(radiance) if sources else None, *(outs.get(n) for n in _lib.ADVANCE_OUTPUTS), address(kept["count"]))
+            return p, r, o
+
+        inputs = [("times", times, (), ("float64",), False), ("rng_state", rng_state, (6,), ("uint32", "int32"), False),
+                  ("throughput", throughput, (3,), ("float64",), False), ("ray_id", ray_id, (), ("int32",), False),
+                  ("alive", alive, (), ("uint8",), False)]
+        required = tuple(n for n in ("origin", "direction") if n not in wanted)
+        out, st = self._ray_batch("path advance", origins, directions, inputs, _lib.ADVANCE_OUTPUTS, wanted + required,
+                                  (lib().rt_scene_path_advance, lib().rt_scene_path_advance_device), structs, PathAdvanceStats if stats else None, device)
+        survivors = int(kept["count"][0])   # (a tensor: the copy waits for the stream the call was enqueued on)
+        out = {name: out[name][:survivors] for name in wanted}
+        return (out, st) if stats else out
+
     # ---- one-call render on one GPU ----
     def render(self, width, height, spp, max_depth=50, seed=1984, variant=0, device=0, flags=0, coop_threshold=0,
                overdue=0, shade_batch=0, max_blocks_per_cu=0, pixels_per_wave=0, adaptive=None):
@@ -470,6 +527,130 @@ class Scene:
         st = RenderStats()
         _check(lib().rt_render(self._p, C.byref(p), frame.ctypes.data_as(_lib.D3), C.byref(st)))
         return frame, st
+
+
+class PathBatch:
+    """A batch of paths that lives on the device (include/rtow.h rt_scene_path_advance_device): two sets of ray tensors, a
+    workspace, a one-word count tensor and ``radiance`` ((n, 3) float64, zeros).  ``advance`` enqueues bounces on
+    ``torch.cuda.current_stream()`` without the host ever waiting: each call steps the live rays of the current side, folds the
+    paths that ended into ``radiance`` and writes the survivors packed, in order, into the other side, which becomes the current
+    one.  Takes torch CUDA tensors only: ``origins`` and ``directions`` (n, 3) float64, ``times`` (n,) float64 or None (``time``
+    for all), ``rng_state`` (n, 6) uint32 / int32 or None (ray k draws from ``curand_init(seed, k + first_sequence, 0)``).
+    The current side's ``origin``, ``direction``, ``time``, ``rng_state``, ``throughput``, ``ray_id`` (and ``t``, ``normal``,
+    ``front_face``, ``material`` of the last hit with ``hits=True``) are attributes: tensors of n rows of which the first
+    ``live()`` hold the live rays.  A caller may read them and scale ``throughput`` in place (Russian roulette: ``kill`` the
+    losers, divide the winners' throughput by their chance).  Work on them on the stream the advances are enqueued on."""
+
+    def __init__(self, scene, origins, directions, times=None, rng_state=None, time=0.0, seed=1984, first_sequence=0, variant=0, hits=False):
+        import torch
+        for name, a, tail, dtypes in (("origins", origins, (3,), (torch.float64,)), ("directions", directions, (3,), (torch.float64,)),
+                                      ("times", times, (), (torch.float64,)), ("rng_state", rng_state, (6,), (torch.uint32, torch.int32))):
+            if a is None and name in ("times", "rng_state"):
+                continue
+            if not isinstance(a, torch.Tensor) or not a.is_cuda or a.dtype not in dtypes or not a.is_contiguous():
+                raise RtowError(f"{name}: a contiguous CUDA tensor of dtype {' or '.join(str(d) for d in dtypes)} is required")
+            if a.device != origins.device or a.ndim != 1 + len(tail) or tuple(a.shape[1:]) != tail or a.shape[0] != origins.shape[0]:
+                raise RtowError(f"{name}: shape {('count',) + tail} on the device of the origins is required, got {tuple(a.shape)} on {a.device}")
+        if variant not in (0, 1):
+            raise RtowError("variant must be 0 (strict) or 1 (fast)")
+        self.scene = scene
+        self.n = n = int(origins.shape[0])
+        self.device = dev = origins.device
+        self._index = dev.index if dev.index is not None else torch.cuda.current_device()
+        rows = max(n, 1)   # (never an empty allocation: its address may be null)
+        names = list(_lib.ADVANCE_OUTPUTS) if hits else ["origin", "direction", "time", "rng_state", "throughput", "ray_id"]
+        state_dtype = rng_state.dtype if rng_state is not None else torch.uint32
+        kinds = {"float64": torch.float64, "uint32": torch.int32, "int32": torch.int32, "uint8": torch.uint8}
+        self._sides = [{name: torch.zeros((rows,) + _lib.ADVANCE_OUTPUTS[name][1], dtype=kinds[_lib.ADVANCE_OUTPUTS[name][0]], device=dev)
+                        for name in names} for _ in range(2)]
+        for side in self._sides:   # (allocated as int32: the words are the same)
+            side["rng_state"] = side["rng_state"].view(state_dtype)
+        first = self._sides[0]
+        first["origin"][:n] = origins
+        first["direction"][:n] = directions
+        first["time"][:n] = times if times is not None else float(time)
+        first["throughput"].fill_(1.0)
+        first["ray_id"][:n] = torch.arange(n, dtype=torch.int32, device=dev)
+        if rng_state is not None:
+            first["rng_state"].view(torch.int32)[:n] = rng_state.view(torch.int32)
+        self._seeded_by_library = rng_state is None   # until the first advance the current side's rng_state holds nothing
+        self._current = 0
+        self.radiance = torch.zeros((rows, 3), dtype=torch.float64, device=dev)[:n]
+        self._count = torch.full((1,), n, dtype=torch.int32, device=dev)
+        self._alive = torch.ones(rows, dtype=torch.uint8, device=dev)
+        self._killed = False
+        nbytes = int(lib().rt_path_advance_workspace_bytes(n))
+        self._workspace = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+        # the structs of a call from side 0 to side 1 and back, built once: the pointers do not change
+        self._calls = []
+        for src in (0, 1):
+            a, b = self._sides[src], self._sides[1 - src]
+            p = PathAdvanceParams(n, n, float(time), int(seed), int(first_sequence), int(variant), self._index, None, self._workspace.data_ptr(), nbytes)
+            rays = PathAdvanceRays(a["origin"].data_ptr(), a["direction"].data_ptr(), a["time"].data_ptr(), a["rng_state"].data_ptr(),
+                                   a["throughput"].data_ptr(), a["ray_id"].data_ptr(), None, self._count.data_ptr())
+            out = PathAdvanceOut(self.radiance.data_ptr() if n else None, *(b[name].data_ptr() if name in b else None for name in _lib.ADVANCE_OUTPUTS),
+                                 self._count.data_ptr())
+            self._calls.append((p, rays, out))
+
+    def __getattr__(self, name):   # the current side's tensors
+        sides = self.__dict__.get("_sides")
+        if sides and name in sides[self._current]:
+            return sides[self._current][name]
+        raise AttributeError(name)
+
+    def advance(self, bounces=1, capacity=None, stats=False):
+        """Enqueues ``bounces`` advances on the current stream and returns; nothing waits.  ``capacity``: rows a launch covers, at
+        least the live rays' count (``run`` narrows it to a count it has read); None: all n.  ``stats=True`` (measurements): every
+        call waits and the list of their PathAdvanceStats comes back."""
+        import torch
+        taken = []
+        if self.n == 0:
+            return taken if stats else None
+        capacity = self.n if capacity is None else int(capacity)
+        if not 0 < capacity <= self.n:
+            raise RtowError(f"capacity must be 1 .. {self.n}")
+        stream = torch.cuda.current_stream(self.device).cuda_stream or None
+        fn = lib().rt_scene_path_advance_device
+        for _ in range(int(bounces)):
+            p, rays, out = self._calls[self._current]
+            p.count = capacity
+            p.stream = stream
+            rays.rng_state = None if self._seeded_by_library else self._sides[self._current]["rng_state"].data_ptr()
+            rays.alive = self._alive.data_ptr() if self._killed else None
+            if stats:
+                taken.append(PathAdvanceStats())
+            _check(fn(self.scene._p, C.byref(p), C.byref(rays), C.byref(out), C.byref(taken[-1]) if stats else None))
+            if self._killed:
+                self._alive.fill_(1)   # (behind the kernels that read the flags, on their stream)
+                self._killed = False
+            self._seeded_by_library = False
+            self._current = 1 - self._current
+        return taken if stats else None
+
+    def live(self):
+        """The number of live rays: reads the count word, so it waits for the advances enqueued so far."""
+        return int(self._count.item()) if self.n else 0
+
+    def kill(self, mask):
+        """Drops the rays ``mask`` marks (a bool tensor over the first rows of the current side) at the next advance: they are not
+        traced and add nothing to ``radiance``.  The marks are forgotten after that advance."""
+        self._alive[:mask.shape[0]].masked_fill_(mask, 0)   # (no wait, unlike an indexed assignment)
+        self._killed = True
+
+    def run(self, max_depth, check_every=8):
+        """``max_depth`` bounces: the paths still alive after the last are dropped, as ``RayColor`` cuts them, and ``radiance`` is
+        ``Scene.radiance(samples=1, max_depth=max_depth)`` of the batch's rays, bit for bit in the strict build.  Every
+        ``check_every`` bounces the count is read (a wait) to stop when no ray is left and to narrow later launches to the count;
+        0: never, all ``max_depth`` bounces are enqueued at once.  Returns ``radiance``; the caller synchronizes before reading it
+        on another stream."""
+        done, capacity = 0, self.n
+        while done < max_depth and capacity > 0:
+            bounces = max_depth - done if check_every <= 0 else min(int(check_every), max_depth - done)
+            self.advance(bounces, capacity)
+            done += bounces
+            if check_every > 0 and done < max_depth:
+                capacity = self.live()
+        return self.radiance
 
 
 def builtin_scene(scene_id, world_kind, width, height, seed=1984, earth=None):

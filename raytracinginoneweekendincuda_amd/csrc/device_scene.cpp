@@ -10,6 +10,7 @@
 #include <map>
 #include <mutex>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/rtow.h"
@@ -38,9 +39,19 @@ struct DeviceTables {
     DeviceArena memory;       // every table below
     DeviceScene scene{};
     const uint32_t *node_leaf_pos = nullptr;  // ray queries (rt_scene_intersect_device): FlatScene::node_leaf_pos
+    // path advances without statistics return before their kernels have run (rt_scene_path_advance_device): recorded behind the
+    // last of them, created by the first
+    hipEvent_t advance_done = nullptr;
 };
 
-void release_device_tables(DeviceTables *t) { delete t; }
+void release_device_tables(DeviceTables *t)
+{
+    if (t && t->advance_done) {  // an advance may still be reading the tables
+        hipEventSynchronize(t->advance_done);
+        hipEventDestroy(t->advance_done);
+    }
+    delete t;
+}
 
 // jump table: one copy per device for the life of the process
 static std::mutex g_jump_mutex;
@@ -475,12 +486,13 @@ struct Build {
     hipError_t (*query)(const DeviceScene &, const QueryArgs &, hipStream_t, QueryKernelInfo *);
     hipError_t (*radiance)(const DeviceScene &, const RadianceArgs &, hipStream_t, QueryKernelInfo *);
     hipError_t (*step)(const DeviceScene &, const StepArgs &, hipStream_t, QueryKernelInfo *);
+    hipError_t (*advance)(const DeviceScene &, const AdvanceArgs &, hipStream_t, QueryKernelInfo *);
 };
 static const Build kBuilds[2] = {
     {launch_seed_strict, launch_render_strict, kernel_info_strict, launch_adaptive_rule_strict, launch_features_strict, launch_query_strict,
-     launch_radiance_strict, launch_step_strict},
+     launch_radiance_strict, launch_step_strict, launch_advance_strict},
     {launch_seed_fast, launch_render_fast, kernel_info_fast, launch_adaptive_rule_fast, launch_features_fast, launch_query_fast,
-     launch_radiance_fast, launch_step_fast}};
+     launch_radiance_fast, launch_step_fast, launch_advance_fast}};
 
 static int seed_film(FilmImpl &f, const rt_render_params *p, hipStream_t stream)
 {
@@ -1336,6 +1348,224 @@ void rt_path_step_abi_sizes(uint32_t out4[4])
     out4[1] = (uint32_t)sizeof(rt_path_step_rays);
     out4[2] = (uint32_t)sizeof(rt_path_step_out);
     out4[3] = (uint32_t)sizeof(rt_path_step_stats);
+}
+
+// ---- path advances ----
+// The workspace of an advance of capacity `count` (private): the workgroups' counts and offsets, the survivor flags, then one
+// staging array per output, each from a multiple of 256 bytes.  Every piece grows with the count, so the total does.
+struct AdvanceWorkspace {
+    uint64_t block_counts, block_offsets, survivor;
+    uint64_t origin, direction, time, rng_state, throughput, ray_id, t, normal, front_face, material;
+    uint64_t bytes;
+    uint32_t n_blocks;
+};
+static AdvanceWorkspace advance_workspace(int64_t count)
+{
+    AdvanceWorkspace w{};
+    if (count <= 0) return w;
+    const uint64_t n = (uint64_t)count;
+    w.n_blocks = (uint32_t)((n + kAdvanceBlock - 1) / kAdvanceBlock);
+    uint64_t at = 0;
+    const auto piece = [&](uint64_t bytes) {
+        const uint64_t here = at;
+        at += (bytes + 255u) & ~(uint64_t)255u;
+        return here;
+    };
+    w.block_counts = piece((uint64_t)w.n_blocks * sizeof(uint32_t));
+    w.block_offsets = piece((uint64_t)w.n_blocks * sizeof(uint32_t));
+    w.survivor = piece(n);
+    w.origin = piece(n * 3 * sizeof(double));
+    w.direction = piece(n * 3 * sizeof(double));
+    w.time = piece(n * sizeof(double));
+    w.rng_state = piece(n * 6 * sizeof(uint32_t));
+    w.throughput = piece(n * 3 * sizeof(double));
+    w.ray_id = piece(n * sizeof(int32_t));
+    w.t = piece(n * sizeof(double));
+    w.normal = piece(n * 3 * sizeof(double));
+    w.front_face = piece(n);
+    w.material = piece(n);
+    w.bytes = at;
+    return w;
+}
+
+// everything that can be refused without a device, in the order include/rtow.h lists it
+static int path_advance_check(rt_scene *scene, const rt_path_advance_params *p, const rt_path_advance_rays *rays, const rt_path_advance_out *out,
+                              bool device_call, const char *who)
+{
+    const std::string name(who);
+    const auto sources = [&] { return p->sources < 0 || p->sources > ((int64_t)1 << 30) ? ": sources must be 0 .. 2^30" : nullptr; };
+    if (int rc = batch_check(scene, p, rays, out, name, sources)) return rc;
+    if (!out->origin || !out->direction || !out->count) return fail(RT_ERR_INVALID, name + ": out->origin, out->direction and out->count are required");
+    if (out->radiance && p->sources == 0) return fail(RT_ERR_INVALID, name + ": a radiance array of no rows (sources is 0)");
+    const std::pair<const void *, const void *> pairs[] = {{rays->origin, out->origin},       {rays->direction, out->direction},
+                                                           {rays->time, out->time},           {rays->rng_state, out->rng_state},
+                                                           {rays->throughput, out->throughput}, {rays->ray_id, out->ray_id}};
+    for (const auto &pair : pairs)
+        if (pair.first && pair.first == pair.second)
+            return fail(RT_ERR_INVALID, name + ": an output is the input array of the same meaning (the compaction cannot be done in place)");
+    if (device_call && p->count > 0 && (!p->workspace || p->workspace_bytes < advance_workspace(p->count).bytes))
+        return fail(RT_ERR_INVALID, name + ": the workspace is null or smaller than rt_path_advance_workspace_bytes(count)");
+    return RT_OK;
+}
+
+uint64_t rt_path_advance_workspace_bytes(int64_t count) { return advance_workspace(count > ((int64_t)1 << 30) ? (int64_t)1 << 30 : count).bytes; }
+
+int rt_scene_path_advance_device(rt_scene *scene, const rt_path_advance_params *p, const rt_path_advance_rays *rays,
+                                 const rt_path_advance_out *out, rt_path_advance_stats *stats)
+{
+    const char *who = "rt_scene_path_advance_device";
+    if (int rc = path_advance_check(scene, p, rays, out, true, who)) return rc;
+    if (stats) *stats = rt_path_advance_stats{};
+    if (p->count == 0) return RT_OK;
+    SceneImpl &s = *S(scene);
+    if (int rc = rt_scene_upload(scene, p->device)) return rc;  // (selects the device)
+    DeviceTables &dt = *s.device[p->device];
+    const AdvanceWorkspace w = advance_workspace(p->count);
+    char *base = static_cast<char *>(p->workspace);
+    const auto at = [&](uint64_t offset, const void *wanted) { return wanted ? base + offset : nullptr; };  // stage what is asked for
+    AdvanceArgs aa{};
+    aa.origin = rays->origin;
+    aa.direction = rays->direction;
+    aa.time = rays->time;
+    aa.time_all = p->time;
+    aa.rng_in = rays->rng_state;
+    aa.throughput = rays->throughput;
+    aa.ray_id = rays->ray_id;
+    aa.alive = rays->alive;
+    aa.count_in = rays->count;
+    aa.radiance = out->radiance;
+    aa.stage.origin = (double *)at(w.origin, out->origin);
+    aa.stage.direction = (double *)at(w.direction, out->direction);
+    aa.stage.time = (double *)at(w.time, out->time);
+    aa.stage.rng_state = (uint32_t *)at(w.rng_state, out->rng_state);
+    aa.stage.throughput = (double *)at(w.throughput, out->throughput);
+    aa.stage.ray_id = (int32_t *)at(w.ray_id, out->ray_id);
+    aa.stage.t = (double *)at(w.t, out->t);
+    aa.stage.normal = (double *)at(w.normal, out->normal);
+    aa.stage.front_face = (uint8_t *)at(w.front_face, out->front_face);
+    aa.stage.material = (uint8_t *)at(w.material, out->material);
+    aa.survivor = (uint8_t *)(base + w.survivor);
+    aa.block_counts = (uint32_t *)(base + w.block_counts);
+    if (int rc = device_jump_table(p->device, &aa.jump_table)) return rc;
+    aa.base = xorwow_seed(p->seed, kSaltCurandDevice);
+    aa.first_sequence = p->first_sequence;
+    aa.capacity = (uint32_t)p->count;
+    aa.sources = (uint32_t)p->sources;
+    AdvanceGatherArgs ga{};
+    ga.from = aa.stage;
+    ga.to = AdvanceStage{out->origin, out->direction, out->time, out->rng_state, out->throughput, out->ray_id, out->t, out->normal, out->front_face, out->material};
+    ga.survivor = aa.survivor;
+    ga.block_offsets = (uint32_t *)(base + w.block_offsets);
+    ga.capacity = aa.capacity;
+    hipStream_t stream = (hipStream_t)p->stream;
+    if (!dt.advance_done) HIP_TRY(hipEventCreateWithFlags(&dt.advance_done, hipEventDisableTiming));
+    const auto three = [&]() -> hipError_t {  // the call's kernels, in the stream's order
+        hipError_t e = kBuilds[p->variant].advance(dt.scene, aa, stream, nullptr);
+        if (e == hipSuccess) e = launch_advance_scan(aa.block_counts, const_cast<uint32_t *>(ga.block_offsets), w.n_blocks, out->count, stream);
+        if (e == hipSuccess) e = launch_advance_gather(ga, stream);
+        return e;
+    };
+    if (!stats) {  // enqueue and return: whoever frees the tables waits for the event
+        hipError_t e = three();
+        const hipError_t recorded = hipEventRecord(dt.advance_done, stream);
+        if (e == hipSuccess) e = recorded;
+        return e == hipSuccess ? RT_OK : hip_fail(e, who);
+    }
+    QueryKernelInfo info{};
+    HIP_TRY(kBuilds[p->variant].advance(dt.scene, aa, stream, &info));
+    DeviceArena scratch(p->device);
+    HIP_TRY(scratch.alloc(1, aa.stepped_counter));
+    // from here on the chain: the events are destroyed, and the stream waited for, whatever fails
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    unsigned long long stepped = 0;
+    uint32_t survivors = 0;
+    hipError_t e = hipEventCreate(&ev[0]);
+    if (e == hipSuccess) e = hipEventCreate(&ev[1]);
+    if (e == hipSuccess) e = hipMemsetAsync(aa.stepped_counter, 0, sizeof(unsigned long long), stream);
+    if (e == hipSuccess) e = hipEventRecord(ev[0], stream);
+    if (e == hipSuccess) e = three();
+    if (e == hipSuccess) e = hipEventRecord(ev[1], stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(&stepped, aa.stepped_counter, sizeof stepped, hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(&survivors, out->count, sizeof survivors, hipMemcpyDeviceToHost, stream);
+    const hipError_t waited = hipStreamSynchronize(stream);
+    if (e == hipSuccess) e = waited;
+    float ms = 0.0f;
+    if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev[0], ev[1]);
+    for (hipEvent_t v : ev)
+        if (v) hipEventDestroy(v);
+    if (e != hipSuccess) return hip_fail(e, who);
+    stats->rays = stepped;
+    stats->scattered = survivors;
+    stats->seconds = (double)ms * 1e-3;
+    stats->kernel_vgprs = (uint32_t)info.vgprs;
+    stats->scratch_bytes = (uint32_t)info.scratch_bytes;
+    return RT_OK;
+}
+
+int rt_scene_path_advance(rt_scene *scene, const rt_path_advance_params *p, const rt_path_advance_rays *rays, const rt_path_advance_out *out,
+                          rt_path_advance_stats *stats)
+{
+    if (int rc = path_advance_check(scene, p, rays, out, false, "rt_scene_path_advance")) return rc;
+    if (stats) *stats = rt_path_advance_stats{};
+    if (p->count == 0) return RT_OK;
+    if (int rc = select_device(p->device)) return rc;
+    // the host knows the word: only the rows below n travel
+    const int64_t n = rays->count && (int64_t)*rays->count < p->count ? (int64_t)*rays->count : p->count;
+    if (n == 0) {
+        *out->count = 0;
+        return RT_OK;
+    }
+    Staging stage{DeviceArena(p->device), (size_t)n, {}};
+    rt_path_advance_rays dr{};
+    HIP_TRY(stage.in(rays->origin, 3, dr.origin));
+    HIP_TRY(stage.in(rays->direction, 3, dr.direction));
+    HIP_TRY(stage.in(rays->time, 1, dr.time));
+    HIP_TRY(stage.in(rays->rng_state, 6, dr.rng_state));
+    HIP_TRY(stage.in(rays->throughput, 3, dr.throughput));
+    HIP_TRY(stage.in(rays->ray_id, 1, dr.ray_id));
+    HIP_TRY(stage.in(rays->alive, 1, dr.alive));
+    rt_path_advance_out dout{};
+    if (out->radiance) {
+        const double *uploaded = nullptr;
+        HIP_TRY(stage.arena.upload(out->radiance, (size_t)p->sources * 3, uploaded));
+        dout.radiance = const_cast<double *>(uploaded);
+    }
+    HIP_TRY(stage.out(out->origin, 3, dout.origin));
+    HIP_TRY(stage.out(out->direction, 3, dout.direction));
+    HIP_TRY(stage.out(out->time, 1, dout.time));
+    HIP_TRY(stage.out(out->rng_state, 6, dout.rng_state));
+    HIP_TRY(stage.out(out->throughput, 3, dout.throughput));
+    HIP_TRY(stage.out(out->ray_id, 1, dout.ray_id));
+    HIP_TRY(stage.out(out->t, 1, dout.t));
+    HIP_TRY(stage.out(out->normal, 3, dout.normal));
+    HIP_TRY(stage.out(out->front_face, 1, dout.front_face));
+    HIP_TRY(stage.out(out->material, 1, dout.material));
+    HIP_TRY(stage.arena.alloc(1, dout.count));
+    rt_path_advance_params dp = *p;
+    dp.count = n;
+    dp.stream = nullptr;  // the copies around the advance are synchronous: nothing to order on the caller's stream
+    dp.workspace_bytes = advance_workspace(n).bytes;
+    unsigned char *workspace = nullptr;
+    HIP_TRY(stage.arena.alloc((size_t)dp.workspace_bytes, workspace));
+    dp.workspace = workspace;
+    rt_path_advance_stats waited{};  // with statistics the device call waits
+    if (int rc = rt_scene_path_advance_device(scene, &dp, &dr, &dout, stats ? stats : &waited)) return rc;
+    uint32_t survivors = 0;
+    HIP_TRY(hipMemcpy(&survivors, dout.count, sizeof survivors, hipMemcpyDeviceToHost));
+    if (survivors > (uint32_t)n) survivors = (uint32_t)n;  // (never)
+    for (const Staging::Out &o : stage.outs)  // the first `survivors` rows of each
+        if (survivors) HIP_TRY(hipMemcpy(o.host, o.dev, o.bytes / (size_t)n * survivors, hipMemcpyDeviceToHost));
+    if (out->radiance) HIP_TRY(hipMemcpy(out->radiance, dout.radiance, (size_t)p->sources * 3 * sizeof(double), hipMemcpyDeviceToHost));
+    *out->count = survivors;
+    return RT_OK;
+}
+
+void rt_path_advance_abi_sizes(uint32_t out4[4])
+{
+    out4[0] = (uint32_t)sizeof(rt_path_advance_params);
+    out4[1] = (uint32_t)sizeof(rt_path_advance_rays);
+    out4[2] = (uint32_t)sizeof(rt_path_advance_out);
+    out4[3] = (uint32_t)sizeof(rt_path_advance_stats);
 }
 
 int rt_render(rt_scene *scene, const rt_render_params *params, double *frame, rt_render_stats *stats)

@@ -56,6 +56,9 @@
 #ifndef RT_STEP  // 1: this translation unit holds the path-step kernels (step_kernel) and nothing else
 #define RT_STEP 0
 #endif
+#ifndef RT_ADVANCE  // 1: this translation unit holds the path-advance kernels (advance_kernel) and nothing else
+#define RT_ADVANCE 0
+#endif
 
 namespace rtow {
 namespace {
@@ -303,7 +306,7 @@ DEV bool sphere_test(Vec oc, Vec d, double a, double r2, double tmin, double tma
 // times with the branch (the select costs the media kernel of scene 8 3 %), the lane-per-ray kernels of the feature pass and the
 // queries keep their registers with the select (the branch takes the radiance kernel of list worlds from 168 to 170 VGPRs, from
 // three waves per SIMD to two, 35 % on scene 7).  A third form, a switch case of its own in quad_test_at, cost most kernels spills.
-#define RT_PLANAR_SELECT (RT_FEATURES || RT_QUERY || RT_RADIANCE || RT_STEP)
+#define RT_PLANAR_SELECT (RT_FEATURES || RT_QUERY || RT_RADIANCE || RT_STEP || RT_ADVANCE)
 DEV bool quad_test(const QuadGeom &q, bool tri, const Ray &r, double tmin, double tmax, double &t_out)
 {
     Vec n = mk(q.nx, q.ny, q.nz);
@@ -458,7 +461,7 @@ DEV bool prim_test(const DeviceScene &sc, uint32_t ref, const Ray &r, double a, 
 #ifndef RT_PHASES
 #define RT_PHASES 0  // diagnostic build: per-phase wave cycles and lane occupancy, summed into ray_counter[7] and [32..119]
 #endif
-#if RT_PHASES && (RT_FEATURES || RT_QUERY || RT_RADIANCE || RT_STEP)
+#if RT_PHASES && (RT_FEATURES || RT_QUERY || RT_RADIANCE || RT_STEP || RT_ADVANCE)
 #undef RT_PHASES
 #define RT_PHASES 0  // the phases are render_kernel's: the feature and query units of a diagnostic build are the ordinary ones
 #endif
@@ -4242,10 +4245,10 @@ hipError_t RT_CAT(launch_composite_, RT_SUFFIX)(int which, const DeviceScene &sc
 hipError_t RT_CAT(launch_adaptive_prims_, RT_SUFFIX)(int which, const DeviceScene &sc, const RenderArgs &a, hipStream_t stream, KernelInfo *info);
 hipError_t RT_CAT(launch_adaptive_composite_, RT_SUFFIX)(int which, const DeviceScene &sc, const RenderArgs &a, hipStream_t stream, KernelInfo *info);
 
-#if RT_FEATURES || RT_QUERY || RT_RADIANCE || RT_STEP
+#if RT_FEATURES || RT_QUERY || RT_RADIANCE || RT_STEP || RT_ADVANCE
 // ------------------------------------------------------------------------------------------------
-// Shared by the four lane-per-ray sections below (first-hit features, ray queries, radiance queries, path steps): one lane per pixel or per
-// caller-supplied ray, no persistent waves, no LDS staging.  The next kernel of this family starts from these.
+// Shared by the five lane-per-ray sections below (first-hit features, ray queries, radiance queries, path steps, path advances): one lane
+// per pixel or per caller-supplied ray, no persistent waves, no LDS staging.  The next kernel of this family starts from these.
 // ------------------------------------------------------------------------------------------------
 namespace {
 // every table from global memory: a kernel of this family calls this first
@@ -4769,6 +4772,118 @@ hipError_t RT_CAT(launch_step_, RT_SUFFIX)(const DeviceScene &sc, const StepArgs
     if (!a.origin || !a.direction || !any) return hipErrorInvalidValue;
     void (*kernel)(DeviceScene, StepArgs) = sc.world_kind == WORLD_BVH ? step_kernel<RT_STRICT, TBvhNested> : step_kernel<RT_STRICT, TListNested>;
     return info_or_launch(kernel, sc, a, a.count, stream, info);
+}
+#elif RT_ADVANCE
+// ------------------------------------------------------------------------------------------------
+// Path advances (rt_scene_path_advance), launch 1 of 3 (render_iface.h AdvanceArgs): step_kernel's iteration, restated line for
+// line, for every row below n = min(*count_in, capacity) whose ray is alive, and then what a caller's loop did with the outputs:
+//   an ended ray (status 0 or 1) adds thr * emitted to its row of `radiance` -- the product, then the sum, two operations in the
+//   strict build; the ids of live rays are distinct, so a plain load, add and store;
+//   a scattered ray (status 2) stages its record at its own row k of the staging arrays and sets survivor[k]; the gather launch
+//   moves it to its packed row once the scan launch knows how many survivors the workgroups before this one have.
+// The throughput and the id are loaded after the search: they are not live across it.  No lane returns early: rows at or beyond n
+// and dead rays take part in the ballot and the barrier as non-survivors, and every row below `capacity` gets its flag, every
+// workgroup its count, so that the two launches behind this one read nothing stale.  Termination as for step_kernel.
+// ------------------------------------------------------------------------------------------------
+template <int STRICT, class T>
+__global__ __launch_bounds__(256) void advance_kernel(DeviceScene sc, AdvanceArgs a)
+{
+    __shared__ uint32_t wave_survivors[4];
+    global_tables_only(sc);
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t n = a.count_in ? min(*a.count_in, a.capacity) : a.capacity;
+    const bool stepped = k < n && (!a.alive || a.alive[k] != 0);
+    bool scattered = false;
+    if (stepped) {
+        Ray ray = caller_ray(a.origin, a.direction, a.time, a.time_all, k);
+        Xorwow rng;
+        if (a.rng_in) {  // {d, v0..v4} as rt_rng_state writes them
+            const uint32_t *w = a.rng_in + (size_t)k * 6;
+            rng.d = w[0]; rng.v0 = w[1]; rng.v1 = w[2]; rng.v2 = w[3]; rng.v3 = w[4]; rng.v4 = w[5];
+        } else {  // curand_init(seed, k + first_sequence, 0)
+            rng = a.base;
+            xorwow_skip_sequences(a.jump_table, a.first_sequence + (uint64_t)k, rng);
+        }
+        const NodeView nv{sc.nodes, 0u, false};
+        Vec throughput = mk(1.0, 1.0, 1.0), accumulated = mk(0.0, 0.0, 0.0);
+        HitInfo h;
+        h.t = 0.0;
+        h.ref = kNone;
+        h.obj = kNone;
+        bool hit = false;
+        if constexpr (T::WORLD == 0) {
+            if (sc.n_world_nodes != 0) {
+                Walk w{};
+                walk_begin<false>(w, ray, DBL_MAX);
+                while (w.state != kNone) {
+                    if (walk_moving(w.state)) walk_node<false>(nv, ray, 0.001, w);
+                    else walk_leaves<T>(sc, nv, ray, 0.001, w, h, rng);
+                }
+                hit = w.any;
+            }
+        } else {
+            hit = world_hit_list<T>(sc, ray, 0.001, DBL_MAX, h, rng);
+        }
+        Vec normal = mk(0.0, 0.0, 0.0);
+        uint32_t kind = 255u;
+        bool front = false;
+        if (!hit) {  // R/kernel.cu:74-79
+            accumulated = accumulated + throughput * load3c(((const RT_CONST CameraRec *)(uintptr_t)sc.camera)->bg);
+        } else {
+            const Surface s = make_surface<T>(sc, ray, h);
+            if (a.stage.normal && (h.ref >> kRefShift) != REF_MEDIUM) normal = s.n;
+            front = s.front;
+            if (a.stage.material) kind = material_view<false>(sc, s.mat).u32(MAT_OFF(kind));
+            scattered = shade<T>(sc, s, ray, throughput, accumulated, rng);  // scattered: `ray` is the next ray
+        }
+        // what the path carried into this bounce: `throughput` is 1 * attenuation and `accumulated` 0 + 1 * emitted (step_kernel)
+        const Vec carried = a.throughput ? mk(a.throughput[(size_t)k * 3 + 0], a.throughput[(size_t)k * 3 + 1], a.throughput[(size_t)k * 3 + 2])
+                                         : mk(1.0, 1.0, 1.0);
+        const int32_t id = a.ray_id ? a.ray_id[k] : (int32_t)k;
+        if (!scattered) {
+            if (a.radiance && id >= 0 && (uint32_t)id < a.sources) {
+                const Vec product = carried * accumulated;
+                double *row = a.radiance + (size_t)id * 3;
+                const Vec sum = mk(row[0], row[1], row[2]) + product;
+                row[0] = sum.x;
+                row[1] = sum.y;
+                row[2] = sum.z;
+            }
+        } else {
+            if (a.stage.origin) store3(a.stage.origin, k, ray.o);
+            if (a.stage.direction) store3(a.stage.direction, k, ray.d);
+            if (a.stage.time) a.stage.time[k] = ray.tm;
+            if (a.stage.rng_state) {
+                uint32_t *w = a.stage.rng_state + (size_t)k * 6;
+                w[0] = rng.d; w[1] = rng.v0; w[2] = rng.v1; w[3] = rng.v2; w[4] = rng.v3; w[5] = rng.v4;
+            }
+            if (a.stage.throughput) store3(a.stage.throughput, k, carried * throughput);
+            if (a.stage.ray_id) a.stage.ray_id[k] = id;
+            if (a.stage.t) a.stage.t[k] = h.t;
+            if (a.stage.normal) store3(a.stage.normal, k, mk(0.0, 0.0, 0.0) + normal);  // as query_kernel: no negative zeros
+            if (a.stage.front_face) a.stage.front_face[k] = front ? 1 : 0;
+            if (a.stage.material) a.stage.material[k] = (uint8_t)kind;
+        }
+    }
+    // every lane of the workgroup is here again
+    if (k < a.capacity) a.survivor[k] = scattered ? 1 : 0;
+    const unsigned long long survivors = __ballot(scattered);
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    if (lane == 0) wave_survivors[wave] = (uint32_t)__popcll(survivors);
+    if (a.stepped_counter) {  // one atomic per wave
+        const unsigned long long took = __ballot(stepped);
+        if (lane == 0 && took) atomicAdd(a.stepped_counter, (unsigned long long)__popcll(took));
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) a.block_counts[blockIdx.x] = (wave_survivors[0] + wave_survivors[1]) + (wave_survivors[2] + wave_survivors[3]);
+}
+
+hipError_t RT_CAT(launch_advance_, RT_SUFFIX)(const DeviceScene &sc, const AdvanceArgs &a, hipStream_t stream, QueryKernelInfo *info)
+{
+    if (!info && (!a.origin || !a.direction || !a.survivor || !a.block_counts)) return hipErrorInvalidValue;
+    void (*kernel)(DeviceScene, AdvanceArgs) =
+        sc.world_kind == WORLD_BVH ? advance_kernel<RT_STRICT, TBvhNested> : advance_kernel<RT_STRICT, TListNested>;
+    return info_or_launch(kernel, sc, a, a.capacity, stream, info);
 }
 #elif RT_GROUP == 1
 namespace {

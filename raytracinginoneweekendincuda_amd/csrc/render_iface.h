@@ -208,6 +208,56 @@ struct StepArgs {
 hipError_t launch_step_strict(const DeviceScene &sc, const StepArgs &a, hipStream_t stream, QueryKernelInfo *info = nullptr);
 hipError_t launch_step_fast(const DeviceScene &sc, const StepArgs &a, hipStream_t stream, QueryKernelInfo *info = nullptr);
 
+// Path advances (rt_scene_path_advance; the RT_ADVANCE objects of render.hip and advance_pack.hip): three launches on one stream.
+//   1. advance_kernel: one lane per input row, step_kernel's iteration for the rows below n = min(*count_in, capacity) that are
+//      alive; an ended ray is folded into `radiance`, a scattered one (a survivor) stages its record at its own row of the staging
+//      arrays; every row below `capacity` gets its flag in `survivor`, every workgroup its number of survivors in block_counts.
+//   2. launch_advance_scan: one workgroup, the exclusive prefix of block_counts into block_offsets, the total into *count_out.
+//   3. launch_advance_gather: one lane per row; survivor k of workgroup b goes to row block_offsets[b] + (survivors before it in
+//      the workgroup) of every output asked for: input order is kept.
+// No workgroup waits for another: the order between the three is the stream's.  A staging array whose output is not asked for is
+// nullptr and neither written nor read.
+struct AdvanceStage {
+    double *origin, *direction, *time;   // capacity x 3, x 3, x 1
+    uint32_t *rng_state;                 // capacity x 6
+    double *throughput;                  // capacity x 3
+    int32_t *ray_id;                     // capacity
+    double *t, *normal;                  // capacity, capacity x 3
+    uint8_t *front_face, *material;      // capacity each
+};
+struct AdvanceArgs {
+    const double *origin, *direction;   // capacity x 3 each
+    const double *time;                 // capacity, or nullptr: time_all
+    double time_all;
+    const uint32_t *rng_in;             // capacity x 6, or nullptr: seeded from base
+    const double *throughput;           // capacity x 3, or nullptr: (1, 1, 1)
+    const int32_t *ray_id;              // capacity, or nullptr: k
+    const uint8_t *alive;               // capacity, or nullptr: all
+    const uint32_t *count_in;           // one word, or nullptr: capacity
+    double *radiance;                   // sources x 3, or nullptr: nothing is folded
+    AdvanceStage stage;                 // the workspace's rows (launch 1 writes, launch 3 reads)
+    uint8_t *survivor;                  // capacity: 1 where row k scattered
+    uint32_t *block_counts;             // one per workgroup of 256 rows
+    unsigned long long *stepped_counter;  // one word, zeroed by the caller: rows stepped; nullptr: not counted
+    const uint32_t *jump_table;         // kJumpTableWords
+    Xorwow base;                        // salted seed state (sequence 0)
+    uint64_t first_sequence;
+    uint32_t capacity, sources;
+};
+struct AdvanceGatherArgs {
+    AdvanceStage from, to;              // a nullptr in `to`: that output is not asked for
+    const uint8_t *survivor;
+    const uint32_t *block_offsets;
+    uint32_t capacity;
+};
+// info != nullptr: report the instantiation that would run instead of launching it
+hipError_t launch_advance_strict(const DeviceScene &sc, const AdvanceArgs &a, hipStream_t stream, QueryKernelInfo *info = nullptr);
+hipError_t launch_advance_fast(const DeviceScene &sc, const AdvanceArgs &a, hipStream_t stream, QueryKernelInfo *info = nullptr);
+// (advance_pack.hip: neither depends on the variant)
+hipError_t launch_advance_scan(const uint32_t *block_counts, uint32_t *block_offsets, uint32_t n_blocks, uint32_t *count_out, hipStream_t stream);
+hipError_t launch_advance_gather(const AdvanceGatherArgs &a, hipStream_t stream);
+constexpr uint32_t kAdvanceBlock = 256;  // rows per workgroup of launches 1 and 3
+
 // One level of the edge-avoiding a-trous filter (denoise.hip; include/rtow.h rt_denoise_params has the stencil): full-frame
 // planes, `in` and `out` distinct.  A guide that is nullptr switches its term off; inv_* = 1 / sigma^2 (0 for sigma = +inf), the
 // colour's already scaled for the level.
