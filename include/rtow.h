@@ -173,7 +173,8 @@ typedef struct rt_scene_info {
     uint32_t n_xforms, n_media, n_materials, n_textures, n_perlin, n_images;
     uint32_t table_bytes;         /* bytes of the geometry tables staged on chip */
     uint32_t image_bytes;
-    uint32_t reserved[3];         /* [0] = n_triangles: the rows of n_quads that are triangles; [1], [2] = 0 */
+    uint32_t reserved[3];         /* [0] = n_triangles: the rows of n_quads that are triangles; [1] = n_lights: the rows of the
+                                     light table (rt_scene_dump_lights); [2] = 0 */
 } rt_scene_info;
 RTOW_API int rt_scene_get_info(rt_scene *s, rt_scene_info *out);
 
@@ -198,6 +199,33 @@ RTOW_API int rt_scene_dump_scan_segments(rt_scene *s, int max_segments, uint32_t
  * Host only.  Returns the tile count (negative: error); writes min(tiles, max_tiles) lists where lists_out is given. */
 RTOW_API int rt_scene_dump_primary_lists(rt_scene *s, int width, int height, int stripe_rows, int rank, int world_size, int max_tiles,
                                          uint16_t *lists_out);
+
+/* The light table (valid after commit): one row per world primitive whose material is a DiffuseLight -- spheres, moving spheres,
+ * quads, triangles (those of meshes included), the six faces of a MakeBox -- wherever it sits in the world: in lists, in BvhNodes,
+ * under any chain of Translate / RotateY, in the general object tree.  Nothing that is, or lies inside, the boundary of a
+ * ConstantMedium is listed.  The order is the depth-first order of the world as constructed: the world's leaves in
+ * rt_scene_dump_leaves order, and below a leaf a list's members in list order, a BvhNode's in its sorted order.  Every row is in
+ * WORLD space: the forward transforms of the chain above the primitive (innermost first; a RotateY turns points and vectors, x' =
+ * (cos * x) + (sin * z), z' = (-sin * x) + (cos * z), a Translate adds its offset to points) are applied on the host, in fp64,
+ * one IEEE operation at a time.
+ *   kind 0 quad, 1 triangle   a = Q, b = u, c = v (corners Q, Q + u, Q + v [, Q + u + v]), n = the unit normal the primitive was
+ *                             constructed with, turned through the chain; s = the area |u x v| (half of it for a triangle) of the
+ *                             primitive as constructed
+ *   kind 2 sphere             a = the centre, s = the radius
+ *   kind 3 moving sphere      a = c0, b = dc = c1 - c0 (turned), c = (time0, time1 - time0, 0), s = the radius; the centre at time t
+ *                             is a + ((t - c[0]) / c[1]) * b
+ * mat = the row of the material table, leaf = the position of the world leaf the light belongs to (rt_query_hits.leaf).
+ * cdf_out[2k + st] = the cumulative selection table of strategy st at light k: entry k = fl(fl(w_0 + ... + w_k) / fl(w_0 + ... +
+ * w_{n-1})), summed in order, the last entry exactly 1.0.  Strategy 0: uniform, entry k = fl((k + 1) / n).  Strategy 1: w = the area
+ * (4 pi r^2 for a sphere) x max(r, g, b) of a SolidColor emission texture, x 1 for any other texture; where those weights do not
+ * sum to a finite positive number it is strategy 0's table.  Returns the number of lights (rt_scene_info.reserved[1]); writes
+ * min(lights, max_lights) entries of each array given. */
+typedef struct rt_light_row {
+    double a[3], b[3], c[3], n[3], s;
+    uint32_t kind, mat, leaf, pad0;
+    double pad1;
+} rt_light_row;                           /* 128 bytes, exactly as uploaded */
+RTOW_API int rt_scene_dump_lights(rt_scene *s, int max_lights, int *kind_out, int *leaf_out, rt_light_row *rows_out, double *cdf_out);
 
 /* ---- render (RenderInit + Render, R/kernel.cu:110-154,675-691) ---- */
 typedef struct rt_render_params {
@@ -741,6 +769,127 @@ RTOW_API int rt_scene_path_advance(rt_scene *s, const rt_path_advance_params *pa
 RTOW_API uint64_t rt_path_advance_workspace_bytes(int64_t count);
 /* sizeof of rt_path_advance_params, rt_path_advance_rays, rt_path_advance_out, rt_path_advance_stats as this library was compiled */
 RTOW_API void rt_path_advance_abi_sizes(uint32_t out4[4]);
+
+/* ---- light sampling queries: sample the emitters of the light table, and the density of doing so ----
+ * For next-event estimation and multiple importance sampling beside rt_scene_path_step and the occlusion mode of
+ * rt_scene_intersect.  Two calls over the rows of rt_scene_dump_lights; neither searches the world (visibility is the caller's
+ * shadow ray).  Every operation below is one IEEE-754 double operation in the order written, a * b + c two of them; the strict
+ * build fuses nothing, so its outputs can be restated to the bit (tests/light_restated.py does); the fast build may fuse.
+ * P(k) = cdf[k] - cdf[k - 1] (cdf[0] for k = 0) under params->strategy; pi = 3.1415926535897932385.
+ *
+ * rt_scene_sample_lights: for point k, P = point[3k..3k+2] at time[k] (params->time where `time` is NULL), from the stream
+ * rng_state[6k..6k+5] = {d, v0..v4} or, where that is NULL, curand_init(seed, k + first_sequence, 0).  Draws, all (double)
+ * curand_uniform, in this order:
+ *   1. xi: the light is the first k with cdf[k] >= xi (a binary search; the draw happens with one light too)
+ *   2. quad:      a, b.                                      S = (Q + a * u) + b * v, per component
+ *      triangle:  a, b; where a + b > 1: a = 1 - a, b = 1 - b.    S as for the quad
+ *      sphere (centre C, moving spheres at the point's time; radius r): pairs a, b, p = (2 * a - 1, 2 * b - 1), s = p.x * p.x + p.y * p.y,
+ *      until s < 1 and s > 0 (the lens loop of the camera).  Then, whatever P is -- the draws depend on the stream alone:
+ *        oc = C - P, d2 = (oc.x * oc.x + oc.y * oc.y) + oc.z * oc.z, r2 = r * r;  d2 <= r2 (P inside, or a NaN): invalid sample
+ *        w = (1 / sqrt(d2)) * oc;  cosmax = sqrt(1 - r2 / d2);  omc = 1 - cosmax;  omc == 0: invalid sample
+ *        z = 1 - s * omc;  rho = sqrt(1 - z * z);  q = sqrt(s);  ex = (rho * p.x) / q;  ey = (rho * p.y) / q
+ *        e1: with ax = |w.x|, ay = |w.y|, az = |w.z|:  ax >= ay and ax >= az: t = (w.z, 0, -w.x), e1 = (1 / sqrt(w.z * w.z + w.x * w.x)) * t
+ *                                                     else ay >= az:         t = (-w.y, w.x, 0), e1 = (1 / sqrt(w.y * w.y + w.x * w.x)) * t
+ *                                                     else:                  t = (0, -w.z, w.y), e1 = (1 / sqrt(w.z * w.z + w.y * w.y)) * t
+ *        e2 = w x e1 (the full cross product, its zero terms included)
+ *        g = (z * w + ex * e1) + ey * e2;  direction = (1 / sqrt((g.x * g.x + g.y * g.y) + g.z * g.z)) * g
+ *        the near intersection, as the renderer's own sphere test finds it for the ray (P, direction) (R/Sphere.h:28-50), so that a shadow
+ *        ray along `direction` meets the lamp at this very parameter: po = P - C, qa = direction . direction, qb = po . direction,
+ *        qc = po . po - r2 (every dot product (x + y) + z), disc = qb * qb - qa * qc, distance = (-qb - sqrt(disc)) / qa;  disc <= 0
+ *        (the rounded direction grazes past the sphere: a sample within a few ulps of the cone's rim) or distance <= 0: invalid
+ *        sample;  S = P + distance * direction
+ *   planar lights: D = S - P, d2 = (D.x * D.x + D.y * D.y) + D.z * D.z, distance = sqrt(d2), direction = (1 / distance) * D;
+ *     d2 == 0 (or a NaN): invalid sample
+ *   either kind: a density (below) that is not a positive finite number -- a light of area 0, a chance of 0 -- is an invalid sample
+ * Outputs, each only where its pointer is not NULL (not all may be NULL):
+ *   direction    count x 3: the unit direction from P to the sample; (0, 0, 0) for an invalid sample and without lights
+ *   distance     count: P + distance * direction is the sample; 0 for an invalid sample
+ *   light        count: the light's row, also for an invalid sample; -1 in a scene without lights
+ *   pdf          count: the solid-angle density of the direction under the picked light TIMES P(light); 0 for an invalid sample.
+ *                planar: c = |(n.x * dir.x + n.y * dir.y) + n.z * dir.z|; c == 0: invalid; else (d2 / (c * area)) * P(k)
+ *                sphere: P(k) / ((2 * pi) * omc), uniform over the cone the sphere subtends
+ *   emitted      count x 3: the light's texture at the sample (both sides emit, as Material::Emitted does), through the render
+ *                kernels' texture code with the point S and the primitive's own U, V: a and b for a quad or triangle; for a sphere
+ *                the reference's (R/Sphere.h:74-81) of (1 / r) * (S - C), computed only where the material has an image texture,
+ *                else 0 -- of the sphere in WORLD space: an image on a sphere under RotateY is not turned.  0 for an invalid sample
+ *   scatter_pdf  count: the density with which the renderer's own Material::Scatter sends a ray from a surface of normal[3k..] and
+ *                material[k] (as rt_query_hits.material) into `direction`: Lambertian (0), c = n . direction: c > 0: (2 * ((c * c) *
+ *                c)) / pi, else 0 -- the exact density of unit-normal + uniform point of the unit ball (R/Material.h:67-82), which is
+ *                NOT a cosine lobe; isotropic (4): 1 / (4 * pi); metal, dielectric, diffuse light, 255: 0 (they are treated as
+ *                specular: all their light arrives through Scatter).  0 for an invalid sample
+ *   contribution count x 3: (scatter_pdf / pdf) * emitted, (0, 0, 0) where either density is 0
+ *   rng_state    count x 6: the stream after the last draw; may be the array points->rng_state points to
+ * A scene without lights: RT_OK, light = -1, every other output 0, the stream that goes out is the stream that came in (or was seeded).
+ *
+ * rt_scene_light_pdf: for ray k (origin, direction -- not necessarily unit -- and time as above) pdf[k] = the sum over ALL lights
+ * whose surface the ray meets at a parameter t > 0 of that light's density above under params->strategy: the density with which
+ * rt_scene_sample_lights from `origin` produces this direction -- what multiple importance sampling needs when a scattered ray
+ * finds a lamp.  Planar lights: the plane at t = (n . (Q - o)) / (n . d), n . d != 0, the interior rule of the primitive (quad: 0 <=
+ * alpha, beta <= 1; triangle: 0 <= alpha, 0 <= beta, alpha + beta <= 1, with alpha, beta from m = u x v as m . (ph x v) / (m . m),
+ * m . (u x ph) / (m . m)); density ((t * t) * (d . d)) / ((|n . d| / sqrt(d . d)) * area) * P(k).  Spheres: origin outside (d2 > r2),
+ * b = oc . d > 0 and b * b - (d . d) * (d2 - r2) >= 0; the density is the expression of the sampling call, which depends on the origin
+ * alone -- bit for bit the sampled pdf wherever the hit test agrees.  light[k] = the row of the nearest light met, -1 for none.
+ * Nothing is drawn.
+ *
+ * Both calls return when the results are there (they wait on the stream), like the path steps.  Refusals, before the device is
+ * touched, in this order: RT_ERR_INVALID for a NULL argument; RT_ERR_STATE before commit; RT_ERR_INVALID for a count below 0 or
+ * above 2^30, a strategy other than 0 / 1, a variant other than 0 / 1, a NULL point (origin or direction) with count > 0, every
+ * output NULL, and scatter_pdf or contribution asked for without both normal and material.  count == 0 returns RT_OK without a
+ * launch. */
+typedef struct rt_light_params {
+    int64_t  count;            /* points or rays; 0 is allowed (no launch), > 2^30 is RT_ERR_INVALID */
+    double   time;             /* used where the per-point array is NULL (moving spheres) */
+    uint64_t seed;             /* point k: curand_init(seed, k + first_sequence, 0), unless points->rng_state is given */
+    uint64_t first_sequence;
+    int32_t  strategy;         /* 0 uniform over lights, 1 by area x brightest channel (rt_scene_dump_lights) */
+    int32_t  variant;          /* 0 strict, 1 fast */
+    int32_t  device;
+    void    *stream;           /* NULL = the default stream */
+    int32_t  reserved[4];
+} rt_light_params;
+typedef struct rt_light_points {
+    const double   *point;         /* count x 3; required */
+    const double   *normal;        /* count x 3, or NULL */
+    const uint8_t  *material;      /* count, as rt_query_hits.material, or NULL */
+    const double   *time;          /* count, or NULL */
+    const uint32_t *rng_state;     /* count x 6, or NULL: seeded */
+} rt_light_points;
+typedef struct rt_light_samples {
+    double   *direction;       /* count x 3 */
+    double   *distance;        /* count */
+    int32_t  *light;           /* count */
+    double   *pdf;             /* count */
+    double   *emitted;         /* count x 3 */
+    double   *scatter_pdf;     /* count */
+    double   *contribution;    /* count x 3 */
+    uint32_t *rng_state;       /* count x 6; any pointer may be NULL, not all */
+} rt_light_samples;
+typedef struct rt_light_rays {
+    const double *origin, *direction;   /* count x 3 each */
+    const double *time;                 /* count, or NULL */
+} rt_light_rays;
+typedef struct rt_light_pdf_out {
+    double  *pdf;              /* count */
+    int32_t *light;            /* count; either may be NULL, not both */
+} rt_light_pdf_out;
+typedef struct rt_light_stats {
+    uint64_t points, valid;                 /* points sampled / rays looked up; valid samples / rays that meet a light */
+    double seconds;                         /* the kernel, HIP events */
+    uint32_t kernel_vgprs, scratch_bytes;   /* of the kernel that ran: registers, private memory per lane */
+} rt_light_stats;
+/* points and out hold device pointers (on params->device).  stats may be NULL: the call is then the launch and the wait alone. */
+RTOW_API int rt_scene_sample_lights_device(rt_scene *s, const rt_light_params *params, const rt_light_points *points,
+                                           const rt_light_samples *out, rt_light_stats *stats);
+/* the same on host arrays (uploaded, sampled, copied back) */
+RTOW_API int rt_scene_sample_lights(rt_scene *s, const rt_light_params *params, const rt_light_points *points, const rt_light_samples *out,
+                                    rt_light_stats *stats);
+RTOW_API int rt_scene_light_pdf_device(rt_scene *s, const rt_light_params *params, const rt_light_rays *rays, const rt_light_pdf_out *out,
+                                       rt_light_stats *stats);
+RTOW_API int rt_scene_light_pdf(rt_scene *s, const rt_light_params *params, const rt_light_rays *rays, const rt_light_pdf_out *out,
+                                rt_light_stats *stats);
+/* sizeof of rt_light_params, rt_light_points, rt_light_samples, rt_light_rays, rt_light_pdf_out, rt_light_stats, rt_light_row as
+ * this library was compiled, and kLightLdsRows: the rows of the light table the kernels stage on chip */
+RTOW_API void rt_light_abi_sizes(uint32_t out8[8]);
 
 /* Convenience: create film, upload, render 1 GPU, download.  frame = W*H*3 doubles. */
 RTOW_API int rt_render(rt_scene *s, const rt_render_params *params, double *frame, rt_render_stats *stats);

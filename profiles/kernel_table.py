@@ -49,6 +49,11 @@ for i, st in enumerate(idx[1:]):
                 name = 'advance_kernel world %s %s' % (m.group(2), 'strict' if int(m.group(1)) else 'fast')
                 others.append((name, int(cur['vgpr_count']), int(cur['private_segment_fixed_size']), int(cur['vgpr_spill_count']),
                                int(cur['group_segment_fixed_size'])))
+            m = re.search(r'(light_sample_kernel|light_pdf_kernel)ILi(\d)E', n)
+            if m:
+                name = '%s %s' % (m.group(1), 'strict' if int(m.group(2)) else 'fast')
+                others.append((name, int(cur['vgpr_count']), int(cur['private_segment_fixed_size']), int(cur['vgpr_spill_count']),
+                               int(cur['group_segment_fixed_size'])))
             m = re.search(r'(advance_scan_kernel|advance_gather_kernel)', n)
             if m:
                 others.append((m.group(1), int(cur['vgpr_count']), int(cur['private_segment_fixed_size']), int(cur['vgpr_spill_count']),

@@ -14,6 +14,7 @@ from .api import (  # noqa: F401
     RenderStats,
     LaunchPlan,
     builtin_scene,
+    scatter_pdf,
     stripe_rows,
     deinterleave,
     write_ppm,

@@ -135,6 +135,47 @@ class PathAdvanceStats(C.Structure):
                 ("scratch_bytes", C.c_uint32)]
 
 
+class LightParams(C.Structure):
+    _fields_ = [("count", C.c_int64), ("time", C.c_double), ("seed", C.c_uint64), ("first_sequence", C.c_uint64), ("strategy", C.c_int32),
+                ("variant", C.c_int32), ("device", C.c_int32), ("stream", C.c_void_p), ("reserved", C.c_int32 * 4)]
+
+
+class LightPoints(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("point", "normal", "material", "time", "rng_state")]
+
+
+# the outputs of a light sample in the order of rt_light_samples: name -> (numpy dtype, trailing shape)
+LIGHT_SAMPLE_OUTPUTS = {"direction": ("float64", (3,)), "distance": ("float64", ()), "light": ("int32", ()), "pdf": ("float64", ()),
+                        "emitted": ("float64", (3,)), "scatter_pdf": ("float64", ()), "contribution": ("float64", (3,)),
+                        "rng_state": ("uint32", (6,))}
+
+
+class LightSamples(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in LIGHT_SAMPLE_OUTPUTS]
+
+
+class LightRays(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("origin", "direction", "time")]
+
+
+LIGHT_PDF_OUTPUTS = {"pdf": ("float64", ()), "light": ("int32", ())}
+
+
+class LightPdfOut(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in LIGHT_PDF_OUTPUTS]
+
+
+class LightStats(C.Structure):
+    _fields_ = [("points", C.c_uint64), ("valid", C.c_uint64), ("seconds", C.c_double), ("kernel_vgprs", C.c_uint32),
+                ("scratch_bytes", C.c_uint32)]
+
+
+class LightRow(C.Structure):
+    """rt_light_row: one row of the light table, in world space (include/rtow.h rt_scene_dump_lights)."""
+    _fields_ = [("a", C.c_double * 3), ("b", C.c_double * 3), ("c", C.c_double * 3), ("n", C.c_double * 3), ("s", C.c_double),
+                ("kind", C.c_uint32), ("mat", C.c_uint32), ("leaf", C.c_uint32), ("pad0", C.c_uint32), ("pad1", C.c_double)]
+
+
 class LaunchPlan(C.Structure):
     """rt_launch_plan: what a launch decides (csrc/launch_plan.h); every scalar field but ray_budget is an int32."""
     _fields_ = [(n, C.c_uint32 if n == "ray_budget" else C.c_int32) for n in (
@@ -221,6 +262,7 @@ SIGNATURES = {
     "rt_scene_dump_camera": (I, [P, D3]),
     "rt_scene_dump_scan_segments": (I, [P, I, C.POINTER(C.c_uint32), C.POINTER(C.c_float)]),
     "rt_scene_dump_primary_lists": (I, [P, I, I, I, I, I, I, C.POINTER(C.c_uint16)]),
+    "rt_scene_dump_lights": (I, [P, I, C.POINTER(C.c_int), C.POINTER(C.c_int), P, D3]),
     "rt_stripe_rows": (I, [I, I, I, I, C.POINTER(C.c_int), I]),
     "rt_film_create": (P, [I, I, I, I, I, I]),
     "rt_film_destroy": (None, [P]),
@@ -256,6 +298,11 @@ SIGNATURES = {
     "rt_scene_path_advance": (I, [P, C.POINTER(PathAdvanceParams), C.POINTER(PathAdvanceRays), C.POINTER(PathAdvanceOut), C.POINTER(PathAdvanceStats)]),
     "rt_path_advance_workspace_bytes": (C.c_uint64, [C.c_int64]),
     "rt_path_advance_abi_sizes": (None, [C.POINTER(C.c_uint32)]),
+    "rt_scene_sample_lights_device": (I, [P, C.POINTER(LightParams), C.POINTER(LightPoints), C.POINTER(LightSamples), C.POINTER(LightStats)]),
+    "rt_scene_sample_lights": (I, [P, C.POINTER(LightParams), C.POINTER(LightPoints), C.POINTER(LightSamples), C.POINTER(LightStats)]),
+    "rt_scene_light_pdf_device": (I, [P, C.POINTER(LightParams), C.POINTER(LightRays), C.POINTER(LightPdfOut), C.POINTER(LightStats)]),
+    "rt_scene_light_pdf": (I, [P, C.POINTER(LightParams), C.POINTER(LightRays), C.POINTER(LightPdfOut), C.POINTER(LightStats)]),
+    "rt_light_abi_sizes": (None, [C.POINTER(C.c_uint32)]),
     "rt_deinterleave": (I, [D3, I, I, I, I, C.c_size_t, D3]),
     "rt_render": (I, [P, C.POINTER(RenderParams), D3, C.POINTER(RenderStats)]),
     "rt_write_ppm": (I, [C.c_char_p, D3, I, I]),
@@ -290,5 +337,17 @@ def load():
         ours = [C.sizeof(x) for x in structs]
         if list(sizes) != ours:
             raise ImportError(f"{LIB_PATH}: {what} structures are {list(sizes)} bytes in the library, {ours} in the binding")
+    sizes = (C.c_uint32 * 8)()
+    lib.rt_light_abi_sizes(sizes)
+    ours = [C.sizeof(x) for x in (LightParams, LightPoints, LightSamples, LightRays, LightPdfOut, LightStats, LightRow)]
+    if list(sizes)[:7] != ours:
+        raise ImportError(f"{LIB_PATH}: rt_light_* structures are {list(sizes)[:7]} bytes in the library, {ours} in the binding")
     _lib = lib
     return lib
+
+
+def light_lds_rows():
+    """kLightLdsRows: the rows of the light table the light kernels stage on chip (tests cover both sides of it)."""
+    sizes = (C.c_uint32 * 8)()
+    load().rt_light_abi_sizes(sizes)
+    return int(sizes[7])

@@ -12,7 +12,8 @@ import numbers
 import numpy as np
 
 from . import _lib
-from ._lib import (AdaptiveParams, DenoiseParams, FeatureParams, LaunchPlan, QueryHits, QueryParams, QueryRays, QueryStats,  # noqa: F401
+from ._lib import (AdaptiveParams, DenoiseParams, FeatureParams, LaunchPlan, LightParams, LightPdfOut, LightPoints, LightRays,  # noqa: F401
+                   LightSamples, LightStats, QueryHits, QueryParams, QueryRays, QueryStats,  # noqa: F401
                    PathAdvanceOut, PathAdvanceParams, PathAdvanceRays, PathAdvanceStats,
                    PathStepOut, PathStepParams, PathStepRays, PathStepStats, RadianceOut, RadianceParams, RadianceRays, RadianceStats,
                    RenderParams, RenderStats, SceneInfo)
@@ -232,7 +233,27 @@ class Scene:
         _check(lib().rt_scene_get_info(self._p, C.byref(out)))
         info = {n: getattr(out, n) for n, _ in SceneInfo._fields_ if n != "reserved"}
         info["n_triangles"] = out.reserved[0]  # the rows of n_quads that are triangles
+        info["n_lights"] = out.reserved[1]     # the rows of the light table (lights())
         return info
+
+    def lights(self):
+        """The light table (rt_scene_dump_lights; no device needed): every emissive world primitive in world space, in the
+        depth-first order of the world, as a dict of arrays with one entry per light -- "kind" (0 quad, 1 triangle, 2 sphere,
+        3 moving sphere), "leaf" (the world leaf, as ``intersect`` reports it), "material" (the material row), "a", "b", "c", "n"
+        ((n, 3) each) and "s" as include/rtow.h rt_light_row names them, and "cdf" (n, 2): the cumulative selection tables of
+        strategy 0 (uniform) and 1 (area x brightest channel), each ending at exactly 1.0."""
+        n = lib().rt_scene_dump_lights(self._p, 0, None, None, None, None)
+        if n < 0:
+            raise RtowError(_err())
+        rows = np.zeros(max(n, 1), dtype=np.dtype([("a", "f8", 3), ("b", "f8", 3), ("c", "f8", 3), ("n", "f8", 3), ("s", "f8"), ("kind", "u4"),
+                                                   ("mat", "u4"), ("leaf", "u4"), ("pad0", "u4"), ("pad1", "f8")]))
+        assert rows.dtype.itemsize == C.sizeof(_lib.LightRow)
+        cdf = np.ones((max(n, 1), 2), dtype=np.float64)
+        lib().rt_scene_dump_lights(self._p, n, None, None, rows.ctypes.data, cdf.ctypes.data_as(_lib.D3))
+        rows = rows[:n]
+        out = {name: np.ascontiguousarray(rows[name]) for name in ("a", "b", "c", "n", "s")}
+        out.update(kind=rows["kind"].astype(np.int32), leaf=rows["leaf"].astype(np.int32), material=rows["mat"].astype(np.int32), cdf=cdf[:n])
+        return out
 
     def dump_leaves(self):
         n = lib().rt_scene_dump_leaves(self._p, 0, None, None)
@@ -308,12 +329,14 @@ class Scene:
         _check(lib().rt_scene_upload(self._p, device))
 
     # ---- caller-supplied rays: the engine under the ray queries, the radiance queries and the path steps ----
-    def _ray_batch(self, kind, origins, directions, inputs, outputs, want, calls, structs, stats, device):
+    def _ray_batch(self, kind, origins, directions, inputs, outputs, want, calls, structs, stats, device, points_only=False, into=None):
         """One batch of rays through a pair of library entry points, ``calls`` = (on host arrays, on device arrays): numpy arrays
         take the first, torch CUDA tensors the second, in place and on the current stream.  ``inputs``: the optional per-ray arrays as
         (name, value, tail shape, dtype names, scalar_ok); None, or a scalar where ``scalar_ok``, leaves the name to the call's
         parameters.  ``outputs``: the library's table {name: (dtype name, tail shape)} (_lib.*_OUTPUTS), of which ``want`` names
-        those to return.  ``structs(count, rays, outs, device, stream)`` builds the call's three ctypes structs from the addresses
+        those to return (``into``: {name: the caller's own array for that output}, checked like an input; the others are
+        allocated here).  ``points_only``: the batch has no directions (light samples).
+        ``structs(count, rays, outs, device, stream)`` builds the call's three ctypes structs from the addresses
         of the arrays given and wanted; ``stats``: the statistics struct's type, or None.  Returns ({name: output[:count]}, stats)."""
         on_gpu = type(origins).__module__.split(".")[0] == "torch"
         if on_gpu:
@@ -337,7 +360,7 @@ class Scene:
             raise RtowError("origins: torch tensors must live on the GPU (numpy arrays take the host call)")
         arrays = {"origins": ray_array("origins", origins, (3,))}
         count = int(origins.shape[0])
-        for name, a, tail, dtypes, scalar_ok in [("directions", directions, (3,), ("float64",), False)] + list(inputs):
+        for name, a, tail, dtypes, scalar_ok in ([] if points_only else [("directions", directions, (3,), ("float64",), False)]) + list(inputs):
             if name != "directions" and (a is None or (scalar_ok and (isinstance(a, numbers.Real) or (isinstance(a, np.ndarray) and a.ndim == 0)))):
                 continue   # one value for all rays (a Python or numpy scalar), or none: the call's parameters
             arrays[name] = ray_array(name, a, tail, dtypes)
@@ -354,7 +377,11 @@ class Scene:
         for name in want:
             dtype, tail = outputs[name]
             shape = (max(count, 1),) + tail   # (never an empty allocation: its address may be null)
-            if on_gpu:   # (an output that continues an input, rng_state, has the input's dtype)
+            if into and into.get(name) is not None:
+                out[name] = ray_array(name + " (output)", into[name], tail, (dtype, "int32") if dtype == "uint32" else (dtype,))
+                if int(out[name].shape[0]) != count or count == 0:
+                    raise RtowError(f"{name} (output): {count} entries are required (and at least one)")
+            elif on_gpu:   # (an output that continues an input, rng_state, has the input's dtype)
                 out[name] = torch.empty(shape, dtype=arrays[name].dtype if name in arrays else getattr(torch, dtype), device=origins.device)
             else:
                 out[name] = np.empty(shape, dtype=dtype)
@@ -505,6 +532,62 @@ class Scene:
         out = {name: out[name][:survivors] for name in wanted}
         return (out, st) if stats else out
 
+    # ---- light sampling queries (include/rtow.h rt_scene_sample_lights, rt_scene_light_pdf) ----
+    def sample_lights(self, points, normals=None, materials=None, times=None, rng_state=None, strategy=0, want=None, time=0.0, seed=1984,
+                      first_sequence=0, variant=0, device=0, stats=False, out=None):
+        """One sample of the scene's emitters (``lights()``) for every point ``points[k]`` ((count, 3) float64), for next-event
+        estimation beside ``path_step`` and ``occluded``: a light picked by ``strategy`` (0 uniform, 1 by area x brightness), a
+        point on it -- uniform over a quad or triangle, uniform over the cone a sphere subtends -- and the solid-angle density of
+        doing so (include/rtow.h rt_scene_sample_lights states every operation).  ``normals`` (count, 3) float64 and ``materials``
+        (count,) uint8, as ``path_step`` returns them, are needed for "scatter_pdf" and "contribution"; ``times`` (count,) or ``time``
+        place moving spheres; ``rng_state`` as for ``path_step`` (None: point k draws from ``curand_init(seed, k + first_sequence,
+        0)``).  Returns a dict of the outputs named in ``want`` (default: all that the inputs allow): "direction" (count, 3), unit;
+        "distance"; "light" int32, -1 without lights; "pdf", 0 for an invalid sample; "emitted" (count, 3); "scatter_pdf";
+        "contribution" (count, 3) = emitted * scatter_pdf / pdf; "rng_state" (count, 6).  Visibility is the caller's:
+        ``occluded(*shadow_rays(points, direction, distance))``.  ``out``: {name: an array of the caller's to write that output into}
+        -- "rng_state" may be the input array.  numpy arrays take the host call; torch CUDA tensors are read in place, on
+        ``torch.cuda.current_stream()``.  ``stats=True``: (outputs, LightStats)."""
+        if want is None:
+            want = ("direction", "distance", "light", "pdf", "emitted", "rng_state") + \
+                (("scatter_pdf", "contribution") if normals is not None and materials is not None else ())
+
+        def structs(count, rays, outs, device, stream):
+            if not outs:
+                raise RtowError("want: at least one of " + ", ".join(_lib.LIGHT_SAMPLE_OUTPUTS))
+            p = LightParams(count, float(time), int(seed), int(first_sequence), int(strategy), int(variant), device, stream)
+            return p, LightPoints(*(rays.get(n) for n in ("origins", "normals", "materials", "times", "rng_state"))), LightSamples(**outs)
+
+        inputs = [("normals", normals, (3,), ("float64",), False), ("materials", materials, (), ("uint8",), False),
+                  ("times", times, (), ("float64",), False), ("rng_state", rng_state, (6,), ("uint32", "int32"), False)]
+        res, st = self._ray_batch("light sample", points, None, inputs, _lib.LIGHT_SAMPLE_OUTPUTS, tuple(want),
+                                  (lib().rt_scene_sample_lights, lib().rt_scene_sample_lights_device), structs, LightStats if stats else None, device,
+                                  points_only=True, into=out)
+        return (res, st) if stats else res
+
+    def light_pdf(self, origins, directions, times=None, strategy=0, want=("pdf",), time=0.0, variant=0, device=0, stats=False):
+        """The density with which ``sample_lights`` at ``origins[k]`` produces the direction ``directions[k]`` (both (count, 3)
+        float64; the direction need not be unit): the sum over all lights the ray meets of that light's density times its chance
+        under ``strategy`` -- the other half of multiple importance sampling, for a scattered ray that finds a lamp.  "light": the
+        nearest light met, -1 for none (then "pdf" is 0).  Nothing is drawn.  Arrays as for ``sample_lights``."""
+        def structs(count, rays, outs, device, stream):
+            if not outs:
+                raise RtowError("want: at least one of " + ", ".join(_lib.LIGHT_PDF_OUTPUTS))
+            p = LightParams(count, float(time), 0, 0, int(strategy), int(variant), device, stream)
+            return p, LightRays(*(rays.get(n) for n in ("origins", "directions", "times"))), LightPdfOut(**outs)
+
+        inputs = [("times", times, (), ("float64",), False)]
+        res, st = self._ray_batch("light pdf", origins, directions, inputs, _lib.LIGHT_PDF_OUTPUTS, tuple(want),
+                                  (lib().rt_scene_light_pdf, lib().rt_scene_light_pdf_device), structs, LightStats if stats else None, device)
+        return (res, st) if stats else res
+
+    @staticmethod
+    def shadow_rays(points, directions, distances, times=None):
+        """The arguments of ``occluded`` for shadow rays towards light samples: ``(points, directions, times, tmin, tmax)`` with
+        ``(tmin, tmax) = (0.001, distances * (1 - 2**-20))``.  The rays run along the unit ``directions``, so t is the distance: the
+        interval begins where the renderer's own rays begin and ends 2^-20 of the distance short of the lamp -- far above the
+        rounding of the sample (a few 2^-52 of it), far below anything a scene resolves.  A stated rule, not a measurement."""
+        return points, directions, times, 0.001, distances * (1.0 - 2.0 ** -20)
+
     # ---- one-call render on one GPU ----
     def render(self, width, height, spp, max_depth=50, seed=1984, variant=0, device=0, flags=0, coop_threshold=0,
                overdue=0, shade_batch=0, max_blocks_per_cu=0, pixels_per_wave=0, adaptive=None):
@@ -651,6 +734,23 @@ class PathBatch:
             if check_every > 0 and done < max_depth:
                 capacity = self.live()
         return self.radiance
+
+
+def scatter_pdf(materials, normals, directions):
+    """The solid-angle density with which the renderer's own ``Material::Scatter`` sends a ray from a surface of unit shading
+    normal ``normals[k]`` and material kind ``materials[k]`` (as ``intersect`` and ``path_step`` report it) into the unit direction
+    ``directions[k]`` -- the closed forms of include/rtow.h rt_scene_sample_lights, for numpy arrays and torch tensors alike:
+    Lambertian (0): ``2 cos^3 / pi`` for ``cos = n . d > 0``, else 0 -- the exact density of ``n + uniform point of the unit ball``
+    (R/Material.h:67-82; a chord of length ``2 cos`` through a ball of volume ``4 pi / 3``), which is not a cosine lobe;
+    isotropic (4): ``1 / (4 pi)``; metal, dielectric, diffuse light and a miss (255): 0, they are treated as specular."""
+    pi = 3.1415926535897932385
+    c = (normals[..., 0] * directions[..., 0] + normals[..., 1] * directions[..., 1]) + normals[..., 2] * directions[..., 2]
+    xp = np
+    if type(c).__module__.split(".")[0] == "torch":
+        import torch as xp
+    zero = xp.zeros_like(c)
+    lambertian = xp.where(c > 0, (2.0 * ((c * c) * c)) / pi, zero)
+    return xp.where(materials == 0, lambertian, xp.where(materials == 4, zero + 1.0 / (4.0 * pi), zero))
 
 
 def builtin_scene(scene_id, world_kind, width, height, seed=1984, earth=None):

@@ -39,6 +39,10 @@ struct DeviceTables {
     DeviceArena memory;       // every table below
     DeviceScene scene{};
     const uint32_t *node_leaf_pos = nullptr;  // ray queries (rt_scene_intersect_device): FlatScene::node_leaf_pos
+    // light sampling queries (rt_scene_sample_lights_device): FlatScene::lights and its two cumulative tables
+    const LightRow *lights = nullptr;
+    const double *light_cdf[2] = {nullptr, nullptr};
+    uint32_t n_lights = 0;
     // path advances without statistics return before their kernels have run (rt_scene_path_advance_device): recorded behind the
     // last of them, created by the first
     hipEvent_t advance_done = nullptr;
@@ -386,6 +390,10 @@ int rt_scene_upload(rt_scene *scene, int device)
     up(f.seg_cand, d.seg_cand);
     up(f.world_items, d.world_items);
     up(f.node_leaf_pos, dt->node_leaf_pos);
+    up(f.lights, dt->lights);
+    up(f.light_cdf[0], dt->light_cdf[0]);
+    up(f.light_cdf[1], dt->light_cdf[1]);
+    dt->n_lights = (uint32_t)f.lights.size();
     up(f.materials, d.materials);
     up(f.textures, d.textures);
     up(f.images, d.images);
@@ -487,12 +495,14 @@ struct Build {
     hipError_t (*radiance)(const DeviceScene &, const RadianceArgs &, hipStream_t, QueryKernelInfo *);
     hipError_t (*step)(const DeviceScene &, const StepArgs &, hipStream_t, QueryKernelInfo *);
     hipError_t (*advance)(const DeviceScene &, const AdvanceArgs &, hipStream_t, QueryKernelInfo *);
+    hipError_t (*light_sample)(const DeviceScene &, const LightArgs &, hipStream_t, QueryKernelInfo *);
+    hipError_t (*light_pdf)(const DeviceScene &, const LightArgs &, hipStream_t, QueryKernelInfo *);
 };
 static const Build kBuilds[2] = {
     {launch_seed_strict, launch_render_strict, kernel_info_strict, launch_adaptive_rule_strict, launch_features_strict, launch_query_strict,
-     launch_radiance_strict, launch_step_strict, launch_advance_strict},
+     launch_radiance_strict, launch_step_strict, launch_advance_strict, launch_light_sample_strict, launch_light_pdf_strict},
     {launch_seed_fast, launch_render_fast, kernel_info_fast, launch_adaptive_rule_fast, launch_features_fast, launch_query_fast,
-     launch_radiance_fast, launch_step_fast, launch_advance_fast}};
+     launch_radiance_fast, launch_step_fast, launch_advance_fast, launch_light_sample_fast, launch_light_pdf_fast}};
 
 static int seed_film(FilmImpl &f, const rt_render_params *p, hipStream_t stream)
 {
@@ -1348,6 +1358,163 @@ void rt_path_step_abi_sizes(uint32_t out4[4])
     out4[1] = (uint32_t)sizeof(rt_path_step_rays);
     out4[2] = (uint32_t)sizeof(rt_path_step_out);
     out4[3] = (uint32_t)sizeof(rt_path_step_stats);
+}
+
+// ---- light sampling queries ----
+// everything that can be refused without a device, in the order include/rtow.h lists it
+static int light_check(rt_scene *scene, const rt_light_params *p, const void *in, const void *out, const std::string &name)
+{
+    if (!scene || !p || !in || !out) return fail(RT_ERR_INVALID, name + ": null argument");
+    if (!S(scene)->committed) return fail(RT_ERR_STATE, name + ": scene not committed (rt_scene_commit)");
+    if (p->count < 0 || p->count > ((int64_t)1 << 30)) return fail(RT_ERR_INVALID, name + ": count must be 0 .. 2^30");
+    if (p->strategy != 0 && p->strategy != 1) return fail(RT_ERR_INVALID, name + ": strategy must be 0 (uniform) or 1 (by area and brightness)");
+    if (p->variant != 0 && p->variant != 1) return fail(RT_ERR_INVALID, name + ": variant must be 0 (strict) or 1 (fast)");
+    return RT_OK;
+}
+static int light_sample_check(rt_scene *scene, const rt_light_params *p, const rt_light_points *pts, const rt_light_samples *out, const char *who)
+{
+    const std::string name(who);
+    if (int rc = light_check(scene, p, pts, out, name)) return rc;
+    if (p->count > 0 && !pts->point) return fail(RT_ERR_INVALID, name + ": null point");
+    if (!out->direction && !out->distance && !out->light && !out->pdf && !out->emitted && !out->scatter_pdf && !out->contribution && !out->rng_state)
+        return fail(RT_ERR_INVALID, name + ": every output is null");
+    if ((out->scatter_pdf || out->contribution) && (!pts->normal || !pts->material))
+        return fail(RT_ERR_INVALID, name + ": scatter_pdf and contribution need normal and material");
+    return RT_OK;
+}
+static int light_pdf_check(rt_scene *scene, const rt_light_params *p, const rt_light_rays *rays, const rt_light_pdf_out *out, const char *who)
+{
+    const std::string name(who);
+    if (int rc = light_check(scene, p, rays, out, name)) return rc;
+    if (p->count > 0 && (!rays->origin || !rays->direction)) return fail(RT_ERR_INVALID, name + ": null origin or direction");
+    if (!out->pdf && !out->light) return fail(RT_ERR_INVALID, name + ": every output is null");
+    return RT_OK;
+}
+
+// the arguments both kernels share, and the run: `la` holds the caller's arrays already
+static int run_light_kernel(rt_scene *scene, const rt_light_params *p, LightArgs &la, bool pdf_mode, const char *who, rt_light_stats *stats)
+{
+    SceneImpl &s = *S(scene);
+    if (int rc = rt_scene_upload(scene, p->device)) return rc;  // (selects the device)
+    DeviceTables &dt = *s.device[p->device];
+    la.rows = dt.lights;
+    la.cdf = dt.light_cdf[p->strategy];
+    la.n_lights = dt.n_lights;
+    la.time_all = p->time;
+    if (int rc = device_jump_table(p->device, &la.jump_table)) return rc;
+    la.base = xorwow_seed(p->seed, kSaltCurandDevice);
+    la.first_sequence = p->first_sequence;
+    la.count = (uint32_t)p->count;
+    // (la by reference: run_lane_kernel sets la.valid_counter between the launch that reports and the one that runs)
+    const auto launch = [&](hipStream_t stream, QueryKernelInfo *info) {
+        return pdf_mode ? kBuilds[p->variant].light_pdf(dt.scene, la, stream, info) : kBuilds[p->variant].light_sample(dt.scene, la, stream, info);
+    };
+    unsigned long long valid = 0;
+    if (int rc = run_lane_kernel(launch, &la.valid_counter, p->device, (hipStream_t)p->stream, who, stats, &valid)) return rc;
+    if (stats) {
+        stats->points = (uint64_t)p->count;
+        stats->valid = valid;
+    }
+    return RT_OK;
+}
+
+int rt_scene_sample_lights_device(rt_scene *scene, const rt_light_params *p, const rt_light_points *pts, const rt_light_samples *out,
+                                  rt_light_stats *stats)
+{
+    if (int rc = light_sample_check(scene, p, pts, out, "rt_scene_sample_lights_device")) return rc;
+    if (stats) *stats = rt_light_stats{};
+    if (p->count == 0) return RT_OK;
+    LightArgs la{};
+    la.point = pts->point;
+    la.normal = pts->normal;
+    la.material = pts->material;
+    la.time = pts->time;
+    la.rng_in = pts->rng_state;
+    la.direction = out->direction;
+    la.distance = out->distance;
+    la.light = out->light;
+    la.pdf = out->pdf;
+    la.emitted = out->emitted;
+    la.scatter_pdf = out->scatter_pdf;
+    la.contribution = out->contribution;
+    la.rng_out = out->rng_state;
+    return run_light_kernel(scene, p, la, false, "rt_scene_sample_lights_device", stats);
+}
+
+int rt_scene_sample_lights(rt_scene *scene, const rt_light_params *p, const rt_light_points *pts, const rt_light_samples *out, rt_light_stats *stats)
+{
+    if (int rc = light_sample_check(scene, p, pts, out, "rt_scene_sample_lights")) return rc;
+    if (stats) *stats = rt_light_stats{};
+    if (p->count == 0) return RT_OK;
+    if (int rc = select_device(p->device)) return rc;
+    Staging stage{DeviceArena(p->device), (size_t)p->count, {}};
+    rt_light_points dp_in{};
+    HIP_TRY(stage.in(pts->point, 3, dp_in.point));
+    HIP_TRY(stage.in(pts->normal, 3, dp_in.normal));
+    HIP_TRY(stage.in(pts->material, 1, dp_in.material));
+    HIP_TRY(stage.in(pts->time, 1, dp_in.time));
+    HIP_TRY(stage.in(pts->rng_state, 6, dp_in.rng_state));
+    rt_light_samples dout{};
+    HIP_TRY(stage.out(out->direction, 3, dout.direction));
+    HIP_TRY(stage.out(out->distance, 1, dout.distance));
+    HIP_TRY(stage.out(out->light, 1, dout.light));
+    HIP_TRY(stage.out(out->pdf, 1, dout.pdf));
+    HIP_TRY(stage.out(out->emitted, 3, dout.emitted));
+    HIP_TRY(stage.out(out->scatter_pdf, 1, dout.scatter_pdf));
+    HIP_TRY(stage.out(out->contribution, 3, dout.contribution));
+    HIP_TRY(stage.out(out->rng_state, 6, dout.rng_state));
+    rt_light_params dp = *p;
+    dp.stream = nullptr;  // the copies around the call are synchronous: nothing to order on the caller's stream
+    if (int rc = rt_scene_sample_lights_device(scene, &dp, &dp_in, &dout, stats)) return rc;
+    HIP_TRY(stage.fetch());
+    return RT_OK;
+}
+
+int rt_scene_light_pdf_device(rt_scene *scene, const rt_light_params *p, const rt_light_rays *rays, const rt_light_pdf_out *out, rt_light_stats *stats)
+{
+    if (int rc = light_pdf_check(scene, p, rays, out, "rt_scene_light_pdf_device")) return rc;
+    if (stats) *stats = rt_light_stats{};
+    if (p->count == 0) return RT_OK;
+    LightArgs la{};
+    la.point = rays->origin;
+    la.direction_in = rays->direction;
+    la.time = rays->time;
+    la.pdf = out->pdf;
+    la.light = out->light;
+    return run_light_kernel(scene, p, la, true, "rt_scene_light_pdf_device", stats);
+}
+
+int rt_scene_light_pdf(rt_scene *scene, const rt_light_params *p, const rt_light_rays *rays, const rt_light_pdf_out *out, rt_light_stats *stats)
+{
+    if (int rc = light_pdf_check(scene, p, rays, out, "rt_scene_light_pdf")) return rc;
+    if (stats) *stats = rt_light_stats{};
+    if (p->count == 0) return RT_OK;
+    if (int rc = select_device(p->device)) return rc;
+    Staging stage{DeviceArena(p->device), (size_t)p->count, {}};
+    rt_light_rays dr{};
+    HIP_TRY(stage.in(rays->origin, 3, dr.origin));
+    HIP_TRY(stage.in(rays->direction, 3, dr.direction));
+    HIP_TRY(stage.in(rays->time, 1, dr.time));
+    rt_light_pdf_out dout{};
+    HIP_TRY(stage.out(out->pdf, 1, dout.pdf));
+    HIP_TRY(stage.out(out->light, 1, dout.light));
+    rt_light_params dp = *p;
+    dp.stream = nullptr;
+    if (int rc = rt_scene_light_pdf_device(scene, &dp, &dr, &dout, stats)) return rc;
+    HIP_TRY(stage.fetch());
+    return RT_OK;
+}
+
+void rt_light_abi_sizes(uint32_t out8[8])
+{
+    out8[0] = (uint32_t)sizeof(rt_light_params);
+    out8[1] = (uint32_t)sizeof(rt_light_points);
+    out8[2] = (uint32_t)sizeof(rt_light_samples);
+    out8[3] = (uint32_t)sizeof(rt_light_rays);
+    out8[4] = (uint32_t)sizeof(rt_light_pdf_out);
+    out8[5] = (uint32_t)sizeof(rt_light_stats);
+    out8[6] = (uint32_t)sizeof(rt_light_row);
+    out8[7] = kLightLdsRows;
 }
 
 // ---- path advances ----

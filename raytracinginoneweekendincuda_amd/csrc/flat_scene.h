@@ -198,6 +198,28 @@ struct TextureRec { double r, g, b, s; uint32_t kind, a, b_, pad; };
 struct ImageRec { uint64_t offset; int32_t width, height; };
 struct PerlinRec { double vec[256][3]; int32_t perm_x[256], perm_y[256], perm_z[256]; };  // R/Perlin.h:82-85
 
+// Light table (rt_scene_sample_lights, rt_scene_light_pdf): one row per emissive world primitive, in WORLD space -- the chain of
+// Translate / RotateY above the primitive applied on the host (scene_builder.cpp collect_lights), so that the light kernels need
+// neither the object records nor the transforms.  128 bytes, the layout of rt_light_row in include/rtow.h:
+//   quad, triangle   a = Q, b = u, c = v, n = the unit normal, s = the area
+//   sphere           a = the centre, s = the radius
+//   moving sphere    a = c0, b = dc, c = (t0, dt, 0), s = the radius; the centre at time t is MSphereGeom's c0 + ((t - t0) / dt) * dc
+// Not a member of DeviceScene: the light kernels get the table through LightArgs (render_iface.h).
+enum : uint32_t { LIGHT_QUAD = 0u, LIGHT_TRIANGLE = 1u, LIGHT_SPHERE = 2u, LIGHT_MSPHERE = 3u };
+struct LightRow {
+    double a[3], b[3], c[3], n[3], s;
+    uint32_t kind;  // LIGHT_*
+    uint32_t mat;   // row of materials[]
+    uint32_t leaf;  // position of the world leaf it belongs to, in rt_scene_dump_leaves order
+    uint32_t pad0;
+    double pad1;
+};
+static_assert(sizeof(LightRow) == 128, "eight 16-byte loads a row");
+// Rows a workgroup of the light kernels stages in LDS, with their entries of the cumulative table of the call's strategy (a call
+// has one strategy: the other table's column would be staged to be left unread): 256 * (128 + 8) bytes = 34 KB a workgroup, so four
+// workgroups (136 KB) still fit a CU's 160 KB.  Rows beyond the cap are read from global memory.  Even: the staging loads pairs.
+constexpr uint32_t kLightLdsRows = 256;
+
 // Camera (R/Camera.h:92-101)
 struct CameraRec {
     double bg[3], origin[3], llc[3], horizontal[3], vertical[3], u[3], v[3], w[3];

@@ -220,6 +220,7 @@ int main(int argc, char **argv)
     int pick_i = 0, pick_j = 0;
     bool radiance_at = false;    // --radiance-at i,j: the light that comes back along the centre ray of that pixel, one line, no render
     bool trace_at = false;       // --trace-at i,j: that path vertex by vertex (rt_scene_path_step), then --radiance-at's line
+    bool list_lights = false;    // --lights: the scene's light table (rt_scene_dump_lights), a line per light, no render
     for (int k = 1; k < argc; k++) {
         std::string a = argv[k];
         auto val = [&](const char *name) -> const char * {
@@ -258,6 +259,7 @@ int main(int argc, char **argv)
             adaptive_option = true;
         }
         else if (a == "--denoise") denoise = true;
+        else if (a == "--lights") list_lights = true;
         else if (const char *v = val("--denoise-iterations")) {
             dp.iterations = std::atoi(v);
             denoise_option = true;
@@ -304,7 +306,9 @@ int main(int argc, char **argv)
                          "            [--earth earthmap.jpg|decoded.ppm | --earth-bytes texture.ppm] [--accelerate-lists] [--flags N]\n"
                          "            [--noise T [--min-spp N] [--check-every K] [--samples-map file.pgm]]\n"
                          "            [--denoise [--denoise-iterations N] [--denoise-sigmas c,a,n,z] [--raw-output file.ppm]]\n"
-                         "            [--aov-prefix P] [--feature-samples N] [--pick i,j] [--radiance-at i,j] [--trace-at i,j]\n"
+                         "            [--aov-prefix P] [--feature-samples N] [--pick i,j] [--radiance-at i,j] [--trace-at i,j] [--lights]\n"
+                         "  --lights       render nothing: print the light table (rt_scene_dump_lights), a line per emissive primitive in world space --\n"
+                         "                 kind, world leaf, material row, geometry, and its entries of the two cumulative selection tables\n"
                          "  --pick         render nothing: print what the ray through the centre of pixel (i, j) hits (j = 0 is the bottom row) --\n"
                          "                 leaf, material kind, t, point, normal, albedo -- at the shutter's opening, over [0.001, inf)\n"
                          "  --radiance-at  render nothing: path-trace the same ray, --spp samples (default 1) of --depth bounces from the pixel's stream,\n"
@@ -370,7 +374,7 @@ int main(int argc, char **argv)
         std::fprintf(stderr, "%s: pixel (%d, %d) is outside the %dx%d frame\n", trace_at ? "--trace-at" : radiance_at ? "--radiance-at" : "--pick", pick_i, pick_j, width, height);
         return 2;
     }
-    if (!pick) std::fprintf(stderr, "Rendering a %dx%d image with %d samples per pixel in 8x8 blocks.\n", width, height, spp);
+    if (!pick && !list_lights) std::fprintf(stderr, "Rendering a %dx%d image with %d samples per pixel in 8x8 blocks.\n", width, height, spp);
     rt_scene *scene = rt_scene_create();
     // R/kernel.cu:656-665: scenes 2 and 9 load earthmap.jpg through stb_image.  This executable carries no JPEG decoder:
     // the decoded pixels come in as a PPM (--earth / --earth-bytes; ./earthmap.ppm is picked up like the reference picks
@@ -414,6 +418,30 @@ int main(int argc, char **argv)
     if (rt_scene_build_builtin(scene, scene_id, world_kind, width, height, seed, earth.empty() ? nullptr : earth.data(), earth_w,
                                earth_h) != RT_OK)
         return die("scene");
+
+    if (list_lights) {  // host only: the table as rt_scene_upload would copy it
+        const int n = rt_scene_dump_lights(scene, 0, nullptr, nullptr, nullptr, nullptr);
+        if (n < 0) return die("lights");
+        std::vector<rt_light_row> rows((size_t)n + 1);
+        std::vector<double> cdf(2 * (size_t)n + 2);
+        rt_scene_dump_lights(scene, n, nullptr, nullptr, rows.data(), cdf.data());
+        static const char *const names[] = {"quad", "triangle", "sphere", "moving_sphere"};
+        std::printf("%d lights\n", n);
+        for (int k = 0; k < n; k++) {
+            const rt_light_row &r = rows[(size_t)k];
+            std::printf("%d %s leaf %u material %u", k, names[r.kind & 3u], r.leaf, r.mat);
+            if (r.kind <= 1)
+                std::printf(" Q %.17g %.17g %.17g u %.17g %.17g %.17g v %.17g %.17g %.17g n %.17g %.17g %.17g area %.17g", r.a[0], r.a[1], r.a[2],
+                            r.b[0], r.b[1], r.b[2], r.c[0], r.c[1], r.c[2], r.n[0], r.n[1], r.n[2], r.s);
+            else if (r.kind == 2) std::printf(" centre %.17g %.17g %.17g radius %.17g", r.a[0], r.a[1], r.a[2], r.s);
+            else
+                std::printf(" c0 %.17g %.17g %.17g dc %.17g %.17g %.17g t0 %.17g dt %.17g radius %.17g", r.a[0], r.a[1], r.a[2], r.b[0], r.b[1],
+                            r.b[2], r.c[0], r.c[1], r.s);
+            std::printf(" cdf %.17g %.17g\n", cdf[2 * (size_t)k], cdf[2 * (size_t)k + 1]);
+        }
+        rt_scene_destroy(scene);
+        return 0;
+    }
 
     if (pick) {  // one closest-hit query (rt_scene_intersect) for the pixel's centre ray as the feature pass builds it
         double cam[27];  // bg, origin, lower-left corner, horizontal, vertical, u, v, w, lens radius, time0, time1

@@ -59,6 +59,9 @@
 #ifndef RT_ADVANCE  // 1: this translation unit holds the path-advance kernels (advance_kernel) and nothing else
 #define RT_ADVANCE 0
 #endif
+#ifndef RT_LIGHTS  // 1: this translation unit holds the light sampling kernels (light_sample_kernel, light_pdf_kernel) and nothing else
+#define RT_LIGHTS 0
+#endif
 
 namespace rtow {
 namespace {
@@ -461,7 +464,7 @@ DEV bool prim_test(const DeviceScene &sc, uint32_t ref, const Ray &r, double a, 
 #ifndef RT_PHASES
 #define RT_PHASES 0  // diagnostic build: per-phase wave cycles and lane occupancy, summed into ray_counter[7] and [32..119]
 #endif
-#if RT_PHASES && (RT_FEATURES || RT_QUERY || RT_RADIANCE || RT_STEP || RT_ADVANCE)
+#if RT_PHASES && (RT_FEATURES || RT_QUERY || RT_RADIANCE || RT_STEP || RT_ADVANCE || RT_LIGHTS)
 #undef RT_PHASES
 #define RT_PHASES 0  // the phases are render_kernel's: the feature and query units of a diagnostic build are the ordinary ones
 #endif
@@ -4245,10 +4248,11 @@ hipError_t RT_CAT(launch_composite_, RT_SUFFIX)(int which, const DeviceScene &sc
 hipError_t RT_CAT(launch_adaptive_prims_, RT_SUFFIX)(int which, const DeviceScene &sc, const RenderArgs &a, hipStream_t stream, KernelInfo *info);
 hipError_t RT_CAT(launch_adaptive_composite_, RT_SUFFIX)(int which, const DeviceScene &sc, const RenderArgs &a, hipStream_t stream, KernelInfo *info);
 
-#if RT_FEATURES || RT_QUERY || RT_RADIANCE || RT_STEP || RT_ADVANCE
+#if RT_FEATURES || RT_QUERY || RT_RADIANCE || RT_STEP || RT_ADVANCE || RT_LIGHTS
 // ------------------------------------------------------------------------------------------------
-// Shared by the five lane-per-ray sections below (first-hit features, ray queries, radiance queries, path steps, path advances): one lane
-// per pixel or per caller-supplied ray, no persistent waves, no LDS staging.  The next kernel of this family starts from these.
+// Shared by the six lane-per-ray sections below (first-hit features, ray queries, radiance queries, path steps, path advances, light
+// sampling): one lane per pixel or per caller-supplied ray or point, no persistent waves; only the light kernels stage anything in
+// LDS (their own table).  The next kernel of this family starts from these.
 // ------------------------------------------------------------------------------------------------
 namespace {
 // every table from global memory: a kernel of this family calls this first
@@ -4884,6 +4888,279 @@ hipError_t RT_CAT(launch_advance_, RT_SUFFIX)(const DeviceScene &sc, const Advan
     void (*kernel)(DeviceScene, AdvanceArgs) =
         sc.world_kind == WORLD_BVH ? advance_kernel<RT_STRICT, TBvhNested> : advance_kernel<RT_STRICT, TListNested>;
     return info_or_launch(kernel, sc, a, a.capacity, stream, info);
+}
+#elif RT_LIGHTS
+// ------------------------------------------------------------------------------------------------
+// Light sampling queries (rt_scene_sample_lights, rt_scene_light_pdf; include/rtow.h states both operation by operation, and
+// tests/light_restated.py restates the strict build to the bit).  One lane per point or ray, the callers' arrays read and written
+// coalesced.  The light table comes through LightArgs, in world space: no object records, no transforms, no search of the world.
+// A workgroup first stages the first kLightLdsRows rows and their entries of the call's cumulative table in LDS with 16-byte
+// loads; rows beyond the cap come from global memory.  light_sample_kernel reads one row per lane (whichever its draw picked);
+// light_pdf_kernel loops over all rows wave-uniformly, every lane on the same row -- an LDS broadcast -- which is the count x
+// n_lights loop the staging is for.  No lane returns early (all meet at the barriers), no wave waits for another workgroup; the
+// count of valid results reduces per wave, then per workgroup, then one atomic.
+// ------------------------------------------------------------------------------------------------
+namespace {
+constexpr double kLightPi = 3.1415926535897932385;
+constexpr uint32_t kLightRowDoubles = (uint32_t)(sizeof(LightRow) / sizeof(double));
+static_assert(kLightLdsRows % 2 == 0 && sizeof(LightRow) % 16 == 0, "whole 16-byte loads");
+
+struct LightLds {
+    const double *rows, *cdf;  // the workgroup's copies
+};
+DEV void stage_lights(const LightArgs &a, double *rows_lds, double *cdf_lds)
+{
+    const uint32_t n = min(a.n_lights, kLightLdsRows);
+    const double2 *src = reinterpret_cast<const double2 *>(a.rows);
+    double2 *dst = reinterpret_cast<double2 *>(rows_lds);
+    for (uint32_t i = threadIdx.x; i < n * (kLightRowDoubles / 2u); i += 256u) dst[i] = src[i];
+    // (the table is padded to an even length, and kLightLdsRows is even: the last pair is in bounds on both sides)
+    const double2 *csrc = reinterpret_cast<const double2 *>(a.cdf);
+    double2 *cdst = reinterpret_cast<double2 *>(cdf_lds);
+    for (uint32_t i = threadIdx.x; i < (n + 1u) / 2u; i += 256u) cdst[i] = csrc[i];
+    __syncthreads();
+}
+DEV LightRow light_row(const LightArgs &a, const LightLds &lds, uint32_t i)
+{
+    if (i < kLightLdsRows) return *reinterpret_cast<const LightRow *>(lds.rows + (size_t)i * kLightRowDoubles);
+    return a.rows[i];
+}
+DEV double light_cdf(const LightArgs &a, const LightLds &lds, uint32_t i) { return i < kLightLdsRows ? lds.cdf[i] : a.cdf[i]; }
+DEV Vec load3(const double *p) { return mk(p[0], p[1], p[2]); }
+DEV Vec light_centre(const LightRow &L, double tm)  // MSphereGeom's formula for a moving sphere
+{
+    if (L.kind == LIGHT_MSPHERE) return load3(L.a) + ((tm - L.c[0]) / L.c[1]) * load3(L.b);
+    return load3(L.a);
+}
+DEV bool usable_density(double pdf) { return pdf > 0.0 && pdf < (double)INFINITY; }  // (a NaN is not)
+// the valid results of the workgroup: per wave, then one atomic
+DEV void count_valid(unsigned long long *counter, bool valid, uint32_t *wave_valid)
+{
+    const unsigned long long found = __ballot(valid);
+    if ((threadIdx.x & 63u) == 0) wave_valid[threadIdx.x >> 6] = (uint32_t)__popcll(found);
+    __syncthreads();
+    if (threadIdx.x == 0 && counter) {
+        const uint32_t total = (wave_valid[0] + wave_valid[1]) + (wave_valid[2] + wave_valid[3]);
+        if (total) atomicAdd(counter, (unsigned long long)total);
+    }
+}
+}  // namespace
+
+template <int STRICT, class T>
+__global__ __launch_bounds__(256) void light_sample_kernel(DeviceScene sc, LightArgs a)
+{
+    __shared__ __attribute__((aligned(16))) double rows_lds[kLightLdsRows * kLightRowDoubles];
+    __shared__ __attribute__((aligned(16))) double cdf_lds[kLightLdsRows];
+    __shared__ uint32_t wave_valid[4];
+    global_tables_only(sc);
+    stage_lights(a, rows_lds, cdf_lds);
+    const LightLds lds{rows_lds, cdf_lds};
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    bool valid = false;
+    if (k < a.count) {
+        // the point and the six words are read here, before anything is written: rng_out may be rng_in
+        const Vec P = load3(a.point + (size_t)k * 3);
+        const double tm = a.time ? a.time[k] : a.time_all;
+        Xorwow rng;
+        if (a.rng_in) {  // {d, v0..v4} as rt_rng_state writes them
+            const uint32_t *w = a.rng_in + (size_t)k * 6;
+            rng.d = w[0]; rng.v0 = w[1]; rng.v1 = w[2]; rng.v2 = w[3]; rng.v3 = w[4]; rng.v4 = w[5];
+        } else {  // curand_init(seed, k + first_sequence, 0)
+            rng = a.base;
+            xorwow_skip_sequences(a.jump_table, a.first_sequence + (uint64_t)k, rng);
+        }
+        Vec dir = mk(0.0, 0.0, 0.0), emitted = mk(0.0, 0.0, 0.0), contribution = mk(0.0, 0.0, 0.0);
+        double distance = 0.0, pdf = 0.0, scatter = 0.0;
+        int32_t light = -1;
+        if (a.n_lights != 0) {
+            const double xi = (double)xorwow_uniform(rng);
+            uint32_t lo = 0, hi = a.n_lights - 1u;  // the first row with cdf >= xi; the last entry is 1.0 >= xi
+            while (lo < hi) {
+                const uint32_t mid = (lo + hi) / 2u;
+                if (light_cdf(a, lds, mid) >= xi) hi = mid;
+                else lo = mid + 1u;
+            }
+            light = (int32_t)lo;
+            const double chance = light_cdf(a, lds, lo) - (lo ? light_cdf(a, lds, lo - 1u) : 0.0);
+            const LightRow L = light_row(a, lds, lo);
+            Vec S = mk(0.0, 0.0, 0.0), centre = mk(0.0, 0.0, 0.0);
+            double u = 0.0, v = 0.0;
+            if (L.kind <= LIGHT_TRIANGLE) {
+                double ua = (double)xorwow_uniform(rng);
+                double ub = (double)xorwow_uniform(rng);
+                if (L.kind == LIGHT_TRIANGLE && ua + ub > 1.0) {
+                    ua = 1.0 - ua;
+                    ub = 1.0 - ub;
+                }
+                S = (load3(L.a) + ua * load3(L.b)) + ub * load3(L.c);
+                const Vec D = S - P;
+                const double d2 = dot(D, D);
+                if (d2 > 0.0) {
+                    const double len = sqrt(d2);
+                    const Vec unit_d = over(D, len);
+                    const double c = fabs(dot(load3(L.n), unit_d));
+                    if (c != 0.0) {
+                        const double density = (d2 / (c * L.s)) * chance;
+                        if (usable_density(density)) {
+                            valid = true;
+                            dir = unit_d;
+                            distance = len;
+                            pdf = density;
+                        }
+                    }
+                }
+                u = ua;
+                v = ub;
+            } else {
+                Vec p;
+                double s;
+                do {  // the lens loop of camera_ray
+                    const double da = (double)xorwow_uniform(rng);
+                    const double db = (double)xorwow_uniform(rng);
+                    p = mk(2.0 * da - 1.0, 2.0 * db - 1.0, 0.0);
+                    s = p.x * p.x + p.y * p.y;
+                } while (!(s < 1.0 && s > 0.0));
+                centre = light_centre(L, tm);
+                const Vec oc = centre - P;
+                const double d2 = dot(oc, oc), r2 = L.s * L.s;
+                if (d2 > r2) {
+                    const Vec w = over(oc, sqrt(d2));
+                    const double cosmax = sqrt(1.0 - r2 / d2);
+                    const double omc = 1.0 - cosmax;
+                    const double z = 1.0 - s * omc;
+                    const double rho = sqrt(1.0 - z * z);
+                    const double q = sqrt(s);
+                    const double ex = (rho * p.x) / q, ey = (rho * p.y) / q;
+                    const double ax = fabs(w.x), ay = fabs(w.y), az = fabs(w.z);
+                    Vec e1;
+                    if (ax >= ay && ax >= az) e1 = over(mk(w.z, 0.0, -w.x), sqrt(w.z * w.z + w.x * w.x));
+                    else if (ay >= az) e1 = over(mk(-w.y, w.x, 0.0), sqrt(w.y * w.y + w.x * w.x));
+                    else e1 = over(mk(0.0, -w.z, w.y), sqrt(w.z * w.z + w.y * w.y));
+                    const Vec e2 = cross(w, e1);
+                    const Vec g = (z * w + ex * e1) + ey * e2;
+                    const Vec unit_d = over(g, sqrt(dot(g, g)));
+                    // the near root as the renderer's own sphere test finds it for this ray (sphere_test / sphere_roots: R/Sphere.h:28-50),
+                    // operation by operation: a shadow ray along `unit_d` meets the lamp at this very parameter
+                    const Vec po = P - centre;
+                    const double qa = dot(unit_d, unit_d), qb = dot(po, unit_d), qc = dot(po, po) - r2;
+                    const double disc = qb * qb - qa * qc;
+                    const double len = (-qb - sqrt(disc)) / qa;
+                    const double density = chance / ((2.0 * kLightPi) * omc);
+                    if (omc != 0.0 && usable_density(density) && disc > 0.0 && len > 0.0) {
+                        valid = true;
+                        dir = unit_d;
+                        distance = len;
+                        pdf = density;
+                        S = P + len * unit_d;
+                    }
+                }
+            }
+            if (valid && (a.emitted || a.contribution)) {
+                const MatView mp = material_view<false>(sc, L.mat);
+                if (L.kind >= LIGHT_SPHERE && mp.u32(MAT_OFF(needs_uv)) != 0) sphere_uv((1 / L.s) * (S - centre), u, v);
+                emitted = material_texture<T>(sc, mp, mp.u32(MAT_OFF(tex_inline)), u, v, S);
+            }
+            if (valid && (a.scatter_pdf || a.contribution)) {
+                const uint32_t kind = a.material[k];
+                if (kind == MAT_LAMBERTIAN) {
+                    const double c = dot(load3(a.normal + (size_t)k * 3), dir);
+                    if (c > 0.0) scatter = (2.0 * ((c * c) * c)) / kLightPi;
+                } else if (kind == MAT_ISOTROPIC) {
+                    scatter = 1.0 / (4.0 * kLightPi);
+                }
+                if (scatter != 0.0) contribution = (scatter / pdf) * emitted;
+            }
+        }
+        if (a.direction) store3(a.direction, k, dir);
+        if (a.distance) a.distance[k] = distance;
+        if (a.light) a.light[k] = light;
+        if (a.pdf) a.pdf[k] = pdf;
+        if (a.emitted) store3(a.emitted, k, emitted);
+        if (a.scatter_pdf) a.scatter_pdf[k] = scatter;
+        if (a.contribution) store3(a.contribution, k, contribution);
+        if (a.rng_out) {  // may be the array the state came from: this lane has read its six words
+            uint32_t *w = a.rng_out + (size_t)k * 6;
+            w[0] = rng.d; w[1] = rng.v0; w[2] = rng.v1; w[3] = rng.v2; w[4] = rng.v3; w[5] = rng.v4;
+        }
+    }
+    count_valid(a.valid_counter, valid, wave_valid);
+}
+
+template <int STRICT>
+__global__ __launch_bounds__(256) void light_pdf_kernel(DeviceScene sc, LightArgs a)
+{
+    __shared__ __attribute__((aligned(16))) double rows_lds[kLightLdsRows * kLightRowDoubles];
+    __shared__ __attribute__((aligned(16))) double cdf_lds[kLightLdsRows];
+    __shared__ uint32_t wave_valid[4];
+    stage_lights(a, rows_lds, cdf_lds);
+    const LightLds lds{rows_lds, cdf_lds};
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    const bool mine = k < a.count;
+    const size_t at3 = mine ? (size_t)k * 3 : 0;  // (a lane beyond the count reads ray 0 and writes nothing: the loop stays wave-uniform)
+    const Vec o = load3(a.point + at3), d = load3(a.direction_in + at3);
+    const double tm = a.time ? a.time[mine ? k : 0] : a.time_all;
+    const double dd = dot(d, d);
+    double sum = 0.0, nearest = (double)INFINITY, before = 0.0;
+    int32_t light = -1;
+    for (uint32_t i = 0; i < a.n_lights; i++) {  // every lane of the wave on row i
+        const LightRow L = light_row(a, lds, i);
+        const double upto = light_cdf(a, lds, i);
+        const double chance = upto - before;
+        before = upto;
+        double density = 0.0, t = 0.0;
+        if (L.kind <= LIGHT_TRIANGLE) {
+            const Vec n = load3(L.n), Q = load3(L.a), U = load3(L.b), V = load3(L.c);
+            const double denom = dot(n, d);
+            if (denom != 0.0) {
+                t = dot(n, Q - o) / denom;
+                if (t > 0.0) {
+                    const Vec ph = (o + t * d) - Q;
+                    const Vec m = cross(U, V);
+                    const double mm = dot(m, m);
+                    const double alpha = dot(m, cross(ph, V)) / mm, beta = dot(m, cross(U, ph)) / mm;
+                    const bool below = L.kind == LIGHT_TRIANGLE ? alpha + beta <= 1.0 : (alpha <= 1.0 && beta <= 1.0);
+                    if (0.0 <= alpha && 0.0 <= beta && below) density = (((t * t) * dd) / ((fabs(denom) / sqrt(dd)) * L.s)) * chance;
+                }
+            }
+        } else {
+            const Vec oc = light_centre(L, tm) - o;
+            const double d2 = dot(oc, oc), r2 = L.s * L.s;
+            if (d2 > r2) {
+                const double b = dot(oc, d);
+                const double disc = b * b - dd * (d2 - r2);
+                if (b > 0.0 && disc >= 0.0) {
+                    const double omc = 1.0 - sqrt(1.0 - r2 / d2);
+                    if (omc != 0.0) density = chance / ((2.0 * kLightPi) * omc);
+                    t = (b - sqrt(disc)) / dd;
+                }
+            }
+        }
+        if (usable_density(density)) {
+            sum = sum + density;
+            if (t < nearest) {
+                nearest = t;
+                light = (int32_t)i;
+            }
+        }
+    }
+    if (mine) {
+        if (a.pdf) a.pdf[k] = sum;
+        if (a.light) a.light[k] = light;
+    }
+    count_valid(a.valid_counter, mine && light >= 0, wave_valid);
+}
+
+hipError_t RT_CAT(launch_light_sample_, RT_SUFFIX)(const DeviceScene &sc, const LightArgs &a, hipStream_t stream, QueryKernelInfo *info)
+{
+    const bool any = a.direction || a.distance || a.light || a.pdf || a.emitted || a.scatter_pdf || a.contribution || a.rng_out;
+    if (!info && (!a.point || !any || !a.rows || !a.cdf)) return hipErrorInvalidValue;
+    if (!info && (a.scatter_pdf || a.contribution) && (!a.normal || !a.material)) return hipErrorInvalidValue;
+    return info_or_launch(light_sample_kernel<RT_STRICT, TListNested>, sc, a, a.count, stream, info);
+}
+hipError_t RT_CAT(launch_light_pdf_, RT_SUFFIX)(const DeviceScene &sc, const LightArgs &a, hipStream_t stream, QueryKernelInfo *info)
+{
+    if (!info && (!a.point || !a.direction_in || !(a.pdf || a.light) || !a.rows || !a.cdf)) return hipErrorInvalidValue;
+    return info_or_launch(light_pdf_kernel<RT_STRICT>, sc, a, a.count, stream, info);
 }
 #elif RT_GROUP == 1
 namespace {

@@ -258,6 +258,39 @@ hipError_t launch_advance_scan(const uint32_t *block_counts, uint32_t *block_off
 hipError_t launch_advance_gather(const AdvanceGatherArgs &a, hipStream_t stream);
 constexpr uint32_t kAdvanceBlock = 256;  // rows per workgroup of launches 1 and 3
 
+// Light sampling queries (rt_scene_sample_lights, rt_scene_light_pdf; the RT_LIGHTS objects of render.hip): one lane per point or
+// ray, 256-thread workgroups that first stage the first kLightLdsRows rows of the light table and of its cumulative table in LDS.
+// The table is not part of DeviceScene: it comes through these arguments.  `sc` is still passed, for the material and texture
+// tables that `emitted` reads.
+struct LightArgs {
+    const LightRow *rows;               // n_lights
+    const double *cdf;                  // the cumulative table of the call's strategy, padded to an even length
+    uint32_t n_lights;
+    // mode 0 (light_sample_kernel): points in, samples out; mode 1 (light_pdf_kernel): origin = point, direction in, pdf / light out
+    const double *point;                // count x 3
+    const double *direction_in;         // count x 3 (mode 1)
+    const double *normal;               // count x 3, or nullptr
+    const uint8_t *material;            // count, or nullptr
+    const double *time;                 // count, or nullptr: time_all
+    double time_all;
+    const uint32_t *rng_in;             // count x 6, or nullptr: seeded from base
+    double *direction, *distance;       // outputs of mode 0, each may be nullptr
+    int32_t *light;                     // count (both modes)
+    double *pdf;                        // count (both modes)
+    double *emitted, *scatter_pdf, *contribution;
+    uint32_t *rng_out;                  // count x 6; may be rng_in
+    unsigned long long *valid_counter;  // one word, zeroed by the caller: valid samples / rays that meet a light; nullptr: not counted
+    const uint32_t *jump_table;         // kJumpTableWords
+    Xorwow base;                        // salted seed state (sequence 0)
+    uint64_t first_sequence;
+    uint32_t count;
+};
+// info != nullptr: report the kernel that would run instead of launching it
+hipError_t launch_light_sample_strict(const DeviceScene &sc, const LightArgs &a, hipStream_t stream, QueryKernelInfo *info = nullptr);
+hipError_t launch_light_sample_fast(const DeviceScene &sc, const LightArgs &a, hipStream_t stream, QueryKernelInfo *info = nullptr);
+hipError_t launch_light_pdf_strict(const DeviceScene &sc, const LightArgs &a, hipStream_t stream, QueryKernelInfo *info = nullptr);
+hipError_t launch_light_pdf_fast(const DeviceScene &sc, const LightArgs &a, hipStream_t stream, QueryKernelInfo *info = nullptr);
+
 // One level of the edge-avoiding a-trous filter (denoise.hip; include/rtow.h rt_denoise_params has the stencil): full-frame
 // planes, `in` and `out` distinct.  A guide that is nullptr switches its term off; inv_* = 1 / sigma^2 (0 for sigma = +inf), the
 // colour's already scaled for the level.

@@ -1344,6 +1344,125 @@ static void build_segment_tree(FlatScene &f, bool reference_tree_only)
     f.flags |= SCENE_SEGMENTED;
 }
 
+// ------------------------------------------------------------------------------------------------
+// The light table (flat_scene.h LightRow): every primitive with a DiffuseLight material below world leaf `leaf`, found through
+// lists, BvhNodes (in their sorted order) and Translate / RotateY, never through a ConstantMedium (its boundary is no surface).
+// `chain` = the instances above the primitive, outermost first; their forward transforms -- what the hit record goes through on
+// its way back to the world, R/Instance.h:53,137-147 -- are applied innermost first, in fp64, nothing fused (this file is built
+// with contraction off).  A RotateY turns points and vectors alike, a Translate moves points only.
+// ------------------------------------------------------------------------------------------------
+namespace {
+struct LightCollector {
+    const SceneImpl &s;
+    FlatScene &f;
+    std::vector<const HostHittable *> chain;
+    std::vector<double> weight;  // strategy 1, parallel to f.lights
+    bool too_deep = false;       // an object graph deeper than kLightMaxDepth levels: the commit is refused
+    static constexpr int kLightMaxDepth = 64;  // (recursion bound; far beyond kTreeMaxDepth, which the flattener enforces for trees)
+
+    D3 forward(D3 p, bool point) const
+    {
+        for (size_t k = chain.size(); k-- > 0;) {
+            const HostHittable &x = *chain[k];
+            if (x.kind == HKind::Translate) {
+                if (point) p = add(p, x.offset);
+            } else {
+                p = mk((x.cos_t * p.x) + (x.sin_t * p.z), p.y, (-x.sin_t * p.x) + (x.cos_t * p.z));
+            }
+        }
+        return p;
+    }
+    static void put(double *dst, D3 v) { dst[0] = v.x; dst[1] = v.y; dst[2] = v.z; }
+
+    void walk(uint32_t handle, uint32_t leaf, int depth)
+    {
+        if (depth > kLightMaxDepth) {
+            too_deep = true;
+            return;
+        }
+        const HostHittable &h = s.hittables[handle - 1];
+        switch (h.kind) {
+        case HKind::Medium: return;
+        case HKind::Translate:
+        case HKind::RotateY:
+            chain.push_back(&h);
+            walk(h.child, leaf, depth + 1);
+            chain.pop_back();
+            return;
+        case HKind::List:
+        case HKind::Bvh:
+            for (uint32_t c : h.items) walk(c, leaf, depth + 1);
+            return;
+        default: break;
+        }
+        const HostMaterial &m = s.materials[h.material - 1];
+        if (m.kind != MAT_DIFFUSE_LIGHT) return;
+        LightRow r{};
+        r.mat = h.material - 1;
+        r.leaf = leaf;
+        double area;
+        if (h.kind == HKind::Sphere || h.kind == HKind::MovingSphere) {
+            const double pi = 3.1415926535897932385;
+            put(r.a, forward(h.c0, true));
+            r.s = h.radius;
+            area = 4.0 * pi * (h.radius * h.radius);
+            r.kind = LIGHT_SPHERE;
+            if (h.kind == HKind::MovingSphere) {
+                r.kind = LIGHT_MSPHERE;
+                put(r.b, forward(sub(h.c1, h.c0), false));  // MSphereGeom's dc, turned
+                r.c[0] = h.t0;
+                r.c[1] = h.t1 - h.t0;
+            }
+        } else {
+            put(r.a, forward(h.q, true));
+            put(r.b, forward(h.u, false));
+            put(r.c, forward(h.v, false));
+            put(r.n, forward(h.normal, false));
+            area = length(cross(h.u, h.v));  // of the primitive as constructed: the instances are rigid
+            r.kind = LIGHT_QUAD;
+            if (h.kind == HKind::Triangle) {
+                r.kind = LIGHT_TRIANGLE;
+                area = 0.5 * area;
+            }
+            r.s = area;
+        }
+        double brightest = 1.0;  // any texture but a solid colour
+        if (m.texture && s.textures[m.texture - 1].kind == TEX_SOLID) {
+            const D3 c = s.textures[m.texture - 1].color;
+            brightest = std::fmax(c.x, std::fmax(c.y, c.z));
+        }
+        f.lights.push_back(r);
+        weight.push_back(area * brightest);
+    }
+
+    // cumulative tables: entry k = (w_0 + ... + w_k) / total, summed in order; the last entry exactly 1.0
+    void finish()
+    {
+        const size_t n = f.lights.size(), padded = (n + 1) & ~(size_t)1;
+        double total = 0.0;
+        bool usable = n > 0;
+        for (double w : weight) {
+            usable = usable && std::isfinite(w) && w >= 0.0;
+            total += w;
+        }
+        usable = usable && std::isfinite(total) && total > 0.0;  // otherwise strategy 1 is strategy 0
+        for (int st = 0; st < 2; st++) {
+            std::vector<double> &cdf = f.light_cdf[st];
+            cdf.assign(padded, 1.0);
+            double run = 0.0;
+            for (size_t k = 0; k + 1 < n; k++) {
+                if (st == 1 && usable) {
+                    run += weight[k];
+                    cdf[k] = std::fmin(run / total, 1.0);
+                } else {
+                    cdf[k] = (double)(k + 1) / (double)n;
+                }
+            }
+        }
+    }
+};
+}  // namespace
+
 int flatten_scene(SceneImpl &s)
 {
     if (s.world == 0) return fail(RT_ERR_STATE, "rt_scene_commit: no world set (rt_scene_set_world)");
@@ -1431,6 +1550,14 @@ int flatten_scene(SceneImpl &s)
         bool all_spheres = !f.world_items.empty();
         for (size_t k = 0; k < f.world_items.size(); k++) all_spheres &= f.world_items[k] == make_ref(REF_SPHERE, (uint32_t)k);
         if (all_spheres && f.spheres.size() == f.world_items.size()) f.flags |= SCENE_LIST_ALL_SPHERES;
+    }
+    {
+        LightCollector lc{s, f, {}, {}};
+        for (size_t k = 0; k < leaves.size(); k++) lc.walk(leaves[k], (uint32_t)k, 0);
+        if (lc.too_deep)
+            return fail(RT_ERR_UNSUPPORTED, "object nesting deeper than " + std::to_string(LightCollector::kLightMaxDepth) +
+                                                " levels (the walk that collects the lights is bounded)");
+        lc.finish();
     }
     fl.emit_pending();
     if (fl.tree_depth_seen > kTreeMaxDepth)
@@ -2177,7 +2304,28 @@ int rt_scene_get_info(rt_scene *s, rt_scene_info *out)
                                   f.materials.size() * sizeof(MaterialRec));
     out->image_bytes = (uint32_t)f.image_bytes.size();
     for (const AAQuad &a : f.quad_aa) out->reserved[0] += a.code == kQuadTriangle;  // n_triangles (counted in n_quads too)
+    out->reserved[1] = (uint32_t)f.lights.size();  // n_lights
     return RT_OK;
+}
+
+static_assert(sizeof(rt_light_row) == sizeof(LightRow) && offsetof(rt_light_row, s) == offsetof(LightRow, s) &&
+                  offsetof(rt_light_row, kind) == offsetof(LightRow, kind) && offsetof(rt_light_row, leaf) == offsetof(LightRow, leaf),
+              "rt_light_row is LightRow");
+int rt_scene_dump_lights(rt_scene *s, int max_lights, int *kind_out, int *leaf_out, rt_light_row *rows_out, double *cdf_out)
+{
+    if (!s || !S(s)->committed) return -fail(RT_ERR_STATE, "rt_scene_dump_lights: scene not committed");
+    const FlatScene &f = S(s)->flat;
+    const int n = (int)f.lights.size();
+    for (int k = 0; k < n && k < max_lights; k++) {
+        if (kind_out) kind_out[k] = (int)f.lights[k].kind;
+        if (leaf_out) leaf_out[k] = (int)f.lights[k].leaf;
+        if (rows_out) std::memcpy(&rows_out[k], &f.lights[k], sizeof(LightRow));
+        if (cdf_out) {
+            cdf_out[2 * k] = f.light_cdf[0][k];
+            cdf_out[2 * k + 1] = f.light_cdf[1][k];
+        }
+    }
+    return n;
 }
 
 int rt_scene_dump_leaves(rt_scene *s, int max_leaves, int *kind_out, double *box_out)

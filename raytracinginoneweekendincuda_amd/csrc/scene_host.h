@@ -108,6 +108,12 @@ struct FlatScene {
     // row has a non-finite centre, motion or interval, and no shutter keeps it inside its box.
     std::vector<MsInterval> ms_intervals;
     bool ms_nonfinite = false;
+    // The emissive world primitives in world space, in the depth-first construction order of the world (scene_builder.cpp
+    // collect_lights), and their cumulative selection tables: [0] uniform over lights, [1] by area x the brightest channel.  Each
+    // table's entry lights.size() - 1 is exactly 1.0; both are padded with 1.0 to an even length (the kernels stage them in LDS
+    // with 16-byte loads).
+    std::vector<LightRow> lights;
+    std::vector<double> light_cdf[2];
 };
 
 struct DeviceTables;  // device_scene.cpp
