@@ -38,6 +38,13 @@ def sphere_roots(o, d, centre, radius):
     return (-b - root) / a, (-b + root) / a, disc / (b * b)
 
 
+def uv_bound(n):
+    """What the sphere's U/V may differ by, per hit: they are functions of the unit normal n with |dv/dn| <= 1 / (pi s) and
+    |du/dn| <= 1 / (2 pi s), s = sqrt(1 - ny^2) = sqrt(nx^2 + nz^2) (acos and atan2 are ill-conditioned towards the poles).  The
+    normals are held to 1e-12; numpy's acos / atan2 and the device's are good to a few ulp of a value in [0, 2 pi]: 1e-14."""
+    return (1e-12 / (np.pi * np.sqrt(1.0 - n[:, 1] * n[:, 1])) + 1e-14)[:, None]
+
+
 def mixed_world(s, Rng, world_kind, aspect):
     """Builds into ``s`` (rt.Scene, conftest.OracleScene or a view of one) with ``Rng`` of its side, as a conftest.build_both
     callback does: ten items of every primitive, texture and material kind, nine small spheres so that the BvhNode world

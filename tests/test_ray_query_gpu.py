@@ -14,7 +14,7 @@ import torch
 import raytracinginoneweekendincuda_amd as rt
 from raytracinginoneweekendincuda_amd import _lib, api
 from conftest import ROOT
-from query_helpers import bits, centre_rays, dot3, mixed_world, sphere_roots
+from query_helpers import bits, centre_rays, dot3, mixed_world, sphere_roots, uv_bound
 
 pytestmark = pytest.mark.gpu
 
@@ -28,13 +28,6 @@ def sphere_uv(n):
     """R/Sphere.h:74-81 on unit outward normals (N, 3): (u, v) as (N, 2)."""
     theta, phi = np.arccos(-n[:, 1]), np.arctan2(-n[:, 2], n[:, 0]) + np.pi
     return np.stack([phi / (2.0 * np.pi), theta / np.pi], axis=-1)
-
-
-def uv_bound(n):
-    """What the sphere's U/V may differ by, per hit: they are functions of the unit normal n with |dv/dn| <= 1 / (pi s) and
-    |du/dn| <= 1 / (2 pi s), s = sqrt(1 - ny^2) = sqrt(nx^2 + nz^2) (acos and atan2 are ill-conditioned towards the poles).  The
-    normals are held to 1e-12; numpy's acos / atan2 and the device's are good to a few ulp of a value in [0, 2 pi]: 1e-14."""
-    return (1e-12 / (np.pi * np.sqrt(1.0 - n[:, 1] * n[:, 1])) + 1e-14)[:, None]
 
 
 # ---- scenes ----
