@@ -891,6 +891,103 @@ RTOW_API int rt_scene_light_pdf(rt_scene *s, const rt_light_params *params, cons
  * this library was compiled, and kLightLdsRows: the rows of the light table the kernels stage on chip */
 RTOW_API void rt_light_abi_sizes(uint32_t out8[8]);
 
+/* ---- path advances with light samples: next-event estimation and its MIS weights inside the advance ----
+ * rt_scene_path_advance with the light sample, the mixture density, the shadow ray and the balance-heuristic weights of a
+ * caller's loop around rt_scene_sample_lights, rt_scene_light_pdf and rt_scene_intersect done by the library, in the same call.
+ * Everything rt_scene_path_advance states holds -- n, the rows read, the ids, the stable compaction, the count words, the
+ * waiting (stats == NULL: enqueue and return; whatever frees the scene's device tables waits for the last call enqueued) -- with
+ * these additions.  Every operation below is one IEEE-754 double operation in the order written in the strict build; the fast
+ * build may fuse.
+ * Row k is stepped exactly as rt_scene_path_advance steps it.  The step gives a status, emitted E, attenuation A, the scattered
+ * ray (o', d', tm), the normal n, the material kind m (both as rt_query_hits) and the stream R1 after its last draw; the row
+ * carries thr = throughput[3k..3k+2], its id and q = scatter_pdf[k] (0 where rays->scatter_pdf is NULL): the density with which
+ * the bounce before sent the ray this way, 0 meaning "no light sample was taken there: count a lamp in full".
+ *   status 0 or 1 (the path ends): w = 1, unless status is 1, m is a diffuse light (3) and q > 0: then p = the pdf of
+ *     rt_scene_light_pdf for the incoming ray as given (origin, direction -- not normalised --, time, params->strategy) and
+ *     w = q / (q + p).  radiance[id] = radiance[id] + (thr * E) * w; with w = 1 this is rt_scene_path_advance to the bit.
+ *   status 2 (scattered): thr' = thr * A and the survivor's row as in rt_scene_path_advance.  Where m is Lambertian (0) or
+ *     isotropic (4), the scene has lights and params->sample is 1:
+ *       the sample of rt_scene_sample_lights for the point o', normal n, material m, time tm, from the stream R1 under
+ *       params->strategy: dir, distance, contribution C, scatter_pdf s, and the stream R2 (the draws happen whether or not the
+ *       sample is valid, as there).  Where C is not all zero:
+ *         p = the pdf of rt_scene_light_pdf at (o', dir, tm);  w = p / (p + s), 0 where p + s == 0;  L = (thr' * C) * w
+ *         the shadow ray (o', dir, tm) over (0.001, distance * (1 - 2^-20)) is searched as rt_scene_intersect mode 1 searches; a
+ *         ConstantMedium draws from the path's own stream, which continues at R2.  Not occluded: radiance[id] = radiance[id] + L
+ *         (where out->radiance is given and 0 <= id < sources; the search happens either way)
+ *       the survivor's stream is the one after the last draw, and its density
+ *         q' = scatter_pdf(m, n, u), u = (1 / sqrt((d'.x * d'.x + d'.y * d'.y) + d'.z * d'.z)) * d'
+ *       with the closed form stated for rt_scene_sample_lights' scatter_pdf.
+ *     In every other case (metal, glass, a scene without lights, sample == 0) nothing is drawn and q' = 0.
+ * A row either ends or scatters: a call makes at most one addition per id, so distinct live ids still need no atomics.
+ * out->scatter_pdf, row j: q' of survivor j.
+ * The estimator: fresh rays start with q = 0 (rays->scatter_pdf NULL); sample = 1 in every call but the last of max_depth calls;
+ * whoever is alive after the last call is dropped.  The radiance so folded has the expectation of rt_scene_radiance with samples
+ * = 1 and the same max_depth: a light sample at bounce b stands for the lamp that scattering would find at bounce b + 1, which is
+ * why the last call takes none.
+ * Aliasing as for rt_scene_path_advance, and out->scatter_pdf may not be rays->scatter_pdf.
+ * Refusals, all before the device is touched, in this order: those of rt_scene_path_advance up to the variant; a strategy other
+ * than 0 / 1; a sample other than 0 / 1; the rest of rt_scene_path_advance's (the aliased pairs now include scatter_pdf; the
+ * workspace is measured by rt_path_advance_direct_workspace_bytes).  count == 0 is RT_OK with nothing launched and nothing
+ * written; the other parameters are still checked. */
+typedef struct rt_path_advance_direct_params {
+    int64_t  count;            /* as rt_path_advance_params, field for field ... */
+    int64_t  sources;
+    double   time;
+    uint64_t seed;
+    uint64_t first_sequence;
+    int32_t  variant;
+    int32_t  device;
+    void    *stream;
+    void    *workspace;        /* device call only: >= rt_path_advance_direct_workspace_bytes(count) */
+    uint64_t workspace_bytes;
+    int32_t  reserved[4];
+    int32_t  strategy;         /* ... and: 0 uniform over lights, 1 by area x brightest channel, as rt_light_params */
+    int32_t  sample;           /* 1: a light sample at every diffuse or isotropic hit of this call; 0: none (the last bounce) */
+} rt_path_advance_direct_params;
+typedef struct rt_path_advance_direct_rays {
+    const double   *origin, *direction;   /* as rt_path_advance_rays, field for field ... */
+    const double   *time;
+    const uint32_t *rng_state;
+    const double   *throughput;
+    const int32_t  *ray_id;
+    const uint8_t  *alive;
+    const uint32_t *count;
+    const double   *scatter_pdf;          /* ... and: count, or NULL: all 0 */
+} rt_path_advance_direct_rays;
+typedef struct rt_path_advance_direct_out {
+    double   *radiance;        /* as rt_path_advance_out, field for field ... */
+    double   *origin;
+    double   *direction;
+    double   *time;
+    uint32_t *rng_state;
+    double   *throughput;
+    int32_t  *ray_id;
+    double   *t;
+    double   *normal;
+    uint8_t  *front_face;
+    uint8_t  *material;
+    uint32_t *count;
+    double   *scatter_pdf;     /* ... and: count; optional */
+} rt_path_advance_direct_out;
+typedef struct rt_path_advance_direct_stats {
+    uint64_t rays, scattered;                 /* rays stepped (below n and alive); the survivors */
+    uint64_t shadow_rays, shadow_reached;     /* shadow rays cast; those that reached their lamp */
+    double seconds;                           /* the call's four kernels, HIP events */
+    uint32_t kernel_vgprs, scratch_bytes;     /* of the step-and-sample kernel that ran: registers, private memory per lane */
+    uint32_t shadow_vgprs, shadow_scratch_bytes;  /* of the shadow-ray kernel */
+} rt_path_advance_direct_stats;
+/* rays and out hold device pointers (on params->device), the two count words included.  stats == NULL: enqueue and return. */
+RTOW_API int rt_scene_path_advance_direct_device(rt_scene *s, const rt_path_advance_direct_params *params,
+                                                 const rt_path_advance_direct_rays *rays, const rt_path_advance_direct_out *out,
+                                                 rt_path_advance_direct_stats *stats);
+/* the same on host arrays (uploaded, advanced, waited for, copied back) */
+RTOW_API int rt_scene_path_advance_direct(rt_scene *s, const rt_path_advance_direct_params *params, const rt_path_advance_direct_rays *rays,
+                                          const rt_path_advance_direct_out *out, rt_path_advance_direct_stats *stats);
+/* bytes of workspace a device call of capacity `count` needs: 0 for 0, non-decreasing in count, at least the plain call's */
+RTOW_API uint64_t rt_path_advance_direct_workspace_bytes(int64_t count);
+/* sizeof of rt_path_advance_direct_params, _rays, _out, _stats as this library was compiled */
+RTOW_API void rt_path_advance_direct_abi_sizes(uint32_t out4[4]);
+
 /* Convenience: create film, upload, render 1 GPU, download.  frame = W*H*3 doubles. */
 RTOW_API int rt_render(rt_scene *s, const rt_render_params *params, double *frame, rt_render_stats *stats);
 

@@ -203,6 +203,15 @@ public:
         check(device_pointers ? rt_scene_path_advance_device(s_, &params, &rays, &out, stats) : rt_scene_path_advance(s_, &params, &rays, &out, stats));
     }
 
+    // The same with a light sample, its shadow ray and the MIS weights at every diffuse hit (rtow.h "path advances with light
+    // samples"): params.sample = 1 in every call of a path but its last.
+    void PathAdvanceDirect(const rt_path_advance_direct_params &params, const rt_path_advance_direct_rays &rays,
+                           const rt_path_advance_direct_out &out, rt_path_advance_direct_stats *stats = nullptr, bool device_pointers = true)
+    {
+        check(device_pointers ? rt_scene_path_advance_direct_device(s_, &params, &rays, &out, stats)
+                              : rt_scene_path_advance_direct(s_, &params, &rays, &out, stats));
+    }
+
 private:
     rt_handle ok(rt_handle h)
     {

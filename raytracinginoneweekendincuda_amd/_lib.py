@@ -135,6 +135,29 @@ class PathAdvanceStats(C.Structure):
                 ("scratch_bytes", C.c_uint32)]
 
 
+# rt_path_advance_direct_*: the plain advance's structs, field for field, and what the light samples add behind them
+class PathAdvanceDirectParams(C.Structure):
+    _fields_ = PathAdvanceParams._fields_ + [("strategy", C.c_int32), ("sample", C.c_int32)]
+
+
+class PathAdvanceDirectRays(C.Structure):
+    _fields_ = PathAdvanceRays._fields_ + [("scatter_pdf", C.c_void_p)]
+
+
+# the per-survivor outputs of a path advance with light samples: the plain advance's and the density the ray was sent with
+ADVANCE_DIRECT_OUTPUTS = dict(ADVANCE_OUTPUTS, scatter_pdf=("float64", ()))
+
+
+class PathAdvanceDirectOut(C.Structure):
+    _fields_ = PathAdvanceOut._fields_ + [("scatter_pdf", C.c_void_p)]
+
+
+class PathAdvanceDirectStats(C.Structure):
+    _fields_ = [("rays", C.c_uint64), ("scattered", C.c_uint64), ("shadow_rays", C.c_uint64), ("shadow_reached", C.c_uint64),
+                ("seconds", C.c_double), ("kernel_vgprs", C.c_uint32), ("scratch_bytes", C.c_uint32), ("shadow_vgprs", C.c_uint32),
+                ("shadow_scratch_bytes", C.c_uint32)]
+
+
 class LightParams(C.Structure):
     _fields_ = [("count", C.c_int64), ("time", C.c_double), ("seed", C.c_uint64), ("first_sequence", C.c_uint64), ("strategy", C.c_int32),
                 ("variant", C.c_int32), ("device", C.c_int32), ("stream", C.c_void_p), ("reserved", C.c_int32 * 4)]
@@ -303,6 +326,10 @@ SIGNATURES = {
     "rt_scene_light_pdf_device": (I, [P, C.POINTER(LightParams), C.POINTER(LightRays), C.POINTER(LightPdfOut), C.POINTER(LightStats)]),
     "rt_scene_light_pdf": (I, [P, C.POINTER(LightParams), C.POINTER(LightRays), C.POINTER(LightPdfOut), C.POINTER(LightStats)]),
     "rt_light_abi_sizes": (None, [C.POINTER(C.c_uint32)]),
+    "rt_scene_path_advance_direct_device": (I, [P, C.POINTER(PathAdvanceDirectParams), C.POINTER(PathAdvanceDirectRays), C.POINTER(PathAdvanceDirectOut), C.POINTER(PathAdvanceDirectStats)]),
+    "rt_scene_path_advance_direct": (I, [P, C.POINTER(PathAdvanceDirectParams), C.POINTER(PathAdvanceDirectRays), C.POINTER(PathAdvanceDirectOut), C.POINTER(PathAdvanceDirectStats)]),
+    "rt_path_advance_direct_workspace_bytes": (C.c_uint64, [C.c_int64]),
+    "rt_path_advance_direct_abi_sizes": (None, [C.POINTER(C.c_uint32)]),
     "rt_deinterleave": (I, [D3, I, I, I, I, C.c_size_t, D3]),
     "rt_render": (I, [P, C.POINTER(RenderParams), D3, C.POINTER(RenderStats)]),
     "rt_write_ppm": (I, [C.c_char_p, D3, I, I]),
@@ -331,7 +358,9 @@ def load():
     # caller's arrays
     for what, sizes_of, structs in (("rt_radiance_*", lib.rt_radiance_abi_sizes, (RadianceParams, RadianceRays, RadianceOut, RadianceStats)),
                                     ("rt_path_step_*", lib.rt_path_step_abi_sizes, (PathStepParams, PathStepRays, PathStepOut, PathStepStats)),
-                                    ("rt_path_advance_*", lib.rt_path_advance_abi_sizes, (PathAdvanceParams, PathAdvanceRays, PathAdvanceOut, PathAdvanceStats))):
+                                    ("rt_path_advance_*", lib.rt_path_advance_abi_sizes, (PathAdvanceParams, PathAdvanceRays, PathAdvanceOut, PathAdvanceStats)),
+                                    ("rt_path_advance_direct_*", lib.rt_path_advance_direct_abi_sizes,
+                                     (PathAdvanceDirectParams, PathAdvanceDirectRays, PathAdvanceDirectOut, PathAdvanceDirectStats))):
         sizes = (C.c_uint32 * 4)()
         sizes_of(sizes)
         ours = [C.sizeof(x) for x in structs]

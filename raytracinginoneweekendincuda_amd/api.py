@@ -15,6 +15,7 @@ from . import _lib
 from ._lib import (AdaptiveParams, DenoiseParams, FeatureParams, LaunchPlan, LightParams, LightPdfOut, LightPoints, LightRays,  # noqa: F401
                    LightSamples, LightStats, QueryHits, QueryParams, QueryRays, QueryStats,  # noqa: F401
                    PathAdvanceOut, PathAdvanceParams, PathAdvanceRays, PathAdvanceStats,
+                   PathAdvanceDirectOut, PathAdvanceDirectParams, PathAdvanceDirectRays, PathAdvanceDirectStats,
                    PathStepOut, PathStepParams, PathStepRays, PathStepStats, RadianceOut, RadianceParams, RadianceRays, RadianceStats,
                    RenderParams, RenderStats, SceneInfo)
 
@@ -491,8 +492,32 @@ class Scene:
         survivors' count, so it waits for the device (``PathBatch`` is the form that does not).  numpy arrays take the host call;
         torch CUDA tensors are read in place, on ``torch.cuda.current_stream()``, with a workspace tensor of this call's own.
         Other dtypes, shapes and non-contiguous inputs raise RtowError.  ``stats=True``: (outputs, PathAdvanceStats)."""
+        return self._path_advance(None, origins, directions, times, rng_state, throughput, ray_id, alive, radiance, time, seed, first_sequence,
+                                  variant, want, device, stats)
+
+    def path_advance_direct(self, origins, directions, times=None, rng_state=None, throughput=None, ray_id=None, alive=None, radiance=None,
+                            scatter_pdf=None, strategy=1, sample=True, time=0.0, seed=1984, first_sequence=0, variant=0,
+                            want=("origin", "direction", "time", "rng_state", "throughput", "ray_id", "scatter_pdf"), device=0, stats=False):
+        """``path_advance`` with next-event estimation and its MIS weights done in the same call (include/rtow.h
+        rt_scene_path_advance_direct states every operation): with ``sample=True`` every ray that scatters from a Lambertian or
+        isotropic hit draws one ``sample_lights`` sample from its own stream under ``strategy``, casts its shadow ray and adds the
+        sample, weighted ``p_light / (p_light + p_scatter)``, to ``radiance``; a ray that ends on a lamp adds its light weighted
+        ``q / (q + p_light)``, where q = ``scatter_pdf[k]`` ((count,) float64, None: zeros) is the density the bounce before sent it
+        with -- 0 where no light sample was taken, the lamp then counts in full.  The output "scatter_pdf" is that density for the
+        survivors.  ``sample=False`` for the last bounce of a path of fixed length: a light sample stands for the lamp the next
+        bounce would find.  Everything else as ``path_advance``.  ``stats=True``: (outputs, PathAdvanceDirectStats)."""
+        if strategy not in (0, 1):
+            raise RtowError("strategy must be 0 (uniform) or 1 (by area and brightness)")
+        return self._path_advance((scatter_pdf, int(strategy), 1 if sample else 0), origins, directions, times, rng_state, throughput, ray_id,
+                                  alive, radiance, time, seed, first_sequence, variant, want, device, stats)
+
+    def _path_advance(self, direct, origins, directions, times, rng_state, throughput, ray_id, alive, radiance, time, seed, first_sequence,
+                      variant, want, device, stats):
+        """Both forms of the advance; ``direct``: None, or (scatter_pdf, strategy, sample) of ``path_advance_direct``."""
         on_gpu = type(origins).__module__.split(".")[0] == "torch"
         wanted = tuple(want)
+        outputs = _lib.ADVANCE_DIRECT_OUTPUTS if direct else _lib.ADVANCE_OUTPUTS
+        bytes_of = lib().rt_path_advance_direct_workspace_bytes if direct else lib().rt_path_advance_workspace_bytes
         kept = {}   # what the call uses beside the per-ray arrays: alive until the count has been read
 
         def structs(count, rays, outs, device, stream):
@@ -507,7 +532,7 @@ class Scene:
                 if not ok or radiance.ndim != 2 or radiance.shape[1] != 3:
                     raise RtowError("radiance: a contiguous (sources, 3) float64 array of the kind of the origins is required")
                 sources = int(radiance.shape[0])
-            nbytes = int(lib().rt_path_advance_workspace_bytes(count))
+            nbytes = int(bytes_of(count))
             if on_gpu:
                 import torch
                 kept["count"] = torch.zeros(1, dtype=torch.int32, device=origins.device)
@@ -516,18 +541,25 @@ class Scene:
             else:
                 kept["count"] = np.zeros(1, dtype=np.uint32)
                 address = lambda a: a.ctypes.data   # noqa: E731
-            p = PathAdvanceParams(count, sources, float(time), int(seed), int(first_sequence), int(variant), device, stream,
-                                  address(kept["workspace"]) if on_gpu else None, nbytes if on_gpu else 0)
-            r = PathAdvanceRays(*(rays.get(n) for n in ("origins", "directions", "times", "rng_state", "throughput", "ray_id", "alive")), None)
-            o = PathAdvanceOut(address(radiance) if sources else None, *(outs.get(n) for n in _lib.ADVANCE_OUTPUTS), address(kept["count"]))
-            return p, r, o
+            params = (count, sources, float(time), int(seed), int(first_sequence), int(variant), device, stream,
+                      address(kept["workspace"]) if on_gpu else None, nbytes if on_gpu else 0)
+            ray_arrays = tuple(rays.get(n) for n in ("origins", "directions", "times", "rng_state", "throughput", "ray_id", "alive")) + (None,)
+            out_arrays = (address(radiance) if sources else None,) + tuple(outs.get(n) for n in _lib.ADVANCE_OUTPUTS) + (address(kept["count"]),)
+            if direct:
+                return (PathAdvanceDirectParams(*params, (C.c_int32 * 4)(), direct[1], direct[2]),
+                        PathAdvanceDirectRays(*ray_arrays, rays.get("scatter_pdf")), PathAdvanceDirectOut(*out_arrays, outs.get("scatter_pdf")))
+            return PathAdvanceParams(*params), PathAdvanceRays(*ray_arrays), PathAdvanceOut(*out_arrays)
 
         inputs = [("times", times, (), ("float64",), False), ("rng_state", rng_state, (6,), ("uint32", "int32"), False),
                   ("throughput", throughput, (3,), ("float64",), False), ("ray_id", ray_id, (), ("int32",), False),
                   ("alive", alive, (), ("uint8",), False)]
+        calls, stats_type = (lib().rt_scene_path_advance, lib().rt_scene_path_advance_device), PathAdvanceStats
+        if direct:
+            inputs.append(("scatter_pdf", direct[0], (), ("float64",), False))
+            calls, stats_type = (lib().rt_scene_path_advance_direct, lib().rt_scene_path_advance_direct_device), PathAdvanceDirectStats
         required = tuple(n for n in ("origin", "direction") if n not in wanted)
-        out, st = self._ray_batch("path advance", origins, directions, inputs, _lib.ADVANCE_OUTPUTS, wanted + required,
-                                  (lib().rt_scene_path_advance, lib().rt_scene_path_advance_device), structs, PathAdvanceStats if stats else None, device)
+        out, st = self._ray_batch("path advance", origins, directions, inputs, outputs, wanted + required, calls, structs,
+                                  stats_type if stats else None, device)
         survivors = int(kept["count"][0])   # (a tensor: the copy waits for the stream the call was enqueued on)
         out = {name: out[name][:survivors] for name in wanted}
         return (out, st) if stats else out
@@ -622,9 +654,13 @@ class PathBatch:
     The current side's ``origin``, ``direction``, ``time``, ``rng_state``, ``throughput``, ``ray_id`` (and ``t``, ``normal``,
     ``front_face``, ``material`` of the last hit with ``hits=True``) are attributes: tensors of n rows of which the first
     ``live()`` hold the live rays.  A caller may read them and scale ``throughput`` in place (Russian roulette: ``kill`` the
-    losers, divide the winners' throughput by their chance).  Work on them on the stream the advances are enqueued on."""
+    losers, divide the winners' throughput by their chance).  Work on them on the stream the advances are enqueued on.
+    ``direct="mis"``: every advance is a ``Scene.path_advance_direct`` (rt_scene_path_advance_direct_device) under ``strategy`` --
+    a light sample, its shadow ray and the MIS weights at every diffuse hit; the sides then hold ``scatter_pdf`` as well, and
+    ``run`` takes no light sample at its last bounce.  ``direct=None``: the plain advance."""
 
-    def __init__(self, scene, origins, directions, times=None, rng_state=None, time=0.0, seed=1984, first_sequence=0, variant=0, hits=False):
+    def __init__(self, scene, origins, directions, times=None, rng_state=None, time=0.0, seed=1984, first_sequence=0, variant=0, hits=False,
+                 direct=None, strategy=1):
         import torch
         for name, a, tail, dtypes in (("origins", origins, (3,), (torch.float64,)), ("directions", directions, (3,), (torch.float64,)),
                                       ("times", times, (), (torch.float64,)), ("rng_state", rng_state, (6,), (torch.uint32, torch.int32))):
@@ -636,15 +672,21 @@ class PathBatch:
                 raise RtowError(f"{name}: shape {('count',) + tail} on the device of the origins is required, got {tuple(a.shape)} on {a.device}")
         if variant not in (0, 1):
             raise RtowError("variant must be 0 (strict) or 1 (fast)")
+        if direct not in (None, "mis"):
+            raise RtowError('direct must be None or "mis"')
+        if strategy not in (0, 1):
+            raise RtowError("strategy must be 0 (uniform) or 1 (by area and brightness)")
+        self.direct = direct
+        outputs = _lib.ADVANCE_DIRECT_OUTPUTS if direct else _lib.ADVANCE_OUTPUTS
         self.scene = scene
         self.n = n = int(origins.shape[0])
         self.device = dev = origins.device
         self._index = dev.index if dev.index is not None else torch.cuda.current_device()
         rows = max(n, 1)   # (never an empty allocation: its address may be null)
-        names = list(_lib.ADVANCE_OUTPUTS) if hits else ["origin", "direction", "time", "rng_state", "throughput", "ray_id"]
+        names = list(outputs) if hits else ["origin", "direction", "time", "rng_state", "throughput", "ray_id"] + (["scatter_pdf"] if direct else [])
         state_dtype = rng_state.dtype if rng_state is not None else torch.uint32
         kinds = {"float64": torch.float64, "uint32": torch.int32, "int32": torch.int32, "uint8": torch.uint8}
-        self._sides = [{name: torch.zeros((rows,) + _lib.ADVANCE_OUTPUTS[name][1], dtype=kinds[_lib.ADVANCE_OUTPUTS[name][0]], device=dev)
+        self._sides = [{name: torch.zeros((rows,) + outputs[name][1], dtype=kinds[outputs[name][0]], device=dev)
                         for name in names} for _ in range(2)]
         for side in self._sides:   # (allocated as int32: the words are the same)
             side["rng_state"] = side["rng_state"].view(state_dtype)
@@ -662,18 +704,23 @@ class PathBatch:
         self._count = torch.full((1,), n, dtype=torch.int32, device=dev)
         self._alive = torch.ones(rows, dtype=torch.uint8, device=dev)
         self._killed = False
-        nbytes = int(lib().rt_path_advance_workspace_bytes(n))
+        nbytes = int((lib().rt_path_advance_direct_workspace_bytes if direct else lib().rt_path_advance_workspace_bytes)(n))
         self._workspace = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
         # the structs of a call from side 0 to side 1 and back, built once: the pointers do not change
         self._calls = []
         for src in (0, 1):
             a, b = self._sides[src], self._sides[1 - src]
-            p = PathAdvanceParams(n, n, float(time), int(seed), int(first_sequence), int(variant), self._index, None, self._workspace.data_ptr(), nbytes)
-            rays = PathAdvanceRays(a["origin"].data_ptr(), a["direction"].data_ptr(), a["time"].data_ptr(), a["rng_state"].data_ptr(),
-                                   a["throughput"].data_ptr(), a["ray_id"].data_ptr(), None, self._count.data_ptr())
-            out = PathAdvanceOut(self.radiance.data_ptr() if n else None, *(b[name].data_ptr() if name in b else None for name in _lib.ADVANCE_OUTPUTS),
-                                 self._count.data_ptr())
-            self._calls.append((p, rays, out))
+            params = (n, n, float(time), int(seed), int(first_sequence), int(variant), self._index, None, self._workspace.data_ptr(), nbytes)
+            ray_arrays = (a["origin"].data_ptr(), a["direction"].data_ptr(), a["time"].data_ptr(), a["rng_state"].data_ptr(),
+                          a["throughput"].data_ptr(), a["ray_id"].data_ptr(), None, self._count.data_ptr())
+            out_arrays = (self.radiance.data_ptr() if n else None,) + tuple(b[name].data_ptr() if name in b else None for name in _lib.ADVANCE_OUTPUTS) + \
+                (self._count.data_ptr(),)
+            if direct:   # (fresh rays: the first side's scatter_pdf is zeros)
+                self._calls.append((PathAdvanceDirectParams(*params, (C.c_int32 * 4)(), int(strategy), 1),
+                                    PathAdvanceDirectRays(*ray_arrays, a["scatter_pdf"].data_ptr()),
+                                    PathAdvanceDirectOut(*out_arrays, b["scatter_pdf"].data_ptr())))
+            else:
+                self._calls.append((PathAdvanceParams(*params), PathAdvanceRays(*ray_arrays), PathAdvanceOut(*out_arrays)))
 
     def __getattr__(self, name):   # the current side's tensors
         sides = self.__dict__.get("_sides")
@@ -681,10 +728,11 @@ class PathBatch:
             return sides[self._current][name]
         raise AttributeError(name)
 
-    def advance(self, bounces=1, capacity=None, stats=False):
+    def advance(self, bounces=1, capacity=None, stats=False, sample=True):
         """Enqueues ``bounces`` advances on the current stream and returns; nothing waits.  ``capacity``: rows a launch covers, at
         least the live rays' count (``run`` narrows it to a count it has read); None: all n.  ``stats=True`` (measurements): every
-        call waits and the list of their PathAdvanceStats comes back."""
+        call waits and the list of their PathAdvanceStats (PathAdvanceDirectStats with ``direct``) comes back.  ``sample`` (with
+        ``direct`` only): False, these advances draw no light samples -- for the last bounce of a path of fixed length."""
         import torch
         taken = []
         if self.n == 0:
@@ -693,15 +741,17 @@ class PathBatch:
         if not 0 < capacity <= self.n:
             raise RtowError(f"capacity must be 1 .. {self.n}")
         stream = torch.cuda.current_stream(self.device).cuda_stream or None
-        fn = lib().rt_scene_path_advance_device
+        fn = lib().rt_scene_path_advance_direct_device if self.direct else lib().rt_scene_path_advance_device
         for _ in range(int(bounces)):
             p, rays, out = self._calls[self._current]
             p.count = capacity
             p.stream = stream
+            if self.direct:
+                p.sample = 1 if sample else 0
             rays.rng_state = None if self._seeded_by_library else self._sides[self._current]["rng_state"].data_ptr()
             rays.alive = self._alive.data_ptr() if self._killed else None
             if stats:
-                taken.append(PathAdvanceStats())
+                taken.append(PathAdvanceDirectStats() if self.direct else PathAdvanceStats())
             _check(fn(self.scene._p, C.byref(p), C.byref(rays), C.byref(out), C.byref(taken[-1]) if stats else None))
             if self._killed:
                 self._alive.fill_(1)   # (behind the kernels that read the flags, on their stream)
@@ -725,11 +775,16 @@ class PathBatch:
         ``Scene.radiance(samples=1, max_depth=max_depth)`` of the batch's rays, bit for bit in the strict build.  Every
         ``check_every`` bounces the count is read (a wait) to stop when no ray is left and to narrow later launches to the count;
         0: never, all ``max_depth`` bounces are enqueued at once.  Returns ``radiance``; the caller synchronizes before reading it
-        on another stream."""
+        on another stream.  With ``direct`` the radiance is the MIS estimator of the same expectation, and the last bounce takes no
+        light sample."""
         done, capacity = 0, self.n
         while done < max_depth and capacity > 0:
             bounces = max_depth - done if check_every <= 0 else min(int(check_every), max_depth - done)
-            self.advance(bounces, capacity)
+            if self.direct and done + bounces == max_depth:   # the last bounce on its own
+                self.advance(bounces - 1, capacity)
+                self.advance(1, capacity, sample=False)
+            else:
+                self.advance(bounces, capacity)
             done += bounces
             if check_every > 0 and done < max_depth:
                 capacity = self.live()

@@ -1,4 +1,5 @@
-// advance_pack.hip -- launches 2 and 3 of a path advance (rt_scene_path_advance; render_iface.h AdvanceArgs), gfx950: the scan
+// advance_pack.hip -- the last two launches of a path advance (rt_scene_path_advance, rt_scene_path_advance_direct; render_iface.h
+// AdvanceArgs, AdvanceDirectArgs), gfx950: the scan
 // of the workgroups' survivor counts and the gather of the staged survivors into packed rows.  Neither depends on the scene or
 // on the variant, so they are built once, here.
 //
@@ -58,21 +59,26 @@ __device__ __forceinline__ void move_row(const V *from, V *to, size_t k, size_t 
     for (int c = 0; c < width; c++) to[j * width + c] = from[k * width + c];
 }
 
-// One lane per row: survivor k goes to row j = block_offsets[its workgroup] + the survivors before it in the workgroup.
-__global__ __launch_bounds__(256) void advance_gather_kernel(AdvanceGatherArgs a)
+// One lane per row: survivor k goes to row j = block_offsets[its workgroup] + the survivors before it in the workgroup.  Every lane
+// of the workgroup calls this (its only barrier); kNoRow for a lane that moves nothing.
+constexpr uint32_t kNoRow = 0xFFFFFFFFu;
+__device__ __forceinline__ uint32_t packed_row(const AdvanceGatherArgs &a, uint32_t k, uint32_t *wave_survivors)
 {
-    __shared__ uint32_t wave_survivors[4];
-    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
     const bool survivor = k < a.capacity && a.survivor[k] != 0;
     const unsigned long long ballot = __ballot(survivor);
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     if (lane == 0) wave_survivors[wave] = (uint32_t)__popcll(ballot);
     __syncthreads();
-    if (!survivor) return;  // (behind the only barrier)
+    if (!survivor) return kNoRow;  // (behind the only barrier)
     uint32_t j = a.block_offsets[blockIdx.x];
     for (uint32_t w = 0; w < wave; w++) j += wave_survivors[w];
     j += (uint32_t)__popcll(ballot & ((1ull << lane) - 1ull));
-    if (j > k) return;  // never: a row moves towards the front.  Nothing is written beyond the capacity whatever the flags hold
+    if (j > k) return kNoRow;  // never: a row moves towards the front.  Nothing is written beyond the capacity whatever the flags hold
+    return j;
+}
+
+__device__ __forceinline__ void move_rows(const AdvanceGatherArgs &a, uint32_t k, uint32_t j)
+{
     if (a.to.origin) move_row(a.from.origin, a.to.origin, k, j, 3);
     if (a.to.direction) move_row(a.from.direction, a.to.direction, k, j, 3);
     if (a.to.time) a.to.time[j] = a.from.time[k];
@@ -83,6 +89,26 @@ __global__ __launch_bounds__(256) void advance_gather_kernel(AdvanceGatherArgs a
     if (a.to.normal) move_row(a.from.normal, a.to.normal, k, j, 3);
     if (a.to.front_face) a.to.front_face[j] = a.from.front_face[k];
     if (a.to.material) a.to.material[j] = a.from.material[k];
+}
+
+__global__ __launch_bounds__(256) void advance_gather_kernel(AdvanceGatherArgs a)
+{
+    __shared__ uint32_t wave_survivors[4];
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t j = packed_row(a, k, wave_survivors);
+    if (j == kNoRow) return;
+    move_rows(a, k, j);
+}
+
+// the same for an advance with light samples (rt_scene_path_advance_direct): the density the ray was sent with moves too
+__global__ __launch_bounds__(256) void advance_direct_gather_kernel(AdvanceDirectGatherArgs a)
+{
+    __shared__ uint32_t wave_survivors[4];
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t j = packed_row(a.rows, k, wave_survivors);
+    if (j == kNoRow) return;
+    move_rows(a.rows, k, j);
+    if (a.scatter_pdf_to) a.scatter_pdf_to[j] = a.scatter_pdf_from[k];
 }
 
 }  // namespace
@@ -99,6 +125,14 @@ hipError_t launch_advance_gather(const AdvanceGatherArgs &a, hipStream_t stream)
     if (!a.survivor || !a.block_offsets) return hipErrorInvalidValue;
     if (a.capacity == 0) return hipSuccess;
     hipLaunchKernelGGL(advance_gather_kernel, dim3((a.capacity + kAdvanceBlock - 1u) / kAdvanceBlock), dim3(kAdvanceBlock), 0, stream, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_advance_direct_gather(const AdvanceDirectGatherArgs &a, hipStream_t stream)
+{
+    if (!a.rows.survivor || !a.rows.block_offsets || (a.scatter_pdf_to && !a.scatter_pdf_from)) return hipErrorInvalidValue;
+    if (a.rows.capacity == 0) return hipSuccess;
+    hipLaunchKernelGGL(advance_direct_gather_kernel, dim3((a.rows.capacity + kAdvanceBlock - 1u) / kAdvanceBlock), dim3(kAdvanceBlock), 0, stream, a);
     return hipGetLastError();
 }
 

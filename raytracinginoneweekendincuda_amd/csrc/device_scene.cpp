@@ -497,12 +497,16 @@ struct Build {
     hipError_t (*advance)(const DeviceScene &, const AdvanceArgs &, hipStream_t, QueryKernelInfo *);
     hipError_t (*light_sample)(const DeviceScene &, const LightArgs &, hipStream_t, QueryKernelInfo *);
     hipError_t (*light_pdf)(const DeviceScene &, const LightArgs &, hipStream_t, QueryKernelInfo *);
+    hipError_t (*advance_direct)(const DeviceScene &, const AdvanceDirectArgs &, hipStream_t, QueryKernelInfo *);
+    hipError_t (*advance_shadow)(const DeviceScene &, const AdvanceDirectArgs &, hipStream_t, QueryKernelInfo *);
 };
 static const Build kBuilds[2] = {
     {launch_seed_strict, launch_render_strict, kernel_info_strict, launch_adaptive_rule_strict, launch_features_strict, launch_query_strict,
-     launch_radiance_strict, launch_step_strict, launch_advance_strict, launch_light_sample_strict, launch_light_pdf_strict},
+     launch_radiance_strict, launch_step_strict, launch_advance_strict, launch_light_sample_strict, launch_light_pdf_strict,
+     launch_advance_direct_strict, launch_advance_shadow_strict},
     {launch_seed_fast, launch_render_fast, kernel_info_fast, launch_adaptive_rule_fast, launch_features_fast, launch_query_fast,
-     launch_radiance_fast, launch_step_fast, launch_advance_fast, launch_light_sample_fast, launch_light_pdf_fast}};
+     launch_radiance_fast, launch_step_fast, launch_advance_fast, launch_light_sample_fast, launch_light_pdf_fast,
+     launch_advance_direct_fast, launch_advance_shadow_fast}};
 
 static int seed_film(FilmImpl &f, const rt_render_params *p, hipStream_t stream)
 {
@@ -1555,6 +1559,29 @@ static AdvanceWorkspace advance_workspace(int64_t count)
     return w;
 }
 
+extern "C++" {  // (two templates among the C entry points)
+// what both kinds of advance refuse alike behind their parameters (rt_path_advance_* or rt_path_advance_direct_*, which begin with
+// their fields): the required outputs, the aliased pairs -- `extra_in` / `extra_out` one more -- and a device call's workspace of
+// at least `workspace_needed` bytes (0: the host call, which brings its own), as `measured_by` reports them
+template <class Params, class Rays, class Out>
+static int advance_arrays_check(const Params *p, const Rays *rays, const Out *out, const void *extra_in, const void *extra_out,
+                                uint64_t workspace_needed, const char *measured_by, const std::string &name)
+{
+    if (!out->origin || !out->direction || !out->count) return fail(RT_ERR_INVALID, name + ": out->origin, out->direction and out->count are required");
+    if (out->radiance && p->sources == 0) return fail(RT_ERR_INVALID, name + ": a radiance array of no rows (sources is 0)");
+    const std::pair<const void *, const void *> pairs[] = {{rays->origin, out->origin},       {rays->direction, out->direction},
+                                                           {rays->time, out->time},           {rays->rng_state, out->rng_state},
+                                                           {rays->throughput, out->throughput}, {rays->ray_id, out->ray_id},
+                                                           {extra_in, extra_out}};
+    for (const auto &pair : pairs)
+        if (pair.first && pair.first == pair.second)
+            return fail(RT_ERR_INVALID, name + ": an output is the input array of the same meaning (the compaction cannot be done in place)");
+    if (workspace_needed && p->count > 0 && (!p->workspace || p->workspace_bytes < workspace_needed))
+        return fail(RT_ERR_INVALID, name + ": the workspace is null or smaller than " + measured_by + "(count)");
+    return RT_OK;
+}
+}  // extern "C++"
+
 // everything that can be refused without a device, in the order include/rtow.h lists it
 static int path_advance_check(rt_scene *scene, const rt_path_advance_params *p, const rt_path_advance_rays *rays, const rt_path_advance_out *out,
                               bool device_call, const char *who)
@@ -1562,35 +1589,17 @@ static int path_advance_check(rt_scene *scene, const rt_path_advance_params *p, 
     const std::string name(who);
     const auto sources = [&] { return p->sources < 0 || p->sources > ((int64_t)1 << 30) ? ": sources must be 0 .. 2^30" : nullptr; };
     if (int rc = batch_check(scene, p, rays, out, name, sources)) return rc;
-    if (!out->origin || !out->direction || !out->count) return fail(RT_ERR_INVALID, name + ": out->origin, out->direction and out->count are required");
-    if (out->radiance && p->sources == 0) return fail(RT_ERR_INVALID, name + ": a radiance array of no rows (sources is 0)");
-    const std::pair<const void *, const void *> pairs[] = {{rays->origin, out->origin},       {rays->direction, out->direction},
-                                                           {rays->time, out->time},           {rays->rng_state, out->rng_state},
-                                                           {rays->throughput, out->throughput}, {rays->ray_id, out->ray_id}};
-    for (const auto &pair : pairs)
-        if (pair.first && pair.first == pair.second)
-            return fail(RT_ERR_INVALID, name + ": an output is the input array of the same meaning (the compaction cannot be done in place)");
-    if (device_call && p->count > 0 && (!p->workspace || p->workspace_bytes < advance_workspace(p->count).bytes))
-        return fail(RT_ERR_INVALID, name + ": the workspace is null or smaller than rt_path_advance_workspace_bytes(count)");
-    return RT_OK;
+    return advance_arrays_check(p, rays, out, nullptr, nullptr, device_call ? advance_workspace(p->count).bytes : 0, "rt_path_advance_workspace_bytes", name);
 }
 
-uint64_t rt_path_advance_workspace_bytes(int64_t count) { return advance_workspace(count > ((int64_t)1 << 30) ? (int64_t)1 << 30 : count).bytes; }
-
-int rt_scene_path_advance_device(rt_scene *scene, const rt_path_advance_params *p, const rt_path_advance_rays *rays,
-                                 const rt_path_advance_out *out, rt_path_advance_stats *stats)
+extern "C++" {
+// the launch arguments of an advance from the call's three structs (rt_path_advance_* or rt_path_advance_direct_*, which begin with
+// their fields) and the workspace's layout: what is asked for is staged
+template <class Params, class Rays, class Out>
+static void advance_args(const Params *p, const Rays *rays, const Out *out, const AdvanceWorkspace &w, AdvanceArgs &aa, AdvanceGatherArgs &ga)
 {
-    const char *who = "rt_scene_path_advance_device";
-    if (int rc = path_advance_check(scene, p, rays, out, true, who)) return rc;
-    if (stats) *stats = rt_path_advance_stats{};
-    if (p->count == 0) return RT_OK;
-    SceneImpl &s = *S(scene);
-    if (int rc = rt_scene_upload(scene, p->device)) return rc;  // (selects the device)
-    DeviceTables &dt = *s.device[p->device];
-    const AdvanceWorkspace w = advance_workspace(p->count);
     char *base = static_cast<char *>(p->workspace);
     const auto at = [&](uint64_t offset, const void *wanted) { return wanted ? base + offset : nullptr; };  // stage what is asked for
-    AdvanceArgs aa{};
     aa.origin = rays->origin;
     aa.direction = rays->direction;
     aa.time = rays->time;
@@ -1613,17 +1622,35 @@ int rt_scene_path_advance_device(rt_scene *scene, const rt_path_advance_params *
     aa.stage.material = (uint8_t *)at(w.material, out->material);
     aa.survivor = (uint8_t *)(base + w.survivor);
     aa.block_counts = (uint32_t *)(base + w.block_counts);
-    if (int rc = device_jump_table(p->device, &aa.jump_table)) return rc;
     aa.base = xorwow_seed(p->seed, kSaltCurandDevice);
     aa.first_sequence = p->first_sequence;
     aa.capacity = (uint32_t)p->count;
     aa.sources = (uint32_t)p->sources;
-    AdvanceGatherArgs ga{};
     ga.from = aa.stage;
     ga.to = AdvanceStage{out->origin, out->direction, out->time, out->rng_state, out->throughput, out->ray_id, out->t, out->normal, out->front_face, out->material};
     ga.survivor = aa.survivor;
     ga.block_offsets = (uint32_t *)(base + w.block_offsets);
     ga.capacity = aa.capacity;
+}
+}  // extern "C++"
+
+uint64_t rt_path_advance_workspace_bytes(int64_t count) { return advance_workspace(count > ((int64_t)1 << 30) ? (int64_t)1 << 30 : count).bytes; }
+
+int rt_scene_path_advance_device(rt_scene *scene, const rt_path_advance_params *p, const rt_path_advance_rays *rays,
+                                 const rt_path_advance_out *out, rt_path_advance_stats *stats)
+{
+    const char *who = "rt_scene_path_advance_device";
+    if (int rc = path_advance_check(scene, p, rays, out, true, who)) return rc;
+    if (stats) *stats = rt_path_advance_stats{};
+    if (p->count == 0) return RT_OK;
+    SceneImpl &s = *S(scene);
+    if (int rc = rt_scene_upload(scene, p->device)) return rc;  // (selects the device)
+    DeviceTables &dt = *s.device[p->device];
+    const AdvanceWorkspace w = advance_workspace(p->count);
+    AdvanceArgs aa{};
+    AdvanceGatherArgs ga{};
+    advance_args(p, rays, out, w, aa, ga);
+    if (int rc = device_jump_table(p->device, &aa.jump_table)) return rc;
     hipStream_t stream = (hipStream_t)p->stream;
     if (!dt.advance_done) HIP_TRY(hipEventCreateWithFlags(&dt.advance_done, hipEventDisableTiming));
     const auto three = [&]() -> hipError_t {  // the call's kernels, in the stream's order
@@ -1733,6 +1760,216 @@ void rt_path_advance_abi_sizes(uint32_t out4[4])
     out4[1] = (uint32_t)sizeof(rt_path_advance_rays);
     out4[2] = (uint32_t)sizeof(rt_path_advance_out);
     out4[3] = (uint32_t)sizeof(rt_path_advance_stats);
+}
+
+// ---- path advances with light samples ----
+// The plain advance's workspace (every staging array: launch 2 reads rows the caller may not have asked for), then the staged
+// densities, the shadow rays, their weighted contributions and the pending flags.
+struct AdvanceDirectWorkspace {
+    AdvanceWorkspace plain;
+    uint64_t scatter_pdf, shadow_direction, shadow_distance, shadow_radiance, pending;
+    uint64_t bytes;
+};
+static AdvanceDirectWorkspace advance_direct_workspace(int64_t count)
+{
+    AdvanceDirectWorkspace w{};
+    if (count <= 0) return w;
+    w.plain = advance_workspace(count);
+    const uint64_t n = (uint64_t)count;
+    uint64_t at = w.plain.bytes;  // (a multiple of 256)
+    const auto piece = [&](uint64_t bytes) {
+        const uint64_t here = at;
+        at += (bytes + 255u) & ~(uint64_t)255u;
+        return here;
+    };
+    w.scatter_pdf = piece(n * sizeof(double));
+    w.shadow_direction = piece(n * 3 * sizeof(double));
+    w.shadow_distance = piece(n * sizeof(double));
+    w.shadow_radiance = piece(n * 3 * sizeof(double));
+    w.pending = piece(n);
+    w.bytes = at;
+    return w;
+}
+
+// everything that can be refused without a device, in the order include/rtow.h lists it: batch_check's order, with the strategy and
+// the sample switch behind the variant
+static int path_advance_direct_check(rt_scene *scene, const rt_path_advance_direct_params *p, const rt_path_advance_direct_rays *rays,
+                                     const rt_path_advance_direct_out *out, bool device_call, const char *who)
+{
+    const std::string name(who);
+    if (!scene || !p || !rays || !out) return fail(RT_ERR_INVALID, name + ": null argument");
+    if (!S(scene)->committed) return fail(RT_ERR_STATE, name + ": scene not committed (rt_scene_commit)");
+    if (p->count < 0 || p->count > ((int64_t)1 << 30)) return fail(RT_ERR_INVALID, name + ": count must be 0 .. 2^30");
+    if (p->sources < 0 || p->sources > ((int64_t)1 << 30)) return fail(RT_ERR_INVALID, name + ": sources must be 0 .. 2^30");
+    if (p->variant != 0 && p->variant != 1) return fail(RT_ERR_INVALID, name + ": variant must be 0 (strict) or 1 (fast)");
+    if (p->strategy != 0 && p->strategy != 1) return fail(RT_ERR_INVALID, name + ": strategy must be 0 (uniform) or 1 (by area and brightness)");
+    if (p->sample != 0 && p->sample != 1) return fail(RT_ERR_INVALID, name + ": sample must be 0 (no light samples in this call) or 1");
+    if (p->count > 0 && (!rays->origin || !rays->direction)) return fail(RT_ERR_INVALID, name + ": null origin or direction");
+    return advance_arrays_check(p, rays, out, rays->scatter_pdf, out->scatter_pdf, device_call ? advance_direct_workspace(p->count).bytes : 0,
+                                "rt_path_advance_direct_workspace_bytes", name);
+}
+
+uint64_t rt_path_advance_direct_workspace_bytes(int64_t count)
+{
+    return advance_direct_workspace(count > ((int64_t)1 << 30) ? (int64_t)1 << 30 : count).bytes;
+}
+
+int rt_scene_path_advance_direct_device(rt_scene *scene, const rt_path_advance_direct_params *p, const rt_path_advance_direct_rays *rays,
+                                        const rt_path_advance_direct_out *out, rt_path_advance_direct_stats *stats)
+{
+    const char *who = "rt_scene_path_advance_direct_device";
+    if (int rc = path_advance_direct_check(scene, p, rays, out, true, who)) return rc;
+    if (stats) *stats = rt_path_advance_direct_stats{};
+    if (p->count == 0) return RT_OK;
+    SceneImpl &s = *S(scene);
+    if (int rc = rt_scene_upload(scene, p->device)) return rc;  // (selects the device)
+    DeviceTables &dt = *s.device[p->device];
+    const AdvanceDirectWorkspace w = advance_direct_workspace(p->count);
+    char *base = static_cast<char *>(p->workspace);
+    AdvanceDirectArgs da{};
+    AdvanceDirectGatherArgs ga{};
+    advance_args(p, rays, out, w.plain, da.adv, ga.rows);
+    // launch 2 reads these of every pending row, whether the caller asked for them or not
+    da.adv.stage.time = (double *)(base + w.plain.time);
+    da.adv.stage.rng_state = (uint32_t *)(base + w.plain.rng_state);
+    da.adv.stage.ray_id = (int32_t *)(base + w.plain.ray_id);
+    ga.rows.from = da.adv.stage;
+    if (int rc = device_jump_table(p->device, &da.adv.jump_table)) return rc;
+    da.rows = dt.lights;
+    da.cdf = dt.light_cdf[p->strategy];
+    da.n_lights = dt.n_lights;
+    da.sample = p->sample;
+    da.scatter_pdf = rays->scatter_pdf;
+    da.scatter_pdf_stage = (double *)(base + w.scatter_pdf);
+    da.shadow_direction = (double *)(base + w.shadow_direction);
+    da.shadow_distance = (double *)(base + w.shadow_distance);
+    da.shadow_radiance = (double *)(base + w.shadow_radiance);
+    da.pending = (uint8_t *)(base + w.pending);
+    da.node_leaf_pos = dt.node_leaf_pos;
+    ga.scatter_pdf_from = da.scatter_pdf_stage;
+    ga.scatter_pdf_to = out->scatter_pdf;
+    const bool shadows = da.n_lights != 0 && da.sample != 0;  // else launch 1 leaves no row pending: launch 2 is not enqueued
+    hipStream_t stream = (hipStream_t)p->stream;
+    if (!dt.advance_done) HIP_TRY(hipEventCreateWithFlags(&dt.advance_done, hipEventDisableTiming));
+    const auto four = [&]() -> hipError_t {  // the call's kernels, in the stream's order
+        hipError_t e = kBuilds[p->variant].advance_direct(dt.scene, da, stream, nullptr);
+        if (e == hipSuccess && shadows) e = kBuilds[p->variant].advance_shadow(dt.scene, da, stream, nullptr);
+        if (e == hipSuccess)
+            e = launch_advance_scan(da.adv.block_counts, const_cast<uint32_t *>(ga.rows.block_offsets), w.plain.n_blocks, out->count, stream);
+        if (e == hipSuccess) e = launch_advance_direct_gather(ga, stream);
+        return e;
+    };
+    if (!stats) {  // enqueue and return: whoever frees the tables waits for the event
+        hipError_t e = four();
+        const hipError_t recorded = hipEventRecord(dt.advance_done, stream);
+        if (e == hipSuccess) e = recorded;
+        return e == hipSuccess ? RT_OK : hip_fail(e, who);
+    }
+    QueryKernelInfo info{}, shadow_info{};
+    HIP_TRY(kBuilds[p->variant].advance_direct(dt.scene, da, stream, &info));
+    HIP_TRY(kBuilds[p->variant].advance_shadow(dt.scene, da, stream, &shadow_info));
+    DeviceArena scratch(p->device);
+    unsigned long long *counters = nullptr;  // rows stepped, shadow rays cast, shadow rays that reached their lamp
+    HIP_TRY(scratch.alloc(3, counters));
+    da.adv.stepped_counter = counters;
+    da.shadow_counters = counters + 1;
+    // from here on the chain: the events are destroyed, and the stream waited for, whatever fails
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    unsigned long long counted[3] = {0, 0, 0};
+    uint32_t survivors = 0;
+    hipError_t e = hipEventCreate(&ev[0]);
+    if (e == hipSuccess) e = hipEventCreate(&ev[1]);
+    if (e == hipSuccess) e = hipMemsetAsync(counters, 0, sizeof counted, stream);
+    if (e == hipSuccess) e = hipEventRecord(ev[0], stream);
+    if (e == hipSuccess) e = four();
+    if (e == hipSuccess) e = hipEventRecord(ev[1], stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(counted, counters, sizeof counted, hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(&survivors, out->count, sizeof survivors, hipMemcpyDeviceToHost, stream);
+    const hipError_t waited = hipStreamSynchronize(stream);
+    if (e == hipSuccess) e = waited;
+    float ms = 0.0f;
+    if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev[0], ev[1]);
+    for (hipEvent_t v : ev)
+        if (v) hipEventDestroy(v);
+    if (e != hipSuccess) return hip_fail(e, who);
+    stats->rays = counted[0];
+    stats->scattered = survivors;
+    stats->shadow_rays = counted[1];
+    stats->shadow_reached = counted[2];
+    stats->seconds = (double)ms * 1e-3;
+    stats->kernel_vgprs = (uint32_t)info.vgprs;
+    stats->scratch_bytes = (uint32_t)info.scratch_bytes;
+    stats->shadow_vgprs = (uint32_t)shadow_info.vgprs;
+    stats->shadow_scratch_bytes = (uint32_t)shadow_info.scratch_bytes;
+    return RT_OK;
+}
+
+int rt_scene_path_advance_direct(rt_scene *scene, const rt_path_advance_direct_params *p, const rt_path_advance_direct_rays *rays,
+                                 const rt_path_advance_direct_out *out, rt_path_advance_direct_stats *stats)
+{
+    if (int rc = path_advance_direct_check(scene, p, rays, out, false, "rt_scene_path_advance_direct")) return rc;
+    if (stats) *stats = rt_path_advance_direct_stats{};
+    if (p->count == 0) return RT_OK;
+    if (int rc = select_device(p->device)) return rc;
+    // the host knows the word: only the rows below n travel
+    const int64_t n = rays->count && (int64_t)*rays->count < p->count ? (int64_t)*rays->count : p->count;
+    if (n == 0) {
+        *out->count = 0;
+        return RT_OK;
+    }
+    Staging stage{DeviceArena(p->device), (size_t)n, {}};
+    rt_path_advance_direct_rays dr{};
+    HIP_TRY(stage.in(rays->origin, 3, dr.origin));
+    HIP_TRY(stage.in(rays->direction, 3, dr.direction));
+    HIP_TRY(stage.in(rays->time, 1, dr.time));
+    HIP_TRY(stage.in(rays->rng_state, 6, dr.rng_state));
+    HIP_TRY(stage.in(rays->throughput, 3, dr.throughput));
+    HIP_TRY(stage.in(rays->ray_id, 1, dr.ray_id));
+    HIP_TRY(stage.in(rays->alive, 1, dr.alive));
+    HIP_TRY(stage.in(rays->scatter_pdf, 1, dr.scatter_pdf));
+    rt_path_advance_direct_out dout{};
+    if (out->radiance) {
+        const double *uploaded = nullptr;
+        HIP_TRY(stage.arena.upload(out->radiance, (size_t)p->sources * 3, uploaded));
+        dout.radiance = const_cast<double *>(uploaded);
+    }
+    HIP_TRY(stage.out(out->origin, 3, dout.origin));
+    HIP_TRY(stage.out(out->direction, 3, dout.direction));
+    HIP_TRY(stage.out(out->time, 1, dout.time));
+    HIP_TRY(stage.out(out->rng_state, 6, dout.rng_state));
+    HIP_TRY(stage.out(out->throughput, 3, dout.throughput));
+    HIP_TRY(stage.out(out->ray_id, 1, dout.ray_id));
+    HIP_TRY(stage.out(out->t, 1, dout.t));
+    HIP_TRY(stage.out(out->normal, 3, dout.normal));
+    HIP_TRY(stage.out(out->front_face, 1, dout.front_face));
+    HIP_TRY(stage.out(out->material, 1, dout.material));
+    HIP_TRY(stage.out(out->scatter_pdf, 1, dout.scatter_pdf));
+    HIP_TRY(stage.arena.alloc(1, dout.count));
+    rt_path_advance_direct_params dp = *p;
+    dp.count = n;
+    dp.stream = nullptr;  // the copies around the advance are synchronous: nothing to order on the caller's stream
+    dp.workspace_bytes = advance_direct_workspace(n).bytes;
+    unsigned char *workspace = nullptr;
+    HIP_TRY(stage.arena.alloc((size_t)dp.workspace_bytes, workspace));
+    dp.workspace = workspace;
+    rt_path_advance_direct_stats waited{};  // with statistics the device call waits
+    if (int rc = rt_scene_path_advance_direct_device(scene, &dp, &dr, &dout, stats ? stats : &waited)) return rc;
+    uint32_t survivors = 0;
+    HIP_TRY(hipMemcpy(&survivors, dout.count, sizeof survivors, hipMemcpyDeviceToHost));
+    if (survivors > (uint32_t)n) survivors = (uint32_t)n;  // (never)
+    for (const Staging::Out &o : stage.outs)  // the first `survivors` rows of each
+        if (survivors) HIP_TRY(hipMemcpy(o.host, o.dev, o.bytes / (size_t)n * survivors, hipMemcpyDeviceToHost));
+    if (out->radiance) HIP_TRY(hipMemcpy(out->radiance, dout.radiance, (size_t)p->sources * 3 * sizeof(double), hipMemcpyDeviceToHost));
+    *out->count = survivors;
+    return RT_OK;
+}
+
+void rt_path_advance_direct_abi_sizes(uint32_t out4[4])
+{
+    out4[0] = (uint32_t)sizeof(rt_path_advance_direct_params);
+    out4[1] = (uint32_t)sizeof(rt_path_advance_direct_rays);
+    out4[2] = (uint32_t)sizeof(rt_path_advance_direct_out);
+    out4[3] = (uint32_t)sizeof(rt_path_advance_direct_stats);
 }
 
 int rt_render(rt_scene *scene, const rt_render_params *params, double *frame, rt_render_stats *stats)

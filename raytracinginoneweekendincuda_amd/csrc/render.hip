@@ -62,6 +62,11 @@
 #ifndef RT_LIGHTS  // 1: this translation unit holds the light sampling kernels (light_sample_kernel, light_pdf_kernel) and nothing else
 #define RT_LIGHTS 0
 #endif
+#ifndef RT_ADVANCE_DIRECT  // 1: this translation unit holds the kernels of a path advance with light samples (advance_direct_kernel, shadow_kernel) and nothing else
+#define RT_ADVANCE_DIRECT 0
+#endif
+// the lane-per-ray units: one lane per pixel, ray or point, no persistent waves
+#define RT_LANE_UNIT (RT_FEATURES || RT_QUERY || RT_RADIANCE || RT_STEP || RT_ADVANCE || RT_LIGHTS || RT_ADVANCE_DIRECT)
 
 namespace rtow {
 namespace {
@@ -309,7 +314,7 @@ DEV bool sphere_test(Vec oc, Vec d, double a, double r2, double tmin, double tma
 // times with the branch (the select costs the media kernel of scene 8 3 %), the lane-per-ray kernels of the feature pass and the
 // queries keep their registers with the select (the branch takes the radiance kernel of list worlds from 168 to 170 VGPRs, from
 // three waves per SIMD to two, 35 % on scene 7).  A third form, a switch case of its own in quad_test_at, cost most kernels spills.
-#define RT_PLANAR_SELECT (RT_FEATURES || RT_QUERY || RT_RADIANCE || RT_STEP || RT_ADVANCE)
+#define RT_PLANAR_SELECT (RT_FEATURES || RT_QUERY || RT_RADIANCE || RT_STEP || RT_ADVANCE || RT_ADVANCE_DIRECT)
 DEV bool quad_test(const QuadGeom &q, bool tri, const Ray &r, double tmin, double tmax, double &t_out)
 {
     Vec n = mk(q.nx, q.ny, q.nz);
@@ -464,7 +469,7 @@ DEV bool prim_test(const DeviceScene &sc, uint32_t ref, const Ray &r, double a, 
 #ifndef RT_PHASES
 #define RT_PHASES 0  // diagnostic build: per-phase wave cycles and lane occupancy, summed into ray_counter[7] and [32..119]
 #endif
-#if RT_PHASES && (RT_FEATURES || RT_QUERY || RT_RADIANCE || RT_STEP || RT_ADVANCE || RT_LIGHTS)
+#if RT_PHASES && RT_LANE_UNIT
 #undef RT_PHASES
 #define RT_PHASES 0  // the phases are render_kernel's: the feature and query units of a diagnostic build are the ordinary ones
 #endif
@@ -4248,7 +4253,7 @@ hipError_t RT_CAT(launch_composite_, RT_SUFFIX)(int which, const DeviceScene &sc
 hipError_t RT_CAT(launch_adaptive_prims_, RT_SUFFIX)(int which, const DeviceScene &sc, const RenderArgs &a, hipStream_t stream, KernelInfo *info);
 hipError_t RT_CAT(launch_adaptive_composite_, RT_SUFFIX)(int which, const DeviceScene &sc, const RenderArgs &a, hipStream_t stream, KernelInfo *info);
 
-#if RT_FEATURES || RT_QUERY || RT_RADIANCE || RT_STEP || RT_ADVANCE || RT_LIGHTS
+#if RT_LANE_UNIT
 // ------------------------------------------------------------------------------------------------
 // Shared by the six lane-per-ray sections below (first-hit features, ray queries, radiance queries, path steps, path advances, light
 // sampling): one lane per pixel or per caller-supplied ray or point, no persistent waves; only the light kernels stage anything in
@@ -4399,7 +4404,8 @@ hipError_t RT_CAT(launch_features_, RT_SUFFIX)(const DeviceScene &sc, const Feat
     else hipLaunchKernelGGL((feature_kernel<RT_STRICT, TListNested>), grid, block, 0, stream, sc, a);
     return hipGetLastError();
 }
-#elif RT_QUERY
+#endif
+#if RT_QUERY || RT_ADVANCE_DIRECT  // (the search is shadow_kernel's too)
 // ------------------------------------------------------------------------------------------------
 // Ray queries (rt_scene_intersect): closest hit or occlusion for caller-supplied rays.  The feature pass's search once more -- one
 // lane per ray, no LDS, every table from global memory, the reference's tree or list in the reference's order through leaf_test /
@@ -4519,7 +4525,9 @@ DEV void query_uv(const DeviceScene &sc, const Ray &r, const HitInfo &h, double 
     }
 }
 }  // namespace
+#endif
 
+#if RT_QUERY
 // MODE 0 closest hit, 1 occlusion
 template <int STRICT, class T, int MODE>
 __global__ __launch_bounds__(256) void query_kernel(DeviceScene sc, QueryArgs a)
@@ -4889,7 +4897,8 @@ hipError_t RT_CAT(launch_advance_, RT_SUFFIX)(const DeviceScene &sc, const Advan
         sc.world_kind == WORLD_BVH ? advance_kernel<RT_STRICT, TBvhNested> : advance_kernel<RT_STRICT, TListNested>;
     return info_or_launch(kernel, sc, a, a.capacity, stream, info);
 }
-#elif RT_LIGHTS
+#endif
+#if RT_LIGHTS || RT_ADVANCE_DIRECT  // (the staging and the table's readers are advance_direct_kernel's too)
 // ------------------------------------------------------------------------------------------------
 // Light sampling queries (rt_scene_sample_lights, rt_scene_light_pdf; include/rtow.h states both operation by operation, and
 // tests/light_restated.py restates the strict build to the bit).  One lane per point or ray, the callers' arrays read and written
@@ -4934,7 +4943,7 @@ DEV Vec light_centre(const LightRow &L, double tm)  // MSphereGeom's formula for
 }
 DEV bool usable_density(double pdf) { return pdf > 0.0 && pdf < (double)INFINITY; }  // (a NaN is not)
 // the valid results of the workgroup: per wave, then one atomic
-DEV void count_valid(unsigned long long *counter, bool valid, uint32_t *wave_valid)
+[[maybe_unused]] DEV void count_valid(unsigned long long *counter, bool valid, uint32_t *wave_valid)  // (the light kernels)
 {
     const unsigned long long found = __ballot(valid);
     if ((threadIdx.x & 63u) == 0) wave_valid[threadIdx.x >> 6] = (uint32_t)__popcll(found);
@@ -4945,7 +4954,9 @@ DEV void count_valid(unsigned long long *counter, bool valid, uint32_t *wave_val
     }
 }
 }  // namespace
+#endif
 
+#if RT_LIGHTS
 template <int STRICT, class T>
 __global__ __launch_bounds__(256) void light_sample_kernel(DeviceScene sc, LightArgs a)
 {
@@ -5162,6 +5173,387 @@ hipError_t RT_CAT(launch_light_pdf_, RT_SUFFIX)(const DeviceScene &sc, const Lig
     if (!info && (!a.point || !a.direction_in || !(a.pdf || a.light) || !a.rows || !a.cdf)) return hipErrorInvalidValue;
     return info_or_launch(light_pdf_kernel<RT_STRICT>, sc, a, a.count, stream, info);
 }
+#elif RT_ADVANCE_DIRECT
+// ------------------------------------------------------------------------------------------------
+// Path advances with light samples (rt_scene_path_advance_direct; include/rtow.h states the operation), launches 1 and 2 of 4
+// (render_iface.h AdvanceDirectArgs).  The world is searched twice for a row that scatters from a diffuse hit -- once for the
+// path, once for the shadow ray -- and the two searches are two kernels: one kernel with both would hold the registers and the
+// scratch of the larger through the other, and every lane whose path ended would idle through the second.
+//   advance_direct_kernel: advance_kernel's iteration restated line for line; then, for a row that scattered from a Lambertian or
+//   isotropic hit, light_sample_kernel's sample restated from the path's own stream; then, every lane of the wave here again, one
+//   loop over the light table, every lane on the same row (light_pdf_kernel's loop restated), for the one density a lane can
+//   need: along its incoming ray where it ended on a lamp with a density carried in, along its sample where it scattered.  A wave
+//   in which no lane needs one skips the loop.  The table is staged in LDS as the light kernels stage it.
+//   shadow_kernel: query_kernel's occlusion search for the rows launch 1 left pending.
+// No lane returns before a barrier, no workgroup waits for another.  Termination: as for advance_kernel, the rejection loop of the
+// sphere sample depends on the stream alone, the density loop runs n_lights times, the search is the ray queries'.
+// ------------------------------------------------------------------------------------------------
+template <int STRICT, class T>
+__global__ __launch_bounds__(256) void advance_direct_kernel(DeviceScene sc, AdvanceDirectArgs d)
+{
+    __shared__ __attribute__((aligned(16))) double rows_lds[kLightLdsRows * kLightRowDoubles];
+    __shared__ __attribute__((aligned(16))) double cdf_lds[kLightLdsRows];
+    __shared__ uint32_t wave_survivors[4];
+    global_tables_only(sc);
+    const AdvanceArgs &a = d.adv;
+    LightArgs la{};  // what the table's readers take
+    la.rows = d.rows;
+    la.cdf = d.cdf;
+    la.n_lights = d.n_lights;
+    stage_lights(la, rows_lds, cdf_lds);
+    const LightLds lds{rows_lds, cdf_lds};
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t n = a.count_in ? min(*a.count_in, a.capacity) : a.capacity;
+    const bool stepped = k < n && (!a.alive || a.alive[k] != 0);
+    bool scattered = false, lamp = false, sampled = false;
+    // what the density loop and the fold behind it read: the ray the density is asked along, the row's id, its light and weights
+    Vec along_o = mk(0.0, 0.0, 0.0), along_d = mk(0.0, 0.0, 1.0), light = mk(0.0, 0.0, 0.0);
+    double along_tm = 0.0, other = 0.0, distance = 0.0;
+    int32_t id = -1;
+    if (stepped) {
+        Ray ray = caller_ray(a.origin, a.direction, a.time, a.time_all, k);
+        Xorwow rng;
+        if (a.rng_in) {  // {d, v0..v4} as rt_rng_state writes them
+            const uint32_t *w = a.rng_in + (size_t)k * 6;
+            rng.d = w[0]; rng.v0 = w[1]; rng.v1 = w[2]; rng.v2 = w[3]; rng.v3 = w[4]; rng.v4 = w[5];
+        } else {  // curand_init(seed, k + first_sequence, 0)
+            rng = a.base;
+            xorwow_skip_sequences(a.jump_table, a.first_sequence + (uint64_t)k, rng);
+        }
+        const NodeView nv{sc.nodes, 0u, false};
+        Vec throughput = mk(1.0, 1.0, 1.0), accumulated = mk(0.0, 0.0, 0.0);
+        HitInfo h;
+        h.t = 0.0;
+        h.ref = kNone;
+        h.obj = kNone;
+        bool hit = false;
+        if constexpr (T::WORLD == 0) {
+            if (sc.n_world_nodes != 0) {
+                Walk w{};
+                walk_begin<false>(w, ray, DBL_MAX);
+                while (w.state != kNone) {
+                    if (walk_moving(w.state)) walk_node<false>(nv, ray, 0.001, w);
+                    else walk_leaves<T>(sc, nv, ray, 0.001, w, h, rng);
+                }
+                hit = w.any;
+            }
+        } else {
+            hit = world_hit_list<T>(sc, ray, 0.001, DBL_MAX, h, rng);
+        }
+        Vec normal = mk(0.0, 0.0, 0.0);
+        uint32_t kind = 255u;
+        bool front = false;
+        if (!hit) {  // R/kernel.cu:74-79
+            accumulated = accumulated + throughput * load3c(((const RT_CONST CameraRec *)(uintptr_t)sc.camera)->bg);
+        } else {
+            const Surface s = make_surface<T>(sc, ray, h);
+            if ((h.ref >> kRefShift) != REF_MEDIUM) normal = s.n;
+            front = s.front;
+            kind = material_view<false>(sc, s.mat).u32(MAT_OFF(kind));
+            scattered = shade<T>(sc, s, ray, throughput, accumulated, rng);  // scattered: `ray` is the next ray; else it is untouched
+        }
+        normal = mk(0.0, 0.0, 0.0) + normal;  // as query_kernel: no negative zeros
+        const Vec carried = a.throughput ? mk(a.throughput[(size_t)k * 3 + 0], a.throughput[(size_t)k * 3 + 1], a.throughput[(size_t)k * 3 + 2])
+                                         : mk(1.0, 1.0, 1.0);
+        id = a.ray_id ? a.ray_id[k] : (int32_t)k;
+        const double sent = d.scatter_pdf ? d.scatter_pdf[k] : 0.0;  // the density the bounce before sent this ray with
+        if (!scattered) {
+            lamp = hit && kind == MAT_DIFFUSE_LIGHT && sent > 0.0 && a.radiance && id >= 0 && (uint32_t)id < a.sources;
+            if (lamp) {  // weighted behind the density loop, along the incoming ray as given
+                along_o = ray.o;
+                along_d = ray.d;
+                along_tm = ray.tm;
+                light = carried * accumulated;
+                other = sent;
+            } else if (a.radiance && id >= 0 && (uint32_t)id < a.sources) {  // w = 1: the plain advance's fold
+                const Vec product = carried * accumulated;
+                double *row = a.radiance + (size_t)id * 3;
+                const Vec sum = mk(row[0], row[1], row[2]) + product;
+                row[0] = sum.x;
+                row[1] = sum.y;
+                row[2] = sum.z;
+            }
+        } else {
+            const Vec next = carried * throughput;
+            double sent_next = 0.0;
+            if ((kind == MAT_LAMBERTIAN || kind == MAT_ISOTROPIC) && d.n_lights != 0 && d.sample != 0) {
+                // light_sample_kernel's sample for the point ray.o at the time ray.tm, from the path's stream
+                const Vec P = ray.o;
+                const double tm = ray.tm;
+                bool valid = false;
+                Vec dir = mk(0.0, 0.0, 0.0), emitted = mk(0.0, 0.0, 0.0), contribution = mk(0.0, 0.0, 0.0);
+                double pdf = 0.0, scatter = 0.0;
+                const double xi = (double)xorwow_uniform(rng);
+                uint32_t lo = 0, hi = d.n_lights - 1u;  // the first row with cdf >= xi; the last entry is 1.0 >= xi
+                while (lo < hi) {
+                    const uint32_t mid = (lo + hi) / 2u;
+                    if (light_cdf(la, lds, mid) >= xi) hi = mid;
+                    else lo = mid + 1u;
+                }
+                const double chance = light_cdf(la, lds, lo) - (lo ? light_cdf(la, lds, lo - 1u) : 0.0);
+                const LightRow L = light_row(la, lds, lo);
+                Vec S = mk(0.0, 0.0, 0.0), centre = mk(0.0, 0.0, 0.0);
+                double u = 0.0, v = 0.0;
+                if (L.kind <= LIGHT_TRIANGLE) {
+                    double ua = (double)xorwow_uniform(rng);
+                    double ub = (double)xorwow_uniform(rng);
+                    if (L.kind == LIGHT_TRIANGLE && ua + ub > 1.0) {
+                        ua = 1.0 - ua;
+                        ub = 1.0 - ub;
+                    }
+                    S = (load3(L.a) + ua * load3(L.b)) + ub * load3(L.c);
+                    const Vec D = S - P;
+                    const double d2 = dot(D, D);
+                    if (d2 > 0.0) {
+                        const double len = sqrt(d2);
+                        const Vec unit_d = over(D, len);
+                        const double c = fabs(dot(load3(L.n), unit_d));
+                        if (c != 0.0) {
+                            const double density = (d2 / (c * L.s)) * chance;
+                            if (usable_density(density)) {
+                                valid = true;
+                                dir = unit_d;
+                                distance = len;
+                                pdf = density;
+                            }
+                        }
+                    }
+                    u = ua;
+                    v = ub;
+                } else {
+                    Vec p;
+                    double s;
+                    do {  // the lens loop of camera_ray
+                        const double da = (double)xorwow_uniform(rng);
+                        const double db = (double)xorwow_uniform(rng);
+                        p = mk(2.0 * da - 1.0, 2.0 * db - 1.0, 0.0);
+                        s = p.x * p.x + p.y * p.y;
+                    } while (!(s < 1.0 && s > 0.0));
+                    centre = light_centre(L, tm);
+                    const Vec oc = centre - P;
+                    const double d2 = dot(oc, oc), r2 = L.s * L.s;
+                    if (d2 > r2) {
+                        const Vec w = over(oc, sqrt(d2));
+                        const double cosmax = sqrt(1.0 - r2 / d2);
+                        const double omc = 1.0 - cosmax;
+                        const double z = 1.0 - s * omc;
+                        const double rho = sqrt(1.0 - z * z);
+                        const double q = sqrt(s);
+                        const double ex = (rho * p.x) / q, ey = (rho * p.y) / q;
+                        const double ax = fabs(w.x), ay = fabs(w.y), az = fabs(w.z);
+                        Vec e1;
+                        if (ax >= ay && ax >= az) e1 = over(mk(w.z, 0.0, -w.x), sqrt(w.z * w.z + w.x * w.x));
+                        else if (ay >= az) e1 = over(mk(-w.y, w.x, 0.0), sqrt(w.y * w.y + w.x * w.x));
+                        else e1 = over(mk(0.0, -w.z, w.y), sqrt(w.z * w.z + w.y * w.y));
+                        const Vec e2 = cross(w, e1);
+                        const Vec g = (z * w + ex * e1) + ey * e2;
+                        const Vec unit_d = over(g, sqrt(dot(g, g)));
+                        const Vec po = P - centre;
+                        const double qa = dot(unit_d, unit_d), qb = dot(po, unit_d), qc = dot(po, po) - r2;
+                        const double disc = qb * qb - qa * qc;
+                        const double len = (-qb - sqrt(disc)) / qa;
+                        const double density = chance / ((2.0 * kLightPi) * omc);
+                        if (omc != 0.0 && usable_density(density) && disc > 0.0 && len > 0.0) {
+                            valid = true;
+                            dir = unit_d;
+                            distance = len;
+                            pdf = density;
+                            S = P + len * unit_d;
+                        }
+                    }
+                }
+                if (valid) {
+                    const MatView mp = material_view<false>(sc, L.mat);
+                    if (L.kind >= LIGHT_SPHERE && mp.u32(MAT_OFF(needs_uv)) != 0) sphere_uv((1 / L.s) * (S - centre), u, v);
+                    emitted = material_texture<T>(sc, mp, mp.u32(MAT_OFF(tex_inline)), u, v, S);
+                    if (kind == MAT_LAMBERTIAN) {
+                        const double c = dot(normal, dir);
+                        if (c > 0.0) scatter = (2.0 * ((c * c) * c)) / kLightPi;
+                    } else {
+                        scatter = 1.0 / (4.0 * kLightPi);
+                    }
+                    if (scatter != 0.0) contribution = (scatter / pdf) * emitted;
+                }
+                sampled = contribution.x != 0.0 || contribution.y != 0.0 || contribution.z != 0.0;
+                if (sampled) {  // weighted behind the density loop, along the sample
+                    along_o = P;
+                    along_d = dir;
+                    along_tm = tm;
+                    light = next * contribution;
+                    other = scatter;
+                }
+                // the density with which the material sent the scattered ray where it goes: the closed form above for its unit direction
+                const Vec unit_next = (1 / sqrt((ray.d.x * ray.d.x + ray.d.y * ray.d.y) + ray.d.z * ray.d.z)) * ray.d;
+                if (kind == MAT_LAMBERTIAN) {
+                    const double c = dot(normal, unit_next);
+                    if (c > 0.0) sent_next = (2.0 * ((c * c) * c)) / kLightPi;
+                } else {
+                    sent_next = 1.0 / (4.0 * kLightPi);
+                }
+            }
+            if (a.stage.origin) store3(a.stage.origin, k, ray.o);
+            if (a.stage.direction) store3(a.stage.direction, k, ray.d);
+            if (a.stage.time) a.stage.time[k] = ray.tm;
+            if (a.stage.rng_state) {  // the stream after the last draw, the sample's included
+                uint32_t *w = a.stage.rng_state + (size_t)k * 6;
+                w[0] = rng.d; w[1] = rng.v0; w[2] = rng.v1; w[3] = rng.v2; w[4] = rng.v3; w[5] = rng.v4;
+            }
+            if (a.stage.throughput) store3(a.stage.throughput, k, next);
+            if (a.stage.ray_id) a.stage.ray_id[k] = id;
+            if (a.stage.t) a.stage.t[k] = h.t;
+            if (a.stage.normal) store3(a.stage.normal, k, normal);
+            if (a.stage.front_face) a.stage.front_face[k] = front ? 1 : 0;
+            if (a.stage.material) a.stage.material[k] = (uint8_t)kind;
+            d.scatter_pdf_stage[k] = sent_next;
+        }
+    }
+    // every lane of the workgroup is here again.  The mixture density along `along`: light_pdf_kernel's loop, every lane of the wave
+    // on row i (a lane that needs none runs it on a ray of its own that meets what it meets: its sum is not read)
+    double density_sum = 0.0;
+    if (__ballot(lamp || sampled) != 0ull) {
+        const Vec o = along_o, dv = along_d;
+        const double tm = along_tm;
+        const double dd = dot(dv, dv);
+        double before = 0.0;
+        for (uint32_t i = 0; i < d.n_lights; i++) {
+            const LightRow L = light_row(la, lds, i);
+            const double upto = light_cdf(la, lds, i);
+            const double chance = upto - before;
+            before = upto;
+            double density = 0.0;
+            if (L.kind <= LIGHT_TRIANGLE) {
+                const Vec nn = load3(L.n), Q = load3(L.a), U = load3(L.b), V = load3(L.c);
+                const double denom = dot(nn, dv);
+                if (denom != 0.0) {
+                    const double t = dot(nn, Q - o) / denom;
+                    if (t > 0.0) {
+                        const Vec ph = (o + t * dv) - Q;
+                        const Vec m = cross(U, V);
+                        const double mm = dot(m, m);
+                        const double alpha = dot(m, cross(ph, V)) / mm, beta = dot(m, cross(U, ph)) / mm;
+                        const bool below = L.kind == LIGHT_TRIANGLE ? alpha + beta <= 1.0 : (alpha <= 1.0 && beta <= 1.0);
+                        if (0.0 <= alpha && 0.0 <= beta && below) density = (((t * t) * dd) / ((fabs(denom) / sqrt(dd)) * L.s)) * chance;
+                    }
+                }
+            } else {
+                const Vec oc = light_centre(L, tm) - o;
+                const double d2 = dot(oc, oc), r2 = L.s * L.s;
+                if (d2 > r2) {
+                    const double b = dot(oc, dv);
+                    const double disc = b * b - dd * (d2 - r2);
+                    if (b > 0.0 && disc >= 0.0) {
+                        const double omc = 1.0 - sqrt(1.0 - r2 / d2);
+                        if (omc != 0.0) density = chance / ((2.0 * kLightPi) * omc);
+                    }
+                }
+            }
+            if (usable_density(density)) density_sum = density_sum + density;
+        }
+    }
+    if (lamp) {  // w = q / (q + p): the scattered ray found the lamp a light sample of the bounce before could have found
+        const double w = other / (other + density_sum);
+        double *row = a.radiance + (size_t)id * 3;
+        const Vec sum = mk(row[0], row[1], row[2]) + w * light;
+        row[0] = sum.x;
+        row[1] = sum.y;
+        row[2] = sum.z;
+    }
+    if (sampled) {  // w = p / (p + s); the shadow ray decides in launch 2
+        const double both = density_sum + other;
+        const double w = both == 0.0 ? 0.0 : density_sum / both;
+        store3(d.shadow_direction, k, along_d);
+        d.shadow_distance[k] = distance;
+        store3(d.shadow_radiance, k, w * light);
+    }
+    if (k < a.capacity) {
+        a.survivor[k] = scattered ? 1 : 0;
+        d.pending[k] = sampled ? 1 : 0;
+    }
+    const unsigned long long survivors = __ballot(scattered);
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    if (lane == 0) wave_survivors[wave] = (uint32_t)__popcll(survivors);
+    if (a.stepped_counter) {  // one atomic per wave
+        const unsigned long long took = __ballot(stepped);
+        if (lane == 0 && took) atomicAdd(a.stepped_counter, (unsigned long long)__popcll(took));
+    }
+    if (d.shadow_counters) {
+        const unsigned long long cast = __ballot(sampled);
+        if (lane == 0 && cast) atomicAdd(d.shadow_counters, (unsigned long long)__popcll(cast));
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) a.block_counts[blockIdx.x] = (wave_survivors[0] + wave_survivors[1]) + (wave_survivors[2] + wave_survivors[3]);
+}
+
+// Launch 2: row k's shadow ray (staged origin, shadow direction, staged time) over (0.001, distance * (1 - 2^-20)), searched as
+// query_kernel searches in occlusion mode.  Only a medium's test draws: from the row's staged stream, which is written back.
+template <int STRICT, class T>
+__global__ __launch_bounds__(256) void shadow_kernel(DeviceScene sc, AdvanceDirectArgs d)
+{
+    global_tables_only(sc);
+    const AdvanceArgs &a = d.adv;
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    const bool pending = k < a.capacity && d.pending[k] != 0;
+    if (__ballot(pending) == 0ull) return;  // (the whole wave: no barrier in this kernel)
+    bool reached = false;
+    if (pending) {
+        Ray ray;
+        ray.o = mk(a.stage.origin[(size_t)k * 3 + 0], a.stage.origin[(size_t)k * 3 + 1], a.stage.origin[(size_t)k * 3 + 2]);
+        ray.d = mk(d.shadow_direction[(size_t)k * 3 + 0], d.shadow_direction[(size_t)k * 3 + 1], d.shadow_direction[(size_t)k * 3 + 2]);
+        ray.tm = a.stage.time[k];
+        const double tmax = fmin(d.shadow_distance[k] * (1.0 - 0x1p-20), DBL_MAX);
+        const bool media = (sc.flags & SCENE_HAS_MEDIA) != 0;
+        Xorwow rng{};
+        uint32_t *w = a.stage.rng_state + (size_t)k * 6;
+        if (media) {
+            rng.d = w[0]; rng.v0 = w[1]; rng.v1 = w[2]; rng.v2 = w[3]; rng.v3 = w[4]; rng.v4 = w[5];
+        }
+        HitInfo h;
+        uint32_t leaf = kNone;
+        reached = !query_search<T>(sc, d.node_leaf_pos, ray, 0.001, tmax, !media, h, leaf, rng);  // a medium's answer depends on what was found before it: the full search
+        if (media) {
+            w[0] = rng.d; w[1] = rng.v0; w[2] = rng.v1; w[3] = rng.v2; w[4] = rng.v3; w[5] = rng.v4;
+        }
+        const int32_t id = a.stage.ray_id[k];
+        if (reached && a.radiance && id >= 0 && (uint32_t)id < a.sources) {
+            double *row = a.radiance + (size_t)id * 3;
+            const Vec sum = mk(row[0], row[1], row[2]) +
+                            mk(d.shadow_radiance[(size_t)k * 3 + 0], d.shadow_radiance[(size_t)k * 3 + 1], d.shadow_radiance[(size_t)k * 3 + 2]);
+            row[0] = sum.x;
+            row[1] = sum.y;
+            row[2] = sum.z;
+        }
+    }
+    if (d.shadow_counters) {  // one atomic per wave
+        const unsigned long long found = __ballot(reached);
+        if ((threadIdx.x & 63u) == 0 && found) atomicAdd(d.shadow_counters + 1, (unsigned long long)__popcll(found));
+    }
+}
+
+hipError_t RT_CAT(launch_advance_direct_, RT_SUFFIX)(const DeviceScene &sc, const AdvanceDirectArgs &a, hipStream_t stream, QueryKernelInfo *info)
+{
+    const AdvanceArgs &v = a.adv;
+    if (!info && (!v.origin || !v.direction || !v.survivor || !v.block_counts || !v.stage.origin || !v.stage.time || !v.stage.rng_state ||
+                  !v.stage.ray_id || !a.scatter_pdf_stage || !a.shadow_direction || !a.shadow_distance || !a.shadow_radiance || !a.pending))
+        return hipErrorInvalidValue;
+    if (!info && a.n_lights != 0 && (!a.rows || !a.cdf)) return hipErrorInvalidValue;
+    void (*kernel)(DeviceScene, AdvanceDirectArgs) =
+        sc.world_kind == WORLD_BVH ? advance_direct_kernel<RT_STRICT, TBvhNested> : advance_direct_kernel<RT_STRICT, TListNested>;
+    return info_or_launch(kernel, sc, a, v.capacity, stream, info);
+}
+
+hipError_t RT_CAT(launch_advance_shadow_, RT_SUFFIX)(const DeviceScene &sc, const AdvanceDirectArgs &a, hipStream_t stream, QueryKernelInfo *info)
+{
+    const AdvanceArgs &v = a.adv;
+    if (!info && (!v.stage.origin || !v.stage.time || !v.stage.rng_state || !v.stage.ray_id || !a.shadow_direction || !a.shadow_distance ||
+                  !a.shadow_radiance || !a.pending))
+        return hipErrorInvalidValue;
+    if (!info && sc.world_kind == WORLD_BVH && !a.node_leaf_pos) return hipErrorInvalidValue;
+    void (*kernel)(DeviceScene, AdvanceDirectArgs) =
+        sc.world_kind == WORLD_BVH ? shadow_kernel<RT_STRICT, TBvhNested> : shadow_kernel<RT_STRICT, TListNested>;
+    return info_or_launch(kernel, sc, a, v.capacity, stream, info);
+}
+#elif RT_LANE_UNIT
+// (a lane-per-ray unit defined above)
 #elif RT_GROUP == 1
 namespace {
 template <bool AD>

@@ -258,6 +258,43 @@ hipError_t launch_advance_scan(const uint32_t *block_counts, uint32_t *block_off
 hipError_t launch_advance_gather(const AdvanceGatherArgs &a, hipStream_t stream);
 constexpr uint32_t kAdvanceBlock = 256;  // rows per workgroup of launches 1 and 3
 
+// Path advances with light samples (rt_scene_path_advance_direct; the RT_ADVANCE_DIRECT objects of render.hip and advance_pack.hip):
+// four launches on one stream.
+//   1. advance_direct_kernel: advance_kernel's iteration, then, behind its reconvergence point, the light sample of the rows that
+//      scattered from a diffuse or isotropic hit and one wave-uniform loop over the light table (staged in LDS as the light kernels
+//      stage it) for the mixture density a lane needs: along its incoming ray where it ended on a lamp with a density carried in,
+//      along its sample direction where it scattered.  A weighted lamp is folded here; a light sample that can add something
+//      leaves its shadow ray, its weighted contribution and pending[k] = 1 at its row of the workspace.  stage.time and
+//      stage.rng_state of `adv` are always given: launch 2 reads them.
+//   2. shadow_kernel: one lane per row; a pending row searches the world as an occlusion query does, from the staged stream,
+//      which it writes back where the scene has media, and adds its contribution to `radiance` where the lamp is visible.  A wave
+//      without pending rows leaves at once.
+//   3, 4. the scan and the gather of the plain advance; the gather moves scatter_pdf as well.
+struct AdvanceDirectArgs {
+    AdvanceArgs adv;
+    const LightRow *rows;               // n_lights
+    const double *cdf;                  // the cumulative table of the call's strategy, padded to an even length
+    uint32_t n_lights;
+    int32_t sample;                     // 1: draw a light sample at every diffuse or isotropic hit
+    const double *scatter_pdf;          // capacity, or nullptr: all 0
+    double *scatter_pdf_stage;          // capacity: the density the scattered ray was sent with, 0 where no sample was drawn
+    double *shadow_direction, *shadow_distance, *shadow_radiance;  // capacity x 3, x 1, x 3: written where pending[k] is set
+    uint8_t *pending;                   // capacity
+    const uint32_t *node_leaf_pos;      // as QueryArgs
+    unsigned long long *shadow_counters;  // two words, zeroed by the caller: shadow rays cast, shadow rays that reached their lamp; nullptr: not counted
+};
+struct AdvanceDirectGatherArgs {
+    AdvanceGatherArgs rows;
+    const double *scatter_pdf_from;
+    double *scatter_pdf_to;             // nullptr: not asked for
+};
+// info != nullptr: report the instantiation that would run instead of launching it
+hipError_t launch_advance_direct_strict(const DeviceScene &sc, const AdvanceDirectArgs &a, hipStream_t stream, QueryKernelInfo *info = nullptr);
+hipError_t launch_advance_direct_fast(const DeviceScene &sc, const AdvanceDirectArgs &a, hipStream_t stream, QueryKernelInfo *info = nullptr);
+hipError_t launch_advance_shadow_strict(const DeviceScene &sc, const AdvanceDirectArgs &a, hipStream_t stream, QueryKernelInfo *info = nullptr);
+hipError_t launch_advance_shadow_fast(const DeviceScene &sc, const AdvanceDirectArgs &a, hipStream_t stream, QueryKernelInfo *info = nullptr);
+hipError_t launch_advance_direct_gather(const AdvanceDirectGatherArgs &a, hipStream_t stream);
+
 // Light sampling queries (rt_scene_sample_lights, rt_scene_light_pdf; the RT_LIGHTS objects of render.hip): one lane per point or
 // ray, 256-thread workgroups that first stage the first kLightLdsRows rows of the light table and of its cumulative table in LDS.
 // The table is not part of DeviceScene: it comes through these arguments.  `sc` is still passed, for the material and texture
