@@ -988,6 +988,61 @@ RTOW_API uint64_t rt_path_advance_direct_workspace_bytes(int64_t count);
 /* sizeof of rt_path_advance_direct_params, _rays, _out, _stats as this library was compiled */
 RTOW_API void rt_path_advance_direct_abi_sizes(uint32_t out4[4]);
 
+/* ---- radiance queries with light samples: the MIS estimator of the advances above in one call ----
+ * rt_scene_radiance with every sample replaced by the estimator rt_scene_path_advance_direct states: one launch, any number of
+ * samples, no workspace.  Rays, streams and outputs are rt_scene_radiance's (rt_radiance_rays and rt_radiance_out as they are).
+ * Every operation below is one IEEE-754 double operation in the order written in the strict build; the fast build may fuse.
+ * Sample s of ray k is the fold of rt_scene_path_advance_direct over one path: thr = (1, 1, 1), acc = (0, 0, 0), q = 0, the
+ * ray as given, the stream R where the sample before left it (sample 0: the ray's stream).  At most max_depth bounces; bounce
+ * b = 0, 1, ... is one row of that call with throughput thr, scatter_pdf q, params->strategy, and sample = 1 where
+ * b + 1 < max_depth, sample = 0 at the last -- in this order:
+ *   1. the step's draws.  A path that ends (status 0 or 1) does acc = acc + (thr * E) * w, w = q / (q + p) only where status is 1,
+ *      the material is a diffuse light and q > 0 (p as stated there, along the incoming ray as given); in every other case w = 1
+ *      and the term is thr * E.  The sample is over.
+ *   2. status 2: thr' = thr * A.  Where the hit is Lambertian or isotropic, the scene has lights and sample is 1: the light
+ *      sample's draws, and, where its contribution C is not all zero, L = (thr' * C) * w with w = p / (p + s), 0 where p + s == 0.
+ *   3. the shadow ray (o', dir, tm) over (0.001, distance * (1 - 2^-20)), searched as rt_scene_intersect mode 1 searches; a
+ *      ConstantMedium draws from the path's own stream.  Where the lamp is reached, acc = acc + L.
+ *   4. the survivor goes on with thr', (o', d', tm), the stream after the last draw and q' as stated there (0 where no sample
+ *      was drawn).  A path still alive after bounce max_depth - 1 is dropped.
+ * Then sum = sum + acc (sum starts at (0, 0, 0)) and the next sample starts from the same ray with the stream where it stands.
+ * Outputs as rt_scene_radiance: radiance = the mean as that call forms it; path_rays counts the path searches only (the shadow
+ * searches are in the statistics); rng_state is the stream after the last draw, and may alias the input.
+ * With samples == 1 the radiance is what max_depth calls of rt_scene_path_advance_direct fold for the ray, to the bit in the strict
+ * build.  max_depth == 0: black, nothing searched, nothing drawn.  max_depth == 1, or a scene without lights: rt_scene_radiance to
+ * the bit in the strict build.  The expectation is rt_scene_radiance's for every max_depth.
+ * Both calls return when the results are there.  Refusals, all before the device is touched: rt_scene_radiance's, in its order,
+ * then a strategy other than 0 / 1.  count == 0 returns RT_OK without a launch.  Termination as for rt_scene_radiance, with at
+ * most as many shadow searches as path searches. */
+typedef struct rt_radiance_direct_params {
+    int64_t  count;            /* as rt_radiance_params, field for field ... */
+    int32_t  samples;
+    int32_t  max_depth;
+    double   time;
+    uint64_t seed;
+    uint64_t first_sequence;
+    int32_t  variant;
+    int32_t  device;
+    void    *stream;
+    int32_t  reserved[4];
+    int32_t  strategy;         /* ... and: 0 uniform over lights, 1 by area x brightest channel, as rt_light_params */
+    int32_t  reserved2[3];
+} rt_radiance_direct_params;
+typedef struct rt_radiance_direct_stats {
+    uint64_t rays;                            /* the sum of path_rays: path searches */
+    uint64_t shadow_rays, shadow_reached;     /* shadow rays cast; those that reached their lamp */
+    double seconds;                           /* the kernel, HIP events */
+    uint32_t kernel_vgprs, scratch_bytes;     /* of the instantiation that ran: registers, private memory per lane */
+} rt_radiance_direct_stats;
+/* rays and out hold device pointers (on params->device).  stats may be NULL: the call is then the launch and the wait alone. */
+RTOW_API int rt_scene_radiance_direct_device(rt_scene *s, const rt_radiance_direct_params *params, const rt_radiance_rays *rays,
+                                             const rt_radiance_out *out, rt_radiance_direct_stats *stats);
+/* the same on host arrays (uploaded, traced, copied back) */
+RTOW_API int rt_scene_radiance_direct(rt_scene *s, const rt_radiance_direct_params *params, const rt_radiance_rays *rays,
+                                      const rt_radiance_out *out, rt_radiance_direct_stats *stats);
+/* sizeof of rt_radiance_direct_params, rt_radiance_rays, rt_radiance_out, rt_radiance_direct_stats as this library was compiled */
+RTOW_API void rt_radiance_direct_abi_sizes(uint32_t out4[4]);
+
 /* Convenience: create film, upload, render 1 GPU, download.  frame = W*H*3 doubles. */
 RTOW_API int rt_render(rt_scene *s, const rt_render_params *params, double *frame, rt_render_stats *stats);
 

@@ -212,6 +212,14 @@ public:
                               : rt_scene_path_advance_direct(s_, &params, &rays, &out, stats));
     }
 
+    // Whole paths with those light samples, any number of samples a ray, in one launch (rtow.h "radiance queries with light
+    // samples"): rays and outputs are the plain radiance query's structs.  The call returns when the results are there.
+    void RadianceDirect(const rt_radiance_direct_params &params, const rt_radiance_rays &rays, const rt_radiance_out &out,
+                        rt_radiance_direct_stats *stats = nullptr, bool device_pointers = true)
+    {
+        check(device_pointers ? rt_scene_radiance_direct_device(s_, &params, &rays, &out, stats) : rt_scene_radiance_direct(s_, &params, &rays, &out, stats));
+    }
+
 private:
     rt_handle ok(rt_handle h)
     {

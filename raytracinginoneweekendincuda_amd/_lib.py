@@ -85,6 +85,16 @@ class RadianceStats(C.Structure):
     _fields_ = [("rays", C.c_uint64), ("seconds", C.c_double), ("kernel_vgprs", C.c_uint32), ("scratch_bytes", C.c_uint32)]
 
 
+# rt_radiance_direct_*: rt_radiance_params field for field and the strategy behind it; the rays and the outputs are the plain call's
+class RadianceDirectParams(C.Structure):
+    _fields_ = RadianceParams._fields_ + [("strategy", C.c_int32), ("reserved2", C.c_int32 * 3)]
+
+
+class RadianceDirectStats(C.Structure):
+    _fields_ = [("rays", C.c_uint64), ("shadow_rays", C.c_uint64), ("shadow_reached", C.c_uint64), ("seconds", C.c_double),
+                ("kernel_vgprs", C.c_uint32), ("scratch_bytes", C.c_uint32)]
+
+
 class PathStepParams(C.Structure):
     _fields_ = [("count", C.c_int64), ("time", C.c_double), ("seed", C.c_uint64), ("first_sequence", C.c_uint64), ("variant", C.c_int32),
                 ("device", C.c_int32), ("stream", C.c_void_p), ("reserved", C.c_int32 * 4)]
@@ -330,6 +340,9 @@ SIGNATURES = {
     "rt_scene_path_advance_direct": (I, [P, C.POINTER(PathAdvanceDirectParams), C.POINTER(PathAdvanceDirectRays), C.POINTER(PathAdvanceDirectOut), C.POINTER(PathAdvanceDirectStats)]),
     "rt_path_advance_direct_workspace_bytes": (C.c_uint64, [C.c_int64]),
     "rt_path_advance_direct_abi_sizes": (None, [C.POINTER(C.c_uint32)]),
+    "rt_scene_radiance_direct_device": (I, [P, C.POINTER(RadianceDirectParams), C.POINTER(RadianceRays), C.POINTER(RadianceOut), C.POINTER(RadianceDirectStats)]),
+    "rt_scene_radiance_direct": (I, [P, C.POINTER(RadianceDirectParams), C.POINTER(RadianceRays), C.POINTER(RadianceOut), C.POINTER(RadianceDirectStats)]),
+    "rt_radiance_direct_abi_sizes": (None, [C.POINTER(C.c_uint32)]),
     "rt_deinterleave": (I, [D3, I, I, I, I, C.c_size_t, D3]),
     "rt_render": (I, [P, C.POINTER(RenderParams), D3, C.POINTER(RenderStats)]),
     "rt_write_ppm": (I, [C.c_char_p, D3, I, I]),
@@ -360,7 +373,9 @@ def load():
                                     ("rt_path_step_*", lib.rt_path_step_abi_sizes, (PathStepParams, PathStepRays, PathStepOut, PathStepStats)),
                                     ("rt_path_advance_*", lib.rt_path_advance_abi_sizes, (PathAdvanceParams, PathAdvanceRays, PathAdvanceOut, PathAdvanceStats)),
                                     ("rt_path_advance_direct_*", lib.rt_path_advance_direct_abi_sizes,
-                                     (PathAdvanceDirectParams, PathAdvanceDirectRays, PathAdvanceDirectOut, PathAdvanceDirectStats))):
+                                     (PathAdvanceDirectParams, PathAdvanceDirectRays, PathAdvanceDirectOut, PathAdvanceDirectStats)),
+                                    ("rt_radiance_direct_*", lib.rt_radiance_direct_abi_sizes,
+                                     (RadianceDirectParams, RadianceRays, RadianceOut, RadianceDirectStats))):
         sizes = (C.c_uint32 * 4)()
         sizes_of(sizes)
         ours = [C.sizeof(x) for x in structs]

@@ -17,6 +17,7 @@ from ._lib import (AdaptiveParams, DenoiseParams, FeatureParams, LaunchPlan, Lig
                    PathAdvanceOut, PathAdvanceParams, PathAdvanceRays, PathAdvanceStats,
                    PathAdvanceDirectOut, PathAdvanceDirectParams, PathAdvanceDirectRays, PathAdvanceDirectStats,
                    PathStepOut, PathStepParams, PathStepRays, PathStepStats, RadianceOut, RadianceParams, RadianceRays, RadianceStats,
+                   RadianceDirectParams, RadianceDirectStats,
                    RenderParams, RenderStats, SceneInfo)
 
 
@@ -429,7 +430,7 @@ class Scene:
 
     # ---- radiance queries (include/rtow.h rt_scene_radiance) ----
     def radiance(self, origins, directions, times=None, samples=1, max_depth=50, time=0.0, seed=1984, first_sequence=0, rng_state=None,
-                 variant=0, want=("radiance",), device=0, stats=False):
+                 variant=0, want=("radiance",), device=0, stats=False, direct=None, strategy=1):
         """The light that comes back along every ray ``origins[k] + t * directions[k]`` (both (count, 3) float64): ``samples`` paths
         per ray, each the reference's ``RayColor`` with ``max_depth`` bounces, all from the ray's one stream (include/rtow.h
         rt_scene_radiance has the rules).  ``times`` may be a (count,) array or None (``time`` for all rays).  ``rng_state`` is a
@@ -439,18 +440,31 @@ class Scene:
         stream after its last draw.  numpy arrays take the host call and come back as numpy arrays; torch CUDA tensors are read in
         place, on ``torch.cuda.current_stream()``, and come back as tensors on the same device (``rng_state`` then of dtype uint32 or
         int32; the output has the input's dtype, uint32 without one).  Other dtypes, shapes and non-contiguous inputs raise RtowError:
-        nothing is converted silently.  ``stats=True``: (outputs, RadianceStats)."""
+        nothing is converted silently.  ``stats=True``: (outputs, RadianceStats).
+        ``direct="mis"``: every sample is the estimator of ``PathBatch(direct="mis", strategy=strategy).run(max_depth)`` instead --
+        a light sample, its shadow ray and the MIS weights at every diffuse hit but the last bounce's -- in the same one launch
+        (include/rtow.h rt_scene_radiance_direct); the expectation is the same, "path_rays" counts the path's own searches, and
+        ``stats=True`` gives RadianceDirectStats, with the shadow rays.  ``direct=None``: the plain call, whatever ``strategy`` says."""
+        if direct not in (None, "mis"):
+            raise RtowError('direct must be None or "mis"')
+        if direct and strategy not in (0, 1):
+            raise RtowError("strategy must be 0 (uniform) or 1 (by area and brightness)")
+
         def structs(count, rays, outs, device, stream):   # (its own refusals after the engine's, as they always came)
             if not outs:
                 raise RtowError("want: at least one of " + ", ".join(_lib.RADIANCE_OUTPUTS))
             if not isinstance(samples, numbers.Integral) or not isinstance(max_depth, numbers.Integral):
                 raise RtowError("samples and max_depth are integers")
-            p = RadianceParams(count, int(samples), int(max_depth), float(time), int(seed), int(first_sequence), int(variant), device, stream)
+            params = (count, int(samples), int(max_depth), float(time), int(seed), int(first_sequence), int(variant), device, stream)
+            p = RadianceDirectParams(*params, (C.c_int32 * 4)(), int(strategy)) if direct else RadianceParams(*params)
             return p, RadianceRays(*(rays.get(n) for n in ("origins", "directions", "times", "rng_state"))), RadianceOut(**outs)
 
         inputs = [("times", times, (), ("float64",), False), ("rng_state", rng_state, (6,), ("uint32", "int32"), False)]
-        out, st = self._ray_batch("radiance", origins, directions, inputs, _lib.RADIANCE_OUTPUTS, tuple(want),
-                                  (lib().rt_scene_radiance, lib().rt_scene_radiance_device), structs, RadianceStats if stats else None, device)
+        calls, stats_type = (lib().rt_scene_radiance, lib().rt_scene_radiance_device), RadianceStats
+        if direct:
+            calls, stats_type = (lib().rt_scene_radiance_direct, lib().rt_scene_radiance_direct_device), RadianceDirectStats
+        out, st = self._ray_batch("radiance", origins, directions, inputs, _lib.RADIANCE_OUTPUTS, tuple(want), calls, structs,
+                                  stats_type if stats else None, device)
         return (out, st) if stats else out
 
     # ---- path steps (include/rtow.h rt_scene_path_step) ----

@@ -499,14 +499,15 @@ struct Build {
     hipError_t (*light_pdf)(const DeviceScene &, const LightArgs &, hipStream_t, QueryKernelInfo *);
     hipError_t (*advance_direct)(const DeviceScene &, const AdvanceDirectArgs &, hipStream_t, QueryKernelInfo *);
     hipError_t (*advance_shadow)(const DeviceScene &, const AdvanceDirectArgs &, hipStream_t, QueryKernelInfo *);
+    hipError_t (*radiance_direct)(const DeviceScene &, const RadianceDirectArgs &, hipStream_t, QueryKernelInfo *);
 };
 static const Build kBuilds[2] = {
     {launch_seed_strict, launch_render_strict, kernel_info_strict, launch_adaptive_rule_strict, launch_features_strict, launch_query_strict,
      launch_radiance_strict, launch_step_strict, launch_advance_strict, launch_light_sample_strict, launch_light_pdf_strict,
-     launch_advance_direct_strict, launch_advance_shadow_strict},
+     launch_advance_direct_strict, launch_advance_shadow_strict, launch_radiance_direct_strict},
     {launch_seed_fast, launch_render_fast, kernel_info_fast, launch_adaptive_rule_fast, launch_features_fast, launch_query_fast,
      launch_radiance_fast, launch_step_fast, launch_advance_fast, launch_light_sample_fast, launch_light_pdf_fast,
-     launch_advance_direct_fast, launch_advance_shadow_fast}};
+     launch_advance_direct_fast, launch_advance_shadow_fast, launch_radiance_direct_fast}};
 
 static int seed_film(FilmImpl &f, const rt_render_params *p, hipStream_t stream)
 {
@@ -1970,6 +1971,126 @@ void rt_path_advance_direct_abi_sizes(uint32_t out4[4])
     out4[1] = (uint32_t)sizeof(rt_path_advance_direct_rays);
     out4[2] = (uint32_t)sizeof(rt_path_advance_direct_out);
     out4[3] = (uint32_t)sizeof(rt_path_advance_direct_stats);
+}
+
+// ---- radiance queries with light samples ----
+// rt_radiance_direct_params begins with rt_radiance_params, field for field
+static_assert(sizeof(rt_radiance_direct_params) == sizeof(rt_radiance_params) + 4 * sizeof(int32_t) &&
+                  offsetof(rt_radiance_direct_params, strategy) == sizeof(rt_radiance_params) &&
+                  offsetof(rt_radiance_direct_params, stream) == offsetof(rt_radiance_params, stream) &&
+                  offsetof(rt_radiance_direct_params, variant) == offsetof(rt_radiance_params, variant),
+              "rt_radiance_direct_params: rt_radiance_params and the strategy behind it");
+
+// everything that can be refused without a device, in the order include/rtow.h lists it: rt_scene_radiance's, then the strategy
+static int radiance_direct_check(rt_scene *scene, const rt_radiance_direct_params *p, const rt_radiance_rays *rays, const rt_radiance_out *out,
+                                 const char *who)
+{
+    if (int rc = radiance_check(scene, reinterpret_cast<const rt_radiance_params *>(p), rays, out, who)) return rc;
+    if (p->strategy != 0 && p->strategy != 1) return fail(RT_ERR_INVALID, std::string(who) + ": strategy must be 0 (uniform) or 1 (by area and brightness)");
+    return RT_OK;
+}
+
+int rt_scene_radiance_direct_device(rt_scene *scene, const rt_radiance_direct_params *p, const rt_radiance_rays *rays, const rt_radiance_out *out,
+                                    rt_radiance_direct_stats *stats)
+{
+    const char *who = "rt_scene_radiance_direct_device";
+    if (int rc = radiance_direct_check(scene, p, rays, out, who)) return rc;
+    if (stats) *stats = rt_radiance_direct_stats{};
+    if (p->count == 0) return RT_OK;
+    SceneImpl &s = *S(scene);
+    if (int rc = rt_scene_upload(scene, p->device)) return rc;  // (selects the device)
+    DeviceTables &dt = *s.device[p->device];
+    RadianceDirectArgs da{};
+    RadianceArgs &ra = da.rad;
+    ra.origin = rays->origin;
+    ra.direction = rays->direction;
+    ra.time = rays->time;
+    ra.time_all = p->time;
+    ra.rng_in = rays->rng_state;
+    ra.radiance = out->radiance;
+    ra.path_rays = out->path_rays;
+    ra.rng_out = out->rng_state;
+    if (int rc = device_jump_table(p->device, &ra.jump_table)) return rc;
+    ra.base = xorwow_seed(p->seed, kSaltCurandDevice);
+    ra.first_sequence = p->first_sequence;
+    ra.count = (uint32_t)p->count;
+    ra.samples = p->samples;
+    ra.max_depth = p->max_depth;
+    da.rows = dt.lights;
+    da.cdf = dt.light_cdf[p->strategy];
+    da.n_lights = dt.n_lights;
+    da.node_leaf_pos = dt.node_leaf_pos;
+    hipStream_t stream = (hipStream_t)p->stream;
+    if (!stats) {  // the launch and the wait alone
+        hipError_t e = kBuilds[p->variant].radiance_direct(dt.scene, da, stream, nullptr);
+        const hipError_t waited = hipStreamSynchronize(stream);
+        if (e == hipSuccess) e = waited;
+        return e == hipSuccess ? RT_OK : hip_fail(e, who);
+    }
+    // with statistics: the kernel's registers, two events around it, and three words of this call's own for the counts
+    QueryKernelInfo info{};
+    HIP_TRY(kBuilds[p->variant].radiance_direct(dt.scene, da, stream, &info));
+    DeviceArena scratch(p->device);
+    unsigned long long *counters = nullptr;  // path searches, shadow rays cast, shadow rays that reached their lamp
+    HIP_TRY(scratch.alloc(3, counters));
+    ra.ray_counter = counters;
+    da.shadow_counters = counters + 1;
+    // from here on the chain: the events are destroyed, and the stream waited for, whatever fails
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    unsigned long long counted[3] = {0, 0, 0};
+    hipError_t e = hipEventCreate(&ev[0]);
+    if (e == hipSuccess) e = hipEventCreate(&ev[1]);
+    if (e == hipSuccess) e = hipMemsetAsync(counters, 0, sizeof counted, stream);
+    if (e == hipSuccess) e = hipEventRecord(ev[0], stream);
+    if (e == hipSuccess) e = kBuilds[p->variant].radiance_direct(dt.scene, da, stream, nullptr);
+    if (e == hipSuccess) e = hipEventRecord(ev[1], stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(counted, counters, sizeof counted, hipMemcpyDeviceToHost, stream);
+    const hipError_t waited = hipStreamSynchronize(stream);
+    if (e == hipSuccess) e = waited;
+    float ms = 0.0f;
+    if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev[0], ev[1]);
+    for (hipEvent_t v : ev)
+        if (v) hipEventDestroy(v);
+    if (e != hipSuccess) return hip_fail(e, who);
+    stats->rays = counted[0];
+    stats->shadow_rays = counted[1];
+    stats->shadow_reached = counted[2];
+    stats->seconds = (double)ms * 1e-3;
+    stats->kernel_vgprs = (uint32_t)info.vgprs;
+    stats->scratch_bytes = (uint32_t)info.scratch_bytes;
+    return RT_OK;
+}
+
+int rt_scene_radiance_direct(rt_scene *scene, const rt_radiance_direct_params *p, const rt_radiance_rays *rays, const rt_radiance_out *out,
+                             rt_radiance_direct_stats *stats)
+{
+    if (int rc = radiance_direct_check(scene, p, rays, out, "rt_scene_radiance_direct")) return rc;
+    if (stats) *stats = rt_radiance_direct_stats{};
+    if (p->count == 0) return RT_OK;
+    if (int rc = select_device(p->device)) return rc;
+    Staging stage{DeviceArena(p->device), (size_t)p->count, {}};
+    rt_radiance_rays dr{};
+    HIP_TRY(stage.in(rays->origin, 3, dr.origin));
+    HIP_TRY(stage.in(rays->direction, 3, dr.direction));
+    HIP_TRY(stage.in(rays->time, 1, dr.time));
+    HIP_TRY(stage.in(rays->rng_state, 6, dr.rng_state));
+    rt_radiance_out dout{};
+    HIP_TRY(stage.out(out->radiance, 3, dout.radiance));
+    HIP_TRY(stage.out(out->path_rays, 1, dout.path_rays));
+    HIP_TRY(stage.out(out->rng_state, 6, dout.rng_state));
+    rt_radiance_direct_params dp = *p;
+    dp.stream = nullptr;  // the copies around the query are synchronous: nothing to order on the caller's stream
+    if (int rc = rt_scene_radiance_direct_device(scene, &dp, &dr, &dout, stats)) return rc;
+    HIP_TRY(stage.fetch());
+    return RT_OK;
+}
+
+void rt_radiance_direct_abi_sizes(uint32_t out4[4])
+{
+    out4[0] = (uint32_t)sizeof(rt_radiance_direct_params);
+    out4[1] = (uint32_t)sizeof(rt_radiance_rays);
+    out4[2] = (uint32_t)sizeof(rt_radiance_out);
+    out4[3] = (uint32_t)sizeof(rt_radiance_direct_stats);
 }
 
 int rt_render(rt_scene *scene, const rt_render_params *params, double *frame, rt_render_stats *stats)

@@ -220,6 +220,7 @@ int main(int argc, char **argv)
     int pick_i = 0, pick_j = 0;
     bool radiance_at = false;    // --radiance-at i,j: the light that comes back along the centre ray of that pixel, one line, no render
     bool trace_at = false;       // --trace-at i,j: that path vertex by vertex (rt_scene_path_step), then --radiance-at's line
+    bool direct_mis = false;     // --direct mis: --radiance-at's samples are the MIS estimator with light samples (rt_scene_radiance_direct)
     bool list_lights = false;    // --lights: the scene's light table (rt_scene_dump_lights), a line per light, no render
     for (int k = 1; k < argc; k++) {
         std::string a = argv[k];
@@ -295,6 +296,13 @@ int main(int argc, char **argv)
             }
             pick = radiance_at = trace_at = true;
         }
+        else if (const char *v = val("--direct")) {
+            if (std::strcmp(v, "mis") != 0) {
+                std::fprintf(stderr, "--direct needs 'mis', not '%s'\n", v);
+                return 2;
+            }
+            direct_mis = true;
+        }
         else if (const char *v = val("--earth")) earth_path = v;
         else if (const char *v = val("--earth-bytes")) {
             earth_path = v;
@@ -306,13 +314,16 @@ int main(int argc, char **argv)
                          "            [--earth earthmap.jpg|decoded.ppm | --earth-bytes texture.ppm] [--accelerate-lists] [--flags N]\n"
                          "            [--noise T [--min-spp N] [--check-every K] [--samples-map file.pgm]]\n"
                          "            [--denoise [--denoise-iterations N] [--denoise-sigmas c,a,n,z] [--raw-output file.ppm]]\n"
-                         "            [--aov-prefix P] [--feature-samples N] [--pick i,j] [--radiance-at i,j] [--trace-at i,j] [--lights]\n"
+                         "            [--aov-prefix P] [--feature-samples N] [--pick i,j] [--radiance-at i,j [--direct mis]] [--trace-at i,j] [--lights]\n"
                          "  --lights       render nothing: print the light table (rt_scene_dump_lights), a line per emissive primitive in world space --\n"
                          "                 kind, world leaf, material row, geometry, and its entries of the two cumulative selection tables\n"
                          "  --pick         render nothing: print what the ray through the centre of pixel (i, j) hits (j = 0 is the bottom row) --\n"
                          "                 leaf, material kind, t, point, normal, albedo -- at the shutter's opening, over [0.001, inf)\n"
                          "  --radiance-at  render nothing: path-trace the same ray, --spp samples (default 1) of --depth bounces from the pixel's stream,\n"
                          "                 and print the linear radiance, the rays traced and the kernel's time\n"
+                         "  --direct mis   with --radiance-at: every sample takes a light sample at each diffuse hit and weights it against the lamps\n"
+                         "                 scattering finds (rt_scene_radiance_direct); the line then ends with the shadow rays cast and those that\n"
+                         "                 reached their lamp\n"
                          "  --trace-at     render nothing: the same paths one bounce at a time (rt_scene_path_step), a line per vertex -- sample, depth,\n"
                          "                 status (0 miss, 1 the path ends, 2 scattered), t, material, emitted, attenuation -- folded here, on the host;\n"
                          "                 the last line is --radiance-at's (to the last bit with --variant strict; its time is the steps' kernels')\n"
@@ -364,6 +375,10 @@ int main(int argc, char **argv)
         return 2;
     }
     if (radiance_at && spp < 0) spp = 1;
+    if (direct_mis && (!radiance_at || trace_at)) {
+        std::fprintf(stderr, "--direct goes with --radiance-at\n");
+        return 2;
+    }
     if (trace_at && (spp < 1 || depth < 0)) {  // (what rt_scene_radiance refuses for --radiance-at)
         std::fprintf(stderr, "--trace-at needs --spp >= 1 and --depth >= 0\n");
         return 2;
@@ -496,6 +511,29 @@ int main(int argc, char **argv)
             const double inv = 1 / (double)spp;
             std::printf("radiance %d,%d: samples %d radiance %.17g %.17g %.17g rays %u seconds %.9g\n", pick_i, pick_j, spp, inv * sum[0], inv * sum[1],
                         inv * sum[2], rays_traced, seconds);
+            rt_scene_destroy(scene);
+            return 0;
+        }
+        if (radiance_at && direct_mis) {  // the same query with light samples (rt_scene_radiance_direct), strategy 1
+            rt_radiance_direct_params rp{};
+            rp.count = 1;
+            rp.samples = spp;
+            rp.max_depth = depth;
+            rp.time = cam[25];
+            rp.seed = seed;
+            rp.first_sequence = (unsigned long long)pick_j * (unsigned long long)width + (unsigned long long)pick_i;
+            rp.variant = variant;
+            rp.device = device;
+            rp.strategy = 1;
+            const rt_radiance_rays rr{o, d, nullptr, nullptr};
+            double radiance[3];
+            uint32_t path_rays = 0;
+            const rt_radiance_out ro{radiance, &path_rays, nullptr};
+            rt_radiance_direct_stats rs{};
+            if (rt_scene_radiance_direct(scene, &rp, &rr, &ro, &rs) != RT_OK) return die("radiance-at");
+            std::printf("radiance %d,%d: samples %d radiance %.17g %.17g %.17g rays %u seconds %.9g shadow_rays %llu reached %llu\n", pick_i, pick_j, spp,
+                        radiance[0], radiance[1], radiance[2], (unsigned)path_rays, rs.seconds, (unsigned long long)rs.shadow_rays,
+                        (unsigned long long)rs.shadow_reached);
             rt_scene_destroy(scene);
             return 0;
         }

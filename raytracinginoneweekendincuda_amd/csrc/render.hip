@@ -65,8 +65,11 @@
 #ifndef RT_ADVANCE_DIRECT  // 1: this translation unit holds the kernels of a path advance with light samples (advance_direct_kernel, shadow_kernel) and nothing else
 #define RT_ADVANCE_DIRECT 0
 #endif
+#ifndef RT_RADIANCE_DIRECT  // 1: this translation unit holds the radiance-query kernels with light samples (radiance_direct_kernel) and nothing else
+#define RT_RADIANCE_DIRECT 0
+#endif
 // the lane-per-ray units: one lane per pixel, ray or point, no persistent waves
-#define RT_LANE_UNIT (RT_FEATURES || RT_QUERY || RT_RADIANCE || RT_STEP || RT_ADVANCE || RT_LIGHTS || RT_ADVANCE_DIRECT)
+#define RT_LANE_UNIT (RT_FEATURES || RT_QUERY || RT_RADIANCE || RT_STEP || RT_ADVANCE || RT_LIGHTS || RT_ADVANCE_DIRECT || RT_RADIANCE_DIRECT)
 
 namespace rtow {
 namespace {
@@ -314,7 +317,7 @@ DEV bool sphere_test(Vec oc, Vec d, double a, double r2, double tmin, double tma
 // times with the branch (the select costs the media kernel of scene 8 3 %), the lane-per-ray kernels of the feature pass and the
 // queries keep their registers with the select (the branch takes the radiance kernel of list worlds from 168 to 170 VGPRs, from
 // three waves per SIMD to two, 35 % on scene 7).  A third form, a switch case of its own in quad_test_at, cost most kernels spills.
-#define RT_PLANAR_SELECT (RT_FEATURES || RT_QUERY || RT_RADIANCE || RT_STEP || RT_ADVANCE || RT_ADVANCE_DIRECT)
+#define RT_PLANAR_SELECT (RT_FEATURES || RT_QUERY || RT_RADIANCE || RT_STEP || RT_ADVANCE || RT_ADVANCE_DIRECT || RT_RADIANCE_DIRECT)
 DEV bool quad_test(const QuadGeom &q, bool tri, const Ray &r, double tmin, double tmax, double &t_out)
 {
     Vec n = mk(q.nx, q.ny, q.nz);
@@ -4405,7 +4408,7 @@ hipError_t RT_CAT(launch_features_, RT_SUFFIX)(const DeviceScene &sc, const Feat
     return hipGetLastError();
 }
 #endif
-#if RT_QUERY || RT_ADVANCE_DIRECT  // (the search is shadow_kernel's too)
+#if RT_QUERY || RT_ADVANCE_DIRECT || RT_RADIANCE_DIRECT  // (the search is shadow_kernel's and radiance_direct_kernel's too)
 // ------------------------------------------------------------------------------------------------
 // Ray queries (rt_scene_intersect): closest hit or occlusion for caller-supplied rays.  The feature pass's search once more -- one
 // lane per ray, no LDS, every table from global memory, the reference's tree or list in the reference's order through leaf_test /
@@ -4898,7 +4901,7 @@ hipError_t RT_CAT(launch_advance_, RT_SUFFIX)(const DeviceScene &sc, const Advan
     return info_or_launch(kernel, sc, a, a.capacity, stream, info);
 }
 #endif
-#if RT_LIGHTS || RT_ADVANCE_DIRECT  // (the staging and the table's readers are advance_direct_kernel's too)
+#if RT_LIGHTS || RT_ADVANCE_DIRECT || RT_RADIANCE_DIRECT  // (the staging and the table's readers are advance_direct_kernel's and radiance_direct_kernel's too)
 // ------------------------------------------------------------------------------------------------
 // Light sampling queries (rt_scene_sample_lights, rt_scene_light_pdf; include/rtow.h states both operation by operation, and
 // tests/light_restated.py restates the strict build to the bit).  One lane per point or ray, the callers' arrays read and written
@@ -5551,6 +5554,337 @@ hipError_t RT_CAT(launch_advance_shadow_, RT_SUFFIX)(const DeviceScene &sc, cons
     void (*kernel)(DeviceScene, AdvanceDirectArgs) =
         sc.world_kind == WORLD_BVH ? shadow_kernel<RT_STRICT, TBvhNested> : shadow_kernel<RT_STRICT, TListNested>;
     return info_or_launch(kernel, sc, a, v.capacity, stream, info);
+}
+#elif RT_RADIANCE_DIRECT
+// ------------------------------------------------------------------------------------------------
+// Radiance queries with light samples (rt_scene_radiance_direct; include/rtow.h states the operation): the estimator of max_depth
+// calls of rt_scene_path_advance_direct, folded over `samples` paths a ray, in radiance_kernel's one flattened loop -- one launch,
+// no workspace, no compaction.  An iteration is ONE world search for every lane still in the loop: of its path ray over
+// (0.001, DBL_MAX), or of the shadow ray its last bounce left pending over (0.001, distance * (1 - 2^-20)), both through
+// query_search, which takes the interval and the early exit as arguments -- lanes in the two phases share the search code, and no
+// lane idles through a second search.  The state beside the search is one path's: the shadow ray shares the path ray's origin and
+// time, so a pending sample costs its direction, its end and its weighted light (seven doubles).
+//   after a path search: advance_direct_kernel's step, light sample and fold restated line for line -- shade from throughput
+//   (1, 1, 1) and accumulated (0, 0, 0), the carried throughput multiplied in behind it, as the advance does;
+//   then, every lane still in the loop here again, the density loop over the LDS-staged light table, every lane on the same row,
+//   skipped where no lane of the wave needs a density (a lane in its shadow phase never does);
+//   after a shadow search: the parked light is added where nothing was found, and the lane is back on its path ray.
+// A path ends only where no sample is pending (an ended path draws none, the last bounce takes none): it folds into the sum and the
+// next sample starts in the same iteration.  Every lane, k >= count included, reaches the barriers of stage_lights; there is none
+// behind them.  Termination: at most samples * max_depth path searches and as many shadow searches, each bounded (the ray queries'
+// argument); the rejection loops depend on the stream alone; the density loop runs n_lights times.
+// ------------------------------------------------------------------------------------------------
+template <int STRICT, class T>
+__global__ __launch_bounds__(256) void radiance_direct_kernel(DeviceScene sc, RadianceDirectArgs d)
+{
+    __shared__ __attribute__((aligned(16))) double rows_lds[kLightLdsRows * kLightRowDoubles];
+    __shared__ __attribute__((aligned(16))) double cdf_lds[kLightLdsRows];
+    global_tables_only(sc);
+    const RadianceArgs &a = d.rad;
+    LightArgs la{};  // what the table's readers take
+    la.rows = d.rows;
+    la.cdf = d.cdf;
+    la.n_lights = d.n_lights;
+    stage_lights(la, rows_lds, cdf_lds);
+    const LightLds lds{rows_lds, cdf_lds};
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t rays = 0, cast = 0, reached = 0;  // path searches, shadow searches, shadow rays that met nothing: this lane's, all samples
+    if (k < a.count) {
+        const Ray first = caller_ray(a.origin, a.direction, a.time, a.time_all, k);
+        Xorwow rng;
+        if (a.rng_in) {  // {d, v0..v4} as rt_rng_state writes them
+            const uint32_t *w = a.rng_in + (size_t)k * 6;
+            rng.d = w[0]; rng.v0 = w[1]; rng.v1 = w[2]; rng.v2 = w[3]; rng.v3 = w[4]; rng.v4 = w[5];
+        } else {  // curand_init(seed, k + first_sequence, 0)
+            rng = a.base;
+            xorwow_skip_sequences(a.jump_table, a.first_sequence + (uint64_t)k, rng);
+        }
+        const bool media = (sc.flags & SCENE_HAS_MEDIA) != 0;
+        Vec sum = mk(0.0, 0.0, 0.0);
+        if (a.max_depth > 0) {  // otherwise no bounce runs: black, nothing drawn
+            Ray ray = first;
+            Vec carried = mk(1.0, 1.0, 1.0), acc = mk(0.0, 0.0, 0.0);  // thr and acc of include/rtow.h
+            double sent = 0.0;                                         // q: the density the bounce before sent `ray` with
+            int depth = 0, sample = 0;
+            bool pending = false;  // a shadow ray (ray.o, shadow_d, ray.tm) up to shadow_end waits; where none is in the way it brings parked
+            Vec shadow_d = mk(0.0, 0.0, 1.0), parked = mk(0.0, 0.0, 0.0);
+            double shadow_end = 0.0;
+            for (;;) {
+                const bool shadow = pending;
+                Ray searched = ray;
+                double tmax = DBL_MAX;
+                bool stop_at_first = false;
+                if (shadow) {  // as shadow_kernel calls the search
+                    searched.d = shadow_d;
+                    tmax = shadow_end;
+                    stop_at_first = !media;  // a medium's answer depends on what was found before it: the full search
+                }
+                HitInfo h;
+                uint32_t leaf = kNone;
+                const bool hit = query_search<T>(sc, d.node_leaf_pos, searched, 0.001, tmax, stop_at_first, h, leaf, rng);
+                bool lamp = false, sampled = false, path_ends = false;
+                // what the density loop and the fold behind it read: the ray the density is asked along, its light and weights
+                Vec along_o = mk(0.0, 0.0, 0.0), along_d = mk(0.0, 0.0, 1.0), light = mk(0.0, 0.0, 0.0);
+                double along_tm = 0.0, other = 0.0, distance = 0.0;
+                if (shadow) {
+                    cast++;
+                    if (!hit) {
+                        reached++;
+                        acc = acc + parked;
+                    }
+                    pending = false;
+                } else {
+                    rays++;
+                    Vec throughput = mk(1.0, 1.0, 1.0), accumulated = mk(0.0, 0.0, 0.0);
+                    Vec normal = mk(0.0, 0.0, 0.0);
+                    uint32_t kind = 255u;
+                    bool scattered = false;
+                    if (!hit) {  // R/kernel.cu:74-79
+                        accumulated = accumulated + throughput * load3c(((const RT_CONST CameraRec *)(uintptr_t)sc.camera)->bg);
+                    } else {
+                        const Surface s = make_surface<T>(sc, ray, h);
+                        if ((h.ref >> kRefShift) != REF_MEDIUM) normal = s.n;
+                        kind = material_view<false>(sc, s.mat).u32(MAT_OFF(kind));
+                        scattered = shade<T>(sc, s, ray, throughput, accumulated, rng);  // scattered: `ray` is the next ray; else it is untouched
+                    }
+                    normal = mk(0.0, 0.0, 0.0) + normal;  // as query_kernel: no negative zeros
+                    if (!scattered) {
+                        path_ends = true;
+                        lamp = hit && kind == MAT_DIFFUSE_LIGHT && sent > 0.0;
+                        if (lamp) {  // weighted behind the density loop, along the incoming ray as given
+                            along_o = ray.o;
+                            along_d = ray.d;
+                            along_tm = ray.tm;
+                            light = carried * accumulated;
+                            other = sent;
+                        } else {  // w = 1
+                            acc = acc + carried * accumulated;
+                        }
+                    } else {
+                        const Vec next = carried * throughput;
+                        double sent_next = 0.0;
+                        const bool sample_here = depth + 1 < a.max_depth;  // the last bounce takes none: its light sample would stand for bounce max_depth
+                        if ((kind == MAT_LAMBERTIAN || kind == MAT_ISOTROPIC) && d.n_lights != 0 && sample_here) {
+                            // light_sample_kernel's sample for the point ray.o at the time ray.tm, from the path's stream
+                            const Vec P = ray.o;
+                            const double tm = ray.tm;
+                            bool valid = false;
+                            Vec dir = mk(0.0, 0.0, 0.0), emitted = mk(0.0, 0.0, 0.0), contribution = mk(0.0, 0.0, 0.0);
+                            double pdf = 0.0, scatter = 0.0;
+                            const double xi = (double)xorwow_uniform(rng);
+                            uint32_t lo = 0, hi = d.n_lights - 1u;  // the first row with cdf >= xi; the last entry is 1.0 >= xi
+                            while (lo < hi) {
+                                const uint32_t mid = (lo + hi) / 2u;
+                                if (light_cdf(la, lds, mid) >= xi) hi = mid;
+                                else lo = mid + 1u;
+                            }
+                            const double chance = light_cdf(la, lds, lo) - (lo ? light_cdf(la, lds, lo - 1u) : 0.0);
+                            const LightRow L = light_row(la, lds, lo);
+                            Vec S = mk(0.0, 0.0, 0.0), centre = mk(0.0, 0.0, 0.0);
+                            double u = 0.0, v = 0.0;
+                            if (L.kind <= LIGHT_TRIANGLE) {
+                                double ua = (double)xorwow_uniform(rng);
+                                double ub = (double)xorwow_uniform(rng);
+                                if (L.kind == LIGHT_TRIANGLE && ua + ub > 1.0) {
+                                    ua = 1.0 - ua;
+                                    ub = 1.0 - ub;
+                                }
+                                S = (load3(L.a) + ua * load3(L.b)) + ub * load3(L.c);
+                                const Vec D = S - P;
+                                const double d2 = dot(D, D);
+                                if (d2 > 0.0) {
+                                    const double len = sqrt(d2);
+                                    const Vec unit_d = over(D, len);
+                                    const double c = fabs(dot(load3(L.n), unit_d));
+                                    if (c != 0.0) {
+                                        const double density = (d2 / (c * L.s)) * chance;
+                                        if (usable_density(density)) {
+                                            valid = true;
+                                            dir = unit_d;
+                                            distance = len;
+                                            pdf = density;
+                                        }
+                                    }
+                                }
+                                u = ua;
+                                v = ub;
+                            } else {
+                                Vec p;
+                                double s;
+                                do {  // the lens loop of camera_ray
+                                    const double da = (double)xorwow_uniform(rng);
+                                    const double db = (double)xorwow_uniform(rng);
+                                    p = mk(2.0 * da - 1.0, 2.0 * db - 1.0, 0.0);
+                                    s = p.x * p.x + p.y * p.y;
+                                } while (!(s < 1.0 && s > 0.0));
+                                centre = light_centre(L, tm);
+                                const Vec oc = centre - P;
+                                const double d2 = dot(oc, oc), r2 = L.s * L.s;
+                                if (d2 > r2) {
+                                    const Vec w = over(oc, sqrt(d2));
+                                    const double cosmax = sqrt(1.0 - r2 / d2);
+                                    const double omc = 1.0 - cosmax;
+                                    const double z = 1.0 - s * omc;
+                                    const double rho = sqrt(1.0 - z * z);
+                                    const double q = sqrt(s);
+                                    const double ex = (rho * p.x) / q, ey = (rho * p.y) / q;
+                                    const double ax = fabs(w.x), ay = fabs(w.y), az = fabs(w.z);
+                                    Vec e1;
+                                    if (ax >= ay && ax >= az) e1 = over(mk(w.z, 0.0, -w.x), sqrt(w.z * w.z + w.x * w.x));
+                                    else if (ay >= az) e1 = over(mk(-w.y, w.x, 0.0), sqrt(w.y * w.y + w.x * w.x));
+                                    else e1 = over(mk(0.0, -w.z, w.y), sqrt(w.z * w.z + w.y * w.y));
+                                    const Vec e2 = cross(w, e1);
+                                    const Vec g = (z * w + ex * e1) + ey * e2;
+                                    const Vec unit_d = over(g, sqrt(dot(g, g)));
+                                    const Vec po = P - centre;
+                                    const double qa = dot(unit_d, unit_d), qb = dot(po, unit_d), qc = dot(po, po) - r2;
+                                    const double disc = qb * qb - qa * qc;
+                                    const double len = (-qb - sqrt(disc)) / qa;
+                                    const double density = chance / ((2.0 * kLightPi) * omc);
+                                    if (omc != 0.0 && usable_density(density) && disc > 0.0 && len > 0.0) {
+                                        valid = true;
+                                        dir = unit_d;
+                                        distance = len;
+                                        pdf = density;
+                                        S = P + len * unit_d;
+                                    }
+                                }
+                            }
+                            if (valid) {
+                                const MatView mp = material_view<false>(sc, L.mat);
+                                if (L.kind >= LIGHT_SPHERE && mp.u32(MAT_OFF(needs_uv)) != 0) sphere_uv((1 / L.s) * (S - centre), u, v);
+                                emitted = material_texture<T>(sc, mp, mp.u32(MAT_OFF(tex_inline)), u, v, S);
+                                if (kind == MAT_LAMBERTIAN) {
+                                    const double c = dot(normal, dir);
+                                    if (c > 0.0) scatter = (2.0 * ((c * c) * c)) / kLightPi;
+                                } else {
+                                    scatter = 1.0 / (4.0 * kLightPi);
+                                }
+                                if (scatter != 0.0) contribution = (scatter / pdf) * emitted;
+                            }
+                            sampled = contribution.x != 0.0 || contribution.y != 0.0 || contribution.z != 0.0;
+                            if (sampled) {  // weighted behind the density loop, along the sample
+                                along_o = P;
+                                along_d = dir;
+                                along_tm = tm;
+                                light = next * contribution;
+                                other = scatter;
+                            }
+                            // the density with which the material sent the scattered ray where it goes: the closed form above for its unit direction
+                            const Vec unit_next = (1 / sqrt((ray.d.x * ray.d.x + ray.d.y * ray.d.y) + ray.d.z * ray.d.z)) * ray.d;
+                            if (kind == MAT_LAMBERTIAN) {
+                                const double c = dot(normal, unit_next);
+                                if (c > 0.0) sent_next = (2.0 * ((c * c) * c)) / kLightPi;
+                            } else {
+                                sent_next = 1.0 / (4.0 * kLightPi);
+                            }
+                        }
+                        carried = next;
+                        sent = sent_next;
+                        if (++depth >= a.max_depth) path_ends = true;  // still alive after the last bounce: dropped (R/kernel.cu:71,97)
+                    }
+                }
+                // every lane still in the loop is here again.  The mixture density along `along`: advance_direct_kernel's loop, every such
+                // lane of the wave on row i (a lane that needs none runs it on a ray of its own that meets what it meets: its sum is not read)
+                double density_sum = 0.0;
+                if (__ballot(lamp || sampled) != 0ull) {
+                    const Vec o = along_o, dv = along_d;
+                    const double tm = along_tm;
+                    const double dd = dot(dv, dv);
+                    double before = 0.0;
+                    for (uint32_t i = 0; i < d.n_lights; i++) {
+                        const LightRow L = light_row(la, lds, i);
+                        const double upto = light_cdf(la, lds, i);
+                        const double chance = upto - before;
+                        before = upto;
+                        double density = 0.0;
+                        if (L.kind <= LIGHT_TRIANGLE) {
+                            const Vec nn = load3(L.n), Q = load3(L.a), U = load3(L.b), V = load3(L.c);
+                            const double denom = dot(nn, dv);
+                            if (denom != 0.0) {
+                                const double t = dot(nn, Q - o) / denom;
+                                if (t > 0.0) {
+                                    const Vec ph = (o + t * dv) - Q;
+                                    const Vec m = cross(U, V);
+                                    const double mm = dot(m, m);
+                                    const double alpha = dot(m, cross(ph, V)) / mm, beta = dot(m, cross(U, ph)) / mm;
+                                    const bool below = L.kind == LIGHT_TRIANGLE ? alpha + beta <= 1.0 : (alpha <= 1.0 && beta <= 1.0);
+                                    if (0.0 <= alpha && 0.0 <= beta && below) density = (((t * t) * dd) / ((fabs(denom) / sqrt(dd)) * L.s)) * chance;
+                                }
+                            }
+                        } else {
+                            const Vec oc = light_centre(L, tm) - o;
+                            const double d2 = dot(oc, oc), r2 = L.s * L.s;
+                            if (d2 > r2) {
+                                const double b = dot(oc, dv);
+                                const double disc = b * b - dd * (d2 - r2);
+                                if (b > 0.0 && disc >= 0.0) {
+                                    const double omc = 1.0 - sqrt(1.0 - r2 / d2);
+                                    if (omc != 0.0) density = chance / ((2.0 * kLightPi) * omc);
+                                }
+                            }
+                        }
+                        if (usable_density(density)) density_sum = density_sum + density;
+                    }
+                }
+                if (lamp) {  // w = q / (q + p): the scattered ray found the lamp a light sample of the bounce before could have found
+                    const double w = other / (other + density_sum);
+                    acc = acc + w * light;
+                }
+                if (sampled) {  // w = p / (p + s); the shadow ray decides in this lane's next iteration
+                    const double both = density_sum + other;
+                    const double w = both == 0.0 ? 0.0 : density_sum / both;
+                    parked = w * light;
+                    shadow_d = along_d;
+                    shadow_end = fmin(distance * (1.0 - 0x1p-20), DBL_MAX);
+                    pending = true;
+                }
+                if (path_ends) {  // (never with a sample pending)
+                    sum = sum + acc;
+                    if (++sample >= a.samples) break;
+                    ray = first;
+                    carried = mk(1.0, 1.0, 1.0);
+                    acc = mk(0.0, 0.0, 0.0);
+                    sent = 0.0;
+                    depth = 0;
+                }
+            }
+        }
+        if (a.radiance) {  // linear: the mean as rt_scene_radiance forms it
+            const Vec mean = over(sum, (double)a.samples);
+            store3(a.radiance, k, mean);
+        }
+        if (a.path_rays) a.path_rays[k] = rays;
+        if (a.rng_out) {  // may be the array the state came from: this lane has read its six words
+            uint32_t *w = a.rng_out + (size_t)k * 6;
+            w[0] = rng.d; w[1] = rng.v0; w[2] = rng.v1; w[3] = rng.v2; w[4] = rng.v3; w[5] = rng.v4;
+        }
+    }
+    if (a.ray_counter) {  // three atomics per wave at the most: every lane of the wave is here again
+        unsigned long long searched = rays, shadows = cast, unblocked = reached;
+        for (int step = 32; step > 0; step >>= 1) {
+            searched += __shfl_xor(searched, step, 64);
+            shadows += __shfl_xor(shadows, step, 64);
+            unblocked += __shfl_xor(unblocked, step, 64);
+        }
+        if ((threadIdx.x & 63u) == 0) {
+            if (searched) atomicAdd(a.ray_counter, searched);
+            if (shadows) atomicAdd(d.shadow_counters, shadows);
+            if (unblocked) atomicAdd(d.shadow_counters + 1, unblocked);
+        }
+    }
+}
+
+hipError_t RT_CAT(launch_radiance_direct_, RT_SUFFIX)(const DeviceScene &sc, const RadianceDirectArgs &d, hipStream_t stream, QueryKernelInfo *info)
+{
+    const RadianceArgs &a = d.rad;
+    if (a.samples < 1 || a.max_depth < 0 || !a.origin || !a.direction || !(a.radiance || a.path_rays || a.rng_out)) return hipErrorInvalidValue;
+    if (!info && d.n_lights != 0 && (!d.rows || !d.cdf)) return hipErrorInvalidValue;
+    if (!info && sc.world_kind == WORLD_BVH && !d.node_leaf_pos) return hipErrorInvalidValue;
+    if (!info && a.ray_counter && !d.shadow_counters) return hipErrorInvalidValue;
+    void (*kernel)(DeviceScene, RadianceDirectArgs) =
+        sc.world_kind == WORLD_BVH ? radiance_direct_kernel<RT_STRICT, TBvhNested> : radiance_direct_kernel<RT_STRICT, TListNested>;
+    return info_or_launch(kernel, sc, d, a.count, stream, info);
 }
 #elif RT_LANE_UNIT
 // (a lane-per-ray unit defined above)

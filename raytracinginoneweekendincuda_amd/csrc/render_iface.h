@@ -295,6 +295,22 @@ hipError_t launch_advance_shadow_strict(const DeviceScene &sc, const AdvanceDire
 hipError_t launch_advance_shadow_fast(const DeviceScene &sc, const AdvanceDirectArgs &a, hipStream_t stream, QueryKernelInfo *info = nullptr);
 hipError_t launch_advance_direct_gather(const AdvanceDirectGatherArgs &a, hipStream_t stream);
 
+// Radiance queries with light samples (rt_scene_radiance_direct; the RT_RADIANCE_DIRECT objects of render.hip): the estimator of
+// max_depth advances with light samples in one launch.  radiance_kernel's lane per ray and flattened loop, with one world search
+// an iteration: of the lane's path ray, or of the shadow ray its last bounce left pending.  The light table comes as it comes to
+// advance_direct_kernel and is staged in LDS the same way; there is no workspace.
+struct RadianceDirectArgs {
+    RadianceArgs rad;                   // rad.ray_counter counts path searches only
+    const LightRow *rows;               // n_lights
+    const double *cdf;                  // the cumulative table of the call's strategy, padded to an even length
+    uint32_t n_lights;
+    const uint32_t *node_leaf_pos;      // as QueryArgs
+    unsigned long long *shadow_counters;  // two words, zeroed by the caller: shadow rays cast, shadow rays that reached their lamp; given where rad.ray_counter is
+};
+// info != nullptr: report the instantiation that would run instead of launching it
+hipError_t launch_radiance_direct_strict(const DeviceScene &sc, const RadianceDirectArgs &a, hipStream_t stream, QueryKernelInfo *info = nullptr);
+hipError_t launch_radiance_direct_fast(const DeviceScene &sc, const RadianceDirectArgs &a, hipStream_t stream, QueryKernelInfo *info = nullptr);
+
 // Light sampling queries (rt_scene_sample_lights, rt_scene_light_pdf; the RT_LIGHTS objects of render.hip): one lane per point or
 // ray, 256-thread workgroups that first stage the first kLightLdsRows rows of the light table and of its cumulative table in LDS.
 // The table is not part of DeviceScene: it comes through these arguments.  `sc` is still passed, for the material and texture
