@@ -52,6 +52,9 @@ RTOW_API uint32_t rt_rng_next_u32(rt_rng *rng);
 RTOW_API void rt_rng_state(const rt_rng *rng, uint32_t out6[6]);   /* {d, v0..v4} */
 /* salt_kind 0 = cuRAND device-API seed salts (the product's RNG); 1 = rocRAND's salts (test cross-check only) */
 RTOW_API rt_rng *rt_rng_create_salted(uint64_t seed, uint64_t sequence, int salt_kind);
+/* a host stream that continues where a stream stood: {d, v0..v4} as rt_rng_state writes them, and as the films and the queries
+ * save and return the device streams (NULL for a NULL argument) */
+RTOW_API rt_rng *rt_rng_create_from_state(const uint32_t in6[6]);
 
 /* ---- scene lifetime ---- */
 RTOW_API rt_scene *rt_scene_create(void);
@@ -1042,6 +1045,51 @@ RTOW_API int rt_scene_radiance_direct(rt_scene *s, const rt_radiance_direct_para
                                       const rt_radiance_out *out, rt_radiance_direct_stats *stats);
 /* sizeof of rt_radiance_direct_params, rt_radiance_rays, rt_radiance_out, rt_radiance_direct_stats as this library was compiled */
 RTOW_API void rt_radiance_direct_abi_sizes(uint32_t out4[4]);
+
+/* ---- frames with light samples: a film rendered by the estimator of rt_scene_radiance_direct ----
+ * rt_render_launch with every sample of every pixel replaced by one sample of rt_scene_radiance_direct.  Take the film of W x H,
+ * params with seed, S = samples_per_pixel and max_depth, and direct->strategy.  Pixel (i, j), owned by the film's rank through the
+ * usual stripes, has the film's saved stream under RT_FLAG_KEEP_RNG_STATE and curand_init(seed, j * W + i, 0) otherwise, as for
+ * rt_render_launch.  For s = 0 .. S - 1, in this order:
+ *   1. the camera ray of the render kernels for (i, j) (their own draws and operations);
+ *   2. one sample of rt_scene_radiance_direct for that ray -- samples = 1, this max_depth and strategy, steps 1-4 of the comment
+ *      above rt_radiance_direct_params -- drawn from the stream where step 1 left it; the stream moves on as that call moves it;
+ *   3. col = col + acc, where col starts at (0, 0, 0), or at the film's running sum under RT_FLAG_ACCUMULATE on a continued frame.
+ * The pixel is then finished as rt_render_launch finishes it: the six stream words go to the film's state, col to the running sum
+ * where the frame accumulates, pixels = sqrt(col / (double)N) with N all samples of the frame so far.  With adaptive sampling set
+ * on the film (rt_film_set_adaptive) the pixel is finished by that rule instead, exactly as rt_render_launch applies it: q takes
+ * the sample's y^2 after each sample, the rule is looked at with the pixel's total n, a pixel that stops keeps its own n and is
+ * marked, and a marked pixel is never touched by a later launch of the frame.  In the strict build every operation is one IEEE-754
+ * double operation in that order; the fast build may fuse (never inside the rule).
+ * Consequences: without lights, or at max_depth == 1, the frame is rt_render_launch's bit for bit in the strict build;
+ * max_depth == 0 gives a black frame with only the camera's draws taken; k launches of S with KEEP_RNG_STATE | ACCUMULATE are one
+ * launch of kS; a frame may mix plain and direct launches (the sums and streams are the same objects, both estimators have the
+ * same expectation; the changed-adaptive-setting rule applies as it does to rt_render_launch).  No frame depends on which lane
+ * rendered which pixel.
+ * S == 0 is accepted and finishes no pixel: the launch does what every launch does before its kernel (it seeds the streams where
+ * it does not keep them, and begins a frame where it does not continue one) and runs no kernel, so no pixel and no running sum is
+ * written (rt_render_launch would write every pixel again from a sum of no samples), and rt_render_finish reports no samples, no
+ * rays and no shadow rays.
+ * rt_render_finish ends the launch and fills rt_render_stats as for any launch: rays counts the path searches only (the shadow
+ * searches are in rt_film_last_direct_stats), pixels_per_wave is 64, kernel_kind carries the bit 1024 beside the bits of the
+ * nested kernel whose search runs.  variant, device, stream, stripe_rows / rank / world_size, RT_FLAG_KEEP_RNG_STATE and
+ * RT_FLAG_ACCUMULATE mean what they mean for rt_render_launch; max_blocks_per_cu caps the resident workgroups; every other
+ * RT_FLAG_* scheduling or tuning bit and every other tuning field is accepted and ignored (none changes a picture).
+ * Refusals, all before the device is touched: rt_render_launch's own, in its order; then a NULL direct, a strategy other than
+ * 0 / 1, a non-zero reserved word (RT_ERR_INVALID, the message names the field). */
+typedef struct rt_film_direct_params {
+    int32_t strategy;        /* 0 uniform over lights, 1 by area x brightest channel, as rt_light_params */
+    int32_t reserved[7];     /* must be 0 */
+} rt_film_direct_params;
+typedef struct rt_film_direct_stats {
+    uint64_t shadow_rays, shadow_reached;   /* of the last direct launch that was finished: shadow rays cast; those that reached their lamp */
+    uint32_t scratch_bytes, reserved;       /* private memory per lane of the kernel that ran */
+} rt_film_direct_stats;
+RTOW_API int rt_render_launch_direct(rt_scene *s, rt_film *film, const rt_render_params *params, const rt_film_direct_params *direct);
+/* RT_ERR_STATE before a direct launch of this film was finished */
+RTOW_API int rt_film_last_direct_stats(rt_film *film, rt_film_direct_stats *out);
+/* sizeof of rt_film_direct_params, rt_film_direct_stats as this library was compiled */
+RTOW_API void rt_film_direct_abi_sizes(uint32_t out2[2]);
 
 /* Convenience: create film, upload, render 1 GPU, download.  frame = W*H*3 doubles. */
 RTOW_API int rt_render(rt_scene *s, const rt_render_params *params, double *frame, rt_render_stats *stats);

@@ -258,6 +258,18 @@ public:
         check(rt_render_finish(scene.raw(), f_, &st));
         return st;
     }
+    // the same frame with light samples (rtow.h "frames with light samples"): strategy 0 uniform over lights, 1 by area x brightest
+    // channel; the shadow statistics of the launch come back through `direct` where given
+    rt_render_stats RenderDirect(Scene &scene, const rt_render_params &params, int strategy = 1, rt_film_direct_stats *direct = nullptr)
+    {
+        rt_render_stats st{};
+        rt_film_direct_params dp{};
+        dp.strategy = strategy;
+        check(rt_render_launch_direct(scene.raw(), f_, &params, &dp));
+        check(rt_render_finish(scene.raw(), f_, &st));
+        if (direct) check(rt_film_last_direct_stats(f_, direct));
+        return st;
+    }
     std::vector<double> Download()
     {
         std::vector<double> frame((size_t)w_ * h_ * 3);

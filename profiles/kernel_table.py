@@ -1,7 +1,7 @@
 """VGPRs / scratch / spills of every render_kernel instantiation in the built library (llvm-readelf on the code objects), then
 the feature, filter, ray-query, radiance-query, path-step and path-advance kernels (feature_kernel, atrous_kernel, query_kernel,
 radiance_kernel, step_kernel, advance_kernel, advance_scan_kernel, advance_gather_kernel, light_sample_kernel, light_pdf_kernel,
-advance_direct_kernel, shadow_kernel, advance_direct_gather_kernel, radiance_direct_kernel) by name with their static LDS as well."""
+advance_direct_kernel, shadow_kernel, advance_direct_gather_kernel, radiance_direct_kernel, film_direct_kernel) by name with their static LDS as well."""
 import os, re, subprocess, sys
 so = sys.argv[1] if len(sys.argv) > 1 else os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', 'raytracinginoneweekendincuda_amd', 'librtow_hip.so')
 data = open(so, 'rb').read()
@@ -56,6 +56,11 @@ for i, st in enumerate(idx[1:]):
                 others.append((name, int(cur['vgpr_count']), int(cur['private_segment_fixed_size']), int(cur['vgpr_spill_count']),
                                int(cur['group_segment_fixed_size'])))
             m = re.search(r'(advance_direct_kernel|shadow_kernel)ILi(\d)ENS_12_GLOBAL__N_16TraitsILi(\d)E', n)
+            if m:
+                name = '%s world %s %s' % (m.group(1), m.group(3), 'strict' if int(m.group(2)) else 'fast')
+                others.append((name, int(cur['vgpr_count']), int(cur['private_segment_fixed_size']), int(cur['vgpr_spill_count']),
+                               int(cur['group_segment_fixed_size'])))
+            m = re.search(r'(film_direct_kernel)ILi(\d)ENS_12_GLOBAL__N_16TraitsILi(\d)E', n)
             if m:
                 name = '%s world %s %s' % (m.group(1), m.group(3), 'strict' if int(m.group(2)) else 'fast')
                 others.append((name, int(cur['vgpr_count']), int(cur['private_segment_fixed_size']), int(cur['vgpr_spill_count']),

@@ -95,6 +95,15 @@ class RadianceDirectStats(C.Structure):
                 ("kernel_vgprs", C.c_uint32), ("scratch_bytes", C.c_uint32)]
 
 
+# rt_render_launch_direct: the strategy of a frame with light samples, and the shadow statistics of the last one finished
+class FilmDirectParams(C.Structure):
+    _fields_ = [("strategy", C.c_int32), ("reserved", C.c_int32 * 7)]
+
+
+class FilmDirectStats(C.Structure):
+    _fields_ = [("shadow_rays", C.c_uint64), ("shadow_reached", C.c_uint64), ("scratch_bytes", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class PathStepParams(C.Structure):
     _fields_ = [("count", C.c_int64), ("time", C.c_double), ("seed", C.c_uint64), ("first_sequence", C.c_uint64), ("variant", C.c_int32),
                 ("device", C.c_int32), ("stream", C.c_void_p), ("reserved", C.c_int32 * 4)]
@@ -250,6 +259,7 @@ SIGNATURES = {
     "rt_rng_uniform": (C.c_float, [P]),
     "rt_rng_next_u32": (C.c_uint32, [P]),
     "rt_rng_state": (None, [P, C.POINTER(C.c_uint32)]),
+    "rt_rng_create_from_state": (P, [C.POINTER(C.c_uint32)]),
     "rt_scene_create": (P, []),
     "rt_scene_destroy": (None, [P]),
     "rt_scene_set_options": (I, [P, C.c_uint32]),
@@ -307,6 +317,9 @@ SIGNATURES = {
     "rt_scene_upload": (I, [P, I]),
     "rt_render_launch": (I, [P, P, C.POINTER(RenderParams)]),
     "rt_render_finish": (I, [P, P, C.POINTER(RenderStats)]),
+    "rt_render_launch_direct": (I, [P, P, C.POINTER(RenderParams), C.POINTER(FilmDirectParams)]),
+    "rt_film_last_direct_stats": (I, [P, C.POINTER(FilmDirectStats)]),
+    "rt_film_direct_abi_sizes": (None, [C.POINTER(C.c_uint32)]),
     "rt_film_download": (I, [P, D3, I, I]),
     "rt_film_set_adaptive": (I, [P, C.POINTER(AdaptiveParams)]),
     "rt_film_download_sample_counts": (I, [P, C.POINTER(C.c_uint32), I, I]),
@@ -381,6 +394,11 @@ def load():
         ours = [C.sizeof(x) for x in structs]
         if list(sizes) != ours:
             raise ImportError(f"{LIB_PATH}: {what} structures are {list(sizes)} bytes in the library, {ours} in the binding")
+    sizes = (C.c_uint32 * 2)()
+    lib.rt_film_direct_abi_sizes(sizes)
+    ours = [C.sizeof(FilmDirectParams), C.sizeof(FilmDirectStats)]
+    if list(sizes) != ours:
+        raise ImportError(f"{LIB_PATH}: rt_film_direct_* structures are {list(sizes)} bytes in the library, {ours} in the binding")
     sizes = (C.c_uint32 * 8)()
     lib.rt_light_abi_sizes(sizes)
     ours = [C.sizeof(x) for x in (LightParams, LightPoints, LightSamples, LightRays, LightPdfOut, LightStats, LightRow)]

@@ -12,7 +12,7 @@ import numbers
 import numpy as np
 
 from . import _lib
-from ._lib import (AdaptiveParams, DenoiseParams, FeatureParams, LaunchPlan, LightParams, LightPdfOut, LightPoints, LightRays,  # noqa: F401
+from ._lib import (AdaptiveParams, DenoiseParams, FeatureParams, FilmDirectParams, FilmDirectStats, LaunchPlan, LightParams, LightPdfOut, LightPoints, LightRays,  # noqa: F401
                    LightSamples, LightStats, QueryHits, QueryParams, QueryRays, QueryStats,  # noqa: F401
                    PathAdvanceOut, PathAdvanceParams, PathAdvanceRays, PathAdvanceStats,
                    PathAdvanceDirectOut, PathAdvanceDirectParams, PathAdvanceDirectRays, PathAdvanceDirectStats,
@@ -98,6 +98,19 @@ class Rng:
         out = (C.c_uint32 * 6)()
         lib().rt_rng_state(self._p, out)
         return list(out)
+
+    @classmethod
+    def from_state(cls, words):
+        """The stream that continues where ``words`` stood: six 32-bit words {d, v0..v4} as ``state()`` gives them, and as the
+        films and the queries return the device streams (include/rtow.h rt_rng_create_from_state)."""
+        words = [int(w) & 0xFFFFFFFF for w in words]
+        if len(words) != 6:
+            raise ValueError("a stream's state is six 32-bit words")
+        self = cls.__new__(cls)
+        self._p = lib().rt_rng_create_from_state((C.c_uint32 * 6)(*words))
+        if not self._p:
+            raise RtowError(_err())
+        return self
 
 
 class Scene:
@@ -636,19 +649,25 @@ class Scene:
 
     # ---- one-call render on one GPU ----
     def render(self, width, height, spp, max_depth=50, seed=1984, variant=0, device=0, flags=0, coop_threshold=0,
-               overdue=0, shade_batch=0, max_blocks_per_cu=0, pixels_per_wave=0, adaptive=None):
+               overdue=0, shade_batch=0, max_blocks_per_cu=0, pixels_per_wave=0, adaptive=None, direct=None, strategy=1):
         """``adaptive``: None, or the arguments of ``Film.set_adaptive`` as a tuple / dict -- ``spp`` is then the most
-        samples a pixel takes, and the stats carry the per-pixel counts as ``sample_counts`` ((H, W) uint32)."""
-        if adaptive is not None:
+        samples a pixel takes, and the stats carry the per-pixel counts as ``sample_counts`` ((H, W) uint32).
+        ``direct="mis"``: every sample is the estimator of ``radiance(direct="mis", strategy=strategy)`` (``Film.launch``); the stats
+        then carry ``direct_stats``, the film's FilmDirectStats.  ``direct=None``: the plain render, whatever ``strategy`` says."""
+        _direct_or_raise(direct)
+        if adaptive is not None or direct is not None:
             film = Film(width, height, device=device)
             if isinstance(adaptive, dict):
                 film.set_adaptive(**adaptive)
-            else:
+            elif adaptive is not None:
                 film.set_adaptive(*adaptive)
-            st = film.render(self, spp, max_depth=max_depth, seed=seed, variant=variant, flags=flags, coop_threshold=coop_threshold,
-                             overdue=overdue, shade_batch=shade_batch, max_blocks_per_cu=max_blocks_per_cu,
+            st = film.render(self, spp, direct=direct, strategy=strategy, max_depth=max_depth, seed=seed, variant=variant, flags=flags,
+                             coop_threshold=coop_threshold, overdue=overdue, shade_batch=shade_batch, max_blocks_per_cu=max_blocks_per_cu,
                              pixels_per_wave=pixels_per_wave)
-            st.sample_counts = film.sample_counts()
+            if adaptive is not None:
+                st.sample_counts = film.sample_counts()
+            if direct is not None:
+                st.direct_stats = film.direct_stats()
             return film.download(), st
         p = RenderParams(width, height, spp, max_depth, seed, 8, 0, 1, variant, device, flags, None, coop_threshold, overdue,
                          shade_batch, max_blocks_per_cu, pixels_per_wave, 0)
@@ -827,6 +846,11 @@ def builtin_scene(scene_id, world_kind, width, height, seed=1984, earth=None):
     return Scene().build_builtin(scene_id, world_kind, width, height, seed, earth)
 
 
+def _direct_or_raise(direct):
+    if direct not in (None, "mis"):
+        raise ValueError('direct must be None or "mis"')
+
+
 class Film:
     """frameBuffer + randState of one GPU (R/kernel.cu:606-613), restricted to this rank's row stripes."""
 
@@ -849,8 +873,19 @@ class Film:
                             variant, self.device, flags, stream, coop_threshold, overdue, shade_batch, max_blocks_per_cu,
                             pixels_per_wave, 0)
 
-    def launch(self, scene, params):
-        _check(lib().rt_render_launch(scene._p, self._p, C.byref(params)))
+    def launch(self, scene, params, direct=None, strategy=1):
+        """``direct="mis"``: the frame with light samples (include/rtow.h rt_render_launch_direct) -- every sample of every pixel is
+        one sample of ``Scene.radiance(direct="mis", strategy=strategy)`` for the pixel's camera ray, from the pixel's stream; seeds,
+        saved streams, running sums, stripes and adaptive sampling are the film's, as for the plain launch, and launches of both
+        kinds may follow each other in one frame.  ``direct=None``: the plain launch, whatever ``strategy`` says."""
+        _direct_or_raise(direct)
+        if direct is None:
+            _check(lib().rt_render_launch(scene._p, self._p, C.byref(params)))
+        else:
+            if not isinstance(strategy, numbers.Integral):
+                raise ValueError("strategy must be 0 (uniform) or 1 (by area and brightness)")
+            dp = FilmDirectParams(int(strategy))
+            _check(lib().rt_render_launch_direct(scene._p, self._p, C.byref(params), C.byref(dp)))
         self._scene = scene   # the kernel reads the scene's tables: keep it alive until finish()
 
     def finish(self, scene=None):
@@ -862,9 +897,16 @@ class Film:
             self._scene = None
         return st
 
-    def render(self, scene, spp, **kw):
-        self.launch(scene, self.params(spp, **kw))
+    def render(self, scene, spp, direct=None, strategy=1, **kw):
+        self.launch(scene, self.params(spp, **kw), direct=direct, strategy=strategy)
         return self.finish(scene)
+
+    def direct_stats(self):
+        """FilmDirectStats of the last ``direct="mis"`` launch of this film that was finished: shadow rays cast, those that reached
+        their lamp, the private memory of the kernel."""
+        st = FilmDirectStats()
+        _check(lib().rt_film_last_direct_stats(self._p, C.byref(st)))
+        return st
 
     def device_pixels(self):
         return lib().rt_film_device_pixels(self._p), lib().rt_film_pixel_bytes(self._p)

@@ -132,7 +132,13 @@ struct FilmImpl {
     // like the pixels; denoise_tmp is the other half of the filter's ping-pong
     double *feat_albedo = nullptr, *feat_normal = nullptr, *feat_depth = nullptr, *denoised = nullptr, *denoise_tmp = nullptr;
     bool has_features = false, has_denoised = false;
+    // frames with light samples (rt_render_launch_direct): was the launch in flight (or the last one) a direct one, the private
+    // memory of its kernel, and the statistics of the last one that rt_render_finish ended
+    bool last_direct = false, has_direct_stats = false;
+    int last_direct_scratch = 0;
+    rt_film_direct_stats direct_stats{};
 };
+constexpr size_t kShadowCounterWord = 10;  // FilmImpl::ray_counter[10], [11]: shadow rays cast, shadow rays that reached their lamp (direct launches)
 
 static bool same_rule(const AdaptiveRule &a, const AdaptiveRule &b)
 {
@@ -500,14 +506,15 @@ struct Build {
     hipError_t (*advance_direct)(const DeviceScene &, const AdvanceDirectArgs &, hipStream_t, QueryKernelInfo *);
     hipError_t (*advance_shadow)(const DeviceScene &, const AdvanceDirectArgs &, hipStream_t, QueryKernelInfo *);
     hipError_t (*radiance_direct)(const DeviceScene &, const RadianceDirectArgs &, hipStream_t, QueryKernelInfo *);
+    hipError_t (*film_direct)(const DeviceScene &, const FilmDirectArgs &, hipStream_t, FilmDirectInfo *);
 };
 static const Build kBuilds[2] = {
     {launch_seed_strict, launch_render_strict, kernel_info_strict, launch_adaptive_rule_strict, launch_features_strict, launch_query_strict,
      launch_radiance_strict, launch_step_strict, launch_advance_strict, launch_light_sample_strict, launch_light_pdf_strict,
-     launch_advance_direct_strict, launch_advance_shadow_strict, launch_radiance_direct_strict},
+     launch_advance_direct_strict, launch_advance_shadow_strict, launch_radiance_direct_strict, launch_film_direct_strict},
     {launch_seed_fast, launch_render_fast, kernel_info_fast, launch_adaptive_rule_fast, launch_features_fast, launch_query_fast,
      launch_radiance_fast, launch_step_fast, launch_advance_fast, launch_light_sample_fast, launch_light_pdf_fast,
-     launch_advance_direct_fast, launch_advance_shadow_fast, launch_radiance_direct_fast}};
+     launch_advance_direct_fast, launch_advance_shadow_fast, launch_radiance_direct_fast, launch_film_direct_fast}};
 
 static int seed_film(FilmImpl &f, const rt_render_params *p, hipStream_t stream)
 {
@@ -698,23 +705,40 @@ static int enqueue_rehearsal(FilmImpl &f, const DeviceScene &ds, const rt_launch
     return RT_OK;
 }
 
-// Everything rt_render_launch puts on the stream: seeding, the rehearsal and its bookkeeping, the render kernel, the
-// counter copy.  Called with the film already marked in flight (a failure half-way leaves kernels running).  What runs and
-// how is plan_launch's decision (launch_plan.h); this function carries it out.
-static int enqueue_frame(SceneImpl &s, FilmImpl &f, const rt_render_params *p, hipStream_t stream)
+// What every launch of a frame, plain or with light samples, puts on the stream first: the counters zeroed, the seeding between
+// its two events, the film's bookkeeping (book_frame fills its part of `ra`) ...
+static int enqueue_frame_begin(FilmImpl &f, const rt_render_params *p, RenderArgs &ra, hipStream_t stream)
 {
     const bool keep = (p->flags & RT_FLAG_KEEP_RNG_STATE) && f.seeded;
     const bool continues = continues_frame(f, p);
-    const Build &build = kBuilds[p->variant];
-    const DeviceScene &ds = s.device[f.device]->scene;
-
     HIP_TRY(hipMemsetAsync(f.ray_counter, 0, kCounterWords * sizeof(unsigned long long), stream));
     HIP_TRY(hipEventRecord(f.ev[0], stream));
     if (!keep)
         if (int rc = seed_film(f, p, stream)) return rc;
     HIP_TRY(hipEventRecord(f.ev[1], stream));
+    return book_frame(f, p, keep, continues, ra, stream);
+}
+// ... and last, behind its kernels: the event, the counter copy, the event rt_render_finish waits for.
+static int enqueue_frame_end(FilmImpl &f, hipStream_t stream)
+{
+    HIP_TRY(hipEventRecord(f.ev[2], stream));
+    // The counters come home on the film's own stream: a blocking hipMemcpy in rt_render_finish would wait for every
+    // other film's frame as well and serialise frames that were launched to overlap.
+    HIP_TRY(hipMemcpyAsync(f.host_counters, f.ray_counter, kCounterWords * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipEventRecord(f.ev[3], stream));
+    return RT_OK;
+}
+
+// Everything rt_render_launch puts on the stream: seeding, the rehearsal and its bookkeeping, the render kernel, the
+// counter copy.  Called with the film already marked in flight (a failure half-way leaves kernels running).  What runs and
+// how is plan_launch's decision (launch_plan.h); this function carries it out.
+static int enqueue_frame(SceneImpl &s, FilmImpl &f, const rt_render_params *p, hipStream_t stream)
+{
+    const Build &build = kBuilds[p->variant];
+    const DeviceScene &ds = s.device[f.device]->scene;
+
     RenderArgs ra{};
-    if (int rc = book_frame(f, p, keep, continues, ra, stream)) return rc;
+    if (int rc = enqueue_frame_begin(f, p, ra, stream)) return rc;
     const rt_launch_plan plan = plan_launch(ds, f.geometry, f.num_cus, *p, f.adaptive, hits_stay_in_boxes(s.flat, s.camera, p->variant));
     fill_render_args(f, p, plan, ra);
     KernelInfo info{};
@@ -736,31 +760,83 @@ static int enqueue_frame(SceneImpl &s, FilmImpl &f, const rt_render_params *p, h
     if (plan.probe_spp > 0)
         if (int rc = enqueue_rehearsal(f, ds, plan, build, ra, stream)) return rc;
     HIP_TRY(build.render(plan.kernel, ds, ra, stream));
-    HIP_TRY(hipEventRecord(f.ev[2], stream));
-    // The counters come home on the film's own stream: a blocking hipMemcpy in rt_render_finish would wait for every
-    // other film's frame as well and serialise frames that were launched to overlap.
-    HIP_TRY(hipMemcpyAsync(f.host_counters, f.ray_counter, kCounterWords * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipEventRecord(f.ev[3], stream));
-    return RT_OK;
+    return enqueue_frame_end(f, stream);
 }
 
-int rt_render_launch(rt_scene *scene, rt_film *film, const rt_render_params *p)
+// Everything rt_render_launch_direct puts on the stream: what every frame launch begins and ends with, and between them the one
+// kernel -- no rehearsal, no pixel classes, no primary lists.  The light table is the copy rt_scene_radiance_direct_device reads.
+static int enqueue_frame_direct(SceneImpl &s, FilmImpl &f, const rt_render_params *p, const rt_film_direct_params *direct, hipStream_t stream)
 {
-    if (!scene || !film || !p) return fail(RT_ERR_INVALID, "rt_render_launch: null argument");
-    SceneImpl &s = *S(scene);
+    const Build &build = kBuilds[p->variant];
+    const DeviceTables &dt = *s.device[f.device];
+
+    RenderArgs ra{};
+    if (int rc = enqueue_frame_begin(f, p, ra, stream)) return rc;
+    FilmDirectArgs da{};
+    da.pixels = f.pixels;
+    da.accum = ra.accum;
+    da.spp_before = ra.spp_before;
+    da.state = f.state;
+    da.ray_counter = f.ray_counter;
+    da.cursor = reinterpret_cast<uint32_t *>(f.ray_counter + 1);
+    da.n_pixels = f.geometry.n_pixels;
+    da.width = f.geometry.width;
+    da.height = f.geometry.height;
+    da.rows_owned = f.geometry.rows_owned;
+    da.spp = p->samples_per_pixel;
+    da.max_depth = p->max_depth;
+    da.stripe_rows = f.stripe_rows;
+    da.rank = f.rank;
+    da.world_size = f.world_size;
+    da.num_cus = f.num_cus;
+    da.max_blocks_per_cu = p->max_blocks_per_cu;
+    da.adaptive = ra.adaptive;
+    da.rule = ra.rule;
+    da.ad_n = ra.ad_n;
+    da.ad_q = ra.ad_q;
+    da.ad_mark = ra.ad_mark;
+    da.rows = dt.lights;
+    da.cdf = dt.light_cdf[direct->strategy];
+    da.n_lights = dt.n_lights;
+    da.node_leaf_pos = dt.node_leaf_pos;
+    da.shadow_counters = f.ray_counter + kShadowCounterWord;
+    FilmDirectInfo info{};
+    HIP_TRY(build.film_direct(dt.scene, da, stream, &info));
+    f.last_plan = rt_launch_plan{};
+    f.last_plan.pixels_per_wave = 64;
+    f.last_plan.kernel_kind = info.kernel.kind;
+    f.last_plan.lds_bytes = info.kernel.lds_bytes;
+    f.last_kernel = info.kernel;
+    f.last_direct_scratch = info.scratch_bytes;
+    HIP_TRY(build.film_direct(dt.scene, da, stream, nullptr));
+    return enqueue_frame_end(f, stream);
+}
+
+// everything a frame launch refuses without a device, in the order include/rtow.h lists it
+static int frame_launch_check(rt_scene *scene, rt_film *film, const rt_render_params *p, const std::string &who)
+{
+    if (!scene || !film || !p) return fail(RT_ERR_INVALID, who + ": null argument");
     FilmImpl &f = *F(film);
     if (p->width != f.geometry.width || p->height != f.geometry.height || p->stripe_rows != f.stripe_rows || p->rank != f.rank ||
         p->world_size != f.world_size || p->device != f.device)
-        return fail(RT_ERR_INVALID, "rt_render_launch: params do not match the film's geometry/device");
-    if (p->samples_per_pixel < 0 || p->max_depth < 0) return fail(RT_ERR_INVALID, "rt_render_launch: negative spp/depth");
-    if (p->variant != 0 && p->variant != 1) return fail(RT_ERR_INVALID, "rt_render_launch: variant must be 0 (strict) or 1 (fast)");
-    if (p->pixels_per_wave < 0 || p->pixels_per_wave > 64) return fail(RT_ERR_INVALID, "rt_render_launch: pixels_per_wave must be 0 (automatic) or 1..64");
+        return fail(RT_ERR_INVALID, who + ": params do not match the film's geometry/device");
+    if (p->samples_per_pixel < 0 || p->max_depth < 0) return fail(RT_ERR_INVALID, who + ": negative spp/depth");
+    if (p->variant != 0 && p->variant != 1) return fail(RT_ERR_INVALID, who + ": variant must be 0 (strict) or 1 (fast)");
+    if (p->pixels_per_wave < 0 || p->pixels_per_wave > 64) return fail(RT_ERR_INVALID, who + ": pixels_per_wave must be 0 (automatic) or 1..64");
     if (f.in_flight)
-        return fail(RT_ERR_STATE, "rt_render_launch: this film already has a render in flight (rt_render_finish it first; "
-                                  "use one film per frame in flight)");
+        return fail(RT_ERR_STATE, who + ": this film already has a render in flight (rt_render_finish it first; "
+                                        "use one film per frame in flight)");
     if (continues_frame(f, p) && (f.adaptive != f.frame_adaptive || (f.adaptive && !same_rule(f.rule, f.frame_rule))))
-        return fail(RT_ERR_STATE, "rt_render_launch: adaptive sampling was switched or given other parameters in the middle of an "
-                                  "accumulated frame (begin a frame by re-seeding, or set it back)");
+        return fail(RT_ERR_STATE, who + ": adaptive sampling was switched or given other parameters in the middle of an "
+                                        "accumulated frame (begin a frame by re-seeding, or set it back)");
+    return RT_OK;
+}
+
+// rt_render_launch and rt_render_launch_direct behind their checks (direct == nullptr: the plain launch)
+static int launch_frame(rt_scene *scene, rt_film *film, const rt_render_params *p, const rt_film_direct_params *direct)
+{
+    SceneImpl &s = *S(scene);
+    FilmImpl &f = *F(film);
     if (int rc = rt_scene_upload(scene, f.device)) return rc;
     if (int rc = select_device(f.device)) return rc;
     hipStream_t stream = p->stream ? (hipStream_t)p->stream : f.own_stream;
@@ -768,7 +844,7 @@ int rt_render_launch(rt_scene *scene, rt_film *film, const rt_render_params *p)
     // when a later step of the launch fails.
     f.last_stream = stream;
     mark_in_flight(s, f);
-    const int rc = enqueue_frame(s, f, p, stream);
+    const int rc = direct ? enqueue_frame_direct(s, f, p, direct, stream) : enqueue_frame(s, f, p, stream);
     if (rc != RT_OK) {
         const std::string why = rt_last_error();
         hipStreamSynchronize(stream);  // whatever did get enqueued
@@ -780,8 +856,41 @@ int rt_render_launch(rt_scene *scene, rt_film *film, const rt_render_params *p)
     f.last_samples = (uint64_t)f.geometry.n_pixels * (uint64_t)p->samples_per_pixel;
     f.last_variant = p->variant;
     f.last_adaptive = f.adaptive;
+    f.last_direct = direct != nullptr;
     f.rendered = true;
     return RT_OK;
+}
+
+int rt_render_launch(rt_scene *scene, rt_film *film, const rt_render_params *p)
+{
+    if (int rc = frame_launch_check(scene, film, p, "rt_render_launch")) return rc;
+    return launch_frame(scene, film, p, nullptr);
+}
+
+int rt_render_launch_direct(rt_scene *scene, rt_film *film, const rt_render_params *p, const rt_film_direct_params *direct)
+{
+    const std::string who = "rt_render_launch_direct";
+    if (int rc = frame_launch_check(scene, film, p, who)) return rc;
+    if (!direct) return fail(RT_ERR_INVALID, who + ": direct is NULL");
+    if (direct->strategy != 0 && direct->strategy != 1) return fail(RT_ERR_INVALID, who + ": strategy must be 0 (uniform) or 1 (by area and brightness)");
+    for (int32_t word : direct->reserved)
+        if (word != 0) return fail(RT_ERR_INVALID, who + ": reserved must be 0");
+    return launch_frame(scene, film, p, direct);
+}
+
+int rt_film_last_direct_stats(rt_film *film, rt_film_direct_stats *out)
+{
+    if (!film || !out) return fail(RT_ERR_INVALID, "rt_film_last_direct_stats: null argument");
+    const FilmImpl &f = *F(film);
+    if (!f.has_direct_stats) return fail(RT_ERR_STATE, "rt_film_last_direct_stats: no direct launch of this film has been finished");
+    *out = f.direct_stats;
+    return RT_OK;
+}
+
+void rt_film_direct_abi_sizes(uint32_t out2[2])
+{
+    out2[0] = (uint32_t)sizeof(rt_film_direct_params);
+    out2[1] = (uint32_t)sizeof(rt_film_direct_stats);
 }
 
 #if RT_PHASES  // diagnostic builds (make EXTRA=-DRT_PHASES=1 LIBNAME=...): the per-phase table
@@ -845,6 +954,10 @@ int rt_render_finish(rt_scene *scene, rt_film *film, rt_render_stats *stats)
     if (waited != hipSuccess && f.last_stream) hipStreamSynchronize(f.last_stream);  // whatever is left on the stream
     mark_done(f);  // also when the wait failed: the scene must not stay locked for ever
     if (waited != hipSuccess) return hip_fail(waited, "hipEventSynchronize(render finished)");
+    if (f.last_direct) {
+        f.direct_stats = rt_film_direct_stats{f.host_counters[kShadowCounterWord], f.host_counters[kShadowCounterWord + 1], (uint32_t)f.last_direct_scratch, 0u};
+        f.has_direct_stats = true;
+    }
     if (stats) {
         std::memset(stats, 0, sizeof *stats);
         float ms_seed = 0, ms_render = 0;

@@ -481,6 +481,16 @@ rt_launch_plan plan_launch(const DeviceScene &sc, const FilmGeometry &film, int 
     return plan;
 }
 
+uint32_t film_direct_blocks(int fit_per_cu, int max_blocks_per_cu, int num_cus, uint32_t n_tiles)
+{
+    uint32_t per_cu = fit_per_cu > 0 ? (uint32_t)fit_per_cu : 1u;
+    if (max_blocks_per_cu > 0 && per_cu > (uint32_t)max_blocks_per_cu) per_cu = (uint32_t)max_blocks_per_cu;
+    const uint32_t resident = per_cu * (uint32_t)(num_cus > 0 ? num_cus : 256);
+    const uint32_t needed = (n_tiles + 3u) / 4u;  // a workgroup's 256 lanes are four tiles' positions
+    const uint32_t blocks = needed < resident ? needed : resident;
+    return blocks > 0 ? blocks : 1u;
+}
+
 }  // namespace rtow
 
 using namespace rtow;

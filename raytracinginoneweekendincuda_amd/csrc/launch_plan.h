@@ -25,6 +25,7 @@ enum : int {
     KIND_GROUPED = 128,       // list scan with the leaves of every ray dealt to several lanes
     KIND_SEGMENTED = 256,     // composite world walked through the library's tree, one walk per run of surfaces between media
     KIND_ADAPTIVE = 512,      // the Adaptive<> form of the instantiation
+    KIND_DIRECT = 1024,       // film_direct_kernel: a frame with light samples (rt_render_launch_direct), beside the world's bits
     // The scheduler's predicates look at the bits below KIND_LIBRARY_TREE only (the same kernel is scheduled the same way with
     // or without the bits above).  KIND_NESTED is one of them, so a nested kernel (39, 47) is none of "BVH kernel", "list-scan
     // kernel", "sphere-list kernel": it gets no tile ranking and no pixel classes.  Kept as it has always been: the nested
@@ -101,6 +102,9 @@ constexpr int kernel_kind(const KernelProps &k, bool adaptive)
            (k.seg ? KIND_SEGMENTED : 0) + (adaptive ? KIND_ADAPTIVE : 0);
 }
 
+// a frame with light samples: the kind of the nested instantiation whose search it runs, and KIND_DIRECT
+constexpr int film_direct_kind(const KernelProps &k, bool adaptive) { return kernel_kind(k, adaptive) | KIND_DIRECT; }
+
 // ---- 2. The LDS layout of one instantiation for one scene ----
 // Sizes of what the kernels keep in LDS besides the scene's tables (render.hip asserts that they are its own).
 constexpr size_t kStagedNodeBytes = 72;                   // a reference-tree node row as staged (render.hip kLdsNodeBytes)
@@ -169,5 +173,11 @@ rt_launch_plan plan_frame(int kernel_kind, int lds_bytes, const FilmGeometry &fi
 // The whole plan: kernel choice (with plan_frame's pixels_per_wave), LDS layout, frame plan.
 rt_launch_plan plan_launch(const DeviceScene &sc, const FilmGeometry &film, int num_cus, const rt_render_params &p, bool adaptive,
                            bool in_boxes);
+
+// ---- 5. The grid of a frame with light samples (render.hip film_direct_kernel) ----
+// Persistent workgroups of 256 lanes that take pixels from a queue of n_tiles * 64 positions: as many as are resident at once
+// -- `fit_per_cu` per CU as the runtime reports it (at least one), capped by max_blocks_per_cu where that is positive -- and
+// never more than the queue has lanes' worth of positions; at least one.
+uint32_t film_direct_blocks(int fit_per_cu, int max_blocks_per_cu, int num_cus, uint32_t n_tiles);
 
 }  // namespace rtow

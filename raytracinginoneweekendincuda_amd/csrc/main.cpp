@@ -220,7 +220,7 @@ int main(int argc, char **argv)
     int pick_i = 0, pick_j = 0;
     bool radiance_at = false;    // --radiance-at i,j: the light that comes back along the centre ray of that pixel, one line, no render
     bool trace_at = false;       // --trace-at i,j: that path vertex by vertex (rt_scene_path_step), then --radiance-at's line
-    bool direct_mis = false;     // --direct mis: --radiance-at's samples are the MIS estimator with light samples (rt_scene_radiance_direct)
+    bool direct_mis = false;     // --direct mis: the MIS estimator with light samples, for --radiance-at's samples (rt_scene_radiance_direct) or, without it, for the frame (rt_render_launch_direct)
     bool list_lights = false;    // --lights: the scene's light table (rt_scene_dump_lights), a line per light, no render
     for (int k = 1; k < argc; k++) {
         std::string a = argv[k];
@@ -314,16 +314,18 @@ int main(int argc, char **argv)
                          "            [--earth earthmap.jpg|decoded.ppm | --earth-bytes texture.ppm] [--accelerate-lists] [--flags N]\n"
                          "            [--noise T [--min-spp N] [--check-every K] [--samples-map file.pgm]]\n"
                          "            [--denoise [--denoise-iterations N] [--denoise-sigmas c,a,n,z] [--raw-output file.ppm]]\n"
-                         "            [--aov-prefix P] [--feature-samples N] [--pick i,j] [--radiance-at i,j [--direct mis]] [--trace-at i,j] [--lights]\n"
+                         "            [--aov-prefix P] [--feature-samples N] [--pick i,j] [--radiance-at i,j] [--trace-at i,j] [--lights] [--direct mis]\n"
                          "  --lights       render nothing: print the light table (rt_scene_dump_lights), a line per emissive primitive in world space --\n"
                          "                 kind, world leaf, material row, geometry, and its entries of the two cumulative selection tables\n"
                          "  --pick         render nothing: print what the ray through the centre of pixel (i, j) hits (j = 0 is the bottom row) --\n"
                          "                 leaf, material kind, t, point, normal, albedo -- at the shutter's opening, over [0.001, inf)\n"
                          "  --radiance-at  render nothing: path-trace the same ray, --spp samples (default 1) of --depth bounces from the pixel's stream,\n"
                          "                 and print the linear radiance, the rays traced and the kernel's time\n"
-                         "  --direct mis   with --radiance-at: every sample takes a light sample at each diffuse hit and weights it against the lamps\n"
-                         "                 scattering finds (rt_scene_radiance_direct); the line then ends with the shadow rays cast and those that\n"
-                         "                 reached their lamp\n"
+                         "  --direct mis   every sample takes a light sample at each diffuse hit and weights it against the lamps scattering finds.\n"
+                         "                 With --radiance-at (rt_scene_radiance_direct): the line then ends with the shadow rays cast and those that\n"
+                         "                 reached their lamp.  Without it the frame is rendered that way (rt_render_launch_direct, lights picked by area\n"
+                         "                 and brightness), with --noise, --denoise, --aov-prefix, --samples-map and --output as for any frame.  One GPU\n"
+                         "                 (no --gpus)\n"
                          "  --trace-at     render nothing: the same paths one bounce at a time (rt_scene_path_step), a line per vertex -- sample, depth,\n"
                          "                 status (0 miss, 1 the path ends, 2 scattered), t, material, emitted, attenuation -- folded here, on the host;\n"
                          "                 the last line is --radiance-at's (to the last bit with --variant strict; its time is the steps' kernels')\n"
@@ -375,8 +377,13 @@ int main(int argc, char **argv)
         return 2;
     }
     if (radiance_at && spp < 0) spp = 1;
-    if (direct_mis && (!radiance_at || trace_at)) {
-        std::fprintf(stderr, "--direct goes with --radiance-at\n");
+    if (direct_mis && (trace_at || list_lights || (pick && !radiance_at))) {
+        std::fprintf(stderr, "--direct goes with --radiance-at, or with a frame: not with --pick, --trace-at or --lights\n");
+        return 2;
+    }
+    const bool direct_frame = direct_mis && !pick;  // the frame itself by the MIS estimator (rt_render_launch_direct)
+    if (direct_frame && gpus >= 1) {
+        std::fprintf(stderr, "--direct renders its frame on one GPU (no --gpus)\n");
         return 2;
     }
     if (trace_at && (spp < 1 || depth < 0)) {  // (what rt_scene_radiance refuses for --radiance-at)
@@ -617,6 +624,8 @@ int main(int argc, char **argv)
         clean.resize(frame.size());
         return rt_film_denoise(film, &dp) == RT_OK && rt_film_download_denoised(film, clean.data(), width, height) == RT_OK;
     };
+    const rt_film_direct_params direct_params{1, {0, 0, 0, 0, 0, 0, 0}};  // lights picked by area x brightest channel
+    auto launch = [&](rt_film *film) { return direct_frame ? rt_render_launch_direct(scene, film, &p, &direct_params) : rt_render_launch(scene, film, &p); };
     if (gpus >= 1) {
         if (render_multi_gpu(scene, p, gpus, frame.data(), &st, &gather_s, wants_features ? &features : nullptr) != 0) return die("render (multi-GPU)");
         if (denoise) {  // the planes are gathered: the same kernel on the whole frame, on GPU 0
@@ -625,19 +634,19 @@ int main(int argc, char **argv)
                                  clean.data()) != RT_OK)
                 return die("denoise");
         }
-    } else if (wants_features && !adaptive) {
+    } else if ((wants_features || direct_frame) && !adaptive) {
         rt_film *film = rt_film_create(device, width, height, p.stripe_rows, 0, 1);
         if (!film) return die("film");
-        if (rt_render_launch(scene, film, &p) != RT_OK || rt_render_finish(scene, film, &st) != RT_OK) return die("render");
+        if (launch(film) != RT_OK || rt_render_finish(scene, film, &st) != RT_OK) return die("render");
         if (rt_film_download(film, frame.data(), width, height) != RT_OK) return die("download");
-        if (!film_features(film)) return die("features / denoise");
+        if (wants_features && !film_features(film)) return die("features / denoise");
         rt_film_destroy(film);
     } else if (adaptive) {
         rt_film *film = rt_film_create(device, width, height, p.stripe_rows, 0, 1);
         if (!film) return die("film");
         const rt_adaptive_params ap{min_spp, check_every, noise, 0.01};
         if (rt_film_set_adaptive(film, &ap) != RT_OK) return die("adaptive");
-        if (rt_render_launch(scene, film, &p) != RT_OK || rt_render_finish(scene, film, &st) != RT_OK) return die("render");
+        if (launch(film) != RT_OK || rt_render_finish(scene, film, &st) != RT_OK) return die("render");
         if (rt_film_download(film, frame.data(), width, height) != RT_OK) return die("download");
         std::vector<uint32_t> counts((size_t)width * height);
         if (rt_film_download_sample_counts(film, counts.data(), width, height) != RT_OK) return die("sample counts");

@@ -68,8 +68,11 @@
 #ifndef RT_RADIANCE_DIRECT  // 1: this translation unit holds the radiance-query kernels with light samples (radiance_direct_kernel) and nothing else
 #define RT_RADIANCE_DIRECT 0
 #endif
-// the lane-per-ray units: one lane per pixel, ray or point, no persistent waves
-#define RT_LANE_UNIT (RT_FEATURES || RT_QUERY || RT_RADIANCE || RT_STEP || RT_ADVANCE || RT_LIGHTS || RT_ADVANCE_DIRECT || RT_RADIANCE_DIRECT)
+#ifndef RT_FILM_DIRECT  // 1: this translation unit holds the frame kernels with light samples (film_direct_kernel) and nothing else
+#define RT_FILM_DIRECT 0
+#endif
+// the lane-per-ray units: one lane per pixel, ray or point, no persistent waves (film_direct_kernel alone is persistent: its lanes take pixels from a queue)
+#define RT_LANE_UNIT (RT_FEATURES || RT_QUERY || RT_RADIANCE || RT_STEP || RT_ADVANCE || RT_LIGHTS || RT_ADVANCE_DIRECT || RT_RADIANCE_DIRECT || RT_FILM_DIRECT)
 
 namespace rtow {
 namespace {
@@ -317,7 +320,7 @@ DEV bool sphere_test(Vec oc, Vec d, double a, double r2, double tmin, double tma
 // times with the branch (the select costs the media kernel of scene 8 3 %), the lane-per-ray kernels of the feature pass and the
 // queries keep their registers with the select (the branch takes the radiance kernel of list worlds from 168 to 170 VGPRs, from
 // three waves per SIMD to two, 35 % on scene 7).  A third form, a switch case of its own in quad_test_at, cost most kernels spills.
-#define RT_PLANAR_SELECT (RT_FEATURES || RT_QUERY || RT_RADIANCE || RT_STEP || RT_ADVANCE || RT_ADVANCE_DIRECT || RT_RADIANCE_DIRECT)
+#define RT_PLANAR_SELECT (RT_FEATURES || RT_QUERY || RT_RADIANCE || RT_STEP || RT_ADVANCE || RT_ADVANCE_DIRECT || RT_RADIANCE_DIRECT || RT_FILM_DIRECT)
 DEV bool quad_test(const QuadGeom &q, bool tri, const Ray &r, double tmin, double tmax, double &t_out)
 {
     Vec n = mk(q.nx, q.ny, q.nz);
@@ -4408,7 +4411,7 @@ hipError_t RT_CAT(launch_features_, RT_SUFFIX)(const DeviceScene &sc, const Feat
     return hipGetLastError();
 }
 #endif
-#if RT_QUERY || RT_ADVANCE_DIRECT || RT_RADIANCE_DIRECT  // (the search is shadow_kernel's and radiance_direct_kernel's too)
+#if RT_QUERY || RT_ADVANCE_DIRECT || RT_RADIANCE_DIRECT || RT_FILM_DIRECT  // (the search is shadow_kernel's, radiance_direct_kernel's and film_direct_kernel's too)
 // ------------------------------------------------------------------------------------------------
 // Ray queries (rt_scene_intersect): closest hit or occlusion for caller-supplied rays.  The feature pass's search once more -- one
 // lane per ray, no LDS, every table from global memory, the reference's tree or list in the reference's order through leaf_test /
@@ -4901,7 +4904,7 @@ hipError_t RT_CAT(launch_advance_, RT_SUFFIX)(const DeviceScene &sc, const Advan
     return info_or_launch(kernel, sc, a, a.capacity, stream, info);
 }
 #endif
-#if RT_LIGHTS || RT_ADVANCE_DIRECT || RT_RADIANCE_DIRECT  // (the staging and the table's readers are advance_direct_kernel's and radiance_direct_kernel's too)
+#if RT_LIGHTS || RT_ADVANCE_DIRECT || RT_RADIANCE_DIRECT || RT_FILM_DIRECT  // (the staging and the table's readers are advance_direct_kernel's, radiance_direct_kernel's and film_direct_kernel's too)
 // ------------------------------------------------------------------------------------------------
 // Light sampling queries (rt_scene_sample_lights, rt_scene_light_pdf; include/rtow.h states both operation by operation, and
 // tests/light_restated.py restates the strict build to the bit).  One lane per point or ray, the callers' arrays read and written
@@ -5885,6 +5888,442 @@ hipError_t RT_CAT(launch_radiance_direct_, RT_SUFFIX)(const DeviceScene &sc, con
     void (*kernel)(DeviceScene, RadianceDirectArgs) =
         sc.world_kind == WORLD_BVH ? radiance_direct_kernel<RT_STRICT, TBvhNested> : radiance_direct_kernel<RT_STRICT, TListNested>;
     return info_or_launch(kernel, sc, d, a.count, stream, info);
+}
+#elif RT_FILM_DIRECT
+// ------------------------------------------------------------------------------------------------
+// Frames with light samples (rt_render_launch_direct; include/rtow.h states the operation): a film rendered by the estimator of
+// rt_scene_radiance_direct.  The loop is radiance_direct_kernel's, restated line for line -- one world search an iteration, of the
+// lane's path ray or of its pending shadow ray, the light sample and the mixture density between them, the light table staged in
+// LDS once before the loop.  What is new is where the work comes from: the workgroups are persistent, and a lane without a pixel
+// takes the next one from the film's queue word at the top of an iteration -- at the start of the kernel, and when its pixel has
+// just finished -- with one atomic per wave (ballot, popcount, lane prefix).  Queue position q is pixel q % 64 of the 8x8 tile
+// q / 64 of this rank's rows, numbered as render_kernel numbers them; a position outside the frame, or a pixel an adaptive frame
+// has marked, is skipped by taking again.  A lane leaves when the queue is dry and it holds nothing; there is no barrier behind
+// those of stage_lights, so lanes leave at different times.  One refinement, for the frame's last pixels: once the queue holds
+// fewer positions than half the grid's lanes, a wave takes only when none of its lanes holds a pixel -- the last pixels
+// then fill few waves, as a launch of a lane per pixel would fill them, instead of keeping every resident wave alive for one more
+// pixel's time with a handful of lanes each (measured: profiles/r25_film_direct.txt).  A pixel is taken up and laid down as render_kernel does it (stream
+// words, running sum, the planes of adaptive sampling), by one lane from its first sample to its last, from its own stream: the
+// frame cannot depend on which lane took which pixel.
+// Termination: the queue word only grows, and a wave that has seen it pass the queue's length never takes again; a pixel is at
+// most spp samples of at most max_depth path searches and as many shadow searches, each bounded as in radiance_direct_kernel.
+// ------------------------------------------------------------------------------------------------
+template <int STRICT, class T>
+__global__ __launch_bounds__(256) void film_direct_kernel(DeviceScene sc, FilmDirectArgs d)
+{
+    __shared__ __attribute__((aligned(16))) double rows_lds[kLightLdsRows * kLightRowDoubles];
+    __shared__ __attribute__((aligned(16))) double cdf_lds[kLightLdsRows];
+    global_tables_only(sc);
+    LightArgs la{};  // what the table's readers take
+    la.rows = d.rows;
+    la.cdf = d.cdf;
+    la.n_lights = d.n_lights;
+    stage_lights(la, rows_lds, cdf_lds);
+    const LightLds lds{rows_lds, cdf_lds};
+    const CameraRec *__restrict__ cam = sc.camera;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t tiles_x = ((uint32_t)d.width + 7u) >> 3;
+    const uint32_t queue_len = tiles_x * (((uint32_t)d.rows_owned + 7u) >> 3) * 64u;
+    const bool media = (sc.flags & SCENE_HAS_MEDIA) != 0;
+    const bool adaptive = d.adaptive != 0;
+    uint32_t rays = 0, cast = 0, reached = 0, taken = 0;  // path searches, shadow searches, shadow rays that met nothing, samples: this lane's, all its pixels
+    bool dry = false;      // the queue word has passed the queue's length (the same for every lane of the wave still here)
+    bool tail = false;     // the queue held fewer positions than half the grid's lanes when this wave last took (as uniform as dry)
+    const uint32_t grid_lanes = gridDim.x * 256u;
+    bool holding = false;  // this lane has a pixel
+    // the pixel
+    int i = 0, j = 0, sample = 0;
+    size_t local = 0;
+    Xorwow rng{};
+    Vec col = mk(0.0, 0.0, 0.0);
+    uint32_t ad_before = 0;
+    double ad_q = 0.0;
+    // the path: radiance_direct_kernel's state
+    Ray ray;
+    ray.o = mk(0.0, 0.0, 0.0);
+    ray.d = mk(0.0, 0.0, 1.0);
+    ray.tm = 0.0;
+    Vec carried = mk(1.0, 1.0, 1.0), acc = mk(0.0, 0.0, 0.0);  // thr and acc of include/rtow.h
+    double sent = 0.0;                                         // q: the density the bounce before sent `ray` with
+    int depth = 0;
+    bool pending = false;  // a shadow ray (ray.o, shadow_d, ray.tm) up to shadow_end waits; where none is in the way it brings parked
+    Vec shadow_d = mk(0.0, 0.0, 1.0), parked = mk(0.0, 0.0, 0.0);
+    double shadow_end = 0.0;
+    for (;;) {
+        // the take: every lane of the wave still in the loop is here.  One atomic for the lanes without a pixel, again while a
+        // position fell outside the frame or on a marked pixel.
+        while (!dry) {
+            const unsigned long long here = __ballot(true);
+            const unsigned long long need = __ballot(!holding);
+            if (need == 0ull) break;
+            if (tail && need != here) break;  // the last pixels: the wave waits until it is empty, then takes for all its lanes
+            const uint32_t cnt = (uint32_t)__popcll(need);
+            uint32_t base = 0;
+            if (lane == (uint32_t)(__ffsll((long long)here) - 1)) base = atomicAdd(d.cursor, cnt);  // the first lane still here
+            base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
+            if (base + cnt >= queue_len || base + cnt < base) dry = true;
+            else tail = queue_len - (base + cnt) < grid_lanes / 2u;
+            const uint32_t slot = base + (uint32_t)__popcll(need & ((1ull << lane) - 1ull));
+            if (!holding && slot >= base && slot < queue_len) {
+                const uint32_t w = slot & 63u, tile = slot >> 6;
+                const int pi = (int)((tile % tiles_x) * 8u + (w & 7u));
+                const int lr = (int)((tile / tiles_x) * 8u + (w >> 3));
+                bool take = pi < d.width && lr < d.rows_owned;
+                if (take && adaptive) take = d.ad_mark[(size_t)lr * (size_t)d.width + (size_t)pi] == 0;  // stopped in an earlier launch of this frame: it stays as it is
+                if (take) {
+                    i = pi;
+                    j = owned_row(lr, d.stripe_rows, d.rank, d.world_size);
+                    local = (size_t)lr * (size_t)d.width + (size_t)pi;
+                    if (adaptive) {
+                        ad_before = d.ad_n[local];
+                        ad_q = d.ad_q[local];
+                    }
+                    rng.d = d.state[0 * (size_t)d.n_pixels + local];
+                    rng.v0 = d.state[1 * (size_t)d.n_pixels + local];
+                    rng.v1 = d.state[2 * (size_t)d.n_pixels + local];
+                    rng.v2 = d.state[3 * (size_t)d.n_pixels + local];
+                    rng.v3 = d.state[4 * (size_t)d.n_pixels + local];
+                    rng.v4 = d.state[5 * (size_t)d.n_pixels + local];
+                    col = mk(0.0, 0.0, 0.0);
+                    if (d.accum && d.spp_before > 0)  // progressive: continue the running sum in the same order
+                        col = mk(d.accum[local * 3 + 0], d.accum[local * 3 + 1], d.accum[local * 3 + 2]);
+                    sample = 0;
+                    ray = camera_ray(cam, i, j, d.width, d.height, rng);
+                    carried = mk(1.0, 1.0, 1.0);
+                    acc = mk(0.0, 0.0, 0.0);
+                    sent = 0.0;
+                    depth = 0;
+                    pending = false;
+                    holding = true;
+                }
+            }
+        }
+        if (!holding) {
+            if (dry) break;  // the queue is dry and this lane holds nothing
+            continue;        // (the last pixels: lanes of this wave still hold theirs; it takes again when they are done)
+        }
+        bool lamp = false, sampled = false, path_ends = false;
+        // what the density loop and the fold behind it read: the ray the density is asked along, its light and weights
+        Vec along_o = mk(0.0, 0.0, 0.0), along_d = mk(0.0, 0.0, 1.0), light = mk(0.0, 0.0, 0.0);
+        double along_tm = 0.0, other = 0.0, distance = 0.0;
+        if (d.max_depth <= 0) {  // no bounce runs: black, only the camera's draws are taken
+            path_ends = true;
+        } else {
+            const bool shadow = pending;
+            Ray searched = ray;
+            double tmax = DBL_MAX;
+            bool stop_at_first = false;
+            if (shadow) {  // as shadow_kernel calls the search
+                searched.d = shadow_d;
+                tmax = shadow_end;
+                stop_at_first = !media;  // a medium's answer depends on what was found before it: the full search
+            }
+            HitInfo h;
+            uint32_t leaf = kNone;
+            const bool hit = query_search<T>(sc, d.node_leaf_pos, searched, 0.001, tmax, stop_at_first, h, leaf, rng);
+            if (shadow) {
+                cast++;
+                if (!hit) {
+                    reached++;
+                    acc = acc + parked;
+                }
+                pending = false;
+            } else {
+                rays++;
+                Vec throughput = mk(1.0, 1.0, 1.0), accumulated = mk(0.0, 0.0, 0.0);
+                Vec normal = mk(0.0, 0.0, 0.0);
+                uint32_t kind = 255u;
+                bool scattered = false;
+                if (!hit) {  // R/kernel.cu:74-79
+                    accumulated = accumulated + throughput * load3c(((const RT_CONST CameraRec *)(uintptr_t)sc.camera)->bg);
+                } else {
+                    const Surface s = make_surface<T>(sc, ray, h);
+                    if ((h.ref >> kRefShift) != REF_MEDIUM) normal = s.n;
+                    kind = material_view<false>(sc, s.mat).u32(MAT_OFF(kind));
+                    scattered = shade<T>(sc, s, ray, throughput, accumulated, rng);  // scattered: `ray` is the next ray; else it is untouched
+                }
+                normal = mk(0.0, 0.0, 0.0) + normal;  // as query_kernel: no negative zeros
+                if (!scattered) {
+                    path_ends = true;
+                    lamp = hit && kind == MAT_DIFFUSE_LIGHT && sent > 0.0;
+                    if (lamp) {  // weighted behind the density loop, along the incoming ray as given
+                        along_o = ray.o;
+                        along_d = ray.d;
+                        along_tm = ray.tm;
+                        light = carried * accumulated;
+                        other = sent;
+                    } else {  // w = 1
+                        acc = acc + carried * accumulated;
+                    }
+                } else {
+                    const Vec next = carried * throughput;
+                    double sent_next = 0.0;
+                    const bool sample_here = depth + 1 < d.max_depth;  // the last bounce takes none: its light sample would stand for bounce max_depth
+                    if ((kind == MAT_LAMBERTIAN || kind == MAT_ISOTROPIC) && d.n_lights != 0 && sample_here) {
+                        // light_sample_kernel's sample for the point ray.o at the time ray.tm, from the path's stream
+                        const Vec P = ray.o;
+                        const double tm = ray.tm;
+                        bool valid = false;
+                        Vec dir = mk(0.0, 0.0, 0.0), emitted = mk(0.0, 0.0, 0.0), contribution = mk(0.0, 0.0, 0.0);
+                        double pdf = 0.0, scatter = 0.0;
+                        const double xi = (double)xorwow_uniform(rng);
+                        uint32_t lo = 0, hi = d.n_lights - 1u;  // the first row with cdf >= xi; the last entry is 1.0 >= xi
+                        while (lo < hi) {
+                            const uint32_t mid = (lo + hi) / 2u;
+                            if (light_cdf(la, lds, mid) >= xi) hi = mid;
+                            else lo = mid + 1u;
+                        }
+                        const double chance = light_cdf(la, lds, lo) - (lo ? light_cdf(la, lds, lo - 1u) : 0.0);
+                        const LightRow L = light_row(la, lds, lo);
+                        Vec S = mk(0.0, 0.0, 0.0), centre = mk(0.0, 0.0, 0.0);
+                        double u = 0.0, v = 0.0;
+                        if (L.kind <= LIGHT_TRIANGLE) {
+                            double ua = (double)xorwow_uniform(rng);
+                            double ub = (double)xorwow_uniform(rng);
+                            if (L.kind == LIGHT_TRIANGLE && ua + ub > 1.0) {
+                                ua = 1.0 - ua;
+                                ub = 1.0 - ub;
+                            }
+                            S = (load3(L.a) + ua * load3(L.b)) + ub * load3(L.c);
+                            const Vec D = S - P;
+                            const double d2 = dot(D, D);
+                            if (d2 > 0.0) {
+                                const double len = sqrt(d2);
+                                const Vec unit_d = over(D, len);
+                                const double c = fabs(dot(load3(L.n), unit_d));
+                                if (c != 0.0) {
+                                    const double density = (d2 / (c * L.s)) * chance;
+                                    if (usable_density(density)) {
+                                        valid = true;
+                                        dir = unit_d;
+                                        distance = len;
+                                        pdf = density;
+                                    }
+                                }
+                            }
+                            u = ua;
+                            v = ub;
+                        } else {
+                            Vec p;
+                            double s;
+                            do {  // the lens loop of camera_ray
+                                const double da = (double)xorwow_uniform(rng);
+                                const double db = (double)xorwow_uniform(rng);
+                                p = mk(2.0 * da - 1.0, 2.0 * db - 1.0, 0.0);
+                                s = p.x * p.x + p.y * p.y;
+                            } while (!(s < 1.0 && s > 0.0));
+                            centre = light_centre(L, tm);
+                            const Vec oc = centre - P;
+                            const double d2 = dot(oc, oc), r2 = L.s * L.s;
+                            if (d2 > r2) {
+                                const Vec w = over(oc, sqrt(d2));
+                                const double cosmax = sqrt(1.0 - r2 / d2);
+                                const double omc = 1.0 - cosmax;
+                                const double z = 1.0 - s * omc;
+                                const double rho = sqrt(1.0 - z * z);
+                                const double q = sqrt(s);
+                                const double ex = (rho * p.x) / q, ey = (rho * p.y) / q;
+                                const double ax = fabs(w.x), ay = fabs(w.y), az = fabs(w.z);
+                                Vec e1;
+                                if (ax >= ay && ax >= az) e1 = over(mk(w.z, 0.0, -w.x), sqrt(w.z * w.z + w.x * w.x));
+                                else if (ay >= az) e1 = over(mk(-w.y, w.x, 0.0), sqrt(w.y * w.y + w.x * w.x));
+                                else e1 = over(mk(0.0, -w.z, w.y), sqrt(w.z * w.z + w.y * w.y));
+                                const Vec e2 = cross(w, e1);
+                                const Vec g = (z * w + ex * e1) + ey * e2;
+                                const Vec unit_d = over(g, sqrt(dot(g, g)));
+                                const Vec po = P - centre;
+                                const double qa = dot(unit_d, unit_d), qb = dot(po, unit_d), qc = dot(po, po) - r2;
+                                const double disc = qb * qb - qa * qc;
+                                const double len = (-qb - sqrt(disc)) / qa;
+                                const double density = chance / ((2.0 * kLightPi) * omc);
+                                if (omc != 0.0 && usable_density(density) && disc > 0.0 && len > 0.0) {
+                                    valid = true;
+                                    dir = unit_d;
+                                    distance = len;
+                                    pdf = density;
+                                    S = P + len * unit_d;
+                                }
+                            }
+                        }
+                        if (valid) {
+                            const MatView mp = material_view<false>(sc, L.mat);
+                            if (L.kind >= LIGHT_SPHERE && mp.u32(MAT_OFF(needs_uv)) != 0) sphere_uv((1 / L.s) * (S - centre), u, v);
+                            emitted = material_texture<T>(sc, mp, mp.u32(MAT_OFF(tex_inline)), u, v, S);
+                            if (kind == MAT_LAMBERTIAN) {
+                                const double c = dot(normal, dir);
+                                if (c > 0.0) scatter = (2.0 * ((c * c) * c)) / kLightPi;
+                            } else {
+                                scatter = 1.0 / (4.0 * kLightPi);
+                            }
+                            if (scatter != 0.0) contribution = (scatter / pdf) * emitted;
+                        }
+                        sampled = contribution.x != 0.0 || contribution.y != 0.0 || contribution.z != 0.0;
+                        if (sampled) {  // weighted behind the density loop, along the sample
+                            along_o = P;
+                            along_d = dir;
+                            along_tm = tm;
+                            light = next * contribution;
+                            other = scatter;
+                        }
+                        // the density with which the material sent the scattered ray where it goes: the closed form above for its unit direction
+                        const Vec unit_next = (1 / sqrt((ray.d.x * ray.d.x + ray.d.y * ray.d.y) + ray.d.z * ray.d.z)) * ray.d;
+                        if (kind == MAT_LAMBERTIAN) {
+                            const double c = dot(normal, unit_next);
+                            if (c > 0.0) sent_next = (2.0 * ((c * c) * c)) / kLightPi;
+                        } else {
+                            sent_next = 1.0 / (4.0 * kLightPi);
+                        }
+                    }
+                    carried = next;
+                    sent = sent_next;
+                    if (++depth >= d.max_depth) path_ends = true;  // still alive after the last bounce: dropped (R/kernel.cu:71,97)
+                }
+            }
+        }
+        // every lane that holds a pixel is here again.  The mixture density along `along`: radiance_direct_kernel's loop, every such
+        // lane of the wave on row i (a lane that needs none runs it on a ray of its own that meets what it meets: its sum is not read)
+        double density_sum = 0.0;
+        if (__ballot(lamp || sampled) != 0ull) {
+            const Vec o = along_o, dv = along_d;
+            const double tm = along_tm;
+            const double dd = dot(dv, dv);
+            double before = 0.0;
+            for (uint32_t k = 0; k < d.n_lights; k++) {
+                const LightRow L = light_row(la, lds, k);
+                const double upto = light_cdf(la, lds, k);
+                const double chance = upto - before;
+                before = upto;
+                double density = 0.0;
+                if (L.kind <= LIGHT_TRIANGLE) {
+                    const Vec nn = load3(L.n), Q = load3(L.a), U = load3(L.b), V = load3(L.c);
+                    const double denom = dot(nn, dv);
+                    if (denom != 0.0) {
+                        const double t = dot(nn, Q - o) / denom;
+                        if (t > 0.0) {
+                            const Vec ph = (o + t * dv) - Q;
+                            const Vec m = cross(U, V);
+                            const double mm = dot(m, m);
+                            const double alpha = dot(m, cross(ph, V)) / mm, beta = dot(m, cross(U, ph)) / mm;
+                            const bool below = L.kind == LIGHT_TRIANGLE ? alpha + beta <= 1.0 : (alpha <= 1.0 && beta <= 1.0);
+                            if (0.0 <= alpha && 0.0 <= beta && below) density = (((t * t) * dd) / ((fabs(denom) / sqrt(dd)) * L.s)) * chance;
+                        }
+                    }
+                } else {
+                    const Vec oc = light_centre(L, tm) - o;
+                    const double d2 = dot(oc, oc), r2 = L.s * L.s;
+                    if (d2 > r2) {
+                        const double b = dot(oc, dv);
+                        const double disc = b * b - dd * (d2 - r2);
+                        if (b > 0.0 && disc >= 0.0) {
+                            const double omc = 1.0 - sqrt(1.0 - r2 / d2);
+                            if (omc != 0.0) density = chance / ((2.0 * kLightPi) * omc);
+                        }
+                    }
+                }
+                if (usable_density(density)) density_sum = density_sum + density;
+            }
+        }
+        if (lamp) {  // w = q / (q + p): the scattered ray found the lamp a light sample of the bounce before could have found
+            const double w = other / (other + density_sum);
+            acc = acc + w * light;
+        }
+        if (sampled) {  // w = p / (p + s); the shadow ray decides in this lane's next iteration
+            const double both = density_sum + other;
+            const double w = both == 0.0 ? 0.0 : density_sum / both;
+            parked = w * light;
+            shadow_d = along_d;
+            shadow_end = fmin(distance * (1.0 - 0x1p-20), DBL_MAX);
+            pending = true;
+        }
+        if (path_ends) {  // (never with a sample pending)  R/kernel.cu:143: col += RayColor(...)
+            col = col + acc;
+            taken++;
+            bool more = ++sample < d.spp;
+            bool converged = false;
+            if (adaptive) {
+                ad_q = adaptive_add_sample(ad_q, acc.x, acc.y, acc.z);
+                // (also at the launch's cap: the mark must be right for a later launch of the frame)
+                converged = adaptive_converged(d.rule, ad_before + (uint32_t)sample, col.x, col.y, col.z, ad_q);
+                if (converged) more = false;
+            }
+            if (more) {
+                ray = camera_ray(cam, i, j, d.width, d.height, rng);
+                carried = mk(1.0, 1.0, 1.0);
+                acc = mk(0.0, 0.0, 0.0);
+                sent = 0.0;
+                depth = 0;
+            } else {
+                // R/kernel.cu:146-153: save the RNG state, average, gamma 2
+                d.state[0 * (size_t)d.n_pixels + local] = rng.d;
+                d.state[1 * (size_t)d.n_pixels + local] = rng.v0;
+                d.state[2 * (size_t)d.n_pixels + local] = rng.v1;
+                d.state[3 * (size_t)d.n_pixels + local] = rng.v2;
+                d.state[4 * (size_t)d.n_pixels + local] = rng.v3;
+                d.state[5 * (size_t)d.n_pixels + local] = rng.v4;
+                if (d.accum) {
+                    d.accum[local * 3 + 0] = col.x;
+                    d.accum[local * 3 + 1] = col.y;
+                    d.accum[local * 3 + 2] = col.z;
+                }
+                if (adaptive) {  // the pixel's own n
+                    const uint32_t n = ad_before + (uint32_t)sample;
+                    d.ad_n[local] = n;
+                    d.ad_q[local] = ad_q;
+                    d.ad_mark[local] = converged ? 1 : 0;
+                    col = over(col, (double)n);
+                } else {
+                    col = over(col, (double)(d.spp_before + d.spp));
+                }
+                d.pixels[local * 3 + 0] = sqrt(col.x);
+                d.pixels[local * 3 + 1] = sqrt(col.y);
+                d.pixels[local * 3 + 2] = sqrt(col.z);
+                holding = false;
+            }
+        }
+    }
+    // four atomics per wave at the most: every lane of the wave is here again
+    unsigned long long searched = rays, shadows = cast, unblocked = reached, samples = taken;
+    for (int step = 32; step > 0; step >>= 1) {
+        searched += __shfl_xor(searched, step, 64);
+        shadows += __shfl_xor(shadows, step, 64);
+        unblocked += __shfl_xor(unblocked, step, 64);
+        samples += __shfl_xor(samples, step, 64);
+    }
+    if (lane == 0) {
+        if (searched) atomicAdd(d.ray_counter, searched);
+        if (adaptive && samples) atomicAdd(d.ray_counter + 2, samples);  // as the Adaptive<> render kernels count them
+        if (shadows) atomicAdd(d.shadow_counters, shadows);
+        if (unblocked) atomicAdd(d.shadow_counters + 1, unblocked);
+    }
+}
+
+hipError_t RT_CAT(launch_film_direct_, RT_SUFFIX)(const DeviceScene &sc, const FilmDirectArgs &d, hipStream_t stream, FilmDirectInfo *info)
+{
+    if (d.spp < 0 || d.max_depth < 0 || d.width <= 0 || d.rows_owned < 0) return hipErrorInvalidValue;
+    if (!info) {
+        if (!d.pixels || !d.state || !d.ray_counter || !d.cursor || !d.shadow_counters) return hipErrorInvalidValue;
+        if (d.adaptive && (!d.ad_n || !d.ad_q || !d.ad_mark)) return hipErrorInvalidValue;
+        if (d.n_lights != 0 && (!d.rows || !d.cdf)) return hipErrorInvalidValue;
+        if (sc.world_kind == WORLD_BVH && !d.node_leaf_pos) return hipErrorInvalidValue;
+    }
+    const bool bvh = sc.world_kind == WORLD_BVH;
+    void (*kernel)(DeviceScene, FilmDirectArgs) = bvh ? film_direct_kernel<RT_STRICT, TBvhNested> : film_direct_kernel<RT_STRICT, TListNested>;
+    if (info) {
+        hipFuncAttributes attr;
+        if (hipError_t e = hipFuncGetAttributes(&attr, reinterpret_cast<const void *>(kernel)); e != hipSuccess) return e;
+        info->kernel.vgprs = attr.numRegs;
+        info->kernel.lds_bytes = (int)attr.sharedSizeBytes;
+        info->kernel.kind = film_direct_kind(bvh ? props_of<TBvhNested>() : props_of<TListNested>(), d.adaptive != 0);
+        info->scratch_bytes = (int)attr.localSizeBytes;
+        return hipSuccess;
+    }
+    if (d.n_pixels == 0 || d.spp <= 0) return hipSuccess;
+    int per_cu = 0;
+    if (hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 256, 0); e != hipSuccess) return e;
+    const uint32_t tiles = (((uint32_t)d.width + 7u) >> 3) * (((uint32_t)d.rows_owned + 7u) >> 3);
+    const uint32_t blocks = film_direct_blocks(per_cu, d.max_blocks_per_cu, d.num_cus, tiles);
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, stream, sc, d);
+    return hipGetLastError();
 }
 #elif RT_LANE_UNIT
 // (a lane-per-ray unit defined above)

@@ -311,6 +311,42 @@ struct RadianceDirectArgs {
 hipError_t launch_radiance_direct_strict(const DeviceScene &sc, const RadianceDirectArgs &a, hipStream_t stream, QueryKernelInfo *info = nullptr);
 hipError_t launch_radiance_direct_fast(const DeviceScene &sc, const RadianceDirectArgs &a, hipStream_t stream, QueryKernelInfo *info = nullptr);
 
+// Frames with light samples (rt_render_launch_direct; the RT_FILM_DIRECT objects of render.hip): the film's planes as RenderArgs
+// carries them, the light table and node_leaf_pos as RadianceDirectArgs carries them.  film_direct_kernel is
+// radiance_direct_kernel's loop in persistent workgroups of 256 whose lanes take pixels from the queue word `cursor`, one
+// wave-aggregated atomic a take; no rehearsal, no pixel classes, no tile order, no primary lists.
+struct FilmDirectArgs {
+    double *pixels;              // rows_owned x width x 3
+    double *accum;               // progressive rendering: running (unnormalised) colour sums, or nullptr
+    int32_t spp_before;          // samples already in accum
+    uint32_t *state;             // 6 planes of n_pixels words: d, v0..v4
+    unsigned long long *ray_counter;  // [0] path searches, [2] samples taken (adaptive sampling), as RenderArgs
+    uint32_t *cursor;            // pixel-queue cursor, zeroed before every launch
+    uint32_t n_pixels;
+    int32_t width, height, rows_owned;
+    int32_t spp, max_depth;
+    int32_t stripe_rows, rank, world_size;
+    int32_t num_cus;
+    int32_t max_blocks_per_cu;   // cap on resident workgroups per CU (0 = whatever fits)
+    int32_t adaptive;            // as RenderArgs: spp is the most a pixel may take in this launch
+    AdaptiveRule rule;
+    uint32_t *ad_n;
+    double *ad_q;
+    uint8_t *ad_mark;
+    const LightRow *rows;               // n_lights
+    const double *cdf;                  // the cumulative table of the launch's strategy, padded to an even length
+    uint32_t n_lights;
+    const uint32_t *node_leaf_pos;      // as QueryArgs
+    unsigned long long *shadow_counters;  // two words, zeroed by the caller: shadow rays cast, shadow rays that reached their lamp
+};
+struct FilmDirectInfo {
+    KernelInfo kernel;  // kind: the nested instantiation's, with KIND_DIRECT
+    int scratch_bytes;
+};
+// info != nullptr: report the instantiation that would run instead of launching it
+hipError_t launch_film_direct_strict(const DeviceScene &sc, const FilmDirectArgs &a, hipStream_t stream, FilmDirectInfo *info = nullptr);
+hipError_t launch_film_direct_fast(const DeviceScene &sc, const FilmDirectArgs &a, hipStream_t stream, FilmDirectInfo *info = nullptr);
+
 // Light sampling queries (rt_scene_sample_lights, rt_scene_light_pdf; the RT_LIGHTS objects of render.hip): one lane per point or
 // ray, 256-thread workgroups that first stage the first kLightLdsRows rows of the light table and of its cumulative table in LDS.
 // The table is not part of DeviceScene: it comes through these arguments.  `sc` is still passed, for the material and texture

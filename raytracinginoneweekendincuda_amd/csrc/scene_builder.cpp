@@ -1729,6 +1729,16 @@ rt_rng *rt_rng_create_salted(uint64_t seed, uint64_t sequence, int salt_kind)
     return reinterpret_cast<rt_rng *>(r);
 }
 rt_rng *rt_rng_create(uint64_t seed, uint64_t sequence) { return rt_rng_create_salted(seed, sequence, 0); }
+rt_rng *rt_rng_create_from_state(const uint32_t in6[6])
+{
+    if (!in6) {
+        fail(RT_ERR_INVALID, "rt_rng_create_from_state: null state");
+        return nullptr;
+    }
+    RngImpl *r = new RngImpl;
+    r->state.d = in6[0]; r->state.v0 = in6[1]; r->state.v1 = in6[2]; r->state.v2 = in6[3]; r->state.v3 = in6[4]; r->state.v4 = in6[5];
+    return reinterpret_cast<rt_rng *>(r);
+}
 void rt_rng_destroy(rt_rng *rng) { delete reinterpret_cast<RngImpl *>(rng); }
 float rt_rng_uniform(rt_rng *rng) { return xorwow_uniform(reinterpret_cast<RngImpl *>(rng)->state); }
 uint32_t rt_rng_next_u32(rt_rng *rng) { return xorwow_next(reinterpret_cast<RngImpl *>(rng)->state); }
