@@ -2341,8 +2341,11 @@ DEV void scan_grouped(const SphereView &sv, uint32_t lane, unsigned long long to
     const int log2g = 6 - log2m;
     const uint32_t g = 1u << log2g;
     const uint32_t q = lane >> log2g, s = lane & (g - 1u);  // my ray slot and my place in its group
-    // owner of slot q = the q-th live lane
-    int owner = (int)lane;
+    // owner of slot q = the q-th live lane.  L rays go to m >= L groups: a group without a ray (q >= L) scans the FIRST ray once
+    // more, in step with group 0 -- the same spheres pass in the same slots, so it adds no block, and nobody reads its result.
+    // (Left with their own lanes' registers, each lane of such a group scanned another stale ray, and what the filters call
+    // degenerate passes every sphere: on C2 109.7 of the 118.1 lanes tested per pass were theirs, profiles/r26_c2_grouped_far.txt.)
+    int owner = todo ? __ffsll((long long)todo) - 1 : (int)lane;
     {
         unsigned long long m = todo;
         for (int r = 0; r < L; r++) {
