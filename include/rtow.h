@@ -114,7 +114,7 @@ RTOW_API rt_handle rt_quad(rt_scene *s, const double q[3], const double u[3], co
  *               alpha, beta, with the same t bit for bit.  Neighbouring triangles of a mesh are decided each by its own rounded
  *               alpha, beta: the arithmetic promises no watertightness along shared edges (DESIGN.md section 5 has the count).
  *   HitRecord   U = alpha, V = beta (the barycentric coordinates of Q+u and Q+v); the normal is the flat geometric one, set
- *               against the ray (SetFaceNormal); no vertex normals, no per-vertex texture coordinates
+ *               against the ray (SetFaceNormal); corner normals and texture coordinates: rt_triangle_attr below
  *   degenerate  u x v = 0: normal and w are not finite and no ray is accepted, like a degenerate quad
  *   box         per axis the min and max of Q, fl(Q+u), fl(Q+v), through the corner constructor the quad uses (AABB.h:34-40) with
  *               its padding of axes thinner than 0.0001 (AABB.h:114-120)
@@ -135,6 +135,57 @@ RTOW_API rt_handle rt_triangle_mesh(rt_scene *s, const double *vertices, int n_v
  * a face, an index out of range (0 included), a vertex with fewer than three numbers or a face with fewer than three corners. */
 RTOW_API int rt_obj_load(const char *path, double **vertices, int *n_vertices, int32_t **indices, int *n_triangles);
 RTOW_API void rt_mesh_free(double *vertices, int32_t *indices);
+/* Corner attributes: a triangle may carry three corner normals n0, n1, n2 (normals: 9 doubles, or NULL) and / or three corner
+ * texture coordinates t0, t1, t2 (texcoords: 6 doubles u0 v0 u1 v1 u2 v2, or NULL).  Corner 0 is Q, corner 1 is Q+u, corner 2 is Q+v.
+ * With both NULL the call is rt_triangle exactly.
+ *   Hit         unchanged: t, the interior rule, the box, the leaf, the ties and front_face = dot(dir, ng) < 0 are rt_triangle's,
+ *               where ng is the row's geometric unit normal (`normal` above).  Only the hit record differs.
+ *   HitRecord   in the space the hit was found in (below any Translate / RotateY), each line one IEEE double operation per
+ *               arithmetic sign, nothing contracted in the strict build:
+ *                 p = ray(t), ph = p - Q
+ *                 alpha = dot(w, cross(ph, v)), beta = dot(w, cross(u, ph))     (the U, V of rt_triangle)
+ *                 gamma = (1.0 - alpha) - beta
+ *               with normals, per component:
+ *                 m  = (gamma * n0 + alpha * n1) + beta * n2
+ *                 ns = unit(m) = (1 / sqrt(length_sq(m))) * m,  length_sq(m) = m.x*m.x + m.y*m.y + m.z*m.z
+ *                 ns = ng  where length_sq(m) is not a finite positive number or dot(ns, ng) <= 0: a shading normal never points
+ *                          under the geometric surface
+ *                 Normal = front_face ? ns : -ns, then back through the instance chain as the flat normal goes
+ *               with texture coordinates:
+ *                 U = (gamma * t0.u + alpha * t1.u) + beta * t2.u,  V = (gamma * t0.v + alpha * t1.v) + beta * t2.v
+ *               without them U = alpha, V = beta.  Render and shading kernels compute U, V only for materials that read them
+ *               (an ImageTexture in the texture tree), ray queries whenever they are asked for.
+ *   scatter     materials see only Normal: a direction scattered about ns may point below the geometric surface and is accepted
+ *               as it is (a Lambertian's ns + unit vector, a metal's reflection about ns near a silhouette).
+ *   refused     (returns 0, nothing added, rt_last_error says why) a corner normal with a non-finite component or all zero -- they
+ *               are otherwise taken as given, not normalised; a non-finite texture coordinate; texture coordinates on an emissive
+ *               (DiffuseLight) material: the light table evaluates emission at the barycentric U, V.  An emissive triangle with
+ *               normals only is accepted (Emitted reads U, V and P, never the normal); its light row is the flat triangle's. */
+RTOW_API rt_handle rt_triangle_attr(rt_scene *s, const double q[3], const double u[3], const double v[3], const double *normals,
+                                    const double *texcoords, rt_handle material);
+/* rt_triangle_mesh with attribute arrays: normals (3 doubles each, n_normals of them) indexed by normal_indices, texcoords
+ * (2 doubles each, n_texcoords of them) indexed by texcoord_indices, three indices a triangle like `indices`.  An index array that
+ * is NULL means "use indices"; an attribute array that is NULL means the mesh has none of that kind, and with both NULL the call is
+ * rt_triangle_mesh exactly.  Triangle k is rt_triangle_attr of its corners' entries.  Every index and every triangle's attributes
+ * are checked before the first triangle is added: on a refusal (rt_triangle_mesh's, rt_triangle_attr's, an attribute index outside
+ * its array) nothing is added. */
+RTOW_API rt_handle rt_triangle_mesh_attr(rt_scene *s, const double *vertices, int n_vertices, const int32_t *indices,
+                                         int n_triangles, const double *normals, int n_normals, const int32_t *normal_indices,
+                                         const double *texcoords, int n_texcoords, const int32_t *texcoord_indices,
+                                         rt_handle material, rt_handle *triangles_out);
+/* rt_obj_load that also reads `vn x y z`, `vt u v [w]` and the j (vt) and k (vn) of the face forms i/j, i/j/k, i//k.  A negative
+ * index is relative to the count of its own kind so far; polygons are fanned as by rt_obj_load.  normals / normal_indices come
+ * back only if every corner of every face names a normal, else NULL with n_normals = 0; the same, separately, for texcoords.
+ * The index arrays hold 3 * n_triangles 0-based entries.  RT_ERR_INVALID as for rt_obj_load (file and line in the message), and
+ * for a vn with fewer than three numbers, a vt with fewer than two, and a j or k that is 0 or out of range.  The arrays are the
+ * library's: release them with rt_obj_mesh_free, which also clears the struct. */
+typedef struct rt_obj_mesh {
+    double *vertices, *normals, *texcoords;
+    int32_t *indices, *normal_indices, *texcoord_indices;
+    int n_vertices, n_normals, n_texcoords, n_triangles;
+} rt_obj_mesh;
+RTOW_API int rt_obj_load_attr(const char *path, rt_obj_mesh *out);
+RTOW_API void rt_obj_mesh_free(rt_obj_mesh *mesh);
 RTOW_API rt_handle rt_translate(rt_scene *s, rt_handle object, double ox, double oy, double oz); /* Instance.h:31 */
 RTOW_API rt_handle rt_rotate_y(rt_scene *s, rt_handle object, double angle_degrees);          /* Instance.h:74 */
 RTOW_API rt_handle rt_make_box(rt_scene *s, const double a[3], const double b[3], rt_handle material); /* Instance.h:166 */
@@ -158,7 +209,8 @@ RTOW_API int rt_scene_set_camera(rt_scene *s, const double lookfrom[3], const do
 /* Built-in scenes: ids 0..9 = the reference's sceneId (R/kernel.cu:199-517); 10 = three-spheres (config C1);
  * 11 = scene 0 with every MovingSphere made static (config C2); 12 = scene 7's Cornell walls, light and camera with two triangle
  * meshes in place of the boxes (a 320-triangle Lambertian icosphere under Translate, a 20-triangle metal icosahedron under
- * RotateY + Translate; both rt_triangle_mesh).  world_kind 0 = BvhNode world (the
+ * RotateY + Translate; both rt_triangle_mesh); 13 = scene 12 with both meshes given corner normals unit(vertex position) in mesh
+ * space (rt_triangle_mesh_attr) and nothing else changed.  world_kind 0 = BvhNode world (the
  * reference's), 1 = HittableList world ("no BVH").  earth_rgb may be NULL (scenes 2 and 9 then show cyan). */
 RTOW_API int rt_scene_build_builtin(rt_scene *s, int scene_id, int world_kind, int image_width,
                                     int image_height, uint64_t seed, const unsigned char *earth_rgb,
@@ -177,7 +229,8 @@ typedef struct rt_scene_info {
     uint32_t table_bytes;         /* bytes of the geometry tables staged on chip */
     uint32_t image_bytes;
     uint32_t reserved[3];         /* [0] = n_triangles: the rows of n_quads that are triangles; [1] = n_lights: the rows of the
-                                     light table (rt_scene_dump_lights); [2] = 0 */
+                                     light table (rt_scene_dump_lights); [2] = n_attributed_triangles: the triangle rows that
+                                     carry corner normals or texture coordinates (rt_triangle_attr) */
 } rt_scene_info;
 RTOW_API int rt_scene_get_info(rt_scene *s, rt_scene_info *out);
 

@@ -102,6 +102,36 @@ public:
         }
         return {root};
     }
+    // rt_triangle_attr: corner normals (three) and / or corner texture coordinates (three (u, v) pairs); nullptr = none
+    Hittable Triangle(const Point3 &q, const Vector3 &u, const Vector3 &v, Material m, const Vector3 *normals, const double *texcoords = nullptr)
+    {
+        const double qq[3] = {q.x, q.y, q.z}, uu[3] = {u.x, u.y, u.z}, vv[3] = {v.x, v.y, v.z};
+        double nn[9] = {};
+        for (int c = 0; normals && c < 3; c++) nn[3 * c] = normals[c].x, nn[3 * c + 1] = normals[c].y, nn[3 * c + 2] = normals[c].z;
+        return {ok(rt_triangle_attr(s_, qq, uu, vv, normals ? nn : nullptr, texcoords, m.h))};
+    }
+    // rt_triangle_mesh_attr: `normals` indexed by `normal_indices`, `texcoords` (u, v pairs) by `texcoord_indices`; an empty attribute
+    // array = none of that kind, an empty index array = `indices`
+    Hittable TriangleMesh(const std::vector<Point3> &vertices, const std::vector<int32_t> &indices, Material m, const std::vector<Vector3> &normals,
+                          const std::vector<int32_t> &normal_indices = {}, const std::vector<double> &texcoords = {},
+                          const std::vector<int32_t> &texcoord_indices = {}, std::vector<Hittable> *triangles = nullptr)
+    {
+        if ((!normal_indices.empty() && normal_indices.size() != indices.size()) || (!texcoord_indices.empty() && texcoord_indices.size() != indices.size()))
+            throw Error("TriangleMesh: an attribute index array must be as long as indices");
+        std::vector<double> xyz, nrm;
+        for (const Point3 &p : vertices) xyz.insert(xyz.end(), {p.x, p.y, p.z});
+        for (const Vector3 &n : normals) nrm.insert(nrm.end(), {n.x, n.y, n.z});
+        std::vector<rt_handle> hs(indices.size() / 3);
+        const rt_handle root = ok(rt_triangle_mesh_attr(
+            s_, xyz.data(), (int)vertices.size(), indices.data(), (int)(indices.size() / 3), normals.empty() ? nullptr : nrm.data(), (int)normals.size(),
+            normal_indices.empty() ? nullptr : normal_indices.data(), texcoords.empty() ? nullptr : texcoords.data(), (int)(texcoords.size() / 2),
+            texcoord_indices.empty() ? nullptr : texcoord_indices.data(), m.h, hs.data()));
+        if (triangles) {
+            triangles->clear();
+            for (rt_handle h : hs) triangles->push_back({h});
+        }
+        return {root};
+    }
     Hittable Translate(Hittable o, const Vector3 &off) { return {ok(rt_translate(s_, o.h, off.x, off.y, off.z))}; }
     Hittable RotateY(Hittable o, double degrees) { return {ok(rt_rotate_y(s_, o.h, degrees))}; }
     Hittable MakeBox(const Point3 &a, const Point3 &b, Material m)

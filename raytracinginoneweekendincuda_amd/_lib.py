@@ -248,6 +248,13 @@ P = C.c_void_p
 D = C.c_double
 I = C.c_int
 D3 = C.POINTER(C.c_double)
+I32P = C.POINTER(C.c_int32)
+
+
+class ObjMesh(C.Structure):  # rt_obj_mesh
+    _fields_ = [("vertices", D3), ("normals", D3), ("texcoords", D3), ("indices", I32P), ("normal_indices", I32P), ("texcoord_indices", I32P),
+                ("n_vertices", I), ("n_normals", I), ("n_texcoords", I), ("n_triangles", I)]
+
 
 # name -> (restype, argtypes); exactly the symbols include/rtow.h declares
 SIGNATURES = {
@@ -286,6 +293,10 @@ SIGNATURES = {
     "rt_triangle_mesh": (H, [P, D3, I, C.POINTER(C.c_int32), I, H, C.POINTER(H)]),
     "rt_obj_load": (I, [C.c_char_p, C.POINTER(D3), C.POINTER(I), C.POINTER(C.POINTER(C.c_int32)), C.POINTER(I)]),
     "rt_mesh_free": (None, [D3, C.POINTER(C.c_int32)]),
+    "rt_triangle_attr": (H, [P, D3, D3, D3, D3, D3, H]),
+    "rt_triangle_mesh_attr": (H, [P, D3, I, I32P, I, D3, I, I32P, D3, I, I32P, H, C.POINTER(H)]),
+    "rt_obj_load_attr": (I, [C.c_char_p, C.POINTER(ObjMesh)]),
+    "rt_obj_mesh_free": (None, [C.POINTER(ObjMesh)]),
     "rt_translate": (H, [P, H, D, D, D]),
     "rt_rotate_y": (H, [P, H, D]),
     "rt_make_box": (H, [P, D3, D3, H]),

@@ -6,6 +6,7 @@ is R/Material.h:57/63, ``Scene.BvhNode(list)`` is ``new BvhNode(list, 0, n, ...)
 so on; ``Film.render`` is the RenderInit + Render launch pair (R/kernel.cu:675-691) and ``write_ppm`` the
 writer at R/kernel.cu:696-721.  Errors surface as RtowError carrying the library's message.
 """
+import collections
 import ctypes as C
 import numbers
 
@@ -174,20 +175,52 @@ class Scene:
     def Quad(self, q, u, v, material):
         return _h(lib().rt_quad(self._p, _v3(q), _v3(u), _v3(v), material))
 
-    def Triangle(self, q, u, v, material):
-        """Corners q, q + u, q + v; the quad's plane and the interior rule 0 <= alpha, 0 <= beta, alpha + beta <= 1 (rtow.h)."""
-        return _h(lib().rt_triangle(self._p, _v3(q), _v3(u), _v3(v), material))
+    def Triangle(self, q, u, v, material, normals=None, texcoords=None):
+        """Corners q, q + u, q + v; the quad's plane and the interior rule 0 <= alpha, 0 <= beta, alpha + beta <= 1 (rtow.h).
+        ``normals`` (3, 3): the corners' shading normals, ``texcoords`` (3, 2): their texture coordinates (rt_triangle_attr)."""
+        if normals is None and texcoords is None:
+            return _h(lib().rt_triangle(self._p, _v3(q), _v3(u), _v3(v), material))
+        n = None if normals is None else np.ascontiguousarray(normals, dtype=np.float64)
+        t = None if texcoords is None else np.ascontiguousarray(texcoords, dtype=np.float64)
+        if (n is not None and n.shape != (3, 3)) or (t is not None and t.shape != (3, 2)):
+            raise RtowError("Triangle: normals must be (3, 3) and texcoords (3, 2)")
+        return _h(lib().rt_triangle_attr(self._p, _v3(q), _v3(u), _v3(v), None if n is None else n.ctypes.data_as(_lib.D3),
+                                         None if t is None else t.ctypes.data_as(_lib.D3), material))
 
-    def TriangleMesh(self, vertices, faces, material, return_triangles=False):
+    def TriangleMesh(self, vertices, faces, material, return_triangles=False, normals=None, normal_faces=None, texcoords=None,
+                     texcoord_faces=None):
         """A BvhNode over the triangles of an indexed mesh: vertices (N, 3), faces (M, 3) of indices into them (rt_triangle_mesh).
-        With ``return_triangles`` also the M triangle handles in input order, for a list or a BvhNode shared with other objects."""
+        With ``return_triangles`` also the M triangle handles in input order, for a list or a BvhNode shared with other objects.
+        ``normals`` (K, 3) indexed by ``normal_faces`` (M, 3) and ``texcoords`` (L, 2) indexed by ``texcoord_faces`` (M, 3) give
+        the corners shading normals and texture coordinates (rt_triangle_mesh_attr); an index array left None is ``faces``."""
         v = np.ascontiguousarray(vertices, dtype=np.float64)
         f = np.ascontiguousarray(faces, dtype=np.int32)
         if v.ndim != 2 or v.shape[1] != 3 or f.ndim != 2 or f.shape[1] != 3:
             raise RtowError("TriangleMesh: vertices must be (N, 3) and faces (M, 3)")
         tris = (C.c_uint32 * max(1, f.shape[0]))()
-        root = _h(lib().rt_triangle_mesh(self._p, v.ctypes.data_as(_lib.D3), v.shape[0], f.ctypes.data_as(C.POINTER(C.c_int32)),
-                                         f.shape[0], material, tris))
+        i32p = C.POINTER(C.c_int32)
+        if normals is None and texcoords is None:
+            if normal_faces is not None or texcoord_faces is not None:
+                raise RtowError("TriangleMesh: normal_faces / texcoord_faces without normals / texcoords")
+            root = _h(lib().rt_triangle_mesh(self._p, v.ctypes.data_as(_lib.D3), v.shape[0], f.ctypes.data_as(i32p), f.shape[0], material, tris))
+            return (root, list(tris)[: f.shape[0]]) if return_triangles else root
+
+        def attribute(values, index, width, name):
+            if values is None:
+                if index is not None:
+                    raise RtowError(f"TriangleMesh: {name}_faces without {name}s")
+                return None, 0, None, ()
+            a = np.ascontiguousarray(values, dtype=np.float64)
+            i = None if index is None else np.ascontiguousarray(index, dtype=np.int32)
+            if a.ndim != 2 or a.shape[1] != width or (i is not None and i.shape != f.shape):
+                raise RtowError(f"TriangleMesh: {name}s must be (K, {width}) and {name}_faces shaped like faces")
+            return a.ctypes.data_as(_lib.D3), a.shape[0], None if i is None else i.ctypes.data_as(i32p), (a, i)
+
+        np_, nn, ni, keep_n = attribute(normals, normal_faces, 3, "normal")
+        tp, nt, ti, keep_t = attribute(texcoords, texcoord_faces, 2, "texcoord")
+        root = _h(lib().rt_triangle_mesh_attr(self._p, v.ctypes.data_as(_lib.D3), v.shape[0], f.ctypes.data_as(i32p), f.shape[0],
+                                              np_, nn, ni, tp, nt, ti, material, tris))
+        del keep_n, keep_t
         return (root, list(tris)[: f.shape[0]]) if return_triangles else root
 
     def Translate(self, obj, offset):
@@ -249,6 +282,7 @@ class Scene:
         info = {n: getattr(out, n) for n, _ in SceneInfo._fields_ if n != "reserved"}
         info["n_triangles"] = out.reserved[0]  # the rows of n_quads that are triangles
         info["n_lights"] = out.reserved[1]     # the rows of the light table (lights())
+        info["n_attributed_triangles"] = out.reserved[2]  # the triangle rows with corner normals or texture coordinates
         return info
 
     def lights(self):
@@ -1059,8 +1093,24 @@ def jpeg_decode(data):
     return _take_image(ptr, w, h)
 
 
-def load_obj(path):
-    """Wavefront OBJ, positions and faces only (rt_obj_load): vertices (N, 3) float64, faces (M, 3) int32, polygons fanned."""
+ObjMesh = collections.namedtuple("ObjMesh", "vertices faces normals normal_faces texcoords texcoord_faces")
+
+
+def load_obj(path, attributes=False):
+    """Wavefront OBJ, positions and faces only (rt_obj_load): vertices (N, 3) float64, faces (M, 3) int32, polygons fanned.
+    With ``attributes`` (rt_obj_load_attr) an ``ObjMesh`` tuple (vertices, faces, normals (K, 3), normal_faces (M, 3), texcoords
+    (L, 2), texcoord_faces (M, 3)) as ``Scene.TriangleMesh`` takes them; a kind that some face corner does not name is None, None."""
+    if attributes:
+        m = _lib.ObjMesh()
+        _check(lib().rt_obj_load_attr(str(path).encode(), C.byref(m)))
+        try:
+            def take(ptr, rows, width):
+                return np.ctypeslib.as_array(ptr, shape=(rows, width)).copy() if ptr else None
+            return ObjMesh(take(m.vertices, m.n_vertices, 3), take(m.indices, m.n_triangles, 3),
+                           take(m.normals, m.n_normals, 3), take(m.normal_indices, m.n_triangles, 3),
+                           take(m.texcoords, m.n_texcoords, 2), take(m.texcoord_indices, m.n_triangles, 3))
+        finally:
+            lib().rt_obj_mesh_free(C.byref(m))
     v, f = _lib.D3(), C.POINTER(C.c_int32)()
     nv, nf = C.c_int(), C.c_int()
     _check(lib().rt_obj_load(str(path).encode(), C.byref(v), C.byref(nv), C.byref(f), C.byref(nf)))

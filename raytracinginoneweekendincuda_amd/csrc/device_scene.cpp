@@ -327,6 +327,10 @@ int rt_scene_upload(rt_scene *scene, int device)
         }
         if (!tiled || at != trips) return fail(RT_ERR_STATE, "rt_scene_upload: the scan segments do not tile the sphere table");
     }
+    // The hit record reads quads[AAQuad::pad] for a marked triangle (render.hip vertex_attr): every mark must name an attribute row.
+    for (const AAQuad &a : f.quad_aa)
+        if (a.code == kQuadTriangle && a.pad && (a.pad < f.quads.size() || a.pad - f.quads.size() >= f.tri_attr.size()))
+            return fail(RT_ERR_STATE, "rt_scene_upload: a triangle's attribute row lies outside the table");
     DeviceTables *dt = new DeviceTables;
     dt->memory = DeviceArena(device);
     dt->generation = s.generation;
@@ -343,7 +347,14 @@ int rt_scene_upload(rt_scene *scene, int device)
     up(f.mspheres, d.mspheres);
     up(f.ms_planes, d.ms_planes);
     up(f.msphere_aux, d.msphere_aux);
-    up(f.quads, d.quads);
+    if (f.tri_attr.empty()) {
+        up(f.quads, d.quads);
+    } else {  // the attribute rows directly behind the quad rows, one allocation: quads[n_quads + k] is row k (flat_scene.h TriAttrRow)
+        std::vector<QuadGeom> rows(f.quads.size() + f.tri_attr.size());
+        std::memcpy(rows.data(), f.quads.data(), f.quads.size() * sizeof(QuadGeom));
+        std::memcpy(rows.data() + f.quads.size(), f.tri_attr.data(), f.tri_attr.size() * sizeof(TriAttrRow));
+        up(rows, d.quads);
+    }
     up(f.quad_aa, d.quad_aa);
     up(f.boxes, d.boxes);
     up(f.quad_mat, d.quad_mat);

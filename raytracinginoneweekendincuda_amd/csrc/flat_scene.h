@@ -75,6 +75,15 @@ struct AAQuad { double na, d, wa, qp, qq, ku, kv; uint32_t code, pad; };  // cod
 // and beta, hits that are REF_QUAD.  Only the interior rule differs (render.hip quad_test), and the row says so with a code
 // outside the axis-aligned range 1 .. 8; every other field of its AAQuad is zero (a triangle always takes the general test).
 constexpr uint32_t kQuadTriangle = 16u;
+// A triangle with corner normals and / or corner texture coordinates (rt_triangle_attr) is that row plus one of these: 128 bytes,
+// the stride of QuadGeom, uploaded directly BEHIND the quad rows in the same device allocation (device_scene.cpp), so that
+// AAQuad::pad -- 0: none, else n_quads + its index here -- addresses it as quads[pad].  The host's quads vector and n_quads do
+// not know of these rows; the search never reads them (the row's code stays kQuadTriangle).  Only the hit record does
+// (render.hip vertex_attr), behind SCENE_VERTEX_ATTR.  n: corner normals n0, n1, n2 (corners Q, Q+u, Q+v), t: (u, v) of the
+// three corners; `kinds` says which of the two the triangle was given.
+enum : uint32_t { ATTR_NORMALS = 1u, ATTR_TEXCOORDS = 2u };
+struct TriAttrRow { double n[9], t[6]; uint32_t kinds, pad; };
+static_assert(sizeof(TriAttrRow) == sizeof(QuadGeom), "attribute rows continue the quad table");
 // MakeBox (R/Instance.h:166-184): the six faces' planes and the two corners.  A face's interior test only decides
 // accept / reject, and alpha = (P[p] - Q[p]) / u[p] up to a few ulps; so a hit point P that is inside [mn, mx] by more
 // than 2^-30 of the coordinates' magnitude is accepted, one that is outside by as much is rejected, and only the
@@ -299,6 +308,7 @@ enum : uint32_t {
     SCENE_HAS_TREES = 32u,        // some leaf is a REF_TREE: rendered by the nested instantiations
     SCENE_WORLD_MSPHERES = 16u,   // WORLD_BVH of spheres / unit-time moving spheres only: ms_planes is filled
     SCENE_SEGMENTED = 64u,        // WORLD_BVH with composite leaves: fast_nodes / fast_order / seg_media describe the segmented walk
+    SCENE_VERTEX_ATTR = 128u,     // some triangle row carries corner normals or texture coordinates (TriAttrRow)
 };
 
 } // namespace rtow

@@ -2702,6 +2702,35 @@ DEV void face(Surface &s, const Ray &r, Vec outward)  // R/Hittable.h:26-30
     s.n = s.front ? outward : -outward;
 }
 
+// Corner normals and texture coordinates of a triangle (include/rtow.h rt_triangle_attr has the operations, flat_scene.h TriAttrRow
+// the row: quads[AAQuad::pad], behind the quad rows).  Scenes without such a triangle pay the scalar test of the scene flag per
+// planar hit; the search never comes here.  attr_row: the row's index in quads[], 0 for a row without attributes.
+DEV uint32_t attr_row(const DeviceScene &sc, uint32_t idx) { return (sc.flags & SCENE_VERTEX_ATTR) ? get_quad_aa(sc, idx).pad : 0u; }
+DEV void attr_uv(const RT_CONST double *a, double alpha, double beta, double gamma, double &u, double &v)
+{
+    u = (gamma * a[9] + alpha * a[11]) + beta * a[13];
+    v = (gamma * a[10] + alpha * a[12]) + beta * a[14];
+}
+// s.p: the hit point in the space the hit was found in; s.n, s.front: face()'s, of the geometric normal q.n
+DEV void vertex_attr(const DeviceScene &sc, uint32_t row, const QuadGeom &q, bool want_uv, Surface &s)
+{
+    const RT_CONST double *a = const_doubles(sc.quads + row);
+    const uint32_t kinds = ((const RT_CONST uint32_t *)a)[30];
+    const Vec ph = s.p - mk(q.qx, q.qy, q.qz), w = mk(q.wx, q.wy, q.wz);
+    const double alpha = dot(w, cross(ph, mk(q.vx, q.vy, q.vz)));
+    const double beta = dot(w, cross(mk(q.ux, q.uy, q.uz), ph));
+    const double gamma = (1.0 - alpha) - beta;
+    if (kinds & ATTR_NORMALS) {
+        const Vec ng = mk(q.nx, q.ny, q.nz);
+        const Vec m = (gamma * mk(a[0], a[1], a[2]) + alpha * mk(a[3], a[4], a[5])) + beta * mk(a[6], a[7], a[8]);
+        const double lsq = length_sq(m);
+        Vec ns = unit(m);
+        if (!(lsq > 0.0 && lsq < (double)INFINITY) || dot(ns, ng) <= 0.0) ns = ng;  // never under the geometric surface
+        s.n = s.front ? ns : -ns;
+    }
+    if (want_uv && (kinds & ATTR_TEXCOORDS)) attr_uv(a, alpha, beta, gamma, s.u, s.v);
+}
+
 template <class T>
 DEV Surface make_surface(const DeviceScene &sc, const Ray &r, const HitInfo &h)
 {
@@ -2746,6 +2775,11 @@ DEV Surface make_surface(const DeviceScene &sc, const Ray &r, const HitInfo &h)
                 s.u = dot(w, cross(ph, mk(q.vx, q.vy, q.vz)));
                 s.v = dot(w, cross(mk(q.ux, q.uy, q.uz), ph));
             }
+        }
+        if (const uint32_t row = attr_row(sc, idx)) {
+            bool want_uv = false;
+            if constexpr (T::RICH) want_uv = material_needs_uv(sc, s.mat);
+            vertex_attr(sc, row, q, want_uv, s);
         }
     } else {  // R/Sphere.h:40-46
         s.p = at(lr, h.t);
@@ -4525,6 +4559,10 @@ DEV void query_uv(const DeviceScene &sc, const Ray &r, const HitInfo &h, double 
         const Vec ph = p - mk(q.qx, q.qy, q.qz), w = mk(q.wx, q.wy, q.wz);
         u = dot(w, cross(ph, mk(q.vx, q.vy, q.vz)));
         v = dot(w, cross(mk(q.ux, q.uy, q.uz), ph));
+        if (const uint32_t row = attr_row(sc, idx)) {
+            const RT_CONST double *a = const_doubles(sc.quads + row);
+            if (((const RT_CONST uint32_t *)a)[30] & ATTR_TEXCOORDS) attr_uv(a, u, v, (1.0 - u) - v, u, v);
+        }
     } else if (tag == REF_SPHERE) {
         const SphereGeom g = sc.spheres[idx];
         sphere_uv(sc.sphere_aux[idx].inv_r * (p - mk(g.cx, g.cy, g.cz)), u, v);

@@ -599,8 +599,13 @@ struct Flattener {
         // RT_SCENE_PLAIN_QUADS (tests): every quad takes the general test, boxes stay lists of six quads
         // A triangle is the quad's row with the mark that selects its interior rule (flat_scene.h kQuadTriangle).
         AAQuad aa{};
-        if (h.kind == HKind::Triangle) aa.code = kQuadTriangle;
-        else if (!plain_quads) aa = axis_aligned(f.quads.back());
+        if (h.kind == HKind::Triangle) {
+            aa.code = kQuadTriangle;
+            if (h.attr) {  // 1 + the attribute row for now; flatten_scene adds the final number of quad rows (flat_scene.h TriAttrRow)
+                f.tri_attr.push_back(s.tri_attr[h.attr - 1]);
+                aa.pad = (uint32_t)f.tri_attr.size();
+            }
+        } else if (!plain_quads) aa = axis_aligned(f.quads.back());
         f.quad_aa.push_back(aa);
         f.quad_mat.push_back(h.material - 1);
         return make_ref(REF_QUAD, (uint32_t)f.quads.size() - 1);
@@ -1696,6 +1701,11 @@ int flatten_scene(SceneImpl &s)
             f.flags |= SCENE_WORLD_MSPHERES;
         }
     }
+    if (!f.tri_attr.empty()) {  // the attribute rows stand behind the quad rows on the device: AAQuad::pad = the row's index there
+        for (AAQuad &a : f.quad_aa)
+            if (a.code == kQuadTriangle && a.pad) a.pad += (uint32_t)f.quads.size() - 1u;
+        f.flags |= SCENE_VERTEX_ATTR;
+    }
     s.committed = true;
     return RT_OK;
 }
@@ -1993,26 +2003,118 @@ rt_handle rt_triangle_mesh(rt_scene *s, const double *vertices, int n_vertices, 
     return rt_bvh_node(s, tris.data(), n_triangles);
 }
 
-// Wavefront OBJ, positions and faces only.
-int rt_obj_load(const char *path, double **vertices, int *n_vertices, int32_t **indices, int *n_triangles)
+// Corner attributes (include/rtow.h rt_triangle_attr): what a triangle may be given, checked before anything is added.
+static bool attr_acceptable(SceneImpl *sc, const double *normals, const double *texcoords, rt_handle material, const char *who)
 {
-    if (!path || !vertices || !n_vertices || !indices || !n_triangles) return fail(RT_ERR_INVALID, "rt_obj_load: null argument");
-    *vertices = nullptr;
-    *indices = nullptr;
-    *n_vertices = *n_triangles = 0;
+    if (normals)
+        for (int c = 0; c < 3; c++) {
+            const double *n = normals + 3 * c;
+            if (!std::isfinite(n[0]) || !std::isfinite(n[1]) || !std::isfinite(n[2]) || (n[0] == 0.0 && n[1] == 0.0 && n[2] == 0.0)) {
+                set_error(std::string(who) + ": a corner normal is not finite or is all zero");
+                return false;
+            }
+        }
+    if (texcoords) {
+        for (int c = 0; c < 6; c++)
+            if (!std::isfinite(texcoords[c])) {
+                set_error(std::string(who) + ": a texture coordinate is not finite");
+                return false;
+            }
+        if (sc->materials[material - 1].kind == MAT_DIFFUSE_LIGHT) {
+            set_error(std::string(who) + ": an emissive triangle takes no texture coordinates (the light table evaluates emission at the barycentric U, V)");
+            return false;
+        }
+    }
+    return true;
+}
+rt_handle rt_triangle_attr(rt_scene *s, const double q[3], const double u[3], const double v[3], const double *normals,
+                           const double *texcoords, rt_handle material)
+{
+    if (!normals && !texcoords) return rt_triangle(s, q, u, v, material);
+    if (!valid_mat(S(s), material) || !q || !u || !v) {
+        set_error("rt_triangle_attr: invalid material handle or null vector");
+        return 0;
+    }
+    if (!attr_acceptable(S(s), normals, texcoords, material, "rt_triangle_attr")) return 0;
+    const rt_handle t = rt_triangle(s, q, u, v, material);
+    if (!t) return 0;
+    TriAttrRow row{};
+    if (normals) std::memcpy(row.n, normals, sizeof row.n);
+    if (texcoords) std::memcpy(row.t, texcoords, sizeof row.t);
+    row.kinds = (normals ? ATTR_NORMALS : 0u) | (texcoords ? ATTR_TEXCOORDS : 0u);
+    S(s)->tri_attr.push_back(row);
+    S(s)->hittables[t - 1].attr = (uint32_t)S(s)->tri_attr.size();
+    return t;
+}
+rt_handle rt_triangle_mesh_attr(rt_scene *s, const double *vertices, int n_vertices, const int32_t *indices, int n_triangles,
+                                const double *normals, int n_normals, const int32_t *normal_indices, const double *texcoords,
+                                int n_texcoords, const int32_t *texcoord_indices, rt_handle material, rt_handle *triangles_out)
+{
+    if (!normals && !texcoords) return rt_triangle_mesh(s, vertices, n_vertices, indices, n_triangles, material, triangles_out);
+    if (!valid_mat(S(s), material) || !vertices || !indices || n_vertices < 3 || n_triangles < 1) {
+        set_error("rt_triangle_mesh_attr: invalid material handle, null array, fewer than 3 vertices or no triangle");
+        return 0;
+    }
+    if ((normals && n_normals < 1) || (texcoords && n_texcoords < 1)) {
+        set_error("rt_triangle_mesh_attr: an attribute array without entries");
+        return 0;
+    }
+    const int32_t *ni = normal_indices ? normal_indices : indices, *ti = texcoord_indices ? texcoord_indices : indices;
+    const size_t corners = 3 * (size_t)n_triangles;
+    auto in_range = [&](const int32_t *idx, int n, const char *what) {
+        for (size_t k = 0; k < corners; k++)
+            if (idx[k] < 0 || idx[k] >= n) {
+                set_error(std::string("rt_triangle_mesh_attr: ") + what + " " + std::to_string(idx[k]) + " outside [0, " + std::to_string(n) + ")");
+                return false;
+            }
+        return true;
+    };
+    if (!in_range(indices, n_vertices, "index") || (normals && !in_range(ni, n_normals, "normal index")) ||
+        (texcoords && !in_range(ti, n_texcoords, "texture coordinate index")))
+        return 0;
+    std::vector<double> nrm(normals ? 3 * corners : 0), tex(texcoords ? 2 * corners : 0);  // per corner, gathered
+    for (size_t k = 0; k < corners; k++) {
+        if (normals) std::memcpy(&nrm[3 * k], normals + 3 * (size_t)ni[k], 3 * sizeof(double));
+        if (texcoords) std::memcpy(&tex[2 * k], texcoords + 2 * (size_t)ti[k], 2 * sizeof(double));
+    }
+    for (size_t k = 0; k < (size_t)n_triangles; k++)  // every triangle's attributes before the first one is added
+        if (!attr_acceptable(S(s), normals ? &nrm[9 * k] : nullptr, texcoords ? &tex[6 * k] : nullptr, material, "rt_triangle_mesh_attr")) return 0;
+    std::vector<rt_handle> tris((size_t)n_triangles);
+    for (size_t k = 0; k < tris.size(); k++) {
+        const double *a = vertices + 3 * (size_t)indices[3 * k], *b = vertices + 3 * (size_t)indices[3 * k + 1],
+                     *c = vertices + 3 * (size_t)indices[3 * k + 2];
+        const double u[3] = {b[0] - a[0], b[1] - a[1], b[2] - a[2]}, v[3] = {c[0] - a[0], c[1] - a[1], c[2] - a[2]};
+        tris[k] = rt_triangle_attr(s, a, u, v, normals ? &nrm[9 * k] : nullptr, texcoords ? &tex[6 * k] : nullptr, material);
+        if (!tris[k]) return 0;
+    }
+    if (triangles_out) std::memcpy(triangles_out, tris.data(), sizeof(rt_handle) * tris.size());
+    return rt_bvh_node(s, tris.data(), n_triangles);
+}
+
+// Wavefront OBJ: positions and faces, and for rt_obj_load_attr (`attr`) the vn / vt statements and the j, k of a face corner.
+// fs, fn, ft: three corner indices a triangle, 0-based; a positive one may name an entry that follows (checked at the end).
+// fn / ft come back empty unless every corner of every face named a normal / a texture coordinate.
+namespace {
+struct ObjText {
+    std::vector<double> vs, vn, vt;
+    std::vector<long long> fs, fn, ft;
+};
+int obj_parse(const char *who, const char *path, bool attr, ObjText &o)
+{
     FILE *fp = std::fopen(path, "rb");
-    if (!fp) return fail(RT_ERR_INVALID, std::string("rt_obj_load: cannot open ") + path);
+    if (!fp) return fail(RT_ERR_INVALID, std::string(who) + ": cannot open " + path);
     std::string text;
     char buf[1 << 16];
     for (size_t got; (got = std::fread(buf, 1, sizeof buf, fp)) > 0;) text.append(buf, got);
     const bool read_error = std::ferror(fp) != 0;
     std::fclose(fp);
-    if (read_error) return fail(RT_ERR_INVALID, std::string("rt_obj_load: cannot read ") + path);
+    if (read_error) return fail(RT_ERR_INVALID, std::string(who) + ": cannot read " + path);
 
-    std::vector<double> vs;
-    std::vector<long long> fs;  // corner indices, 0-based; a positive one may name a vertex that follows (checked at the end)
+    std::vector<double> &vs = o.vs;
+    std::vector<long long> &fs = o.fs;
+    bool all_n = attr, all_t = attr;  // so far every corner named a normal / a texture coordinate
     size_t line_no = 0;
-    auto bad = [&](const char *what) { return fail(RT_ERR_INVALID, std::string("rt_obj_load: ") + path + ":" + std::to_string(line_no) + ": " + what); };
+    auto bad = [&](const char *what) { return fail(RT_ERR_INVALID, std::string(who) + ": " + path + ":" + std::to_string(line_no) + ": " + what); };
     for (size_t pos = 0; pos < text.size();) {
         size_t eol = text.find('\n', pos);
         if (eol == std::string::npos) eol = text.size();
@@ -2024,22 +2126,26 @@ int rt_obj_load(const char *path, double **vertices, int *n_vertices, int32_t **
         const char *c = line.c_str();
         while (*c == ' ' || *c == '\t') c++;
         const bool is_v = c[0] == 'v' && (c[1] == ' ' || c[1] == '\t'), is_f = c[0] == 'f' && (c[1] == ' ' || c[1] == '\t');
-        if (!is_v && !is_f) continue;  // vn, vt, g, o, s, usemtl, mtllib, ...: skipped
-        c += 2;
-        if (is_v) {
+        const bool is_vn = attr && c[0] == 'v' && c[1] == 'n' && (c[2] == ' ' || c[2] == '\t');
+        const bool is_vt = attr && c[0] == 'v' && c[1] == 't' && (c[2] == ' ' || c[2] == '\t');
+        if (!is_v && !is_f && !is_vn && !is_vt) continue;  // g, o, s, usemtl, mtllib, ... (and vn, vt for rt_obj_load): skipped
+        c += is_v || is_f ? 2 : 3;
+        if (!is_f) {
             const char *line_end = line.c_str() + line.size();
-            for (int k = 0; k < 3; k++) {  // std::from_chars: the "C" number format whatever locale the host program has set
+            std::vector<double> &into = is_v ? vs : (is_vn ? o.vn : o.vt);
+            for (int k = 0; k < (is_vt ? 2 : 3); k++) {  // std::from_chars: the "C" number format whatever locale the host program has set
                 while (*c == ' ' || *c == '\t') c++;
                 if (*c == '+') c++;
                 double x = 0.0;
                 const auto parsed = std::from_chars(c, line_end, x);
-                if (parsed.ec != std::errc() || parsed.ptr == c) return bad("a vertex needs three numbers");
-                vs.push_back(x);
+                if (parsed.ec != std::errc() || parsed.ptr == c)
+                    return bad(is_v ? "a vertex needs three numbers" : (is_vn ? "a vn needs three numbers" : "a vt needs two numbers"));
+                into.push_back(x);
                 c = parsed.ptr;
             }
-            continue;
+            continue;  // (a vt's third number, a vertex's w or colour: not read)
         }
-        std::vector<long long> corner;
+        std::vector<long long> corner, corner_n, corner_t;
         for (;;) {
             while (*c == ' ' || *c == '\t' || *c == '\r') c++;
             if (!*c) break;
@@ -2050,34 +2156,125 @@ int rt_obj_load(const char *path, double **vertices, int *n_vertices, int32_t **
             if (i < -n_so_far) return bad("relative vertex index out of range");
             corner.push_back(i > 0 ? i - 1 : n_so_far + i);
             c = end;
-            while (*c && *c != ' ' && *c != '\t' && *c != '\r') c++;  // "/j", "/j/k", "//k": texture and normal indices are not read
+            if (attr) {  // "/j", "/j/k", "//k": each relative to the count of its own kind so far
+                bool has_t = false, has_n = false;
+                if (*c == '/') {
+                    c++;
+                    if (*c != '/' && *c && *c != ' ' && *c != '\t' && *c != '\r') {
+                        const long long j = std::strtoll(c, &end, 10);
+                        const long long nt = (long long)(o.vt.size() / 2);
+                        if (end == c || j == 0) return bad("a face corner's texture coordinate index must be a non-zero number");
+                        if (j < -nt) return bad("relative texture coordinate index out of range");
+                        corner_t.push_back(j > 0 ? j - 1 : nt + j);
+                        has_t = true;
+                        c = end;
+                    }
+                    if (*c == '/') {
+                        c++;
+                        if (*c && *c != ' ' && *c != '\t' && *c != '\r') {
+                            const long long k = std::strtoll(c, &end, 10);
+                            const long long nn = (long long)(o.vn.size() / 3);
+                            if (end == c || k == 0) return bad("a face corner's normal index must be a non-zero number");
+                            if (k < -nn) return bad("relative normal index out of range");
+                            corner_n.push_back(k > 0 ? k - 1 : nn + k);
+                            has_n = true;
+                            c = end;
+                        }
+                    }
+                }
+                all_t = all_t && has_t;
+                all_n = all_n && has_n;
+            }
+            while (*c && *c != ' ' && *c != '\t' && *c != '\r') c++;  // rt_obj_load: "/j", "/j/k", "//k" are not read
         }
         if (corner.size() < 3) return bad("a face needs three corners");
         for (size_t k = 1; k + 1 < corner.size(); k++) {  // a polygon is fanned from its first corner
             fs.push_back(corner[0]);
             fs.push_back(corner[k]);
             fs.push_back(corner[k + 1]);
+            if (all_n) o.fn.insert(o.fn.end(), {corner_n[0], corner_n[k], corner_n[k + 1]});
+            if (all_t) o.ft.insert(o.ft.end(), {corner_t[0], corner_t[k], corner_t[k + 1]});
         }
     }
-    if (fs.empty()) return fail(RT_ERR_INVALID, std::string("rt_obj_load: ") + path + " has no face");
+    if (fs.empty()) return fail(RT_ERR_INVALID, std::string(who) + ": " + path + " has no face");
     const long long nv = (long long)(vs.size() / 3);
     for (long long i : fs)
-        if (i < 0 || i >= nv) return fail(RT_ERR_INVALID, std::string("rt_obj_load: ") + path + ": vertex index out of range");
-    if (fs.size() / 3 > (size_t)INT32_MAX || nv > (long long)INT32_MAX) return fail(RT_ERR_INVALID, "rt_obj_load: mesh too large");
-    double *vout = (double *)std::malloc(vs.size() * sizeof(double));
-    int32_t *iout = (int32_t *)std::malloc(fs.size() * sizeof(int32_t));
-    if (!vout || !iout) {
+        if (i < 0 || i >= nv) return fail(RT_ERR_INVALID, std::string(who) + ": " + path + ": vertex index out of range");
+    if (!all_n) o.fn.clear();
+    if (!all_t) o.ft.clear();
+    for (long long i : o.fn)
+        if (i < 0 || i >= (long long)(o.vn.size() / 3)) return fail(RT_ERR_INVALID, std::string(who) + ": " + path + ": normal index out of range");
+    for (long long i : o.ft)
+        if (i < 0 || i >= (long long)(o.vt.size() / 2)) return fail(RT_ERR_INVALID, std::string(who) + ": " + path + ": texture coordinate index out of range");
+    if (fs.size() / 3 > (size_t)INT32_MAX || nv > (long long)INT32_MAX || o.vn.size() / 3 > (size_t)INT32_MAX || o.vt.size() / 2 > (size_t)INT32_MAX)
+        return fail(RT_ERR_INVALID, std::string(who) + ": mesh too large");
+    return RT_OK;
+}
+// malloc'ed copies for the caller (rt_mesh_free, rt_obj_mesh_free); false: out of memory
+bool obj_copy_numbers(const std::vector<double> &from, double *&to)
+{
+    to = (double *)std::malloc(std::max<size_t>(from.size(), 1) * sizeof(double));
+    if (to) std::memcpy(to, from.data(), from.size() * sizeof(double));
+    return to != nullptr;
+}
+bool obj_copy_indices(const std::vector<long long> &from, int32_t *&to)
+{
+    to = (int32_t *)std::malloc(std::max<size_t>(from.size(), 1) * sizeof(int32_t));
+    for (size_t k = 0; to && k < from.size(); k++) to[k] = (int32_t)from[k];
+    return to != nullptr;
+}
+}  // namespace
+
+int rt_obj_load(const char *path, double **vertices, int *n_vertices, int32_t **indices, int *n_triangles)
+{
+    if (!path || !vertices || !n_vertices || !indices || !n_triangles) return fail(RT_ERR_INVALID, "rt_obj_load: null argument");
+    *vertices = nullptr;
+    *indices = nullptr;
+    *n_vertices = *n_triangles = 0;
+    ObjText o;
+    if (int rc = obj_parse("rt_obj_load", path, false, o)) return rc;
+    double *vout = nullptr;
+    int32_t *iout = nullptr;
+    if (!obj_copy_numbers(o.vs, vout) || !obj_copy_indices(o.fs, iout)) {
         std::free(vout);
         std::free(iout);
         return fail(RT_ERR_INVALID, "rt_obj_load: out of memory");
     }
-    std::memcpy(vout, vs.data(), vs.size() * sizeof(double));
-    for (size_t k = 0; k < fs.size(); k++) iout[k] = (int32_t)fs[k];
     *vertices = vout;
     *indices = iout;
-    *n_vertices = (int)nv;
-    *n_triangles = (int)(fs.size() / 3);
+    *n_vertices = (int)(o.vs.size() / 3);
+    *n_triangles = (int)(o.fs.size() / 3);
     return RT_OK;
+}
+int rt_obj_load_attr(const char *path, rt_obj_mesh *out)
+{
+    if (!path || !out) return fail(RT_ERR_INVALID, "rt_obj_load_attr: null argument");
+    std::memset(out, 0, sizeof *out);
+    ObjText o;
+    if (int rc = obj_parse("rt_obj_load_attr", path, true, o)) return rc;
+    bool ok = obj_copy_numbers(o.vs, out->vertices) && obj_copy_indices(o.fs, out->indices);
+    if (ok && !o.fn.empty()) ok = obj_copy_numbers(o.vn, out->normals) && obj_copy_indices(o.fn, out->normal_indices);
+    if (ok && !o.ft.empty()) ok = obj_copy_numbers(o.vt, out->texcoords) && obj_copy_indices(o.ft, out->texcoord_indices);
+    if (!ok) {
+        rt_obj_mesh_free(out);
+        return fail(RT_ERR_INVALID, "rt_obj_load_attr: out of memory");
+    }
+    out->n_vertices = (int)(o.vs.size() / 3);
+    out->n_triangles = (int)(o.fs.size() / 3);
+    out->n_normals = o.fn.empty() ? 0 : (int)(o.vn.size() / 3);
+    out->n_texcoords = o.ft.empty() ? 0 : (int)(o.vt.size() / 2);
+    return RT_OK;
+}
+void rt_obj_mesh_free(rt_obj_mesh *m)
+{
+    if (!m) return;
+    std::free(m->vertices);
+    std::free(m->normals);
+    std::free(m->texcoords);
+    std::free(m->indices);
+    std::free(m->normal_indices);
+    std::free(m->texcoord_indices);
+    std::memset(m, 0, sizeof *m);
 }
 void rt_mesh_free(double *vertices, int32_t *indices)
 {
@@ -2315,6 +2512,7 @@ int rt_scene_get_info(rt_scene *s, rt_scene_info *out)
     out->image_bytes = (uint32_t)f.image_bytes.size();
     for (const AAQuad &a : f.quad_aa) out->reserved[0] += a.code == kQuadTriangle;  // n_triangles (counted in n_quads too)
     out->reserved[1] = (uint32_t)f.lights.size();  // n_lights
+    out->reserved[2] = (uint32_t)f.tri_attr.size();  // triangle rows with corner attributes
     return RT_OK;
 }
 

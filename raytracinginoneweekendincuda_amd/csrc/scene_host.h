@@ -29,6 +29,7 @@ struct HostHittable {
     double t0 = 0, t1 = 0, radius = 0;
     D3 q{}, u{}, v{}, w{}, normal{};   // quad, triangle
     double plane_d = 0;
+    uint32_t attr = 0;                 // triangle with corner normals / texture coordinates: 1 + its row of SceneImpl::tri_attr
     uint32_t child = 0;                // instance / medium: wrapped hittable handle
     D3 offset{};
     double sin_t = 0, cos_t = 0;
@@ -75,6 +76,7 @@ struct FlatScene {
     std::vector<SphereAux> msphere_aux;
     std::vector<QuadGeom> quads;
     std::vector<AAQuad> quad_aa;
+    std::vector<TriAttrRow> tri_attr;    // SCENE_VERTEX_ATTR: row k is quads[quads.size() + k] on the device (flat_scene.h TriAttrRow)
     std::vector<BoxRec> boxes;
     std::vector<uint32_t> quad_mat;
     std::vector<ObjectRec> objects;
@@ -122,6 +124,7 @@ struct SceneImpl {
     std::vector<HostHittable> hittables;  // handle = index + 1
     std::vector<HostMaterial> materials;
     std::vector<HostTexture> textures;
+    std::vector<TriAttrRow> tri_attr;     // HostHittable::attr
     std::vector<ImageRec> images;
     std::vector<unsigned char> image_bytes;
     std::vector<PerlinRec> perlin;

@@ -274,7 +274,8 @@ extern "C" int rt_scene_build_builtin(rt_scene *s, int scene_id, int world_kind,
             view.vfov = 90.0;
             break;
         }
-        case 12: {  // scene 7's walls, light and camera; two triangle meshes stand where its boxes stand
+        case 12:    // scene 7's walls, light and camera; two triangle meshes stand where its boxes stand
+        case 13: {  // scene 12 with corner normals unit(vertex position) in mesh space on both meshes: smooth shading
             CornellMaterials m = cornell_materials(w, 15.0);
             list.push_back(w.Quad(Vector3(555, 0, 0), Vector3(0, 555, 0), Vector3(0, 0, 555), m.green));
             list.push_back(w.Quad(Vector3(0, 0, 0), Vector3(0, 555, 0), Vector3(0, 0, 555), m.red));
@@ -284,16 +285,25 @@ extern "C" int rt_scene_build_builtin(rt_scene *s, int scene_id, int world_kind,
             list.push_back(w.Quad(Vector3(0, 0, 555), Vector3(555, 0, 0), Vector3(0, 555, 0), m.white));
             std::vector<Point3> vertices;
             std::vector<int32_t> indices;
+            auto mesh = [&](Material material) {
+                if (scene_id == 12) return w.TriangleMesh(vertices, indices, material);
+                std::vector<Vector3> normals;
+                for (const Point3 &p : vertices) {
+                    const double k = 1.0 / std::sqrt(p.x * p.x + p.y * p.y + p.z * p.z);
+                    normals.push_back(Vector3(k * p.x, k * p.y, k * p.z));
+                }
+                return w.TriangleMesh(vertices, indices, material, normals);
+            };
             icosphere(2, 100.0, vertices, indices);  // 320 triangles
-            list.push_back(w.Translate(w.TriangleMesh(vertices, indices, m.white), Vector3(347.5, 100.0, 377.5)));
+            list.push_back(w.Translate(mesh(m.white), Vector3(347.5, 100.0, 377.5)));
             icosphere(0, 90.0, vertices, indices);   // the icosahedron itself
-            Hittable solid = w.TriangleMesh(vertices, indices, w.Metal(Color(0.8, 0.85, 0.88), 0.0));
+            Hittable solid = mesh(w.Metal(Color(0.8, 0.85, 0.88), 0.0));
             list.push_back(w.Translate(w.RotateY(solid, -18.0), Vector3(212.5, 90.0, 147.5)));
             cornell_view(view);
             break;
         }
         default:
-            return rtow::fail(RT_ERR_INVALID, "rt_scene_build_builtin: scene_id must be 0..12");
+            return rtow::fail(RT_ERR_INVALID, "rt_scene_build_builtin: scene_id must be 0..13");
         }
 
         // R/kernel.cu:523-528: BvhNode(list, 0, i, ...) as world; "no BVH" = HittableList(list, i)
