@@ -215,6 +215,43 @@ def test_tile_ranking_does_not_change_the_image(scene_id, earth):
     assert st_ranked.rays == st_plain.rays          # the rehearsal's rays are not counted
 
 
+# (width, height, (rank, world_size) of 8-row stripes): more tiles than the 1024 threads of the one workgroup that ranks them
+MANY_TILES = [
+    (264, 256, (0, 1)),      # 1056 tiles: a second trip for 32 threads only
+    (520, 256, (0, 1)),      # 2080 tiles: a third trip
+    (250, 332, (0, 1)),      # neither side a multiple of 8
+    (256, 816, (1, 3)),      # rank 1 of 3 owns 34 stripes of 8 rows
+]
+
+
+@pytest.mark.parametrize("w,h,share", MANY_TILES, ids=lambda v: "x".join(str(k) for k in v) if isinstance(v, tuple) else str(v))
+def test_tile_ranking_of_more_tiles_than_threads_does_not_change_the_image(w, h, share):
+    """test_tile_ranking_does_not_change_the_image beyond its 1024 tiles, where the threads of tile_order_kernel take a second and a
+    third trip through their loops and the last trip is partial: the ranked frame of scene 0 (a BVH world, strict build) equals
+    the row-major one (RT_FLAG_ROW_MAJOR_TILES) bit for bit with equal ray counts, and the plan of the launch says it ranks.
+    What this shows: the order the kernel leaves is a permutation of the tiles -- the pixel queue follows it, so a tile left out
+    or named twice changes the frame.  What it does not show: that the order is the ranked one (that changes the time alone), nor
+    whether the kernel took its ranked branch or kept the row-major order for a flat frame; the library has no call that downloads
+    the order.  The tile count is the library's own film geometry (the tile count rt_scene_dump_primary_lists returns).
+    32 samples a pixel: frames of fewer are not ranked (csrc/launch_plan.cpp plan_frame), and the plan is asserted to rank."""
+    rank, world_size = share
+    spp = 32
+    s = rt.builtin_scene(0, 0, w, h)
+    tiles = rt.api.lib().rt_scene_dump_primary_lists(s._p, w, h, 8, rank, world_size, 0, None)
+    assert tiles > 1024 and tiles % 1024 != 0, "more than one trip, and a partial last one"
+    ranked, plain = (rt.Film(w, h, stripe_rows=8, rank=rank, world_size=world_size) for _ in range(2))
+    assert s.plan_launch(ranked.params(spp, variant=0))["rank_tiles"] == 1
+    assert s.plan_launch(plain.params(spp, variant=0, flags=rt.FLAG_ROW_MAJOR_TILES))["rank_tiles"] == 0
+    st_ranked = ranked.render(s, spp, variant=0)
+    st_plain = plain.render(s, spp, variant=0, flags=rt.FLAG_ROW_MAJOR_TILES)
+    rows = rt.stripe_rows(h, 8, rank, world_size)
+    assert len(rows) * w == st_ranked.pixels == st_plain.pixels
+    got, want = ranked.download()[rows], plain.download()[rows]
+    assert np.array_equal(got.view(np.uint64), want.view(np.uint64)), f"{np.sum((got != want).any(axis=-1))} pixels of {tiles} tiles differ"
+    assert st_ranked.rays == st_plain.rays and st_ranked.samples == st_plain.samples == len(rows) * w * spp
+    assert want.any()
+
+
 def _quad_zoo(world_kind, plain):
     """Quads in every axis pairing and winding, a slanted quad, boxes plain / instanced / paper-thin / far from the origin."""
     if True:

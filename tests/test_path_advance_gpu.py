@@ -3,7 +3,8 @@ compaction done on the device.  The keystone is the path step, which existing te
 the render: one advance is a path step, a mask and a fold restated in numpy, bit for bit and in order; fifty advances enqueued
 without a wait in between are rt_scene_radiance bit for bit in the strict build.  Beside it the batch edges with guard rows, the
 device count word, `alive`, carried throughputs and ids, the survivors' hit records, the fast build, repeatability and statistics.
-Every ray set is at most 32 x 24 rays: three workgroups."""
+Every ray set is at most 32 x 24 rays: three workgroups.
+tests/test_path_advance_scale_gpu.py has the sizes beyond: up to 3137 workgroups, every level of the compaction's scan."""
 import ctypes as C
 import functools
 
