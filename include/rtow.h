@@ -188,6 +188,48 @@ RTOW_API int rt_obj_load_attr(const char *path, rt_obj_mesh *out);
 RTOW_API void rt_obj_mesh_free(rt_obj_mesh *mesh);
 RTOW_API rt_handle rt_translate(rt_scene *s, rt_handle object, double ox, double oy, double oz); /* Instance.h:31 */
 RTOW_API rt_handle rt_rotate_y(rt_scene *s, rt_handle object, double angle_degrees);          /* Instance.h:74 */
+/* A general affine instance: the child placed by x_world = L x_obj + t.  m is row-major 3x4: L[r][c] = m[4 r + c], t[r] = m[4 r + 3].
+ * The reference has no such class; it stands wherever Translate / RotateY may stand -- in chains of any length and order, above
+ * lists, BvhNodes, meshes, boxes, media, and in the general object tree -- and is stated here operation by operation, each operation
+ * one IEEE double operation, nothing contracted in the strict build:
+ *   creation    Li, the inverse of L, is computed once, in fp64, from cofactors over the determinant:
+ *                 c00 = (L11*L22) - (L12*L21)   c01 = (L12*L20) - (L10*L22)   c02 = (L10*L21) - (L11*L20)
+ *                 c10 = (L02*L21) - (L01*L22)   c11 = (L00*L22) - (L02*L20)   c12 = (L01*L20) - (L00*L21)
+ *                 c20 = (L01*L12) - (L02*L11)   c21 = (L02*L10) - (L00*L12)   c22 = (L00*L11) - (L01*L10)
+ *                 det = ((L00*c00) + (L01*c01)) + (L02*c02)
+ *                 Li[r][c] = c[c][r] / det      (the transposed cofactor over det, one division an entry)
+ *               L, t and Li are stored, uploaded and used exactly as rt_transform_get returns them.
+ *   refused     (returns 0, nothing added, rt_last_error says why) an invalid handle or NULL m; a non-finite entry of m; a det that
+ *               is zero or non-finite; a non-finite entry of Li; a child subtree that holds an emissive (DiffuseLight) Sphere or
+ *               MovingSphere outside any ConstantMedium boundary -- under a general map such a lamp is an ellipsoid, which the light
+ *               table cannot hold.  Mirrors (det < 0) are accepted.
+ *   Hit         the local ray: p = o - t, then per row r
+ *                 o'[r] = ((Li[r][0]*p.x) + (Li[r][1]*p.y)) + (Li[r][2]*p.z)      d'[r] the same from d
+ *               The time is unchanged and d' is NOT normalised: the child's Hit is called with the caller's interval and its t is
+ *               the world's t, as under RotateY.
+ *   HitRecord   P[r] = (((L[r][0]*P'.x) + (L[r][1]*P'.y)) + (L[r][2]*P'.z)) + t[r]
+ *               n[c] = ((Li[0][c]*n'.x) + (Li[1][c]*n'.y)) + (Li[2][c]*n'.z)
+ *               Normal = (1 / sqrt(length_sq(n))) * n,  length_sq(n) = n.x*n.x + n.y*n.y + n.z*n.z
+ *               renormalised at every Transform step of a chain; Translate and RotateY steps stay exactly as they are.  front_face,
+ *               U, V, the material and the leaf are the child's.  A shading normal from corner attributes (rt_triangle_attr) goes
+ *               the same way as the flat normal.
+ *   box         the eight corners of the child's box (x outermost, then y, then z; lo before hi) go forward as P does; per axis
+ *               their fmin / fmax, then the corner constructor with its padding (AABB.h:34-40), as rt_rotate_y does.
+ *   media       a ConstantMedium UNDER a Transform measures its path in object space (length(d') of the local ray): a fog scaled by
+ *               2 is as opaque across its width as before.  A ConstantMedium whose BOUNDARY is a Transform measures in the space the
+ *               medium itself is called in.
+ *   lights      an emissive quad or triangle under a Transform is listed in the light table: see rt_scene_dump_lights. */
+RTOW_API rt_handle rt_transform(rt_scene *s, rt_handle object, const double m[12]);
+/* The three convenience constructors fill the twelve numbers and call rt_transform.  Angles are converted as rt_rotate_y converts
+ * them: radians = angle_degrees * 3.1415926535897932385 / 180.0, s = std::sin(radians), c = std::cos(radians); every t is 0.
+ *   rt_rotate_x   L = 1 0 0 / 0 c -s / 0 s c     (+sin in L[2][1], -sin in L[1][2])
+ *   rt_rotate_z   L = c -s 0 / s c 0 / 0 0 1     (+sin in L[1][0], -sin in L[0][1])
+ *   rt_scale      L = sx 0 0 / 0 sy 0 / 0 0 sz   (a zero factor is refused as a zero determinant) */
+RTOW_API rt_handle rt_rotate_x(rt_scene *s, rt_handle object, double angle_degrees);
+RTOW_API rt_handle rt_rotate_z(rt_scene *s, rt_handle object, double angle_degrees);
+RTOW_API rt_handle rt_scale(rt_scene *s, rt_handle object, double sx, double sy, double sz);
+/* L (9, row-major), t (3), Li (9, row-major) of a Transform exactly as stored and uploaded.  RT_ERR_INVALID: not a Transform. */
+RTOW_API int rt_transform_get(rt_scene *s, rt_handle transform, double out21[21]);
 RTOW_API rt_handle rt_make_box(rt_scene *s, const double a[3], const double b[3], rt_handle material); /* Instance.h:166 */
 RTOW_API rt_handle rt_hittable_list(rt_scene *s, const rt_handle *objects, int count);        /* HittableList.h:21 */
 RTOW_API rt_handle rt_constant_medium(rt_scene *s, rt_handle boundary, double density, double r, double g,
@@ -210,7 +252,10 @@ RTOW_API int rt_scene_set_camera(rt_scene *s, const double lookfrom[3], const do
  * 11 = scene 0 with every MovingSphere made static (config C2); 12 = scene 7's Cornell walls, light and camera with two triangle
  * meshes in place of the boxes (a 320-triangle Lambertian icosphere under Translate, a 20-triangle metal icosahedron under
  * RotateY + Translate; both rt_triangle_mesh); 13 = scene 12 with both meshes given corner normals unit(vertex position) in mesh
- * space (rt_triangle_mesh_attr) and nothing else changed.  world_kind 0 = BvhNode world (the
+ * space (rt_triangle_mesh_attr) and nothing else changed; 14 = scene 7's walls, light and camera with four general affine
+ * instances: scene 13's icosphere under one rt_transform (scale 1.1, 1.6, 0.8, then 25 degrees about Z, then a translation), a metal
+ * MakeBox under rt_rotate_x + rt_translate, a glass unit Sphere under rt_scale + rt_translate (an ellipsoid), and a ConstantMedium
+ * whose boundary is a unit MakeBox under rt_scale + rt_translate.  world_kind 0 = BvhNode world (the
  * reference's), 1 = HittableList world ("no BVH").  earth_rgb may be NULL (scenes 2 and 9 then show cyan). */
 RTOW_API int rt_scene_build_builtin(rt_scene *s, int scene_id, int world_kind, int image_width,
                                     int image_height, uint64_t seed, const unsigned char *earth_rgb,
@@ -263,7 +308,11 @@ RTOW_API int rt_scene_dump_primary_lists(rt_scene *s, int width, int height, int
  * rt_scene_dump_leaves order, and below a leaf a list's members in list order, a BvhNode's in its sorted order.  Every row is in
  * WORLD space: the forward transforms of the chain above the primitive (innermost first; a RotateY turns points and vectors, x' =
  * (cos * x) + (sin * z), z' = (-sin * x) + (cos * z), a Translate adds its offset to points) are applied on the host, in fp64,
- * one IEEE operation at a time.
+ * one IEEE operation at a time.  A Transform (rt_transform) takes points through (L p) + t, the vectors u, v and a moving sphere's
+ * dc through L, and n through its normal rule (Li^T, renormalised), each in the row form stated there.  Where the chain above a quad
+ * or triangle holds a Transform, s is the area of the TRANSFORMED primitive: |b x c| of the world-space row (half of it for a
+ * triangle); without a Transform s is bit for bit what it always was.  (No sphere lamp stands under a Transform: rt_transform
+ * refuses it.)
  *   kind 0 quad, 1 triangle   a = Q, b = u, c = v (corners Q, Q + u, Q + v [, Q + u + v]), n = the unit normal the primitive was
  *                             constructed with, turned through the chain; s = the area |u x v| (half of it for a triangle) of the
  *                             primitive as constructed

@@ -134,6 +134,11 @@ public:
     }
     Hittable Translate(Hittable o, const Vector3 &off) { return {ok(rt_translate(s_, o.h, off.x, off.y, off.z))}; }
     Hittable RotateY(Hittable o, double degrees) { return {ok(rt_rotate_y(s_, o.h, degrees))}; }
+    // general affine instances (rt_transform): m = row-major 3x4, x_world = L x_obj + t
+    Hittable Transform(Hittable o, const double m[12]) { return {ok(rt_transform(s_, o.h, m))}; }
+    Hittable RotateX(Hittable o, double degrees) { return {ok(rt_rotate_x(s_, o.h, degrees))}; }
+    Hittable RotateZ(Hittable o, double degrees) { return {ok(rt_rotate_z(s_, o.h, degrees))}; }
+    Hittable Scale(Hittable o, double sx, double sy, double sz) { return {ok(rt_scale(s_, o.h, sx, sy, sz))}; }
     Hittable MakeBox(const Point3 &a, const Point3 &b, Material m)
     {
         const double aa[3] = {a.x, a.y, a.z}, bb[3] = {b.x, b.y, b.z};

@@ -19,56 +19,57 @@ for i, st in enumerate(idx[1:]):
         if m: cur[m.group(1)] = m.group(2)
         if line.startswith('.wavefront_size'):
             n = cur.get('name', '')
-            m = re.search(r'render_kernelILi(\d)ENS_12_GLOBAL__N_1(8AdaptiveINS\d_)?6TraitsILi(\d)ELb(\d)ELb(\d)ELi(\d)ELb(\d)ELb(\d)ELb(\d)ELi(\d+)ELb(\d)ELb(\d)', n)
+            affine = ' affine' if 'NS_6affine' in n else ''   # a unit compiled with the general affine chain step (render.hip RT_AFFINE)
+            m = re.search(r'render_kernelILi(\d)ENS_(?:6affine)?12_GLOBAL__N_1(8AdaptiveINS\d_)?6TraitsILi(\d)ELb(\d)ELb(\d)ELi(\d)ELb(\d)ELb(\d)ELb(\d)ELi(\d+)ELb(\d)ELb(\d)', n)
             if m:
                 adaptive = m.group(2) is not None  # the Adaptive<> form of the instantiation (render.hip)
                 strict, world, comp, rich, waves, media, batch, nested, block, fast, grouped = (int(x) for k, x in enumerate(m.groups()) if k != 1)
-                rows.append((int(adaptive), world, comp, rich, media, batch, nested, fast, grouped, block, waves, 'strict' if strict else 'fast',
+                rows.append((int(adaptive) + (2 if affine else 0), world, comp, rich, media, batch, nested, fast, grouped, block, waves, 'strict' if strict else 'fast',
                              int(cur['vgpr_count']), int(cur['private_segment_fixed_size']), int(cur['vgpr_spill_count'])))
-            m = re.search(r'(feature_kernel)ILi(\d)ENS_12_GLOBAL__N_16TraitsILi(\d)|(atrous_kernel)', n)
+            m = re.search(r'(feature_kernel)ILi(\d)ENS_(?:6affine)?12_GLOBAL__N_16TraitsILi(\d)|(atrous_kernel)', n)
             if m:
                 name = m.group(4) or '%s world %s %s' % (m.group(1), m.group(3), 'strict' if int(m.group(2)) else 'fast')
-                others.append((name, int(cur['vgpr_count']), int(cur['private_segment_fixed_size']), int(cur['vgpr_spill_count']),
+                others.append((name + affine, int(cur['vgpr_count']), int(cur['private_segment_fixed_size']), int(cur['vgpr_spill_count']),
                                int(cur['group_segment_fixed_size'])))
-            m = re.search(r'query_kernelILi(\d)ENS_12_GLOBAL__N_16TraitsILi(\d)E.*?EELi(\d)EEEv', n)
+            m = re.search(r'query_kernelILi(\d)ENS_(?:6affine)?12_GLOBAL__N_16TraitsILi(\d)E.*?EELi(\d)EEEv', n)
             if m:
                 name = 'query_kernel world %s %s %s' % (m.group(2), 'occlusion' if int(m.group(3)) else 'closest', 'strict' if int(m.group(1)) else 'fast')
-                others.append((name, int(cur['vgpr_count']), int(cur['private_segment_fixed_size']), int(cur['vgpr_spill_count']),
+                others.append((name + affine, int(cur['vgpr_count']), int(cur['private_segment_fixed_size']), int(cur['vgpr_spill_count']),
                                int(cur['group_segment_fixed_size'])))
-            m = re.search(r'radiance_kernelILi(\d)ENS_12_GLOBAL__N_16TraitsILi(\d)E', n)
+            m = re.search(r'radiance_kernelILi(\d)ENS_(?:6affine)?12_GLOBAL__N_16TraitsILi(\d)E', n)
             if m:
                 name = 'radiance_kernel world %s %s' % (m.group(2), 'strict' if int(m.group(1)) else 'fast')
-                others.append((name, int(cur['vgpr_count']), int(cur['private_segment_fixed_size']), int(cur['vgpr_spill_count']),
+                others.append((name + affine, int(cur['vgpr_count']), int(cur['private_segment_fixed_size']), int(cur['vgpr_spill_count']),
                                int(cur['group_segment_fixed_size'])))
-            m = re.search(r'step_kernelILi(\d)ENS_12_GLOBAL__N_16TraitsILi(\d)E', n)
+            m = re.search(r'step_kernelILi(\d)ENS_(?:6affine)?12_GLOBAL__N_16TraitsILi(\d)E', n)
             if m:
                 name = 'step_kernel world %s %s' % (m.group(2), 'strict' if int(m.group(1)) else 'fast')
-                others.append((name, int(cur['vgpr_count']), int(cur['private_segment_fixed_size']), int(cur['vgpr_spill_count']),
+                others.append((name + affine, int(cur['vgpr_count']), int(cur['private_segment_fixed_size']), int(cur['vgpr_spill_count']),
                                int(cur['group_segment_fixed_size'])))
-            m = re.search(r'advance_kernelILi(\d)ENS_12_GLOBAL__N_16TraitsILi(\d)E', n)
+            m = re.search(r'advance_kernelILi(\d)ENS_(?:6affine)?12_GLOBAL__N_16TraitsILi(\d)E', n)
             if m:
                 name = 'advance_kernel world %s %s' % (m.group(2), 'strict' if int(m.group(1)) else 'fast')
-                others.append((name, int(cur['vgpr_count']), int(cur['private_segment_fixed_size']), int(cur['vgpr_spill_count']),
+                others.append((name + affine, int(cur['vgpr_count']), int(cur['private_segment_fixed_size']), int(cur['vgpr_spill_count']),
                                int(cur['group_segment_fixed_size'])))
             m = re.search(r'(light_sample_kernel|light_pdf_kernel)ILi(\d)E', n)
             if m:
                 name = '%s %s' % (m.group(1), 'strict' if int(m.group(2)) else 'fast')
-                others.append((name, int(cur['vgpr_count']), int(cur['private_segment_fixed_size']), int(cur['vgpr_spill_count']),
+                others.append((name + affine, int(cur['vgpr_count']), int(cur['private_segment_fixed_size']), int(cur['vgpr_spill_count']),
                                int(cur['group_segment_fixed_size'])))
-            m = re.search(r'(advance_direct_kernel|shadow_kernel)ILi(\d)ENS_12_GLOBAL__N_16TraitsILi(\d)E', n)
+            m = re.search(r'(advance_direct_kernel|shadow_kernel)ILi(\d)ENS_(?:6affine)?12_GLOBAL__N_16TraitsILi(\d)E', n)
             if m:
                 name = '%s world %s %s' % (m.group(1), m.group(3), 'strict' if int(m.group(2)) else 'fast')
-                others.append((name, int(cur['vgpr_count']), int(cur['private_segment_fixed_size']), int(cur['vgpr_spill_count']),
+                others.append((name + affine, int(cur['vgpr_count']), int(cur['private_segment_fixed_size']), int(cur['vgpr_spill_count']),
                                int(cur['group_segment_fixed_size'])))
-            m = re.search(r'(film_direct_kernel)ILi(\d)ENS_12_GLOBAL__N_16TraitsILi(\d)E', n)
+            m = re.search(r'(film_direct_kernel)ILi(\d)ENS_(?:6affine)?12_GLOBAL__N_16TraitsILi(\d)E', n)
             if m:
                 name = '%s world %s %s' % (m.group(1), m.group(3), 'strict' if int(m.group(2)) else 'fast')
-                others.append((name, int(cur['vgpr_count']), int(cur['private_segment_fixed_size']), int(cur['vgpr_spill_count']),
+                others.append((name + affine, int(cur['vgpr_count']), int(cur['private_segment_fixed_size']), int(cur['vgpr_spill_count']),
                                int(cur['group_segment_fixed_size'])))
-            m = re.search(r'(radiance_direct_kernel)ILi(\d)ENS_12_GLOBAL__N_16TraitsILi(\d)E', n)
+            m = re.search(r'(radiance_direct_kernel)ILi(\d)ENS_(?:6affine)?12_GLOBAL__N_16TraitsILi(\d)E', n)
             if m:
                 name = '%s world %s %s' % (m.group(1), m.group(3), 'strict' if int(m.group(2)) else 'fast')
-                others.append((name, int(cur['vgpr_count']), int(cur['private_segment_fixed_size']), int(cur['vgpr_spill_count']),
+                others.append((name + affine, int(cur['vgpr_count']), int(cur['private_segment_fixed_size']), int(cur['vgpr_spill_count']),
                                int(cur['group_segment_fixed_size'])))
             m = re.search(r'(advance_scan_kernel|advance_gather_kernel|advance_direct_gather_kernel)', n)
             if m:
@@ -76,7 +77,7 @@ for i, st in enumerate(idx[1:]):
                                int(cur['group_segment_fixed_size'])))
             cur = {}
 print("world comp rich media batch nested fast grouped block waves build vgpr scratchB spills")
-for r in sorted(rows): print(*r[1:], *(['adaptive'] if r[0] else []))
+for r in sorted(rows): print(*r[1:], *(['adaptive'] if r[0] & 1 else []), *(['affine'] if r[0] & 2 else []))
 if others:
     print("kernel vgpr scratchB spills ldsB")
     for r in sorted(others): print(*r)

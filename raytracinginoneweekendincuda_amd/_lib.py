@@ -299,6 +299,11 @@ SIGNATURES = {
     "rt_obj_mesh_free": (None, [C.POINTER(ObjMesh)]),
     "rt_translate": (H, [P, H, D, D, D]),
     "rt_rotate_y": (H, [P, H, D]),
+    "rt_transform": (H, [P, H, C.POINTER(C.c_double)]),
+    "rt_rotate_x": (H, [P, H, D]),
+    "rt_rotate_z": (H, [P, H, D]),
+    "rt_scale": (H, [P, H, D, D, D]),
+    "rt_transform_get": (C.c_int, [P, H, C.POINTER(C.c_double)]),
     "rt_make_box": (H, [P, D3, D3, H]),
     "rt_hittable_list": (H, [P, C.POINTER(H), I]),
     "rt_constant_medium": (H, [P, H, D, D, D, D]),

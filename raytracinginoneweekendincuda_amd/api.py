@@ -229,6 +229,37 @@ class Scene:
     def RotateY(self, obj, degrees):
         return _h(lib().rt_rotate_y(self._p, obj, degrees))
 
+    def Transform(self, obj, matrix):
+        """A general affine instance x_world = L x_obj + t (rt_transform): ``matrix`` is 3x4 ``[L | t]``, or 4x4 with the last row
+        0 0 0 1.  Stands wherever Translate / RotateY may stand; rtow.h states its arithmetic operation by operation."""
+        m = np.array(matrix, dtype=np.float64)
+        if m.shape == (4, 4):
+            if not np.array_equal(m[3], [0.0, 0.0, 0.0, 1.0]):
+                raise RtowError("Transform: the last row of a 4x4 matrix must be 0 0 0 1")
+            m = m[:3]
+        if m.shape != (3, 4):
+            raise RtowError("Transform: matrix must be 3x4 or 4x4")
+        m = np.ascontiguousarray(m)
+        return _h(lib().rt_transform(self._p, obj, m.ctypes.data_as(C.POINTER(C.c_double))))
+
+    def RotateX(self, obj, degrees):
+        return _h(lib().rt_rotate_x(self._p, obj, degrees))
+
+    def RotateZ(self, obj, degrees):
+        return _h(lib().rt_rotate_z(self._p, obj, degrees))
+
+    def Scale(self, obj, s):
+        """``s``: one factor for the three axes, or three."""
+        sx, sy, sz = (float(s),) * 3 if np.ndim(s) == 0 else map(float, s)
+        return _h(lib().rt_scale(self._p, obj, sx, sy, sz))
+
+    def transform_matrices(self, handle):
+        """``(L, t, Li)`` of a Transform exactly as stored and uploaded: (3, 3), (3,), (3, 3) float64 (rt_transform_get)."""
+        out = (C.c_double * 21)()
+        _check(lib().rt_transform_get(self._p, handle, out))
+        a = np.array(out, dtype=np.float64)
+        return a[:9].reshape(3, 3).copy(), a[9:12].copy(), a[12:].reshape(3, 3).copy()
+
     def MakeBox(self, a, b, material):
         return _h(lib().rt_make_box(self._p, _v3(a), _v3(b), material))
 

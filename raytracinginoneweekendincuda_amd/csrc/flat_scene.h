@@ -92,10 +92,19 @@ struct BoxRec { double na[6], d[6], mn[3], mx[3]; uint32_t quad_first, pad; };
 
 
 // Instance transform step (R/Instance.h:31-37 Translate, :74-112 RotateY).
-enum : uint32_t { XF_TRANSLATE = 0u, XF_ROTATE_Y = 1u };
+enum : uint32_t { XF_TRANSLATE = 0u, XF_ROTATE_Y = 1u, XF_AFFINE = 2u, XF_AFFINE_ROW = 3u };
 struct Xform { double a, b, c; uint32_t kind; uint32_t pad; };  // translate: offset xyz; rotate: a = sin, b = cos
+// A general affine step (include/rtow.h rt_transform: x_world = L x_obj + t, Li = the inverse of L) is kAffineRows consecutive rows
+// of this table, so that it is staged in LDS, or not, with the chain it belongs to:
+//   row 0      XF_AFFINE      a, b, c = t                  pad = 0
+//   rows 1..3  XF_AFFINE_ROW  a, b, c = row 0..2 of L      pad = the row's offset from row 0
+//   rows 4..6  XF_AFFINE_ROW  a, b, c = row 0..2 of Li     pad = the row's offset from row 0
+// A walk outermost first meets row 0 and skips the other six; a walk innermost first meets row 6 and finds row 0 six rows before
+// it.  ObjectRec::xf_count and TreeNodeRec::chain_count count ROWS; rt_scene_info::n_xforms counts steps.  Only a scene with
+// SCENE_AFFINE holds such rows.
+constexpr uint32_t kAffineRows = 7;
 
-// Composite leaf: [ConstantMedium] -> chain of Translate/RotateY (outermost first) -> geometry.
+// Composite leaf: [ConstantMedium] -> chain of Translate / RotateY / Transform steps (outermost first) -> geometry.
 enum : uint32_t { GEOM_SINGLE = 0u, GEOM_SPHERES = 1u, GEOM_MSPHERES = 2u, GEOM_QUADS = 3u, GEOM_MIXED = 4u,
                   GEOM_BVH = 5u,    // `first` = root of a sub-BVH (in nodes[]) over the group's primitives
                   GEOM_BOX = 6u };  // six axis-aligned quads that form a MakeBox box: `first` = index into boxes
@@ -125,10 +134,10 @@ struct MediumRec { double neg_inv_density; uint32_t phase_mat; uint32_t sphere; 
 // evaluated by an explicit-stack interpreter (render.hip tree_hit) that makes the reference's calls in the reference's order.
 // `chain` = the transforms the world ray has gone through when this node's Hit is called (outermost first, a private
 // contiguous run of xforms[]): the local ray is always recomputed from the world ray, never un-transformed.
-enum : uint32_t { TN_PRIM = 0u, TN_TRANSLATE = 1u, TN_ROTATE_Y = 2u, TN_MEDIUM = 3u, TN_LIST = 4u, TN_BVH = 5u };
+enum : uint32_t { TN_PRIM = 0u, TN_TRANSLATE = 1u, TN_ROTATE_Y = 2u, TN_MEDIUM = 3u, TN_LIST = 4u, TN_BVH = 5u, TN_TRANSFORM = 6u };
 struct TreeNodeRec {
     uint32_t kind;
-    uint32_t a;  // PRIM: primitive ref; TRANSLATE / ROTATE_Y / MEDIUM: child node; LIST: first entry of tree_items[]; BVH: root in tree_bvh[]
+    uint32_t a;  // PRIM: primitive ref; TRANSLATE / ROTATE_Y / TRANSFORM / MEDIUM: child node; LIST: first entry of tree_items[]; BVH: root in tree_bvh[]
     uint32_t b;  // MEDIUM: index into media; LIST: number of children
     uint32_t chain_first, chain_count;
     uint32_t pad0, pad1, pad2;
@@ -208,7 +217,7 @@ struct ImageRec { uint64_t offset; int32_t width, height; };
 struct PerlinRec { double vec[256][3]; int32_t perm_x[256], perm_y[256], perm_z[256]; };  // R/Perlin.h:82-85
 
 // Light table (rt_scene_sample_lights, rt_scene_light_pdf): one row per emissive world primitive, in WORLD space -- the chain of
-// Translate / RotateY above the primitive applied on the host (scene_builder.cpp collect_lights), so that the light kernels need
+// Translate / RotateY / Transform above the primitive applied on the host (scene_builder.cpp collect_lights), so that the light kernels need
 // neither the object records nor the transforms.  128 bytes, the layout of rt_light_row in include/rtow.h:
 //   quad, triangle   a = Q, b = u, c = v, n = the unit normal, s = the area
 //   sphere           a = the centre, s = the radius
@@ -309,6 +318,7 @@ enum : uint32_t {
     SCENE_WORLD_MSPHERES = 16u,   // WORLD_BVH of spheres / unit-time moving spheres only: ms_planes is filled
     SCENE_SEGMENTED = 64u,        // WORLD_BVH with composite leaves: fast_nodes / fast_order / seg_media describe the segmented walk
     SCENE_VERTEX_ATTR = 128u,     // some triangle row carries corner normals or texture coordinates (TriAttrRow)
+    SCENE_AFFINE = 256u,          // some chain holds a general affine step (XF_AFFINE): served by the units compiled with RT_AFFINE (render.hip RT_TO_AFFINE)
 };
 
 } // namespace rtow

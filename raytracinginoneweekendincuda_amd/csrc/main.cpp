@@ -309,7 +309,7 @@ int main(int argc, char **argv)
             earth_is_bytes = true;
         } else {
             std::fprintf(stderr,
-                         "usage: rtow [--scene 0..13] [--width W] [--height H] [--spp N] [--depth D] [--seed S]\n"
+                         "usage: rtow [--scene 0..14] [--width W] [--height H] [--spp N] [--depth D] [--seed S]\n"
                          "            [--world bvh|list] [--variant strict|fast] [--device N] [--gpus N] [--output file.ppm]\n"
                          "            [--earth earthmap.jpg|decoded.ppm | --earth-bytes texture.ppm] [--accelerate-lists] [--flags N]\n"
                          "            [--noise T [--min-spp N] [--check-every K] [--samples-map file.pgm]]\n"
@@ -390,7 +390,7 @@ int main(int argc, char **argv)
         std::fprintf(stderr, "--trace-at needs --spp >= 1 and --depth >= 0\n");
         return 2;
     }
-    if (spp < 0) spp = (scene_id == 9) ? 100 : (((scene_id >= 5 && scene_id <= 8) || scene_id == 12 || scene_id == 13) ? 200 : 10);  // R/kernel.cu:593 (12, 13: lit like 7)
+    if (spp < 0) spp = (scene_id == 9) ? 100 : (((scene_id >= 5 && scene_id <= 8) || (scene_id >= 12 && scene_id <= 14)) ? 200 : 10);  // R/kernel.cu:593 (12 .. 14: lit like 7)
 
     if (pick && (pick_i < 0 || pick_i >= width || pick_j < 0 || pick_j >= height)) {
         std::fprintf(stderr, "%s: pixel (%d, %d) is outside the %dx%d frame\n", trace_at ? "--trace-at" : radiance_at ? "--radiance-at" : "--pick", pick_i, pick_j, width, height);

@@ -71,11 +71,18 @@
 #ifndef RT_FILM_DIRECT  // 1: this translation unit holds the frame kernels with light samples (film_direct_kernel) and nothing else
 #define RT_FILM_DIRECT 0
 #endif
+#ifndef RT_AFFINE  // 1: this translation unit compiles the general affine chain step (rt_transform) into its chain walks; its launchers
+#define RT_AFFINE 0  // carry the suffix _x and serve the scenes with SCENE_AFFINE.  0: chains hold Translate / RotateY only, the code without it
+#endif
 // the lane-per-ray units: one lane per pixel, ray or point, no persistent waves (film_direct_kernel alone is persistent: its lanes take pixels from a queue)
 #define RT_LANE_UNIT (RT_FEATURES || RT_QUERY || RT_RADIANCE || RT_STEP || RT_ADVANCE || RT_LIGHTS || RT_ADVANCE_DIRECT || RT_RADIANCE_DIRECT || RT_FILM_DIRECT)
 
 namespace rtow {
+#if RT_AFFINE
+inline namespace affine {
+#endif
 namespace {
+constexpr bool kAffineUnit = RT_AFFINE != 0;
 
 // Kernel specialisation.  One source, a few instantiations; the host picks by what the scene contains so
 // that a scene never pays registers or code for features it does not use:
@@ -538,6 +545,30 @@ struct GroupedSums {
 #define PH_COUNT(k) do { } while (0)
 #define PH_SUB_END(k) do { } while (0)
 #endif
+// A general affine step (include/rtow.h rt_transform; flat_scene.h XF_AFFINE has the rows): x_world = L x_obj + t.  Only scenes that
+// hold one (SCENE_AFFINE) are served by the units compiled with RT_AFFINE (kAffineUnit); every other unit compiles the two-way branch of
+// Translate / RotateY alone, the code it compiled before there was a third kind.
+// affine_rows: M p for the matrix whose rows are xforms[row .. row + 2], each row ((m0 * p.x) + (m1 * p.y)) + (m2 * p.z).
+DEV Vec affine_rows(const DeviceScene &sc, uint32_t row, Vec p)
+{
+    const Xform r0 = get_xform(sc, row), r1 = get_xform(sc, row + 1), r2 = get_xform(sc, row + 2);
+    return mk(((r0.a * p.x) + (r0.b * p.y)) + (r0.c * p.z), ((r1.a * p.x) + (r1.b * p.y)) + (r1.c * p.z), ((r2.a * p.x) + (r2.b * p.y)) + (r2.c * p.z));
+}
+// head: the step's first row (x, holding t).  o' = Li (o - t), d' = Li d; the time stays and d' is not normalised, so the child's t is the world's.
+DEV void affine_to_local(const DeviceScene &sc, uint32_t head, const Xform &x, Ray &lr)
+{
+    lr.o = affine_rows(sc, head + 4, lr.o - mk(x.a, x.b, x.c));
+    lr.d = affine_rows(sc, head + 4, lr.d);
+}
+// The way back of the hit record: P = (L P') + t; n = Li^T n', renormalised at every such step.
+DEV void affine_to_world(const DeviceScene &sc, uint32_t head, Vec &p, Vec &n)
+{
+    const Xform t = get_xform(sc, head);
+    p = affine_rows(sc, head + 1, p) + mk(t.a, t.b, t.c);
+    const Xform i0 = get_xform(sc, head + 4), i1 = get_xform(sc, head + 5), i2 = get_xform(sc, head + 6);
+    const Vec m = mk(((i0.a * n.x) + (i1.a * n.y)) + (i2.a * n.z), ((i0.b * n.x) + (i1.b * n.y)) + (i2.b * n.z), ((i0.c * n.x) + (i1.c * n.y)) + (i2.c * n.z));
+    n = (1.0 / sqrt(length_sq(m))) * m;
+}
 // Ray into the object space of a composite leaf: Translate (R/Instance.h:46) and RotateY (:121-131)
 // applied outermost first.
 DEV Ray to_object_space(const DeviceScene &sc, const ObjectRec &o, const Ray &r)
@@ -547,10 +578,13 @@ DEV Ray to_object_space(const DeviceScene &sc, const ObjectRec &o, const Ray &r)
         Xform x = get_xform(sc, o.xf_first + k);
         if (x.kind == XF_TRANSLATE) {
             lr.o = lr.o - mk(x.a, x.b, x.c);
-        } else {
+        } else if (!kAffineUnit || x.kind == XF_ROTATE_Y) {
             double st = x.a, ct = x.b;
             lr.o = mk((ct * lr.o.x) - (st * lr.o.z), lr.o.y, (st * lr.o.x) + (ct * lr.o.z));
             lr.d = mk((ct * lr.d.x) - (st * lr.d.z), lr.d.y, (st * lr.d.x) + (ct * lr.d.z));
+        } else {
+            affine_to_local(sc, o.xf_first + k, x, lr);
+            k += kAffineRows - 1;
         }
     }
     return lr;
@@ -790,10 +824,13 @@ DEV Ray chain_ray(const DeviceScene &sc, uint32_t first, uint32_t count, const R
         Xform x = get_xform(sc, first + k);
         if (x.kind == XF_TRANSLATE) {
             lr.o = lr.o - mk(x.a, x.b, x.c);
-        } else {
+        } else if (!kAffineUnit || x.kind == XF_ROTATE_Y) {
             double st = x.a, ct = x.b;
             lr.o = mk((ct * lr.o.x) - (st * lr.o.z), lr.o.y, (st * lr.o.x) + (ct * lr.o.z));
             lr.d = mk((ct * lr.d.x) - (st * lr.d.z), lr.d.y, (st * lr.d.x) + (ct * lr.d.z));
+        } else {
+            affine_to_local(sc, first + k, x, lr);
+            k += kAffineRows - 1;
         }
     }
     return lr;
@@ -832,6 +869,9 @@ DEV bool tree_hit(const DeviceScene &sc, uint32_t root, const Ray &r, double tmi
         }
         case TN_TRANSLATE:
         case TN_ROTATE_Y:
+#if RT_AFFINE
+        case TN_TRANSFORM:
+#endif
             if (f.step == 0) {
                 f.step = 1;
                 call = n.a; call_tmin = f.tmin; call_tmax = f.tmax;
@@ -2806,10 +2846,13 @@ DEV Surface make_surface(const DeviceScene &sc, const Ray &r, const HitInfo &h)
                 Xform x = get_xform(sc, xf_first + k);
                 if (x.kind == XF_TRANSLATE) {
                     s.p = s.p + mk(x.a, x.b, x.c);
-                } else {
+                } else if (!kAffineUnit || x.kind == XF_ROTATE_Y) {
                     double st = x.a, ct = x.b;
                     s.p = mk((ct * s.p.x) + (st * s.p.z), s.p.y, (-st * s.p.x) + (ct * s.p.z));
                     s.n = mk((ct * s.n.x) + (st * s.n.z), s.n.y, (-st * s.n.x) + (ct * s.n.z));
+                } else {  // x is the last row of the step
+                    k -= kAffineRows - 1;
+                    affine_to_world(sc, xf_first + k, s.p, s.n);
                 }
             }
         }
@@ -3098,6 +3141,9 @@ DEV int owned_row(int lr, int stripe, int rank, int world)
 }
 
 } // namespace
+#if RT_AFFINE
+}  // inline namespace affine
+#endif
 
 // ------------------------------------------------------------------------------------------------
 // kernels
@@ -4163,13 +4209,34 @@ hipError_t launch_tile_order(const uint32_t *tile_cost, uint32_t *tile_order, ui
 }
 #endif
 
-#if RT_STRICT
-#define RT_SUFFIX strict
-#else
-#define RT_SUFFIX fast
-#endif
 #define RT_CAT2(a, b) a##b
 #define RT_CAT(a, b) RT_CAT2(a, b)
+#if RT_STRICT
+#define RT_BUILD strict
+#else
+#define RT_BUILD fast
+#endif
+// A scene with a general affine step in some chain (SCENE_AFFINE) is served by the units compiled with RT_AFFINE: every launcher of a
+// kernel that walks chains hands such a scene to its twin there, so a scene without one runs the code it ran before.
+#if RT_AFFINE
+#define RT_SUFFIX RT_CAT(RT_BUILD, _x)
+#define RT_TO_AFFINE(name, ...) do { } while (0)
+#else
+#define RT_SUFFIX RT_BUILD
+#define RT_X(name) RT_CAT(RT_CAT(name, RT_BUILD), _x)
+#define RT_TO_AFFINE(name, ...) do { if (sc.flags & SCENE_AFFINE) return RT_X(name)(__VA_ARGS__); } while (0)
+hipError_t RT_X(launch_composite_)(int which, const DeviceScene &sc, const RenderArgs &a, hipStream_t stream, KernelInfo *info);
+hipError_t RT_X(launch_adaptive_composite_)(int which, const DeviceScene &sc, const RenderArgs &a, hipStream_t stream, KernelInfo *info);
+hipError_t RT_X(launch_features_)(const DeviceScene &sc, const FeatureArgs &a, hipStream_t stream);
+hipError_t RT_X(launch_query_)(const DeviceScene &sc, const QueryArgs &a, hipStream_t stream, QueryKernelInfo *info);
+hipError_t RT_X(launch_radiance_)(const DeviceScene &sc, const RadianceArgs &a, hipStream_t stream, QueryKernelInfo *info);
+hipError_t RT_X(launch_step_)(const DeviceScene &sc, const StepArgs &a, hipStream_t stream, QueryKernelInfo *info);
+hipError_t RT_X(launch_advance_)(const DeviceScene &sc, const AdvanceArgs &a, hipStream_t stream, QueryKernelInfo *info);
+hipError_t RT_X(launch_advance_direct_)(const DeviceScene &sc, const AdvanceDirectArgs &a, hipStream_t stream, QueryKernelInfo *info);
+hipError_t RT_X(launch_advance_shadow_)(const DeviceScene &sc, const AdvanceDirectArgs &a, hipStream_t stream, QueryKernelInfo *info);
+hipError_t RT_X(launch_radiance_direct_)(const DeviceScene &sc, const RadianceDirectArgs &d, hipStream_t stream, QueryKernelInfo *info);
+hipError_t RT_X(launch_film_direct_)(const DeviceScene &sc, const FilmDirectArgs &d, hipStream_t stream, FilmDirectInfo *info);
+#endif
 
 #if RT_GROUP == 0 && !RT_ADAPT && !RT_FEATURES
 hipError_t RT_CAT(launch_seed_, RT_SUFFIX)(const SeedArgs &a, hipStream_t stream)
@@ -4441,6 +4508,7 @@ __global__ __launch_bounds__(256) void feature_kernel(DeviceScene sc, FeatureArg
 
 hipError_t RT_CAT(launch_features_, RT_SUFFIX)(const DeviceScene &sc, const FeatureArgs &a, hipStream_t stream)
 {
+    RT_TO_AFFINE(launch_features_, sc, a, stream);
     if (a.n_pixels == 0) return hipSuccess;
     const dim3 grid((a.n_pixels + 255u) / 256u), block(256);
     if (sc.world_kind == WORLD_BVH) hipLaunchKernelGGL((feature_kernel<RT_STRICT, TBvhNested>), grid, block, 0, stream, sc, a);
@@ -4637,6 +4705,7 @@ __global__ __launch_bounds__(256) void query_kernel(DeviceScene sc, QueryArgs a)
 
 hipError_t RT_CAT(launch_query_, RT_SUFFIX)(const DeviceScene &sc, const QueryArgs &a, hipStream_t stream, QueryKernelInfo *info)
 {
+    RT_TO_AFFINE(launch_query_, sc, a, stream, info);
     if (a.mode != 0 && a.mode != 1) return hipErrorInvalidValue;
     if (sc.world_kind == WORLD_BVH && !a.node_leaf_pos) return hipErrorInvalidValue;
     void (*kernel)(DeviceScene, QueryArgs);
@@ -4738,6 +4807,7 @@ __global__ __launch_bounds__(256) void radiance_kernel(DeviceScene sc, RadianceA
 
 hipError_t RT_CAT(launch_radiance_, RT_SUFFIX)(const DeviceScene &sc, const RadianceArgs &a, hipStream_t stream, QueryKernelInfo *info)
 {
+    RT_TO_AFFINE(launch_radiance_, sc, a, stream, info);
     if (a.samples < 1 || a.max_depth < 0 || !a.origin || !a.direction || !(a.radiance || a.path_rays || a.rng_out)) return hipErrorInvalidValue;
     void (*kernel)(DeviceScene, RadianceArgs) =
         sc.world_kind == WORLD_BVH ? radiance_kernel<RT_STRICT, TBvhNested> : radiance_kernel<RT_STRICT, TListNested>;
@@ -4826,6 +4896,7 @@ __global__ __launch_bounds__(256) void step_kernel(DeviceScene sc, StepArgs a)
 
 hipError_t RT_CAT(launch_step_, RT_SUFFIX)(const DeviceScene &sc, const StepArgs &a, hipStream_t stream, QueryKernelInfo *info)
 {
+    RT_TO_AFFINE(launch_step_, sc, a, stream, info);
     const bool any = a.status || a.emitted || a.attenuation || a.origin_out || a.direction_out || a.time_out || a.t || a.normal || a.front_face ||
                      a.material || a.rng_out;
     if (!a.origin || !a.direction || !any) return hipErrorInvalidValue;
@@ -4939,6 +5010,7 @@ __global__ __launch_bounds__(256) void advance_kernel(DeviceScene sc, AdvanceArg
 
 hipError_t RT_CAT(launch_advance_, RT_SUFFIX)(const DeviceScene &sc, const AdvanceArgs &a, hipStream_t stream, QueryKernelInfo *info)
 {
+    RT_TO_AFFINE(launch_advance_, sc, a, stream, info);
     if (!info && (!a.origin || !a.direction || !a.survivor || !a.block_counts)) return hipErrorInvalidValue;
     void (*kernel)(DeviceScene, AdvanceArgs) =
         sc.world_kind == WORLD_BVH ? advance_kernel<RT_STRICT, TBvhNested> : advance_kernel<RT_STRICT, TListNested>;
@@ -5578,6 +5650,7 @@ __global__ __launch_bounds__(256) void shadow_kernel(DeviceScene sc, AdvanceDire
 
 hipError_t RT_CAT(launch_advance_direct_, RT_SUFFIX)(const DeviceScene &sc, const AdvanceDirectArgs &a, hipStream_t stream, QueryKernelInfo *info)
 {
+    RT_TO_AFFINE(launch_advance_direct_, sc, a, stream, info);
     const AdvanceArgs &v = a.adv;
     if (!info && (!v.origin || !v.direction || !v.survivor || !v.block_counts || !v.stage.origin || !v.stage.time || !v.stage.rng_state ||
                   !v.stage.ray_id || !a.scatter_pdf_stage || !a.shadow_direction || !a.shadow_distance || !a.shadow_radiance || !a.pending))
@@ -5590,6 +5663,7 @@ hipError_t RT_CAT(launch_advance_direct_, RT_SUFFIX)(const DeviceScene &sc, cons
 
 hipError_t RT_CAT(launch_advance_shadow_, RT_SUFFIX)(const DeviceScene &sc, const AdvanceDirectArgs &a, hipStream_t stream, QueryKernelInfo *info)
 {
+    RT_TO_AFFINE(launch_advance_shadow_, sc, a, stream, info);
     const AdvanceArgs &v = a.adv;
     if (!info && (!v.stage.origin || !v.stage.time || !v.stage.rng_state || !v.stage.ray_id || !a.shadow_direction || !a.shadow_distance ||
                   !a.shadow_radiance || !a.pending))
@@ -5921,6 +5995,7 @@ __global__ __launch_bounds__(256) void radiance_direct_kernel(DeviceScene sc, Ra
 
 hipError_t RT_CAT(launch_radiance_direct_, RT_SUFFIX)(const DeviceScene &sc, const RadianceDirectArgs &d, hipStream_t stream, QueryKernelInfo *info)
 {
+    RT_TO_AFFINE(launch_radiance_direct_, sc, d, stream, info);
     const RadianceArgs &a = d.rad;
     if (a.samples < 1 || a.max_depth < 0 || !a.origin || !a.direction || !(a.radiance || a.path_rays || a.rng_out)) return hipErrorInvalidValue;
     if (!info && d.n_lights != 0 && (!d.rows || !d.cdf)) return hipErrorInvalidValue;
@@ -6340,6 +6415,7 @@ __global__ __launch_bounds__(256) void film_direct_kernel(DeviceScene sc, FilmDi
 
 hipError_t RT_CAT(launch_film_direct_, RT_SUFFIX)(const DeviceScene &sc, const FilmDirectArgs &d, hipStream_t stream, FilmDirectInfo *info)
 {
+    RT_TO_AFFINE(launch_film_direct_, sc, d, stream, info);
     if (d.spp < 0 || d.max_depth < 0 || d.width <= 0 || d.rows_owned < 0) return hipErrorInvalidValue;
     if (!info) {
         if (!d.pixels || !d.state || !d.ray_counter || !d.cursor || !d.shadow_counters) return hipErrorInvalidValue;
@@ -6397,11 +6473,13 @@ hipError_t launch_composite_as(int which, const DeviceScene &sc, const RenderArg
 #if RT_ADAPT
 hipError_t RT_CAT(launch_adaptive_composite_, RT_SUFFIX)(int which, const DeviceScene &sc, const RenderArgs &a, hipStream_t stream, KernelInfo *info)
 {
+    RT_TO_AFFINE(launch_adaptive_composite_, which, sc, a, stream, info);
     return launch_composite_as<true>(which, sc, a, stream, info);
 }
 #else
 hipError_t RT_CAT(launch_composite_, RT_SUFFIX)(int which, const DeviceScene &sc, const RenderArgs &a, hipStream_t stream, KernelInfo *info)
 {
+    RT_TO_AFFINE(launch_composite_, which, sc, a, stream, info);
     return launch_composite_as<false>(which, sc, a, stream, info);
 }
 #endif

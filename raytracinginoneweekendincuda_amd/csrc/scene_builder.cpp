@@ -49,6 +49,20 @@ static inline double length(D3 a) { return std::sqrt(a.x * a.x + a.y * a.y + a.z
 static inline D3 over(D3 a, double t) { return scale(1 / t, a); }
 static inline D3 normalize(D3 a) { return over(a, length(a)); }
 static inline double comp(D3 a, int k) { return k == 0 ? a.x : (k == 1 ? a.y : a.z); }
+// A general affine instance's arithmetic as include/rtow.h rt_transform states it (and render.hip affine_rows computes it): one
+// rounding per operation, this file is built with contraction off.  m: a row-major 3x3.
+static inline D3 mat_rows(const double *m, D3 p)
+{
+    return mk(((m[0] * p.x) + (m[1] * p.y)) + (m[2] * p.z), ((m[3] * p.x) + (m[4] * p.y)) + (m[5] * p.z), ((m[6] * p.x) + (m[7] * p.y)) + (m[8] * p.z));
+}
+static inline D3 affine_point(const HostAffine &a, D3 p) { return add(mat_rows(a.L, p), mk(a.t[0], a.t[1], a.t[2])); }  // (L p) + t
+static inline D3 affine_normal(const HostAffine &a, D3 n)  // Li^T n, renormalised
+{
+    const double *i = a.Li;
+    const D3 m = mk(((i[0] * n.x) + (i[3] * n.y)) + (i[6] * n.z), ((i[1] * n.x) + (i[4] * n.y)) + (i[7] * n.z), ((i[2] * n.x) + (i[5] * n.y)) + (i[8] * n.z));
+    return scale(1.0 / std::sqrt(m.x * m.x + m.y * m.y + m.z * m.z), m);
+}
+static inline bool is_instance(HKind k) { return k == HKind::Translate || k == HKind::RotateY || k == HKind::Transform; }
 
 // ------------------------------------------------------------------------------------------------
 // boxes (R/AABB.h, R/Interval.h)
@@ -259,8 +273,8 @@ namespace {
 //   spheres   Sphere and MovingSphere leaves.  A moving sphere that rests (center0 == center1, time0 != time1) is at c0 + frac * 0
 //             = c0 exactly at every time and is keyed as the static sphere it is; one with time0 == time1 has a centre of inf /
 //             NaN and is never hit.  Exact comparison.
-//   faces     every quad: a Quad leaf, the quads of a list leaf (MakeBox: six), and both behind a Translate / RotateY chain, in
-//             world space.  Two faces that were not transformed are compared bit for bit (surfaces that differ in the last bit
+//   faces     every quad: a Quad leaf, the quads of a list leaf (MakeBox: six), and both behind a Translate / RotateY / Transform chain,
+//             in world space.  Two faces that were not transformed are compared bit for bit (surfaces that differ in the last bit
 //             do not tie); a transformed face is compared with a tolerance far above its rounding, since finding a tie too
 //             many costs only speed.  Rectangles overlap when their (padded) bounding boxes meet.
 // One kind of overlap is left alone, or a field of boxes that stand side by side (the ground of the Book-2 final scene) would
@@ -421,7 +435,8 @@ static bool has_coincident_primitives(const SceneImpl &s, const std::vector<uint
                 for (size_t k = chain.size(); k-- > 0;) {  // innermost transform first (R/Instance.h:49-50, :142-147)
                     const HostHittable &x = *chain[k];
                     if (x.kind == HKind::Translate) p = add(p, x.offset);
-                    else p = mk(x.cos_t * p.x + x.sin_t * p.z, p.y, -x.sin_t * p.x + x.cos_t * p.z);
+                    else if (x.kind == HKind::RotateY) p = mk(x.cos_t * p.x + x.sin_t * p.z, p.y, -x.sin_t * p.x + x.cos_t * p.z);
+                    else p = affine_point(s.transforms[x.xf - 1], p);
                 }
             const D3 nn = normalize(cross(sub(c[1], c[0]), sub(c[3], c[0])));
             n[0] = nn.x; n[1] = nn.y; n[2] = nn.z;
@@ -471,7 +486,7 @@ static bool has_coincident_primitives(const SceneImpl &s, const std::vector<uint
     for (uint32_t leaf = 0; leaf < handles.size(); leaf++) {
         const HostHittable *h = &s.hittables[handles[leaf] - 1];
         std::vector<const HostHittable *> chain;  // outermost first
-        while (h->kind == HKind::Translate || h->kind == HKind::RotateY) {
+        while (is_instance(h->kind)) {
             chain.push_back(h);
             h = &s.hittables[h->child - 1];
         }
@@ -706,9 +721,24 @@ struct Flattener {
     {
         const HostHittable *h = &s.hittables[handle - 1];
         if (h->kind == HKind::Medium) h = &s.hittables[h->child - 1];
-        while (h->kind == HKind::Translate || h->kind == HKind::RotateY) h = &s.hittables[h->child - 1];
+        while (is_instance(h->kind)) h = &s.hittables[h->child - 1];
         if (h->kind == HKind::Medium) return false;
         return only_primitives(s, (uint32_t)(h - s.hittables.data()) + 1);
+    }
+    // One instance as rows of xforms[] (flat_scene.h Xform; a Transform is kAffineRows of them and sets SCENE_AFFINE).
+    void push_step(std::vector<Xform> &to, const HostHittable &h)
+    {
+        if (h.kind == HKind::Translate) {
+            to.push_back({h.offset.x, h.offset.y, h.offset.z, XF_TRANSLATE, 0});
+        } else if (h.kind == HKind::RotateY) {
+            to.push_back({h.sin_t, h.cos_t, 0.0, XF_ROTATE_Y, 0});
+        } else {
+            const HostAffine &a = s.transforms[h.xf - 1];
+            to.push_back({a.t[0], a.t[1], a.t[2], XF_AFFINE, 0});
+            for (uint32_t r = 0; r < 3; r++) to.push_back({a.L[3 * r], a.L[3 * r + 1], a.L[3 * r + 2], XF_AFFINE_ROW, 1 + r});
+            for (uint32_t r = 0; r < 3; r++) to.push_back({a.Li[3 * r], a.Li[3 * r + 1], a.Li[3 * r + 2], XF_AFFINE_ROW, 4 + r});
+            f.flags |= SCENE_AFFINE;
+        }
     }
     uint32_t tree_depth_seen = 0;
     // One node of the tree for `handle`, whose Hit is called with the ray transformed by `chain` (outermost first).
@@ -725,11 +755,10 @@ struct Flattener {
         if (is_primitive(h.kind)) {
             rec.kind = TN_PRIM;
             rec.a = add_primitive(h);
-        } else if (h.kind == HKind::Translate || h.kind == HKind::RotateY) {
+        } else if (is_instance(h.kind)) {
             std::vector<Xform> inner = chain;
-            if (h.kind == HKind::Translate) inner.push_back({h.offset.x, h.offset.y, h.offset.z, XF_TRANSLATE, 0});
-            else inner.push_back({h.sin_t, h.cos_t, 0.0, XF_ROTATE_Y, 0});
-            rec.kind = h.kind == HKind::Translate ? TN_TRANSLATE : TN_ROTATE_Y;
+            push_step(inner, h);
+            rec.kind = h.kind == HKind::Translate ? TN_TRANSLATE : (h.kind == HKind::RotateY ? TN_ROTATE_Y : TN_TRANSFORM);
             rec.a = lower_tree(h.child, inner, depth + 1);
         } else if (h.kind == HKind::Medium) {
             f.media.push_back({h.neg_inv_density, h.material - 1, kNone, 0.0, 0.0, 0.0, 0.0});
@@ -845,14 +874,11 @@ struct Flattener {
             }
         }
         obj.xf_first = (uint32_t)f.xforms.size();
-        while (h->kind == HKind::Translate || h->kind == HKind::RotateY) {
-            if (h->kind == HKind::Translate)
-                f.xforms.push_back({h->offset.x, h->offset.y, h->offset.z, XF_TRANSLATE, 0});
-            else
-                f.xforms.push_back({h->sin_t, h->cos_t, 0.0, XF_ROTATE_Y, 0});
-            obj.xf_count++;
+        while (is_instance(h->kind)) {
+            push_step(f.xforms, *h);
             h = &s.hittables[h->child - 1];
         }
+        obj.xf_count = (uint32_t)f.xforms.size() - obj.xf_first;
         if (h->kind == HKind::Medium) {
             err = "unsupported nesting: ConstantMedium inside an instance transform";
             return kNone;
@@ -1354,7 +1380,8 @@ static void build_segment_tree(FlatScene &f, bool reference_tree_only)
 // lists, BvhNodes (in their sorted order) and Translate / RotateY, never through a ConstantMedium (its boundary is no surface).
 // `chain` = the instances above the primitive, outermost first; their forward transforms -- what the hit record goes through on
 // its way back to the world, R/Instance.h:53,137-147 -- are applied innermost first, in fp64, nothing fused (this file is built
-// with contraction off).  A RotateY turns points and vectors alike, a Translate moves points only.
+// with contraction off).  A RotateY turns points and vectors alike, a Translate moves points only, a Transform (rt_transform) takes
+// points through (L p) + t, vectors through L and the normal through Li^T, renormalised; under one, s is the transformed area.
 // ------------------------------------------------------------------------------------------------
 namespace {
 struct LightCollector {
@@ -1371,11 +1398,30 @@ struct LightCollector {
             const HostHittable &x = *chain[k];
             if (x.kind == HKind::Translate) {
                 if (point) p = add(p, x.offset);
-            } else {
+            } else if (x.kind == HKind::RotateY) {
                 p = mk((x.cos_t * p.x) + (x.sin_t * p.z), p.y, (-x.sin_t * p.x) + (x.cos_t * p.z));
+            } else {
+                const HostAffine &a = s.transforms[x.xf - 1];
+                p = point ? affine_point(a, p) : mat_rows(a.L, p);
             }
         }
         return p;
+    }
+    // a unit normal: a RotateY turns it, a Transform takes it through Li^T and renormalises it (include/rtow.h rt_transform)
+    D3 forward_normal(D3 n) const
+    {
+        for (size_t k = chain.size(); k-- > 0;) {
+            const HostHittable &x = *chain[k];
+            if (x.kind == HKind::RotateY) n = mk((x.cos_t * n.x) + (x.sin_t * n.z), n.y, (-x.sin_t * n.x) + (x.cos_t * n.z));
+            else if (x.kind == HKind::Transform) n = affine_normal(s.transforms[x.xf - 1], n);
+        }
+        return n;
+    }
+    bool chain_has_transform() const
+    {
+        for (const HostHittable *x : chain)
+            if (x->kind == HKind::Transform) return true;
+        return false;
     }
     static void put(double *dst, D3 v) { dst[0] = v.x; dst[1] = v.y; dst[2] = v.z; }
 
@@ -1390,6 +1436,7 @@ struct LightCollector {
         case HKind::Medium: return;
         case HKind::Translate:
         case HKind::RotateY:
+        case HKind::Transform:
             chain.push_back(&h);
             walk(h.child, leaf, depth + 1);
             chain.pop_back();
@@ -1422,8 +1469,9 @@ struct LightCollector {
             put(r.a, forward(h.q, true));
             put(r.b, forward(h.u, false));
             put(r.c, forward(h.v, false));
-            put(r.n, forward(h.normal, false));
-            area = length(cross(h.u, h.v));  // of the primitive as constructed: the instances are rigid
+            put(r.n, forward_normal(h.normal));
+            area = length(cross(h.u, h.v));  // of the primitive as constructed: Translate and RotateY are rigid
+            if (chain_has_transform()) area = length(cross(mk(r.b[0], r.b[1], r.b[2]), mk(r.c[0], r.c[1], r.c[2])));  // of the world-space row
             r.kind = LIGHT_QUAD;
             if (h.kind == HKind::Triangle) {
                 r.kind = LIGHT_TRIANGLE;
@@ -2327,6 +2375,113 @@ rt_handle rt_rotate_y(rt_scene *s, rt_handle object, double angle_degrees)
     h.box = box_from_corners(mk(mn[0], mn[1], mn[2]), mk(mx[0], mx[1], mx[2]));
     return push_h(S(s), std::move(h));
 }
+// An emissive Sphere / MovingSphere below `handle`, found as the light collector finds lights: never through a ConstantMedium.
+static bool holds_sphere_lamp(const SceneImpl &s, uint32_t handle, int depth)
+{
+    if (depth > 64) return false;  // (deeper than the light collector goes: the commit refuses such a graph)
+    const HostHittable &h = s.hittables[handle - 1];
+    switch (h.kind) {
+    case HKind::Medium: return false;
+    case HKind::Translate:
+    case HKind::RotateY:
+    case HKind::Transform: return holds_sphere_lamp(s, h.child, depth + 1);
+    case HKind::List:
+    case HKind::Bvh:
+        for (uint32_t c : h.items)
+            if (holds_sphere_lamp(s, c, depth + 1)) return true;
+        return false;
+    case HKind::Sphere:
+    case HKind::MovingSphere: return s.materials[h.material - 1].kind == MAT_DIFFUSE_LIGHT;
+    default: return false;
+    }
+}
+rt_handle rt_transform(rt_scene *s, rt_handle object, const double m[12])
+{
+    HostHittable *c = get_h(S(s), object);
+    if (!c || !m) {
+        set_error("rt_transform: invalid object handle or null matrix");
+        return 0;
+    }
+    HostAffine a{};
+    for (int r = 0; r < 3; r++) {
+        for (int k = 0; k < 3; k++) a.L[3 * r + k] = m[4 * r + k];
+        a.t[r] = m[4 * r + 3];
+    }
+    for (int k = 0; k < 12; k++)
+        if (!std::isfinite(m[k])) {
+            set_error("rt_transform: a matrix entry is not finite");
+            return 0;
+        }
+    // the inverse from cofactors over the determinant, in the order include/rtow.h states (this file: contraction off)
+    const double *L = a.L;
+    const double cf[9] = {(L[4] * L[8]) - (L[5] * L[7]), (L[5] * L[6]) - (L[3] * L[8]), (L[3] * L[7]) - (L[4] * L[6]),
+                          (L[2] * L[7]) - (L[1] * L[8]), (L[0] * L[8]) - (L[2] * L[6]), (L[1] * L[6]) - (L[0] * L[7]),
+                          (L[1] * L[5]) - (L[2] * L[4]), (L[2] * L[3]) - (L[0] * L[5]), (L[0] * L[4]) - (L[1] * L[3])};
+    const double det = ((L[0] * cf[0]) + (L[1] * cf[1])) + (L[2] * cf[2]);
+    if (!std::isfinite(det) || det == 0.0) {
+        set_error("rt_transform: the determinant is zero or not finite");
+        return 0;
+    }
+    for (int r = 0; r < 3; r++)
+        for (int k = 0; k < 3; k++) {
+            a.Li[3 * r + k] = cf[3 * k + r] / det;
+            if (!std::isfinite(a.Li[3 * r + k])) {
+                set_error("rt_transform: an entry of the inverse is not finite");
+                return 0;
+            }
+        }
+    if (holds_sphere_lamp(*S(s), object, 0)) {
+        set_error("rt_transform: the child holds an emissive Sphere or MovingSphere (an ellipsoid lamp; the light table cannot hold it)");
+        return 0;
+    }
+    HostHittable h{};
+    h.kind = HKind::Transform;
+    h.child = object;
+    const Box cb = c->box;
+    double mn[3] = {DBL_MAX, DBL_MAX, DBL_MAX}, mx[3] = {-DBL_MAX, -DBL_MAX, -DBL_MAX};
+    for (int i = 0; i < 2; i++)  // the eight corners forward, as rt_rotate_y
+        for (int j = 0; j < 2; j++)
+            for (int k = 0; k < 2; k++) {
+                const D3 p = affine_point(a, mk(i ? cb.hi[0] : cb.lo[0], j ? cb.hi[1] : cb.lo[1], k ? cb.hi[2] : cb.lo[2]));
+                for (int c2 = 0; c2 < 3; c2++) {
+                    mn[c2] = std::fmin(mn[c2], comp(p, c2));
+                    mx[c2] = std::fmax(mx[c2], comp(p, c2));
+                }
+            }
+    h.box = box_from_corners(mk(mn[0], mn[1], mn[2]), mk(mx[0], mx[1], mx[2]));
+    S(s)->transforms.push_back(a);
+    h.xf = (uint32_t)S(s)->transforms.size();
+    return push_h(S(s), std::move(h));
+}
+rt_handle rt_rotate_x(rt_scene *s, rt_handle object, double angle_degrees)
+{
+    const double radians = angle_degrees * 3.1415926535897932385 / 180.0;  // as rt_rotate_y
+    const double sn = std::sin(radians), cs = std::cos(radians);
+    const double m[12] = {1.0, 0.0, 0.0, 0.0, 0.0, cs, -sn, 0.0, 0.0, sn, cs, 0.0};
+    return rt_transform(s, object, m);
+}
+rt_handle rt_rotate_z(rt_scene *s, rt_handle object, double angle_degrees)
+{
+    const double radians = angle_degrees * 3.1415926535897932385 / 180.0;
+    const double sn = std::sin(radians), cs = std::cos(radians);
+    const double m[12] = {cs, -sn, 0.0, 0.0, sn, cs, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0};
+    return rt_transform(s, object, m);
+}
+rt_handle rt_scale(rt_scene *s, rt_handle object, double sx, double sy, double sz)
+{
+    const double m[12] = {sx, 0.0, 0.0, 0.0, 0.0, sy, 0.0, 0.0, 0.0, 0.0, sz, 0.0};
+    return rt_transform(s, object, m);
+}
+int rt_transform_get(rt_scene *s, rt_handle transform, double out21[21])
+{
+    HostHittable *h = get_h(S(s), transform);
+    if (!h || !out21 || h->kind != HKind::Transform) return fail(RT_ERR_INVALID, "rt_transform_get: not a Transform handle, or null output");
+    const HostAffine &a = S(s)->transforms[h->xf - 1];
+    std::memcpy(out21, a.L, 9 * sizeof(double));
+    std::memcpy(out21 + 9, a.t, 3 * sizeof(double));
+    std::memcpy(out21 + 12, a.Li, 9 * sizeof(double));
+    return RT_OK;
+}
 rt_handle rt_hittable_list(rt_scene *s, const rt_handle *objects, int count)
 {
     if (!s || count < 0 || (count > 0 && !objects)) {
@@ -2499,7 +2654,8 @@ int rt_scene_get_info(rt_scene *s, rt_scene_info *out)
     out->n_moving_spheres = (uint32_t)f.mspheres.size();
     out->n_quads = (uint32_t)f.quads.size();
     out->n_objects = (uint32_t)f.objects.size();
-    out->n_xforms = (uint32_t)f.xforms.size();
+    out->n_xforms = 0;  // steps: a Transform's kAffineRows rows are one
+    for (const Xform &x : f.xforms) out->n_xforms += x.kind != XF_AFFINE_ROW;
     out->n_media = (uint32_t)f.media.size();
     out->n_materials = (uint32_t)f.materials.size();
     out->n_textures = (uint32_t)f.textures.size();

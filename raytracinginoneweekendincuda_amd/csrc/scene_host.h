@@ -19,7 +19,12 @@ struct Box {  // R/AABB.h:16-22: three closed intervals
 };
 
 enum class HKind : uint8_t { Sphere, MovingSphere, Quad, Translate, RotateY, List, Bvh, Medium,
-                             Triangle };  // the quad's fields and plane constants; corners Q, Q + u, Q + v
+                             Triangle,    // the quad's fields and plane constants; corners Q, Q + u, Q + v
+                             Transform }; // a general affine instance (rt_transform): HostHittable::xf
+// The numbers of a Transform exactly as rt_transform stored them and as they are uploaded: x_world = L x_obj + t, Li = inverse of L.
+struct HostAffine {
+    double L[9], t[3], Li[9];  // L, Li row-major
+};
 
 struct HostHittable {
     HKind kind;
@@ -33,6 +38,7 @@ struct HostHittable {
     uint32_t child = 0;                // instance / medium: wrapped hittable handle
     D3 offset{};
     double sin_t = 0, cos_t = 0;
+    uint32_t xf = 0;                   // Transform: 1 + its row of SceneImpl::transforms
     std::vector<uint32_t> items;       // list children / bvh leaves (in sorted order, after build)
     double neg_inv_density = 0;
     // bvh topology (built at construction): nodes in preorder
@@ -125,6 +131,7 @@ struct SceneImpl {
     std::vector<HostMaterial> materials;
     std::vector<HostTexture> textures;
     std::vector<TriAttrRow> tri_attr;     // HostHittable::attr
+    std::vector<HostAffine> transforms;   // HostHittable::xf
     std::vector<ImageRec> images;
     std::vector<unsigned char> image_bytes;
     std::vector<PerlinRec> perlin;

@@ -302,8 +302,40 @@ extern "C" int rt_scene_build_builtin(rt_scene *s, int scene_id, int world_kind,
             cornell_view(view);
             break;
         }
+        case 14: {  // scene 7's walls, light and camera; four general affine instances (rt_transform) stand inside
+            CornellMaterials m = cornell_materials(w, 15.0);
+            list.push_back(w.Quad(Vector3(555, 0, 0), Vector3(0, 555, 0), Vector3(0, 0, 555), m.green));
+            list.push_back(w.Quad(Vector3(0, 0, 0), Vector3(0, 555, 0), Vector3(0, 0, 555), m.red));
+            list.push_back(w.Quad(Vector3(343, 554, 332), Vector3(-130, 0, 0), Vector3(0, 0, -105), m.light));
+            list.push_back(w.Quad(Vector3(0, 0, 0), Vector3(555, 0, 0), Vector3(0, 0, 555), m.white));
+            list.push_back(w.Quad(Vector3(555, 555, 555), Vector3(-555, 0, 0), Vector3(0, 0, -555), m.white));
+            list.push_back(w.Quad(Vector3(0, 0, 555), Vector3(555, 0, 0), Vector3(0, 555, 0), m.white));
+            // scene 13's icosphere with its corner normals, under one matrix: scale (1.1, 1.6, 0.8), then 25 degrees about Z, then a move
+            std::vector<Point3> vertices;
+            std::vector<int32_t> indices;
+            std::vector<Vector3> normals;
+            icosphere(2, 100.0, vertices, indices);
+            for (const Point3 &p : vertices) {
+                const double k = 1.0 / std::sqrt(p.x * p.x + p.y * p.y + p.z * p.z);
+                normals.push_back(Vector3(k * p.x, k * p.y, k * p.z));
+            }
+            const double rz = 25.0 * 3.1415926535897932385 / 180.0, cz = std::cos(rz), sz = std::sin(rz);
+            const double placed[12] = {cz * 1.1, -sz * 1.6, 0.0, 380.0, sz * 1.1, cz * 1.6, 0.0, 175.0, 0.0, 0.0, 0.8, 400.0};
+            list.push_back(w.Transform(w.TriangleMesh(vertices, indices, m.white, normals), placed));
+            // a MakeBox tilted about X
+            Hittable slab = w.MakeBox(Point3(0, 0, 0), Point3(150, 40, 150), w.Metal(Color(0.8, 0.85, 0.88), 0.0));
+            list.push_back(w.Translate(w.RotateX(slab, -20.0), Vector3(60, 60, 250)));
+            // a glass unit sphere scaled into an ellipsoid
+            Hittable glass = w.Sphere(Point3(0, 0, 0), 1.0, w.Dielectric(1.5));
+            list.push_back(w.Translate(w.Scale(glass, 90.0, 55.0, 70.0), Vector3(170, 200, 120)));
+            // a fog whose boundary is a scaled box
+            Hittable unit = w.MakeBox(Point3(0, 0, 0), Point3(1, 1, 1), m.white);
+            list.push_back(w.ConstantMedium(w.Translate(w.Scale(unit, 120.0, 200.0, 120.0), Vector3(330, 330, 60)), 0.01, Color(1.0, 1.0, 1.0)));
+            cornell_view(view);
+            break;
+        }
         default:
-            return rtow::fail(RT_ERR_INVALID, "rt_scene_build_builtin: scene_id must be 0..13");
+            return rtow::fail(RT_ERR_INVALID, "rt_scene_build_builtin: scene_id must be 0..14");
         }
 
         // R/kernel.cu:523-528: BvhNode(list, 0, i, ...) as world; "no BVH" = HittableList(list, i)
