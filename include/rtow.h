@@ -293,6 +293,19 @@ RTOW_API int rt_scene_dump_camera(rt_scene *s, double out27[27]);
  * that the fp32 filter decides has shared_out[k] as that centre coordinate, bit for bit, and the scan forms its terms once per ray;
  * 3: a general segment (shared_out[k] = 0).  The segments tile the rows exactly.  Host only.  Returns the segment count. */
 RTOW_API int rt_scene_dump_scan_segments(rt_scene *s, int max_segments, uint32_t *rows_axis_out, float *shared_out);
+/* The windows of those segments (csrc/scan_window_rule.h), tables beside them: per segment the window axis -- 0 x, 1 y, 2 z; 3: the
+ * segment has no table and is scanned whole, as every general segment and every run whose trips are not selective is -- and the
+ * slab {lo, hi} of the run's decided rows on the run's own axis; per trip of eight rows of the whole table the span {lo, hi} of its
+ * decided rows on the window axis: (-inf, +inf) for a trip with a row the fp32 filter does not decide and outside the windowed runs,
+ * (+inf, -inf) for a trip of padding alone.  A pixel-parallel pass runs, of a windowed run, the trips whose span meets the union of
+ * its rays' extents inside the slab (gaps of one or two trips filled).  Host only.  Returns the segment count (negative: error);
+ * writes min(segments, max_segments) records and min(trips, max_trips) spans where the arrays are given. */
+RTOW_API int rt_scene_dump_scan_windows(rt_scene *s, int max_segments, uint32_t *axis_out, float *slab_out, int max_trips, float *spans_out);
+/* The same rule for caller-supplied rays, one at a time, as the device evaluates it: needed_out[k * max_trips + t] = 1 where trip t
+ * must run for ray k (origin and direction: n_rays x 3), 0 where the rule proves that the reference's Sphere::Hit accepts no decided
+ * row of the trip over (0.001, inf).  Trips outside the windowed runs are always 1, entries from the table's trips on 0.  Host only.
+ * Returns the table's trips (negative: error; max_trips must not be below them where needed_out is given). */
+RTOW_API int rt_scene_scan_window_trips(rt_scene *s, int n_rays, const double *origin, const double *direction, int max_trips, uint8_t *needed_out);
 /* The camera rays' candidate lists of a sphere-list world, as a launch on a film of this geometry builds them on the device (same
  * rule, csrc/primary_cull_rule.h): per 8x8 tile of the rank's rows, row-major over its compact rows, 16 uint16 -- [0] the number
  * of listed spheres, 0..14, or 15: too many, the tile has no list; [1..count] their positions in the sphere list, ascending.  A
@@ -393,6 +406,12 @@ typedef struct rt_render_params {
                                       scans one ray per lane, camera rays are tested against the short list of spheres that a ray through
                                       their 8x8 tile can reach, in list order, with the reference's test; the image is the same bit for
                                       bit either way) -- tests, timing */
+#define RT_FLAG_NO_SCAN_WINDOWS 8192u /* sphere-list worlds: a pixel-parallel pass scans every trip of every run of the list (default: of a
+                                      run whose trips are selective along an axis, only the trips that the pass's rays can reach while
+                                      they are inside the run's slab, csrc/scan_window_rule.h; the image is the same bit for bit
+                                      either way).  With the flag a launch runs the scan as it was before the windows, entered by the
+                                      lanes that hold a ray; without it, where the scene has a window table, all 64 lanes of a wave
+                                      enter the scan, idle lanes with a filter term that passes no sphere -- tests, timing */
 #define RT_FLAG_ACCELERATE_LISTS 512u /* HittableList worlds of primitives only (no leaf draws random numbers): render through the library's
                                       own tree as a BvhNode world would be -- the reference's "BVH image == list image" invariant the other
                                       way round; off by default so that a list world is scanned as the reference scans it.  Ignored for
@@ -495,16 +514,16 @@ typedef struct rt_launch_plan {
      * 0xFFFFFFFF = the kernel reads it from global memory; lds_table_bytes[k] = the table's unpadded size, 0 for an empty table and
      * for one this instantiation never considers. */
     int32_t lds_front_bytes;
-    uint32_t lds_table_offset[17], lds_table_bytes[17];
+    uint32_t lds_table_offset[18], lds_table_bytes[18];
     /* The rehearsal's samples: probe_keeps = 1 where the frame launch resumes from them (it renders samples_per_pixel - probe_spp
      * more of every pixel), 0 where it renders every sample again (adaptive films) and where there is no rehearsal.  probe_ray_cap:
      * rays at which a rehearsed pixel stops at once, its place on the longest-chain list being decided (super_threshold; 0: no
      * cap) -- such a pixel keeps nothing and the frame launch renders all of its samples. */
     int32_t probe_keeps, probe_ray_cap;
 } rt_launch_plan;
-#define RT_LDS_TABLES 17
+#define RT_LDS_TABLES 18
 #define RT_LDS_TABLE_NAMES "quad_aa boxes objects xforms media materials perlin spheres_tab group_boxes mspheres msphere_aux " \
-                           "sphere_aux fast_order seg_media seg_cand park scan_pairs"
+                           "sphere_aux fast_order seg_media seg_cand park scan_pairs scan_spans"
 RTOW_API int rt_plan_launch(rt_scene *s, const rt_render_params *params, int num_cus, int adaptive, rt_launch_plan *out);
 /* Introspection for tests: the rays the rehearsal of the film's last launch booked for every pixel, full W x H like
  * rt_film_download_sample_counts -- at least rt_launch_plan.probe_ray_cap for a pixel the cap stopped.  RT_ERR_STATE where that

@@ -186,7 +186,11 @@ def main():
             headers = []
             for i in range(lo, hi):
                 m = LABEL.match(lines[i])
-                if m and i + 1 < hi and "Loop Header" in " ".join(lines[i:i + 3]):
+                # (the label's own comment block: one "Parent Loop" line per level of nesting, then the header's)
+                j = i + 1
+                while j < hi and "Parent Loop" in lines[j] and not LABEL.match(lines[j]):
+                    j += 1
+                if m and i + 1 < hi and "Loop Header" in " ".join(lines[i:j + 1]):
                     headers.append(m.group(1))
             for header in headers:
                 path, notes = quiet_trip(lines, lo, hi, header, headers)

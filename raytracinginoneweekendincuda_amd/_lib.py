@@ -226,13 +226,13 @@ class LaunchPlan(C.Structure):
         "node_burst", "park_ratio", "leaf_batch", "object_batch", "rounds", "shade_batch", "ray_budget",
         "rank_tiles", "pixel_classes", "probe_spp", "tile_flatness_x8", "heavy_threshold", "super_threshold",
         "near_percent", "near_neighbours", "heavy_waves", "heavy_ppw", "super_ppw", "heavy_priority", "adaptive_ppw",
-        "lds_front_bytes")] + [("lds_table_offset", C.c_uint32 * 17), ("lds_table_bytes", C.c_uint32 * 17),
+        "lds_front_bytes")] + [("lds_table_offset", C.c_uint32 * 18), ("lds_table_bytes", C.c_uint32 * 18),
                                ("probe_keeps", C.c_int32), ("probe_ray_cap", C.c_int32)]
 
 
 # the order of rt_launch_plan.lds_table_offset / lds_table_bytes (include/rtow.h RT_LDS_TABLE_NAMES, csrc/launch_plan.h LdsTable)
 LDS_TABLES = ("quad_aa", "boxes", "objects", "xforms", "media", "materials", "perlin", "spheres_tab", "group_boxes", "mspheres",
-              "msphere_aux", "sphere_aux", "fast_order", "seg_media", "seg_cand", "park", "scan_pairs")
+              "msphere_aux", "sphere_aux", "fast_order", "seg_media", "seg_cand", "park", "scan_pairs", "scan_spans")
 LDS_GLOBAL = 0xFFFFFFFF   # lds_table_offset of a table the kernel reads from global memory
 
 
@@ -320,6 +320,8 @@ SIGNATURES = {
     "rt_scene_dump_fast_nodes": (I, [P, I, D3, C.POINTER(C.c_uint32), C.POINTER(C.c_uint16)]),
     "rt_scene_dump_camera": (I, [P, D3]),
     "rt_scene_dump_scan_segments": (I, [P, I, C.POINTER(C.c_uint32), C.POINTER(C.c_float)]),
+    "rt_scene_dump_scan_windows": (I, [P, I, C.POINTER(C.c_uint32), C.POINTER(C.c_float), I, C.POINTER(C.c_float)]),
+    "rt_scene_scan_window_trips": (I, [P, I, C.POINTER(C.c_double), C.POINTER(C.c_double), I, C.POINTER(C.c_uint8)]),
     "rt_scene_dump_primary_lists": (I, [P, I, I, I, I, I, I, C.POINTER(C.c_uint16)]),
     "rt_scene_dump_lights": (I, [P, I, C.POINTER(C.c_int), C.POINTER(C.c_int), P, D3]),
     "rt_stripe_rows": (I, [I, I, I, I, C.POINTER(C.c_int), I]),

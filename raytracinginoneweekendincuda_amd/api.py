@@ -38,6 +38,7 @@ FLAG_EXACT_SCAN = 256       # sphere-list worlds: the reference's discriminant f
 FLAG_REFERENCE_TREE = 128   # primitive BVH worlds: walk the reference's own tree (default: the library's SAH tree)
 FLAG_FILTER_FP64 = 2048     # sphere-list worlds: the fp64 filter instead of its packed fp32 form (tests, timing)
 FLAG_COOP_SINGLE = 1024     # tests: sphere-list worlds, thin waves scan one ray at a time (the older scheme)
+FLAG_NO_SCAN_WINDOWS = 8192  # sphere-list worlds: a pass scans every trip of every run (default: the trips its rays can reach; tests, timing)
 FLAG_NO_PRIMARY_LISTS = 4096  # sphere-list worlds: camera rays scan the whole list too (default: their tile's candidate list; tests, timing)
 FLAG_NO_PIXEL_CLASSES = 64  # sphere-list worlds: one launch for all pixels (no separate launch for the long-chain pixels)
 
@@ -381,6 +382,39 @@ class Scene:
         shared = np.zeros(max(n, 1), dtype=np.float32)
         lib().rt_scene_dump_scan_segments(self._p, n, rows.ctypes.data_as(C.POINTER(C.c_uint32)), shared.ctypes.data_as(C.POINTER(C.c_float)))
         return [(int(r[0]), int(r[1]), None if r[2] == 3 else int(r[2]), shared[k]) for k, r in enumerate(rows[:n])]
+
+    def scan_windows(self):
+        """Tests: the windows of the sphere-list scan's segments (rt_scene_dump_scan_windows; no device needed): a list with one
+        entry per segment of scan_segments() -- None for a segment without a table, else (window axis, slab lo, slab hi) -- and
+        the spans of all trips of the table as a float32 array (trips, 2)."""
+        n = lib().rt_scene_dump_scan_windows(self._p, 0, None, None, 0, None)
+        if n < 0:
+            raise RtowError(_err())
+        trips = lib().rt_scene_scan_window_trips(self._p, 0, None, None, 0, None)
+        if trips < 0:
+            raise RtowError(_err())
+        axis = np.zeros(max(n, 1), dtype=np.uint32)
+        slab = np.zeros((max(n, 1), 2), dtype=np.float32)
+        spans = np.zeros((max(trips, 1), 2), dtype=np.float32)
+        fp = C.POINTER(C.c_float)
+        lib().rt_scene_dump_scan_windows(self._p, n, axis.ctypes.data_as(C.POINTER(C.c_uint32)), slab.ctypes.data_as(fp), trips, spans.ctypes.data_as(fp))
+        return [None if axis[k] == 3 else (int(axis[k]), slab[k, 0], slab[k, 1]) for k in range(n)], spans[:trips]
+
+    def scan_window_trips(self, origins, directions):
+        """Tests: the window rule for rays, one at a time, as the device evaluates it (rt_scene_scan_window_trips; no device
+        needed): a bool array (rays, trips), True where the trip must run for the ray.  Trips outside windowed runs are True."""
+        o = np.ascontiguousarray(origins, dtype=np.float64).reshape(-1, 3)
+        d = np.ascontiguousarray(directions, dtype=np.float64).reshape(-1, 3)
+        if o.shape != d.shape:
+            raise ValueError("origins and directions must have the same shape")
+        trips = lib().rt_scene_scan_window_trips(self._p, 0, None, None, 0, None)
+        if trips < 0:
+            raise RtowError(_err())
+        out = np.zeros((o.shape[0], max(trips, 1)), dtype=np.uint8)
+        dp = C.POINTER(C.c_double)
+        if lib().rt_scene_scan_window_trips(self._p, o.shape[0], o.ctypes.data_as(dp), d.ctypes.data_as(dp), max(trips, 1), out.ctypes.data_as(C.POINTER(C.c_uint8))) < 0:
+            raise RtowError(_err())
+        return out[:, :trips].astype(bool)
 
     def primary_lists(self, width, height, stripe_rows=8, rank=0, world_size=1):
         """Tests: the camera rays' candidate lists of a sphere-list world for a film of this geometry (rt_scene_dump_primary_lists;

@@ -39,6 +39,7 @@ struct DeviceTables {
     DeviceArena memory;       // every table below
     DeviceScene scene{};
     const uint32_t *node_leaf_pos = nullptr;  // ray queries (rt_scene_intersect_device): FlatScene::node_leaf_pos
+    bool scan_windows = false;  // sphere-list frames: some run of the scan has a window table (FlatScene::scan_windows)
     // light sampling queries (rt_scene_sample_lights_device): FlatScene::lights and its two cumulative tables
     const LightRow *lights = nullptr;
     const double *light_cdf[2] = {nullptr, nullptr};
@@ -326,6 +327,9 @@ int rt_scene_upload(rt_scene *scene, int device)
             at += sg.n_trips;
         }
         if (!tiled || at != trips) return fail(RT_ERR_STATE, "rt_scene_upload: the scan segments do not tile the sphere table");
+        // ... and its windows are read by segment and by trip index: a table is whole or absent
+        if (!f.scan_windows.empty() && (f.scan_windows.size() != f.scan_segments.size() || f.scan_trip_spans.size() != trips))
+            return fail(RT_ERR_STATE, "rt_scene_upload: the scan windows do not match the scan segments");
     }
     // The hit record reads quads[AAQuad::pad] for a marked triangle (render.hip vertex_attr): every mark must name an attribute row.
     for (const AAQuad &a : f.quad_aa)
@@ -342,7 +346,28 @@ int rt_scene_upload(rt_scene *scene, int device)
     up(f.spheres, d.spheres);
     up(f.sphere_scan, d.sphere_scan);
     up(f.sphere_scan32, d.sphere_scan32);
-    up(f.scan_segments, d.scan_segments);
+    {
+        // The scan segments and, directly behind them in the one allocation, the windows of the runs: a ScanWindowSeg per segment, then
+        // a ScanTripSpan per trip (flat_scene.h).  The scan reaches the windows from the segments' pointer (render.hip scan_filtered32:
+        // no register of its own across the loops), and only where a launch says that the scene has them.
+        static_assert(sizeof(ScanWindowSeg) == sizeof(ScanSegment) && sizeof(ScanSegment) == 16 && sizeof(ScanTripSpan) == 8, "the windows are addressed in segment records");
+        const size_t ns = f.scan_segments.size(), bytes = 2 * ns * sizeof(ScanSegment) + f.scan_trip_spans.size() * sizeof(ScanTripSpan);
+        std::vector<unsigned char> table(bytes);
+        if (ns) std::memcpy(table.data(), f.scan_segments.data(), ns * sizeof(ScanSegment));
+        if (!f.scan_windows.empty()) {
+            std::memcpy(table.data() + ns * sizeof(ScanSegment), f.scan_windows.data(), ns * sizeof(ScanWindowSeg));
+            std::memcpy(table.data() + 2 * ns * sizeof(ScanSegment), f.scan_trip_spans.data(), f.scan_trip_spans.size() * sizeof(ScanTripSpan));
+        } else {
+            for (size_t k = 0; k < ns; k++) {
+                const ScanWindowSeg none{kScanAxisNone, 0.0f, 0.0f, 0u};
+                std::memcpy(table.data() + (ns + k) * sizeof(ScanSegment), &none, sizeof none);
+            }
+        }
+        const unsigned char *dev = nullptr;
+        up(table, dev);
+        d.scan_segments = reinterpret_cast<const ScanSegment *>(dev);
+        dt->scan_windows = !f.scan_windows.empty();
+    }
     up(f.sphere_aux, d.sphere_aux);
     up(f.mspheres, d.mspheres);
     up(f.ms_planes, d.ms_planes);
@@ -752,6 +777,7 @@ static int enqueue_frame(SceneImpl &s, FilmImpl &f, const rt_render_params *p, h
     if (int rc = enqueue_frame_begin(f, p, ra, stream)) return rc;
     const rt_launch_plan plan = plan_launch(ds, f.geometry, f.num_cus, *p, f.adaptive, hits_stay_in_boxes(s.flat, s.camera, p->variant));
     fill_render_args(f, p, plan, ra);
+    ra.scan_windows = !(p->flags & RT_FLAG_NO_SCAN_WINDOWS) && s.device[f.device]->scan_windows ? 1 : 0;  // sphere lists: the windows of the scan's runs
     KernelInfo info{};
     HIP_TRY(build.info(plan.kernel, ds, ra, &info));  // the registers the compiler gave it; the rest is the plan's
     if (info.kind != plan.kernel_kind || info.lds_bytes != plan.lds_bytes)
@@ -934,6 +960,13 @@ static void print_phases(const FilmImpl &f)
             std::fprintf(stderr, "primary: %llu rounds, %.2f fresh lanes per round, %.2f list entries tested per round (%.2f per lane), %.0f cycles per round "
                          "(%.1f %% of wave time)\n", c[96 + 23], (double)c[64 + 23] / c[96 + 23], (double)c[32 + 15] / c[96 + 23],
                          (double)c[32 + 15] / (double)c[64 + 23], (double)c[32 + 23] / c[96 + 23], 100.0 * c[32 + 23] / (double)c[7]);
+        // slots 14 and 7: the windows of the pixel-parallel scan's runs (render.hip ScanSums win_*).  Both are per-lane slots, which the
+        // flush sums over the wave and scales by 1 / 1024: the counts come back times 64 / 1024, the ratios as they are.
+        name[14] = name[7] = "";
+        if (c[96 + 7])
+            std::fprintf(stderr, "window: %llu windowed passes (%llu windowed runs), %.2f trips scanned per pass in them, %.2f ranges per pass, %.0f cycles "
+                         "of window computation per pass\n", c[96 + 7] * 16ull, c[96 + 14] * 16ull, (double)c[64 + 14] / c[96 + 7], (double)c[64 + 7] / c[96 + 7],
+                         (double)c[32 + 14] / c[96 + 7]);
         name[16] = name[17] = name[18] = "";  // slots 16, 17, 18: the counts of the grouped scan (render.hip GroupedSums)
         const double gp = (double)c[96 + 16];
         if (gp > 0) {

@@ -57,6 +57,13 @@ constexpr uint32_t kScanAxisNone = 3u;
 // A switch of segments costs the wave about ten instructions and a trip of a run saves eight, so a run pays from two trips on;
 // four leaves a margin and keeps lists that only happen to repeat a coordinate here and there on the one loop they run today.
 constexpr uint32_t kScanRunMinTrips = 4u;
+// The windows of the runs (scan_window_rule.h; scene_builder.cpp build_scan_windows), tables parallel to the two above and never a
+// part of them.  One record per segment, 16 bytes, one scalar load: the window axis -- kScanAxisNone: the segment has no table
+// (every general segment, and the runs whose trips are not selective) and is scanned whole -- and the slab of the run's decided
+// rows on the run's own axis.  One span per trip of the whole table, by trip index: the extent of the trip's decided rows on the
+// window axis; (-inf, +inf) for a trip with an undecided row and outside the windowed runs, (+inf, -inf) for padding alone.
+struct ScanWindowSeg { uint32_t axis; float slab_lo, slab_hi; uint32_t pad; };
+struct ScanTripSpan { float lo, hi; };
 struct SphereAux { double inv_r; uint32_t mat; uint32_t pad; };
 
 // MovingSphere (R/MovingSphere.h:19-36): centre(t) = c0 + ((t - t0) / dt) * dc
@@ -298,6 +305,7 @@ struct DeviceScene {
     uint32_t n_spheres, n_mspheres, n_quads, n_objects, n_boxes, n_xforms;
     uint32_t n_media, n_materials, n_perlin, n_group_boxes;
     uint32_t n_scan_segments;
+    uint32_t n_scan_window_trips;  // trips of the scan's window tables (ScanTripSpan rows behind the segments): 0 where no run has a table
     // Tables a leaf test or the shading chases through -- object record -> transforms -> box / quad rows, medium rows,
     // material rows, Perlin tables -- are staged in LDS behind the node rows where they fit.  Byte offsets into the
     // dynamic LDS block, set by the launcher per table; kNone = read the global table.
@@ -305,6 +313,7 @@ struct DeviceScene {
         lds_mspheres, lds_msphere_aux, lds_sphere_aux;  // the primitive tables of a sphere world (library-tree kernel, one workgroup per CU)
     uint32_t lds_fast_order, lds_seg_media, lds_seg_cand;  // segmented walk: always staged (launch_plan.cpp lds_layout)
     uint32_t lds_park;  // parked path state of the instanced-list kernel (render.hip Traits::PARK)
+    uint32_t lds_scan_spans;  // sphere-list kernel: the window spans of the scan's trips (ScanTripSpan), behind the packed rows (kNone: read from global memory)
     uint32_t lds_scan_pairs;  // sphere-list kernel: the packed fp32 rows of the grouped scan, behind the planes (kNone: its filter stays fp64)
     uint32_t flags;
 };

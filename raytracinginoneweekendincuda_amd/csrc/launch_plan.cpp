@@ -123,6 +123,14 @@ LdsLayout lds_layout(const KernelProps &k, const DeviceScene &sc)
             lds += pair_rows;
             l.table_bytes[T_SCAN_PAIRS] = (uint32_t)pair_rows;
         }
+        // the window spans of the scan's trips (scan_window_rule.h; render.hip scan_filtered32 reads one per lane and chunk of 64 trips),
+        // 8 B a trip, where some run of the scene has a table: with the planes, under the same budget (C2: 61 trips, 488 B)
+        const size_t span_rows = (size_t)sc.n_scan_window_trips * 8;
+        l.table_bytes[T_SCAN_SPANS] = (uint32_t)span_rows;
+        if (l.lds_spheres && span_rows && up16(lds) + span_rows <= kSharedCuBudget) {
+            l.scan_spans = (uint32_t)up16(lds);
+            lds = up16(lds) + span_rows;
+        }
     }
     if (k.park) {  // the parked path state, one entry per thread (list worlds stage no tables: their rows come through scalar loads)
         off = up16(lds);
@@ -156,6 +164,7 @@ void scene_counts(const FlatScene &f, DeviceScene &d)
     d.n_perlin = (uint32_t)f.perlin.size();
     d.n_group_boxes = (uint32_t)f.group_boxes.size();
     d.n_scan_segments = (uint32_t)f.scan_segments.size();
+    d.n_scan_window_trips = (uint32_t)f.scan_trip_spans.size();
     d.flags = f.flags;
     apply_layout(LdsLayout{}, d);  // nothing is staged until a launch lays its LDS out
 }
@@ -439,7 +448,7 @@ static void show_layout(const LdsLayout &l, rt_launch_plan &plan)
 {
     const uint32_t offsets[kLdsTables] = {l.quad_aa, l.boxes, l.objects, l.xforms, l.media, l.materials, l.perlin, l.spheres_tab,
                                           l.group_boxes, l.mspheres, l.msphere_aux, l.sphere_aux, l.fast_order, l.seg_media, l.seg_cand, l.park,
-                                          l.scan_pairs};
+                                          l.scan_pairs, l.scan_spans};
     plan.lds_front_bytes = (int)l.front;
     for (int t = 0; t < kLdsTables; t++) {
         plan.lds_table_offset[t] = offsets[t];

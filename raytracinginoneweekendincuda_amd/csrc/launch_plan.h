@@ -118,6 +118,7 @@ struct LdsLayout {
     uint32_t fast_order = kNone, seg_media = kNone, seg_cand = kNone;
     uint32_t park = 0;
     uint32_t scan_pairs = kNone;
+    uint32_t scan_spans = kNone;
     int lds_nodes = 0, lds_spheres = 0;  // RenderArgs::lds_nodes, ::lds_spheres
     size_t bytes = 0;                    // dynamic LDS of the launch (the render kernels have no static LDS)
     bool fits = true;                    // everything this instantiation reads from LDS only is staged
@@ -129,7 +130,7 @@ struct LdsLayout {
 // The slots of LdsLayout in the order rt_launch_plan lists them (include/rtow.h RT_LDS_TABLE_NAMES).
 enum LdsTable : int {
     T_QUAD_AA, T_BOXES, T_OBJECTS, T_XFORMS, T_MEDIA, T_MATERIALS, T_PERLIN, T_SPHERES_TAB, T_GROUP_BOXES, T_MSPHERES, T_MSPHERE_AUX,
-    T_SPHERE_AUX, T_FAST_ORDER, T_SEG_MEDIA, T_SEG_CAND, T_PARK, T_SCAN_PAIRS,
+    T_SPHERE_AUX, T_FAST_ORDER, T_SEG_MEDIA, T_SEG_CAND, T_PARK, T_SCAN_PAIRS, T_SCAN_SPANS,
     kLdsTables,
 };
 static_assert(kLdsTables == RT_LDS_TABLES, "rt_launch_plan lists another number of tables than LdsLayout has slots");
@@ -142,6 +143,7 @@ inline void apply_layout(const LdsLayout &l, DeviceScene &sc)
     sc.lds_mspheres = l.mspheres; sc.lds_msphere_aux = l.msphere_aux; sc.lds_sphere_aux = l.sphere_aux;
     sc.lds_fast_order = l.fast_order; sc.lds_seg_media = l.seg_media; sc.lds_seg_cand = l.seg_cand; sc.lds_park = l.park;
     sc.lds_scan_pairs = l.scan_pairs;
+    sc.lds_scan_spans = l.scan_spans;
 }
 
 // ---- 3. The kernel choice ----

@@ -32,6 +32,7 @@
 #include "flat_scene.h"
 #include "launch_plan.h"
 #include "primary_cull_rule.h"
+#include "scan_window_rule.h"
 #include "render_iface.h"
 #include "rng.h"
 
@@ -526,6 +527,7 @@ struct PhaseSums {
 struct ScanSums {
     uint32_t groups, taken, spheres, appends, behind;  // groups of 4 examined / taken; spheres with a passing lane; lane appends; lanes behind
     uint32_t drains, drain_iters, drain_cycles;        // drain calls; wave max of count per call, summed; cycles spent draining
+    uint32_t win_runs, win_trips, win_ranges, win_cycles;  // windowed runs scanned; trips and ranges of trips run in them; cycles of forming the windows
 };
 #define SS_ARG , ScanSums &ss
 #define SS_PASS , ss
@@ -2065,9 +2067,59 @@ DEV void scan_swap(v2f &a, v2f &b) { const v2f t = a; a = b; b = t; }
 // entries: true at the start, kept by a trip that appends nothing, and restored by the drain test that follows every trip in
 // which some lane passed a sphere.  A trip appends at most kFilterTrip entries per lane, so a lane writes its slot `count` only
 // while count < kQueueCap.
-template <bool ROWS_IN_LDS>
-DEV bool scan_filtered32(const DeviceScene &sc, uint32_t planes_off, uint32_t n_padded, uint16_t *queue, uint32_t lane, const Ray &r, double tmin,
-                         double tmax, HitInfo &best SS_ARG)
+//
+// Windows (r29; scan_window_rule.h), the WINDOWS instantiation: a launch takes it where some run of the scene has a window table and
+// RT_FLAG_NO_SCAN_WINDOWS is not set; every other launch takes the other instantiation, which is the scan as it was before r29,
+// called by the live lanes only.  With WINDOWS all 64 lanes come here and `live` says which of them hold a ray: the others get
+// a filter addend of -inf, so that their Q is -inf or NaN and passes no row (k = -inf included: -inf > -inf is false); they
+// append nothing and drain nothing, and every ballot, the drain test's too, is what it is when only the live lanes come.  In a
+// run whose window record names an axis (the records lie behind the segment records, the spans behind those: no pointer of
+// their own is carried through the loops) every lane forms the extent of its ray on that axis inside the run's slab, the wave
+// unites them (two DPP reductions), lane t tests trip t of a chunk of 64 against the union, and the ballot, its short gaps
+// filled, is the set of trips to run: `off` and `end` are set per range of set bits, set A is read afresh where `off` jumps,
+// and behind the run `off` stands at its end with set A of whatever follows.  The spans are read from their LDS copy where the
+// launch staged one (with the sphere planes: launch_plan.cpp lds_layout), else from global memory: 8 bytes a lane, one read a
+// chunk, issued ahead of the extents' arithmetic.  A run without a table keeps
+// the loop it had, in a copy of its own.  A range comes from set bits of lanes below the chunk's number of trips and nowhere
+// else, so first <= last < n_trips, and a range is never empty: the loop's `off != end` test is reached with off < end only.
+// Survivors reach the queues in ascending list position as before, and the queue bound above holds verbatim.
+DEV ScanWindowSeg load_scan_window(const ScanWindowSeg *table, uint32_t k)
+{
+    const RT_CONST uint32_t *p = (const RT_CONST uint32_t *)(uintptr_t)(table + k);
+    return ScanWindowSeg{p[0], __builtin_bit_cast(float, p[1]), __builtin_bit_cast(float, p[2]), p[3]};
+}
+// The span of trip t: from the LDS copy where the launch staged one (launch_plan.cpp lds_layout), else from behind the segment records.
+DEV ScanTripSpan load_scan_span(const DeviceScene &sc, uint32_t t)
+{
+    if (sc.lds_scan_spans != kNone && sc.lds_scan_spans != 0u) {
+        const v2f v = *(const RT_LDS v2f *)(lds_raw + sc.lds_scan_spans + t * (uint32_t)sizeof(ScanTripSpan));
+        return ScanTripSpan{v.x, v.y};
+    }
+    return reinterpret_cast<const ScanTripSpan *>(sc.scan_segments + 2u * sc.n_scan_segments)[t];
+}
+template <int CTRL, int ROW_MASK>
+DEV void fmin_step(float &x, float &y)
+{
+    const float ox = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, x), __builtin_bit_cast(int, x), CTRL, ROW_MASK, 0xf, false));
+    const float oy = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, y), __builtin_bit_cast(int, y), CTRL, ROW_MASK, 0xf, false));
+    x = __builtin_fminf(x, ox);
+    y = __builtin_fminf(y, oy);
+}
+// Wave-wide minimum of x and of y (neither is ever NaN), as scalars: the steps of wave_min.  All 64 lanes must be enabled.
+DEV void wave_fmin2(float &x, float &y)
+{
+    fmin_step<0xB1, 0xf>(x, y);
+    fmin_step<0x4E, 0xf>(x, y);
+    fmin_step<0x114, 0xf>(x, y);
+    fmin_step<0x118, 0xf>(x, y);
+    fmin_step<0x142, 0xa>(x, y);
+    fmin_step<0x143, 0xc>(x, y);
+    x = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), 63));
+    y = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, y), 63));
+}
+template <bool ROWS_IN_LDS, bool WINDOWS>
+DEV bool scan_filtered32(const DeviceScene &sc, bool live, uint32_t planes_off, uint32_t n_padded, uint16_t *queue, uint32_t lane,
+                         const Ray &r, double tmin, double tmax, HitInfo &best SS_ARG)
 {
     static_assert(kFilterTrip == 2 * kScanTripPairs && kScanAheadPairs == 2, "one trip = four pairs in two halves; set A of the next trip is read ahead");
     constexpr uint32_t kPairBytes = (uint32_t)sizeof(SphereScanPair), kTripBytes = kScanTripPairs * kPairBytes;
@@ -2077,6 +2129,8 @@ DEV bool scan_filtered32(const DeviceScene &sc, uint32_t planes_off, uint32_t n_
     const uint32_t n_segments = sc.n_scan_segments;  // they tile the table's trips in order (scene_builder.cpp cut_scan_segments)
     const double a = dot(r.d, r.d);
     ScanRayPairs f = scan_ray_pairs(scan_ray32(r, a, sc.scan_reach32));
+    if constexpr (WINDOWS)
+        if (!live) f.nt = v2f{-__builtin_inff(), -__builtin_inff()};
     double closest = tmax;
     uint32_t best_k = kNone, count = 0;
     if (n_segments) {
@@ -2089,14 +2143,90 @@ DEV bool scan_filtered32(const DeviceScene &sc, uint32_t planes_off, uint32_t n_
                 do scan_trip<false, ROWS_IN_LDS>(rows, spheres, off, end, a0, a1, f, f.ux, f.nt, planes_off, n_padded, queue, lane, count, r, a, tmin, closest, best_k SS_PASS);
                 while (off != end);
             } else {
+                const uint32_t seg_end = end;
+                bool windowed = false;  // the run has a window table, and x0, x1 hold the wave's window
+                float x0 = 0.0f, x1 = 0.0f;  // the union of the wave's extents on the window axis
+                uint32_t chunk = sg.first_trip;  // the first trip of the chunk of 64 that `need` speaks of
+                unsigned long long need = 0;     // that chunk's trips still to run
+                if constexpr (WINDOWS) {
+                    // the window records lie directly behind the segment records, the spans behind those (device_scene.cpp rt_scene_upload)
+                    const ScanWindowSeg *windows = reinterpret_cast<const ScanWindowSeg *>(segments + n_segments);
+                    const ScanWindowSeg ws = load_scan_window(windows, seg);
+                    const uint32_t window_axis = ws.axis;
+                    windowed = window_axis != kScanAxisNone;
+                    if (windowed) {
+#if RT_PHASES
+                        const unsigned long long ss_w0 = __builtin_readcyclecounter();
+#endif
+                        // lane t's trip of the run's first chunk, read ahead of the extents' arithmetic
+                        const bool in_run = lane < sg.n_trips;
+                        ScanTripSpan sp{0.0f, 0.0f};
+                        if (in_run) sp = load_scan_span(sc, sg.first_trip + lane);
+                        float e0 = __builtin_inff(), e1 = __builtin_inff();  // min of lo, min of -hi: no ray, the empty extent
+                        if (live) {
+                            const double oa = sg.axis == 0u ? r.o.x : (sg.axis == 1u ? r.o.y : r.o.z), da = sg.axis == 0u ? r.d.x : (sg.axis == 1u ? r.d.y : r.d.z);
+                            const double ow = window_axis == 0u ? r.o.x : (window_axis == 1u ? r.o.y : r.o.z), dw = window_axis == 0u ? r.d.x : (window_axis == 1u ? r.d.y : r.d.z);
+                            const ScanExtent ex = scan_window_extent(oa, da, ow, dw, __builtin_fabs(r.o.x) + __builtin_fabs(r.o.y) + __builtin_fabs(r.o.z), a, sc.scan_reach32, (double)ws.slab_lo, (double)ws.slab_hi);
+                            e0 = (float)ex.lo;
+                            e1 = -(float)ex.hi;
+                        }
+                        wave_fmin2(e0, e1);
+                        x0 = e0;
+                        x1 = -e1;
+                        need = scan_window_fill(__ballot(in_run && scan_window_needs(sp.lo, sp.hi, x0, x1)));
+#if RT_PHASES
+                        asm volatile("" ::"s"(x0), "s"(x1));
+                        ss.win_cycles += (uint32_t)(__builtin_readcyclecounter() - ss_w0);
+                        ss.win_runs++;
+#endif
+                    }
+                }
                 // The ray's terms for the run's two varying coordinates go where the rows keep those (flat_scene.h ScanSegment),
                 // the shared coordinate's to the middle slot, and back behind the run.
                 if (sg.axis == 0u) { scan_swap(f.ux, f.uy); scan_swap(f.px, f.py); }
                 if (sg.axis == 2u) { scan_swap(f.uz, f.uy); scan_swap(f.pz, f.py); }
                 const v2f c = {sg.c, sg.c};
                 v2f s0 = c * f.uy, l0 = __builtin_elementwise_fma(f.py, c, f.nt);  // one rounding each, as in the general form's chains
-                do scan_trip<true, ROWS_IN_LDS>(rows, spheres, off, end, a0, a1, f, s0, l0, planes_off, n_padded, queue, lane, count, r, a, tmin, closest, best_k SS_PASS);
-                while (off != end);
+                if (!windowed) {
+                    do scan_trip<true, ROWS_IN_LDS>(rows, spheres, off, end, a0, a1, f, s0, l0, planes_off, n_padded, queue, lane, count, r, a, tmin, closest, best_k SS_PASS);
+                    while (off != end);
+                } else {
+                    for (;;) {
+                        while (!need && (chunk + 64u) * kTripBytes < seg_end) {
+                            chunk += 64u;
+                            const uint32_t n = seg_end / kTripBytes - chunk;  // trips of the run from the chunk's first on: lanes below it test one each
+                            bool mine = false;
+                            if (lane < n) {
+                                const ScanTripSpan sp = load_scan_span(sc, chunk + lane);
+                                mine = scan_window_needs(sp.lo, sp.hi, x0, x1);
+                            }
+                            need = scan_window_fill(__ballot(mine));
+                        }
+                        if (!need) break;
+                        const uint32_t first = (uint32_t)__builtin_ctzll(need);
+                        const unsigned long long behind = ~(need >> first);  // bit 0 clear; no bit set: the range ends with the chunk
+                        const uint32_t len = behind ? (uint32_t)__builtin_ctzll(behind) : 64u - first;
+                        need &= need + (1ull << first);  // the lowest range of set bits leaves
+                        const uint32_t start = (chunk + first) * kTripBytes;
+                        if (start != off) {
+                            off = start;
+                            a0 = load_scan_pair(rows, off, 0u);
+                            a1 = load_scan_pair(rows, off, kPairBytes);
+                        }
+                        end = start + len * kTripBytes;
+#if RT_PHASES
+                        ss.win_ranges++;
+                        ss.win_trips += len;
+#endif
+                        do scan_trip<true, ROWS_IN_LDS>(rows, spheres, off, end, a0, a1, f, s0, l0, planes_off, n_padded, queue, lane, count, r, a, tmin, closest, best_k SS_PASS);
+                        while (off != end);
+                    }
+                }
+                if (off != seg_end) {  // the window ended short of the run: set A of what follows
+                    off = seg_end;
+                    a0 = load_scan_pair(rows, off, 0u);
+                    a1 = load_scan_pair(rows, off, kPairBytes);
+                }
                 if (sg.axis == 0u) { scan_swap(f.ux, f.uy); scan_swap(f.px, f.py); }
                 if (sg.axis == 2u) { scan_swap(f.uz, f.uy); scan_swap(f.pz, f.py); }
             }
@@ -3361,6 +3491,12 @@ __global__ __launch_bounds__(T::BLOCK, T::MIN_WAVES) void render_kernel(DeviceSc
                     rows[n_pairs + p] = v4f{pr.cz[0], pr.cz[1], pr.k[0], pr.k[1]};
                 }
             }
+            // the window spans of the scan's trips (scan_filtered32), from behind the segment records
+            if (sc.lds_scan_spans != kNone && sc.lds_scan_spans != 0u) {
+                const ScanTripSpan *from = reinterpret_cast<const ScanTripSpan *>(sc.scan_segments + 2u * sc.n_scan_segments);
+                ScanTripSpan *to = reinterpret_cast<ScanTripSpan *>(lds_raw + sc.lds_scan_spans);
+                for (uint32_t t = threadIdx.x; t < sc.n_scan_window_trips; t += blockDim.x) to[t] = from[t];
+            }
             __syncthreads();
         }
     }
@@ -3693,23 +3829,31 @@ __global__ __launch_bounds__(T::BLOCK, T::MIN_WAVES) void render_kernel(DeviceSc
 #if RT_PHASES
                 ScanSums ss{};
 #endif
-                if (active) hit = a.exact_scan    ? scan_uniform(sc, queue, lane, ray, 0.001, DBL_MAX, h)
-                                 : a.filter_fp64 ? (sv.in_lds ? scan_filtered<true>(sc, sv.planes_off, sv.n_padded, queue, lane, ray, 0.001, DBL_MAX, h SS_PASS)
-                                                              : scan_filtered<false>(sc, 0u, 0u, queue, lane, ray, 0.001, DBL_MAX, h SS_PASS))
-                                 : sv.in_lds     ? scan_filtered32<true>(sc, sv.planes_off, sv.n_padded, queue, lane, ray, 0.001, DBL_MAX, h SS_PASS)
-                                                 : scan_filtered32<false>(sc, 0u, 0u, queue, lane, ray, 0.001, DBL_MAX, h SS_PASS);
+                if (a.exact_scan || a.filter_fp64) {
+                    if (active) hit = a.exact_scan ? scan_uniform(sc, queue, lane, ray, 0.001, DBL_MAX, h)
+                                      : sv.in_lds  ? scan_filtered<true>(sc, sv.planes_off, sv.n_padded, queue, lane, ray, 0.001, DBL_MAX, h SS_PASS)
+                                                   : scan_filtered<false>(sc, 0u, 0u, queue, lane, ray, 0.001, DBL_MAX, h SS_PASS);
+                } else if (a.scan_windows) {  // some run has a window table: the windows are the wave's, formed by all 64 lanes (scan_filtered32)
+                    hit = sv.in_lds ? scan_filtered32<true, true>(sc, active, sv.planes_off, sv.n_padded, queue, lane, ray, 0.001, DBL_MAX, h SS_PASS)
+                                    : scan_filtered32<false, true>(sc, active, 0u, 0u, queue, lane, ray, 0.001, DBL_MAX, h SS_PASS);
+                } else {
+                    if (active) hit = sv.in_lds ? scan_filtered32<true, false>(sc, true, sv.planes_off, sv.n_padded, queue, lane, ray, 0.001, DBL_MAX, h SS_PASS)
+                                                : scan_filtered32<false, false>(sc, true, 0u, 0u, queue, lane, ray, 0.001, DBL_MAX, h SS_PASS);
+                }
                 PH_END(0, active);
 #if RT_PHASES
                 ph.n[19] += 1ull;  // slot 19 (no primitive pass in this kernel): live lanes of the pass, and those with a camera ray
                 ph.l[19] += (unsigned long long)__popcll(live);
                 ph.t[19] += (unsigned long long)__popcll(__ballot(active && depth == 0));
-                {  // the scan ran in the active lanes only: take the (wave-uniform) sums from the first of them
+                {  // the sums are wave-uniform (the packed scan runs in all lanes, the others in the active ones): take them from the first active lane
                     const int src = __ffsll((long long)__ballot(active)) - 1;
                     if (src >= 0) {
                     const auto rl = [src](uint32_t v) { return (unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)v, src); };
                     ph.n[12] += rl(ss.groups);  ph.l[12] += rl(ss.taken);        ph.t[12] += rl(ss.spheres);
                     ph.n[13] += rl(ss.appends); ph.l[13] += rl(ss.behind);       ph.t[13] += rl(ss.drain_cycles);
                     ph.n[15] += rl(ss.drains);  ph.l[15] += rl(ss.drain_iters);
+                    ph.n[14] += rl(ss.win_runs); ph.l[14] += rl(ss.win_trips);   ph.t[14] += rl(ss.win_cycles);
+                    ph.n[7] += rl(ss.win_runs) ? 1ull : 0ull; ph.l[7] += rl(ss.win_ranges);
                     }
                 }
 #endif

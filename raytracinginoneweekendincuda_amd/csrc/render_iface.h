@@ -97,6 +97,9 @@ struct RenderArgs {
     uint32_t *ad_n;
     double *ad_q;
     uint8_t *ad_mark;
+    // sphere-list kernel: the scan's runs are windowed (scan_window_rule.h; the tables lie behind the scan segments, flat_scene.h
+    // ScanWindowSeg).  0: every run is scanned whole (RT_FLAG_NO_SCAN_WINDOWS, or no run of the scene has a table)
+    int32_t scan_windows;
 };
 
 struct KernelInfo {

@@ -20,6 +20,7 @@
 #include "../../include/rtow.h"
 #include "launch_plan.h"
 #include "primary_cull_rule.h"
+#include "scan_window_rule.h"
 #include "scene_host.h"
 
 namespace rtow {
@@ -1272,6 +1273,84 @@ static void cut_scan_segments(FlatScene &f)
     }
 }
 
+// The window tables of the runs (scan_window_rule.h; flat_scene.h ScanWindowSeg, ScanTripSpan).  Slab and spans come from the
+// fp64 centres and radii the reference's test reads (FlatScene::spheres), not from the filter's fp32 rows, and are stored as fp32
+// numbers rounded outwards; a row counts as decided exactly where the filter's row does (finite k).  A run gets a table where its
+// trips are selective on one of its varying axes (kScanWindowMaxMeanSpan), on the axis where they are most so.
+static void build_scan_windows(FlatScene &f)
+{
+    f.scan_windows.clear();
+    f.scan_trip_spans.clear();
+    const size_t trips = (f.sphere_scan.size() + 2 * kScanTripPairs - 1) / (2 * kScanTripPairs);
+    const float inf = std::numeric_limits<float>::infinity();
+    auto down = [](double v) { float x = (float)v; return (double)x > v ? std::nextafterf(x, -INFINITY) : x; };
+    auto up = [](double v) { float x = (float)v; return (double)x < v ? std::nextafterf(x, INFINITY) : x; };
+    std::vector<ScanWindowSeg> segs(f.scan_segments.size(), ScanWindowSeg{kScanAxisNone, 0.0f, 0.0f, 0u});
+    std::vector<ScanTripSpan> spans(trips, ScanTripSpan{-inf, inf});
+    bool any = false;
+    for (size_t k = 0; k < f.scan_segments.size(); k++) {
+        const ScanSegment &sg = f.scan_segments[k];
+        if (sg.axis == kScanAxisNone) continue;
+        // per trip and axis: the extent of the decided rows; whether the trip holds an undecided row
+        struct Extent { double lo, hi; };
+        std::vector<Extent> ext(3 * (size_t)sg.n_trips, Extent{INFINITY, -INFINITY});
+        std::vector<char> undecided(sg.n_trips, 0);
+        for (uint32_t t = 0; t < sg.n_trips; t++)
+            for (size_t row = 2 * kScanTripPairs * (size_t)(sg.first_trip + t); row < 2 * kScanTripPairs * (size_t)(sg.first_trip + t + 1); row++) {
+                const float fk = f.sphere_scan32[row / 2].k[row & 1];
+                if (fk == inf) continue;  // padding
+                if (fk == -inf) {
+                    undecided[t] = 1;
+                    continue;
+                }
+                const SphereGeom &g = f.spheres[row];
+                const double r = std::sqrt(std::fabs(g.r2)) * (1.0 + 0x1p-40), c[3] = {g.cx, g.cy, g.cz};
+                for (int a = 0; a < 3; a++) {
+                    Extent &e = ext[3 * (size_t)t + a];
+                    e.lo = std::fmin(e.lo, c[a] - r);
+                    e.hi = std::fmax(e.hi, c[a] + r);
+                }
+            }
+        uint32_t best_axis = kScanAxisNone;
+        double best_mean = INFINITY;
+        for (uint32_t a = 0; a < 3; a++) {
+            if (a == sg.axis) continue;
+            double lo = INFINITY, hi = -INFINITY, sum = 0.0;
+            size_t counted = 0;
+            for (uint32_t t = 0; t < sg.n_trips; t++) {
+                const Extent &e = ext[3 * (size_t)t + a];
+                if (!(e.lo <= e.hi)) continue;  // no decided row
+                lo = std::fmin(lo, e.lo);
+                hi = std::fmax(hi, e.hi);
+                sum += e.hi - e.lo;
+                counted++;
+            }
+            if (!counted || !(hi - lo > 0.0) || !std::isfinite(hi - lo)) continue;
+            const double mean = sum / (double)counted / (hi - lo);
+            if (mean <= kScanWindowMaxMeanSpan && mean < best_mean) {
+                best_mean = mean;
+                best_axis = a;
+            }
+        }
+        if (best_axis == kScanAxisNone) continue;
+        double slab_lo = INFINITY, slab_hi = -INFINITY;
+        for (uint32_t t = 0; t < sg.n_trips; t++) {
+            const Extent &own = ext[3 * (size_t)t + sg.axis], &e = ext[3 * (size_t)t + best_axis];
+            slab_lo = std::fmin(slab_lo, own.lo);
+            slab_hi = std::fmax(slab_hi, own.hi);
+            ScanTripSpan &sp = spans[sg.first_trip + t];
+            if (undecided[t]) sp = ScanTripSpan{-inf, inf};
+            else if (!(e.lo <= e.hi)) sp = ScanTripSpan{inf, -inf};
+            else sp = ScanTripSpan{down(e.lo), up(e.hi)};
+        }
+        segs[k] = ScanWindowSeg{best_axis, down(slab_lo), up(slab_hi), 0u};
+        any = true;
+    }
+    if (!any) return;
+    f.scan_windows = std::move(segs);
+    f.scan_trip_spans = std::move(spans);
+}
+
 // The segmented walk of a BVH world with composite leaves (flat_scene.h FastOrder / SegMedium): the library's tree over the
 // world's surface leaves, every node with the range of leaf positions below it, and the medium leaves in visiting order.
 static void build_segment_tree(FlatScene &f, bool reference_tree_only)
@@ -1695,6 +1774,7 @@ int flatten_scene(SceneImpl &s)
             }
             f.scan_reach32 *= 1.0 + 0x1p-20;
             cut_scan_segments(f);
+            build_scan_windows(f);
         }
     }
     {
@@ -2772,6 +2852,57 @@ int rt_scene_dump_scan_segments(rt_scene *s, int max_segments, uint32_t *rows_ax
         if (shared_out) shared_out[k] = sg.c;
     }
     return n;
+}
+
+int rt_scene_dump_scan_windows(rt_scene *s, int max_segments, uint32_t *axis_out, float *slab_out, int max_trips, float *spans_out)
+{
+    if (!s || !S(s)->committed) return -fail(RT_ERR_STATE, "rt_scene_dump_scan_windows: scene not committed");
+    const FlatScene &f = S(s)->flat;
+    const float inf = std::numeric_limits<float>::infinity();
+    const int n = (int)f.scan_segments.size();
+    for (int k = 0; k < n && k < max_segments; k++) {
+        const ScanWindowSeg w = f.scan_windows.empty() ? ScanWindowSeg{kScanAxisNone, 0.0f, 0.0f, 0u} : f.scan_windows[k];
+        if (axis_out) axis_out[k] = w.axis;
+        if (slab_out) {
+            slab_out[2 * k] = w.slab_lo;
+            slab_out[2 * k + 1] = w.slab_hi;
+        }
+    }
+    const int trips = (int)((f.sphere_scan.size() + 2 * kScanTripPairs - 1) / (2 * kScanTripPairs));
+    for (int t = 0; t < trips && t < max_trips && spans_out; t++) {
+        spans_out[2 * t] = f.scan_trip_spans.empty() ? -inf : f.scan_trip_spans[t].lo;
+        spans_out[2 * t + 1] = f.scan_trip_spans.empty() ? inf : f.scan_trip_spans[t].hi;
+    }
+    return n;
+}
+
+int rt_scene_scan_window_trips(rt_scene *s, int n_rays, const double *origin, const double *direction, int max_trips, uint8_t *needed_out)
+{
+    if (!s || !S(s)->committed) return -fail(RT_ERR_STATE, "rt_scene_scan_window_trips: scene not committed");
+    if (n_rays < 0 || (n_rays > 0 && (!origin || !direction))) return -fail(RT_ERR_INVALID, "rt_scene_scan_window_trips: no rays");
+    const FlatScene &f = S(s)->flat;
+    const int trips = (int)((f.sphere_scan.size() + 2 * kScanTripPairs - 1) / (2 * kScanTripPairs));
+    if (!needed_out) return trips;
+    if (max_trips < trips) return -fail(RT_ERR_INVALID, "rt_scene_scan_window_trips: max_trips is below the table's trips");
+    for (int k = 0; k < n_rays; k++) {
+        const double *o = origin + 3 * (size_t)k, *d = direction + 3 * (size_t)k;
+        uint8_t *out = needed_out + (size_t)k * (size_t)max_trips;
+        for (int t = 0; t < max_trips; t++) out[t] = t < trips ? 1 : 0;
+        for (size_t g = 0; g < f.scan_windows.size(); g++) {
+            const ScanSegment &sg = f.scan_segments[g];
+            const ScanWindowSeg &w = f.scan_windows[g];
+            if (w.axis == kScanAxisNone) continue;
+            // the kernel's own steps (render.hip scan_filtered32): the extent in fp64, the union's ends in fp32, the test per trip
+            const ScanExtent ex = scan_window_extent(o[sg.axis], d[sg.axis], o[w.axis], d[w.axis], std::fabs(o[0]) + std::fabs(o[1]) + std::fabs(o[2]),
+                                                     d[0] * d[0] + d[1] * d[1] + d[2] * d[2], f.scan_reach32, (double)w.slab_lo, (double)w.slab_hi);
+            const float x0 = (float)ex.lo, x1 = -(-(float)ex.hi);
+            for (uint32_t t = 0; t < sg.n_trips; t++) {
+                const ScanTripSpan &sp = f.scan_trip_spans[sg.first_trip + t];
+                out[sg.first_trip + t] = scan_window_needs(sp.lo, sp.hi, x0, x1) ? 1 : 0;
+            }
+        }
+    }
+    return trips;
 }
 
 int rt_scene_dump_primary_lists(rt_scene *s, int width, int height, int stripe_rows, int rank, int world_size, int max_tiles, uint16_t *lists_out)

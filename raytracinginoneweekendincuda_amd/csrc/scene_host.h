@@ -75,6 +75,10 @@ struct FlatScene {
     std::vector<SphereScanPair> sphere_scan32;  // pairs of sphere_scan rows in fp32
     double scan_reach32 = 0.0;
     std::vector<ScanSegment> scan_segments;  // tile the trips of sphere_scan32 in order (flat_scene.h ScanSegment)
+    // the windows of the runs (flat_scene.h ScanWindowSeg, ScanTripSpan): one record per segment, one span per trip; both empty
+    // where no run has a table
+    std::vector<ScanWindowSeg> scan_windows;
+    std::vector<ScanTripSpan> scan_trip_spans;
     std::vector<SphereAux> sphere_aux;
     std::vector<MSphereGeom> mspheres;
     std::vector<double> ms_planes;       // SCENE_WORLD_MSPHERES: seven planes of ms_padded doubles (see DeviceScene)
