@@ -4,6 +4,14 @@ radiance_kernel, step_kernel, advance_kernel, advance_scan_kernel, advance_gathe
 advance_direct_kernel, shadow_kernel, advance_direct_gather_kernel, radiance_direct_kernel, film_direct_kernel) by name with their static LDS as well."""
 import os, re, subprocess, sys
 so = sys.argv[1] if len(sys.argv) > 1 else os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', 'raytracinginoneweekendincuda_amd', 'librtow_hip.so')
+# The kernels listed by name: patterns of the mangled name whose groups (name, strict, world, mode -- those the kernel has) make the label
+TRAITS = r'ILi(?P<strict>\d)ENS_(?:6affine)?12_GLOBAL__N_16TraitsILi(?P<world>\d)E'
+LANE_KERNELS = [
+    r'(?P<name>feature_kernel|radiance_kernel|step_kernel|advance_kernel|advance_direct_kernel|shadow_kernel|radiance_direct_kernel|film_direct_kernel)' + TRAITS,
+    r'(?P<name>query_kernel)' + TRAITS + r'.*?EELi(?P<mode>\d)EEEv',  # MODE 0 closest hit, 1 occlusion
+    r'(?P<name>light_sample_kernel|light_pdf_kernel)ILi(?P<strict>\d)E',
+    r'(?P<name>atrous_kernel|advance_scan_kernel|advance_gather_kernel|advance_direct_gather_kernel)',
+]
 data = open(so, 'rb').read()
 idx = [m.start() for m in re.finditer(b'\x7fELF', data)]
 rows = []
@@ -26,54 +34,14 @@ for i, st in enumerate(idx[1:]):
                 strict, world, comp, rich, waves, media, batch, nested, block, fast, grouped = (int(x) for k, x in enumerate(m.groups()) if k != 1)
                 rows.append((int(adaptive) + (2 if affine else 0), world, comp, rich, media, batch, nested, fast, grouped, block, waves, 'strict' if strict else 'fast',
                              int(cur['vgpr_count']), int(cur['private_segment_fixed_size']), int(cur['vgpr_spill_count'])))
-            m = re.search(r'(feature_kernel)ILi(\d)ENS_(?:6affine)?12_GLOBAL__N_16TraitsILi(\d)|(atrous_kernel)', n)
-            if m:
-                name = m.group(4) or '%s world %s %s' % (m.group(1), m.group(3), 'strict' if int(m.group(2)) else 'fast')
+            for pattern in LANE_KERNELS:
+                m = re.search(pattern, n)
+                if not m: continue
+                g = m.groupdict()
+                name = g['name'] + (' world ' + g['world'] if g.get('world') else '')
+                if g.get('mode'): name += ' occlusion' if int(g['mode']) else ' closest'
+                if g.get('strict'): name += ' strict' if int(g['strict']) else ' fast'
                 others.append((name + affine, int(cur['vgpr_count']), int(cur['private_segment_fixed_size']), int(cur['vgpr_spill_count']),
-                               int(cur['group_segment_fixed_size'])))
-            m = re.search(r'query_kernelILi(\d)ENS_(?:6affine)?12_GLOBAL__N_16TraitsILi(\d)E.*?EELi(\d)EEEv', n)
-            if m:
-                name = 'query_kernel world %s %s %s' % (m.group(2), 'occlusion' if int(m.group(3)) else 'closest', 'strict' if int(m.group(1)) else 'fast')
-                others.append((name + affine, int(cur['vgpr_count']), int(cur['private_segment_fixed_size']), int(cur['vgpr_spill_count']),
-                               int(cur['group_segment_fixed_size'])))
-            m = re.search(r'radiance_kernelILi(\d)ENS_(?:6affine)?12_GLOBAL__N_16TraitsILi(\d)E', n)
-            if m:
-                name = 'radiance_kernel world %s %s' % (m.group(2), 'strict' if int(m.group(1)) else 'fast')
-                others.append((name + affine, int(cur['vgpr_count']), int(cur['private_segment_fixed_size']), int(cur['vgpr_spill_count']),
-                               int(cur['group_segment_fixed_size'])))
-            m = re.search(r'step_kernelILi(\d)ENS_(?:6affine)?12_GLOBAL__N_16TraitsILi(\d)E', n)
-            if m:
-                name = 'step_kernel world %s %s' % (m.group(2), 'strict' if int(m.group(1)) else 'fast')
-                others.append((name + affine, int(cur['vgpr_count']), int(cur['private_segment_fixed_size']), int(cur['vgpr_spill_count']),
-                               int(cur['group_segment_fixed_size'])))
-            m = re.search(r'advance_kernelILi(\d)ENS_(?:6affine)?12_GLOBAL__N_16TraitsILi(\d)E', n)
-            if m:
-                name = 'advance_kernel world %s %s' % (m.group(2), 'strict' if int(m.group(1)) else 'fast')
-                others.append((name + affine, int(cur['vgpr_count']), int(cur['private_segment_fixed_size']), int(cur['vgpr_spill_count']),
-                               int(cur['group_segment_fixed_size'])))
-            m = re.search(r'(light_sample_kernel|light_pdf_kernel)ILi(\d)E', n)
-            if m:
-                name = '%s %s' % (m.group(1), 'strict' if int(m.group(2)) else 'fast')
-                others.append((name + affine, int(cur['vgpr_count']), int(cur['private_segment_fixed_size']), int(cur['vgpr_spill_count']),
-                               int(cur['group_segment_fixed_size'])))
-            m = re.search(r'(advance_direct_kernel|shadow_kernel)ILi(\d)ENS_(?:6affine)?12_GLOBAL__N_16TraitsILi(\d)E', n)
-            if m:
-                name = '%s world %s %s' % (m.group(1), m.group(3), 'strict' if int(m.group(2)) else 'fast')
-                others.append((name + affine, int(cur['vgpr_count']), int(cur['private_segment_fixed_size']), int(cur['vgpr_spill_count']),
-                               int(cur['group_segment_fixed_size'])))
-            m = re.search(r'(film_direct_kernel)ILi(\d)ENS_(?:6affine)?12_GLOBAL__N_16TraitsILi(\d)E', n)
-            if m:
-                name = '%s world %s %s' % (m.group(1), m.group(3), 'strict' if int(m.group(2)) else 'fast')
-                others.append((name + affine, int(cur['vgpr_count']), int(cur['private_segment_fixed_size']), int(cur['vgpr_spill_count']),
-                               int(cur['group_segment_fixed_size'])))
-            m = re.search(r'(radiance_direct_kernel)ILi(\d)ENS_(?:6affine)?12_GLOBAL__N_16TraitsILi(\d)E', n)
-            if m:
-                name = '%s world %s %s' % (m.group(1), m.group(3), 'strict' if int(m.group(2)) else 'fast')
-                others.append((name + affine, int(cur['vgpr_count']), int(cur['private_segment_fixed_size']), int(cur['vgpr_spill_count']),
-                               int(cur['group_segment_fixed_size'])))
-            m = re.search(r'(advance_scan_kernel|advance_gather_kernel|advance_direct_gather_kernel)', n)
-            if m:
-                others.append((m.group(1), int(cur['vgpr_count']), int(cur['private_segment_fixed_size']), int(cur['vgpr_spill_count']),
                                int(cur['group_segment_fixed_size'])))
             cur = {}
 print("world comp rich media batch nested fast grouped block waves build vgpr scratchB spills")

@@ -4540,12 +4540,109 @@ DEV Vec first_hit_albedo(const DeviceScene &sc, const MatView &mp, uint32_t kind
     return material_texture<T>(sc, mp, mp.u32(MAT_OFF(tex_inline)), s.u, s.v, s.p);  // Lambertian, isotropic, diffuse light
 }
 
-// (not in radiance_kernel: there the helper moves the address arithmetic, and the unit is kept the parent build's to the instruction)
 [[maybe_unused]] DEV void store3(double *out, size_t k, Vec v)
 {
     out[k * 3 + 0] = v.x;
     out[k * 3 + 1] = v.y;
     out[k * 3 + 2] = v.z;
+}
+
+// A stream's six words {d, v0..v4}, `stride` words apart: 1 in the rows rt_rng_state writes (count x 6), n_pixels in a film's planes.
+[[maybe_unused]] DEV Xorwow load_stream(const uint32_t *w, size_t stride)
+{
+    Xorwow rng;
+    rng.d = w[0]; rng.v0 = w[stride]; rng.v1 = w[2 * stride]; rng.v2 = w[3 * stride]; rng.v3 = w[4 * stride]; rng.v4 = w[5 * stride];
+    return rng;
+}
+// (the words may be the ones the stream came from: a lane stores only after it has read its six)
+[[maybe_unused]] DEV void store_stream(uint32_t *w, size_t stride, const Xorwow &rng)
+{
+    w[0] = rng.d; w[stride] = rng.v0; w[2 * stride] = rng.v1; w[3 * stride] = rng.v2; w[4 * stride] = rng.v3; w[5 * stride] = rng.v4;
+}
+// the stream of lane k of a call: row k of rng_in or, without that array, curand_init(seed, k + first_sequence, 0)
+template <class Args>
+DEV Xorwow lane_stream(const Args &a, uint32_t k)
+{
+    if (a.rng_in) return load_stream(a.rng_in + (size_t)k * 6, 1);
+    Xorwow rng = a.base;
+    xorwow_skip_sequences(a.jump_table, a.first_sequence + (uint64_t)k, rng);
+    return rng;
+}
+
+// The two searches of this family, both the general kernels' search under RT_FLAG_REFERENCE_TREE | RT_FLAG_FORCE_GENERAL: the
+// reference's tree (walk_node / walk_leaves) or list (world_hit_list) in the reference's order, never the library's own tree.
+//   The closest hit over (0.001, DBL_MAX), what RayColor asks of the world (R/kernel.cu:77), for a kernel that needs the hit
+//   record and nothing else: the block "HitInfo h; ... walk_begin<false>(w, ray, DBL_MAX) ... world_hit_list" that feature_kernel,
+//   radiance_kernel, step_kernel, advance_kernel and advance_direct_kernel each hold in their own text.  It is not a function
+//   because it was measured as one (closest_hit<T>(sc, ray, h, rng), profiles/r30_lane_units_ab.txt): behind the call the tree
+//   walk of each kernel compiled with 6 to 14 more SGPRs spilled to VGPR lanes -- the walk_* functions are then first met inside
+//   a helper, and the inliner takes them in another order; no way of writing the function changed that -- and radiance_kernel,
+//   advance_kernel, advance_direct_kernel and step_kernel ran 6.2 %, 2.5 %, 2.7 % and 1.5 % slower on tree worlds, beyond the
+//   spread of the runs; as text they run as before.  A change to one of the five is a change to all.
+//   query_search (below, in the units that use it): the caller's interval, the position of the winning leaf from node_leaf_pos
+//   and an exit at the first accepted hit -- query_kernel, shadow_kernel, and radiance_direct_kernel and film_direct_kernel, whose
+//   one search an iteration is of a path ray or of a shadow ray.  It restates the two short outer loops to note the leaf; the
+//   kernels above do not pay for that.
+// Termination for any ray, degenerate ones included: the list loop runs n_world_items times; every walk_node step either moves
+// to a node with a higher index (n + 1, or an escape link, which always points forward in the preorder array) or parks, a
+// parked lane leaves through the escape link, and the last escape is kNone -- at most two steps per node whatever the box tests
+// answer (NaNs only make them false); leaf tests are straight-line code or loops over table counts (tree_hit: a bounded stack).
+//
+// One bounce of RayColor (R/kernel.cu:74-94) behind a search that answered `hit` with record h, exactly the block of render_kernel
+// at "R/kernel.cu:74-79": a miss adds the background, a hit goes through make_surface and shade.  Returns scattered: `ray` is then
+// the next ray, else it is untouched.  radiance_kernel passes its path's throughput and sum.  Every other caller passes (1, 1, 1)
+// and (0, 0, 0): what shade leaves in `accumulated` is then 0 + 1 * x, the emitted or background value x itself, and what it
+// leaves in `throughput` is 1 * a, the attenuation a itself (a negative zero comes out positive), in the strict build and in the
+// fast one (fma(1, x, 0) is x) -- so a caller that folds acc = acc + thr * emitted, thr = thr * attenuation over the bounces
+// repeats radiance_kernel's arithmetic in the strict build.  (A metal whose direction falls below the surface ends the path
+// before shade multiplies: throughput is still (1, 1, 1).)  The hit record's facts are query_kernel's: the shading normal where
+// want_normal, left (0, 0, 0) for a medium and washed through 0 + n so that no negative zero leaves; the kind where want_kind,
+// else 255.  Straight-line code; the rejection loops of shade depend on the stream alone.
+template <class T>
+DEV bool bounce(const DeviceScene &sc, Ray &ray, const HitInfo &h, bool hit, Xorwow &rng, Vec &throughput, Vec &accumulated, bool want_normal,
+                bool want_kind, Vec &normal, bool &front, uint32_t &kind)
+{
+    normal = mk(0.0, 0.0, 0.0);
+    kind = 255u;
+    front = false;
+    bool scattered = false;
+    if (!hit) {  // R/kernel.cu:74-79
+        accumulated = accumulated + throughput * load3c(((const RT_CONST CameraRec *)(uintptr_t)sc.camera)->bg);
+    } else {
+        const Surface s = make_surface<T>(sc, ray, h);
+        if (want_normal && (h.ref >> kRefShift) != REF_MEDIUM) normal = s.n;
+        front = s.front;
+        if (want_kind) kind = material_view<false>(sc, s.mat).u32(MAT_OFF(kind));
+        scattered = shade<T>(sc, s, ray, throughput, accumulated, rng);
+    }
+    normal = mk(0.0, 0.0, 0.0) + normal;
+    return scattered;
+}
+// (a caller that wants none of the hit record's facts)
+template <class T>
+DEV bool bounce(const DeviceScene &sc, Ray &ray, const HitInfo &h, bool hit, Xorwow &rng, Vec &throughput, Vec &accumulated)
+{
+    Vec normal;
+    bool front;
+    uint32_t kind;
+    return bounce<T>(sc, ray, h, hit, rng, throughput, accumulated, false, false, normal, front, kind);
+}
+
+// What the scan and the gather behind a path advance read: row k's survivor flag and the workgroup's count of survivors -- per
+// wave, then one store (as count_valid reduces) -- and one atomic per wave for the rows that took a step.  Every lane of the
+// workgroup comes here, rows at or beyond the count and dead rays as non-survivors.
+[[maybe_unused]] DEV void count_survivors(const AdvanceArgs &a, uint32_t k, bool stepped, bool scattered, uint32_t *wave_survivors)
+{
+    if (k < a.capacity) a.survivor[k] = scattered ? 1 : 0;
+    const unsigned long long survivors = __ballot(scattered);
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    if (lane == 0) wave_survivors[wave] = (uint32_t)__popcll(survivors);
+    if (a.stepped_counter) {
+        const unsigned long long took = __ballot(stepped);
+        if (lane == 0 && took) atomicAdd(a.stepped_counter, (unsigned long long)__popcll(took));
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) a.block_counts[blockIdx.x] = (wave_survivors[0] + wave_survivors[1]) + (wave_survivors[2] + wave_survivors[3]);
 }
 
 // info != nullptr: report the registers and scratch of the chosen instantiation instead of launching it; else a lane per ray
@@ -4569,10 +4666,9 @@ hipError_t info_or_launch(void (*kernel)(DeviceScene, Args), const DeviceScene &
 #if RT_FEATURES
 // ------------------------------------------------------------------------------------------------
 // First-hit feature pass (rt_film_render_features): albedo, shading normal and depth of the closest hit over [0.001, inf) of
-// every primary ray.  One lane per owned pixel, no persistent waves, no LDS staging, every table from global memory; the world is
-// searched as the general kernels search it under RT_FLAG_REFERENCE_TREE | RT_FLAG_FORCE_GENERAL -- the reference's tree
-// (walk_node / walk_leaves) or list (world_hit_list) in the reference's order, so that media draw what they draw in a render and
-// coincident primitives are decided as the reference decides them -- and the hit record is make_surface's.
+// every primary ray.  One lane per owned pixel, no persistent waves, no LDS staging, every table from global memory; the search
+// is the closest-hit block (the comment on the two searches above), so that media draw what they draw in a render and coincident primitives are decided as the reference decides
+// them, and the hit record is make_surface's.
 // ------------------------------------------------------------------------------------------------
 namespace {
 // samples == 0: the ray through the pixel centre, no lens offset, at the shutter's opening; the camera takes no draws
@@ -4662,16 +4758,12 @@ hipError_t RT_CAT(launch_features_, RT_SUFFIX)(const DeviceScene &sc, const Feat
 #endif
 #if RT_QUERY || RT_ADVANCE_DIRECT || RT_RADIANCE_DIRECT || RT_FILM_DIRECT  // (the search is shadow_kernel's, radiance_direct_kernel's and film_direct_kernel's too)
 // ------------------------------------------------------------------------------------------------
-// Ray queries (rt_scene_intersect): closest hit or occlusion for caller-supplied rays.  The feature pass's search once more -- one
-// lane per ray, no LDS, every table from global memory, the reference's tree or list in the reference's order through leaf_test /
-// walk_node -- with the ray, its time and its interval read from the caller's arrays.  query_search is that search over this
-// section's copies of the two short outer loops (world_hit_list, walk_leaves), which note the world leaf that produced the winning
-// record and, for an occlusion query of a world without media, stop at the first accepted hit.  The library's own tree is never
-// walked here: valid only while hits stay inside their leaves' boxes, which depends on the shutter; a caller's times are arbitrary.
-// Termination for any ray, degenerate ones included: the list loop runs n_world_items times; every walk_node step either moves
-// to a node with a higher index (n + 1, or an escape link, which always points forward in the preorder array) or parks, a
-// parked lane leaves through the escape link, and the last escape is kNone -- at most two steps per node whatever the box tests
-// answer (NaNs only make them false); leaf tests are straight-line code or loops over table counts (tree_hit: a bounded stack).
+// Ray queries (rt_scene_intersect): closest hit or occlusion for caller-supplied rays.  One lane per ray, no LDS, every table from
+// global memory, the ray, its time and its interval read from the caller's arrays.  query_search is the closest-hit search (the
+// comment on the two searches above says which kernel uses which, and why it terminates) over this section's copies of the two short outer loops
+// (world_hit_list, walk_leaves), which note the world leaf that produced the winning record and, for an occlusion query of a
+// world without media, stop at the first accepted hit.  The library's own tree is never walked here: valid only while hits stay
+// inside their leaves' boxes, which depends on the shutter; a caller's times are arbitrary.
 // ------------------------------------------------------------------------------------------------
 namespace {
 // R/HittableList.h:39-57 as world_hit_list runs it, plus the position of the winning leaf; FIRST: leave at the first accepted hit
@@ -4859,15 +4951,14 @@ hipError_t RT_CAT(launch_query_, RT_SUFFIX)(const DeviceScene &sc, const QueryAr
 }
 #elif RT_RADIANCE
 // ------------------------------------------------------------------------------------------------
-// Radiance queries (rt_scene_radiance): RayColor (R/kernel.cu:66-98) for caller-supplied rays.  The ray queries' search -- one
-// lane per ray, no LDS, every table from global memory, the reference's tree or list in the reference's order (walk_node /
-// walk_leaves, world_hit_list) -- followed by make_surface and shade, exactly the block of render_kernel at "R/kernel.cu:74-79".
+// Radiance queries (rt_scene_radiance): RayColor (R/kernel.cu:66-98) for caller-supplied rays.  One lane per ray, no LDS, every
+// table from global memory; the closest-hit search, then bounce on the path's own
+// throughput and sum.
 // One flattened loop: an iteration is one world search and one shade step for every lane still live; a lane whose path ends adds
 // it to its sum and starts its next sample, from the same ray, in the same iteration (render_kernel's path regeneration), and
 // leaves when its last sample is done.  Lanes at different samples and depths so share the search code; a loop over samples
 // around a loop over bounces would idle every lane until the longest path of each round ends.
-// Termination for any ray: at most samples * max_depth iterations, each a bounded search (the ray queries' argument above
-// query_hit_list) and straight-line shading; the rejection loops of shade depend on the stream alone.
+// Termination for any ray: at most samples * max_depth iterations, each a bounded search and a bounce.
 // ------------------------------------------------------------------------------------------------
 template <int STRICT, class T>
 __global__ __launch_bounds__(256) void radiance_kernel(DeviceScene sc, RadianceArgs a)
@@ -4877,14 +4968,7 @@ __global__ __launch_bounds__(256) void radiance_kernel(DeviceScene sc, RadianceA
     uint32_t rays = 0;  // world searches of this lane's ray, all samples
     if (k < a.count) {
         const Ray first = caller_ray(a.origin, a.direction, a.time, a.time_all, k);
-        Xorwow rng;
-        if (a.rng_in) {  // {d, v0..v4} as rt_rng_state writes them
-            const uint32_t *w = a.rng_in + (size_t)k * 6;
-            rng.d = w[0]; rng.v0 = w[1]; rng.v1 = w[2]; rng.v2 = w[3]; rng.v3 = w[4]; rng.v4 = w[5];
-        } else {  // curand_init(seed, k + first_sequence, 0)
-            rng = a.base;
-            xorwow_skip_sequences(a.jump_table, a.first_sequence + (uint64_t)k, rng);
-        }
+        Xorwow rng = lane_stream(a, k);
         const NodeView nv{sc.nodes, 0u, false};
         Vec sum = mk(0.0, 0.0, 0.0);
         if (a.max_depth > 0) {  // R/kernel.cu:71: otherwise the bounce loop never runs, RayColor returns black and draws nothing
@@ -4911,15 +4995,8 @@ __global__ __launch_bounds__(256) void radiance_kernel(DeviceScene sc, RadianceA
                     hit = world_hit_list<T>(sc, ray, 0.001, DBL_MAX, h, rng);
                 }
                 rays++;
-                bool path_ends;
-                if (!hit) {  // R/kernel.cu:74-79
-                    accumulated = accumulated + throughput * load3c(((const RT_CONST CameraRec *)(uintptr_t)sc.camera)->bg);
-                    path_ends = true;
-                } else {
-                    const Surface s = make_surface<T>(sc, ray, h);
-                    path_ends = !shade<T>(sc, s, ray, throughput, accumulated, rng);
-                    if (!path_ends && ++depth >= a.max_depth) path_ends = true;  // R/kernel.cu:71,97
-                }
+                bool path_ends = !bounce<T>(sc, ray, h, hit, rng, throughput, accumulated);
+                if (!path_ends && ++depth >= a.max_depth) path_ends = true;  // R/kernel.cu:71,97
                 if (path_ends) {  // R/kernel.cu:143: col += RayColor(...)
                     sum = sum + accumulated;
                     if (++sample >= a.samples) break;
@@ -4932,15 +5009,10 @@ __global__ __launch_bounds__(256) void radiance_kernel(DeviceScene sc, RadianceA
         }
         if (a.radiance) {  // linear: the mean as a render forms it (R/kernel.cu:150), no gamma
             const Vec mean = over(sum, (double)a.samples);
-            a.radiance[(size_t)k * 3 + 0] = mean.x;
-            a.radiance[(size_t)k * 3 + 1] = mean.y;
-            a.radiance[(size_t)k * 3 + 2] = mean.z;
+            store3(a.radiance, k, mean);
         }
         if (a.path_rays) a.path_rays[k] = rays;
-        if (a.rng_out) {  // may be the array the state came from: this lane has read its six words
-            uint32_t *w = a.rng_out + (size_t)k * 6;
-            w[0] = rng.d; w[1] = rng.v0; w[2] = rng.v1; w[3] = rng.v2; w[4] = rng.v3; w[5] = rng.v4;
-        }
+        if (a.rng_out) store_stream(a.rng_out + (size_t)k * 6, 1, rng);
     }
     if (a.ray_counter) {  // one atomic per wave: every lane of the wave is here again
         unsigned long long total = rays;
@@ -4960,13 +5032,9 @@ hipError_t RT_CAT(launch_radiance_, RT_SUFFIX)(const DeviceScene &sc, const Radi
 #elif RT_STEP
 // ------------------------------------------------------------------------------------------------
 // Path steps (rt_scene_path_step): one iteration of RayColor's loop (R/kernel.cu:74-94) for caller-supplied rays, so that an
-// integrator outside the library can continue the path itself.  radiance_kernel's iteration -- its search loop, its miss branch and
-// its make_surface / shade call, line for line -- run once, from throughput (1, 1, 1) and accumulated (0, 0, 0): what shade leaves
-// in `accumulated` is then 0 + 1 * x, the emitted or background value x itself, and what it leaves in `throughput` is 1 * a, the
-// attenuation a itself (a negative zero comes out positive), in the strict build and in the fast one (fma(1, x, 0) is x).  A host
-// that folds acc = acc + thr * emitted, thr = thr * attenuation over the steps repeats radiance_kernel's arithmetic in the strict
-// build.  The hit record's outputs are query_kernel's.  Termination for any ray: one bounded search (the argument above
-// query_hit_list) and straight-line shading; the rejection loops of shade depend on the stream alone.
+// integrator outside the library can continue the path itself.  radiance_kernel's iteration -- the closest-hit search and bounce -- run once,
+// from throughput (1, 1, 1) and accumulated (0, 0, 0), which come back as the attenuation and the emitted or background value
+// themselves (bounce says why).  Termination for any ray: one bounded search and one bounce.
 // ------------------------------------------------------------------------------------------------
 template <int STRICT, class T>
 __global__ __launch_bounds__(256) void step_kernel(DeviceScene sc, StepArgs a)
@@ -4976,14 +5044,7 @@ __global__ __launch_bounds__(256) void step_kernel(DeviceScene sc, StepArgs a)
     if (k >= a.count) return;
     // the ray and the six words are read here, before anything is written: every output may be the input array of the same meaning
     Ray ray = caller_ray(a.origin, a.direction, a.time, a.time_all, k);
-    Xorwow rng;
-    if (a.rng_in) {  // {d, v0..v4} as rt_rng_state writes them
-        const uint32_t *w = a.rng_in + (size_t)k * 6;
-        rng.d = w[0]; rng.v0 = w[1]; rng.v1 = w[2]; rng.v2 = w[3]; rng.v3 = w[4]; rng.v4 = w[5];
-    } else {  // curand_init(seed, k + first_sequence, 0)
-        rng = a.base;
-        xorwow_skip_sequences(a.jump_table, a.first_sequence + (uint64_t)k, rng);
-    }
+    Xorwow rng = lane_stream(a, k);
     const NodeView nv{sc.nodes, 0u, false};
     Vec throughput = mk(1.0, 1.0, 1.0), accumulated = mk(0.0, 0.0, 0.0);
     HitInfo h;
@@ -5004,18 +5065,10 @@ __global__ __launch_bounds__(256) void step_kernel(DeviceScene sc, StepArgs a)
     } else {
         hit = world_hit_list<T>(sc, ray, 0.001, DBL_MAX, h, rng);
     }
-    Vec normal = mk(0.0, 0.0, 0.0);
-    uint32_t kind = 255u;
-    bool front = false, scattered = false;
-    if (!hit) {  // R/kernel.cu:74-79
-        accumulated = accumulated + throughput * load3c(((const RT_CONST CameraRec *)(uintptr_t)sc.camera)->bg);
-    } else {
-        const Surface s = make_surface<T>(sc, ray, h);
-        if (a.normal && (h.ref >> kRefShift) != REF_MEDIUM) normal = s.n;
-        front = s.front;
-        if (a.material) kind = material_view<false>(sc, s.mat).u32(MAT_OFF(kind));
-        scattered = shade<T>(sc, s, ray, throughput, accumulated, rng);  // scattered: `ray` is the next ray; else it is untouched
-    }
+    Vec normal;
+    uint32_t kind;
+    bool front;
+    const bool scattered = bounce<T>(sc, ray, h, hit, rng, throughput, accumulated, a.normal != nullptr, a.material != nullptr, normal, front, kind);
     if (a.scattered_counter) {
         const unsigned long long found = __ballot(scattered);  // one atomic per wave (per group of lanes that arrive together)
         if (scattered && (uint32_t)__ffsll((long long)found) - 1u == (threadIdx.x & 63u))
@@ -5023,19 +5076,15 @@ __global__ __launch_bounds__(256) void step_kernel(DeviceScene sc, StepArgs a)
     }
     if (a.status) a.status[k] = !hit ? 0 : scattered ? 2 : 1;
     if (a.emitted) store3(a.emitted, k, accumulated);
-    // (a metal whose direction falls below the surface ends the path before shade multiplies: throughput is still (1, 1, 1))
     if (a.attenuation) store3(a.attenuation, k, scattered ? throughput : mk(0.0, 0.0, 0.0));
     if (a.origin_out) store3(a.origin_out, k, ray.o);
     if (a.direction_out) store3(a.direction_out, k, ray.d);
     if (a.time_out) a.time_out[k] = ray.tm;
     if (a.t) a.t[k] = hit ? h.t : (double)INFINITY;
-    if (a.normal) store3(a.normal, k, mk(0.0, 0.0, 0.0) + normal);  // as query_kernel: no negative zeros
+    if (a.normal) store3(a.normal, k, normal);
     if (a.front_face) a.front_face[k] = front ? 1 : 0;
     if (a.material) a.material[k] = (uint8_t)kind;
-    if (a.rng_out) {  // may be the array the state came from: this lane has read its six words
-        uint32_t *w = a.rng_out + (size_t)k * 6;
-        w[0] = rng.d; w[1] = rng.v0; w[2] = rng.v1; w[3] = rng.v2; w[4] = rng.v3; w[5] = rng.v4;
-    }
+    if (a.rng_out) store_stream(a.rng_out + (size_t)k * 6, 1, rng);
 }
 
 hipError_t RT_CAT(launch_step_, RT_SUFFIX)(const DeviceScene &sc, const StepArgs &a, hipStream_t stream, QueryKernelInfo *info)
@@ -5049,15 +5098,15 @@ hipError_t RT_CAT(launch_step_, RT_SUFFIX)(const DeviceScene &sc, const StepArgs
 }
 #elif RT_ADVANCE
 // ------------------------------------------------------------------------------------------------
-// Path advances (rt_scene_path_advance), launch 1 of 3 (render_iface.h AdvanceArgs): step_kernel's iteration, restated line for
-// line, for every row below n = min(*count_in, capacity) whose ray is alive, and then what a caller's loop did with the outputs:
+// Path advances (rt_scene_path_advance), launch 1 of 3 (render_iface.h AdvanceArgs): step_kernel's iteration (the
+// closest-hit search and bounce) for every row below n = min(*count_in, capacity) whose ray is alive, and then what a caller's loop did with the outputs:
 //   an ended ray (status 0 or 1) adds thr * emitted to its row of `radiance` -- the product, then the sum, two operations in the
 //   strict build; the ids of live rays are distinct, so a plain load, add and store;
 //   a scattered ray (status 2) stages its record at its own row k of the staging arrays and sets survivor[k]; the gather launch
 //   moves it to its packed row once the scan launch knows how many survivors the workgroups before this one have.
 // The throughput and the id are loaded after the search: they are not live across it.  No lane returns early: rows at or beyond n
-// and dead rays take part in the ballot and the barrier as non-survivors, and every row below `capacity` gets its flag, every
-// workgroup its count, so that the two launches behind this one read nothing stale.  Termination as for step_kernel.
+// and dead rays reach count_survivors as non-survivors, and every row below `capacity` gets its flag, every workgroup its count,
+// so that the two launches behind this one read nothing stale.  Termination as for step_kernel.
 // ------------------------------------------------------------------------------------------------
 template <int STRICT, class T>
 __global__ __launch_bounds__(256) void advance_kernel(DeviceScene sc, AdvanceArgs a)
@@ -5070,14 +5119,7 @@ __global__ __launch_bounds__(256) void advance_kernel(DeviceScene sc, AdvanceArg
     bool scattered = false;
     if (stepped) {
         Ray ray = caller_ray(a.origin, a.direction, a.time, a.time_all, k);
-        Xorwow rng;
-        if (a.rng_in) {  // {d, v0..v4} as rt_rng_state writes them
-            const uint32_t *w = a.rng_in + (size_t)k * 6;
-            rng.d = w[0]; rng.v0 = w[1]; rng.v1 = w[2]; rng.v2 = w[3]; rng.v3 = w[4]; rng.v4 = w[5];
-        } else {  // curand_init(seed, k + first_sequence, 0)
-            rng = a.base;
-            xorwow_skip_sequences(a.jump_table, a.first_sequence + (uint64_t)k, rng);
-        }
+        Xorwow rng = lane_stream(a, k);
         const NodeView nv{sc.nodes, 0u, false};
         Vec throughput = mk(1.0, 1.0, 1.0), accumulated = mk(0.0, 0.0, 0.0);
         HitInfo h;
@@ -5098,19 +5140,11 @@ __global__ __launch_bounds__(256) void advance_kernel(DeviceScene sc, AdvanceArg
         } else {
             hit = world_hit_list<T>(sc, ray, 0.001, DBL_MAX, h, rng);
         }
-        Vec normal = mk(0.0, 0.0, 0.0);
-        uint32_t kind = 255u;
-        bool front = false;
-        if (!hit) {  // R/kernel.cu:74-79
-            accumulated = accumulated + throughput * load3c(((const RT_CONST CameraRec *)(uintptr_t)sc.camera)->bg);
-        } else {
-            const Surface s = make_surface<T>(sc, ray, h);
-            if (a.stage.normal && (h.ref >> kRefShift) != REF_MEDIUM) normal = s.n;
-            front = s.front;
-            if (a.stage.material) kind = material_view<false>(sc, s.mat).u32(MAT_OFF(kind));
-            scattered = shade<T>(sc, s, ray, throughput, accumulated, rng);  // scattered: `ray` is the next ray
-        }
-        // what the path carried into this bounce: `throughput` is 1 * attenuation and `accumulated` 0 + 1 * emitted (step_kernel)
+        Vec normal;
+        uint32_t kind;
+        bool front;
+        scattered = bounce<T>(sc, ray, h, hit, rng, throughput, accumulated, a.stage.normal != nullptr, a.stage.material != nullptr, normal, front, kind);
+        // what the path carried into this bounce: `throughput` is 1 * attenuation and `accumulated` 0 + 1 * emitted (bounce)
         const Vec carried = a.throughput ? mk(a.throughput[(size_t)k * 3 + 0], a.throughput[(size_t)k * 3 + 1], a.throughput[(size_t)k * 3 + 2])
                                          : mk(1.0, 1.0, 1.0);
         const int32_t id = a.ray_id ? a.ray_id[k] : (int32_t)k;
@@ -5127,29 +5161,16 @@ __global__ __launch_bounds__(256) void advance_kernel(DeviceScene sc, AdvanceArg
             if (a.stage.origin) store3(a.stage.origin, k, ray.o);
             if (a.stage.direction) store3(a.stage.direction, k, ray.d);
             if (a.stage.time) a.stage.time[k] = ray.tm;
-            if (a.stage.rng_state) {
-                uint32_t *w = a.stage.rng_state + (size_t)k * 6;
-                w[0] = rng.d; w[1] = rng.v0; w[2] = rng.v1; w[3] = rng.v2; w[4] = rng.v3; w[5] = rng.v4;
-            }
+            if (a.stage.rng_state) store_stream(a.stage.rng_state + (size_t)k * 6, 1, rng);
             if (a.stage.throughput) store3(a.stage.throughput, k, carried * throughput);
             if (a.stage.ray_id) a.stage.ray_id[k] = id;
             if (a.stage.t) a.stage.t[k] = h.t;
-            if (a.stage.normal) store3(a.stage.normal, k, mk(0.0, 0.0, 0.0) + normal);  // as query_kernel: no negative zeros
+            if (a.stage.normal) store3(a.stage.normal, k, normal);
             if (a.stage.front_face) a.stage.front_face[k] = front ? 1 : 0;
             if (a.stage.material) a.stage.material[k] = (uint8_t)kind;
         }
     }
-    // every lane of the workgroup is here again
-    if (k < a.capacity) a.survivor[k] = scattered ? 1 : 0;
-    const unsigned long long survivors = __ballot(scattered);
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    if (lane == 0) wave_survivors[wave] = (uint32_t)__popcll(survivors);
-    if (a.stepped_counter) {  // one atomic per wave
-        const unsigned long long took = __ballot(stepped);
-        if (lane == 0 && took) atomicAdd(a.stepped_counter, (unsigned long long)__popcll(took));
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) a.block_counts[blockIdx.x] = (wave_survivors[0] + wave_survivors[1]) + (wave_survivors[2] + wave_survivors[3]);
+    count_survivors(a, k, stepped, scattered, wave_survivors);  // every lane of the workgroup is here again
 }
 
 hipError_t RT_CAT(launch_advance_, RT_SUFFIX)(const DeviceScene &sc, const AdvanceArgs &a, hipStream_t stream, QueryKernelInfo *info)
@@ -5216,167 +5237,177 @@ DEV bool usable_density(double pdf) { return pdf > 0.0 && pdf < (double)INFINITY
         if (total) atomicAdd(counter, (unsigned long long)total);
     }
 }
-}  // namespace
-#endif
 
-#if RT_LIGHTS
-template <int STRICT, class T>
-__global__ __launch_bounds__(256) void light_sample_kernel(DeviceScene sc, LightArgs a)
+// The light sample of rt_scene_sample_lights for the point P at the time tm, drawn from rng (include/rtow.h states it operation by
+// operation, tests/light_restated.py restates the strict build to the bit; n_lights != 0).  One draw picks the row: `row` is the
+// first with cdf >= xi by bisection (the last entry is 1.0 >= xi), L that row.  A parallelogram or triangle takes two draws for
+// the point S = a + ua b + ub c (a triangle folds ua + ub > 1 back), (u, v) = (ua, ub).  A sphere takes the rejection loop of the
+// lens for a point of the unit disc and maps it into the cone the sphere subtends from P, around the axis to `centre` (a moving
+// sphere's centre at tm); `distance` is then the near root as the renderer's own sphere test finds it for this ray (sphere_test /
+// sphere_roots: R/Sphere.h:28-50), operation by operation -- a shadow ray along `dir` meets the lamp at this very parameter --
+// and S the point there.  Returns validity; an invalid sample leaves dir (0, 0, 0), distance 0 and pdf 0, and has taken the same
+// draws.  Termination: the bisection halves hi - lo; the rejection loop depends on the stream alone.
+[[maybe_unused]] DEV bool light_sample(const LightArgs &a, const LightLds &lds, Vec P, double tm, Xorwow &rng, uint32_t &row, LightRow &L, Vec &dir,
+                                      double &distance, double &pdf, Vec &S, Vec &centre, double &u, double &v)
 {
-    __shared__ __attribute__((aligned(16))) double rows_lds[kLightLdsRows * kLightRowDoubles];
-    __shared__ __attribute__((aligned(16))) double cdf_lds[kLightLdsRows];
-    __shared__ uint32_t wave_valid[4];
-    global_tables_only(sc);
-    stage_lights(a, rows_lds, cdf_lds);
-    const LightLds lds{rows_lds, cdf_lds};
-    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
     bool valid = false;
-    if (k < a.count) {
-        // the point and the six words are read here, before anything is written: rng_out may be rng_in
-        const Vec P = load3(a.point + (size_t)k * 3);
-        const double tm = a.time ? a.time[k] : a.time_all;
-        Xorwow rng;
-        if (a.rng_in) {  // {d, v0..v4} as rt_rng_state writes them
-            const uint32_t *w = a.rng_in + (size_t)k * 6;
-            rng.d = w[0]; rng.v0 = w[1]; rng.v1 = w[2]; rng.v2 = w[3]; rng.v3 = w[4]; rng.v4 = w[5];
-        } else {  // curand_init(seed, k + first_sequence, 0)
-            rng = a.base;
-            xorwow_skip_sequences(a.jump_table, a.first_sequence + (uint64_t)k, rng);
+    dir = mk(0.0, 0.0, 0.0);
+    distance = 0.0;
+    pdf = 0.0;
+    const double xi = (double)xorwow_uniform(rng);
+    uint32_t lo = 0, hi = a.n_lights - 1u;
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) / 2u;
+        if (light_cdf(a, lds, mid) >= xi) hi = mid;
+        else lo = mid + 1u;
+    }
+    row = lo;
+    const double chance = light_cdf(a, lds, lo) - (lo ? light_cdf(a, lds, lo - 1u) : 0.0);
+    L = light_row(a, lds, lo);
+    S = mk(0.0, 0.0, 0.0);
+    centre = mk(0.0, 0.0, 0.0);
+    u = 0.0;
+    v = 0.0;
+    if (L.kind <= LIGHT_TRIANGLE) {
+        double ua = (double)xorwow_uniform(rng);
+        double ub = (double)xorwow_uniform(rng);
+        if (L.kind == LIGHT_TRIANGLE && ua + ub > 1.0) {
+            ua = 1.0 - ua;
+            ub = 1.0 - ub;
         }
-        Vec dir = mk(0.0, 0.0, 0.0), emitted = mk(0.0, 0.0, 0.0), contribution = mk(0.0, 0.0, 0.0);
-        double distance = 0.0, pdf = 0.0, scatter = 0.0;
-        int32_t light = -1;
-        if (a.n_lights != 0) {
-            const double xi = (double)xorwow_uniform(rng);
-            uint32_t lo = 0, hi = a.n_lights - 1u;  // the first row with cdf >= xi; the last entry is 1.0 >= xi
-            while (lo < hi) {
-                const uint32_t mid = (lo + hi) / 2u;
-                if (light_cdf(a, lds, mid) >= xi) hi = mid;
-                else lo = mid + 1u;
-            }
-            light = (int32_t)lo;
-            const double chance = light_cdf(a, lds, lo) - (lo ? light_cdf(a, lds, lo - 1u) : 0.0);
-            const LightRow L = light_row(a, lds, lo);
-            Vec S = mk(0.0, 0.0, 0.0), centre = mk(0.0, 0.0, 0.0);
-            double u = 0.0, v = 0.0;
-            if (L.kind <= LIGHT_TRIANGLE) {
-                double ua = (double)xorwow_uniform(rng);
-                double ub = (double)xorwow_uniform(rng);
-                if (L.kind == LIGHT_TRIANGLE && ua + ub > 1.0) {
-                    ua = 1.0 - ua;
-                    ub = 1.0 - ub;
+        S = (load3(L.a) + ua * load3(L.b)) + ub * load3(L.c);
+        const Vec D = S - P;
+        const double d2 = dot(D, D);
+        if (d2 > 0.0) {
+            const double len = sqrt(d2);
+            const Vec unit_d = over(D, len);
+            const double c = fabs(dot(load3(L.n), unit_d));
+            if (c != 0.0) {
+                const double density = (d2 / (c * L.s)) * chance;
+                if (usable_density(density)) {
+                    valid = true;
+                    dir = unit_d;
+                    distance = len;
+                    pdf = density;
                 }
-                S = (load3(L.a) + ua * load3(L.b)) + ub * load3(L.c);
-                const Vec D = S - P;
-                const double d2 = dot(D, D);
-                if (d2 > 0.0) {
-                    const double len = sqrt(d2);
-                    const Vec unit_d = over(D, len);
-                    const double c = fabs(dot(load3(L.n), unit_d));
-                    if (c != 0.0) {
-                        const double density = (d2 / (c * L.s)) * chance;
-                        if (usable_density(density)) {
-                            valid = true;
-                            dir = unit_d;
-                            distance = len;
-                            pdf = density;
-                        }
-                    }
-                }
-                u = ua;
-                v = ub;
-            } else {
-                Vec p;
-                double s;
-                do {  // the lens loop of camera_ray
-                    const double da = (double)xorwow_uniform(rng);
-                    const double db = (double)xorwow_uniform(rng);
-                    p = mk(2.0 * da - 1.0, 2.0 * db - 1.0, 0.0);
-                    s = p.x * p.x + p.y * p.y;
-                } while (!(s < 1.0 && s > 0.0));
-                centre = light_centre(L, tm);
-                const Vec oc = centre - P;
-                const double d2 = dot(oc, oc), r2 = L.s * L.s;
-                if (d2 > r2) {
-                    const Vec w = over(oc, sqrt(d2));
-                    const double cosmax = sqrt(1.0 - r2 / d2);
-                    const double omc = 1.0 - cosmax;
-                    const double z = 1.0 - s * omc;
-                    const double rho = sqrt(1.0 - z * z);
-                    const double q = sqrt(s);
-                    const double ex = (rho * p.x) / q, ey = (rho * p.y) / q;
-                    const double ax = fabs(w.x), ay = fabs(w.y), az = fabs(w.z);
-                    Vec e1;
-                    if (ax >= ay && ax >= az) e1 = over(mk(w.z, 0.0, -w.x), sqrt(w.z * w.z + w.x * w.x));
-                    else if (ay >= az) e1 = over(mk(-w.y, w.x, 0.0), sqrt(w.y * w.y + w.x * w.x));
-                    else e1 = over(mk(0.0, -w.z, w.y), sqrt(w.z * w.z + w.y * w.y));
-                    const Vec e2 = cross(w, e1);
-                    const Vec g = (z * w + ex * e1) + ey * e2;
-                    const Vec unit_d = over(g, sqrt(dot(g, g)));
-                    // the near root as the renderer's own sphere test finds it for this ray (sphere_test / sphere_roots: R/Sphere.h:28-50),
-                    // operation by operation: a shadow ray along `unit_d` meets the lamp at this very parameter
-                    const Vec po = P - centre;
-                    const double qa = dot(unit_d, unit_d), qb = dot(po, unit_d), qc = dot(po, po) - r2;
-                    const double disc = qb * qb - qa * qc;
-                    const double len = (-qb - sqrt(disc)) / qa;
-                    const double density = chance / ((2.0 * kLightPi) * omc);
-                    if (omc != 0.0 && usable_density(density) && disc > 0.0 && len > 0.0) {
-                        valid = true;
-                        dir = unit_d;
-                        distance = len;
-                        pdf = density;
-                        S = P + len * unit_d;
-                    }
-                }
-            }
-            if (valid && (a.emitted || a.contribution)) {
-                const MatView mp = material_view<false>(sc, L.mat);
-                if (L.kind >= LIGHT_SPHERE && mp.u32(MAT_OFF(needs_uv)) != 0) sphere_uv((1 / L.s) * (S - centre), u, v);
-                emitted = material_texture<T>(sc, mp, mp.u32(MAT_OFF(tex_inline)), u, v, S);
-            }
-            if (valid && (a.scatter_pdf || a.contribution)) {
-                const uint32_t kind = a.material[k];
-                if (kind == MAT_LAMBERTIAN) {
-                    const double c = dot(load3(a.normal + (size_t)k * 3), dir);
-                    if (c > 0.0) scatter = (2.0 * ((c * c) * c)) / kLightPi;
-                } else if (kind == MAT_ISOTROPIC) {
-                    scatter = 1.0 / (4.0 * kLightPi);
-                }
-                if (scatter != 0.0) contribution = (scatter / pdf) * emitted;
             }
         }
-        if (a.direction) store3(a.direction, k, dir);
-        if (a.distance) a.distance[k] = distance;
-        if (a.light) a.light[k] = light;
-        if (a.pdf) a.pdf[k] = pdf;
-        if (a.emitted) store3(a.emitted, k, emitted);
-        if (a.scatter_pdf) a.scatter_pdf[k] = scatter;
-        if (a.contribution) store3(a.contribution, k, contribution);
-        if (a.rng_out) {  // may be the array the state came from: this lane has read its six words
-            uint32_t *w = a.rng_out + (size_t)k * 6;
-            w[0] = rng.d; w[1] = rng.v0; w[2] = rng.v1; w[3] = rng.v2; w[4] = rng.v3; w[5] = rng.v4;
+        u = ua;
+        v = ub;
+    } else {
+        Vec p;
+        double s;
+        do {  // the lens loop of camera_ray
+            const double da = (double)xorwow_uniform(rng);
+            const double db = (double)xorwow_uniform(rng);
+            p = mk(2.0 * da - 1.0, 2.0 * db - 1.0, 0.0);
+            s = p.x * p.x + p.y * p.y;
+        } while (!(s < 1.0 && s > 0.0));
+        centre = light_centre(L, tm);
+        const Vec oc = centre - P;
+        const double d2 = dot(oc, oc), r2 = L.s * L.s;
+        if (d2 > r2) {
+            const Vec w = over(oc, sqrt(d2));
+            const double cosmax = sqrt(1.0 - r2 / d2);
+            const double omc = 1.0 - cosmax;
+            const double z = 1.0 - s * omc;
+            const double rho = sqrt(1.0 - z * z);
+            const double q = sqrt(s);
+            const double ex = (rho * p.x) / q, ey = (rho * p.y) / q;
+            const double ax = fabs(w.x), ay = fabs(w.y), az = fabs(w.z);
+            Vec e1;
+            if (ax >= ay && ax >= az) e1 = over(mk(w.z, 0.0, -w.x), sqrt(w.z * w.z + w.x * w.x));
+            else if (ay >= az) e1 = over(mk(-w.y, w.x, 0.0), sqrt(w.y * w.y + w.x * w.x));
+            else e1 = over(mk(0.0, -w.z, w.y), sqrt(w.z * w.z + w.y * w.y));
+            const Vec e2 = cross(w, e1);
+            const Vec g = (z * w + ex * e1) + ey * e2;
+            const Vec unit_d = over(g, sqrt(dot(g, g)));
+            const Vec po = P - centre;
+            const double qa = dot(unit_d, unit_d), qb = dot(po, unit_d), qc = dot(po, po) - r2;
+            const double disc = qb * qb - qa * qc;
+            const double len = (-qb - sqrt(disc)) / qa;
+            const double density = chance / ((2.0 * kLightPi) * omc);
+            if (omc != 0.0 && usable_density(density) && disc > 0.0 && len > 0.0) {
+                valid = true;
+                dir = unit_d;
+                distance = len;
+                pdf = density;
+                S = P + len * unit_d;
+            }
         }
     }
-    count_valid(a.valid_counter, valid, wave_valid);
+    return valid;
 }
 
-template <int STRICT>
-__global__ __launch_bounds__(256) void light_pdf_kernel(DeviceScene sc, LightArgs a)
+// what the lamp of a valid sample emits towards the point: its material's texture at S, at the sample's (u, v) or, for a sphere
+// whose material reads them, at the sphere's own
+template <class T>
+DEV Vec light_emitted(const DeviceScene &sc, const LightRow &L, Vec S, Vec centre, double u, double v)
 {
-    __shared__ __attribute__((aligned(16))) double rows_lds[kLightLdsRows * kLightRowDoubles];
-    __shared__ __attribute__((aligned(16))) double cdf_lds[kLightLdsRows];
-    __shared__ uint32_t wave_valid[4];
-    stage_lights(a, rows_lds, cdf_lds);
-    const LightLds lds{rows_lds, cdf_lds};
-    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
-    const bool mine = k < a.count;
-    const size_t at3 = mine ? (size_t)k * 3 : 0;  // (a lane beyond the count reads ray 0 and writes nothing: the loop stays wave-uniform)
-    const Vec o = load3(a.point + at3), d = load3(a.direction_in + at3);
-    const double tm = a.time ? a.time[mine ? k : 0] : a.time_all;
+    const MatView mp = material_view<false>(sc, L.mat);
+    if (L.kind >= LIGHT_SPHERE && mp.u32(MAT_OFF(needs_uv)) != 0) sphere_uv((1 / L.s) * (S - centre), u, v);
+    return material_texture<T>(sc, mp, mp.u32(MAT_OFF(tex_inline)), u, v, S);
+}
+
+// the density with which a material of this kind sends a ray from a hit with shading normal n along the unit direction d, in
+// closed form: 2 cos^3 / pi above a Lambertian surface, 1 / 4 pi for an isotropic medium; no other kind has one (0)
+[[maybe_unused]] DEV double scatter_density(uint32_t kind, Vec n, Vec d)
+{
+    if (kind == MAT_LAMBERTIAN) {
+        const double c = dot(n, d);
+        return c > 0.0 ? (2.0 * ((c * c) * c)) / kLightPi : 0.0;
+    }
+    return kind == MAT_ISOTROPIC ? 1.0 / (4.0 * kLightPi) : 0.0;
+}
+
+// What a path that scattered from a Lambertian or isotropic hit (kind, normal) into `ray` does about the lights (include/rtow.h
+// rt_scene_path_advance_direct; the three path kernels): the three functions above for the point ray.o at the time ray.tm, drawn
+// from the path's stream; contribution = (scatter / pdf) * emitted.  Returns sampled, contribution != 0: then the sample waits to be
+// weighted behind the density loop, which is asked along it (along_o, along_d, along_tm), with light = next * contribution (next:
+// the path's throughput behind this bounce), other = its scatter density and `distance` where a shadow ray along it meets the lamp.
+// sent_next: the density with which the material sent the scattered ray where it goes, the closed form for its unit direction.
+template <class T>
+DEV bool path_light_sample(const DeviceScene &sc, const LightArgs &la, const LightLds &lds, const Ray &ray, uint32_t kind, Vec normal, Vec next,
+                           Xorwow &rng, Vec &along_o, Vec &along_d, double &along_tm, Vec &light, double &other, double &distance, double &sent_next)
+{
+    const Vec P = ray.o;
+    const double tm = ray.tm;
+    uint32_t row;
+    LightRow L;
+    Vec dir, S, centre, contribution = mk(0.0, 0.0, 0.0);
+    double pdf, u, v, scatter = 0.0;
+    if (light_sample(la, lds, P, tm, rng, row, L, dir, distance, pdf, S, centre, u, v)) {
+        const Vec emitted = light_emitted<T>(sc, L, S, centre, u, v);
+        scatter = scatter_density(kind, normal, dir);
+        if (scatter != 0.0) contribution = (scatter / pdf) * emitted;
+    }
+    const bool sampled = contribution.x != 0.0 || contribution.y != 0.0 || contribution.z != 0.0;
+    if (sampled) {
+        along_o = P;
+        along_d = dir;
+        along_tm = tm;
+        light = next * contribution;
+        other = scatter;
+    }
+    const Vec unit_next = (1 / sqrt((ray.d.x * ray.d.x + ray.d.y * ray.d.y) + ray.d.z * ray.d.z)) * ray.d;
+    sent_next = scatter_density(kind, normal, unit_next);
+    return sampled;
+}
+
+// The mixture density of rt_scene_light_pdf along the ray (o, d) at the time tm: the sum over the table of each light's chance
+// times the density with which light_sample would have drawn the direction d from o, where the ray meets the light (a plane
+// inside the parallelogram or triangle, a sphere seen from outside in front of o).  Wave-uniform: every lane on row i, an LDS
+// broadcast below the cap.  NEAREST (light_pdf_kernel): also the row of the usable light met at the smallest parameter, or -1,
+// into *nearest_light -- a template argument because the compiler did not drop the sphere's root and the comparison from the
+// path kernels, which ask for neither, when it was a null pointer (81 instructions in advance_direct's strict unit).  The loop
+// runs n_lights times.
+template <bool NEAREST = false>
+DEV double mixture_density(const LightArgs &a, const LightLds &lds, Vec o, Vec d, double tm, int32_t *nearest_light = nullptr)
+{
     const double dd = dot(d, d);
     double sum = 0.0, nearest = (double)INFINITY, before = 0.0;
     int32_t light = -1;
-    for (uint32_t i = 0; i < a.n_lights; i++) {  // every lane of the wave on row i
+    for (uint32_t i = 0; i < a.n_lights; i++) {
         const LightRow L = light_row(a, lds, i);
         const double upto = light_cdf(a, lds, i);
         const double chance = upto - before;
@@ -5405,18 +5436,87 @@ __global__ __launch_bounds__(256) void light_pdf_kernel(DeviceScene sc, LightArg
                 if (b > 0.0 && disc >= 0.0) {
                     const double omc = 1.0 - sqrt(1.0 - r2 / d2);
                     if (omc != 0.0) density = chance / ((2.0 * kLightPi) * omc);
-                    t = (b - sqrt(disc)) / dd;
+                    if constexpr (NEAREST) t = (b - sqrt(disc)) / dd;
                 }
             }
         }
         if (usable_density(density)) {
             sum = sum + density;
-            if (t < nearest) {
-                nearest = t;
-                light = (int32_t)i;
+            if constexpr (NEAREST) {
+                if (t < nearest) {
+                    nearest = t;
+                    light = (int32_t)i;
+                }
             }
         }
     }
+    if constexpr (NEAREST) *nearest_light = light;
+    return sum;
+}
+}  // namespace
+#endif
+
+#if RT_LIGHTS
+template <int STRICT, class T>
+__global__ __launch_bounds__(256) void light_sample_kernel(DeviceScene sc, LightArgs a)
+{
+    __shared__ __attribute__((aligned(16))) double rows_lds[kLightLdsRows * kLightRowDoubles];
+    __shared__ __attribute__((aligned(16))) double cdf_lds[kLightLdsRows];
+    __shared__ uint32_t wave_valid[4];
+    global_tables_only(sc);
+    stage_lights(a, rows_lds, cdf_lds);
+    const LightLds lds{rows_lds, cdf_lds};
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    bool valid = false;
+    if (k < a.count) {
+        // the point and the six words are read here, before anything is written: rng_out may be rng_in
+        const Vec P = load3(a.point + (size_t)k * 3);
+        const double tm = a.time ? a.time[k] : a.time_all;
+        Xorwow rng = lane_stream(a, k);
+        Vec dir = mk(0.0, 0.0, 0.0), emitted = mk(0.0, 0.0, 0.0), contribution = mk(0.0, 0.0, 0.0);
+        double distance = 0.0, pdf = 0.0, scatter = 0.0;
+        int32_t light = -1;
+        if (a.n_lights != 0) {
+            uint32_t row;
+            LightRow L;
+            Vec S, centre;
+            double u, v;
+            valid = light_sample(a, lds, P, tm, rng, row, L, dir, distance, pdf, S, centre, u, v);
+            light = (int32_t)row;
+            if (valid && (a.emitted || a.contribution)) emitted = light_emitted<T>(sc, L, S, centre, u, v);
+            if (valid && (a.scatter_pdf || a.contribution)) {
+                const uint32_t kind = a.material[k];
+                scatter = scatter_density(kind, kind == MAT_LAMBERTIAN ? load3(a.normal + (size_t)k * 3) : mk(0.0, 0.0, 0.0), dir);  // (only it reads the normal)
+                if (scatter != 0.0) contribution = (scatter / pdf) * emitted;
+            }
+        }
+        if (a.direction) store3(a.direction, k, dir);
+        if (a.distance) a.distance[k] = distance;
+        if (a.light) a.light[k] = light;
+        if (a.pdf) a.pdf[k] = pdf;
+        if (a.emitted) store3(a.emitted, k, emitted);
+        if (a.scatter_pdf) a.scatter_pdf[k] = scatter;
+        if (a.contribution) store3(a.contribution, k, contribution);
+        if (a.rng_out) store_stream(a.rng_out + (size_t)k * 6, 1, rng);
+    }
+    count_valid(a.valid_counter, valid, wave_valid);
+}
+
+template <int STRICT>
+__global__ __launch_bounds__(256) void light_pdf_kernel(DeviceScene sc, LightArgs a)
+{
+    __shared__ __attribute__((aligned(16))) double rows_lds[kLightLdsRows * kLightRowDoubles];
+    __shared__ __attribute__((aligned(16))) double cdf_lds[kLightLdsRows];
+    __shared__ uint32_t wave_valid[4];
+    stage_lights(a, rows_lds, cdf_lds);
+    const LightLds lds{rows_lds, cdf_lds};
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    const bool mine = k < a.count;
+    const size_t at3 = mine ? (size_t)k * 3 : 0;  // (a lane beyond the count reads ray 0 and writes nothing: the loop stays wave-uniform)
+    const Vec o = load3(a.point + at3), d = load3(a.direction_in + at3);
+    const double tm = a.time ? a.time[mine ? k : 0] : a.time_all;
+    int32_t light;
+    const double sum = mixture_density<true>(a, lds, o, d, tm, &light);
     if (mine) {
         if (a.pdf) a.pdf[k] = sum;
         if (a.light) a.light[k] = light;
@@ -5442,14 +5542,13 @@ hipError_t RT_CAT(launch_light_pdf_, RT_SUFFIX)(const DeviceScene &sc, const Lig
 // (render_iface.h AdvanceDirectArgs).  The world is searched twice for a row that scatters from a diffuse hit -- once for the
 // path, once for the shadow ray -- and the two searches are two kernels: one kernel with both would hold the registers and the
 // scratch of the larger through the other, and every lane whose path ended would idle through the second.
-//   advance_direct_kernel: advance_kernel's iteration restated line for line; then, for a row that scattered from a Lambertian or
-//   isotropic hit, light_sample_kernel's sample restated from the path's own stream; then, every lane of the wave here again, one
-//   loop over the light table, every lane on the same row (light_pdf_kernel's loop restated), for the one density a lane can
-//   need: along its incoming ray where it ended on a lamp with a density carried in, along its sample where it scattered.  A wave
-//   in which no lane needs one skips the loop.  The table is staged in LDS as the light kernels stage it.
-//   shadow_kernel: query_kernel's occlusion search for the rows launch 1 left pending.
-// No lane returns before a barrier, no workgroup waits for another.  Termination: as for advance_kernel, the rejection loop of the
-// sphere sample depends on the stream alone, the density loop runs n_lights times, the search is the ray queries'.
+//   advance_direct_kernel: advance_kernel's iteration (its search in text, bounce); then, for a row that scattered from a Lambertian or
+//   isotropic hit, path_light_sample from the path's own stream; then, every lane of the wave here again, mixture_density for the
+//   one density a lane can need: along its incoming ray where it ended on a lamp with a density carried in, along its sample
+//   where it scattered.  A wave in which no lane needs one skips the loop.  The table is staged in LDS as the light kernels stage it.
+//   shadow_kernel: query_kernel's occlusion search (query_search) for the rows launch 1 left pending.
+// No lane returns before a barrier, no workgroup waits for another.  Termination: as for advance_kernel, and as light_sample,
+// mixture_density and query_search say.
 // ------------------------------------------------------------------------------------------------
 template <int STRICT, class T>
 __global__ __launch_bounds__(256) void advance_direct_kernel(DeviceScene sc, AdvanceDirectArgs d)
@@ -5475,14 +5574,7 @@ __global__ __launch_bounds__(256) void advance_direct_kernel(DeviceScene sc, Adv
     int32_t id = -1;
     if (stepped) {
         Ray ray = caller_ray(a.origin, a.direction, a.time, a.time_all, k);
-        Xorwow rng;
-        if (a.rng_in) {  // {d, v0..v4} as rt_rng_state writes them
-            const uint32_t *w = a.rng_in + (size_t)k * 6;
-            rng.d = w[0]; rng.v0 = w[1]; rng.v1 = w[2]; rng.v2 = w[3]; rng.v3 = w[4]; rng.v4 = w[5];
-        } else {  // curand_init(seed, k + first_sequence, 0)
-            rng = a.base;
-            xorwow_skip_sequences(a.jump_table, a.first_sequence + (uint64_t)k, rng);
-        }
+        Xorwow rng = lane_stream(a, k);
         const NodeView nv{sc.nodes, 0u, false};
         Vec throughput = mk(1.0, 1.0, 1.0), accumulated = mk(0.0, 0.0, 0.0);
         HitInfo h;
@@ -5503,19 +5595,10 @@ __global__ __launch_bounds__(256) void advance_direct_kernel(DeviceScene sc, Adv
         } else {
             hit = world_hit_list<T>(sc, ray, 0.001, DBL_MAX, h, rng);
         }
-        Vec normal = mk(0.0, 0.0, 0.0);
-        uint32_t kind = 255u;
-        bool front = false;
-        if (!hit) {  // R/kernel.cu:74-79
-            accumulated = accumulated + throughput * load3c(((const RT_CONST CameraRec *)(uintptr_t)sc.camera)->bg);
-        } else {
-            const Surface s = make_surface<T>(sc, ray, h);
-            if ((h.ref >> kRefShift) != REF_MEDIUM) normal = s.n;
-            front = s.front;
-            kind = material_view<false>(sc, s.mat).u32(MAT_OFF(kind));
-            scattered = shade<T>(sc, s, ray, throughput, accumulated, rng);  // scattered: `ray` is the next ray; else it is untouched
-        }
-        normal = mk(0.0, 0.0, 0.0) + normal;  // as query_kernel: no negative zeros
+        Vec normal;
+        uint32_t kind;
+        bool front;
+        scattered = bounce<T>(sc, ray, h, hit, rng, throughput, accumulated, true, true, normal, front, kind);
         const Vec carried = a.throughput ? mk(a.throughput[(size_t)k * 3 + 0], a.throughput[(size_t)k * 3 + 1], a.throughput[(size_t)k * 3 + 2])
                                          : mk(1.0, 1.0, 1.0);
         id = a.ray_id ? a.ray_id[k] : (int32_t)k;
@@ -5540,127 +5623,12 @@ __global__ __launch_bounds__(256) void advance_direct_kernel(DeviceScene sc, Adv
             const Vec next = carried * throughput;
             double sent_next = 0.0;
             if ((kind == MAT_LAMBERTIAN || kind == MAT_ISOTROPIC) && d.n_lights != 0 && d.sample != 0) {
-                // light_sample_kernel's sample for the point ray.o at the time ray.tm, from the path's stream
-                const Vec P = ray.o;
-                const double tm = ray.tm;
-                bool valid = false;
-                Vec dir = mk(0.0, 0.0, 0.0), emitted = mk(0.0, 0.0, 0.0), contribution = mk(0.0, 0.0, 0.0);
-                double pdf = 0.0, scatter = 0.0;
-                const double xi = (double)xorwow_uniform(rng);
-                uint32_t lo = 0, hi = d.n_lights - 1u;  // the first row with cdf >= xi; the last entry is 1.0 >= xi
-                while (lo < hi) {
-                    const uint32_t mid = (lo + hi) / 2u;
-                    if (light_cdf(la, lds, mid) >= xi) hi = mid;
-                    else lo = mid + 1u;
-                }
-                const double chance = light_cdf(la, lds, lo) - (lo ? light_cdf(la, lds, lo - 1u) : 0.0);
-                const LightRow L = light_row(la, lds, lo);
-                Vec S = mk(0.0, 0.0, 0.0), centre = mk(0.0, 0.0, 0.0);
-                double u = 0.0, v = 0.0;
-                if (L.kind <= LIGHT_TRIANGLE) {
-                    double ua = (double)xorwow_uniform(rng);
-                    double ub = (double)xorwow_uniform(rng);
-                    if (L.kind == LIGHT_TRIANGLE && ua + ub > 1.0) {
-                        ua = 1.0 - ua;
-                        ub = 1.0 - ub;
-                    }
-                    S = (load3(L.a) + ua * load3(L.b)) + ub * load3(L.c);
-                    const Vec D = S - P;
-                    const double d2 = dot(D, D);
-                    if (d2 > 0.0) {
-                        const double len = sqrt(d2);
-                        const Vec unit_d = over(D, len);
-                        const double c = fabs(dot(load3(L.n), unit_d));
-                        if (c != 0.0) {
-                            const double density = (d2 / (c * L.s)) * chance;
-                            if (usable_density(density)) {
-                                valid = true;
-                                dir = unit_d;
-                                distance = len;
-                                pdf = density;
-                            }
-                        }
-                    }
-                    u = ua;
-                    v = ub;
-                } else {
-                    Vec p;
-                    double s;
-                    do {  // the lens loop of camera_ray
-                        const double da = (double)xorwow_uniform(rng);
-                        const double db = (double)xorwow_uniform(rng);
-                        p = mk(2.0 * da - 1.0, 2.0 * db - 1.0, 0.0);
-                        s = p.x * p.x + p.y * p.y;
-                    } while (!(s < 1.0 && s > 0.0));
-                    centre = light_centre(L, tm);
-                    const Vec oc = centre - P;
-                    const double d2 = dot(oc, oc), r2 = L.s * L.s;
-                    if (d2 > r2) {
-                        const Vec w = over(oc, sqrt(d2));
-                        const double cosmax = sqrt(1.0 - r2 / d2);
-                        const double omc = 1.0 - cosmax;
-                        const double z = 1.0 - s * omc;
-                        const double rho = sqrt(1.0 - z * z);
-                        const double q = sqrt(s);
-                        const double ex = (rho * p.x) / q, ey = (rho * p.y) / q;
-                        const double ax = fabs(w.x), ay = fabs(w.y), az = fabs(w.z);
-                        Vec e1;
-                        if (ax >= ay && ax >= az) e1 = over(mk(w.z, 0.0, -w.x), sqrt(w.z * w.z + w.x * w.x));
-                        else if (ay >= az) e1 = over(mk(-w.y, w.x, 0.0), sqrt(w.y * w.y + w.x * w.x));
-                        else e1 = over(mk(0.0, -w.z, w.y), sqrt(w.z * w.z + w.y * w.y));
-                        const Vec e2 = cross(w, e1);
-                        const Vec g = (z * w + ex * e1) + ey * e2;
-                        const Vec unit_d = over(g, sqrt(dot(g, g)));
-                        const Vec po = P - centre;
-                        const double qa = dot(unit_d, unit_d), qb = dot(po, unit_d), qc = dot(po, po) - r2;
-                        const double disc = qb * qb - qa * qc;
-                        const double len = (-qb - sqrt(disc)) / qa;
-                        const double density = chance / ((2.0 * kLightPi) * omc);
-                        if (omc != 0.0 && usable_density(density) && disc > 0.0 && len > 0.0) {
-                            valid = true;
-                            dir = unit_d;
-                            distance = len;
-                            pdf = density;
-                            S = P + len * unit_d;
-                        }
-                    }
-                }
-                if (valid) {
-                    const MatView mp = material_view<false>(sc, L.mat);
-                    if (L.kind >= LIGHT_SPHERE && mp.u32(MAT_OFF(needs_uv)) != 0) sphere_uv((1 / L.s) * (S - centre), u, v);
-                    emitted = material_texture<T>(sc, mp, mp.u32(MAT_OFF(tex_inline)), u, v, S);
-                    if (kind == MAT_LAMBERTIAN) {
-                        const double c = dot(normal, dir);
-                        if (c > 0.0) scatter = (2.0 * ((c * c) * c)) / kLightPi;
-                    } else {
-                        scatter = 1.0 / (4.0 * kLightPi);
-                    }
-                    if (scatter != 0.0) contribution = (scatter / pdf) * emitted;
-                }
-                sampled = contribution.x != 0.0 || contribution.y != 0.0 || contribution.z != 0.0;
-                if (sampled) {  // weighted behind the density loop, along the sample
-                    along_o = P;
-                    along_d = dir;
-                    along_tm = tm;
-                    light = next * contribution;
-                    other = scatter;
-                }
-                // the density with which the material sent the scattered ray where it goes: the closed form above for its unit direction
-                const Vec unit_next = (1 / sqrt((ray.d.x * ray.d.x + ray.d.y * ray.d.y) + ray.d.z * ray.d.z)) * ray.d;
-                if (kind == MAT_LAMBERTIAN) {
-                    const double c = dot(normal, unit_next);
-                    if (c > 0.0) sent_next = (2.0 * ((c * c) * c)) / kLightPi;
-                } else {
-                    sent_next = 1.0 / (4.0 * kLightPi);
-                }
+                sampled = path_light_sample<T>(sc, la, lds, ray, kind, normal, next, rng, along_o, along_d, along_tm, light, other, distance, sent_next);
             }
             if (a.stage.origin) store3(a.stage.origin, k, ray.o);
             if (a.stage.direction) store3(a.stage.direction, k, ray.d);
             if (a.stage.time) a.stage.time[k] = ray.tm;
-            if (a.stage.rng_state) {  // the stream after the last draw, the sample's included
-                uint32_t *w = a.stage.rng_state + (size_t)k * 6;
-                w[0] = rng.d; w[1] = rng.v0; w[2] = rng.v1; w[3] = rng.v2; w[4] = rng.v3; w[5] = rng.v4;
-            }
+            if (a.stage.rng_state) store_stream(a.stage.rng_state + (size_t)k * 6, 1, rng);  // the stream after the last draw, the sample's included
             if (a.stage.throughput) store3(a.stage.throughput, k, next);
             if (a.stage.ray_id) a.stage.ray_id[k] = id;
             if (a.stage.t) a.stage.t[k] = h.t;
@@ -5670,49 +5638,10 @@ __global__ __launch_bounds__(256) void advance_direct_kernel(DeviceScene sc, Adv
             d.scatter_pdf_stage[k] = sent_next;
         }
     }
-    // every lane of the workgroup is here again.  The mixture density along `along`: light_pdf_kernel's loop, every lane of the wave
-    // on row i (a lane that needs none runs it on a ray of its own that meets what it meets: its sum is not read)
+    // every lane of the workgroup is here again.  The mixture density along `along`, every lane of the wave on the same row (a lane
+    // that needs none runs the loop on a ray of its own that meets what it meets: its sum is not read)
     double density_sum = 0.0;
-    if (__ballot(lamp || sampled) != 0ull) {
-        const Vec o = along_o, dv = along_d;
-        const double tm = along_tm;
-        const double dd = dot(dv, dv);
-        double before = 0.0;
-        for (uint32_t i = 0; i < d.n_lights; i++) {
-            const LightRow L = light_row(la, lds, i);
-            const double upto = light_cdf(la, lds, i);
-            const double chance = upto - before;
-            before = upto;
-            double density = 0.0;
-            if (L.kind <= LIGHT_TRIANGLE) {
-                const Vec nn = load3(L.n), Q = load3(L.a), U = load3(L.b), V = load3(L.c);
-                const double denom = dot(nn, dv);
-                if (denom != 0.0) {
-                    const double t = dot(nn, Q - o) / denom;
-                    if (t > 0.0) {
-                        const Vec ph = (o + t * dv) - Q;
-                        const Vec m = cross(U, V);
-                        const double mm = dot(m, m);
-                        const double alpha = dot(m, cross(ph, V)) / mm, beta = dot(m, cross(U, ph)) / mm;
-                        const bool below = L.kind == LIGHT_TRIANGLE ? alpha + beta <= 1.0 : (alpha <= 1.0 && beta <= 1.0);
-                        if (0.0 <= alpha && 0.0 <= beta && below) density = (((t * t) * dd) / ((fabs(denom) / sqrt(dd)) * L.s)) * chance;
-                    }
-                }
-            } else {
-                const Vec oc = light_centre(L, tm) - o;
-                const double d2 = dot(oc, oc), r2 = L.s * L.s;
-                if (d2 > r2) {
-                    const double b = dot(oc, dv);
-                    const double disc = b * b - dd * (d2 - r2);
-                    if (b > 0.0 && disc >= 0.0) {
-                        const double omc = 1.0 - sqrt(1.0 - r2 / d2);
-                        if (omc != 0.0) density = chance / ((2.0 * kLightPi) * omc);
-                    }
-                }
-            }
-            if (usable_density(density)) density_sum = density_sum + density;
-        }
-    }
+    if (__ballot(lamp || sampled) != 0ull) density_sum = mixture_density(la, lds, along_o, along_d, along_tm);
     if (lamp) {  // w = q / (q + p): the scattered ray found the lamp a light sample of the bounce before could have found
         const double w = other / (other + density_sum);
         double *row = a.radiance + (size_t)id * 3;
@@ -5728,23 +5657,12 @@ __global__ __launch_bounds__(256) void advance_direct_kernel(DeviceScene sc, Adv
         d.shadow_distance[k] = distance;
         store3(d.shadow_radiance, k, w * light);
     }
-    if (k < a.capacity) {
-        a.survivor[k] = scattered ? 1 : 0;
-        d.pending[k] = sampled ? 1 : 0;
-    }
-    const unsigned long long survivors = __ballot(scattered);
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    if (lane == 0) wave_survivors[wave] = (uint32_t)__popcll(survivors);
-    if (a.stepped_counter) {  // one atomic per wave
-        const unsigned long long took = __ballot(stepped);
-        if (lane == 0 && took) atomicAdd(a.stepped_counter, (unsigned long long)__popcll(took));
-    }
-    if (d.shadow_counters) {
+    if (k < a.capacity) d.pending[k] = sampled ? 1 : 0;
+    if (d.shadow_counters) {  // one atomic per wave
         const unsigned long long cast = __ballot(sampled);
-        if (lane == 0 && cast) atomicAdd(d.shadow_counters, (unsigned long long)__popcll(cast));
+        if ((threadIdx.x & 63u) == 0 && cast) atomicAdd(d.shadow_counters, (unsigned long long)__popcll(cast));
     }
-    __syncthreads();
-    if (threadIdx.x == 0) a.block_counts[blockIdx.x] = (wave_survivors[0] + wave_survivors[1]) + (wave_survivors[2] + wave_survivors[3]);
+    count_survivors(a, k, stepped, scattered, wave_survivors);
 }
 
 // Launch 2: row k's shadow ray (staged origin, shadow direction, staged time) over (0.001, distance * (1 - 2^-20)), searched as
@@ -5767,15 +5685,11 @@ __global__ __launch_bounds__(256) void shadow_kernel(DeviceScene sc, AdvanceDire
         const bool media = (sc.flags & SCENE_HAS_MEDIA) != 0;
         Xorwow rng{};
         uint32_t *w = a.stage.rng_state + (size_t)k * 6;
-        if (media) {
-            rng.d = w[0]; rng.v0 = w[1]; rng.v1 = w[2]; rng.v2 = w[3]; rng.v3 = w[4]; rng.v4 = w[5];
-        }
+        if (media) rng = load_stream(w, 1);
         HitInfo h;
         uint32_t leaf = kNone;
         reached = !query_search<T>(sc, d.node_leaf_pos, ray, 0.001, tmax, !media, h, leaf, rng);  // a medium's answer depends on what was found before it: the full search
-        if (media) {
-            w[0] = rng.d; w[1] = rng.v0; w[2] = rng.v1; w[3] = rng.v2; w[4] = rng.v3; w[5] = rng.v4;
-        }
+        if (media) store_stream(w, 1, rng);
         const int32_t id = a.stage.ray_id[k];
         if (reached && a.radiance && id >= 0 && (uint32_t)id < a.sources) {
             double *row = a.radiance + (size_t)id * 3;
@@ -5826,15 +5740,15 @@ hipError_t RT_CAT(launch_advance_shadow_, RT_SUFFIX)(const DeviceScene &sc, cons
 // query_search, which takes the interval and the early exit as arguments -- lanes in the two phases share the search code, and no
 // lane idles through a second search.  The state beside the search is one path's: the shadow ray shares the path ray's origin and
 // time, so a pending sample costs its direction, its end and its weighted light (seven doubles).
-//   after a path search: advance_direct_kernel's step, light sample and fold restated line for line -- shade from throughput
-//   (1, 1, 1) and accumulated (0, 0, 0), the carried throughput multiplied in behind it, as the advance does;
-//   then, every lane still in the loop here again, the density loop over the LDS-staged light table, every lane on the same row,
+//   after a path search: advance_direct_kernel's step, light sample and fold -- bounce from throughput (1, 1, 1) and accumulated
+//   (0, 0, 0), the carried throughput multiplied in behind it, as the advance does, then path_light_sample;
+//   then, every lane still in the loop here again, mixture_density over the LDS-staged light table, every lane on the same row,
 //   skipped where no lane of the wave needs a density (a lane in its shadow phase never does);
 //   after a shadow search: the parked light is added where nothing was found, and the lane is back on its path ray.
 // A path ends only where no sample is pending (an ended path draws none, the last bounce takes none): it folds into the sum and the
 // next sample starts in the same iteration.  Every lane, k >= count included, reaches the barriers of stage_lights; there is none
-// behind them.  Termination: at most samples * max_depth path searches and as many shadow searches, each bounded (the ray queries'
-// argument); the rejection loops depend on the stream alone; the density loop runs n_lights times.
+// behind them.  Termination: at most samples * max_depth path searches and as many shadow searches, each bounded (the argument
+// on the two searches), each followed by bounded helpers.
 // ------------------------------------------------------------------------------------------------
 template <int STRICT, class T>
 __global__ __launch_bounds__(256) void radiance_direct_kernel(DeviceScene sc, RadianceDirectArgs d)
@@ -5853,14 +5767,7 @@ __global__ __launch_bounds__(256) void radiance_direct_kernel(DeviceScene sc, Ra
     uint32_t rays = 0, cast = 0, reached = 0;  // path searches, shadow searches, shadow rays that met nothing: this lane's, all samples
     if (k < a.count) {
         const Ray first = caller_ray(a.origin, a.direction, a.time, a.time_all, k);
-        Xorwow rng;
-        if (a.rng_in) {  // {d, v0..v4} as rt_rng_state writes them
-            const uint32_t *w = a.rng_in + (size_t)k * 6;
-            rng.d = w[0]; rng.v0 = w[1]; rng.v1 = w[2]; rng.v2 = w[3]; rng.v3 = w[4]; rng.v4 = w[5];
-        } else {  // curand_init(seed, k + first_sequence, 0)
-            rng = a.base;
-            xorwow_skip_sequences(a.jump_table, a.first_sequence + (uint64_t)k, rng);
-        }
+        Xorwow rng = lane_stream(a, k);
         const bool media = (sc.flags & SCENE_HAS_MEDIA) != 0;
         Vec sum = mk(0.0, 0.0, 0.0);
         if (a.max_depth > 0) {  // otherwise no bounce runs: black, nothing drawn
@@ -5898,18 +5805,10 @@ __global__ __launch_bounds__(256) void radiance_direct_kernel(DeviceScene sc, Ra
                 } else {
                     rays++;
                     Vec throughput = mk(1.0, 1.0, 1.0), accumulated = mk(0.0, 0.0, 0.0);
-                    Vec normal = mk(0.0, 0.0, 0.0);
-                    uint32_t kind = 255u;
-                    bool scattered = false;
-                    if (!hit) {  // R/kernel.cu:74-79
-                        accumulated = accumulated + throughput * load3c(((const RT_CONST CameraRec *)(uintptr_t)sc.camera)->bg);
-                    } else {
-                        const Surface s = make_surface<T>(sc, ray, h);
-                        if ((h.ref >> kRefShift) != REF_MEDIUM) normal = s.n;
-                        kind = material_view<false>(sc, s.mat).u32(MAT_OFF(kind));
-                        scattered = shade<T>(sc, s, ray, throughput, accumulated, rng);  // scattered: `ray` is the next ray; else it is untouched
-                    }
-                    normal = mk(0.0, 0.0, 0.0) + normal;  // as query_kernel: no negative zeros
+                    Vec normal;
+                    uint32_t kind;
+                    bool front;
+                    const bool scattered = bounce<T>(sc, ray, h, hit, rng, throughput, accumulated, true, true, normal, front, kind);
                     if (!scattered) {
                         path_ends = true;
                         lamp = hit && kind == MAT_DIFFUSE_LIGHT && sent > 0.0;
@@ -5927,168 +5826,17 @@ __global__ __launch_bounds__(256) void radiance_direct_kernel(DeviceScene sc, Ra
                         double sent_next = 0.0;
                         const bool sample_here = depth + 1 < a.max_depth;  // the last bounce takes none: its light sample would stand for bounce max_depth
                         if ((kind == MAT_LAMBERTIAN || kind == MAT_ISOTROPIC) && d.n_lights != 0 && sample_here) {
-                            // light_sample_kernel's sample for the point ray.o at the time ray.tm, from the path's stream
-                            const Vec P = ray.o;
-                            const double tm = ray.tm;
-                            bool valid = false;
-                            Vec dir = mk(0.0, 0.0, 0.0), emitted = mk(0.0, 0.0, 0.0), contribution = mk(0.0, 0.0, 0.0);
-                            double pdf = 0.0, scatter = 0.0;
-                            const double xi = (double)xorwow_uniform(rng);
-                            uint32_t lo = 0, hi = d.n_lights - 1u;  // the first row with cdf >= xi; the last entry is 1.0 >= xi
-                            while (lo < hi) {
-                                const uint32_t mid = (lo + hi) / 2u;
-                                if (light_cdf(la, lds, mid) >= xi) hi = mid;
-                                else lo = mid + 1u;
-                            }
-                            const double chance = light_cdf(la, lds, lo) - (lo ? light_cdf(la, lds, lo - 1u) : 0.0);
-                            const LightRow L = light_row(la, lds, lo);
-                            Vec S = mk(0.0, 0.0, 0.0), centre = mk(0.0, 0.0, 0.0);
-                            double u = 0.0, v = 0.0;
-                            if (L.kind <= LIGHT_TRIANGLE) {
-                                double ua = (double)xorwow_uniform(rng);
-                                double ub = (double)xorwow_uniform(rng);
-                                if (L.kind == LIGHT_TRIANGLE && ua + ub > 1.0) {
-                                    ua = 1.0 - ua;
-                                    ub = 1.0 - ub;
-                                }
-                                S = (load3(L.a) + ua * load3(L.b)) + ub * load3(L.c);
-                                const Vec D = S - P;
-                                const double d2 = dot(D, D);
-                                if (d2 > 0.0) {
-                                    const double len = sqrt(d2);
-                                    const Vec unit_d = over(D, len);
-                                    const double c = fabs(dot(load3(L.n), unit_d));
-                                    if (c != 0.0) {
-                                        const double density = (d2 / (c * L.s)) * chance;
-                                        if (usable_density(density)) {
-                                            valid = true;
-                                            dir = unit_d;
-                                            distance = len;
-                                            pdf = density;
-                                        }
-                                    }
-                                }
-                                u = ua;
-                                v = ub;
-                            } else {
-                                Vec p;
-                                double s;
-                                do {  // the lens loop of camera_ray
-                                    const double da = (double)xorwow_uniform(rng);
-                                    const double db = (double)xorwow_uniform(rng);
-                                    p = mk(2.0 * da - 1.0, 2.0 * db - 1.0, 0.0);
-                                    s = p.x * p.x + p.y * p.y;
-                                } while (!(s < 1.0 && s > 0.0));
-                                centre = light_centre(L, tm);
-                                const Vec oc = centre - P;
-                                const double d2 = dot(oc, oc), r2 = L.s * L.s;
-                                if (d2 > r2) {
-                                    const Vec w = over(oc, sqrt(d2));
-                                    const double cosmax = sqrt(1.0 - r2 / d2);
-                                    const double omc = 1.0 - cosmax;
-                                    const double z = 1.0 - s * omc;
-                                    const double rho = sqrt(1.0 - z * z);
-                                    const double q = sqrt(s);
-                                    const double ex = (rho * p.x) / q, ey = (rho * p.y) / q;
-                                    const double ax = fabs(w.x), ay = fabs(w.y), az = fabs(w.z);
-                                    Vec e1;
-                                    if (ax >= ay && ax >= az) e1 = over(mk(w.z, 0.0, -w.x), sqrt(w.z * w.z + w.x * w.x));
-                                    else if (ay >= az) e1 = over(mk(-w.y, w.x, 0.0), sqrt(w.y * w.y + w.x * w.x));
-                                    else e1 = over(mk(0.0, -w.z, w.y), sqrt(w.z * w.z + w.y * w.y));
-                                    const Vec e2 = cross(w, e1);
-                                    const Vec g = (z * w + ex * e1) + ey * e2;
-                                    const Vec unit_d = over(g, sqrt(dot(g, g)));
-                                    const Vec po = P - centre;
-                                    const double qa = dot(unit_d, unit_d), qb = dot(po, unit_d), qc = dot(po, po) - r2;
-                                    const double disc = qb * qb - qa * qc;
-                                    const double len = (-qb - sqrt(disc)) / qa;
-                                    const double density = chance / ((2.0 * kLightPi) * omc);
-                                    if (omc != 0.0 && usable_density(density) && disc > 0.0 && len > 0.0) {
-                                        valid = true;
-                                        dir = unit_d;
-                                        distance = len;
-                                        pdf = density;
-                                        S = P + len * unit_d;
-                                    }
-                                }
-                            }
-                            if (valid) {
-                                const MatView mp = material_view<false>(sc, L.mat);
-                                if (L.kind >= LIGHT_SPHERE && mp.u32(MAT_OFF(needs_uv)) != 0) sphere_uv((1 / L.s) * (S - centre), u, v);
-                                emitted = material_texture<T>(sc, mp, mp.u32(MAT_OFF(tex_inline)), u, v, S);
-                                if (kind == MAT_LAMBERTIAN) {
-                                    const double c = dot(normal, dir);
-                                    if (c > 0.0) scatter = (2.0 * ((c * c) * c)) / kLightPi;
-                                } else {
-                                    scatter = 1.0 / (4.0 * kLightPi);
-                                }
-                                if (scatter != 0.0) contribution = (scatter / pdf) * emitted;
-                            }
-                            sampled = contribution.x != 0.0 || contribution.y != 0.0 || contribution.z != 0.0;
-                            if (sampled) {  // weighted behind the density loop, along the sample
-                                along_o = P;
-                                along_d = dir;
-                                along_tm = tm;
-                                light = next * contribution;
-                                other = scatter;
-                            }
-                            // the density with which the material sent the scattered ray where it goes: the closed form above for its unit direction
-                            const Vec unit_next = (1 / sqrt((ray.d.x * ray.d.x + ray.d.y * ray.d.y) + ray.d.z * ray.d.z)) * ray.d;
-                            if (kind == MAT_LAMBERTIAN) {
-                                const double c = dot(normal, unit_next);
-                                if (c > 0.0) sent_next = (2.0 * ((c * c) * c)) / kLightPi;
-                            } else {
-                                sent_next = 1.0 / (4.0 * kLightPi);
-                            }
+                            sampled = path_light_sample<T>(sc, la, lds, ray, kind, normal, next, rng, along_o, along_d, along_tm, light, other, distance, sent_next);
                         }
                         carried = next;
                         sent = sent_next;
                         if (++depth >= a.max_depth) path_ends = true;  // still alive after the last bounce: dropped (R/kernel.cu:71,97)
                     }
                 }
-                // every lane still in the loop is here again.  The mixture density along `along`: advance_direct_kernel's loop, every such
-                // lane of the wave on row i (a lane that needs none runs it on a ray of its own that meets what it meets: its sum is not read)
+                // every lane still in the loop is here again.  The mixture density along `along`, every such lane of the wave on the same
+                // row (a lane that needs none runs the loop on a ray of its own that meets what it meets: its sum is not read)
                 double density_sum = 0.0;
-                if (__ballot(lamp || sampled) != 0ull) {
-                    const Vec o = along_o, dv = along_d;
-                    const double tm = along_tm;
-                    const double dd = dot(dv, dv);
-                    double before = 0.0;
-                    for (uint32_t i = 0; i < d.n_lights; i++) {
-                        const LightRow L = light_row(la, lds, i);
-                        const double upto = light_cdf(la, lds, i);
-                        const double chance = upto - before;
-                        before = upto;
-                        double density = 0.0;
-                        if (L.kind <= LIGHT_TRIANGLE) {
-                            const Vec nn = load3(L.n), Q = load3(L.a), U = load3(L.b), V = load3(L.c);
-                            const double denom = dot(nn, dv);
-                            if (denom != 0.0) {
-                                const double t = dot(nn, Q - o) / denom;
-                                if (t > 0.0) {
-                                    const Vec ph = (o + t * dv) - Q;
-                                    const Vec m = cross(U, V);
-                                    const double mm = dot(m, m);
-                                    const double alpha = dot(m, cross(ph, V)) / mm, beta = dot(m, cross(U, ph)) / mm;
-                                    const bool below = L.kind == LIGHT_TRIANGLE ? alpha + beta <= 1.0 : (alpha <= 1.0 && beta <= 1.0);
-                                    if (0.0 <= alpha && 0.0 <= beta && below) density = (((t * t) * dd) / ((fabs(denom) / sqrt(dd)) * L.s)) * chance;
-                                }
-                            }
-                        } else {
-                            const Vec oc = light_centre(L, tm) - o;
-                            const double d2 = dot(oc, oc), r2 = L.s * L.s;
-                            if (d2 > r2) {
-                                const double b = dot(oc, dv);
-                                const double disc = b * b - dd * (d2 - r2);
-                                if (b > 0.0 && disc >= 0.0) {
-                                    const double omc = 1.0 - sqrt(1.0 - r2 / d2);
-                                    if (omc != 0.0) density = chance / ((2.0 * kLightPi) * omc);
-                                }
-                            }
-                        }
-                        if (usable_density(density)) density_sum = density_sum + density;
-                    }
-                }
+                if (__ballot(lamp || sampled) != 0ull) density_sum = mixture_density(la, lds, along_o, along_d, along_tm);
                 if (lamp) {  // w = q / (q + p): the scattered ray found the lamp a light sample of the bounce before could have found
                     const double w = other / (other + density_sum);
                     acc = acc + w * light;
@@ -6117,10 +5865,7 @@ __global__ __launch_bounds__(256) void radiance_direct_kernel(DeviceScene sc, Ra
             store3(a.radiance, k, mean);
         }
         if (a.path_rays) a.path_rays[k] = rays;
-        if (a.rng_out) {  // may be the array the state came from: this lane has read its six words
-            uint32_t *w = a.rng_out + (size_t)k * 6;
-            w[0] = rng.d; w[1] = rng.v0; w[2] = rng.v1; w[3] = rng.v2; w[4] = rng.v3; w[5] = rng.v4;
-        }
+        if (a.rng_out) store_stream(a.rng_out + (size_t)k * 6, 1, rng);
     }
     if (a.ray_counter) {  // three atomics per wave at the most: every lane of the wave is here again
         unsigned long long searched = rays, shadows = cast, unblocked = reached;
@@ -6238,12 +5983,7 @@ __global__ __launch_bounds__(256) void film_direct_kernel(DeviceScene sc, FilmDi
                         ad_before = d.ad_n[local];
                         ad_q = d.ad_q[local];
                     }
-                    rng.d = d.state[0 * (size_t)d.n_pixels + local];
-                    rng.v0 = d.state[1 * (size_t)d.n_pixels + local];
-                    rng.v1 = d.state[2 * (size_t)d.n_pixels + local];
-                    rng.v2 = d.state[3 * (size_t)d.n_pixels + local];
-                    rng.v3 = d.state[4 * (size_t)d.n_pixels + local];
-                    rng.v4 = d.state[5 * (size_t)d.n_pixels + local];
+                    rng = load_stream(d.state + local, (size_t)d.n_pixels);
                     col = mk(0.0, 0.0, 0.0);
                     if (d.accum && d.spp_before > 0)  // progressive: continue the running sum in the same order
                         col = mk(d.accum[local * 3 + 0], d.accum[local * 3 + 1], d.accum[local * 3 + 2]);
@@ -6291,18 +6031,10 @@ __global__ __launch_bounds__(256) void film_direct_kernel(DeviceScene sc, FilmDi
             } else {
                 rays++;
                 Vec throughput = mk(1.0, 1.0, 1.0), accumulated = mk(0.0, 0.0, 0.0);
-                Vec normal = mk(0.0, 0.0, 0.0);
-                uint32_t kind = 255u;
-                bool scattered = false;
-                if (!hit) {  // R/kernel.cu:74-79
-                    accumulated = accumulated + throughput * load3c(((const RT_CONST CameraRec *)(uintptr_t)sc.camera)->bg);
-                } else {
-                    const Surface s = make_surface<T>(sc, ray, h);
-                    if ((h.ref >> kRefShift) != REF_MEDIUM) normal = s.n;
-                    kind = material_view<false>(sc, s.mat).u32(MAT_OFF(kind));
-                    scattered = shade<T>(sc, s, ray, throughput, accumulated, rng);  // scattered: `ray` is the next ray; else it is untouched
-                }
-                normal = mk(0.0, 0.0, 0.0) + normal;  // as query_kernel: no negative zeros
+                Vec normal;
+                uint32_t kind;
+                bool front;
+                const bool scattered = bounce<T>(sc, ray, h, hit, rng, throughput, accumulated, true, true, normal, front, kind);
                 if (!scattered) {
                     path_ends = true;
                     lamp = hit && kind == MAT_DIFFUSE_LIGHT && sent > 0.0;
@@ -6320,119 +6052,7 @@ __global__ __launch_bounds__(256) void film_direct_kernel(DeviceScene sc, FilmDi
                     double sent_next = 0.0;
                     const bool sample_here = depth + 1 < d.max_depth;  // the last bounce takes none: its light sample would stand for bounce max_depth
                     if ((kind == MAT_LAMBERTIAN || kind == MAT_ISOTROPIC) && d.n_lights != 0 && sample_here) {
-                        // light_sample_kernel's sample for the point ray.o at the time ray.tm, from the path's stream
-                        const Vec P = ray.o;
-                        const double tm = ray.tm;
-                        bool valid = false;
-                        Vec dir = mk(0.0, 0.0, 0.0), emitted = mk(0.0, 0.0, 0.0), contribution = mk(0.0, 0.0, 0.0);
-                        double pdf = 0.0, scatter = 0.0;
-                        const double xi = (double)xorwow_uniform(rng);
-                        uint32_t lo = 0, hi = d.n_lights - 1u;  // the first row with cdf >= xi; the last entry is 1.0 >= xi
-                        while (lo < hi) {
-                            const uint32_t mid = (lo + hi) / 2u;
-                            if (light_cdf(la, lds, mid) >= xi) hi = mid;
-                            else lo = mid + 1u;
-                        }
-                        const double chance = light_cdf(la, lds, lo) - (lo ? light_cdf(la, lds, lo - 1u) : 0.0);
-                        const LightRow L = light_row(la, lds, lo);
-                        Vec S = mk(0.0, 0.0, 0.0), centre = mk(0.0, 0.0, 0.0);
-                        double u = 0.0, v = 0.0;
-                        if (L.kind <= LIGHT_TRIANGLE) {
-                            double ua = (double)xorwow_uniform(rng);
-                            double ub = (double)xorwow_uniform(rng);
-                            if (L.kind == LIGHT_TRIANGLE && ua + ub > 1.0) {
-                                ua = 1.0 - ua;
-                                ub = 1.0 - ub;
-                            }
-                            S = (load3(L.a) + ua * load3(L.b)) + ub * load3(L.c);
-                            const Vec D = S - P;
-                            const double d2 = dot(D, D);
-                            if (d2 > 0.0) {
-                                const double len = sqrt(d2);
-                                const Vec unit_d = over(D, len);
-                                const double c = fabs(dot(load3(L.n), unit_d));
-                                if (c != 0.0) {
-                                    const double density = (d2 / (c * L.s)) * chance;
-                                    if (usable_density(density)) {
-                                        valid = true;
-                                        dir = unit_d;
-                                        distance = len;
-                                        pdf = density;
-                                    }
-                                }
-                            }
-                            u = ua;
-                            v = ub;
-                        } else {
-                            Vec p;
-                            double s;
-                            do {  // the lens loop of camera_ray
-                                const double da = (double)xorwow_uniform(rng);
-                                const double db = (double)xorwow_uniform(rng);
-                                p = mk(2.0 * da - 1.0, 2.0 * db - 1.0, 0.0);
-                                s = p.x * p.x + p.y * p.y;
-                            } while (!(s < 1.0 && s > 0.0));
-                            centre = light_centre(L, tm);
-                            const Vec oc = centre - P;
-                            const double d2 = dot(oc, oc), r2 = L.s * L.s;
-                            if (d2 > r2) {
-                                const Vec w = over(oc, sqrt(d2));
-                                const double cosmax = sqrt(1.0 - r2 / d2);
-                                const double omc = 1.0 - cosmax;
-                                const double z = 1.0 - s * omc;
-                                const double rho = sqrt(1.0 - z * z);
-                                const double q = sqrt(s);
-                                const double ex = (rho * p.x) / q, ey = (rho * p.y) / q;
-                                const double ax = fabs(w.x), ay = fabs(w.y), az = fabs(w.z);
-                                Vec e1;
-                                if (ax >= ay && ax >= az) e1 = over(mk(w.z, 0.0, -w.x), sqrt(w.z * w.z + w.x * w.x));
-                                else if (ay >= az) e1 = over(mk(-w.y, w.x, 0.0), sqrt(w.y * w.y + w.x * w.x));
-                                else e1 = over(mk(0.0, -w.z, w.y), sqrt(w.z * w.z + w.y * w.y));
-                                const Vec e2 = cross(w, e1);
-                                const Vec g = (z * w + ex * e1) + ey * e2;
-                                const Vec unit_d = over(g, sqrt(dot(g, g)));
-                                const Vec po = P - centre;
-                                const double qa = dot(unit_d, unit_d), qb = dot(po, unit_d), qc = dot(po, po) - r2;
-                                const double disc = qb * qb - qa * qc;
-                                const double len = (-qb - sqrt(disc)) / qa;
-                                const double density = chance / ((2.0 * kLightPi) * omc);
-                                if (omc != 0.0 && usable_density(density) && disc > 0.0 && len > 0.0) {
-                                    valid = true;
-                                    dir = unit_d;
-                                    distance = len;
-                                    pdf = density;
-                                    S = P + len * unit_d;
-                                }
-                            }
-                        }
-                        if (valid) {
-                            const MatView mp = material_view<false>(sc, L.mat);
-                            if (L.kind >= LIGHT_SPHERE && mp.u32(MAT_OFF(needs_uv)) != 0) sphere_uv((1 / L.s) * (S - centre), u, v);
-                            emitted = material_texture<T>(sc, mp, mp.u32(MAT_OFF(tex_inline)), u, v, S);
-                            if (kind == MAT_LAMBERTIAN) {
-                                const double c = dot(normal, dir);
-                                if (c > 0.0) scatter = (2.0 * ((c * c) * c)) / kLightPi;
-                            } else {
-                                scatter = 1.0 / (4.0 * kLightPi);
-                            }
-                            if (scatter != 0.0) contribution = (scatter / pdf) * emitted;
-                        }
-                        sampled = contribution.x != 0.0 || contribution.y != 0.0 || contribution.z != 0.0;
-                        if (sampled) {  // weighted behind the density loop, along the sample
-                            along_o = P;
-                            along_d = dir;
-                            along_tm = tm;
-                            light = next * contribution;
-                            other = scatter;
-                        }
-                        // the density with which the material sent the scattered ray where it goes: the closed form above for its unit direction
-                        const Vec unit_next = (1 / sqrt((ray.d.x * ray.d.x + ray.d.y * ray.d.y) + ray.d.z * ray.d.z)) * ray.d;
-                        if (kind == MAT_LAMBERTIAN) {
-                            const double c = dot(normal, unit_next);
-                            if (c > 0.0) sent_next = (2.0 * ((c * c) * c)) / kLightPi;
-                        } else {
-                            sent_next = 1.0 / (4.0 * kLightPi);
-                        }
+                        sampled = path_light_sample<T>(sc, la, lds, ray, kind, normal, next, rng, along_o, along_d, along_tm, light, other, distance, sent_next);
                     }
                     carried = next;
                     sent = sent_next;
@@ -6440,49 +6060,10 @@ __global__ __launch_bounds__(256) void film_direct_kernel(DeviceScene sc, FilmDi
                 }
             }
         }
-        // every lane that holds a pixel is here again.  The mixture density along `along`: radiance_direct_kernel's loop, every such
-        // lane of the wave on row i (a lane that needs none runs it on a ray of its own that meets what it meets: its sum is not read)
+        // every lane that holds a pixel is here again.  The mixture density along `along`, every such lane of the wave on the same
+        // row (a lane that needs none runs the loop on a ray of its own that meets what it meets: its sum is not read)
         double density_sum = 0.0;
-        if (__ballot(lamp || sampled) != 0ull) {
-            const Vec o = along_o, dv = along_d;
-            const double tm = along_tm;
-            const double dd = dot(dv, dv);
-            double before = 0.0;
-            for (uint32_t k = 0; k < d.n_lights; k++) {
-                const LightRow L = light_row(la, lds, k);
-                const double upto = light_cdf(la, lds, k);
-                const double chance = upto - before;
-                before = upto;
-                double density = 0.0;
-                if (L.kind <= LIGHT_TRIANGLE) {
-                    const Vec nn = load3(L.n), Q = load3(L.a), U = load3(L.b), V = load3(L.c);
-                    const double denom = dot(nn, dv);
-                    if (denom != 0.0) {
-                        const double t = dot(nn, Q - o) / denom;
-                        if (t > 0.0) {
-                            const Vec ph = (o + t * dv) - Q;
-                            const Vec m = cross(U, V);
-                            const double mm = dot(m, m);
-                            const double alpha = dot(m, cross(ph, V)) / mm, beta = dot(m, cross(U, ph)) / mm;
-                            const bool below = L.kind == LIGHT_TRIANGLE ? alpha + beta <= 1.0 : (alpha <= 1.0 && beta <= 1.0);
-                            if (0.0 <= alpha && 0.0 <= beta && below) density = (((t * t) * dd) / ((fabs(denom) / sqrt(dd)) * L.s)) * chance;
-                        }
-                    }
-                } else {
-                    const Vec oc = light_centre(L, tm) - o;
-                    const double d2 = dot(oc, oc), r2 = L.s * L.s;
-                    if (d2 > r2) {
-                        const double b = dot(oc, dv);
-                        const double disc = b * b - dd * (d2 - r2);
-                        if (b > 0.0 && disc >= 0.0) {
-                            const double omc = 1.0 - sqrt(1.0 - r2 / d2);
-                            if (omc != 0.0) density = chance / ((2.0 * kLightPi) * omc);
-                        }
-                    }
-                }
-                if (usable_density(density)) density_sum = density_sum + density;
-            }
-        }
+        if (__ballot(lamp || sampled) != 0ull) density_sum = mixture_density(la, lds, along_o, along_d, along_tm);
         if (lamp) {  // w = q / (q + p): the scattered ray found the lamp a light sample of the bounce before could have found
             const double w = other / (other + density_sum);
             acc = acc + w * light;
@@ -6514,12 +6095,7 @@ __global__ __launch_bounds__(256) void film_direct_kernel(DeviceScene sc, FilmDi
                 depth = 0;
             } else {
                 // R/kernel.cu:146-153: save the RNG state, average, gamma 2
-                d.state[0 * (size_t)d.n_pixels + local] = rng.d;
-                d.state[1 * (size_t)d.n_pixels + local] = rng.v0;
-                d.state[2 * (size_t)d.n_pixels + local] = rng.v1;
-                d.state[3 * (size_t)d.n_pixels + local] = rng.v2;
-                d.state[4 * (size_t)d.n_pixels + local] = rng.v3;
-                d.state[5 * (size_t)d.n_pixels + local] = rng.v4;
+                store_stream(d.state + local, (size_t)d.n_pixels, rng);
                 if (d.accum) {
                     d.accum[local * 3 + 0] = col.x;
                     d.accum[local * 3 + 1] = col.y;
