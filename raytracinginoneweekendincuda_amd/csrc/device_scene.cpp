@@ -10,6 +10,7 @@
 #include <map>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -217,50 +218,68 @@ using namespace rtow;
 static inline SceneImpl *S(rt_scene *s) { return reinterpret_cast<SceneImpl *>(s); }
 static inline FilmImpl *F(rt_film *f) { return reinterpret_cast<FilmImpl *>(f); }
 
-// ---- lane-per-ray batches: what the ray queries, the radiance queries and the path steps below share ----
-// everything both refuse alike without a device, in the order include/rtow.h lists it; `own` answers, between the count and the
-// variant, with the family's refusal of its own parameters (": what is wrong") or nullptr
-template <class Params, class Rays, class Own>
-static int batch_check(rt_scene *scene, const Params *p, const Rays *rays, const void *outputs, const std::string &name, Own own)
+// ---- lane-per-ray batches: what the eight families of calls on caller-supplied rays below share ----
+// (ray queries, radiance, path steps, light samples, light densities, path advances, and the advances and the radiance with light
+// samples: each a call on device arrays, which checks, fills its kernel's arguments and runs them, and a call on host arrays)
+static const char *nothing_more() { return nullptr; }  // a family without a refusal of its own at one of batch_check's hooks
+static const char *strategy_error(int32_t strategy)
+{
+    return strategy != 0 && strategy != 1 ? ": strategy must be 0 (uniform) or 1 (by area and brightness)" : nullptr;
+}
+// the per-ray input a batch cannot do without: a ray, or the point of a light sample
+template <class Rays>
+static const char *missing_input(const Rays *rays) { return !rays->origin || !rays->direction ? ": null origin or direction" : nullptr; }
+static const char *missing_input(const rt_light_points *pts) { return !pts->point ? ": null point" : nullptr; }
+
+// everything the families refuse alike without a device, in the order include/rtow.h lists it; `own` answers between the count and
+// the variant, `after` behind the variant, with the family's refusal of its own parameters (": what is wrong") or nullptr
+template <class Params, class Rays, class Own, class After = const char *(*)()>
+static int batch_check(rt_scene *scene, const Params *p, const Rays *rays, const void *outputs, const std::string &name, Own own,
+                       After after = nothing_more)
 {
     if (!scene || !p || !rays || !outputs) return fail(RT_ERR_INVALID, name + ": null argument");
     if (!S(scene)->committed) return fail(RT_ERR_STATE, name + ": scene not committed (rt_scene_commit)");
     if (p->count < 0 || p->count > ((int64_t)1 << 30)) return fail(RT_ERR_INVALID, name + ": count must be 0 .. 2^30");
     if (const char *why = own()) return fail(RT_ERR_INVALID, name + why);
     if (p->variant != 0 && p->variant != 1) return fail(RT_ERR_INVALID, name + ": variant must be 0 (strict) or 1 (fast)");
-    if (p->count > 0 && (!rays->origin || !rays->direction)) return fail(RT_ERR_INVALID, name + ": null origin or direction");
+    if (const char *why = after()) return fail(RT_ERR_INVALID, name + why);
+    if (const char *why = p->count > 0 ? missing_input(rays) : nullptr) return fail(RT_ERR_INVALID, name + why);
     return RT_OK;
 }
 
-// Runs a lane-per-ray kernel on `stream` and waits for it: the kernel reads the scene's tables and the caller's arrays, and is
-// done before either may change.  `launch(stream, info)` is the family's launcher on its filled arguments, `*counter` those
-// arguments' counter pointer.  stats == nullptr: the launch and the wait alone; otherwise the time and the kernel's registers go
-// to the members both families' statistics have, the counter's value to `*counted`.
-template <class Launch, class Stats>
-static int run_lane_kernel(Launch launch, unsigned long long **counter, int device, hipStream_t stream, const char *who, Stats *stats,
-                           unsigned long long *counted)
+// What a call with statistics learns beside its results (timed_run).
+struct TimedRun {
+    QueryKernelInfo kernel[2];      // the registers of the call's kernels, as `enqueue` reports them (most calls have one)
+    unsigned long long counted[3];  // the counters behind the run
+    uint32_t word;                  // the extra word behind the run
+};
+
+// The one run with statistics.  `enqueue(info)` puts the call's kernels on `stream` (info == nullptr) or reports the instantiations
+// that would run into info[0 ..] instead.  The call gets `n_counters` 64-bit counters of its own (batches of one scene may run on
+// several streams at once): `*slots[k]`, pointers among the kernels' arguments, are set to counter k before anything is enqueued --
+// a kernel that takes an array of counters takes the last slot.  The counters are cleared, the kernels run between two events, the
+// counters and `*word` (device memory, where not null: the advances' survivors) are copied to `run`, and the stream is waited for.
+// The time and the first kernel's registers go to the members every family's statistics have.
+template <class Enqueue, class Stats>
+static int timed_run(Enqueue enqueue, std::initializer_list<unsigned long long **> slots, size_t n_counters, const uint32_t *word, int device,
+                     hipStream_t stream, const char *who, Stats *stats, TimedRun &run)
 {
-    if (!stats) {
-        hipError_t e = launch(stream, nullptr);
-        const hipError_t waited = hipStreamSynchronize(stream);
-        if (e == hipSuccess) e = waited;
-        return e == hipSuccess ? RT_OK : hip_fail(e, who);
-    }
-    // with statistics: the kernel's registers, two events around it, and a word of this call's own for the count (batches of one
-    // scene may run on several streams at once)
-    QueryKernelInfo info{};
-    HIP_TRY(launch(stream, &info));
+    HIP_TRY(enqueue(run.kernel));
     DeviceArena scratch(device);
-    HIP_TRY(scratch.alloc(1, *counter));
+    unsigned long long *counters = nullptr;
+    HIP_TRY(scratch.alloc(n_counters, counters));
+    size_t k = 0;
+    for (unsigned long long **slot : slots) *slot = counters + k++;
     // from here on the chain: the events are destroyed, and the stream waited for, whatever fails
     hipEvent_t ev[2] = {nullptr, nullptr};
     hipError_t e = hipEventCreate(&ev[0]);
     if (e == hipSuccess) e = hipEventCreate(&ev[1]);
-    if (e == hipSuccess) e = hipMemsetAsync(*counter, 0, sizeof(unsigned long long), stream);
+    if (e == hipSuccess) e = hipMemsetAsync(counters, 0, n_counters * sizeof(unsigned long long), stream);
     if (e == hipSuccess) e = hipEventRecord(ev[0], stream);
-    if (e == hipSuccess) e = launch(stream, nullptr);
+    if (e == hipSuccess) e = enqueue(nullptr);
     if (e == hipSuccess) e = hipEventRecord(ev[1], stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(counted, *counter, sizeof *counted, hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(run.counted, counters, n_counters * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess && word) e = hipMemcpyAsync(&run.word, word, sizeof run.word, hipMemcpyDeviceToHost, stream);
     const hipError_t waited = hipStreamSynchronize(stream);
     if (e == hipSuccess) e = waited;
     float ms = 0.0f;
@@ -269,35 +288,237 @@ static int run_lane_kernel(Launch launch, unsigned long long **counter, int devi
         if (v) hipEventDestroy(v);
     if (e != hipSuccess) return hip_fail(e, who);
     stats->seconds = (double)ms * 1e-3;
-    stats->kernel_vgprs = (uint32_t)info.vgprs;
-    stats->scratch_bytes = (uint32_t)info.scratch_bytes;
+    stats->kernel_vgprs = (uint32_t)run.kernel[0].vgprs;
+    stats->scratch_bytes = (uint32_t)run.kernel[0].scratch_bytes;
     return RT_OK;
 }
 
-// The host arrays of one batch of `n` rays on the device (rt_scene_intersect, rt_scene_radiance, rt_scene_path_step); the copies are synchronous.
+// Runs a lane-per-ray kernel on `stream` and waits for it: the kernel reads the scene's tables and the caller's arrays, and is
+// done before either may change.  stats == nullptr: the launch and the wait alone; otherwise timed_run, whose arguments these are.
+template <class Enqueue, class Stats>
+static int run_lane_kernel(Enqueue enqueue, std::initializer_list<unsigned long long **> slots, size_t n_counters, int device, hipStream_t stream,
+                           const char *who, Stats *stats, TimedRun &run)
+{
+    if (stats) return timed_run(enqueue, slots, n_counters, nullptr, device, stream, who, stats, run);
+    hipError_t e = enqueue(nullptr);
+    const hipError_t waited = hipStreamSynchronize(stream);
+    if (e == hipSuccess) e = waited;
+    return e == hipSuccess ? RT_OK : hip_fail(e, who);
+}
+
+// The host arrays of one batch of `n` rays on the device (host_batch below); the copies are synchronous.
 // `dev` comes in null: an input the caller left null, an output the caller does not want, stays so.
 struct Staging {
-    struct Out { void *host; const void *dev; size_t bytes; };
+    struct Out { void *host; const void *dev; size_t bytes_per_ray; };
     DeviceArena arena;
     size_t n;
     std::vector<Out> outs;
+    hipError_t error = hipSuccess;  // the first failure of in() or out(), behind which neither does anything
     template <class T>
-    hipError_t in(const T *host, size_t per_ray, const T *&dev) { return host ? arena.upload(host, n * per_ray, dev) : hipSuccess; }  // `per_ray` values a ray
-    template <class T>
-    hipError_t out(T *host, size_t per_ray, T *&dev)  // room for them, remembered for fetch()
+    void in(const T *host, size_t per_ray, const T *&dev)  // `per_ray` values a ray
     {
-        if (!host) return hipSuccess;
-        const hipError_t e = arena.alloc(n * per_ray, dev);
-        if (e == hipSuccess) outs.push_back(Out{host, dev, n * per_ray * sizeof(T)});
-        return e;
+        if (host && error == hipSuccess) error = arena.upload(host, n * per_ray, dev);
     }
-    hipError_t fetch() const  // every remembered output back to its host array
+    template <class T>
+    void out(T *host, size_t per_ray, T *&dev)  // room for them, remembered for fetch()
+    {
+        if (!host || error != hipSuccess) return;
+        error = arena.alloc(n * per_ray, dev);
+        if (error == hipSuccess) outs.push_back(Out{host, dev, per_ray * sizeof(T)});
+    }
+    hipError_t fetch(size_t rows) const  // the first `rows` rows of every remembered output back to its host array
     {
         hipError_t e = hipSuccess;
-        for (size_t k = 0; k < outs.size() && e == hipSuccess; k++) e = hipMemcpy(outs[k].host, outs[k].dev, outs[k].bytes, hipMemcpyDeviceToHost);
+        for (size_t k = 0; k < outs.size() && e == hipSuccess && rows; k++)
+            e = hipMemcpy(outs[k].host, outs[k].dev, outs[k].bytes_per_ray * rows, hipMemcpyDeviceToHost);
         return e;
     }
 };
+
+// ---- the per-ray arrays of every rays struct and every outputs struct, stated once: member, values per ray, in or out ----
+// Each walks a caller's struct of host arrays `h` and its zero-initialised twin `d`, which receives the device arrays.
+static void stage_arrays(Staging &st, const rt_query_rays &h, rt_query_rays &d)
+{
+    st.in(h.origin, 3, d.origin);
+    st.in(h.direction, 3, d.direction);
+    st.in(h.time, 1, d.time);
+    st.in(h.tmin, 1, d.tmin);
+    st.in(h.tmax, 1, d.tmax);
+}
+static void stage_arrays(Staging &st, const rt_query_hits &h, rt_query_hits &d)
+{
+    st.out(h.t, 1, d.t);
+    st.out(h.normal, 3, d.normal);
+    st.out(h.uv, 2, d.uv);
+    st.out(h.albedo, 3, d.albedo);
+    st.out(h.leaf, 1, d.leaf);
+    st.out(h.front_face, 1, d.front_face);
+    st.out(h.material, 1, d.material);
+    st.out(h.occluded, 1, d.occluded);
+}
+static void stage_arrays(Staging &st, const rt_radiance_rays &h, rt_radiance_rays &d)  // (radiance and radiance direct)
+{
+    st.in(h.origin, 3, d.origin);
+    st.in(h.direction, 3, d.direction);
+    st.in(h.time, 1, d.time);
+    st.in(h.rng_state, 6, d.rng_state);
+}
+static void stage_arrays(Staging &st, const rt_radiance_out &h, rt_radiance_out &d)
+{
+    st.out(h.radiance, 3, d.radiance);
+    st.out(h.path_rays, 1, d.path_rays);
+    st.out(h.rng_state, 6, d.rng_state);
+}
+static void stage_arrays(Staging &st, const rt_path_step_rays &h, rt_path_step_rays &d)
+{
+    st.in(h.origin, 3, d.origin);
+    st.in(h.direction, 3, d.direction);
+    st.in(h.time, 1, d.time);
+    st.in(h.rng_state, 6, d.rng_state);
+}
+static void stage_arrays(Staging &st, const rt_path_step_out &h, rt_path_step_out &d)
+{
+    st.out(h.status, 1, d.status);
+    st.out(h.emitted, 3, d.emitted);
+    st.out(h.attenuation, 3, d.attenuation);
+    st.out(h.origin, 3, d.origin);
+    st.out(h.direction, 3, d.direction);
+    st.out(h.time, 1, d.time);
+    st.out(h.t, 1, d.t);
+    st.out(h.normal, 3, d.normal);
+    st.out(h.front_face, 1, d.front_face);
+    st.out(h.material, 1, d.material);
+    st.out(h.rng_state, 6, d.rng_state);
+}
+static void stage_arrays(Staging &st, const rt_light_points &h, rt_light_points &d)
+{
+    st.in(h.point, 3, d.point);
+    st.in(h.normal, 3, d.normal);
+    st.in(h.material, 1, d.material);
+    st.in(h.time, 1, d.time);
+    st.in(h.rng_state, 6, d.rng_state);
+}
+static void stage_arrays(Staging &st, const rt_light_samples &h, rt_light_samples &d)
+{
+    st.out(h.direction, 3, d.direction);
+    st.out(h.distance, 1, d.distance);
+    st.out(h.light, 1, d.light);
+    st.out(h.pdf, 1, d.pdf);
+    st.out(h.emitted, 3, d.emitted);
+    st.out(h.scatter_pdf, 1, d.scatter_pdf);
+    st.out(h.contribution, 3, d.contribution);
+    st.out(h.rng_state, 6, d.rng_state);
+}
+static void stage_arrays(Staging &st, const rt_light_rays &h, rt_light_rays &d)
+{
+    st.in(h.origin, 3, d.origin);
+    st.in(h.direction, 3, d.direction);
+    st.in(h.time, 1, d.time);
+}
+static void stage_arrays(Staging &st, const rt_light_pdf_out &h, rt_light_pdf_out &d)
+{
+    st.out(h.pdf, 1, d.pdf);
+    st.out(h.light, 1, d.light);
+}
+// the advances: the structs of the one with light samples begin with the plain one's fields (advance_args and advance_arrays_check
+// below rely on the same), so these two serve both and the direct structs add their density.  The two count words and the
+// `radiance` rows are no per-ray arrays: host_batch has them.
+template <class Rays>
+static void stage_advance_rays(Staging &st, const Rays &h, Rays &d)
+{
+    st.in(h.origin, 3, d.origin);
+    st.in(h.direction, 3, d.direction);
+    st.in(h.time, 1, d.time);
+    st.in(h.rng_state, 6, d.rng_state);
+    st.in(h.throughput, 3, d.throughput);
+    st.in(h.ray_id, 1, d.ray_id);
+    st.in(h.alive, 1, d.alive);
+}
+template <class Out>
+static void stage_advance_out(Staging &st, const Out &h, Out &d)
+{
+    st.out(h.origin, 3, d.origin);
+    st.out(h.direction, 3, d.direction);
+    st.out(h.time, 1, d.time);
+    st.out(h.rng_state, 6, d.rng_state);
+    st.out(h.throughput, 3, d.throughput);
+    st.out(h.ray_id, 1, d.ray_id);
+    st.out(h.t, 1, d.t);
+    st.out(h.normal, 3, d.normal);
+    st.out(h.front_face, 1, d.front_face);
+    st.out(h.material, 1, d.material);
+}
+static void stage_arrays(Staging &st, const rt_path_advance_rays &h, rt_path_advance_rays &d) { stage_advance_rays(st, h, d); }
+static void stage_arrays(Staging &st, const rt_path_advance_out &h, rt_path_advance_out &d) { stage_advance_out(st, h, d); }
+static void stage_arrays(Staging &st, const rt_path_advance_direct_rays &h, rt_path_advance_direct_rays &d)
+{
+    stage_advance_rays(st, h, d);
+    st.in(h.scatter_pdf, 1, d.scatter_pdf);
+}
+static void stage_arrays(Staging &st, const rt_path_advance_direct_out &h, rt_path_advance_direct_out &d)
+{
+    stage_advance_out(st, h, d);
+    st.out(h.scatter_pdf, 1, d.scatter_pdf);
+}
+
+template <class Params>
+constexpr bool kIsAdvanceDirect = std::is_same<Params, rt_path_advance_direct_params>::value;
+template <class Params>
+constexpr bool kIsAdvance = std::is_same<Params, rt_path_advance_params>::value || kIsAdvanceDirect<Params>;
+
+// The call on host arrays of every family, behind its check: the arrays are staged on the device, `device_call` -- the family's
+// entry point on device arrays -- runs on them, and the outputs come back.
+// The advances differ in what include/rtow.h states of their host form: the rows below the word rays->count alone travel, the
+// `sources` rows of `radiance` go up and come back, the survivors' count and the workspace are this call's own, the call waits
+// (the device call with statistics does), and the first *out->count rows of each output are copied back.
+template <class Params, class Rays, class Out, class Stats>
+static int host_batch(rt_scene *scene, const Params *p, const Rays *rays, const Out *out, Stats *stats,
+                      int (*device_call)(rt_scene *, const Params *, const Rays *, const Out *, Stats *))
+{
+    if (stats) *stats = Stats{};
+    if (p->count == 0) return RT_OK;
+    if (int rc = select_device(p->device)) return rc;
+    Params dp = *p;
+    dp.stream = nullptr;  // the copies around the call are synchronous: nothing to order on the caller's stream
+    if constexpr (kIsAdvance<Params>) {  // the host knows the word
+        if (rays->count && (int64_t)*rays->count < p->count) dp.count = (int64_t)*rays->count;
+        if (dp.count == 0) {
+            *out->count = 0;
+            return RT_OK;
+        }
+    }
+    Staging stage{DeviceArena(p->device), (size_t)dp.count, {}};
+    Rays dr{};
+    Out dout{};
+    stage_arrays(stage, *rays, dr);
+    stage_arrays(stage, *out, dout);
+    HIP_TRY(stage.error);
+    if constexpr (kIsAdvance<Params>) {
+        const size_t folded = out->radiance ? (size_t)p->sources * 3 : 0;
+        if (folded) {
+            const double *uploaded = nullptr;
+            HIP_TRY(stage.arena.upload(out->radiance, folded, uploaded));
+            dout.radiance = const_cast<double *>(uploaded);
+        }
+        HIP_TRY(stage.arena.alloc(1, dout.count));
+        dp.workspace_bytes = kIsAdvanceDirect<Params> ? rt_path_advance_direct_workspace_bytes(dp.count) : rt_path_advance_workspace_bytes(dp.count);
+        unsigned char *workspace = nullptr;
+        HIP_TRY(stage.arena.alloc((size_t)dp.workspace_bytes, workspace));
+        dp.workspace = workspace;
+        Stats waited{};
+        if (int rc = device_call(scene, &dp, &dr, &dout, stats ? stats : &waited)) return rc;
+        uint32_t survivors = 0;
+        HIP_TRY(hipMemcpy(&survivors, dout.count, sizeof survivors, hipMemcpyDeviceToHost));
+        if (survivors > (uint32_t)dp.count) survivors = (uint32_t)dp.count;  // (never)
+        HIP_TRY(stage.fetch(survivors));
+        if (folded) HIP_TRY(hipMemcpy(out->radiance, dout.radiance, folded * sizeof(double), hipMemcpyDeviceToHost));
+        *out->count = survivors;
+    } else {
+        if (int rc = device_call(scene, &dp, &dr, &dout, stats)) return rc;
+        HIP_TRY(stage.fetch(stage.n));
+    }
+    return RT_OK;
+}
 
 extern "C" {
 
@@ -1302,13 +1523,14 @@ int rt_scene_intersect_device(rt_scene *scene, const rt_query_params *p, const r
     qa.first_sequence = p->first_sequence;
     qa.count = (uint32_t)p->count;
     qa.mode = p->mode;
-    // (qa by reference: run_lane_kernel sets qa.hit_counter between the launch that reports and the one that runs)
-    const auto launch = [&](hipStream_t stream, QueryKernelInfo *info) { return kBuilds[p->variant].query(dt.scene, qa, stream, info); };
-    unsigned long long found = 0;
-    if (int rc = run_lane_kernel(launch, &qa.hit_counter, p->device, (hipStream_t)p->stream, "rt_scene_intersect_device", stats, &found)) return rc;
+    hipStream_t stream = (hipStream_t)p->stream;
+    // (qa by reference: the run sets qa.hit_counter between the launch that reports and the one that runs)
+    const auto launch = [&](QueryKernelInfo *info) { return kBuilds[p->variant].query(dt.scene, qa, stream, info); };
+    TimedRun run{};
+    if (int rc = run_lane_kernel(launch, {&qa.hit_counter}, 1, p->device, stream, "rt_scene_intersect_device", stats, run)) return rc;
     if (stats) {
         stats->rays = (uint64_t)p->count;
-        stats->hits = found;
+        stats->hits = run.counted[0];
     }
     return RT_OK;
 }
@@ -1316,32 +1538,9 @@ int rt_scene_intersect_device(rt_scene *scene, const rt_query_params *p, const r
 int rt_scene_intersect(rt_scene *scene, const rt_query_params *p, const rt_query_rays *rays, const rt_query_hits *hits, rt_query_stats *stats)
 {
     if (int rc = query_check(scene, p, rays, hits, "rt_scene_intersect")) return rc;
-    if (stats) *stats = rt_query_stats{};
-    if (p->count == 0) return RT_OK;
-    if (int rc = select_device(p->device)) return rc;
-    Staging stage{DeviceArena(p->device), (size_t)p->count, {}};
-    rt_query_rays dr{};
-    HIP_TRY(stage.in(rays->origin, 3, dr.origin));
-    HIP_TRY(stage.in(rays->direction, 3, dr.direction));
-    HIP_TRY(stage.in(rays->time, 1, dr.time));
-    HIP_TRY(stage.in(rays->tmin, 1, dr.tmin));
-    HIP_TRY(stage.in(rays->tmax, 1, dr.tmax));
-    rt_query_hits dh{};
-    if (p->mode == 0) {  // an occlusion query writes `occluded` alone: its other outputs are neither allocated nor copied
-        HIP_TRY(stage.out(hits->t, 1, dh.t));
-        HIP_TRY(stage.out(hits->normal, 3, dh.normal));
-        HIP_TRY(stage.out(hits->uv, 2, dh.uv));
-        HIP_TRY(stage.out(hits->albedo, 3, dh.albedo));
-        HIP_TRY(stage.out(hits->leaf, 1, dh.leaf));
-        HIP_TRY(stage.out(hits->front_face, 1, dh.front_face));
-        HIP_TRY(stage.out(hits->material, 1, dh.material));
-    }
-    HIP_TRY(stage.out(hits->occluded, 1, dh.occluded));
-    rt_query_params dp = *p;
-    dp.stream = nullptr;  // the copies around the query are synchronous: nothing to order on the caller's stream
-    if (int rc = rt_scene_intersect_device(scene, &dp, &dr, &dh, stats)) return rc;
-    HIP_TRY(stage.fetch());
-    return RT_OK;
+    rt_query_hits only{};  // an occlusion query writes `occluded` alone: its other outputs are neither allocated nor copied
+    only.occluded = hits->occluded;
+    return host_batch(scene, p, rays, p->mode == 0 ? hits : &only, stats, rt_scene_intersect_device);
 }
 
 void rt_query_abi_sizes(uint32_t out4[4])
@@ -1353,8 +1552,18 @@ void rt_query_abi_sizes(uint32_t out4[4])
 }
 
 // ---- radiance queries ----
+// rt_radiance_direct_params (the radiance queries with light samples, below) begins with rt_radiance_params, field for field: the
+// check and the arguments of both are one template each
+static_assert(sizeof(rt_radiance_direct_params) == sizeof(rt_radiance_params) + 4 * sizeof(int32_t) &&
+                  offsetof(rt_radiance_direct_params, strategy) == sizeof(rt_radiance_params) &&
+                  offsetof(rt_radiance_direct_params, stream) == offsetof(rt_radiance_params, stream) &&
+                  offsetof(rt_radiance_direct_params, variant) == offsetof(rt_radiance_params, variant),
+              "rt_radiance_direct_params: rt_radiance_params and the strategy behind it");
+
+extern "C++" {  // (two templates among the C entry points)
 // everything that can be refused without a device, in the order include/rtow.h lists it
-static int radiance_check(rt_scene *scene, const rt_radiance_params *p, const rt_radiance_rays *rays, const rt_radiance_out *out, const char *who)
+template <class Params>
+static int radiance_check(rt_scene *scene, const Params *p, const rt_radiance_rays *rays, const rt_radiance_out *out, const char *who)
 {
     const std::string name(who);
     const auto paths = [&] { return p->samples < 1 || p->samples > (1 << 20) ? ": samples must be 1 .. 2^20" : p->max_depth < 0 ? ": max_depth must be >= 0" : nullptr; };
@@ -1363,16 +1572,10 @@ static int radiance_check(rt_scene *scene, const rt_radiance_params *p, const rt
     return RT_OK;
 }
 
-int rt_scene_radiance_device(rt_scene *scene, const rt_radiance_params *p, const rt_radiance_rays *rays, const rt_radiance_out *out,
-                             rt_radiance_stats *stats)
+// the radiance kernels' arguments from the call's three structs
+template <class Params>
+static int radiance_args(const Params *p, const rt_radiance_rays *rays, const rt_radiance_out *out, RadianceArgs &ra)
 {
-    if (int rc = radiance_check(scene, p, rays, out, "rt_scene_radiance_device")) return rc;
-    if (stats) *stats = rt_radiance_stats{};
-    if (p->count == 0) return RT_OK;
-    SceneImpl &s = *S(scene);
-    if (int rc = rt_scene_upload(scene, p->device)) return rc;  // (selects the device)
-    DeviceTables &dt = *s.device[p->device];
-    RadianceArgs ra{};
     ra.origin = rays->origin;
     ra.direction = rays->direction;
     ra.time = rays->time;
@@ -1387,11 +1590,27 @@ int rt_scene_radiance_device(rt_scene *scene, const rt_radiance_params *p, const
     ra.count = (uint32_t)p->count;
     ra.samples = p->samples;
     ra.max_depth = p->max_depth;
-    // (ra by reference: run_lane_kernel sets ra.ray_counter between the launch that reports and the one that runs)
-    const auto launch = [&](hipStream_t stream, QueryKernelInfo *info) { return kBuilds[p->variant].radiance(dt.scene, ra, stream, info); };
-    unsigned long long traced = 0;
-    if (int rc = run_lane_kernel(launch, &ra.ray_counter, p->device, (hipStream_t)p->stream, "rt_scene_radiance_device", stats, &traced)) return rc;
-    if (stats) stats->rays = traced;
+    return RT_OK;
+}
+}  // extern "C++"
+
+int rt_scene_radiance_device(rt_scene *scene, const rt_radiance_params *p, const rt_radiance_rays *rays, const rt_radiance_out *out,
+                             rt_radiance_stats *stats)
+{
+    if (int rc = radiance_check(scene, p, rays, out, "rt_scene_radiance_device")) return rc;
+    if (stats) *stats = rt_radiance_stats{};
+    if (p->count == 0) return RT_OK;
+    SceneImpl &s = *S(scene);
+    if (int rc = rt_scene_upload(scene, p->device)) return rc;  // (selects the device)
+    DeviceTables &dt = *s.device[p->device];
+    RadianceArgs ra{};
+    if (int rc = radiance_args(p, rays, out, ra)) return rc;
+    hipStream_t stream = (hipStream_t)p->stream;
+    // (ra by reference: the run sets ra.ray_counter between the launch that reports and the one that runs)
+    const auto launch = [&](QueryKernelInfo *info) { return kBuilds[p->variant].radiance(dt.scene, ra, stream, info); };
+    TimedRun run{};
+    if (int rc = run_lane_kernel(launch, {&ra.ray_counter}, 1, p->device, stream, "rt_scene_radiance_device", stats, run)) return rc;
+    if (stats) stats->rays = run.counted[0];
     return RT_OK;
 }
 
@@ -1399,24 +1618,7 @@ int rt_scene_radiance(rt_scene *scene, const rt_radiance_params *p, const rt_rad
                       rt_radiance_stats *stats)
 {
     if (int rc = radiance_check(scene, p, rays, out, "rt_scene_radiance")) return rc;
-    if (stats) *stats = rt_radiance_stats{};
-    if (p->count == 0) return RT_OK;
-    if (int rc = select_device(p->device)) return rc;
-    Staging stage{DeviceArena(p->device), (size_t)p->count, {}};
-    rt_radiance_rays dr{};
-    HIP_TRY(stage.in(rays->origin, 3, dr.origin));
-    HIP_TRY(stage.in(rays->direction, 3, dr.direction));
-    HIP_TRY(stage.in(rays->time, 1, dr.time));
-    HIP_TRY(stage.in(rays->rng_state, 6, dr.rng_state));
-    rt_radiance_out dout{};
-    HIP_TRY(stage.out(out->radiance, 3, dout.radiance));
-    HIP_TRY(stage.out(out->path_rays, 1, dout.path_rays));
-    HIP_TRY(stage.out(out->rng_state, 6, dout.rng_state));
-    rt_radiance_params dp = *p;
-    dp.stream = nullptr;  // the copies around the query are synchronous: nothing to order on the caller's stream
-    if (int rc = rt_scene_radiance_device(scene, &dp, &dr, &dout, stats)) return rc;
-    HIP_TRY(stage.fetch());
-    return RT_OK;
+    return host_batch(scene, p, rays, out, stats, rt_scene_radiance_device);
 }
 
 void rt_radiance_abi_sizes(uint32_t out4[4])
@@ -1432,8 +1634,7 @@ void rt_radiance_abi_sizes(uint32_t out4[4])
 static int path_step_check(rt_scene *scene, const rt_path_step_params *p, const rt_path_step_rays *rays, const rt_path_step_out *out, const char *who)
 {
     const std::string name(who);
-    const auto nothing = [] { return (const char *)nullptr; };  // no parameters of its own
-    if (int rc = batch_check(scene, p, rays, out, name, nothing)) return rc;
+    if (int rc = batch_check(scene, p, rays, out, name, nothing_more)) return rc;  // no parameters of its own
     if (!out->status && !out->emitted && !out->attenuation && !out->origin && !out->direction && !out->time && !out->t && !out->normal &&
         !out->front_face && !out->material && !out->rng_state)
         return fail(RT_ERR_INVALID, name + ": every output is null");
@@ -1470,14 +1671,14 @@ int rt_scene_path_step_device(rt_scene *scene, const rt_path_step_params *p, con
     sa.base = xorwow_seed(p->seed, kSaltCurandDevice);
     sa.first_sequence = p->first_sequence;
     sa.count = (uint32_t)p->count;
-    // (sa by reference: run_lane_kernel sets sa.scattered_counter between the launch that reports and the one that runs)
-    const auto launch = [&](hipStream_t stream, QueryKernelInfo *info) { return kBuilds[p->variant].step(dt.scene, sa, stream, info); };
-    unsigned long long scattered = 0;
-    if (int rc = run_lane_kernel(launch, &sa.scattered_counter, p->device, (hipStream_t)p->stream, "rt_scene_path_step_device", stats, &scattered))
-        return rc;
+    hipStream_t stream = (hipStream_t)p->stream;
+    // (sa by reference: the run sets sa.scattered_counter between the launch that reports and the one that runs)
+    const auto launch = [&](QueryKernelInfo *info) { return kBuilds[p->variant].step(dt.scene, sa, stream, info); };
+    TimedRun run{};
+    if (int rc = run_lane_kernel(launch, {&sa.scattered_counter}, 1, p->device, stream, "rt_scene_path_step_device", stats, run)) return rc;
     if (stats) {
         stats->rays = (uint64_t)p->count;
-        stats->scattered = scattered;
+        stats->scattered = run.counted[0];
     }
     return RT_OK;
 }
@@ -1486,32 +1687,7 @@ int rt_scene_path_step(rt_scene *scene, const rt_path_step_params *p, const rt_p
                        rt_path_step_stats *stats)
 {
     if (int rc = path_step_check(scene, p, rays, out, "rt_scene_path_step")) return rc;
-    if (stats) *stats = rt_path_step_stats{};
-    if (p->count == 0) return RT_OK;
-    if (int rc = select_device(p->device)) return rc;
-    Staging stage{DeviceArena(p->device), (size_t)p->count, {}};
-    rt_path_step_rays dr{};
-    HIP_TRY(stage.in(rays->origin, 3, dr.origin));
-    HIP_TRY(stage.in(rays->direction, 3, dr.direction));
-    HIP_TRY(stage.in(rays->time, 1, dr.time));
-    HIP_TRY(stage.in(rays->rng_state, 6, dr.rng_state));
-    rt_path_step_out dout{};
-    HIP_TRY(stage.out(out->status, 1, dout.status));
-    HIP_TRY(stage.out(out->emitted, 3, dout.emitted));
-    HIP_TRY(stage.out(out->attenuation, 3, dout.attenuation));
-    HIP_TRY(stage.out(out->origin, 3, dout.origin));
-    HIP_TRY(stage.out(out->direction, 3, dout.direction));
-    HIP_TRY(stage.out(out->time, 1, dout.time));
-    HIP_TRY(stage.out(out->t, 1, dout.t));
-    HIP_TRY(stage.out(out->normal, 3, dout.normal));
-    HIP_TRY(stage.out(out->front_face, 1, dout.front_face));
-    HIP_TRY(stage.out(out->material, 1, dout.material));
-    HIP_TRY(stage.out(out->rng_state, 6, dout.rng_state));
-    rt_path_step_params dp = *p;
-    dp.stream = nullptr;  // the copies around the step are synchronous: nothing to order on the caller's stream
-    if (int rc = rt_scene_path_step_device(scene, &dp, &dr, &dout, stats)) return rc;
-    HIP_TRY(stage.fetch());
-    return RT_OK;
+    return host_batch(scene, p, rays, out, stats, rt_scene_path_step_device);
 }
 
 void rt_path_step_abi_sizes(uint32_t out4[4])
@@ -1523,21 +1699,11 @@ void rt_path_step_abi_sizes(uint32_t out4[4])
 }
 
 // ---- light sampling queries ----
-// everything that can be refused without a device, in the order include/rtow.h lists it
-static int light_check(rt_scene *scene, const rt_light_params *p, const void *in, const void *out, const std::string &name)
-{
-    if (!scene || !p || !in || !out) return fail(RT_ERR_INVALID, name + ": null argument");
-    if (!S(scene)->committed) return fail(RT_ERR_STATE, name + ": scene not committed (rt_scene_commit)");
-    if (p->count < 0 || p->count > ((int64_t)1 << 30)) return fail(RT_ERR_INVALID, name + ": count must be 0 .. 2^30");
-    if (p->strategy != 0 && p->strategy != 1) return fail(RT_ERR_INVALID, name + ": strategy must be 0 (uniform) or 1 (by area and brightness)");
-    if (p->variant != 0 && p->variant != 1) return fail(RT_ERR_INVALID, name + ": variant must be 0 (strict) or 1 (fast)");
-    return RT_OK;
-}
+// everything that can be refused without a device, in the order include/rtow.h lists it: batch_check's, the strategy before the variant
 static int light_sample_check(rt_scene *scene, const rt_light_params *p, const rt_light_points *pts, const rt_light_samples *out, const char *who)
 {
     const std::string name(who);
-    if (int rc = light_check(scene, p, pts, out, name)) return rc;
-    if (p->count > 0 && !pts->point) return fail(RT_ERR_INVALID, name + ": null point");
+    if (int rc = batch_check(scene, p, pts, out, name, [&] { return strategy_error(p->strategy); })) return rc;
     if (!out->direction && !out->distance && !out->light && !out->pdf && !out->emitted && !out->scatter_pdf && !out->contribution && !out->rng_state)
         return fail(RT_ERR_INVALID, name + ": every output is null");
     if ((out->scatter_pdf || out->contribution) && (!pts->normal || !pts->material))
@@ -1547,8 +1713,7 @@ static int light_sample_check(rt_scene *scene, const rt_light_params *p, const r
 static int light_pdf_check(rt_scene *scene, const rt_light_params *p, const rt_light_rays *rays, const rt_light_pdf_out *out, const char *who)
 {
     const std::string name(who);
-    if (int rc = light_check(scene, p, rays, out, name)) return rc;
-    if (p->count > 0 && (!rays->origin || !rays->direction)) return fail(RT_ERR_INVALID, name + ": null origin or direction");
+    if (int rc = batch_check(scene, p, rays, out, name, [&] { return strategy_error(p->strategy); })) return rc;
     if (!out->pdf && !out->light) return fail(RT_ERR_INVALID, name + ": every output is null");
     return RT_OK;
 }
@@ -1567,15 +1732,16 @@ static int run_light_kernel(rt_scene *scene, const rt_light_params *p, LightArgs
     la.base = xorwow_seed(p->seed, kSaltCurandDevice);
     la.first_sequence = p->first_sequence;
     la.count = (uint32_t)p->count;
-    // (la by reference: run_lane_kernel sets la.valid_counter between the launch that reports and the one that runs)
-    const auto launch = [&](hipStream_t stream, QueryKernelInfo *info) {
+    hipStream_t stream = (hipStream_t)p->stream;
+    // (la by reference: the run sets la.valid_counter between the launch that reports and the one that runs)
+    const auto launch = [&](QueryKernelInfo *info) {
         return pdf_mode ? kBuilds[p->variant].light_pdf(dt.scene, la, stream, info) : kBuilds[p->variant].light_sample(dt.scene, la, stream, info);
     };
-    unsigned long long valid = 0;
-    if (int rc = run_lane_kernel(launch, &la.valid_counter, p->device, (hipStream_t)p->stream, who, stats, &valid)) return rc;
+    TimedRun run{};
+    if (int rc = run_lane_kernel(launch, {&la.valid_counter}, 1, p->device, stream, who, stats, run)) return rc;
     if (stats) {
         stats->points = (uint64_t)p->count;
-        stats->valid = valid;
+        stats->valid = run.counted[0];
     }
     return RT_OK;
 }
@@ -1606,30 +1772,7 @@ int rt_scene_sample_lights_device(rt_scene *scene, const rt_light_params *p, con
 int rt_scene_sample_lights(rt_scene *scene, const rt_light_params *p, const rt_light_points *pts, const rt_light_samples *out, rt_light_stats *stats)
 {
     if (int rc = light_sample_check(scene, p, pts, out, "rt_scene_sample_lights")) return rc;
-    if (stats) *stats = rt_light_stats{};
-    if (p->count == 0) return RT_OK;
-    if (int rc = select_device(p->device)) return rc;
-    Staging stage{DeviceArena(p->device), (size_t)p->count, {}};
-    rt_light_points dp_in{};
-    HIP_TRY(stage.in(pts->point, 3, dp_in.point));
-    HIP_TRY(stage.in(pts->normal, 3, dp_in.normal));
-    HIP_TRY(stage.in(pts->material, 1, dp_in.material));
-    HIP_TRY(stage.in(pts->time, 1, dp_in.time));
-    HIP_TRY(stage.in(pts->rng_state, 6, dp_in.rng_state));
-    rt_light_samples dout{};
-    HIP_TRY(stage.out(out->direction, 3, dout.direction));
-    HIP_TRY(stage.out(out->distance, 1, dout.distance));
-    HIP_TRY(stage.out(out->light, 1, dout.light));
-    HIP_TRY(stage.out(out->pdf, 1, dout.pdf));
-    HIP_TRY(stage.out(out->emitted, 3, dout.emitted));
-    HIP_TRY(stage.out(out->scatter_pdf, 1, dout.scatter_pdf));
-    HIP_TRY(stage.out(out->contribution, 3, dout.contribution));
-    HIP_TRY(stage.out(out->rng_state, 6, dout.rng_state));
-    rt_light_params dp = *p;
-    dp.stream = nullptr;  // the copies around the call are synchronous: nothing to order on the caller's stream
-    if (int rc = rt_scene_sample_lights_device(scene, &dp, &dp_in, &dout, stats)) return rc;
-    HIP_TRY(stage.fetch());
-    return RT_OK;
+    return host_batch(scene, p, pts, out, stats, rt_scene_sample_lights_device);
 }
 
 int rt_scene_light_pdf_device(rt_scene *scene, const rt_light_params *p, const rt_light_rays *rays, const rt_light_pdf_out *out, rt_light_stats *stats)
@@ -1649,22 +1792,7 @@ int rt_scene_light_pdf_device(rt_scene *scene, const rt_light_params *p, const r
 int rt_scene_light_pdf(rt_scene *scene, const rt_light_params *p, const rt_light_rays *rays, const rt_light_pdf_out *out, rt_light_stats *stats)
 {
     if (int rc = light_pdf_check(scene, p, rays, out, "rt_scene_light_pdf")) return rc;
-    if (stats) *stats = rt_light_stats{};
-    if (p->count == 0) return RT_OK;
-    if (int rc = select_device(p->device)) return rc;
-    Staging stage{DeviceArena(p->device), (size_t)p->count, {}};
-    rt_light_rays dr{};
-    HIP_TRY(stage.in(rays->origin, 3, dr.origin));
-    HIP_TRY(stage.in(rays->direction, 3, dr.direction));
-    HIP_TRY(stage.in(rays->time, 1, dr.time));
-    rt_light_pdf_out dout{};
-    HIP_TRY(stage.out(out->pdf, 1, dout.pdf));
-    HIP_TRY(stage.out(out->light, 1, dout.light));
-    rt_light_params dp = *p;
-    dp.stream = nullptr;
-    if (int rc = rt_scene_light_pdf_device(scene, &dp, &dr, &dout, stats)) return rc;
-    HIP_TRY(stage.fetch());
-    return RT_OK;
+    return host_batch(scene, p, rays, out, stats, rt_scene_light_pdf_device);
 }
 
 void rt_light_abi_sizes(uint32_t out8[8])
@@ -1790,6 +1918,20 @@ static void advance_args(const Params *p, const Rays *rays, const Out *out, cons
     ga.block_offsets = (uint32_t *)(base + w.block_offsets);
     ga.capacity = aa.capacity;
 }
+
+// Runs an advance's kernels on `stream`.  stats == nullptr: enqueue, record dt.advance_done behind them and return -- whoever frees
+// the tables waits for the event; otherwise timed_run, whose arguments these are, with the survivors' count for its extra word.
+template <class Enqueue, class Stats>
+static int run_advance(Enqueue enqueue, std::initializer_list<unsigned long long **> slots, size_t n_counters, const uint32_t *survivors,
+                       DeviceTables &dt, int device, hipStream_t stream, const char *who, Stats *stats, TimedRun &run)
+{
+    if (!dt.advance_done) HIP_TRY(hipEventCreateWithFlags(&dt.advance_done, hipEventDisableTiming));
+    if (stats) return timed_run(enqueue, slots, n_counters, survivors, device, stream, who, stats, run);
+    hipError_t e = enqueue(nullptr);
+    const hipError_t recorded = hipEventRecord(dt.advance_done, stream);
+    if (e == hipSuccess) e = recorded;
+    return e == hipSuccess ? RT_OK : hip_fail(e, who);
+}
 }  // extern "C++"
 
 uint64_t rt_path_advance_workspace_bytes(int64_t count) { return advance_workspace(count > ((int64_t)1 << 30) ? (int64_t)1 << 30 : count).bytes; }
@@ -1810,47 +1952,19 @@ int rt_scene_path_advance_device(rt_scene *scene, const rt_path_advance_params *
     advance_args(p, rays, out, w, aa, ga);
     if (int rc = device_jump_table(p->device, &aa.jump_table)) return rc;
     hipStream_t stream = (hipStream_t)p->stream;
-    if (!dt.advance_done) HIP_TRY(hipEventCreateWithFlags(&dt.advance_done, hipEventDisableTiming));
-    const auto three = [&]() -> hipError_t {  // the call's kernels, in the stream's order
-        hipError_t e = kBuilds[p->variant].advance(dt.scene, aa, stream, nullptr);
+    const auto three = [&](QueryKernelInfo *info) -> hipError_t {  // the call's kernels, in the stream's order (or the first one's registers)
+        hipError_t e = kBuilds[p->variant].advance(dt.scene, aa, stream, info);
+        if (info) return e;
         if (e == hipSuccess) e = launch_advance_scan(aa.block_counts, const_cast<uint32_t *>(ga.block_offsets), w.n_blocks, out->count, stream);
         if (e == hipSuccess) e = launch_advance_gather(ga, stream);
         return e;
     };
-    if (!stats) {  // enqueue and return: whoever frees the tables waits for the event
-        hipError_t e = three();
-        const hipError_t recorded = hipEventRecord(dt.advance_done, stream);
-        if (e == hipSuccess) e = recorded;
-        return e == hipSuccess ? RT_OK : hip_fail(e, who);
+    TimedRun run{};
+    if (int rc = run_advance(three, {&aa.stepped_counter}, 1, out->count, dt, p->device, stream, who, stats, run)) return rc;
+    if (stats) {
+        stats->rays = run.counted[0];
+        stats->scattered = run.word;
     }
-    QueryKernelInfo info{};
-    HIP_TRY(kBuilds[p->variant].advance(dt.scene, aa, stream, &info));
-    DeviceArena scratch(p->device);
-    HIP_TRY(scratch.alloc(1, aa.stepped_counter));
-    // from here on the chain: the events are destroyed, and the stream waited for, whatever fails
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    unsigned long long stepped = 0;
-    uint32_t survivors = 0;
-    hipError_t e = hipEventCreate(&ev[0]);
-    if (e == hipSuccess) e = hipEventCreate(&ev[1]);
-    if (e == hipSuccess) e = hipMemsetAsync(aa.stepped_counter, 0, sizeof(unsigned long long), stream);
-    if (e == hipSuccess) e = hipEventRecord(ev[0], stream);
-    if (e == hipSuccess) e = three();
-    if (e == hipSuccess) e = hipEventRecord(ev[1], stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(&stepped, aa.stepped_counter, sizeof stepped, hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(&survivors, out->count, sizeof survivors, hipMemcpyDeviceToHost, stream);
-    const hipError_t waited = hipStreamSynchronize(stream);
-    if (e == hipSuccess) e = waited;
-    float ms = 0.0f;
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev[0], ev[1]);
-    for (hipEvent_t v : ev)
-        if (v) hipEventDestroy(v);
-    if (e != hipSuccess) return hip_fail(e, who);
-    stats->rays = stepped;
-    stats->scattered = survivors;
-    stats->seconds = (double)ms * 1e-3;
-    stats->kernel_vgprs = (uint32_t)info.vgprs;
-    stats->scratch_bytes = (uint32_t)info.scratch_bytes;
     return RT_OK;
 }
 
@@ -1858,58 +1972,7 @@ int rt_scene_path_advance(rt_scene *scene, const rt_path_advance_params *p, cons
                           rt_path_advance_stats *stats)
 {
     if (int rc = path_advance_check(scene, p, rays, out, false, "rt_scene_path_advance")) return rc;
-    if (stats) *stats = rt_path_advance_stats{};
-    if (p->count == 0) return RT_OK;
-    if (int rc = select_device(p->device)) return rc;
-    // the host knows the word: only the rows below n travel
-    const int64_t n = rays->count && (int64_t)*rays->count < p->count ? (int64_t)*rays->count : p->count;
-    if (n == 0) {
-        *out->count = 0;
-        return RT_OK;
-    }
-    Staging stage{DeviceArena(p->device), (size_t)n, {}};
-    rt_path_advance_rays dr{};
-    HIP_TRY(stage.in(rays->origin, 3, dr.origin));
-    HIP_TRY(stage.in(rays->direction, 3, dr.direction));
-    HIP_TRY(stage.in(rays->time, 1, dr.time));
-    HIP_TRY(stage.in(rays->rng_state, 6, dr.rng_state));
-    HIP_TRY(stage.in(rays->throughput, 3, dr.throughput));
-    HIP_TRY(stage.in(rays->ray_id, 1, dr.ray_id));
-    HIP_TRY(stage.in(rays->alive, 1, dr.alive));
-    rt_path_advance_out dout{};
-    if (out->radiance) {
-        const double *uploaded = nullptr;
-        HIP_TRY(stage.arena.upload(out->radiance, (size_t)p->sources * 3, uploaded));
-        dout.radiance = const_cast<double *>(uploaded);
-    }
-    HIP_TRY(stage.out(out->origin, 3, dout.origin));
-    HIP_TRY(stage.out(out->direction, 3, dout.direction));
-    HIP_TRY(stage.out(out->time, 1, dout.time));
-    HIP_TRY(stage.out(out->rng_state, 6, dout.rng_state));
-    HIP_TRY(stage.out(out->throughput, 3, dout.throughput));
-    HIP_TRY(stage.out(out->ray_id, 1, dout.ray_id));
-    HIP_TRY(stage.out(out->t, 1, dout.t));
-    HIP_TRY(stage.out(out->normal, 3, dout.normal));
-    HIP_TRY(stage.out(out->front_face, 1, dout.front_face));
-    HIP_TRY(stage.out(out->material, 1, dout.material));
-    HIP_TRY(stage.arena.alloc(1, dout.count));
-    rt_path_advance_params dp = *p;
-    dp.count = n;
-    dp.stream = nullptr;  // the copies around the advance are synchronous: nothing to order on the caller's stream
-    dp.workspace_bytes = advance_workspace(n).bytes;
-    unsigned char *workspace = nullptr;
-    HIP_TRY(stage.arena.alloc((size_t)dp.workspace_bytes, workspace));
-    dp.workspace = workspace;
-    rt_path_advance_stats waited{};  // with statistics the device call waits
-    if (int rc = rt_scene_path_advance_device(scene, &dp, &dr, &dout, stats ? stats : &waited)) return rc;
-    uint32_t survivors = 0;
-    HIP_TRY(hipMemcpy(&survivors, dout.count, sizeof survivors, hipMemcpyDeviceToHost));
-    if (survivors > (uint32_t)n) survivors = (uint32_t)n;  // (never)
-    for (const Staging::Out &o : stage.outs)  // the first `survivors` rows of each
-        if (survivors) HIP_TRY(hipMemcpy(o.host, o.dev, o.bytes / (size_t)n * survivors, hipMemcpyDeviceToHost));
-    if (out->radiance) HIP_TRY(hipMemcpy(out->radiance, dout.radiance, (size_t)p->sources * 3 * sizeof(double), hipMemcpyDeviceToHost));
-    *out->count = survivors;
-    return RT_OK;
+    return host_batch(scene, p, rays, out, stats, rt_scene_path_advance_device);
 }
 
 void rt_path_advance_abi_sizes(uint32_t out4[4])
@@ -1955,14 +2018,12 @@ static int path_advance_direct_check(rt_scene *scene, const rt_path_advance_dire
                                      const rt_path_advance_direct_out *out, bool device_call, const char *who)
 {
     const std::string name(who);
-    if (!scene || !p || !rays || !out) return fail(RT_ERR_INVALID, name + ": null argument");
-    if (!S(scene)->committed) return fail(RT_ERR_STATE, name + ": scene not committed (rt_scene_commit)");
-    if (p->count < 0 || p->count > ((int64_t)1 << 30)) return fail(RT_ERR_INVALID, name + ": count must be 0 .. 2^30");
-    if (p->sources < 0 || p->sources > ((int64_t)1 << 30)) return fail(RT_ERR_INVALID, name + ": sources must be 0 .. 2^30");
-    if (p->variant != 0 && p->variant != 1) return fail(RT_ERR_INVALID, name + ": variant must be 0 (strict) or 1 (fast)");
-    if (p->strategy != 0 && p->strategy != 1) return fail(RT_ERR_INVALID, name + ": strategy must be 0 (uniform) or 1 (by area and brightness)");
-    if (p->sample != 0 && p->sample != 1) return fail(RT_ERR_INVALID, name + ": sample must be 0 (no light samples in this call) or 1");
-    if (p->count > 0 && (!rays->origin || !rays->direction)) return fail(RT_ERR_INVALID, name + ": null origin or direction");
+    const auto sources = [&] { return p->sources < 0 || p->sources > ((int64_t)1 << 30) ? ": sources must be 0 .. 2^30" : nullptr; };
+    const auto lights = [&] {
+        const char *why = strategy_error(p->strategy);
+        return why || p->sample == 0 || p->sample == 1 ? why : ": sample must be 0 (no light samples in this call) or 1";
+    };
+    if (int rc = batch_check(scene, p, rays, out, name, sources, lights)) return rc;
     return advance_arrays_check(p, rays, out, rays->scatter_pdf, out->scatter_pdf, device_call ? advance_direct_workspace(p->count).bytes : 0,
                                 "rt_path_advance_direct_workspace_bytes", name);
 }
@@ -2008,57 +2069,26 @@ int rt_scene_path_advance_direct_device(rt_scene *scene, const rt_path_advance_d
     ga.scatter_pdf_to = out->scatter_pdf;
     const bool shadows = da.n_lights != 0 && da.sample != 0;  // else launch 1 leaves no row pending: launch 2 is not enqueued
     hipStream_t stream = (hipStream_t)p->stream;
-    if (!dt.advance_done) HIP_TRY(hipEventCreateWithFlags(&dt.advance_done, hipEventDisableTiming));
-    const auto four = [&]() -> hipError_t {  // the call's kernels, in the stream's order
-        hipError_t e = kBuilds[p->variant].advance_direct(dt.scene, da, stream, nullptr);
-        if (e == hipSuccess && shadows) e = kBuilds[p->variant].advance_shadow(dt.scene, da, stream, nullptr);
+    const auto four = [&](QueryKernelInfo *info) -> hipError_t {  // the call's kernels, in the stream's order (or the registers of the first two)
+        hipError_t e = kBuilds[p->variant].advance_direct(dt.scene, da, stream, info);
+        if (e == hipSuccess && (shadows || info)) e = kBuilds[p->variant].advance_shadow(dt.scene, da, stream, info ? info + 1 : nullptr);
+        if (info) return e;
         if (e == hipSuccess)
             e = launch_advance_scan(da.adv.block_counts, const_cast<uint32_t *>(ga.rows.block_offsets), w.plain.n_blocks, out->count, stream);
         if (e == hipSuccess) e = launch_advance_direct_gather(ga, stream);
         return e;
     };
-    if (!stats) {  // enqueue and return: whoever frees the tables waits for the event
-        hipError_t e = four();
-        const hipError_t recorded = hipEventRecord(dt.advance_done, stream);
-        if (e == hipSuccess) e = recorded;
-        return e == hipSuccess ? RT_OK : hip_fail(e, who);
+    // the counters: rows stepped; shadow rays cast, shadow rays that reached their lamp
+    TimedRun run{};
+    if (int rc = run_advance(four, {&da.adv.stepped_counter, &da.shadow_counters}, 3, out->count, dt, p->device, stream, who, stats, run)) return rc;
+    if (stats) {
+        stats->rays = run.counted[0];
+        stats->scattered = run.word;
+        stats->shadow_rays = run.counted[1];
+        stats->shadow_reached = run.counted[2];
+        stats->shadow_vgprs = (uint32_t)run.kernel[1].vgprs;
+        stats->shadow_scratch_bytes = (uint32_t)run.kernel[1].scratch_bytes;
     }
-    QueryKernelInfo info{}, shadow_info{};
-    HIP_TRY(kBuilds[p->variant].advance_direct(dt.scene, da, stream, &info));
-    HIP_TRY(kBuilds[p->variant].advance_shadow(dt.scene, da, stream, &shadow_info));
-    DeviceArena scratch(p->device);
-    unsigned long long *counters = nullptr;  // rows stepped, shadow rays cast, shadow rays that reached their lamp
-    HIP_TRY(scratch.alloc(3, counters));
-    da.adv.stepped_counter = counters;
-    da.shadow_counters = counters + 1;
-    // from here on the chain: the events are destroyed, and the stream waited for, whatever fails
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    unsigned long long counted[3] = {0, 0, 0};
-    uint32_t survivors = 0;
-    hipError_t e = hipEventCreate(&ev[0]);
-    if (e == hipSuccess) e = hipEventCreate(&ev[1]);
-    if (e == hipSuccess) e = hipMemsetAsync(counters, 0, sizeof counted, stream);
-    if (e == hipSuccess) e = hipEventRecord(ev[0], stream);
-    if (e == hipSuccess) e = four();
-    if (e == hipSuccess) e = hipEventRecord(ev[1], stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(counted, counters, sizeof counted, hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(&survivors, out->count, sizeof survivors, hipMemcpyDeviceToHost, stream);
-    const hipError_t waited = hipStreamSynchronize(stream);
-    if (e == hipSuccess) e = waited;
-    float ms = 0.0f;
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev[0], ev[1]);
-    for (hipEvent_t v : ev)
-        if (v) hipEventDestroy(v);
-    if (e != hipSuccess) return hip_fail(e, who);
-    stats->rays = counted[0];
-    stats->scattered = survivors;
-    stats->shadow_rays = counted[1];
-    stats->shadow_reached = counted[2];
-    stats->seconds = (double)ms * 1e-3;
-    stats->kernel_vgprs = (uint32_t)info.vgprs;
-    stats->scratch_bytes = (uint32_t)info.scratch_bytes;
-    stats->shadow_vgprs = (uint32_t)shadow_info.vgprs;
-    stats->shadow_scratch_bytes = (uint32_t)shadow_info.scratch_bytes;
     return RT_OK;
 }
 
@@ -2066,60 +2096,7 @@ int rt_scene_path_advance_direct(rt_scene *scene, const rt_path_advance_direct_p
                                  const rt_path_advance_direct_out *out, rt_path_advance_direct_stats *stats)
 {
     if (int rc = path_advance_direct_check(scene, p, rays, out, false, "rt_scene_path_advance_direct")) return rc;
-    if (stats) *stats = rt_path_advance_direct_stats{};
-    if (p->count == 0) return RT_OK;
-    if (int rc = select_device(p->device)) return rc;
-    // the host knows the word: only the rows below n travel
-    const int64_t n = rays->count && (int64_t)*rays->count < p->count ? (int64_t)*rays->count : p->count;
-    if (n == 0) {
-        *out->count = 0;
-        return RT_OK;
-    }
-    Staging stage{DeviceArena(p->device), (size_t)n, {}};
-    rt_path_advance_direct_rays dr{};
-    HIP_TRY(stage.in(rays->origin, 3, dr.origin));
-    HIP_TRY(stage.in(rays->direction, 3, dr.direction));
-    HIP_TRY(stage.in(rays->time, 1, dr.time));
-    HIP_TRY(stage.in(rays->rng_state, 6, dr.rng_state));
-    HIP_TRY(stage.in(rays->throughput, 3, dr.throughput));
-    HIP_TRY(stage.in(rays->ray_id, 1, dr.ray_id));
-    HIP_TRY(stage.in(rays->alive, 1, dr.alive));
-    HIP_TRY(stage.in(rays->scatter_pdf, 1, dr.scatter_pdf));
-    rt_path_advance_direct_out dout{};
-    if (out->radiance) {
-        const double *uploaded = nullptr;
-        HIP_TRY(stage.arena.upload(out->radiance, (size_t)p->sources * 3, uploaded));
-        dout.radiance = const_cast<double *>(uploaded);
-    }
-    HIP_TRY(stage.out(out->origin, 3, dout.origin));
-    HIP_TRY(stage.out(out->direction, 3, dout.direction));
-    HIP_TRY(stage.out(out->time, 1, dout.time));
-    HIP_TRY(stage.out(out->rng_state, 6, dout.rng_state));
-    HIP_TRY(stage.out(out->throughput, 3, dout.throughput));
-    HIP_TRY(stage.out(out->ray_id, 1, dout.ray_id));
-    HIP_TRY(stage.out(out->t, 1, dout.t));
-    HIP_TRY(stage.out(out->normal, 3, dout.normal));
-    HIP_TRY(stage.out(out->front_face, 1, dout.front_face));
-    HIP_TRY(stage.out(out->material, 1, dout.material));
-    HIP_TRY(stage.out(out->scatter_pdf, 1, dout.scatter_pdf));
-    HIP_TRY(stage.arena.alloc(1, dout.count));
-    rt_path_advance_direct_params dp = *p;
-    dp.count = n;
-    dp.stream = nullptr;  // the copies around the advance are synchronous: nothing to order on the caller's stream
-    dp.workspace_bytes = advance_direct_workspace(n).bytes;
-    unsigned char *workspace = nullptr;
-    HIP_TRY(stage.arena.alloc((size_t)dp.workspace_bytes, workspace));
-    dp.workspace = workspace;
-    rt_path_advance_direct_stats waited{};  // with statistics the device call waits
-    if (int rc = rt_scene_path_advance_direct_device(scene, &dp, &dr, &dout, stats ? stats : &waited)) return rc;
-    uint32_t survivors = 0;
-    HIP_TRY(hipMemcpy(&survivors, dout.count, sizeof survivors, hipMemcpyDeviceToHost));
-    if (survivors > (uint32_t)n) survivors = (uint32_t)n;  // (never)
-    for (const Staging::Out &o : stage.outs)  // the first `survivors` rows of each
-        if (survivors) HIP_TRY(hipMemcpy(o.host, o.dev, o.bytes / (size_t)n * survivors, hipMemcpyDeviceToHost));
-    if (out->radiance) HIP_TRY(hipMemcpy(out->radiance, dout.radiance, (size_t)p->sources * 3 * sizeof(double), hipMemcpyDeviceToHost));
-    *out->count = survivors;
-    return RT_OK;
+    return host_batch(scene, p, rays, out, stats, rt_scene_path_advance_direct_device);
 }
 
 void rt_path_advance_direct_abi_sizes(uint32_t out4[4])
@@ -2131,19 +2108,12 @@ void rt_path_advance_direct_abi_sizes(uint32_t out4[4])
 }
 
 // ---- radiance queries with light samples ----
-// rt_radiance_direct_params begins with rt_radiance_params, field for field
-static_assert(sizeof(rt_radiance_direct_params) == sizeof(rt_radiance_params) + 4 * sizeof(int32_t) &&
-                  offsetof(rt_radiance_direct_params, strategy) == sizeof(rt_radiance_params) &&
-                  offsetof(rt_radiance_direct_params, stream) == offsetof(rt_radiance_params, stream) &&
-                  offsetof(rt_radiance_direct_params, variant) == offsetof(rt_radiance_params, variant),
-              "rt_radiance_direct_params: rt_radiance_params and the strategy behind it");
-
 // everything that can be refused without a device, in the order include/rtow.h lists it: rt_scene_radiance's, then the strategy
 static int radiance_direct_check(rt_scene *scene, const rt_radiance_direct_params *p, const rt_radiance_rays *rays, const rt_radiance_out *out,
                                  const char *who)
 {
-    if (int rc = radiance_check(scene, reinterpret_cast<const rt_radiance_params *>(p), rays, out, who)) return rc;
-    if (p->strategy != 0 && p->strategy != 1) return fail(RT_ERR_INVALID, std::string(who) + ": strategy must be 0 (uniform) or 1 (by area and brightness)");
+    if (int rc = radiance_check(scene, p, rays, out, who)) return rc;
+    if (const char *why = strategy_error(p->strategy)) return fail(RT_ERR_INVALID, std::string(who) + why);
     return RT_OK;
 }
 
@@ -2158,63 +2128,21 @@ int rt_scene_radiance_direct_device(rt_scene *scene, const rt_radiance_direct_pa
     if (int rc = rt_scene_upload(scene, p->device)) return rc;  // (selects the device)
     DeviceTables &dt = *s.device[p->device];
     RadianceDirectArgs da{};
-    RadianceArgs &ra = da.rad;
-    ra.origin = rays->origin;
-    ra.direction = rays->direction;
-    ra.time = rays->time;
-    ra.time_all = p->time;
-    ra.rng_in = rays->rng_state;
-    ra.radiance = out->radiance;
-    ra.path_rays = out->path_rays;
-    ra.rng_out = out->rng_state;
-    if (int rc = device_jump_table(p->device, &ra.jump_table)) return rc;
-    ra.base = xorwow_seed(p->seed, kSaltCurandDevice);
-    ra.first_sequence = p->first_sequence;
-    ra.count = (uint32_t)p->count;
-    ra.samples = p->samples;
-    ra.max_depth = p->max_depth;
+    if (int rc = radiance_args(p, rays, out, da.rad)) return rc;
     da.rows = dt.lights;
     da.cdf = dt.light_cdf[p->strategy];
     da.n_lights = dt.n_lights;
     da.node_leaf_pos = dt.node_leaf_pos;
     hipStream_t stream = (hipStream_t)p->stream;
-    if (!stats) {  // the launch and the wait alone
-        hipError_t e = kBuilds[p->variant].radiance_direct(dt.scene, da, stream, nullptr);
-        const hipError_t waited = hipStreamSynchronize(stream);
-        if (e == hipSuccess) e = waited;
-        return e == hipSuccess ? RT_OK : hip_fail(e, who);
+    const auto launch = [&](QueryKernelInfo *info) { return kBuilds[p->variant].radiance_direct(dt.scene, da, stream, info); };
+    // the counters: path searches; shadow rays cast, shadow rays that reached their lamp
+    TimedRun run{};
+    if (int rc = run_lane_kernel(launch, {&da.rad.ray_counter, &da.shadow_counters}, 3, p->device, stream, who, stats, run)) return rc;
+    if (stats) {
+        stats->rays = run.counted[0];
+        stats->shadow_rays = run.counted[1];
+        stats->shadow_reached = run.counted[2];
     }
-    // with statistics: the kernel's registers, two events around it, and three words of this call's own for the counts
-    QueryKernelInfo info{};
-    HIP_TRY(kBuilds[p->variant].radiance_direct(dt.scene, da, stream, &info));
-    DeviceArena scratch(p->device);
-    unsigned long long *counters = nullptr;  // path searches, shadow rays cast, shadow rays that reached their lamp
-    HIP_TRY(scratch.alloc(3, counters));
-    ra.ray_counter = counters;
-    da.shadow_counters = counters + 1;
-    // from here on the chain: the events are destroyed, and the stream waited for, whatever fails
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    unsigned long long counted[3] = {0, 0, 0};
-    hipError_t e = hipEventCreate(&ev[0]);
-    if (e == hipSuccess) e = hipEventCreate(&ev[1]);
-    if (e == hipSuccess) e = hipMemsetAsync(counters, 0, sizeof counted, stream);
-    if (e == hipSuccess) e = hipEventRecord(ev[0], stream);
-    if (e == hipSuccess) e = kBuilds[p->variant].radiance_direct(dt.scene, da, stream, nullptr);
-    if (e == hipSuccess) e = hipEventRecord(ev[1], stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(counted, counters, sizeof counted, hipMemcpyDeviceToHost, stream);
-    const hipError_t waited = hipStreamSynchronize(stream);
-    if (e == hipSuccess) e = waited;
-    float ms = 0.0f;
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev[0], ev[1]);
-    for (hipEvent_t v : ev)
-        if (v) hipEventDestroy(v);
-    if (e != hipSuccess) return hip_fail(e, who);
-    stats->rays = counted[0];
-    stats->shadow_rays = counted[1];
-    stats->shadow_reached = counted[2];
-    stats->seconds = (double)ms * 1e-3;
-    stats->kernel_vgprs = (uint32_t)info.vgprs;
-    stats->scratch_bytes = (uint32_t)info.scratch_bytes;
     return RT_OK;
 }
 
@@ -2222,24 +2150,7 @@ int rt_scene_radiance_direct(rt_scene *scene, const rt_radiance_direct_params *p
                              rt_radiance_direct_stats *stats)
 {
     if (int rc = radiance_direct_check(scene, p, rays, out, "rt_scene_radiance_direct")) return rc;
-    if (stats) *stats = rt_radiance_direct_stats{};
-    if (p->count == 0) return RT_OK;
-    if (int rc = select_device(p->device)) return rc;
-    Staging stage{DeviceArena(p->device), (size_t)p->count, {}};
-    rt_radiance_rays dr{};
-    HIP_TRY(stage.in(rays->origin, 3, dr.origin));
-    HIP_TRY(stage.in(rays->direction, 3, dr.direction));
-    HIP_TRY(stage.in(rays->time, 1, dr.time));
-    HIP_TRY(stage.in(rays->rng_state, 6, dr.rng_state));
-    rt_radiance_out dout{};
-    HIP_TRY(stage.out(out->radiance, 3, dout.radiance));
-    HIP_TRY(stage.out(out->path_rays, 1, dout.path_rays));
-    HIP_TRY(stage.out(out->rng_state, 6, dout.rng_state));
-    rt_radiance_direct_params dp = *p;
-    dp.stream = nullptr;  // the copies around the query are synchronous: nothing to order on the caller's stream
-    if (int rc = rt_scene_radiance_direct_device(scene, &dp, &dr, &dout, stats)) return rc;
-    HIP_TRY(stage.fetch());
-    return RT_OK;
+    return host_batch(scene, p, rays, out, stats, rt_scene_radiance_direct_device);
 }
 
 void rt_radiance_direct_abi_sizes(uint32_t out4[4])
