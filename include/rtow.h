@@ -230,6 +230,51 @@ RTOW_API rt_handle rt_rotate_z(rt_scene *s, rt_handle object, double angle_degre
 RTOW_API rt_handle rt_scale(rt_scene *s, rt_handle object, double sx, double sy, double sz);
 /* L (9, row-major), t (3), Li (9, row-major) of a Transform exactly as stored and uploaded.  RT_ERR_INVALID: not a Transform. */
 RTOW_API int rt_transform_get(rt_scene *s, rt_handle transform, double out21[21]);
+/* A moving instance: rt_transform's matrix keyed at two times and interpolated ENTRY BY ENTRY per ray on the device, so that any
+ * hittable -- a mesh, a box, a fog, a whole BvhNode -- moves during the shutter.  m0 = [L0 | t0] holds at time0, m1 = [L1 | t1] at
+ * time1 (both row-major 3x4 as rt_transform's m).  It stands wherever an rt_transform may stand.  The reference has no such class;
+ * each line below is one IEEE double operation, nothing contracted in the strict build:
+ *   creation    dL[r][c] = L1[r][c] - L0[r][c]      dt[r] = t1[r] - t0[r]      dtime = time1 - time0
+ *               L0, t0, dL, dt, time0, dtime are stored, uploaded and used exactly as rt_moving_transform_get returns them.
+ *   per ray     of time tm:
+ *                 s = (tm - time0) / dtime,  then  s = fmin(fmax(s, 0.0), 1.0)
+ *                 L[r][c] = L0[r][c] + (s * dL[r][c])      t[r] = t0[r] + (s * dt[r])
+ *                 Li from L by rt_transform's cofactor formula: the same nine cofactors, the same det, one division an entry,
+ *                 computed on the device in that order.
+ *               A time outside [time0, time1] sees the nearer key and a NaN time sees key 0 (fmax drops the NaN).  MovingSphere's
+ *               unclamped rule is the reference's and stays; this class is the library's, and the clamp is what makes its box valid
+ *               for every ray a query can send.
+ *   Hit, HitRecord, media
+ *               exactly rt_transform's lines with this ray's L, t, Li: the local ray is recomputed from the world ray, d' is not
+ *               normalised, t is the world's, P = (L P') + t, the normal goes through Li^T and is renormalised.  A ConstantMedium
+ *               under the step measures in object space, one whose boundary is the step measures where it is called.  The way back
+ *               of the hit record forms L and Li again from the same tm, so it uses the same bits.
+ *   box         the eight corners of the child's box (rt_transform's order) go forward with (L0, t0) and with the matrices of s = 1
+ *               as the device forms them, L0 + (1.0 * dL) and t0 + (1.0 * dt); per axis fmin / fmax over the sixteen points; every
+ *               bound is then widened outward by 16 * DBL_EPSILON * (the largest absolute coordinate among the sixteen) -- a point
+ *               at an intermediate s is a convex combination of its two key positions only up to the seven roundings of (L p) + t,
+ *               each at most half an ulp of a sum of three products bounded by that coordinate --; then the corner constructor with
+ *               its padding, as rt_rotate_y.
+ *   refused     (returns 0, nothing added, rt_last_error says why) whatever rt_transform refuses, for either key; time0 or time1
+ *               non-finite, or time1 <= time0; a non-finite dL, dt or dtime; a matrix L(s) that is singular, or cannot be shown
+ *               regular, somewhere in [0, 1] (below); a child subtree that holds ANY emissive primitive outside a ConstantMedium
+ *               boundary: the light table is in world space and static, a moving lamp is out of scope.
+ *   singular in between
+ *               det(L(s)) is a cubic in s.  With rows a_i of L0 and b_i of L0 + (1.0 * dL) its Bernstein coefficients over [0, 1]
+ *               are det(a0,a1,a2); a third of det(b0,a1,a2) + det(a0,b1,a2) + det(a0,a1,b2); a third of det(b0,b1,a2) +
+ *               det(b0,a1,b2) + det(a0,b1,b2); det(b0,b1,b2).  The step is accepted if all four have one strict sign; otherwise
+ *               the interval is halved (de Casteljau) up to depth 8 and accepted only if every piece is proven so.  A coefficient
+ *               counts as positive (negative) only beyond 2^-30 of the largest of the first four in absolute value, which covers
+ *               the roundings of the halving.  Equal signs of the two key determinants are not enough: a half turn about Z,
+ *               L1 = diag(-1, -1, 1), has det = (1 - 2s)^2.
+ * Entry-wise interpolation is no rotation: keys that differ by a rotation through an angle theta shrink the object by cos(theta / 2)
+ * at mid-shutter.  Key rotations in small angles, and split a long motion into several steps of consecutive time intervals. */
+RTOW_API rt_handle rt_moving_transform(rt_scene *s, rt_handle object, const double m0[12], const double m1[12], double time0, double time1);
+/* L = the identity at both keys, t = offset0 at time0 and offset1 at time1; calls rt_moving_transform. */
+RTOW_API rt_handle rt_moving_translate(rt_scene *s, rt_handle object, const double offset0[3], const double offset1[3], double time0, double time1);
+/* L0 (9, row-major), t0 (3), dL (9, row-major), dt (3), time0, dtime = time1 - time0 of a moving instance exactly as stored and
+ * uploaded.  RT_ERR_INVALID: not such a handle. */
+RTOW_API int rt_moving_transform_get(rt_scene *s, rt_handle h, double out26[26]);
 RTOW_API rt_handle rt_make_box(rt_scene *s, const double a[3], const double b[3], rt_handle material); /* Instance.h:166 */
 RTOW_API rt_handle rt_hittable_list(rt_scene *s, const rt_handle *objects, int count);        /* HittableList.h:21 */
 RTOW_API rt_handle rt_constant_medium(rt_scene *s, rt_handle boundary, double density, double r, double g,

@@ -139,6 +139,18 @@ public:
     Hittable RotateX(Hittable o, double degrees) { return {ok(rt_rotate_x(s_, o.h, degrees))}; }
     Hittable RotateZ(Hittable o, double degrees) { return {ok(rt_rotate_z(s_, o.h, degrees))}; }
     Hittable Scale(Hittable o, double sx, double sy, double sz) { return {ok(rt_scale(s_, o.h, sx, sy, sz))}; }
+    // moving instances (rt_moving_transform): m0 holds at time0, m1 at time1, interpolated entry by entry per ray
+    Hittable MovingTransform(Hittable o, const double m0[12], const double m1[12], double time0 = 0.0, double time1 = 1.0)
+    {
+        return {ok(rt_moving_transform(s_, o.h, m0, m1, time0, time1))};
+    }
+    Hittable MovingTranslate(Hittable o, const Vector3 &off0, const Vector3 &off1, double time0 = 0.0, double time1 = 1.0)
+    {
+        const double a[3] = {off0.x, off0.y, off0.z}, b[3] = {off1.x, off1.y, off1.z};
+        return {ok(rt_moving_translate(s_, o.h, a, b, time0, time1))};
+    }
+    // L0 (9), t0 (3), dL (9), dt (3), time0, time1 - time0 of a moving instance as stored and uploaded (rt_moving_transform_get)
+    void MovingTransformKeys(Hittable moving, double out26[26]) { check(rt_moving_transform_get(s_, moving.h, out26)); }
     Hittable MakeBox(const Point3 &a, const Point3 &b, Material m)
     {
         const double aa[3] = {a.x, a.y, a.z}, bb[3] = {b.x, b.y, b.z};

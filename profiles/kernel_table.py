@@ -5,7 +5,7 @@ advance_direct_kernel, shadow_kernel, advance_direct_gather_kernel, radiance_dir
 import os, re, subprocess, sys
 so = sys.argv[1] if len(sys.argv) > 1 else os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', 'raytracinginoneweekendincuda_amd', 'librtow_hip.so')
 # The kernels listed by name: patterns of the mangled name whose groups (name, strict, world, mode -- those the kernel has) make the label
-TRAITS = r'ILi(?P<strict>\d)ENS_(?:6affine)?12_GLOBAL__N_16TraitsILi(?P<world>\d)E'
+TRAITS = r'ILi(?P<strict>\d)ENS\d?_(?:6affine)?12_GLOBAL__N_16TraitsILi(?P<world>\d)E'
 LANE_KERNELS = [
     r'(?P<name>feature_kernel|radiance_kernel|step_kernel|advance_kernel|advance_direct_kernel|shadow_kernel|radiance_direct_kernel|film_direct_kernel)' + TRAITS,
     r'(?P<name>query_kernel)' + TRAITS + r'.*?EELi(?P<mode>\d)EEEv',  # MODE 0 closest hit, 1 occlusion
@@ -27,12 +27,13 @@ for i, st in enumerate(idx[1:]):
         if m: cur[m.group(1)] = m.group(2)
         if line.startswith('.wavefront_size'):
             n = cur.get('name', '')
-            affine = ' affine' if 'NS_6affine' in n else ''   # a unit compiled with the general affine chain step (render.hip RT_AFFINE)
-            m = re.search(r'render_kernelILi(\d)ENS_(?:6affine)?12_GLOBAL__N_1(8AdaptiveINS\d_)?6TraitsILi(\d)ELb(\d)ELb(\d)ELi(\d)ELb(\d)ELb(\d)ELb(\d)ELi(\d+)ELb(\d)ELb(\d)', n)
+            affine = ' affine' if '_6affine' in n else ''   # a unit compiled with the general affine chain step (render.hip RT_AFFINE)
+            if 'rtow6moving' in n: affine += ' moving'    # its second pass, with the moving step as well (render.hip RT_MOVING)
+            m = re.search(r'render_kernelILi(\d)ENS\d?_(?:6affine)?12_GLOBAL__N_1(8AdaptiveINS\d_)?6TraitsILi(\d)ELb(\d)ELb(\d)ELi(\d)ELb(\d)ELb(\d)ELb(\d)ELi(\d+)ELb(\d)ELb(\d)', n)
             if m:
                 adaptive = m.group(2) is not None  # the Adaptive<> form of the instantiation (render.hip)
                 strict, world, comp, rich, waves, media, batch, nested, block, fast, grouped = (int(x) for k, x in enumerate(m.groups()) if k != 1)
-                rows.append((int(adaptive) + (2 if affine else 0), world, comp, rich, media, batch, nested, fast, grouped, block, waves, 'strict' if strict else 'fast',
+                rows.append((int(adaptive) + (2 if affine else 0) + (4 if 'moving' in affine else 0), world, comp, rich, media, batch, nested, fast, grouped, block, waves, 'strict' if strict else 'fast',
                              int(cur['vgpr_count']), int(cur['private_segment_fixed_size']), int(cur['vgpr_spill_count'])))
             for pattern in LANE_KERNELS:
                 m = re.search(pattern, n)
@@ -45,7 +46,7 @@ for i, st in enumerate(idx[1:]):
                                int(cur['group_segment_fixed_size'])))
             cur = {}
 print("world comp rich media batch nested fast grouped block waves build vgpr scratchB spills")
-for r in sorted(rows): print(*r[1:], *(['adaptive'] if r[0] & 1 else []), *(['affine'] if r[0] & 2 else []))
+for r in sorted(rows): print(*r[1:], *(['adaptive'] if r[0] & 1 else []), *(['affine'] if r[0] & 2 else []), *(['moving'] if r[0] & 4 else []))
 if others:
     print("kernel vgpr scratchB spills ldsB")
     for r in sorted(others): print(*r)

@@ -304,6 +304,9 @@ SIGNATURES = {
     "rt_rotate_z": (H, [P, H, D]),
     "rt_scale": (H, [P, H, D, D, D]),
     "rt_transform_get": (C.c_int, [P, H, C.POINTER(C.c_double)]),
+    "rt_moving_transform": (H, [P, H, C.POINTER(C.c_double), C.POINTER(C.c_double), D, D]),
+    "rt_moving_translate": (H, [P, H, D3, D3, D, D]),
+    "rt_moving_transform_get": (C.c_int, [P, H, C.POINTER(C.c_double)]),
     "rt_make_box": (H, [P, D3, D3, H]),
     "rt_hittable_list": (H, [P, C.POINTER(H), I]),
     "rt_constant_medium": (H, [P, H, D, D, D, D]),

@@ -230,18 +230,41 @@ class Scene:
     def RotateY(self, obj, degrees):
         return _h(lib().rt_rotate_y(self._p, obj, degrees))
 
-    def Transform(self, obj, matrix):
-        """A general affine instance x_world = L x_obj + t (rt_transform): ``matrix`` is 3x4 ``[L | t]``, or 4x4 with the last row
-        0 0 0 1.  Stands wherever Translate / RotateY may stand; rtow.h states its arithmetic operation by operation."""
+    @staticmethod
+    def _matrix34(matrix, who):
         m = np.array(matrix, dtype=np.float64)
         if m.shape == (4, 4):
             if not np.array_equal(m[3], [0.0, 0.0, 0.0, 1.0]):
-                raise RtowError("Transform: the last row of a 4x4 matrix must be 0 0 0 1")
+                raise RtowError(f"{who}: the last row of a 4x4 matrix must be 0 0 0 1")
             m = m[:3]
         if m.shape != (3, 4):
-            raise RtowError("Transform: matrix must be 3x4 or 4x4")
-        m = np.ascontiguousarray(m)
+            raise RtowError(f"{who}: matrix must be 3x4 or 4x4")
+        return np.ascontiguousarray(m)
+
+    def Transform(self, obj, matrix):
+        """A general affine instance x_world = L x_obj + t (rt_transform): ``matrix`` is 3x4 ``[L | t]``, or 4x4 with the last row
+        0 0 0 1.  Stands wherever Translate / RotateY may stand; rtow.h states its arithmetic operation by operation."""
+        m = self._matrix34(matrix, "Transform")
         return _h(lib().rt_transform(self._p, obj, m.ctypes.data_as(C.POINTER(C.c_double))))
+
+    def MovingTransform(self, obj, matrix0, matrix1, time0=0.0, time1=1.0):
+        """A moving instance (rt_moving_transform): ``matrix0`` holds at ``time0``, ``matrix1`` at ``time1`` (each as Transform's
+        ``matrix``); per ray the two are interpolated entry by entry at the ray's time, clamped to the interval.  Stands wherever a
+        Transform may stand; a child that holds a lamp and a matrix that turns singular in between are refused."""
+        m0, m1 = self._matrix34(matrix0, "MovingTransform"), self._matrix34(matrix1, "MovingTransform")
+        dp = C.POINTER(C.c_double)
+        return _h(lib().rt_moving_transform(self._p, obj, m0.ctypes.data_as(dp), m1.ctypes.data_as(dp), float(time0), float(time1)))
+
+    def MovingTranslate(self, obj, offset0, offset1, time0=0.0, time1=1.0):
+        """A moving instance whose matrix is the identity: at ``offset0`` at ``time0``, at ``offset1`` at ``time1``."""
+        return _h(lib().rt_moving_translate(self._p, obj, _v3(offset0), _v3(offset1), float(time0), float(time1)))
+
+    def moving_transform_keys(self, handle):
+        """``(L0, t0, dL, dt, time0, dtime)`` of a moving instance exactly as stored and uploaded (rt_moving_transform_get)."""
+        out = (C.c_double * 26)()
+        _check(lib().rt_moving_transform_get(self._p, handle, out))
+        a = np.array(out, dtype=np.float64)
+        return a[:9].reshape(3, 3).copy(), a[9:12].copy(), a[12:21].reshape(3, 3).copy(), a[21:24].copy(), float(a[24]), float(a[25])
 
     def RotateX(self, obj, degrees):
         return _h(lib().rt_rotate_x(self._p, obj, degrees))

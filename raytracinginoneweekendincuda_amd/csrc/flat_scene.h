@@ -99,7 +99,7 @@ struct BoxRec { double na[6], d[6], mn[3], mx[3]; uint32_t quad_first, pad; };
 
 
 // Instance transform step (R/Instance.h:31-37 Translate, :74-112 RotateY).
-enum : uint32_t { XF_TRANSLATE = 0u, XF_ROTATE_Y = 1u, XF_AFFINE = 2u, XF_AFFINE_ROW = 3u };
+enum : uint32_t { XF_TRANSLATE = 0u, XF_ROTATE_Y = 1u, XF_AFFINE = 2u, XF_AFFINE_ROW = 3u, XF_MOVING = 4u };
 struct Xform { double a, b, c; uint32_t kind; uint32_t pad; };  // translate: offset xyz; rotate: a = sin, b = cos
 // A general affine step (include/rtow.h rt_transform: x_world = L x_obj + t, Li = the inverse of L) is kAffineRows consecutive rows
 // of this table, so that it is staged in LDS, or not, with the chain it belongs to:
@@ -110,8 +110,18 @@ struct Xform { double a, b, c; uint32_t kind; uint32_t pad; };  // translate: of
 // it.  ObjectRec::xf_count and TreeNodeRec::chain_count count ROWS; rt_scene_info::n_xforms counts steps.  Only a scene with
 // SCENE_AFFINE holds such rows.
 constexpr uint32_t kAffineRows = 7;
+// A moving affine step (include/rtow.h rt_moving_transform: the matrix keyed at two times, L(s) = L0 + s dL, t(s) = t0 + s dt with
+// s = clamp((time - time0) / dtime, 0, 1) per ray; Li is formed on the device from L(s)) is kMovingRows consecutive rows:
+//   row 0      XF_MOVING      a, b, c = t0                 pad = 0
+//   rows 1..3  XF_AFFINE_ROW  a, b, c = row 0..2 of L0     pad = the row's offset from row 0
+//   row 4      XF_AFFINE_ROW  a, b, c = dt                 pad = 4
+//   rows 5..7  XF_AFFINE_ROW  a, b, c = row 0..2 of dL     pad = the row's offset from row 0
+//   row 8      XF_AFFINE_ROW  a = time0, b = dtime, c = 0  pad = 8
+// Only the head row is not XF_AFFINE_ROW, so steps are counted as before.  A walk innermost first tells the two kinds of step by the
+// pad of the last row it meets (kAffineRows - 1 or kMovingRows - 1).  Such a step sets SCENE_AFFINE and SCENE_MOVING.
+constexpr uint32_t kMovingRows = 9;
 
-// Composite leaf: [ConstantMedium] -> chain of Translate / RotateY / Transform steps (outermost first) -> geometry.
+// Composite leaf: [ConstantMedium] -> chain of Translate / RotateY / Transform / MovingTransform steps (outermost first) -> geometry.
 enum : uint32_t { GEOM_SINGLE = 0u, GEOM_SPHERES = 1u, GEOM_MSPHERES = 2u, GEOM_QUADS = 3u, GEOM_MIXED = 4u,
                   GEOM_BVH = 5u,    // `first` = root of a sub-BVH (in nodes[]) over the group's primitives
                   GEOM_BOX = 6u };  // six axis-aligned quads that form a MakeBox box: `first` = index into boxes
@@ -141,7 +151,7 @@ struct MediumRec { double neg_inv_density; uint32_t phase_mat; uint32_t sphere; 
 // evaluated by an explicit-stack interpreter (render.hip tree_hit) that makes the reference's calls in the reference's order.
 // `chain` = the transforms the world ray has gone through when this node's Hit is called (outermost first, a private
 // contiguous run of xforms[]): the local ray is always recomputed from the world ray, never un-transformed.
-enum : uint32_t { TN_PRIM = 0u, TN_TRANSLATE = 1u, TN_ROTATE_Y = 2u, TN_MEDIUM = 3u, TN_LIST = 4u, TN_BVH = 5u, TN_TRANSFORM = 6u };
+enum : uint32_t { TN_PRIM = 0u, TN_TRANSLATE = 1u, TN_ROTATE_Y = 2u, TN_MEDIUM = 3u, TN_LIST = 4u, TN_BVH = 5u, TN_TRANSFORM = 6u };  // TN_TRANSFORM: a Transform or a MovingTransform (the node's chain tells them apart)
 struct TreeNodeRec {
     uint32_t kind;
     uint32_t a;  // PRIM: primitive ref; TRANSLATE / ROTATE_Y / TRANSFORM / MEDIUM: child node; LIST: first entry of tree_items[]; BVH: root in tree_bvh[]
@@ -327,7 +337,8 @@ enum : uint32_t {
     SCENE_WORLD_MSPHERES = 16u,   // WORLD_BVH of spheres / unit-time moving spheres only: ms_planes is filled
     SCENE_SEGMENTED = 64u,        // WORLD_BVH with composite leaves: fast_nodes / fast_order / seg_media describe the segmented walk
     SCENE_VERTEX_ATTR = 128u,     // some triangle row carries corner normals or texture coordinates (TriAttrRow)
-    SCENE_AFFINE = 256u,          // some chain holds a general affine step (XF_AFFINE): served by the units compiled with RT_AFFINE (render.hip RT_TO_AFFINE)
+    SCENE_AFFINE = 256u,          // some chain holds a general affine step (XF_AFFINE, XF_MOVING): served by the units compiled with RT_AFFINE (render.hip RT_TO_AFFINE)
+    SCENE_MOVING = 512u,          // some chain holds a moving step (XF_MOVING; SCENE_AFFINE is set too): served by the second pass of those units (render.hip RT_MOVING)
 };
 
 } // namespace rtow

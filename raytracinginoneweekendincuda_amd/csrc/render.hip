@@ -75,15 +75,22 @@
 #ifndef RT_AFFINE  // 1: this translation unit compiles the general affine chain step (rt_transform) into its chain walks; its launchers
 #define RT_AFFINE 0  // carry the suffix _x and serve the scenes with SCENE_AFFINE.  0: chains hold Translate / RotateY only, the code without it
 #endif
+#ifndef RT_MOVING  // 1: the second pass of an RT_AFFINE unit over this file (its last lines include it once more): everything again in
+#define RT_MOVING 0  // namespace rtow::moving with the moving chain step (rt_moving_transform) compiled into the chain walks; those launchers
+#endif               // carry the suffix _xm and serve the scenes with SCENE_MOVING.  0: the walks hold no such branch
 // the lane-per-ray units: one lane per pixel, ray or point, no persistent waves (film_direct_kernel alone is persistent: its lanes take pixels from a queue)
 #define RT_LANE_UNIT (RT_FEATURES || RT_QUERY || RT_RADIANCE || RT_STEP || RT_ADVANCE || RT_LIGHTS || RT_ADVANCE_DIRECT || RT_RADIANCE_DIRECT || RT_FILM_DIRECT)
 
 namespace rtow {
+#if RT_MOVING
+namespace moving {
+#endif
 #if RT_AFFINE
 inline namespace affine {
 #endif
 namespace {
 constexpr bool kAffineUnit = RT_AFFINE != 0;
+constexpr bool kMovingUnit = RT_MOVING != 0;
 
 // Kernel specialisation.  One source, a few instantiations; the host picks by what the scene contains so
 // that a scene never pays registers or code for features it does not use:
@@ -571,6 +578,70 @@ DEV void affine_to_world(const DeviceScene &sc, uint32_t head, Vec &p, Vec &n)
     const Vec m = mk(((i0.a * n.x) + (i1.a * n.y)) + (i2.a * n.z), ((i0.b * n.x) + (i1.b * n.y)) + (i2.b * n.z), ((i0.c * n.x) + (i1.c * n.y)) + (i2.c * n.z));
     n = (1.0 / sqrt(length_sq(m))) * m;
 }
+// A moving affine step (include/rtow.h rt_moving_transform; flat_scene.h XF_MOVING has the rows): the step above with its matrix keyed at
+// two times.  Per ray: s = clamp((tm - time0) / dtime, 0, 1) (a NaN time sees key 0: fmax drops it), L = L0 + (s * dL), t = t0 + (s * dt)
+// entry by entry, Li from L by rt_transform's cofactor formula.  Nothing of it is kept between the walks: make_surface forms the same
+// L and Li again from the same tm, so the way back uses the bits the way in used, and no walk carries eighteen doubles for the rest of
+// a bounce.  Li's rows are M.i[0..2], L's M.l[0..2].
+// Only the second pass of an affine unit (kMovingUnit) compiles the step into its walks, as their unlikely branch: a scene whose chains
+// hold static steps alone runs the walks without it.  moving_local / moving_world read the step's rows through a generic pointer,
+// from LDS or from global memory as the table is staged.
+struct MovingPose { Vec l[3], i[3], t; };
+struct VecPair { Vec a, b; };
+DEV MovingPose moving_pose(const Xform *rows, double tm)
+{
+    const Xform t0 = rows[0], dt = rows[4], key = rows[8];
+    double s = (tm - key.a) / key.b;
+    s = fmin(fmax(s, 0.0), 1.0);
+    MovingPose m;
+    for (uint32_t r = 0; r < 3; r++) {
+        const Xform a = rows[1 + r], d = rows[5 + r];
+        m.l[r] = mk(a.a + (s * d.a), a.b + (s * d.b), a.c + (s * d.c));
+    }
+    m.t = mk(t0.a + (s * dt.a), t0.b + (s * dt.b), t0.c + (s * dt.c));
+    const Vec l0 = m.l[0], l1 = m.l[1], l2 = m.l[2];
+    const double c00 = (l1.y * l2.z) - (l1.z * l2.y), c01 = (l1.z * l2.x) - (l1.x * l2.z), c02 = (l1.x * l2.y) - (l1.y * l2.x);
+    const double c10 = (l0.z * l2.y) - (l0.y * l2.z), c11 = (l0.x * l2.z) - (l0.z * l2.x), c12 = (l0.y * l2.x) - (l0.x * l2.y);
+    const double c20 = (l0.y * l1.z) - (l0.z * l1.y), c21 = (l0.z * l1.x) - (l0.x * l1.z), c22 = (l0.x * l1.y) - (l0.y * l1.x);
+    const double det = ((l0.x * c00) + (l0.y * c01)) + (l0.z * c02);
+    m.i[0] = mk(c00 / det, c10 / det, c20 / det);
+    m.i[1] = mk(c01 / det, c11 / det, c21 / det);
+    m.i[2] = mk(c02 / det, c12 / det, c22 / det);
+    return m;
+}
+DEV Vec pose_rows(const Vec (&m)[3], Vec p)
+{
+    return mk(((m[0].x * p.x) + (m[0].y * p.y)) + (m[0].z * p.z), ((m[1].x * p.x) + (m[1].y * p.y)) + (m[1].z * p.z), ((m[2].x * p.x) + (m[2].y * p.y)) + (m[2].z * p.z));
+}
+// rows: the step's kMovingRows rows.  o' = Li (o - t), d' = Li d with this ray's matrices.
+DEV VecPair moving_local(const Xform *rows, double tm, Vec o, Vec d)
+{
+    const MovingPose m = moving_pose(rows, tm);
+    return VecPair{pose_rows(m.i, o - m.t), pose_rows(m.i, d)};
+}
+// P = (L P') + t; n = Li^T n', renormalised.
+DEV VecPair moving_world(const Xform *rows, double tm, Vec p, Vec n)
+{
+    const MovingPose m = moving_pose(rows, tm);
+    const Vec v = mk(((m.i[0].x * n.x) + (m.i[1].x * n.y)) + (m.i[2].x * n.z), ((m.i[0].y * n.x) + (m.i[1].y * n.y)) + (m.i[2].y * n.z), ((m.i[0].z * n.x) + (m.i[1].z * n.y)) + (m.i[2].z * n.z));
+    return VecPair{pose_rows(m.l, p) + m.t, (1.0 / sqrt(length_sq(v))) * v};
+}
+DEV const Xform *xform_rows(const DeviceScene &sc, uint32_t i)
+{
+    return (sc.lds_xforms != kNone ? reinterpret_cast<const Xform *>(lds_raw + sc.lds_xforms) : sc.xforms) + i;
+}
+DEV void moving_to_local(const DeviceScene &sc, uint32_t head, Ray &lr)
+{
+    const VecPair v = moving_local(xform_rows(sc, head), lr.tm, lr.o, lr.d);
+    lr.o = v.a;
+    lr.d = v.b;
+}
+DEV void moving_to_world(const DeviceScene &sc, uint32_t head, double tm, Vec &p, Vec &n)
+{
+    const VecPair v = moving_world(xform_rows(sc, head), tm, p, n);
+    p = v.a;
+    n = v.b;
+}
 // Ray into the object space of a composite leaf: Translate (R/Instance.h:46) and RotateY (:121-131)
 // applied outermost first.
 DEV Ray to_object_space(const DeviceScene &sc, const ObjectRec &o, const Ray &r)
@@ -584,9 +655,12 @@ DEV Ray to_object_space(const DeviceScene &sc, const ObjectRec &o, const Ray &r)
             double st = x.a, ct = x.b;
             lr.o = mk((ct * lr.o.x) - (st * lr.o.z), lr.o.y, (st * lr.o.x) + (ct * lr.o.z));
             lr.d = mk((ct * lr.d.x) - (st * lr.d.z), lr.d.y, (st * lr.d.x) + (ct * lr.d.z));
-        } else {
+        } else if (!kMovingUnit || __builtin_expect(x.kind == XF_AFFINE, 1)) {
             affine_to_local(sc, o.xf_first + k, x, lr);
             k += kAffineRows - 1;
+        } else {
+            moving_to_local(sc, o.xf_first + k, lr);
+            k += kMovingRows - 1;
         }
     }
     return lr;
@@ -830,9 +904,12 @@ DEV Ray chain_ray(const DeviceScene &sc, uint32_t first, uint32_t count, const R
             double st = x.a, ct = x.b;
             lr.o = mk((ct * lr.o.x) - (st * lr.o.z), lr.o.y, (st * lr.o.x) + (ct * lr.o.z));
             lr.d = mk((ct * lr.d.x) - (st * lr.d.z), lr.d.y, (st * lr.d.x) + (ct * lr.d.z));
-        } else {
+        } else if (!kMovingUnit || __builtin_expect(x.kind == XF_AFFINE, 1)) {
             affine_to_local(sc, first + k, x, lr);
             k += kAffineRows - 1;
+        } else {
+            moving_to_local(sc, first + k, lr);
+            k += kMovingRows - 1;
         }
     }
     return lr;
@@ -2980,9 +3057,12 @@ DEV Surface make_surface(const DeviceScene &sc, const Ray &r, const HitInfo &h)
                     double st = x.a, ct = x.b;
                     s.p = mk((ct * s.p.x) + (st * s.p.z), s.p.y, (-st * s.p.x) + (ct * s.p.z));
                     s.n = mk((ct * s.n.x) + (st * s.n.z), s.n.y, (-st * s.n.x) + (ct * s.n.z));
-                } else {  // x is the last row of the step
+                } else if (!kMovingUnit || __builtin_expect(x.pad == kAffineRows - 1, 1)) {  // x is the last row of the step
                     k -= kAffineRows - 1;
                     affine_to_world(sc, xf_first + k, s.p, s.n);
+                } else {  // the last row of a moving step
+                    k -= kMovingRows - 1;
+                    moving_to_world(sc, xf_first + k, r.tm, s.p, s.n);
                 }
             }
         }
@@ -3702,7 +3782,7 @@ __global__ __launch_bounds__(T::BLOCK, T::MIN_WAVES) void render_kernel(DeviceSc
                             park_put_vec<T::BLOCK>(sc.lds_park, 0, col);
                             park_put_vec<T::BLOCK>(sc.lds_park, 3, throughput);
                             park_put_vec<T::BLOCK>(sc.lds_park, 6, accumulated);
-                            park_put_rng<T::BLOCK>(sc.lds_park, rng);
+                            (park_put_rng<T::BLOCK>)(sc.lds_park, rng);  // (in parentheses: no argument-dependent lookup, which would find the first pass's from the second)
                         }
                         if constexpr (T::WORLD == 0) {
                             walk_begin<T::FAST || T::SEG>(walk, ray, DBL_MAX);
@@ -4066,7 +4146,7 @@ __global__ __launch_bounds__(T::BLOCK, T::MIN_WAVES) void render_kernel(DeviceSc
             if constexpr (T::PARK) {  // back from LDS: what the shading works on (no leaf of these worlds draws random numbers)
                 throughput = park_get_vec<T::BLOCK>(sc.lds_park, 3);
                 accumulated = park_get_vec<T::BLOCK>(sc.lds_park, 6);
-                park_get_rng<T::BLOCK>(sc.lds_park, rng);
+                (park_get_rng<T::BLOCK>)(sc.lds_park, rng);
             }
             bool path_ends;
             if (no_bounces) {
@@ -4182,7 +4262,7 @@ __global__ __launch_bounds__(T::BLOCK, T::MIN_WAVES) void render_kernel(DeviceSc
                 if (active) {
                     park_put_vec<T::BLOCK>(sc.lds_park, 3, throughput);
                     park_put_vec<T::BLOCK>(sc.lds_park, 6, accumulated);
-                    park_put_rng<T::BLOCK>(sc.lds_park, rng);
+                    (park_put_rng<T::BLOCK>)(sc.lds_park, rng);  // (in parentheses: no argument-dependent lookup, which would find the first pass's from the second)
                 }
             }
             if constexpr (T::WORLD == 0) {
@@ -4362,9 +4442,29 @@ hipError_t launch_tile_order(const uint32_t *tile_cost, uint32_t *tile_order, ui
 #endif
 // A scene with a general affine step in some chain (SCENE_AFFINE) is served by the units compiled with RT_AFFINE: every launcher of a
 // kernel that walks chains hands such a scene to its twin there, so a scene without one runs the code it ran before.
-#if RT_AFFINE
-#define RT_SUFFIX RT_CAT(RT_BUILD, _x)
+// A scene with a moving step (SCENE_MOVING) goes one launcher further, to the second pass of the affine unit (RT_MOVING).
+#if RT_AFFINE && RT_MOVING
+#undef RT_SUFFIX
+#undef RT_TO_AFFINE
+#define RT_SUFFIX RT_CAT(RT_BUILD, _xm)
 #define RT_TO_AFFINE(name, ...) do { } while (0)
+#elif RT_AFFINE
+#define RT_SUFFIX RT_CAT(RT_BUILD, _x)
+#define RT_XM(name) moving::RT_CAT(RT_CAT(name, RT_BUILD), _xm)
+#define RT_TO_AFFINE(name, ...) do { if (sc.flags & SCENE_MOVING) return RT_XM(name)(__VA_ARGS__); } while (0)
+namespace moving {
+hipError_t RT_CAT(RT_CAT(launch_composite_, RT_BUILD), _xm)(int which, const DeviceScene &sc, const RenderArgs &a, hipStream_t stream, KernelInfo *info);
+hipError_t RT_CAT(RT_CAT(launch_adaptive_composite_, RT_BUILD), _xm)(int which, const DeviceScene &sc, const RenderArgs &a, hipStream_t stream, KernelInfo *info);
+hipError_t RT_CAT(RT_CAT(launch_features_, RT_BUILD), _xm)(const DeviceScene &sc, const FeatureArgs &a, hipStream_t stream);
+hipError_t RT_CAT(RT_CAT(launch_query_, RT_BUILD), _xm)(const DeviceScene &sc, const QueryArgs &a, hipStream_t stream, QueryKernelInfo *info);
+hipError_t RT_CAT(RT_CAT(launch_radiance_, RT_BUILD), _xm)(const DeviceScene &sc, const RadianceArgs &a, hipStream_t stream, QueryKernelInfo *info);
+hipError_t RT_CAT(RT_CAT(launch_step_, RT_BUILD), _xm)(const DeviceScene &sc, const StepArgs &a, hipStream_t stream, QueryKernelInfo *info);
+hipError_t RT_CAT(RT_CAT(launch_advance_, RT_BUILD), _xm)(const DeviceScene &sc, const AdvanceArgs &a, hipStream_t stream, QueryKernelInfo *info);
+hipError_t RT_CAT(RT_CAT(launch_advance_direct_, RT_BUILD), _xm)(const DeviceScene &sc, const AdvanceDirectArgs &a, hipStream_t stream, QueryKernelInfo *info);
+hipError_t RT_CAT(RT_CAT(launch_advance_shadow_, RT_BUILD), _xm)(const DeviceScene &sc, const AdvanceDirectArgs &a, hipStream_t stream, QueryKernelInfo *info);
+hipError_t RT_CAT(RT_CAT(launch_radiance_direct_, RT_BUILD), _xm)(const DeviceScene &sc, const RadianceDirectArgs &d, hipStream_t stream, QueryKernelInfo *info);
+hipError_t RT_CAT(RT_CAT(launch_film_direct_, RT_BUILD), _xm)(const DeviceScene &sc, const FilmDirectArgs &d, hipStream_t stream, FilmDirectInfo *info);
+}  // namespace moving
 #else
 #define RT_SUFFIX RT_BUILD
 #define RT_X(name) RT_CAT(RT_CAT(name, RT_BUILD), _x)
@@ -6263,4 +6363,14 @@ hipError_t RT_CAT(kernel_info_, RT_SUFFIX)(int kernel, const DeviceScene &sc, co
 }
 #endif
 
+#if RT_MOVING
+}  // namespace moving
+#endif
 } // namespace rtow
+
+// An affine unit holds everything twice: once for the scenes whose chains hold static steps alone, once more with the moving step.
+#if RT_AFFINE && !RT_MOVING
+#undef RT_MOVING
+#define RT_MOVING 1
+#include "render.hip"
+#endif

@@ -63,7 +63,7 @@ static inline D3 affine_normal(const HostAffine &a, D3 n)  // Li^T n, renormalis
     const D3 m = mk(((i[0] * n.x) + (i[3] * n.y)) + (i[6] * n.z), ((i[1] * n.x) + (i[4] * n.y)) + (i[7] * n.z), ((i[2] * n.x) + (i[5] * n.y)) + (i[8] * n.z));
     return scale(1.0 / std::sqrt(m.x * m.x + m.y * m.y + m.z * m.z), m);
 }
-static inline bool is_instance(HKind k) { return k == HKind::Translate || k == HKind::RotateY || k == HKind::Transform; }
+static inline bool is_instance(HKind k) { return k == HKind::Translate || k == HKind::RotateY || k == HKind::Transform || k == HKind::MovingTransform; }
 
 // ------------------------------------------------------------------------------------------------
 // boxes (R/AABB.h, R/Interval.h)
@@ -484,16 +484,27 @@ static bool has_coincident_primitives(const SceneImpl &s, const std::vector<uint
             }
         }
     };
+    // A face or sphere under a MovingTransform (rt_moving_transform) stands at no one position, and the guard knows no time: such a
+    // leaf counts as coincident with every other compared leaf whose box meets its own, which is the swept box of the step with the
+    // static steps above it applied.  Too many ties only keep the reference's order.
+    std::vector<uint32_t> moving_leaves, compared_leaves;
     for (uint32_t leaf = 0; leaf < handles.size(); leaf++) {
         const HostHittable *h = &s.hittables[handles[leaf] - 1];
         std::vector<const HostHittable *> chain;  // outermost first
+        bool moves = false;
         while (is_instance(h->kind)) {
             chain.push_back(h);
+            moves |= h->kind == HKind::MovingTransform;
             h = &s.hittables[h->child - 1];
         }
         // a medium's hit is drawn, not found: it ties with nothing.  General nesting gets no library tree in the first place.
         const uint32_t inner = (uint32_t)(h - s.hittables.data()) + 1;
         if (h->kind == HKind::Medium || !only_primitives(s, inner)) continue;
+        compared_leaves.push_back(leaf);
+        if (moves) {
+            moving_leaves.push_back(leaf);
+            continue;
+        }
         TieBox b;
         int axis_of[6], end_of[6], box = -1;
         if (chain.empty() && closed_box(s, *h, b, axis_of, end_of)) {
@@ -501,6 +512,17 @@ static bool has_coincident_primitives(const SceneImpl &s, const std::vector<uint
             boxes.push_back(b);
         }
         add_prims(add_prims, inner, chain, leaf, box, axis_of, end_of);
+    }
+
+    for (uint32_t m : moving_leaves) {
+        const Box &mb = s.hittables[handles[m] - 1].box;
+        for (uint32_t o : compared_leaves) {
+            if (o == m) continue;
+            const Box &ob = s.hittables[handles[o] - 1].box;
+            bool meet = true;
+            for (int k = 0; k < 3; k++) meet &= mb.lo[k] <= ob.hi[k] && ob.lo[k] <= mb.hi[k];
+            if (meet) return true;
+        }
     }
 
     std::sort(spheres.begin(), spheres.end(), less);
@@ -726,13 +748,21 @@ struct Flattener {
         if (h->kind == HKind::Medium) return false;
         return only_primitives(s, (uint32_t)(h - s.hittables.data()) + 1);
     }
-    // One instance as rows of xforms[] (flat_scene.h Xform; a Transform is kAffineRows of them and sets SCENE_AFFINE).
+    // One instance as rows of xforms[] (flat_scene.h Xform; a Transform is kAffineRows of them, a MovingTransform kMovingRows and sets SCENE_MOVING besides SCENE_AFFINE).
     void push_step(std::vector<Xform> &to, const HostHittable &h)
     {
         if (h.kind == HKind::Translate) {
             to.push_back({h.offset.x, h.offset.y, h.offset.z, XF_TRANSLATE, 0});
         } else if (h.kind == HKind::RotateY) {
             to.push_back({h.sin_t, h.cos_t, 0.0, XF_ROTATE_Y, 0});
+        } else if (h.kind == HKind::MovingTransform) {  // flat_scene.h kMovingRows has the rows
+            const HostMovingAffine &a = s.moving_transforms[h.xf - 1];
+            to.push_back({a.t0[0], a.t0[1], a.t0[2], XF_MOVING, 0});
+            for (uint32_t r = 0; r < 3; r++) to.push_back({a.L0[3 * r], a.L0[3 * r + 1], a.L0[3 * r + 2], XF_AFFINE_ROW, 1 + r});
+            to.push_back({a.dt[0], a.dt[1], a.dt[2], XF_AFFINE_ROW, 4});
+            for (uint32_t r = 0; r < 3; r++) to.push_back({a.dL[3 * r], a.dL[3 * r + 1], a.dL[3 * r + 2], XF_AFFINE_ROW, 5 + r});
+            to.push_back({a.time0, a.dtime, 0.0, XF_AFFINE_ROW, kMovingRows - 1});
+            f.flags |= SCENE_AFFINE | SCENE_MOVING;
         } else {
             const HostAffine &a = s.transforms[h.xf - 1];
             to.push_back({a.t[0], a.t[1], a.t[2], XF_AFFINE, 0});
@@ -1516,6 +1546,7 @@ struct LightCollector {
         case HKind::Translate:
         case HKind::RotateY:
         case HKind::Transform:
+        case HKind::MovingTransform:  // (holds no light: rt_moving_transform refused an emissive child, so forward() never meets one)
             chain.push_back(&h);
             walk(h.child, leaf, depth + 1);
             chain.pop_back();
@@ -2455,8 +2486,9 @@ rt_handle rt_rotate_y(rt_scene *s, rt_handle object, double angle_degrees)
     h.box = box_from_corners(mk(mn[0], mn[1], mn[2]), mk(mx[0], mx[1], mx[2]));
     return push_h(S(s), std::move(h));
 }
-// An emissive Sphere / MovingSphere below `handle`, found as the light collector finds lights: never through a ConstantMedium.
-static bool holds_sphere_lamp(const SceneImpl &s, uint32_t handle, int depth)
+// An emissive primitive below `handle`, found as the light collector finds lights: never through a ConstantMedium.  spheres_only: a
+// Sphere or MovingSphere (what rt_transform cannot hold); otherwise a quad or triangle too (what rt_moving_transform cannot hold).
+static bool holds_lamp(const SceneImpl &s, uint32_t handle, bool spheres_only, int depth)
 {
     if (depth > 64) return false;  // (deeper than the light collector goes: the commit refuses such a graph)
     const HostHittable &h = s.hittables[handle - 1];
@@ -2464,16 +2496,60 @@ static bool holds_sphere_lamp(const SceneImpl &s, uint32_t handle, int depth)
     case HKind::Medium: return false;
     case HKind::Translate:
     case HKind::RotateY:
-    case HKind::Transform: return holds_sphere_lamp(s, h.child, depth + 1);
+    case HKind::Transform:
+    case HKind::MovingTransform: return holds_lamp(s, h.child, spheres_only, depth + 1);
     case HKind::List:
     case HKind::Bvh:
         for (uint32_t c : h.items)
-            if (holds_sphere_lamp(s, c, depth + 1)) return true;
+            if (holds_lamp(s, c, spheres_only, depth + 1)) return true;
         return false;
+    case HKind::Quad:
+    case HKind::Triangle: return !spheres_only && s.materials[h.material - 1].kind == MAT_DIFFUSE_LIGHT;
     case HKind::Sphere:
     case HKind::MovingSphere: return s.materials[h.material - 1].kind == MAT_DIFFUSE_LIGHT;
     default: return false;
     }
+}
+// The nine cofactors and the determinant of a row-major 3x3, in the order include/rtow.h rt_transform states (this file: contraction off).
+static double cofactors(const double *L, double cf[9])
+{
+    const double c[9] = {(L[4] * L[8]) - (L[5] * L[7]), (L[5] * L[6]) - (L[3] * L[8]), (L[3] * L[7]) - (L[4] * L[6]),
+                         (L[2] * L[7]) - (L[1] * L[8]), (L[0] * L[8]) - (L[2] * L[6]), (L[1] * L[6]) - (L[0] * L[7]),
+                         (L[1] * L[5]) - (L[2] * L[4]), (L[2] * L[3]) - (L[0] * L[5]), (L[0] * L[4]) - (L[1] * L[3])};
+    std::memcpy(cf, c, sizeof c);
+    return ((L[0] * c[0]) + (L[1] * c[1])) + (L[2] * c[2]);
+}
+// L, t and Li of the row-major 3x4 m as rt_transform stores them; why such a matrix is refused, or nullptr.
+static const char *affine_from_matrix(const double m[12], HostAffine &a)
+{
+    for (int r = 0; r < 3; r++) {
+        for (int k = 0; k < 3; k++) a.L[3 * r + k] = m[4 * r + k];
+        a.t[r] = m[4 * r + 3];
+    }
+    for (int k = 0; k < 12; k++)
+        if (!std::isfinite(m[k])) return "a matrix entry is not finite";
+    double cf[9];
+    const double det = cofactors(a.L, cf);
+    if (!std::isfinite(det) || det == 0.0) return "the determinant is zero or not finite";
+    for (int r = 0; r < 3; r++)
+        for (int k = 0; k < 3; k++) {
+            a.Li[3 * r + k] = cf[3 * k + r] / det;
+            if (!std::isfinite(a.Li[3 * r + k])) return "an entry of the inverse is not finite";
+        }
+    return nullptr;
+}
+// fmin / fmax per axis over the eight corners of `cb` taken forward by (L p) + t, as rt_rotate_y takes them: x outermost, lo before hi
+static void corners_forward(const Box &cb, const HostAffine &a, double mn[3], double mx[3])
+{
+    for (int i = 0; i < 2; i++)
+        for (int j = 0; j < 2; j++)
+            for (int k = 0; k < 2; k++) {
+                const D3 p = affine_point(a, mk(i ? cb.hi[0] : cb.lo[0], j ? cb.hi[1] : cb.lo[1], k ? cb.hi[2] : cb.lo[2]));
+                for (int c2 = 0; c2 < 3; c2++) {
+                    mn[c2] = std::fmin(mn[c2], comp(p, c2));
+                    mx[c2] = std::fmax(mx[c2], comp(p, c2));
+                }
+            }
 }
 rt_handle rt_transform(rt_scene *s, rt_handle object, const double m[12])
 {
@@ -2483,55 +2559,140 @@ rt_handle rt_transform(rt_scene *s, rt_handle object, const double m[12])
         return 0;
     }
     HostAffine a{};
-    for (int r = 0; r < 3; r++) {
-        for (int k = 0; k < 3; k++) a.L[3 * r + k] = m[4 * r + k];
-        a.t[r] = m[4 * r + 3];
-    }
-    for (int k = 0; k < 12; k++)
-        if (!std::isfinite(m[k])) {
-            set_error("rt_transform: a matrix entry is not finite");
-            return 0;
-        }
-    // the inverse from cofactors over the determinant, in the order include/rtow.h states (this file: contraction off)
-    const double *L = a.L;
-    const double cf[9] = {(L[4] * L[8]) - (L[5] * L[7]), (L[5] * L[6]) - (L[3] * L[8]), (L[3] * L[7]) - (L[4] * L[6]),
-                          (L[2] * L[7]) - (L[1] * L[8]), (L[0] * L[8]) - (L[2] * L[6]), (L[1] * L[6]) - (L[0] * L[7]),
-                          (L[1] * L[5]) - (L[2] * L[4]), (L[2] * L[3]) - (L[0] * L[5]), (L[0] * L[4]) - (L[1] * L[3])};
-    const double det = ((L[0] * cf[0]) + (L[1] * cf[1])) + (L[2] * cf[2]);
-    if (!std::isfinite(det) || det == 0.0) {
-        set_error("rt_transform: the determinant is zero or not finite");
+    if (const char *why = affine_from_matrix(m, a)) {
+        set_error(std::string("rt_transform: ") + why);
         return 0;
     }
-    for (int r = 0; r < 3; r++)
-        for (int k = 0; k < 3; k++) {
-            a.Li[3 * r + k] = cf[3 * k + r] / det;
-            if (!std::isfinite(a.Li[3 * r + k])) {
-                set_error("rt_transform: an entry of the inverse is not finite");
-                return 0;
-            }
-        }
-    if (holds_sphere_lamp(*S(s), object, 0)) {
+    if (holds_lamp(*S(s), object, true, 0)) {
         set_error("rt_transform: the child holds an emissive Sphere or MovingSphere (an ellipsoid lamp; the light table cannot hold it)");
         return 0;
     }
     HostHittable h{};
     h.kind = HKind::Transform;
     h.child = object;
-    const Box cb = c->box;
     double mn[3] = {DBL_MAX, DBL_MAX, DBL_MAX}, mx[3] = {-DBL_MAX, -DBL_MAX, -DBL_MAX};
-    for (int i = 0; i < 2; i++)  // the eight corners forward, as rt_rotate_y
-        for (int j = 0; j < 2; j++)
-            for (int k = 0; k < 2; k++) {
-                const D3 p = affine_point(a, mk(i ? cb.hi[0] : cb.lo[0], j ? cb.hi[1] : cb.lo[1], k ? cb.hi[2] : cb.lo[2]));
-                for (int c2 = 0; c2 < 3; c2++) {
-                    mn[c2] = std::fmin(mn[c2], comp(p, c2));
-                    mx[c2] = std::fmax(mx[c2], comp(p, c2));
-                }
-            }
+    corners_forward(c->box, a, mn, mx);
     h.box = box_from_corners(mk(mn[0], mn[1], mn[2]), mk(mx[0], mx[1], mx[2]));
     S(s)->transforms.push_back(a);
     h.xf = (uint32_t)S(s)->transforms.size();
     return push_h(S(s), std::move(h));
+}
+// Is det(L(s)), L(s) = L0 + s dL, of one strict sign over [0, 1]?  It is a cubic in s; with rows a_i of L0 and b_i of L0 + dL its Bernstein
+// coefficients are det(a0,a1,a2), a third of the three determinants with one b row, a third of the three with two, det(b0,b1,b2), and
+// a polynomial lies in the hull of its coefficients.  Where the four do not agree the interval is halved (de Casteljau), to depth 8.
+// A coefficient has a sign only beyond `margin`, 2^-30 of the largest of the first four: the halving rounds, and a double root (a half
+// turn about an axis: det = (1 - 2s)^2) would otherwise be passed by a midpoint that comes out as a few 1e-17 instead of zero.
+static bool det_keeps_sign(const double c[4], double margin, int depth)
+{
+    if ((c[0] > margin && c[1] > margin && c[2] > margin && c[3] > margin) || (c[0] < -margin && c[1] < -margin && c[2] < -margin && c[3] < -margin))
+        return true;
+    const bool ends_agree = (c[0] > margin && c[3] > margin) || (c[0] < -margin && c[3] < -margin);
+    if (depth >= 8 || !ends_agree) return false;  // the ends are values of det: a zero or a change of sign there is final
+    const double p01 = 0.5 * (c[0] + c[1]), p12 = 0.5 * (c[1] + c[2]), p23 = 0.5 * (c[2] + c[3]);
+    const double p012 = 0.5 * (p01 + p12), p123 = 0.5 * (p12 + p23), mid = 0.5 * (p012 + p123);
+    const double left[4] = {c[0], p01, p012, mid}, right[4] = {mid, p123, p23, c[3]};
+    return det_keeps_sign(left, margin, depth + 1) && det_keeps_sign(right, margin, depth + 1);
+}
+rt_handle rt_moving_transform(rt_scene *s, rt_handle object, const double m0[12], const double m1[12], double time0, double time1)
+{
+    HostHittable *c = get_h(S(s), object);
+    if (!c || !m0 || !m1) {
+        set_error("rt_moving_transform: invalid object handle or null matrix");
+        return 0;
+    }
+    HostAffine key0{}, key1{};
+    const char *why = affine_from_matrix(m0, key0);
+    if (!why) why = affine_from_matrix(m1, key1);
+    if (why) {
+        set_error(std::string("rt_moving_transform: ") + why);
+        return 0;
+    }
+    if (!std::isfinite(time0) || !std::isfinite(time1) || !(time1 > time0)) {
+        set_error("rt_moving_transform: time0 and time1 must be finite with time0 < time1");
+        return 0;
+    }
+    HostMovingAffine a{};
+    HostAffine end{};  // the matrices of s = 1 as the device forms them: L0 + (1.0 * dL), t0 + (1.0 * dt)
+    for (int k = 0; k < 9; k++) {
+        a.L0[k] = key0.L[k];
+        a.dL[k] = key1.L[k] - key0.L[k];
+        end.L[k] = a.L0[k] + (1.0 * a.dL[k]);
+    }
+    for (int k = 0; k < 3; k++) {
+        a.t0[k] = key0.t[k];
+        a.dt[k] = key1.t[k] - key0.t[k];
+        end.t[k] = a.t0[k] + (1.0 * a.dt[k]);
+    }
+    a.time0 = time0;
+    a.dtime = time1 - time0;
+    bool finite = std::isfinite(a.dtime);
+    for (int k = 0; k < 9; k++) finite &= std::isfinite(a.dL[k]) && std::isfinite(end.L[k]);
+    for (int k = 0; k < 3; k++) finite &= std::isfinite(a.dt[k]) && std::isfinite(end.t[k]);
+    if (!finite) {
+        set_error("rt_moving_transform: the difference of the keys is not finite");
+        return 0;
+    }
+    auto det3 = [](const double *r0, const double *r1, const double *r2) {
+        const double L[9] = {r0[0], r0[1], r0[2], r1[0], r1[1], r1[2], r2[0], r2[1], r2[2]};
+        double cf[9];
+        return cofactors(L, cf);
+    };
+    const double *a0 = a.L0, *a1 = a.L0 + 3, *a2 = a.L0 + 6, *b0 = end.L, *b1 = end.L + 3, *b2 = end.L + 6;
+    const double bern[4] = {det3(a0, a1, a2), ((det3(b0, a1, a2) + det3(a0, b1, a2)) + det3(a0, a1, b2)) / 3.0,
+                            ((det3(b0, b1, a2) + det3(b0, a1, b2)) + det3(a0, b1, b2)) / 3.0, det3(b0, b1, b2)};
+    double largest = 0.0;
+    for (double b : bern) largest = std::fmax(largest, std::fabs(b));
+    if (!std::isfinite(largest) || !det_keeps_sign(bern, 0x1p-30 * largest, 0)) {
+        set_error("rt_moving_transform: the interpolated matrix L0 + s (L1 - L0) is singular, or cannot be shown regular, for some s in "
+                  "[0, 1]; split the motion into smaller steps");
+        return 0;
+    }
+    if (holds_lamp(*S(s), object, false, 0)) {
+        set_error("rt_moving_transform: the child holds an emissive primitive (the light table is static; a moving lamp is out of scope)");
+        return 0;
+    }
+    HostHittable h{};
+    h.kind = HKind::MovingTransform;
+    h.child = object;
+    double mn[3] = {DBL_MAX, DBL_MAX, DBL_MAX}, mx[3] = {-DBL_MAX, -DBL_MAX, -DBL_MAX};
+    corners_forward(c->box, key0, mn, mx);
+    corners_forward(c->box, end, mn, mx);
+    // a point at an intermediate s is a convex combination of its two key positions only up to the roundings of (L p) + t
+    double reach = 0.0;
+    for (int k = 0; k < 3; k++) reach = std::fmax(reach, std::fmax(std::fabs(mn[k]), std::fabs(mx[k])));
+    const double widen = 16.0 * DBL_EPSILON * reach;
+    for (int k = 0; k < 3; k++) {
+        mn[k] -= widen;
+        mx[k] += widen;
+    }
+    h.box = box_from_corners(mk(mn[0], mn[1], mn[2]), mk(mx[0], mx[1], mx[2]));
+    S(s)->moving_transforms.push_back(a);
+    h.xf = (uint32_t)S(s)->moving_transforms.size();
+    return push_h(S(s), std::move(h));
+}
+rt_handle rt_moving_translate(rt_scene *s, rt_handle object, const double offset0[3], const double offset1[3], double time0, double time1)
+{
+    if (!offset0 || !offset1) {
+        set_error("rt_moving_translate: null offset");
+        return 0;
+    }
+    const double m0[12] = {1.0, 0.0, 0.0, offset0[0], 0.0, 1.0, 0.0, offset0[1], 0.0, 0.0, 1.0, offset0[2]};
+    const double m1[12] = {1.0, 0.0, 0.0, offset1[0], 0.0, 1.0, 0.0, offset1[1], 0.0, 0.0, 1.0, offset1[2]};
+    return rt_moving_transform(s, object, m0, m1, time0, time1);
+}
+int rt_moving_transform_get(rt_scene *s, rt_handle h, double out26[26])
+{
+    HostHittable *x = get_h(S(s), h);
+    if (!x || !out26 || x->kind != HKind::MovingTransform)
+        return fail(RT_ERR_INVALID, "rt_moving_transform_get: not a MovingTransform handle, or null output");
+    const HostMovingAffine &a = S(s)->moving_transforms[x->xf - 1];
+    std::memcpy(out26, a.L0, 9 * sizeof(double));
+    std::memcpy(out26 + 9, a.t0, 3 * sizeof(double));
+    std::memcpy(out26 + 12, a.dL, 9 * sizeof(double));
+    std::memcpy(out26 + 21, a.dt, 3 * sizeof(double));
+    out26[24] = a.time0;
+    out26[25] = a.dtime;
+    return RT_OK;
 }
 rt_handle rt_rotate_x(rt_scene *s, rt_handle object, double angle_degrees)
 {

@@ -20,10 +20,15 @@ struct Box {  // R/AABB.h:16-22: three closed intervals
 
 enum class HKind : uint8_t { Sphere, MovingSphere, Quad, Translate, RotateY, List, Bvh, Medium,
                              Triangle,    // the quad's fields and plane constants; corners Q, Q + u, Q + v
-                             Transform }; // a general affine instance (rt_transform): HostHittable::xf
+                             Transform,   // a general affine instance (rt_transform): HostHittable::xf
+                             MovingTransform };  // an affine instance keyed at two times (rt_moving_transform): HostHittable::xf
 // The numbers of a Transform exactly as rt_transform stored them and as they are uploaded: x_world = L x_obj + t, Li = inverse of L.
 struct HostAffine {
     double L[9], t[3], Li[9];  // L, Li row-major
+};
+// The numbers of a MovingTransform exactly as rt_moving_transform stored them and as they are uploaded (rt_moving_transform_get).
+struct HostMovingAffine {
+    double L0[9], t0[3], dL[9], dt[3], time0, dtime;  // L0, dL row-major
 };
 
 struct HostHittable {
@@ -38,7 +43,7 @@ struct HostHittable {
     uint32_t child = 0;                // instance / medium: wrapped hittable handle
     D3 offset{};
     double sin_t = 0, cos_t = 0;
-    uint32_t xf = 0;                   // Transform: 1 + its row of SceneImpl::transforms
+    uint32_t xf = 0;                   // Transform: 1 + its row of SceneImpl::transforms; MovingTransform: of SceneImpl::moving_transforms
     std::vector<uint32_t> items;       // list children / bvh leaves (in sorted order, after build)
     double neg_inv_density = 0;
     // bvh topology (built at construction): nodes in preorder
@@ -136,6 +141,7 @@ struct SceneImpl {
     std::vector<HostTexture> textures;
     std::vector<TriAttrRow> tri_attr;     // HostHittable::attr
     std::vector<HostAffine> transforms;   // HostHittable::xf
+    std::vector<HostMovingAffine> moving_transforms;  // HostHittable::xf of a MovingTransform
     std::vector<ImageRec> images;
     std::vector<unsigned char> image_bytes;
     std::vector<PerlinRec> perlin;
