@@ -305,6 +305,11 @@ RTOW_API int rt_scene_set_camera(rt_scene *s, const double lookfrom[3], const do
 RTOW_API int rt_scene_build_builtin(rt_scene *s, int scene_id, int world_kind, int image_width,
                                     int image_height, uint64_t seed, const unsigned char *earth_rgb,
                                     int earth_w, int earth_h);
+/* The environment's demonstration scene, `rtow --scene 15` (not an id of rt_scene_build_builtin, whose ids stay 0..14): the static
+ * random spheres of scene 11 on their ground under a sky computed here -- a 256 x 128 linear float image with a vertical gradient
+ * and a small, very bright sun disc (rt_scene_set_environment) -- with a black camera background, so that a miss that does not
+ * reach the environment shows.  Builds, sets world, camera and environment, and commits, like rt_scene_build_builtin. */
+RTOW_API int rt_scene_build_sky_demo(rt_scene *s, int world_kind, int image_width, int image_height, uint64_t seed);
 
 /* Flatten the object graph into the SoA tables the kernel reads (host only; no GPU needed). */
 RTOW_API int rt_scene_commit(rt_scene *s);
@@ -323,6 +328,10 @@ typedef struct rt_scene_info {
                                      carry corner normals or texture coordinates (rt_triangle_attr) */
 } rt_scene_info;
 RTOW_API int rt_scene_get_info(rt_scene *s, rt_scene_info *out);
+/* The committed scene's flags word as the kernels receive it (csrc/flat_scene.h SCENE_*), 0 before commit.  Introspection for
+ * tests: a scene without an environment has the word it always had, one with an environment additionally this bit. */
+#define RT_SCENE_FLAG_ENVIRONMENT 1024u
+RTOW_API uint32_t rt_scene_flags(rt_scene *s);
 
 /* Introspection for tests (valid after commit): world leaves in final order. kind: 0 sphere, 1 moving
  * sphere, 2 quad, 3 composite object, 4 triangle; box = {xmin,xmax,ymin,ymax,zmin,zmax}. Returns the leaf count. */
@@ -389,6 +398,59 @@ typedef struct rt_light_row {
     double pad1;
 } rt_light_row;                           /* 128 bytes, exactly as uploaded */
 RTOW_API int rt_scene_dump_lights(rt_scene *s, int max_lights, int *kind_out, int *leaf_out, rt_light_row *rows_out, double *cdf_out);
+
+/* ---- the environment: a textured sky at every miss ----
+ * A scene without one gives a ray that leaves the world the camera's `background`, whatever its direction.  With one, such a ray
+ * gets the environment's value along its direction, in every frame and every call on caller-supplied rays (renders, adaptive and
+ * direct films, radiance queries, path steps, advances, and the albedo of a miss in the feature pass and in rt_scene_intersect);
+ * the camera's background is then not read.  A construction call: it takes effect with the next rt_scene_commit (the scene counts
+ * as not committed behind it, as behind rt_scene_set_world).  A scene without an environment commits to the flags, tables and
+ * launch plans it always had; one with an environment is rendered by the instantiations that carry the texture code (the
+ * general, deep, segmented and nested kernels: rt_plan_launch says which).
+ *
+ * The value for a ray of direction d (not necessarily unit), one IEEE fp64 operation at a time in the strict build:
+ *   n = (1 / sqrt((d.x * d.x + d.y * d.y) + d.z * d.z)) * d
+ *   e = R n, each row (r0 * n.x + r1 * n.y) + r2 * n.z                        (rotation: world -> environment)
+ *   theta = acos(-e.y), phi = atan2(-e.z, e.x) + pi, u = phi / (2 pi), v = theta / pi          (the reference's GetSphereUV: the
+ *       earth map used as a sky has its north pole at +y, exactly as it lies on the reference's globe)
+ *   texture != 0:  value = intensity * texture_value(texture, u, v, e)   -- a checker or marble sky is a function of the direction
+ *   rgb != NULL:   ImageTexture::Value's index rule (R/Texture.h:110-133): u and v clamped to [0, 1], v = 1 - v, i = int(u * width),
+ *                  j = int(v * height), each clamped to the table; value = intensity * the three floats of texel (i, j) of row j
+ *                  (top row first) widened to double
+ * The float image is copied at the call; it is a table of its own, not a texture: no material can name it.
+ *
+ * Refused with RT_ERR_INVALID: a NULL scene; both or neither of texture and rgb; a texture handle that is none of this scene's;
+ * with rgb, a width or height below 1 or a texel that is negative or not finite; an intensity that is negative or not finite; a
+ * rotation with an entry that is not finite or with |R R^T - I| above 1e-9 in some entry.  RT_ERR_STATE while a render of the
+ * scene is in flight.  env == NULL removes the environment: back to the camera's background. */
+typedef struct rt_environment {
+    rt_handle    texture;        /* a texture of this scene (solid, checker, noise, 8-bit image), or 0 */
+    const float *rgb;            /* or: a linear float image, width x height x 3, top row first, copied; NULL with `texture` */
+    int32_t      width, height;  /* of rgb */
+    double       intensity[3];   /* multiplies the value per channel */
+    double       rotation[9];    /* row-major R, world -> environment; must be orthonormal to 1e-9 */
+    int32_t      reserved[4];
+} rt_environment;
+RTOW_API int rt_scene_set_environment(rt_scene *s, const rt_environment *env);
+/* What was set: *out as given (rgb points at the scene's own copy, valid until the next rt_scene_set_environment or the scene's
+ * end); without an environment *out is all zeros and the call returns RT_OK.  *has_distribution (may be NULL): 1 where the
+ * committed scene holds the importance sampler's tables (below), else 0 -- before commit always 0. */
+RTOW_API int rt_scene_get_environment(rt_scene *s, rt_environment *out, int *has_distribution);
+/* The importance sampler's tables, built by rt_scene_commit on the host in fp64, for an environment that is an image -- the float
+ * image, or a texture that is itself an 8-bit image (W x H its own size; a checker of images is not one).  Texel (i, j), j counted
+ * from the top row, has the weight w = max over the channels c of (intensity_c * value_c) times sin(pi * (j + 0.5) / H), value_c
+ * the float widened to double or (1.0 / 255.0) * byte; pi = 3.1415926535897932385, sin the host's libm.  Row sums are taken in
+ * order, i = 0 .. W - 1, and the total over the row sums in order, j = 0 .. H - 1.  marginal[j] = fl(fl(s_0 + ... + s_j) /
+ * fl(total)), conditional[j * W + i] = fl(fl(w_0 + ... + w_i) / fl(s_j)), the last entry of each table exactly 1.0 -- the rule of
+ * rt_scene_dump_lights.  A row of sum 0 holds 1.0 throughout and is never consulted.  A total that is not a positive finite
+ * number, or an environment that is no image (solid, checker, noise), gives no tables.  Returns height (0: no tables; negative:
+ * error, e.g. before commit) and *width_out; fills the arrays given where max_entries >= width * height. */
+RTOW_API int rt_scene_dump_environment_cdf(rt_scene *s, int *width_out, int max_entries, double *marginal_out, double *conditional_out);
+/* Reads what rt_write_pfm writes: "PF", width and height, a scale whose sign gives the byte order (negative: little endian) and
+ * whose magnitude multiplies every value, then the rows bottom first.  Hands back width x height x 3 floats with the TOP row
+ * first (what rt_environment::rgb takes), to be released with rt_pfm_free. */
+RTOW_API int rt_pfm_load(const char *path, float **rgb_out, int *width, int *height);
+RTOW_API void rt_pfm_free(float *rgb);
 
 /* ---- render (RenderInit + Render, R/kernel.cu:110-154,675-691) ---- */
 typedef struct rt_render_params {
@@ -602,6 +664,8 @@ RTOW_API int rt_deinterleave(const double *gathered, int width, int height, int 
  *            its albedo; dielectric: (1, 1, 1); diffuse light: its emitted colour      texture value               background
  *   normal   the unit shading normal, faced against the ray, in world space            (0, 0, 0)                   (0, 0, 0)
  *   depth    t * |ray direction|                                                       the same                    0
+ * With an environment (rt_scene_set_environment) the albedo of a miss is the environment's value along the sample's ray, not the
+ * camera's background; normal and depth stay 0.
  * The film's saved RNG state, its pixels, sums and statistics are neither read nor written: a feature pass between two
  * progressive launches changes nothing of the frame.  The call returns when the planes are filled (it waits on params->stream,
  * NULL = the film's own).  RT_ERR_STATE while a render of the film is in flight. */
@@ -1059,6 +1123,59 @@ RTOW_API int rt_scene_light_pdf(rt_scene *s, const rt_light_params *params, cons
 /* sizeof of rt_light_params, rt_light_points, rt_light_samples, rt_light_rays, rt_light_pdf_out, rt_light_stats, rt_light_row as
  * this library was compiled, and kLightLdsRows: the rows of the light table the kernels stage on chip */
 RTOW_API void rt_light_abi_sizes(uint32_t out8[8]);
+
+/* ---- environment sampling: draw directions by the brightness of the map, and the density of doing so ----
+ * The environment (rt_scene_set_environment) is no row of the light table, and direct = "mis" does not sample it: a path that
+ * misses adds it with weight 1, as it adds the background.  These two calls are the building block for doing better: one lane a
+ * point, the light calls' structs where the fields mean the same.  points->point is required as there (a shadow ray starts at
+ * it; the sample itself does not depend on it), ->time is not read.  RT_ERR_STATE for a scene without an environment; the other
+ * refusals are the light calls', without the strategy.
+ *
+ * rt_scene_sample_environment.  Four draws from the point's stream, each (double) curand_uniform, in this order: a, b, c, d.
+ * With tables (rt_scene_dump_environment_cdf):
+ *   j = the first row with marginal[j] >= a, by bisection (lo = 0, hi = H - 1; mid = (lo + hi) / 2; table[mid] >= x ? hi = mid :
+ *       lo = mid + 1); i = the first column with conditional[j * W + i] >= b, likewise          -- light[k] = j * W + i
+ *   u = (i + c) / W, v = 1 - (j + d) / H            -- the position inside the texel: c along the row, d down from its top edge
+ *   theta = pi * v, phi = (2 pi) * u - pi, e = (sin(theta) * cos(phi), -cos(theta), -(sin(theta) * sin(phi)))
+ * Without tables the sphere uniformly: y = 1 - 2 c, s = sqrt(1 - y * y), phi = (2 pi) * d - pi, e = (s * cos(phi), y,
+ * -(s * sin(phi))); light[k] = -1.
+ *   direction = R^T e, each row (r0 * e.x + r3 * e.y) + r6 * e.z
+ * pdf and emitted are then computed FROM direction: pdf = the density below, emitted = the environment's value along it, the very
+ * lookup a miss makes -- so rt_scene_environment_pdf of the direction is the sampled pdf, and a path step along it returns the
+ * sampled emitted, bit for bit in the strict build.  A pdf that is not positive and finite (a pole; a texel of chance 0 reached
+ * through rounding) makes the sample invalid: direction (0, 0, 0), distance 0, pdf 0, emitted, scatter_pdf, contribution 0, the
+ * same four draws taken.  distance of a valid sample is +inf.  scatter_pdf and contribution = (scatter_pdf / pdf) * emitted are
+ * the light calls' own.
+ *
+ * The density of a direction (both calls): with n, e, (u, v) and the texel (i, j) exactly as the value's lookup forms them,
+ *   P(j) = marginal[j] - marginal[j - 1], P(i | j) = conditional[j * W + i] - conditional[j * W + i - 1]    (entry -1 = 0)
+ *   pdf = ((P(j) * P(i | j)) * ((double)W * (double)H)) / (((2 pi) * pi) * sqrt(1 - e.y * e.y))
+ * a density that is constant over a texel in (u, v), over the Jacobian of the map; without tables 1 / (4 pi).
+ * rt_scene_environment_pdf: pdf[k] of rays->direction[k] (0 where it is not positive and finite), light[k] = j * W + i of its
+ * texel (-1 without tables); rays->origin is required and not read.
+ *
+ * The kernel stages the first kEnvLdsRows entries of the marginal table in LDS; beyond the cap it reads the table from global
+ * memory, with the same results. */
+typedef struct rt_environment_params {
+    int64_t  count;            /* points or rays; 0 is allowed (no launch), > 2^30 is RT_ERR_INVALID */
+    uint64_t seed;             /* point k: curand_init(seed, k + first_sequence, 0), unless points->rng_state is given */
+    uint64_t first_sequence;
+    int32_t  variant;          /* 0 strict, 1 fast */
+    int32_t  device;
+    void    *stream;           /* NULL = the default stream */
+    int32_t  reserved[4];
+} rt_environment_params;
+RTOW_API int rt_scene_sample_environment_device(rt_scene *s, const rt_environment_params *params, const rt_light_points *points,
+                                                const rt_light_samples *out, rt_light_stats *stats);
+RTOW_API int rt_scene_sample_environment(rt_scene *s, const rt_environment_params *params, const rt_light_points *points,
+                                         const rt_light_samples *out, rt_light_stats *stats);
+RTOW_API int rt_scene_environment_pdf_device(rt_scene *s, const rt_environment_params *params, const rt_light_rays *rays,
+                                             const rt_light_pdf_out *out, rt_light_stats *stats);
+RTOW_API int rt_scene_environment_pdf(rt_scene *s, const rt_environment_params *params, const rt_light_rays *rays,
+                                      const rt_light_pdf_out *out, rt_light_stats *stats);
+/* sizeof of rt_environment and rt_environment_params as this library was compiled, kEnvLdsRows (the entries of the marginal
+ * table the sample kernel stages on chip), and 0 */
+RTOW_API void rt_environment_abi_sizes(uint32_t out4[4]);
 
 /* ---- path advances with light samples: next-event estimation and its MIS weights inside the advance ----
  * rt_scene_path_advance with the light sample, the mixture density, the shadow ray and the balance-heuristic weights of a

@@ -189,6 +189,18 @@ public:
         const double u[3] = {vup.x, vup.y, vup.z}, bg[3] = {background.x, background.y, background.z};
         check(rt_scene_set_camera(s_, f, a, u, vfov, aspect, aperture, focusDist, time0, time1, bg));
     }
+    // What a ray that leaves the world sees in place of the camera's background (rtow.h "the environment"): a texture of this
+    // scene, or a linear float image of width x height x 3 values, top row first (copied).  rotation: row-major 3 x 3, world ->
+    // environment, nullptr = identity.  Takes effect with the next Commit.
+    void Environment(Texture texture, const Color &intensity = Color(1.0, 1.0, 1.0), const double *rotation = nullptr)
+    {
+        set_environment(texture.h, nullptr, 0, 0, intensity, rotation);
+    }
+    void Environment(const float *rgb, int width, int height, const Color &intensity = Color(1.0, 1.0, 1.0), const double *rotation = nullptr)
+    {
+        set_environment(0, rgb, width, height, intensity, rotation);
+    }
+    void NoEnvironment() { check(rt_scene_set_environment(s_, nullptr)); }
     void Commit() { check(rt_scene_commit(s_)); }
 
     // Ray queries on host arrays (rtow.h "ray queries"): origins and directions hold 3 doubles per ray; an output vector is
@@ -276,6 +288,19 @@ private:
     void check(int status)
     {
         if (status != RT_OK) throw Error(rt_last_error());
+    }
+    void set_environment(rt_handle texture, const float *rgb, int width, int height, const Color &intensity, const double *rotation)
+    {
+        rt_environment env{};
+        env.texture = texture;
+        env.rgb = rgb;
+        env.width = width;
+        env.height = height;
+        env.intensity[0] = intensity.x;
+        env.intensity[1] = intensity.y;
+        env.intensity[2] = intensity.z;
+        for (int k = 0; k < 9; k++) env.rotation[k] = rotation ? rotation[k] : (k % 4 == 0 ? 1.0 : 0.0);
+        check(rt_scene_set_environment(s_, &env));
     }
     rt_scene *s_;
     bool own_ = true;

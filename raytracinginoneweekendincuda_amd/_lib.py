@@ -212,6 +212,18 @@ class LightStats(C.Structure):
                 ("scratch_bytes", C.c_uint32)]
 
 
+class Environment(C.Structure):
+    """rt_environment: what a miss sees (include/rtow.h rt_scene_set_environment)."""
+    _fields_ = [("texture", C.c_uint32), ("rgb", C.c_void_p), ("width", C.c_int32), ("height", C.c_int32), ("intensity", C.c_double * 3),
+                ("rotation", C.c_double * 9), ("reserved", C.c_int32 * 4)]
+
+
+class EnvironmentParams(C.Structure):
+    """rt_environment_params: rt_light_params without time and strategy."""
+    _fields_ = [("count", C.c_int64), ("seed", C.c_uint64), ("first_sequence", C.c_uint64), ("variant", C.c_int32), ("device", C.c_int32),
+                ("stream", C.c_void_p), ("reserved", C.c_int32 * 4)]
+
+
 class LightRow(C.Structure):
     """rt_light_row: one row of the light table, in world space (include/rtow.h rt_scene_dump_lights)."""
     _fields_ = [("a", C.c_double * 3), ("b", C.c_double * 3), ("c", C.c_double * 3), ("n", C.c_double * 3), ("s", C.c_double),
@@ -316,6 +328,7 @@ SIGNATURES = {
     "rt_scene_set_world": (I, [P, H]),
     "rt_scene_set_camera": (I, [P, D3, D3, D3, D, D, D, D, D, D, D3]),
     "rt_scene_build_builtin": (I, [P, I, I, I, I, C.c_uint64, P, I, I]),
+    "rt_scene_build_sky_demo": (I, [P, I, I, I, C.c_uint64]),
     "rt_scene_commit": (I, [P]),
     "rt_scene_get_info": (I, [P, C.POINTER(SceneInfo)]),
     "rt_scene_dump_leaves": (I, [P, I, C.POINTER(C.c_int), D3]),
@@ -370,6 +383,17 @@ SIGNATURES = {
     "rt_scene_light_pdf_device": (I, [P, C.POINTER(LightParams), C.POINTER(LightRays), C.POINTER(LightPdfOut), C.POINTER(LightStats)]),
     "rt_scene_light_pdf": (I, [P, C.POINTER(LightParams), C.POINTER(LightRays), C.POINTER(LightPdfOut), C.POINTER(LightStats)]),
     "rt_light_abi_sizes": (None, [C.POINTER(C.c_uint32)]),
+    "rt_scene_flags": (C.c_uint32, [P]),
+    "rt_scene_set_environment": (I, [P, C.POINTER(Environment)]),
+    "rt_scene_get_environment": (I, [P, C.POINTER(Environment), C.POINTER(I)]),
+    "rt_scene_dump_environment_cdf": (I, [P, C.POINTER(I), I, D3, D3]),
+    "rt_pfm_load": (I, [C.c_char_p, C.POINTER(P), C.POINTER(I), C.POINTER(I)]),
+    "rt_pfm_free": (None, [P]),
+    "rt_scene_sample_environment_device": (I, [P, C.POINTER(EnvironmentParams), C.POINTER(LightPoints), C.POINTER(LightSamples), C.POINTER(LightStats)]),
+    "rt_scene_sample_environment": (I, [P, C.POINTER(EnvironmentParams), C.POINTER(LightPoints), C.POINTER(LightSamples), C.POINTER(LightStats)]),
+    "rt_scene_environment_pdf_device": (I, [P, C.POINTER(EnvironmentParams), C.POINTER(LightRays), C.POINTER(LightPdfOut), C.POINTER(LightStats)]),
+    "rt_scene_environment_pdf": (I, [P, C.POINTER(EnvironmentParams), C.POINTER(LightRays), C.POINTER(LightPdfOut), C.POINTER(LightStats)]),
+    "rt_environment_abi_sizes": (None, [C.POINTER(C.c_uint32)]),
     "rt_scene_path_advance_direct_device": (I, [P, C.POINTER(PathAdvanceDirectParams), C.POINTER(PathAdvanceDirectRays), C.POINTER(PathAdvanceDirectOut), C.POINTER(PathAdvanceDirectStats)]),
     "rt_scene_path_advance_direct": (I, [P, C.POINTER(PathAdvanceDirectParams), C.POINTER(PathAdvanceDirectRays), C.POINTER(PathAdvanceDirectOut), C.POINTER(PathAdvanceDirectStats)]),
     "rt_path_advance_direct_workspace_bytes": (C.c_uint64, [C.c_int64]),
@@ -425,8 +449,20 @@ def load():
     ours = [C.sizeof(x) for x in (LightParams, LightPoints, LightSamples, LightRays, LightPdfOut, LightStats, LightRow)]
     if list(sizes)[:7] != ours:
         raise ImportError(f"{LIB_PATH}: rt_light_* structures are {list(sizes)[:7]} bytes in the library, {ours} in the binding")
+    sizes = (C.c_uint32 * 4)()
+    lib.rt_environment_abi_sizes(sizes)
+    ours = [C.sizeof(Environment), C.sizeof(EnvironmentParams)]
+    if list(sizes)[:2] != ours:
+        raise ImportError(f"{LIB_PATH}: rt_environment* structures are {list(sizes)[:2]} bytes in the library, {ours} in the binding")
     _lib = lib
     return lib
+
+
+def env_lds_rows():
+    """kEnvLdsRows: the entries of the environment's marginal table the sample kernel stages on chip (tests cover both sides of it)."""
+    sizes = (C.c_uint32 * 4)()
+    load().rt_environment_abi_sizes(sizes)
+    return int(sizes[2])
 
 
 def light_lds_rows():

@@ -46,6 +46,7 @@ FLAG_NO_PIXEL_CLASSES = 64  # sphere-list worlds: one launch for all pixels (no 
 # rt_scene_set_options (read by the next commit)
 SCENE_PLAIN_QUADS = 1           # every quad takes the general test; boxes stay lists of six quads
 SCENE_REFERENCE_TREE_ONLY = 2   # no library tree for primitive worlds
+SCENE_FLAG_ENVIRONMENT = 1024   # Scene.flags(): the committed scene has an environment (rtow.h RT_SCENE_FLAG_ENVIRONMENT)
 
 
 # Film.denoise / denoise_frame defaults (DESIGN.md section 5 has the frames they were chosen on)
@@ -316,6 +317,62 @@ class Scene:
                background=(0.70, 0.80, 1.00)):
         _check(lib().rt_scene_set_camera(self._p, _v3(lookfrom), _v3(lookat), _v3(vup), vfov, aspect, aperture,
                                          focus_dist, time0, time1, _v3(background)))
+
+    def Environment(self, texture=None, image=None, intensity=1.0, rotation=None):
+        """What a ray that leaves the world sees, in place of the camera's ``background`` (rt_scene_set_environment; rtow.h states
+        the lookup operation by operation): a texture handle of this scene -- solid, checker, noise or 8-bit image, looked up at the
+        reference's sphere (u, v) of the direction -- or ``image``, a linear float32 H x W x 3 array, top row first (``load_pfm``).
+        ``intensity``: one factor or three, per channel.  ``rotation``: 3x3, world -> environment, orthonormal.  Both None: the scene
+        goes back to the background.  Takes effect with the next ``Commit``."""
+        if texture is None and image is None:
+            _check(lib().rt_scene_set_environment(self._p, None))
+            return
+        env = _lib.Environment()
+        env.texture = 0 if texture is None else int(texture)
+        a = None
+        if image is not None:
+            a = np.ascontiguousarray(image, dtype=np.float32)
+            if a.ndim != 3 or a.shape[2] != 3:
+                raise RtowError("Environment: image must be H x W x 3")
+            env.rgb, env.width, env.height = a.ctypes.data, a.shape[1], a.shape[0]
+        k = (float(intensity),) * 3 if np.ndim(intensity) == 0 else tuple(map(float, intensity))
+        r = np.eye(3) if rotation is None else np.array(rotation, dtype=np.float64)
+        if len(k) != 3 or r.shape != (3, 3):
+            raise RtowError("Environment: intensity is one factor or three, rotation 3 x 3")
+        env.intensity = (C.c_double * 3)(*k)
+        env.rotation = (C.c_double * 9)(*r.reshape(9))
+        _check(lib().rt_scene_set_environment(self._p, C.byref(env)))  # (the image is copied)
+
+    def environment(self):
+        """The environment as it was set (rt_scene_get_environment): None, or a dict with "texture" (a handle, or None), "image"
+        (float32 H x W x 3, or None), "intensity" (3,), "rotation" (3, 3) and "has_distribution": does the committed scene hold the
+        importance sampler's tables (``environment_cdf``)."""
+        env, has = _lib.Environment(), C.c_int()
+        _check(lib().rt_scene_get_environment(self._p, C.byref(env), C.byref(has)))
+        if not env.texture and not env.rgb:
+            return None
+        image = None
+        if env.rgb:
+            image = np.ctypeslib.as_array(C.cast(env.rgb, C.POINTER(C.c_float)), shape=(env.height, env.width, 3)).copy()
+        return {"texture": env.texture or None, "image": image, "intensity": np.array(env.intensity, dtype=np.float64),
+                "rotation": np.array(env.rotation, dtype=np.float64).reshape(3, 3), "has_distribution": bool(has.value)}
+
+    def environment_cdf(self):
+        """The importance sampler's tables of the committed scene (rt_scene_dump_environment_cdf): ``(marginal (H,), conditional
+        (H, W))`` float64, each row ending at exactly 1.0, or None where the environment has no distribution."""
+        w = C.c_int()
+        h = lib().rt_scene_dump_environment_cdf(self._p, C.byref(w), 0, None, None)
+        if h < 0:
+            raise RtowError(_err())
+        if h == 0:
+            return None
+        marginal, conditional = np.zeros(h, dtype=np.float64), np.zeros((h, w.value), dtype=np.float64)
+        lib().rt_scene_dump_environment_cdf(self._p, C.byref(w), h * w.value, marginal.ctypes.data_as(_lib.D3), conditional.ctypes.data_as(_lib.D3))
+        return marginal, conditional
+
+    def flags(self):
+        """The committed scene's flags word as the kernels receive it (rt_scene_flags); ``SCENE_FLAG_ENVIRONMENT`` is one bit of it."""
+        return int(lib().rt_scene_flags(self._p))
 
     def Commit(self):
         _check(lib().rt_scene_commit(self._p))
@@ -761,6 +818,47 @@ class Scene:
                                   (lib().rt_scene_light_pdf, lib().rt_scene_light_pdf_device), structs, LightStats if stats else None, device)
         return (res, st) if stats else res
 
+    # ---- environment sampling (include/rtow.h rt_scene_sample_environment, rt_scene_environment_pdf) ----
+    def sample_environment(self, points, normals=None, materials=None, rng_state=None, want=None, seed=1984, first_sequence=0, variant=0,
+                           device=0, stats=False, out=None):
+        """One direction towards the environment for every point ``points[k]``, drawn by the brightness of the map (uniformly over
+        the sphere where the environment has no distribution: ``environment()``); include/rtow.h rt_scene_sample_environment states
+        every operation.  Arrays and outputs as for ``sample_lights``: "distance" is +inf for a valid sample -- ``shadow_rays`` turns
+        it into ``tmax = inf`` --, "light" the texel drawn, row * W + column with rows counted from the top, -1 without a
+        distribution; "pdf" and "emitted" are those of the final direction: ``environment_pdf`` of it and what a ``path_step``
+        along it returns."""
+        if want is None:
+            want = ("direction", "distance", "light", "pdf", "emitted", "rng_state") + \
+                (("scatter_pdf", "contribution") if normals is not None and materials is not None else ())
+
+        def structs(count, rays, outs, device, stream):
+            if not outs:
+                raise RtowError("want: at least one of " + ", ".join(_lib.LIGHT_SAMPLE_OUTPUTS))
+            p = _lib.EnvironmentParams(count, int(seed), int(first_sequence), int(variant), device, stream)
+            return p, LightPoints(rays.get("origins"), rays.get("normals"), rays.get("materials"), None, rays.get("rng_state")), LightSamples(**outs)
+
+        inputs = [("normals", normals, (3,), ("float64",), False), ("materials", materials, (), ("uint8",), False),
+                  ("rng_state", rng_state, (6,), ("uint32", "int32"), False)]
+        res, st = self._ray_batch("environment sample", points, None, inputs, _lib.LIGHT_SAMPLE_OUTPUTS, tuple(want),
+                                  (lib().rt_scene_sample_environment, lib().rt_scene_sample_environment_device), structs,
+                                  LightStats if stats else None, device, points_only=True, into=out)
+        return (res, st) if stats else res
+
+    def environment_pdf(self, origins, directions, want=("pdf",), variant=0, device=0, stats=False):
+        """The density with which ``sample_environment`` produces the direction ``directions[k]`` (not necessarily unit; the origin
+        does not matter): bit for bit the sampled "pdf" in the strict build.  "light": the texel the direction looks up, -1 without
+        a distribution.  Nothing is drawn."""
+        def structs(count, rays, outs, device, stream):
+            if not outs:
+                raise RtowError("want: at least one of " + ", ".join(_lib.LIGHT_PDF_OUTPUTS))
+            p = _lib.EnvironmentParams(count, 0, 0, int(variant), device, stream)
+            return p, LightRays(rays.get("origins"), rays.get("directions"), None), LightPdfOut(**outs)
+
+        res, st = self._ray_batch("environment pdf", origins, directions, [], _lib.LIGHT_PDF_OUTPUTS, tuple(want),
+                                  (lib().rt_scene_environment_pdf, lib().rt_scene_environment_pdf_device), structs,
+                                  LightStats if stats else None, device)
+        return (res, st) if stats else res
+
     @staticmethod
     def shadow_rays(points, directions, distances, times=None):
         """The arguments of ``occluded`` for shadow rays towards light samples: ``(points, directions, times, tmin, tmax)`` with
@@ -966,6 +1064,14 @@ def scatter_pdf(materials, normals, directions):
 def builtin_scene(scene_id, world_kind, width, height, seed=1984, earth=None):
     """CreateWorld(sceneId) (R/kernel.cu:176-543); world_kind 0 = BvhNode world, 1 = HittableList world."""
     return Scene().build_builtin(scene_id, world_kind, width, height, seed, earth)
+
+
+def sky_demo_scene(world_kind, width, height, seed=1984):
+    """The environment's demonstration scene, ``rtow --scene 15`` (rt_scene_build_sky_demo): the static random spheres on their
+    ground under a computed 256 x 128 sky with a small, very bright sun; the camera's background is black.  Committed."""
+    s = Scene()
+    _check(lib().rt_scene_build_sky_demo(s._p, world_kind, width, height, seed))
+    return s
 
 
 def _direct_or_raise(direct):
@@ -1245,6 +1351,18 @@ def write_ppm_binary(path, frame):
 def write_pfm(path, frame):
     f = np.ascontiguousarray(frame, dtype=np.float64)
     _check(lib().rt_write_pfm(str(path).encode(), f.ctypes.data_as(_lib.D3), f.shape[1], f.shape[0]))
+
+
+def load_pfm(path):
+    """A colour PFM file as a float32 H x W x 3 array, TOP row first -- what ``Scene.Environment(image=...)`` takes (rt_pfm_load:
+    either byte order, the scale's magnitude applied).  ``write_pfm`` writes a frame's rows bottom first, as the format has them:
+    ``load_pfm(write_pfm(frame))`` is ``float32(frame[::-1])``."""
+    ptr, w, h = C.c_void_p(), C.c_int(), C.c_int()
+    _check(lib().rt_pfm_load(str(path).encode(), C.byref(ptr), C.byref(w), C.byref(h)))
+    try:
+        return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_float)), shape=(h.value, w.value, 3)).copy()
+    finally:
+        lib().rt_pfm_free(ptr)
 
 
 def write_ppm(path, frame):

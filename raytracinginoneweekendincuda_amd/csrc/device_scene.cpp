@@ -662,8 +662,22 @@ int rt_scene_upload(rt_scene *scene, int device)
     up(f.images, d.images);
     up(f.image_bytes, d.image_bytes);
     up(f.perlin, d.perlin);
-    std::vector<CameraRec> cam_host(1, s.camera);
-    up(cam_host, d.camera);
+    if (!(f.flags & SCENE_ENVIRONMENT)) {
+        std::vector<CameraRec> cam_host(1, s.camera);
+        up(cam_host, d.camera);
+    } else {  // the environment's record directly behind the camera's, one allocation: camera + 1 (flat_scene.h EnvRec)
+        static_assert(sizeof(CameraRec) % 8 == 0, "the record behind it holds doubles and pointers");
+        EnvRec env = f.env;
+        up(f.env_rgb, env.rgb);
+        up(f.env_mcdf, env.mcdf);
+        up(f.env_ccdf, env.ccdf);
+        std::vector<unsigned char> both(sizeof(CameraRec) + sizeof(EnvRec));
+        std::memcpy(both.data(), &s.camera, sizeof(CameraRec));
+        std::memcpy(both.data() + sizeof(CameraRec), &env, sizeof(EnvRec));
+        const unsigned char *dev = nullptr;
+        up(both, dev);
+        d.camera = reinterpret_cast<const CameraRec *>(dev);
+    }
     if (e != hipSuccess) {
         release_device_tables(dt);
         return hip_fail(e, "rt_scene_upload: table upload");
@@ -760,6 +774,8 @@ struct Build {
     hipError_t (*advance)(const DeviceScene &, const AdvanceArgs &, hipStream_t, QueryKernelInfo *);
     hipError_t (*light_sample)(const DeviceScene &, const LightArgs &, hipStream_t, QueryKernelInfo *);
     hipError_t (*light_pdf)(const DeviceScene &, const LightArgs &, hipStream_t, QueryKernelInfo *);
+    hipError_t (*env_sample)(const DeviceScene &, const LightArgs &, hipStream_t, QueryKernelInfo *);
+    hipError_t (*env_pdf)(const DeviceScene &, const LightArgs &, hipStream_t, QueryKernelInfo *);
     hipError_t (*advance_direct)(const DeviceScene &, const AdvanceDirectArgs &, hipStream_t, QueryKernelInfo *);
     hipError_t (*advance_shadow)(const DeviceScene &, const AdvanceDirectArgs &, hipStream_t, QueryKernelInfo *);
     hipError_t (*radiance_direct)(const DeviceScene &, const RadianceDirectArgs &, hipStream_t, QueryKernelInfo *);
@@ -768,9 +784,11 @@ struct Build {
 static const Build kBuilds[2] = {
     {launch_seed_strict, launch_render_strict, kernel_info_strict, launch_adaptive_rule_strict, launch_features_strict, launch_query_strict,
      launch_radiance_strict, launch_step_strict, launch_advance_strict, launch_light_sample_strict, launch_light_pdf_strict,
+     launch_env_sample_strict, launch_env_pdf_strict,
      launch_advance_direct_strict, launch_advance_shadow_strict, launch_radiance_direct_strict, launch_film_direct_strict},
     {launch_seed_fast, launch_render_fast, kernel_info_fast, launch_adaptive_rule_fast, launch_features_fast, launch_query_fast,
      launch_radiance_fast, launch_step_fast, launch_advance_fast, launch_light_sample_fast, launch_light_pdf_fast,
+     launch_env_sample_fast, launch_env_pdf_fast,
      launch_advance_direct_fast, launch_advance_shadow_fast, launch_radiance_direct_fast, launch_film_direct_fast}};
 
 static int seed_film(FilmImpl &f, const rt_render_params *p, hipStream_t stream)
@@ -1805,6 +1823,112 @@ void rt_light_abi_sizes(uint32_t out8[8])
     out8[5] = (uint32_t)sizeof(rt_light_stats);
     out8[6] = (uint32_t)sizeof(rt_light_row);
     out8[7] = kLightLdsRows;
+}
+
+// ---- environment sampling ----
+// everything that can be refused without a device: batch_check's, then the scene's own state
+static int environment_state_check(rt_scene *scene, bool any_output, const std::string &name)
+{
+    if (!any_output) return fail(RT_ERR_INVALID, name + ": every output is null");
+    if (!(S(scene)->flat.flags & SCENE_ENVIRONMENT)) return fail(RT_ERR_STATE, name + ": the scene has no environment (rt_scene_set_environment)");
+    return RT_OK;
+}
+static int environment_sample_check(rt_scene *scene, const rt_environment_params *p, const rt_light_points *pts, const rt_light_samples *out, const char *who)
+{
+    const std::string name(who);
+    if (int rc = batch_check(scene, p, pts, out, name, nothing_more)) return rc;
+    const bool any = out->direction || out->distance || out->light || out->pdf || out->emitted || out->scatter_pdf || out->contribution || out->rng_state;
+    if (int rc = environment_state_check(scene, any, name)) return rc;
+    if ((out->scatter_pdf || out->contribution) && (!pts->normal || !pts->material))
+        return fail(RT_ERR_INVALID, name + ": scatter_pdf and contribution need normal and material");
+    return RT_OK;
+}
+static int environment_pdf_check(rt_scene *scene, const rt_environment_params *p, const rt_light_rays *rays, const rt_light_pdf_out *out, const char *who)
+{
+    const std::string name(who);
+    if (int rc = batch_check(scene, p, rays, out, name, nothing_more)) return rc;
+    return environment_state_check(scene, out->pdf || out->light, name);
+}
+
+// the arguments both kernels share, and the run: `la` holds the caller's arrays already (run_light_kernel without a table)
+static int run_environment_kernel(rt_scene *scene, const rt_environment_params *p, LightArgs &la, bool pdf_mode, const char *who, rt_light_stats *stats)
+{
+    SceneImpl &s = *S(scene);
+    if (int rc = rt_scene_upload(scene, p->device)) return rc;  // (selects the device)
+    DeviceTables &dt = *s.device[p->device];
+    if (int rc = device_jump_table(p->device, &la.jump_table)) return rc;
+    la.base = xorwow_seed(p->seed, kSaltCurandDevice);
+    la.first_sequence = p->first_sequence;
+    la.count = (uint32_t)p->count;
+    hipStream_t stream = (hipStream_t)p->stream;
+    const auto launch = [&](QueryKernelInfo *info) {
+        return pdf_mode ? kBuilds[p->variant].env_pdf(dt.scene, la, stream, info) : kBuilds[p->variant].env_sample(dt.scene, la, stream, info);
+    };
+    TimedRun run{};
+    if (int rc = run_lane_kernel(launch, {&la.valid_counter}, 1, p->device, stream, who, stats, run)) return rc;
+    if (stats) {
+        stats->points = (uint64_t)p->count;
+        stats->valid = run.counted[0];
+    }
+    return RT_OK;
+}
+
+int rt_scene_sample_environment_device(rt_scene *scene, const rt_environment_params *p, const rt_light_points *pts, const rt_light_samples *out,
+                                       rt_light_stats *stats)
+{
+    if (int rc = environment_sample_check(scene, p, pts, out, "rt_scene_sample_environment_device")) return rc;
+    if (stats) *stats = rt_light_stats{};
+    if (p->count == 0) return RT_OK;
+    LightArgs la{};
+    la.point = pts->point;
+    la.normal = pts->normal;
+    la.material = pts->material;
+    la.rng_in = pts->rng_state;
+    la.direction = out->direction;
+    la.distance = out->distance;
+    la.light = out->light;
+    la.pdf = out->pdf;
+    la.emitted = out->emitted;
+    la.scatter_pdf = out->scatter_pdf;
+    la.contribution = out->contribution;
+    la.rng_out = out->rng_state;
+    return run_environment_kernel(scene, p, la, false, "rt_scene_sample_environment_device", stats);
+}
+
+int rt_scene_sample_environment(rt_scene *scene, const rt_environment_params *p, const rt_light_points *pts, const rt_light_samples *out,
+                                rt_light_stats *stats)
+{
+    if (int rc = environment_sample_check(scene, p, pts, out, "rt_scene_sample_environment")) return rc;
+    return host_batch(scene, p, pts, out, stats, rt_scene_sample_environment_device);
+}
+
+int rt_scene_environment_pdf_device(rt_scene *scene, const rt_environment_params *p, const rt_light_rays *rays, const rt_light_pdf_out *out,
+                                    rt_light_stats *stats)
+{
+    if (int rc = environment_pdf_check(scene, p, rays, out, "rt_scene_environment_pdf_device")) return rc;
+    if (stats) *stats = rt_light_stats{};
+    if (p->count == 0) return RT_OK;
+    LightArgs la{};
+    la.point = rays->origin;
+    la.direction_in = rays->direction;
+    la.pdf = out->pdf;
+    la.light = out->light;
+    return run_environment_kernel(scene, p, la, true, "rt_scene_environment_pdf_device", stats);
+}
+
+int rt_scene_environment_pdf(rt_scene *scene, const rt_environment_params *p, const rt_light_rays *rays, const rt_light_pdf_out *out,
+                             rt_light_stats *stats)
+{
+    if (int rc = environment_pdf_check(scene, p, rays, out, "rt_scene_environment_pdf")) return rc;
+    return host_batch(scene, p, rays, out, stats, rt_scene_environment_pdf_device);
+}
+
+void rt_environment_abi_sizes(uint32_t out4[4])
+{
+    out4[0] = (uint32_t)sizeof(rt_environment);
+    out4[1] = (uint32_t)sizeof(rt_environment_params);
+    out4[2] = kEnvLdsRows;
+    out4[3] = 0;
 }
 
 // ---- path advances ----

@@ -261,6 +261,28 @@ struct CameraRec {
     double lens_radius, time0, time1;
 };
 
+// The environment of a scene (include/rtow.h rt_scene_set_environment; render.hip environment_value): what a ray that leaves the
+// world sees in place of CameraRec::bg.  One record, uploaded directly BEHIND the camera's in the same device allocation
+// (device_scene.cpp), so that the kernels reach it as camera + 1 and DeviceScene, a kernel argument of every instantiation, stays
+// as it is; present only where the scene's flags hold SCENE_ENVIRONMENT.  The float image is a table of its own, read by nothing
+// else.  mcdf / ccdf: the importance sampler's tables (rt_scene_dump_environment_cdf), H and H x W doubles, where
+// has_distribution; width and height are then the float image's or the image texture's own.
+struct EnvRec {
+    double intensity[3];
+    double rot[9];          // row-major R, world -> environment
+    uint32_t texture;       // row of textures[], or kNone: the float image
+    int32_t width, height;
+    uint32_t has_distribution;
+    const float *rgb;       // width x height x 3, top row first
+    const double *mcdf;     // cumulative chance of rows 0 .. j, rows counted from the top; entry height - 1 is 1.0
+    const double *ccdf;     // row j: cumulative chance of columns 0 .. i within it; entry width - 1 is 1.0
+};
+static_assert(sizeof(EnvRec) % 8 == 0, "follows CameraRec, 27 doubles");
+// Rows of the marginal table a workgroup of env_sample_kernel stages in LDS: 2048 doubles = 16 KB, so eight workgroups of four
+// waves -- the 32 waves a CU can hold -- fit its 160 KB and the staging never lowers the occupancy; a 4096 x 2048 panorama's
+// marginal table fits whole.  Rows beyond the cap are read from global memory.
+constexpr uint32_t kEnvLdsRows = 2048;
+
 enum : uint32_t { WORLD_BVH = 0u, WORLD_LIST = 1u };
 
 // What the kernel receives (by value).  All pointers are device pointers.
@@ -339,6 +361,7 @@ enum : uint32_t {
     SCENE_VERTEX_ATTR = 128u,     // some triangle row carries corner normals or texture coordinates (TriAttrRow)
     SCENE_AFFINE = 256u,          // some chain holds a general affine step (XF_AFFINE, XF_MOVING): served by the units compiled with RT_AFFINE (render.hip RT_TO_AFFINE)
     SCENE_MOVING = 512u,          // some chain holds a moving step (XF_MOVING; SCENE_AFFINE is set too): served by the second pass of those units (render.hip RT_MOVING)
+    SCENE_ENVIRONMENT = 1024u,    // an EnvRec follows the camera's record: a miss reads it, not CameraRec::bg; rendered by the RICH instantiations (launch_plan.cpp choose_kernel)
 };
 
 } // namespace rtow

@@ -187,7 +187,8 @@ static int list_instances_waves(const KernelOptions &o)
 KernelId choose_kernel(const DeviceScene &sc, const KernelOptions &o)
 {
     const bool composite = sc.n_objects != 0 || sc.n_boxes != 0;
-    const bool rich = (sc.flags & SCENE_RICH_TEXTURES) != 0, media = (sc.flags & SCENE_HAS_MEDIA) != 0, trees = (sc.flags & SCENE_HAS_TREES) != 0;
+    // (an environment is read by the instantiations that carry the texture code: render.hip miss_value)
+    const bool rich = (sc.flags & (SCENE_RICH_TEXTURES | SCENE_ENVIRONMENT)) != 0, media = (sc.flags & SCENE_HAS_MEDIA) != 0, trees = (sc.flags & SCENE_HAS_TREES) != 0;
     const bool library_tree = sc.n_fast_nodes != 0;
     // an instantiation that reads its tables from LDS only is chosen where they fit, and the next best one where they do not
     auto fits = [&](KernelId k) { return lds_layout(kKernelProps[k], sc).fits; };

@@ -203,6 +203,8 @@ int main(int argc, char **argv)
     unsigned long long seed = 1984;
     unsigned flags = 0;          // RT_FLAG_* bits (schedulers and the opt-in list acceleration; none changes the picture)
     std::string out = "output.ppm";
+    std::string environment_path;  // --environment: a .pfm float image or a JPEG, the sky of any scene
+    double environment_intensity = 1.0, environment_rotate_y = 0.0;
     std::string earth_path;      // decoded 8-bit sRGB pixels of the earth texture (P6): converted like RtwImage::Load does
     bool earth_is_bytes = false; // --earth-bytes: the file already holds what RtwImage::Load hands to ImageTexture
     // adaptive sampling (--noise): a pixel stops once its noise is below the threshold, --spp is then the most it takes
@@ -303,18 +305,26 @@ int main(int argc, char **argv)
             }
             direct_mis = true;
         }
+        else if (const char *v = val("--environment-intensity")) environment_intensity = std::atof(v);
+        else if (const char *v = val("--environment-rotate-y")) environment_rotate_y = std::atof(v);
+        else if (const char *v = val("--environment")) environment_path = v;
         else if (const char *v = val("--earth")) earth_path = v;
         else if (const char *v = val("--earth-bytes")) {
             earth_path = v;
             earth_is_bytes = true;
         } else {
             std::fprintf(stderr,
-                         "usage: rtow [--scene 0..14] [--width W] [--height H] [--spp N] [--depth D] [--seed S]\n"
+                         "usage: rtow [--scene 0..15] [--width W] [--height H] [--spp N] [--depth D] [--seed S]\n"
                          "            [--world bvh|list] [--variant strict|fast] [--device N] [--gpus N] [--output file.ppm]\n"
                          "            [--earth earthmap.jpg|decoded.ppm | --earth-bytes texture.ppm] [--accelerate-lists] [--flags N]\n"
                          "            [--noise T [--min-spp N] [--check-every K] [--samples-map file.pgm]]\n"
                          "            [--denoise [--denoise-iterations N] [--denoise-sigmas c,a,n,z] [--raw-output file.ppm]]\n"
                          "            [--aov-prefix P] [--feature-samples N] [--pick i,j] [--radiance-at i,j] [--trace-at i,j] [--lights] [--direct mis]\n"
+                         "            [--environment sky.pfm|sky.jpg] [--environment-intensity X] [--environment-rotate-y DEG]\n"
+                         "  --environment  what a ray that leaves the scene sees, in place of the scene's background colour: a .pfm file is a linear\n"
+                         "                 float image (an HDR panorama, top row = up), any other file is read as --earth reads a JPEG, as an 8-bit\n"
+                         "                 image texture; --environment-intensity multiplies it, --environment-rotate-y turns it about the vertical.\n"
+                         "                 Scene 15 brings a computed sky along (the two options adjust that one too)\n"
                          "  --lights       render nothing: print the light table (rt_scene_dump_lights), a line per emissive primitive in world space --\n"
                          "                 kind, world leaf, material row, geometry, and its entries of the two cumulative selection tables\n"
                          "  --pick         render nothing: print what the ray through the centre of pixel (i, j) hits (j = 0 is the bottom row) --\n"
@@ -390,7 +400,7 @@ int main(int argc, char **argv)
         std::fprintf(stderr, "--trace-at needs --spp >= 1 and --depth >= 0\n");
         return 2;
     }
-    if (spp < 0) spp = (scene_id == 9) ? 100 : (((scene_id >= 5 && scene_id <= 8) || (scene_id >= 12 && scene_id <= 14)) ? 200 : 10);  // R/kernel.cu:593 (12 .. 14: lit like 7)
+    if (spp < 0) spp = (scene_id == 9) ? 100 : (((scene_id >= 5 && scene_id <= 8) || (scene_id >= 12 && scene_id <= 14)) ? 200 : (scene_id == 15 ? 100 : 10));  // R/kernel.cu:593 (12 .. 14: lit like 7; 15: lit by its sun)
 
     if (pick && (pick_i < 0 || pick_i >= width || pick_j < 0 || pick_j >= height)) {
         std::fprintf(stderr, "%s: pixel (%d, %d) is outside the %dx%d frame\n", trace_at ? "--trace-at" : radiance_at ? "--radiance-at" : "--pick", pick_i, pick_j, width, height);
@@ -437,9 +447,42 @@ int main(int argc, char **argv)
             std::fprintf(stderr, "Loaded image '%s' (%dx%d) and uploaded to device.\n", earth_path.c_str(), earth_w, earth_h);
         }
     }
-    if (rt_scene_build_builtin(scene, scene_id, world_kind, width, height, seed, earth.empty() ? nullptr : earth.data(), earth_w,
-                               earth_h) != RT_OK)
+    if (scene_id == 15) {  // the environment's demonstration: a scene of its own call, not a builtin id
+        if (rt_scene_build_sky_demo(scene, world_kind, width, height, seed) != RT_OK) return die("scene");
+    } else if (rt_scene_build_builtin(scene, scene_id, world_kind, width, height, seed, earth.empty() ? nullptr : earth.data(), earth_w,
+                                      earth_h) != RT_OK)
         return die("scene");
+
+    // --environment FILE: a sky for any scene (.pfm: a linear float image; anything else goes through RtwImage::Load as an 8-bit image
+    // texture); --environment-intensity and --environment-rotate-y also adjust the sky a scene brings along (scene 15)
+    if (!environment_path.empty() || environment_intensity != 1.0 || environment_rotate_y != 0.0) {
+        rt_environment env{};
+        float *pfm = nullptr;
+        if (environment_path.empty()) {
+            if (rt_scene_get_environment(scene, &env, nullptr) != RT_OK) return die("environment");
+            if (!env.texture && !env.rgb) {
+                std::fprintf(stderr, "--environment-intensity / --environment-rotate-y: the scene has no environment (--environment FILE, or --scene 15)\n");
+                return 1;
+            }
+        } else if (environment_path.size() > 4 && environment_path.rfind(".pfm") == environment_path.size() - 4) {
+            if (rt_pfm_load(environment_path.c_str(), &pfm, &env.width, &env.height) != RT_OK) return die("environment");
+            env.rgb = pfm;
+        } else {
+            unsigned char *bytes = nullptr;
+            int w = 0, h = 0;
+            if (rt_rtwimage_load(environment_path.c_str(), &bytes, &w, &h) != RT_OK) return die("environment");
+            env.texture = rt_image_texture(scene, bytes, w, h);
+            rt_image_free(bytes);
+            if (!env.texture) return die("environment");
+        }
+        const double radians = environment_rotate_y * 3.1415926535897932385 / 180.0, cs = std::cos(radians), sn = std::sin(radians);
+        const double about_y[9] = {cs, 0.0, -sn, 0.0, 1.0, 0.0, sn, 0.0, cs};
+        for (int k = 0; k < 3; k++) env.intensity[k] = environment_intensity;
+        for (int k = 0; k < 9; k++) env.rotation[k] = about_y[k];
+        const int rc = rt_scene_set_environment(scene, &env);  // (copies the image)
+        rt_pfm_free(pfm);
+        if (rc != RT_OK || rt_scene_commit(scene) != RT_OK) return die("environment");
+    }
 
     if (list_lights) {  // host only: the table as rt_scene_upload would copy it
         const int n = rt_scene_dump_lights(scene, 0, nullptr, nullptr, nullptr, nullptr);

@@ -3321,6 +3321,64 @@ DEV bool shade(const DeviceScene &sc, const Surface &s, Ray &ray, Vec &throughpu
 // Camera::GetRay (R/Camera.h:76-85) behind the pixel jitter of Render (R/kernel.cu:140-142).
 DEV Vec load3c(const RT_CONST double *p) { return mk(p[0], p[1], p[2]); }
 
+// The environment (include/rtow.h rt_scene_set_environment states every operation; tests/environment_restated.py restates the
+// strict build): the record behind the camera's (flat_scene.h EnvRec), valid only under SCENE_ENVIRONMENT.
+DEV const RT_CONST EnvRec *environment_of(const CameraRec *cam) { return (const RT_CONST EnvRec *)(uintptr_t)(cam + 1); }
+// the direction d, not necessarily unit, in the environment's frame, and its (u, v): the reference's GetSphereUV (R/Sphere.h:74-81)
+DEV void environment_coords(const RT_CONST EnvRec *env, Vec d, Vec &e, double &u, double &v)
+{
+    const Vec n = (1 / sqrt((d.x * d.x + d.y * d.y) + d.z * d.z)) * d;
+    e = mk((env->rot[0] * n.x + env->rot[1] * n.y) + env->rot[2] * n.z, (env->rot[3] * n.x + env->rot[4] * n.y) + env->rot[5] * n.z,
+           (env->rot[6] * n.x + env->rot[7] * n.y) + env->rot[8] * n.z);
+    sphere_uv(e, u, v);
+}
+// ImageTexture::Value's index rule (R/Texture.h:110-133) for a table of width x height texels, top row first; the index is
+// clamped on both sides, so that no (u, v), a NaN included, names a texel outside the table
+DEV void environment_texel(int width, int height, double u, double v, int &i, int &j)
+{
+    u = u < 0.0 ? 0.0 : (u > 1.0 ? 1.0 : u);
+    v = v < 0.0 ? 0.0 : (v > 1.0 ? 1.0 : v);
+    v = 1.0 - v;
+    i = (int)(u * width);
+    j = (int)(v * height);
+    i = i >= width ? width - 1 : (i < 0 ? 0 : i);
+    j = j >= height ? height - 1 : (j < 0 ? 0 : j);
+}
+// the value at e, (u, v): intensity * the texture there, or intensity * the float image's texel widened to double
+template <class T>
+DEV Vec environment_lookup(const DeviceScene &sc, const RT_CONST EnvRec *env, Vec e, double u, double v)
+{
+    Vec value;
+    if (env->texture != kNone) {
+        value = texture_value<T>(sc, env->texture, u, v, e);
+    } else {
+        int i, j;
+        environment_texel(env->width, env->height, u, v, i, j);
+        const float *px = env->rgb + ((size_t)j * (size_t)env->width + (size_t)i) * 3;
+        value = mk((double)px[0], (double)px[1], (double)px[2]);
+    }
+    return load3c(env->intensity) * value;
+}
+template <class T>
+DEV Vec environment_value(const DeviceScene &sc, const CameraRec *cam, Vec d)
+{
+    const RT_CONST EnvRec *env = environment_of(cam);
+    Vec e;
+    double u, v;
+    environment_coords(env, d, e, u, v);
+    return environment_lookup<T>(sc, env, e, u, v);
+}
+// What a ray that leaves the world adds (R/kernel.cu:74-79): the environment along it where the scene has one -- one wave-uniform
+// test of the scene's flags, compiled only into the instantiations that carry the texture code -- else the camera's background.
+template <class T>
+DEV Vec miss_value(const DeviceScene &sc, const CameraRec *cam, Vec d)
+{
+    if constexpr (T::RICH) {
+        if ((sc.flags & SCENE_ENVIRONMENT) != 0) return environment_value<T>(sc, cam, d);
+    }
+    return load3c(((const RT_CONST CameraRec *)(uintptr_t)cam)->bg);
+}
+
 DEV Ray camera_ray(const CameraRec *cam_generic, int i, int j, int width, int height, Xorwow &rng)
 {
     const RT_CONST CameraRec *cam = (const RT_CONST CameraRec *)(uintptr_t)cam_generic;
@@ -4152,7 +4210,7 @@ __global__ __launch_bounds__(T::BLOCK, T::MIN_WAVES) void render_kernel(DeviceSc
             if (no_bounces) {
                 path_ends = true;
             } else if (!hit) {  // R/kernel.cu:74-79
-                accumulated = accumulated + throughput * load3c(((const RT_CONST CameraRec *)(uintptr_t)cam)->bg);
+                accumulated = accumulated + throughput * miss_value<T>(sc, cam, ray.d);
                 path_ends = true;
             } else {
 #if RT_PHASES
@@ -4689,7 +4747,8 @@ DEV Xorwow lane_stream(const Args &a, uint32_t k)
 // answer (NaNs only make them false); leaf tests are straight-line code or loops over table counts (tree_hit: a bounded stack).
 //
 // One bounce of RayColor (R/kernel.cu:74-94) behind a search that answered `hit` with record h, exactly the block of render_kernel
-// at "R/kernel.cu:74-79": a miss adds the background, a hit goes through make_surface and shade.  Returns scattered: `ray` is then
+// at "R/kernel.cu:74-79": a miss adds the background -- or, under SCENE_ENVIRONMENT, the environment along the ray (miss_value: every
+// lane-per-ray kernel gets the environment from this one place) --, a hit goes through make_surface and shade.  Returns scattered: `ray` is then
 // the next ray, else it is untouched.  radiance_kernel passes its path's throughput and sum.  Every other caller passes (1, 1, 1)
 // and (0, 0, 0): what shade leaves in `accumulated` is then 0 + 1 * x, the emitted or background value x itself, and what it
 // leaves in `throughput` is 1 * a, the attenuation a itself (a negative zero comes out positive), in the strict build and in the
@@ -4707,7 +4766,7 @@ DEV bool bounce(const DeviceScene &sc, Ray &ray, const HitInfo &h, bool hit, Xor
     front = false;
     bool scattered = false;
     if (!hit) {  // R/kernel.cu:74-79
-        accumulated = accumulated + throughput * load3c(((const RT_CONST CameraRec *)(uintptr_t)sc.camera)->bg);
+        accumulated = accumulated + throughput * miss_value<T>(sc, sc.camera, ray.d);
     } else {
         const Surface s = make_surface<T>(sc, ray, h);
         if (want_normal && (h.ref >> kRefShift) != REF_MEDIUM) normal = s.n;
@@ -4823,7 +4882,7 @@ __global__ __launch_bounds__(256) void feature_kernel(DeviceScene sc, FeatureArg
         Vec value, sn = mk(0.0, 0.0, 0.0);
         double sd = 0.0;
         if (!hit) {
-            value = load3c(((const RT_CONST CameraRec *)(uintptr_t)cam)->bg);
+            value = miss_value<T>(sc, cam, ray.d);
         } else {
             const Surface s = make_surface<T>(sc, ray, h);
             const MatView mp = material_view<false>(sc, s.mat);
@@ -5011,7 +5070,7 @@ __global__ __launch_bounds__(256) void query_kernel(DeviceScene sc, QueryArgs a)
         uint32_t kind = 255u;
         bool front = false;
         if (!hit) {
-            if (a.albedo) value = load3c(((const RT_CONST CameraRec *)(uintptr_t)sc.camera)->bg);
+            if (a.albedo) value = miss_value<T>(sc, sc.camera, ray.d);
         } else {
             if (a.uv) query_uv<T>(sc, ray, h, u, v);
             if (a.normal || a.front_face || want_material) {  // (U/V alone need no hit record)
@@ -5622,6 +5681,165 @@ __global__ __launch_bounds__(256) void light_pdf_kernel(DeviceScene sc, LightArg
         if (a.light) a.light[k] = light;
     }
     count_valid(a.valid_counter, mine && light >= 0, wave_valid);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Environment sampling (rt_scene_sample_environment, rt_scene_environment_pdf; include/rtow.h states both operation by operation,
+// tests/environment_restated.py restates the strict build).  One lane a point or a ray, the light calls' arrays (LightArgs: no
+// light table, no strategy).  The tables are the EnvRec's: a marginal table over the rows of the map and one conditional table a
+// row.  A sample bisects both, log2 H + log2 W dependent loads a lane: a workgroup first stages the first kEnvLdsRows entries of
+// the marginal table in LDS with coalesced loads (flat_scene.h says why that many), so the first chain is LDS reads; the chain
+// through the lane's own conditional row stays in global memory -- 64 lanes stand on up to 64 rows of W doubles, which no LDS
+// holds.  Rows of the marginal table beyond the cap are read from global memory.  The density is one expression, of the texel the
+// environment's own lookup names for the direction: the sample's pdf is environment_pdf of its direction.  No lane returns early
+// (all meet at the barriers); the count of valid results reduces as the light kernels' does.
+// ------------------------------------------------------------------------------------------------
+namespace {
+// STAGED: the caller holds the workgroup's copy of the first kEnvLdsRows entries
+template <bool STAGED>
+DEV double env_mcdf(const RT_CONST EnvRec *env, const double *lds, uint32_t j)
+{
+    if constexpr (STAGED) {
+        if (j < kEnvLdsRows) return lds[j];
+    }
+    return env->mcdf[j];
+}
+// the density of the direction whose environment coordinates are e, (u, v); `texel`: j * width + i of its texel, -1 without tables
+template <bool STAGED>
+DEV double environment_density(const RT_CONST EnvRec *env, const double *lds, Vec e, double u, double v, int32_t &texel)
+{
+    texel = -1;
+    if (!env->has_distribution) return 1.0 / (4.0 * kLightPi);
+    int i, j;
+    environment_texel(env->width, env->height, u, v, i, j);
+    texel = j * env->width + i;
+    const double pj = env_mcdf<STAGED>(env, lds, (uint32_t)j) - (j ? env_mcdf<STAGED>(env, lds, (uint32_t)j - 1u) : 0.0);
+    const double *row = env->ccdf + (size_t)j * (size_t)env->width;
+    const double pi = row[i] - (i ? row[i - 1] : 0.0);
+    return ((pj * pi) * ((double)env->width * (double)env->height)) / (((2.0 * kLightPi) * kLightPi) * sqrt(1.0 - e.y * e.y));
+}
+}  // namespace
+
+template <int STRICT, class T>
+__global__ __launch_bounds__(256) void env_sample_kernel(DeviceScene sc, LightArgs a)
+{
+    __shared__ double mcdf_lds[kEnvLdsRows];
+    __shared__ uint32_t wave_valid[4];
+    global_tables_only(sc);
+    const RT_CONST EnvRec *env = environment_of(sc.camera);
+    const bool tables = env->has_distribution != 0;
+    const uint32_t width = (uint32_t)env->width, height = (uint32_t)env->height;
+    if (tables) {
+        const double *src = env->mcdf;
+        const uint32_t n = min(height, kEnvLdsRows);
+        for (uint32_t i = threadIdx.x; i < n; i += 256u) mcdf_lds[i] = src[i];
+    }
+    __syncthreads();
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    bool valid = false;
+    if (k < a.count) {
+        // the six words are read here, before anything is written: rng_out may be rng_in
+        Xorwow rng = lane_stream(a, k);
+        const double xa = (double)xorwow_uniform(rng);
+        const double xb = (double)xorwow_uniform(rng);
+        const double xc = (double)xorwow_uniform(rng);
+        const double xd = (double)xorwow_uniform(rng);
+        Vec e;
+        int32_t texel = -1;
+        if (tables) {
+            uint32_t lo = 0, hi = height - 1u;
+            while (lo < hi) {  // the first row with mcdf >= xa (the last entry is 1.0 >= xa)
+                const uint32_t mid = (lo + hi) / 2u;
+                if (env_mcdf<true>(env, mcdf_lds, mid) >= xa) hi = mid;
+                else lo = mid + 1u;
+            }
+            const uint32_t j = lo;
+            const double *row = env->ccdf + (size_t)j * width;
+            lo = 0;
+            hi = width - 1u;
+            while (lo < hi) {
+                const uint32_t mid = (lo + hi) / 2u;
+                if (row[mid] >= xb) hi = mid;
+                else lo = mid + 1u;
+            }
+            const uint32_t i = lo;
+            texel = (int32_t)(j * width + i);
+            const double u = ((double)i + xc) / (double)width;
+            const double v = 1.0 - ((double)j + xd) / (double)height;
+            const double theta = kLightPi * v, phi = (2.0 * kLightPi) * u - kLightPi;
+            const double st = sin(theta);
+            e = mk(st * cos(phi), -cos(theta), -(st * sin(phi)));
+        } else {  // no tables: the sphere uniformly
+            const double y = 1.0 - 2.0 * xc;
+            const double st = sqrt(1.0 - y * y), phi = (2.0 * kLightPi) * xd - kLightPi;
+            e = mk(st * cos(phi), y, -(st * sin(phi)));
+        }
+        // R^T e, each row (a + b) + c
+        Vec dir = mk((env->rot[0] * e.x + env->rot[3] * e.y) + env->rot[6] * e.z, (env->rot[1] * e.x + env->rot[4] * e.y) + env->rot[7] * e.z,
+                     (env->rot[2] * e.x + env->rot[5] * e.y) + env->rot[8] * e.z);
+        // density and value from the direction itself, through the environment's own lookup
+        Vec el;
+        double u, v;
+        environment_coords(env, dir, el, u, v);
+        int32_t seen;
+        double pdf = environment_density<true>(env, mcdf_lds, el, u, v, seen);
+        valid = usable_density(pdf);
+        Vec emitted = mk(0.0, 0.0, 0.0), contribution = mk(0.0, 0.0, 0.0);
+        double scatter = 0.0;
+        if (!valid) {
+            dir = mk(0.0, 0.0, 0.0);
+            pdf = 0.0;
+        }
+        if (valid && (a.emitted || a.contribution)) emitted = environment_lookup<T>(sc, env, el, u, v);
+        if (valid && (a.scatter_pdf || a.contribution)) {
+            const uint32_t kind = a.material[k];
+            scatter = scatter_density(kind, kind == MAT_LAMBERTIAN ? load3(a.normal + (size_t)k * 3) : mk(0.0, 0.0, 0.0), dir);  // (only it reads the normal)
+            if (scatter != 0.0) contribution = (scatter / pdf) * emitted;
+        }
+        if (a.direction) store3(a.direction, k, dir);
+        if (a.distance) a.distance[k] = valid ? (double)INFINITY : 0.0;
+        if (a.light) a.light[k] = texel;
+        if (a.pdf) a.pdf[k] = pdf;
+        if (a.emitted) store3(a.emitted, k, emitted);
+        if (a.scatter_pdf) a.scatter_pdf[k] = scatter;
+        if (a.contribution) store3(a.contribution, k, contribution);
+        if (a.rng_out) store_stream(a.rng_out + (size_t)k * 6, 1, rng);
+    }
+    count_valid(a.valid_counter, valid, wave_valid);
+}
+
+template <int STRICT>
+__global__ __launch_bounds__(256) void env_pdf_kernel(DeviceScene sc, LightArgs a)
+{
+    __shared__ uint32_t wave_valid[4];
+    const RT_CONST EnvRec *env = environment_of(sc.camera);
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    bool valid = false;
+    if (k < a.count) {
+        Vec e;
+        double u, v;
+        environment_coords(env, load3(a.direction_in + (size_t)k * 3), e, u, v);
+        int32_t texel;
+        double pdf = environment_density<false>(env, nullptr, e, u, v, texel);
+        valid = usable_density(pdf);
+        if (!valid) pdf = 0.0;
+        if (a.pdf) a.pdf[k] = pdf;
+        if (a.light) a.light[k] = texel;
+    }
+    count_valid(a.valid_counter, valid, wave_valid);
+}
+
+hipError_t RT_CAT(launch_env_sample_, RT_SUFFIX)(const DeviceScene &sc, const LightArgs &a, hipStream_t stream, QueryKernelInfo *info)
+{
+    const bool any = a.direction || a.distance || a.light || a.pdf || a.emitted || a.scatter_pdf || a.contribution || a.rng_out;
+    if (!info && (!any || !(sc.flags & SCENE_ENVIRONMENT))) return hipErrorInvalidValue;
+    if (!info && (a.scatter_pdf || a.contribution) && (!a.normal || !a.material)) return hipErrorInvalidValue;
+    return info_or_launch(env_sample_kernel<RT_STRICT, TListNested>, sc, a, a.count, stream, info);
+}
+hipError_t RT_CAT(launch_env_pdf_, RT_SUFFIX)(const DeviceScene &sc, const LightArgs &a, hipStream_t stream, QueryKernelInfo *info)
+{
+    if (!info && (!a.direction_in || !(a.pdf || a.light) || !(sc.flags & SCENE_ENVIRONMENT))) return hipErrorInvalidValue;
+    return info_or_launch(env_pdf_kernel<RT_STRICT>, sc, a, a.count, stream, info);
 }
 
 hipError_t RT_CAT(launch_light_sample_, RT_SUFFIX)(const DeviceScene &sc, const LightArgs &a, hipStream_t stream, QueryKernelInfo *info)

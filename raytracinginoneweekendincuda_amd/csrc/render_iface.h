@@ -382,6 +382,13 @@ hipError_t launch_light_sample_strict(const DeviceScene &sc, const LightArgs &a,
 hipError_t launch_light_sample_fast(const DeviceScene &sc, const LightArgs &a, hipStream_t stream, QueryKernelInfo *info = nullptr);
 hipError_t launch_light_pdf_strict(const DeviceScene &sc, const LightArgs &a, hipStream_t stream, QueryKernelInfo *info = nullptr);
 hipError_t launch_light_pdf_fast(const DeviceScene &sc, const LightArgs &a, hipStream_t stream, QueryKernelInfo *info = nullptr);
+// Environment sampling (rt_scene_sample_environment, rt_scene_environment_pdf; the same objects): the light calls' arguments
+// without a table -- rows, cdf, n_lights, point and time stay unread; the tables are the EnvRec's behind the camera's record.
+// `light` receives the texel, j * width + i, or -1 where the environment has no distribution.
+hipError_t launch_env_sample_strict(const DeviceScene &sc, const LightArgs &a, hipStream_t stream, QueryKernelInfo *info = nullptr);
+hipError_t launch_env_sample_fast(const DeviceScene &sc, const LightArgs &a, hipStream_t stream, QueryKernelInfo *info = nullptr);
+hipError_t launch_env_pdf_strict(const DeviceScene &sc, const LightArgs &a, hipStream_t stream, QueryKernelInfo *info = nullptr);
+hipError_t launch_env_pdf_fast(const DeviceScene &sc, const LightArgs &a, hipStream_t stream, QueryKernelInfo *info = nullptr);
 
 // One level of the edge-avoiding a-trous filter (denoise.hip; include/rtow.h rt_denoise_params has the stencil): full-frame
 // planes, `in` and `out` distinct.  A guide that is nullptr switches its term off; inv_* = 1 / sigma^2 (0 for sigma = +inf), the

@@ -1626,6 +1626,68 @@ struct LightCollector {
 };
 }  // namespace
 
+// The environment's record and, for an image, the importance sampler's tables (include/rtow.h rt_scene_dump_environment_cdf states
+// the rule; tests/environment_restated.py restates it to the bit).
+static void build_environment(const SceneImpl &s, FlatScene &f)
+{
+    const HostEnvironment &h = s.environment;
+    f.flags |= SCENE_ENVIRONMENT;
+    EnvRec &r = f.env;
+    std::memcpy(r.intensity, h.intensity, sizeof r.intensity);
+    std::memcpy(r.rot, h.rotation, sizeof r.rot);
+    r.texture = h.texture ? h.texture - 1 : kNone;
+    r.width = h.width;
+    r.height = h.height;
+    f.env_rgb = h.rgb;
+    const unsigned char *bytes = nullptr;
+    if (h.texture) {
+        const HostTexture &t = s.textures[h.texture - 1];
+        r.width = r.height = 0;
+        if (t.kind != TEX_IMAGE || s.images[t.a].height <= 0 || s.images[t.a].width <= 0) return;  // no image: no distribution
+        r.width = s.images[t.a].width;
+        r.height = s.images[t.a].height;
+        bytes = s.image_bytes.data() + s.images[t.a].offset;
+    }
+    const size_t W = (size_t)r.width, H = (size_t)r.height;
+    const double pi = 3.1415926535897932385, cs = 1.0 / 255.0;
+    std::vector<double> weight(W * H), row_sum(H);
+    double total = 0.0;
+    for (size_t j = 0; j < H; j++) {
+        const double sn = std::sin(pi * ((double)j + 0.5) / (double)H);
+        double sum = 0.0;
+        for (size_t i = 0; i < W; i++) {
+            double brightest = 0.0;
+            for (int c = 0; c < 3; c++) {
+                const size_t at = (j * W + i) * 3 + (size_t)c;
+                const double value = bytes ? cs * bytes[at] : (double)h.rgb[at];
+                const double x = h.intensity[c] * value;
+                brightest = c == 0 || x > brightest ? x : brightest;
+            }
+            weight[j * W + i] = brightest * sn;
+            sum += weight[j * W + i];
+        }
+        row_sum[j] = sum;
+        total += sum;
+    }
+    if (!(std::isfinite(total) && total > 0.0)) return;
+    f.env_mcdf.assign(H, 1.0);
+    f.env_ccdf.assign(W * H, 1.0);
+    double run = 0.0;
+    for (size_t j = 0; j + 1 < H; j++) {
+        run += row_sum[j];
+        f.env_mcdf[j] = run / total;
+    }
+    for (size_t j = 0; j < H; j++) {
+        if (!(row_sum[j] > 0.0)) continue;  // never consulted
+        double part = 0.0;
+        for (size_t i = 0; i + 1 < W; i++) {
+            part += weight[j * W + i];
+            f.env_ccdf[j * W + i] = part / row_sum[j];
+        }
+    }
+    r.has_distribution = 1;
+}
+
 int flatten_scene(SceneImpl &s)
 {
     if (s.world == 0) return fail(RT_ERR_STATE, "rt_scene_commit: no world set (rt_scene_set_world)");
@@ -1865,6 +1927,7 @@ int flatten_scene(SceneImpl &s)
             if (a.code == kQuadTriangle && a.pad) a.pad += (uint32_t)f.quads.size() - 1u;
         f.flags |= SCENE_VERTEX_ATTR;
     }
+    if (s.has_environment) build_environment(s, f);
     s.committed = true;
     return RT_OK;
 }
@@ -2875,6 +2938,135 @@ int rt_scene_set_camera(rt_scene *s, const double lookfrom[3], const double look
     S(s)->generation++;  // the uploaded CameraRec is stale; the flat tables do not depend on the camera
     return RT_OK;
 }
+
+static_assert(RT_SCENE_FLAG_ENVIRONMENT == SCENE_ENVIRONMENT, "the bit the header names");
+uint32_t rt_scene_flags(rt_scene *s) { return s && S(s)->committed ? S(s)->flat.flags : 0u; }
+
+int rt_scene_set_environment(rt_scene *s, const rt_environment *env)
+{
+    if (!s) return fail(RT_ERR_INVALID, "rt_scene_set_environment: null scene");
+    SceneImpl &sc = *S(s);
+    if (sc.launches_in_flight > 0)
+        return fail(RT_ERR_STATE, "rt_scene_set_environment: a render of this scene is in flight (rt_render_finish it first)");
+    if (!env) {
+        sc.has_environment = false;
+        sc.environment = HostEnvironment{};
+        sc.committed = false;
+        return RT_OK;
+    }
+    if ((env->texture != 0) == (env->rgb != nullptr)) return fail(RT_ERR_INVALID, "rt_scene_set_environment: give a texture or a float image, not both, not neither");
+    if (env->texture && !valid_tex(&sc, env->texture)) return fail(RT_ERR_INVALID, "rt_scene_set_environment: invalid texture handle");
+    for (int c = 0; c < 3; c++)
+        if (!(std::isfinite(env->intensity[c]) && env->intensity[c] >= 0.0))
+            return fail(RT_ERR_INVALID, "rt_scene_set_environment: intensity must be finite and not negative");
+    for (int k = 0; k < 9; k++)
+        if (!std::isfinite(env->rotation[k])) return fail(RT_ERR_INVALID, "rt_scene_set_environment: rotation is not finite");
+    for (int a = 0; a < 3; a++)
+        for (int b = 0; b < 3; b++) {
+            const double *ra = env->rotation + 3 * a, *rb = env->rotation + 3 * b;
+            const double d = (ra[0] * rb[0] + ra[1] * rb[1]) + ra[2] * rb[2];
+            if (!(std::fabs(d - (a == b ? 1.0 : 0.0)) <= 1e-9)) return fail(RT_ERR_INVALID, "rt_scene_set_environment: rotation is not orthonormal to 1e-9");
+        }
+    HostEnvironment h;
+    h.texture = env->texture;
+    if (env->rgb) {
+        if (env->width < 1 || env->height < 1) return fail(RT_ERR_INVALID, "rt_scene_set_environment: width and height must be at least 1");
+        const size_t n = (size_t)env->width * (size_t)env->height * 3;
+        for (size_t k = 0; k < n; k++)
+            if (!(std::isfinite(env->rgb[k]) && env->rgb[k] >= 0.0f))
+                return fail(RT_ERR_INVALID, "rt_scene_set_environment: a texel of the float image is negative or not finite");
+        h.rgb.assign(env->rgb, env->rgb + n);
+        h.width = env->width;
+        h.height = env->height;
+    }
+    std::memcpy(h.intensity, env->intensity, sizeof h.intensity);
+    std::memcpy(h.rotation, env->rotation, sizeof h.rotation);
+    sc.environment = std::move(h);
+    sc.has_environment = true;
+    sc.committed = false;
+    return RT_OK;
+}
+
+int rt_scene_get_environment(rt_scene *s, rt_environment *out, int *has_distribution)
+{
+    if (!s || !out) return fail(RT_ERR_INVALID, "rt_scene_get_environment: null argument");
+    const SceneImpl &sc = *S(s);
+    std::memset(out, 0, sizeof *out);
+    if (has_distribution) *has_distribution = 0;
+    if (!sc.has_environment) return RT_OK;
+    const HostEnvironment &h = sc.environment;
+    out->texture = h.texture;
+    out->rgb = h.rgb.empty() ? nullptr : h.rgb.data();
+    out->width = h.width;
+    out->height = h.height;
+    std::memcpy(out->intensity, h.intensity, sizeof h.intensity);
+    std::memcpy(out->rotation, h.rotation, sizeof h.rotation);
+    if (has_distribution) *has_distribution = sc.committed && sc.flat.env.has_distribution ? 1 : 0;
+    return RT_OK;
+}
+
+int rt_scene_dump_environment_cdf(rt_scene *s, int *width_out, int max_entries, double *marginal_out, double *conditional_out)
+{
+    if (!s || !S(s)->committed) return -fail(RT_ERR_STATE, "rt_scene_dump_environment_cdf: scene not committed");
+    const FlatScene &f = S(s)->flat;
+    if (width_out) *width_out = 0;
+    if (!(f.flags & SCENE_ENVIRONMENT) || !f.env.has_distribution) return 0;
+    if (width_out) *width_out = f.env.width;
+    if ((int64_t)max_entries >= (int64_t)f.env.width * f.env.height) {
+        if (marginal_out) std::memcpy(marginal_out, f.env_mcdf.data(), f.env_mcdf.size() * sizeof(double));
+        if (conditional_out) std::memcpy(conditional_out, f.env_ccdf.data(), f.env_ccdf.size() * sizeof(double));
+    }
+    return f.env.height;
+}
+
+int rt_pfm_load(const char *path, float **rgb_out, int *width, int *height)
+{
+    if (!path || !rgb_out || !width || !height) return fail(RT_ERR_INVALID, "rt_pfm_load: null argument");
+    *rgb_out = nullptr;
+    FILE *fp = std::fopen(path, "rb");
+    if (!fp) return fail(RT_ERR_INVALID, std::string("rt_pfm_load: cannot open ") + path);
+    char magic[3] = {0, 0, 0};
+    int w = 0, h = 0;
+    double scale = 0.0;
+    // "PF", the two sizes and the scale, separated by white space; exactly one white-space byte before the data
+    const bool head = std::fscanf(fp, "%2s %d %d %lf", magic, &w, &h, &scale) == 4 && std::strcmp(magic, "PF") == 0 && std::isspace(std::fgetc(fp));
+    if (!head || w < 1 || h < 1 || (int64_t)w * h > ((int64_t)1 << 28) || !std::isfinite(scale) || scale == 0.0) {
+        std::fclose(fp);
+        return fail(RT_ERR_INVALID, std::string("rt_pfm_load: not a colour PFM file: ") + path);
+    }
+    const size_t row = (size_t)w * 3;
+    float *rgb = static_cast<float *>(std::malloc(row * (size_t)h * sizeof(float)));
+    if (!rgb) {
+        std::fclose(fp);
+        return fail(RT_ERR_INVALID, "rt_pfm_load: out of memory");
+    }
+    const bool little = scale < 0.0;
+    const float magnitude = (float)std::fabs(scale);
+    bool ok = true;
+    for (int j = h - 1; j >= 0 && ok; j--) {  // the file's first row is the bottom one
+        float *dst = rgb + (size_t)j * row;
+        ok = std::fread(dst, sizeof(float), row, fp) == row;
+        for (size_t k = 0; k < row && ok; k++) {
+            unsigned char b[4];
+            std::memcpy(b, &dst[k], 4);
+            const uint32_t bits = little ? (uint32_t)b[0] | (uint32_t)b[1] << 8 | (uint32_t)b[2] << 16 | (uint32_t)b[3] << 24
+                                         : (uint32_t)b[3] | (uint32_t)b[2] << 8 | (uint32_t)b[1] << 16 | (uint32_t)b[0] << 24;
+            float x;
+            std::memcpy(&x, &bits, 4);
+            dst[k] = magnitude == 1.0f ? x : magnitude * x;
+        }
+    }
+    std::fclose(fp);
+    if (!ok) {
+        std::free(rgb);
+        return fail(RT_ERR_INVALID, std::string("rt_pfm_load: file ends before its last row: ") + path);
+    }
+    *rgb_out = rgb;
+    *width = w;
+    *height = h;
+    return RT_OK;
+}
+void rt_pfm_free(float *rgb) { std::free(rgb); }
 
 int rt_scene_commit(rt_scene *s)
 {

@@ -131,6 +131,20 @@ struct FlatScene {
     // with 16-byte loads).
     std::vector<LightRow> lights;
     std::vector<double> light_cdf[2];
+    // SCENE_ENVIRONMENT: the record as it is uploaded behind the camera's, its three pointers null (device_scene.cpp sets them), the
+    // float image, and the importance sampler's tables (scene_builder.cpp build_environment; empty: no distribution)
+    EnvRec env{};
+    std::vector<float> env_rgb;
+    std::vector<double> env_mcdf, env_ccdf;
+};
+
+// The environment exactly as rt_scene_set_environment took it (rt_scene_get_environment hands it back).
+struct HostEnvironment {
+    uint32_t texture = 0;  // handle (1-based), or 0: the float image
+    std::vector<float> rgb;
+    int32_t width = 0, height = 0;
+    double intensity[3] = {1.0, 1.0, 1.0};
+    double rotation[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0};
 };
 
 struct DeviceTables;  // device_scene.cpp
@@ -148,6 +162,8 @@ struct SceneImpl {
     uint32_t world = 0;
     bool has_camera = false;
     CameraRec camera{};
+    bool has_environment = false;
+    HostEnvironment environment;
     bool committed = false;
     FlatScene flat;
     std::vector<DeviceTables *> device;  // one per device ordinal, lazily

@@ -60,6 +60,36 @@ void random_spheres(Scene &w, Rng &rnd, std::vector<Hittable> &list, View &view,
     view.shutter1 = 1.0;
 }
 
+// Scene 15's sky: a linear float image, top row first, no asset needed.  Above the horizon a vertical gradient from a pale horizon
+// to a blue zenith, below it a dim grey; and a small, very bright sun disc -- every texel whose centre direction lies within
+// kSunRadius of the sun's -- 38 degrees above the horizon.  The texel centre (i, j) looks along the direction of
+// u = (i + 0.5) / W, v = 1 - (j + 0.5) / H as the environment's lookup maps it (rtow.h rt_scene_set_environment).
+constexpr int kSkyWidth = 256, kSkyHeight = 128;
+std::vector<float> scene15_sky()
+{
+    const double pi = 3.1415926535897932385, kSunRadius = 0.03, kSunValue = 4000.0;
+    const double se = 38.0 * pi / 180.0, sa = 200.0 * pi / 180.0;
+    const double sun[3] = {std::cos(se) * std::cos(sa), std::sin(se), std::cos(se) * std::sin(sa)};
+    std::vector<float> sky((size_t)kSkyWidth * kSkyHeight * 3);
+    for (int j = 0; j < kSkyHeight; j++)
+        for (int i = 0; i < kSkyWidth; i++) {
+            const double u = (i + 0.5) / kSkyWidth, v = 1.0 - (j + 0.5) / kSkyHeight;
+            const double theta = pi * v, phi = 2.0 * pi * u - pi;
+            const double e[3] = {std::sin(theta) * std::cos(phi), -std::cos(theta), -(std::sin(theta) * std::sin(phi))};
+            double c[3] = {0.12, 0.11, 0.10};
+            if (e[1] > 0.0) {
+                const double t = e[1];  // 0 at the horizon, 1 at the zenith
+                c[0] = (1.0 - t) * 0.95 + t * 0.25;
+                c[1] = (1.0 - t) * 0.95 + t * 0.45;
+                c[2] = (1.0 - t) * 1.00 + t * 0.95;
+            }
+            const double cs = e[0] * sun[0] + e[1] * sun[1] + e[2] * sun[2];
+            if (std::acos(cs > 1.0 ? 1.0 : cs) < kSunRadius) c[0] = c[1] = c[2] = kSunValue;
+            for (int k = 0; k < 3; k++) sky[((size_t)j * kSkyWidth + i) * 3 + k] = (float)c[k];
+        }
+    return sky;
+}
+
 struct CornellMaterials {
     Material red, white, green, light;
 };
@@ -130,8 +160,10 @@ void icosphere(int levels, double radius, std::vector<Point3> &vertices, std::ve
 
 } // namespace
 
-extern "C" int rt_scene_build_builtin(rt_scene *s, int scene_id, int world_kind, int image_width, int image_height,
-                                      uint64_t seed, const unsigned char *earth_rgb, int earth_w, int earth_h)
+// Scene 15, the sky demonstration, is built by rt_scene_build_sky_demo alone: rt_scene_build_builtin keeps the ids it had.
+constexpr int kSkyDemoScene = 15;
+static int build_scene(rt_scene *s, int scene_id, int world_kind, int image_width, int image_height, uint64_t seed,
+                       const unsigned char *earth_rgb, int earth_w, int earth_h)
 {
     if (!s || image_width <= 0 || image_height <= 0) return rtow::fail(RT_ERR_INVALID, "rt_scene_build_builtin: bad arguments");
     if (world_kind != 0 && world_kind != 1) return rtow::fail(RT_ERR_INVALID, "rt_scene_build_builtin: world_kind must be 0 (bvh) or 1 (list)");
@@ -334,6 +366,13 @@ extern "C" int rt_scene_build_builtin(rt_scene *s, int scene_id, int world_kind,
             cornell_view(view);
             break;
         }
+        case kSkyDemoScene: {  // the static random spheres (scene 11) on their ground under a computed sky; the background is black, so a bug shows
+            random_spheres(w, rnd, list, view, true);
+            view.shutter1 = 0.0;
+            view.background = Color(0.0, 0.0, 0.0);
+            w.Environment(scene15_sky().data(), kSkyWidth, kSkyHeight);
+            break;
+        }
         default:
             return rtow::fail(RT_ERR_INVALID, "rt_scene_build_builtin: scene_id must be 0..14");
         }
@@ -348,4 +387,16 @@ extern "C" int rt_scene_build_builtin(rt_scene *s, int scene_id, int world_kind,
         return rtow::fail(RT_ERR_INVALID, std::string("rt_scene_build_builtin: ") + e.what());
     }
     return RT_OK;
+}
+
+extern "C" int rt_scene_build_builtin(rt_scene *s, int scene_id, int world_kind, int image_width, int image_height,
+                                      uint64_t seed, const unsigned char *earth_rgb, int earth_w, int earth_h)
+{
+    if (scene_id == kSkyDemoScene) return rtow::fail(RT_ERR_INVALID, "rt_scene_build_builtin: scene_id must be 0..14");
+    return build_scene(s, scene_id, world_kind, image_width, image_height, seed, earth_rgb, earth_w, earth_h);
+}
+
+extern "C" int rt_scene_build_sky_demo(rt_scene *s, int world_kind, int image_width, int image_height, uint64_t seed)
+{
+    return build_scene(s, kSkyDemoScene, world_kind, image_width, image_height, seed, nullptr, 0, 0);
 }
