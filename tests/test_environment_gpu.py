@@ -58,8 +58,8 @@ def open_scene(environment, lamp_texture=None):
     return s
 
 
-def emitted_along(scene, d, status=MISS):
-    out = scene.path_step(np.zeros_like(d), np.ascontiguousarray(d), want=("status", "emitted"))
+def emitted_along(scene, d, status=MISS, variant=0):
+    out = scene.path_step(np.zeros_like(d), np.ascontiguousarray(d), variant=variant, want=("status", "emitted"))
     assert np.all(out["status"] == status)
     return out["emitted"]
 
@@ -201,10 +201,10 @@ def route_world(name):
 
 
 @functools.lru_cache(maxsize=None)
-def routes_of(name):
+def routes_of(name, variant=0):
     scene = route_world(name)
     film = rt.Film(W, H)
-    st = film.render(scene, SPP, max_depth=DEPTH, seed=SEED, variant=0)
+    st = film.render(scene, SPP, max_depth=DEPTH, seed=SEED, variant=variant)
     return scene, film.download(), st
 
 

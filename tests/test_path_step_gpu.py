@@ -65,7 +65,7 @@ def step_of(name, variant=0):
 
 
 # ---- 1. the fold is the radiance ----
-def fold(scene, o, d, tm, states, max_depth, seen):
+def fold(scene, o, d, tm, states, max_depth, seen, variant=0):
     """One sample of RayColor by steps, as include/rtow.h states the fold: numpy float64, one operation a line, nothing fused.
     Returns (acc (n, 3), steps per ray (n,), the streams after the paths (n, 6)); the statuses and material kinds met go to `seen`."""
     n = len(o)
@@ -76,7 +76,7 @@ def fold(scene, o, d, tm, states, max_depth, seen):
     for _ in range(max_depth):
         if live.size == 0:
             break
-        out = scene.path_step(o, d, times=tm, rng_state=states, variant=0,
+        out = scene.path_step(o, d, times=tm, rng_state=states, variant=variant,
                               want=("status", "emitted", "attenuation", "origin", "direction", "time", "material", "rng_state"))
         status = out["status"]
         seen["status"].update(np.unique(status).tolist())
