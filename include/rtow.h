@@ -436,6 +436,21 @@ RTOW_API int rt_scene_set_environment(rt_scene *s, const rt_environment *env);
  * end); without an environment *out is all zeros and the call returns RT_OK.  *has_distribution (may be NULL): 1 where the
  * committed scene holds the importance sampler's tables (below), else 0 -- before commit always 0. */
 RTOW_API int rt_scene_get_environment(rt_scene *s, rt_environment *out, int *has_distribution);
+/* The environment as a light of the direct estimators (rt_scene_path_advance_direct states what changes; nothing else does: plain
+ * renders, launch plans, rt_scene_dump_lights and rt_scene_get_info of such a scene are what they were).  `chance` is the share of
+ * the light samples that go to the environment where the scene also has lamps.  A construction call like
+ * rt_scene_set_environment: it takes effect with the next rt_scene_commit, and the scene counts as not committed behind it.  The
+ * default is 0.  It is independent of rt_scene_set_environment: it survives a change of environment, and it has no effect while
+ * the committed scene has no environment.  At commit the effective shares c_e (environment) and c_l (light table) are fixed:
+ *   no environment, or chance == 0:            c_e = 0,       c_l = 1,                 flag bit 2048 clear
+ *   environment, chance > 0, no lights:        c_e = 1,       c_l = 0,                 flag bit 2048 set
+ *   environment, chance > 0, lights:           c_e = chance,  c_l = fl(1 - chance),    flag bit 2048 set
+ * Refusals, in this order: RT_ERR_INVALID for a NULL scene; RT_ERR_STATE while a render of the scene is in flight;
+ * RT_ERR_INVALID for a chance that is NaN, below 0 or above 1. */
+#define RT_SCENE_FLAG_ENVIRONMENT_LIGHT 2048u
+RTOW_API int rt_scene_set_environment_light(rt_scene *s, double chance);
+/* *chance_out: as set; *effective_out: c_e of the committed scene, 0 before commit.  Either may be NULL. */
+RTOW_API int rt_scene_get_environment_light(rt_scene *s, double *chance_out, double *effective_out);
 /* The importance sampler's tables, built by rt_scene_commit on the host in fp64, for an environment that is an image -- the float
  * image, or a texture that is itself an 8-bit image (W x H its own size; a checker of images is not one).  Texel (i, j), j counted
  * from the top row, has the weight w = max over the channels c of (intensity_c * value_c) times sin(pi * (j + 0.5) / H), value_c
@@ -1125,8 +1140,9 @@ RTOW_API int rt_scene_light_pdf(rt_scene *s, const rt_light_params *params, cons
 RTOW_API void rt_light_abi_sizes(uint32_t out8[8]);
 
 /* ---- environment sampling: draw directions by the brightness of the map, and the density of doing so ----
- * The environment (rt_scene_set_environment) is no row of the light table, and direct = "mis" does not sample it: a path that
- * misses adds it with weight 1, as it adds the background.  These two calls are the building block for doing better: one lane a
+ * The environment (rt_scene_set_environment) is no row of the light table, and direct = "mis" samples it only where the scene
+ * says so (rt_scene_set_environment_light; rt_scene_path_advance_direct states the estimator): otherwise a path that misses adds
+ * it with weight 1, as it adds the background.  These two calls are what that estimator is made of, for a caller's own: one lane a
  * point, the light calls' structs where the fields mean the same.  points->point is required as there (a shadow ray starts at
  * it; the sample itself does not depend on it), ->time is not read.  RT_ERR_STATE for a scene without an environment; the other
  * refusals are the light calls', without the strategy.
@@ -1203,13 +1219,42 @@ RTOW_API void rt_environment_abi_sizes(uint32_t out4[4]);
  *       the survivor's stream is the one after the last draw, and its density
  *         q' = scatter_pdf(m, n, u), u = (1 / sqrt((d'.x * d'.x + d'.y * d'.y) + d'.z * d'.z)) * d'
  *       with the closed form stated for rt_scene_sample_lights' scatter_pdf.
- *     In every other case (metal, glass, a scene without lights, sample == 0) nothing is drawn and q' = 0.
+ *     In every other case (metal, glass, a scene without lights -- and without flag bit 2048, below --, sample == 0) nothing is drawn and q' = 0.
  * A row either ends or scatters: a call makes at most one addition per id, so distinct live ids still need no atomics.
  * out->scatter_pdf, row j: q' of survivor j.
  * The estimator: fresh rays start with q = 0 (rays->scatter_pdf NULL); sample = 1 in every call but the last of max_depth calls;
  * whoever is alive after the last call is dropped.  The radiance so folded has the expectation of rt_scene_radiance with samples
  * = 1 and the same max_depth: a light sample at bounce b stands for the lamp that scattering would find at bounce b + 1, which is
  * why the last call takes none.
+ * A scene without lights and without flag bit 2048: rt_scene_path_advance to the bit.
+ *
+ * A scene whose environment is a light (RT_SCENE_FLAG_ENVIRONMENT_LIGHT, shares c_e and c_l: rt_scene_set_environment_light).
+ * Everything above holds; a scene without the bit is the call above to the bit; with the bit only this differs:
+ *   who samples: a row that scatters from a Lambertian or isotropic hit with sample == 1 takes a sample where the scene has
+ *     lights OR the bit; q' is the closed form wherever a sample was drawn, valid or not.
+ *   the pick: where c_e < 1 (so lights exist), x = (double) curand_uniform(R1), and the environment is picked where x <= c_e;
+ *     where c_e == 1 nothing is drawn for the pick.
+ *   the light table picked: the sample of rt_scene_sample_lights exactly as above, from the stream behind the pick's draw;
+ *     C = (s / (c_l * pdf)) * emitted, all 0 where s == 0.  Where C is not all zero: p = c_l * light_pdf(o', dir, tm),
+ *     w = p / (p + s), 0 where p + s == 0, L = (thr' * C) * w; the shadow ray as above.
+ *   the environment picked: the sample of rt_scene_sample_environment for the point o', normal n, material m, from the stream
+ *     behind the pick's draw -- four draws, valid or not --: dir, pdf, emitted, s.  C = (s / (c_e * pdf)) * emitted, all 0 for an
+ *     invalid sample or s == 0.  Where C is not all zero: p = c_e * pdf, w = p / (p + s), L = (thr' * C) * w; the shadow ray is
+ *     (o', dir, tm) over (0.001, fmin(inf * (1 - 2^-20), DBL_MAX)), the expression above with distance = +inf, searched as above
+ *     (a medium draws from the path's stream as above); L is added where nothing is met.  No loop over the light table runs.
+ *   status 0 (a miss) with q > 0: p = c_e * environment_pdf(d) for the incoming direction as given (rt_scene_environment_pdf's
+ *     value: 0 where it is not positive and finite), w = q / (q + p), radiance[id] = radiance[id] + (thr * E) * w.  With q == 0,
+ *     w = 1 as above.
+ *   status 1 on a lamp with q > 0: p = c_l * light_pdf(...), w = q / (q + p); with c_l == 0, p = 0 and w = q / q = 1 (the table is
+ *     then not consulted).
+ * The weights are per emitter, not one mixture c_e p_e + c_l p_l everywhere: an environment sample along a direction that meets
+ * a lamp is always occluded, so environment sampling is no technique for the lamp's light, and table sampling is none for the
+ * sky's.  Under the one mixture the weights of the techniques that can produce a contribution would not sum to 1 -- at chance 1 in
+ * a scene with lamps a visible bias.  So the sky's light is weighted between scattering and environment sampling, a lamp's
+ * between scattering and table sampling, each technique's density scaled by the share of the samples it gets.
+ * With the bit, max_depth == 1 (one call, sample = 0) is still rt_scene_radiance to the bit; the expectation is
+ * rt_scene_radiance's for every max_depth.  stats->shadow_rays / shadow_reached count both kinds of shadow ray.
+ *
  * Aliasing as for rt_scene_path_advance, and out->scatter_pdf may not be rays->scatter_pdf.
  * Refusals, all before the device is touched, in this order: those of rt_scene_path_advance up to the variant; a strategy other
  * than 0 / 1; a sample other than 0 / 1; the rest of rt_scene_path_advance's (the aliased pairs now include scatter_pdf; the
@@ -1295,7 +1340,7 @@ RTOW_API void rt_path_advance_direct_abi_sizes(uint32_t out4[4]);
  * Outputs as rt_scene_radiance: radiance = the mean as that call forms it; path_rays counts the path searches only (the shadow
  * searches are in the statistics); rng_state is the stream after the last draw, and may alias the input.
  * With samples == 1 the radiance is what max_depth calls of rt_scene_path_advance_direct fold for the ray, to the bit in the strict
- * build.  max_depth == 0: black, nothing searched, nothing drawn.  max_depth == 1, or a scene without lights: rt_scene_radiance to
+ * build.  max_depth == 0: black, nothing searched, nothing drawn.  max_depth == 1, or a scene without lights and without flag bit 2048: rt_scene_radiance to
  * the bit in the strict build.  The expectation is rt_scene_radiance's for every max_depth.
  * Both calls return when the results are there.  Refusals, all before the device is touched: rt_scene_radiance's, in its order,
  * then a strategy other than 0 / 1.  count == 0 returns RT_OK without a launch.  Termination as for rt_scene_radiance, with at
@@ -1344,7 +1389,7 @@ RTOW_API void rt_radiance_direct_abi_sizes(uint32_t out4[4]);
  * the sample's y^2 after each sample, the rule is looked at with the pixel's total n, a pixel that stops keeps its own n and is
  * marked, and a marked pixel is never touched by a later launch of the frame.  In the strict build every operation is one IEEE-754
  * double operation in that order; the fast build may fuse (never inside the rule).
- * Consequences: without lights, or at max_depth == 1, the frame is rt_render_launch's bit for bit in the strict build;
+ * Consequences: without lights and without flag bit 2048, or at max_depth == 1, the frame is rt_render_launch's bit for bit in the strict build;
  * max_depth == 0 gives a black frame with only the camera's draws taken; k launches of S with KEEP_RNG_STATE | ACCUMULATE are one
  * launch of kS; a frame may mix plain and direct launches (the sums and streams are the same objects, both estimators have the
  * same expectation; the changed-adaptive-setting rule applies as it does to rt_render_launch).  No frame depends on which lane

@@ -201,6 +201,16 @@ public:
         set_environment(0, rgb, width, height, intensity, rotation);
     }
     void NoEnvironment() { check(rt_scene_set_environment(s_, nullptr)); }
+    // The environment as a light of the direct estimators (rtow.h rt_scene_set_environment_light): the share of the light samples
+    // that go to it where the scene also has lamps.  Takes effect with the next Commit.
+    void EnvironmentLight(double chance = 0.5) { check(rt_scene_set_environment_light(s_, chance)); }
+    // c_e of the committed scene (0 before Commit, without an environment and at chance 0); *chance: as set
+    double EnvironmentLightShare(double *chance = nullptr)
+    {
+        double effective = 0.0;
+        check(rt_scene_get_environment_light(s_, chance, &effective));
+        return effective;
+    }
     void Commit() { check(rt_scene_commit(s_)); }
 
     // Ray queries on host arrays (rtow.h "ray queries"): origins and directions hold 3 doubles per ray; an output vector is

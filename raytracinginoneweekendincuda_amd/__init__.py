@@ -36,7 +36,7 @@ from .api import (  # noqa: F401
     FLAG_ROW_MAJOR_TILES,
     FLAG_ALWAYS_WALK, FLAG_NO_PIXEL_CLASSES, FLAG_REFERENCE_TREE, FLAG_EXACT_SCAN, FLAG_ACCELERATE_LISTS, FLAG_COOP_SINGLE, FLAG_FILTER_FP64,
     FLAG_NO_PRIMARY_LISTS, FLAG_NO_SCAN_WINDOWS,
-    SCENE_PLAIN_QUADS, SCENE_REFERENCE_TREE_ONLY, SCENE_FLAG_ENVIRONMENT,
+    SCENE_PLAIN_QUADS, SCENE_REFERENCE_TREE_ONLY, SCENE_FLAG_ENVIRONMENT, SCENE_FLAG_ENVIRONMENT_LIGHT,
     load_pfm, sky_demo_scene,
 )
 

@@ -386,6 +386,8 @@ SIGNATURES = {
     "rt_scene_flags": (C.c_uint32, [P]),
     "rt_scene_set_environment": (I, [P, C.POINTER(Environment)]),
     "rt_scene_get_environment": (I, [P, C.POINTER(Environment), C.POINTER(I)]),
+    "rt_scene_set_environment_light": (I, [P, C.c_double]),
+    "rt_scene_get_environment_light": (I, [P, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "rt_scene_dump_environment_cdf": (I, [P, C.POINTER(I), I, D3, D3]),
     "rt_pfm_load": (I, [C.c_char_p, C.POINTER(P), C.POINTER(I), C.POINTER(I)]),
     "rt_pfm_free": (None, [P]),

@@ -47,6 +47,7 @@ FLAG_NO_PIXEL_CLASSES = 64  # sphere-list worlds: one launch for all pixels (no 
 SCENE_PLAIN_QUADS = 1           # every quad takes the general test; boxes stay lists of six quads
 SCENE_REFERENCE_TREE_ONLY = 2   # no library tree for primitive worlds
 SCENE_FLAG_ENVIRONMENT = 1024   # Scene.flags(): the committed scene has an environment (rtow.h RT_SCENE_FLAG_ENVIRONMENT)
+SCENE_FLAG_ENVIRONMENT_LIGHT = 2048  # ... and direct="mis" samples it as a light (rtow.h RT_SCENE_FLAG_ENVIRONMENT_LIGHT)
 
 
 # Film.denoise / denoise_frame defaults (DESIGN.md section 5 has the frames they were chosen on)
@@ -356,6 +357,20 @@ class Scene:
             image = np.ctypeslib.as_array(C.cast(env.rgb, C.POINTER(C.c_float)), shape=(env.height, env.width, 3)).copy()
         return {"texture": env.texture or None, "image": image, "intensity": np.array(env.intensity, dtype=np.float64),
                 "rotation": np.array(env.rotation, dtype=np.float64).reshape(3, 3), "has_distribution": bool(has.value)}
+
+    def EnvironmentLight(self, chance=0.5):
+        """Make the environment a light of ``direct="mis"`` (rt_scene_set_environment_light; rtow.h states the estimator under
+        rt_scene_path_advance_direct): a light sample goes to the environment with this chance and to the light table otherwise;
+        without lamps every sample goes to the environment.  0 switches it off.  Independent of ``Environment``, without effect
+        while the scene has none.  Takes effect with the next ``Commit``; plain renders are not changed by it."""
+        _check(lib().rt_scene_set_environment_light(self._p, float(chance)))
+
+    def environment_light(self):
+        """``{"chance": as set, "effective": the share c_e of the committed scene}`` (rt_scene_get_environment_light); effective is
+        0 before ``Commit``, without an environment and at chance 0, and 1 in a scene without lamps."""
+        chance, effective = C.c_double(), C.c_double()
+        _check(lib().rt_scene_get_environment_light(self._p, C.byref(chance), C.byref(effective)))
+        return {"chance": chance.value, "effective": effective.value}
 
     def environment_cdf(self):
         """The importance sampler's tables of the committed scene (rt_scene_dump_environment_cdf): ``(marginal (H,), conditional

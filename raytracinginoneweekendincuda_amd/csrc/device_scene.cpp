@@ -2191,7 +2191,8 @@ int rt_scene_path_advance_direct_device(rt_scene *scene, const rt_path_advance_d
     da.node_leaf_pos = dt.node_leaf_pos;
     ga.scatter_pdf_from = da.scatter_pdf_stage;
     ga.scatter_pdf_to = out->scatter_pdf;
-    const bool shadows = da.n_lights != 0 && da.sample != 0;  // else launch 1 leaves no row pending: launch 2 is not enqueued
+    // else launch 1 leaves no row pending: launch 2 is not enqueued.  (A scene whose environment is a light samples it without a table.)
+    const bool shadows = (da.n_lights != 0 || (dt.scene.flags & SCENE_ENVIRONMENT_LIGHT) != 0) && da.sample != 0;
     hipStream_t stream = (hipStream_t)p->stream;
     const auto four = [&](QueryKernelInfo *info) -> hipError_t {  // the call's kernels, in the stream's order (or the registers of the first two)
         hipError_t e = kBuilds[p->variant].advance_direct(dt.scene, da, stream, info);

@@ -276,6 +276,10 @@ struct EnvRec {
     const float *rgb;       // width x height x 3, top row first
     const double *mcdf;     // cumulative chance of rows 0 .. j, rows counted from the top; entry height - 1 is 1.0
     const double *ccdf;     // row j: cumulative chance of columns 0 .. i within it; entry width - 1 is 1.0
+    // SCENE_ENVIRONMENT_LIGHT (include/rtow.h rt_scene_set_environment_light): the shares c_e and c_l with which a light sample of
+    // the direct estimators picks the environment and the light table, fixed at commit; (0, 1) without the bit.  Behind every
+    // field the other kernels read, whose offsets stay as they were.
+    double light_share, table_share;
 };
 static_assert(sizeof(EnvRec) % 8 == 0, "follows CameraRec, 27 doubles");
 // Rows of the marginal table a workgroup of env_sample_kernel stages in LDS: 2048 doubles = 16 KB, so eight workgroups of four
@@ -362,6 +366,7 @@ enum : uint32_t {
     SCENE_AFFINE = 256u,          // some chain holds a general affine step (XF_AFFINE, XF_MOVING): served by the units compiled with RT_AFFINE (render.hip RT_TO_AFFINE)
     SCENE_MOVING = 512u,          // some chain holds a moving step (XF_MOVING; SCENE_AFFINE is set too): served by the second pass of those units (render.hip RT_MOVING)
     SCENE_ENVIRONMENT = 1024u,    // an EnvRec follows the camera's record: a miss reads it, not CameraRec::bg; rendered by the RICH instantiations (launch_plan.cpp choose_kernel)
+    SCENE_ENVIRONMENT_LIGHT = 2048u,  // the direct estimators sample the environment as a light (EnvRec::light_share > 0; SCENE_ENVIRONMENT is set too): their launchers alone read it, no plan or kernel choice does
 };
 
 } // namespace rtow

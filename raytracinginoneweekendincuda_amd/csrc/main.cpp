@@ -205,6 +205,8 @@ int main(int argc, char **argv)
     std::string out = "output.ppm";
     std::string environment_path;  // --environment: a .pfm float image or a JPEG, the sky of any scene
     double environment_intensity = 1.0, environment_rotate_y = 0.0;
+    double environment_light = 0.0;  // --environment-light C: --direct mis samples the sky as a light with chance C (rt_scene_set_environment_light)
+    bool environment_light_given = false;
     std::string earth_path;      // decoded 8-bit sRGB pixels of the earth texture (P6): converted like RtwImage::Load does
     bool earth_is_bytes = false; // --earth-bytes: the file already holds what RtwImage::Load hands to ImageTexture
     // adaptive sampling (--noise): a pixel stops once its noise is below the threshold, --spp is then the most it takes
@@ -305,6 +307,15 @@ int main(int argc, char **argv)
             }
             direct_mis = true;
         }
+        else if (const char *v = val("--environment-light")) {  // (before the prefix match of --environment)
+            char *end = nullptr;
+            environment_light = std::strtod(v, &end);
+            if (end == v || *end != '\0') {
+                std::fprintf(stderr, "--environment-light needs a number in [0, 1], not '%s'\n", v);
+                return 2;
+            }
+            environment_light_given = true;
+        }
         else if (const char *v = val("--environment-intensity")) environment_intensity = std::atof(v);
         else if (const char *v = val("--environment-rotate-y")) environment_rotate_y = std::atof(v);
         else if (const char *v = val("--environment")) environment_path = v;
@@ -320,7 +331,7 @@ int main(int argc, char **argv)
                          "            [--noise T [--min-spp N] [--check-every K] [--samples-map file.pgm]]\n"
                          "            [--denoise [--denoise-iterations N] [--denoise-sigmas c,a,n,z] [--raw-output file.ppm]]\n"
                          "            [--aov-prefix P] [--feature-samples N] [--pick i,j] [--radiance-at i,j] [--trace-at i,j] [--lights] [--direct mis]\n"
-                         "            [--environment sky.pfm|sky.jpg] [--environment-intensity X] [--environment-rotate-y DEG]\n"
+                         "            [--environment sky.pfm|sky.jpg] [--environment-intensity X] [--environment-rotate-y DEG] [--environment-light C]\n"
                          "  --environment  what a ray that leaves the scene sees, in place of the scene's background colour: a .pfm file is a linear\n"
                          "                 float image (an HDR panorama, top row = up), any other file is read as --earth reads a JPEG, as an 8-bit\n"
                          "                 image texture; --environment-intensity multiplies it, --environment-rotate-y turns it about the vertical.\n"
@@ -331,6 +342,8 @@ int main(int argc, char **argv)
                          "                 leaf, material kind, t, point, normal, albedo -- at the shutter's opening, over [0.001, inf)\n"
                          "  --radiance-at  render nothing: path-trace the same ray, --spp samples (default 1) of --depth bounces from the pixel's stream,\n"
                          "                 and print the linear radiance, the rays traced and the kernel's time\n"
+                         "  --environment-light C  with --direct mis: the environment is a light too -- a light sample goes to it with chance C, to the\n"
+                         "                 lamps otherwise (to it alone in a scene without lamps); C in [0, 1], 0 = off (rt_scene_set_environment_light)\n"
                          "  --direct mis   every sample takes a light sample at each diffuse hit and weights it against the lamps scattering finds.\n"
                          "                 With --radiance-at (rt_scene_radiance_direct): the line then ends with the shadow rays cast and those that\n"
                          "                 reached their lamp.  Without it the frame is rendered that way (rt_render_launch_direct, lights picked by area\n"
@@ -389,6 +402,14 @@ int main(int argc, char **argv)
     if (radiance_at && spp < 0) spp = 1;
     if (direct_mis && (trace_at || list_lights || (pick && !radiance_at))) {
         std::fprintf(stderr, "--direct goes with --radiance-at, or with a frame: not with --pick, --trace-at or --lights\n");
+        return 2;
+    }
+    if (environment_light_given && !direct_mis) {
+        std::fprintf(stderr, "--environment-light goes with --direct mis: no other estimator samples the sky\n");
+        return 2;
+    }
+    if (environment_light_given && !(environment_light >= 0.0 && environment_light <= 1.0)) {
+        std::fprintf(stderr, "--environment-light needs a chance in [0, 1]\n");
         return 2;
     }
     const bool direct_frame = direct_mis && !pick;  // the frame itself by the MIS estimator (rt_render_launch_direct)
@@ -482,6 +503,14 @@ int main(int argc, char **argv)
         const int rc = rt_scene_set_environment(scene, &env);  // (copies the image)
         rt_pfm_free(pfm);
         if (rc != RT_OK || rt_scene_commit(scene) != RT_OK) return die("environment");
+    }
+
+    if (environment_light_given) {  // --environment-light C: the sky as a light of --direct mis
+        if (!(rt_scene_flags(scene) & RT_SCENE_FLAG_ENVIRONMENT)) {
+            std::fprintf(stderr, "--environment-light: the scene has no environment (--environment FILE, or --scene 15)\n");
+            return 1;
+        }
+        if (rt_scene_set_environment_light(scene, environment_light) != RT_OK || rt_scene_commit(scene) != RT_OK) return die("environment light");
     }
 
     if (list_lights) {  // host only: the table as rt_scene_upload would copy it

@@ -5519,15 +5519,113 @@ DEV Vec light_emitted(const DeviceScene &sc, const LightRow &L, Vec S, Vec centr
     return kind == MAT_ISOTROPIC ? 1.0 / (4.0 * kLightPi) : 0.0;
 }
 
+// The environment's importance sampler (rt_scene_sample_environment, rt_scene_environment_pdf; the comment above env_sample_kernel
+// says what the tables are): here because the three path kernels sample the environment too, where the scene makes it a light.
+// STAGED: the caller holds the workgroup's copy of the first kEnvLdsRows entries
+template <bool STAGED>
+DEV double env_mcdf(const RT_CONST EnvRec *env, const double *lds, uint32_t j)
+{
+    if constexpr (STAGED) {
+        if (j < kEnvLdsRows) return lds[j];
+    }
+    return env->mcdf[j];
+}
+// the density of the direction whose environment coordinates are e, (u, v); `texel`: j * width + i of its texel, -1 without tables
+template <bool STAGED>
+DEV double environment_density(const RT_CONST EnvRec *env, const double *lds, Vec e, double u, double v, int32_t &texel)
+{
+    texel = -1;
+    if (!env->has_distribution) return 1.0 / (4.0 * kLightPi);
+    int i, j;
+    environment_texel(env->width, env->height, u, v, i, j);
+    texel = j * env->width + i;
+    const double pj = env_mcdf<STAGED>(env, lds, (uint32_t)j) - (j ? env_mcdf<STAGED>(env, lds, (uint32_t)j - 1u) : 0.0);
+    const double *row = env->ccdf + (size_t)j * (size_t)env->width;
+    const double pi = row[i] - (i ? row[i - 1] : 0.0);
+    return ((pj * pi) * ((double)env->width * (double)env->height)) / (((2.0 * kLightPi) * kLightPi) * sqrt(1.0 - e.y * e.y));
+}
+// the first min(height, kEnvLdsRows) entries of the marginal table into the workgroup's copy; every lane, then one barrier
+DEV void stage_environment(const RT_CONST EnvRec *env, double *mcdf_lds)
+{
+    if (env->has_distribution != 0) {
+        const double *src = env->mcdf;
+        const uint32_t n = min((uint32_t)env->height, kEnvLdsRows);
+        for (uint32_t i = threadIdx.x; i < n; i += 256u) mcdf_lds[i] = src[i];
+    }
+    __syncthreads();
+}
+// The sample of rt_scene_sample_environment from its four draws (include/rtow.h states it operation by operation): with tables,
+// xa bisects the marginal table for the row and xb that row's conditional table for the column, (xc, xd) place the direction
+// inside the texel; without, (xc, xd) place it on the sphere uniformly.  Then R^T e, and the density -- and, where asked for, the
+// value -- from that final direction through the environment's own lookup (environment_coords): the sample's pdf is
+// environment_pdf of its direction, and what a path along it adds at its miss.  `texel` is the one the bisections named.  Returns
+// validity; an invalid sample leaves dir (0, 0, 0), pdf 0 and emitted (0, 0, 0).  Termination: each bisection halves hi - lo.
+template <class T>
+DEV bool environment_sample(const DeviceScene &sc, const RT_CONST EnvRec *env, const double *mcdf_lds, double xa, double xb, double xc, double xd,
+                            bool want_emitted, Vec &dir, double &pdf, Vec &emitted, int32_t &texel)
+{
+    const uint32_t width = (uint32_t)env->width, height = (uint32_t)env->height;
+    Vec e;
+    texel = -1;
+    if (env->has_distribution != 0) {
+        uint32_t lo = 0, hi = height - 1u;
+        while (lo < hi) {  // the first row with mcdf >= xa (the last entry is 1.0 >= xa)
+            const uint32_t mid = (lo + hi) / 2u;
+            if (env_mcdf<true>(env, mcdf_lds, mid) >= xa) hi = mid;
+            else lo = mid + 1u;
+        }
+        const uint32_t j = lo;
+        const double *row = env->ccdf + (size_t)j * width;
+        lo = 0;
+        hi = width - 1u;
+        while (lo < hi) {
+            const uint32_t mid = (lo + hi) / 2u;
+            if (row[mid] >= xb) hi = mid;
+            else lo = mid + 1u;
+        }
+        const uint32_t i = lo;
+        texel = (int32_t)(j * width + i);
+        const double u = ((double)i + xc) / (double)width;
+        const double v = 1.0 - ((double)j + xd) / (double)height;
+        const double theta = kLightPi * v, phi = (2.0 * kLightPi) * u - kLightPi;
+        const double st = sin(theta);
+        e = mk(st * cos(phi), -cos(theta), -(st * sin(phi)));
+    } else {  // no tables: the sphere uniformly
+        const double y = 1.0 - 2.0 * xc;
+        const double st = sqrt(1.0 - y * y), phi = (2.0 * kLightPi) * xd - kLightPi;
+        e = mk(st * cos(phi), y, -(st * sin(phi)));
+    }
+    // R^T e, each row (a + b) + c
+    dir = mk((env->rot[0] * e.x + env->rot[3] * e.y) + env->rot[6] * e.z, (env->rot[1] * e.x + env->rot[4] * e.y) + env->rot[7] * e.z,
+             (env->rot[2] * e.x + env->rot[5] * e.y) + env->rot[8] * e.z);
+    // density and value from the direction itself, through the environment's own lookup
+    Vec el;
+    double u, v;
+    environment_coords(env, dir, el, u, v);
+    int32_t seen;
+    pdf = environment_density<true>(env, mcdf_lds, el, u, v, seen);
+    const bool valid = usable_density(pdf);
+    emitted = mk(0.0, 0.0, 0.0);
+    if (!valid) {
+        dir = mk(0.0, 0.0, 0.0);
+        pdf = 0.0;
+    }
+    if (valid && want_emitted) emitted = environment_lookup<T>(sc, env, el, u, v);
+    return valid;
+}
+
 // What a path that scattered from a Lambertian or isotropic hit (kind, normal) into `ray` does about the lights (include/rtow.h
 // rt_scene_path_advance_direct; the three path kernels): the three functions above for the point ray.o at the time ray.tm, drawn
 // from the path's stream; contribution = (scatter / pdf) * emitted.  Returns sampled, contribution != 0: then the sample waits to be
 // weighted behind the density loop, which is asked along it (along_o, along_d, along_tm), with light = next * contribution (next:
 // the path's throughput behind this bounce), other = its scatter density and `distance` where a shadow ray along it meets the lamp.
 // sent_next: the density with which the material sent the scattered ray where it goes, the closed form for its unit direction.
-template <class T>
+// SHARED (a scene whose environment is a light too): the table gets the share `share` = c_l of the samples, contribution =
+// (scatter / (share * pdf)) * emitted.
+template <class T, bool SHARED = false>
 DEV bool path_light_sample(const DeviceScene &sc, const LightArgs &la, const LightLds &lds, const Ray &ray, uint32_t kind, Vec normal, Vec next,
-                           Xorwow &rng, Vec &along_o, Vec &along_d, double &along_tm, Vec &light, double &other, double &distance, double &sent_next)
+                           Xorwow &rng, Vec &along_o, Vec &along_d, double &along_tm, Vec &light, double &other, double &distance, double &sent_next,
+                           double share = 1.0)
 {
     const Vec P = ray.o;
     const double tm = ray.tm;
@@ -5538,7 +5636,11 @@ DEV bool path_light_sample(const DeviceScene &sc, const LightArgs &la, const Lig
     if (light_sample(la, lds, P, tm, rng, row, L, dir, distance, pdf, S, centre, u, v)) {
         const Vec emitted = light_emitted<T>(sc, L, S, centre, u, v);
         scatter = scatter_density(kind, normal, dir);
-        if (scatter != 0.0) contribution = (scatter / pdf) * emitted;
+        if constexpr (SHARED) {
+            if (scatter != 0.0) contribution = (scatter / (share * pdf)) * emitted;
+        } else {
+            if (scatter != 0.0) contribution = (scatter / pdf) * emitted;
+        }
     }
     const bool sampled = contribution.x != 0.0 || contribution.y != 0.0 || contribution.z != 0.0;
     if (sampled) {
@@ -5551,6 +5653,85 @@ DEV bool path_light_sample(const DeviceScene &sc, const LightArgs &la, const Lig
     const Vec unit_next = (1 / sqrt((ray.d.x * ray.d.x + ray.d.y * ray.d.y) + ray.d.z * ray.d.z)) * ray.d;
     sent_next = scatter_density(kind, normal, unit_next);
     return sampled;
+}
+
+// The same where the pick fell on the environment (SCENE_ENVIRONMENT_LIGHT; include/rtow.h rt_scene_path_advance_direct): the sample
+// of rt_scene_sample_environment, four draws from the path's stream; contribution = (scatter / (share * pdf)) * emitted with share =
+// c_e.  The out-parameters are path_light_sample's, distance = +inf (the shadow ray runs to the end of the world), and `own` = share *
+// pdf: the density the sample is weighted with, which is this lane's alone -- no loop over the light table runs for it.
+template <class T>
+DEV bool path_environment_sample(const DeviceScene &sc, const RT_CONST EnvRec *env, const double *mcdf_lds, const Ray &ray, uint32_t kind, Vec normal,
+                                 Vec next, Xorwow &rng, Vec &along_o, Vec &along_d, double &along_tm, Vec &light, double &other, double &distance,
+                                 double &sent_next, double share, double &own)
+{
+    const double xa = (double)xorwow_uniform(rng);
+    const double xb = (double)xorwow_uniform(rng);
+    const double xc = (double)xorwow_uniform(rng);
+    const double xd = (double)xorwow_uniform(rng);
+    Vec dir, emitted, contribution = mk(0.0, 0.0, 0.0);
+    double pdf, scatter = 0.0;
+    int32_t texel;
+    if (environment_sample<T>(sc, env, mcdf_lds, xa, xb, xc, xd, true, dir, pdf, emitted, texel)) {
+        scatter = scatter_density(kind, normal, dir);
+        if (scatter != 0.0) contribution = (scatter / (share * pdf)) * emitted;
+    }
+    const bool sampled = contribution.x != 0.0 || contribution.y != 0.0 || contribution.z != 0.0;
+    if (sampled) {
+        along_o = ray.o;
+        along_d = dir;
+        along_tm = ray.tm;
+        light = next * contribution;
+        other = scatter;
+        distance = (double)INFINITY;
+        own = share * pdf;
+    }
+    const Vec unit_next = (1 / sqrt((ray.d.x * ray.d.x + ray.d.y * ray.d.y) + ray.d.z * ray.d.z)) * ray.d;
+    sent_next = scatter_density(kind, normal, unit_next);
+    return sampled;
+}
+// What the two ends of a path and the sample site of the three kernels share under SCENE_ENVIRONMENT_LIGHT.
+// the density with which an environment sample would have drawn the incoming direction of a path that ends in a miss: c_e *
+// rt_scene_environment_pdf's value, through environment_coords again (bounce() keeps its signature, the plain lane units their text)
+[[maybe_unused]] DEV double environment_end_density(const RT_CONST EnvRec *env, const double *mcdf_lds, Vec d)
+{
+    Vec e;
+    double u, v;
+    environment_coords(env, d, e, u, v);
+    int32_t texel;
+    const double pdf = environment_density<true>(env, mcdf_lds, e, u, v, texel);
+    return env->light_share * (usable_density(pdf) ? pdf : 0.0);
+}
+// The workgroup's copy of the marginal table for a path kernel compiled for such scenes (ENV), staged as env_sample_kernel stages
+// it: 16 KB beside the light rows.  Every lane comes here; the barrier is stage_environment's.  nullptr in the other instantiations,
+// which hold no such array.
+template <bool ENV>
+DEV const double *staged_environment(const DeviceScene &sc)
+{
+    if constexpr (ENV) {
+        __shared__ double mcdf_lds[kEnvLdsRows];
+        stage_environment(environment_of(sc.camera), mcdf_lds);
+        return mcdf_lds;
+    } else {
+        return nullptr;
+    }
+}
+// The sample site: the pick (one draw where the table has a share, none where c_e == 1), then one of the two samplers.  `table`:
+// the sample waits for the table's density (mixture_density); otherwise `own` holds its density.
+template <class T>
+DEV bool path_emitter_sample(const DeviceScene &sc, const LightArgs &la, const LightLds &lds, const RT_CONST EnvRec *env, const double *mcdf_lds,
+                             const Ray &ray, uint32_t kind, Vec normal, Vec next, Xorwow &rng, Vec &along_o, Vec &along_d, double &along_tm,
+                             Vec &light, double &other, double &distance, double &sent_next, bool &table, double &own)
+{
+    const double c_e = env->light_share;
+    bool sky = true;
+    if (c_e < 1.0 && la.n_lights != 0) {  // (c_e < 1 only where the table has rows: scene_builder.cpp build_environment)
+        const double x = (double)xorwow_uniform(rng);
+        sky = x <= c_e;
+    }
+    table = false;
+    if (sky) return path_environment_sample<T>(sc, env, mcdf_lds, ray, kind, normal, next, rng, along_o, along_d, along_tm, light, other, distance, sent_next, c_e, own);
+    table = path_light_sample<T, true>(sc, la, lds, ray, kind, normal, next, rng, along_o, along_d, along_tm, light, other, distance, sent_next, env->table_share);
+    return table;
 }
 
 // The mixture density of rt_scene_light_pdf along the ray (o, d) at the time tm: the sum over the table of each light's chance
@@ -5694,32 +5875,6 @@ __global__ __launch_bounds__(256) void light_pdf_kernel(DeviceScene sc, LightArg
 // environment's own lookup names for the direction: the sample's pdf is environment_pdf of its direction.  No lane returns early
 // (all meet at the barriers); the count of valid results reduces as the light kernels' does.
 // ------------------------------------------------------------------------------------------------
-namespace {
-// STAGED: the caller holds the workgroup's copy of the first kEnvLdsRows entries
-template <bool STAGED>
-DEV double env_mcdf(const RT_CONST EnvRec *env, const double *lds, uint32_t j)
-{
-    if constexpr (STAGED) {
-        if (j < kEnvLdsRows) return lds[j];
-    }
-    return env->mcdf[j];
-}
-// the density of the direction whose environment coordinates are e, (u, v); `texel`: j * width + i of its texel, -1 without tables
-template <bool STAGED>
-DEV double environment_density(const RT_CONST EnvRec *env, const double *lds, Vec e, double u, double v, int32_t &texel)
-{
-    texel = -1;
-    if (!env->has_distribution) return 1.0 / (4.0 * kLightPi);
-    int i, j;
-    environment_texel(env->width, env->height, u, v, i, j);
-    texel = j * env->width + i;
-    const double pj = env_mcdf<STAGED>(env, lds, (uint32_t)j) - (j ? env_mcdf<STAGED>(env, lds, (uint32_t)j - 1u) : 0.0);
-    const double *row = env->ccdf + (size_t)j * (size_t)env->width;
-    const double pi = row[i] - (i ? row[i - 1] : 0.0);
-    return ((pj * pi) * ((double)env->width * (double)env->height)) / (((2.0 * kLightPi) * kLightPi) * sqrt(1.0 - e.y * e.y));
-}
-}  // namespace
-
 template <int STRICT, class T>
 __global__ __launch_bounds__(256) void env_sample_kernel(DeviceScene sc, LightArgs a)
 {
@@ -5727,14 +5882,7 @@ __global__ __launch_bounds__(256) void env_sample_kernel(DeviceScene sc, LightAr
     __shared__ uint32_t wave_valid[4];
     global_tables_only(sc);
     const RT_CONST EnvRec *env = environment_of(sc.camera);
-    const bool tables = env->has_distribution != 0;
-    const uint32_t width = (uint32_t)env->width, height = (uint32_t)env->height;
-    if (tables) {
-        const double *src = env->mcdf;
-        const uint32_t n = min(height, kEnvLdsRows);
-        for (uint32_t i = threadIdx.x; i < n; i += 256u) mcdf_lds[i] = src[i];
-    }
-    __syncthreads();
+    stage_environment(env, mcdf_lds);
     const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
     bool valid = false;
     if (k < a.count) {
@@ -5744,53 +5892,10 @@ __global__ __launch_bounds__(256) void env_sample_kernel(DeviceScene sc, LightAr
         const double xb = (double)xorwow_uniform(rng);
         const double xc = (double)xorwow_uniform(rng);
         const double xd = (double)xorwow_uniform(rng);
-        Vec e;
-        int32_t texel = -1;
-        if (tables) {
-            uint32_t lo = 0, hi = height - 1u;
-            while (lo < hi) {  // the first row with mcdf >= xa (the last entry is 1.0 >= xa)
-                const uint32_t mid = (lo + hi) / 2u;
-                if (env_mcdf<true>(env, mcdf_lds, mid) >= xa) hi = mid;
-                else lo = mid + 1u;
-            }
-            const uint32_t j = lo;
-            const double *row = env->ccdf + (size_t)j * width;
-            lo = 0;
-            hi = width - 1u;
-            while (lo < hi) {
-                const uint32_t mid = (lo + hi) / 2u;
-                if (row[mid] >= xb) hi = mid;
-                else lo = mid + 1u;
-            }
-            const uint32_t i = lo;
-            texel = (int32_t)(j * width + i);
-            const double u = ((double)i + xc) / (double)width;
-            const double v = 1.0 - ((double)j + xd) / (double)height;
-            const double theta = kLightPi * v, phi = (2.0 * kLightPi) * u - kLightPi;
-            const double st = sin(theta);
-            e = mk(st * cos(phi), -cos(theta), -(st * sin(phi)));
-        } else {  // no tables: the sphere uniformly
-            const double y = 1.0 - 2.0 * xc;
-            const double st = sqrt(1.0 - y * y), phi = (2.0 * kLightPi) * xd - kLightPi;
-            e = mk(st * cos(phi), y, -(st * sin(phi)));
-        }
-        // R^T e, each row (a + b) + c
-        Vec dir = mk((env->rot[0] * e.x + env->rot[3] * e.y) + env->rot[6] * e.z, (env->rot[1] * e.x + env->rot[4] * e.y) + env->rot[7] * e.z,
-                     (env->rot[2] * e.x + env->rot[5] * e.y) + env->rot[8] * e.z);
-        // density and value from the direction itself, through the environment's own lookup
-        Vec el;
-        double u, v;
-        environment_coords(env, dir, el, u, v);
-        int32_t seen;
-        double pdf = environment_density<true>(env, mcdf_lds, el, u, v, seen);
-        valid = usable_density(pdf);
-        Vec emitted = mk(0.0, 0.0, 0.0), contribution = mk(0.0, 0.0, 0.0);
-        double scatter = 0.0;
-        if (!valid) {
-            dir = mk(0.0, 0.0, 0.0);
-            pdf = 0.0;
-        }
-        if (valid && (a.emitted || a.contribution)) emitted = environment_lookup<T>(sc, env, el, u, v);
+        Vec dir, emitted, contribution = mk(0.0, 0.0, 0.0);
+        double pdf, scatter = 0.0;
+        int32_t texel;
+        valid = environment_sample<T>(sc, env, mcdf_lds, xa, xb, xc, xd, a.emitted || a.contribution, dir, pdf, emitted, texel);
         if (valid && (a.scatter_pdf || a.contribution)) {
             const uint32_t kind = a.material[k];
             scatter = scatter_density(kind, kind == MAT_LAMBERTIAN ? load3(a.normal + (size_t)k * 3) : mk(0.0, 0.0, 0.0), dir);  // (only it reads the normal)
@@ -5865,10 +5970,15 @@ hipError_t RT_CAT(launch_light_pdf_, RT_SUFFIX)(const DeviceScene &sc, const Lig
 //   one density a lane can need: along its incoming ray where it ended on a lamp with a density carried in, along its sample
 //   where it scattered.  A wave in which no lane needs one skips the loop.  The table is staged in LDS as the light kernels stage it.
 //   shadow_kernel: query_kernel's occlusion search (query_search) for the rows launch 1 left pending.
+// ENV (the launcher's choice for a scene with SCENE_ENVIRONMENT_LIGHT; every other scene runs the instantiations without it, whose
+// code holds none of this): the environment is a light too.  The sample site picks between it and the table (path_emitter_sample),
+// a miss with a density carried in is a second kind of weighted end, whose density is the lane's own, and only the lanes that
+// need the TABLE's density -- a lamp end, a table sample -- vote for the loop; the marginal table's first kEnvLdsRows entries are
+// staged beside the light rows (staged_environment: every lane, one barrier, none behind it).
 // No lane returns before a barrier, no workgroup waits for another.  Termination: as for advance_kernel, and as light_sample,
-// mixture_density and query_search say.
+// mixture_density and query_search say; the two bisections of an environment sample each halve hi - lo.
 // ------------------------------------------------------------------------------------------------
-template <int STRICT, class T>
+template <int STRICT, class T, bool ENV = false>
 __global__ __launch_bounds__(256) void advance_direct_kernel(DeviceScene sc, AdvanceDirectArgs d)
 {
     __shared__ __attribute__((aligned(16))) double rows_lds[kLightLdsRows * kLightRowDoubles];
@@ -5882,10 +5992,14 @@ __global__ __launch_bounds__(256) void advance_direct_kernel(DeviceScene sc, Adv
     la.n_lights = d.n_lights;
     stage_lights(la, rows_lds, cdf_lds);
     const LightLds lds{rows_lds, cdf_lds};
+    [[maybe_unused]] const double *mcdf_lds = staged_environment<ENV>(sc);
+    [[maybe_unused]] const RT_CONST EnvRec *env = environment_of(sc.camera);
     const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
     const uint32_t n = a.count_in ? min(*a.count_in, a.capacity) : a.capacity;
     const bool stepped = k < n && (!a.alive || a.alive[k] != 0);
     bool scattered = false, lamp = false, sampled = false;
+    [[maybe_unused]] bool sky = false, table = false;  // ENV: a miss weighted like a lamp end; the sample waits for the table's density
+    [[maybe_unused]] double own = 0.0;                 // ENV: the density of a sky end or of an environment sample, this lane's alone
     // what the density loop and the fold behind it read: the ray the density is asked along, the row's id, its light and weights
     Vec along_o = mk(0.0, 0.0, 0.0), along_d = mk(0.0, 0.0, 1.0), light = mk(0.0, 0.0, 0.0);
     double along_tm = 0.0, other = 0.0, distance = 0.0;
@@ -5923,10 +6037,15 @@ __global__ __launch_bounds__(256) void advance_direct_kernel(DeviceScene sc, Adv
         const double sent = d.scatter_pdf ? d.scatter_pdf[k] : 0.0;  // the density the bounce before sent this ray with
         if (!scattered) {
             lamp = hit && kind == MAT_DIFFUSE_LIGHT && sent > 0.0 && a.radiance && id >= 0 && (uint32_t)id < a.sources;
+            if constexpr (ENV) sky = !hit && sent > 0.0 && a.radiance && id >= 0 && (uint32_t)id < a.sources;
             if (lamp) {  // weighted behind the density loop, along the incoming ray as given
                 along_o = ray.o;
                 along_d = ray.d;
                 along_tm = ray.tm;
+                light = carried * accumulated;
+                other = sent;
+            } else if (sky) {  // weighted against the environment sample the bounce before could have taken: no loop
+                own = environment_end_density(env, mcdf_lds, ray.d);
                 light = carried * accumulated;
                 other = sent;
             } else if (a.radiance && id >= 0 && (uint32_t)id < a.sources) {  // w = 1: the plain advance's fold
@@ -5940,7 +6059,12 @@ __global__ __launch_bounds__(256) void advance_direct_kernel(DeviceScene sc, Adv
         } else {
             const Vec next = carried * throughput;
             double sent_next = 0.0;
-            if ((kind == MAT_LAMBERTIAN || kind == MAT_ISOTROPIC) && d.n_lights != 0 && d.sample != 0) {
+            if constexpr (ENV) {
+                if ((kind == MAT_LAMBERTIAN || kind == MAT_ISOTROPIC) && d.sample != 0) {
+                    sampled = path_emitter_sample<T>(sc, la, lds, env, mcdf_lds, ray, kind, normal, next, rng, along_o, along_d, along_tm, light, other,
+                                                     distance, sent_next, table, own);
+                }
+            } else if ((kind == MAT_LAMBERTIAN || kind == MAT_ISOTROPIC) && d.n_lights != 0 && d.sample != 0) {
                 sampled = path_light_sample<T>(sc, la, lds, ray, kind, normal, next, rng, along_o, along_d, along_tm, light, other, distance, sent_next);
             }
             if (a.stage.origin) store3(a.stage.origin, k, ray.o);
@@ -5959,7 +6083,14 @@ __global__ __launch_bounds__(256) void advance_direct_kernel(DeviceScene sc, Adv
     // every lane of the workgroup is here again.  The mixture density along `along`, every lane of the wave on the same row (a lane
     // that needs none runs the loop on a ray of its own that meets what it meets: its sum is not read)
     double density_sum = 0.0;
-    if (__ballot(lamp || sampled) != 0ull) density_sum = mixture_density(la, lds, along_o, along_d, along_tm);
+    if constexpr (ENV) {  // only the lanes that need the TABLE's density vote: a wave whose lanes all picked the sky skips the loop, and so does
+        // every wave where the table has no share (chance 1 beside lamps: c_l * sum is 0 without walking the table, a lamp end's w = q / q)
+        if (env->table_share != 0.0 && __ballot(lamp || table) != 0ull) density_sum = mixture_density(la, lds, along_o, along_d, along_tm);
+        density_sum = lamp || table ? env->table_share * density_sum : own;  // p of include/rtow.h, per emitter
+        lamp = lamp || sky;
+    } else {
+        if (__ballot(lamp || sampled) != 0ull) density_sum = mixture_density(la, lds, along_o, along_d, along_tm);
+    }
     if (lamp) {  // w = q / (q + p): the scattered ray found the lamp a light sample of the bounce before could have found
         const double w = other / (other + density_sum);
         double *row = a.radiance + (size_t)id * 3;
@@ -6034,6 +6165,8 @@ hipError_t RT_CAT(launch_advance_direct_, RT_SUFFIX)(const DeviceScene &sc, cons
     if (!info && a.n_lights != 0 && (!a.rows || !a.cdf)) return hipErrorInvalidValue;
     void (*kernel)(DeviceScene, AdvanceDirectArgs) =
         sc.world_kind == WORLD_BVH ? advance_direct_kernel<RT_STRICT, TBvhNested> : advance_direct_kernel<RT_STRICT, TListNested>;
+    if (sc.flags & SCENE_ENVIRONMENT_LIGHT)  // the instantiations that sample the environment too; every other scene launches what it did
+        kernel = sc.world_kind == WORLD_BVH ? advance_direct_kernel<RT_STRICT, TBvhNested, true> : advance_direct_kernel<RT_STRICT, TListNested, true>;
     return info_or_launch(kernel, sc, a, v.capacity, stream, info);
 }
 
@@ -6065,10 +6198,12 @@ hipError_t RT_CAT(launch_advance_shadow_, RT_SUFFIX)(const DeviceScene &sc, cons
 //   after a shadow search: the parked light is added where nothing was found, and the lane is back on its path ray.
 // A path ends only where no sample is pending (an ended path draws none, the last bounce takes none): it folds into the sum and the
 // next sample starts in the same iteration.  Every lane, k >= count included, reaches the barriers of stage_lights; there is none
-// behind them.  Termination: at most samples * max_depth path searches and as many shadow searches, each bounded (the argument
-// on the two searches), each followed by bounded helpers.
+// behind them.  ENV: as advance_direct_kernel says -- the pick at the sample site, the weighted miss, the ballot of the lanes that
+// need the table's density, the marginal table staged behind the light rows' barrier by every lane.  Termination: at most
+// samples * max_depth path searches and as many shadow searches, each bounded (the argument on the two searches), each followed by
+// bounded helpers; the two bisections of an environment sample each halve hi - lo.
 // ------------------------------------------------------------------------------------------------
-template <int STRICT, class T>
+template <int STRICT, class T, bool ENV = false>
 __global__ __launch_bounds__(256) void radiance_direct_kernel(DeviceScene sc, RadianceDirectArgs d)
 {
     __shared__ __attribute__((aligned(16))) double rows_lds[kLightLdsRows * kLightRowDoubles];
@@ -6081,6 +6216,8 @@ __global__ __launch_bounds__(256) void radiance_direct_kernel(DeviceScene sc, Ra
     la.n_lights = d.n_lights;
     stage_lights(la, rows_lds, cdf_lds);
     const LightLds lds{rows_lds, cdf_lds};
+    [[maybe_unused]] const double *mcdf_lds = staged_environment<ENV>(sc);
+    [[maybe_unused]] const RT_CONST EnvRec *env = environment_of(sc.camera);
     const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
     uint32_t rays = 0, cast = 0, reached = 0;  // path searches, shadow searches, shadow rays that met nothing: this lane's, all samples
     if (k < a.count) {
@@ -6110,6 +6247,8 @@ __global__ __launch_bounds__(256) void radiance_direct_kernel(DeviceScene sc, Ra
                 uint32_t leaf = kNone;
                 const bool hit = query_search<T>(sc, d.node_leaf_pos, searched, 0.001, tmax, stop_at_first, h, leaf, rng);
                 bool lamp = false, sampled = false, path_ends = false;
+                [[maybe_unused]] bool sky = false, table = false;  // ENV: a miss weighted like a lamp end; the sample waits for the table's density
+                [[maybe_unused]] double own = 0.0;                 // ENV: the density of a sky end or of an environment sample, this lane's alone
                 // what the density loop and the fold behind it read: the ray the density is asked along, its light and weights
                 Vec along_o = mk(0.0, 0.0, 0.0), along_d = mk(0.0, 0.0, 1.0), light = mk(0.0, 0.0, 0.0);
                 double along_tm = 0.0, other = 0.0, distance = 0.0;
@@ -6130,10 +6269,15 @@ __global__ __launch_bounds__(256) void radiance_direct_kernel(DeviceScene sc, Ra
                     if (!scattered) {
                         path_ends = true;
                         lamp = hit && kind == MAT_DIFFUSE_LIGHT && sent > 0.0;
+                        if constexpr (ENV) sky = !hit && sent > 0.0;
                         if (lamp) {  // weighted behind the density loop, along the incoming ray as given
                             along_o = ray.o;
                             along_d = ray.d;
                             along_tm = ray.tm;
+                            light = carried * accumulated;
+                            other = sent;
+                        } else if (sky) {  // weighted against the environment sample the bounce before could have taken: no loop
+                            own = environment_end_density(env, mcdf_lds, ray.d);
                             light = carried * accumulated;
                             other = sent;
                         } else {  // w = 1
@@ -6143,7 +6287,12 @@ __global__ __launch_bounds__(256) void radiance_direct_kernel(DeviceScene sc, Ra
                         const Vec next = carried * throughput;
                         double sent_next = 0.0;
                         const bool sample_here = depth + 1 < a.max_depth;  // the last bounce takes none: its light sample would stand for bounce max_depth
-                        if ((kind == MAT_LAMBERTIAN || kind == MAT_ISOTROPIC) && d.n_lights != 0 && sample_here) {
+                        if constexpr (ENV) {
+                            if ((kind == MAT_LAMBERTIAN || kind == MAT_ISOTROPIC) && sample_here) {
+                                sampled = path_emitter_sample<T>(sc, la, lds, env, mcdf_lds, ray, kind, normal, next, rng, along_o, along_d, along_tm, light, other,
+                                                                 distance, sent_next, table, own);
+                            }
+                        } else if ((kind == MAT_LAMBERTIAN || kind == MAT_ISOTROPIC) && d.n_lights != 0 && sample_here) {
                             sampled = path_light_sample<T>(sc, la, lds, ray, kind, normal, next, rng, along_o, along_d, along_tm, light, other, distance, sent_next);
                         }
                         carried = next;
@@ -6154,7 +6303,14 @@ __global__ __launch_bounds__(256) void radiance_direct_kernel(DeviceScene sc, Ra
                 // every lane still in the loop is here again.  The mixture density along `along`, every such lane of the wave on the same
                 // row (a lane that needs none runs the loop on a ray of its own that meets what it meets: its sum is not read)
                 double density_sum = 0.0;
-                if (__ballot(lamp || sampled) != 0ull) density_sum = mixture_density(la, lds, along_o, along_d, along_tm);
+                if constexpr (ENV) {  // only the lanes that need the TABLE's density vote: a wave whose lanes all picked the sky skips the loop, and so does
+                    // every wave where the table has no share (chance 1 beside lamps: c_l * sum is 0 without walking the table, a lamp end's w = q / q)
+                    if (env->table_share != 0.0 && __ballot(lamp || table) != 0ull) density_sum = mixture_density(la, lds, along_o, along_d, along_tm);
+                    density_sum = lamp || table ? env->table_share * density_sum : own;  // p of include/rtow.h, per emitter
+                    lamp = lamp || sky;
+                } else {
+                    if (__ballot(lamp || sampled) != 0ull) density_sum = mixture_density(la, lds, along_o, along_d, along_tm);
+                }
                 if (lamp) {  // w = q / (q + p): the scattered ray found the lamp a light sample of the bounce before could have found
                     const double w = other / (other + density_sum);
                     acc = acc + w * light;
@@ -6210,6 +6366,8 @@ hipError_t RT_CAT(launch_radiance_direct_, RT_SUFFIX)(const DeviceScene &sc, con
     if (!info && a.ray_counter && !d.shadow_counters) return hipErrorInvalidValue;
     void (*kernel)(DeviceScene, RadianceDirectArgs) =
         sc.world_kind == WORLD_BVH ? radiance_direct_kernel<RT_STRICT, TBvhNested> : radiance_direct_kernel<RT_STRICT, TListNested>;
+    if (sc.flags & SCENE_ENVIRONMENT_LIGHT)  // the instantiations that sample the environment too; every other scene launches what it did
+        kernel = sc.world_kind == WORLD_BVH ? radiance_direct_kernel<RT_STRICT, TBvhNested, true> : radiance_direct_kernel<RT_STRICT, TListNested, true>;
     return info_or_launch(kernel, sc, d, a.count, stream, info);
 }
 #elif RT_FILM_DIRECT
@@ -6228,10 +6386,12 @@ hipError_t RT_CAT(launch_radiance_direct_, RT_SUFFIX)(const DeviceScene &sc, con
 // pixel's time with a handful of lanes each (measured: profiles/r25_film_direct.txt).  A pixel is taken up and laid down as render_kernel does it (stream
 // words, running sum, the planes of adaptive sampling), by one lane from its first sample to its last, from its own stream: the
 // frame cannot depend on which lane took which pixel.
+// ENV: as radiance_direct_kernel; the marginal table is staged once, before the persistent loop, like the light table.
 // Termination: the queue word only grows, and a wave that has seen it pass the queue's length never takes again; a pixel is at
-// most spp samples of at most max_depth path searches and as many shadow searches, each bounded as in radiance_direct_kernel.
+// most spp samples of at most max_depth path searches and as many shadow searches, each bounded as in radiance_direct_kernel
+// (the two bisections of an environment sample each halve hi - lo).
 // ------------------------------------------------------------------------------------------------
-template <int STRICT, class T>
+template <int STRICT, class T, bool ENV = false>
 __global__ __launch_bounds__(256) void film_direct_kernel(DeviceScene sc, FilmDirectArgs d)
 {
     __shared__ __attribute__((aligned(16))) double rows_lds[kLightLdsRows * kLightRowDoubles];
@@ -6243,6 +6403,8 @@ __global__ __launch_bounds__(256) void film_direct_kernel(DeviceScene sc, FilmDi
     la.n_lights = d.n_lights;
     stage_lights(la, rows_lds, cdf_lds);
     const LightLds lds{rows_lds, cdf_lds};
+    [[maybe_unused]] const double *mcdf_lds = staged_environment<ENV>(sc);
+    [[maybe_unused]] const RT_CONST EnvRec *env = environment_of(sc.camera);
     const CameraRec *__restrict__ cam = sc.camera;
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t tiles_x = ((uint32_t)d.width + 7u) >> 3;
@@ -6321,6 +6483,8 @@ __global__ __launch_bounds__(256) void film_direct_kernel(DeviceScene sc, FilmDi
             continue;        // (the last pixels: lanes of this wave still hold theirs; it takes again when they are done)
         }
         bool lamp = false, sampled = false, path_ends = false;
+        [[maybe_unused]] bool sky = false, table = false;  // ENV: a miss weighted like a lamp end; the sample waits for the table's density
+        [[maybe_unused]] double own = 0.0;                 // ENV: the density of a sky end or of an environment sample, this lane's alone
         // what the density loop and the fold behind it read: the ray the density is asked along, its light and weights
         Vec along_o = mk(0.0, 0.0, 0.0), along_d = mk(0.0, 0.0, 1.0), light = mk(0.0, 0.0, 0.0);
         double along_tm = 0.0, other = 0.0, distance = 0.0;
@@ -6356,10 +6520,15 @@ __global__ __launch_bounds__(256) void film_direct_kernel(DeviceScene sc, FilmDi
                 if (!scattered) {
                     path_ends = true;
                     lamp = hit && kind == MAT_DIFFUSE_LIGHT && sent > 0.0;
+                    if constexpr (ENV) sky = !hit && sent > 0.0;
                     if (lamp) {  // weighted behind the density loop, along the incoming ray as given
                         along_o = ray.o;
                         along_d = ray.d;
                         along_tm = ray.tm;
+                        light = carried * accumulated;
+                        other = sent;
+                    } else if (sky) {  // weighted against the environment sample the bounce before could have taken: no loop
+                        own = environment_end_density(env, mcdf_lds, ray.d);
                         light = carried * accumulated;
                         other = sent;
                     } else {  // w = 1
@@ -6369,7 +6538,12 @@ __global__ __launch_bounds__(256) void film_direct_kernel(DeviceScene sc, FilmDi
                     const Vec next = carried * throughput;
                     double sent_next = 0.0;
                     const bool sample_here = depth + 1 < d.max_depth;  // the last bounce takes none: its light sample would stand for bounce max_depth
-                    if ((kind == MAT_LAMBERTIAN || kind == MAT_ISOTROPIC) && d.n_lights != 0 && sample_here) {
+                    if constexpr (ENV) {
+                        if ((kind == MAT_LAMBERTIAN || kind == MAT_ISOTROPIC) && sample_here) {
+                            sampled = path_emitter_sample<T>(sc, la, lds, env, mcdf_lds, ray, kind, normal, next, rng, along_o, along_d, along_tm, light, other,
+                                                             distance, sent_next, table, own);
+                        }
+                    } else if ((kind == MAT_LAMBERTIAN || kind == MAT_ISOTROPIC) && d.n_lights != 0 && sample_here) {
                         sampled = path_light_sample<T>(sc, la, lds, ray, kind, normal, next, rng, along_o, along_d, along_tm, light, other, distance, sent_next);
                     }
                     carried = next;
@@ -6381,7 +6555,14 @@ __global__ __launch_bounds__(256) void film_direct_kernel(DeviceScene sc, FilmDi
         // every lane that holds a pixel is here again.  The mixture density along `along`, every such lane of the wave on the same
         // row (a lane that needs none runs the loop on a ray of its own that meets what it meets: its sum is not read)
         double density_sum = 0.0;
-        if (__ballot(lamp || sampled) != 0ull) density_sum = mixture_density(la, lds, along_o, along_d, along_tm);
+        if constexpr (ENV) {  // only the lanes that need the TABLE's density vote: a wave whose lanes all picked the sky skips the loop, and so does
+            // every wave where the table has no share (chance 1 beside lamps: c_l * sum is 0 without walking the table, a lamp end's w = q / q)
+            if (env->table_share != 0.0 && __ballot(lamp || table) != 0ull) density_sum = mixture_density(la, lds, along_o, along_d, along_tm);
+            density_sum = lamp || table ? env->table_share * density_sum : own;  // p of include/rtow.h, per emitter
+            lamp = lamp || sky;
+        } else {
+            if (__ballot(lamp || sampled) != 0ull) density_sum = mixture_density(la, lds, along_o, along_d, along_tm);
+        }
         if (lamp) {  // w = q / (q + p): the scattered ray found the lamp a light sample of the bounce before could have found
             const double w = other / (other + density_sum);
             acc = acc + w * light;
@@ -6463,6 +6644,8 @@ hipError_t RT_CAT(launch_film_direct_, RT_SUFFIX)(const DeviceScene &sc, const F
     }
     const bool bvh = sc.world_kind == WORLD_BVH;
     void (*kernel)(DeviceScene, FilmDirectArgs) = bvh ? film_direct_kernel<RT_STRICT, TBvhNested> : film_direct_kernel<RT_STRICT, TListNested>;
+    if (sc.flags & SCENE_ENVIRONMENT_LIGHT)  // the instantiations that sample the environment too; every other scene launches what it did
+        kernel = bvh ? film_direct_kernel<RT_STRICT, TBvhNested, true> : film_direct_kernel<RT_STRICT, TListNested, true>;
     if (info) {
         hipFuncAttributes attr;
         if (hipError_t e = hipFuncGetAttributes(&attr, reinterpret_cast<const void *>(kernel)); e != hipSuccess) return e;

@@ -1633,6 +1633,14 @@ static void build_environment(const SceneImpl &s, FlatScene &f)
     const HostEnvironment &h = s.environment;
     f.flags |= SCENE_ENVIRONMENT;
     EnvRec &r = f.env;
+    // the environment as a light of the direct estimators: the shares of a light sample, fixed here (f.lights is complete)
+    r.light_share = 0.0;
+    r.table_share = 1.0;
+    if (s.environment_light > 0.0) {
+        f.flags |= SCENE_ENVIRONMENT_LIGHT;
+        r.light_share = f.lights.empty() ? 1.0 : s.environment_light;
+        r.table_share = f.lights.empty() ? 0.0 : 1.0 - s.environment_light;
+    }
     std::memcpy(r.intensity, h.intensity, sizeof r.intensity);
     std::memcpy(r.rot, h.rotation, sizeof r.rot);
     r.texture = h.texture ? h.texture - 1 : kNone;
@@ -2984,6 +2992,28 @@ int rt_scene_set_environment(rt_scene *s, const rt_environment *env)
     sc.environment = std::move(h);
     sc.has_environment = true;
     sc.committed = false;
+    return RT_OK;
+}
+
+static_assert(RT_SCENE_FLAG_ENVIRONMENT_LIGHT == SCENE_ENVIRONMENT_LIGHT, "the bit the header names");
+int rt_scene_set_environment_light(rt_scene *s, double chance)
+{
+    if (!s) return fail(RT_ERR_INVALID, "rt_scene_set_environment_light: null scene");
+    SceneImpl &sc = *S(s);
+    if (sc.launches_in_flight > 0)
+        return fail(RT_ERR_STATE, "rt_scene_set_environment_light: a render of this scene is in flight (rt_render_finish it first)");
+    if (!(chance >= 0.0 && chance <= 1.0)) return fail(RT_ERR_INVALID, "rt_scene_set_environment_light: chance must lie in [0, 1]");
+    sc.environment_light = chance;
+    sc.committed = false;
+    return RT_OK;
+}
+
+int rt_scene_get_environment_light(rt_scene *s, double *chance_out, double *effective_out)
+{
+    if (!s) return fail(RT_ERR_INVALID, "rt_scene_get_environment_light: null scene");
+    const SceneImpl &sc = *S(s);
+    if (chance_out) *chance_out = sc.environment_light;
+    if (effective_out) *effective_out = sc.committed && (sc.flat.flags & SCENE_ENVIRONMENT_LIGHT) ? sc.flat.env.light_share : 0.0;
     return RT_OK;
 }
 

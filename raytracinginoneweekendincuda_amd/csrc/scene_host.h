@@ -164,6 +164,7 @@ struct SceneImpl {
     CameraRec camera{};
     bool has_environment = false;
     HostEnvironment environment;
+    double environment_light = 0.0;  // rt_scene_set_environment_light's chance, read by the next rt_scene_commit; it outlives a change of environment
     bool committed = false;
     FlatScene flat;
     std::vector<DeviceTables *> device;  // one per device ordinal, lazily
