@@ -1206,6 +1206,9 @@ static void print_phases(const FilmImpl &f)
             std::fprintf(stderr, "window: %llu windowed passes (%llu windowed runs), %.2f trips scanned per pass in them, %.2f ranges per pass, %.0f cycles "
                          "of window computation per pass\n", c[96 + 7] * 16ull, c[96 + 14] * 16ull, (double)c[64 + 14] / c[96 + 7], (double)c[64 + 7] / c[96 + 7],
                          (double)c[32 + 14] / c[96 + 7]);
+        if (c[96 + 7])  // the cycle word of slot 7: what the lanes' OWN extents need of those runs (a work-item form's trips)
+            std::fprintf(stderr, "window: %.1f lane-trips per windowed pass by each lane's own extent (sum over the live lanes), %.2f a live lane\n",
+                         (double)c[32 + 7] / c[96 + 7], c[64 + 19] ? (double)c[32 + 7] / c[96 + 7] / ((double)c[64 + 19] / c[96 + 19]) : 0.0);
         name[16] = name[17] = name[18] = "";  // slots 16, 17, 18: the counts of the grouped scan (render.hip GroupedSums)
         const double gp = (double)c[96 + 16];
         if (gp > 0) {
@@ -1216,6 +1219,9 @@ static void print_phases(const FilmImpl &f)
             std::fprintf(stderr, "grouped: cycles per pass: filter %.0f, exact tests %.0f (%.1f %% and %.1f %% of the cooperative scans' %.0f)\n",
                          (double)c[64 + 18] / gp, (double)c[32 + 18] / gp, 100.0 * c[64 + 18] / c[32 + 1], 100.0 * c[32 + 18] / c[32 + 1],
                          (double)c[32 + 1] / (double)c[96 + 1]);
+            // the packed fp32 branch queues its survivors: there "blocks" above are drain iterations and "survivors" appends
+            std::fprintf(stderr, "grouped: appends per pass %.2f, drains per pass %.2f, drain iterations per pass %.2f\n", (double)c[32 + 17] / gp,
+                         (double)c[96 + 17] / gp, (double)c[32 + 16] / gp);
         }
     }
     const double total = (double)c[7];

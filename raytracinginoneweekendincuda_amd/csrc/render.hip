@@ -535,6 +535,7 @@ struct ScanSums {
     uint32_t groups, taken, spheres, appends, behind;  // groups of 4 examined / taken; spheres with a passing lane; lane appends; lanes behind
     uint32_t drains, drain_iters, drain_cycles;        // drain calls; wave max of count per call, summed; cycles spent draining
     uint32_t win_runs, win_trips, win_ranges, win_cycles;  // windowed runs scanned; trips and ranges of trips run in them; cycles of forming the windows
+    uint32_t win_lane_trips;  // trips of those runs that each live lane's OWN extent needs, summed over the lanes (what a work-item form would run)
 };
 #define SS_ARG , ScanSums &ss
 #define SS_PASS , ss
@@ -543,6 +544,8 @@ struct ScanSums {
 struct GroupedSums {
     uint32_t rays, tests, survivors, lane_max;  // L; exact-test blocks the wave executed; lanes that went on to the exact test; largest count of one lane
     uint32_t drains, filter_cycles, test_cycles;  // drain calls; cycles in the filter's part and in the exact tests' part of the pass
+    // The packed fp32 branch queues its survivors (r36): there `tests` counts drain iterations (the wave's largest queue per drain,
+    // summed), `survivors` appends, `test_cycles` the drains' cycles and `filter_cycles` the rest of the loop.
 };
 #define GS_ARG , GroupedSums &gs
 #define GS_PASS , gs
@@ -2247,6 +2250,9 @@ DEV bool scan_filtered32(const DeviceScene &sc, bool live, uint32_t planes_off, 
                             e0 = (float)ex.lo;
                             e1 = -(float)ex.hi;
                         }
+#if RT_PHASES
+                        const float own0 = e0, own1 = -e1;  // this lane's own extent (no ray: empty)
+#endif
                         wave_fmin2(e0, e1);
                         x0 = e0;
                         x1 = -e1;
@@ -2255,6 +2261,10 @@ DEV bool scan_filtered32(const DeviceScene &sc, bool live, uint32_t planes_off, 
                         asm volatile("" ::"s"(x0), "s"(x1));
                         ss.win_cycles += (uint32_t)(__builtin_readcyclecounter() - ss_w0);
                         ss.win_runs++;
+                        for (uint32_t t = 0; t < sg.n_trips; t++) {  // outside the cycle count: what each lane's own extent needs of the run
+                            const ScanTripSpan own = load_scan_span(sc, sg.first_trip + t);
+                            ss.win_lane_trips += (uint32_t)__popcll(__ballot(live && scan_window_needs(own.lo, own.hi, own0, own1)));
+                        }
 #endif
                     }
                 }
@@ -2579,7 +2589,18 @@ DEV void min_with_lane(double &t, uint32_t &k, int partner)
 // lanes (m = L rounded up to a power of two), lane s of a group tests spheres s, s+g, s+2g, ...; one reduction over
 // (t, index) per group serves all the rays at once.  Same winner as scan_cooperative (and as the sequential scan),
 // at 1/L of its per-ray bookkeeping; against the pixel-parallel scan every lane does 1/g of the sphere tests.
-DEV void scan_grouped(const SphereView &sv, uint32_t lane, unsigned long long todo, const Ray &ray, double tmin, double tmax,
+//
+// The packed fp32 branch queues its survivors (r36): a sphere that passes a lane's filter and is not behind goes to that lane's
+// column of the survivor queue (idle in a grouped pass), as in filter_pairs / append_survivor, and the lanes run the reference's
+// test on their own entries in ascending order against their running hit behind the last iteration -- drain_filtered itself: its
+// signature fits, and it reads the rows from the fp64 planes as the tests in place did.  A lane meets its survivors in the order
+// and with the running hit it met them in place, so its (t, index) is the same bit for bit, and the wave runs the test
+// max-over-lanes-of-count times instead of once per slot that some lane passed (C2: 1.18 iterations a pass against 3.66 blocks).
+// Queue bound, as above scan_filtered32: `count` changes only in append_survivor; at the head of an iteration every lane holds
+// at most kQueueCap - 4 entries (true at the start, kept by an iteration that appends nothing, restored by the drain test behind
+// every iteration in which some lane passed a sphere); an iteration appends at most its 4 spheres, so a lane writes its slot
+// `count` only while count < kQueueCap.
+DEV void scan_grouped(const SphereView &sv, uint16_t *queue, uint32_t lane, unsigned long long todo, const Ray &ray, double tmin, double tmax,
                       HitInfo &best, bool &hit GS_ARG)
 {
     const int L = __popcll(todo);
@@ -2613,20 +2634,23 @@ DEV void scan_grouped(const SphereView &sv, uint32_t lane, unsigned long long to
         const ScanRayPairs f = scan_ray_pairs(scan_ray32(r, a, sv.reach32));
         const uint32_t n_pairs = sv.n_padded / 2u;
         const v4f *rows = reinterpret_cast<const v4f *>(lds_raw + sv.pairs_off);
+        uint32_t count = 0;
 #if RT_PHASES
+        ScanSums ss{};
         uint32_t gs_mine = 0;
         gs.rays = (uint32_t)L;
+        const unsigned long long gs_t0 = __builtin_readcyclecounter();
 #endif
         for (uint32_t base = 0; base < n_pairs; base += 2u * g) {
             v2f fs[2], fq[2], fk[2];
-#if RT_PHASES
-            const unsigned long long gs_t0 = __builtin_readcyclecounter();
-#endif
+            uint32_t jj[2];
+            bool on[2];  // this lane has a pair in this half of the iteration
 #pragma unroll
             for (int h = 0; h < 2; h++) {
-                uint32_t j = base + g * h + s;
-                j = j < n_pairs ? j : n_pairs - 1u;  // keeps the address inside the rows
-                const v4f lo = rows[j], hi = rows[n_pairs + j];
+                const uint32_t j = base + g * h + s;
+                on[h] = j < n_pairs;
+                jj[h] = on[h] ? j : n_pairs - 1u;  // keeps the address inside the rows
+                const v4f lo = rows[jj[h]], hi = rows[n_pairs + jj[h]];
                 const v2f cx = {lo.x, lo.y}, cy = {lo.z, lo.w}, cz = {hi.x, hi.y};
                 fk[h] = v2f{hi.z, hi.w};
                 fs[h] = __builtin_elementwise_fma(cz, f.uz, __builtin_elementwise_fma(cy, f.uy, cx * f.ux));
@@ -2634,40 +2658,35 @@ DEV void scan_grouped(const SphereView &sv, uint32_t lane, unsigned long long to
             }
             const float sv4[4] = {fs[0].x, fs[0].y, fs[1].x, fs[1].y}, qv4[4] = {fq[0].x, fq[0].y, fq[1].x, fq[1].y};
             const float kv4[4] = {fk[0].x, fk[0].y, fk[1].x, fk[1].y};
-#if RT_PHASES
-            const unsigned long long gs_t1 = __builtin_readcyclecounter();
+            // A row behind the list's last sphere never passes, so no test of its index is needed: its k is +inf, in the table's own
+            // padding (scene_builder.cpp, where sphere_scan32 is filled: "padding: never passes"; flat_scene.h SphereScanPair) and in
+            // the rows the kernel stages behind the table (render_kernel: "never passes").
+            const bool p[4] = {on[0] && qv4[0] > kv4[0], on[0] && qv4[1] > kv4[1], on[1] && qv4[2] > kv4[2], on[1] && qv4[3] > kv4[3]};
+            const unsigned long long m[4] = {__ballot(p[0]), __ballot(p[1]), __ballot(p[2]), __ballot(p[3])};  // the compares' own lane masks
+            if (__builtin_expect((m[0] | m[1] | m[2] | m[3]) != 0, 0)) {
 #pragma unroll
-            for (int u = 0; u < 4; u++) {  // a block executes for a slot some lane passed; a lane behind leaves it before the test proper
-                const bool tested = 2u * (base + g * (uint32_t)(u >> 1) + s) + (uint32_t)(u & 1) < sv.n && qv4[u] > kv4[u];
-                const unsigned long long m = __ballot(tested);
-                gs.tests += m ? 1u : 0u;
-                gs.survivors += (uint32_t)__popcll(m);
-                gs_mine += tested ? 1u : 0u;
-            }
-            const unsigned long long gs_t2 = __builtin_readcyclecounter();
-            gs.filter_cycles += (uint32_t)(gs_t1 - gs_t0);
-#endif
-#pragma unroll
-            for (int u = 0; u < 4; u++) {
-                const uint32_t k = 2u * (base + g * (uint32_t)(u >> 1) + s) + (uint32_t)(u & 1);
-                if (k < sv.n && qv4[u] > kv4[u]) {
+                for (int u = 0; u < 4; u++) {
+                    if (!m[u]) continue;  // wave-uniform: no lane passed this slot
                     const float bu = f.od - sv4[u];
                     const bool behind = bu > f.root_m && __builtin_fmaf(bu, bu, kv4[u] - qv4[u]) > 0.0f;  // k = -inf (always passes): never behind
-                    double t;
-                    if (!behind && sphere_test(r.o - mk(sv.plane(0, k), sv.plane(1, k), sv.plane(2, k)), r.d, a, sv.plane(3, k), tmin, bt, t)) {
-                        bt = t;
-                        bk = k;
-                    }
-                }
-            }
 #if RT_PHASES
-            asm volatile("" ::"v"(bt), "v"(bk));
-            gs.test_cycles += (uint32_t)(__builtin_readcyclecounter() - gs_t2);
+                    gs.survivors += (uint32_t)__popcll(__ballot(p[u] && !behind));
+                    gs_mine += p[u] && !behind ? 1u : 0u;
 #endif
+                    append_survivor(queue, lane, count, 2u * jj[u >> 1] + (uint32_t)(u & 1), p[u] && !behind);
+                }
+                if (__any(count > (uint32_t)(kQueueCap - 4))) drain_filtered<true>(sv.global, sv.planes_off, sv.n_padded, queue, lane, count, r, a, tmin, bt, bk SS_PASS);
+            }
         }
+        drain_filtered<true>(sv.global, sv.planes_off, sv.n_padded, queue, lane, count, r, a, tmin, bt, bk SS_PASS);
 #if RT_PHASES
+        asm volatile("" ::"v"(bt), "v"(bk));
         for (int off = 32; off > 0; off >>= 1) gs_mine = max(gs_mine, (uint32_t)__shfl_xor((int)gs_mine, off, 64));
         gs.lane_max = gs_mine;
+        gs.drains = ss.drains;
+        gs.tests = ss.drain_iters;
+        gs.test_cycles = ss.drain_cycles;
+        gs.filter_cycles = (uint32_t)(__builtin_readcyclecounter() - gs_t0) - ss.drain_cycles;
 #endif
     } else if (!sv.exact) {
         const ScanRay f = scan_ray(r, a, sv.reach);
@@ -3991,7 +4010,7 @@ __global__ __launch_bounds__(T::BLOCK, T::MIN_WAVES) void render_kernel(DeviceSc
                     ph.n[13] += rl(ss.appends); ph.l[13] += rl(ss.behind);       ph.t[13] += rl(ss.drain_cycles);
                     ph.n[15] += rl(ss.drains);  ph.l[15] += rl(ss.drain_iters);
                     ph.n[14] += rl(ss.win_runs); ph.l[14] += rl(ss.win_trips);   ph.t[14] += rl(ss.win_cycles);
-                    ph.n[7] += rl(ss.win_runs) ? 1ull : 0ull; ph.l[7] += rl(ss.win_ranges);
+                    ph.n[7] += rl(ss.win_runs) ? 1ull : 0ull; ph.l[7] += rl(ss.win_ranges); ph.t[7] += rl(ss.win_lane_trips);
                     }
                 }
 #endif
@@ -4000,7 +4019,7 @@ __global__ __launch_bounds__(T::BLOCK, T::MIN_WAVES) void render_kernel(DeviceSc
 #if RT_PHASES
                 GroupedSums gs{};
 #endif
-                if (sv.in_lds && !a.coop_single) scan_grouped(sv, lane, todo, ray, 0.001, DBL_MAX, h, hit GS_PASS);
+                if (sv.in_lds && !a.coop_single) scan_grouped(sv, queue, lane, todo, ray, 0.001, DBL_MAX, h, hit GS_PASS);
                 else scan_cooperative(sv, lane, todo, ray, 0.001, DBL_MAX, h, hit);
                 PH_END(1, (todo >> lane) & 1ull);
 #if RT_PHASES
